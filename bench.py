@@ -6,8 +6,17 @@ Horizon (24 000) scans = 52 800 points, local map of 200 000 points; one STEP = 
 down-sampling + one 5-NN association pass + 10 trust-region (GN / dogleg) iterations for a batch of scans whose raw
 points are already resident in HBM.  value = whole-job scans/s.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|2|3|4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|2|3|4] [--full] [--dump-outputs DIR]
 
+A plain run sets up, warms up, times the K steps, writes its outputs (--dump-outputs) and prints the JSON line: metric, value,
+ms_per_step (one timed step), config.  Everything else it can measure or check is behind --full (see "Added to the JSON line").
+
+  --dump-outputs DIR  after the timed steps: what the timed path computed in its last step, as DIR/<name>.npy (float32 /
+              float64, at most 64 MB in all; ranks r > 0 add _rank<r> to the name).  The inputs are seeded: the same
+              arguments give the same inputs on every run, so two builds can be compared output for output.
+              configs 1, 3, 4: poses (slots x 6: translation | rotation vector, what mml_step returned for every resident
+              slot), corner_features / surf_features (the down-sampled stacks of the first distinct slots, concatenated)
+              and feature_counts (corner, surf per dumped slot); config 2: poses (scans x 4 x 4) of the last replay pass
   --config 1  BASELINE configs[1] (default; the driver's line)
   --config 2  BASELINE configs[2]: replay, one scan at a time through the WHOLE odometry loop (upload, extract, undistort,
               down-sample, Estimate 5 outer x 10 inner, key-scan rule + map upkeep on the device) plus the joint solve of
@@ -22,7 +31,8 @@ max-over-ranks clock.  The path shards by scan with no data-path collective ("sc
 the path -- the joint window solve -- runs through the C-ABI's own RCCL calls (mml_window_solve_allgather) and is
 reported in "window_solve".
 
-Added to the JSON line:
+Added to the JSON line with --full (configs 1, 3, 4: replica check of the timed region's slots, value_by_slots,
+value_with_upload, window_solve, rccl; config 2: the B = 1 step latency, full_window_imu, the C++ adapter leg):
   roofline     -- dominant kernel: algorithmic bytes per launch / its mean launch time (HIP events on the library's own
                   stream around every launch of a single-stream pass) against 8 TB/s HBM
   cpu_baseline -- oracle/bench_cpu (the CPU restatement, pure C++, -O3 -ffp-contract=off; the reference binary cannot be
@@ -96,6 +106,10 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", type=int, default=1, choices=[1, 2, 3, 4], help="index into BASELINE.json configs")
+    ap.add_argument("--full", action="store_true", help="every section besides the headline: checks, roofline, CPU baseline, "
+                    "other batch sizes, uploads, window solve (the options below that tune a section act only with --full)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the timed path computed in its last step "
+                    "to DIR/<name>.npy")
     ap.add_argument("--slots", type=int, default=0, help="resident scan slots per GPU (0: the config's default)")
     ap.add_argument("--batch", type=int, default=0, help="scans per step per GPU (0: the config's default; rounded up to whole passes over the slots)")
     ap.add_argument("--map-points", type=int, default=0)
@@ -287,6 +301,42 @@ def pinned(a):
     return t.numpy().view(a.dtype).reshape(a.shape)
 
 
+# ---- --dump-outputs ---------------------------------------------------------------------------------------------------
+DUMP_BYTES = 64 << 20   # all arrays of one rank together
+
+
+def throughput_outputs(ctx, x, n_slots, max_slots=64):
+    """What the last timed step computed: the poses mml_step returned for every resident slot, and the down-sampled corner /
+    surf features of the first min(n_slots, max_slots) slots (the distinct scans), as many whole slots as fit DUMP_BYTES."""
+    out = {"poses": np.ascontiguousarray(x, np.float64)}
+    budget = DUMP_BYTES - out["poses"].nbytes
+    corner, surf, counts = [], [], []
+    for s in range(min(n_slots, max_slots)):
+        cf = np.ascontiguousarray(ctx.features_download(s, 0), np.float32).reshape(-1, 3)
+        sf = np.ascontiguousarray(ctx.features_download(s, 1), np.float32).reshape(-1, 3)
+        nbytes = cf.nbytes + sf.nbytes + 16
+        if nbytes > budget:
+            break
+        budget -= nbytes
+        corner.append(cf)
+        surf.append(sf)
+        counts.append((len(cf), len(sf)))
+    out["corner_features"] = np.concatenate(corner) if corner else np.zeros((0, 3), np.float32)
+    out["surf_features"] = np.concatenate(surf) if surf else np.zeros((0, 3), np.float32)
+    out["feature_counts"] = np.array(counts, np.float64).reshape(-1, 2)
+    return out
+
+
+def dump_outputs(path, rank, arrays):
+    """DIR/<name>.npy for every array (DIR/<name>_rank<r>.npy on rank r > 0)."""
+    arrays = {name: np.asarray(a) for name, a in arrays.items()}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BYTES
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ("_rank%d" % rank if rank else "") + ".npy"), a)
+
+
 # >>> cpu_baseline leg (the only code that may name the oracle)
 def write_cpu_workload(path, ctx, cfg, scans, dR, dt, x0, corner_map, surf_map, gn_iters, thres):
     import struct
@@ -419,6 +469,38 @@ def run_throughput(args, rank, local_rank, world, dist):
     barrier()
     elapsed = time.perf_counter() - t0
     errors = []
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, throughput_outputs(ctx, x, nd))
+
+    # pose sanity: the step must actually have registered the scans.  Only the slots on tile 0 count -- the original,
+    # un-jittered copy of the scene, where the generating pose IS the registration optimum up to the range noise; on the
+    # jittered copies of grow_map the optimum sits wherever the jitter put it -- and the number is asserted, not just printed.
+    on_tile0 = np.array([(s // nd) % len(tiles) == 0 for s in range(B)])
+    gt_err = float(np.abs(x[on_tile0, :3] - gt[on_tile0]).max())
+
+    def headline(elapsed):
+        return {
+            "metric": "scans/s (feature-extract+kNN+%d GN iters) on %s" % (gn_iters, "16-ring x1800 + Livox 24k fused cloud" if args.config == 1 else cfg["name"].split(": ")[1]),
+            "value": world * batch * args.steps / elapsed, "unit": "scans/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None, "dtype": "f32/f64", "data": "synthetic",
+            "config": {"workload": "%s, local map %d pts, 1 association pass (thres_dist 25), %d GN iterations, W=1"
+                                   % (cfg["name"], map_points, gn_iters),
+                       "scans_per_step_per_gpu": batch, "resident_slots": B, "passes_per_step": passes, "stream_lanes": n_lanes, "distinct_scans": nd,
+                       "map_tiles_touched": len(tiles), "map_tiles_complete": full_tiles, "parallelism": "scan-sharded x%d" % world,
+                       "device": dev_name, "cus": cus, "max_pose_err_vs_gt_m_tile0": gt_err, "timed_region_s": elapsed}}
+
+    if not args.full:   # the plain run: the headline and nothing else
+        bad = 0.0 if gt_err < 0.05 else 1.0
+        if dist is not None:
+            t = torch.tensor([elapsed, bad], dtype=torch.float64, device="cuda")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            elapsed, bad = float(t[0].item()), float(t[1].item())
+        if bad:
+            raise RuntimeError("bench: the step did not register the scans (pose error %.3f m on the un-jittered tile)" % gt_err)
+        return (json.dumps(dict(headline(elapsed), errors=errors)) if rank == 0 else None), False, errors
+
+    # ---- --full from here on: every section below runs outside the timed region -----------------------------------------
     # ---- replica check (outside the timed region): slots that were given the same scan on the same map tile with the same initial
     # pose must hold bit-identical results -- labels, rings, undistorted cloud, times, both stacks, both factor lists, pose
     # (mml_slot_digest, ten words per slot) -- at the launch shapes of the timed region.  tests/test_gpu_shapes.py ties the
@@ -483,11 +565,6 @@ def run_throughput(args, rank, local_rank, world, dist):
         except Exception as e:
             errors.append("value_by_slots: " + repr(e)[:200])
 
-    # pose sanity: the step must actually have registered the scans.  Only the slots on tile 0 count -- the original,
-    # un-jittered copy of the scene, where the generating pose IS the registration optimum up to the range noise; on the
-    # jittered copies of grow_map the optimum sits wherever the jitter put it -- and the number is asserted, not just printed.
-    on_tile0 = np.array([(s // nd) % len(tiles) == 0 for s in range(B)])
-    gt_err = float(np.abs(x[on_tile0, :3] - gt[on_tile0]).max())
     if not gt_err < 0.05:
         raise RuntimeError("bench: the step did not register the scans (pose error %.3f m on the un-jittered tile)" % gt_err)
 
@@ -741,18 +818,9 @@ def run_throughput(args, rank, local_rank, world, dist):
             errors.append("cpu_baseline: " + str(cpu["error"])[:200])
 
     if rank == 0:
-        out = {
-            "metric": "scans/s (feature-extract+kNN+%d GN iters) on %s" % (gn_iters, "16-ring x1800 + Livox 24k fused cloud" if args.config == 1 else cfg["name"].split(": ")[1]),
-            "value": value, "unit": "scans/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "f32/f64", "data": "synthetic",
-            "config": {"workload": "%s, local map %d pts, 1 association pass (thres_dist 25), %d GN iterations, W=1"
-                                   % (cfg["name"], map_points, gn_iters),
-                       "scans_per_step_per_gpu": batch, "resident_slots": B, "passes_per_step": passes, "stream_lanes": n_lanes, "distinct_scans": nd,
-                       "map_tiles_touched": len(tiles), "map_tiles_complete": full_tiles, "parallelism": "scan-sharded x%d" % world,
-                       "device": dev_name, "cus": cus, "features_per_scan": nf / KB, "points_per_scan": (n_v + n_l) / KB,
-                       "algorithmic_bytes_per_scan": bytes_per_scan, "max_pose_err_vs_gt_m_tile0": gt_err,
-                       "timed_region_s": elapsed},
+        out = headline(elapsed)
+        out["config"].update(features_per_scan=nf / KB, points_per_scan=(n_v + n_l) / KB, algorithmic_bytes_per_scan=bytes_per_scan)
+        out.update({
             "value_with_upload": with_upload,
             "roofline": {"bound": bound, "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                          "frac": hbm_frac, "traffic": traffic, "traffic_source": traffic_file, "traffic_stale": traffic_stale,
@@ -769,7 +837,7 @@ def run_throughput(args, rank, local_rank, world, dist):
             "replica_check": replica,
             "value_by_slots": value_by_slots,
             "errors": errors,
-        }
+        })
         return json.dumps(out), window_timed_out, errors
     return None, window_timed_out, errors
 
@@ -936,12 +1004,13 @@ def run_replay(args, rank, local_rank, world, dist):
     motions = [synth.sweep_motion(k0 + i) for i in range(n)]
     T_bl = np.eye(4)
 
-    pose_helpers_selfcheck()
+    if args.full:
+        pose_helpers_selfcheck()
 
     def replay(timed):
         odo = odometry.LidarOdometry(ctx, lidar_mode=2)
         poses_x = np.zeros((W, 6))   # the window's poses as (translation | rotation vector), the form the solver takes and returns
-        lat, lat_win = [], []
+        lat, lat_win, poses = [], [], []
         T_prev = T_prev_gt = None
         worst_gt = 0.0
         t_all = time.perf_counter()
@@ -969,12 +1038,13 @@ def run_replay(args, rank, local_rank, world, dist):
             t3 = time.perf_counter()
             lat.append((t3 - t1) * 1e3)
             lat_win.append((t3 - t2) * 1e3)
+            poses.append(T)
             if i > 0:
                 worst_gt = max(worst_gt, float(np.abs(T[:3, 3] - T_gt[:3, 3]).max()))
             T_prev, T_prev_gt = T, T_gt
         total = time.perf_counter() - t_all
         return dict(total=total, lat=lat, lat_win=lat_win, worst_gt=worst_gt, key_scans=odo.key_scans,
-                    map=(odo.n_corner_local, odo.n_surf_local))
+                    map=(odo.n_corner_local, odo.n_surf_local), poses=np.array(poses))
 
     def barrier():
         torch.cuda.synchronize()
@@ -998,7 +1068,28 @@ def run_replay(args, rank, local_rank, world, dist):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     hz = world * n * reps / elapsed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, {"poses": runs[-1]["poses"]})
 
+    def headline():
+        return {
+            "metric": "scans/s sustained (full odometry loop incl. upload + 8-scan window solve), one scan at a time",
+            "value": hz, "unit": "scans/s", "n_gpus": world, "steps": n * reps, "warmup": n,
+            "ms_per_step": elapsed / (n * reps) * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32/f64", "data": "synthetic",
+            "config": {"workload": "BASELINE configs[2]: replay of %d fused 52.8k-pt scans (synthetic room, the office bag is not "
+                                   "available offline) through EstimateLidarPose (5 outer x 10 inner) with the local map grown on the "
+                                   "device, plus the joint solve of the 8-scan sliding window after every scan" % n,
+                       "window": W, "replay_passes": reps, "device": dev_name, "cus": cus, "bag_rate_hz": BAG_RATE_HZ,
+                       "headroom_vs_bag_rate": hz / world / BAG_RATE_HZ, "key_scans": r["key_scans"], "local_map_points": list(r["map"]),
+                       "max_pose_err_vs_gt_m": r["worst_gt"], "timed_region_s": elapsed},
+            "latency_ms": {"per_scan_p50": pctl(r["lat"], 50), "per_scan_p99": pctl(r["lat"], 99), "per_scan_max": float(np.max(r["lat"])),
+                           "window8_part_p50": pctl(r["lat_win"], 50), "window8_part_p99": pctl(r["lat_win"], 99)}}
+
+    if not args.full:   # the plain run: the headline and nothing else
+        return (json.dumps(dict(headline(), errors=[])) if rank == 0 else None), []
+
+    # ---- --full from here on ----------------------------------------------------------------------------------------------
     # B = 1 latency of the configs[1] step against the replay's final map, and of the W = 8 joint solve alone
     dR1, dt1 = motions[-1][0].reshape(1, 9), motions[-1][1].reshape(1, 3)
     x1 = np.concatenate([synth.pose_matrix(k0 + n - 1)[:3, 3] + [0.03, -0.02, 0.01],
@@ -1133,20 +1224,9 @@ def run_replay(args, rank, local_rank, world, dist):
             errors.append("cpp_adapter_loop: " + repr(e)[:200])
 
     if rank == 0:
-        out = {
-            "metric": "scans/s sustained (full odometry loop incl. upload + 8-scan window solve), one scan at a time",
-            "value": hz, "unit": "scans/s", "n_gpus": world, "steps": n * reps, "warmup": n,
-            "ms_per_step": elapsed / (n * reps) * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32/f64", "data": "synthetic",
-            "config": {"workload": "BASELINE configs[2]: replay of %d fused 52.8k-pt scans (synthetic room, the office bag is not "
-                                   "available offline) through EstimateLidarPose (5 outer x 10 inner) with the local map grown on the "
-                                   "device, plus the joint solve of the 8-scan sliding window after every scan" % n,
-                       "window": W, "replay_passes": reps, "device": dev_name, "cus": cus, "bag_rate_hz": BAG_RATE_HZ,
-                       "headroom_vs_bag_rate": hz / world / BAG_RATE_HZ, "key_scans": r["key_scans"], "local_map_points": list(r["map"]),
-                       "max_pose_err_vs_gt_m": r["worst_gt"], "timed_region_s": elapsed},
-            "latency_ms": {"per_scan_p50": pctl(r["lat"], 50), "per_scan_p99": pctl(r["lat"], 99), "per_scan_max": float(np.max(r["lat"])),
-                           "window8_part_p50": pctl(r["lat_win"], 50), "window8_part_p99": pctl(r["lat_win"], 99),
-                           "configs1_step_B1_p50": pctl(lat1, 50), "configs1_step_B1_p99": pctl(lat1, 99)},
+        out = headline()
+        out["latency_ms"].update(configs1_step_B1_p50=pctl(lat1, 50), configs1_step_B1_p99=pctl(lat1, 99))
+        out.update({
             "latency_ms_cpp_adapter": cpp,
             "full_window_imu": fullwin,
             "roofline": {"bound": "hbm", "kernel": dom, "achieved": alg / (stage_ms[dom] * 1e-3) / 1e9, "peak": HBM_PEAK_GBPS,
@@ -1157,7 +1237,7 @@ def run_replay(args, rank, local_rank, world, dist):
                                  "dependency chain, not by HBM"},
             "cpu_baseline": cpu,
             "errors": errors,
-        }
+        })
         return json.dumps(out), errors
     return None, errors
 

@@ -151,7 +151,7 @@ def _args(bench, monkeypatch, argv):
 def test_run_throughput_on_a_stub_context(stubbed, monkeypatch):
     bench = stubbed
     args = _args(bench, monkeypatch, ["--steps", "2", "--warmup", "1", "--slots", "8", "--batch", "16", "--distinct", "2", "--map-points", "20000",
-                                      "--cpu-seconds", "0", "--kernel-steps", "1", "--skip-upload", "--window-demo"])
+                                      "--cpu-seconds", "0", "--kernel-steps", "1", "--skip-upload", "--window-demo", "--full"])
     line, stuck, errors = bench.run_throughput(args, 0, 0, 1, None)
     assert errors == [] and not stuck
     r = json.loads(line)
@@ -165,7 +165,7 @@ def test_run_throughput_on_a_stub_context(stubbed, monkeypatch):
 
 def test_run_replay_on_a_stub_context(stubbed, monkeypatch):
     bench = stubbed
-    args = _args(bench, monkeypatch, ["--config", "2", "--steps", "3", "--replay-scans", "10", "--cpu-seconds", "0"])
+    args = _args(bench, monkeypatch, ["--config", "2", "--steps", "3", "--replay-scans", "10", "--cpu-seconds", "0", "--full"])
     line, errors = bench.run_replay(args, 0, 0, 1, None)
     assert errors == []
     r = json.loads(line)
@@ -176,6 +176,87 @@ def test_run_replay_on_a_stub_context(stubbed, monkeypatch):
         assert "error" not in v and v["evaluations"] == 7 and isinstance(v["estimate_ms"], float), (k, v)
     assert r["latency_ms"]["per_scan_p50"] is not None and r["config"]["key_scans"] == 10
     assert r["latency_ms_cpp_adapter"]["scans"] == 10
+
+
+# ---- a plain run (no --full): set-up, warm-up, the timed steps, the outputs, the headline -- nothing else --------------------
+HEADLINE = ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step")
+FULL_ONLY = ("roofline", "cpu_baseline", "replica_check", "value_by_slots", "value_with_upload", "window_solve", "rccl",
+             "full_window_imu", "latency_ms_cpp_adapter")
+
+
+@pytest.fixture()
+def lean(stubbed, monkeypatch):
+    """The stub context, counting mml_step calls and refusing every entry point only a --full section calls."""
+    made = []
+
+    class LeanContext(StubContext):
+        def __init__(self, *a, **k):
+            super().__init__(*a, **k)
+            self.steps = 0
+            made.append(self)
+
+        def step(self, *a):
+            self.steps += 1
+            return super().step(*a)
+
+        def _full_only(self, *a, **k):
+            raise AssertionError("a plain run called an entry point of a --full section")
+        slot_digest = profile_get = issue_rate = copy_bandwidth = window_solve_allgather = scan_upload_batch = _full_only
+
+    monkeypatch.setattr(stubbed.importlib.import_module("multi-modal-loam_amd"), "Context", LeanContext)
+    monkeypatch.setattr(stubbed, "cpu_baseline_cpp", lambda *a, **k: pytest.fail("CPU baseline in a plain run"))
+    monkeypatch.setattr(stubbed, "cpp_live_loop", lambda *a, **k: pytest.fail("C++ adapter leg in a plain run"))
+    monkeypatch.setattr(stubbed, "pose_helpers_selfcheck", lambda: pytest.fail("self-check in a plain run"))
+    return stubbed, made
+
+
+def test_plain_run_times_the_steps_and_nothing_else(lean, monkeypatch):
+    bench, made = lean
+    args = _args(bench, monkeypatch, ["--steps", "3", "--warmup", "2", "--slots", "8", "--batch", "16", "--distinct", "2",
+                                      "--map-points", "20000"])
+    line, stuck, errors = bench.run_throughput(args, 0, 0, 1, None)
+    assert errors == [] and not stuck
+    (ctx,) = made
+    assert ctx.steps == (2 + 3) * 2                     # (warm-up + timed steps) x passes over the resident slots
+    assert not {"profile_enable", "comm_init", "associate"} & set(ctx.calls)
+    r = json.loads(line)
+    assert all(k in r for k in HEADLINE) and not [k for k in FULL_ONLY if k in r]
+    assert r["steps"] == 3 and r["warmup"] == 2 and r["unit"] == "scans/s" and r["higher_is_better"] is True
+    t = r["config"]["timed_region_s"]
+    assert np.isclose(r["ms_per_step"], t / 3 * 1e3) and np.isclose(r["value"], 16 * 3 / t)
+
+    args = _args(bench, monkeypatch, ["--config", "2", "--steps", "3", "--replay-scans", "10"])
+    line, errors = bench.run_replay(args, 0, 0, 1, None)
+    assert errors == [] and made[-1].steps == 0        # (the B = 1 latency of the configs[1] step is a --full section)
+    r = json.loads(line)
+    assert all(k in r for k in HEADLINE) and not [k for k in FULL_ONLY if k in r]
+    assert r["latency_ms"]["per_scan_p50"] is not None and "configs1_step_B1_p50" not in r["latency_ms"]
+
+
+def test_dump_outputs_are_the_last_steps_results_and_repeat(lean, monkeypatch, tmp_path):
+    bench, made = lean
+    dumps = []
+    for run in ("a", "b"):
+        args = _args(bench, monkeypatch, ["--steps", "2", "--warmup", "1", "--slots", "8", "--batch", "8", "--distinct", "2",
+                                          "--map-points", "20000", "--dump-outputs", str(tmp_path / run)])
+        bench.run_throughput(args, 0, 0, 1, None)
+        dumps.append({f[:-4]: np.load(tmp_path / run / f) for f in sorted(os.listdir(tmp_path / run))})
+    a, b = dumps
+    assert sorted(a) == ["corner_features", "feature_counts", "poses", "surf_features"]
+    assert a["poses"].shape == (8, 6) and a["poses"].dtype == np.float64
+    assert a["feature_counts"].tolist() == [[300, 900], [300, 900]] and a["corner_features"].shape == (600, 3)
+    assert all(a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]) for k in a)
+
+    args = _args(bench, monkeypatch, ["--config", "2", "--steps", "3", "--replay-scans", "10", "--dump-outputs", str(tmp_path / "c")])
+    bench.run_replay(args, 0, 0, 1, None)
+    assert os.listdir(tmp_path / "c") == ["poses.npy"] and np.load(tmp_path / "c" / "poses.npy").shape == (10, 4, 4)
+
+
+def test_dump_outputs_stay_within_the_byte_budget(bench, monkeypatch):
+    monkeypatch.setattr(bench, "DUMP_BYTES", 8 * 6 * 8 + 2 * (300 + 900) * 12 + 40)   # the poses + two slots' features
+    ctx = StubContext(None)
+    out = bench.throughput_outputs(ctx, np.zeros((8, 6)), 5)
+    assert len(out["feature_counts"]) == 2 and sum(a.nbytes for a in out.values()) <= bench.DUMP_BYTES
 
 
 def test_strict_turns_errors_into_a_nonzero_exit(tmp_path):

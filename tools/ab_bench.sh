@@ -5,7 +5,7 @@
 PREV=${1:-multi-modal-loam_amd/libmmloam_hip_prev.so}; NEW=${2:-multi-modal-loam_amd/libmmloam_hip.so}; shift 2 2>/dev/null
 for i in 1 2; do
 for L in $PREV $NEW; do
-MML_LIB_PATH=$L python bench.py --steps 3 --warmup 1 --cpu-seconds 0 --skip-upload "$@" 2>/dev/null | python -c "
+MML_LIB_PATH=$L python bench.py --full --steps 3 --warmup 1 --cpu-seconds 0 --skip-upload "$@" 2>/dev/null | python -c "
 import json,sys
 r=json.loads(sys.stdin.read().strip().splitlines()[-1]); st=r['roofline']['stage_ms_per_launch']
 print('$L'.split('/')[-1], round(r['value']), 'sum %.3f'%sum(st.values()), ' '.join('%s %.3f'%(k,v) for k,v in st.items()), 'replica mismatches', r['replica_check']['mismatches'], r['errors'])"

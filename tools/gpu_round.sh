@@ -11,7 +11,7 @@ if [ -n "$TESTS" ]; then
 fi
 for c in $CONFIGS; do
   SUF=""; [ "$c" != "1" ] && SUF=_config$c
-  python bench.py --config $c --strict > $OUT/bench$SUF.json 2> $OUT/bench$SUF.err
+  python bench.py --config $c --full --strict > $OUT/bench$SUF.json 2> $OUT/bench$SUF.err
   echo "bench --config $c rc=$?" | tee -a $OUT/bench$SUF.err
   tail -3 $OUT/bench$SUF.err
   python - <<PY

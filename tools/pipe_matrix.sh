@@ -4,7 +4,7 @@ TAG=$1; shift
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 run() {  # label, env...
   L=$1; shift
-  env "$@" python bench.py --steps 8 --warmup 2 --cpu-seconds 0 --skip-upload --kernel-steps 1 $EXTRA > $OUT/m_$L.json 2> $OUT/m_$L.err
+  env "$@" python bench.py --full --steps 8 --warmup 2 --cpu-seconds 0 --skip-upload --kernel-steps 1 $EXTRA > $OUT/m_$L.json 2> $OUT/m_$L.err
   python - <<PY
 import json
 try:

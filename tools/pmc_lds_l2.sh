@@ -7,7 +7,7 @@ SUF=""
 case "$*" in *"--config 3"*) SUF=_config3;; *"--config 4"*) SUF=_config4;; esac
 OUT=gpurun_out/prof_$TAG$SUF; mkdir -p $OUT
 export TMPDIR=/tmp
-PMCARGS="--steps 1 --warmup 0 --cpu-seconds 0 --slots ${KB:-1024} --batch ${KB:-1024} --skip-upload $*"
+PMCARGS="--full --steps 1 --warmup 0 --cpu-seconds 0 --slots ${KB:-1024} --batch ${KB:-1024} --skip-upload $*"
 rocprofv3 --kernel-trace --pmc SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS --output-format csv -d $OUT/pmc_lds -o l -- env MML_LANES=1 python bench.py $PMCARGS > /dev/null 2> $OUT/pmc_lds.err
 rocprofv3 --kernel-trace --pmc TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum --output-format csv -d $OUT/pmc_tcc -o t -- env MML_LANES=1 python bench.py $PMCARGS > /dev/null 2> $OUT/pmc_tcc.err
 L=$(find $OUT/pmc_lds -name "*counter_collection.csv" | head -1); T=$(find $OUT/pmc_tcc -name "*counter_collection.csv" | head -1)

@@ -12,11 +12,11 @@ OUT=gpurun_out/prof_$TAG$SUF
 mkdir -p $OUT
 export TMPDIR=/tmp
 export MML_LIB_SHA16=$(sha256sum multi-modal-loam_amd/libmmloam_hip.so | cut -c1-16)
-ARGS="--steps 4 --warmup 1 --cpu-seconds 0 --strict $*"
+ARGS="--full --steps 4 --warmup 1 --cpu-seconds 0 --strict $*"
 # The counter passes run ONLY launches of 1024 scans on one stream (the launches bench.py times for its roofline object): the
 # summarisers average a kernel's launches of the largest grid, and the kernels with a fixed grid (k_associate, the k_select rows) look
 # the same at every batch size -- mixed with the timed region's per-lane launches their counters would describe no launch at all.
-PMCARGS="--steps 1 --warmup 0 --cpu-seconds 0 --slots ${KB:-1024} --batch ${KB:-1024} --skip-upload --skip-by-slots $*"
+PMCARGS="--full --steps 1 --warmup 0 --cpu-seconds 0 --slots ${KB:-1024} --batch ${KB:-1024} --skip-upload --skip-by-slots $*"
 export PMC_LANES=1
 rocprofv3 --kernel-trace --stats -d $OUT/trace -o $TAG -- python bench.py $ARGS > $OUT/bench_under_rocprof.json 2> $OUT/trace.err
 DB=$(ls $OUT/trace/*/*.db 2>/dev/null | head -1); [ -z "$DB" ] && DB=$(ls $OUT/trace/*.db 2>/dev/null | head -1)
@@ -37,6 +37,6 @@ rm -rf $OUT/trace $OUT/pmc_fetch $OUT/pmc_write $OUT/pmc_sq
 # checkout (on the GPU box: the scratch copy) so that the line carries their traffic and instruction counts as current, not
 # stale; what is to be committed still has to be copied from gpurun_out/prof_<tag>/ into profiles/ by hand.
 for f in $OUT/traffic_*.json $OUT/sq_*.json; do [ -s "$f" ] && cp $f profiles/; done
-python bench.py --strict $* > $OUT/${TAG}_bench$SUF.json 2> $OUT/bench.err
+python bench.py --full --strict $* > $OUT/${TAG}_bench$SUF.json 2> $OUT/bench.err
 echo "bench rc=$?" >> $OUT/bench.err
 ls -la $OUT; tail -c 400 $OUT/${TAG}_bench$SUF.json; echo; head -30 $OUT/${TAG}_kernel_stats$SUF.md | cut -c1-150

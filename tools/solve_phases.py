@@ -7,7 +7,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.argv = ["bench.py", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--kernel-steps", "2"]
+sys.argv = ["bench.py", "--full", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0", "--kernel-steps", "2"]
 import bench  # noqa: E402
 import torch  # noqa: E402
 
