@@ -490,6 +490,44 @@ int mml_fullwindow_normal_equations(const mml_fullwindow*, const double* records
 /* MarginalizationInfo::marginalize for the factor set of Estimator.cpp:1453-1546 (previous prior, IMU factor 0-1,
  * lidar factors of frame 0 as their loss-free normal equations).  x: W x 15.  out: the prior for the slid window. */
 int mml_fullwindow_marginalize(const mml_fullwindow*, const double* lidar_record0, const double* x, mml_prior* out);
+/* ---- the LIO initialisation that opens full-window mode (TryMAPInitialization, unionPoseEstimation.cpp:425-625) ------
+ * Host side like the rest of this section: no context, no device. */
+/* IMUIntegrator::GyroIntegration (IMUIntegrator.cpp:90-106): the gyro samples accumulated onto dq (x, y, z, w; in/out,
+ * not reset first).  samples: n x 7 as for mml_imu_preintegrate; only angular_velocity and dt are read.  A dt < 0 (the
+ * reference's ROS_ASSERT) is MML_ERR_INVALID and leaves dq unchanged. */
+int mml_imu_gyro_integrate(const double* samples, int n, double* dq);
+/* Cost_Initialization_IMU (ceresfunc.h:654-741) with sqrt_information = LLT(covariance.block<9,9>(0,0)^-1).matrixL()^T
+ * (unionPoseEstimation.cpp:558-561).  ri, rj: rotation vectors of the two body orientations; dp: body position j minus
+ * body position i; rwg, vi, vj, ba, bg: the parameter blocks.  residual: 9; jacobian (may be NULL): 9 x 15 row-major,
+ * columns [rwg | vi | vj | ba | bg] (analytic). */
+int mml_imu_init_factor(const mml_imu_preint* pre, const double* ri, const double* rj, const double* dp, const double* rwg,
+                        const double* vi, const double* vj, const double* ba, const double* bg, double* residual,
+                        double* jacobian);
+typedef struct {
+    int status;                  /* 0 initialised; 1 |b_a| or |b_g| > 0.5 (nothing written); 2 a velocity more than 2.0
+                                    from its prior (frames 0..fail_frame hold the new biases, 0..fail_frame-1 the new V) */
+    int fail_frame;              /* status 2: that frame; -1 otherwise */
+    int keep_from;               /* status 0: the caller drops frames [0, keep_from) (the list is trimmed to 5 frames) */
+    int _pad;
+    double gravity[3];           /* GravityVector = exp(r_wg) (0, 0, -9.805) */
+    double r_wg[3];              /* the joint solve's rotation vector */
+    double q_wg[4];              /* the gravity solve's quaternion, x y z w */
+    double average_acc[3];       /* -GetAverageAcc() of frame 0, rescaled to norm 9.805 */
+    double ba[3], bg[3];         /* the joint solve's biases (also when a check failed) */
+    mml_solve_summary gravity_solve, joint_solve;   /* the two ceres::Solve calls */
+} mml_lio_init_result;
+/* TryMAPInitialization on n >= 2 frames (the reference's list, front first).  t: n time stamps; P (n x 3), Q (n x 4,
+ * x y z w): lidar poses, world <- lidar; V, bg, ba (n x 3): the frame states, written as the reference writes them
+ * (status 0: all; status 2: the partial state above; the back frame's P, Q converted to the body on status 0 only).
+ * samples / offsets: frame i's IMU messages are rows offsets[i] .. offsets[i+1]-1 of an n x 7 array as for
+ * mml_imu_preintegrate (frame i's first dt counts from t[i-1]); frame 0 needs at least one.  exTlb: 4 x 4 row-major.
+ * pre_in (may be NULL): n entries, entry i >= 1 the pre-integration frame i holds; NULL: each is computed from its
+ * samples with frame i-1's bg / ba.  pre_out (may be NULL): n entries, entry i >= 1 receives the pre-integration the
+ * joint solve used, on status 0 the one redone with the new biases (entry 0 is not written).  Returns MML_OK whatever
+ * the status; < 0 on a bad argument or a covariance that is not positive definite. */
+int mml_lio_initialize(int n, const double* t, double* P, double* Q, double* V, double* bg, double* ba, const double* samples,
+                       const int* offsets, const double* exTlb, const mml_imu_preint* pre_in, mml_imu_preint* pre_out,
+                       mml_lio_init_result* out);
 /* The minimisation of the mml_fullwindow_step loop with the whole trust-region iteration resident on the device: the
  * lidar factors of the W frames in slots first_slot .. first_slot + W - 1 (associated beforehand, evaluated with the
  * handle's plan_weight_tan / huber_delta), the IMU factors and the prior set on `fw` are evaluated, assembled into the

@@ -694,6 +694,61 @@ def imu_factor(pre, gravity, pr_i, vb_i, pr_j, vb_j, jac=True):
     return r, J
 
 
+class LioInitResult(C.Structure):
+    _fields_ = [("status", C.c_int), ("fail_frame", C.c_int), ("keep_from", C.c_int), ("_pad", C.c_int),
+                ("gravity", C.c_double * 3), ("r_wg", C.c_double * 3), ("q_wg", C.c_double * 4),
+                ("average_acc", C.c_double * 3), ("ba", C.c_double * 3), ("bg", C.c_double * 3),
+                ("gravity_solve", SolveSummary), ("joint_solve", SolveSummary)]
+
+
+LIO_INIT_OK, LIO_INIT_BIAS, LIO_INIT_VELOCITY = 0, 1, 2
+
+
+def imu_gyro_integrate(samples, dq=(0.0, 0.0, 0.0, 1.0)):
+    """IMUIntegrator::GyroIntegration: the gyro samples (n, 7) accumulated onto dq (x, y, z, w).  Returns the new dq."""
+    smp = _f64(samples).reshape(-1, 7)
+    q = _f64(dq).reshape(4).copy()
+    rc = lib().mml_imu_gyro_integrate(_p(smp), C.c_int(len(smp)), _p(q))
+    if rc != MML_OK:
+        raise MmlError(rc, "mml_imu_gyro_integrate")
+    return q
+
+
+def imu_init_factor(pre, ri, rj, dp, rwg, vi, vj, ba, bg, jac=True):
+    """Cost_Initialization_IMU: weighted residual (9) and Jacobian (9, 15) [rwg | vi | vj | ba | bg]."""
+    r = np.zeros(9)
+    J = np.zeros((9, 15)) if jac else None
+    rc = lib().mml_imu_init_factor(C.byref(pre), *[_p(_f64(a).reshape(3)) for a in (ri, rj, dp, rwg, vi, vj, ba, bg)],
+                                   _p(r), _p(J))
+    if rc != MML_OK:
+        raise MmlError(rc, "mml_imu_init_factor")
+    return r, J
+
+
+def lio_initialize(t, P, Q, V, bg, ba, samples, exTlb, pre=None):
+    """TryMAPInitialization on arrays (mml_lio_initialize).  t (n,), P (n,3), Q (n,4 x y z w), V / bg / ba (n,3); samples:
+    a list of n (k_i, 7) arrays (frame i's IMU messages); pre: None or a list of n pre-integrations (entry 0 unused).
+    Returns (result, dict of the written P, Q, V, bg, ba arrays, list of n pre-integrations with entry 0 None)."""
+    n = len(t)
+    st = {k: _f64(a).reshape(n, w).copy() for k, a, w in (("P", P, 3), ("Q", Q, 4), ("V", V, 3), ("bg", bg, 3), ("ba", ba, 3))}
+    smp = [_f64(s).reshape(-1, 7) for s in samples]
+    offsets = np.concatenate([[0], np.cumsum([len(s) for s in smp])]).astype(np.int32)
+    flat = _f64(np.concatenate(smp) if offsets[-1] else np.zeros((0, 7)))
+    pin = None
+    if pre is not None:
+        pin = (ImuPreint * n)()
+        for i in range(1, n):
+            pin[i] = pre[i]
+    pout = (ImuPreint * n)()
+    res = LioInitResult()
+    rc = lib().mml_lio_initialize(C.c_int(n), _p(_f64(t).reshape(n)), _p(st["P"]), _p(st["Q"]), _p(st["V"]), _p(st["bg"]),
+                                  _p(st["ba"]), _p(flat), _p(offsets), _p(_f64(exTlb).reshape(16)), pin, pout, C.byref(res))
+    if rc != MML_OK:
+        raise MmlError(rc, "mml_lio_initialize")
+    pres = [None] + [ImuPreint.from_buffer_copy(pout[i]) for i in range(1, n)]
+    return res, st, pres
+
+
 class FullWindowSolver:
     """Estimator::Estimate in full-window mode on the host: W x [PR 6 | VBias 9], lidar records from the device,
     IMU factors between consecutive frames, optional marginalization prior on frame 0."""

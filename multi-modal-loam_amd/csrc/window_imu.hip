@@ -123,29 +123,37 @@ void sym_eig(const double* Ain, int n, double* ev, double* V) {
 constexpr double kGnorm = 9.805;                                        // IMUIntegrator.h:84
 constexpr double kAccN = 0.08, kGyrN = 0.004, kAccW = 2.0e-4, kGyrW = 2.0e-5;  // IMUIntegrator.h:79-82
 
-// sqrt information of one pre-integration: LLT(covariance^-1).matrixL().transpose() (Estimator.cpp:1240-1242)
-bool imu_sqrt_info(const mml_imu_preint* pre, double* U /*15x15 upper*/) {
+// sqrt information of the leading n x n block (n <= 15) of a covariance stored with row stride ld:
+// LLT(block^-1).matrixL().transpose(), n x n upper, row-major
+bool sqrt_info_block(const double* cov, int ld, int n, double* U) {
     double L[225];
-    memcpy(L, pre->covariance, sizeof(L));
-    if (!cholesky(L, 15)) return false;
+    for (int r = 0; r < n; ++r)
+        for (int c = 0; c < n; ++c) L[r * n + c] = cov[r * ld + c];
+    if (!cholesky(L, n)) return false;
     double inv[225];
-    for (int c = 0; c < 15; ++c) {
+    for (int c = 0; c < n; ++c) {
         double e[15] = {0};
         e[c] = 1.0;
-        chol_solve(L, 15, e);
-        for (int r = 0; r < 15; ++r) inv[r * 15 + c] = e[r];
+        chol_solve(L, n, e);
+        for (int r = 0; r < n; ++r) inv[r * n + c] = e[r];
     }
-    for (int r = 0; r < 15; ++r)
-        for (int c = r + 1; c < 15; ++c) inv[r * 15 + c] = inv[c * 15 + r] = 0.5 * (inv[r * 15 + c] + inv[c * 15 + r]);
-    if (!cholesky(inv, 15)) return false;
-    for (int r = 0; r < 15; ++r)
-        for (int c = 0; c < 15; ++c) U[r * 15 + c] = (c >= r) ? inv[c * 15 + r] : 0.0;  // U = L^T
+    for (int r = 0; r < n; ++r)
+        for (int c = r + 1; c < n; ++c) inv[r * n + c] = inv[c * n + r] = 0.5 * (inv[r * n + c] + inv[c * n + r]);
+    if (!cholesky(inv, n)) return false;
+    for (int r = 0; r < n; ++r)
+        for (int c = 0; c < n; ++c) U[r * n + c] = (c >= r) ? inv[c * n + r] : 0.0;  // U = L^T
     return true;
 }
+
+// sqrt information of one pre-integration: LLT(covariance^-1).matrixL().transpose() (Estimator.cpp:1240-1242)
+bool imu_sqrt_info(const mml_imu_preint* pre, double* U /*15x15 upper*/) { return sqrt_info_block(pre->covariance, 15, 15, U); }
 
 }  // namespace
 
 bool mml_imu_sqrt_info(const mml_imu_preint* pre, double* U) { return imu_sqrt_info(pre, U); }
+bool mml_sqrt_info_block(const double* cov, int ld, int n, double* U) { return n >= 1 && n <= 15 && sqrt_info_block(cov, ld, n, U); }
+bool mml_cholesky(double* A, int n) { return cholesky(A, n); }
+void mml_chol_solve(const double* L, int n, double* b) { chol_solve(L, n, b); }
 
 extern "C" {
 

@@ -667,5 +667,113 @@ inline TimeOffsetResult EstimateTimeOffsetCore(Context& ctx, const float* velo_f
     return r;
 }
 
+// ---- IMUIntegrator (IMUIntegrator.h / IMUIntegrator.cpp) over the caller's messages ----------------------------------------
+// A message is 7 doubles: angular_velocity xyz, linear_acceleration xyz (units of g, as the Livox IMU reports them), dt to the
+// previous message (the stamp difference the reference forms from lastTime, :95-97, :122).  Reset() keeps the messages, as
+// the reference's Reset (:49-58) does.
+class IMUIntegrator {
+   public:
+    void PushIMUMsg(const double* msg) { msgs.insert(msgs.end(), msg, msg + 7); }
+    void PushIMUMsg(const std::vector<double>& msg7n) { msgs.insert(msgs.end(), msg7n.begin(), msg7n.end()); }
+    int size() const { return (int)(msgs.size() / 7); }
+    void Reset() {
+        dq = Quaterniond();
+        has_pre = false;
+    }
+    // GyroIntegration (:90-106): accumulates onto dq (not reset); throws on a dt < 0 (the reference's ROS_ASSERT)
+    void GyroIntegration() {
+        double q[4] = {dq.x, dq.y, dq.z, dq.w};
+        check(nullptr, mml_imu_gyro_integrate(msgs.data(), size(), q), "mml_imu_gyro_integrate");
+        dq.x = q[0], dq.y = q[1], dq.z = q[2], dq.w = q[3];
+    }
+    // PreIntegration (:108-166) with the linearisation biases bg / ba; `pre` holds the result
+    void PreIntegration(const Vector3d& bg, const Vector3d& ba) {
+        check(nullptr, mml_imu_preintegrate(msgs.data(), size(), bg.v, ba.v, &pre), "mml_imu_preintegrate");
+        dq.x = pre.dq[0], dq.y = pre.dq[1], dq.z = pre.dq[2], dq.w = pre.dq[3];
+        has_pre = true;
+    }
+    // GetAverageAcc (:168-181): the mean of the first 31 messages' linear_acceleration * gnorm
+    Vector3d GetAverageAcc() const {
+        Vector3d s{{0, 0, 0}};
+        int i = 0;
+        for (int k = 0; k < size(); ++k) {
+            for (int c = 0; c < 3; ++c) s.v[c] += msgs[7 * (size_t)k + 3 + c] * 9.805;
+            i++;
+            if (i > 30) break;
+        }
+        for (int c = 0; c < 3; ++c) s.v[c] /= i;
+        return s;
+    }
+    const Quaterniond& GetDeltaQ() const { return dq; }
+
+    std::vector<double> msgs;  // size() x 7
+    Quaterniond dq;            // GyroIntegration's accumulator / the last pre-integration's dq
+    mml_imu_preint pre{};      // the last PreIntegration
+    bool has_pre = false;
+};
+
+// TryMAPInitialization (unionPoseEstimation.cpp:425-625) through mml_lio_initialize.  frameList: the reference's list
+// (lidar poses P / Q, V, bg, ba, timeStamp); imu[i]: frame i's integrator (its messages; its `pre` when every frame after
+// the first has one, else frame i's messages are pre-integrated with frame i-1's biases).  Both are changed the way the
+// reference changes its list: on success the new V / biases, the pre-integrations redone with them, the list trimmed to
+// SLIDEWINDOWSIZE and the back frame moved from lidar to body; nothing when the biases are too large; the partial writes
+// of :589-598 when a velocity is.  GravityVector is written in every case, as the reference writes it before its checks.
+inline bool TryMAPInitialization(std::list<Estimator::LidarFrame>& frameList, std::vector<IMUIntegrator>& imu,
+                                 const Matrix4d& exTlb, Vector3d& GravityVector) {
+    const int n = (int)frameList.size();
+    if (n < 2 || (int)imu.size() != n) throw std::runtime_error("TryMAPInitialization: one IMUIntegrator per frame, >= 2 frames");
+    std::vector<double> t(n), P(3 * (size_t)n), Q(4 * (size_t)n), V(3 * (size_t)n), bg(3 * (size_t)n), ba(3 * (size_t)n), smp;
+    std::vector<int> offsets(1, 0);
+    std::vector<mml_imu_preint> pre_in(n), pre_out(n);
+    bool given = true;
+    int i = 0;
+    for (const auto& f : frameList) {
+        t[i] = f.timeStamp;
+        const double q[4] = {f.Q.x, f.Q.y, f.Q.z, f.Q.w};
+        for (int k = 0; k < 3; ++k) {
+            P[3 * i + k] = f.P.v[k];
+            V[3 * i + k] = f.V.v[k];
+            bg[3 * i + k] = f.bg.v[k];
+            ba[3 * i + k] = f.ba.v[k];
+        }
+        for (int k = 0; k < 4; ++k) Q[4 * i + k] = q[k];
+        smp.insert(smp.end(), imu[i].msgs.begin(), imu[i].msgs.end());
+        offsets.push_back(offsets.back() + imu[i].size());
+        if (i >= 1) {
+            given = given && imu[i].has_pre;
+            pre_in[i] = imu[i].pre;
+        }
+        ++i;
+    }
+    mml_lio_init_result res;
+    check(nullptr,
+          mml_lio_initialize(n, t.data(), P.data(), Q.data(), V.data(), bg.data(), ba.data(), smp.data(), offsets.data(), exTlb.m,
+                             given ? pre_in.data() : nullptr, pre_out.data(), &res),
+          "mml_lio_initialize");
+    for (int k = 0; k < 3; ++k) GravityVector.v[k] = res.gravity[k];
+    if (res.status == 1) return false;
+    i = 0;
+    for (auto& f : frameList) {  // V / bg / ba as written (all of them, or the partial state)
+        for (int k = 0; k < 3; ++k) {
+            f.V.v[k] = V[3 * i + k];
+            f.bg.v[k] = bg[3 * i + k];
+            f.ba.v[k] = ba[3 * i + k];
+        }
+        ++i;
+    }
+    if (res.status != 0) return false;
+    for (int j = 1; j < n; ++j) {
+        imu[j].pre = pre_out[j];
+        imu[j].dq.x = pre_out[j].dq[0], imu[j].dq.y = pre_out[j].dq[1], imu[j].dq.z = pre_out[j].dq[2], imu[j].dq.w = pre_out[j].dq[3];
+        imu[j].has_pre = true;
+    }
+    Estimator::LidarFrame& back = frameList.back();
+    for (int k = 0; k < 3; ++k) back.P.v[k] = P[3 * (n - 1) + k];
+    back.Q.x = Q[4 * (n - 1)], back.Q.y = Q[4 * (n - 1) + 1], back.Q.z = Q[4 * (n - 1) + 2], back.Q.w = Q[4 * (n - 1) + 3];
+    for (int j = 0; j < res.keep_from; ++j) frameList.pop_front();  // WINDOWSIZE = SLIDEWINDOWSIZE (:611-614)
+    imu.erase(imu.begin(), imu.begin() + res.keep_from);
+    return true;
+}
+
 }  // namespace mml
 #endif

@@ -182,3 +182,40 @@ class WindowEstimator:
                 self.prior = fw.marginalize(rec0, x) if W >= 2 else None
                 break
         return info
+
+
+def try_map_initialization(frames, samples, exTlb=None):
+    """TryMAPInitialization (unionPoseEstimation.cpp:425-625) through mml_lio_initialize.  frames: the reference's frame
+    list, front first, as dicts in the shape WindowEstimator.estimate uses (P, Q as x y z w = the lidar pose, V, bg, ba)
+    plus the time stamp "t" and, for frames after the first, optionally "pre": the pre-integration the frame holds
+    (without it: frame i's samples pre-integrated with frame i-1's biases).  samples: list of the frames' IMU messages
+    ((k, 7) arrays as for imu_preintegrate).  Both lists are changed in place the way the reference changes its
+    std::list: on success every frame gets the new V / bg / ba, frames after the first their redone "pre", the lists
+    are trimmed to SLIDEWINDOWSIZE (5) and the back frame alone is moved from the lidar to the body; when the biases are
+    too large nothing is written; when a velocity is too large the frames up to it keep the partial writes.
+    Returns (ok, gravity, preints): preints[f] (f >= 1) between frames f-1 and f of the (trimmed) list, ready for
+    WindowEstimator(gravity=gravity).estimate(slots, frames, preints)."""
+    import importlib
+    M = importlib.import_module(__package__)
+    n = len(frames)
+    pre = [None] + [fr["pre"] for fr in frames[1:]] if all("pre" in fr for fr in frames[1:]) else None
+    res, st, pres = M.lio_initialize([fr["t"] for fr in frames], [fr["P"] for fr in frames], [fr["Q"] for fr in frames],
+                                     [fr["V"] for fr in frames], [fr["bg"] for fr in frames], [fr["ba"] for fr in frames],
+                                     samples, np.eye(4) if exTlb is None else exTlb, pre)
+    gravity = np.array(res.gravity)
+    if res.status == M.LIO_INIT_BIAS:
+        return False, gravity, pres
+    written = n if res.status == M.LIO_INIT_OK else res.fail_frame + 1
+    for i in range(written):
+        frames[i]["bg"], frames[i]["ba"] = st["bg"][i].copy(), st["ba"][i].copy()
+        if res.status == M.LIO_INIT_OK or i < res.fail_frame:
+            frames[i]["V"] = st["V"][i].copy()
+    if res.status != M.LIO_INIT_OK:
+        return False, gravity, pres
+    for i in range(1, n):
+        frames[i]["pre"] = pres[i]
+    frames[-1]["P"], frames[-1]["Q"] = st["P"][-1].copy(), st["Q"][-1].copy()
+    del frames[:res.keep_from]
+    del samples[:res.keep_from]
+    pres = [None] + pres[1 + res.keep_from:]
+    return True, gravity, pres
