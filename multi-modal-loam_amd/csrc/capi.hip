@@ -32,6 +32,31 @@ double* stage_alloc(mml_ctx* ctx, size_t doubles) {
     return p;
 }
 
+// The launch settings of a context, read once when it is created: the CU count of its device and the environment switches.
+// Nothing else in the library reads the environment, so every choice below holds for this context alone.
+hipError_t read_settings(mml_ctx* ctx) {
+    hipDeviceProp_t prop;
+    const hipError_t e = hipGetDeviceProperties(&prop, ctx->device);
+    if (e != hipSuccess) return e;
+    ctx->cus = prop.multiProcessorCount;
+    // (two lanes: with calls of ~2000 scans two to four lanes give the same rate, with 8192 two give 360 k scans/s against 351 k for
+    //  four, and a call of a few hundred scans splits into launches that still fill the device)
+    ctx->n_lanes = 2;
+    if (const char* v = getenv("MML_LANES")) {  // tuning knob: number of stream lanes mml_step pipelines over
+        const int n = atoi(v);
+        if (n >= 1 && n <= mml_ctx::MAX_LANES) ctx->n_lanes = n;
+    }
+    // measurement switches, each selecting the other form of a stage (same results bit for bit)
+    const auto off = [](const char* name) {
+        const char* v = getenv(name);
+        return v && atoi(v) == 0;
+    };
+    ctx->onepass_wanted = !off("MML_ASSIGN_ONEPASS");
+    ctx->solve_wide = !off("MML_SOLVE_WIDE");
+    ctx->use_graph = getenv("MML_NO_GRAPH") == nullptr;
+    return hipSuccess;
+}
+
 }  // namespace
 
 double* mml_stage_alloc(mml_ctx* ctx, size_t doubles) { return stage_alloc(ctx, doubles); }
@@ -148,13 +173,7 @@ int mml_create(const mml_config* cfg, int device, mml_ctx** out) {
     };
     hipError_t e;
     if ((e = hipSetDevice(device)) != hipSuccess) return fail(e, "hipSetDevice");
-    // (two lanes: with calls of ~2000 scans two to four lanes give the same rate, with 8192 two give 360 k scans/s against 351 k for
-    //  four, and a call of a few hundred scans splits into launches that still fill the device)
-    ctx->n_lanes = 2;
-    if (const char* e_l = getenv("MML_LANES")) {  // tuning knob: number of stream lanes mml_step pipelines over
-        int v = atoi(e_l);
-        if (v >= 1 && v <= mml_ctx::MAX_LANES) ctx->n_lanes = v;
-    }
+    if ((e = read_settings(ctx)) != hipSuccess) return fail(e, "hipGetDeviceProperties");
     for (int l = 0; l < mml_ctx::MAX_LANES; ++l) {
         if ((e = hipStreamCreateWithFlags(&ctx->streams[l], hipStreamNonBlocking)) != hipSuccess)
             return fail(e, "hipStreamCreate");
@@ -1514,7 +1533,7 @@ int mml_step(mml_ctx* ctx, int first_slot, int count, const double* dR, const do
     // kernel of the chain fills the CUs' registers / LDS by itself at these batch sizes.  Round 5 measured the other
     // schedule -- pieces of 512 .. 2048 scans, stream 0 extracting piece i + 1 while other streams run the back end of piece
     // i, 2 .. 5 streams, three stage-to-stream maps: 306 k .. 330 k scans/s against 355 k for two lanes (HISTORY.md).
-    const int lanes = (count >= 64 && ctx->lanes_enabled) ? ctx->n_lanes : 1;
+    const int lanes = count >= 64 ? ctx->n_lanes : 1;
     const int n_pieces = lanes;
     const int chunk = (count + n_pieces - 1) / n_pieces;
     std::vector<double> Twl(16 * (size_t)chunk);
@@ -1944,9 +1963,7 @@ __global__ __launch_bounds__(256) void k_issue_rate(float* out, float a, float b
 extern "C" int mml_issue_rate(mml_ctx* ctx, int kind, int reps, double* wave_instr_per_s) {
     if (!ctx || !wave_instr_per_s || reps <= 0 || kind < 0 || kind > 1) return MML_ERR_INVALID;
     MML_HIP(hipSetDevice(ctx->device));
-    hipDeviceProp_t prop;
-    MML_HIP(hipGetDeviceProperties(&prop, ctx->device));
-    const int blocks = prop.multiProcessorCount * 64;  // eight workgroups of four wavefronts per CU, eight rounds of them
+    const int blocks = ctx->cus * 64;  // eight workgroups of four wavefronts per CU, eight rounds of them
     float* d = nullptr;
     MML_HIP(hipMalloc(reinterpret_cast<void**>(&d), sizeof(float) * 256 * (size_t)blocks));
     hipEvent_t e0, e1;

@@ -103,7 +103,6 @@ struct FeatParams {
     int4* seg_rs;   // per 64 line indices: (boundary, offset below it, offset from it on, 1 = no second boundary): rounds of k_stencil
     int4* seg_rw;   //   the same for aligned windows (k_select_part)
     int seg_rstride;
-    int xcd_remap;  // k_assign_c_staged: slots dealt to the XCDs (measurement switch MML_XCD_REMAP=0)
     int ab_ppt;     // points per thread of pass A on the Velodyne part (dense layouts: 4, i.e. 1024-point count blocks)
     int ends_inline;  // k_assign_onepass computes the sweep's start / end azimuth itself (a handful of scans: one launch less)
 };
@@ -696,7 +695,7 @@ __global__ __launch_bounds__(CB_THREADS) void k_assign_c_staged(FeatParams P) {
     // line.  Remapped: XCD x owns the slots x, x + 8, ... of the launch and walks their tiles in order, so the pieces of a line meet
     // in ONE L2 and leave it merged (configs[3]: 4.42 -> 4.01 ms per 1024 scans with the 1024-point tiles).
     int bx = blockIdx.x, by = blockIdx.y;
-    if (P.xcd_remap && (gridDim.y & 7) == 0) {
+    if ((gridDim.y & 7) == 0) {
         const int g = blockIdx.y * gridDim.x + blockIdx.x;
         const int xcd = g & 7, idx = g >> 3;
         by = (idx / (int)gridDim.x) * 8 + xcd;
@@ -1891,13 +1890,9 @@ constexpr int ST_SEGMENT_MAX_SLOTS = 16;  // batches up to this size take the se
 //         offset, reloads the tile (it is in the L2), walks it, and runs the included-angle pass.  Same results as MODE 0.
 template <int MODE>
 __global__ __launch_bounds__(64 * ST_LINES) void k_stencil(FeatParams P) {
-#ifdef MML_ST_GLOBAL_TAB
-    const unsigned long long* s_row = g_walk_tab.row;
-#else
     __shared__ unsigned long long s_row[256];  // the transfer table (2 KB): eight look-ups per window walk
     for (int k = threadIdx.x; k < 256; k += 64 * ST_LINES) s_row[k] = g_walk_tab.row[k];
     __syncthreads();  // (the only workgroup barrier: before any wavefront leaves)
-#endif
     // MODE 0: grid (slots, line groups), the line groups taken Livox lines first: the long lines (4 000 points against 1 800) of ALL
     // slots are dispatched before the short ones, so that the launch does not end on a few long workgroups (with the slot as the slow
     // grid index every slot's three Livox groups came behind its eight ring groups: 0.59 -> 0.54 ms per 1024-scan launch)
@@ -2083,7 +2078,6 @@ __global__ __launch_bounds__(64 * ST_LINES) void k_stencil(FeatParams P) {
         ST_MARK(2);
         // ---- the walk over this tile: lane (w, e), w < 4, = window w entered at offset e ----
         unsigned long long vmask[4] = {0ull, 0ull, 0ull, 0ull};
-#ifndef MML_ST_NOWALK
         {
             PHASE_IDS();
             const int w = (lane >> 2) & 3;
@@ -2143,7 +2137,6 @@ __global__ __launch_bounds__(64 * ST_LINES) void k_stencil(FeatParams P) {
                 carry = e;
             }
         }
-#endif
         ST_MARK(3);
         if constexpr (MODE == 1) {  // the attribute words as the rounds left them (launch 2 reads the flatness bits back)
             PHASE_IDS();
@@ -2171,9 +2164,6 @@ __global__ __launch_bounds__(64 * ST_LINES) void k_stencil(FeatParams P) {
                 n150 += __popcll(wm);
             }
             WAVE_SYNC();
-#ifdef MML_ST_NO150
-            n150 = 0;
-#endif
             for (int e = lane; e < n150; e += 64) {
                 const int tp = s_list[e];
                 bool decided;
@@ -3978,7 +3968,7 @@ FeatParams make_params(mml_ctx* ctx, int first) {
     P.brk_cnt = ctx->brk_cnt;
     P.redo_queue = ctx->redo_queue;
     P.redo_cnt = ctx->brk_cnt + ctx->B;
-    P.sel_done = ctx->select_part ? ctx->sel_done : nullptr;
+    P.sel_done = ctx->sel_done;
     P.sel_list = ctx->sel_list;
     P.sel_list_cnt = ctx->sel_list_cnt;
     P.st_exit = ctx->st_exit;
@@ -3994,11 +3984,6 @@ FeatParams make_params(mml_ctx* ctx, int first) {
     P.seg_rs = ctx->seg_rs;
     P.seg_rw = ctx->seg_rw;
     P.seg_rstride = ctx->seg_rstride;
-    {
-        static int remap = -1;
-        if (remap < 0) remap = getenv("MML_XCD_REMAP") ? atoi(getenv("MML_XCD_REMAP")) : 1;
-        P.xcd_remap = remap;
-    }
     return P;
 }
 
@@ -4129,7 +4114,7 @@ int mml_launch_extract(mml_ctx* ctx, int first, int count, bool have_extrinsic) 
         Pl.line0 = ctx->cfg.n_rings;
         // (a handful of scans -- the live one-scan call -- cannot fill the device with one wavefront per line: there the
         //  workgroup-per-line kernel is the shorter chain, 0.054 against 0.132 ms for one scan)
-        const bool part = ctx->select_part && count > ST_SEGMENT_MAX_SLOTS;
+        const bool part = count > ST_SEGMENT_MAX_SLOTS;
         if (!part) {
             Pv.sel_done = nullptr;
             Pl.sel_done = nullptr;
@@ -4247,10 +4232,8 @@ int mml_launch_detect_line(mml_ctx* ctx, int n, uint16_t* d_final) {
         hipLaunchKernelGGL(k_stencil_redo, dim3(4, 1), dim3(256), 0, s, P);
         hipLaunchKernelGGL(k_stencil_break, dim3(2, 1), dim3(256), 0, s, P);
     }
-    if (ctx->select_part) {
-        hipLaunchKernelGGL((k_select_part<u64m, SP_LINES, SP_MAXWIN>), dim3(1, 1), dim3(64 * SP_LINES), 0, s, P, 1);
-        hipLaunchKernelGGL((k_select_part<u128m, SP_LINES_WIDE, SP_MAXWIN_WIDE>), dim3(1, 1), dim3(64 * SP_LINES_WIDE), 0, s, P, 1);
-    }
+    hipLaunchKernelGGL((k_select_part<u64m, SP_LINES, SP_MAXWIN>), dim3(1, 1), dim3(64 * SP_LINES), 0, s, P, 1);
+    hipLaunchKernelGGL((k_select_part<u128m, SP_LINES_WIDE, SP_MAXWIN_WIDE>), dim3(1, 1), dim3(64 * SP_LINES_WIDE), 0, s, P, 1);
     // (direct mode: the workgroup finds its line done by k_select_part, or does it)
     hipLaunchKernelGGL(select_variant(ctx->sel_cap), dim3(1, 1), dim3(SELP_THREADS), select_lds_bytes(ctx->sel_cap), s, P, -1);
     MML_HIP(hipGetLastError());
@@ -4259,15 +4242,11 @@ int mml_launch_detect_line(mml_ctx* ctx, int n, uint16_t* d_final) {
 
 int mml_feature_init(mml_ctx* ctx) {
     {
-        const char* e = getenv("MML_SELECT_PART");  // measurement switch: 0 = every line through k_select
-        ctx->select_part = !(e && atoi(e) == 0);
-    }
-    {
         // one-pass bucketing: ring layouts whose block tables fit (lines as lanes of one wavefront, <= 16 blocks per sensor);
-        // dense layouts (128 rings, 262 k points) keep the three staged passes.  MML_ASSIGN_ONEPASS=0: measurement switch
-        const char* e = getenv("MML_ASSIGN_ONEPASS");
+        // dense layouts (128 rings, 262 k points) keep the three staged passes.  (ctx->onepass_wanted false, $MML_ASSIGN_ONEPASS=0:
+        // the staged passes everywhere)
         const int nbv = (ctx->NV + MML_OP_BLK - 1) / MML_OP_BLK, nbl = (ctx->NL + MML_OP_BLK - 1) / MML_OP_BLK;
-        ctx->onepass = !(e && atoi(e) == 0) && ctx->cfg.n_rings >= 1 && ctx->cfg.n_rings <= OP_MAXKEYS && ctx->cfg.n_livox_lines <= OP_MAXKEYS &&
+        ctx->onepass = ctx->onepass_wanted && ctx->cfg.n_rings >= 1 && ctx->cfg.n_rings <= OP_MAXKEYS && ctx->cfg.n_livox_lines <= OP_MAXKEYS &&
                        ctx->L <= 64 && nbv <= MML_SEG_MAX && nbl <= MML_SEG_MAX && nbv * ctx->cfg.n_rings <= MML_SEG_FLAT &&
                        nbl * ctx->cfg.n_livox_lines <= MML_SEG_FLAT;
     }

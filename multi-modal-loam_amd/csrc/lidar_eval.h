@@ -381,32 +381,12 @@ __device__ __forceinline__ double lane_xor_f64(double v, int lane) {
     return __hiloint2double((int)hi, (int)lo);
 }
 
-#ifdef MML_REDUCE_DPP
-template <int C, int O>
-__device__ __forceinline__ void halve_step(double* v, int lane, int& idx) {
-    const bool up = (lane & O) != 0;
-#pragma unroll
-    for (int j = 0; j < C; ++j) {
-        const double keep = up ? v[j + C] : v[j], send = up ? v[j] : v[j + C];
-        v[j] = keep + lane_xor_f64<O>(send, lane);
-    }
-    idx += up ? C : 0;
-}
-#endif
 __device__ void block_reduce28(double* acc, double* s_part /*SOLVE_WAVES*28*/, double* out) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double v[32];
 #pragma unroll
     for (int k = 0; k < 32; ++k) v[k] = k < 28 ? acc[k] : 0.0;
     int idx = 0;  // which of the 32 sums this lane ends up holding
-#ifdef MML_REDUCE_DPP
-    halve_step<16, 32>(v, lane, idx);
-    halve_step<8, 16>(v, lane, idx);
-    halve_step<4, 8>(v, lane, idx);
-    halve_step<2, 4>(v, lane, idx);
-    halve_step<1, 2>(v, lane, idx);
-    const double tot = v[0] + lane_xor_f64<1>(v[0], lane);
-#else
 #pragma unroll
     for (int c = 16, o = 32; c >= 1; c >>= 1, o >>= 1) {
         const bool up = (lane & o) != 0;
@@ -418,7 +398,6 @@ __device__ void block_reduce28(double* acc, double* s_part /*SOLVE_WAVES*28*/, d
         idx += up ? c : 0;
     }
     const double tot = v[0] + shfl_xor_f64(v[0], 1);
-#endif
     if (!(lane & 1) && idx < 28) s_part[wave * 28 + idx] = tot;
     __syncthreads();
     if (threadIdx.x < 28) {

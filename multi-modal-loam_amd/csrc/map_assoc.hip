@@ -623,7 +623,7 @@ struct AssocParams {
     double thres_d;  // gate, compared as in the reference: (double)d2[4] < thres_dist
     int map_m[2];
     int count;
-    int fresh_all;  // small batches: every feature goes to the 16-lane search of k_associate_hard from ring 0
+    int fresh_all;  // small batches: every feature goes to the 64- / 32-lane search of k_associate_hard from ring 0
     const int* work_off;
     int* hard_count;   // queue of features whose 5-NN search goes beyond ring 1
     int4* hard_list;
@@ -994,10 +994,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MML_AW_FIT)
         k.key[2] = knn_key(d5, r0.z);
         k.key[3] = knn_key(d5, r0.w);
         k.key[4] = knn_key(d5, r1.x);
-        bool ok = (double)d5 < P.thres_d;  // :201,285 / :631,705
-#ifdef MML_EXP_NOFIT
-        ok = false;
-#endif
+        const bool ok = (double)d5 < P.thres_d;  // :201,285 / :631,705
         const bool stored = fit_and_store(P, kind, b, i, f, T, sx, sy, sz, ok, k, stage == 0 ? P.gmap_orig[kind] : P.map_orig[kind]);
         if (!stored) {
             if (stage == 0 && P.map_m[kind] > 20) {
@@ -1016,12 +1013,12 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MML_AW_FIT)
 // Queue entry word: bit 0 stage (0 cube cloud, 1 local map), bits 1..14 cube, bit 30 HARD_REDO "search again in the
 // local map".
 
-// Far queries, search only: one 16-lane group per queued feature, the lanes split the rows of every shell and merge
+// Far queries, search only: one group of SPAN lanes per queued feature, the lanes split the rows of every shell and merge
 // their private top-5 lists with shuffles.  The result goes back to hard_knn; the model fit runs in k_associate_fit with
-// one LANE per feature -- inside this kernel it would run on one lane in sixteen.
+// one LANE per feature -- inside this kernel it would run on one lane in SPAN.
 // round 0: every queued feature, continuing after ring 1 of the stage it was queued in.
 // round 1: the features whose cube-stage fit failed (HARD_REDO), local map from ring 0 (:283 / :702).
-// SPAN = lanes that share one query (they split the rows of every shell): 16 for batches -- many queries, throughput --, 64 for
+// SPAN = lanes that share one query (they split the rows of every shell): 4 for batches -- many queries, throughput --, 64 / 32 for
 // the live path's handful of scans, where the kernel lasts as long as its slowest query and a far query walks up to 169 rows a shell.
 template <int SPAN>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MML_AW_HARD))) void k_associate_hard(AssocParams P, int round) {
@@ -1463,8 +1460,7 @@ int mml_launch_associate(mml_ctx* ctx, int first, int count, const double* d_Twl
     P.hard_list = ctx->hard_list + (size_t)first * ctx->MF * 2;
     P.hard_knn = ctx->hard_knn + (size_t)first * ctx->MF * 2 * 10;
     P.count = count;
-    static const bool no_group = getenv("MML_NO_GROUP_SEARCH") != nullptr;  // A/B switch for measurements
-    P.fresh_all = (count <= 8 && ctx->assoc_group_search && !no_group) ? 1 : 0;
+    P.fresh_all = count <= 8 ? 1 : 0;
     int* work_off = ctx->work_off + 2 * (size_t)first + ctx->cur;
     P.work_off = work_off;
     {
@@ -1484,25 +1480,14 @@ int mml_launch_associate(mml_ctx* ctx, int first, int count, const double* d_Twl
         // lanes per far query of a batch: FOUR.  A batch has tens of thousands of far queries -- throughput, not the slowest query,
         // is what its kernel lasts -- and the lanes of a group split the (y, z) rows of a shell: 25 rows at ring 2 leave a 16-lane
         // group's second turn half empty.  Per 1024 scans (configs[1] / configs[3]): 64 lanes 0.331, 32: 0.224, 16: 0.164 / 0.118,
-        // 8: 0.153, 4: 0.147 / 0.113, 2: 0.142 / 0.153, 1: 0.185 ms ($MML_HARD_SPAN: measurement switch).
-        static int span_batch = -1;
-        if (span_batch < 0) span_batch = getenv("MML_HARD_SPAN") ? atoi(getenv("MML_HARD_SPAN")) : 4;
-        const int span = !P.fresh_all ? span_batch : (count <= 4 ? 64 : 32);
+        // 8: 0.153, 4: 0.147 / 0.113, 2: 0.142 / 0.153, 1: 0.185 ms.
         auto launch_hard = [&](int round) {
-            if (span == 64)
-                hipLaunchKernelGGL(k_associate_hard<64>, dim3(2048), dim3(256), 0, MML_STREAM(ctx), P, round);
-            else if (span == 32)
-                hipLaunchKernelGGL(k_associate_hard<32>, dim3(2048), dim3(256), 0, MML_STREAM(ctx), P, round);
-            else if (span == 8)
-                hipLaunchKernelGGL(k_associate_hard<8>, dim3(1024), dim3(256), 0, MML_STREAM(ctx), P, round);
-            else if (span == 4)
+            if (!P.fresh_all)
                 hipLaunchKernelGGL(k_associate_hard<4>, dim3(1024), dim3(256), 0, MML_STREAM(ctx), P, round);
-            else if (span == 2)
-                hipLaunchKernelGGL(k_associate_hard<2>, dim3(1024), dim3(256), 0, MML_STREAM(ctx), P, round);
-            else if (span == 1)
-                hipLaunchKernelGGL(k_associate_hard<1>, dim3(1024), dim3(256), 0, MML_STREAM(ctx), P, round);
+            else if (count <= 4)
+                hipLaunchKernelGGL(k_associate_hard<64>, dim3(2048), dim3(256), 0, MML_STREAM(ctx), P, round);
             else
-                hipLaunchKernelGGL(k_associate_hard<16>, dim3(1024), dim3(256), 0, MML_STREAM(ctx), P, round);
+                hipLaunchKernelGGL(k_associate_hard<32>, dim3(2048), dim3(256), 0, MML_STREAM(ctx), P, round);
         };
         launch_hard(0);
         hipLaunchKernelGGL(k_associate_fit, dim3(512), dim3(128), 0, MML_STREAM(ctx), P, 0);

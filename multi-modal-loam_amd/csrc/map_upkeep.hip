@@ -203,10 +203,6 @@ int voxel_filter_device(mml_ctx* ctx, const float4* pts, int m, float leaf, floa
 }  // namespace
 
 namespace {
-__global__ void k_gather_list(const float4* pts, const unsigned* list, int n, float4* out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = pts[list[i]];
-}
 int ensure_vox_scratch(mml_ctx* ctx, size_t pts) {
     if (pts <= ctx->vox_cap) return MML_OK;
     MML_HIP(hipStreamSynchronize(MML_STREAM(ctx)));

@@ -76,8 +76,6 @@ struct mml_ctx {
     void* wstate = nullptr;
     double* wrec = nullptr;
     double* waux = nullptr;
-    bool window_frame_parallel = true;
-    bool assoc_group_search = true;  // mml_associate on <= 8 slots: 16 lanes per feature from ring 0 (map_assoc.hip)
     struct WinGraph {  // captured launch chain of one frame-parallel window solve
         int first, count, W, max_iters, fixed;
         double huber, w_tan;
@@ -88,6 +86,11 @@ struct mml_ctx {
     };
     std::vector<WinGraph> win_graphs;
     int device = 0;
+    // launch settings, read once by mml_create (capi.hip read_settings): the device's CU count and the environment switches
+    int cus = 0;                 // multiProcessorCount of `device`
+    bool onepass_wanted = true;  // $MML_ASSIGN_ONEPASS=0: false (mml_feature_init still decides `onepass` from the layout)
+    bool solve_wide = true;      // $MML_SOLVE_WIDE=0: false, the live path's one-frame solve through k_solve<true>
+    bool use_graph = true;       // $MML_NO_GRAPH: false, the window solve's chain launched kernel by kernel
     // `lanes`: independent HIP streams.  Entry points enqueue on lane `cur` (0 unless mml_step is pipelining
     // sub-batches); per-call scratch is sliced by slot index so lanes never share a byte.
     static constexpr int MAX_LANES = 8;
@@ -104,7 +107,6 @@ struct mml_ctx {
     std::vector<hipEvent_t> upload_event_pool;
     int n_lanes = 1;
     int cur = 0;
-    bool lanes_enabled = true;
     std::string err;
 
     int B = 0, NV = 0, NL = 0, NT = 0, L = 0, MF = 0;
@@ -158,7 +160,6 @@ struct mml_ctx {
     int* queue_off = nullptr;       // 2 (B + MAX_LANES + 1): per launch the offsets of the slots' redo / break-point queues in their concatenation
     unsigned* redo_queue = nullptr; // B * NT: points k_stencil left to k_stencil_redo
     uint8_t* sel_done = nullptr;       // B * L: lines finished by k_select_part
-    bool select_part = true;
     int* sel_list = nullptr;           // 2 * B * L * 2 ints: (slot, line) lists of the lines left to k_select (rings | Livox lines)
     int* sel_list_cnt = nullptr;       // 2 B ints
     unsigned char* st_exit = nullptr;  // B * (NT / 256 + L + 8): k_stencil segment mode, exit offsets of the stride walk per tile

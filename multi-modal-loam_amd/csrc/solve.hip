@@ -56,7 +56,6 @@ struct SolveParams {
     double* result;         // per problem MML_SOLVE_RESULT doubles, or nullptr: x (6 * window <= 48 ... window 1 only), the two stack
                             // sizes of slot b0, the 16 association statistics of slot b0
     const double* stats;    // assoc_stats (16 doubles per slot) or nullptr
-    int pairs;              // k_solve<true>: two plane factors of a thread side by side (measurement switch $MML_SOLVE_PAIRS=0: off)
 };
 
 // Trust-region state kept in LDS, manipulated by lane 0 (restates ceres 2.1.0 trust_region_minimizer.cc +
@@ -1074,7 +1073,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(SolveParams P) {
     } else {
         if (tid < 6 * W) S.x[tid] = S.x_init[tid] = P.x[(size_t)b0 * 6 + tid];
     }
-    const bool pairs = SMALL && P.pairs && P.w_tan == 0.0;  // (uniform)
+    const bool pairs = SMALL && P.w_tan == 0.0;  // (uniform)
     __syncthreads();
 
     double acc[28];
@@ -1130,11 +1129,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(SolveParams P) {
         // lane 0 owns the trust-region state between the barriers; every other lane only reads it after one
         // lane 0 (first wavefront for W = 1) owns the trust-region state between the barriers
         if (W == 1) {
-#ifdef MML_BATCH_PROPOSE_REGS
-            if (tid < 64) tr_propose_w1_regs(S, s_work, P.max_iters, tid);
-#else
             if (tid < 64) tr_propose_w1_wave(S, s_work, P.max_iters);
-#endif
         } else if (tid == 0) {
             tr_propose(S, W, P.max_iters);
         }
@@ -1187,17 +1182,17 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(SolveParams P) {
 
 // k_solve<true> for one-frame problems with one-row plane factors (the live path's only setting), on all four SIMDs of the problem's
 // CU: 4 x 128 threads, the factor passes through eval_frame_wide (lidar_eval.h: rows formed by 512 threads, sums and reduction tree of
-// the 128-thread pass -- bit-identical), the trust-region code between the passes on the first wavefront as in k_solve.  123 KB of
-// LDS for the rows of a round: one workgroup per CU, which is what these launches (at most one problem per CU) have anyway.
+// the 128-thread pass -- bit-identical), the trust-region code between the passes on the first wavefront as in k_solve.  About 148 KiB
+// of LDS (110 592 B for the rows of a round, 32 768 B for the sums saved between rounds, ~8 KB for the trust-region state and the
+// reduction scratch): one workgroup per CU, which is what these launches (at most one problem per CU) have anyway.
 __global__ __launch_bounds__(WIDE_THREADS) void k_solve_wide(SolveParams P) {
     __shared__ TRState S;
     __shared__ double s_part[SOLVE_WAVES * 28];
     __shared__ double s_work[92];
-#ifdef MML_WIDE_PROPOSE_WAVE
-    __shared__ double s_wd[TRW_DOUBLES];
-#endif
     __shared__ double s_rows[WIDE_ROW_LDS];
     __shared__ double s_vsave[WIDE_SAVE_LDS];
+    static_assert(sizeof(S) + sizeof(s_part) + sizeof(s_work) + sizeof(s_rows) + sizeof(s_vsave) <= 160 * 1024,
+                  "k_solve_wide: static LDS beyond gfx950's 160 KiB per workgroup");
     const int prob = blockIdx.x;
     const int b0 = P.first + prob;
     const int tid = threadIdx.x;
@@ -1256,11 +1251,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void k_solve_wide(SolveParams P) {
         int lane_op = tid;
         asm volatile("" : "+v"(lane_op));
         SV_MARK(0);  // (everything outside the two trust-region phases: set-up, factor passes, the loop's barriers)
-#ifdef MML_WIDE_PROPOSE_WAVE
-        if (tid < 64) tr_propose_w1_wave(S, s_work, P.max_iters, lane_op);
-#else
         if (tid < 64) tr_propose_w1_regs(S, s_work, P.max_iters, lane_op);
-#endif
         __syncthreads();
         SV_MARK(1);  // trust-region proposal (first wavefront) + barrier
         go = S.go;
@@ -1272,11 +1263,7 @@ __global__ __launch_bounds__(WIDE_THREADS) void k_solve_wide(SolveParams P) {
             eval_frame_wide(lf, nlf, pf, npf, pose, P.huber, s_rows, s_vsave, s_part, S.recc);
             asm volatile("" : "+v"(lane_op));
             SV_MARK(0);
-#ifdef MML_WIDE_PROPOSE_WAVE
-            if (tid < 64) tr_decide_wave(S, s_wd, 1, P.fixed, lane_op);
-#else
             if (tid < 64) tr_decide_w1_regs(S, P.fixed, lane_op);
-#endif
         }
         __syncthreads();
         SV_MARK(4);  // accept / reject (first wavefront) + barrier
@@ -1582,9 +1569,8 @@ static int launch_solve_frame_parallel(mml_ctx* ctx, int first, int count, int W
     MmlStageScope t(ctx, "solve");
     // The chain is launch-bound (a dozen kernels of ~10 us that depend on each other): it is captured once per
     // (slot range, window, options, stream) into a HIP graph and replayed, which removes the per-launch gaps.  Every
-    // pointer in it is a fixed function of the key.
-    static const bool use_graph = getenv("MML_NO_GRAPH") == nullptr;
-    if (use_graph) {
+    // pointer in it is a fixed function of the key.  (ctx->use_graph false, $MML_NO_GRAPH: the kernels are launched one by one)
+    if (ctx->use_graph) {
         mml_ctx::WinGraph* g = nullptr;
         for (auto& c : ctx->win_graphs)
             if (c.first == first && c.count == count && c.W == W && c.max_iters == opts.max_num_iterations &&
@@ -1661,7 +1647,7 @@ int mml_launch_solve(mml_ctx* ctx, int first, int count, int window, const doubl
                      bool want_trace, const double* d_x_in, double* d_result) {
     MML_REQUIRE(window >= 1 && window <= MAXW && count % window == 0, MML_ERR_INVALID,
                 "window must be in [1,8] and divide count");
-    if (window > 1 && !want_trace && ctx->window_frame_parallel) return launch_solve_frame_parallel(ctx, first, count, window, d_Tbl, opts, false);
+    if (window > 1 && !want_trace) return launch_solve_frame_parallel(ctx, first, count, window, d_Tbl, opts, false);
     SolveParams P;
     P.first = first;
     P.B = ctx->B;
@@ -1683,19 +1669,11 @@ int mml_launch_solve(mml_ctx* ctx, int first, int count, int window, const doubl
     P.stats = ctx->assoc_stats;
     MML_REQUIRE((!d_x_in && !d_result) || window == 1, MML_ERR_INVALID, "packed start poses / result records: one-frame problems only");
     MmlStageScope t(ctx, "solve");
-    static int n_cus = -1, pairs_on = 1;
-    if (n_cus < 0) {
-        const char* e = getenv("MML_SOLVE_PAIRS");
-        pairs_on = (e && atoi(e) == 0) ? 0 : 1;
-        hipDeviceProp_t prop;
-        n_cus = hipGetDeviceProperties(&prop, ctx->device) == hipSuccess ? prop.multiProcessorCount : 64;
-    }
-    const bool small = count / window <= n_cus;  // at most one problem per CU
+    const bool small = count / window <= ctx->cus;  // at most one problem per CU
     MML_REQUIRE((!d_x_in && !d_result) || small, MML_ERR_INVALID, "packed start poses / result records: small launches only");
-    P.pairs = pairs_on;
-    // one-frame problems with one-row plane factors (the live path): the 512-thread form ($MML_SOLVE_WIDE=0: measurement switch)
-    static const bool wide_on = !(getenv("MML_SOLVE_WIDE") && atoi(getenv("MML_SOLVE_WIDE")) == 0);
-    if (small && wide_on && window == 1 && opts.plan_weight_tan == 0.0)
+    // one-frame problems with one-row plane factors (the live path): the 512-thread form (ctx->solve_wide false, $MML_SOLVE_WIDE=0:
+    // k_solve<true>, the same values bit for bit)
+    if (small && ctx->solve_wide && window == 1 && opts.plan_weight_tan == 0.0)
         hipLaunchKernelGGL(k_solve_wide, dim3(count), dim3(WIDE_THREADS), 0, MML_STREAM(ctx), P);
     else if (small)
         hipLaunchKernelGGL(k_solve<true>, dim3(count / window), dim3(SOLVE_THREADS), 0, MML_STREAM(ctx), P);

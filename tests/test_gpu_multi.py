@@ -221,3 +221,31 @@ def test_broadcasts_from_another_rank_on_one_device(M, O, scene):
     finally:
         for c in ctxs:
             c.close()
+
+
+def test_window_solve_graph_replay_equals_direct_launches(M, O, scene):
+    """The frame-parallel window solve (window 8, no trace) captures its chain of k_window_round launches into a graph and replays
+    it; a context created with MML_NO_GRAPH=1 launches the same kernels one by one.  Called twice on each context (the second call
+    of the default context replays the cached graph): poses and summaries equal bit for bit."""
+    import os
+    key = lambda q: (q.iterations, q.successful, q.termination, q.initial_cost, q.final_cost)
+    out = {}
+    for no_graph in (False, True):
+        if no_graph:
+            os.environ["MML_NO_GRAPH"] = "1"
+        try:
+            c, lfs, pfs, x0, T_bl = _window8(M, O, scene)
+        finally:
+            os.environ.pop("MML_NO_GRAPH", None)
+        try:
+            runs = []
+            for fixed, huber, w_tan in ((False, 0.0, 3e-4), (True, 0.1 / 1.5e-3, 0.0)):
+                for rep in range(2):
+                    xs, ss, _ = c.solve(0, W8, x0, T_bl, window=W8, max_iters=10, fixed=fixed, huber=huber, w_tan=w_tan)
+                    runs.append((xs, [key(q) for q in ss]))
+            out[no_graph] = runs
+        finally:
+            c.close()
+    for (xg, sg), (xd, sd) in zip(out[False], out[True]):
+        assert np.array_equal(xg, xd), np.abs(xg - xd).max()
+        assert sg == sd

@@ -180,3 +180,39 @@ def test_wide_solve_long_factor_lists_equal_batch_kernel(M, O, scene):
                     assert np.abs(x1 - xo).max() < 1e-9 and s1[0].iterations == so["iterations"], (ci, huber, fixed, np.abs(x1 - xo).max())
     finally:
         c.close()
+
+
+def test_live_step_wide_solve_equals_paired_small_kernel(M, synth, scene):
+    """The live path's one-frame solve has two forms: k_solve_wide (the default) and k_solve<true> with two plane rows of a thread
+    side by side (a context created with MML_SOLVE_WIDE=0).  One-slot and 17-slot mml_step calls on the twelve batch scans: poses
+    and all ten digest words bit-identical between a default context and one with the switch."""
+    import os
+    B = 17
+    cases = batch_cases(synth)
+    dR = np.stack([cases[s % 12]["dR"].reshape(9) for s in range(B)])
+    dt = np.stack([cases[s % 12]["dt"] for s in range(B)])
+    x0 = np.stack([cases[s % 12]["x0"] for s in range(B)])
+    out = {}
+    for wide in ("1", "0"):
+        os.environ["MML_SOLVE_WIDE"] = wide
+        try:
+            c = M.Context(max_scans=B)
+        finally:
+            del os.environ["MML_SOLVE_WIDE"]
+        try:
+            c.map_set_local(0, scene["corner_map"])
+            c.map_set_local(1, scene["surf_map"])
+            for s in range(B):
+                c.scan_upload(s, cases[s % 12]["velo"], cases[s % 12]["livox"])
+            xb = c.step(0, B, dR, dt, np.eye(4), 25.0, 10, x0)
+            dgb = c.slot_digest(0, B)
+            ones = [(c.step(s, 1, dR[s:s + 1], dt[s:s + 1], np.eye(4), 25.0, 10, x0[s:s + 1])[0], c.slot_digest(s, 1)[0])
+                    for s in (0, 6, 11, B - 1)]
+            out[wide] = (xb, dgb, ones)
+        finally:
+            c.close()
+    (xw, dw, ow), (xp, dp, op) = out["1"], out["0"]
+    assert np.array_equal(xw, xp), np.argwhere(xw != xp)[:5]
+    assert np.array_equal(dw, dp), [PIECES[w] for w in range(10) if not np.array_equal(dw[:, w], dp[:, w])]
+    for (a, da), (b, db) in zip(ow, op):
+        assert np.array_equal(a, b) and np.array_equal(da, db)

@@ -1,5 +1,6 @@
 """Phase clocks of the live path's solve (one slot per mml_step call; library built with -DMML_SV_TIMING=0):
-MML_SOLVE_WIDE=1 -> k_solve_wide's factor pass (rows / barrier wait / sums / tree), MML_SOLVE_WIDE=0 -> k_solve<true>'s phases.
+MML_SOLVE_WIDE=1 -> k_solve_wide's factor pass (rows / barrier wait / sums / tree), MML_SOLVE_WIDE=0 -> k_solve<true>'s phases
+(the library reads the switch when stage_probe creates its context).
   MML_LIB_PATH=multi-modal-loam_amd/libmmloam_hip_svt.so python tools/solve_wide_phases.py [reps]"""
 import ctypes as C
 import importlib
