@@ -551,6 +551,20 @@ int mml_extract_queue_counts(mml_ctx* ctx, int slot, int* redo, int* brk);
  * atan2f, the float overloads unionFeatureExtract.cpp:1136-1139,1159,1168 resolve to), evaluated on n host values on the
  * context's device.  out_atan2[i] = atan2f(y[i], x[i]), out_atan[i] = atanf(y[i]); either output may be NULL. */
 int mml_libm_f32(mml_ctx* ctx, const float* y, const float* x, long n, float* out_atan2, float* out_atan);
+/* Test hook: the device's own model-fit code (the __device__ functions the association and GICP kernels call) on n
+ * caller-supplied items, one lane per item, on the context's device.  Per item, by operation code:
+ *   MML_FIT_EIG3    in  6 doubles m00 m10 m11 m20 m21 m22 (lower triangle)
+ *                   out 12 doubles: eigenvalues ascending, then the eigenvectors of ev[0], ev[1], ev[2]
+ *   MML_FIT_QR      in  15 doubles, 5 x 3 row-major;  out 4 doubles: X[3] of the column-pivoted QR solve of A X = -1, rank
+ *   MML_FIT_LINE    in  15 floats, the 5 neighbours in search order
+ *                   out 13 doubles: accepted (0 / 1), centroid[3], ev[3], p1[3], p2[3] (the float values as stored)
+ *   MML_FIT_PLANE   in  18 floats, the 5 neighbours and the selected point
+ *                   out 11 doubles: accepted, X[3], pa pb pc pd (floats), proj[3]
+ *   MML_FIT_OPS_F64 in  2 doubles a b;  out 2 doubles sqrt(a), a / b
+ *   MML_FIT_OPS_F32 in  2 floats a b;   out 2 floats sqrtf(a), a / b
+ * p1 / p2 and proj of a rejected model are never computed and come back as 0.  Codes from 6 on are free. */
+enum { MML_FIT_EIG3 = 0, MML_FIT_QR = 1, MML_FIT_LINE = 2, MML_FIT_PLANE = 3, MML_FIT_OPS_F64 = 4, MML_FIT_OPS_F32 = 5 };
+int mml_model_fit5(mml_ctx* ctx, int op, const void* in, long n, void* out);
 /* How many 5-NN queries of the context's last association call (mml_associate / mml_step's association on the lane that ran
  * last) went beyond rings 0-1 of the grid into the far-query kernels (k_associate_hard): the share to watch when the map's density
  * and the configured cell edge do not fit each other. */

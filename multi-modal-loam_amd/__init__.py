@@ -637,6 +637,18 @@ class Context:
         self._ck(lib().mml_libm_f32(self._h, _p(y), _p(x), C.c_long(len(x)), _p(o2), _p(o1)))
         return o2, o1
 
+    _FIT_SHAPES = {0: (np.float64, 6, np.float64, 12), 1: (np.float64, 15, np.float64, 4), 2: (np.float32, 15, np.float64, 13),
+                   3: (np.float32, 18, np.float64, 11), 4: (np.float64, 2, np.float64, 2), 5: (np.float32, 2, np.float32, 2)}
+
+    def model_fit5(self, op, items):
+        """The device's line / plane model fit on caller-supplied items (mml_model_fit5, a test hook): op 0 eig3, 1 qr,
+        2 line model, 3 plane model, 4 / 5 double / float sqrt and division; layouts in include/mmloam_hip.h."""
+        ti, wi, to, wo = self._FIT_SHAPES[op]
+        a = np.ascontiguousarray(items, ti).reshape(-1, wi)
+        out = np.empty((len(a), wo), to)
+        self._ck(lib().mml_model_fit5(self._h, C.c_int(op), _p(a), C.c_long(len(a)), _p(out)))
+        return out
+
     def associate_far_count(self):
         """5-NN queries of the last association that went to the far-query kernels (summed over the stream lanes)."""
         n = C.c_int(0)

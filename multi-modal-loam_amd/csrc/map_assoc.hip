@@ -488,7 +488,8 @@ __device__ __forceinline__ void qr_step(Col5& ck, Col5& o1, Col5& o2, double& nu
     if (has2) downdate(o2, nu2, nd2);
 }
 
-__device__ void plane_fit5(const double (*Ain)[3], double* xout) {
+// rank_out (optional): nonzero_pivots, the rank Eigen's solve() uses.
+__device__ void plane_fit5(const double (*Ain)[3], double* xout, int* rank_out = nullptr) {
     Col5 c0, c1, c2;
 #pragma unroll
     for (int r = 0; r < 5; ++r) {
@@ -550,6 +551,7 @@ __device__ void plane_fit5(const double (*Ain)[3], double* xout) {
         qr_step<2>(c2, dmy1, dmy2, du1, dd1, du2, dd2, tau2, false, false);
     }
     xout[0] = xout[1] = xout[2] = 0;
+    if (rank_out) *rank_out = nonzero_pivots;
     if (nonzero_pivots == 0) return;
     double c[5] = {-1, -1, -1, -1, -1};
     // c = Q^T b : apply H_0, H_1, H_2 (only the first nonzero_pivots reflectors)
@@ -666,6 +668,100 @@ __device__ __forceinline__ int find_used_map(float x, float y, float z, const in
     return 5000;
 }
 
+// The line model of a14 from the 5 neighbours in search order: float centroid and covariance, double eigen-system, the
+// gate ev[2] > 3 * ev[1], and the tripod p1 / p2 = centroid +- 0.1 * (eigenvector of ev[2]) stored as floats.  Shared by
+// fit_and_store and the test hook mml_model_fit5; p1 / p2 are set only when the model is accepted.
+struct LineModel5 {
+    float cx, cy, cz;
+    double ev[3];
+    float p1[3], p2[3];
+};
+__device__ __forceinline__ bool line_model5(const float* nx, const float* ny, const float* nz, LineModel5& m) {
+    float cx = 0, cy = 0, cz = 0;
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+        cx += nx[j];
+        cy += ny[j];
+        cz += nz[j];
+    }
+    cx /= 5;
+    cy /= 5;
+    cz /= 5;
+    float a11 = 0, a12 = 0, a13 = 0, a22 = 0, a23 = 0, a33 = 0;
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+        float ax = nx[j] - cx, ay = ny[j] - cy, az = nz[j] - cz;
+        a11 += ax * ax;
+        a12 += ax * ay;
+        a13 += ax * az;
+        a22 += ay * ay;
+        a23 += ay * az;
+        a33 += az * az;
+    }
+    a11 /= 5;
+    a12 /= 5;
+    a13 /= 5;
+    a22 /= 5;
+    a23 /= 5;
+    a33 /= 5;
+    double ud[3];
+    eig3_sym(a11, a12, a22, a13, a23, a33, m.ev, ud);
+    m.cx = cx;
+    m.cy = cy;
+    m.cz = cz;
+    if (!(m.ev[2] > 3 * m.ev[1])) return false;
+    m.p1[0] = cx + 0.1 * ud[0];
+    m.p1[1] = cy + 0.1 * ud[1];
+    m.p1[2] = cz + 0.1 * ud[2];
+    m.p2[0] = cx - 0.1 * ud[0];
+    m.p2[1] = cy - 0.1 * ud[1];
+    m.p2[2] = cz - 0.1 * ud[2];
+    return true;
+}
+
+// The plane model of a15 from the 5 neighbours in search order and the selected point s: X of the QR solve, the
+// normalised float coefficients, the 0.2 m gate on every neighbour, and the projection of s (set only when accepted).
+struct PlaneModel5 {
+    double X[3];
+    float pa, pb, pc, pd;
+    double proj[3];
+};
+__device__ __forceinline__ bool plane_model5(const float* nx, const float* ny, const float* nz, float sx, float sy, float sz,
+                                             PlaneModel5& m) {
+    double A[5][3];
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+        A[j][0] = nx[j];
+        A[j][1] = ny[j];
+        A[j][2] = nz[j];
+    }
+    plane_fit5(A, m.X);
+    float pa = m.X[0], pb = m.X[1], pc = m.X[2], pd = 1;
+    float ps = sqrtf(pa * pa + pb * pb + pc * pc);
+    pa /= ps;
+    pb /= ps;
+    pc /= ps;
+    pd /= ps;
+    m.pa = pa;
+    m.pb = pb;
+    m.pc = pc;
+    m.pd = pd;
+    bool planeValid = true;
+#pragma unroll
+    for (int j = 0; j < 5; j++) {
+        if (fabs((double)(pa * nx[j] + pb * ny[j] + pc * nz[j] + pd)) > 0.2) {
+            planeValid = false;
+            break;
+        }
+    }
+    if (!planeValid) return false;
+    double dist = pa * sx + pb * sy + pc * sz + pd;  // float expression, :740-742
+    m.proj[0] = (double)sx - dist * (double)pa;
+    m.proj[1] = (double)sy - dist * (double)pb;
+    m.proj[2] = (double)sz - dist * (double)pc;
+    return true;
+}
+
 // returns true (and stores the factor) when the neighbourhood passes the gate and yields a model
 __device__ __forceinline__ bool fit_and_store(const AssocParams& P, int kind, int b, int i, const float4 f, const double* T,
                                               float sx, float sy, float sz, bool ok, const Knn5& k, const float4* mp) {
@@ -682,42 +778,9 @@ __device__ __forceinline__ bool fit_and_store(const AssocParams& P, int kind, in
                 ny[j] = q.y;
                 nz[j] = q.z;
             }
-            float cx = 0, cy = 0, cz = 0;
-#pragma unroll
-            for (int j = 0; j < 5; j++) {
-                cx += nx[j];
-                cy += ny[j];
-                cz += nz[j];
-            }
-            cx /= 5;
-            cy /= 5;
-            cz /= 5;
-            float a11 = 0, a12 = 0, a13 = 0, a22 = 0, a23 = 0, a33 = 0;
-#pragma unroll
-            for (int j = 0; j < 5; j++) {
-                float ax = nx[j] - cx, ay = ny[j] - cy, az = nz[j] - cz;
-                a11 += ax * ax;
-                a12 += ax * ay;
-                a13 += ax * az;
-                a22 += ay * ay;
-                a23 += ay * az;
-                a33 += az * az;
-            }
-            a11 /= 5;
-            a12 /= 5;
-            a13 /= 5;
-            a22 /= 5;
-            a23 /= 5;
-            a33 /= 5;
-            double ev[3], ud[3];
-            eig3_sym(a11, a12, a22, a13, a23, a33, ev, ud);
-            if (ev[2] > 3 * ev[1]) {
-                float x1 = cx + 0.1 * ud[0];
-                float y1 = cy + 0.1 * ud[1];
-                float z1 = cz + 0.1 * ud[2];
-                float x2 = cx - 0.1 * ud[0];
-                float y2 = cy - 0.1 * ud[1];
-                float z2 = cz - 0.1 * ud[2];
+            LineModel5 m;
+            if (line_model5(nx, ny, nz, m)) {
+                const float x1 = m.p1[0], y1 = m.p1[1], z1 = m.p1[2], x2 = m.p2[0], y2 = m.p2[1], z2 = m.p2[2];
                 out.ori[0] = f.x;
                 out.ori[1] = f.y;
                 out.ori[2] = f.z;
@@ -748,7 +811,6 @@ __device__ __forceinline__ bool fit_and_store(const AssocParams& P, int kind, in
         out.error = 0;
         out._pad = 0;
         if (ok) {
-            double A[5][3];
             float nx[5], ny[5], nz[5];
 #pragma unroll
             for (int j = 0; j < 5; j++) {
@@ -756,37 +818,18 @@ __device__ __forceinline__ bool fit_and_store(const AssocParams& P, int kind, in
                 nx[j] = q.x;
                 ny[j] = q.y;
                 nz[j] = q.z;
-                A[j][0] = q.x;
-                A[j][1] = q.y;
-                A[j][2] = q.z;
             }
-            double X[3];
-            plane_fit5(A, X);
-            float pa = X[0], pb = X[1], pc = X[2], pd = 1;
-            float ps = sqrtf(pa * pa + pb * pb + pc * pc);
-            pa /= ps;
-            pb /= ps;
-            pc /= ps;
-            pd /= ps;
-            bool planeValid = true;
-#pragma unroll
-            for (int j = 0; j < 5; j++) {
-                if (fabs((double)(pa * nx[j] + pb * ny[j] + pc * nz[j] + pd)) > 0.2) {
-                    planeValid = false;
-                    break;
-                }
-            }
-            if (planeValid) {
-                double dist = pa * sx + pb * sy + pc * sz + pd;  // float expression, :740-742
+            PlaneModel5 m;
+            if (plane_model5(nx, ny, nz, sx, sy, sz, m)) {
                 out.ori[0] = f.x;
                 out.ori[1] = f.y;
                 out.ori[2] = f.z;
-                out.omega[0] = pa;
-                out.omega[1] = pb;
-                out.omega[2] = pc;
-                out.proj[0] = (double)sx - dist * (double)pa;
-                out.proj[1] = (double)sy - dist * (double)pb;
-                out.proj[2] = (double)sz - dist * (double)pc;
+                out.omega[0] = m.pa;
+                out.omega[1] = m.pb;
+                out.omega[2] = m.pc;
+                out.proj[0] = m.proj[0];
+                out.proj[1] = m.proj[1];
+                out.proj[2] = m.proj[2];
                 double Px, Py, Pz;
                 tf_point(T, f.x, f.y, f.z, Px, Py, Pz);
                 double ex = Px - out.proj[0], ey = Py - out.proj[1], ez = Pz - out.proj[2];
@@ -796,6 +839,82 @@ __device__ __forceinline__ bool fit_and_store(const AssocParams& P, int kind, in
         }
         if (out.src >= 0) P.pf[(size_t)b * P.MF + i] = out;
         return out.src >= 0;
+    }
+}
+
+// ---- test hook: the model fit above on caller-supplied inputs, one lane per item (mml_model_fit5) ----
+__global__ __launch_bounds__(128) void k_model_fit5(int op, const void* in_, long n, void* out_) {
+    const long i = (long)blockIdx.x * 128 + threadIdx.x;
+    if (i >= n) return;
+    if (op == MML_FIT_EIG3) {
+        const double* a = (const double*)in_ + 6 * i;
+        double* o = (double*)out_ + 12 * i;
+        double ev[3], v0[3], v1[3], v2[3];
+        eig3_sym(a[0], a[1], a[2], a[3], a[4], a[5], ev, v2, v0, v1);
+        for (int r = 0; r < 3; ++r) {
+            o[r] = ev[r];
+            o[3 + r] = v0[r];
+            o[6 + r] = v1[r];
+            o[9 + r] = v2[r];
+        }
+    } else if (op == MML_FIT_QR) {
+        const double* a = (const double*)in_ + 15 * i;
+        double* o = (double*)out_ + 4 * i;
+        double A[5][3], X[3];
+        int rank = 0;
+        for (int r = 0; r < 5; ++r)
+            for (int c = 0; c < 3; ++c) A[r][c] = a[3 * r + c];
+        plane_fit5(A, X, &rank);
+        o[0] = X[0];
+        o[1] = X[1];
+        o[2] = X[2];
+        o[3] = rank;
+    } else if (op == MML_FIT_LINE || op == MML_FIT_PLANE) {
+        const int w = op == MML_FIT_LINE ? 15 : 18;
+        const float* a = (const float*)in_ + w * i;
+        float nx[5], ny[5], nz[5];
+        for (int j = 0; j < 5; j++) {
+            nx[j] = a[3 * j];
+            ny[j] = a[3 * j + 1];
+            nz[j] = a[3 * j + 2];
+        }
+        if (op == MML_FIT_LINE) {
+            double* o = (double*)out_ + 13 * i;
+            LineModel5 m;
+            const bool ok = line_model5(nx, ny, nz, m);
+            o[0] = ok ? 1 : 0;
+            o[1] = m.cx;
+            o[2] = m.cy;
+            o[3] = m.cz;
+            for (int r = 0; r < 3; ++r) {
+                o[4 + r] = m.ev[r];
+                o[7 + r] = ok ? m.p1[r] : 0.f;
+                o[10 + r] = ok ? m.p2[r] : 0.f;
+            }
+        } else {
+            double* o = (double*)out_ + 11 * i;
+            PlaneModel5 m;
+            const bool ok = plane_model5(nx, ny, nz, a[15], a[16], a[17], m);
+            o[0] = ok ? 1 : 0;
+            o[1] = m.X[0];
+            o[2] = m.X[1];
+            o[3] = m.X[2];
+            o[4] = m.pa;
+            o[5] = m.pb;
+            o[6] = m.pc;
+            o[7] = m.pd;
+            for (int r = 0; r < 3; ++r) o[8 + r] = ok ? m.proj[r] : 0.0;
+        }
+    } else if (op == MML_FIT_OPS_F64) {
+        const double* a = (const double*)in_ + 2 * i;
+        double* o = (double*)out_ + 2 * i;
+        o[0] = sqrt(a[0]);
+        o[1] = a[0] / a[1];
+    } else {
+        const float* a = (const float*)in_ + 2 * i;
+        float* o = (float*)out_ + 2 * i;
+        o[0] = sqrtf(a[0]);
+        o[1] = a[0] / a[1];
     }
 }
 
@@ -1184,6 +1303,28 @@ __global__ __launch_bounds__(256) void k_assoc_stats(int first, int B, int MF, c
 }
 
 }  // namespace
+
+extern "C" int mml_model_fit5(mml_ctx* ctx, int op, const void* in, long n, void* out) {
+    static const size_t in_bytes[6] = {6 * sizeof(double), 15 * sizeof(double), 15 * sizeof(float),
+                                       18 * sizeof(float), 2 * sizeof(double),  2 * sizeof(float)};
+    static const size_t out_bytes[6] = {12 * sizeof(double), 4 * sizeof(double), 13 * sizeof(double),
+                                        11 * sizeof(double), 2 * sizeof(double), 2 * sizeof(float)};
+    if (!ctx || !in || !out || n < 0 || op < 0 || op > MML_FIT_OPS_F32 || n > (long)1 << 26) return MML_ERR_INVALID;
+    if (n == 0) return MML_OK;
+    int rc = mml_sync_all(ctx);
+    if (rc != MML_OK) return rc;
+    void *d_in = nullptr, *d_out = nullptr;
+    bool ok = hipMalloc(&d_in, in_bytes[op] * (size_t)n) == hipSuccess && hipMalloc(&d_out, out_bytes[op] * (size_t)n) == hipSuccess;
+    ok = ok && hipMemcpy(d_in, in, in_bytes[op] * (size_t)n, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        hipLaunchKernelGGL(k_model_fit5, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, MML_STREAM(ctx), op, (const void*)d_in, n, d_out);
+        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(MML_STREAM(ctx)) == hipSuccess;
+    }
+    ok = ok && hipMemcpy(out, d_out, out_bytes[op] * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess;
+    if (d_in) (void)hipFree(d_in);
+    if (d_out) (void)hipFree(d_out);
+    return ok ? MML_OK : MML_ERR_HIP;
+}
 
 // Builds the radix-sorted grid `g` over m points (host xyz), keeping the unsorted cloud in `orig`.
 static int build_grid_into(mml_ctx* ctx, MmlGrid& g, float4* orig, const float* h_xyz, int m, float cell,

@@ -468,7 +468,8 @@ static double line_error(const Vec3& po, const Vec3& a, const Vec3& b, const dou
 
 // a14  line model of processPointToLine (Estimator.cpp:204-277 for the cube cloud, :288-358 for the local cloud:
 // the two copies are arithmetically identical).  nb: coordinates of the 5 neighbours in search order.
-static bool fit_line(const float* ori, const float nb[5][3], const double* T, mmlo_line_factor* f) {
+// mid (optional): the intermediates of the model, centroid[3] and ev[3], for mmlo_model_fit5.
+static bool fit_line(const float* ori, const float nb[5][3], const double* T, mmlo_line_factor* f, double* mid = nullptr) {
     float cx = 0, cy = 0, cz = 0;
     for (int j = 0; j < 5; j++) {
         cx += nb[j][0];
@@ -500,6 +501,14 @@ static bool fit_line(const float* ori, const float nb[5][3], const double* T, mm
     double ev[3], V[9];
     eig3_sym(A, ev, V);
     double ud[3] = {V[2], V[5], V[8]};  // eigenvectors().col(2)
+    if (mid) {
+        mid[0] = cx;
+        mid[1] = cy;
+        mid[2] = cz;
+        mid[3] = ev[0];
+        mid[4] = ev[1];
+        mid[5] = ev[2];
+    }
     if (!(ev[2] > 3 * ev[1])) return false;
     float x1 = cx + 0.1 * ud[0];
     float y1 = cy + 0.1 * ud[1];
@@ -521,7 +530,9 @@ static bool fit_line(const float* ori, const float nb[5][3], const double* T, mm
 }
 
 // a15  plane model of processPointToPlanVec (Estimator.cpp:634-693 cube cloud, :708-764 local cloud).
-static bool fit_plane(const float* ori, const float* sel, const float nb[5][3], const double* T, mmlo_plane_factor* f) {
+// mid (optional): X[3] of the QR solve and the normalised pa, pb, pc, pd as floats, for mmlo_model_fit5.
+static bool fit_plane(const float* ori, const float* sel, const float nb[5][3], const double* T, mmlo_plane_factor* f,
+                      double* mid = nullptr) {
     double A[15];
     for (int j = 0; j < 5; j++) {
         A[3 * j] = nb[j][0];
@@ -539,6 +550,15 @@ static bool fit_plane(const float* ori, const float* sel, const float nb[5][3], 
     pb /= ps;
     pc /= ps;
     pd /= ps;
+    if (mid) {
+        mid[0] = X[0];
+        mid[1] = X[1];
+        mid[2] = X[2];
+        mid[3] = pa;
+        mid[4] = pb;
+        mid[5] = pc;
+        mid[6] = pd;
+    }
     for (int j = 0; j < 5; j++) {
         if (std::fabs(pa * nb[j][0] + pb * nb[j][1] + pc * nb[j][2] + pd) > 0.2) return false;
     }
@@ -1399,3 +1419,81 @@ extern "C" void mmlo_so3_log(const double* q, double* phi) {
 }
 extern "C" void mmlo_eig3_sym(const double* A, double* evals, double* evecs) { eig3_sym(A, evals, evecs); }
 extern "C" void mmlo_plane_fit5(const double* A, double* x) { plane_fit5(A, x); }
+
+// The model fit over arrays, one item after the other: the layouts of mml_model_fit5 (include/mmloam_hip.h), so that
+// the device's fit can be compared with this one item by item.  Fields of a rejected model that the reference never
+// computes (p1 / p2, proj) are 0.
+extern "C" int mmlo_model_fit5(int op, const void* in_, long n, void* out_) {
+    if (!in_ || !out_ || n < 0) return -1;
+    static const double I4[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
+    const float zero3[3] = {0, 0, 0};
+    if (op == 0) {
+        const double* in = (const double*)in_;
+        double* out = (double*)out_;
+        for (long i = 0; i < n; ++i) {
+            const double* m = in + 6 * i;
+            const double A[9] = {m[0], m[1], m[3], m[1], m[2], m[4], m[3], m[4], m[5]};
+            double V[9];
+            double* o = out + 12 * i;
+            eig3_sym(A, o, V);
+            for (int k = 0; k < 3; ++k)
+                for (int r = 0; r < 3; ++r) o[3 + 3 * k + r] = V[3 * r + k];
+        }
+    } else if (op == 1) {
+        const double* in = (const double*)in_;
+        double* out = (double*)out_;
+        for (long i = 0; i < n; ++i) {
+            int rank = 0;
+            plane_fit5(in + 15 * i, out + 4 * i, &rank);
+            out[4 * i + 3] = rank;
+        }
+    } else if (op == 2) {
+        const float* in = (const float*)in_;
+        double* out = (double*)out_;
+        for (long i = 0; i < n; ++i) {
+            float nb[5][3];
+            memcpy(nb, in + 15 * i, sizeof(nb));
+            mmlo_line_factor f;
+            double* o = out + 13 * i;
+            for (int k = 0; k < 13; ++k) o[k] = 0;
+            const bool ok = fit_line(zero3, nb, I4, &f, o + 1);
+            o[0] = ok ? 1 : 0;
+            if (ok)
+                for (int k = 0; k < 3; ++k) {
+                    o[7 + k] = f.p1[k];
+                    o[10 + k] = f.p2[k];
+                }
+        }
+    } else if (op == 3) {
+        const float* in = (const float*)in_;
+        double* out = (double*)out_;
+        for (long i = 0; i < n; ++i) {
+            float nb[5][3];
+            memcpy(nb, in + 18 * i, sizeof(nb));
+            mmlo_plane_factor f;
+            double* o = out + 11 * i;
+            for (int k = 0; k < 11; ++k) o[k] = 0;
+            const bool ok = fit_plane(zero3, in + 18 * i + 15, nb, I4, &f, o + 1);
+            o[0] = ok ? 1 : 0;
+            if (ok)
+                for (int k = 0; k < 3; ++k) o[8 + k] = f.point_proj[k];
+        }
+    } else if (op == 4) {
+        const double* in = (const double*)in_;
+        double* out = (double*)out_;
+        for (long i = 0; i < n; ++i) {
+            out[2 * i] = std::sqrt(in[2 * i]);
+            out[2 * i + 1] = in[2 * i] / in[2 * i + 1];
+        }
+    } else if (op == 5) {
+        const float* in = (const float*)in_;
+        float* out = (float*)out_;
+        for (long i = 0; i < n; ++i) {
+            out[2 * i] = std::sqrt(in[2 * i]);
+            out[2 * i + 1] = in[2 * i] / in[2 * i + 1];
+        }
+    } else {
+        return -1;
+    }
+    return 0;
+}

@@ -285,7 +285,8 @@ inline void eig3_sym(const double* A, double* evals, double* evecs) {
 }
 
 // Eigen 3.3.4 ColPivHouseholderQR<Matrix<double,5,3>>::compute + solve(b = -1):  A row-major 5x3.
-inline void plane_fit5(const double* A_in, double* xout) {
+// rank_out (optional): nonzero_pivots, the rank Eigen's solve() uses.
+inline void plane_fit5(const double* A_in, double* xout, int* rank_out = nullptr) {
     const int rows = 5, cols = 3, size = 3;
     double qr[5][3];
     for (int r = 0; r < rows; ++r)
@@ -377,6 +378,7 @@ inline void plane_fit5(const double* A_in, double* xout) {
     for (int k = 0; k < size; ++k) std::swap(perm[k], perm[transp[k]]);
 
     xout[0] = xout[1] = xout[2] = 0;
+    if (rank_out) *rank_out = nonzero_pivots;
     if (nonzero_pivots == 0) return;
     double c[5] = {-1, -1, -1, -1, -1};
     // c = Q^T b : apply H_0, H_1, ... in order

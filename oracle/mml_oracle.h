@@ -213,6 +213,9 @@ void mmlo_so3_exp(const double* phi, double* q_xyzw);   /* sophus/so3.hpp:585-62
 void mmlo_so3_log(const double* q_xyzw, double* phi);   /* sophus/so3.hpp:247-287 */
 void mmlo_eig3_sym(const double* A /*row-major 3x3*/, double* evals /*ascending*/, double* evecs /*columns, row-major 3x3*/);
 void mmlo_plane_fit5(const double* A /*5x3 row-major*/, double* x /*3*/);
+/* fit_line / fit_plane / eig3_sym / plane_fit5 and the basic operations over arrays of n items, with the operation
+ * codes and the per-item layouts of mml_model_fit5 (include/mmloam_hip.h).  Returns 0, -1 on a bad argument. */
+int mmlo_model_fit5(int op, const void* in, long n, void* out);
 
 #ifdef __cplusplus
 }

@@ -398,6 +398,21 @@ def plane_fit5(A):
     return x
 
 
+_FIT_SHAPES = {0: (np.float64, 6, np.float64, 12), 1: (np.float64, 15, np.float64, 4), 2: (np.float32, 15, np.float64, 13),
+               3: (np.float32, 18, np.float64, 11), 4: (np.float64, 2, np.float64, 2), 5: (np.float32, 2, np.float32, 2)}
+
+
+def model_fit5(op, items):
+    """fit_line / fit_plane / eig3_sym / plane_fit5 / sqrt and division over an array of items (mmlo_model_fit5): op 0 eig3,
+    1 qr, 2 line model, 3 plane model, 4 / 5 double / float basic operations; layouts as mml_model_fit5's."""
+    ti, wi, to, wo = _FIT_SHAPES[op]
+    a = np.ascontiguousarray(items, ti).reshape(-1, wi)
+    out = np.empty((len(a), wo), to)
+    rc = lib().mmlo_model_fit5(C.c_int(op), _p(a), C.c_long(len(a)), _p(out))
+    assert rc == 0
+    return out
+
+
 def gicp_align(src, tgt, T0=None):
     """icp_ext_matching: returns (converged, T 4x4 float32, outer iterations, objective evaluations, last objective)."""
     src = _f32(src).reshape(-1, 3)

@@ -49,23 +49,22 @@ def random_dirt(rng, v, l):
     return v, l
 
 
-def plane_records_close(g, o):
-    """Plane factor records (point_ori, point_proj, omega, error) against the oracle's: <= 1e-9 in every field -- or, for a record whose
-    omega is one FLOAT ulp off in some component, <= 1e-6 in the fields computed from it.  omega is `float pa = X[0]` of the plane fit's
-    double solution (Estimator.cpp:722-738) normalised in float: the oracle's and the device's QR agree on X to ~1e-16 relative, so the
-    cast rounds the other way for about one value in 1e8 -- campaign seed 930 met the first one in 1.3e8 plane records (round 6,
-    identical on the libraries before and after that round's changes: pose difference 8.5e-14).  Returns (ok, flipped records)."""
-    if len(g) != len(o):
-        return False, 0
-    if len(g) == 0:
-        return True, 0
-    d = np.abs(g - o)
-    bad = np.flatnonzero(d.max(axis=1) > 1e-9)
-    if len(bad) == 0:
-        return True, 0
-    og, oo = g[bad, 6:9].astype(np.float32), o[bad, 6:9].astype(np.float32)
-    one_ulp = np.abs(og - oo) <= np.spacing(np.maximum(np.abs(og), np.abs(oo)))
-    return bool(np.all(one_ulp) and np.all(d[bad] <= 1e-6)), len(bad)
+def step_pose_matrix(O, x):
+    """T_wl as mml_step forms it from the 6-vector it is given: Sophus' SO3 exp, then Eigen's toRotationMatrix.  The oracle pipeline has
+    to associate at THIS matrix, not at the matrix x was derived from: the round trip matrix -> rotation vector -> matrix moves T by
+    ~1e-16, and float(T p) of a feature (pointAssociateToMap) then rounds the other way about once in 1e8 points.  Campaign seed 930
+    met that point (batch round 12, scan 13): the selected point's x one float ulp off and, through it, point_proj[0] (1.49e-8) and
+    the error (5e-11) of ONE plane record; omega and the plane fit itself were bit-equal (the neighbourhood is a permanent item of
+    tests/golden/modelfit_kat.npz, family seed930)."""
+    qx, qy, qz, qw = O.so3_exp(x[3:])
+    tx, ty, tz = 2 * qx, 2 * qy, 2 * qz
+    twx, twy, twz = tx * qw, ty * qw, tz * qw
+    txx, txy, txz = tx * qx, ty * qx, tz * qx
+    tyy, tyz, tzz = ty * qy, tz * qy, tz * qz
+    T = np.eye(4)
+    T[:3, :3] = [[1 - (tyy + tzz), txy - twz, txz + twy], [txy + twz, 1 - (txx + tzz), tyz - twx], [txz - twy, tyz + twx, 1 - (txx + tyy)]]
+    T[:3, 3] = x[:3]
+    return T
 
 
 def batch_section(args, M, O, synth, rng):
@@ -93,7 +92,6 @@ def batch_section(args, M, O, synth, rng):
     c.map_set_local(1, sm)
     n_pts = n_fac = redo = 0
     worst_pose = 0.0
-    flips = 0  # plane records (slots) whose omega is one float ulp off the oracle's (plane_records_close)
     for rnd in range(args.batch):
         cases = []
         for j in range(ND):
@@ -118,7 +116,8 @@ def batch_section(args, M, O, synth, rng):
                 v, l = (None, l) if rng.integers(0, 2) else (v, None)
             dR, dt = synth.sweep_motion(k) if motion else (np.eye(3), np.zeros(3))
             T0 = perturbed(synth.pose_matrix(k), dt=rng.normal(0, 0.03, 3), rotvec=rng.normal(0, 0.004, 3))
-            cases.append(dict(velo=v, livox=l, dR=dR, dt=dt, T0=T0, x0=pose_to_x(T0), k=k))
+            x0 = pose_to_x(T0)
+            cases.append(dict(velo=v, livox=l, dR=dR, dt=dt, T0=step_pose_matrix(O, x0), x0=x0, k=k))
         ora = [oracle_pipeline(O, cs, tc, ts) for cs in cases]
         perm = rng.permutation(B) % ND                      # which scan a slot holds
         for s in range(B):
@@ -147,10 +146,7 @@ def batch_section(args, M, O, synth, rng):
             ok = (np.array_equal(d["label"], o["label"]) and np.array_equal(d["xyzi"][:, :3], o["und"]) and np.all(d["reltime"] == 1.0)
                   and c.features_download(s, 0).tobytes() == o["corner"].tobytes() and c.features_download(s, 1).tobytes() == o["surf"].tobytes()
                   and np.array_equal(glsrc, o["lsrc"]) and np.array_equal(gpsrc, o["psrc"])
-                  and np.allclose(gl, o["lf_arr"], rtol=0, atol=1e-9))
-            pok, nflip = plane_records_close(gp, o["pf_arr"])
-            ok = ok and pok
-            flips += nflip
+                  and np.allclose(gl, o["lf_arr"], rtol=0, atol=1e-9) and np.allclose(gp, o["pf_arr"], rtol=0, atol=1e-9))
             dd = float(np.abs(x[s] - o["x"]).max())
             worst_pose = max(worst_pose, dd)
             if not ok or not dd < 1e-6:
@@ -165,11 +161,8 @@ def batch_section(args, M, O, synth, rng):
                 return 1
             n_pts += len(o["xyzi"])
             n_fac += len(glsrc) + len(gpsrc)
-    if flips > 16:
-        print("BATCH: %d plane records with a float-ulp omega -- more than the cast's rounding explains" % flips)
-        return 1
-    print("batch: %d rounds x %d slots ok (%d points, %d factor records%s, redo-queue share %.3f %%, worst pose difference %.2e) %.0f s"
-          % (args.batch, B, n_pts, n_fac, ", %d of them with omega one float ulp off" % flips if flips else "", 100.0 * redo / max(n_pts, 1), worst_pose,
+    print("batch: %d rounds x %d slots ok (%d points, %d factor records, redo-queue share %.3f %%, worst pose difference %.2e) %.0f s"
+          % (args.batch, B, n_pts, n_fac, 100.0 * redo / max(n_pts, 1), worst_pose,
              time.time() - t0), flush=True)
     c.close()
     return 0
