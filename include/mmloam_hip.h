@@ -536,6 +536,26 @@ int mml_lio_initialize(int n, const double* t, double* P, double* Q, double* V, 
  * reports this solve and mml_fullwindow_marginalize can be called with the returned x. */
 int mml_fullwindow_solve(mml_ctx* ctx, mml_fullwindow* fw, int first_slot, const double* T_bl, double* x,
                          mml_solve_summary* summary, int* evaluations);
+/* n such solves in one device call: the same kernels with a window dimension, so that many windows (a fleet's bags, one
+ * bag cut into segments) fill the device instead of the 2 W + 1 workgroups of one.  Window w is handle fws[w] -- its own
+ * W, options, IMU factors and prior; windows may differ in all of them -- on the factor lists of slots first_slot[w] ..
+ * first_slot[w] + W_w - 1 (windows may share slots: the solve only reads them), with its state in the first 15 W_w doubles
+ * of x + MML_FW_X_STRIDE w (in/out) and one T_bl for all.  The rounds run to the largest max_num_iterations + 1 of the
+ * batch; a window that has finished costs nothing further, and the enqueue loop stops when none is left.  Every window's
+ * result is bit-identical to mml_fullwindow_solve called on it alone, and every handle is left as that call leaves it
+ * (mml_fullwindow_summary, mml_fullwindow_marginalize).  summaries / evaluations: n entries or NULL.  records0 (n x 32 or
+ * NULL): entry w receives the record of window w's frame 0 at the returned x, linearised with that handle's
+ * plan_weight_tan and huber_delta -- what mml_linearize_window(first_slot[w], 1, ...) returns and
+ * mml_fullwindow_marginalize takes -- all of them from one launch and one read-back.
+ * Everything is checked before anything is enqueued and the message names the window: MML_ERR_INVALID for n < 1 or
+ * n > MML_FW_BATCH_MAX, a null entry, a handle that appears twice, a window that does not fit the slots,
+ * max_num_iterations outside 0 .. 1000; MML_ERR_STATE for a pre-integration whose covariance is not positive definite.
+ * The context keeps device and pinned buffers for the largest n it has seen (about 0.2 MB per window). */
+#define MML_FW_X_STRIDE 120   /* 15 * 8 doubles per window in x */
+#define MML_FW_BATCH_MAX 1024 /* windows per call */
+int mml_fullwindow_solve_batch(mml_ctx* ctx, int n, mml_fullwindow* const* fws, const int* first_slot, const double* T_bl,
+                               double* x /* n x MML_FW_X_STRIDE, in/out */, mml_solve_summary* summaries /* n or NULL */,
+                               int* evaluations /* n or NULL */, double* records0 /* n x 32 or NULL */);
 
 /* Number of HIP streams mml_step pipelines its sub-batches over (1..8, default 2 or $MML_LANES).  With 1 every
  * kernel covers the whole batch and runs alone on the device, which is what per-kernel timing wants. */

@@ -24,6 +24,8 @@ MML_OK, MML_ERR_INVALID, MML_ERR_NO_DEVICE, MML_ERR_HIP, MML_ERR_CAPACITY, MML_E
 NEQ_RECORD_DOUBLES = 32
 MAX_STAGES = 32
 DIGEST_WORDS = 10
+FW_X_STRIDE = 120      # MML_FW_X_STRIDE: doubles per window in the state array of mml_fullwindow_solve_batch
+FW_BATCH_MAX = 1024     # MML_FW_BATCH_MAX: windows per call
 
 LIVOX_DTYPE = np.dtype([("offset_time", "<u4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4"),
                         ("reflectivity", "u1"), ("tag", "u1"), ("line", "u1"), ("_pad", "u1")])
@@ -211,6 +213,9 @@ def lib():
         L.mml_window_solver_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.mml_window_solver_summary.argtypes = [C.c_void_p, C.POINTER(SolveSummary)]
         L.mml_destroy.argtypes = [C.c_void_p]
+        if hasattr(L, "mml_fullwindow_solve_batch"):     # (an A/B build of an older commit through $MML_LIB_PATH has none)
+            L.mml_fullwindow_solve_batch.restype = C.c_int
+            L.mml_fullwindow_solve_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
         _lib = L
     return _lib
 
@@ -827,6 +832,32 @@ class FullWindowSolver:
                 self._h = None
         except Exception:
             pass
+
+
+def fullwindow_solve_batch(ctx, solvers, first_slots, T_bl, xs, records0=False):
+    """mml_fullwindow_solve_batch: the device-resident solve of FullWindowSolver.solve_device for a list of windows in one
+    device call.  solvers[w]: the FullWindowSolver of window w (its own W, options, IMU factors, prior), first_slots[w]: its
+    first scan slot, xs[w]: its state (W_w, 15).  Returns (list of x (W_w, 15), list of SolveSummary, list of evaluation
+    counts) and, with records0=True, a fourth entry: the (n, 32) records of every window's frame 0 at the returned x (what
+    FullWindowSolver.marginalize takes).  Every window's result equals solve_device called on it alone."""
+    n = len(solvers)
+    if len(first_slots) != n or len(xs) != n:
+        raise ValueError("solvers, first_slots and xs must have one entry per window (%d, %d, %d)" % (n, len(first_slots), len(xs)))
+    x = np.zeros((max(n, 1), FW_X_STRIDE))
+    for w, (fw, xw) in enumerate(zip(solvers, xs)):
+        xw = np.asarray(xw, dtype=np.float64)
+        if xw.shape != (fw.W, 15):
+            raise ValueError("xs[%d] has shape %s, window %d needs (%d, 15)" % (w, xw.shape, w, fw.W))
+        x[w, :15 * fw.W] = xw.reshape(-1)
+    handles = (C.c_void_p * max(n, 1))(*[fw._h.value if isinstance(fw._h, C.c_void_p) else fw._h for fw in solvers])
+    first = np.ascontiguousarray(list(first_slots) + [0] * (n == 0), dtype=np.int32)
+    summ = (SolveSummary * max(n, 1))()
+    ev = np.zeros(max(n, 1), np.int32)
+    rec = np.zeros((max(n, 1), NEQ_RECORD_DOUBLES)) if records0 else None
+    ctx._ck(lib().mml_fullwindow_solve_batch(ctx._h, C.c_int(n), handles, _p(first), _p(_f64(T_bl).reshape(16)), _p(x), summ, _p(ev),
+                                             _p(rec)))
+    out = ([x[w, :15 * fw.W].reshape(fw.W, 15).copy() for w, fw in enumerate(solvers)], list(summ)[:n], [int(e) for e in ev[:n]])
+    return out + (rec[:n],) if records0 else out
 
 
 class WindowSolver:

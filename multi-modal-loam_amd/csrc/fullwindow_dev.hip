@@ -21,10 +21,18 @@
 //               Ceres takes sequentially are taken sequentially by one lane each, on different wavefronts at once.
 // Differences to the host loop are limited to libm vs device sin / cos / atan / sqrt and the summation order of the
 // back substitution.
+// Every kernel carries a window dimension (blockIdx.y = w; parameter block, state machine and output record live in
+// arrays of n): mml_fullwindow_solve_batch advances n independent windows with the same launches, mml_fullwindow_solve
+// is its n = 1 case.  A window's workgroups touch that window's records only, so its arithmetic does not depend on
+// what else is in the batch.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
+#include <stddef.h>
 #include <string.h>
+
+#include <algorithm>
+#include <utility>
 
 #include "fullwindow_internal.h"
 #include "imu_math.h"
@@ -98,13 +106,14 @@ struct FwDevOut {
 };
 
 struct FwKernelArgs {
-    const FwDevParams* P;
-    FwGlobal* G;
-    FwDevOut* out;
+    const FwDevParams* P;  // n parameter blocks
+    FwGlobal* G;           // n state machines
+    FwDevOut* out;         // n output records
+    int* alive;            // alive[r]: windows still going after round r (counted in the rounds the host polls)
     const int* ft_n;
     const MmlLineFactor* lf;
     const MmlPlaneFactor* pf;
-    int B, MF, round, last;
+    int B, MF, round, poll;
 };
 
 __device__ __forceinline__ int band0(int a) { return 15 * (a / 15 - 1); }  // first column of row a's band (may be -15)
@@ -131,10 +140,11 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_fw_eval(FwKernelArgs A) {
     __shared__ double s_x[30];
     __shared__ double s_r[15], s_rs[15];
     __shared__ double s_J[450], s_Js[450];
-    const FwDevParams* P = A.P;
-    FwGlobal* G = A.G;
+    const FwDevParams* P = A.P + blockIdx.y;
+    FwGlobal* G = A.G + blockIdx.y;
     if (!G->s.go) return;
     const int tid = threadIdx.x, W = P->W, blk = blockIdx.x;
+    if (blk >= 2 * W) return;  // the grid covers the largest window of the batch
     if (blk < W) {  // lidar factors of frame blk
         const int b = P->first + blk;
         if (tid < 6) s_x[tid] = G->v.xc[15 * blk + tid];
@@ -517,11 +527,11 @@ __device__ int fw_propose(const FwDevParams* P, FwShared& sh, int n) {
 
 // accept / reject after the candidate was evaluated into slot 1 - cur; true when the minimiser stops.  On acceptance
 // sh.H (holding the candidate's band) becomes the current band; on rejection the current band is read back.
-__device__ bool fw_decide(const FwKernelArgs& A, FwShared& sh, int n) {
+__device__ bool fw_decide(const FwDevParams* P, const FwGlobal* G, FwShared& sh, int n) {
     FwScalars& S = sh.s;
     FwVectors& V = sh.v;
     const int tid = threadIdx.x;
-    const bool fixed = A.P->fixed != 0;
+    const bool fixed = P->fixed != 0;
     __syncthreads();
     const double cur = S.cost[S.cur], cand = S.cost[1 - S.cur];
     if (!fixed) {
@@ -567,7 +577,7 @@ __device__ bool fw_decide(const FwKernelArgs& A, FwShared& sh, int n) {
             S.flag = stop;
         }
     } else {
-        for (int o = tid; o < n * FW_BW; o += FW_THREADS) sh.H[o] = A.G->Hb[cur_slot][o];
+        for (int o = tid; o < n * FW_BW; o += FW_THREADS) sh.H[o] = G->Hb[cur_slot][o];
         if (tid == 0) {
             S.radius *= 0.5;
             S.reuse = 1;
@@ -580,13 +590,12 @@ __device__ bool fw_decide(const FwKernelArgs& A, FwShared& sh, int n) {
 
 __global__ __launch_bounds__(FW_THREADS) void k_fw_step(FwKernelArgs A) {
     __shared__ FwShared sh;
-    const FwDevParams* P = A.P;
-    FwGlobal* G = A.G;
+    const FwDevParams* P = A.P + blockIdx.y;
+    FwGlobal* G = A.G + blockIdx.y;
+    FwDevOut* out = A.out + blockIdx.y;
     const int tid = threadIdx.x, W = P->W, n = 15 * W;
-    if (!G->s.go) {
-        if (A.last && tid == 0) A.out->steps = G->s.steps;
-        return;
-    }
+    if (!G->s.go) return;  // finished: nothing of this window is written any more
+    const bool last = A.round >= P->max_iters;  // this window's own last round
     FwScalars& S = sh.s;
     FwVectors& V = sh.v;
     {
@@ -671,7 +680,7 @@ __global__ __launch_bounds__(FW_THREADS) void k_fw_step(FwKernelArgs A) {
         __syncthreads();
         done = S.flag != 0;
     } else {
-        done = fw_decide(A, sh, n);
+        done = fw_decide(P, G, sh, n);
     }
     FW_T(1);
     if (!done) {
@@ -690,25 +699,31 @@ __global__ __launch_bounds__(FW_THREADS) void k_fw_step(FwKernelArgs A) {
         const double* src = reinterpret_cast<const double*>(&V);
         for (int i = tid; i < (int)(sizeof(FwVectors) / sizeof(double)); i += FW_THREADS) dst[i] = src[i];
     }
-    if (done || A.last) {
-        if (tid < n) A.out->x[tid] = V.x[tid];
+    if (done || last) {
+        if (tid < n) out->x[tid] = V.x[tid];
         if (tid == 0) {
-            A.out->initial_cost = S.initial_cost;
-            A.out->final_cost = S.cost[S.cur];
-            A.out->iterations = S.iter;
-            A.out->successful = S.successful;
-            A.out->termination = S.termination;
-            A.out->evaluations = S.evals;
-            A.out->steps = S.steps;
+            out->initial_cost = S.initial_cost;
+            out->final_cost = S.cost[S.cur];
+            out->iterations = S.iter;
+            out->successful = S.successful;
+            out->termination = S.termination;
+            out->evaluations = S.evals;
+            out->steps = S.steps;
 #ifdef MML_FW_TIMING
-            for (int k = 0; k < 16; ++k) A.out->ticks[k] = S.ticks[k];
+            for (int k = 0; k < 16; ++k) out->ticks[k] = S.ticks[k];
 #endif
         }
     }
+    // the early-out of the enqueue loop: one count for the whole batch, read back once per chunk
+    if (A.poll && !done && tid == 0) atomicAdd(&A.alive[A.round], 1);
 }
 
-__global__ void k_fw_init(const FwDevParams* P, FwGlobal* G) {
+__global__ void k_fw_init(const FwDevParams* P, FwGlobal* G, int* alive, int rounds) {
+    P += blockIdx.y;
+    G += blockIdx.y;
     const int tid = threadIdx.x, n = 15 * P->W;
+    if (blockIdx.y == 0)
+        for (int r = tid; r < rounds; r += blockDim.x) alive[r] = 0;
     if (tid < n) G->v.x[tid] = G->v.xc[tid] = G->v.x_init[tid] = P->x[tid];
     if (tid == 0) {
         FwScalars s;
@@ -720,135 +735,246 @@ __global__ void k_fw_init(const FwDevParams* P, FwGlobal* G) {
     }
 }
 
+// the 32-double record of every window's frame 0 at the returned x (k_linearize's record: what mml_linearize_window(first, 1, ...)
+// hands out and mml_fullwindow_marginalize consumes), workgroup w for window w
+__global__ __launch_bounds__(SOLVE_THREADS) void k_fw_record0(FwKernelArgs A, const double* stats, double* record) {
+    __shared__ double s_part[SOLVE_WAVES * 28];
+    __shared__ double s_out[28];
+    const FwDevParams* P = A.P + blockIdx.x;
+    const int b = P->first;
+    record += 32 * (size_t)blockIdx.x;
+    Pose pose;
+    make_pose(A.out[blockIdx.x].x, P->Tbl, pose);
+    double acc[28];
+    eval_frame(A.lf + (size_t)b * A.MF, A.ft_n[b], A.pf + (size_t)b * A.MF, A.ft_n[A.B + b], pose, P->w_tan, P->huber, acc);
+    block_reduce28(acc, s_part, s_out);
+    if (threadIdx.x < 28) record[threadIdx.x] = s_out[threadIdx.x];
+    if (threadIdx.x == 0) {
+        record[28] = stats[16 * b + 2];
+        record[29] = stats[16 * b + 3];
+        record[30] = 0;
+        record[31] = 0;
+    }
+}
+
+constexpr int FW_MAX_ROUNDS = 1001;  // max_num_iterations <= 1000
+
 }  // namespace
 
-struct MmlFwDev {
+struct MmlFwDev {  // sized for `cap` windows, the largest batch seen
+    int cap = 0;
     FwDevParams* d_par = nullptr;
     FwGlobal* d_state = nullptr;
     FwDevOut* d_out = nullptr;
+    int* d_alive = nullptr;        // FW_MAX_ROUNDS
+    double* d_rec0 = nullptr;      // cap x 32
     FwDevParams* h_par = nullptr;  // pinned
     FwDevOut* h_out = nullptr;     // pinned
+    double* h_rec0 = nullptr;      // pinned
 };
+
+static void fw_free(MmlFwDev* d) {
+    if (d->d_par) hipFree(d->d_par);
+    if (d->d_state) hipFree(d->d_state);
+    if (d->d_out) hipFree(d->d_out);
+    if (d->d_alive) hipFree(d->d_alive);
+    if (d->d_rec0) hipFree(d->d_rec0);
+    if (d->h_par) hipHostFree(d->h_par);
+    if (d->h_out) hipHostFree(d->h_out);
+    if (d->h_rec0) hipHostFree(d->h_rec0);
+    *d = MmlFwDev();
+}
 
 void mml_fullwindow_dev_release(mml_ctx* ctx) {
     MmlFwDev* d = ctx->fwdev;
     if (!d) return;
-    if (d->d_par) hipFree(d->d_par);
-    if (d->d_state) hipFree(d->d_state);
-    if (d->d_out) hipFree(d->d_out);
-    if (d->h_par) hipHostFree(d->h_par);
-    if (d->h_out) hipHostFree(d->h_out);
+    fw_free(d);
     delete d;
     ctx->fwdev = nullptr;
 }
 
-extern "C" int mml_fullwindow_solve(mml_ctx* ctx, mml_fullwindow* fw, int first_slot, const double* T_bl, double* x,
-                                    mml_solve_summary* summary, int* evaluations) {
-    if (!ctx) return MML_ERR_INVALID;
-    MML_REQUIRE(fw && T_bl && x, MML_ERR_INVALID, "mml_fullwindow_solve: null argument");
-    const int W = fw->W;
-    MML_REQUIRE(W >= 1 && W <= MAXW && first_slot >= 0 && first_slot + W <= ctx->B, MML_ERR_INVALID,
-                "mml_fullwindow_solve: window does not fit the scan slots");
-    MML_REQUIRE(fw->opts.max_num_iterations >= 0 && fw->opts.max_num_iterations <= 1000, MML_ERR_INVALID,
-                "mml_fullwindow_solve: max_num_iterations out of range");
+// buffers for n windows (they only grow)
+static int fw_reserve(mml_ctx* ctx, int n) {
+    if (!ctx->fwdev) ctx->fwdev = new MmlFwDev();
+    MmlFwDev* d = ctx->fwdev;
+    if (n <= d->cap) return MML_OK;
+    fw_free(d);  // (every call drains the stream before it returns: nothing is in flight)
+    MML_HIP(hipMalloc(reinterpret_cast<void**>(&d->d_par), sizeof(FwDevParams) * n));
+    MML_HIP(hipMalloc(reinterpret_cast<void**>(&d->d_state), sizeof(FwGlobal) * n));
+    MML_HIP(hipMalloc(reinterpret_cast<void**>(&d->d_out), sizeof(FwDevOut) * n));
+    MML_HIP(hipMalloc(reinterpret_cast<void**>(&d->d_alive), sizeof(int) * FW_MAX_ROUNDS));
+    MML_HIP(hipMalloc(reinterpret_cast<void**>(&d->d_rec0), sizeof(double) * 32 * n));
+    MML_HIP(hipHostMalloc(reinterpret_cast<void**>(&d->h_par), sizeof(FwDevParams) * n, hipHostMallocDefault));
+    MML_HIP(hipHostMalloc(reinterpret_cast<void**>(&d->h_out), sizeof(FwDevOut) * n, hipHostMallocDefault));
+    MML_HIP(hipHostMalloc(reinterpret_cast<void**>(&d->h_rec0), sizeof(double) * 32 * n, hipHostMallocDefault));
+    d->cap = n;
+    return MML_OK;
+}
+
+#define FW_REFUSE(cond, code, w, what)                                       \
+    do {                                                                     \
+        if (!(cond)) {                                                       \
+            char m_[192];                                                    \
+            snprintf(m_, sizeof(m_), "%s: window %d: %s", who, (w), (what)); \
+            ctx->err = m_;                                                   \
+            return (code);                                                   \
+        }                                                                    \
+    } while (0)
+
+// n windows, window w in x + x_stride w; everything is checked before anything is enqueued
+static int fw_solve_batch(mml_ctx* ctx, const char* who, int n, mml_fullwindow* const* fws, const int* first_slot,
+                          const double* T_bl, double* x, size_t x_stride, mml_solve_summary* summaries, int* evaluations,
+                          double* records0) {
+    int Wmax = 0, rounds = 0;
+    {
+        std::vector<std::pair<const mml_fullwindow*, int>> seen(n);
+        for (int w = 0; w < n; ++w) {
+            const mml_fullwindow* fw = fws[w];
+            FW_REFUSE(fw, MML_ERR_INVALID, w, "null handle");
+            const int W = fw->W;
+            FW_REFUSE(W >= 1 && W <= MAXW && first_slot[w] >= 0 && first_slot[w] <= ctx->B - W, MML_ERR_INVALID, w,
+                      "window does not fit the scan slots");
+            FW_REFUSE(fw->opts.max_num_iterations >= 0 && fw->opts.max_num_iterations <= FW_MAX_ROUNDS - 1, MML_ERR_INVALID, w,
+                      "max_num_iterations out of range");
+            for (int f = 1; f < W; ++f)
+                FW_REFUSE(!fw->have_imu[f] || fw->U_ok[f], MML_ERR_STATE, w, "pre-integration covariance is not positive definite");
+            seen[w] = {fw, w};
+            Wmax = std::max(Wmax, W);
+            rounds = std::max(rounds, fw->opts.max_num_iterations + 1);
+        }
+        std::sort(seen.begin(), seen.end());
+        for (int i = 1; i < n; ++i)
+            FW_REFUSE(seen[i].first != seen[i - 1].first, MML_ERR_INVALID, seen[i].second, "the same handle appears twice in the batch");
+    }
     MML_HIP(hipSetDevice(ctx->device));
-    if (!ctx->fwdev) {
-        MmlFwDev* d = new MmlFwDev();
-        ctx->fwdev = d;
-        MML_HIP(hipMalloc(reinterpret_cast<void**>(&d->d_par), sizeof(FwDevParams)));
-        MML_HIP(hipMalloc(reinterpret_cast<void**>(&d->d_state), sizeof(FwGlobal)));
-        MML_HIP(hipMalloc(reinterpret_cast<void**>(&d->d_out), sizeof(FwDevOut)));
-        MML_HIP(hipHostMalloc(reinterpret_cast<void**>(&d->h_par), sizeof(FwDevParams), hipHostMallocDefault));
-        MML_HIP(hipHostMalloc(reinterpret_cast<void**>(&d->h_out), sizeof(FwDevOut), hipHostMallocDefault));
+    {
+        const int rc = fw_reserve(ctx, n);
+        if (rc != MML_OK) return rc;
     }
     MmlFwDev* d = ctx->fwdev;
-    FwDevParams& p = *d->h_par;
-    memset(&p, 0, sizeof(p));
-    p.W = W;
-    p.max_iters = fw->opts.max_num_iterations;
-    p.fixed = fw->opts.fixed_iterations;
-    p.first = first_slot;
-    p.huber = fw->opts.huber_delta;
-    p.w_tan = fw->opts.plan_weight_tan;
-    memcpy(p.gravity, fw->gravity, sizeof(p.gravity));
-    memcpy(p.Tbl, T_bl, sizeof(p.Tbl));
-    memcpy(p.x, x, sizeof(double) * 15 * W);
-    p.has_prior = fw->prior.valid ? 1 : 0;
-    if (fw->prior.valid) {
-        memcpy(p.prior.J, fw->prior.J, sizeof(p.prior.J));
-        memcpy(p.prior.r0, fw->prior.r0, sizeof(p.prior.r0));
-        memcpy(p.prior.x0, fw->prior.x0, sizeof(p.prior.x0));
-        for (int a = 0; a < 15; ++a)
-            for (int b = 0; b < 15; ++b) {
-                double h = 0;
-                for (int i = 0; i < 15; ++i) h += fw->prior.J[i * 15 + a] * fw->prior.J[i * 15 + b];
-                p.PP[a * 15 + b] = h;
-            }
-    }
-    for (int f = 1; f < W; ++f) {
-        if (!fw->have_imu[f]) continue;
-        p.have_imu[f] = 1;
-        p.imu[f] = fw->imu[f];
-        MML_REQUIRE(fw->U_ok[f], MML_ERR_STATE, "mml_fullwindow_solve: pre-integration covariance is not positive definite");
-        memcpy(p.U[f], &fw->U[225 * (size_t)f], sizeof(p.U[f]));
+    // the per-window parameter blocks, staged in pinned memory; only what the kernels read is written (the flags of the
+    // header gate every optional part)
+    for (int w = 0; w < n; ++w) {
+        const mml_fullwindow* fw = fws[w];
+        const int W = fw->W;
+        FwDevParams& p = d->h_par[w];
+        memset(&p, 0, offsetof(FwDevParams, x));
+        p.W = W;
+        p.max_iters = fw->opts.max_num_iterations;
+        p.fixed = fw->opts.fixed_iterations;
+        p.first = first_slot[w];
+        p.huber = fw->opts.huber_delta;
+        p.w_tan = fw->opts.plan_weight_tan;
+        memcpy(p.gravity, fw->gravity, sizeof(p.gravity));
+        memcpy(p.Tbl, T_bl, sizeof(p.Tbl));
+        memcpy(p.x, x + x_stride * w, sizeof(double) * 15 * W);
+        p.has_prior = fw->prior.valid ? 1 : 0;
+        if (fw->prior.valid) {
+            memcpy(p.prior.J, fw->prior.J, sizeof(p.prior.J));
+            memcpy(p.prior.r0, fw->prior.r0, sizeof(p.prior.r0));
+            memcpy(p.prior.x0, fw->prior.x0, sizeof(p.prior.x0));
+            for (int a = 0; a < 15; ++a)
+                for (int b = 0; b < 15; ++b) {
+                    double h = 0;
+                    for (int i = 0; i < 15; ++i) h += fw->prior.J[i * 15 + a] * fw->prior.J[i * 15 + b];
+                    p.PP[a * 15 + b] = h;
+                }
+        }
+        for (int f = 1; f < W; ++f) {
+            if (!fw->have_imu[f]) continue;
+            p.have_imu[f] = 1;
+            p.imu[f] = fw->imu[f];
+            memcpy(p.U[f], &fw->U[225 * (size_t)f], sizeof(p.U[f]));
+        }
     }
     hipStream_t s = MML_STREAM(ctx);
+    if (records0)  // (the records carry the used-factor counts of the association's statistics)
+        for (int w = 0; w < n; ++w) {
+            const int rs = mml_ensure_assoc_stats(ctx, first_slot[w], 1);
+            if (rs != MML_OK) return rs;
+        }
     MmlStageScope t(ctx, "fullwindow");
-    MML_HIP(hipMemcpyAsync(d->d_par, d->h_par, sizeof(FwDevParams), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_fw_init, dim3(1), dim3(128), 0, s, d->d_par, d->d_state);
+    MML_HIP(hipMemcpyAsync(d->d_par, d->h_par, sizeof(FwDevParams) * n, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_fw_init, dim3(1, n), dim3(128), 0, s, d->d_par, d->d_state, d->d_alive, rounds);
     FwKernelArgs a;
     a.P = d->d_par;
     a.G = d->d_state;
     a.out = d->d_out;
+    a.alive = d->d_alive;
     a.ft_n = ctx->ft_n;
     a.lf = ctx->lf;
     a.pf = ctx->pf;
     a.B = ctx->B;
     a.MF = ctx->MF;
     // at most max_iterations + 1 evaluations: the first point and one candidate per iteration (an invalid step consumes
-    // an iteration without an evaluation).  Enqueued in chunks of four; between chunks the `go` flag comes back (one
-    // 4-byte copy), so that a solve that converged early does not pay for the launches of the remaining no-op rounds.
-    const int rounds = p.max_iters + 1;
+    // an iteration without an evaluation); the batch runs to its largest count.  Enqueued in chunks of four; the last
+    // round of a chunk counts the windows that are still going and that count comes back (one 4-byte copy for the whole
+    // batch), so that a batch that converged early does not pay for the launches of the remaining no-op rounds.
     for (int r = 0; r < rounds; ++r) {
         a.round = r;
-        a.last = r + 1 == rounds;
-        hipLaunchKernelGGL(k_fw_eval, dim3(2 * W), dim3(SOLVE_THREADS), 0, s, a);
-        hipLaunchKernelGGL(k_fw_step, dim3(1), dim3(FW_THREADS), 0, s, a);
-        if ((r & 3) == 3 && r + 1 < rounds) {
+        a.poll = (r & 3) == 3 && r + 1 < rounds;
+        hipLaunchKernelGGL(k_fw_eval, dim3(2 * Wmax, n), dim3(SOLVE_THREADS), 0, s, a);
+        hipLaunchKernelGGL(k_fw_step, dim3(1, n), dim3(FW_THREADS), 0, s, a);
+        if (a.poll) {
             MML_HIP(hipGetLastError());
-            MML_HIP(hipMemcpyAsync(&d->h_out->pad_, &d->d_state->s.go, sizeof(int), hipMemcpyDeviceToHost, s));
+            MML_HIP(hipMemcpyAsync(&d->h_out->pad_, d->d_alive + r, sizeof(int), hipMemcpyDeviceToHost, s));
             MML_HIP(hipStreamSynchronize(s));
             if (!d->h_out->pad_) break;
         }
     }
+    if (records0) hipLaunchKernelGGL(k_fw_record0, dim3(n), dim3(SOLVE_THREADS), 0, s, a, ctx->assoc_stats, d->d_rec0);
     MML_HIP(hipGetLastError());
-    MML_HIP(hipMemcpyAsync(d->h_out, d->d_out, sizeof(FwDevOut), hipMemcpyDeviceToHost, s));
+    MML_HIP(hipMemcpyAsync(d->h_out, d->d_out, sizeof(FwDevOut) * n, hipMemcpyDeviceToHost, s));
+    if (records0) MML_HIP(hipMemcpyAsync(d->h_rec0, d->d_rec0, sizeof(double) * 32 * n, hipMemcpyDeviceToHost, s));
     MML_HIP(hipStreamSynchronize(s));
-    const FwDevOut& o = *d->h_out;
+    if (records0) memcpy(records0, d->h_rec0, sizeof(double) * 32 * n);
+    for (int w = 0; w < n; ++w) {
+        mml_fullwindow* fw = fws[w];
+        const int W = fw->W;
+        const FwDevOut& o = d->h_out[w];
+        double* xw = x + x_stride * w;
 #ifdef MML_FW_TIMING
-    {
-        static const char* names[12] = {"assemble", "decide", "prep", "build", "factor_solve_rest", "dogleg", "xc", "fs_setup", "fs_chol", "fs_fwd", "fs_bwd", "chol_shader_clocks/100"};
-        fprintf(stderr, "[fw step timing W=%d evals=%d iters=%d] us:", W, o.evaluations, o.iterations);
-        for (int k = 0; k < 12; ++k) fprintf(stderr, " %s=%.1f", names[k], o.ticks[k] * 0.01);
-        fprintf(stderr, "\n");
-    }
+        {
+            static const char* names[12] = {"assemble", "decide", "prep", "build", "factor_solve_rest", "dogleg", "xc", "fs_setup", "fs_chol", "fs_fwd", "fs_bwd", "chol_shader_clocks/100"};
+            fprintf(stderr, "[fw step timing window=%d W=%d evals=%d iters=%d] us:", w, W, o.evaluations, o.iterations);
+            for (int k = 0; k < 12; ++k) fprintf(stderr, " %s=%.1f", names[k], o.ticks[k] * 0.01);
+            fprintf(stderr, "\n");
+        }
 #endif
-    memcpy(x, o.x, sizeof(double) * 15 * W);
-    // the handle reports this solve through mml_fullwindow_summary, and marginalizes at the returned x
-    fw->iter = o.iterations;
-    fw->successful = o.successful;
-    fw->termination = o.termination;
-    fw->initial_cost = o.initial_cost;
-    fw->cur.cost = o.final_cost;
-    fw->started = fw->done = 1;
-    fw->x.assign(x, x + 15 * W);
-    if (summary) {
-        summary->iterations = o.iterations;
-        summary->successful = o.successful;
-        summary->initial_cost = o.initial_cost;
-        summary->final_cost = o.final_cost;
-        summary->termination = o.termination;
+        memcpy(xw, o.x, sizeof(double) * 15 * W);
+        // the handle reports this solve through mml_fullwindow_summary, and marginalizes at the returned x
+        fw->iter = o.iterations;
+        fw->successful = o.successful;
+        fw->termination = o.termination;
+        fw->initial_cost = o.initial_cost;
+        fw->cur.cost = o.final_cost;
+        fw->started = fw->done = 1;
+        fw->x.assign(xw, xw + 15 * W);
+        if (summaries) {
+            summaries[w].iterations = o.iterations;
+            summaries[w].successful = o.successful;
+            summaries[w].initial_cost = o.initial_cost;
+            summaries[w].final_cost = o.final_cost;
+            summaries[w].termination = o.termination;
+        }
+        if (evaluations) evaluations[w] = o.evaluations;
     }
-    if (evaluations) *evaluations = o.evaluations;
     return MML_OK;
+}
+
+extern "C" int mml_fullwindow_solve(mml_ctx* ctx, mml_fullwindow* fw, int first_slot, const double* T_bl, double* x,
+                                    mml_solve_summary* summary, int* evaluations) {
+    if (!ctx) return MML_ERR_INVALID;
+    MML_REQUIRE(fw && T_bl && x, MML_ERR_INVALID, "mml_fullwindow_solve: null argument");
+    return fw_solve_batch(ctx, "mml_fullwindow_solve", 1, &fw, &first_slot, T_bl, x, 0, summary, evaluations, nullptr);
+}
+
+extern "C" int mml_fullwindow_solve_batch(mml_ctx* ctx, int n, mml_fullwindow* const* fws, const int* first_slot,
+                                          const double* T_bl, double* x, mml_solve_summary* summaries, int* evaluations,
+                                          double* records0) {
+    if (!ctx) return MML_ERR_INVALID;
+    MML_REQUIRE(n >= 1 && n <= MML_FW_BATCH_MAX, MML_ERR_INVALID, "mml_fullwindow_solve_batch: n outside 1 .. MML_FW_BATCH_MAX");
+    MML_REQUIRE(fws && first_slot && T_bl && x, MML_ERR_INVALID, "mml_fullwindow_solve_batch: null argument");
+    return fw_solve_batch(ctx, "mml_fullwindow_solve_batch", n, fws, first_slot, T_bl, x, MML_FW_X_STRIDE, summaries, evaluations,
+                          records0);
 }

@@ -184,6 +184,102 @@ class WindowEstimator:
         return info
 
 
+class BatchWindowEstimator:
+    """WindowEstimator(solver="device") for n windows at once -- a fleet's bags, or one bag cut into segments, replayed in
+    full-window mode.  The outer loops of all windows run in lockstep: one association call per run of adjacent slots at
+    outer iteration 0, then one mml_fullwindow_solve_batch per outer iteration over the windows that have not converged yet.
+    Every window keeps its own convergence test, its own gravity and its own prior (priors[w], marginalized on the host from
+    the frame-0 record the batch call hands back), so its frames, counts and prior equal what a WindowEstimator of its own
+    produces on the same inputs."""
+
+    def __init__(self, ctx, n, exTlb=None, gravity=(0.0, 0.0, -9.805), max_outer=5, inner_iters=10):
+        import importlib
+        self.M = importlib.import_module(__package__)
+        self.ctx, self.n = ctx, n
+        self.exTlb = np.eye(4) if exTlb is None else np.asarray(exTlb, dtype=np.float64)
+        self.T_bl = np.linalg.inv(self.exTlb)
+        self.exRbl = self.exTlb[:3, :3].T.copy()
+        self.exPbl = -1.0 * self.exRbl @ self.exTlb[:3, 3]
+        g = np.asarray(gravity, dtype=np.float64)
+        if g.shape not in ((3,), (n, 3)):
+            raise ValueError("gravity must be one vector or one per window")
+        self.gravity = np.broadcast_to(g, (n, 3)).copy()
+        self.max_outer, self.inner_iters = max_outer, inner_iters
+        self.priors = [None] * n          # last_marginalization_info of every window
+        self.plan_weight_tan = 0.0003     # :1203
+        self.thres_dist = 1.0             # :1204
+
+    _T_wl = WindowEstimator._T_wl
+
+    @staticmethod
+    def _state(frames):
+        return np.stack([np.concatenate([fr["P"], _rotvec_from_quat(fr["Q"]), fr["V"], fr["bg"], fr["ba"]]) for fr in frames])
+
+    def estimate(self, slots, frames, preints):
+        """One entry per window in each list: slots[w] the (consecutive) scan slots of window w's frames, frames[w] its
+        frame dicts (updated in place), preints[w][f] (f >= 1) its pre-integrations.  Windows must not share a slot (each
+        is associated at its own poses).  Returns one info dict per window (outer, evaluations, summaries); the new priors
+        are in self.priors."""
+        M, ctx, n = self.M, self.ctx, self.n
+        if not (len(slots) == len(frames) == len(preints) == n):
+            raise ValueError("slots, frames and preints must have one entry per window (%d)" % n)
+        for w in range(n):
+            if len(slots[w]) < 1 or len(frames[w]) != len(slots[w]) or len(preints[w]) != len(slots[w]):
+                raise ValueError("window %d: slots, frames and preints differ in length" % w)
+            if any(s != slots[w][0] + f for f, s in enumerate(slots[w])):
+                raise ValueError("window %d: its slots must be consecutive" % w)
+        owner = {}
+        for w in range(n):
+            for f, s in enumerate(slots[w]):
+                if s in owner:
+                    raise ValueError("slot %d belongs to windows %d and %d" % (s, owner[s][0], w))
+                owner[s] = (w, f)
+        infos = [dict(outer=0, summaries=[], evaluations=0) for _ in range(n)]
+        active = list(range(n))
+        for it in range(self.max_outer):
+            xs = [self._state(frames[w]) for w in active]
+            if it == 0:                                        # vLineFeatures / vPlanFeatures are empty only here
+                order = sorted(owner)
+                run = []
+                for i, s in enumerate(order):                  # one enqueue per run of adjacent slots, no read-back
+                    run.append(s)
+                    if i + 1 == len(order) or order[i + 1] != s + 1:
+                        T = np.stack([self._T_wl(xs[owner[r][0]][owner[r][1]]) for r in run])
+                        ctx.associate(run[0], len(run), T, self.thres_dist, stats=False)
+                        run = []
+            before = [(frames[w][-1]["Q"].copy(), frames[w][-1]["P"].copy()) for w in active]
+            solvers = []
+            for w in active:
+                fw = M.FullWindowSolver(len(slots[w]), max_iters=self.inner_iters, fixed=False, huber=0.0, w_tan=self.plan_weight_tan)
+                for f in range(1, len(slots[w])):
+                    fw.set_imu(f, preints[w][f], self.gravity[w])
+                if self.priors[w] is not None:
+                    fw.set_prior(self.priors[w])
+                solvers.append(fw)
+            xo, _, evals, rec0 = M.fullwindow_solve_batch(ctx, solvers, [slots[w][0] for w in active], self.T_bl, xs, records0=True)
+            still = []
+            for i, w in enumerate(active):
+                x, info = xo[i], infos[w]
+                info["evaluations"] += evals[i]
+                info["summaries"].append(solvers[i].summary())
+                for f, fr in enumerate(frames[w]):             # double2vector
+                    fr["P"], fr["Q"] = x[f][0:3].copy(), _quat_from_rotvec(x[f][3:6])
+                    fr["V"], fr["bg"], fr["ba"] = x[f][6:9].copy(), x[f][9:12].copy(), x[f][12:15].copy()
+                info["outer"] = it + 1
+                d = abs(float(np.dot(before[i][0], frames[w][-1]["Q"])))
+                deltaR = 2.0 * np.arccos(min(1.0, d)) * 180.0 / np.pi      # angularDistance, :1443
+                deltaT = float(np.linalg.norm(before[i][1] - frames[w][-1]["P"]))
+                if (deltaR < 0.05 and deltaT < 0.05) or it + 1 == self.max_outer:
+                    # marginalize frame 0 (:1453-1546): previous prior, IMU factor 0-1, the stored lidar factors of frame 0
+                    self.priors[w] = solvers[i].marginalize(rec0[i], x) if len(slots[w]) >= 2 else None
+                else:
+                    still.append(w)
+            active = still
+            if not active:
+                break
+        return infos
+
+
 def try_map_initialization(frames, samples, exTlb=None):
     """TryMAPInitialization (unionPoseEstimation.cpp:425-625) through mml_lio_initialize.  frames: the reference's frame
     list, front first, as dicts in the shape WindowEstimator.estimate uses (P, Q as x y z w = the lidar pose, V, bg, ba)
