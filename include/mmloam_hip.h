@@ -556,6 +556,20 @@ int mml_fullwindow_solve(mml_ctx* ctx, mml_fullwindow* fw, int first_slot, const
 int mml_fullwindow_solve_batch(mml_ctx* ctx, int n, mml_fullwindow* const* fws, const int* first_slot, const double* T_bl,
                                double* x /* n x MML_FW_X_STRIDE, in/out */, mml_solve_summary* summaries /* n or NULL */,
                                int* evaluations /* n or NULL */, double* records0 /* n x 32 or NULL */);
+/* mml_fullwindow_marginalize for n windows in one device call: one launch (a workgroup per window) and one read-back of
+ * n priors, no lidar record fetched first.  Window w uses handle fws[w] -- its IMU factor 1, prior, gravity and
+ * plan_weight_tan; the handles are only read, so one may appear more than once -- the associated factor lists of slot
+ * first_slot[w] (the window's frame 0) and the state in x + MML_FW_X_STRIDE w (its first 30 doubles are read).  The lidar
+ * factors are linearised WITHOUT a loss function whatever huber_delta the handle holds (the reference stores them so).
+ * priors[w] is bit-identical to mml_fullwindow_marginalize(fws[w], rec, x_w, ...) with rec the record
+ * mml_linearize_window(first_slot[w], 1, x_w, T_bl, plan_weight_tan, 0.0) returns: the device runs the host's operations
+ * in the host's order (csrc/marg_dense.h).
+ * Everything is checked before anything is enqueued and the message names the window: MML_ERR_INVALID for n < 1 or
+ * n > MML_FW_BATCH_MAX, a null entry, W < 2, no IMU factor 1, a slot out of range (a NULL ctx after the handle checks);
+ * MML_ERR_STATE for a pre-integration whose covariance is not positive definite.  The context keeps device and pinned
+ * buffers for the largest n it has seen (about 20 KB per window). */
+int mml_fullwindow_marginalize_batch(mml_ctx* ctx, int n, mml_fullwindow* const* fws, const int* first_slot, const double* T_bl,
+                                     const double* x /* n x MML_FW_X_STRIDE */, mml_prior* priors /* n */);
 
 /* Number of HIP streams mml_step pipelines its sub-batches over (1..8, default 2 or $MML_LANES).  With 1 every
  * kernel covers the whole batch and runs alone on the device, which is what per-kernel timing wants. */
@@ -585,6 +599,12 @@ int mml_libm_f32(mml_ctx* ctx, const float* y, const float* x, long n, float* ou
  * p1 / p2 and proj of a rejected model are never computed and come back as 0.  Codes from 6 on are free. */
 enum { MML_FIT_EIG3 = 0, MML_FIT_QR = 1, MML_FIT_LINE = 2, MML_FIT_PLANE = 3, MML_FIT_OPS_F64 = 4, MML_FIT_OPS_F32 = 5 };
 int mml_model_fit5(mml_ctx* ctx, int op, const void* in, long n, void* out);
+/* Test hook: the dense tail of the marginalization (csrc/marg_dense.h: eigen-decomposition of the marginalized block, Schur
+ * complement, square-root form) on n caller-supplied systems.  A: n x 900 (30 x 30 row-major, the first 15 parameters are
+ * marginalized), b: n x 30; J: n x 225, r0: n x 15.  ctx NULL: the host build of the routine, what
+ * mml_fullwindow_marginalize runs (no device needed); otherwise the device build, one workgroup of one wavefront per item.
+ * The two are bit-identical. */
+int mml_marginalize_dense(mml_ctx* ctx, long n, const double* A, const double* b, double* J, double* r0);
 /* How many 5-NN queries of the context's last association call (mml_associate / mml_step's association on the lane that ran
  * last) went beyond rings 0-1 of the grid into the far-query kernels (k_associate_hard): the share to watch when the map's density
  * and the configured cell edge do not fit each other. */

@@ -216,6 +216,11 @@ def lib():
         if hasattr(L, "mml_fullwindow_solve_batch"):     # (an A/B build of an older commit through $MML_LIB_PATH has none)
             L.mml_fullwindow_solve_batch.restype = C.c_int
             L.mml_fullwindow_solve_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
+        if hasattr(L, "mml_fullwindow_marginalize_batch"):
+            L.mml_fullwindow_marginalize_batch.restype = C.c_int
+            L.mml_fullwindow_marginalize_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
+            L.mml_marginalize_dense.restype = C.c_int
+            L.mml_marginalize_dense.argtypes = [C.c_void_p, C.c_long] + [C.c_void_p] * 4
         _lib = L
     return _lib
 
@@ -825,6 +830,11 @@ class FullWindowSolver:
                                                   _p(_f64(x).reshape(self.W, 15)), C.byref(out)), "marginalize")
         return out
 
+    def marginalize_device(self, ctx, first_slot, T_bl, x):
+        """mml_fullwindow_marginalize_batch for this window alone: the prior `marginalize` returns for the loss-free record
+        of slot `first_slot` at x[0], computed on the device without fetching that record."""
+        return fullwindow_marginalize_batch(ctx, [self], [first_slot], T_bl, [x])[0]
+
     def __del__(self):
         try:
             if self._h:
@@ -858,6 +868,56 @@ def fullwindow_solve_batch(ctx, solvers, first_slots, T_bl, xs, records0=False):
                                              _p(rec)))
     out = ([x[w, :15 * fw.W].reshape(fw.W, 15).copy() for w, fw in enumerate(solvers)], list(summ)[:n], [int(e) for e in ev[:n]])
     return out + (rec[:n],) if records0 else out
+
+
+def fullwindow_marginalize_batch(ctx, solvers, first_slots, T_bl, xs):
+    """mml_fullwindow_marginalize_batch: FullWindowSolver.marginalize for a list of windows in one device call.  solvers[w]:
+    the FullWindowSolver of window w (W >= 2, IMU factor 1 set; a solver may appear more than once), first_slots[w]: the
+    scan slot of its frame 0, xs[w]: its state (W_w, 15).  Returns a list of Prior, each bit-identical to
+    solvers[w].marginalize(record, xs[w]) with the loss-free record of that slot at xs[w][0]."""
+    n = len(solvers)
+    if len(first_slots) != n or len(xs) != n:
+        raise ValueError("solvers, first_slots and xs must have one entry per window (%d, %d, %d)" % (n, len(first_slots), len(xs)))
+    x = np.zeros((max(n, 1), FW_X_STRIDE))
+    for w, (fw, xw) in enumerate(zip(solvers, xs)):
+        xw = np.asarray(xw, dtype=np.float64)
+        if xw.shape != (fw.W, 15):
+            raise ValueError("xs[%d] has shape %s, window %d needs (%d, 15)" % (w, xw.shape, w, fw.W))
+        x[w, :15 * fw.W] = xw.reshape(-1)
+    handles = (C.c_void_p * max(n, 1))(*[fw._h.value if isinstance(fw._h, C.c_void_p) else fw._h for fw in solvers])
+    first = np.ascontiguousarray(list(first_slots) + [0] * (n == 0), dtype=np.int32)
+    out = (Prior * max(n, 1))()
+    rc = lib().mml_fullwindow_marginalize_batch(ctx._h if ctx is not None else None, C.c_int(n), handles, _p(first),
+                                                _p(_f64(T_bl).reshape(16)), _p(x), out)
+    if ctx is not None:
+        ctx._ck(rc)
+    elif rc != MML_OK:
+        raise MmlError(rc, "mml_fullwindow_marginalize_batch")
+    return [Prior.from_buffer_copy(out[w]) for w in range(n)]
+
+
+def marginalize_dense(ctx, A, b):
+    """The dense tail of the marginalization on caller-supplied systems (mml_marginalize_dense, a test hook).  A: (n, 30, 30)
+    or (30, 30), the first 15 parameters are marginalized; b: (n, 30) or (30,).  ctx None: the host routine (no device
+    needed); a Context: the device routine, bit-identical to it.  Returns (J (n, 15, 15), r0 (n, 15)), without the leading
+    axis for a single system."""
+    A = np.asarray(A, dtype=np.float64)
+    b = np.asarray(b, dtype=np.float64)
+    single = A.ndim == 2
+    if A.shape[-2:] != (30, 30) or A.ndim not in (2, 3):
+        raise ValueError("A must be (n, 30, 30) or (30, 30), not %s" % (A.shape,))
+    if b.shape != A.shape[:-2] + (30,):
+        raise ValueError("b must be %s, not %s" % (A.shape[:-2] + (30,), b.shape))
+    A = np.ascontiguousarray(A.reshape(-1, 900))
+    b = np.ascontiguousarray(b.reshape(-1, 30))
+    n = len(A)
+    J, r0 = np.zeros((n, 15, 15)), np.zeros((n, 15))
+    rc = lib().mml_marginalize_dense(ctx._h if ctx is not None else None, C.c_long(n), _p(A), _p(b), _p(J), _p(r0))
+    if ctx is not None:
+        ctx._ck(rc)
+    elif rc != MML_OK:
+        raise MmlError(rc, "mml_marginalize_dense")
+    return (J[0], r0[0]) if single else (J, r0)
 
 
 class WindowSolver:

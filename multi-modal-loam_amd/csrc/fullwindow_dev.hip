@@ -25,6 +25,9 @@
 // arrays of n): mml_fullwindow_solve_batch advances n independent windows with the same launches, mml_fullwindow_solve
 // is its n = 1 case.  A window's workgroups touch that window's records only, so its arithmetic does not depend on
 // what else is in the batch.
+//   k_fw_marginalize   n workgroups.  Frame 0 of window w marginalized into the next prior (mml_fullwindow_marginalize_batch):
+//               the loss-free lidar record of frame 0, prior and IMU factor 1, the 30 x 30 system, then the dense tail of
+//               marg_dense.h -- the routine the host function runs -- on one wavefront; bit-identical to the host.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -37,6 +40,7 @@
 #include "fullwindow_internal.h"
 #include "imu_math.h"
 #include "lidar_eval.h"
+#include "marg_dense.h"
 #include "mml_internal.h"
 
 // k_fw_step -- the dense 15 W-dimensional trust-region iteration -- keeps 256 threads; the lidar evaluation (k_fw_eval: eval_frame +
@@ -757,6 +761,99 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_fw_record0(FwKernelArgs A, co
     }
 }
 
+// ---- marginalization of frame 0 (mml_fullwindow_marginalize on the device) ------------------------------------------------
+struct FwMargParams {  // one window's inputs, about 8 KB (the 49 KB FwDevParams carries the whole window)
+    int first, has_prior, pad_[2];
+    double w_tan, huber;  // huber: always 0 -- the reference stores these factors without a loss function
+    double gravity[3];
+    double pad2_;
+    double Tbl[16];
+    double x[30];  // frames 0 and 1
+    mml_prior prior;
+    mml_imu_preint imu;  // between frames 0 and 1
+    double U[225];       // its sqrt information
+};
+
+struct FwMargShared {
+    double A[900], b[30];
+    MargWork work;
+    double x[30];
+    double rec[28];
+    double rp[15], r[15], rs[15];  // prior residual; IMU residual before / after the sqrt information
+    double J[450], Js[450];        // IMU Jacobian before / after
+    double part[SOLVE_WAVES * 28];
+};
+
+// Workgroup w: MarginalizationInfo::preMarginalize + marginalize for window w.  The loss-free lidar record of frame 0 as
+// k_fw_record0 / k_linearize form it, the prior residual and the IMU factor 0-1 on one lane each (imu_math.h), A and b
+// element-parallel with every element accumulated in the order of the host loop (prior terms, IMU terms, lidar value),
+// then the dense tail (marg_dense.h) on wavefront 0.
+__global__ __launch_bounds__(SOLVE_THREADS) void k_fw_marginalize(const FwMargParams* Pn, mml_prior* outn, const int* ft_n,
+                                                                 const MmlLineFactor* lf, const MmlPlaneFactor* pf, int B, int MF) {
+    __shared__ FwMargShared sh;
+    const FwMargParams* P = Pn + blockIdx.x;
+    mml_prior* out = outn + blockIdx.x;
+    const int tid = threadIdx.x, b0 = P->first, has_prior = P->has_prior;
+    if (tid < 30) sh.x[tid] = P->x[tid];
+    __syncthreads();
+    {
+        Pose pose;
+        make_pose(sh.x, P->Tbl, pose);
+        double acc[28];
+        eval_frame(lf + (size_t)b0 * MF, ft_n[b0], pf + (size_t)b0 * MF, ft_n[B + b0], pose, P->w_tan, P->huber, acc);
+        block_reduce28(acc, sh.part, sh.rec);
+    }
+    if (tid == 0 && has_prior) prior_residual(P->prior, sh.x, sh.rp);
+    if (tid == 64) imu_raw(&P->imu, P->gravity, sh.x, sh.x + 6, sh.x + 15, sh.x + 21, sh.r, sh.J);
+    __syncthreads();
+    // eResiduals.applyOnTheLeft(sqrt_information), the same for the Jacobian (ceresfunc.h:352,388-391)
+    for (int o = tid; o < 465; o += SOLVE_THREADS) {
+        double s = 0;
+        if (o < 450) {
+            const int i = o / 30, c = o - 30 * i;
+            for (int k = i; k < 15; ++k) s += P->U[i * 15 + k] * sh.J[k * 30 + c];
+            sh.Js[o] = s;
+        } else {
+            const int i = o - 450;
+            for (int k = i; k < 15; ++k) s += P->U[i * 15 + k] * sh.r[k];
+            sh.rs[i] = s;
+        }
+    }
+    __syncthreads();
+    for (int o = tid; o < 930; o += SOLVE_THREADS) {
+        double h = 0.0;
+        if (o < 900) {
+            const int a = o / 30, c = o - 30 * a;
+            if (has_prior && a < 15 && c < 15)
+                for (int i = 0; i < 15; ++i) h += P->prior.J[i * 15 + a] * P->prior.J[i * 15 + c];
+            for (int i = 0; i < 15; ++i) h += sh.Js[i * 30 + a] * sh.Js[i * 30 + c];
+            if (a < 6 && c < 6) h += Hget(sh.rec, a, c);
+            sh.A[o] = h;
+        } else {
+            const int a = o - 900;
+            if (has_prior && a < 15)
+                for (int i = 0; i < 15; ++i) h += P->prior.J[i * 15 + a] * sh.rp[i];
+            for (int i = 0; i < 15; ++i) h += sh.Js[i * 30 + a] * sh.rs[i];
+            if (a < 6) h += sh.rec[21 + a];
+            sh.b[a] = h;
+        }
+    }
+    __syncthreads();
+    if (tid < 64) marg_dense(sh.A, sh.b, out->J, out->r0, sh.work);
+    else if (tid < 64 + 15) out->x0[tid - 64] = sh.x[15 + tid - 64];  // parameter_block_data of the kept blocks
+}
+
+// test hook (mml_marginalize_dense): the dense tail alone, one workgroup of one wavefront per caller-supplied system
+__global__ __launch_bounds__(64) void k_marg_dense(const double* A, const double* b, double* J, double* r0) {
+    __shared__ double s_A[900], s_b[30];
+    __shared__ MargWork s_work;
+    const size_t w = blockIdx.x;
+    for (int o = threadIdx.x; o < 900; o += 64) s_A[o] = A[900 * w + o];
+    if (threadIdx.x < 30) s_b[threadIdx.x] = b[30 * w + threadIdx.x];
+    __syncthreads();
+    marg_dense(s_A, s_b, J + 225 * w, r0 + 15 * w, s_work);
+}
+
 constexpr int FW_MAX_ROUNDS = 1001;  // max_num_iterations <= 1000
 
 }  // namespace
@@ -771,9 +868,26 @@ struct MmlFwDev {  // sized for `cap` windows, the largest batch seen
     FwDevParams* h_par = nullptr;  // pinned
     FwDevOut* h_out = nullptr;     // pinned
     double* h_rec0 = nullptr;      // pinned
+    // mml_fullwindow_marginalize_batch, sized for `mcap` windows
+    int mcap = 0;
+    FwMargParams* d_mpar = nullptr;
+    mml_prior* d_mout = nullptr;
+    FwMargParams* h_mpar = nullptr;  // pinned
+    mml_prior* h_mout = nullptr;     // pinned
 };
 
+static void fw_marg_free(MmlFwDev* d) {
+    if (d->d_mpar) hipFree(d->d_mpar);
+    if (d->d_mout) hipFree(d->d_mout);
+    if (d->h_mpar) hipHostFree(d->h_mpar);
+    if (d->h_mout) hipHostFree(d->h_mout);
+    d->d_mpar = d->h_mpar = nullptr;
+    d->d_mout = d->h_mout = nullptr;
+    d->mcap = 0;
+}
+
 static void fw_free(MmlFwDev* d) {
+    fw_marg_free(d);
     if (d->d_par) hipFree(d->d_par);
     if (d->d_state) hipFree(d->d_state);
     if (d->d_out) hipFree(d->d_out);
@@ -808,6 +922,19 @@ static int fw_reserve(mml_ctx* ctx, int n) {
     MML_HIP(hipHostMalloc(reinterpret_cast<void**>(&d->h_out), sizeof(FwDevOut) * n, hipHostMallocDefault));
     MML_HIP(hipHostMalloc(reinterpret_cast<void**>(&d->h_rec0), sizeof(double) * 32 * n, hipHostMallocDefault));
     d->cap = n;
+    return MML_OK;
+}
+
+static int fw_marg_reserve(mml_ctx* ctx, int n) {
+    if (!ctx->fwdev) ctx->fwdev = new MmlFwDev();
+    MmlFwDev* d = ctx->fwdev;
+    if (n <= d->mcap) return MML_OK;
+    fw_marg_free(d);  // (every call drains the stream before it returns: nothing is in flight)
+    MML_HIP(hipMalloc(reinterpret_cast<void**>(&d->d_mpar), sizeof(FwMargParams) * n));
+    MML_HIP(hipMalloc(reinterpret_cast<void**>(&d->d_mout), sizeof(mml_prior) * n));
+    MML_HIP(hipHostMalloc(reinterpret_cast<void**>(&d->h_mpar), sizeof(FwMargParams) * n, hipHostMallocDefault));
+    MML_HIP(hipHostMalloc(reinterpret_cast<void**>(&d->h_mout), sizeof(mml_prior) * n, hipHostMallocDefault));
+    d->mcap = n;
     return MML_OK;
 }
 
@@ -977,4 +1104,94 @@ extern "C" int mml_fullwindow_solve_batch(mml_ctx* ctx, int n, mml_fullwindow* c
     MML_REQUIRE(fws && first_slot && T_bl && x, MML_ERR_INVALID, "mml_fullwindow_solve_batch: null argument");
     return fw_solve_batch(ctx, "mml_fullwindow_solve_batch", n, fws, first_slot, T_bl, x, MML_FW_X_STRIDE, summaries, evaluations,
                           records0);
+}
+
+// the same refusal without a context to carry the message (the argument checks come before anything needs one)
+#define FW_MARG_REFUSE(cond, code, w, what)                                                                  \
+    do {                                                                                                     \
+        if (!(cond)) {                                                                                       \
+            if (ctx) {                                                                                       \
+                char m_[192];                                                                                \
+                snprintf(m_, sizeof(m_), "mml_fullwindow_marginalize_batch: window %d: %s", (w), (what));    \
+                ctx->err = m_;                                                                               \
+            }                                                                                                \
+            return (code);                                                                                   \
+        }                                                                                                    \
+    } while (0)
+
+extern "C" int mml_fullwindow_marginalize_batch(mml_ctx* ctx, int n, mml_fullwindow* const* fws, const int* first_slot,
+                                                const double* T_bl, const double* x, mml_prior* priors) {
+    if (n < 1 || !fws || !first_slot || !T_bl || !x || !priors) {
+        if (ctx) ctx->err = "mml_fullwindow_marginalize_batch: n < 1 or a null argument";
+        return MML_ERR_INVALID;
+    }
+    FW_MARG_REFUSE(n <= MML_FW_BATCH_MAX, MML_ERR_INVALID, MML_FW_BATCH_MAX, "the batch holds more than MML_FW_BATCH_MAX windows");
+    for (int w = 0; w < n; ++w) {
+        const mml_fullwindow* fw = fws[w];
+        FW_MARG_REFUSE(fw, MML_ERR_INVALID, w, "null handle");
+        FW_MARG_REFUSE(fw->W >= 2, MML_ERR_INVALID, w, "a window of one frame has nothing to marginalize");
+        FW_MARG_REFUSE(fw->have_imu[1], MML_ERR_INVALID, w, "no IMU factor between frames 0 and 1");
+        FW_MARG_REFUSE(ctx && first_slot[w] >= 0 && first_slot[w] < ctx->B, MML_ERR_INVALID, w, "slot out of range");
+        FW_MARG_REFUSE(fw->U_ok[1], MML_ERR_STATE, w, "pre-integration covariance is not positive definite");
+    }
+    MML_HIP(hipSetDevice(ctx->device));
+    {
+        const int rc = fw_marg_reserve(ctx, n);
+        if (rc != MML_OK) return rc;
+    }
+    MmlFwDev* d = ctx->fwdev;
+    for (int w = 0; w < n; ++w) {  // only what the kernel reads is written (has_prior gates the prior)
+        const mml_fullwindow* fw = fws[w];
+        FwMargParams& p = d->h_mpar[w];
+        p.first = first_slot[w];
+        p.has_prior = fw->prior.valid ? 1 : 0;
+        p.w_tan = fw->opts.plan_weight_tan;
+        p.huber = 0.0;
+        memcpy(p.gravity, fw->gravity, sizeof(p.gravity));
+        memcpy(p.Tbl, T_bl, sizeof(p.Tbl));
+        memcpy(p.x, x + (size_t)MML_FW_X_STRIDE * w, sizeof(p.x));
+        if (fw->prior.valid) {
+            memcpy(p.prior.J, fw->prior.J, sizeof(p.prior.J));
+            memcpy(p.prior.r0, fw->prior.r0, sizeof(p.prior.r0));
+            memcpy(p.prior.x0, fw->prior.x0, sizeof(p.prior.x0));
+        }
+        p.imu = fw->imu[1];
+        memcpy(p.U, &fw->U[225], sizeof(p.U));
+    }
+    hipStream_t s = MML_STREAM(ctx);
+    MmlStageScope t(ctx, "fullwindow_marginalize");
+    MML_HIP(hipMemcpyAsync(d->d_mpar, d->h_mpar, sizeof(FwMargParams) * n, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_fw_marginalize, dim3(n), dim3(SOLVE_THREADS), 0, s, d->d_mpar, d->d_mout, ctx->ft_n, ctx->lf, ctx->pf, ctx->B,
+                       ctx->MF);
+    MML_HIP(hipGetLastError());
+    MML_HIP(hipMemcpyAsync(d->h_mout, d->d_mout, sizeof(mml_prior) * n, hipMemcpyDeviceToHost, s));
+    MML_HIP(hipStreamSynchronize(s));
+    memcpy(priors, d->h_mout, sizeof(mml_prior) * n);
+    return MML_OK;
+}
+
+extern "C" int mml_marginalize_dense(mml_ctx* ctx, long n, const double* A, const double* b, double* J, double* r0) {
+    if (n < 0 || n > (long)1 << 20 || !A || !b || !J || !r0) return MML_ERR_INVALID;
+    if (n == 0) return MML_OK;
+    if (!ctx) {  // the host build of the routine, what mml_fullwindow_marginalize runs
+        MargWork work;
+        for (long w = 0; w < n; ++w) marg_dense(A + 900 * w, b + 30 * w, J + 225 * w, r0 + 15 * w, work);
+        return MML_OK;
+    }
+    int rc = mml_sync_all(ctx);
+    if (rc != MML_OK) return rc;
+    double* d_buf = nullptr;  // A | b | J | r0
+    const size_t nA = 900 * (size_t)n, nb = 30 * (size_t)n, nJ = 225 * (size_t)n, nr = 15 * (size_t)n;
+    bool ok = hipMalloc(reinterpret_cast<void**>(&d_buf), sizeof(double) * (nA + nb + nJ + nr)) == hipSuccess;
+    ok = ok && hipMemcpy(d_buf, A, sizeof(double) * nA, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMemcpy(d_buf + nA, b, sizeof(double) * nb, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        hipLaunchKernelGGL(k_marg_dense, dim3((unsigned)n), dim3(64), 0, MML_STREAM(ctx), (const double*)d_buf, (const double*)(d_buf + nA),
+                           d_buf + nA + nb, d_buf + nA + nb + nJ);
+        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(MML_STREAM(ctx)) == hipSuccess;
+    }
+    ok = ok && hipMemcpy(J, d_buf + nA + nb, sizeof(double) * nJ, hipMemcpyDeviceToHost) == hipSuccess;
+    ok = ok && hipMemcpy(r0, d_buf + nA + nb + nJ, sizeof(double) * nr, hipMemcpyDeviceToHost) == hipSuccess;
+    if (d_buf) (void)hipFree(d_buf);
+    return ok ? MML_OK : MML_ERR_HIP;
 }

@@ -19,6 +19,7 @@
 
 #include "fullwindow_internal.h"
 #include "imu_math.h"
+#include "marg_dense.h"
 
 namespace {
 
@@ -69,57 +70,6 @@ void chol_solve_rcp(const double* L, int n, double* b) {
         b[i] = s * rd[i];
     }
 }
-// cyclic Jacobi eigen-decomposition of a symmetric n x n matrix: A = V diag(ev) V^T, eigenvalues ascending
-void sym_eig(const double* Ain, int n, double* ev, double* V) {
-    std::vector<double> A(Ain, Ain + n * n);
-    for (int i = 0; i < n * n; ++i) V[i] = 0;
-    for (int i = 0; i < n; ++i) V[i * n + i] = 1;
-    for (int sweep = 0; sweep < 100; ++sweep) {
-        double off = 0, diag = 0;
-        for (int i = 0; i < n; ++i)
-            for (int j = 0; j < n; ++j) (i == j ? diag : off) += A[i * n + j] * A[i * n + j];
-        if (off <= 1e-30 * diag || off == 0.0) break;
-        for (int p = 0; p < n - 1; ++p)
-            for (int q = p + 1; q < n; ++q) {
-                const double apq = A[p * n + q];
-                if (apq == 0.0) continue;
-                const double theta = (A[q * n + q] - A[p * n + p]) / (2.0 * apq);
-                const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                for (int k = 0; k < n; ++k) {
-                    const double akp = A[k * n + p], akq = A[k * n + q];
-                    A[k * n + p] = c * akp - s * akq;
-                    A[k * n + q] = s * akp + c * akq;
-                }
-                for (int k = 0; k < n; ++k) {
-                    const double apk = A[p * n + k], aqk = A[q * n + k];
-                    A[p * n + k] = c * apk - s * aqk;
-                    A[q * n + k] = s * apk + c * aqk;
-                }
-                for (int k = 0; k < n; ++k) {
-                    const double vkp = V[k * n + p], vkq = V[k * n + q];
-                    V[k * n + p] = c * vkp - s * vkq;
-                    V[k * n + q] = s * vkp + c * vkq;
-                }
-            }
-    }
-    std::vector<int> order(n);
-    for (int i = 0; i < n; ++i) order[i] = i;
-    for (int i = 0; i < n; ++i)
-        for (int j = i + 1; j < n; ++j)
-            if (A[order[j] * n + order[j]] < A[order[i] * n + order[i]]) {
-                int t = order[i];
-                order[i] = order[j];
-                order[j] = t;
-            }
-    std::vector<double> Vs(n * n);
-    for (int c = 0; c < n; ++c) {
-        ev[c] = A[order[c] * n + order[c]];
-        for (int r = 0; r < n; ++r) Vs[r * n + c] = V[r * n + order[c]];
-    }
-    memcpy(V, Vs.data(), sizeof(double) * n * n);
-}
-
 constexpr double kGnorm = 9.805;                                        // IMUIntegrator.h:84
 constexpr double kAccN = 0.08, kGyrN = 0.004, kAccW = 2.0e-4, kGyrW = 2.0e-5;  // IMUIntegrator.h:79-82
 
@@ -629,7 +579,7 @@ int mml_fullwindow_summary(const mml_fullwindow* s, mml_solve_summary* out) {
 // the window has slid (:1552-1562).
 int mml_fullwindow_marginalize(const mml_fullwindow* s, const double* lidar_record0, const double* x, mml_prior* out) {
     if (!s || !lidar_record0 || !x || !out || s->W < 2 || !s->have_imu[1]) return MML_ERR_INVALID;
-    const int m = 15, n = 15, N = 30;
+    const int N = 30;
     std::vector<double> A((size_t)N * N, 0.0), b(N, 0.0);
     if (s->prior.valid) {
         double r[15];
@@ -661,53 +611,8 @@ int mml_fullwindow_marginalize(const mml_fullwindow* s, const double* lidar_reco
             }
         for (int a = 0; a < 6; ++a) b[a] += lidar_record0[21 + a];
     }
-    const double eps = 1e-8;
-    // Amm^-1 through the eigen-decomposition of its symmetric part, eigenvalues <= eps dropped (:203-206)
-    double Amm[225], ev[15], V[225], Ainv[225];
-    for (int r = 0; r < m; ++r)
-        for (int c = 0; c < m; ++c) Amm[r * m + c] = 0.5 * (A[(size_t)r * N + c] + A[(size_t)c * N + r]);
-    sym_eig(Amm, m, ev, V);
-    for (int r = 0; r < m; ++r)
-        for (int c = 0; c < m; ++c) {
-            double sum = 0;
-            for (int k = 0; k < m; ++k)
-                if (ev[k] > eps) sum += V[r * m + k] * (1.0 / ev[k]) * V[c * m + k];
-            Ainv[r * m + c] = sum;
-        }
-    // Schur complement (:208-214)
-    double T[225];  // Arm * Amm_inv
-    for (int r = 0; r < n; ++r)
-        for (int c = 0; c < m; ++c) {
-            double sum = 0;
-            for (int k = 0; k < m; ++k) sum += A[(size_t)(m + r) * N + k] * Ainv[k * m + c];
-            T[r * m + c] = sum;
-        }
-    double Ar[225], br[15];
-    for (int r = 0; r < n; ++r) {
-        for (int c = 0; c < n; ++c) {
-            double sum = 0;
-            for (int k = 0; k < m; ++k) sum += T[r * m + k] * A[(size_t)k * N + m + c];
-            Ar[r * n + c] = A[(size_t)(m + r) * N + m + c] - sum;
-        }
-        double sb = 0;
-        for (int k = 0; k < m; ++k) sb += T[r * m + k] * b[k];
-        br[r] = b[m + r] - sb;
-    }
-    for (int r = 0; r < n; ++r)
-        for (int c = r + 1; c < n; ++c) Ar[r * n + c] = Ar[c * n + r] = 0.5 * (Ar[r * n + c] + Ar[c * n + r]);
-    // linearized_jacobians = sqrt(S) V^T, linearized_residuals = sqrt(S^-1) V^T b  (:216-227)
-    double ev2[15], V2[225];
-    sym_eig(Ar, n, ev2, V2);
-    for (int i = 0; i < n; ++i) {
-        const double sv = ev2[i] > eps ? sqrt(ev2[i]) : 0.0;
-        const double si = ev2[i] > eps ? sqrt(1.0 / ev2[i]) : 0.0;
-        double vb = 0;
-        for (int k = 0; k < n; ++k) {
-            out->J[i * 15 + k] = sv * V2[k * n + i];
-            vb += V2[k * n + i] * br[k];
-        }
-        out->r0[i] = si * vb;
-    }
+    MargWork work;  // the dense tail, shared with the device (marg_dense.h)
+    marg_dense(A.data(), b.data(), out->J, out->r0, work);
     memcpy(out->x0, x + 15, sizeof(double) * 15);  // parameter_block_data of the kept blocks = their current values
     return MML_OK;
 }

@@ -271,6 +271,9 @@ class Estimator {
     // EstimateFullWindow: true = the joint ceres::Solve is one device-resident iteration (mml_fullwindow_solve, needs the
     // window in consecutive slots); false = host iteration with one device evaluation per trust-region step
     bool device_window_solve = true;
+    // EstimateFullWindow: true = frame 0 is marginalized by one device call (mml_fullwindow_marginalize_batch, n = 1) without
+    // fetching its lidar record; false = record read-back + mml_fullwindow_marginalize on the host.  The priors are bit-identical.
+    bool device_marginalize = false;
 
     // processPointToLine / processPointToPlanVec (Estimator.h:159-186, Estimator.cpp:148-365, 573-777) for the down-sampled
     // stacks of `slot` at lidar pose m4d = transformTobeMapped: kNN + model fit on the device (both kinds in one launch),
@@ -545,8 +548,15 @@ class Estimator {
             for (int k = 0; k < 3; ++k) dT += (t_before.v[k] - frames[W - 1]->P.v[k]) * (t_before.v[k] - frames[W - 1]->P.v[k]);
             const bool last = (deltaR < 0.05 && std::sqrt(dT) < 0.05) || it == 4;
             if (last && W >= 2) {  // :1453-1546
-                lidar_records();
-                have_prior_ = mml_fullwindow_marginalize(fw, rec.data(), x.data(), &prior_) == MML_OK;
+                if (device_marginalize) {
+                    std::vector<double> xw(MML_FW_X_STRIDE, 0.0);
+                    std::memcpy(xw.data(), x.data(), sizeof(double) * x.size());
+                    const int first = frames[0]->slot;
+                    have_prior_ = mml_fullwindow_marginalize_batch(ctx_.get(), 1, &fw, &first, T_bl, xw.data(), &prior_) == MML_OK;
+                } else {
+                    lidar_records();
+                    have_prior_ = mml_fullwindow_marginalize(fw, rec.data(), x.data(), &prior_) == MML_OK;
+                }
             }
             mml_fullwindow_destroy(fw);
             if (last) break;

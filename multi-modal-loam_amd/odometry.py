@@ -106,12 +106,17 @@ class WindowEstimator:
     default when the window sits in consecutive slots): the 15 W trust-region iteration with its IMU factors and
     prior is one kernel launch (mml_fullwindow_solve); solver="host": the iteration is host code behind the same
     C-ABI (mml_fullwindow_step) and every evaluation fetches the per-frame lidar normal equations from the device.
-    The marginalization is host code either way."""
+    marginalize="host" (the default): frame 0's lidar record is fetched and the marginalization is host code;
+    marginalize="device": one device call (mml_fullwindow_marginalize_batch, n = 1) without that round trip, the prior
+    bit-identical to the host's."""
 
-    def __init__(self, ctx, exTlb=None, gravity=(0.0, 0.0, -9.805), max_outer=5, inner_iters=10, solver="device"):
+    def __init__(self, ctx, exTlb=None, gravity=(0.0, 0.0, -9.805), max_outer=5, inner_iters=10, solver="device",
+                 marginalize="host"):
         if solver not in ("device", "host"):
             raise ValueError("solver must be 'device' or 'host'")
-        self.solver = solver
+        if marginalize not in ("device", "host"):
+            raise ValueError("marginalize must be 'device' or 'host'")
+        self.solver, self.marginalize = solver, marginalize
         import importlib
         self.M = importlib.import_module(__package__)
         self.ctx = ctx
@@ -178,8 +183,13 @@ class WindowEstimator:
             deltaT = float(np.linalg.norm(t_before - frames[-1]["P"]))
             if (deltaR < 0.05 and deltaT < 0.05) or it + 1 == self.max_outer:
                 # marginalize frame 0 (:1453-1546): previous prior, IMU factor 0-1, the stored lidar factors of frame 0
-                rec0 = M.pack_record(*ctx.linearize(slots[0], x[0][:6], self.T_bl, self.plan_weight_tan, 0.0))
-                self.prior = fw.marginalize(rec0, x) if W >= 2 else None
+                if W < 2:
+                    self.prior = None
+                elif self.marginalize == "device":
+                    self.prior = fw.marginalize_device(ctx, slots[0], self.T_bl, x)
+                else:
+                    rec0 = M.pack_record(*ctx.linearize(slots[0], x[0][:6], self.T_bl, self.plan_weight_tan, 0.0))
+                    self.prior = fw.marginalize(rec0, x)
                 break
         return info
 
@@ -188,11 +198,16 @@ class BatchWindowEstimator:
     """WindowEstimator(solver="device") for n windows at once -- a fleet's bags, or one bag cut into segments, replayed in
     full-window mode.  The outer loops of all windows run in lockstep: one association call per run of adjacent slots at
     outer iteration 0, then one mml_fullwindow_solve_batch per outer iteration over the windows that have not converged yet.
-    Every window keeps its own convergence test, its own gravity and its own prior (priors[w], marginalized on the host from
-    the frame-0 record the batch call hands back), so its frames, counts and prior equal what a WindowEstimator of its own
-    produces on the same inputs."""
+    Every window keeps its own convergence test, its own gravity and its own prior (priors[w]), so its frames, counts and
+    prior equal what a WindowEstimator of its own produces on the same inputs.  marginalize="host" (the default): the batch
+    call hands back every window's frame-0 record and the windows that converge are marginalized on the host one by one;
+    marginalize="device": no records come back, the windows that converge in an outer iteration are marginalized by one
+    mml_fullwindow_marginalize_batch call, bit-identical priors."""
 
-    def __init__(self, ctx, n, exTlb=None, gravity=(0.0, 0.0, -9.805), max_outer=5, inner_iters=10):
+    def __init__(self, ctx, n, exTlb=None, gravity=(0.0, 0.0, -9.805), max_outer=5, inner_iters=10, marginalize="host"):
+        if marginalize not in ("device", "host"):
+            raise ValueError("marginalize must be 'device' or 'host'")
+        self.marginalize = marginalize
         import importlib
         self.M = importlib.import_module(__package__)
         self.ctx, self.n = ctx, n
@@ -256,8 +271,10 @@ class BatchWindowEstimator:
                 if self.priors[w] is not None:
                     fw.set_prior(self.priors[w])
                 solvers.append(fw)
-            xo, _, evals, rec0 = M.fullwindow_solve_batch(ctx, solvers, [slots[w][0] for w in active], self.T_bl, xs, records0=True)
-            still = []
+            on_device = self.marginalize == "device"
+            out = M.fullwindow_solve_batch(ctx, solvers, [slots[w][0] for w in active], self.T_bl, xs, records0=not on_device)
+            xo, evals, rec0 = out[0], out[2], None if on_device else out[3]
+            still, closing = [], []
             for i, w in enumerate(active):
                 x, info = xo[i], infos[w]
                 info["evaluations"] += evals[i]
@@ -271,9 +288,19 @@ class BatchWindowEstimator:
                 deltaT = float(np.linalg.norm(before[i][1] - frames[w][-1]["P"]))
                 if (deltaR < 0.05 and deltaT < 0.05) or it + 1 == self.max_outer:
                     # marginalize frame 0 (:1453-1546): previous prior, IMU factor 0-1, the stored lidar factors of frame 0
-                    self.priors[w] = solvers[i].marginalize(rec0[i], x) if len(slots[w]) >= 2 else None
+                    if len(slots[w]) < 2:
+                        self.priors[w] = None
+                    elif on_device:
+                        closing.append(i)
+                    else:
+                        self.priors[w] = solvers[i].marginalize(rec0[i], x)
                 else:
                     still.append(w)
+            if closing:                                        # one device call for every window that closes here
+                pr = M.fullwindow_marginalize_batch(ctx, [solvers[i] for i in closing], [slots[active[i]][0] for i in closing],
+                                                    self.T_bl, [xo[i] for i in closing])
+                for i, p in zip(closing, pr):
+                    self.priors[active[i]] = p
             active = still
             if not active:
                 break

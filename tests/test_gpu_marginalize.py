@@ -1,0 +1,247 @@
+"""mml_fullwindow_marginalize_batch (frame 0 of n windows marginalized in one device call) and the device build of the dense
+tail (mml_marginalize_dense) against the host: mml_fullwindow_marginalize fed by the loss-free record of
+mml_linearize_window, and the host build of the same routine.  The device runs the host's operations in the host's order, so
+every comparison is bit-equality -- an eigenvector that flips its sign or two eigenvalues that swap places would pass any
+tolerance that rounding needs."""
+import importlib
+
+import numpy as np
+import pytest
+from scipy.spatial.transform import Rotation as Rsc
+
+from conftest import perturbed
+from test_marginalize_dense import corner_systems
+
+pytestmark = pytest.mark.gpu
+
+SLOTS = 12
+K0 = 20
+W_TAN = 3e-4
+
+
+def prior_fields(p):
+    return [np.array(p.J), np.array(p.r0), np.array(p.x0)]
+
+
+def assert_priors_equal(a, b, what=None):
+    for name, u, v in zip(("J", "r0", "x0"), prior_fields(a), prior_fields(b)):
+        assert np.array_equal(u, v), (what, name, np.abs(u - v).max())
+
+
+class Problems:
+    """12 slots of synthetic scans K0 .. K0 + 11, extracted, undistorted, down-sampled and associated at perturbed poses,
+    pre-integrations between consecutive scans, and a prior produced by marginalizing a first solve of the 8-frame window
+    (the set-up of tests/test_gpu_fullwindow_batch.py)."""
+
+    def __init__(self, M, synth, scene):
+        odometry = importlib.import_module("multi-modal-loam_amd.odometry")
+        self.M, self.G = M, synth.GRAVITY
+        self.c = c = M.Context(max_scans=SLOTS)
+        c.map_set_local(0, scene["corner_map"])
+        c.map_set_local(1, scene["surf_map"])
+        west = odometry.WindowEstimator(c, gravity=self.G)
+        self.T_bl = west.T_bl
+        rng = np.random.default_rng(5)
+        x0, self.pres = [], [None]
+        for f in range(SLOTS):
+            k = K0 + f
+            c.scan_upload(f, synth.velo_scan(k), synth.livox_scan(k))
+            c.extract(f, 1)
+            c.undistort(f, 1, np.eye(3).reshape(1, 9), np.zeros((1, 3)))
+            c.downsample(f, 1)
+            T = perturbed(synth.pose_matrix(k), dt=rng.normal(0, 0.02, 3), rotvec=rng.normal(0, 0.003, 3))
+            x0.append(np.concatenate([T[:3, 3], Rsc.from_matrix(T[:3, :3]).as_rotvec(), synth.velocity_at(k) + rng.normal(0, 0.02, 3),
+                                      rng.normal(0, 1e-4, 3), rng.normal(0, 1e-3, 3)]))
+            if f > 0:
+                self.pres.append(M.imu_preintegrate(synth.imu_samples(k - 1, k), np.zeros(3), np.zeros(3)))
+            c.associate(f, 1, west._T_wl(x0[f])[None], 1.0)
+        self.x0 = np.stack(x0)
+        self.prior = None
+        fw = self.make(dict(W=8, first=0))
+        self.x8, _, _ = fw.solve_device(c, 0, self.T_bl, self.x0[:8])
+        self.prior = self.host(fw, 0, self.x8)
+        self.refs = {}
+
+    def make(self, spec):
+        fw = self.M.FullWindowSolver(spec["W"], max_iters=10, fixed=False, huber=spec.get("huber", 0.0), w_tan=W_TAN)
+        for f in range(1, spec["W"]):
+            if f not in spec.get("skip", ()):
+                fw.set_imu(f, self.pres[spec["first"] + f], self.G)
+        if spec.get("prior"):
+            fw.set_prior(self.prior)
+        return fw
+
+    def state(self, spec):
+        """W = 8 on slot 0: the solved state; otherwise the perturbed start of those slots."""
+        if spec["W"] == 8 and spec["first"] == 0:
+            return self.x8
+        return self.x0[spec["first"]:spec["first"] + spec["W"]]
+
+    def host(self, fw, first, x):
+        """mml_fullwindow_marginalize on the record the reference stores: linearised without a loss function."""
+        return fw.marginalize(self.c.linearize_window(first, 1, x[:1], self.T_bl, W_TAN, 0.0)[0], x)
+
+    def ref(self, spec):
+        key = (spec["W"], spec["first"], bool(spec.get("prior")))
+        if key not in self.refs:
+            self.refs[key] = self.host(self.make(dict(spec, huber=0.0)), spec["first"], self.state(spec))
+        return self.refs[key]
+
+    def device(self, specs):
+        fws = [self.make(s) for s in specs]
+        return self.M.fullwindow_marginalize_batch(self.c, fws, [s["first"] for s in specs], self.T_bl, [self.state(s) for s in specs])
+
+
+@pytest.fixture(scope="module")
+def prob(M, synth, scene):
+    p = Problems(M, synth, scene)
+    yield p
+    p.c.close()
+
+
+SETUPS = [dict(W=8, first=0, prior=True), dict(W=3, first=0), dict(W=2, first=0)]
+
+
+def test_smallest_window_without_prior(prob):
+    spec = dict(W=2, first=0)
+    (p,) = prob.device([spec])
+    assert_priors_equal(p, prob.ref(spec))
+    assert np.array_equal(np.array(p.x0), prob.state(spec)[1]) and np.abs(np.array(p.J)).max() > 0
+
+
+def test_window_of_eight_with_prior_at_the_solved_state(prob):
+    spec = SETUPS[0]
+    (p,) = prob.device([spec])
+    assert_priors_equal(p, prob.ref(spec))
+    assert not np.array_equal(np.array(p.J), np.array(prob.ref(dict(W=8, first=0)).J))       # the prior takes part
+    fw = prob.make(spec)                                                                      # the n = 1 method
+    assert_priors_equal(fw.marginalize_device(prob.c, 0, prob.T_bl, prob.state(spec)), prob.ref(spec))
+
+
+def test_huber_of_the_handle_is_ignored(prob):
+    """The lidar factors enter loss-free whatever the handle holds; a record linearised WITH that loss differs."""
+    spec = dict(W=3, first=1, huber=0.05)
+    (p,) = prob.device([spec])
+    assert_priors_equal(p, prob.ref(spec))
+    x = prob.state(spec)
+    lossy = prob.c.linearize_window(1, 1, x[:1], prob.T_bl, W_TAN, 0.05)[0]
+    assert not np.array_equal(lossy[:28], prob.c.linearize_window(1, 1, x[:1], prob.T_bl, W_TAN, 0.0)[0][:28])
+
+
+def test_mixed_batch_on_different_slots_and_on_one(prob):
+    for firsts in ((0, 4, 9), (0, 0, 0)):
+        specs = [dict(s, first=f) for s, f in zip(SETUPS, firsts)]
+        out = prob.device(specs)
+        assert len(out) == 3
+        for spec, p in zip(specs, out):
+            assert_priors_equal(p, prob.ref(spec), spec)
+    fw = prob.make(SETUPS[1])                                                                 # one handle twice: handles are only read
+    out = prob.M.fullwindow_marginalize_batch(prob.c, [fw, fw], [0, 0], prob.T_bl, [prob.state(SETUPS[1])] * 2)
+    for p in out:
+        assert_priors_equal(p, prob.ref(SETUPS[1]))
+
+
+def test_more_windows_than_compute_units(prob):
+    """n = 300: the launch runs in several waves of workgroups and every prior lands in its own entry."""
+    specs = [dict(SETUPS[w % 3], first=w % 5) for w in range(300)]
+    out = prob.device(specs)
+    assert len(out) == 300
+    for w, (spec, p) in enumerate(zip(specs, out)):
+        assert_priors_equal(p, prob.ref(spec), w)
+    # (frames 0 and 1 are all a marginalization reads: W = 3 and W = 2 on one slot agree, the five slots and the prior do not)
+    assert len({np.array(p.J).tobytes() for p in out}) == 10
+
+
+def test_refusals_leave_the_context_usable(prob):
+    M, c = prob.M, prob.c
+    good, x3 = prob.make(SETUPS[1]), prob.state(SETUPS[1])
+    refusals = [
+        ([good, M.FullWindowSolver(1)], [0, 0], [x3, prob.x0[:1]]),                           # W = 1
+        ([good, prob.make(dict(W=3, first=0, skip=(1,)))], [0, 0], [x3, x3]),                 # IMU factor 1 left unset
+        ([good, good], [0, SLOTS], [x3, x3]),                                                 # a slot past the end
+    ]
+    for fws, firsts, xs in refusals:
+        with pytest.raises(M.MmlError) as e:
+            M.fullwindow_marginalize_batch(c, fws, firsts, prob.T_bl, xs)
+        assert e.value.code == M.MML_ERR_INVALID and "window 1" in str(e.value)
+    n = M.FW_BATCH_MAX + 1
+    with pytest.raises(M.MmlError) as e:
+        M.fullwindow_marginalize_batch(c, [good] * n, [0] * n, prob.T_bl, [x3] * n)
+    assert e.value.code == M.MML_ERR_INVALID and "window %d" % M.FW_BATCH_MAX in str(e.value)
+    (p,) = prob.device([SETUPS[0]])
+    assert_priors_equal(p, prob.ref(SETUPS[0]))
+
+
+def test_dense_tail_on_the_device_equals_the_host_routine(prob):
+    """One batch with the eigen-solver's corner cases (tests/test_marginalize_dense.py::corner_systems: diagonal, exact zeros
+    among the off-diagonals, rank 9 and all-zero marginalized blocks, all-zero system, differing triangles, kept eigenvalues
+    around the 1e-8 threshold, 64 random systems with condition numbers up to 1e12)."""
+    cases = corner_systems()
+    A, b = np.stack([s[1] for s in cases]), np.stack([s[2] for s in cases])
+    Jh, rh = prob.M.marginalize_dense(None, A, b)
+    Jd, rd = prob.M.marginalize_dense(prob.c, A, b)
+    for (name, _, _), a, u, v, w in zip(cases, Jh, Jd, rh, rd):
+        assert np.array_equal(a, u), (name, np.abs(a - u).max())
+        assert np.array_equal(v, w), (name, np.abs(v - w).max())
+    assert np.isfinite(Jd).all() and np.isfinite(rd).all()
+
+
+def _frames(M, synth, c, rng, k0, n, W):
+    frames, pres = [], []
+    for w in range(n):
+        frames.append([])
+        pres.append([None])
+        for f in range(W):
+            k, slot = k0 + W * w + f, W * w + f
+            c.scan_upload(slot, synth.velo_scan(k), synth.livox_scan(k))
+            c.extract(slot, 1)
+            c.undistort(slot, 1, np.eye(3).reshape(1, 9), np.zeros((1, 3)))
+            c.downsample(slot, 1)
+            T = perturbed(synth.pose_matrix(k), dt=rng.normal(0, 0.02, 3), rotvec=rng.normal(0, 0.003, 3))
+            q = Rsc.from_matrix(T[:3, :3]).as_quat()
+            frames[w].append(dict(P=T[:3, 3].copy(), Q=-q if q[3] < 0 else q, V=synth.velocity_at(k) + rng.normal(0, 0.02, 3),
+                                  bg=np.zeros(3), ba=np.zeros(3)))
+            if f > 0:
+                pres[w].append(M.imu_preintegrate(synth.imu_samples(k - 1, k), np.zeros(3), np.zeros(3)))
+    return frames, pres
+
+
+def _summaries(info):
+    return [(s.iterations, s.successful, s.termination, s.initial_cost, s.final_cost) for s in info["summaries"]]
+
+
+def test_estimators_with_device_marginalization_equal_the_host_ones(M, synth, scene):
+    """Three windows of W = 3 over two consecutive estimates (the second consumes the priors of the first):
+    BatchWindowEstimator and WindowEstimator with marginalize="device" against marginalize="host", bit for bit."""
+    odometry = importlib.import_module("multi-modal-loam_amd.odometry")
+    n, W = 3, 3
+    c = M.Context(max_scans=n * W)
+    try:
+        c.map_set_local(0, scene["corner_map"])
+        c.map_set_local(1, scene["surf_map"])
+        est = {m: odometry.BatchWindowEstimator(c, n, gravity=synth.GRAVITY, marginalize=m) for m in ("host", "device")}
+        west = {m: odometry.WindowEstimator(c, gravity=synth.GRAVITY, marginalize=m) for m in ("host", "device")}
+        rng = np.random.default_rng(23)
+        slots = [list(range(W * w, W * w + W)) for w in range(n)]
+        copy = lambda fl: [{kk: vv.copy() for kk, vv in fr.items()} for fr in fl]
+        for k0 in (20, 21):
+            frames, pres = _frames(M, synth, c, rng, k0, n, W)
+            fb = {m: [copy(fl) for fl in frames] for m in est}
+            infos = {m: est[m].estimate(slots, fb[m], pres) for m in ("host", "device")}
+            fs = {m: copy(frames[0]) for m in west}
+            winfo = {m: west[m].estimate(slots[0], fs[m], pres[0]) for m in ("host", "device")}
+            for w in range(n):
+                for fh, fd in zip(fb["host"][w], fb["device"][w]):
+                    for key in ("P", "Q", "V", "bg", "ba"):
+                        assert np.array_equal(fh[key], fd[key]), (w, key)
+                ih, idv = infos["host"][w], infos["device"][w]
+                assert (ih["outer"], ih["evaluations"], _summaries(ih)) == (idv["outer"], idv["evaluations"], _summaries(idv))
+                assert_priors_equal(est["device"].priors[w], est["host"].priors[w], w)
+            for fh, fd in zip(fs["host"], fs["device"]):
+                for key in ("P", "Q", "V", "bg", "ba"):
+                    assert np.array_equal(fh[key], fd[key]), key
+            assert (winfo["host"]["outer"], _summaries(winfo["host"])) == (winfo["device"]["outer"], _summaries(winfo["device"]))
+            assert_priors_equal(west["device"].prior, west["host"].prior)
+            assert_priors_equal(west["device"].prior, est["device"].priors[0])                # (same window, same inputs)
+    finally:
+        c.close()
