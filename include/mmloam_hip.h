@@ -570,6 +570,21 @@ int mml_fullwindow_solve_batch(mml_ctx* ctx, int n, mml_fullwindow* const* fws, 
  * buffers for the largest n it has seen (about 20 KB per window). */
 int mml_fullwindow_marginalize_batch(mml_ctx* ctx, int n, mml_fullwindow* const* fws, const int* first_slot, const double* T_bl,
                                      const double* x /* n x MML_FW_X_STRIDE */, mml_prior* priors /* n */);
+/* mml_imu_preintegrate for n intervals in one call -- what feeds the two batch calls above.  Interval i is rows
+ * offsets[i] .. offsets[i+1]-1 of samples (rows of 7 doubles as for mml_imu_preintegrate) with the linearisation biases
+ * bg + 3 i, ba + 3 i; an empty interval gives the reset state (identity Jacobian, zero covariance, dq = (0, 0, 0, 1)).
+ * ctx NULL: the host build of the routine (csrc/imu_preint.h) in a loop, no device needed.  Otherwise one upload, one launch
+ * (a workgroup of one wavefront per interval) and one read-back; the device build runs the host's operations in the host's
+ * order, so the two are bit-identical.  Against mml_imu_preintegrate the routine differs in one place: the right Jacobian
+ * takes its sin / cos from the project's own kernels (csrc/imu_math.h), not from libm, so out[i] has the bytes of the single
+ * call wherever no step rotates by more than 1e-5 rad, and agrees to rounding elsewhere.
+ * Everything is checked before anything is enqueued or written and the message names the interval: MML_ERR_INVALID for
+ * n < 1 or n > MML_PREINT_BATCH_MAX, a null pointer (samples may be NULL when offsets[n] is 0), offsets[0] != 0, a
+ * decreasing offset.  Sample values are not checked, as in the single call.  The context keeps device and pinned buffers for
+ * the largest call it has seen (3.7 KB per interval and 56 bytes per sample). */
+#define MML_PREINT_BATCH_MAX 8192 /* intervals per call */
+int mml_imu_preintegrate_batch(mml_ctx* ctx, int n, const double* samples, const int* offsets /* n + 1 */,
+                               const double* bg /* n x 3 */, const double* ba /* n x 3 */, mml_imu_preint* out /* n */);
 
 /* Number of HIP streams mml_step pipelines its sub-batches over (1..8, default 2 or $MML_LANES).  With 1 every
  * kernel covers the whole batch and runs alone on the device, which is what per-kernel timing wants. */

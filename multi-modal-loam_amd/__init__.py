@@ -26,6 +26,7 @@ MAX_STAGES = 32
 DIGEST_WORDS = 10
 FW_X_STRIDE = 120      # MML_FW_X_STRIDE: doubles per window in the state array of mml_fullwindow_solve_batch
 FW_BATCH_MAX = 1024     # MML_FW_BATCH_MAX: windows per call
+PREINT_BATCH_MAX = 8192  # MML_PREINT_BATCH_MAX: intervals per call of mml_imu_preintegrate_batch
 
 LIVOX_DTYPE = np.dtype([("offset_time", "<u4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4"),
                         ("reflectivity", "u1"), ("tag", "u1"), ("line", "u1"), ("_pad", "u1")])
@@ -221,6 +222,9 @@ def lib():
             L.mml_fullwindow_marginalize_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
             L.mml_marginalize_dense.restype = C.c_int
             L.mml_marginalize_dense.argtypes = [C.c_void_p, C.c_long] + [C.c_void_p] * 4
+        if hasattr(L, "mml_imu_preintegrate_batch"):
+            L.mml_imu_preintegrate_batch.restype = C.c_int
+            L.mml_imu_preintegrate_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
         _lib = L
     return _lib
 
@@ -703,6 +707,30 @@ def imu_preintegrate(samples, bg, ba):
     if rc != MML_OK:
         raise MmlError(rc, "mml_imu_preintegrate")
     return out
+
+
+def imu_preintegrate_batch(samples_list, bg, ba, ctx=None):
+    """mml_imu_preintegrate_batch: imu_preintegrate for a list of intervals in one call.  samples_list[i]: (k_i, 7), k_i >= 0;
+    bg, ba: one vector for all intervals or one per interval (n, 3).  ctx None: the host routine (no device needed); a
+    Context: one upload, one launch, one read-back, bit-identical to it.  Returns a list of ImuPreint."""
+    n = len(samples_list)
+    smp = [_f64(s).reshape(-1, 7) for s in samples_list]
+    offsets = np.concatenate([[0], np.cumsum([len(s) for s in smp])]).astype(np.int32)
+    flat = _f64(np.concatenate(smp)) if offsets[-1] else np.zeros((1, 7))
+    bias = []
+    for name, b in (("bg", bg), ("ba", ba)):
+        b = np.asarray(b, dtype=np.float64)
+        if b.shape not in ((3,), (n, 3)):
+            raise ValueError("%s must be one vector or one per interval (%d, 3), not %s" % (name, n, b.shape))
+        bias.append(np.ascontiguousarray(np.broadcast_to(b, (n, 3))))
+    out = (ImuPreint * max(n, 1))()
+    rc = lib().mml_imu_preintegrate_batch(ctx._h if ctx is not None else None, C.c_int(n), _p(flat), _p(offsets), _p(bias[0]),
+                                          _p(bias[1]), out)
+    if ctx is not None:
+        ctx._ck(rc)
+    elif rc != MML_OK:
+        raise MmlError(rc, "mml_imu_preintegrate_batch")
+    return [ImuPreint.from_buffer_copy(out[i]) for i in range(n)]
 
 
 def imu_factor(pre, gravity, pr_i, vb_i, pr_j, vb_j, jac=True):

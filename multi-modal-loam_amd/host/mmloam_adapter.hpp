@@ -702,6 +702,31 @@ class IMUIntegrator {
         dq.x = pre.dq[0], dq.y = pre.dq[1], dq.z = pre.dq[2], dq.w = pre.dq[3];
         has_pre = true;
     }
+    // PreIntegration() of many integrators in one mml_imu_preintegrate_batch call: integrators[i] with the biases bg[i] / ba[i].
+    // ctx null: the host routine; otherwise one device call, bit-identical to it.  Every integrator is left as PreIntegration
+    // leaves it; `out` (may be null) also receives the results in order.
+    static void PreIntegrationBatch(mml_ctx* ctx, const std::vector<IMUIntegrator*>& integrators, const std::vector<Vector3d>& bg,
+                                    const std::vector<Vector3d>& ba, std::vector<mml_imu_preint>* out = nullptr) {
+        const size_t n = integrators.size();
+        if (bg.size() != n || ba.size() != n) throw std::runtime_error("PreIntegrationBatch: one bg and one ba per integrator");
+        std::vector<double> smp, b(6 * n);
+        std::vector<int> offsets(1, 0);
+        for (size_t i = 0; i < n; ++i) {
+            smp.insert(smp.end(), integrators[i]->msgs.begin(), integrators[i]->msgs.end());
+            offsets.push_back(offsets.back() + integrators[i]->size());
+            for (int k = 0; k < 3; ++k) b[3 * i + k] = bg[i].v[k], b[3 * (n + i) + k] = ba[i].v[k];
+        }
+        std::vector<mml_imu_preint> pre(n);
+        check(ctx, mml_imu_preintegrate_batch(ctx, (int)n, smp.data(), offsets.data(), b.data(), b.data() + 3 * n, pre.data()),
+              "mml_imu_preintegrate_batch");
+        for (size_t i = 0; i < n; ++i) {
+            IMUIntegrator& it = *integrators[i];
+            it.pre = pre[i];
+            it.dq.x = pre[i].dq[0], it.dq.y = pre[i].dq[1], it.dq.z = pre[i].dq[2], it.dq.w = pre[i].dq[3];
+            it.has_pre = true;
+        }
+        if (out) *out = pre;
+    }
     // GetAverageAcc (:168-181): the mean of the first 31 messages' linear_acceleration * gnorm
     Vector3d GetAverageAcc() const {
         Vector3d s{{0, 0, 0}};

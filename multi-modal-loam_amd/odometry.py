@@ -307,6 +307,27 @@ class BatchWindowEstimator:
         return infos
 
 
+def preintegrate_windows(samples, frames, ctx=None):
+    """The pre-integrations of n windows from ONE mml_imu_preintegrate_batch call, in the shape BatchWindowEstimator.estimate
+    takes: samples[w][f] (f >= 1; entry 0 is not read) are the IMU messages between frames f-1 and f of window w, (k, 7),
+    linearised at frames[w][f-1]["bg"] / ["ba"].  Returns preints with preints[w][0] None and preints[w][f] an ImuPreint.
+    ctx None: the host routine; a Context: the device call, bit-identical to it."""
+    import importlib
+    M = importlib.import_module(__package__)
+    if len(samples) != len(frames):
+        raise ValueError("samples and frames must have one entry per window (%d, %d)" % (len(samples), len(frames)))
+    flat, bg, ba = [], [], []
+    for w, (sw, fw) in enumerate(zip(samples, frames)):
+        if len(sw) != len(fw):
+            raise ValueError("window %d: samples and frames differ in length" % w)
+        for f in range(1, len(fw)):
+            flat.append(sw[f])
+            bg.append(fw[f - 1]["bg"])
+            ba.append(fw[f - 1]["ba"])
+    pres = iter(M.imu_preintegrate_batch(flat, np.stack(bg), np.stack(ba), ctx) if flat else [])
+    return [[None] + [next(pres) for _ in range(1, len(fw))] for fw in frames]
+
+
 def try_map_initialization(frames, samples, exTlb=None):
     """TryMAPInitialization (unionPoseEstimation.cpp:425-625) through mml_lio_initialize.  frames: the reference's frame
     list, front first, as dicts in the shape WindowEstimator.estimate uses (P, Q as x y z w = the lidar pose, V, bg, ba)
