@@ -2,6 +2,8 @@
 // No compute lives here; every entry point validates, stages small parameter blocks through a pinned ring and
 // enqueues the kernels of feature.hip / undistort_voxel.hip / map_assoc.hip / solve.hip on the ctx stream.
 #include <math.h>
+#include <stdarg.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -60,6 +62,18 @@ hipError_t read_settings(mml_ctx* ctx) {
 }  // namespace
 
 double* mml_stage_alloc(mml_ctx* ctx, size_t doubles) { return stage_alloc(ctx, doubles); }
+
+int mml_refuse(mml_ctx* ctx, int code, const char* fmt, ...) {
+    if (ctx) {  // (a NULL context has nowhere to carry the message)
+        char m[192];
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(m, sizeof(m), fmt, ap);
+        va_end(ap);
+        ctx->err = m;
+    }
+    return code;
+}
 
 extern "C" {
 

@@ -6,10 +6,11 @@
 // factors; here the Ceres 2.1 TRADITIONAL_DOGLEG iteration is a device-resident state machine advanced by two kernels
 // per evaluation, enqueued max_iterations + 1 times without reading anything back (a finished state machine turns the
 // remaining launches into no-ops):
-//   k_fw_eval   2 W workgroups.  Workgroup f < W: the lidar factors of frame f at the candidate (lidar_eval.h) -> its
-//               28-value record.  Workgroup W + f: IMU factor f -- residual and Jacobian on one lane (imu_math.h, the
-//               code the host solver runs), then the sqrt-information products and the 30 x 30 J^T J / J^T r of the
-//               factor element-parallel; workgroup W: the prior residual and its J^T r.
+//   k_fw_eval   2 W workgroups.  Workgroup f < W: the lidar factors of frame f at the candidate (lidar_eval.h
+//               frame_record) -> its 28-value record.  Workgroup W + f: IMU factor f -- residual and Jacobian on one lane
+//               (imu_math.h, the code the host solver runs), then the sqrt-information products (imu_math.h imu_whiten,
+//               the host's too) and the 30 x 30 J^T J / J^T r of the factor element-parallel; workgroup W: the prior
+//               residual and its J^T r.
 //   k_fw_step   1 workgroup.  Adds the pieces into the normal equations in the order the host assembly adds them
 //               (lidar, IMU f, IMU f + 1, prior).  The 15 W system is block tridiagonal (a factor couples consecutive
 //               frames only), so H lives as a band of three 15-column blocks per row, in LDS.  Accept / reject the
@@ -26,8 +27,11 @@
 // is its n = 1 case.  A window's workgroups touch that window's records only, so its arithmetic does not depend on
 // what else is in the batch.
 //   k_fw_marginalize   n workgroups.  Frame 0 of window w marginalized into the next prior (mml_fullwindow_marginalize_batch):
-//               the loss-free lidar record of frame 0, prior and IMU factor 1, the 30 x 30 system, then the dense tail of
-//               marg_dense.h -- the routine the host function runs -- on one wavefront; bit-identical to the host.
+//               the loss-free lidar record of frame 0 (frame_record), prior and IMU factor 1 (imu_whiten), the 30 x 30
+//               system, then the dense tail of marg_dense.h -- the routine the host function runs -- on one wavefront;
+//               bit-identical to the host.
+// Host side: the per-call buffers are MmlStaging pairs (mml_internal.h: device array + pinned twin, grow-only), refusals go
+// through mml_refuse, and a prior crosses between handle, parameter block and ABI as one mml_prior.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -153,11 +157,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_fw_eval(FwKernelArgs A) {
         const int b = P->first + blk;
         if (tid < 6) s_x[tid] = G->v.xc[15 * blk + tid];
         __syncthreads();
-        Pose pose;
-        make_pose(s_x, P->Tbl, pose);
-        double acc[28];
-        eval_frame(A.lf + (size_t)b * A.MF, A.ft_n[b], A.pf + (size_t)b * A.MF, A.ft_n[A.B + b], pose, P->w_tan, P->huber, acc);
-        block_reduce28(acc, s_part, G->rec[blk]);
+        frame_record(A.lf, A.pf, A.ft_n, A.B, A.MF, b, s_x, P->Tbl, P->w_tan, P->huber, s_part, G->rec[blk]);
         return;
     }
     const int f = blk - W;
@@ -183,21 +183,10 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_fw_eval(FwKernelArgs A) {
     __syncthreads();
     if (tid == 0) imu_raw(&P->imu[f], P->gravity, s_x, s_x + 6, s_x + 15, s_x + 21, s_r, s_J);
     __syncthreads();
-    // eResiduals.applyOnTheLeft(sqrt_information), the same for the Jacobian (ceresfunc.h:352,388-391)
-    const double* U = P->U[f];
-    for (int o = tid; o < 465; o += SOLVE_THREADS) {
-        double s = 0;
-        if (o < 450) {
-            const int i = o / 30, c = o - 30 * i;
-            for (int k = i; k < 15; ++k) s += U[i * 15 + k] * s_J[k * 30 + c];
-            s_Js[o] = s;
-        } else {
-            const int i = o - 450;
-            for (int k = i; k < 15; ++k) s += U[i * 15 + k] * s_r[k];
-            s_rs[i] = s;
-        }
-    }
+    for (int o = tid; o < 465; o += SOLVE_THREADS) (o < 450 ? s_Js[o] : s_rs[o - 450]) = imu_whiten(P->U[f], s_J, s_r, o);
     __syncthreads();
+    // (each product is summed on its own and handed to k_fw_step, which adds the pieces as the host's assemble does; the
+    //  marginalization accumulates prior, IMU and lidar terms in ONE running value -- two orders, each held by a byte-equality test)
     for (int o = tid; o < 931; o += SOLVE_THREADS) {
         if (o < 900) {
             const int a = o / 30, b = o - 30 * a;
@@ -747,11 +736,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_fw_record0(FwKernelArgs A, co
     const FwDevParams* P = A.P + blockIdx.x;
     const int b = P->first;
     record += 32 * (size_t)blockIdx.x;
-    Pose pose;
-    make_pose(A.out[blockIdx.x].x, P->Tbl, pose);
-    double acc[28];
-    eval_frame(A.lf + (size_t)b * A.MF, A.ft_n[b], A.pf + (size_t)b * A.MF, A.ft_n[A.B + b], pose, P->w_tan, P->huber, acc);
-    block_reduce28(acc, s_part, s_out);
+    frame_record(A.lf, A.pf, A.ft_n, A.B, A.MF, b, A.out[blockIdx.x].x, P->Tbl, P->w_tan, P->huber, s_part, s_out);
     if (threadIdx.x < 28) record[threadIdx.x] = s_out[threadIdx.x];
     if (threadIdx.x == 0) {
         record[28] = stats[16 * b + 2];
@@ -796,30 +781,14 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_fw_marginalize(const FwMargPa
     const int tid = threadIdx.x, b0 = P->first, has_prior = P->has_prior;
     if (tid < 30) sh.x[tid] = P->x[tid];
     __syncthreads();
-    {
-        Pose pose;
-        make_pose(sh.x, P->Tbl, pose);
-        double acc[28];
-        eval_frame(lf + (size_t)b0 * MF, ft_n[b0], pf + (size_t)b0 * MF, ft_n[B + b0], pose, P->w_tan, P->huber, acc);
-        block_reduce28(acc, sh.part, sh.rec);
-    }
+    frame_record(lf, pf, ft_n, B, MF, b0, sh.x, P->Tbl, P->w_tan, P->huber, sh.part, sh.rec);
     if (tid == 0 && has_prior) prior_residual(P->prior, sh.x, sh.rp);
     if (tid == 64) imu_raw(&P->imu, P->gravity, sh.x, sh.x + 6, sh.x + 15, sh.x + 21, sh.r, sh.J);
     __syncthreads();
-    // eResiduals.applyOnTheLeft(sqrt_information), the same for the Jacobian (ceresfunc.h:352,388-391)
-    for (int o = tid; o < 465; o += SOLVE_THREADS) {
-        double s = 0;
-        if (o < 450) {
-            const int i = o / 30, c = o - 30 * i;
-            for (int k = i; k < 15; ++k) s += P->U[i * 15 + k] * sh.J[k * 30 + c];
-            sh.Js[o] = s;
-        } else {
-            const int i = o - 450;
-            for (int k = i; k < 15; ++k) s += P->U[i * 15 + k] * sh.r[k];
-            sh.rs[i] = s;
-        }
-    }
+    for (int o = tid; o < 465; o += SOLVE_THREADS) (o < 450 ? sh.Js[o] : sh.rs[o - 450]) = imu_whiten(P->U, sh.J, sh.r, o);
     __syncthreads();
+    // (prior, IMU and lidar terms go into ONE running value, as in the host's mml_fullwindow_marginalize; k_fw_eval / assemble form
+    //  each product as a sum of its own and add it afterwards -- two orders, each held by a byte-equality test: keep them apart)
     for (int o = tid; o < 930; o += SOLVE_THREADS) {
         double h = 0.0;
         if (o < 900) {
@@ -858,133 +827,73 @@ constexpr int FW_MAX_ROUNDS = 1001;  // max_num_iterations <= 1000
 
 }  // namespace
 
-struct MmlFwDev {  // sized for `cap` windows, the largest batch seen
-    int cap = 0;
-    FwDevParams* d_par = nullptr;
-    FwGlobal* d_state = nullptr;
-    FwDevOut* d_out = nullptr;
-    int* d_alive = nullptr;        // FW_MAX_ROUNDS
-    double* d_rec0 = nullptr;      // cap x 32
-    FwDevParams* h_par = nullptr;  // pinned
-    FwDevOut* h_out = nullptr;     // pinned
-    double* h_rec0 = nullptr;      // pinned
-    // mml_fullwindow_marginalize_batch, sized for `mcap` windows
-    int mcap = 0;
-    FwMargParams* d_mpar = nullptr;
-    mml_prior* d_mout = nullptr;
-    FwMargParams* h_mpar = nullptr;  // pinned
-    mml_prior* h_mout = nullptr;     // pinned
+struct MmlFwDev {  // every buffer holds the largest batch its call has seen; the two sets grow independently
+    MmlStaging<FwDevParams> par;
+    MmlStaging<FwGlobal, false> state;
+    MmlStaging<FwDevOut> out;
+    MmlStaging<int, false> alive;  // FW_MAX_ROUNDS
+    MmlStaging<double> rec0;       // 32 per window
+    // mml_fullwindow_marginalize_batch
+    MmlStaging<FwMargParams> mpar;
+    MmlStaging<mml_prior> mout;
 };
 
-static void fw_marg_free(MmlFwDev* d) {
-    if (d->d_mpar) hipFree(d->d_mpar);
-    if (d->d_mout) hipFree(d->d_mout);
-    if (d->h_mpar) hipHostFree(d->h_mpar);
-    if (d->h_mout) hipHostFree(d->h_mout);
-    d->d_mpar = d->h_mpar = nullptr;
-    d->d_mout = d->h_mout = nullptr;
-    d->mcap = 0;
-}
-
-static void fw_free(MmlFwDev* d) {
-    fw_marg_free(d);
-    if (d->d_par) hipFree(d->d_par);
-    if (d->d_state) hipFree(d->d_state);
-    if (d->d_out) hipFree(d->d_out);
-    if (d->d_alive) hipFree(d->d_alive);
-    if (d->d_rec0) hipFree(d->d_rec0);
-    if (d->h_par) hipHostFree(d->h_par);
-    if (d->h_out) hipHostFree(d->h_out);
-    if (d->h_rec0) hipHostFree(d->h_rec0);
-    *d = MmlFwDev();
+static MmlFwDev* fw_dev(mml_ctx* ctx) {
+    if (!ctx->fwdev) ctx->fwdev = new MmlFwDev();
+    return ctx->fwdev;
 }
 
 void mml_fullwindow_dev_release(mml_ctx* ctx) {
     MmlFwDev* d = ctx->fwdev;
     if (!d) return;
-    fw_free(d);
+    d->par.release();
+    d->state.release();
+    d->out.release();
+    d->alive.release();
+    d->rec0.release();
+    d->mpar.release();
+    d->mout.release();
     delete d;
     ctx->fwdev = nullptr;
 }
-
-// buffers for n windows (they only grow)
-static int fw_reserve(mml_ctx* ctx, int n) {
-    if (!ctx->fwdev) ctx->fwdev = new MmlFwDev();
-    MmlFwDev* d = ctx->fwdev;
-    if (n <= d->cap) return MML_OK;
-    fw_free(d);  // (every call drains the stream before it returns: nothing is in flight)
-    MML_HIP(hipMalloc(reinterpret_cast<void**>(&d->d_par), sizeof(FwDevParams) * n));
-    MML_HIP(hipMalloc(reinterpret_cast<void**>(&d->d_state), sizeof(FwGlobal) * n));
-    MML_HIP(hipMalloc(reinterpret_cast<void**>(&d->d_out), sizeof(FwDevOut) * n));
-    MML_HIP(hipMalloc(reinterpret_cast<void**>(&d->d_alive), sizeof(int) * FW_MAX_ROUNDS));
-    MML_HIP(hipMalloc(reinterpret_cast<void**>(&d->d_rec0), sizeof(double) * 32 * n));
-    MML_HIP(hipHostMalloc(reinterpret_cast<void**>(&d->h_par), sizeof(FwDevParams) * n, hipHostMallocDefault));
-    MML_HIP(hipHostMalloc(reinterpret_cast<void**>(&d->h_out), sizeof(FwDevOut) * n, hipHostMallocDefault));
-    MML_HIP(hipHostMalloc(reinterpret_cast<void**>(&d->h_rec0), sizeof(double) * 32 * n, hipHostMallocDefault));
-    d->cap = n;
-    return MML_OK;
-}
-
-static int fw_marg_reserve(mml_ctx* ctx, int n) {
-    if (!ctx->fwdev) ctx->fwdev = new MmlFwDev();
-    MmlFwDev* d = ctx->fwdev;
-    if (n <= d->mcap) return MML_OK;
-    fw_marg_free(d);  // (every call drains the stream before it returns: nothing is in flight)
-    MML_HIP(hipMalloc(reinterpret_cast<void**>(&d->d_mpar), sizeof(FwMargParams) * n));
-    MML_HIP(hipMalloc(reinterpret_cast<void**>(&d->d_mout), sizeof(mml_prior) * n));
-    MML_HIP(hipHostMalloc(reinterpret_cast<void**>(&d->h_mpar), sizeof(FwMargParams) * n, hipHostMallocDefault));
-    MML_HIP(hipHostMalloc(reinterpret_cast<void**>(&d->h_mout), sizeof(mml_prior) * n, hipHostMallocDefault));
-    d->mcap = n;
-    return MML_OK;
-}
-
-#define FW_REFUSE(cond, code, w, what)                                       \
-    do {                                                                     \
-        if (!(cond)) {                                                       \
-            char m_[192];                                                    \
-            snprintf(m_, sizeof(m_), "%s: window %d: %s", who, (w), (what)); \
-            ctx->err = m_;                                                   \
-            return (code);                                                   \
-        }                                                                    \
-    } while (0)
 
 // n windows, window w in x + x_stride w; everything is checked before anything is enqueued
 static int fw_solve_batch(mml_ctx* ctx, const char* who, int n, mml_fullwindow* const* fws, const int* first_slot,
                           const double* T_bl, double* x, size_t x_stride, mml_solve_summary* summaries, int* evaluations,
                           double* records0) {
     int Wmax = 0, rounds = 0;
+    const auto refuse = [&](int code, int w, const char* what) { return mml_refuse(ctx, code, "%s: window %d: %s", who, w, what); };
     {
         std::vector<std::pair<const mml_fullwindow*, int>> seen(n);
         for (int w = 0; w < n; ++w) {
             const mml_fullwindow* fw = fws[w];
-            FW_REFUSE(fw, MML_ERR_INVALID, w, "null handle");
+            if (!fw) return refuse(MML_ERR_INVALID, w, "null handle");
             const int W = fw->W;
-            FW_REFUSE(W >= 1 && W <= MAXW && first_slot[w] >= 0 && first_slot[w] <= ctx->B - W, MML_ERR_INVALID, w,
-                      "window does not fit the scan slots");
-            FW_REFUSE(fw->opts.max_num_iterations >= 0 && fw->opts.max_num_iterations <= FW_MAX_ROUNDS - 1, MML_ERR_INVALID, w,
-                      "max_num_iterations out of range");
+            if (!(W >= 1 && W <= MAXW && first_slot[w] >= 0 && first_slot[w] <= ctx->B - W))
+                return refuse(MML_ERR_INVALID, w, "window does not fit the scan slots");
+            if (!(fw->opts.max_num_iterations >= 0 && fw->opts.max_num_iterations <= FW_MAX_ROUNDS - 1))
+                return refuse(MML_ERR_INVALID, w, "max_num_iterations out of range");
             for (int f = 1; f < W; ++f)
-                FW_REFUSE(!fw->have_imu[f] || fw->U_ok[f], MML_ERR_STATE, w, "pre-integration covariance is not positive definite");
+                if (fw->have_imu[f] && !fw->U_ok[f]) return refuse(MML_ERR_STATE, w, "pre-integration covariance is not positive definite");
             seen[w] = {fw, w};
             Wmax = std::max(Wmax, W);
             rounds = std::max(rounds, fw->opts.max_num_iterations + 1);
         }
         std::sort(seen.begin(), seen.end());
         for (int i = 1; i < n; ++i)
-            FW_REFUSE(seen[i].first != seen[i - 1].first, MML_ERR_INVALID, seen[i].second, "the same handle appears twice in the batch");
+            if (seen[i].first == seen[i - 1].first) return refuse(MML_ERR_INVALID, seen[i].second, "the same handle appears twice in the batch");
     }
     MML_HIP(hipSetDevice(ctx->device));
-    {
-        const int rc = fw_reserve(ctx, n);
-        if (rc != MML_OK) return rc;
-    }
-    MmlFwDev* d = ctx->fwdev;
+    MmlFwDev* d = fw_dev(ctx);
+    if (d->par.reserve(ctx, n) || d->state.reserve(ctx, n) || d->out.reserve(ctx, n) || d->alive.reserve(ctx, FW_MAX_ROUNDS) ||
+        d->rec0.reserve(ctx, 32 * (size_t)n))
+        return MML_ERR_HIP;
     // the per-window parameter blocks, staged in pinned memory; only what the kernels read is written (the flags of the
     // header gate every optional part)
     for (int w = 0; w < n; ++w) {
         const mml_fullwindow* fw = fws[w];
         const int W = fw->W;
-        FwDevParams& p = d->h_par[w];
+        FwDevParams& p = d->par.h[w];
         memset(&p, 0, offsetof(FwDevParams, x));
         p.W = W;
         p.max_iters = fw->opts.max_num_iterations;
@@ -997,13 +906,11 @@ static int fw_solve_batch(mml_ctx* ctx, const char* who, int n, mml_fullwindow* 
         memcpy(p.x, x + x_stride * w, sizeof(double) * 15 * W);
         p.has_prior = fw->prior.valid ? 1 : 0;
         if (fw->prior.valid) {
-            memcpy(p.prior.J, fw->prior.J, sizeof(p.prior.J));
-            memcpy(p.prior.r0, fw->prior.r0, sizeof(p.prior.r0));
-            memcpy(p.prior.x0, fw->prior.x0, sizeof(p.prior.x0));
+            p.prior = fw->prior.p;
             for (int a = 0; a < 15; ++a)
                 for (int b = 0; b < 15; ++b) {
                     double h = 0;
-                    for (int i = 0; i < 15; ++i) h += fw->prior.J[i * 15 + a] * fw->prior.J[i * 15 + b];
+                    for (int i = 0; i < 15; ++i) h += p.prior.J[i * 15 + a] * p.prior.J[i * 15 + b];
                     p.PP[a * 15 + b] = h;
                 }
         }
@@ -1021,13 +928,13 @@ static int fw_solve_batch(mml_ctx* ctx, const char* who, int n, mml_fullwindow* 
             if (rs != MML_OK) return rs;
         }
     MmlStageScope t(ctx, "fullwindow");
-    MML_HIP(hipMemcpyAsync(d->d_par, d->h_par, sizeof(FwDevParams) * n, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_fw_init, dim3(1, n), dim3(128), 0, s, d->d_par, d->d_state, d->d_alive, rounds);
+    MML_HIP(hipMemcpyAsync(d->par.d, d->par.h, sizeof(FwDevParams) * n, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_fw_init, dim3(1, n), dim3(128), 0, s, d->par.d, d->state.d, d->alive.d, rounds);
     FwKernelArgs a;
-    a.P = d->d_par;
-    a.G = d->d_state;
-    a.out = d->d_out;
-    a.alive = d->d_alive;
+    a.P = d->par.d;
+    a.G = d->state.d;
+    a.out = d->out.d;
+    a.alive = d->alive.d;
     a.ft_n = ctx->ft_n;
     a.lf = ctx->lf;
     a.pf = ctx->pf;
@@ -1044,21 +951,21 @@ static int fw_solve_batch(mml_ctx* ctx, const char* who, int n, mml_fullwindow* 
         hipLaunchKernelGGL(k_fw_step, dim3(1, n), dim3(FW_THREADS), 0, s, a);
         if (a.poll) {
             MML_HIP(hipGetLastError());
-            MML_HIP(hipMemcpyAsync(&d->h_out->pad_, d->d_alive + r, sizeof(int), hipMemcpyDeviceToHost, s));
+            MML_HIP(hipMemcpyAsync(&d->out.h->pad_, d->alive.d + r, sizeof(int), hipMemcpyDeviceToHost, s));
             MML_HIP(hipStreamSynchronize(s));
-            if (!d->h_out->pad_) break;
+            if (!d->out.h->pad_) break;
         }
     }
-    if (records0) hipLaunchKernelGGL(k_fw_record0, dim3(n), dim3(SOLVE_THREADS), 0, s, a, ctx->assoc_stats, d->d_rec0);
+    if (records0) hipLaunchKernelGGL(k_fw_record0, dim3(n), dim3(SOLVE_THREADS), 0, s, a, ctx->assoc_stats, d->rec0.d);
     MML_HIP(hipGetLastError());
-    MML_HIP(hipMemcpyAsync(d->h_out, d->d_out, sizeof(FwDevOut) * n, hipMemcpyDeviceToHost, s));
-    if (records0) MML_HIP(hipMemcpyAsync(d->h_rec0, d->d_rec0, sizeof(double) * 32 * n, hipMemcpyDeviceToHost, s));
+    MML_HIP(hipMemcpyAsync(d->out.h, d->out.d, sizeof(FwDevOut) * n, hipMemcpyDeviceToHost, s));
+    if (records0) MML_HIP(hipMemcpyAsync(d->rec0.h, d->rec0.d, sizeof(double) * 32 * n, hipMemcpyDeviceToHost, s));
     MML_HIP(hipStreamSynchronize(s));
-    if (records0) memcpy(records0, d->h_rec0, sizeof(double) * 32 * n);
+    if (records0) memcpy(records0, d->rec0.h, sizeof(double) * 32 * n);
     for (int w = 0; w < n; ++w) {
         mml_fullwindow* fw = fws[w];
         const int W = fw->W;
-        const FwDevOut& o = d->h_out[w];
+        const FwDevOut& o = d->out.h[w];
         double* xw = x + x_stride * w;
 #ifdef MML_FW_TIMING
         {
@@ -1106,43 +1013,29 @@ extern "C" int mml_fullwindow_solve_batch(mml_ctx* ctx, int n, mml_fullwindow* c
                           records0);
 }
 
-// the same refusal without a context to carry the message (the argument checks come before anything needs one)
-#define FW_MARG_REFUSE(cond, code, w, what)                                                                  \
-    do {                                                                                                     \
-        if (!(cond)) {                                                                                       \
-            if (ctx) {                                                                                       \
-                char m_[192];                                                                                \
-                snprintf(m_, sizeof(m_), "mml_fullwindow_marginalize_batch: window %d: %s", (w), (what));    \
-                ctx->err = m_;                                                                               \
-            }                                                                                                \
-            return (code);                                                                                   \
-        }                                                                                                    \
-    } while (0)
-
 extern "C" int mml_fullwindow_marginalize_batch(mml_ctx* ctx, int n, mml_fullwindow* const* fws, const int* first_slot,
                                                 const double* T_bl, const double* x, mml_prior* priors) {
-    if (n < 1 || !fws || !first_slot || !T_bl || !x || !priors) {
-        if (ctx) ctx->err = "mml_fullwindow_marginalize_batch: n < 1 or a null argument";
-        return MML_ERR_INVALID;
-    }
-    FW_MARG_REFUSE(n <= MML_FW_BATCH_MAX, MML_ERR_INVALID, MML_FW_BATCH_MAX, "the batch holds more than MML_FW_BATCH_MAX windows");
+    if (n < 1 || !fws || !first_slot || !T_bl || !x || !priors)
+        return mml_refuse(ctx, MML_ERR_INVALID, "mml_fullwindow_marginalize_batch: n < 1 or a null argument");
+    // (the argument checks come before anything needs a context; without one the refusal carries no message)
+    const auto refuse = [&](int code, int w, const char* what) {
+        return mml_refuse(ctx, code, "mml_fullwindow_marginalize_batch: window %d: %s", w, what);
+    };
+    if (n > MML_FW_BATCH_MAX) return refuse(MML_ERR_INVALID, MML_FW_BATCH_MAX, "the batch holds more than MML_FW_BATCH_MAX windows");
     for (int w = 0; w < n; ++w) {
         const mml_fullwindow* fw = fws[w];
-        FW_MARG_REFUSE(fw, MML_ERR_INVALID, w, "null handle");
-        FW_MARG_REFUSE(fw->W >= 2, MML_ERR_INVALID, w, "a window of one frame has nothing to marginalize");
-        FW_MARG_REFUSE(fw->have_imu[1], MML_ERR_INVALID, w, "no IMU factor between frames 0 and 1");
-        FW_MARG_REFUSE(ctx && first_slot[w] >= 0 && first_slot[w] < ctx->B, MML_ERR_INVALID, w, "slot out of range");
-        FW_MARG_REFUSE(fw->U_ok[1], MML_ERR_STATE, w, "pre-integration covariance is not positive definite");
+        if (!fw) return refuse(MML_ERR_INVALID, w, "null handle");
+        if (fw->W < 2) return refuse(MML_ERR_INVALID, w, "a window of one frame has nothing to marginalize");
+        if (!fw->have_imu[1]) return refuse(MML_ERR_INVALID, w, "no IMU factor between frames 0 and 1");
+        if (!(ctx && first_slot[w] >= 0 && first_slot[w] < ctx->B)) return refuse(MML_ERR_INVALID, w, "slot out of range");
+        if (!fw->U_ok[1]) return refuse(MML_ERR_STATE, w, "pre-integration covariance is not positive definite");
     }
     MML_HIP(hipSetDevice(ctx->device));
-    {
-        const int rc = fw_marg_reserve(ctx, n);
-        if (rc != MML_OK) return rc;
-    }
-    MmlFwDev* d = ctx->fwdev;
+    MmlFwDev* d = fw_dev(ctx);
+    if (d->mpar.reserve(ctx, n) || d->mout.reserve(ctx, n)) return MML_ERR_HIP;
     for (int w = 0; w < n; ++w) {  // only what the kernel reads is written (has_prior gates the prior)
         const mml_fullwindow* fw = fws[w];
-        FwMargParams& p = d->h_mpar[w];
+        FwMargParams& p = d->mpar.h[w];
         p.first = first_slot[w];
         p.has_prior = fw->prior.valid ? 1 : 0;
         p.w_tan = fw->opts.plan_weight_tan;
@@ -1150,23 +1043,19 @@ extern "C" int mml_fullwindow_marginalize_batch(mml_ctx* ctx, int n, mml_fullwin
         memcpy(p.gravity, fw->gravity, sizeof(p.gravity));
         memcpy(p.Tbl, T_bl, sizeof(p.Tbl));
         memcpy(p.x, x + (size_t)MML_FW_X_STRIDE * w, sizeof(p.x));
-        if (fw->prior.valid) {
-            memcpy(p.prior.J, fw->prior.J, sizeof(p.prior.J));
-            memcpy(p.prior.r0, fw->prior.r0, sizeof(p.prior.r0));
-            memcpy(p.prior.x0, fw->prior.x0, sizeof(p.prior.x0));
-        }
+        if (fw->prior.valid) p.prior = fw->prior.p;
         p.imu = fw->imu[1];
         memcpy(p.U, &fw->U[225], sizeof(p.U));
     }
     hipStream_t s = MML_STREAM(ctx);
     MmlStageScope t(ctx, "fullwindow_marginalize");
-    MML_HIP(hipMemcpyAsync(d->d_mpar, d->h_mpar, sizeof(FwMargParams) * n, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_fw_marginalize, dim3(n), dim3(SOLVE_THREADS), 0, s, d->d_mpar, d->d_mout, ctx->ft_n, ctx->lf, ctx->pf, ctx->B,
+    MML_HIP(hipMemcpyAsync(d->mpar.d, d->mpar.h, sizeof(FwMargParams) * n, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_fw_marginalize, dim3(n), dim3(SOLVE_THREADS), 0, s, d->mpar.d, d->mout.d, ctx->ft_n, ctx->lf, ctx->pf, ctx->B,
                        ctx->MF);
     MML_HIP(hipGetLastError());
-    MML_HIP(hipMemcpyAsync(d->h_mout, d->d_mout, sizeof(mml_prior) * n, hipMemcpyDeviceToHost, s));
+    MML_HIP(hipMemcpyAsync(d->mout.h, d->mout.d, sizeof(mml_prior) * n, hipMemcpyDeviceToHost, s));
     MML_HIP(hipStreamSynchronize(s));
-    memcpy(priors, d->h_mout, sizeof(mml_prior) * n);
+    memcpy(priors, d->mout.h, sizeof(mml_prior) * n);
     return MML_OK;
 }
 

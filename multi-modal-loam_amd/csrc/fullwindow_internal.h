@@ -1,17 +1,14 @@
 // fullwindow_internal.h -- the full-window solver handle shared by window_imu.hip (host trust-region loop, IMU factor,
-// marginalization) and fullwindow_dev.hip (the same loop resident on the device); the dense helpers of window_imu.hip
-// that lio_init.hip (the LIO initialisation) reuses.
+// marginalization) and fullwindow_dev.hip (the same loop resident on the device); its prior is the ABI's mml_prior plus
+// a flag.  The dense helpers of window_imu.hip that lio_init.hip (the LIO initialisation) reuses.
 #pragma once
 #include <vector>
 
 #include "../../include/mmloam_hip.h"
 
-struct MmlFwPrior {       // MarginalizationFactor on (para_PR[0], para_VBias[0]) after the address shift (:1552-1562)
+struct MmlFwPrior {  // MarginalizationFactor on (para_PR[0], para_VBias[0]) after the address shift (:1552-1562)
     bool valid = false;
-    int nres = 15;
-    double J[15 * 15];    // linearized_jacobians, columns [PR 6 | VBias 9]
-    double r0[15];        // linearized_residuals
-    double x0[15];        // keep_block_data
+    mml_prior p;
 };
 
 struct MmlFwEval {  // dense normal equations of the whole window at one x

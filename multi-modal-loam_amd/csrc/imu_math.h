@@ -2,6 +2,7 @@
 // solver (window_imu.hip) and the device-resident one (fullwindow_dev.hip):
 //   * Sophus::SO3d exp / log (include/sophus/so3.hpp:585-622 and logAndTheta), Eigen quaternion <-> matrix
 //   * Cost_NavState_PRV_Bias residual and analytic Jacobian before the sqrt information (ceresfunc.h:321-393)
+//   * the sqrt-information products of that factor, element by element (imu_whiten)
 //   * MarginalizationFactor::Evaluate residual (ceresfunc.h:262-301)
 #pragma once
 #include <math.h>
@@ -320,11 +321,24 @@ MML_HD void imu_raw(const mml_imu_preint* pre, const double* g, const double* pr
     }
 }
 
+// eResiduals.applyOnTheLeft(sqrt_information), the same for the Jacobian (ceresfunc.h:352,388-391), one element at a time:
+// o < 450 is Js[i][c] = sum_{k = i .. 14} U[i][k] J[k][c] with o = 30 i + c, o = 450 + i is rs[i], the same sum over r.
+// U is 15 x 15 upper triangular; the sum starts from 0.0 and takes k ascending -- the one statement of it for the host
+// factor and the device kernels, which are held bit-identical.
+MML_HD double imu_whiten(const double* U, const double* J, const double* r, int o) {
+    double s = 0;
+    if (o < 450) {
+        const int i = o / 30, c = o - 30 * i;
+        for (int k = i; k < 15; ++k) s += U[i * 15 + k] * J[k * 30 + c];
+    } else {
+        const int i = o - 450;
+        for (int k = i; k < 15; ++k) s += U[i * 15 + k] * r[k];
+    }
+    return s;
+}
 
-// MarginalizationFactor::Evaluate (ceresfunc.h:262-301): residual at x, the (constant) Jacobian is P.J.  P: anything
-// with J (15 x 15 row-major), r0, x0 -- mml_prior or the solver's copy of it.
-template <class PriorT>
-MML_HD void prior_residual(const PriorT& P, const double* x15, double* r) {
+// MarginalizationFactor::Evaluate (ceresfunc.h:262-301): residual at x, the (constant) Jacobian is P.J.
+MML_HD void prior_residual(const mml_prior& P, const double* x15, double* r) {
     double dx[15];
     for (int k = 0; k < 3; ++k) dx[k] = x15[k] - P.x0[k];
     const M3 E = m3_mul(m3_t(so3_exp(x15 + 3)), so3_exp(P.x0 + 3));  // exp(x)^-1 * exp(x0)  (:279)

@@ -408,6 +408,18 @@ __device__ void block_reduce28(double* acc, double* s_part /*SOLVE_WAVES*28*/, d
     __syncthreads();
 }
 
+// The 28-value record of the frame in slot b at x6 = [t, phi]: its pose, its factors, the workgroup reduction into out
+// (the whole workgroup calls; x6 must be readable by every thread).
+__device__ __forceinline__ void frame_record(const MmlLineFactor* lf, const MmlPlaneFactor* pf, const int* ft_n, int B, int MF, int b,
+                                             const double* x6, const double* Tbl, double w_tan, double huber,
+                                             double* s_part /*SOLVE_WAVES*28*/, double* out) {
+    Pose pose;
+    make_pose(x6, Tbl, pose);
+    double acc[28];
+    eval_frame(lf + (size_t)b * MF, ft_n[b], pf + (size_t)b * MF, ft_n[B + b], pose, w_tan, huber, acc);
+    block_reduce28(acc, s_part, out);
+}
+
 // ---- the live path's factor pass on all FOUR SIMDs of its CU (k_solve_wide: W = 1, plan_weight_tan = 0) ---------------------------
 // A launch of at most one problem per CU runs the 128-thread pass above on two of the CU's four SIMDs, and the pass is bound by the
 // double-precision issue rate there (1013 factors of configs[1] x ~350 instructions = 2 800 wave-instructions per SIMD at 4.1 cycles).

@@ -303,6 +303,34 @@ int mml_uploads_wait(mml_ctx* ctx, int first, int count);
         }                            \
     } while (0)
 
+// A refusal with a formatted message: the text goes to ctx->err when there is a context to carry it (at most 191 characters),
+// `code` comes back.  capi.hip.
+int mml_refuse(mml_ctx* ctx, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
+
+// A device array and (Pinned) its pinned host twin, sized for the largest request so far: it only grows.  Every entry point that
+// uses one drains its stream before it returns, so nothing is in flight when reserve() replaces the buffers.  A failure midway
+// leaves cap == 0 and each pointer valid or null, which the next reserve() or release() cleans up.
+template <class T, bool Pinned = true>
+struct MmlStaging {
+    T* d = nullptr;
+    T* h = nullptr;  // stays null without Pinned
+    size_t cap = 0;  // elements
+    void release() {
+        if (d) (void)hipFree(d);
+        if (h) (void)hipHostFree(h);
+        d = h = nullptr;
+        cap = 0;
+    }
+    int reserve(mml_ctx* ctx, size_t n) {
+        if (n <= cap) return MML_OK;
+        release();
+        MML_HIP(hipMalloc(reinterpret_cast<void**>(&d), sizeof(T) * n));
+        if (Pinned) MML_HIP(hipHostMalloc(reinterpret_cast<void**>(&h), sizeof(T) * n, hipHostMallocDefault));
+        cap = n;
+        return MML_OK;
+    }
+};
+
 // profiling bracket (no-op unless enabled)
 int mml_stage_begin(mml_ctx* ctx, const char* name);
 void mml_stage_end(mml_ctx* ctx, int token);

@@ -1,7 +1,8 @@
 // window_imu.hip -- SURVEY.md section 8(f) rank 1: the IMU side of the joint window solve.  Host code (W <= 8 frames,
 // 15 parameters each: O(W) tiny dense work next to the per-frame lidar normal equations that come from the device),
 // compiled into the same library so that it sits behind the same C-ABI; the same trust-region loop resident on the
-// device is fullwindow_dev.hip, the shared arithmetic imu_math.h.
+// device is fullwindow_dev.hip, the shared arithmetic imu_math.h (IMU residual and Jacobian, the sqrt-information
+// products imu_whiten, the prior residual) and lidar_eval.h's Hget for a record's upper triangle.
 //   * IMUIntegrator::PreIntegration            mm-loam/src/lio/IMUIntegrator.cpp:108-166  -> mml_imu_preintegrate
 //   * Cost_NavState_PRV_Bias (15 residuals)    mm-loam/include/utils/ceresfunc.h:321-393   -> mml_imu_factor
 //     Jacobians: the reference lets Ceres autodiff the functor; here they are analytic (checked against central
@@ -19,6 +20,7 @@
 
 #include "fullwindow_internal.h"
 #include "imu_math.h"
+#include "lidar_eval.h"
 #include "marg_dense.h"
 
 namespace {
@@ -210,18 +212,7 @@ static void imu_factor_with_U(const mml_imu_preint* pre, const double* U, const 
                               const double* prj, const double* vbj, double* residual, double* jacobian) {
     double r[15], J[15 * 30];
     imu_raw(pre, gravity, pri, vbi, prj, vbj, r, jacobian ? J : nullptr);
-    for (int i = 0; i < 15; ++i) {  // eResiduals.applyOnTheLeft(sqrt_information)
-        double s = 0;
-        for (int k = i; k < 15; ++k) s += U[i * 15 + k] * r[k];
-        residual[i] = s;
-    }
-    if (jacobian)
-        for (int i = 0; i < 15; ++i)
-            for (int c = 0; c < 30; ++c) {
-                double s = 0;
-                for (int k = i; k < 15; ++k) s += U[i * 15 + k] * J[k * 30 + c];
-                jacobian[i * 30 + c] = s;
-            }
+    for (int o = jacobian ? 0 : 450; o < 465; ++o) (o < 450 ? jacobian[o] : residual[o - 450]) = imu_whiten(U, J, r, o);
 }
 
 }  // extern "C"
@@ -237,13 +228,8 @@ int assemble(const mml_fullwindow* s, const double* records, const double* x, Mm
     e.cost = 0;
     for (int f = 0; f < W; ++f) {
         const double* rec = records + 32 * f;
-        int k = 0;
         for (int a = 0; a < 6; ++a)
-            for (int b = a; b < 6; ++b) {
-                const double v = rec[k++];
-                e.H[(size_t)(15 * f + a) * n + 15 * f + b] += v;
-                if (b != a) e.H[(size_t)(15 * f + b) * n + 15 * f + a] += v;
-            }
+            for (int b = 0; b < 6; ++b) e.H[(size_t)(15 * f + a) * n + 15 * f + b] += Hget(rec, a, b);
         for (int a = 0; a < 6; ++a) e.g[15 * f + a] += rec[21 + a];
         e.cost += rec[27];
     }
@@ -255,6 +241,8 @@ int assemble(const mml_fullwindow* s, const double* records, const double* x, Mm
         if (!s->U_ok[f]) return MML_ERR_STATE;
         imu_factor_with_U(&s->imu[f], &s->U[225 * (size_t)f], s->gravity, xi, xi + 6, xj, xj + 6, r, J);
         const int base = 15 * (f - 1);  // the 30 columns are exactly the two consecutive frames
+        // (each product is summed on its own, then added -- k_fw_eval / k_fw_step's order; mml_fullwindow_marginalize below keeps
+        //  ONE running value per element.  Two orders, each held by a byte-equality test against the device: keep them apart)
         for (int a = 0; a < 30; ++a) {
             double ga = 0;
             for (int i = 0; i < 15; ++i) ga += J[i * 30 + a] * r[i];
@@ -271,14 +259,14 @@ int assemble(const mml_fullwindow* s, const double* records, const double* x, Mm
     }
     if (s->prior.valid) {
         double r[15];
-        prior_residual(s->prior, x, r);
+        prior_residual(s->prior.p, x, r);
         for (int a = 0; a < 15; ++a) {
             double ga = 0;
-            for (int i = 0; i < 15; ++i) ga += s->prior.J[i * 15 + a] * r[i];
+            for (int i = 0; i < 15; ++i) ga += s->prior.p.J[i * 15 + a] * r[i];
             e.g[a] += ga;
             for (int b = 0; b < 15; ++b) {
                 double h = 0;
-                for (int i = 0; i < 15; ++i) h += s->prior.J[i * 15 + a] * s->prior.J[i * 15 + b];
+                for (int i = 0; i < 15; ++i) h += s->prior.p.J[i * 15 + a] * s->prior.p.J[i * 15 + b];
                 e.H[(size_t)a * n + b] += h;
             }
         }
@@ -490,9 +478,7 @@ int mml_fullwindow_set_prior(mml_fullwindow* s, const mml_prior* p) {
         return MML_OK;
     }
     s->prior.valid = true;
-    memcpy(s->prior.J, p->J, sizeof(s->prior.J));
-    memcpy(s->prior.r0, p->r0, sizeof(s->prior.r0));
-    memcpy(s->prior.x0, p->x0, sizeof(s->prior.x0));
+    s->prior.p = *p;
     return MML_OK;
 }
 
@@ -581,13 +567,15 @@ int mml_fullwindow_marginalize(const mml_fullwindow* s, const double* lidar_reco
     if (!s || !lidar_record0 || !x || !out || s->W < 2 || !s->have_imu[1]) return MML_ERR_INVALID;
     const int N = 30;
     std::vector<double> A((size_t)N * N, 0.0), b(N, 0.0);
+    // (every element is ONE running value over prior, IMU and lidar terms -- k_fw_marginalize's order; assemble above sums each
+    //  product on its own and adds it.  Two orders, each held by a byte-equality test against the device: keep them apart)
     if (s->prior.valid) {
         double r[15];
-        prior_residual(s->prior, x, r);
+        prior_residual(s->prior.p, x, r);
         for (int a = 0; a < 15; ++a) {
-            for (int i = 0; i < 15; ++i) b[a] += s->prior.J[i * 15 + a] * r[i];
+            for (int i = 0; i < 15; ++i) b[a] += s->prior.p.J[i * 15 + a] * r[i];
             for (int c = 0; c < 15; ++c)
-                for (int i = 0; i < 15; ++i) A[(size_t)a * N + c] += s->prior.J[i * 15 + a] * s->prior.J[i * 15 + c];
+                for (int i = 0; i < 15; ++i) A[(size_t)a * N + c] += s->prior.p.J[i * 15 + a] * s->prior.p.J[i * 15 + c];
         }
     }
     {
@@ -601,15 +589,9 @@ int mml_fullwindow_marginalize(const mml_fullwindow* s, const double* lidar_reco
                 for (int i = 0; i < 15; ++i) A[(size_t)a * N + c] += J[i * 30 + a] * J[i * 30 + c];
         }
     }
-    {
-        int k = 0;
-        for (int a = 0; a < 6; ++a)
-            for (int c = a; c < 6; ++c) {
-                const double v = lidar_record0[k++];
-                A[(size_t)a * N + c] += v;
-                if (c != a) A[(size_t)c * N + a] += v;
-            }
-        for (int a = 0; a < 6; ++a) b[a] += lidar_record0[21 + a];
+    for (int a = 0; a < 6; ++a) {
+        for (int c = 0; c < 6; ++c) A[(size_t)a * N + c] += Hget(lidar_record0, a, c);
+        b[a] += lidar_record0[21 + a];
     }
     MargWork work;  // the dense tail, shared with the device (marg_dense.h)
     marg_dense(A.data(), b.data(), out->J, out->r0, work);

@@ -99,7 +99,68 @@ def _quat_from_rotvec(phi):
     return np.array([im * phi[0], im * phi[1], im * phi[2], re])
 
 
-class WindowEstimator:
+def _pack_state(frames):
+    """vector2double: one row [P | rotation vector | V | bg | ba] per frame."""
+    return np.stack([np.concatenate([fr["P"], _rotvec_from_quat(fr["Q"]), fr["V"], fr["bg"], fr["ba"]]) for fr in frames])
+
+
+def _unpack_state(frames, x):
+    """double2vector: the rows of x back into the frame dicts."""
+    for f, fr in enumerate(frames):
+        fr["P"], fr["Q"] = x[f][0:3].copy(), _quat_from_rotvec(x[f][3:6])
+        fr["V"], fr["bg"], fr["ba"] = x[f][6:9].copy(), x[f][9:12].copy(), x[f][12:15].copy()
+
+
+def _outer_converged(q_before, t_before, frame):
+    """The outer loop's stopping test on the newest frame (Estimator.cpp:1443-1447)."""
+    d = abs(float(np.dot(q_before, frame["Q"])))
+    deltaR = 2.0 * np.arccos(min(1.0, d)) * 180.0 / np.pi      # angularDistance, :1443
+    deltaT = float(np.linalg.norm(t_before - frame["P"]))
+    return deltaR < 0.05 and deltaT < 0.05
+
+
+def _consecutive(slots):
+    return all(s == slots[0] + f for f, s in enumerate(slots))
+
+
+def _new_solver(M, W, inner_iters, w_tan, preints, gravity, prior):
+    """The problem of one outer iteration: IMU factors preints[1 .. W-1], the prior when there is one."""
+    fw = M.FullWindowSolver(W, max_iters=inner_iters, fixed=False, huber=0.0, w_tan=w_tan)
+    for f in range(1, W):
+        fw.set_imu(f, preints[f], gravity)
+    if prior is not None:
+        fw.set_prior(prior)
+    return fw
+
+
+class _FullWindowBase:
+    """What the two full-window estimators share: the extrinsic, the constants of Estimator::Estimate and the
+    marginalization switch."""
+
+    def __init__(self, ctx, exTlb, max_outer, inner_iters, marginalize):
+        if marginalize not in ("device", "host"):
+            raise ValueError("marginalize must be 'device' or 'host'")
+        self.marginalize = marginalize
+        import importlib
+        self.M = importlib.import_module(__package__)
+        self.ctx = ctx
+        self.exTlb = np.eye(4) if exTlb is None else np.asarray(exTlb, dtype=np.float64)
+        self.T_bl = np.linalg.inv(self.exTlb)
+        self.exRbl = self.exTlb[:3, :3].T.copy()
+        self.exPbl = -1.0 * self.exRbl @ self.exTlb[:3, 3]
+        self.max_outer, self.inner_iters = max_outer, inner_iters
+        self.plan_weight_tan = 0.0003     # :1203
+        self.thres_dist = 1.0             # :1204
+
+    def _T_wl(self, x15):
+        R = _quat_to_matrix(_quat_from_rotvec(x15[3:6]))
+        T = np.eye(4)
+        T[:3, :3] = R @ self.exRbl
+        T[:3, 3] = R @ self.exPbl + x15[:3]
+        return T
+
+
+class WindowEstimator(_FullWindowBase):
     """Estimator::Estimate in full-window mode (windowSize == SLIDEWINDOWSIZE, Estimator.cpp:1143-1581): lidar factors
     of every frame (associated once, thres_dist 1, plan_weight_tan 3e-4, no loss), IMU factors between consecutive
     frames, the marginalization prior of the previous call.  Association runs on the device.  solver="device" (the
@@ -114,32 +175,14 @@ class WindowEstimator:
                  marginalize="host"):
         if solver not in ("device", "host"):
             raise ValueError("solver must be 'device' or 'host'")
-        if marginalize not in ("device", "host"):
-            raise ValueError("marginalize must be 'device' or 'host'")
-        self.solver, self.marginalize = solver, marginalize
-        import importlib
-        self.M = importlib.import_module(__package__)
-        self.ctx = ctx
-        self.exTlb = np.eye(4) if exTlb is None else np.asarray(exTlb, dtype=np.float64)
-        self.T_bl = np.linalg.inv(self.exTlb)
-        self.exRbl = self.exTlb[:3, :3].T.copy()
-        self.exPbl = -1.0 * self.exRbl @ self.exTlb[:3, 3]
+        self.solver = solver
+        super().__init__(ctx, exTlb, max_outer, inner_iters, marginalize)
         self.gravity = np.asarray(gravity, dtype=np.float64)
-        self.max_outer, self.inner_iters = max_outer, inner_iters
         self.prior = None                 # last_marginalization_info
-        self.plan_weight_tan = 0.0003     # :1203
-        self.thres_dist = 1.0             # :1204
-
-    def _T_wl(self, x15):
-        R = _quat_to_matrix(_quat_from_rotvec(x15[3:6]))
-        T = np.eye(4)
-        T[:3, :3] = R @ self.exRbl
-        T[:3, 3] = R @ self.exPbl + x15[:3]
-        return T
 
     def _records(self, slots, x):
         # one launch + one read-back per trust-region evaluation when the window sits in consecutive slots
-        if all(s == slots[0] + f for f, s in enumerate(slots)):
+        if _consecutive(slots):
             return self.ctx.linearize_window(slots[0], len(slots), x, self.T_bl, self.plan_weight_tan, 0.0)
         M = self.M
         return np.stack([M.pack_record(*self.ctx.linearize(s, x[f][:6], self.T_bl, self.plan_weight_tan, 0.0))
@@ -151,20 +194,16 @@ class WindowEstimator:
         M, ctx, W = self.M, self.ctx, len(slots)
         info = dict(outer=0, summaries=[])
         for it in range(self.max_outer):
-            x = np.stack([np.concatenate([fr["P"], _rotvec_from_quat(fr["Q"]), fr["V"], fr["bg"], fr["ba"]]) for fr in frames])
+            x = _pack_state(frames)
             if it == 0:                                        # vLineFeatures / vPlanFeatures are empty only here
-                if all(s == slots[0] + f for f, s in enumerate(slots)):   # one enqueue for the whole window, no read-back
+                if _consecutive(slots):                        # one enqueue for the whole window, no read-back
                     ctx.associate(slots[0], W, np.stack([self._T_wl(x[f]) for f in range(W)]), self.thres_dist, stats=False)
                 else:
                     for f, s in enumerate(slots):
                         ctx.associate(s, 1, self._T_wl(x[f])[None], self.thres_dist, stats=False)
             q_before, t_before = frames[-1]["Q"].copy(), frames[-1]["P"].copy()
-            fw = M.FullWindowSolver(W, max_iters=self.inner_iters, fixed=False, huber=0.0, w_tan=self.plan_weight_tan)
-            for f in range(1, W):
-                fw.set_imu(f, preints[f], self.gravity)
-            if self.prior is not None:
-                fw.set_prior(self.prior)
-            if self.solver == "device" and all(s == slots[0] + f for f, s in enumerate(slots)):
+            fw = _new_solver(M, W, self.inner_iters, self.plan_weight_tan, preints, self.gravity, self.prior)
+            if self.solver == "device" and _consecutive(slots):
                 x, _, evals = fw.solve_device(ctx, slots[0], self.T_bl, x)
                 info["evaluations"] = info.get("evaluations", 0) + evals
             else:
@@ -174,14 +213,9 @@ class WindowEstimator:
                     if done:
                         break
             info["summaries"].append(fw.summary())
-            for f, fr in enumerate(frames):                    # double2vector
-                fr["P"], fr["Q"] = x[f][0:3].copy(), _quat_from_rotvec(x[f][3:6])
-                fr["V"], fr["bg"], fr["ba"] = x[f][6:9].copy(), x[f][9:12].copy(), x[f][12:15].copy()
+            _unpack_state(frames, x)
             info["outer"] = it + 1
-            d = abs(float(np.dot(q_before, frames[-1]["Q"])))
-            deltaR = 2.0 * np.arccos(min(1.0, d)) * 180.0 / np.pi      # angularDistance, :1443
-            deltaT = float(np.linalg.norm(t_before - frames[-1]["P"]))
-            if (deltaR < 0.05 and deltaT < 0.05) or it + 1 == self.max_outer:
+            if _outer_converged(q_before, t_before, frames[-1]) or it + 1 == self.max_outer:
                 # marginalize frame 0 (:1453-1546): previous prior, IMU factor 0-1, the stored lidar factors of frame 0
                 if W < 2:
                     self.prior = None
@@ -194,41 +228,25 @@ class WindowEstimator:
         return info
 
 
-class BatchWindowEstimator:
+class BatchWindowEstimator(_FullWindowBase):
     """WindowEstimator(solver="device") for n windows at once -- a fleet's bags, or one bag cut into segments, replayed in
     full-window mode.  The outer loops of all windows run in lockstep: one association call per run of adjacent slots at
     outer iteration 0, then one mml_fullwindow_solve_batch per outer iteration over the windows that have not converged yet.
     Every window keeps its own convergence test, its own gravity and its own prior (priors[w]), so its frames, counts and
-    prior equal what a WindowEstimator of its own produces on the same inputs.  marginalize="host" (the default): the batch
+    prior equal what a WindowEstimator of its own produces on the same inputs (both classes pack, unpack, test and build
+    their problems through the same module functions).  marginalize="host" (the default): the batch
     call hands back every window's frame-0 record and the windows that converge are marginalized on the host one by one;
     marginalize="device": no records come back, the windows that converge in an outer iteration are marginalized by one
     mml_fullwindow_marginalize_batch call, bit-identical priors."""
 
     def __init__(self, ctx, n, exTlb=None, gravity=(0.0, 0.0, -9.805), max_outer=5, inner_iters=10, marginalize="host"):
-        if marginalize not in ("device", "host"):
-            raise ValueError("marginalize must be 'device' or 'host'")
-        self.marginalize = marginalize
-        import importlib
-        self.M = importlib.import_module(__package__)
-        self.ctx, self.n = ctx, n
-        self.exTlb = np.eye(4) if exTlb is None else np.asarray(exTlb, dtype=np.float64)
-        self.T_bl = np.linalg.inv(self.exTlb)
-        self.exRbl = self.exTlb[:3, :3].T.copy()
-        self.exPbl = -1.0 * self.exRbl @ self.exTlb[:3, 3]
+        super().__init__(ctx, exTlb, max_outer, inner_iters, marginalize)
+        self.n = n
         g = np.asarray(gravity, dtype=np.float64)
         if g.shape not in ((3,), (n, 3)):
             raise ValueError("gravity must be one vector or one per window")
         self.gravity = np.broadcast_to(g, (n, 3)).copy()
-        self.max_outer, self.inner_iters = max_outer, inner_iters
         self.priors = [None] * n          # last_marginalization_info of every window
-        self.plan_weight_tan = 0.0003     # :1203
-        self.thres_dist = 1.0             # :1204
-
-    _T_wl = WindowEstimator._T_wl
-
-    @staticmethod
-    def _state(frames):
-        return np.stack([np.concatenate([fr["P"], _rotvec_from_quat(fr["Q"]), fr["V"], fr["bg"], fr["ba"]]) for fr in frames])
 
     def estimate(self, slots, frames, preints):
         """One entry per window in each list: slots[w] the (consecutive) scan slots of window w's frames, frames[w] its
@@ -241,7 +259,7 @@ class BatchWindowEstimator:
         for w in range(n):
             if len(slots[w]) < 1 or len(frames[w]) != len(slots[w]) or len(preints[w]) != len(slots[w]):
                 raise ValueError("window %d: slots, frames and preints differ in length" % w)
-            if any(s != slots[w][0] + f for f, s in enumerate(slots[w])):
+            if not _consecutive(slots[w]):
                 raise ValueError("window %d: its slots must be consecutive" % w)
         owner = {}
         for w in range(n):
@@ -252,7 +270,7 @@ class BatchWindowEstimator:
         infos = [dict(outer=0, summaries=[], evaluations=0) for _ in range(n)]
         active = list(range(n))
         for it in range(self.max_outer):
-            xs = [self._state(frames[w]) for w in active]
+            xs = [_pack_state(frames[w]) for w in active]
             if it == 0:                                        # vLineFeatures / vPlanFeatures are empty only here
                 order = sorted(owner)
                 run = []
@@ -263,14 +281,8 @@ class BatchWindowEstimator:
                         ctx.associate(run[0], len(run), T, self.thres_dist, stats=False)
                         run = []
             before = [(frames[w][-1]["Q"].copy(), frames[w][-1]["P"].copy()) for w in active]
-            solvers = []
-            for w in active:
-                fw = M.FullWindowSolver(len(slots[w]), max_iters=self.inner_iters, fixed=False, huber=0.0, w_tan=self.plan_weight_tan)
-                for f in range(1, len(slots[w])):
-                    fw.set_imu(f, preints[w][f], self.gravity[w])
-                if self.priors[w] is not None:
-                    fw.set_prior(self.priors[w])
-                solvers.append(fw)
+            solvers = [_new_solver(M, len(slots[w]), self.inner_iters, self.plan_weight_tan, preints[w], self.gravity[w], self.priors[w])
+                       for w in active]
             on_device = self.marginalize == "device"
             out = M.fullwindow_solve_batch(ctx, solvers, [slots[w][0] for w in active], self.T_bl, xs, records0=not on_device)
             xo, evals, rec0 = out[0], out[2], None if on_device else out[3]
@@ -279,14 +291,9 @@ class BatchWindowEstimator:
                 x, info = xo[i], infos[w]
                 info["evaluations"] += evals[i]
                 info["summaries"].append(solvers[i].summary())
-                for f, fr in enumerate(frames[w]):             # double2vector
-                    fr["P"], fr["Q"] = x[f][0:3].copy(), _quat_from_rotvec(x[f][3:6])
-                    fr["V"], fr["bg"], fr["ba"] = x[f][6:9].copy(), x[f][9:12].copy(), x[f][12:15].copy()
+                _unpack_state(frames[w], x)
                 info["outer"] = it + 1
-                d = abs(float(np.dot(before[i][0], frames[w][-1]["Q"])))
-                deltaR = 2.0 * np.arccos(min(1.0, d)) * 180.0 / np.pi      # angularDistance, :1443
-                deltaT = float(np.linalg.norm(before[i][1] - frames[w][-1]["P"]))
-                if (deltaR < 0.05 and deltaT < 0.05) or it + 1 == self.max_outer:
+                if _outer_converged(before[i][0], before[i][1], frames[w][-1]) or it + 1 == self.max_outer:
                     # marginalize frame 0 (:1453-1546): previous prior, IMU factor 0-1, the stored lidar factors of frame 0
                     if len(slots[w]) < 2:
                         self.priors[w] = None

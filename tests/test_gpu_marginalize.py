@@ -10,6 +10,7 @@ import pytest
 from scipy.spatial.transform import Rotation as Rsc
 
 from conftest import perturbed
+from test_imu_preint_batch import BA, BG, family
 from test_marginalize_dense import corner_systems
 
 pytestmark = pytest.mark.gpu
@@ -31,19 +32,19 @@ def assert_priors_equal(a, b, what=None):
 class Problems:
     """12 slots of synthetic scans K0 .. K0 + 11, extracted, undistorted, down-sampled and associated at perturbed poses,
     pre-integrations between consecutive scans, and a prior produced by marginalizing a first solve of the 8-frame window
-    (the set-up of tests/test_gpu_fullwindow_batch.py)."""
+    (the set-up of tests/test_gpu_fullwindow_batch.py).  slots < 8: that many slots and no prior."""
 
-    def __init__(self, M, synth, scene):
+    def __init__(self, M, synth, scene, slots=SLOTS):
         odometry = importlib.import_module("multi-modal-loam_amd.odometry")
         self.M, self.G = M, synth.GRAVITY
-        self.c = c = M.Context(max_scans=SLOTS)
+        self.c = c = M.Context(max_scans=slots)
         c.map_set_local(0, scene["corner_map"])
         c.map_set_local(1, scene["surf_map"])
         west = odometry.WindowEstimator(c, gravity=self.G)
         self.T_bl = west.T_bl
         rng = np.random.default_rng(5)
         x0, self.pres = [], [None]
-        for f in range(SLOTS):
+        for f in range(slots):
             k = K0 + f
             c.scan_upload(f, synth.velo_scan(k), synth.livox_scan(k))
             c.extract(f, 1)
@@ -57,10 +58,12 @@ class Problems:
             c.associate(f, 1, west._T_wl(x0[f])[None], 1.0)
         self.x0 = np.stack(x0)
         self.prior = None
+        self.refs = {}
+        if slots < 8:
+            return
         fw = self.make(dict(W=8, first=0))
         self.x8, _, _ = fw.solve_device(c, 0, self.T_bl, self.x0[:8])
         self.prior = self.host(fw, 0, self.x8)
-        self.refs = {}
 
     def make(self, spec):
         fw = self.M.FullWindowSolver(spec["W"], max_iters=10, fixed=False, huber=spec.get("huber", 0.0), w_tan=W_TAN)
@@ -184,6 +187,43 @@ def test_dense_tail_on_the_device_equals_the_host_routine(prob):
         assert np.array_equal(a, u), (name, np.abs(a - u).max())
         assert np.array_equal(v, w), (name, np.abs(v - w).max())
     assert np.isfinite(Jd).all() and np.isfinite(rd).all()
+
+
+def test_staging_buffers_grow_are_reused_and_are_released(M, synth, scene):
+    """The three batch entry points share one kind of staging buffer (device array + pinned twin, grow-only).  On ONE context
+    each is called with n = 2 (allocates), n = 1 (reuses the larger buffers) and n = 5 (frees and allocates again), windows of
+    W = 2 frames and intervals of 3 IMU samples; after every call the results equal, bit for bit, the single-window
+    mml_fullwindow_solve, the host's mml_fullwindow_marginalize and the NULL-context mml_imu_preintegrate_batch.  Then the
+    context is destroyed (the buffers are released) and a second one in the same process does it again."""
+    rng = np.random.default_rng(31)
+    for sizes in ((2, 1, 5), (2,)):
+        p = Problems(M, synth, scene, slots=3)
+        try:
+            specs = [dict(W=2, first=w % 2) for w in range(5)]
+            single = []
+            for spec in specs[:2]:
+                x, s, ev = p.make(spec).solve_device(p.c, spec["first"], p.T_bl, p.state(spec))
+                single.append((x, (s.iterations, s.successful, s.termination, s.initial_cost, s.final_cost), ev))
+            for n in sizes:
+                fws = [p.make(spec) for spec in specs[:n]]
+                xs, ss, evs = M.fullwindow_solve_batch(p.c, fws, [spec["first"] for spec in specs[:n]], p.T_bl,
+                                                       [p.state(spec) for spec in specs[:n]])
+                for w in range(n):
+                    x, summary, ev = single[w % 2]
+                    assert np.array_equal(xs[w], x), (n, w, np.abs(xs[w] - x).max())
+                    assert (ss[w].iterations, ss[w].successful, ss[w].termination, ss[w].initial_cost, ss[w].final_cost) == summary
+                    assert evs[w] == ev
+                out = p.device(specs[:n])
+                assert len(out) == n
+                for w in range(n):
+                    assert_priors_equal(out[w], p.ref(specs[w]), (n, w))
+                smp = [family(rng, 3) for _ in range(n)]
+                dev, host = M.imu_preintegrate_batch(smp, BG, BA, p.c), M.imu_preintegrate_batch(smp, BG, BA)
+                assert len(dev) == len(host) == n
+                for w in range(n):
+                    assert bytes(dev[w]) == bytes(host[w]), (n, w)
+        finally:
+            p.c.close()
 
 
 def _frames(M, synth, c, rng, k0, n, W):
