@@ -505,8 +505,11 @@ int mml_imu_init_factor(const mml_imu_preint* pre, const double* ri, const doubl
                         double* jacobian);
 typedef struct {
     int status;                  /* 0 initialised; 1 |b_a| or |b_g| > 0.5 (nothing written); 2 a velocity more than 2.0
-                                    from its prior (frames 0..fail_frame hold the new biases, 0..fail_frame-1 the new V) */
-    int fail_frame;              /* status 2: that frame; -1 otherwise */
+                                    from its prior (frames 0..fail_frame hold the new biases, 0..fail_frame-1 the new V);
+                                    3 (mml_lio_initialize_batch only; the single call returns MML_ERR_STATE): the
+                                    pre-integration of frame fail_frame has a covariance that is not positive definite,
+                                    e.g. an empty interval (nothing written but status and fail_frame) */
+    int fail_frame;              /* status 2, 3: that frame; -1 otherwise */
     int keep_from;               /* status 0: the caller drops frames [0, keep_from) (the list is trimmed to 5 frames) */
     int _pad;
     double gravity[3];           /* GravityVector = exp(r_wg) (0, 0, -9.805) */
@@ -585,6 +588,34 @@ int mml_fullwindow_marginalize_batch(mml_ctx* ctx, int n, mml_fullwindow* const*
 #define MML_PREINT_BATCH_MAX 8192 /* intervals per call */
 int mml_imu_preintegrate_batch(mml_ctx* ctx, int n, const double* samples, const int* offsets /* n + 1 */,
                                const double* bg /* n x 3 */, const double* ba /* n x 3 */, mml_imu_preint* out /* n */);
+/* mml_lio_initialize for n_seg segments in one call -- what opens full-window mode for the three batch calls above.  Segment s
+ * is frames frame_offsets[s] .. frame_offsets[s+1]-1 (2 .. MML_LIO_BATCH_MAX_FRAMES of them) of the concatenated arrays t, P,
+ * Q, V, bg, ba (F = frame_offsets[n_seg] rows), frame f's IMU messages are rows sample_offsets[f] .. sample_offsets[f+1]-1 of
+ * samples, exTlb + 16 s is the segment's extrinsic, and pre_in / pre_out (either may be NULL) hold F entries of which a
+ * segment's entry 0 is not read or written.  Per segment every argument means what it means in mml_lio_initialize: the partial
+ * writes of status 1 / 2, keep_from, the back frame moved to the body on status 0 only, out[s].  Where the single call fails as
+ * a whole with MML_ERR_STATE (a pre-integration covariance that is not positive definite, e.g. an empty interval of a frame
+ * >= 1) the segment gets status 3 and fail_frame, none of its state or pre_out entries is written, and the other segments are
+ * unaffected.
+ * ctx NULL: the host build of the routine (csrc/lio_init_core.h, csrc/imu_preint.h) in a loop over the segments, no device
+ * needed.  Otherwise one upload, three launches (the pre-integrations a wavefront per frame, the initialisation a wavefront per
+ * segment with the whole solve state in LDS, the pre-integrations again for status-0 segments with the new biases) and one
+ * read-back; the device build runs the host's operations in the host's order, so the two are bit-identical on every output
+ * byte.  Against mml_lio_initialize the routine differs in the two places where that call reaches libm: the quaternion step
+ * of the gravity solve takes its sin / cos from csrc/imu_math.h, and the pre-integrations are mml_imu_preintegrate_batch's.
+ * Both agree with libm to an ulp: results agree to rounding amplified by the solves (1e-9 in the tests).
+ * Everything is checked before anything is enqueued or written and the message names the segment: MML_ERR_INVALID for n_seg
+ * outside 1 .. MML_LIO_BATCH_MAX, a null pointer (pre_in / pre_out may be NULL), frame_offsets[0] != 0, a segment with fewer
+ * than 2 or more than MML_LIO_BATCH_MAX_FRAMES frames, sample_offsets[0] != 0, a decreasing sample offset, a segment whose
+ * frame 0 has no sample.  The context keeps one device and one pinned block for the largest call it has seen (3.8 KB per frame
+ * and 56 bytes per sample). */
+#define MML_LIO_BATCH_MAX        1024   /* segments per call */
+#define MML_LIO_BATCH_MAX_FRAMES 8      /* frames per segment (2 .. 8) */
+int mml_lio_initialize_batch(mml_ctx* ctx, int n_seg, const int* frame_offsets /* n_seg + 1 */,
+        const double* t, double* P, double* Q, double* V, double* bg, double* ba,      /* F rows, F = frame_offsets[n_seg] */
+        const double* samples, const int* sample_offsets /* F + 1 */,
+        const double* exTlb /* n_seg x 16 */, const mml_imu_preint* pre_in /* F or NULL */,
+        mml_imu_preint* pre_out /* F or NULL */, mml_lio_init_result* out /* n_seg */);
 
 /* Number of HIP streams mml_step pipelines its sub-batches over (1..8, default 2 or $MML_LANES).  With 1 every
  * kernel covers the whole batch and runs alone on the device, which is what per-kernel timing wants. */

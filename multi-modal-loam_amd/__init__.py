@@ -27,6 +27,8 @@ DIGEST_WORDS = 10
 FW_X_STRIDE = 120      # MML_FW_X_STRIDE: doubles per window in the state array of mml_fullwindow_solve_batch
 FW_BATCH_MAX = 1024     # MML_FW_BATCH_MAX: windows per call
 PREINT_BATCH_MAX = 8192  # MML_PREINT_BATCH_MAX: intervals per call of mml_imu_preintegrate_batch
+LIO_BATCH_MAX = 1024     # MML_LIO_BATCH_MAX: segments per call of mml_lio_initialize_batch
+LIO_BATCH_MAX_FRAMES = 8  # MML_LIO_BATCH_MAX_FRAMES: frames per segment
 
 LIVOX_DTYPE = np.dtype([("offset_time", "<u4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4"),
                         ("reflectivity", "u1"), ("tag", "u1"), ("line", "u1"), ("_pad", "u1")])
@@ -225,6 +227,9 @@ def lib():
         if hasattr(L, "mml_imu_preintegrate_batch"):
             L.mml_imu_preintegrate_batch.restype = C.c_int
             L.mml_imu_preintegrate_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
+        if hasattr(L, "mml_lio_initialize_batch"):
+            L.mml_lio_initialize_batch.restype = C.c_int
+            L.mml_lio_initialize_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 13
         _lib = L
     return _lib
 
@@ -752,6 +757,7 @@ class LioInitResult(C.Structure):
 
 
 LIO_INIT_OK, LIO_INIT_BIAS, LIO_INIT_VELOCITY = 0, 1, 2
+LIO_INIT_NOT_PD = 3  # mml_lio_initialize_batch only: a pre-integration covariance is not positive definite (nothing written)
 
 
 def imu_gyro_integrate(samples, dq=(0.0, 0.0, 0.0, 1.0)):
@@ -797,6 +803,55 @@ def lio_initialize(t, P, Q, V, bg, ba, samples, exTlb, pre=None):
         raise MmlError(rc, "mml_lio_initialize")
     pres = [None] + [ImuPreint.from_buffer_copy(pout[i]) for i in range(1, n)]
     return res, st, pres
+
+
+def lio_initialize_batch(segments, ctx=None):
+    """mml_lio_initialize_batch: lio_initialize for a list of segments in one call.  segments[s]: the arguments of lio_initialize
+    as a tuple (t, P, Q, V, bg, ba, samples, exTlb[, pre]).  The C call takes pre-integrations for all segments or for none: when
+    some segments bring theirs, the others' are made first by imu_preintegrate_batch (the routine the call itself would use, at
+    frame i-1's biases).  ctx None: the host routine (no device needed); a Context: one upload, three launches, one read-back,
+    bit-identical to it.  Returns per segment what lio_initialize returns: (result, dict of the written P, Q, V, bg, ba, list of
+    n pre-integrations with entry 0 None); a segment with status LIO_INIT_NOT_PD has its state as it came in and no
+    pre-integrations (all None)."""
+    n_seg = len(segments)
+    segs = [tuple(s) + (None,) * (9 - len(s)) for s in segments]
+    ns = [len(s[0]) for s in segs]
+    fo = np.concatenate([[0], np.cumsum(ns)]).astype(np.int32)
+    F = int(fo[-1])
+    widths = (("P", 1, 3), ("Q", 2, 4), ("V", 3, 3), ("bg", 4, 3), ("ba", 5, 3))
+    st = {k: (np.concatenate([_f64(s[j]).reshape(n, w) for s, n in zip(segs, ns)]) if F else np.zeros((0, w))) for k, j, w in widths}
+    t = _f64(np.concatenate([_f64(s[0]).reshape(n) for s, n in zip(segs, ns)])) if F else np.zeros(0)
+    smp = [[_f64(a).reshape(-1, 7) for a in s[6]] for s in segs]
+    for s, (m, n) in enumerate(zip(smp, ns)):
+        if len(m) != n:
+            raise ValueError("segment %d: %d frames but %d sample arrays" % (s, n, len(m)))
+    so = np.concatenate([[0], np.cumsum([len(a) for m in smp for a in m])]).astype(np.int32)
+    flat = _f64(np.concatenate([a for m in smp for a in m])) if so[-1] else np.zeros((1, 7))
+    ex = _f64(np.stack([_f64(s[7]).reshape(16) for s in segs])) if n_seg else np.zeros((1, 16))
+    pin = None
+    if any(s[8] is not None for s in segs):
+        pin = (ImuPreint * max(F, 1))()
+        todo = [(s, i) for s in range(n_seg) if segs[s][8] is None for i in range(1, ns[s])]
+        made = iter(imu_preintegrate_batch([smp[s][i] for s, i in todo], np.stack([st["bg"][fo[s] + i - 1] for s, i in todo]),
+                                           np.stack([st["ba"][fo[s] + i - 1] for s, i in todo]), ctx) if todo else [])
+        for s in range(n_seg):
+            for i in range(1, ns[s]):
+                pin[fo[s] + i] = segs[s][8][i] if segs[s][8] is not None else next(made)
+    pout = (ImuPreint * max(F, 1))()
+    res = (LioInitResult * max(n_seg, 1))()
+    rc = lib().mml_lio_initialize_batch(ctx._h if ctx is not None else None, C.c_int(n_seg), _p(fo), _p(t), _p(st["P"]), _p(st["Q"]),
+                                        _p(st["V"]), _p(st["bg"]), _p(st["ba"]), _p(flat), _p(so), _p(ex), pin, pout, res)
+    if ctx is not None:
+        ctx._ck(rc)
+    elif rc != MML_OK:
+        raise MmlError(rc, "mml_lio_initialize_batch")
+    ret = []
+    for s in range(n_seg):
+        a, b = int(fo[s]), int(fo[s + 1])
+        r = LioInitResult.from_buffer_copy(res[s])
+        pres = [None] + [ImuPreint.from_buffer_copy(pout[f]) if r.status != LIO_INIT_NOT_PD else None for f in range(a + 1, b)]
+        ret.append((r, {k: v[a:b].copy() for k, v in st.items()}, pres))
+    return ret
 
 
 class FullWindowSolver:

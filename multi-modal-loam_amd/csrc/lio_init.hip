@@ -1,6 +1,8 @@
 // lio_init.hip -- the LIO initialisation that opens the full-window (IMU_Mode 2) mode.  Host code: two dense problems of
 // 4 and 9 + 3 n unknowns, solved once per session (retried every third scan until they succeed); the 15 W dogleg of
-// window_imu.hip already showed that a serial dense solve of this size gains nothing on one wavefront.  Compiled into
+// window_imu.hip already showed that ONE serial dense solve of this size gains nothing on one wavefront.  Many of them at
+// once are another matter: mml_lio_initialize_batch (lio_init_batch.hip, the routine in lio_init_core.h) runs a segment per
+// wavefront for a replay of many segments; this file stays the single call.  Compiled into
 // the same library so that it sits behind the same C-ABI and shares imu_math.h / window_imu.hip's dense helpers.
 //   * IMUIntegrator::GyroIntegration        mm-loam/src/lio/IMUIntegrator.cpp:90-106      -> mml_imu_gyro_integrate
 //   * IMUIntegrator::GetAverageAcc          IMUIntegrator.cpp:168-181                     -> (inside mml_lio_initialize)

@@ -810,5 +810,77 @@ inline bool TryMAPInitialization(std::list<Estimator::LidarFrame>& frameList, st
     return true;
 }
 
+// TryMAPInitialization for many frame lists through ONE mml_lio_initialize_batch call: frameLists[s] / imus[s] / exTlbs[s] are
+// one segment's arguments of the function above (2 .. MML_LIO_BATCH_MAX_FRAMES frames), each changed exactly as that function
+// changes them; GravityVectors[s] is written in every case but status 3.  The call takes pre-integrations for all segments or
+// for none: they are handed over when every frame after the first of EVERY segment has one.  ctx null: the host routine;
+// otherwise one device call, bit-identical to it.  Returns per segment whether it initialised; a segment whose pre-integration
+// covariance is not positive definite (status 3, e.g. an empty interval) is left untouched and does not throw.
+inline std::vector<bool> TryMAPInitializationBatch(mml_ctx* ctx, std::vector<std::list<Estimator::LidarFrame>*>& frameLists,
+                                                   std::vector<std::vector<IMUIntegrator>*>& imus, const std::vector<Matrix4d>& exTlbs,
+                                                   std::vector<Vector3d>& GravityVectors) {
+    const size_t ns = frameLists.size();
+    if (imus.size() != ns || exTlbs.size() != ns) throw std::runtime_error("TryMAPInitializationBatch: one imu vector and one exTlb per frame list");
+    std::vector<int> fo(1, 0), so(1, 0);
+    std::vector<double> t, P, Q, V, bg, ba, smp, ex;
+    std::vector<mml_imu_preint> pre_in;
+    bool given = true;
+    for (size_t s = 0; s < ns; ++s) {
+        const int n = (int)frameLists[s]->size();
+        if ((int)imus[s]->size() != n) throw std::runtime_error("TryMAPInitializationBatch: one IMUIntegrator per frame");
+        int i = 0;
+        for (const auto& f : *frameLists[s]) {
+            const IMUIntegrator& it = (*imus[s])[i];
+            t.push_back(f.timeStamp);
+            for (int k = 0; k < 3; ++k) P.push_back(f.P.v[k]), V.push_back(f.V.v[k]), bg.push_back(f.bg.v[k]), ba.push_back(f.ba.v[k]);
+            Q.push_back(f.Q.x), Q.push_back(f.Q.y), Q.push_back(f.Q.z), Q.push_back(f.Q.w);
+            smp.insert(smp.end(), it.msgs.begin(), it.msgs.end());
+            so.push_back(so.back() + it.size());
+            if (i >= 1) given = given && it.has_pre;
+            pre_in.push_back(it.pre);
+            ++i;
+        }
+        fo.push_back(fo.back() + n);
+        ex.insert(ex.end(), exTlbs[s].m, exTlbs[s].m + 16);
+    }
+    if (smp.empty()) smp.resize(7);
+    std::vector<mml_imu_preint> pre_out(pre_in.size());
+    std::vector<mml_lio_init_result> res(ns);
+    check(ctx,
+          mml_lio_initialize_batch(ctx, (int)ns, fo.data(), t.data(), P.data(), Q.data(), V.data(), bg.data(), ba.data(), smp.data(), so.data(),
+                                   ex.data(), given ? pre_in.data() : nullptr, pre_out.data(), res.data()),
+          "mml_lio_initialize_batch");
+    GravityVectors.resize(ns);
+    std::vector<bool> ok(ns, false);
+    for (size_t s = 0; s < ns; ++s) {
+        const mml_lio_init_result& r = res[s];
+        if (r.status == 3) continue;
+        for (int k = 0; k < 3; ++k) GravityVectors[s].v[k] = r.gravity[k];
+        if (r.status == 1) continue;
+        const int f0 = fo[s], n = fo[s + 1] - f0;
+        int i = f0;
+        for (auto& f : *frameLists[s]) {  // V / bg / ba as written (all of them, or the partial state)
+            for (int k = 0; k < 3; ++k) f.V.v[k] = V[3 * i + k], f.bg.v[k] = bg[3 * i + k], f.ba.v[k] = ba[3 * i + k];
+            ++i;
+        }
+        if (r.status != 0) continue;
+        std::vector<IMUIntegrator>& imu = *imus[s];
+        for (int j = 1; j < n; ++j) {
+            const mml_imu_preint& p = pre_out[f0 + j];
+            imu[j].pre = p;
+            imu[j].dq.x = p.dq[0], imu[j].dq.y = p.dq[1], imu[j].dq.z = p.dq[2], imu[j].dq.w = p.dq[3];
+            imu[j].has_pre = true;
+        }
+        Estimator::LidarFrame& back = frameLists[s]->back();
+        const int b = f0 + n - 1;
+        for (int k = 0; k < 3; ++k) back.P.v[k] = P[3 * b + k];
+        back.Q.x = Q[4 * b], back.Q.y = Q[4 * b + 1], back.Q.z = Q[4 * b + 2], back.Q.w = Q[4 * b + 3];
+        for (int j = 0; j < r.keep_from; ++j) frameLists[s]->pop_front();
+        imu.erase(imu.begin(), imu.begin() + r.keep_from);
+        ok[s] = true;
+    }
+    return ok;
+}
+
 }  // namespace mml
 #endif

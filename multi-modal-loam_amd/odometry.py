@@ -348,13 +348,18 @@ def try_map_initialization(frames, samples, exTlb=None):
     WindowEstimator(gravity=gravity).estimate(slots, frames, preints)."""
     import importlib
     M = importlib.import_module(__package__)
-    n = len(frames)
     pre = [None] + [fr["pre"] for fr in frames[1:]] if all("pre" in fr for fr in frames[1:]) else None
     res, st, pres = M.lio_initialize([fr["t"] for fr in frames], [fr["P"] for fr in frames], [fr["Q"] for fr in frames],
                                      [fr["V"] for fr in frames], [fr["bg"] for fr in frames], [fr["ba"] for fr in frames],
                                      samples, np.eye(4) if exTlb is None else exTlb, pre)
+    return _apply_map_initialization(M, frames, samples, res, st, pres)
+
+
+def _apply_map_initialization(M, frames, samples, res, st, pres):
+    """The list edits of TryMAPInitialization for one frame list, from what lio_initialize / lio_initialize_batch returned."""
+    n = len(frames)
     gravity = np.array(res.gravity)
-    if res.status == M.LIO_INIT_BIAS:
+    if res.status in (M.LIO_INIT_BIAS, M.LIO_INIT_NOT_PD):
         return False, gravity, pres
     written = n if res.status == M.LIO_INIT_OK else res.fail_frame + 1
     for i in range(written):
@@ -370,3 +375,28 @@ def try_map_initialization(frames, samples, exTlb=None):
     del samples[:res.keep_from]
     pres = [None] + pres[1 + res.keep_from:]
     return True, gravity, pres
+
+
+def try_map_initialization_batch(frames_list, samples_list, exTlb=None, ctx=None):
+    """try_map_initialization for n segments through ONE mml_lio_initialize_batch call: frames_list[s] / samples_list[s] are one
+    segment's frame list and IMU messages, each changed in place exactly as try_map_initialization changes them; exTlb: None
+    (identity), one 4 x 4 for all, or one per segment (n, 4, 4).  A segment whose pre-integration covariance is not positive
+    definite (status LIO_INIT_NOT_PD, e.g. an empty interval) counts as not ok with nothing written.  ctx None: the host
+    routine; a Context: the device call, bit-identical to it.  Returns a list of (ok, gravity, preints), ready for
+    BatchWindowEstimator(gravity=np.stack([g for _, g, _ in out]))."""
+    import importlib
+    M = importlib.import_module(__package__)
+    n_seg = len(frames_list)
+    if len(samples_list) != n_seg:
+        raise ValueError("frames_list and samples_list must have one entry per segment (%d, %d)" % (n_seg, len(samples_list)))
+    ex = np.eye(4) if exTlb is None else np.asarray(exTlb, dtype=np.float64)
+    if ex.shape not in ((4, 4), (n_seg, 4, 4)):
+        raise ValueError("exTlb must be one 4 x 4 matrix or one per segment (%d, 4, 4), not %s" % (n_seg, ex.shape))
+    ex = np.broadcast_to(ex, (n_seg, 4, 4))
+    segs = []
+    for s, frames in enumerate(frames_list):
+        pre = [None] + [fr["pre"] for fr in frames[1:]] if all("pre" in fr for fr in frames[1:]) else None
+        segs.append(([fr["t"] for fr in frames], [fr["P"] for fr in frames], [fr["Q"] for fr in frames], [fr["V"] for fr in frames],
+                     [fr["bg"] for fr in frames], [fr["ba"] for fr in frames], samples_list[s], ex[s], pre))
+    out = M.lio_initialize_batch(segs, ctx)
+    return [_apply_map_initialization(M, frames_list[s], samples_list[s], *out[s]) for s in range(n_seg)]
