@@ -167,6 +167,31 @@ int mml_gicp_align(mml_ctx* ctx, const float* src_xyz, int n_src, const float* t
  * an uploaded or already undistorted cloud -- the refresh belongs between mml_extract and mml_undistort -- or when the slot's
  * raw scan was uploaded again after the extraction (the line ids of the raw records are re-derived from them).  Synchronous. */
 int mml_gicp_refresh(mml_ctx* ctx, int slot, float* extrinsic_inout, int apply, int* refreshed, mml_gicp_info* info);
+/* The two calls above for many problems in one device call.  The alignments of a call are independent (each starts from the
+ * identity guess) and go through the same kernels as the single calls, one BFGS workgroup per problem: every T, converged and
+ * info is what the single call returns for that problem alone, to the byte.  The context keeps one grow-only scratch block for
+ * the largest call it has seen (88 bytes per surf point, 76 more per source point), released by mml_destroy; MML_ERR_HIP, before
+ * any slot is touched, when it cannot be grown.
+ * mml_gicp_align_batch: problem i is rows src_offsets[i] .. src_offsets[i+1]-1 of src_xyz against rows tgt_offsets[i] ..
+ * tgt_offsets[i+1]-1 of tgt_xyz; T_inout + 16 i is its matrix (left alone unless converged[i]), a problem that does not align
+ * (fewer than 20 points on a side) leaves converged[i] = 0 and info[i] zeroed.  MML_ERR_INVALID for n outside
+ * 1 .. MML_GICP_BATCH_MAX, decreasing or negative offsets, a NULL pointer other than info.
+ * mml_gicp_refresh_batch: slot first_slot + i is treated as mml_gicp_refresh treats it.  chain == 0: row i of extrinsics is slot
+ * i's own matrix, in and out.  chain != 0: row 0 is the caller's persistent extri_mtx on entry (rows 1 .. are not read); on
+ * return row i is the matrix held after frame i -- slot i's alignment if it converged, else what row i - 1 holds -- and it is
+ * what is applied to slot i: a loop of mml_gicp_refresh over one matrix (the chain is run on the host between the result
+ * read-back and the one apply launch).  All slots are checked before any device work; a refusal names the slot, returns the
+ * single call's code (MML_ERR_INVALID for a range outside the context or count outside 1 .. MML_GICP_BATCH_MAX, MML_ERR_STATE
+ * for a slot that is uploaded, undistorted or re-uploaded since its extraction) and changes no slot and no matrix.  Four host
+ * synchronisations per call: slot states, surf counts, results, apply.  (The single calls are the n = 1 case of the same code;
+ * mml_last_error names the entry point that was called.)  MML_GICP_BATCH_MAX bounds n and count because the problem index is
+ * a grid's y dimension. */
+#define MML_GICP_BATCH_MAX 65535   /* problems / slots per call */
+int mml_gicp_align_batch(mml_ctx* ctx, int n, const float* src_xyz, const int* src_offsets /* n + 1 */,
+                         const float* tgt_xyz, const int* tgt_offsets /* n + 1 */,
+                         float* T_inout /* n x 16 */, int* converged /* n */, mml_gicp_info* info /* n, may be NULL */);
+int mml_gicp_refresh_batch(mml_ctx* ctx, int first_slot, int count, float* extrinsics /* count x 16, in/out */, int chain,
+                           int apply, int* refreshed /* count, may be NULL */, mml_gicp_info* info /* count, may be NULL */);
 
 /* ---- a1..a8: feature extraction -----------------------------------------------------------------
  * feature_extraction::unionCloudHandler minus the PCL GICP refresh (unionFeatureExtract.cpp:266-321):

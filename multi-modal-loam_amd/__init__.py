@@ -29,6 +29,7 @@ FW_BATCH_MAX = 1024     # MML_FW_BATCH_MAX: windows per call
 PREINT_BATCH_MAX = 8192  # MML_PREINT_BATCH_MAX: intervals per call of mml_imu_preintegrate_batch
 LIO_BATCH_MAX = 1024     # MML_LIO_BATCH_MAX: segments per call of mml_lio_initialize_batch
 LIO_BATCH_MAX_FRAMES = 8  # MML_LIO_BATCH_MAX_FRAMES: frames per segment
+GICP_BATCH_MAX = 65535    # MML_GICP_BATCH_MAX: problems / slots per call of mml_gicp_align_batch / mml_gicp_refresh_batch
 
 LIVOX_DTYPE = np.dtype([("offset_time", "<u4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4"),
                         ("reflectivity", "u1"), ("tag", "u1"), ("line", "u1"), ("_pad", "u1")])
@@ -230,6 +231,11 @@ def lib():
         if hasattr(L, "mml_lio_initialize_batch"):
             L.mml_lio_initialize_batch.restype = C.c_int
             L.mml_lio_initialize_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 13
+        if hasattr(L, "mml_gicp_align_batch"):
+            L.mml_gicp_align_batch.restype = C.c_int
+            L.mml_gicp_align_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
+            L.mml_gicp_refresh_batch.restype = C.c_int
+            L.mml_gicp_refresh_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -266,6 +272,26 @@ def _f32(a):
 
 def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def gicp_pack_pairs(pairs, T0=None):
+    """The arguments of mml_gicp_align_batch for a ragged list of (src, tgt) clouds: (src n x 3 float32, src_offsets int32[n + 1],
+    tgt, tgt_offsets, T float32[n, 4, 4]).  T0: None (identities), one 4 x 4 matrix for every problem, or n of them."""
+    n = len(pairs)
+    srcs = [_f32(s).reshape(-1, 3) for s, _ in pairs]
+    tgts = [_f32(t).reshape(-1, 3) for _, t in pairs]
+    so = np.zeros(n + 1, np.int32)
+    to = np.zeros(n + 1, np.int32)
+    so[1:] = np.cumsum([len(s) for s in srcs])
+    to[1:] = np.cumsum([len(t) for t in tgts])
+    src = np.ascontiguousarray(np.concatenate(srcs + [np.zeros((0, 3), np.float32)]))
+    tgt = np.ascontiguousarray(np.concatenate(tgts + [np.zeros((0, 3), np.float32)]))
+    if T0 is None:
+        T = np.tile(np.eye(4, dtype=np.float32), (n, 1, 1))
+    else:
+        T0 = np.asarray(T0, np.float32)
+        T = np.tile(T0, (n, 1, 1)) if T0.size == 16 else T0.reshape(n, 4, 4).copy()
+    return src, so, tgt, to, np.ascontiguousarray(T)
 
 
 class Context:
@@ -399,6 +425,33 @@ class Context:
         ref, info = C.c_int(0), GicpInfo()
         self._ck(lib().mml_gicp_refresh(self._h, C.c_int(slot), _p(T), C.c_int(1 if apply else 0), C.byref(ref), C.byref(info)))
         return bool(ref.value), T, info
+
+    def gicp_align_batch(self, pairs, T0=None):
+        """mml_gicp_align_batch: gicp_align for a list of (src, tgt) pairs in one device call; a list of (converged, T, GicpInfo)."""
+        src, so, tgt, to, T = gicp_pack_pairs(pairs, T0)
+        n = len(pairs)
+        conv = np.zeros(max(n, 1), np.int32)
+        info = (GicpInfo * max(n, 1))()
+        self._ck(lib().mml_gicp_align_batch(self._h, C.c_int(n), _p(src) if len(src) else None, _p(so), _p(tgt) if len(tgt) else None,
+                                            _p(to), _p(T), _p(conv), C.cast(info, C.c_void_p)))
+        return [(bool(conv[i]), T[i], info[i]) for i in range(n)]
+
+    def gicp_refresh_batch(self, first_slot, count, extrinsic, chain=True, apply=True):
+        """mml_gicp_refresh_batch: the refresh of `count` extracted slots in one device call.  chain=True: `extrinsic` is the one
+        persistent 4 x 4 extri_mtx carried through the frames; chain=False: count matrices, one per slot.  Returns
+        (refreshed[count] bool, T[count, 4, 4] float32 -- the matrix held after (and applied to) each frame --, [GicpInfo])."""
+        n = max(int(count), 1)
+        T = np.zeros((n, 4, 4), np.float32)
+        e = np.asarray(extrinsic, np.float32)
+        if chain:
+            T[0] = e.reshape(-1)[:16].reshape(4, 4)
+        else:
+            T[:] = e.reshape(n, 4, 4)
+        ref = np.zeros(n, np.int32)
+        info = (GicpInfo * n)()
+        self._ck(lib().mml_gicp_refresh_batch(self._h, C.c_int(first_slot), C.c_int(count), _p(T), C.c_int(1 if chain else 0),
+                                              C.c_int(1 if apply else 0), _p(ref), C.cast(info, C.c_void_p)))
+        return ref[:count].astype(bool), T[:count], list(info)[:count]
 
     def extract(self, first=0, count=1, livox_extrinsic=None):
         e = _f32(livox_extrinsic).reshape(16) if livox_extrinsic is not None else None

@@ -4201,14 +4201,14 @@ int mml_launch_cloud_decode(mml_ctx* ctx, int slot, const float* d_raw, int n, i
     return MML_OK;
 }
 
-// ring / line id of every raw point of one slot into raw_line[] (pass A of the three-pass bucketing on that slot; its block
-// histograms land in blk_cnt, which nobody reads afterwards)
-int mml_launch_raw_lines(mml_ctx* ctx, int slot) {
-    FeatParams P = make_params(ctx, slot);
+// ring / line id of every raw point of `count` slots into raw_line[] (pass A of the three-pass bucketing on those slots; its
+// block histograms land in blk_cnt, which nobody reads afterwards)
+int mml_launch_raw_lines(mml_ctx* ctx, int first, int count) {
+    FeatParams P = make_params(ctx, first);
     if (P.ab_ppt == 4)
-        hipLaunchKernelGGL((k_assign_a<4>), dim3(P.nblk_max, 1, 2), dim3(AB_THREADS), 0, MML_STREAM(ctx), P);
+        hipLaunchKernelGGL((k_assign_a<4>), dim3(P.nblk_max, count, 2), dim3(AB_THREADS), 0, MML_STREAM(ctx), P);
     else
-        hipLaunchKernelGGL((k_assign_a<1>), dim3(P.nblk_max, 1, 2), dim3(AB_THREADS), 0, MML_STREAM(ctx), P);
+        hipLaunchKernelGGL((k_assign_a<1>), dim3(P.nblk_max, count, 2), dim3(AB_THREADS), 0, MML_STREAM(ctx), P);
     MML_HIP(hipGetLastError());
     return MML_OK;
 }

@@ -6,14 +6,19 @@
 // reference tree; this follows the published algorithm of PCL 1.8.1 (gicp.hpp; bfgs.h = GSL's vector_bfgs2 with
 // Fletcher's line search).
 //
-// What runs where (everything on the ctx stream, one 96-byte read-back at the end):
+// ONE set of kernels serves the single calls (mml_gicp_align, mml_gicp_refresh) and the batch calls (mml_gicp_align_batch,
+// mml_gicp_refresh_batch): a call is n >= 1 independent alignments described by a table of GicpProb records, the problem index is
+// blockIdx.y (blockIdx.x of k_gicp_bfgs), and the single calls are the n = 1 case.  A problem's arithmetic does not depend on
+// what else is in the call, so a batch result equals the single call's bit for bit.
+//
+// What runs where (everything on the ctx stream, one read-back of 96 bytes per problem at the end):
 //   k_gicp_cov   one lane per point: exact 20-NN in its own cloud by brute force over LDS tiles (the clouds are a few
 //                hundred to a few thousand surf points -- the search grid of the association would cost more to build
 //                than the N^2 distance tests), top-20 list as sorted 64-bit (distance, index) keys in registers, second
 //                moments in neighbour order, symmetric eigen-solver, covariance = sum of v_k u_k u_k^T as PCL forms it (v = 1, 1, 1e-3)
 //   k_gicp_corr  one lane per source point: transform with the current estimate, exact 1-NN in the target, Mahalanobis
 //                matrix (R C1 R^T + C2)^-1
-//   k_gicp_bfgs  ONE workgroup: the whole inner BFGS minimisation of f(x) = 1/m sum res^T M res over x = (t, roll, pitch, yaw).
+//   k_gicp_bfgs  ONE workgroup per problem: the whole inner BFGS minimisation of f(x) = 1/m sum res^T M res over x = (t, roll, pitch, yaw).
 //                Every thread runs the (scalar) BFGS / line-search control flow on identical values; an objective
 //                evaluation is a strided pass over the correspondences + a block reduction of 13 doubles, broadcast
 //                back to all threads.  The kernel then forms the new 4 x 4 float transformation, the convergence measure
@@ -33,18 +38,37 @@ constexpr int TILE = 1024;        // points per LDS tile of the brute-force sear
 constexpr int BF_THREADS = 256;
 constexpr double GICP_EPS = 1e-3, ROT_EPS = 2e-3, TRANS_EPS = 1e-6;
 
-struct GicpState {  // device-resident state of the outer loop
+struct GicpState {  // device-resident state of the outer loop, one per problem
     float T[16];    // transformation_ (row-major)
     int converged, failed, nr, evals;
     double fobj, delta;
+};
+
+// One alignment of a call: where its clouds and its per-point arrays sit in the call's block.  The clouds of all problems are
+// packed into one float4 array; a point's covariance has the point's index, a source point's Mahalanobis matrix and
+// correspondence the index moff + i.  n_src = n_tgt = 0: nothing to align (a skipped slot, a cloud of fewer than GK points) --
+// every kernel leaves such a problem alone.
+struct GicpProb {
+    int src, tgt;      // first point of the source / target cloud
+    int n_src, n_tgt;
+    int moff;          // first entry of the source cloud in maha[] / corr[]
+    int _pad;
 };
 
 __device__ __forceinline__ unsigned long long dkey(float d, int id) {
     return ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)id;
 }
 
-__global__ __launch_bounds__(256) void k_gicp_cov(const float4* __restrict__ pts, int n, double* __restrict__ cov) {
+// grid (blocks of the call's largest cloud, problems, 2): z = 0 the target clouds, 1 the source clouds.  A block wholly past its
+// cloud's size leaves before the first barrier.
+__global__ __launch_bounds__(256) void k_gicp_cov(const GicpProb* __restrict__ tab, const float4* __restrict__ pts_all,
+                                                  double* __restrict__ cov_all) {
     __shared__ float4 tile[TILE];
+    const GicpProb P = tab[blockIdx.y];
+    const int n = blockIdx.z ? P.n_src : P.n_tgt, first = blockIdx.z ? P.src : P.tgt;
+    if ((int)(blockIdx.x * blockDim.x) >= n) return;
+    const float4* __restrict__ pts = pts_all + first;
+    double* __restrict__ cov = cov_all + 9 * (size_t)first;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const float4 q = pts[i < n ? i : n - 1];
     unsigned long long k[GK];
@@ -119,11 +143,22 @@ __device__ __forceinline__ void tf_pt(const float* T, float x, float y, float z,
     for (int r = 0; r < 3; ++r) o[r] = ((T[4 * r] * x + T[4 * r + 1] * y) + T[4 * r + 2] * z) + T[4 * r + 3];
 }
 
-__global__ __launch_bounds__(256) void k_gicp_corr(const float4* __restrict__ src, int ns, const float4* __restrict__ tgt, int nt,
-                                                   const double* __restrict__ csrc, const double* __restrict__ ctgt,
-                                                   const GicpState* st, int* __restrict__ corr, double* __restrict__ maha) {
+// grid (blocks of the call's largest source cloud, problems)
+__global__ __launch_bounds__(256) void k_gicp_corr(const GicpProb* __restrict__ tab, const float4* __restrict__ pts_all,
+                                                   const double* __restrict__ cov_all, const GicpState* st_all, int* __restrict__ corr_all,
+                                                   double* __restrict__ maha_all) {
     __shared__ float4 tile[TILE];
+    const GicpProb P = tab[blockIdx.y];
+    const int ns = P.n_src, nt = P.n_tgt;
+    if ((int)(blockIdx.x * blockDim.x) >= ns) return;
+    const GicpState* st = st_all + blockIdx.y;
     if (st->converged || st->failed) return;
+    const float4* __restrict__ src = pts_all + P.src;
+    const float4* __restrict__ tgt = pts_all + P.tgt;
+    const double* __restrict__ csrc = cov_all + 9 * (size_t)P.src;
+    const double* __restrict__ ctgt = cov_all + 9 * (size_t)P.tgt;
+    int* __restrict__ corr = corr_all + P.moff;
+    double* __restrict__ maha = maha_all + 9 * (size_t)P.moff;
     float T[16];
 #pragma unroll
     for (int c = 0; c < 16; ++c) T[c] = st->T[c];
@@ -574,11 +609,23 @@ __device__ int bfgs_iterate(Bfgs& B, const EvalCtx& E) {
     return 0;
 }
 
-__global__ __launch_bounds__(BF_THREADS) void k_gicp_bfgs(const float4* src, const float4* tgt, const int* corr, const double* maha, int m,
-                                                         GicpState* st) {
+// grid (problems): one workgroup per problem.  s_terms + s_tot are 13 x 513 + 13 doubles = 53,456 bytes of LDS (53,464 as
+// allocated), so a CU's 160 KiB (163,840 bytes) hold THREE such workgroups.  The scalar BFGS state costs 199 VGPRs per lane, which
+// allows two waves per SIMD, and a workgroup puts one wave on each of the four SIMDs: registers, not LDS, bound a CU to TWO
+// workgroups -- 512 problems resident on the 256 CUs at once, the rest queue behind them.
+__global__ __launch_bounds__(BF_THREADS) void k_gicp_bfgs(const GicpProb* __restrict__ tab, const float4* pts_all, const int* corr_all,
+                                                         const double* maha_all, GicpState* st_all) {
     __shared__ double s_terms[13 * EV_ROW];
     __shared__ double s_tot[13];
+    const GicpProb P = tab[blockIdx.x];
+    const int m = P.n_src;
+    if (m == 0) return;
+    GicpState* st = st_all + blockIdx.x;
     if (st->converged || st->failed) return;
+    const float4* src = pts_all + P.src;
+    const float4* tgt = pts_all + P.tgt;
+    const int* corr = corr_all + P.moff;
+    const double* maha = maha_all + 9 * (size_t)P.moff;
     if (m < 4) {  // NotEnoughPointsException: the outer loop ends unconverged
         if (threadIdx.x == 0) st->failed = 1;
         return;
@@ -638,7 +685,8 @@ __global__ __launch_bounds__(BF_THREADS) void k_gicp_bfgs(const float4* src, con
     }
 }
 
-__global__ void k_gicp_init(GicpState* st) {
+__global__ void k_gicp_init(GicpState* st_all) {  // grid (problems)
+    GicpState* st = st_all + blockIdx.x;
     if (threadIdx.x < 16) st->T[threadIdx.x] = (threadIdx.x % 5 == 0) ? 1.f : 0.f;
     if (threadIdx.x == 0) {
         st->converged = 0;
@@ -650,25 +698,46 @@ __global__ void k_gicp_init(GicpState* st) {
     }
 }
 
-// The slot's surf clouds as the feature node builds them (unionFeatureExtract.cpp:1024-1031, :1242-1252): the points labelled 2 in
+// The slots' surf clouds as the feature node builds them (unionFeatureExtract.cpp:1024-1031, :1242-1252): the points labelled 2 in
 // the order of the sensor's RAW cloud, the Velodyne one cropped near + far (:1287-1293), the Livox one near only (:925) --
-// its labelled points beyond far_th carry bit 7 in their label byte.  One wavefront per sensor walks the raw line ids in
+// its labelled points beyond far_th carry bit 7 in their label byte.  One wavefront per (sensor, slot) walks the raw line ids in
 // order and rebuilds every point's bucketed position (line start + rank among the earlier points of its line), which is
-// where its label and its coordinates live.  Not a hot path: one slot, once per refresh.
-__global__ __launch_bounds__(64) void k_gicp_gather_raw(const uint8_t* raw_line, const int* n_in, const int* seg_flat, const int* seg_flat_n, int blk_points,
-                                                       const uint8_t* label, const float4* ln_pts, int NV, float4* velo, float4* livox, int* counts) {
+// where its label and its coordinates live.  grid (2, slots), run twice: the count pass (tab == nullptr) leaves counts[2 i + sensor]
+// for the host to lay the call's clouds out -- 0, 0 for a slot the refresh skips (livox_corner_num <= 100) --, the write pass puts
+// the clouds of the problems that align at their offsets in pts.
+struct GatherArgs {
+    const uint8_t* raw_line;
+    const int *n_in, *seg_flat, *seg_flat_n, *fu_info;
+    const uint8_t* label;
+    const float4* ln_pts;
+    int first, NT, NV, blk_points;
+};
+__global__ __launch_bounds__(64) void k_gicp_gather_raw(GatherArgs A, const GicpProb* tab, float4* pts, int* counts) {
     __shared__ int s_run[256];
-    const int sensor = blockIdx.x, lane = threadIdx.x;
-    const int n = n_in[sensor], region = sensor == 0 ? 0 : NV;
+    const int sensor = blockIdx.x, lane = threadIdx.x, slot = A.first + blockIdx.y;
+    float4* out = nullptr;
+    if (tab) {
+        const GicpProb P = tab[blockIdx.y];
+        if (P.n_src == 0) return;
+        out = pts + (sensor == 0 ? P.tgt : P.src);
+    } else if (!(A.fu_info[8 * (size_t)slot + 4] > 100)) {  // union_msg.livox_corner_num > 100 (unionFeatureExtract.cpp:302)
+        if (lane == 0) counts[2 * blockIdx.y + sensor] = 0;
+        return;
+    }
+    const size_t o = (size_t)slot * A.NT;
+    const uint8_t* raw_line = A.raw_line + o;
+    const uint8_t* label = A.label + o;
+    const float4* ln_pts = A.ln_pts + o;
+    const int n = A.n_in[2 * (size_t)slot + sensor], region = sensor == 0 ? 0 : A.NV;
+    const int blk_points = A.blk_points;
     for (int k = lane; k < 256; k += 64) s_run[k] = 0;
     __syncthreads();
-    float4* out = sensor == 0 ? velo : livox;
     const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
     int n_out = 0;
     // storage: block-major (blocks of blk_points raw points; one block = the whole scan after the three-pass bucketing), line-bucketed
     // inside a block, raw order inside a (block, line) segment -- segment (blk, key) starts at flat[blk * nkeys + key]
-    const int* flat = seg_flat + sensor * MML_SEG_FLAT;
-    const int nkeys = seg_flat_n[2 * sensor + 1];
+    const int* flat = A.seg_flat + ((size_t)slot * 2 + sensor) * MML_SEG_FLAT;
+    const int nkeys = A.seg_flat_n[(size_t)slot * 4 + 2 * sensor + 1];
     for (int i0 = 0; i0 < n; i0 += 64) {
         if (i0 % blk_points == 0 && i0 > 0) {  // (blk_points is a multiple of 64: a wavefront round never straddles blocks)
             __syncthreads();
@@ -699,15 +768,19 @@ __global__ __launch_bounds__(64) void k_gicp_gather_raw(const uint8_t* raw_line,
             take = (l & 3u) == 2u && l < (sensor == 0 ? 0x80u : 0x100u);
         }
         const unsigned long long wm = __ballot(take);
-        if (take) out[n_out + __popcll(wm & lt)] = ln_pts[p];
+        if (take && out) out[n_out + __popcll(wm & lt)] = ln_pts[p];
         n_out += __popcll(wm);
     }
-    if (lane == 0) counts[sensor] = n_out;
+    if (!tab && lane == 0) counts[2 * blockIdx.y + sensor] = n_out;
 }
 
-__global__ void k_gicp_apply(float4* pts, int n, const float* T) {  // pcl::transformPointCloud, float (PCL 1.8.1)
+// pcl::transformPointCloud, float (PCL 1.8.1), on the Livox regions of the slots first .. : grid (blocks of the largest region,
+// slots), slot i's matrix is T + 16 i and its point count n[i] (0: not transformed)
+__global__ void k_gicp_apply(float4* ln_pts, int first, int NT, int NV, const int* n, const float* T_all) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+    if (i >= n[blockIdx.y]) return;
+    float4* pts = ln_pts + (size_t)(first + blockIdx.y) * NT + NV;
+    const float* T = T_all + 16 * (size_t)blockIdx.y;
     float4 p = pts[i];
     const float x = T[0] * p.x + T[1] * p.y + T[2] * p.z + T[3];
     const float y = T[4] * p.x + T[5] * p.y + T[6] * p.z + T[7];
@@ -718,135 +791,320 @@ __global__ void k_gicp_apply(float4* pts, int n, const float* T) {  // pcl::tran
     pts[i] = p;
 }
 
-struct Scratch {
-    float4 *src = nullptr, *tgt = nullptr;
-    double *csrc = nullptr, *ctgt = nullptr, *maha = nullptr;
-    int* corr = nullptr;
-    GicpState* st = nullptr;
-    int* counts = nullptr;
-    float* dT = nullptr;
-    std::vector<void*> owned;
-    bool take(void** p, size_t bytes) {
-        if (hipMalloc(p, bytes ? bytes : 16) != hipSuccess) return false;
-        owned.push_back(*p);
-        return true;
+size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+// io block (device + pinned twin) of a call of n problems: what crosses the bus.  `pts`: the packed clouds of mml_gicp_align*,
+// which come from the host (the refresh gathers its clouds on the device, into the big block)
+struct IoLayout {
+    size_t tab, st, cnt, mat, napp, fi, cb, fl, pts, bytes;
+    IoLayout(size_t n, size_t n_pts) {
+        size_t o = 0;
+        const auto take = [&](size_t b) {
+            const size_t at = o;
+            o += align16(b);
+            return at;
+        };
+        tab = take(sizeof(GicpProb) * n);
+        st = take(sizeof(GicpState) * n);
+        cnt = take(sizeof(int) * 2 * n);
+        mat = take(sizeof(float) * 16 * n);
+        napp = take(sizeof(int) * n);
+        fi = take(sizeof(int) * 8 * n);
+        cb = take(sizeof(int) * 2 * n);
+        fl = take(sizeof(int) * 2 * n);
+        pts = take(sizeof(float4) * n_pts);
+        bytes = o;
     }
-    ~Scratch() {
-        for (void* p : owned) hipFree(p);
+};
+// big block (device only): 72 bytes of covariance per point, 72 + 4 bytes per source point, and the refresh's 16 bytes per point
+struct BigLayout {
+    size_t pts, cov, maha, corr, bytes;
+    BigLayout(size_t n_pts, size_t n_srcs, bool with_pts) {
+        pts = 0;
+        cov = with_pts ? align16(sizeof(float4) * n_pts) : 0;
+        maha = cov + align16(sizeof(double) * 9 * n_pts);
+        corr = maha + align16(sizeof(double) * 9 * n_srcs);
+        bytes = corr + align16(sizeof(int) * n_srcs);
     }
 };
 
-// align on device clouds already in S.src / S.tgt; T_inout written only on convergence
-int gicp_run(mml_ctx* ctx, Scratch& S, int n_src, int n_tgt, float* T_inout, int* converged, mml_gicp_info* info) {
+}  // namespace
+
+// Grow-only scratch of the alignments, owned by the context: nothing is allocated or freed per call once the largest call has
+// been seen.  Every entry point drains the stream before it returns, so reserve() never replaces a buffer in use.
+struct MmlGicpDev {
+    MmlStaging<char> io;
+    MmlStaging<char, false> big;
+};
+
+void mml_gicp_release(mml_ctx* ctx) {
+    MmlGicpDev* d = ctx->gicp;
+    if (!d) return;
+    d->io.release();
+    d->big.release();
+    delete d;
+    ctx->gicp = nullptr;
+}
+
+namespace {
+
+MmlGicpDev* gicp_dev(mml_ctx* ctx) {
+    if (!ctx->gicp) ctx->gicp = new MmlGicpDev();
+    return ctx->gicp;
+}
+
+// Lays problem `P` of ns source and nt target points out behind the n_pts points and n_srcs source points already placed.
+// PCL: "number of points smaller than k_correspondences_" -> no alignment: such a problem gets no room and n_src = n_tgt = 0.
+void place_problem(GicpProb& P, int ns, int nt, size_t& n_pts, size_t& n_srcs) {
+    memset(&P, 0, sizeof(P));
+    if (ns < GK || nt < GK) return;
+    P.src = (int)n_pts;
+    P.tgt = (int)(n_pts + ns);
+    P.n_src = ns;
+    P.n_tgt = nt;
+    P.moff = (int)n_srcs;
+    n_pts += (size_t)ns + nt;
+    n_srcs += ns;
+}
+
+// The launch sequence of a call: the n alignments of d_tab on the clouds in pts, states read back into h_st (one host
+// synchronisation).  max_src / max_tgt: the largest clouds among the problems that align.
+int gicp_core(mml_ctx* ctx, int n, int max_src, int max_tgt, const GicpProb* d_tab, const float4* pts, double* cov, double* maha, int* corr,
+              GicpState* d_st, GicpState* h_st) {
     hipStream_t s = MML_STREAM(ctx);
-    *converged = 0;
-    if (info) memset(info, 0, sizeof(*info));
-    if (n_src < GK || n_tgt < GK) return MML_OK;  // PCL: "number of points smaller than k_correspondences_" -> no alignment
-    bool ok = S.take((void**)&S.csrc, sizeof(double) * 9 * (size_t)n_src) && S.take((void**)&S.ctgt, sizeof(double) * 9 * (size_t)n_tgt) &&
-              S.take((void**)&S.maha, sizeof(double) * 9 * (size_t)n_src) && S.take((void**)&S.corr, sizeof(int) * (size_t)n_src) &&
-              S.take((void**)&S.st, sizeof(GicpState));
-    MML_REQUIRE(ok, MML_ERR_HIP, "mml_gicp: device allocation failed");
     MmlStageScope t(ctx, "gicp");
-    hipLaunchKernelGGL(k_gicp_init, dim3(1), dim3(64), 0, s, S.st);
-    hipLaunchKernelGGL(k_gicp_cov, dim3((n_tgt + 255) / 256), dim3(256), 0, s, S.tgt, n_tgt, S.ctgt);
-    hipLaunchKernelGGL(k_gicp_cov, dim3((n_src + 255) / 256), dim3(256), 0, s, S.src, n_src, S.csrc);
+    const int max_c = max_src > max_tgt ? max_src : max_tgt;
+    hipLaunchKernelGGL(k_gicp_init, dim3(n), dim3(64), 0, s, d_st);
+    hipLaunchKernelGGL(k_gicp_cov, dim3((max_c + 255) / 256, n, 2), dim3(256), 0, s, d_tab, pts, cov);
     for (int it = 0; it < 10; ++it) {  // setMaximumIterations(10); finished states skip their rounds
-        hipLaunchKernelGGL(k_gicp_corr, dim3((n_src + 255) / 256), dim3(256), 0, s, S.src, n_src, S.tgt, n_tgt, S.csrc, S.ctgt, S.st, S.corr,
-                           S.maha);
-        hipLaunchKernelGGL(k_gicp_bfgs, dim3(1), dim3(BF_THREADS), 0, s, S.src, S.tgt, S.corr, S.maha, n_src, S.st);
+        hipLaunchKernelGGL(k_gicp_corr, dim3((max_src + 255) / 256, n), dim3(256), 0, s, d_tab, pts, cov, d_st, corr, maha);
+        hipLaunchKernelGGL(k_gicp_bfgs, dim3(n), dim3(BF_THREADS), 0, s, d_tab, pts, corr, maha, d_st);
     }
     MML_HIP(hipGetLastError());
-    GicpState h;
-    MML_HIP(hipMemcpyAsync(&h, S.st, sizeof(h), hipMemcpyDeviceToHost, s));
+    MML_HIP(hipMemcpyAsync(h_st, d_st, sizeof(GicpState) * (size_t)n, hipMemcpyDeviceToHost, s));
     MML_HIP(hipStreamSynchronize(s));
+    return MML_OK;
+}
+
+// what the caller sees of problem P: T written only on convergence, info zeroed for a problem that did not align
+void gicp_result(const GicpProb& P, const GicpState& h, float* T, int* converged, mml_gicp_info* info) {
+    *converged = 0;
+    if (info) memset(info, 0, sizeof(*info));
+    if (P.n_src == 0) return;
     *converged = (h.converged && !h.failed) ? 1 : 0;
-    if (*converged) memcpy(T_inout, h.T, sizeof(float) * 16);
+    if (*converged) memcpy(T, h.T, sizeof(float) * 16);
     if (info) {
         info->outer_iterations = h.nr;
         info->objective_evaluations = h.evals;
         info->objective = h.fobj;
-        info->n_source = n_src;
-        info->n_target = n_tgt;
+        info->n_source = P.n_src;
+        info->n_target = P.n_tgt;
     }
+}
+
+int gicp_enter(mml_ctx* ctx) {
+    MML_HIP(hipSetDevice(ctx->device));
+    int rc = mml_sync_all(ctx);
+    if (rc != MML_OK) return rc;
+    ctx->cur = 0;
+    return MML_OK;
+}
+
+// The n alignments of mml_gicp_align_batch; mml_gicp_align is its n = 1 case.  `who`: the entry point the caller used, which
+// is the name a refusal carries.
+int gicp_align_n(mml_ctx* ctx, const char* who, int n, const float* src_xyz, const int* src_offsets, const float* tgt_xyz,
+                 const int* tgt_offsets, float* T_inout, int* converged, mml_gicp_info* info) {
+    if (n < 1 || n > MML_GICP_BATCH_MAX) return mml_refuse(ctx, MML_ERR_INVALID, "%s: n = %d is outside 1 .. %d", who, n, MML_GICP_BATCH_MAX);
+    if (!(src_offsets && tgt_offsets && T_inout && converged)) return mml_refuse(ctx, MML_ERR_INVALID, "%s: a null argument", who);
+    if (src_offsets[0] < 0 || tgt_offsets[0] < 0) return mml_refuse(ctx, MML_ERR_INVALID, "%s: problem 0: a negative offset", who);
+    for (int i = 0; i < n; ++i)
+        if (src_offsets[i + 1] < src_offsets[i] || tgt_offsets[i + 1] < tgt_offsets[i])
+            return mml_refuse(ctx, MML_ERR_INVALID, "%s: problem %d: its clouds end before their start (offsets must not decrease)", who, i);
+    if ((src_offsets[n] > src_offsets[0] && !src_xyz) || (tgt_offsets[n] > tgt_offsets[0] && !tgt_xyz))
+        return mml_refuse(ctx, MML_ERR_INVALID, "%s: a null cloud", who);
+    int rc = gicp_enter(ctx);
+    if (rc != MML_OK) return rc;
+    std::vector<GicpProb> tab((size_t)n);
+    size_t n_pts = 0, n_srcs = 0;
+    int max_src = 0, max_tgt = 0;
+    for (int i = 0; i < n; ++i) {
+        place_problem(tab[i], src_offsets[i + 1] - src_offsets[i], tgt_offsets[i + 1] - tgt_offsets[i], n_pts, n_srcs);
+        max_src = tab[i].n_src > max_src ? tab[i].n_src : max_src;
+        max_tgt = tab[i].n_tgt > max_tgt ? tab[i].n_tgt : max_tgt;
+    }
+    if (n_pts > 0x7fffffffull) return mml_refuse(ctx, MML_ERR_CAPACITY, "%s: %zu points in one call", who, n_pts);
+    const IoLayout io((size_t)n, n_pts);
+    const BigLayout big(n_pts, n_srcs, false);
+    MmlGicpDev* d = gicp_dev(ctx);
+    if (n_pts > 0 && (d->io.reserve(ctx, io.bytes) || d->big.reserve(ctx, big.bytes))) return MML_ERR_HIP;
+    GicpState* h_st = nullptr;
+    if (n_pts > 0) {
+        hipStream_t s = MML_STREAM(ctx);
+        char *h = d->io.h, *g = d->io.d;
+        memcpy(h + io.tab, tab.data(), sizeof(GicpProb) * (size_t)n);
+        float4* hp = reinterpret_cast<float4*>(h + io.pts);
+        for (int i = 0; i < n; ++i) {
+            const GicpProb& P = tab[i];
+            const float* a = src_xyz + 3 * (size_t)src_offsets[i];
+            const float* b = tgt_xyz + 3 * (size_t)tgt_offsets[i];
+            for (int k = 0; k < P.n_src; ++k) hp[P.src + k] = make_float4(a[3 * k], a[3 * k + 1], a[3 * k + 2], 0.f);
+            for (int k = 0; k < P.n_tgt; ++k) hp[P.tgt + k] = make_float4(b[3 * k], b[3 * k + 1], b[3 * k + 2], 0.f);
+        }
+        MML_HIP(hipMemcpyAsync(g + io.tab, h + io.tab, sizeof(GicpProb) * (size_t)n, hipMemcpyHostToDevice, s));
+        MML_HIP(hipMemcpyAsync(g + io.pts, h + io.pts, sizeof(float4) * n_pts, hipMemcpyHostToDevice, s));
+        h_st = reinterpret_cast<GicpState*>(h + io.st);
+        rc = gicp_core(ctx, n, max_src, max_tgt, reinterpret_cast<const GicpProb*>(g + io.tab), reinterpret_cast<const float4*>(g + io.pts),
+                       reinterpret_cast<double*>(d->big.d + big.cov), reinterpret_cast<double*>(d->big.d + big.maha),
+                       reinterpret_cast<int*>(d->big.d + big.corr), reinterpret_cast<GicpState*>(g + io.st), h_st);
+        if (rc != MML_OK) return rc;
+    }
+    const GicpState none = {};
+    for (int i = 0; i < n; ++i) gicp_result(tab[i], h_st ? h_st[i] : none, T_inout + 16 * (size_t)i, converged + i, info ? info + i : nullptr);
     return MML_OK;
 }
 
 }  // namespace
+
+extern "C" int mml_gicp_align_batch(mml_ctx* ctx, int n, const float* src_xyz, const int* src_offsets, const float* tgt_xyz,
+                                    const int* tgt_offsets, float* T_inout, int* converged, mml_gicp_info* info) {
+    if (!ctx) return MML_ERR_INVALID;
+    return gicp_align_n(ctx, "mml_gicp_align_batch", n, src_xyz, src_offsets, tgt_xyz, tgt_offsets, T_inout, converged, info);
+}
 
 extern "C" int mml_gicp_align(mml_ctx* ctx, const float* src_xyz, int n_src, const float* tgt_xyz, int n_tgt, float* T_inout, int* converged,
                               mml_gicp_info* info) {
     if (!ctx) return MML_ERR_INVALID;
     MML_REQUIRE(n_src >= 0 && n_tgt >= 0 && (n_src == 0 || src_xyz) && (n_tgt == 0 || tgt_xyz) && T_inout && converged, MML_ERR_INVALID,
                 "bad arguments");
-    MML_HIP(hipSetDevice(ctx->device));
-    int rc = mml_sync_all(ctx);
+    const int so[2] = {0, n_src}, to[2] = {0, n_tgt};
+    return gicp_align_n(ctx, "mml_gicp_align", 1, src_xyz, so, tgt_xyz, to, T_inout, converged, info);
+}
+
+namespace {
+
+// The refresh of mml_gicp_refresh_batch; mml_gicp_refresh is its count = 1, chain = 0 case.  `who` as in gicp_align_n.
+int gicp_refresh_n(mml_ctx* ctx, const char* who, int first_slot, int count, float* extrinsics, int chain, int apply, int* refreshed,
+                   mml_gicp_info* info) {
+    if (count < 1 || count > MML_GICP_BATCH_MAX)
+        return mml_refuse(ctx, MML_ERR_INVALID, "%s: count = %d is outside 1 .. %d", who, count, MML_GICP_BATCH_MAX);
+    if (first_slot < 0 || first_slot >= ctx->B)
+        return mml_refuse(ctx, MML_ERR_INVALID, "%s: slot %d is outside the context's 0 .. %d", who, first_slot, ctx->B - 1);
+    if (count > ctx->B - first_slot)
+        return mml_refuse(ctx, MML_ERR_INVALID, "%s: slot %d is outside the context's 0 .. %d", who, ctx->B, ctx->B - 1);
+    if (!extrinsics) return mml_refuse(ctx, MML_ERR_INVALID, "%s: a null argument", who);
+    int rc = gicp_enter(ctx);
     if (rc != MML_OK) return rc;
-    ctx->cur = 0;
     hipStream_t s = MML_STREAM(ctx);
-    Scratch S;
-    bool ok = S.take((void**)&S.src, sizeof(float4) * (size_t)(n_src > 0 ? n_src : 1)) && S.take((void**)&S.tgt, sizeof(float4) * (size_t)(n_tgt > 0 ? n_tgt : 1));
-    MML_REQUIRE(ok, MML_ERR_HIP, "mml_gicp_align: device allocation failed");
-    std::vector<float4> h((size_t)(n_src > n_tgt ? n_src : n_tgt) + 1);
-    for (int i = 0; i < n_src; ++i) h[i] = make_float4(src_xyz[3 * i], src_xyz[3 * i + 1], src_xyz[3 * i + 2], 0.f);
-    if (n_src) MML_HIP(hipMemcpyAsync(S.src, h.data(), sizeof(float4) * n_src, hipMemcpyHostToDevice, s));
+    const size_t n = (size_t)count, f = (size_t)first_slot;
+    const IoLayout io(n, 0);
+    MmlGicpDev* d = gicp_dev(ctx);
+    if (d->io.reserve(ctx, io.bytes)) return MML_ERR_HIP;
+    char *h = d->io.h, *g = d->io.d;
+    // counters, valid points per sensor region of the slots' storage, the slots' state flags
+    const int *fi = reinterpret_cast<const int*>(h + io.fi), *cb = reinterpret_cast<const int*>(h + io.cb), *fl = reinterpret_cast<const int*>(h + io.fl);
+    MML_HIP(hipMemcpyAsync(h + io.fi, ctx->fu_info + 8 * f, sizeof(int) * 8 * n, hipMemcpyDeviceToHost, s));
+    MML_HIP(hipMemcpyAsync(h + io.cb, ctx->cb_n + 2 * f, sizeof(int) * 2 * n, hipMemcpyDeviceToHost, s));
+    MML_HIP(hipMemcpyAsync(h + io.fl, ctx->slot_flags + 2 * f, sizeof(int) * 2 * n, hipMemcpyDeviceToHost, s));
     MML_HIP(hipStreamSynchronize(s));
-    for (int i = 0; i < n_tgt; ++i) h[i] = make_float4(tgt_xyz[3 * i], tgt_xyz[3 * i + 1], tgt_xyz[3 * i + 2], 0.f);
-    if (n_tgt) MML_HIP(hipMemcpyAsync(S.tgt, h.data(), sizeof(float4) * n_tgt, hipMemcpyHostToDevice, s));
-    MML_HIP(hipStreamSynchronize(s));
-    return gicp_run(ctx, S, n_src, n_tgt, T_inout, converged, info);
+    for (int i = 0; i < count; ++i) {
+        // the refresh belongs to the feature node: it aligns the surf clouds of the EXTRACTED scan (raw coordinates, raw order)
+        if ((fl[2 * i] & 3) != 0)
+            return mml_refuse(ctx, MML_ERR_STATE, "%s: slot %d holds an uploaded or undistorted cloud (call it after mml_extract, before mml_undistort)",
+                              who, first_slot + i);
+        // (the one-pass bucketing keeps no per-point line ids; they are re-derived below from the slot's RAW buffers, which must
+        //  therefore still be the ones the extraction read -- not a scan staged early for the next call)
+        if (!ctx->raw_extracted[first_slot + i])
+            return mml_refuse(ctx, MML_ERR_STATE, "%s: slot %d's raw scan was re-uploaded after mml_extract (or never extracted)", who, first_slot + i);
+    }
+    std::vector<GicpProb> tab(n);
+    memset(tab.data(), 0, sizeof(GicpProb) * n);
+    int n_go = 0, go_lo = count, go_hi = -1;  // the frames that are not skipped, and the first and last of them
+    for (int i = 0; i < count; ++i)
+        if (fi[8 * i + 4] > 100) {  // union_msg.livox_corner_num > 100 (unionFeatureExtract.cpp:302)
+            ++n_go;
+            go_lo = i < go_lo ? i : go_lo;
+            go_hi = i;
+        }
+    const GicpState* h_st = nullptr;
+    size_t n_pts = 0, n_srcs = 0;
+    if (n_go > 0) {
+        GatherArgs A{ctx->raw_line, ctx->d_n_in, ctx->seg_flat, ctx->seg_flat_n, ctx->fu_info, ctx->ln_label, ctx->ln_pts,
+                     first_slot,    ctx->NT,     ctx->NV,       ctx->onepass ? MML_OP_BLK : (1 << 30)};
+        // (the one-pass bucketing keeps no per-point line ids: they are recomputed in one launch, for the slots from the first
+        //  to the last frame that aligns.  A skipped slot between them has its raw_line / raw_ori / blk_cnt rewritten too: with
+        //  the values they already hold, since they are a function of the slot's raw scan alone, which raw_extracted pins)
+        if (ctx->onepass) {
+            rc = mml_launch_raw_lines(ctx, first_slot + go_lo, go_hi - go_lo + 1);
+            if (rc != MML_OK) return rc;
+        }
+        hipLaunchKernelGGL(k_gicp_gather_raw, dim3(2, count), dim3(64), 0, s, A, (const GicpProb*)nullptr, (float4*)nullptr,
+                           reinterpret_cast<int*>(g + io.cnt));
+        MML_HIP(hipGetLastError());
+        MML_HIP(hipMemcpyAsync(h + io.cnt, g + io.cnt, sizeof(int) * 2 * n, hipMemcpyDeviceToHost, s));
+        MML_HIP(hipStreamSynchronize(s));
+        const int* cnt = reinterpret_cast<const int*>(h + io.cnt);
+        int max_src = 0, max_tgt = 0;
+        for (int i = 0; i < count; ++i) {  // source: Livox surf, target: Velodyne surf (:307)
+            place_problem(tab[i], cnt[2 * i + 1], cnt[2 * i], n_pts, n_srcs);
+            max_src = tab[i].n_src > max_src ? tab[i].n_src : max_src;
+            max_tgt = tab[i].n_tgt > max_tgt ? tab[i].n_tgt : max_tgt;
+        }
+        if (n_pts > 0x7fffffffull) return mml_refuse(ctx, MML_ERR_CAPACITY, "%s: %zu surf points in one call", who, n_pts);
+        if (n_pts > 0) {
+            const BigLayout big(n_pts, n_srcs, true);
+            if (d->big.reserve(ctx, big.bytes)) return MML_ERR_HIP;  // (no slot has been touched yet)
+            memcpy(h + io.tab, tab.data(), sizeof(GicpProb) * n);
+            MML_HIP(hipMemcpyAsync(g + io.tab, h + io.tab, sizeof(GicpProb) * n, hipMemcpyHostToDevice, s));
+            const GicpProb* d_tab = reinterpret_cast<const GicpProb*>(g + io.tab);
+            float4* pts = reinterpret_cast<float4*>(d->big.d + big.pts);
+            hipLaunchKernelGGL(k_gicp_gather_raw, dim3(2, count), dim3(64), 0, s, A, d_tab, pts, (int*)nullptr);
+            GicpState* hs = reinterpret_cast<GicpState*>(h + io.st);
+            rc = gicp_core(ctx, count, max_src, max_tgt, d_tab, pts, reinterpret_cast<double*>(d->big.d + big.cov),
+                           reinterpret_cast<double*>(d->big.d + big.maha), reinterpret_cast<int*>(d->big.d + big.corr),
+                           reinterpret_cast<GicpState*>(g + io.st), hs);
+            if (rc != MML_OK) return rc;
+            h_st = hs;
+        }
+    }
+    // extri_mtx through the frames: a frame that converged replaces it, every other frame keeps what the frame before it left
+    // (chained), or its own row (not chained)
+    const GicpState none = {};
+    float* h_mat = reinterpret_cast<float*>(h + io.mat);
+    int* h_napp = reinterpret_cast<int*>(h + io.napp);
+    int max_app = 0;
+    for (int i = 0; i < count; ++i) {
+        float* row = extrinsics + 16 * (size_t)i;
+        if (chain && i > 0) memcpy(row, row - 16, sizeof(float) * 16);
+        int conv = 0;
+        gicp_result(tab[i], h_st ? h_st[i] : none, row, &conv, info ? info + i : nullptr);
+        if (refreshed) refreshed[i] = conv;
+        // pcl::transformPointCloud(*livoCombinePtr, *livoCombinePtr, extri_mtx) (:312): the Livox region, of a frame that was not skipped
+        h_napp[i] = (apply && fi[8 * i + 4] > 100) ? cb[2 * i + 1] : 0;
+        memcpy(h_mat + 16 * (size_t)i, row, sizeof(float) * 16);
+        max_app = h_napp[i] > max_app ? h_napp[i] : max_app;
+    }
+    if (max_app > 0) {
+        MML_HIP(hipMemcpyAsync(g + io.mat, h + io.mat, io.fi - io.mat, hipMemcpyHostToDevice, s));  // matrices | point counts
+        hipLaunchKernelGGL(k_gicp_apply, dim3((max_app + 255) / 256, count), dim3(256), 0, s, ctx->ln_pts, first_slot, ctx->NT, ctx->NV,
+                           reinterpret_cast<const int*>(g + io.napp), reinterpret_cast<const float*>(g + io.mat));
+        MML_HIP(hipGetLastError());
+        MML_HIP(hipStreamSynchronize(s));
+    }
+    return MML_OK;
+}
+
+}  // namespace
+
+extern "C" int mml_gicp_refresh_batch(mml_ctx* ctx, int first_slot, int count, float* extrinsics, int chain, int apply, int* refreshed,
+                                      mml_gicp_info* info) {
+    if (!ctx) return MML_ERR_INVALID;
+    return gicp_refresh_n(ctx, "mml_gicp_refresh_batch", first_slot, count, extrinsics, chain, apply, refreshed, info);
 }
 
 extern "C" int mml_gicp_refresh(mml_ctx* ctx, int slot, float* extrinsic_inout, int apply, int* refreshed, mml_gicp_info* info) {
     if (!ctx) return MML_ERR_INVALID;
     MML_REQUIRE(slot >= 0 && slot < ctx->B && extrinsic_inout, MML_ERR_INVALID, "bad arguments");
-    MML_HIP(hipSetDevice(ctx->device));
-    int rc = mml_sync_all(ctx);
-    if (rc != MML_OK) return rc;
-    ctx->cur = 0;
-    hipStream_t s = MML_STREAM(ctx);
     if (refreshed) *refreshed = 0;
     if (info) memset(info, 0, sizeof(*info));
-    int fi[8], cb[2], fl[2];  // counters; valid points per sensor region of the slot's storage; the slot's state flags
-    MML_HIP(hipMemcpyAsync(fi, ctx->fu_info + 8 * (size_t)slot, sizeof(fi), hipMemcpyDeviceToHost, s));
-    MML_HIP(hipMemcpyAsync(cb, ctx->cb_n + 2 * (size_t)slot, sizeof(cb), hipMemcpyDeviceToHost, s));
-    MML_HIP(hipMemcpyAsync(fl, ctx->slot_flags + 2 * (size_t)slot, sizeof(fl), hipMemcpyDeviceToHost, s));
-    MML_HIP(hipStreamSynchronize(s));
-    // the refresh belongs to the feature node: it aligns the surf clouds of the EXTRACTED scan (raw coordinates, raw order)
-    MML_REQUIRE((fl[0] & 3) == 0, MML_ERR_STATE,
-                "mml_gicp_refresh: the slot holds an uploaded or undistorted cloud (call it after mml_extract, before mml_undistort)");
-    // (the one-pass bucketing keeps no per-point line ids; they are re-derived below from the slot's RAW buffers, which must
-    //  therefore still be the ones the extraction read -- not a scan staged early for the next call)
-    MML_REQUIRE(ctx->raw_extracted[slot], MML_ERR_STATE,
-                "mml_gicp_refresh: the slot's raw scan was re-uploaded after mml_extract (or never extracted)");
-    if (!(fi[4] > 100)) return MML_OK;  // union_msg.livox_corner_num > 100 (unionFeatureExtract.cpp:302)
-    Scratch S;
-    bool ok = S.take((void**)&S.src, sizeof(float4) * (size_t)(cb[1] + 1)) && S.take((void**)&S.tgt, sizeof(float4) * (size_t)(cb[0] + 1)) &&
-              S.take((void**)&S.counts, sizeof(int) * 2) && S.take((void**)&S.dT, sizeof(float) * 16);
-    MML_REQUIRE(ok, MML_ERR_HIP, "mml_gicp_refresh: device allocation failed");
-    int cnt[2] = {0, 0};
-    {
-        const size_t o = (size_t)slot * ctx->NT;
-        // (the one-pass bucketing keeps no per-point line ids: they are recomputed for this one slot)
-        if (ctx->onepass) {
-            rc = mml_launch_raw_lines(ctx, slot);
-            if (rc != MML_OK) return rc;
-        }
-        hipLaunchKernelGGL(k_gicp_gather_raw, dim3(2), dim3(64), 0, s, ctx->raw_line + o, ctx->d_n_in + 2 * (size_t)slot,
-                           ctx->seg_flat + (size_t)slot * 2 * MML_SEG_FLAT, ctx->seg_flat_n + (size_t)slot * 4,
-                           ctx->onepass ? MML_OP_BLK : (1 << 30), ctx->ln_label + o, ctx->ln_pts + o, ctx->NV, S.tgt, S.src, S.counts);
-        MML_HIP(hipMemcpyAsync(cnt, S.counts, sizeof(cnt), hipMemcpyDeviceToHost, s));
-        MML_HIP(hipStreamSynchronize(s));
-    }
-    int conv = 0;
-    rc = gicp_run(ctx, S, cnt[1], cnt[0], extrinsic_inout, &conv, info);  // source: Livox surf, target: Velodyne surf (:307)
-    if (rc != MML_OK) return rc;
-    if (refreshed) *refreshed = conv;
-    if (apply && cb[1] > 0) {  // pcl::transformPointCloud(*livoCombinePtr, *livoCombinePtr, extri_mtx) (:312): the Livox region
-        MML_HIP(hipMemcpyAsync(S.dT, extrinsic_inout, sizeof(float) * 16, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_gicp_apply, dim3((cb[1] + 255) / 256), dim3(256), 0, s, ctx->ln_pts + (size_t)slot * ctx->NT + ctx->NV,
-                           cb[1], S.dT);
-        MML_HIP(hipGetLastError());
-        MML_HIP(hipStreamSynchronize(s));
-    }
-    return MML_OK;
+    return gicp_refresh_n(ctx, "mml_gicp_refresh", slot, 1, extrinsic_inout, 0, apply, refreshed, info);
 }

@@ -69,6 +69,7 @@ struct MmlComm;   // comm.hip: RCCL communicator + window-solve buffers
 struct MmlFwDev;  // fullwindow_dev.hip: parameter / scratch buffers of the device-resident full-window solve
 struct MmlPreintDev;  // imu_preint.hip: buffers of mml_imu_preintegrate_batch
 struct MmlLioDev;     // lio_init_batch.hip: the block of mml_lio_initialize_batch
+struct MmlGicpDev;    // gicp.hip: the blocks of the GICP alignments (single and batch calls)
 
 struct mml_ctx {
     mml_config cfg;
@@ -76,6 +77,7 @@ struct mml_ctx {
     MmlFwDev* fwdev = nullptr;
     MmlPreintDev* preint = nullptr;
     MmlLioDev* lio = nullptr;
+    MmlGicpDev* gicp = nullptr;
     // frame-parallel window solve (solve.hip): one state machine copy, 4 counters and two record buffers per slot
     void* wstate = nullptr;
     double* wrec = nullptr;
@@ -377,8 +379,9 @@ int mml_feature_init(mml_ctx* ctx);
 void mml_fullwindow_dev_release(mml_ctx* ctx);
 void mml_imu_preint_release(mml_ctx* ctx);
 void mml_lio_init_release(mml_ctx* ctx);
+void mml_gicp_release(mml_ctx* ctx);
 int mml_launch_detect_line(mml_ctx* ctx, int n, uint16_t* d_final);
-int mml_launch_raw_lines(mml_ctx* ctx, int slot);  // raw_line[] of one slot (ring / line id per raw point), for the GICP refresh
+int mml_launch_raw_lines(mml_ctx* ctx, int first, int count);  // raw_line[] of the slots (ring / line id per raw point), for the GICP refresh
 int mml_launch_linearize(mml_ctx* ctx, int slot, const double* d_x, const double* d_Tbl, double w_tan,
                          double huber, double* d_record, int frames = 1);
 

@@ -132,6 +132,33 @@ class feature_extraction {
         return refreshed != 0;
     }
 
+    // The refresh of unionCloudRefresh for `count` scans already uploaded to the slots first_slot .. (offline replay): ONE persistent
+    // extri_mtx carried through the frames -- a frame whose alignment converged replaces it, every other frame (not converged, or
+    // livox_corner_num <= 100) keeps it -- exactly the loop of unionCloudRefresh over the slots, in one mml_extract and one
+    // mml_gicp_refresh_batch.  fused_out[i]: frame i's fused cloud, its Livox part under the matrix held after frame i;
+    // infos (may be null): the frames' counters.  Returns the number of frames that refreshed; extri_mtx is the last frame's matrix.
+    int unionCloudRefreshBatch(int first_slot, int count, float extri_mtx[16], std::vector<PointCloud>& fused_out,
+                               std::vector<mml_scan_info>* infos = nullptr) {
+        mml_ctx* c = ctx_.get();
+        check(c, mml_extract(c, first_slot, count, nullptr), "extract");
+        std::vector<float> T(16 * (size_t)(count > 0 ? count : 1));
+        std::vector<int> refreshed(count > 0 ? count : 1, 0);
+        for (int k = 0; k < 16; ++k) T[k] = extri_mtx[k];
+        check(c, mml_gicp_refresh_batch(c, first_slot, count, T.data(), 1, 1, refreshed.data(), nullptr), "gicp_refresh_batch");
+        for (int k = 0; k < 16; ++k) extri_mtx[k] = T[16 * (size_t)(count - 1) + k];
+        fused_out.resize(count);
+        if (infos) infos->resize(count);
+        int n_refreshed = 0;
+        for (int i = 0; i < count; ++i) {
+            mml_scan_info info;
+            check(c, mml_scan_info_get(c, first_slot + i, &info), "scan_info");
+            download(first_slot + i, info.n_points, fused_out[i]);
+            if (infos) (*infos)[i] = info;
+            n_refreshed += refreshed[i] != 0;
+        }
+        return n_refreshed;
+    }
+
     // getVeloFeature (:1113-1117) and getHoriFeatureExtract (:952-956) on their own
     void getVeloFeature(const float* velo_xyzi, int n, PointCloud& points_normal, mml_scan_info& info, int slot = 0) {
         unionCloud(velo_xyzi, n, nullptr, 0, nullptr, points_normal, info, slot);
@@ -192,6 +219,54 @@ inline bool icp_ext_matching(Context& ctx, const PointCloud& cloud_src, const Po
         p.z = z;
     }
     return true;
+}
+
+// icp_ext_matching for a list of cloud pairs in one device call (mml_gicp_align_batch): pair i's result is what icp_ext_matching
+// returns for it alone.  icp_mtx: 16 floats per pair, in/out; cloud_aligned[i] is filled, and converged[i] set, only when pair i
+// converged.  Returns the number of pairs that converged.
+inline int icp_ext_matching_batch(Context& ctx, const std::vector<PointCloud>& cloud_src, const std::vector<PointCloud>& cloud_tgt,
+                                  std::vector<PointCloud>& cloud_aligned, std::vector<float>& icp_mtx, std::vector<char>& converged) {
+    if (cloud_src.size() != cloud_tgt.size() || icp_mtx.size() != 16 * cloud_src.size())
+        throw std::runtime_error("icp_ext_matching_batch: one target and 16 matrix entries per source cloud");
+    const int n = (int)cloud_src.size();
+    std::vector<int> so(n + 1, 0), to(n + 1, 0);
+    for (int i = 0; i < n; ++i) {
+        so[i + 1] = so[i] + (int)cloud_src[i].size();
+        to[i + 1] = to[i] + (int)cloud_tgt[i].size();
+    }
+    std::vector<float> s(3 * (size_t)so[n] + 3), t(3 * (size_t)to[n] + 3);
+    for (int i = 0; i < n; ++i) {
+        for (size_t k = 0; k < cloud_src[i].size(); ++k) {
+            float* o = &s[3 * ((size_t)so[i] + k)];
+            o[0] = cloud_src[i][k].x, o[1] = cloud_src[i][k].y, o[2] = cloud_src[i][k].z;
+        }
+        for (size_t k = 0; k < cloud_tgt[i].size(); ++k) {
+            float* o = &t[3 * ((size_t)to[i] + k)];
+            o[0] = cloud_tgt[i][k].x, o[1] = cloud_tgt[i][k].y, o[2] = cloud_tgt[i][k].z;
+        }
+    }
+    std::vector<int> conv(n ? n : 1, 0);
+    check(ctx.get(), mml_gicp_align_batch(ctx.get(), n, s.data(), so.data(), t.data(), to.data(), icp_mtx.data(), conv.data(), nullptr),
+          "icp_ext_matching_batch");
+    cloud_aligned.resize(n);
+    converged.assign(n, 0);
+    int n_conv = 0;
+    for (int i = 0; i < n; ++i) {
+        if (!conv[i]) continue;
+        converged[i] = 1;
+        ++n_conv;
+        const float* m = &icp_mtx[16 * (size_t)i];
+        cloud_aligned[i] = cloud_src[i];
+        for (auto& p : cloud_aligned[i]) {
+            const float x = m[0] * p.x + m[1] * p.y + m[2] * p.z + m[3];
+            const float y = m[4] * p.x + m[5] * p.y + m[6] * p.z + m[7];
+            const float z = m[8] * p.x + m[9] * p.y + m[10] * p.z + m[11];
+            p.x = x;
+            p.y = y;
+            p.z = z;
+        }
+    }
+    return n_conv;
 }
 
 // ---- RemoveLidarDistortion (unionPoseEstimation.cpp:402-403): in place on the slot's device-resident fused cloud ----
