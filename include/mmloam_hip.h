@@ -127,6 +127,31 @@ int mml_scan_download_pointxyzinormal(mml_ctx* ctx, int slot, uint8_t* out, int 
  * mml_downsample, mml_estimate work on it); livox_*_num count the kept points only.  Synchronous. */
 int mml_cloud_upload(mml_ctx* ctx, int slot, const uint8_t* pointxyzinormal, int n_points, int n_velo);
 
+/* The registered cloud: the fused cloud of `count` slots moved into the world frame, the payload of /velo_full_cloud_mapped
+ * (unionPoseEstimation.cpp:896-911).  Slot first_slot + i goes through pointAssociateToMap (:199-213) with pose i of T_wl
+ * (count row-major 4x4 matrices: transformTobeMapped of :876-880); the upper three rows are applied as given, orthonormal
+ * or not.  n_points[i] is the slot's fused point count (what mml_scan_info_get returns), its records start at record
+ * n_points[0] + ... + n_points[i-1] of `out`, in the fused order of mml_scan_download_pointxyzinormal (Velodyne part,
+ * then Livox); a slot without points contributes none.  out == NULL: only n_points is filled (the sizing call).
+ * Each record is the 48-byte PointXYZINormal the reference's loop pushes back -- a default-constructed point that receives
+ * five fields, which is NOT the record of mml_scan_download_pointxyzinormal (that one carries the in-sweep time in normal_x
+ * and the ring / line in normal_y; both are 0 here, as in the reference's message):
+ *   x, y, z (floats 0-2): in double, (R[r][0] x + R[r][1] y) + R[r][2] z, then + t[r] -- Eigen's order for
+ *       topLeftCorner(3,3) * pin + topRightCorner(3,1), no fused multiply-add -- rounded once to float;
+ *   float 3 = 1; normal_x = normal_y = 0 (floats 4, 5); normal_z (float 6) = the label 0 / 1 / 2; float 7 = 0;
+ *   intensity (float 8) carried over; curvature and padding (floats 9-11) = 0.
+ * The slots are read as they stand (undistorted or not: the reference passes the undistorted cloud, the order of the calls
+ * is the caller's) and nothing in them is modified; slots filled by mml_extract and by mml_cloud_upload both work.
+ * One kernel launch for the whole call and TWO host synchronisations whatever `count` is (the counts of all slots in one
+ * copy; the records in one copy), one for the sizing call.  MML_ERR_CAPACITY, before any record is written, when
+ * capacity_points is below the total; MML_ERR_INVALID for a slot range outside the context, count < 1 (or above 65535),
+ * NULL T_wl or NULL n_points; MML_ERR_HIP, before any launch, when the device staging cannot be grown to the total. */
+int mml_cloud_download_registered_batch(mml_ctx* ctx, int first_slot, int count, const double* T_wl /* count x 16 */,
+                                        uint8_t* out, long capacity_points, int* n_points /* count */);
+/* One slot: the count = 1 case of the batch call (the same code path). */
+int mml_cloud_download_registered(mml_ctx* ctx, int slot, const double* T_wl /* 16 */, uint8_t* out, int capacity_points,
+                                  int* n_points);
+
 /* ---- the aligner's time-offset search ---------------------------
  * The numeric core of LidarsParamEstimator::estimate_timeoffset (unionLidarsAligner.cpp:1077-1153): the Velodyne
  * cloud (n_velo x 3 floats) goes through pcl::transformPointCloud with tf (row-major 4x4 floats, NULL = identity;

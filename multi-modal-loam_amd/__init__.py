@@ -236,6 +236,11 @@ def lib():
             L.mml_gicp_align_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
             L.mml_gicp_refresh_batch.restype = C.c_int
             L.mml_gicp_refresh_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        if hasattr(L, "mml_cloud_download_registered_batch"):
+            L.mml_cloud_download_registered_batch.restype = C.c_int
+            L.mml_cloud_download_registered_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]
+            L.mml_cloud_download_registered.restype = C.c_int
+            L.mml_cloud_download_registered.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         _lib = L
     return _lib
 
@@ -272,6 +277,23 @@ def _f32(a):
 
 def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def registered_poses(count, T_wl):
+    """The pose argument of mml_cloud_download_registered_batch: (count, 16) float64 from count 4 x 4 matrices -- (count, 4, 4)
+    or (count, 16); one (4, 4) or (16,) pose is accepted when count == 1.  ValueError for anything else."""
+    count = int(count)
+    if count < 1:
+        raise ValueError("count must be at least 1, not %d" % count)
+    T = np.asarray(T_wl, dtype=np.float64)
+    if T.shape in ((4, 4), (16,)):
+        if count != 1:
+            raise ValueError("one pose given for %d slots: T_wl must hold one 4 x 4 matrix per slot" % count)
+    elif T.ndim < 2 or T.shape[1:] not in ((4, 4), (16,)):
+        raise ValueError("T_wl must be (count, 4, 4) or (count, 16), not %s" % (T.shape,))
+    elif T.shape[0] != count:
+        raise ValueError("T_wl holds %d poses for %d slots" % (T.shape[0], count))
+    return np.ascontiguousarray(T.reshape(count, 16))
 
 
 def gicp_pack_pairs(pairs, T0=None):
@@ -401,6 +423,23 @@ class Context:
         out = np.zeros((max(n.value, 1), 12), np.float32)
         self._ck(lib().mml_scan_download_pointxyzinormal(self._h, C.c_int(slot), _p(out), C.c_int(n.value), C.byref(n)))
         return out[:n.value]
+
+    def cloud_download_registered(self, first_slot, count, T_wl):
+        """The registered clouds of `count` slots (unionPoseEstimation.cpp:896-911): slot first_slot + i moved into the world
+        frame by T_wl[i] (transformTobeMapped, 4 x 4; one matrix is enough when count == 1), as a list of (n_i, 12) float32
+        arrays of 48-byte PointXYZINormal records -- x y z 1 | 0 0 label 0 | intensity 0 0 0.  The sizing call, then ONE
+        data call for all slots (mml_cloud_download_registered_batch)."""
+        T = registered_poses(count, T_wl)
+        count = len(T)
+        n = np.zeros(count, np.int32)
+        f = lib().mml_cloud_download_registered_batch
+        self._ck(f(self._h, first_slot, count, _p(T), None, 0, _p(n)))
+        total = int(n.sum())
+        out = np.zeros((max(total, 1), 12), np.float32)
+        if total:
+            self._ck(f(self._h, first_slot, count, _p(T), _p(out), total, _p(n)))
+        ends = np.cumsum(n)
+        return [out[e - k:e] for e, k in zip(ends, n)]
 
     def cloud_upload(self, slot, records, n_velo=None):
         """A labelled fused cloud (n x 12 float32 = 48-byte PointXYZINormal records, velo_combine then livox_combine)

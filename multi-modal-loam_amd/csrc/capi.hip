@@ -504,6 +504,78 @@ __global__ void k_fused_arrays(FusedView V, int n, float4* xyzi, float* rel, uin
     line[g] = (uint8_t)ln;
     label[g] = V.label[pos];
 }
+// the per-point and per-slot arrays of a context that a kernel over the slots [first, ...) indexes by slot
+struct SlotArrays {
+    const float4* pts;
+    const int* gidx;
+    const int* rel;
+    const uint8_t* line;
+    const uint8_t* label;
+    const int* cb_n;
+    const int* seg_flat;
+    const int* seg_flat_n;
+    const int* slot_flags;
+    const int* fu_info;
+    int NV, NT, L, n_rings, first;
+};
+// The FusedView of one slot, derived on the device from the context-wide arrays; the flag word is read here, where fused_view
+// spends a synchronising read-back per slot.
+__device__ __forceinline__ FusedView slot_view(const SlotArrays& A, int slot) {
+    FusedView V;
+    const size_t off = (size_t)slot * A.NT;
+    V.pts = A.pts + off;
+    V.gidx = A.gidx + off;
+    V.rel = A.rel + off;
+    V.line = A.line + off;
+    V.label = A.label + off;
+    V.cb_n = A.cb_n + 2 * (size_t)slot;
+    V.seg_flat = A.seg_flat + (size_t)slot * 2 * MML_SEG_FLAT;
+    V.seg_flat_n = A.seg_flat_n + (size_t)slot * 4;
+    V.NV = A.NV;
+    V.NT = A.NT;
+    V.L = A.L;
+    V.n_rings = A.n_rings;
+    V.flags = A.slot_flags[2 * (size_t)slot];
+    return V;
+}
+// The registered cloud (unionPoseEstimation.cpp:896-903): every fused point of slot A.first + blockIdx.y through
+// pointAssociateToMap (:199-213) with that slot's pose, as the PointXYZINormal the loop pushes back -- a default-constructed
+// point (x y z 1 | 0 0 0 0 | 0 0 0 0) that receives x y z, intensity and normal_z only.  pout = R * pin + t in double, in Eigen's
+// order (R0 x + R1 y) + R2 z, then + t, no contraction (-ffp-contract=off), rounded once to float.  par: the call's poses
+// (16 doubles each, row-major), then its record offsets (one long long each); lane `pos` writes record rec_off[slot] + g as
+// three 16-byte stores.
+__global__ void __launch_bounds__(256) k_encode_registered(SlotArrays A, const double* par, int count, float4* out) {
+    const int i = blockIdx.y, slot = A.first + i;
+    const FusedView V = slot_view(A, slot);
+    const int b0 = blockIdx.x * blockDim.x, cv = V.cb_n[0], cl = V.cb_n[1];
+    // nothing of this block is a valid position: it lies in the unused tail of the Velodyne region or past the Livox part
+    if (b0 >= V.NV + cl || (b0 >= cv && b0 + (int)blockDim.x <= V.NV)) return;
+    int g, line;
+    float4 p;
+    float rel;
+    if (!fused_at(V, b0 + threadIdx.x, g, p, rel, line)) return;
+    if (g >= A.fu_info[8 * (size_t)slot]) return;  // (the records of the slot end at its count, whatever the index array holds)
+    const double* T = par + 16 * (size_t)i;
+    const long long rec_off = reinterpret_cast<const long long*>(par + 16 * (size_t)count)[i];
+    const double x = p.x, y = p.y, z = p.z;
+    float4 a, b, c;
+    a.x = (float)(((T[0] * x + T[1] * y) + T[2] * z) + T[3]);
+    a.y = (float)(((T[4] * x + T[5] * y) + T[6] * z) + T[7]);
+    a.z = (float)(((T[8] * x + T[9] * y) + T[10] * z) + T[11]);
+    a.w = 1.0f;
+    b.x = 0.f;
+    b.y = 0.f;
+    b.z = (float)V.label[b0 + threadIdx.x];  // normal_z: the label (:212)
+    b.w = 0.f;
+    c.x = p.w;                               // intensity (:211)
+    c.y = 0.f;
+    c.z = 0.f;
+    c.w = 0.f;
+    float4* o = out + 3 * (size_t)(rec_off + g);
+    o[0] = a;
+    o[1] = b;
+    o[2] = c;
+}
 // ---- mml_slot_digest: order-independent 64-bit digests of what the download entry points would hand out -----------------------
 __host__ __device__ __forceinline__ unsigned long long dg_mix(unsigned long long z) {  // splitmix64 finaliser
     z ^= z >> 30;
@@ -531,42 +603,17 @@ __device__ __forceinline__ void dg_commit(unsigned long long v, unsigned long lo
     }
     if ((threadIdx.x & 63) == 0 && v) atomicAdd(dst, v);
 }
-struct DigestArgs {
-    const float4* pts;
-    const int* gidx;
-    const int* rel;
-    const uint8_t* line;
-    const uint8_t* label;
-    const int* cb_n;
-    const int* seg_flat;
-    const int* seg_flat_n;
-    const int* slot_flags;
-    const int* fu_info;
+struct DigestArgs : SlotArrays {
     const int* ft_n;
     const float4* ft[2];
     const MmlLineFactor* lf;
     const MmlPlaneFactor* pf;
     const double* x;
-    int B, NV, NT, L, MF, n_rings, first;
+    int B, MF;
 };
 // pieces 1-4: the fused cloud, one storage position per thread (blockIdx.y = slot of the call)
 __global__ void __launch_bounds__(256) k_digest_cloud(DigestArgs A, unsigned long long* out) {
-    const int slot = A.first + blockIdx.y;
-    FusedView V;
-    const size_t off = (size_t)slot * A.NT;
-    V.pts = A.pts + off;
-    V.gidx = A.gidx + off;
-    V.rel = A.rel + off;
-    V.line = A.line + off;
-    V.label = A.label + off;
-    V.cb_n = A.cb_n + 2 * (size_t)slot;
-    V.seg_flat = A.seg_flat + (size_t)slot * 2 * MML_SEG_FLAT;
-    V.seg_flat_n = A.seg_flat_n + (size_t)slot * 4;
-    V.NV = A.NV;
-    V.NT = A.NT;
-    V.L = A.L;
-    V.n_rings = A.n_rings;
-    V.flags = A.slot_flags[2 * (size_t)slot];
+    const FusedView V = slot_view(A, A.first + blockIdx.y);
     const int pos = blockIdx.x * blockDim.x + threadIdx.x;
     int g = 0, ln = 0;
     float4 p;
@@ -633,7 +680,10 @@ __global__ void __launch_bounds__(256) k_digest_stacks(DigestArgs A, unsigned lo
 int ensure_wire_stage(mml_ctx* ctx, size_t bytes) {
     if (bytes <= ctx->wire_stage_bytes) return MML_OK;
     MML_HIP(hipStreamSynchronize(MML_STREAM(ctx)));
-    if (ctx->wire_stage) MML_HIP(hipFree(ctx->wire_stage));
+    void* old = ctx->wire_stage;
+    ctx->wire_stage = nullptr;  // (a failure below leaves no buffer rather than a freed one)
+    ctx->wire_stage_bytes = 0;
+    if (old) MML_HIP(hipFree(old));
     MML_HIP(hipMalloc(&ctx->wire_stage, bytes));
     ctx->wire_stage_bytes = bytes;
     return MML_OK;
@@ -707,6 +757,25 @@ int upload_wire_impl(mml_ctx* ctx, int slot, const uint8_t* data, int n_points, 
 }  // namespace
 
 namespace {
+SlotArrays slot_arrays(const mml_ctx* ctx, int first) {
+    SlotArrays A;
+    A.pts = ctx->ln_pts;
+    A.gidx = ctx->ln_gidx;
+    A.rel = ctx->ln_rel;
+    A.line = ctx->ln_line;
+    A.label = ctx->ln_label;
+    A.cb_n = ctx->cb_n;
+    A.seg_flat = ctx->seg_flat;
+    A.seg_flat_n = ctx->seg_flat_n;
+    A.slot_flags = ctx->slot_flags;
+    A.fu_info = ctx->fu_info;
+    A.NV = ctx->NV;
+    A.NT = ctx->NT;
+    A.L = ctx->L;
+    A.n_rings = ctx->cfg.n_rings;
+    A.first = first;
+    return A;
+}
 int fused_view(mml_ctx* ctx, int slot, FusedView& V) {
     int fl = 0;
     MML_HIP(hipMemcpyAsync(&fl, ctx->slot_flags + 2 * (size_t)slot, sizeof(int), hipMemcpyDeviceToHost, MML_STREAM(ctx)));
@@ -750,6 +819,50 @@ int mml_scan_download_pointxyzinormal(mml_ctx* ctx, int slot, uint8_t* out, int 
     MML_HIP(hipMemcpyAsync(out, ctx->wire_stage, bytes, hipMemcpyDeviceToHost, MML_STREAM(ctx)));
     MML_HIP(hipStreamSynchronize(MML_STREAM(ctx)));
     return MML_OK;
+}
+
+int mml_cloud_download_registered_batch(mml_ctx* ctx, int first_slot, int count, const double* T_wl, uint8_t* out,
+                                        long capacity_points, int* n_points) {
+    CHECK_SLOTS(first_slot, count);
+    MML_REQUIRE(T_wl != nullptr && n_points != nullptr, MML_ERR_INVALID, "null T_wl / n_points");
+    MML_REQUIRE(count <= 65535, MML_ERR_INVALID, "at most 65535 slots per call (the grid's second dimension)");
+    // synchronisation 1 of 2: the counts of all slots in one copy (the flag words stay on the device, slot_view reads them)
+    double* st = stage_alloc(ctx, 21 * (size_t)count);  // pinned: 8 ints per slot back, then 16 + 1 doubles per slot down
+    int* h_info = reinterpret_cast<int*>(st);
+    MML_HIP(hipMemcpyAsync(h_info, ctx->fu_info + 8 * (size_t)first_slot, sizeof(int) * 8 * (size_t)count, hipMemcpyDeviceToHost,
+                           MML_STREAM(ctx)));
+    MML_HIP(hipStreamSynchronize(MML_STREAM(ctx)));
+    long long total = 0;
+    for (int i = 0; i < count; ++i) total += (n_points[i] = h_info[8 * i]);
+    if (!out) return MML_OK;
+    MML_REQUIRE(capacity_points >= total, MML_ERR_CAPACITY, "download capacity too small");
+    if (total == 0) return MML_OK;
+    const size_t bytes = (size_t)total * 48;
+    int rc = ensure_wire_stage(ctx, bytes);
+    if (rc != MML_OK) return rc;
+    // poses, then record offsets (the exclusive prefix sum of the counts), down in one copy into the call's slice of d_pose_in
+    double* h_par = st + 4 * (size_t)count;
+    memcpy(h_par, T_wl, sizeof(double) * 16 * (size_t)count);
+    long long* h_off = reinterpret_cast<long long*>(h_par + 16 * (size_t)count);
+    long long run = 0;
+    for (int i = 0; i < count; ++i) {
+        h_off[i] = run;
+        run += h_info[8 * i];
+    }
+    double* d_par = ctx->d_pose_in + 64 * (size_t)first_slot;
+    MML_HIP(hipMemcpyAsync(d_par, h_par, sizeof(double) * 17 * (size_t)count, hipMemcpyHostToDevice, MML_STREAM(ctx)));
+    const SlotArrays A = slot_arrays(ctx, first_slot);
+    hipLaunchKernelGGL(k_encode_registered, dim3((ctx->NT + 255) / 256, count), dim3(256), 0, MML_STREAM(ctx), A, d_par, count,
+                       reinterpret_cast<float4*>(ctx->wire_stage));
+    MML_HIP(hipGetLastError());
+    // synchronisation 2 of 2: the records
+    MML_HIP(hipMemcpyAsync(out, ctx->wire_stage, bytes, hipMemcpyDeviceToHost, MML_STREAM(ctx)));
+    MML_HIP(hipStreamSynchronize(MML_STREAM(ctx)));
+    return MML_OK;
+}
+
+int mml_cloud_download_registered(mml_ctx* ctx, int slot, const double* T_wl, uint8_t* out, int capacity_points, int* n_points) {
+    return mml_cloud_download_registered_batch(ctx, slot, 1, T_wl, out, capacity_points, n_points);
 }
 
 int mml_cloud_upload(mml_ctx* ctx, int slot, const uint8_t* pointxyzinormal, int n_points, int n_velo) {
@@ -842,16 +955,7 @@ int mml_slot_digest(mml_ctx* ctx, int first_slot, int count, uint64_t* out) {
     MML_HIP(hipMalloc(reinterpret_cast<void**>(&d), bytes));
     hipError_t e = hipMemsetAsync(d, 0, bytes, MML_STREAM(ctx));
     DigestArgs A;
-    A.pts = ctx->ln_pts;
-    A.gidx = ctx->ln_gidx;
-    A.rel = ctx->ln_rel;
-    A.line = ctx->ln_line;
-    A.label = ctx->ln_label;
-    A.cb_n = ctx->cb_n;
-    A.seg_flat = ctx->seg_flat;
-    A.seg_flat_n = ctx->seg_flat_n;
-    A.slot_flags = ctx->slot_flags;
-    A.fu_info = ctx->fu_info;
+    static_cast<SlotArrays&>(A) = slot_arrays(ctx, first_slot);
     A.ft_n = ctx->ft_n;
     A.ft[0] = ctx->ft_xyz[0];
     A.ft[1] = ctx->ft_xyz[1];
@@ -859,11 +963,7 @@ int mml_slot_digest(mml_ctx* ctx, int first_slot, int count, uint64_t* out) {
     A.pf = ctx->pf;
     A.x = ctx->d_x;
     A.B = ctx->B;
-    A.NV = ctx->NV;
-    A.NT = ctx->NT;
-    A.L = ctx->L;
     A.MF = ctx->MF;
-    A.n_rings = ctx->cfg.n_rings;
     // (gridDim.y is limited to 65535: calls of more slots go in pieces)
     for (int done = 0; done < count && e == hipSuccess; done += 32768) {
         const int c = std::min(32768, count - done);

@@ -238,7 +238,7 @@ struct mml_ctx {
     int gs_cen[3] = {10, 5, 10};               // laserCloudCen{Width,Height,Depth} of the live store
     int* gs_work = nullptr;                    // histograms / flags / bbox keys / scan scratch
     unsigned long long* gs_keys = nullptr;     // 64-bit sort keys, 2 x MM
-    void* wire_stage = nullptr;              // raw message bytes on their way in / out (one slot at a time)
+    void* wire_stage = nullptr;              // raw message bytes on their way in / out (one call at a time; grows to the largest)
     size_t wire_stage_bytes = 0;
     int local_map_n[2] = {0, 0};
     float4* map_tmp = nullptr;

@@ -640,6 +640,30 @@ class Estimator {
 
     bool failureDetected() const { return _fail_detected; }  // Estimator.h:278
 
+    // The pose node's loop after EstimateLidarPose (unionPoseEstimation.cpp:896-903: pointAssociateToMap over the front
+    // frame's cloud) and pcl::toROSMsg (:907): `data` becomes laserCloudMsg.data, 48-byte PointXYZINormal records of the
+    // cloud in `slot` at T = transformTobeMapped (row-major 4x4, :876-880), transformed and packed on the device.  Returns
+    // the number of points.
+    int RegisteredCloud(int slot, const double T[16], std::vector<uint8_t>& data) {
+        std::vector<int> n;
+        return (int)RegisteredCloud(slot, 1, T, data, n);
+    }
+    // The same for `count` resident slots in one device call (a replay): slot first_slot + i at T[16 i ...]; the records of
+    // slot i start at record n_points[0] + ... + n_points[i-1] of `data`.  Returns the total number of points.
+    long RegisteredCloud(int first_slot, int count, const double* T, std::vector<uint8_t>& data, std::vector<int>& n_points) {
+        n_points.assign(count > 0 ? count : 1, 0);
+        check(ctx_.get(), mml_cloud_download_registered_batch(ctx_.get(), first_slot, count, T, nullptr, 0, n_points.data()),
+              "mml_cloud_download_registered_batch");
+        long total = 0;
+        for (int i = 0; i < count; ++i) total += n_points[i];
+        data.assign(48 * (size_t)total, 0);
+        if (total)
+            check(ctx_.get(), mml_cloud_download_registered_batch(ctx_.get(), first_slot, count, T, data.data(), total, n_points.data()),
+                  "mml_cloud_download_registered_batch");
+        n_points.resize(count > 0 ? count : 0);
+        return total;
+    }
+
    private:
     mml_assoc_stats associate(int slot, const Matrix4d& m4d) {
         mml_assoc_stats st;

@@ -30,6 +30,7 @@ class LidarOdometry:
         self.n_surf_local = 0
         self.fail_detected = False
         self.key_scans = 0
+        self.last_T = None                                            # transformTobeMapped the last estimate_lidar_pose ended with
         ctx.map_local_reset()
 
     def transform_to_be_mapped(self, P, Q):
@@ -73,7 +74,16 @@ class LidarOdometry:
                 self.key_scans += 1
                 grew = True
         self.fail_detected = is_degenerate                              # :1139
+        self.last_T = T
         return P, Q, grew
+
+    def registered_cloud(self, slot):
+        """The scan of `slot` in the world frame at the pose the last estimate_lidar_pose ended with -- the cloud the pose node
+        publishes after EstimateLidarPose (unionPoseEstimation.cpp:896-911) -- as (n, 12) float32 PointXYZINormal records,
+        transformed and packed on the device."""
+        if self.last_T is None:
+            raise ValueError("registered_cloud needs an estimate_lidar_pose first")
+        return self.ctx.cloud_download_registered(slot, 1, self.last_T)[0]
 
 
 def _rotvec_from_quat(q):
