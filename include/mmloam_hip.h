@@ -390,7 +390,12 @@ int mml_estimate(mml_ctx* ctx, int first_slot, int count, const double* exTlb, d
  * lane ordered behind whatever the context's stream holds when the call is made (no synchronisation is needed between
  * mml_scan_upload and mml_step); inside a lane the stages run in order on the lane's stream; the call returns with every
  * stream of the context drained.  The association statistics of mml_associate (counts, normal Gram matrix) are not part of
- * the step; an entry point that needs them afterwards (mml_linearize*, mml_associate with `stats`) computes them on demand. */
+ * the step; an entry point that needs them afterwards (mml_linearize*, mml_associate with `stats`) computes them on demand.
+ * Of the cloud the step itself undistorts the labelled points only -- all its down-sampler reads; the undistortion of the full
+ * cloud is completed by the first entry point that reads the slot's cloud afterwards (mml_scan_download*,
+ * mml_cloud_download_registered*, mml_slot_digest, mml_undistort, mml_downsample, mml_gicp_refresh*), which then returns what it
+ * returned when the step did all of it; a caller that takes poses and feature stacks only never pays for that pass.
+ * ($MML_LAZY_UNDISTORT=0, read when the context is created: the step undistorts the whole cloud itself.) */
 int mml_step(mml_ctx* ctx, int first_slot, int count, const double* dR, const double* dt,
              const double* exTlb, double thres_dist, int gn_iters, double* x_inout);
 

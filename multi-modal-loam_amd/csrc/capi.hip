@@ -56,6 +56,7 @@ hipError_t read_settings(mml_ctx* ctx) {
     ctx->onepass_wanted = !off("MML_ASSIGN_ONEPASS");
     ctx->solve_wide = !off("MML_SOLVE_WIDE");
     ctx->use_graph = getenv("MML_NO_GRAPH") == nullptr;
+    ctx->lazy_undistort = !off("MML_LAZY_UNDISTORT");
     return hipSuccess;
 }
 
@@ -117,7 +118,7 @@ void mml_destroy(mml_ctx* ctx) {
     mml_imu_preint_release(ctx);
     mml_lio_init_release(ctx);
     mml_gicp_release(ctx);
-    void* ptrs[] = {ctx->wstate, ctx->wrec, ctx->waux, ctx->hard_knn, ctx->d_und, ctx->crop_cnt, ctx->velo_in,  ctx->livox_in, ctx->d_n_in,   ctx->raw_line, ctx->raw_ori,  ctx->ln_pts,
+    void* ptrs[] = {ctx->wstate, ctx->wrec, ctx->waux, ctx->hard_knn, ctx->d_und, ctx->d_und_par, ctx->crop_cnt, ctx->velo_in,  ctx->livox_in, ctx->d_n_in,   ctx->raw_line, ctx->raw_ori,  ctx->ln_pts,
                     ctx->ln_gidx, ctx->ln_rel, ctx->line_start, ctx->line_len, ctx->seg_cum, ctx->seg_pos, ctx->seg_n, ctx->seg_flat, ctx->seg_flat_n, ctx->op_agg, ctx->seg_rs, ctx->seg_rw, ctx->ln_curv, ctx->ln_refl,  ctx->ln_attr,
                     ctx->sel_scratch, ctx->blk_cnt, ctx->assign_aux, ctx->brk_queue, ctx->brk_cnt, ctx->redo_queue, ctx->st_exit, ctx->vx_big, ctx->sel_done, ctx->sel_list, ctx->sel_list_cnt,
                     ctx->cb_n,     ctx->queue_off, ctx->slot_flags, ctx->ln_line,  ctx->ln_label,
@@ -182,6 +183,7 @@ int mml_create(const mml_config* cfg, int device, mml_ctx** out) {
     ctx->h_n_in.assign((size_t)ctx->B * 2, 0);
     ctx->raw_extracted.assign((size_t)ctx->B, 0);
     ctx->stats_stale.assign((size_t)ctx->B, 1);
+    ctx->und_pending.assign((size_t)ctx->B, 0);
     auto fail = [&](hipError_t e, const char* what) {
         ctx->err = std::string(what) + ": " + hipGetErrorString(e);
         // keep ctx alive so the caller can read the message? No: report through the return code only.
@@ -273,6 +275,7 @@ int mml_create(const mml_config* cfg, int device, mml_ctx** out) {
     ALLOC(ctx->d_trace, B * 6 * 64);
     ALLOC(ctx->d_rec, B * 32);
     ALLOC(ctx->d_und, B * 8);
+    ALLOC(ctx->d_und_par, B * 12);
     ALLOC(ctx->d_extr, 16);
     ALLOC(ctx->d_misc, 64);
 #undef ALLOC
@@ -801,8 +804,10 @@ int fused_view(mml_ctx* ctx, int slot, FusedView& V) {
 int mml_scan_download_pointxyzinormal(mml_ctx* ctx, int slot, uint8_t* out, int capacity_points, int* n_points) {
     CHECK_SLOTS(slot, 1);
     MML_REQUIRE(n_points != nullptr, MML_ERR_INVALID, "null n_points");
+    int rc = mml_cloud_settle(ctx, slot, 1);
+    if (rc != MML_OK) return rc;
     mml_scan_info info;
-    int rc = mml_scan_info_get(ctx, slot, &info);
+    rc = mml_scan_info_get(ctx, slot, &info);
     if (rc != MML_OK) return rc;
     *n_points = info.n_points;
     if (!out || info.n_points == 0) return MML_OK;
@@ -826,6 +831,8 @@ int mml_cloud_download_registered_batch(mml_ctx* ctx, int first_slot, int count,
     CHECK_SLOTS(first_slot, count);
     MML_REQUIRE(T_wl != nullptr && n_points != nullptr, MML_ERR_INVALID, "null T_wl / n_points");
     MML_REQUIRE(count <= 65535, MML_ERR_INVALID, "at most 65535 slots per call (the grid's second dimension)");
+    int rc = mml_cloud_settle(ctx, first_slot, count);
+    if (rc != MML_OK) return rc;
     // synchronisation 1 of 2: the counts of all slots in one copy (the flag words stay on the device, slot_view reads them)
     double* st = stage_alloc(ctx, 21 * (size_t)count);  // pinned: 8 ints per slot back, then 16 + 1 doubles per slot down
     int* h_info = reinterpret_cast<int*>(st);
@@ -838,7 +845,7 @@ int mml_cloud_download_registered_batch(mml_ctx* ctx, int first_slot, int count,
     MML_REQUIRE(capacity_points >= total, MML_ERR_CAPACITY, "download capacity too small");
     if (total == 0) return MML_OK;
     const size_t bytes = (size_t)total * 48;
-    int rc = ensure_wire_stage(ctx, bytes);
+    rc = ensure_wire_stage(ctx, bytes);
     if (rc != MML_OK) return rc;
     // poses, then record offsets (the exclusive prefix sum of the counts), down in one copy into the call's slice of d_pose_in
     double* h_par = st + 4 * (size_t)count;
@@ -875,6 +882,7 @@ int mml_cloud_upload(mml_ctx* ctx, int slot, const uint8_t* pointxyzinormal, int
     int rc = ensure_wire_stage(ctx, bytes ? bytes : 48);
     if (rc != MML_OK) return rc;
     if (bytes) MML_HIP(hipMemcpyAsync(ctx->wire_stage, pointxyzinormal, bytes, hipMemcpyHostToDevice, MML_STREAM(ctx)));
+    ctx->und_pending[slot] = 0;  // (the cloud is replaced: nothing of the old one is left to finish)
     rc = mml_launch_cloud_decode(ctx, slot, reinterpret_cast<const float*>(ctx->wire_stage), n_points, n_velo);
     if (rc != MML_OK) return rc;
     // the staging buffer is reused by the next wire-format call and the host buffer belongs to the caller
@@ -917,8 +925,10 @@ int mml_scan_info_get(mml_ctx* ctx, int slot, mml_scan_info* info) {
 int mml_scan_download(mml_ctx* ctx, int slot, float* xyzi, float* reltime, uint8_t* line, uint8_t* label,
                       int capacity) {
     CHECK_SLOTS(slot, 1);
+    int rc = mml_cloud_settle(ctx, slot, 1);
+    if (rc != MML_OK) return rc;
     mml_scan_info info;
-    int rc = mml_scan_info_get(ctx, slot, &info);
+    rc = mml_scan_info_get(ctx, slot, &info);
     if (rc != MML_OK) return rc;
     MML_REQUIRE(capacity >= info.n_points, MML_ERR_CAPACITY, "download capacity too small");
     const size_t n = info.n_points;
@@ -949,6 +959,8 @@ int mml_slot_digest(mml_ctx* ctx, int first_slot, int count, uint64_t* out) {
     CHECK_SLOTS(first_slot, count);
     MML_REQUIRE(out != nullptr, MML_ERR_INVALID, "null out");
     int rc = mml_sync_all(ctx);
+    if (rc != MML_OK) return rc;
+    rc = mml_cloud_settle(ctx, first_slot, count);
     if (rc != MML_OK) return rc;
     unsigned long long* d = nullptr;
     const size_t bytes = sizeof(unsigned long long) * MML_DIGEST_WORDS * (size_t)count;
@@ -991,6 +1003,10 @@ int mml_detect_line(mml_ctx* ctx, const float* pts, int n, int* sharp, int* n_sh
     *n_sharp = 0;
     *n_flat = 0;
     if (n == 0) return MML_OK;
+    {  // (slot 0 is this call's scratch: what it leaves of the slot's cloud is what it left before there were partly undistorted slots)
+        int rc0 = mml_cloud_settle(ctx, 0, 1);
+        if (rc0 != MML_OK) return rc0;
+    }
     for (int i = 0; i < n; ++i)
         MML_REQUIRE(std::isfinite(pts[4 * i]) && std::isfinite(pts[4 * i + 1]) && std::isfinite(pts[4 * i + 2]),
                     MML_ERR_INVALID, "detectFeaturePoints: non-finite input (reference indexes pre-compaction)");
@@ -1015,9 +1031,9 @@ int mml_detect_line(mml_ctx* ctx, const float* pts, int n, int* sharp, int* n_sh
     return MML_OK;
 }
 
-int mml_undistort(mml_ctx* ctx, int first_slot, int count, const double* dR, const double* dt) {
-    CHECK_SLOTS(first_slot, count);
-    MML_REQUIRE(dR && dt, MML_ERR_INVALID, "null dR/dt");
+// the sweep motions of `count` slots into the call's slice of d_pose_in, then the whole cloud (the entry point) or the listed points
+// (mml_step) undistorted with them
+static int undistort_enqueue(mml_ctx* ctx, int first_slot, int count, const double* dR, const double* dt, bool listed_only) {
     double* st = stage_alloc(ctx, 12 * (size_t)count);
     for (int i = 0; i < count; ++i) {
         memcpy(st + 12 * i, dR + 9 * i, sizeof(double) * 9);
@@ -1025,12 +1041,22 @@ int mml_undistort(mml_ctx* ctx, int first_slot, int count, const double* dR, con
     }
     double* d_par = ctx->d_pose_in + 64 * (size_t)first_slot;  // 64 doubles per slot: [0, 12*count) of this call's slice
     MML_HIP(hipMemcpyAsync(d_par, st, sizeof(double) * 12 * count, hipMemcpyHostToDevice, MML_STREAM(ctx)));
-    return mml_launch_undistort(ctx, first_slot, count, d_par);
+    return listed_only ? mml_launch_undistort_listed(ctx, first_slot, count, d_par) : mml_launch_undistort(ctx, first_slot, count, d_par);
+}
+
+int mml_undistort(mml_ctx* ctx, int first_slot, int count, const double* dR, const double* dt) {
+    CHECK_SLOTS(first_slot, count);
+    MML_REQUIRE(dR && dt, MML_ERR_INVALID, "null dR/dt");
+    int rc = mml_cloud_settle(ctx, first_slot, count);  // (a second undistortion starts from a complete first one)
+    if (rc != MML_OK) return rc;
+    return undistort_enqueue(ctx, first_slot, count, dR, dt, false);
 }
 
 int mml_downsample(mml_ctx* ctx, int first_slot, int count) {
     CHECK_SLOTS(first_slot, count);
-    int rc = mml_launch_downsample(ctx, first_slot, count);
+    int rc = mml_cloud_settle(ctx, first_slot, count);
+    if (rc != MML_OK) return rc;
+    rc = mml_launch_downsample(ctx, first_slot, count);
     if (rc != MML_OK) return rc;
     // pcl::VoxelGrid takes a cloud of any size: slots whose labelled cloud is beyond the LDS sort are redone
     return mml_downsample_redo_overflow(ctx, first_slot, count, nullptr);
@@ -1705,9 +1731,9 @@ int mml_step(mml_ctx* ctx, int first_slot, int count, const double* dR, const do
         const int off = f - first_slot;
         switch (stage) {
             case 0: return mml_launch_extract(ctx, f, c, false);
-            case 1:
-                if (packed) return mml_launch_undistort(ctx, f, c, dp);
-                return mml_undistort(ctx, f, c, dR + 9 * (size_t)off, dt + 3 * (size_t)off);
+            case 1:  // (the points the down-sampler reads; the rest of the cloud when somebody asks for it: mml_cloud_settle)
+                if (packed) return ctx->lazy_undistort ? mml_launch_undistort_listed(ctx, f, c, dp) : mml_launch_undistort(ctx, f, c, dp);
+                return undistort_enqueue(ctx, f, c, dR + 9 * (size_t)off, dt + 3 * (size_t)off, ctx->lazy_undistort);
             case 2: return mml_launch_downsample(ctx, f, c);
             case 3:
                 if (packed) return mml_launch_associate(ctx, f, c, dp + 12 * (size_t)count, thres_dist, false);

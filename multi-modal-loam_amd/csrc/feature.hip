@@ -4020,6 +4020,7 @@ extern "C" int mml_libm_f32(mml_ctx* ctx, const float* y, const float* x, long n
 
 int mml_launch_extract(mml_ctx* ctx, int first, int count, bool have_extrinsic) {
     for (int i = 0; i < count; ++i) ctx->raw_extracted[first + i] = 1;  // (mml_gicp_refresh re-derives line ids from the raw buffers)
+    for (int i = 0; i < count; ++i) ctx->und_pending[first + i] = 0;    // (the cloud is rebuilt from the raw points: nothing is left to finish)
     FeatParams P = make_params(ctx, first);
     P.extr = have_extrinsic ? ctx->d_extr : nullptr;
     hipStream_t s = MML_STREAM(ctx);

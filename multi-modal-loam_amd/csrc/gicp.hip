@@ -994,6 +994,10 @@ int gicp_refresh_n(mml_ctx* ctx, const char* who, int first_slot, int count, flo
     if (!extrinsics) return mml_refuse(ctx, MML_ERR_INVALID, "%s: a null argument", who);
     int rc = gicp_enter(ctx);
     if (rc != MML_OK) return rc;
+    // (the gather and the apply below read and rewrite ln_pts / ln_label.  A partly undistorted slot carries the "undistorted" flag
+    //  and is refused further down; it is settled all the same, so that no path into those kernels depends on that refusal)
+    rc = mml_cloud_settle(ctx, first_slot, count);
+    if (rc != MML_OK) return rc;
     hipStream_t s = MML_STREAM(ctx);
     const size_t n = (size_t)count, f = (size_t)first_slot;
     const IoLayout io(n, 0);

@@ -97,6 +97,7 @@ struct mml_ctx {
     bool onepass_wanted = true;  // $MML_ASSIGN_ONEPASS=0: false (mml_feature_init still decides `onepass` from the layout)
     bool solve_wide = true;      // $MML_SOLVE_WIDE=0: false, the live path's one-frame solve through k_solve<true>
     bool use_graph = true;       // $MML_NO_GRAPH: false, the window solve's chain launched kernel by kernel
+    bool lazy_undistort = true;  // $MML_LAZY_UNDISTORT=0: false, mml_step undistorts the whole cloud itself (see und_pending)
     // `lanes`: independent HIP streams.  Entry points enqueue on lane `cur` (0 unless mml_step is pipelining
     // sub-batches); per-call scratch is sliced by slot index so lanes never share a byte.
     static constexpr int MAX_LANES = 8;
@@ -180,8 +181,16 @@ struct mml_ctx {
     uint8_t* ln_line = nullptr;   // B * NT  ring / Livox line (normal_y) of an UPLOADED cloud (an extracted one has its line table)
     int* slot_flags = nullptr;    // B * 2   [0] bit 0: filled by mml_cloud_upload, bit 1: undistorted (in-sweep time reads 1);
                                   //         [1] bit 1 as it was when the current mml_undistort started
+    // INVARIANT (partly undistorted slots).  mml_step undistorts only the points on the slot's two label lists -- all its
+    // down-sampler reads -- and sets und_pending[slot] = 1.  While that byte is set: slot_flags, d_und and d_und_par describe the
+    // sweep motion as after a whole mml_undistort, the LISTED points of ln_pts are final, every other point of ln_pts still holds its
+    // raw coordinates, and the label lists (vx_keys, fu_info[6..7]) are those of the cloud.  mml_cloud_settle(first, count) finishes
+    // the other points and clears the byte; every entry point that reads or rewrites ln_pts / ln_rel / ln_label outside the step
+    // calls it first.  What replaces the cloud (mml_launch_extract, mml_cloud_upload) just clears the byte.
+    std::vector<char> und_pending;  // B
     uint8_t* ln_label = nullptr;  // B * NT  0 none / 1 corner / 2 surf (normal_z) for kept points; 0x81 / 0x82 for labelled Livox
                                   //         points beyond far_th (counted in livox_*_num and aligned by the GICP refresh, not fused)
+                                  //         (bit 6, MML_LABEL_SETTLED, lives only inside mml_cloud_settle: "this point is done")
     int* fu_info = nullptr;  // B * 8: n_points, n_velo, vc, vs, lc, ls, fused corner, fused surf
 
     // down-sampled feature stacks: kind 0 corner, 1 surf
@@ -257,6 +266,8 @@ struct mml_ctx {
     double* d_summ = nullptr;     // B * 8
     double* d_trace = nullptr;    // B * 6 * MAX_ITERS
     double* d_und = nullptr;      // B * 8 per-scan undistortion constants
+    double* d_und_par = nullptr;  // B * 12 the sweep motion (dR, dt) of the slot's last undistortion: k_undistort_prep's copy of the call's
+                                  //        parameters, which live in d_pose_in only until the next stage overwrites them
     double* d_rec = nullptr;      // B * 32
     float* d_extr = nullptr;      // 16 floats
     int* d_misc = nullptr;        // misc ints
@@ -349,6 +360,11 @@ struct MmlStageScope {
 int mml_launch_extract(mml_ctx* ctx, int first, int count, bool have_extrinsic);
 int mml_launch_cloud_decode(mml_ctx* ctx, int slot, const float* d_raw, int n, int n_velo);
 int mml_launch_undistort(mml_ctx* ctx, int first, int count, const double* d_params);
+// mml_step's form: the points on the slots' label lists only; the slots become partly undistorted (mml_ctx::und_pending)
+int mml_launch_undistort_listed(mml_ctx* ctx, int first, int count, const double* d_params);
+// finishes the partly undistorted slots of [first, first + count) on the current stream (a host loop over B bytes when none is)
+int mml_cloud_settle(mml_ctx* ctx, int first, int count);
+#define MML_LABEL_SETTLED 0x40  // no label value uses it: 0, 1, 2, 0x81, 0x82
 int mml_launch_time_offset(mml_ctx* ctx, MmlGrid& g, float4* d_velo4, const float* d_velo_xyz, int n_velo, const float* d_tf,
                            const float* d_livox_xyz, int n_livox, int res, int sliced, int nwin, float* d_nn, double* d_err);
 int mml_launch_downsample(mml_ctx* ctx, int first, int count);

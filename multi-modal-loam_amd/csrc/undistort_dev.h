@@ -1,6 +1,6 @@
 // undistort_dev.h -- the per-point arithmetic of RemoveLidarDistortion (mm-loam/src/unionPoseEstimation.cpp:402-421),
-// shared by k_undistort (undistort_voxel.hip) and by the bucketing pass of the fused step (feature.hip), which writes
-// the fused cloud already undistorted when the sweep motion is known up front.  Compiled with -ffp-contract=off.
+// shared by the kernels of undistort_voxel.hip: k_undistort (the whole cloud: mml_undistort, mml_cloud_settle) and
+// k_undistort_listed (the labelled points: mml_step).  Compiled with -ffp-contract=off.
 #ifndef MML_UNDISTORT_DEV_H
 #define MML_UNDISTORT_DEV_H
 #include <hip/hip_runtime.h>

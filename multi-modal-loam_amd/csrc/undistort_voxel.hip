@@ -14,10 +14,12 @@ namespace {
 using namespace mml_und;
 
 // params: per slot 12 doubles (dR row-major 9, dt 3); derived: per slot 8 doubles written by k_undistort_prep
-// (qlc x,y,z,w | theta | sinTheta | 1/sinTheta | linear-branch flag)
-__global__ void k_undistort_prep(int count, const double* params, double* derived, int* flags /* 2 per slot of this call */) {
+// (qlc x,y,z,w | theta | sinTheta | 1/sinTheta | linear-branch flag); par_keep: the slots' own copy of params (ctx->d_und_par),
+// which mml_cloud_settle reads long after the call's slice of d_pose_in was reused
+__global__ void k_undistort_prep(int count, const double* params, double* derived, double* par_keep, int* flags /* 2 per slot of this call */) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= count) return;
+    for (int k = 0; k < 12; ++k) par_keep[12 * s + k] = params[12 * s + k];
     flags[2 * s + 1] = flags[2 * s];  // what k_undistort reads: was the slot undistorted before this call?
     flags[2 * s] |= 2;                // from now on its in-sweep time reads 1 (:419)
     const double* dR = params + 12 * s;
@@ -50,13 +52,24 @@ __global__ void k_undistort_prep(int count, const double* params, double* derive
 // (in place on the line-bucketed storage: Velodyne points in [0, cb_n[0]), Livox points in [NV, NV + cb_n[1]))
 // "point.normal_x = 1" (:419) is a per-slot flag, not a store per point: k_undistort_prep raises bit 1 of slot_flags[2 b]
 // after saving its previous value in slot_flags[2 b + 1]; a slot that is undistorted again reads its time as 1.
+// SETTLE (mml_cloud_settle): the points k_settle_mark marked were undistorted by k_undistort_listed already; they lose the mark
+// and keep their coordinates.
+template <bool SETTLE>
 __global__ __launch_bounds__(256) void k_undistort(int first, int NT, int NV, const int* cb_n, float4* ln_pts,
                                                   const int* ln_rel, const int* slot_flags, const double* params,
-                                                  const double* derived) {
+                                                  const double* derived, uint8_t* ln_label) {
     const int b = blockIdx.y + first;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= NT) return;
     if (i < NV ? i >= cb_n[2 * b] : i - NV >= cb_n[2 * b + 1]) return;
+    if constexpr (SETTLE) {
+        uint8_t* lab = ln_label + (size_t)b * NT + i;
+        const unsigned l = *lab;
+        if (l & MML_LABEL_SETTLED) {
+            *lab = (uint8_t)(l & ~(unsigned)MML_LABEL_SETTLED);
+            return;
+        }
+    }
     const double* dR = params + 12 * blockIdx.y;
     typedef float v4f __attribute__((ext_vector_type(4)));
     v4f* pp = reinterpret_cast<v4f*>(ln_pts + (size_t)b * NT + i);
@@ -66,6 +79,54 @@ __global__ __launch_bounds__(256) void k_undistort(int first, int NT, int NV, co
     mml_und::undistort_point(dR, dR + 9, derived + 8 * blockIdx.y, s, p);
     v4f outv = {p.x, p.y, p.z, p.w};
     __builtin_nontemporal_store(outv, pp);
+}
+
+// The label lists of a slot as k_voxel reads them (voxel_slot): kind 0 corner, 1 surf; fu_info[8 b + 6 + kind] entries each, clamped to
+// the lists' stride; entry e of the two lists laid end to end -> storage position, or -1
+constexpr int UND_LISTED_G = 8;  // workgroups per slot: 2048 lanes for the ~3 700 listed points of a 52.8 k-point scan
+__device__ __forceinline__ int listed_position(const int* fu_info, const unsigned* lists, int list_stride, int NT, int b, int e) {
+    const int nc = min(max(fu_info[8 * b + 6], 0), list_stride), ns = min(max(fu_info[8 * b + 7], 0), list_stride);
+    if (e >= nc + ns) return -1;
+    const int kind = e >= nc ? 1 : 0;
+    const unsigned pos = lists[((size_t)b * 2 + kind) * list_stride + (e - (kind ? nc : 0))];
+    return pos < (unsigned)NT ? (int)pos : -1;
+}
+__device__ __forceinline__ int listed_total(const int* fu_info, int list_stride, int b) {
+    return min(max(fu_info[8 * b + 6], 0), list_stride) + min(max(fu_info[8 * b + 7], 0), list_stride);
+}
+
+// mml_step's undistortion: the points on the slot's two label lists, in place -- everything the down-sampler (k_voxel, the
+// global-sort filter) reads of the cloud.  Every labelled kept point is on exactly one list, so no two lanes touch one point.  The
+// other 93 % of the cloud are finished by mml_cloud_settle if anybody asks for them.  Plain loads and stores: k_voxel gathers the
+// same 64-byte lines next.  Grid (UND_LISTED_G, slots of the call).
+__global__ __launch_bounds__(256) void k_undistort_listed(int first, int NT, int list_stride, const int* fu_info, const unsigned* lists,
+                                                         float4* ln_pts, const int* ln_rel, const int* slot_flags, const double* params,
+                                                         const double* derived) {
+    const int b = blockIdx.y + first;
+    const int n = listed_total(fu_info, list_stride, b);
+    const bool time_is_one = (slot_flags[2 * b + 1] & 2) != 0;
+    const double* dR = params + 12 * blockIdx.y;
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < n; e += UND_LISTED_G * 256) {
+        const int pos = listed_position(fu_info, lists, list_stride, NT, b, e);
+        if (pos < 0) continue;
+        float4 p = ln_pts[(size_t)b * NT + pos];
+        const float s = time_is_one ? 1.0f : __int_as_float(ln_rel[(size_t)b * NT + pos]);
+        mml_und::undistort_point(dR, dR + 9, derived + 8 * blockIdx.y, s, p);
+        ln_pts[(size_t)b * NT + pos] = p;
+    }
+}
+
+// mml_cloud_settle, first launch: the listed points get MML_LABEL_SETTLED in their label byte; k_undistort<true> takes it off again
+__global__ __launch_bounds__(256) void k_settle_mark(int first, int NT, int list_stride, const int* fu_info, const unsigned* lists,
+                                                    uint8_t* ln_label) {
+    const int b = blockIdx.y + first;
+    const int n = listed_total(fu_info, list_stride, b);
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < n; e += UND_LISTED_G * 256) {
+        const int pos = listed_position(fu_info, lists, list_stride, NT, b, e);
+        if (pos < 0) continue;
+        uint8_t* lab = ln_label + (size_t)b * NT + pos;
+        *lab = (uint8_t)(*lab | MML_LABEL_SETTLED);
+    }
 }
 
 #ifdef MML_VX_TIMING
@@ -507,14 +568,51 @@ __global__ __launch_bounds__(VX_THREADS) __attribute__((amdgpu_waves_per_eu(MML_
 
 }  // namespace
 
+// (the callers have settled the slots: a second undistortion starts from a complete first one)
 int mml_launch_undistort(mml_ctx* ctx, int first, int count, const double* d_params) {
     MmlStageScope t(ctx, "undistort");
     dim3 grid((ctx->NT + 255) / 256, count);
     hipLaunchKernelGGL(k_undistort_prep, dim3((count + 63) / 64), dim3(64), 0, MML_STREAM(ctx), count, d_params, ctx->d_und + 8 * (size_t)first,
-                       ctx->slot_flags + 2 * (size_t)first);
-    hipLaunchKernelGGL(k_undistort, grid, dim3(256), 0, MML_STREAM(ctx), first, ctx->NT, ctx->NV, ctx->cb_n, ctx->ln_pts,
-                       ctx->ln_rel, ctx->slot_flags, d_params, ctx->d_und + 8 * (size_t)first);
+                       ctx->d_und_par + 12 * (size_t)first, ctx->slot_flags + 2 * (size_t)first);
+    hipLaunchKernelGGL(k_undistort<false>, grid, dim3(256), 0, MML_STREAM(ctx), first, ctx->NT, ctx->NV, ctx->cb_n, ctx->ln_pts,
+                       ctx->ln_rel, ctx->slot_flags, d_params, ctx->d_und + 8 * (size_t)first, (uint8_t*)nullptr);
     MML_HIP(hipGetLastError());
+    return MML_OK;
+}
+
+int mml_launch_undistort_listed(mml_ctx* ctx, int first, int count, const double* d_params) {
+    MmlStageScope t(ctx, "undistort");
+    for (int i = 0; i < count; ++i) ctx->und_pending[first + i] = 1;
+    hipLaunchKernelGGL(k_undistort_prep, dim3((count + 63) / 64), dim3(64), 0, MML_STREAM(ctx), count, d_params, ctx->d_und + 8 * (size_t)first,
+                       ctx->d_und_par + 12 * (size_t)first, ctx->slot_flags + 2 * (size_t)first);
+    hipLaunchKernelGGL(k_undistort_listed, dim3(UND_LISTED_G, count), dim3(256), 0, MML_STREAM(ctx), first, ctx->NT, ctx->VX_CAP, ctx->fu_info,
+                       reinterpret_cast<const unsigned*>(ctx->vx_keys), ctx->ln_pts, ctx->ln_rel, ctx->slot_flags, d_params,
+                       ctx->d_und + 8 * (size_t)first);
+    MML_HIP(hipGetLastError());
+    return MML_OK;
+}
+
+// The rest of the cloud of the partly undistorted slots of the range (mml_internal.h, und_pending): per run of such slots the listed
+// points are marked, then k_undistort goes over every point with the slots' kept parameters (d_und_par, d_und, slot_flags[2 b + 1]),
+// skipping and un-marking the marked ones.  Afterwards the slots are what a whole mml_undistort would have left, bit for bit.
+int mml_cloud_settle(mml_ctx* ctx, int first, int count) {
+    for (int i = 0; i < count;) {
+        if (!ctx->und_pending[first + i]) {
+            ++i;
+            continue;
+        }
+        int n = 1;
+        while (i + n < count && ctx->und_pending[first + i + n] && n < 32768) ++n;  // (gridDim.y is limited to 65535)
+        const int f = first + i;
+        MmlStageScope t(ctx, "undistort_settle");
+        hipLaunchKernelGGL(k_settle_mark, dim3(UND_LISTED_G, n), dim3(256), 0, MML_STREAM(ctx), f, ctx->NT, ctx->VX_CAP, ctx->fu_info,
+                           reinterpret_cast<const unsigned*>(ctx->vx_keys), ctx->ln_label);
+        hipLaunchKernelGGL(k_undistort<true>, dim3((ctx->NT + 255) / 256, n), dim3(256), 0, MML_STREAM(ctx), f, ctx->NT, ctx->NV, ctx->cb_n,
+                           ctx->ln_pts, ctx->ln_rel, ctx->slot_flags, ctx->d_und_par + 12 * (size_t)f, ctx->d_und + 8 * (size_t)f, ctx->ln_label);
+        MML_HIP(hipGetLastError());
+        for (int k = 0; k < n; ++k) ctx->und_pending[f + k] = 0;
+        i += n;
+    }
     return MML_OK;
 }
 
