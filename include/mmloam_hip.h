@@ -165,6 +165,40 @@ int mml_cloud_download_registered(mml_ctx* ctx, int slot, const double* T_wl /* 
 int mml_time_offset_search(mml_ctx* ctx, const float* velo_xyz, int n_velo, const float* tf, const float* livox_xyz,
                            int n_livox, int search_resolution, int sliced_points, float* nn_d2, double* window_error,
                            int capacity, int* n_windows, int* best_window, double* lowest_error);
+/* The search above for n problems in one device call.  Problem i: rows velo_offsets[i] .. velo_offsets[i+1]-1 of velo_xyz
+ * (transformed with the matrix tf + 16 i; tf == NULL: no problem is transformed) are searched from rows livox_offsets[i] ..
+ * livox_offsets[i+1]-1 of livox_xyz.  Every output of problem i is what mml_time_offset_search returns for that problem alone, to
+ * the byte: n_windows[i], best_window[i], lowest_error[i], the rows livox_offsets[i] .. of nn_d2 (optional; indexed like
+ * livox_xyz) and the window errors, written at window_error + window_offsets[i] -- at most window_offsets[i+1] - window_offsets[i]
+ * of them, the single call's `capacity` rule (window_error is optional; window_offsets is read only with it).  A problem
+ * without Livox points yields 0 windows, -1 and 1e6; one with no more than sliced_points Livox points yields 0 windows and its
+ * nn_d2 rows.  All problems are checked before any device work and a refusal writes nothing: MML_ERR_INVALID for n outside
+ * 1 .. MML_TOFS_BATCH_MAX, negative or decreasing offsets, a NULL required pointer, search_resolution or sliced_points below 1,
+ * a problem with Livox points and no Velodyne point; MML_ERR_CAPACITY for a Velodyne cloud above max_map_points;
+ * mml_last_error names the entry point and, where there is one, the problem.
+ * Host synchronisations: the call first waits for everything the context has in flight, then synchronises exactly TWICE whatever
+ * n is -- after the read-back of the n bounding boxes, from which the host lays out every problem's grid in one pass, and after
+ * the read-back of the results (none when the call holds no Livox point at all).  With profiling on, each of the two phases
+ * shows as one launch of the stages "tofs_box" and "tofs_search" per call.
+ * The context keeps one grow-only scratch block for the largest call it has seen (100 bytes per Velodyne point -- the grid cells,
+ * 8 per point, included --, 16 per Livox point, 8 per window, the sort's scratch), released by mml_destroy; MML_ERR_HIP, before
+ * any launch, when it cannot be grown.  mml_time_offset_search is the n = 1 case of the same code and uses the same block.
+ * MML_TOFS_BATCH_MAX bounds n because the problem index is a grid's y dimension. */
+#define MML_TOFS_BATCH_MAX 65535   /* problems per call */
+int mml_time_offset_search_batch(mml_ctx* ctx, int n,
+        const float* velo_xyz, const int* velo_offsets /* n + 1 */,
+        const float* tf /* n x 16, or NULL = identity for every problem */,
+        const float* livox_xyz, const int* livox_offsets /* n + 1 */,
+        int search_resolution, int sliced_points,
+        float* nn_d2 /* livox_offsets[n] floats, may be NULL */,
+        double* window_error /* may be NULL */, const long* window_offsets /* n + 1, required iff window_error */,
+        int* n_windows /* n */, int* best_window /* n */, double* lowest_error /* n */);
+/* The checks of the batch call that need no device, on the host alone (no context): the return code the call would refuse the
+ * offsets and parameters with (max_map_points < 0: no capacity check), *bad_problem (optional) = the problem a refusal is
+ * about or -1, and -- only with MML_OK -- n_windows[i] (optional) = (n_livox_i - sliced_points - 1) / search_resolution + 1
+ * when n_livox_i > sliced_points, else 0. */
+int mml_time_offset_plan(int n, const int* velo_offsets, const int* livox_offsets, int search_resolution, int sliced_points,
+                         int max_map_points, int* n_windows /* n, may be NULL */, int* bad_problem /* may be NULL */);
 
 /* ---- SURVEY section 8(f) rank 4 (the other part): the per-frame GICP extrinsic refresh ---------------------------------
  * icp_ext_matching (unionFeatureExtract.cpp:74-123): pcl::GeneralizedIterativeClosestPoint with setMaximumIterations(10),

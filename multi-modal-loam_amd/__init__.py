@@ -29,6 +29,7 @@ FW_BATCH_MAX = 1024     # MML_FW_BATCH_MAX: windows per call
 PREINT_BATCH_MAX = 8192  # MML_PREINT_BATCH_MAX: intervals per call of mml_imu_preintegrate_batch
 LIO_BATCH_MAX = 1024     # MML_LIO_BATCH_MAX: segments per call of mml_lio_initialize_batch
 LIO_BATCH_MAX_FRAMES = 8  # MML_LIO_BATCH_MAX_FRAMES: frames per segment
+TOFS_BATCH_MAX = 65535    # MML_TOFS_BATCH_MAX: problems per call of mml_time_offset_search_batch
 GICP_BATCH_MAX = 65535    # MML_GICP_BATCH_MAX: problems / slots per call of mml_gicp_align_batch / mml_gicp_refresh_batch
 
 LIVOX_DTYPE = np.dtype([("offset_time", "<u4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4"),
@@ -236,6 +237,11 @@ def lib():
             L.mml_gicp_align_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
             L.mml_gicp_refresh_batch.restype = C.c_int
             L.mml_gicp_refresh_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        if hasattr(L, "mml_time_offset_search_batch"):
+            L.mml_time_offset_search_batch.restype = C.c_int
+            L.mml_time_offset_search_batch.argtypes = ([C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_int] + [C.c_void_p] * 6)
+            L.mml_time_offset_plan.restype = C.c_int
+            L.mml_time_offset_plan.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         if hasattr(L, "mml_cloud_download_registered_batch"):
             L.mml_cloud_download_registered_batch.restype = C.c_int
             L.mml_cloud_download_registered_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]
@@ -314,6 +320,43 @@ def gicp_pack_pairs(pairs, T0=None):
         T0 = np.asarray(T0, np.float32)
         T = np.tile(T0, (n, 1, 1)) if T0.size == 16 else T0.reshape(n, 4, 4).copy()
     return src, so, tgt, to, np.ascontiguousarray(T)
+
+
+def time_offset_pack(velo_list, livox_list, tfs=None):
+    """The arguments of mml_time_offset_search_batch for ragged lists of clouds: (velo n x 3 float32, velo_offsets int32[n + 1],
+    livox, livox_offsets, tf float32[n, 16] or None).  tfs: None (no problem is transformed), one 4 x 4 matrix for every problem,
+    or n of them."""
+    if len(velo_list) != len(livox_list):
+        raise ValueError("%d Velodyne clouds for %d Livox clouds" % (len(velo_list), len(livox_list)))
+    n = len(velo_list)
+    vs = [_f32(v).reshape(-1, 3) for v in velo_list]
+    ls = [_f32(l).reshape(-1, 3) for l in livox_list]
+    vo = np.zeros(n + 1, np.int32)
+    lo = np.zeros(n + 1, np.int32)
+    vo[1:] = np.cumsum([len(v) for v in vs])
+    lo[1:] = np.cumsum([len(l) for l in ls])
+    velo = np.ascontiguousarray(np.concatenate(vs + [np.zeros((0, 3), np.float32)]))
+    livox = np.ascontiguousarray(np.concatenate(ls + [np.zeros((0, 3), np.float32)]))
+    tf = None
+    if tfs is not None:
+        t = np.asarray(tfs, np.float32)
+        tf = np.ascontiguousarray(np.tile(t.reshape(1, 16), (n, 1)) if t.size == 16 else t.reshape(n, 16).copy())
+    return velo, vo, livox, lo, tf
+
+
+def time_offset_plan(velo_offsets, livox_offsets, search_resolution=30, sliced_points=12000, max_map_points=-1):
+    """mml_time_offset_plan: the host-only checks of mml_time_offset_search_batch (no context, no device).  Returns
+    (code, bad_problem, n_windows int32[n]); n_windows is filled only when code == MML_OK.  max_map_points < 0: no capacity check."""
+    vo = np.ascontiguousarray(velo_offsets, dtype=np.int32)
+    lo = np.ascontiguousarray(livox_offsets, dtype=np.int32)
+    if len(vo) != len(lo):
+        raise ValueError("the two offset arrays must have the same length (n + 1)")
+    n = len(vo) - 1
+    nwin = np.zeros(max(n, 1), np.int32)
+    bad = C.c_int(-1)
+    rc = lib().mml_time_offset_plan(C.c_int(n), _p(vo), _p(lo), C.c_int(search_resolution), C.c_int(sliced_points),
+                                    C.c_int(max_map_points), _p(nwin), C.byref(bad))
+    return rc, bad.value, nwin[:max(n, 0)]
 
 
 class Context:
@@ -415,6 +458,26 @@ class Context:
                                               C.c_int(sliced_points), _p(nn), _p(err), C.c_int(cap), C.byref(nwin),
                                               C.byref(best), C.byref(lowest)))
         return {"nn_d2": nn[:len(l)], "window_error": err[:nwin.value], "best_window": best.value, "lowest_error": lowest.value}
+
+    def time_offset_search_batch(self, velo_list, livox_list, search_resolution=30, sliced_points=12000, tfs=None):
+        """mml_time_offset_search_batch: time_offset_search for a list of (Velodyne, Livox) cloud pairs in one device call; a
+        list of the dicts time_offset_search returns.  tfs: None, one 4 x 4 matrix for all problems, or one per problem."""
+        velo, vo, livox, lo, tf = time_offset_pack(velo_list, livox_list, tfs)
+        n = len(vo) - 1
+        rc, bad, nwin = time_offset_plan(vo, lo, search_resolution, sliced_points)
+        wo = np.zeros(n + 1, np.int64)     # (C long: 8 bytes on the LP64 hosts ROCm runs on)
+        if rc == MML_OK:
+            wo[1:] = np.cumsum(nwin)
+        nn = np.zeros(max(len(livox), 1), np.float32)
+        err = np.zeros(max(int(wo[-1]), 1), np.float64)
+        nw = np.zeros(max(n, 1), np.int32)
+        best = np.zeros(max(n, 1), np.int32)
+        lowest = np.zeros(max(n, 1), np.float64)
+        self._ck(lib().mml_time_offset_search_batch(self._h, C.c_int(n), _p(velo) if len(velo) else None, _p(vo),
+                                                    _p(tf), _p(livox) if len(livox) else None, _p(lo), C.c_int(search_resolution),
+                                                    C.c_int(sliced_points), _p(nn), _p(err), _p(wo), _p(nw), _p(best), _p(lowest)))
+        return [{"nn_d2": nn[lo[i]:lo[i + 1]], "window_error": err[wo[i]:wo[i] + nw[i]], "best_window": int(best[i]),
+                 "lowest_error": float(lowest[i])} for i in range(n)]
 
     def scan_download_pointxyzinormal(self, slot):
         """The fused labelled cloud as 48-byte PointXYZINormal records (the velo_combine / livox_combine payload)."""

@@ -70,6 +70,7 @@ struct MmlFwDev;  // fullwindow_dev.hip: parameter / scratch buffers of the devi
 struct MmlPreintDev;  // imu_preint.hip: buffers of mml_imu_preintegrate_batch
 struct MmlLioDev;     // lio_init_batch.hip: the block of mml_lio_initialize_batch
 struct MmlGicpDev;    // gicp.hip: the blocks of the GICP alignments (single and batch calls)
+struct MmlTofsDev;    // time_offset.hip: the blocks of the time-offset searches (single and batch calls)
 
 struct mml_ctx {
     mml_config cfg;
@@ -78,6 +79,7 @@ struct mml_ctx {
     MmlPreintDev* preint = nullptr;
     MmlLioDev* lio = nullptr;
     MmlGicpDev* gicp = nullptr;
+    MmlTofsDev* tofs = nullptr;
     // frame-parallel window solve (solve.hip): one state machine copy, 4 counters and two record buffers per slot
     void* wstate = nullptr;
     double* wrec = nullptr;
@@ -365,8 +367,6 @@ int mml_launch_undistort_listed(mml_ctx* ctx, int first, int count, const double
 // finishes the partly undistorted slots of [first, first + count) on the current stream (a host loop over B bytes when none is)
 int mml_cloud_settle(mml_ctx* ctx, int first, int count);
 #define MML_LABEL_SETTLED 0x40  // no label value uses it: 0, 1, 2, 0x81, 0x82
-int mml_launch_time_offset(mml_ctx* ctx, MmlGrid& g, float4* d_velo4, const float* d_velo_xyz, int n_velo, const float* d_tf,
-                           const float* d_livox_xyz, int n_livox, int res, int sliced, int nwin, float* d_nn, double* d_err);
 int mml_launch_downsample(mml_ctx* ctx, int first, int count);
 // labelled corner points per (slot, kind) that the LDS sort of k_voxel takes (surf: MML_VOXEL_LDS_CAP)
 inline int mml_voxel_cap_corner(const mml_ctx* ctx) { return (ctx->NT > 65536 || MML_VOXEL_LDS_CAP < 2048) ? MML_VOXEL_LDS_CAP : 2048; }
@@ -396,6 +396,7 @@ void mml_fullwindow_dev_release(mml_ctx* ctx);
 void mml_imu_preint_release(mml_ctx* ctx);
 void mml_lio_init_release(mml_ctx* ctx);
 void mml_gicp_release(mml_ctx* ctx);
+void mml_time_offset_release(mml_ctx* ctx);
 int mml_launch_detect_line(mml_ctx* ctx, int n, uint16_t* d_final);
 int mml_launch_raw_lines(mml_ctx* ctx, int first, int count);  // raw_line[] of the slots (ring / line id per raw point), for the GICP refresh
 int mml_launch_linearize(mml_ctx* ctx, int slot, const double* d_x, const double* d_Tbl, double w_tan,

@@ -1,0 +1,597 @@
+// time_offset.hip -- SURVEY 8(f) rank 4 (part): the numeric core of LidarsParamEstimator::estimate_timeoffset
+// (unionLidarsAligner.cpp:1077-1153) for n problems per call.
+//   problem = one Velodyne FOV cloud (transformed by its own 4 x 4 float matrix), one merged Livox cloud:
+//   :1080-1082  pcl::transformPointCloud of the Velodyne cloud                      k_tofs_tf
+//   :1084-1103  squared distance of every Livox point to its nearest Velodyne point k_tofs_box .. k_tofs_nn1
+//   :1111-1131  sliding-window error sums                                           k_tofs_window_err
+//   :1107,1141-1150  first strict minimum below 1e6                                 k_tofs_best
+// ONE set of kernels serves mml_time_offset_search and mml_time_offset_search_batch: every kernel reads a per-problem device
+// table (TofsProb) with the problem index in blockIdx.y, and the single call is the n = 1 case.  A problem's arithmetic does
+// not depend on the problems next to it: its distances come from an EXACT search (knn5_dev.h), which returns the same float
+// whatever grid it walks, and its window sums are formed by one lane each in index order.
+// Compiled with -ffp-contract=off.
+#include <math.h>
+#include <string.h>
+
+#include <rocprim/rocprim.hpp>
+
+#include "mml_internal.h"
+
+namespace {
+
+#include "knn5_dev.h"
+
+// One problem of a call.  Rows are counted from the call's first row (velo_offsets[0] / livox_offsets[0]); g.pts and g.cell_start
+// point into the call's blocks and g is complete once the boxes have been read back (tofs_choose_grid).
+struct TofsProb {
+    MmlGrid g;
+    int v_base, n_velo;
+    int l_base, n_livox;
+    long long e_base;  // first window of the problem in the error array
+    int n_win, _pad;
+};
+struct TofsBest {
+    double lowest;
+    int best, _pad;
+};
+
+constexpr int TOFS_BOX_BLOCKS = 64;  // workgroups per problem of the bounding-box pass (each strides over the cloud)
+
+// pcl::transformPointCloud (PCL 1.8.1 common/impl/transforms.hpp), float, left to right; tf == nullptr: copy
+__global__ __launch_bounds__(256) void k_tofs_tf(const TofsProb* __restrict__ tab, const float* __restrict__ xyz, const float* __restrict__ tf,
+                                                 float4* __restrict__ out) {
+    const int base = tab[blockIdx.y].v_base, n = tab[blockIdx.y].n_velo;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float* p = xyz + 3 * (size_t)(base + i);
+    const float x = p[0], y = p[1], z = p[2];
+    float4 o = make_float4(x, y, z, 0.f);
+    if (tf) {
+        const float* t = tf + 16 * (size_t)blockIdx.y;
+        o.x = t[0] * x + t[1] * y + t[2] * z + t[3];
+        o.y = t[4] * x + t[5] * y + t[6] * z + t[7];
+        o.z = t[8] * x + t[9] * y + t[10] * z + t[11];
+    }
+    out[base + i] = o;
+}
+
+// float minimum / maximum into memory (min and max do not depend on the order of arrival)
+__device__ __forceinline__ void atomic_min_f32(float* addr, float v) {
+    int* a = reinterpret_cast<int*>(addr);
+    int old = *a;
+    while (v < __int_as_float(old)) {
+        const int assumed = old;
+        old = atomicCAS(a, assumed, __float_as_int(v));
+        if (old == assumed) break;
+    }
+}
+__device__ __forceinline__ void atomic_max_f32(float* addr, float v) {
+    int* a = reinterpret_cast<int*>(addr);
+    int old = *a;
+    while (v > __int_as_float(old)) {
+        const int assumed = old;
+        old = atomicCAS(a, assumed, __float_as_int(v));
+        if (old == assumed) break;
+    }
+}
+
+// bounding box of every problem's transformed cloud: box[6 p ..] = min xyz, max xyz (the host uploads +inf / -inf)
+__global__ __launch_bounds__(256) void k_tofs_box(const TofsProb* __restrict__ tab, const float4* __restrict__ pts, float* __restrict__ box) {
+    __shared__ float s[6][4];
+    const int base = tab[blockIdx.y].v_base, n = tab[blockIdx.y].n_velo;
+    if ((int)blockIdx.x * 256 >= n) return;  // (the whole workgroup)
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const float4 p = pts[base + i];
+        mn[0] = fminf(mn[0], p.x);
+        mn[1] = fminf(mn[1], p.y);
+        mn[2] = fminf(mn[2], p.z);
+        mx[0] = fmaxf(mx[0], p.x);
+        mx[1] = fmaxf(mx[1], p.y);
+        mx[2] = fmaxf(mx[2], p.z);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int c = 0; c < 3; ++c) {
+        for (int o = 32; o > 0; o >>= 1) {
+            mn[c] = fminf(mn[c], __shfl_xor(mn[c], o));
+            mx[c] = fmaxf(mx[c], __shfl_xor(mx[c], o));
+        }
+        if (lane == 0) {
+            s[c][wave] = mn[c];
+            s[3 + c][wave] = mx[c];
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        const int c = threadIdx.x;
+        float v = s[c][0];
+        for (int w = 1; w < 4; ++w) v = (c < 3) ? fminf(v, s[c][w]) : fmaxf(v, s[c][w]);
+        if (c < 3)
+            atomic_min_f32(box + 6 * (size_t)blockIdx.y + c, v);
+        else
+            atomic_max_f32(box + 6 * (size_t)blockIdx.y + c, v);
+    }
+}
+
+// sort key of every point: problem << 32 | cell (the cell mapping of map_assoc.hip's k_cell_keys), value: its index in the problem
+__global__ __launch_bounds__(256) void k_tofs_keys(const TofsProb* __restrict__ tab, const float4* __restrict__ pts,
+                                                   unsigned long long* __restrict__ keys, unsigned* __restrict__ vals) {
+    const TofsProb& P = tab[blockIdx.y];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= P.n_velo) return;
+    const float4 p = pts[P.v_base + i];
+    const float inv = P.g.inv_cell;
+    const int dx = P.g.dim[0], dy = P.g.dim[1], dz = P.g.dim[2];
+    const int cx = cell_coord(p.x, P.g.origin[0], inv, dx);
+    const int cy = cell_coord(p.y, P.g.origin[1], inv, dy);
+    const int cz = cell_coord(p.z, P.g.origin[2], inv, dz);
+    keys[P.v_base + i] = ((unsigned long long)blockIdx.y << 32) | (unsigned)(cx + dx * (cy + dy * cz));
+    vals[P.v_base + i] = (unsigned)i;
+}
+
+// The sort keeps a problem's points in its own rows (the problem is the key's high word and the rows were in problem order):
+// sorted row v_base + i holds the problem's i-th point in cell order, w = its index in the problem's cloud.
+__global__ __launch_bounds__(256) void k_tofs_gather(const TofsProb* __restrict__ tab, const float4* __restrict__ pts,
+                                                     const unsigned* __restrict__ vals, float4* __restrict__ out) {
+    const int base = tab[blockIdx.y].v_base, n = tab[blockIdx.y].n_velo;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const unsigned src = vals[base + i];
+    float4 p = pts[base + src];
+    p.w = __uint_as_float(src);
+    out[base + i] = p;
+}
+
+// cell_start[c] = first sorted point of the problem whose cell >= c (lower bound); cell_start[ncell] = n_velo
+__global__ __launch_bounds__(256) void k_tofs_cell_start(const TofsProb* __restrict__ tab, const unsigned long long* __restrict__ keys) {
+    const TofsProb& P = tab[blockIdx.y];
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (P.n_velo == 0 || c > P.g.ncell) return;
+    const unsigned long long* k = keys + P.v_base;
+    int lo = 0, hi = P.n_velo;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((unsigned)k[mid] < (unsigned)c)
+            lo = mid + 1;
+        else
+            hi = mid;
+    }
+    P.g.cell_start[c] = lo;
+}
+
+// :1084-1103 squared distance to the nearest neighbour (the exact 5-NN search, first entry).  A workgroup serves ONE problem, so
+// its grid descriptor is wave-uniform: copied out of the table once, it stays in scalar registers (see k_associate, map_assoc.hip).
+__global__ __launch_bounds__(256) void k_tofs_nn1(const TofsProb* __restrict__ tab, const float* __restrict__ q_all, float* __restrict__ d2_all) {
+    const TofsProb& P = tab[blockIdx.y];
+    const int nq = P.n_livox;
+    if ((int)blockIdx.x * 256 >= nq) return;  // (the whole workgroup: knn5_search needs whole wavefronts)
+    MmlGrid g;
+    g.pts = P.g.pts;
+    g.cell_start = P.g.cell_start;
+    g.tags = nullptr;
+    g.m = P.g.m;
+    g.origin[0] = P.g.origin[0];
+    g.origin[1] = P.g.origin[1];
+    g.origin[2] = P.g.origin[2];
+    g.cell = P.g.cell;
+    g.inv_cell = P.g.inv_cell;
+    g.dim[0] = P.g.dim[0];
+    g.dim[1] = P.g.dim[1];
+    g.dim[2] = P.g.dim[2];
+    g.ncell = P.g.ncell;
+    const float* q = q_all + 3 * (size_t)P.l_base;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const bool valid = i < nq;
+    Knn5 k;
+    knn5_search(g, valid, valid ? q[3 * i] : 0.f, valid ? q[3 * i + 1] : 0.f, valid ? q[3 * i + 2] : 0.f, INFINITY, k);
+    if (valid) d2_all[P.l_base + i] = knn_d(k, 0);
+}
+
+// :1111-1131 one lane per (problem, window), found through the exclusive scan of the window counts (woff, n + 1 entries);
+// the terms are added in index order, in double, as the reference's loop does
+__global__ __launch_bounds__(64) void k_tofs_window_err(const TofsProb* __restrict__ tab, int n, const long long* __restrict__ woff,
+                                                        const float* __restrict__ q_all, const float* __restrict__ d2_all, int res, int sliced,
+                                                        double* __restrict__ err) {
+    const long long w = (long long)blockIdx.x * 64 + threadIdx.x;
+    if (w >= woff[n]) return;
+    int lo = 0, hi = n;  // the problem p with woff[p] <= w < woff[p + 1]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (woff[mid] <= w)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    const TofsProb& P = tab[lo];
+    const int cnt = (int)(w - woff[lo]);
+    const float* q = q_all + 3 * (size_t)P.l_base;
+    const float* d2 = d2_all + P.l_base;
+    double sum_error = 0;
+    for (int i = cnt * res; i < cnt * res + sliced; ++i) {
+        const float x = q[3 * i], y = q[3 * i + 1];
+        sum_error += d2[i] + 0.2 * sqrtf(x * x + y * y);
+    }
+    err[w] = sum_error;
+}
+
+// :1107,1141-1150 per problem: the lowest window error below 1e6 and the first window that has it (-1: none)
+__device__ __forceinline__ void tofs_better(double& lo, int& best, double lo2, int best2) {
+    if (lo2 < lo || (lo2 == lo && best2 >= 0 && best2 < best)) {
+        lo = lo2;
+        best = best2;
+    }
+}
+__global__ __launch_bounds__(256) void k_tofs_best(const TofsProb* __restrict__ tab, const double* __restrict__ err, TofsBest* __restrict__ out) {
+    __shared__ double s_lo[4];
+    __shared__ int s_best[4];
+    const TofsProb& P = tab[blockIdx.x];
+    const double* e = err + P.e_base;
+    double lo = 1000000.0;
+    int best = -1;
+    for (int c = threadIdx.x; c < P.n_win; c += 256) {  // (ascending in a lane: the first of equal values stays)
+        const double v = e[c];
+        if (v < lo) {
+            lo = v;
+            best = c;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) tofs_better(lo, best, __shfl_xor(lo, o), __shfl_xor(best, o));
+    if ((threadIdx.x & 63) == 0) {
+        s_lo[threadIdx.x >> 6] = lo;
+        s_best[threadIdx.x >> 6] = best;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w) tofs_better(lo, best, s_lo[w], s_best[w]);
+        out[blockIdx.x].lowest = lo;
+        out[blockIdx.x].best = best;
+    }
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------
+
+// Why a call is refused (mml_time_offset_plan's checks, in this order); `bad`: the problem it is about, -1 when it is not about one.
+enum { TOFS_OK = 0, TOFS_N, TOFS_NULL, TOFS_PARAM, TOFS_NEGATIVE, TOFS_DECREASING, TOFS_NO_VELO, TOFS_TOO_LARGE };
+int tofs_plan(int n, const int* vo, const int* lo, int res, int sliced, int max_map_points, int* nwin, int* bad) {
+    *bad = -1;
+    if (n < 1 || n > MML_TOFS_BATCH_MAX) return TOFS_N;
+    if (!vo || !lo) return TOFS_NULL;
+    if (res < 1 || sliced < 1) return TOFS_PARAM;
+    *bad = 0;
+    if (vo[0] < 0 || lo[0] < 0) return TOFS_NEGATIVE;
+    for (int i = 0; i < n; ++i)
+        if (vo[i + 1] < vo[i] || lo[i + 1] < lo[i]) {
+            *bad = i;
+            return TOFS_DECREASING;
+        }
+    for (int i = 0; i < n; ++i) {
+        const int nv = vo[i + 1] - vo[i], nl = lo[i + 1] - lo[i];
+        *bad = i;
+        if (nl > 0 && nv == 0) return TOFS_NO_VELO;
+        if (max_map_points >= 0 && nv > max_map_points) return TOFS_TOO_LARGE;
+    }
+    *bad = -1;
+    if (nwin)
+        for (int i = 0; i < n; ++i) {  // windows: cnt = 0, 1, ... while cnt * res + sliced < n_livox
+            const int nl = lo[i + 1] - lo[i];
+            nwin[i] = nl > sliced ? (nl - sliced - 1) / res + 1 : 0;
+        }
+    return TOFS_OK;
+}
+int tofs_code(int why) { return why == TOFS_OK ? MML_OK : (why == TOFS_TOO_LARGE ? MML_ERR_CAPACITY : MML_ERR_INVALID); }
+
+// Cells a problem of m Velodyne points may use; the pool of cell_start arrays is reserved for the sum of these before any launch.
+long long tofs_cell_budget(int m) { return 8ll * m + 64; }
+
+// The grid of one problem from its bounding box and point count alone -- no occupancy round trip: start from the 0.5 m cell of an
+// unfiltered scan, grow it by 1.26 (a factor 2 in volume) until the box fits the budget, then halve it up to four times while
+// the box still fits (a scan is a set of surfaces, most cells of its box are empty: the budget of 8 cells per point leaves an
+// occupied cell a handful of points).  The distances do not depend on the choice (the search is exact), only the time does.
+void tofs_choose_grid(const float* box, int m, MmlGrid& g) {
+    const long long cap = tofs_cell_budget(m);
+    const auto dims = [&](float cell, int* dim) {
+        long long total = 1;
+        for (int c = 0; c < 3; ++c) {
+            const float ext = box[3 + c] - box[c];
+            double d = isfinite(ext) ? floor((double)(ext / cell)) + 1.0 : 1.0;  // (a box with an infinite side: one cell across)
+            if (!(d >= 1.0)) d = 1.0;
+            if (d > 1048576.0) d = 1048576.0;  // (2^20 per axis: the product stays below 2^63)
+            dim[c] = (int)d;
+            total *= dim[c];
+        }
+        return total;
+    };
+    float cell = 0.5f;
+    int dim[3];
+    long long total = dims(cell, dim);
+    while (total > cap) {  // (ends: a cell beyond the largest finite side leaves one cell)
+        cell *= 1.26f;
+        total = dims(cell, dim);
+    }
+    for (int round = 0; round < 4; ++round) {
+        int d2[3];
+        const long long t2 = dims(cell * 0.5f, d2);
+        if (t2 > cap || t2 == total) break;
+        cell *= 0.5f;
+        total = t2;
+        memcpy(dim, d2, sizeof(dim));
+    }
+    g.cell = cell;
+    g.inv_cell = 1.0f / cell;
+    for (int c = 0; c < 3; ++c) {
+        g.origin[c] = box[c];
+        g.dim[c] = dim[c];
+    }
+    g.ncell = (int)total;
+}
+
+size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
+
+// io block (device + pinned twin): what crosses the bus in small pieces, and the window errors
+struct IoLayout {
+    size_t tab, tf, box, woff, best, err, bytes;
+    IoLayout(size_t n, size_t n_win) {
+        size_t o = 0;
+        const auto take = [&](size_t b) {
+            const size_t at = o;
+            o += align256(b);
+            return at;
+        };
+        tab = take(sizeof(TofsProb) * n);
+        tf = take(sizeof(float) * 16 * n);
+        box = take(sizeof(float) * 6 * n);
+        woff = take(sizeof(long long) * (n + 1));
+        best = take(sizeof(TofsBest) * n);
+        err = take(sizeof(double) * n_win);
+        bytes = o;
+    }
+};
+// big block (device only): 100 bytes per Velodyne point (cells included), 16 per Livox point, the sort's scratch
+struct BigLayout {
+    size_t vxyz, v4, pts, keys, keys2, vals, vals2, lxyz, nn, cells, sort, bytes;
+    BigLayout(size_t nv, size_t nl, size_t n_cells, size_t sort_bytes) {
+        size_t o = 0;
+        const auto take = [&](size_t b) {
+            const size_t at = o;
+            o += align256(b);
+            return at;
+        };
+        vxyz = take(sizeof(float) * 3 * nv);
+        v4 = take(sizeof(float4) * nv);
+        pts = take(sizeof(float4) * nv);
+        keys = take(sizeof(unsigned long long) * nv);
+        keys2 = take(sizeof(unsigned long long) * nv);
+        vals = take(sizeof(unsigned) * nv);
+        vals2 = take(sizeof(unsigned) * nv);
+        lxyz = take(sizeof(float) * 3 * nl);
+        nn = take(sizeof(float) * nl);
+        cells = take(sizeof(int) * n_cells);
+        sort = take(sort_bytes);
+        bytes = o;
+    }
+};
+
+int bits_for(long long values) {  // bits that hold 0 .. values - 1
+    int bits = 1;
+    while ((1ll << bits) < values) ++bits;
+    return bits;
+}
+
+}  // namespace
+
+// Grow-only scratch of the time-offset searches, owned by the context: nothing is allocated or freed per call once the largest
+// call has been seen.  Every entry point drains the stream before it returns, so reserve() never replaces a buffer in use.
+struct MmlTofsDev {
+    MmlStaging<char> io;
+    MmlStaging<char, false> big;
+};
+
+void mml_time_offset_release(mml_ctx* ctx) {
+    MmlTofsDev* d = ctx->tofs;
+    if (!d) return;
+    d->io.release();
+    d->big.release();
+    delete d;
+    ctx->tofs = nullptr;
+}
+
+namespace {
+
+// The n searches of mml_time_offset_search_batch; mml_time_offset_search is its n = 1 case.  `who`: the entry point the caller
+// used, which is the name a refusal carries.  Every refusal comes before any device work and before any output is written.
+int tofs_run(mml_ctx* ctx, const char* who, int n, const float* velo_xyz, const int* vo, const float* tf, const float* livox_xyz, const int* lo,
+             int res, int sliced, float* nn_d2, double* window_error, const long* wo, int* n_windows, int* best_window, double* lowest_error) {
+    std::vector<int> nwin((size_t)(n > 0 && n <= MML_TOFS_BATCH_MAX ? n : 1));
+    int bad = -1;
+    const int why = tofs_plan(n, vo, lo, res, sliced, ctx->MM, nwin.data(), &bad);
+    switch (why) {
+        case TOFS_N: return mml_refuse(ctx, MML_ERR_INVALID, "%s: n = %d is outside 1 .. %d", who, n, MML_TOFS_BATCH_MAX);
+        case TOFS_NULL: return mml_refuse(ctx, MML_ERR_INVALID, "%s: a null argument", who);
+        case TOFS_PARAM: return mml_refuse(ctx, MML_ERR_INVALID, "%s: search_resolution / sliced_points must be >= 1", who);
+        case TOFS_NEGATIVE: return mml_refuse(ctx, MML_ERR_INVALID, "%s: problem 0: a negative offset", who);
+        case TOFS_DECREASING:
+            return mml_refuse(ctx, MML_ERR_INVALID, "%s: problem %d: its clouds end before their start (offsets must not decrease)", who, bad);
+        case TOFS_NO_VELO:
+            return mml_refuse(ctx, MML_ERR_INVALID, "%s: problem %d: nearest-neighbour search in an empty cloud (Livox points, no Velodyne point)", who,
+                              bad);
+        case TOFS_TOO_LARGE:
+            return mml_refuse(ctx, MML_ERR_CAPACITY, "%s: problem %d: its Velodyne cloud of %d points exceeds max_map_points = %d", who, bad,
+                              vo[bad + 1] - vo[bad], ctx->MM);
+        default: break;
+    }
+    if (!(n_windows && best_window && lowest_error) || (window_error && !wo)) return mml_refuse(ctx, MML_ERR_INVALID, "%s: a null argument", who);
+    if (window_error) {
+        if (wo[0] < 0) return mml_refuse(ctx, MML_ERR_INVALID, "%s: problem 0: a negative window offset", who);
+        for (int i = 0; i < n; ++i)
+            if (wo[i + 1] < wo[i]) return mml_refuse(ctx, MML_ERR_INVALID, "%s: problem %d: window offsets must not decrease", who, i);
+    }
+    const size_t nv = (size_t)(vo[n] - vo[0]), nl = (size_t)(lo[n] - lo[0]);
+    if ((nv > 0 && !velo_xyz) || (nl > 0 && !livox_xyz)) return mml_refuse(ctx, MML_ERR_INVALID, "%s: a null cloud", who);
+
+    // Everything the context has in flight ends here -- every lane of a pipelined mml_step and the upload stream --, so a search that
+    // follows a multi-lane step starts on an idle device; it reads no slot anyway: all it touches is the caller's arrays and its own block.
+    MML_HIP(hipSetDevice(ctx->device));
+    int rc = mml_sync_all(ctx);
+    if (rc != MML_OK) return rc;
+    ctx->cur = 0;
+
+    size_t n_win = 0, n_cells = 0;
+    int max_v = 0, max_l = 0;
+    for (int i = 0; i < n; ++i) {
+        const int m = vo[i + 1] - vo[i], l = lo[i + 1] - lo[i];
+        n_win += (size_t)nwin[i];
+        if (m > 0) n_cells += (size_t)tofs_cell_budget(m) + 1;
+        max_v = m > max_v ? m : max_v;
+        max_l = l > max_l ? l : max_l;
+    }
+    std::vector<TofsBest> best((size_t)n, TofsBest{1000000.0, -1, 0});
+    const double* h_err = nullptr;
+    if (nl > 0) {  // (no Livox point in the whole call: nothing to search)
+        size_t sort_bytes = 0;
+        MML_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (unsigned*)nullptr,
+                                          (unsigned*)nullptr, nv, 0, 64, MML_STREAM(ctx)));
+        const IoLayout io((size_t)n, n_win);
+        const BigLayout big(nv, nl, n_cells, sort_bytes);
+        if (!ctx->tofs) ctx->tofs = new MmlTofsDev();
+        MmlTofsDev* d = ctx->tofs;
+        if (d->io.reserve(ctx, io.bytes) || d->big.reserve(ctx, big.bytes)) {
+            ctx->err = std::string(who) + ": the scratch block could not be grown: " + ctx->err;
+            return MML_ERR_HIP;
+        }
+        hipStream_t s = MML_STREAM(ctx);
+        char *h = d->io.h, *g = d->io.d, *b = d->big.d;
+        TofsProb* h_tab = reinterpret_cast<TofsProb*>(h + io.tab);
+        float* h_box = reinterpret_cast<float*>(h + io.box);
+        long long* h_woff = reinterpret_cast<long long*>(h + io.woff);
+        const TofsProb* d_tab = reinterpret_cast<const TofsProb*>(g + io.tab);
+        const float* d_tf = tf ? reinterpret_cast<const float*>(g + io.tf) : nullptr;
+        float4* d_v4 = reinterpret_cast<float4*>(b + big.v4);
+        float4* d_pts = reinterpret_cast<float4*>(b + big.pts);
+        unsigned long long *d_keys = reinterpret_cast<unsigned long long*>(b + big.keys), *d_keys2 = reinterpret_cast<unsigned long long*>(b + big.keys2);
+        unsigned *d_vals = reinterpret_cast<unsigned*>(b + big.vals), *d_vals2 = reinterpret_cast<unsigned*>(b + big.vals2);
+        float* d_lxyz = reinterpret_cast<float*>(b + big.lxyz);
+        float* d_nn = reinterpret_cast<float*>(b + big.nn);
+        double* d_err = reinterpret_cast<double*>(g + io.err);
+        h_woff[0] = 0;
+        for (int i = 0; i < n; ++i) {
+            TofsProb& P = h_tab[i];
+            P = TofsProb{};
+            P.v_base = vo[i] - vo[0];
+            P.n_velo = vo[i + 1] - vo[i];
+            P.l_base = lo[i] - lo[0];
+            P.n_livox = lo[i + 1] - lo[i];
+            P.e_base = h_woff[i];
+            P.n_win = nwin[i];
+            h_woff[i + 1] = h_woff[i] + nwin[i];
+            for (int c = 0; c < 3; ++c) {
+                h_box[6 * i + c] = INFINITY;
+                h_box[6 * i + 3 + c] = -INFINITY;
+            }
+        }
+        const unsigned by = (unsigned)n, bx_v = (unsigned)((max_v + 255) / 256);
+        {   // host synchronisation 1 of 2: the boxes of all problems in one copy
+            MmlStageScope t(ctx, "tofs_box");
+            MML_HIP(hipMemcpyAsync(g + io.tab, h + io.tab, sizeof(TofsProb) * (size_t)n, hipMemcpyHostToDevice, s));
+            MML_HIP(hipMemcpyAsync(g + io.box, h + io.box, sizeof(float) * 6 * (size_t)n, hipMemcpyHostToDevice, s));
+            MML_HIP(hipMemcpyAsync(g + io.woff, h + io.woff, sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice, s));
+            if (tf) MML_HIP(hipMemcpyAsync(g + io.tf, tf, sizeof(float) * 16 * (size_t)n, hipMemcpyHostToDevice, s));
+            MML_HIP(hipMemcpyAsync(b + big.vxyz, velo_xyz + 3 * (size_t)vo[0], sizeof(float) * 3 * nv, hipMemcpyHostToDevice, s));
+            MML_HIP(hipMemcpyAsync(d_lxyz, livox_xyz + 3 * (size_t)lo[0], sizeof(float) * 3 * nl, hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(k_tofs_tf, dim3(bx_v, by), dim3(256), 0, s, d_tab, reinterpret_cast<const float*>(b + big.vxyz), d_tf, d_v4);
+            hipLaunchKernelGGL(k_tofs_box, dim3(bx_v < (unsigned)TOFS_BOX_BLOCKS ? bx_v : (unsigned)TOFS_BOX_BLOCKS, by), dim3(256), 0, s, d_tab, d_v4,
+                               reinterpret_cast<float*>(g + io.box));
+            MML_HIP(hipGetLastError());
+            MML_HIP(hipMemcpyAsync(h + io.box, g + io.box, sizeof(float) * 6 * (size_t)n, hipMemcpyDeviceToHost, s));
+            MML_HIP(hipStreamSynchronize(s));
+        }
+        // every problem's cell and dims in one pass; its cell_start array follows the previous problem's in the pool
+        size_t cell_at = 0;
+        int max_cells = 0;
+        for (int i = 0; i < n; ++i) {
+            TofsProb& P = h_tab[i];
+            if (P.n_velo == 0) continue;
+            tofs_choose_grid(h_box + 6 * i, P.n_velo, P.g);
+            P.g.m = P.n_velo;
+            P.g.pts = d_pts + P.v_base;
+            P.g.cell_start = reinterpret_cast<int*>(b + big.cells) + cell_at;
+            cell_at += (size_t)P.g.ncell + 1;
+            max_cells = P.g.ncell > max_cells ? P.g.ncell : max_cells;
+        }
+        {   // host synchronisation 2 of 2: the results
+            MmlStageScope t(ctx, "tofs_search");
+            MML_HIP(hipMemcpyAsync(g + io.tab, h + io.tab, sizeof(TofsProb) * (size_t)n, hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(k_tofs_keys, dim3(bx_v, by), dim3(256), 0, s, d_tab, d_v4, d_keys, d_vals);
+            // ONE stable sort over all Velodyne points; with one problem the high word is zero and the cell bits are enough
+            const int end_bit = n == 1 ? bits_for(max_cells) : 32 + bits_for(n);
+            size_t need = 0;
+            MML_HIP(rocprim::radix_sort_pairs(nullptr, need, d_keys, d_keys2, d_vals, d_vals2, nv, 0, end_bit, s));
+            if (need > sort_bytes) return mml_refuse(ctx, MML_ERR_HIP, "%s: the sort asks for %zu bytes of scratch, %zu were reserved", who, need, sort_bytes);
+            MML_HIP(rocprim::radix_sort_pairs(b + big.sort, need, d_keys, d_keys2, d_vals, d_vals2, nv, 0, end_bit, s));
+            hipLaunchKernelGGL(k_tofs_gather, dim3(bx_v, by), dim3(256), 0, s, d_tab, d_v4, d_vals2, d_pts);
+            hipLaunchKernelGGL(k_tofs_cell_start, dim3((unsigned)((max_cells + 1 + 255) / 256), by), dim3(256), 0, s, d_tab, d_keys2);
+            hipLaunchKernelGGL(k_tofs_nn1, dim3((unsigned)((max_l + 255) / 256), by), dim3(256), 0, s, d_tab, d_lxyz, d_nn);
+            if (n_win > 0) {
+                hipLaunchKernelGGL(k_tofs_window_err, dim3((unsigned)((n_win + 63) / 64)), dim3(64), 0, s, d_tab, n,
+                                   reinterpret_cast<const long long*>(g + io.woff), d_lxyz, d_nn, res, sliced, d_err);
+                hipLaunchKernelGGL(k_tofs_best, dim3(by), dim3(256), 0, s, d_tab, d_err, reinterpret_cast<TofsBest*>(g + io.best));
+                MML_HIP(hipMemcpyAsync(h + io.best, g + io.best, sizeof(TofsBest) * (size_t)n, hipMemcpyDeviceToHost, s));
+                if (window_error) MML_HIP(hipMemcpyAsync(h + io.err, g + io.err, sizeof(double) * n_win, hipMemcpyDeviceToHost, s));
+            }
+            MML_HIP(hipGetLastError());
+            if (nn_d2) MML_HIP(hipMemcpyAsync(nn_d2 + lo[0], d_nn, sizeof(float) * nl, hipMemcpyDeviceToHost, s));
+            MML_HIP(hipStreamSynchronize(s));
+        }
+        if (n_win > 0) {
+            memcpy(best.data(), h + io.best, sizeof(TofsBest) * (size_t)n);
+            h_err = reinterpret_cast<const double*>(h + io.err);
+        }
+    }
+    long long e_base = 0;
+    for (int i = 0; i < n; ++i) {
+        n_windows[i] = nwin[i];
+        best_window[i] = best[i].best;
+        lowest_error[i] = best[i].lowest;
+        if (window_error && h_err && nwin[i] > 0) {  // at most the room the caller gave this problem
+            const long room = wo[i + 1] - wo[i];
+            const long k = room < (long)nwin[i] ? room : (long)nwin[i];
+            if (k > 0) memcpy(window_error + wo[i], h_err + e_base, sizeof(double) * (size_t)k);
+        }
+        e_base += nwin[i];
+    }
+    return MML_OK;
+}
+
+}  // namespace
+
+extern "C" int mml_time_offset_plan(int n, const int* velo_offsets, const int* livox_offsets, int search_resolution, int sliced_points,
+                                    int max_map_points, int* n_windows, int* bad_problem) {
+    int bad = -1;
+    const int why = tofs_plan(n, velo_offsets, livox_offsets, search_resolution, sliced_points, max_map_points, n_windows, &bad);
+    if (bad_problem) *bad_problem = bad;
+    return tofs_code(why);
+}
+
+extern "C" int mml_time_offset_search_batch(mml_ctx* ctx, int n, const float* velo_xyz, const int* velo_offsets, const float* tf,
+                                            const float* livox_xyz, const int* livox_offsets, int search_resolution, int sliced_points,
+                                            float* nn_d2, double* window_error, const long* window_offsets, int* n_windows, int* best_window,
+                                            double* lowest_error) {
+    if (!ctx) return MML_ERR_INVALID;
+    return tofs_run(ctx, "mml_time_offset_search_batch", n, velo_xyz, velo_offsets, tf, livox_xyz, livox_offsets, search_resolution, sliced_points,
+                    nn_d2, window_error, window_offsets, n_windows, best_window, lowest_error);
+}
+
+extern "C" int mml_time_offset_search(mml_ctx* ctx, const float* velo_xyz, int n_velo, const float* tf, const float* livox_xyz, int n_livox,
+                                      int search_resolution, int sliced_points, float* nn_d2, double* window_error, int capacity, int* n_windows,
+                                      int* best_window, double* lowest_error) {
+    if (!ctx) return MML_ERR_INVALID;
+    MML_REQUIRE(n_velo >= 0 && n_livox >= 0 && (n_velo == 0 || velo_xyz) && (n_livox == 0 || livox_xyz), MML_ERR_INVALID,
+                "bad point buffers");
+    MML_REQUIRE(search_resolution >= 1 && sliced_points >= 1, MML_ERR_INVALID, "search_resolution / sliced_points must be >= 1");
+    MML_REQUIRE(n_windows && best_window && lowest_error, MML_ERR_INVALID, "null output");
+    MML_REQUIRE(n_velo <= ctx->MM, MML_ERR_CAPACITY, "Velodyne cloud exceeds max_map_points");
+    MML_REQUIRE(n_velo > 0 || n_livox == 0, MML_ERR_INVALID, "nearest-neighbour search in an empty cloud");
+    const int vo[2] = {0, n_velo}, lo[2] = {0, n_livox};
+    const long wo[2] = {0, capacity > 0 ? capacity : 0};
+    return tofs_run(ctx, "mml_time_offset_search", 1, velo_xyz, vo, tf, livox_xyz, lo, search_resolution, sliced_points, nn_d2, window_error, wo,
+                    n_windows, best_window, lowest_error);
+}

@@ -18,6 +18,7 @@
 #ifndef MMLOAM_ADAPTER_HPP
 #define MMLOAM_ADAPTER_HPP
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -773,6 +774,46 @@ inline TimeOffsetResult EstimateTimeOffsetCore(Context& ctx, const float* velo_f
                                             offset_search_sliced_points, nullptr, nullptr, 0, &r.n_windows, &r.best_window,
                                             &r.lowest_error),
           "mml_time_offset_search");
+    return r;
+}
+// EstimateTimeOffsetCore for a list of (Velodyne FOV cloud, merged Livox cloud) pairs in one device call
+// (mml_time_offset_search_batch): every queued velo_fov_vec entry against the merged Livox points, or the searches of a bag's
+// fast-rotation events replayed at once.  velo_fov[i] / livox[i]: packed x, y, z floats; velo_hori_tf: 16 floats used for every
+// pair, 16 per pair, or empty (no transform).  Result i is what EstimateTimeOffsetCore returns for pair i alone.
+inline std::vector<TimeOffsetResult> estimate_timeoffset_batch(Context& ctx, const std::vector<std::vector<float>>& velo_fov,
+                                                               const std::vector<std::vector<float>>& livox,
+                                                               const std::vector<float>& velo_hori_tf, int offset_search_resolution = 30,
+                                                               int offset_search_sliced_points = 12000) {
+    const size_t n = velo_fov.size();
+    if (livox.size() != n || !(velo_hori_tf.empty() || velo_hori_tf.size() == 16 || velo_hori_tf.size() == 16 * n))
+        throw std::runtime_error("estimate_timeoffset_batch: one Livox cloud per Velodyne cloud; 0, 16 or 16 n matrix entries");
+    std::vector<int> vo(n + 1, 0), lo(n + 1, 0);
+    for (size_t i = 0; i < n; ++i) {
+        if (velo_fov[i].size() % 3 || livox[i].size() % 3) throw std::runtime_error("estimate_timeoffset_batch: clouds are packed x, y, z");
+        vo[i + 1] = vo[i] + (int)(velo_fov[i].size() / 3);
+        lo[i + 1] = lo[i] + (int)(livox[i].size() / 3);
+    }
+    std::vector<float> v(3 * (size_t)vo[n] + 3), l(3 * (size_t)lo[n] + 3), tf;
+    for (size_t i = 0; i < n; ++i) {
+        std::copy(velo_fov[i].begin(), velo_fov[i].end(), v.begin() + 3 * (size_t)vo[i]);
+        std::copy(livox[i].begin(), livox[i].end(), l.begin() + 3 * (size_t)lo[i]);
+    }
+    if (velo_hori_tf.size() == 16 && n != 1)
+        for (size_t i = 0; i < n; ++i) tf.insert(tf.end(), velo_hori_tf.begin(), velo_hori_tf.end());
+    else
+        tf = velo_hori_tf;
+    std::vector<int> nwin(n ? n : 1, 0), best(n ? n : 1, -1);
+    std::vector<double> lowest(n ? n : 1, 1000000.0);
+    check(ctx.get(), mml_time_offset_search_batch(ctx.get(), (int)n, v.data(), vo.data(), tf.empty() ? nullptr : tf.data(), l.data(), lo.data(),
+                                                  offset_search_resolution, offset_search_sliced_points, nullptr, nullptr, nullptr, nwin.data(),
+                                                  best.data(), lowest.data()),
+          "mml_time_offset_search_batch");
+    std::vector<TimeOffsetResult> r(n);
+    for (size_t i = 0; i < n; ++i) {
+        r[i].n_windows = nwin[i];
+        r[i].best_window = best[i];
+        r[i].lowest_error = lowest[i];
+    }
     return r;
 }
 
