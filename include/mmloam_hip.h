@@ -200,6 +200,86 @@ int mml_time_offset_search_batch(mml_ctx* ctx, int n,
 int mml_time_offset_plan(int n, const int* velo_offsets, const int* livox_offsets, int search_resolution, int sliced_points,
                          int max_map_points, int* n_windows /* n, may be NULL */, int* bad_problem /* may be NULL */);
 
+/* ---- the aligner node's frame assembly: a Livox point stream cut into scan slots ----------------------------------------
+ * The steady-state work of unionLidarsAligner.cpp on the device.  A mml_livox_stream is the aligner's point queue
+ * (_hori_points_queue / _hori_points_stamp_queue) in device memory: a flat array of 20-byte records and a flat array of
+ * 64-bit stamps.  mml_livox_stream_push is transform_hori_timestamp (:736-763) for one message: hs is the time base of the
+ * first message pushed since creation or reset (_hori_start_stamp, :203-207) and point j gets the stamp
+ * S = (timebase - hs) + offset_time, in nanoseconds.  Points are counted absolutely over everything ever pushed: `front` is
+ * the queue's first point, `tail` one past its last.
+ * Push: one host-to-device copy and one kernel, asynchronous on the context's stream (the host buffer must stay valid until
+ * the next synchronising call); the wire form takes the 19-byte records of mml_scan_upload_wire and decodes them on the
+ * device.  MML_ERR_CAPACITY, changing nothing, when the live points (tail - front) plus n exceed capacity_points.  When the
+ * array's end is reached the live part moves to the front of a second array of the same size (one device-to-device copy on
+ * the stream, no host synchronisation; the two arrays never overlap), so a stream holds 56 bytes per point of capacity, plus
+ * 19 for the wire staging once push_wire has been used.
+ * TIME ORDER.  The frame cut below needs hs + S[i] >= hs + S[i-1] for every point, across messages too (the reference's own
+ * comment at :738 intends that; what it does with unordered stamps depends on the order of its walk and is not reproduced).
+ * The push kernel counts the violations (`disorder`); mml_union_assemble refuses a stream that has any.
+ * A stream belongs to its context and must be destroyed before it.  mml_livox_stream_reset empties it and forgets hs and
+ * the violations. */
+typedef struct mml_livox_stream mml_livox_stream;
+int  mml_livox_stream_create(mml_ctx* ctx, long capacity_points, mml_livox_stream** out);
+void mml_livox_stream_destroy(mml_livox_stream* s);
+int  mml_livox_stream_reset(mml_livox_stream* s);
+int  mml_livox_stream_push(mml_livox_stream* s, uint64_t timebase, const mml_livox_point* pts, int n);
+int  mml_livox_stream_push_wire(mml_livox_stream* s, uint64_t timebase, const uint8_t* wire, int n);
+typedef struct { uint64_t start_stamp; long front, tail; long disorder; } mml_livox_stream_state;
+/* hs (0 before the first push), front, tail and the violations counted so far; synchronises the context's stream. */
+int  mml_livox_stream_state_get(mml_livox_stream* s, mml_livox_stream_state* out);
+
+/* pub_horipoints_given_stamp (:766-868) and the union_cloud assembly of :343-364 for `count` consecutive Velodyne frames in
+ * one call.  Frame i is [stamps[i], stamps[i+1]) in absolute nanoseconds (the Velodyne header stamps, :343-344) and fills
+ * slot first_slot + i:
+ *   Velodyne part: rows velo_offsets[i] .. velo_offsets[i+1]-1 of velo_xyzi (x, y, z, intensity floats) through
+ *     pcl::transformPointCloud with tf (row-major 4 x 4 floats, _velo_hori_tf_matrix, :352; NULL: copied), in float,
+ *     t0 * x + t1 * y + t2 * z + t3 summed left to right, the intensity carried;
+ *   Livox part: the points [begin, end) of the stream, x, y, z, reflectivity, tag, line unchanged, _pad = 0 and
+ *     offset_time = (uint32)(hs + S[k] - stamps[i]), the truncating assignment of :823.
+ * With q the front and A[k] = hs + S[k]:  q == tail: EMPTY (:769-773).  A[q] >= start: begin = q and the gate is A[q];
+ * otherwise the walk of :789-800 ends one past its first match j (the first point at or after q with A[j] >= start):
+ * begin = j + 1 and the gate is A[j]; NOT_REACHED when there is no such j.  The gate, not the stamp of point `begin`, decides
+ * whether `begin` goes out (:811); after it k = begin + 1 ... goes out while k < tail and A[k] < end.  OK moves the front to
+ * max(q, end - 100) (:862-863); every status but OK and OVERFLOW leaves it.
+ * Where the reference is undefined this library defines: a gate at or after `end`, or begin == tail, emits nothing (the
+ * reference then reads front() of an empty vector, :842): NO_POINTS; the read of the stamp one past the last point (:837) ends
+ * the loop; the negative erase count of :862 for end - q < 100 erases nothing.  A frame of more than max_livox_points
+ * points is OVERFLOW: the slot gets no Livox point, n_livox reports the count that was needed, and the front moves as for OK,
+ * so that the frames after it are what they would have been.
+ * Rows of frames that emit nothing have n_livox = 0, front_after = q and begin = end = the `begin` above where it exists
+ * (NO_POINTS), else q.  A frame whose status is not OK still gets its Velodyne part, with zero Livox points.
+ * Afterwards every slot of the call is in the state mml_scan_upload leaves it in (device and host counts set, the extracted
+ * state invalidated), so mml_extract follows.  count frames in one call equal count calls of one frame, to the byte: slots,
+ * rows and the stream afterwards.
+ * Everything is checked before any device work and a refusal writes nothing: MML_ERR_INVALID for a slot range outside the
+ * context, count outside 1 .. MML_UNION_BATCH_MAX, a NULL stream / stamps / velo_offsets / out (or velo_xyzi with rows to
+ * copy), a stream of another context, decreasing stamps or velo_offsets or a negative velo_offsets[0]; MML_ERR_CAPACITY for
+ * a frame with more than max_velo_points Velodyne rows.  MML_ERR_STATE, from the call's one read-back, for a stream with
+ * time-order violations: the kernels have then written neither slots nor counts, and the rows are not written either.
+ * Host synchronisations: ONE whatever count is -- the read-back of the count rows together with the violation counter,
+ * after which the host advances its copy of the front.  Two kernel launches per call whatever count is, which profiling shows
+ * as one launch each of the stages "union_plan" (count + 1 binary searches over the live stamps, then the front's
+ * recurrence by one lane out of LDS, the rows and the slots' counts) and "union_gather" (the Livox records as a dword
+ * stream, the Velodyne transform).  The context keeps one grow-only staging block (16 bytes per Velodyne row of the largest
+ * call, 56 per frame), released by mml_destroy. */
+typedef struct { int status; int n_livox; long begin, end; long front_after; } mml_union_frame;
+/* status: 0 OK, 1 EMPTY, 2 NOT_REACHED, 3 NO_POINTS, 4 OVERFLOW */
+#define MML_UNION_BATCH_MAX 65535   /* frames per call: the frame index is a grid's y dimension */
+int mml_union_assemble(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int count,
+                       const uint64_t* stamps /* count + 1: frame i = [stamps[i], stamps[i+1]) */,
+                       const float* velo_xyzi, const int* velo_offsets /* count + 1 */,
+                       const float* tf /* 16 or NULL */, mml_union_frame* out /* count */);
+/* Host only, no context: the rows mml_union_assemble returns for a stream whose stamps are the host array S, indexed
+ * absolutely (S[front] .. S[tail-1] are read).  MML_ERR_INVALID for count outside 1 .. MML_UNION_BATCH_MAX, a NULL pointer,
+ * front < 0 or tail < front, decreasing stamps; MML_ERR_STATE for a time-order violation in [front, tail). */
+int mml_union_plan(const uint64_t* S, long front, long tail, uint64_t hs, int count, const uint64_t* stamps,
+                   int max_livox_points, mml_union_frame* out);
+/* Test hook like mml_libm_f32: a slot's raw input as it stands -- what the upload entry points or mml_union_assemble put
+ * there: n_velo rows of x, y, z, intensity and n_livox records.  Either buffer may be NULL with capacity 0 to query the
+ * counts; MML_ERR_CAPACITY when a capacity is below its count.  Synchronises. */
+int mml_scan_raw_download(mml_ctx* ctx, int slot, float* velo_xyzi, int cap_velo, mml_livox_point* livox, int cap_livox,
+                          int* n_velo, int* n_livox);
+
 /* ---- SURVEY section 8(f) rank 4 (the other part): the per-frame GICP extrinsic refresh ---------------------------------
  * icp_ext_matching (unionFeatureExtract.cpp:74-123): pcl::GeneralizedIterativeClosestPoint with setMaximumIterations(10),
  * setTransformationEpsilon(1e-6), PCL defaults otherwise, identity guess -- the published PCL 1.8.1 algorithm (20-NN

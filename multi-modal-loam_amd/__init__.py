@@ -31,9 +31,15 @@ LIO_BATCH_MAX = 1024     # MML_LIO_BATCH_MAX: segments per call of mml_lio_initi
 LIO_BATCH_MAX_FRAMES = 8  # MML_LIO_BATCH_MAX_FRAMES: frames per segment
 TOFS_BATCH_MAX = 65535    # MML_TOFS_BATCH_MAX: problems per call of mml_time_offset_search_batch
 GICP_BATCH_MAX = 65535    # MML_GICP_BATCH_MAX: problems / slots per call of mml_gicp_align_batch / mml_gicp_refresh_batch
+UNION_BATCH_MAX = 65535   # MML_UNION_BATCH_MAX: frames per call of mml_union_assemble
+UNION_OK, UNION_EMPTY, UNION_NOT_REACHED, UNION_NO_POINTS, UNION_OVERFLOW = 0, 1, 2, 3, 4   # mml_union_frame.status
 
 LIVOX_DTYPE = np.dtype([("offset_time", "<u4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4"),
                         ("reflectivity", "u1"), ("tag", "u1"), ("line", "u1"), ("_pad", "u1")])
+
+
+# mml_union_frame (C long: 8 bytes on the LP64 hosts ROCm runs on)
+UNION_FRAME_DTYPE = np.dtype([("status", "<i4"), ("n_livox", "<i4"), ("begin", "<i8"), ("end", "<i8"), ("front_after", "<i8")])
 
 
 class MmlError(RuntimeError):
@@ -247,6 +253,23 @@ def lib():
             L.mml_cloud_download_registered_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]
             L.mml_cloud_download_registered.restype = C.c_int
             L.mml_cloud_download_registered.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        if hasattr(L, "mml_union_assemble"):
+            L.mml_livox_stream_create.restype = C.c_int
+            L.mml_livox_stream_create.argtypes = [C.c_void_p, C.c_long, C.c_void_p]
+            L.mml_livox_stream_destroy.restype = None
+            L.mml_livox_stream_destroy.argtypes = [C.c_void_p]
+            L.mml_livox_stream_reset.argtypes = [C.c_void_p]
+            L.mml_livox_stream_push.restype = C.c_int
+            L.mml_livox_stream_push.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int]
+            L.mml_livox_stream_push_wire.restype = C.c_int
+            L.mml_livox_stream_push_wire.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int]
+            L.mml_livox_stream_state_get.argtypes = [C.c_void_p, C.c_void_p]
+            L.mml_union_assemble.restype = C.c_int
+            L.mml_union_assemble.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
+            L.mml_union_plan.restype = C.c_int
+            L.mml_union_plan.argtypes = [C.c_void_p, C.c_long, C.c_long, C.c_uint64, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+            L.mml_scan_raw_download.restype = C.c_int
+            L.mml_scan_raw_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -357,6 +380,76 @@ def time_offset_plan(velo_offsets, livox_offsets, search_resolution=30, sliced_p
     rc = lib().mml_time_offset_plan(C.c_int(n), _p(vo), _p(lo), C.c_int(search_resolution), C.c_int(sliced_points),
                                     C.c_int(max_map_points), _p(nwin), C.byref(bad))
     return rc, bad.value, nwin[:max(n, 0)]
+
+
+def union_plan(S, front, tail, hs, stamps, max_livox_points):
+    """mml_union_plan: the frame rows mml_union_assemble returns, on the host alone (no context, no device), for a stream whose
+    stamps are the array S indexed absolutely (S[front] .. S[tail - 1] are read).  stamps: count + 1 frame boundaries in absolute
+    nanoseconds.  Returns (code, rows UNION_FRAME_DTYPE[count]); the rows are filled only when code == MML_OK."""
+    Sa = np.ascontiguousarray(S, dtype=np.uint64)
+    st = np.ascontiguousarray(stamps, dtype=np.uint64)
+    count = len(st) - 1
+    if tail > len(Sa):
+        raise ValueError("tail = %d lies beyond the %d stamps given" % (tail, len(Sa)))
+    rows = np.zeros(max(count, 1), UNION_FRAME_DTYPE)
+    rc = lib().mml_union_plan(_p(Sa) if len(Sa) else None, C.c_long(front), C.c_long(tail), C.c_uint64(int(hs)), C.c_int(count), _p(st),
+                              C.c_int(max_livox_points), _p(rows))
+    return rc, rows[:max(count, 0)]
+
+
+class LivoxStreamState(C.Structure):
+    _fields_ = [("start_stamp", C.c_uint64), ("front", C.c_long), ("tail", C.c_long), ("disorder", C.c_long)]
+
+
+class LivoxStream:
+    """One mml_livox_stream: the aligner's Livox point queue in device memory (Context.livox_stream).  Close it before its context."""
+
+    def __init__(self, ctx, capacity):
+        self._ctx = ctx
+        self._h = C.c_void_p()
+        self._keep = []
+        ctx._ck(lib().mml_livox_stream_create(ctx._h, C.c_long(capacity), C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self._ctx, "_h", None):
+            lib().mml_livox_stream_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _held(self, a):
+        self._keep.append(a)   # host buffers must outlive the asynchronous copy
+        if len(self._keep) > 64:
+            self._ctx.synchronize()
+            self._keep = self._keep[-1:]
+
+    def push(self, timebase, points):
+        """One livox_ros_driver/CustomMsg: its timebase (ns) and its points (LIVOX_DTYPE)."""
+        l = np.ascontiguousarray(points)
+        assert l.dtype.itemsize == 20
+        self._held(l)
+        self._ctx._ck(lib().mml_livox_stream_push(self._h, C.c_uint64(int(timebase)), _p(l) if len(l) else None, C.c_int(len(l))))
+
+    def push_wire(self, timebase, wire, n):
+        """The same message with its points in wire form: the serialised CustomPoint array, 19 bytes per point."""
+        w = np.frombuffer(wire, dtype=np.uint8) if not isinstance(wire, np.ndarray) else np.ascontiguousarray(wire, dtype=np.uint8)
+        if len(w) < 19 * n:
+            raise ValueError("wire shorter than 19 * n bytes")
+        self._held(w)
+        self._ctx._ck(lib().mml_livox_stream_push_wire(self._h, C.c_uint64(int(timebase)), _p(w) if n else None, C.c_int(n)))
+
+    def state(self):
+        """dict(start_stamp, front, tail, disorder); synchronises."""
+        st = LivoxStreamState()
+        self._ctx._ck(lib().mml_livox_stream_state_get(self._h, C.byref(st)))
+        return {"start_stamp": int(st.start_stamp), "front": int(st.front), "tail": int(st.tail), "disorder": int(st.disorder)}
+
+    def reset(self):
+        self._ctx._ck(lib().mml_livox_stream_reset(self._h))
 
 
 class Context:
@@ -478,6 +571,39 @@ class Context:
                                                     C.c_int(sliced_points), _p(nn), _p(err), _p(wo), _p(nw), _p(best), _p(lowest)))
         return [{"nn_d2": nn[lo[i]:lo[i + 1]], "window_error": err[wo[i]:wo[i] + nw[i]], "best_window": int(best[i]),
                  "lowest_error": float(lowest[i])} for i in range(n)]
+
+    # ---- the aligner node's frame assembly (unionLidarsAligner.cpp:343-364, :736-868) ----
+    def livox_stream(self, capacity):
+        """A LivoxStream of `capacity` points on this context."""
+        return LivoxStream(self, capacity)
+
+    def union_assemble(self, stream, first_slot, stamps, velo_list, tf=None):
+        """mml_union_assemble: frame i = [stamps[i], stamps[i + 1]) (absolute ns) is cut out of `stream` into slot first_slot + i
+        together with velo_list[i] (n x 4 float32: x, y, z, intensity) transformed by tf (4 x 4, None: copied).  Returns the
+        frames' rows (UNION_FRAME_DTYPE)."""
+        st = np.ascontiguousarray(stamps, dtype=np.uint64)
+        count = len(st) - 1
+        if len(velo_list) != count:
+            raise ValueError("%d Velodyne clouds for %d frames" % (len(velo_list), count))
+        vs = [_f32(v).reshape(-1, 4) for v in velo_list]
+        vo = np.zeros(count + 1, np.int32)
+        vo[1:] = np.cumsum([len(v) for v in vs])
+        velo = np.ascontiguousarray(np.concatenate(vs + [np.zeros((0, 4), np.float32)]))
+        t = np.ascontiguousarray(np.asarray(tf, np.float32).reshape(16)) if tf is not None else None
+        rows = np.zeros(max(count, 1), UNION_FRAME_DTYPE)
+        self._ck(lib().mml_union_assemble(self._h, stream._h, C.c_int(first_slot), C.c_int(count), _p(st),
+                                          _p(velo) if len(velo) else None, _p(vo), _p(t), _p(rows)))
+        return rows[:count]
+
+    def scan_raw_download(self, slot):
+        """mml_scan_raw_download: the slot's raw input as it stands, (velo n x 4 float32, livox LIVOX_DTYPE)."""
+        nv, nl = C.c_int(0), C.c_int(0)
+        self._ck(lib().mml_scan_raw_download(self._h, C.c_int(slot), None, C.c_int(0), None, C.c_int(0), C.byref(nv), C.byref(nl)))
+        v = np.zeros((max(nv.value, 1), 4), np.float32)
+        l = np.zeros(max(nl.value, 1), LIVOX_DTYPE)
+        self._ck(lib().mml_scan_raw_download(self._h, C.c_int(slot), _p(v), C.c_int(nv.value), _p(l), C.c_int(nl.value),
+                                             C.byref(nv), C.byref(nl)))
+        return v[:nv.value], l[:nl.value]
 
     def scan_download_pointxyzinormal(self, slot):
         """The fused labelled cloud as 48-byte PointXYZINormal records (the velo_combine / livox_combine payload)."""

@@ -119,6 +119,7 @@ void mml_destroy(mml_ctx* ctx) {
     mml_lio_init_release(ctx);
     mml_gicp_release(ctx);
     mml_time_offset_release(ctx);
+    mml_union_release(ctx);
     void* ptrs[] = {ctx->wstate, ctx->wrec, ctx->waux, ctx->hard_knn, ctx->d_und, ctx->d_und_par, ctx->crop_cnt, ctx->velo_in,  ctx->livox_in, ctx->d_n_in,   ctx->raw_line, ctx->raw_ori,  ctx->ln_pts,
                     ctx->ln_gidx, ctx->ln_rel, ctx->line_start, ctx->line_len, ctx->seg_cum, ctx->seg_pos, ctx->seg_n, ctx->seg_flat, ctx->seg_flat_n, ctx->op_agg, ctx->seg_rs, ctx->seg_rw, ctx->ln_curv, ctx->ln_refl,  ctx->ln_attr,
                     ctx->sel_scratch, ctx->blk_cnt, ctx->assign_aux, ctx->brk_queue, ctx->brk_cnt, ctx->redo_queue, ctx->st_exit, ctx->vx_big, ctx->sel_done, ctx->sel_list, ctx->sel_list_cnt,
@@ -397,6 +398,34 @@ int mml_scan_upload_batch(mml_ctx* ctx, int first_slot, int count, const float* 
     }
     MML_HIP(hipEventRecord(u.done, cs));
     ctx->uploads.push_back(u);
+    return MML_OK;
+}
+
+// The aligner's frame assembly (livox_stream.hip).  Every refusal for an argument comes before the slots are touched.
+int mml_union_assemble(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int count, const uint64_t* stamps, const float* velo_xyzi,
+                       const int* velo_offsets, const float* tf, mml_union_frame* out) {
+    if (!ctx) return MML_ERR_INVALID;
+    const int rc = mml_union_check(ctx, s, first_slot, count, stamps, velo_xyzi, velo_offsets, out);
+    if (rc != MML_OK) return rc;
+    CHECK_SLOTS(first_slot, count);
+    return mml_union_run(ctx, s, first_slot, count, stamps, velo_xyzi, velo_offsets, tf, out);
+}
+
+int mml_scan_raw_download(mml_ctx* ctx, int slot, float* velo_xyzi, int cap_velo, mml_livox_point* livox, int cap_livox, int* n_velo,
+                          int* n_livox) {
+    CHECK_SLOTS(slot, 1);
+    MML_REQUIRE(n_velo && n_livox, MML_ERR_INVALID, "null count outputs");
+    const int nv = ctx->h_n_in[2 * slot], nl = ctx->h_n_in[2 * slot + 1];
+    *n_velo = nv;
+    *n_livox = nl;
+    MML_REQUIRE((!velo_xyzi || cap_velo >= nv) && (!livox || cap_livox >= nl), MML_ERR_CAPACITY, "download capacity too small");
+    if (velo_xyzi && nv)
+        MML_HIP(hipMemcpyAsync(velo_xyzi, ctx->velo_in + (size_t)slot * ctx->NV, sizeof(float4) * (size_t)nv, hipMemcpyDeviceToHost,
+                               MML_STREAM(ctx)));
+    if (livox && nl)
+        MML_HIP(hipMemcpyAsync(livox, ctx->livox_in + (size_t)slot * ctx->NL, sizeof(mml_livox_point) * (size_t)nl, hipMemcpyDeviceToHost,
+                               MML_STREAM(ctx)));
+    MML_HIP(hipStreamSynchronize(MML_STREAM(ctx)));
     return MML_OK;
 }
 

@@ -71,6 +71,7 @@ struct MmlPreintDev;  // imu_preint.hip: buffers of mml_imu_preintegrate_batch
 struct MmlLioDev;     // lio_init_batch.hip: the block of mml_lio_initialize_batch
 struct MmlGicpDev;    // gicp.hip: the blocks of the GICP alignments (single and batch calls)
 struct MmlTofsDev;    // time_offset.hip: the blocks of the time-offset searches (single and batch calls)
+struct MmlUnionDev;   // livox_stream.hip: the staging blocks of mml_union_assemble
 
 struct mml_ctx {
     mml_config cfg;
@@ -80,6 +81,7 @@ struct mml_ctx {
     MmlLioDev* lio = nullptr;
     MmlGicpDev* gicp = nullptr;
     MmlTofsDev* tofs = nullptr;
+    MmlUnionDev* uni = nullptr;
     // frame-parallel window solve (solve.hip): one state machine copy, 4 counters and two record buffers per slot
     void* wstate = nullptr;
     double* wrec = nullptr;
@@ -397,6 +399,12 @@ void mml_imu_preint_release(mml_ctx* ctx);
 void mml_lio_init_release(mml_ctx* ctx);
 void mml_gicp_release(mml_ctx* ctx);
 void mml_time_offset_release(mml_ctx* ctx);
+void mml_union_release(mml_ctx* ctx);
+// mml_union_assemble (livox_stream.hip): the host-only checks, then -- after the entry point's slot checks -- the device part
+int mml_union_check(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int count, const uint64_t* stamps, const float* velo_xyzi,
+                    const int* velo_offsets, mml_union_frame* out);
+int mml_union_run(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int count, const uint64_t* stamps, const float* velo_xyzi,
+                  const int* velo_offsets, const float* tf, mml_union_frame* out);
 int mml_launch_detect_line(mml_ctx* ctx, int n, uint16_t* d_final);
 int mml_launch_raw_lines(mml_ctx* ctx, int first, int count);  // raw_line[] of the slots (ring / line id per raw point), for the GICP refresh
 int mml_launch_linearize(mml_ctx* ctx, int slot, const double* d_x, const double* d_Tbl, double w_tan,

@@ -817,6 +817,71 @@ inline std::vector<TimeOffsetResult> estimate_timeoffset_batch(Context& ctx, con
     return r;
 }
 
+// ---- the aligner node's point queue (unionLidarsAligner.cpp: _hori_points_queue / _hori_points_stamp_queue) on the device -------
+// transform_hori_timestamp (:736-763) pushes the queued messages; pub_horipoints_given_stamp (:766-868) cuts one Velodyne frame
+// interval out of the queue and, where the reference publishes a union_cloud (:343-364), fills a scan slot: the Livox points with
+// their rewritten offset_time and the Velodyne cloud transformed by _velo_hori_tf_matrix.  The return value is the reference's
+// bool; last_frame() tells why a frame came back false (mml_union_frame.status; the cases the reference leaves undefined are
+// defined in include/mmloam_hip.h).  mml_extract on the slot follows, as after mml_scan_upload.  Destroy before the Context.
+struct LivoxMsg {  // what the queue needs of a livox_ros_driver/CustomMsg: msg.timebase, msg.points.data(), msg.points.size()
+    uint64_t timebase = 0;
+    const mml_livox_point* points = nullptr;
+    int point_num = 0;
+};
+class LivoxPointQueue {
+   public:
+    LivoxPointQueue(Context& ctx, long capacity_points) : ctx_(ctx) {
+        check(ctx.get(), mml_livox_stream_create(ctx.get(), capacity_points, &s_), "mml_livox_stream_create");
+    }
+    ~LivoxPointQueue() { mml_livox_stream_destroy(s_); }
+    LivoxPointQueue(const LivoxPointQueue&) = delete;
+    LivoxPointQueue& operator=(const LivoxPointQueue&) = delete;
+    mml_livox_stream* get() const { return s_; }
+
+    // :736-763.  The points must stay valid until the next synchronising call (pub_horipoints_given_stamp is one).
+    void transform_hori_timestamp(const std::vector<LivoxMsg>& hori_msg_vec) {
+        for (const LivoxMsg& m : hori_msg_vec)
+            check(ctx_.get(), mml_livox_stream_push(s_, m.timebase, m.points, m.point_num), "mml_livox_stream_push");
+    }
+    // :766-868 with :350-352: one frame into `slot`.  velo_xyzi: n_velo x (x, y, z, intensity); velo_hori_tf: 16 floats or nullptr.
+    bool pub_horipoints_given_stamp(uint64_t velo_start_stamp, uint64_t velo_end_stamp, const float* velo_xyzi, int n_velo,
+                                    const float* velo_hori_tf, int slot) {
+        const uint64_t stamps[2] = {velo_start_stamp, velo_end_stamp};
+        const int vo[2] = {0, n_velo};
+        frames_.resize(1);
+        check(ctx_.get(), mml_union_assemble(ctx_.get(), s_, slot, 1, stamps, velo_xyzi, vo, velo_hori_tf, frames_.data()), "mml_union_assemble");
+        return frames_[0].status == 0;
+    }
+    // count frames in one device call: frame i = [stamps[i], stamps[i + 1]) with rows velo_offsets[i] .. velo_offsets[i + 1] - 1 of
+    // velo_xyzi into slot first_slot + i.  Returns the reference's bool per frame.
+    std::vector<bool> pub_horipoints_given_stamp(const std::vector<uint64_t>& stamps, const float* velo_xyzi, const std::vector<int>& velo_offsets,
+                                                 const float* velo_hori_tf, int first_slot) {
+        if (stamps.size() < 2 || velo_offsets.size() != stamps.size())
+            throw std::runtime_error("pub_horipoints_given_stamp: count + 1 stamps and count + 1 offsets");
+        const int count = (int)stamps.size() - 1;
+        frames_.resize((size_t)count);
+        check(ctx_.get(), mml_union_assemble(ctx_.get(), s_, first_slot, count, stamps.data(), velo_xyzi, velo_offsets.data(), velo_hori_tf,
+                                             frames_.data()),
+              "mml_union_assemble");
+        std::vector<bool> ok((size_t)count);
+        for (int i = 0; i < count; ++i) ok[(size_t)i] = frames_[(size_t)i].status == 0;
+        return ok;
+    }
+    const std::vector<mml_union_frame>& last_frames() const { return frames_; }
+    const mml_union_frame& last_frame() const { return frames_.back(); }
+    mml_livox_stream_state state() {
+        mml_livox_stream_state st;
+        check(ctx_.get(), mml_livox_stream_state_get(s_, &st), "mml_livox_stream_state_get");
+        return st;
+    }
+    void reset() { check(ctx_.get(), mml_livox_stream_reset(s_), "mml_livox_stream_reset"); }
+
+   private:
+    Context& ctx_;
+    mml_livox_stream* s_ = nullptr;
+    std::vector<mml_union_frame> frames_;
+};
+
 // ---- IMUIntegrator (IMUIntegrator.h / IMUIntegrator.cpp) over the caller's messages ----------------------------------------
 // A message is 7 doubles: angular_velocity xyz, linear_acceleration xyz (units of g, as the Livox IMU reports them), dt to the
 // previous message (the stamp difference the reference forms from lastTime, :95-97, :122).  Reset() keeps the messages, as
