@@ -1,6 +1,7 @@
 // capi.hip -- the C-ABI of libmmloam_hip.so (include/mmloam_hip.h): context, buffers, call sequencing.
-// No compute lives here; every entry point validates, stages small parameter blocks through a pinned ring and
-// enqueues the kernels of feature.hip / undistort_voxel.hip / map_assoc.hip / solve.hip on the ctx stream.
+// Every entry point validates, stages small parameter blocks through a pinned ring and enqueues the kernels of feature.hip /
+// undistort_voxel.hip / map_assoc.hip / solve.hip on the ctx stream.  The only compute that lives here is the kernels of the
+// wire decoders, the fused-cloud downloads, the slot digest and the two device probes (copy bandwidth, issue rate).
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
@@ -14,11 +15,6 @@
 int mml_launch_detect_line(mml_ctx* ctx, int n, uint16_t* d_final);
 
 namespace {
-
-template <typename T>
-hipError_t dalloc(T** p, size_t n) {
-    return hipMalloc(reinterpret_cast<void**>(p), sizeof(T) * (n ? n : 1));
-}
 
 constexpr int kPackMaxSlots = 16;  // calls of up to this many slots move their parameter blocks / results in one copy each way
 // pinned staging ring for small host<->device parameter blocks
@@ -120,25 +116,7 @@ void mml_destroy(mml_ctx* ctx) {
     mml_gicp_release(ctx);
     mml_time_offset_release(ctx);
     mml_union_release(ctx);
-    void* ptrs[] = {ctx->wstate, ctx->wrec, ctx->waux, ctx->hard_knn, ctx->d_und, ctx->d_und_par, ctx->crop_cnt, ctx->velo_in,  ctx->livox_in, ctx->d_n_in,   ctx->raw_line, ctx->raw_ori,  ctx->ln_pts,
-                    ctx->ln_gidx, ctx->ln_rel, ctx->line_start, ctx->line_len, ctx->seg_cum, ctx->seg_pos, ctx->seg_n, ctx->seg_flat, ctx->seg_flat_n, ctx->op_agg, ctx->seg_rs, ctx->seg_rw, ctx->ln_curv, ctx->ln_refl,  ctx->ln_attr,
-                    ctx->sel_scratch, ctx->blk_cnt, ctx->assign_aux, ctx->brk_queue, ctx->brk_cnt, ctx->redo_queue, ctx->st_exit, ctx->vx_big, ctx->sel_done, ctx->sel_list, ctx->sel_list_cnt,
-                    ctx->cb_n,     ctx->queue_off, ctx->slot_flags, ctx->ln_line,  ctx->ln_label,
-                    ctx->fu_info,  ctx->ft_xyz[0], ctx->ft_xyz[1], ctx->ft_n,   ctx->vx_keys,  ctx->vx_gidx, ctx->lf,
-                    ctx->pf,       ctx->assoc_stats, ctx->hard_list, ctx->work_off, ctx->grid[0].pts, ctx->grid[1].pts, ctx->grid[0].cell_start,
-                    ctx->grid[1].cell_start, ctx->map_tmp, ctx->map_keys, ctx->map_keys2, ctx->map_vals,
-                    ctx->map_vals2, ctx->sort_tmp, ctx->d_x, ctx->d_pose_in, ctx->d_result, ctx->d_summ, ctx->d_trace, ctx->d_rec,
-                    ctx->d_extr,   ctx->d_misc,   ctx->ggrid[0].pts, ctx->ggrid[1].pts, ctx->ggrid[0].cell_start,
-                    ctx->ggrid[1].cell_start, ctx->ggrid[0].tags, ctx->ggrid[1].tags, ctx->gmap_orig[0],
-                    ctx->gmap_orig[1], ctx->gtag_orig[0], ctx->gtag_orig[1], ctx->cube_cnt[0], ctx->cube_cnt[1],
-                    ctx->ring[0],  ctx->ring[1],  ctx->ring_cat, ctx->vox_flag, ctx->wire_stage, ctx->gs_pts[0], ctx->gs_pts[1], ctx->gs_tag[0],
-                    ctx->gs_tag[1], ctx->gs_pts2[0], ctx->gs_pts2[1], ctx->gs_tag2[0], ctx->gs_tag2[1], ctx->gp_pts[0],
-                    ctx->gp_pts[1], ctx->gs_work, ctx->gs_keys, ctx->seg_keys, ctx->seg_vals, ctx->seg_cat, ctx->seg_flag, ctx->seg_meta,
-                    ctx->seg_tmp[0], ctx->seg_tmp[1], ctx->seg_tmp[2], ctx->seg_tmp[3], ctx->seg_tmp[4], ctx->seg_tmp[5],
-                    ctx->seg_tmp[6], ctx->seg_tmp[7]};
-    for (void* p : ptrs)
-        if (p) hipFree(p);
-    if (ctx->h_stage) hipHostFree(ctx->h_stage);
+    ctx->release_memory();
     for (auto& pe : ctx->pending) {
         hipEventDestroy(pe.a);
         hipEventDestroy(pe.b);
@@ -204,7 +182,7 @@ int mml_create(const mml_config* cfg, int device, mml_ctx** out) {
     if ((e = hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking)) != hipSuccess) return fail(e, "hipStreamCreate");
     const size_t B = ctx->B, NV = ctx->NV, NL = ctx->NL, NT = ctx->NT, L = ctx->L, MF = ctx->MF, MM = ctx->MM;
 #define ALLOC(ptr, n)                                                  \
-    if ((e = dalloc(&(ptr), (n))) != hipSuccess) return fail(e, #ptr); \
+    if ((e = ctx->fixed.alloc(&(ptr), (n))) != hipSuccess) return fail(e, #ptr); \
     if ((e = hipMemsetAsync((ptr), 0, sizeof(*(ptr)) * ((n) ? (n) : 1), MML_STREAM(ctx))) != hipSuccess) return fail(e, #ptr)
     ALLOC(ctx->velo_in, B * NV);
     ALLOC(ctx->livox_in, B * NL);
@@ -282,9 +260,7 @@ int mml_create(const mml_config* cfg, int device, mml_ctx** out) {
     ALLOC(ctx->d_misc, 64);
 #undef ALLOC
     ctx->h_stage_doubles = kStageDoubles;
-    if ((e = hipHostMalloc(reinterpret_cast<void**>(&ctx->h_stage), sizeof(double) * (ctx->h_stage_doubles + 8),
-                           hipHostMallocDefault)) != hipSuccess)
-        return fail(e, "hipHostMalloc");
+    if ((e = ctx->fixed.alloc_pinned(&ctx->h_stage, ctx->h_stage_doubles + 8)) != hipSuccess) return fail(e, "ctx->h_stage");
     ctx->stage_cursor = 0;
     if (mml_feature_init(ctx) != MML_OK) return fail(hipErrorUnknown, "mml_feature_init");
     if ((e = hipStreamSynchronize(MML_STREAM(ctx))) != hipSuccess) return fail(e, "hipStreamSynchronize");
@@ -710,17 +686,7 @@ __global__ void __launch_bounds__(256) k_digest_stacks(DigestArgs A, unsigned lo
         o[9] = hp;
     }
 }
-int ensure_wire_stage(mml_ctx* ctx, size_t bytes) {
-    if (bytes <= ctx->wire_stage_bytes) return MML_OK;
-    MML_HIP(hipStreamSynchronize(MML_STREAM(ctx)));
-    void* old = ctx->wire_stage;
-    ctx->wire_stage = nullptr;  // (a failure below leaves no buffer rather than a freed one)
-    ctx->wire_stage_bytes = 0;
-    if (old) MML_HIP(hipFree(old));
-    MML_HIP(hipMalloc(&ctx->wire_stage, bytes));
-    ctx->wire_stage_bytes = bytes;
-    return MML_OK;
-}
+int ensure_wire_stage(mml_ctx* ctx, size_t bytes) { return ctx->wire_stage.reserve(ctx, bytes, MML_STREAM(ctx)); }
 }  // namespace
 
 namespace {
@@ -760,15 +726,15 @@ int upload_wire_impl(mml_ctx* ctx, int slot, const uint8_t* data, int n_points, 
         if (rc != MML_OK) return rc;
     }
     if (n_points) {
-        MML_HIP(hipMemcpyAsync(ctx->wire_stage, data, bytes, hipMemcpyHostToDevice, MML_STREAM(ctx)));
+        MML_HIP(hipMemcpyAsync(ctx->wire_stage.d, data, bytes, hipMemcpyHostToDevice, MML_STREAM(ctx)));
         hipLaunchKernelGGL(k_decode_pointcloud2, dim3((n_points + 255) / 256), dim3(256), 0, MML_STREAM(ctx),
-                           reinterpret_cast<const uint8_t*>(ctx->wire_stage), n_points, point_step, off_x, off_y, off_z,
+                           reinterpret_cast<const uint8_t*>(ctx->wire_stage.d), n_points, point_step, off_x, off_y, off_z,
                            off_intensity, ctx->velo_in + (size_t)slot * ctx->NV);
         MML_HIP(hipGetLastError());
     }
     // the Livox part: decoded from its wire form, or as in mml_scan_upload; the two counts travel as there
     if (n_livox && livox_wire) {
-        uint8_t* dst = reinterpret_cast<uint8_t*>(ctx->wire_stage) + loff;
+        uint8_t* dst = reinterpret_cast<uint8_t*>(ctx->wire_stage.d) + loff;
         MML_HIP(hipMemcpyAsync(dst, livox_wire, lbytes, hipMemcpyHostToDevice, MML_STREAM(ctx)));
         hipLaunchKernelGGL(k_decode_custompoints, dim3((n_livox + 255) / 256), dim3(256), 0, MML_STREAM(ctx), dst, n_livox,
                            ctx->livox_in + (size_t)slot * ctx->NL);
@@ -849,9 +815,9 @@ int mml_scan_download_pointxyzinormal(mml_ctx* ctx, int slot, uint8_t* out, int 
     rc = fused_view(ctx, slot, V);
     if (rc != MML_OK) return rc;
     hipLaunchKernelGGL(k_encode_xyzinormal, dim3((ctx->NT + 255) / 256), dim3(256), 0, MML_STREAM(ctx), V,
-                       reinterpret_cast<float*>(ctx->wire_stage));
+                       reinterpret_cast<float*>(ctx->wire_stage.d));
     MML_HIP(hipGetLastError());
-    MML_HIP(hipMemcpyAsync(out, ctx->wire_stage, bytes, hipMemcpyDeviceToHost, MML_STREAM(ctx)));
+    MML_HIP(hipMemcpyAsync(out, ctx->wire_stage.d, bytes, hipMemcpyDeviceToHost, MML_STREAM(ctx)));
     MML_HIP(hipStreamSynchronize(MML_STREAM(ctx)));
     return MML_OK;
 }
@@ -890,10 +856,10 @@ int mml_cloud_download_registered_batch(mml_ctx* ctx, int first_slot, int count,
     MML_HIP(hipMemcpyAsync(d_par, h_par, sizeof(double) * 17 * (size_t)count, hipMemcpyHostToDevice, MML_STREAM(ctx)));
     const SlotArrays A = slot_arrays(ctx, first_slot);
     hipLaunchKernelGGL(k_encode_registered, dim3((ctx->NT + 255) / 256, count), dim3(256), 0, MML_STREAM(ctx), A, d_par, count,
-                       reinterpret_cast<float4*>(ctx->wire_stage));
+                       reinterpret_cast<float4*>(ctx->wire_stage.d));
     MML_HIP(hipGetLastError());
     // synchronisation 2 of 2: the records
-    MML_HIP(hipMemcpyAsync(out, ctx->wire_stage, bytes, hipMemcpyDeviceToHost, MML_STREAM(ctx)));
+    MML_HIP(hipMemcpyAsync(out, ctx->wire_stage.d, bytes, hipMemcpyDeviceToHost, MML_STREAM(ctx)));
     MML_HIP(hipStreamSynchronize(MML_STREAM(ctx)));
     return MML_OK;
 }
@@ -911,9 +877,9 @@ int mml_cloud_upload(mml_ctx* ctx, int slot, const uint8_t* pointxyzinormal, int
     const size_t bytes = (size_t)n_points * 48;
     int rc = ensure_wire_stage(ctx, bytes ? bytes : 48);
     if (rc != MML_OK) return rc;
-    if (bytes) MML_HIP(hipMemcpyAsync(ctx->wire_stage, pointxyzinormal, bytes, hipMemcpyHostToDevice, MML_STREAM(ctx)));
+    if (bytes) MML_HIP(hipMemcpyAsync(ctx->wire_stage.d, pointxyzinormal, bytes, hipMemcpyHostToDevice, MML_STREAM(ctx)));
     ctx->und_pending[slot] = 0;  // (the cloud is replaced: nothing of the old one is left to finish)
-    rc = mml_launch_cloud_decode(ctx, slot, reinterpret_cast<const float*>(ctx->wire_stage), n_points, n_velo);
+    rc = mml_launch_cloud_decode(ctx, slot, reinterpret_cast<const float*>(ctx->wire_stage.d), n_points, n_velo);
     if (rc != MML_OK) return rc;
     // the staging buffer is reused by the next wire-format call and the host buffer belongs to the caller
     MML_HIP(hipStreamSynchronize(MML_STREAM(ctx)));
@@ -967,7 +933,7 @@ int mml_scan_download(mml_ctx* ctx, int slot, float* xyzi, float* reltime, uint8
     const size_t n16 = (n + 15) & ~size_t(15);
     rc = ensure_wire_stage(ctx, n16 * 22);
     if (rc != MML_OK) return rc;
-    uint8_t* st = reinterpret_cast<uint8_t*>(ctx->wire_stage);
+    uint8_t* st = reinterpret_cast<uint8_t*>(ctx->wire_stage.d);
     float4* s_xyzi = reinterpret_cast<float4*>(st);
     float* s_rel = reinterpret_cast<float*>(st + n16 * 16);
     uint8_t* s_line = st + n16 * 20;
@@ -992,9 +958,10 @@ int mml_slot_digest(mml_ctx* ctx, int first_slot, int count, uint64_t* out) {
     if (rc != MML_OK) return rc;
     rc = mml_cloud_settle(ctx, first_slot, count);
     if (rc != MML_OK) return rc;
-    unsigned long long* d = nullptr;
+    MmlTemp<unsigned long long> tmp;
     const size_t bytes = sizeof(unsigned long long) * MML_DIGEST_WORDS * (size_t)count;
-    MML_HIP(hipMalloc(reinterpret_cast<void**>(&d), bytes));
+    MML_HIP(tmp.alloc(MML_DIGEST_WORDS * (size_t)count));
+    unsigned long long* d = tmp.d;
     hipError_t e = hipMemsetAsync(d, 0, bytes, MML_STREAM(ctx));
     DigestArgs A;
     static_cast<SlotArrays&>(A) = slot_arrays(ctx, first_slot);
@@ -1017,7 +984,6 @@ int mml_slot_digest(mml_ctx* ctx, int first_slot, int count, uint64_t* out) {
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, MML_STREAM(ctx));
     if (e == hipSuccess) e = hipStreamSynchronize(MML_STREAM(ctx));
-    hipFree(d);
     if (e != hipSuccess) {
         ctx->err = std::string("mml_slot_digest: ") + hipGetErrorString(e);
         return MML_ERR_HIP;
@@ -1228,22 +1194,18 @@ int mml_knn5(mml_ctx* ctx, int kind, const float* q, int nq, float max_d2, int* 
     MML_REQUIRE(ctx->have_map[kind], MML_ERR_STATE, "mml_knn5 before mml_map_set_local");
     if (nq == 0) return MML_OK;
     MML_HIP(hipSetDevice(ctx->device));
-    float* d_q = nullptr;
-    int* d_idx = nullptr;
-    float* d_d2 = nullptr;
-    MML_HIP(hipMalloc(reinterpret_cast<void**>(&d_q), sizeof(float) * 3 * nq));
-    MML_HIP(hipMalloc(reinterpret_cast<void**>(&d_idx), sizeof(int) * 5 * nq));
-    MML_HIP(hipMalloc(reinterpret_cast<void**>(&d_d2), sizeof(float) * 5 * nq));
-    MML_HIP(hipMemcpyAsync(d_q, q, sizeof(float) * 3 * nq, hipMemcpyHostToDevice, MML_STREAM(ctx)));
-    int rc = mml_launch_knn5(ctx, kind, d_q, nq, max_d2, d_idx, d_d2);
+    MmlTemp<float> d_q, d_d2;
+    MmlTemp<int> d_idx;
+    MML_HIP(d_q.alloc(3 * (size_t)nq));
+    MML_HIP(d_idx.alloc(5 * (size_t)nq));
+    MML_HIP(d_d2.alloc(5 * (size_t)nq));
+    MML_HIP(hipMemcpyAsync(d_q.d, q, sizeof(float) * 3 * nq, hipMemcpyHostToDevice, MML_STREAM(ctx)));
+    int rc = mml_launch_knn5(ctx, kind, d_q.d, nq, max_d2, d_idx.d, d_d2.d);
     if (rc == MML_OK) {
-        hipMemcpyAsync(idx, d_idx, sizeof(int) * 5 * nq, hipMemcpyDeviceToHost, MML_STREAM(ctx));
-        hipMemcpyAsync(d2, d_d2, sizeof(float) * 5 * nq, hipMemcpyDeviceToHost, MML_STREAM(ctx));
+        hipMemcpyAsync(idx, d_idx.d, sizeof(int) * 5 * nq, hipMemcpyDeviceToHost, MML_STREAM(ctx));
+        hipMemcpyAsync(d2, d_d2.d, sizeof(float) * 5 * nq, hipMemcpyDeviceToHost, MML_STREAM(ctx));
     }
     hipError_t e = hipStreamSynchronize(MML_STREAM(ctx));
-    hipFree(d_q);
-    hipFree(d_idx);
-    hipFree(d_d2);
     if (e != hipSuccess) {
         ctx->err = std::string("mml_knn5: ") + hipGetErrorString(e);
         return MML_ERR_HIP;
@@ -1996,9 +1958,10 @@ extern "C" int mml_copy_bandwidth(mml_ctx* ctx, size_t bytes, int reps, double* 
     if (!ctx || !gbps || reps <= 0) return MML_ERR_INVALID;
     MML_HIP(hipSetDevice(ctx->device));
     size_t n = bytes / 16;
-    float4 *a = nullptr, *b = nullptr;
-    MML_HIP(hipMalloc(reinterpret_cast<void**>(&a), n * 16));
-    MML_HIP(hipMalloc(reinterpret_cast<void**>(&b), n * 16));
+    MmlTemp<float4> ta, tb;
+    MML_HIP(ta.alloc(n));
+    MML_HIP(tb.alloc(n));
+    float4 *a = ta.d, *b = tb.d;
     MML_HIP(hipMemsetAsync(a, 1, n * 16, MML_STREAM(ctx)));
     hipEvent_t e0, e1;
     hipEventCreate(&e0);
@@ -2025,8 +1988,6 @@ extern "C" int mml_copy_bandwidth(mml_ctx* ctx, size_t bytes, int reps, double* 
     }
     hipEventDestroy(e0);
     hipEventDestroy(e1);
-    hipFree(a);
-    hipFree(b);
     if (e != hipSuccess) {
         ctx->err = hipGetErrorString(e);
         return MML_ERR_HIP;
@@ -2064,8 +2025,9 @@ extern "C" int mml_issue_rate(mml_ctx* ctx, int kind, int reps, double* wave_ins
     if (!ctx || !wave_instr_per_s || reps <= 0 || kind < 0 || kind > 1) return MML_ERR_INVALID;
     MML_HIP(hipSetDevice(ctx->device));
     const int blocks = ctx->cus * 64;  // eight workgroups of four wavefronts per CU, eight rounds of them
-    float* d = nullptr;
-    MML_HIP(hipMalloc(reinterpret_cast<void**>(&d), sizeof(float) * 256 * (size_t)blocks));
+    MmlTemp<float> tmp;
+    MML_HIP(tmp.alloc(256 * (size_t)blocks));
+    float* d = tmp.d;
     hipEvent_t e0, e1;
     hipEventCreate(&e0);
     hipEventCreate(&e1);
@@ -2089,7 +2051,6 @@ extern "C" int mml_issue_rate(mml_ctx* ctx, int kind, int reps, double* wave_ins
     }
     hipEventDestroy(e0);
     hipEventDestroy(e1);
-    hipFree(d);
     if (e != hipSuccess) {
         ctx->err = hipGetErrorString(e);
         return MML_ERR_HIP;

@@ -3994,19 +3994,12 @@ extern "C" int mml_libm_f32(mml_ctx* ctx, const float* y, const float* x, long n
     if (n == 0) return MML_OK;
     int rc = mml_sync_all(ctx);
     if (rc != MML_OK) return rc;
-    float *dy = nullptr, *dx = nullptr, *d2 = nullptr, *d1 = nullptr;
-    auto release = [&]() {
-        if (dy) (void)hipFree(dy);
-        if (dx) (void)hipFree(dx);
-        if (d2) (void)hipFree(d2);
-        if (d1) (void)hipFree(d1);
-    };
+    MmlTemp<float> ty, tx, t2, t1;
     const size_t bytes = sizeof(float) * (size_t)n;
-    if (hipMalloc(&dy, bytes) != hipSuccess || hipMalloc(&dx, bytes) != hipSuccess ||
-        (out_atan2 && hipMalloc(&d2, bytes) != hipSuccess) || (out_atan && hipMalloc(&d1, bytes) != hipSuccess)) {
-        release();
+    if (ty.alloc((size_t)n) != hipSuccess || tx.alloc((size_t)n) != hipSuccess || (out_atan2 && t2.alloc((size_t)n) != hipSuccess) ||
+        (out_atan && t1.alloc((size_t)n) != hipSuccess))
         return MML_ERR_HIP;
-    }
+    float *dy = ty.d, *dx = tx.d, *d2 = t2.d, *d1 = t1.d;
     bool ok = hipMemcpy(dy, y, bytes, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice) == hipSuccess;
     if (ok) {
         hipLaunchKernelGGL(k_libm_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, MML_STREAM(ctx), dy, dx, n, d2, d1);
@@ -4014,7 +4007,6 @@ extern "C" int mml_libm_f32(mml_ctx* ctx, const float* y, const float* x, long n
     }
     if (ok && out_atan2) ok = hipMemcpy(out_atan2, d2, bytes, hipMemcpyDeviceToHost) == hipSuccess;
     if (ok && out_atan) ok = hipMemcpy(out_atan, d1, bytes, hipMemcpyDeviceToHost) == hipSuccess;
-    release();
     return ok ? MML_OK : MML_ERR_HIP;
 }
 

@@ -30,7 +30,7 @@
 //               the loss-free lidar record of frame 0 (frame_record), prior and IMU factor 1 (imu_whiten), the 30 x 30
 //               system, then the dense tail of marg_dense.h -- the routine the host function runs -- on one wavefront;
 //               bit-identical to the host.
-// Host side: the per-call buffers are MmlStaging pairs (mml_internal.h: device array + pinned twin, grow-only), refusals go
+// Host side: the per-call buffers are MmlStaging pairs (mml_mem.h: device array + pinned twin, grow-only), refusals go
 // through mml_refuse, and a prior crosses between handle, parameter block and ABI as one mml_prior.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -1069,9 +1069,10 @@ extern "C" int mml_marginalize_dense(mml_ctx* ctx, long n, const double* A, cons
     }
     int rc = mml_sync_all(ctx);
     if (rc != MML_OK) return rc;
-    double* d_buf = nullptr;  // A | b | J | r0
+    MmlTemp<double> tmp;  // A | b | J | r0
     const size_t nA = 900 * (size_t)n, nb = 30 * (size_t)n, nJ = 225 * (size_t)n, nr = 15 * (size_t)n;
-    bool ok = hipMalloc(reinterpret_cast<void**>(&d_buf), sizeof(double) * (nA + nb + nJ + nr)) == hipSuccess;
+    bool ok = tmp.alloc(nA + nb + nJ + nr) == hipSuccess;
+    double* d_buf = tmp.d;
     ok = ok && hipMemcpy(d_buf, A, sizeof(double) * nA, hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && hipMemcpy(d_buf + nA, b, sizeof(double) * nb, hipMemcpyHostToDevice) == hipSuccess;
     if (ok) {
@@ -1081,6 +1082,5 @@ extern "C" int mml_marginalize_dense(mml_ctx* ctx, long n, const double* A, cons
     }
     ok = ok && hipMemcpy(J, d_buf + nA + nb, sizeof(double) * nJ, hipMemcpyDeviceToHost) == hipSuccess;
     ok = ok && hipMemcpy(r0, d_buf + nA + nb + nJ, sizeof(double) * nr, hipMemcpyDeviceToHost) == hipSuccess;
-    if (d_buf) (void)hipFree(d_buf);
     return ok ? MML_OK : MML_ERR_HIP;
 }

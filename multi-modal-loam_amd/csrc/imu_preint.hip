@@ -3,7 +3,7 @@
 // runs k_imu_preintegrate, one workgroup of one wavefront per interval -- Jacobian, covariance and the per-sample blocks stay
 // in LDS for the whole chain over the samples (13.0 KB, so twelve intervals are resident on a CU) and are written once at the
 // end.  One upload (offsets | biases | samples from one pinned block), one launch, one read-back; the input block and the
-// output array are MmlStaging pairs (mml_internal.h), refusals go through mml_refuse.
+// output array are MmlStaging pairs (mml_mem.h), refusals go through mml_refuse.
 #include <hip/hip_runtime.h>
 #include <string.h>
 

@@ -8,7 +8,7 @@
 //   k_lio_preint      again over the marked frames, reading the new biases from the state the kernel before it wrote
 // -- between ONE upload (offsets | times | extrinsics | samples | marks | state, and the given pre-integrations, from one pinned
 // block) and ONE read-back (state | results | pre-integrations).  The host applies a segment's bytes unless its status is 3.
-// The block is an MmlStaging pair (mml_internal.h), refusals go through mml_refuse.
+// The block is an MmlStaging pair (mml_mem.h), refusals go through mml_refuse.
 #include <hip/hip_runtime.h>
 #include <string.h>
 

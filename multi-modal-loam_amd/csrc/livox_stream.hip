@@ -22,6 +22,7 @@ struct mml_livox_stream {
     unsigned long long* d_disorder = nullptr;  // time-order violations counted by the push kernels
     unsigned long long* h_disorder = nullptr;  // pinned
     uint8_t* wire = nullptr;                   // 19 * cap bytes, allocated by the first push_wire
+    MmlFixed mem;                              // owns all of the above
 };
 
 // What mml_union_assemble keeps on the context: the small tables (pinned twin) and the Velodyne rows on their way in.  Grow-only;
@@ -218,7 +219,7 @@ int stream_push(mml_livox_stream* s, const char* who, uint64_t timebase, const v
     if ((s->tail - s->front) + n > s->cap)
         return mml_refuse(ctx, MML_ERR_CAPACITY, "%s: %ld live points + %d exceed capacity_points = %ld", who, s->tail - s->front, n, s->cap);
     MML_HIP(hipSetDevice(ctx->device));
-    if (wire && n > 0 && !s->wire) MML_HIP(hipMalloc(reinterpret_cast<void**>(&s->wire), 19 * (size_t)s->cap));
+    if (wire && n > 0 && !s->wire) MML_HIP(s->mem.alloc(&s->wire, 19 * (size_t)s->cap));
     if (!s->have_hs) {  // :203-207, whatever the message holds
         s->hs = timebase;
         s->have_hs = true;
@@ -347,11 +348,11 @@ extern "C" int mml_livox_stream_create(mml_ctx* ctx, long capacity_points, mml_l
     s->cap = capacity_points;
     hipError_t e = hipSuccess;
     for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-        e = hipMalloc(reinterpret_cast<void**>(&s->rec[k]), 20 * (size_t)capacity_points);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->stamp[k]), sizeof(uint64_t) * (size_t)capacity_points);
+        e = s->mem.alloc(&s->rec[k], 5 * (size_t)capacity_points);
+        if (e == hipSuccess) e = s->mem.alloc(&s->stamp[k], (size_t)capacity_points);
     }
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->d_disorder), sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&s->h_disorder), sizeof(unsigned long long), hipHostMallocDefault);
+    if (e == hipSuccess) e = s->mem.alloc(&s->d_disorder, 1);
+    if (e == hipSuccess) e = s->mem.alloc_pinned(&s->h_disorder, 1);
     if (e == hipSuccess) e = hipMemsetAsync(s->d_disorder, 0, sizeof(unsigned long long), MML_STREAM(ctx));
     if (e != hipSuccess) {
         ctx->err = std::string("mml_livox_stream_create: ") + hipGetErrorString(e);
@@ -366,13 +367,7 @@ extern "C" void mml_livox_stream_destroy(mml_livox_stream* s) {
     if (!s) return;
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(MML_STREAM(s->ctx));
-    for (int k = 0; k < 2; ++k) {
-        if (s->rec[k]) (void)hipFree(s->rec[k]);
-        if (s->stamp[k]) (void)hipFree(s->stamp[k]);
-    }
-    if (s->wire) (void)hipFree(s->wire);
-    if (s->d_disorder) (void)hipFree(s->d_disorder);
-    if (s->h_disorder) (void)hipHostFree(s->h_disorder);
+    s->mem.release();
     delete s;
 }
 

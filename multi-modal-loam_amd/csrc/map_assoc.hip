@@ -1058,16 +1058,15 @@ extern "C" int mml_model_fit5(mml_ctx* ctx, int op, const void* in, long n, void
     if (n == 0) return MML_OK;
     int rc = mml_sync_all(ctx);
     if (rc != MML_OK) return rc;
-    void *d_in = nullptr, *d_out = nullptr;
-    bool ok = hipMalloc(&d_in, in_bytes[op] * (size_t)n) == hipSuccess && hipMalloc(&d_out, out_bytes[op] * (size_t)n) == hipSuccess;
+    MmlTemp<char> t_in, t_out;
+    bool ok = t_in.alloc(in_bytes[op] * (size_t)n) == hipSuccess && t_out.alloc(out_bytes[op] * (size_t)n) == hipSuccess;
+    void *d_in = t_in.d, *d_out = t_out.d;
     ok = ok && hipMemcpy(d_in, in, in_bytes[op] * (size_t)n, hipMemcpyHostToDevice) == hipSuccess;
     if (ok) {
         hipLaunchKernelGGL(k_model_fit5, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, MML_STREAM(ctx), op, (const void*)d_in, n, d_out);
         ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(MML_STREAM(ctx)) == hipSuccess;
     }
     ok = ok && hipMemcpy(out, d_out, out_bytes[op] * (size_t)n, hipMemcpyDeviceToHost) == hipSuccess;
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
     return ok ? MML_OK : MML_ERR_HIP;
 }
 
@@ -1129,12 +1128,9 @@ static int build_grid_into(mml_ctx* ctx, MmlGrid& g, float4* orig, const float* 
         size_t need = 0;
         MML_HIP(rocprim::radix_sort_pairs(nullptr, need, ctx->map_keys, ctx->map_keys2, ctx->map_vals, ctx->map_vals2,
                                           (size_t)m, 0, bits, s));
-        if (need > ctx->sort_tmp_bytes) {
-            if (ctx->sort_tmp) MML_HIP(hipFree(ctx->sort_tmp));
-            MML_HIP(hipMalloc(&ctx->sort_tmp, need));
-            ctx->sort_tmp_bytes = need;
-        }
-        MML_HIP(rocprim::radix_sort_pairs(ctx->sort_tmp, need, ctx->map_keys, ctx->map_keys2, ctx->map_vals,
+        const int rt = mml_sort_tmp(ctx, need);
+        if (rt != MML_OK) return rt;
+        MML_HIP(rocprim::radix_sort_pairs(ctx->sort_tmp.d, need, ctx->map_keys, ctx->map_keys2, ctx->map_vals,
                                           ctx->map_vals2, (size_t)m, 0, bits, s));
         int* d_occ = ctx->d_misc + 16;
         MML_HIP(hipMemsetAsync(d_occ, 0, sizeof(int), s));
@@ -1181,25 +1177,17 @@ int mml_build_grid_device(mml_ctx* ctx, int kind, int m) {
 // a12: the global map handed to Estimate() (Estimator.cpp:1170-1184) as one concatenated cloud with the cube index
 // (ToIndex) of every point.  The per-cube kd-trees become one grid whose points carry their cube as a tag.
 static int ensure_global_capacity(mml_ctx* ctx, int kind, int m) {
-    hipStream_t s = MML_STREAM(ctx);
     MmlGrid& g = ctx->ggrid[kind];
-    if (m > ctx->gmap_cap[kind] || !ctx->cube_cnt[kind]) {
-        MML_HIP(hipStreamSynchronize(s));
-        if (g.pts) hipFree(g.pts);
-        if (g.cell_start) hipFree(g.cell_start);
-        if (g.tags) hipFree(g.tags);
-        if (ctx->gmap_orig[kind]) hipFree(ctx->gmap_orig[kind]);
-        if (ctx->gtag_orig[kind]) hipFree(ctx->gtag_orig[kind]);
-        const size_t cap = (size_t)(m > 1024 ? m : 1024);
-        MML_HIP(hipMalloc(reinterpret_cast<void**>(&g.pts), sizeof(float4) * cap));
-        MML_HIP(hipMalloc(reinterpret_cast<void**>(&g.cell_start), sizeof(int) * (4 * (size_t)ctx->MM + 4096 + 2)));
-        MML_HIP(hipMalloc(reinterpret_cast<void**>(&g.tags), sizeof(uint16_t) * cap));
-        MML_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->gmap_orig[kind]), sizeof(float4) * cap));
-        MML_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->gtag_orig[kind]), sizeof(uint16_t) * cap));
-        if (!ctx->cube_cnt[kind]) MML_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->cube_cnt[kind]), sizeof(int) * 4851));
-        ctx->gmap_cap[kind] = (int)cap;
-    }
-    return MML_OK;
+    if (m <= ctx->gmap_cap[kind] && ctx->ggrid_mem[kind].present()) return MML_OK;
+    MML_HIP(hipStreamSynchronize(MML_STREAM(ctx)));
+    const size_t cap = (size_t)(m > 1024 ? m : 1024);
+    ctx->gmap_cap[kind] = 0;
+    // (the cube counts are rewritten by both callers, so they may move with the rest)
+    const int rc = ctx->ggrid_mem[kind].reserve(
+        ctx, {mml_part(g.pts, cap), mml_part(g.cell_start, 4 * (size_t)ctx->MM + 4096 + 2), mml_part(g.tags, cap),
+              mml_part(ctx->gmap_orig[kind], cap), mml_part(ctx->gtag_orig[kind], cap), mml_part(ctx->cube_cnt[kind], 4851)});
+    if (rc == MML_OK) ctx->gmap_cap[kind] = (int)cap;
+    return rc;
 }
 
 int mml_build_global_grid(mml_ctx* ctx, int kind, const float* h_xyz, const int* h_cube, int m, const int* cen) {

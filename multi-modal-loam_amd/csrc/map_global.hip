@@ -188,34 +188,20 @@ __global__ void k_cube_centroid(const float4* pts, const unsigned long long* key
     out_tag[dst] = (uint16_t)(key >> 40);
 }
 
-int ensure_tmp(mml_ctx* ctx, size_t need) {
-    if (need > ctx->sort_tmp_bytes) {
-        MML_HIP(hipStreamSynchronize(MML_STREAM(ctx)));
-        if (ctx->sort_tmp) MML_HIP(hipFree(ctx->sort_tmp));
-        MML_HIP(hipMalloc(&ctx->sort_tmp, need));
-        ctx->sort_tmp_bytes = need;
-    }
-    return MML_OK;
-}
-
 int ensure_store(mml_ctx* ctx) {
-    if (ctx->gs_pts[0]) return MML_OK;
+    if (ctx->cube_store.present()) return MML_OK;
     const size_t MM = (size_t)ctx->MM;
     ctx->gp_cap = 16 * ctx->MF;
-    const size_t U = (MM + (size_t)ctx->gp_cap + 3) & ~size_t(3);  // keeps the carved-out float4 array 16-byte aligned
-    for (int k = 0; k < 2; ++k) {
-        MML_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->gs_pts[k]), sizeof(float4) * MM));
-        MML_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->gs_tag[k]), sizeof(uint16_t) * MM));
-        MML_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->gs_pts2[k]), sizeof(float4) * MM));
-        MML_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->gs_tag2[k]), sizeof(uint16_t) * MM));
-        MML_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->gp_pts[k]), sizeof(float4) * (size_t)ctx->gp_cap));
-    }
-    // cnt | changed | bbox (6 per cube) | keep | keep_pos | sel | sel_pos | n_heads
-    MML_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->gs_work), sizeof(int) * (8 * (size_t)NCUBE + 4 * (U + 1) + 8)));
-    // 64-bit keys (in / out), sort values (in / out), selected points + tags + pending tags
-    MML_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->gs_keys),
-                      sizeof(unsigned long long) * 2 * U + sizeof(unsigned) * 2 * U + sizeof(float4) * U + sizeof(uint16_t) * 2 * U));
-    return MML_OK;
+    const size_t gp = (size_t)ctx->gp_cap;
+    const size_t U = (MM + gp + 3) & ~size_t(3);  // keeps the carved-out float4 array 16-byte aligned
+    return ctx->cube_store.reserve(
+        ctx, {mml_part(ctx->gs_pts[0], MM), mml_part(ctx->gs_tag[0], MM), mml_part(ctx->gs_pts2[0], MM), mml_part(ctx->gs_tag2[0], MM), mml_part(ctx->gp_pts[0], gp),
+              mml_part(ctx->gs_pts[1], MM), mml_part(ctx->gs_tag[1], MM), mml_part(ctx->gs_pts2[1], MM), mml_part(ctx->gs_tag2[1], MM), mml_part(ctx->gp_pts[1], gp),
+              // cnt | changed | bbox (6 per cube) | keep | keep_pos | sel | sel_pos | n_heads
+              mml_part(ctx->gs_work, 8 * (size_t)NCUBE + 4 * (U + 1) + 8),
+              // 64-bit keys (in / out), sort values (in / out), selected points + tags + pending tags
+              MmlPart{reinterpret_cast<void**>(&ctx->gs_keys),
+                      sizeof(unsigned long long) * 2 * U + sizeof(unsigned) * 2 * U + sizeof(float4) * U + sizeof(uint16_t) * 2 * U}});
 }
 
 }  // namespace
@@ -325,10 +311,10 @@ int mml_cube_store_increment(mml_ctx* ctx, const double* T_wl, int* n_out) {
                                keep, sel);
             size_t need = 0;
             MML_HIP(rocprim::exclusive_scan(nullptr, need, keep, keep_pos, 0, (size_t)nu, rocprim::plus<int>(), s));
-            rc = ensure_tmp(ctx, need);
+            rc = mml_sort_tmp(ctx, need);
             if (rc != MML_OK) return rc;
-            MML_HIP(rocprim::exclusive_scan(ctx->sort_tmp, need, keep, keep_pos, 0, (size_t)nu, rocprim::plus<int>(), s));
-            MML_HIP(rocprim::exclusive_scan(ctx->sort_tmp, need, sel, sel_pos, 0, (size_t)nu, rocprim::plus<int>(), s));
+            MML_HIP(rocprim::exclusive_scan(ctx->sort_tmp.d, need, keep, keep_pos, 0, (size_t)nu, rocprim::plus<int>(), s));
+            MML_HIP(rocprim::exclusive_scan(ctx->sort_tmp.d, need, sel, sel_pos, 0, (size_t)nu, rocprim::plus<int>(), s));
             int last[4];
             MML_HIP(hipMemcpyAsync(&last[0], keep + nu - 1, sizeof(int), hipMemcpyDeviceToHost, s));
             MML_HIP(hipMemcpyAsync(&last[1], keep_pos + nu - 1, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -348,15 +334,15 @@ int mml_cube_store_increment(mml_ctx* ctx, const double* T_wl, int* n_out) {
                 hipLaunchKernelGGL(k_cube_vox_keys, dim3(blocks), dim3(256), 0, s, sel_pts, sel_tag, nsel, bbox, leaf, keys, vals);
                 need = 0;
                 MML_HIP(rocprim::radix_sort_pairs(nullptr, need, keys, keys2, vals, vals2, (size_t)nsel, 0, 56, s));
-                rc = ensure_tmp(ctx, need);
+                rc = mml_sort_tmp(ctx, need);
                 if (rc != MML_OK) return rc;
-                MML_HIP(rocprim::radix_sort_pairs(ctx->sort_tmp, need, keys, keys2, vals, vals2, (size_t)nsel, 0, 56, s));
+                MML_HIP(rocprim::radix_sort_pairs(ctx->sort_tmp.d, need, keys, keys2, vals, vals2, (size_t)nsel, 0, 56, s));
                 hipLaunchKernelGGL(k_heads64, dim3(blocks), dim3(256), 0, s, keys2, nsel, keep);  // keep / keep_pos are free again
                 need = 0;
                 MML_HIP(rocprim::exclusive_scan(nullptr, need, keep, keep_pos, 0, (size_t)nsel, rocprim::plus<int>(), s));
-                rc = ensure_tmp(ctx, need);
+                rc = mml_sort_tmp(ctx, need);
                 if (rc != MML_OK) return rc;
-                MML_HIP(rocprim::exclusive_scan(ctx->sort_tmp, need, keep, keep_pos, 0, (size_t)nsel, rocprim::plus<int>(), s));
+                MML_HIP(rocprim::exclusive_scan(ctx->sort_tmp.d, need, keep, keep_pos, 0, (size_t)nsel, rocprim::plus<int>(), s));
                 hipLaunchKernelGGL(k_cube_centroid, dim3(blocks), dim3(256), 0, s, sel_pts, keys2, vals2, keep, keep_pos, nsel, nk,
                                    ctx->MM, ctx->gs_pts2[kind], ctx->gs_tag2[kind], d_heads);
                 MML_HIP(hipMemcpyAsync(&nheads, d_heads, sizeof(int), hipMemcpyDeviceToHost, s));

@@ -141,28 +141,6 @@ __global__ void k_vox_centroid(const float4* pts, const unsigned* keys, const un
     out[dst] = make_float4(sx / c, sy / c, sz / c, 0.f);
 }
 
-int ensure_tmp(mml_ctx* ctx, size_t need) {
-    if (need > ctx->sort_tmp_bytes) {
-        MML_HIP(hipStreamSynchronize(MML_STREAM(ctx)));
-        if (ctx->sort_tmp) MML_HIP(hipFree(ctx->sort_tmp));
-        MML_HIP(hipMalloc(&ctx->sort_tmp, need));
-        ctx->sort_tmp_bytes = need;
-    }
-    return MML_OK;
-}
-
-// rocPRIM temporary storage of the current stream lane (lanes run concurrently: no sharing)
-int ensure_tmp_lane(mml_ctx* ctx, size_t need) {
-    const int l = ctx->cur;
-    if (need > ctx->seg_tmp_bytes[l]) {
-        MML_HIP(hipStreamSynchronize(MML_STREAM(ctx)));
-        if (ctx->seg_tmp[l]) MML_HIP(hipFree(ctx->seg_tmp[l]));
-        MML_HIP(hipMalloc(&ctx->seg_tmp[l], need));
-        ctx->seg_tmp_bytes[l] = need;
-    }
-    return MML_OK;
-}
-
 // pcl::VoxelGrid over `m` device points; the filtered cloud goes to `out` (capacity cap), its size to *h_n
 int voxel_filter_device(mml_ctx* ctx, const float4* pts, int m, float leaf, float4* out, int cap, int* h_n) {
     hipStream_t s = MML_STREAM(ctx);
@@ -180,18 +158,18 @@ int voxel_filter_device(mml_ctx* ctx, const float4* pts, int m, float leaf, floa
     size_t need = 0;
     MML_HIP(rocprim::radix_sort_pairs(nullptr, need, ctx->map_keys, ctx->map_keys2, ctx->map_vals, ctx->map_vals2,
                                       (size_t)m, 0, 32, s));
-    int rc = ensure_tmp(ctx, need);
+    int rc = mml_sort_tmp(ctx, need);
     if (rc != MML_OK) return rc;
-    MML_HIP(rocprim::radix_sort_pairs(ctx->sort_tmp, need, ctx->map_keys, ctx->map_keys2, ctx->map_vals, ctx->map_vals2,
+    MML_HIP(rocprim::radix_sort_pairs(ctx->sort_tmp.d, need, ctx->map_keys, ctx->map_keys2, ctx->map_vals, ctx->map_vals2,
                                       (size_t)m, 0, 32, s));
     int* flag = ctx->vox_flag;
     int* pos = ctx->vox_flag + ctx->vox_cap + 1;
     hipLaunchKernelGGL(k_vox_heads, dim3(blocks), dim3(256), 0, s, ctx->map_keys2, m, flag);
     need = 0;
     MML_HIP(rocprim::exclusive_scan(nullptr, need, flag, pos, 0, (size_t)m, rocprim::plus<int>(), s));
-    rc = ensure_tmp(ctx, need);
+    rc = mml_sort_tmp(ctx, need);
     if (rc != MML_OK) return rc;
-    MML_HIP(rocprim::exclusive_scan(ctx->sort_tmp, need, flag, pos, 0, (size_t)m, rocprim::plus<int>(), s));
+    MML_HIP(rocprim::exclusive_scan(ctx->sort_tmp.d, need, flag, pos, 0, (size_t)m, rocprim::plus<int>(), s));
     hipLaunchKernelGGL(k_vox_centroid, dim3(blocks), dim3(256), 0, s, pts, ctx->map_keys2, ctx->map_vals2, flag, pos, m, cap,
                        out, d_n);
     MML_HIP(hipMemcpyAsync(h_n, d_n, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -200,19 +178,6 @@ int voxel_filter_device(mml_ctx* ctx, const float4* pts, int m, float leaf, floa
     return MML_OK;
 }
 
-}  // namespace
-
-namespace {
-int ensure_vox_scratch(mml_ctx* ctx, size_t pts) {
-    if (pts <= ctx->vox_cap) return MML_OK;
-    MML_HIP(hipStreamSynchronize(MML_STREAM(ctx)));
-    if (ctx->ring_cat) MML_HIP(hipFree(ctx->ring_cat));
-    if (ctx->vox_flag) MML_HIP(hipFree(ctx->vox_flag));
-    MML_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->ring_cat), sizeof(float4) * pts));
-    MML_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->vox_flag), sizeof(int) * 2 * (pts + 1)));
-    ctx->vox_cap = pts;
-    return MML_OK;
-}
 }  // namespace
 
 // ---- a10 for labelled clouds beyond the LDS sort of k_voxel: the whole batch through ONE global sort --------------------
@@ -377,29 +342,11 @@ int mml_downsample_big(mml_ctx* ctx, int first, int count) {
     const int nseg = 2 * count;
     // scratch for the worst case (every point of every slot labelled), allocated on first use
     const size_t cap = (size_t)ctx->B * ctx->NT;
-    if (!ctx->seg_meta) {  // seg_meta is set last: it marks the scratch as complete
-        const hipError_t e1 = hipMalloc(reinterpret_cast<void**>(&ctx->seg_keys), sizeof(unsigned long long) * 2 * cap);
-        const hipError_t e2 = hipMalloc(reinterpret_cast<void**>(&ctx->seg_vals), sizeof(unsigned) * 2 * cap);
-        const hipError_t e3 = hipMalloc(reinterpret_cast<void**>(&ctx->seg_cat), sizeof(float4) * cap);
-        const hipError_t e4 = hipMalloc(reinterpret_cast<void**>(&ctx->seg_flag), sizeof(int) * 2 * (cap + 1));
-        int* meta_buf = nullptr;
-        const hipError_t e5 = hipMalloc(reinterpret_cast<void**>(&meta_buf), sizeof(int) * (8 * (size_t)ctx->B * 2 + 16) * mml_ctx::MAX_LANES);
-        if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess || e5 != hipSuccess) {
-            // all or nothing: a later call must not find a half-allocated scratch and launch on null buffers
-            (void)hipFree(ctx->seg_keys);
-            (void)hipFree(ctx->seg_vals);
-            (void)hipFree(ctx->seg_cat);
-            (void)hipFree(ctx->seg_flag);
-            (void)hipFree(meta_buf);
-            ctx->seg_keys = nullptr;
-            ctx->seg_vals = nullptr;
-            ctx->seg_cat = nullptr;
-            ctx->seg_flag = nullptr;
-            (void)hipGetLastError();
-            ctx->err = "mml_downsample_big: out of device memory for the global-sort scratch";
-            return MML_ERR_HIP;
-        }
-        ctx->seg_meta = meta_buf;
+    if (!ctx->seg_scratch.present()) {
+        const int rc = ctx->seg_scratch.reserve(
+            ctx, {mml_part(ctx->seg_keys, 2 * cap), mml_part(ctx->seg_vals, 2 * cap), mml_part(ctx->seg_cat, cap), mml_part(ctx->seg_flag, 2 * (cap + 1)),
+                  mml_part(ctx->seg_meta, (8 * (size_t)ctx->B * 2 + 16) * mml_ctx::MAX_LANES)});
+        if (rc != MML_OK) return mml_refuse(ctx, rc, "mml_downsample_big: out of device memory for the global-sort scratch");
     }
     // lanes work on disjoint slot ranges: each gets the part of the scratch that its slots' points can fill
     const size_t base = (size_t)first * ctx->NT;
@@ -447,16 +394,16 @@ int mml_downsample_big(mml_ctx* ctx, int first, int count) {
     size_t need = 0;
     MML_REQUIRE(ctx->NT <= (1 << 20) && nseg <= 4096, MML_ERR_CAPACITY, "global-sort down-sampler: scans up to 2^20 points, 2048 slots per call");
     MML_HIP(rocprim::radix_sort_pairs(nullptr, need, P.keys, keys2, P.vals, vals2, (size_t)total, 0, 52 + seg_bits, s));
-    int rc = ensure_tmp_lane(ctx, need);
+    int rc = ctx->seg_tmp[ctx->cur].reserve(ctx, need, s);
     if (rc != MML_OK) return rc;
-    MML_HIP(rocprim::radix_sort_pairs(ctx->seg_tmp[ctx->cur], need, P.keys, keys2, P.vals, vals2, (size_t)total, 0, 52 + seg_bits, s));
+    MML_HIP(rocprim::radix_sort_pairs(ctx->seg_tmp[ctx->cur].d, need, P.keys, keys2, P.vals, vals2, (size_t)total, 0, 52 + seg_bits, s));
     const int blocks = (total + 255) / 256;
     hipLaunchKernelGGL(k_seg_heads, dim3(blocks), dim3(256), 0, s, keys2, total, flag);
     need = 0;
     MML_HIP(rocprim::exclusive_scan(nullptr, need, flag, pos, 0, (size_t)total, rocprim::plus<int>(), s));
-    rc = ensure_tmp_lane(ctx, need);
+    rc = ctx->seg_tmp[ctx->cur].reserve(ctx, need, s);
     if (rc != MML_OK) return rc;
-    MML_HIP(rocprim::exclusive_scan(ctx->seg_tmp[ctx->cur], need, flag, pos, 0, (size_t)total, rocprim::plus<int>(), s));
+    MML_HIP(rocprim::exclusive_scan(ctx->seg_tmp[ctx->cur].d, need, flag, pos, 0, (size_t)total, rocprim::plus<int>(), s));
     hipLaunchKernelGGL(k_seg_centroid, dim3(blocks), dim3(256), 0, s, P, keys2, vals2, flag, pos, total);
     MML_HIP(hipGetLastError());
     return MML_OK;
@@ -491,11 +438,13 @@ int mml_map_upkeep_increment(mml_ctx* ctx, int slot, const double* T_wl, int* n_
     hipStream_t s = MML_STREAM(ctx);
     constexpr int W = mml_ctx::LOCAL_WINDOW;
     const size_t ring_pts = (size_t)W * ctx->MF;
-    if (!ctx->ring[0])
-        for (int k = 0; k < 2; ++k) MML_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->ring[k]), sizeof(float4) * ring_pts));
-    {
-        int rc0 = ensure_vox_scratch(ctx, ring_pts);
+    if (!ctx->ring_mem.present()) {
+        MML_HIP(hipStreamSynchronize(s));
+        ctx->vox_cap = 0;
+        const int rc0 = ctx->ring_mem.reserve(ctx, {mml_part(ctx->ring[0], ring_pts), mml_part(ctx->ring[1], ring_pts), mml_part(ctx->ring_cat, ring_pts),
+                                                    mml_part(ctx->vox_flag, 2 * (ring_pts + 1))});
         if (rc0 != MML_OK) return rc0;
+        ctx->vox_cap = ring_pts;
     }
     int* n_feat = reinterpret_cast<int*>(mml_stage_alloc(ctx, 1));  // pinned
     MML_HIP(hipMemcpyAsync(&n_feat[0], ctx->ft_n + 0 * ctx->B + slot, sizeof(int), hipMemcpyDeviceToHost, s));

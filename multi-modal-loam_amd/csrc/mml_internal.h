@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "mml_mem.h"
 #include "mmloam_hip.h"
 
 #define MML_WAVE 64
@@ -86,6 +87,7 @@ struct mml_ctx {
     void* wstate = nullptr;
     double* wrec = nullptr;
     double* waux = nullptr;
+    MmlGroup win_state;  // owns the three, allocated by the first such solve
     struct WinGraph {  // captured launch chain of one frame-parallel window solve
         int first, count, W, max_iters, fixed;
         double huber, w_tan;
@@ -119,6 +121,7 @@ struct mml_ctx {
     int n_lanes = 1;
     int cur = 0;
     std::string err;
+    MmlFixed fixed;  // owns every buffer below that mml_create allocates (the plain pointers without an owner named beside them)
 
     int B = 0, NV = 0, NL = 0, NT = 0, L = 0, MF = 0;
 
@@ -208,8 +211,8 @@ struct mml_ctx {
     float4* seg_cat = nullptr;
     int* seg_flag = nullptr;
     int* seg_meta = nullptr;
-    void* seg_tmp[8] = {};
-    size_t seg_tmp_bytes[8] = {};
+    MmlGroup seg_scratch;                    // owns the five
+    MmlStaging<char, false> seg_tmp[8];      // rocPRIM temporary storage per stream lane (lanes run concurrently: no sharing)
     int VX_CAP = 0;                          // label-list stride per (slot, kind) = NT: every labelled point is listed
 
     // factors
@@ -229,7 +232,8 @@ struct mml_ctx {
     float4* gmap_orig[2] = {nullptr, nullptr};
     uint16_t* gtag_orig[2] = {nullptr, nullptr};
     int* cube_cnt[2] = {nullptr, nullptr};  // 4851 ints each
-    int gmap_cap[2] = {0, 0};
+    MmlGroup ggrid_mem[2];                  // owns ggrid[k].pts / cell_start / tags, gmap_orig[k], gtag_orig[k], cube_cnt[k]
+    int gmap_cap[2] = {0, 0};               // points the group of a kind is sized for
     int cen[3] = {10, 5, 10};  // laserCloudCen{Width,Height,Depth}_last (Map_Manager.h:113-115)
     // device-side local map upkeep (Estimator::MapIncrementLocal): ring of key scans' features in the world frame
     static constexpr int LOCAL_WINDOW = 50;  // localMapWindowSize, Estimator.h:326
@@ -237,6 +241,7 @@ struct mml_ctx {
     float4* ring_cat = nullptr;              // concatenation scratch, LOCAL_WINDOW x MF
     int* vox_flag = nullptr;                 // head flags / positions, 2 x (vox_cap + 1)
     size_t vox_cap = 0;                      // points ring_cat / vox_flag are sized for
+    MmlGroup ring_mem;                       // owns ring[2], ring_cat, vox_flag; allocated by the first increment
     int ring_n[2][LOCAL_WINDOW] = {};
     long local_map_id = 0;                   // localMapID
     // device-side MAP_MANAGER cube stores (map_global.hip): live points + cube tags, pending world-frame features
@@ -251,16 +256,15 @@ struct mml_ctx {
     int gs_cen[3] = {10, 5, 10};               // laserCloudCen{Width,Height,Depth} of the live store
     int* gs_work = nullptr;                    // histograms / flags / bbox keys / scan scratch
     unsigned long long* gs_keys = nullptr;     // 64-bit sort keys, 2 x MM
-    void* wire_stage = nullptr;              // raw message bytes on their way in / out (one call at a time; grows to the largest)
-    size_t wire_stage_bytes = 0;
+    MmlGroup cube_store;                       // owns gs_pts .. gs_keys, allocated by the first append / increment
+    MmlStaging<char, false> wire_stage;      // raw message bytes on their way in / out (one call at a time; grows to the largest)
     int local_map_n[2] = {0, 0};
     float4* map_tmp = nullptr;
     unsigned* map_keys = nullptr;
     unsigned* map_keys2 = nullptr;
     unsigned* map_vals = nullptr;
     unsigned* map_vals2 = nullptr;
-    void* sort_tmp = nullptr;
-    size_t sort_tmp_bytes = 0;
+    MmlStaging<char, false> sort_tmp;  // rocPRIM temporary storage of the map builds and filters (mml_sort_tmp)
     int MM = 0;
 
     // solver state
@@ -290,6 +294,19 @@ struct mml_ctx {
     };
     std::vector<Pending> pending;
     std::vector<hipEvent_t> event_pool;
+
+    // every owner declared above, for mml_destroy: a new one is added here, next to its declaration
+    void release_memory() {
+        win_state.release();
+        seg_scratch.release();
+        for (auto& t : seg_tmp) t.release();
+        for (auto& g : ggrid_mem) g.release();
+        ring_mem.release();
+        cube_store.release();
+        wire_stage.release();
+        sort_tmp.release();
+        fixed.release();
+    }
 };
 
 // pcl::VoxelGrid::applyFilter (PCL 1.8.1 voxel_grid.hpp): a bounding box of more than INT_MAX voxels ("Leaf size is too small for the
@@ -326,29 +343,8 @@ int mml_uploads_wait(mml_ctx* ctx, int first, int count);
 // `code` comes back.  capi.hip.
 int mml_refuse(mml_ctx* ctx, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
 
-// A device array and (Pinned) its pinned host twin, sized for the largest request so far: it only grows.  Every entry point that
-// uses one drains its stream before it returns, so nothing is in flight when reserve() replaces the buffers.  A failure midway
-// leaves cap == 0 and each pointer valid or null, which the next reserve() or release() cleans up.
-template <class T, bool Pinned = true>
-struct MmlStaging {
-    T* d = nullptr;
-    T* h = nullptr;  // stays null without Pinned
-    size_t cap = 0;  // elements
-    void release() {
-        if (d) (void)hipFree(d);
-        if (h) (void)hipHostFree(h);
-        d = h = nullptr;
-        cap = 0;
-    }
-    int reserve(mml_ctx* ctx, size_t n) {
-        if (n <= cap) return MML_OK;
-        release();
-        MML_HIP(hipMalloc(reinterpret_cast<void**>(&d), sizeof(T) * n));
-        if (Pinned) MML_HIP(hipHostMalloc(reinterpret_cast<void**>(&h), sizeof(T) * n, hipHostMallocDefault));
-        cap = n;
-        return MML_OK;
-    }
-};
+// ctx->sort_tmp with room for `need` bytes; the current stream is drained before a live buffer is replaced
+inline int mml_sort_tmp(mml_ctx* ctx, size_t need) { return ctx->sort_tmp.reserve(ctx, need, MML_STREAM(ctx)); }
 
 // profiling bracket (no-op unless enabled)
 int mml_stage_begin(mml_ctx* ctx, const char* name);

@@ -1519,10 +1519,10 @@ __global__ void k_window_export(int first, int W, const TRState* state, const do
 constexpr int kFirstChunk = 7;
 static int launch_solve_frame_parallel(mml_ctx* ctx, int first, int count, int W, const double* d_Tbl, mml_solve_opts opts,
                                        bool second_chunk) {
-    if (!ctx->wstate) {
-        MML_HIP(hipMalloc(&ctx->wstate, sizeof(TRState) * (size_t)ctx->B));
-        MML_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->wrec), sizeof(double) * 2 * 32 * (size_t)ctx->B));
-        MML_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->waux), sizeof(double) * 4 * (size_t)ctx->B));
+    if (!ctx->win_state.present()) {
+        const int rc = ctx->win_state.reserve(ctx, {MmlPart{&ctx->wstate, sizeof(TRState) * (size_t)ctx->B}, mml_part(ctx->wrec, 2 * 32 * (size_t)ctx->B),
+                                                    mml_part(ctx->waux, 4 * (size_t)ctx->B)});
+        if (rc != MML_OK) return rc;
     }
     hipStream_t s = MML_STREAM(ctx);
     const int nprob = count / W;
