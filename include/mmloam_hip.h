@@ -200,6 +200,45 @@ int mml_time_offset_search_batch(mml_ctx* ctx, int n,
 int mml_time_offset_plan(int n, const int* velo_offsets, const int* livox_offsets, int search_resolution, int sliced_points,
                          int max_map_points, int* n_windows /* n, may be NULL */, int* bad_problem /* may be NULL */);
 
+/* ---- the aligner's Velodyne field-of-view selection: the input of the time-offset search ---------------------------------
+ * velo_cloud_handler (unionLidarsAligner.cpp:437-490) for n Velodyne frames in one call: per point ori = -atan2f(y, x), unwrapped
+ * along the sweep by the halfPassed state machine (:461-477), relTime = (ori - startOri) / (endOri - startOri) (:479), and the
+ * point is kept iff ori lies in (-0.7608, 0.7158) or in that interval + 2 pi (:482-483).  The kept points of a frame, in input
+ * order, are velo_fovs_cloud: what :511 queues, :674 / :1080 hand to estimate_timeoffset and :603-609 publish as velo_inFOV.
+ * The arithmetic is the reference's to the bit (float / double mix as written, glibc's atan2f; csrc/velo_fov.h).
+ * Input, PointCloud2-style as in mml_scan_upload_pointcloud2: frame i is n_points[i] records of point_step bytes at
+ * data + byte_offsets[i] with float32 fields at off_x / off_y / off_z (packed x, y, z, intensity rows: point_step 16, offsets
+ * 0, 4, 8) -- the payload velo_cloud_handler receives.  Frames may lie anywhere in `data`, overlap or repeat.
+ * Output: the kept rows of frame i start at row n_kept[0] + ... + n_kept[i-1] of xyzt (x, y, z, relTime) and of xyz (x, y, z);
+ * either may be NULL.  xyz is the velo_xyz of mml_time_offset_search_batch and the running sums of n_kept are its velo_offsets.
+ * With both NULL the call is the sizing call (n_kept and info only; capacity_rows is not read).  info (optional) gives per frame
+ * startOri, endOri, h = the point that set halfPassed (-1: none did) and n_kept.  A frame of 0 points (where the reference reads
+ * points[0]) keeps nothing: info 0, 0, -1, 0.  A point with a NaN / Inf azimuth is never kept and never sets halfPassed.  A NaN
+ * first (last) point makes startOri (endOri) and every relTime NaN and switches the unwrapping that compares against it off; the
+ * predicate still reads ori alone, so such a frame keeps points by their unadjusted azimuth, as the reference's statements do.
+ * Checks, all before any device work, and a refusal writes nothing: MML_ERR_INVALID for n outside 1 .. MML_FOV_BATCH_MAX, a NULL
+ * byte_offsets / n_points / n_kept (or data with points to read), a negative count, offset or capacity_rows, point_step < 12, a
+ * field offset outside [0, point_step - 4] or not 4-byte aligned; MML_ERR_CAPACITY for a frame above max_velo_points (with a
+ * context only).  MML_ERR_CAPACITY also when capacity_rows is below the total kept: no row, count or info is then written.
+ * mml_last_error names the entry point and, where there is one, the frame.
+ * ctx == NULL runs the same routine on the host, frame after frame, and equals the device path to the byte: rows, counts, info.
+ * With a context: one workgroup per frame (MML_FOV_BATCH_MAX bounds n because the frame index is a grid's y dimension), two
+ * launches and at most TWO host synchronisations whatever n is -- after the read-back of counts and info, and after the
+ * read-back of the rows (the sizing call and a call that keeps nothing: one).  With profiling on each of the two shows as one
+ * launch of the stage "velo_fov".  Frames of up to 4096 points stay in registers between the phases; larger ones (any size up to
+ * max_velo_points) park one float per point in scratch.  The context keeps one grow-only scratch set for the largest call it has
+ * seen -- per input point point_step + 48 bytes on the device and point_step pinned, per frame 48 of each --, released by
+ * mml_destroy; MML_ERR_HIP, before any launch, when it cannot be grown.  mml_velo_fov_select is the n = 1 case of the same code. */
+#define MML_FOV_BATCH_MAX 65535   /* frames per call */
+typedef struct { float start_ori, end_ori; int half_index /* h, -1: never */; int n_kept; } mml_velo_fov_info;
+int mml_velo_fov_select_batch(mml_ctx* ctx /* NULL: the host build of the same routine */, int n,
+        const uint8_t* data, const long* byte_offsets /* n */, const int* n_points /* n */,
+        int point_step, int off_x, int off_y, int off_z,
+        float* xyzt /* kept rows x,y,z,relTime; may be NULL */, float* xyz /* packed x,y,z; may be NULL */,
+        long capacity_rows, int* n_kept /* n */, mml_velo_fov_info* info /* n, may be NULL */);
+int mml_velo_fov_select(mml_ctx* ctx, const uint8_t* data, int n_points, int point_step, int off_x, int off_y, int off_z,
+        float* xyzt, float* xyz, int capacity_rows, int* n_kept, mml_velo_fov_info* info);   /* n = 1, same code path */
+
 /* ---- the aligner node's frame assembly: a Livox point stream cut into scan slots ----------------------------------------
  * The steady-state work of unionLidarsAligner.cpp on the device.  A mml_livox_stream is the aligner's point queue
  * (_hori_points_queue / _hori_points_stamp_queue) in device memory: a flat array of 20-byte records and a flat array of

@@ -32,6 +32,9 @@ LIO_BATCH_MAX_FRAMES = 8  # MML_LIO_BATCH_MAX_FRAMES: frames per segment
 TOFS_BATCH_MAX = 65535    # MML_TOFS_BATCH_MAX: problems per call of mml_time_offset_search_batch
 GICP_BATCH_MAX = 65535    # MML_GICP_BATCH_MAX: problems / slots per call of mml_gicp_align_batch / mml_gicp_refresh_batch
 UNION_BATCH_MAX = 65535   # MML_UNION_BATCH_MAX: frames per call of mml_union_assemble
+FOV_BATCH_MAX = 65535     # MML_FOV_BATCH_MAX: frames per call of mml_velo_fov_select_batch
+FOV_TILE_POINTS = 256     # VFOV_BLOCK (csrc/velo_fov.hip): points one workgroup pass of the selection kernel takes
+FOV_REG_POINTS = 4096     # VFOV_REG_POINTS: frames above this park their azimuths in scratch between the phases
 UNION_OK, UNION_EMPTY, UNION_NOT_REACHED, UNION_NO_POINTS, UNION_OVERFLOW = 0, 1, 2, 3, 4   # mml_union_frame.status
 
 LIVOX_DTYPE = np.dtype([("offset_time", "<u4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4"),
@@ -40,6 +43,8 @@ LIVOX_DTYPE = np.dtype([("offset_time", "<u4"), ("x", "<f4"), ("y", "<f4"), ("z"
 
 # mml_union_frame (C long: 8 bytes on the LP64 hosts ROCm runs on)
 UNION_FRAME_DTYPE = np.dtype([("status", "<i4"), ("n_livox", "<i4"), ("begin", "<i8"), ("end", "<i8"), ("front_after", "<i8")])
+# mml_velo_fov_info
+VELO_FOV_INFO_DTYPE = np.dtype([("start_ori", "<f4"), ("end_ori", "<f4"), ("half_index", "<i4"), ("n_kept", "<i4")])
 
 
 class MmlError(RuntimeError):
@@ -270,6 +275,12 @@ def lib():
             L.mml_union_plan.argtypes = [C.c_void_p, C.c_long, C.c_long, C.c_uint64, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
             L.mml_scan_raw_download.restype = C.c_int
             L.mml_scan_raw_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        if hasattr(L, "mml_velo_fov_select_batch"):
+            L.mml_velo_fov_select_batch.restype = C.c_int
+            L.mml_velo_fov_select_batch.argtypes = ([C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_long]
+                                                    + [C.c_void_p] * 2)
+            L.mml_velo_fov_select.restype = C.c_int
+            L.mml_velo_fov_select.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 2
         _lib = L
     return _lib
 
@@ -380,6 +391,68 @@ def time_offset_plan(velo_offsets, livox_offsets, search_resolution=30, sliced_p
     rc = lib().mml_time_offset_plan(C.c_int(n), _p(vo), _p(lo), C.c_int(search_resolution), C.c_int(sliced_points),
                                     C.c_int(max_map_points), _p(nwin), C.byref(bad))
     return rc, bad.value, nwin[:max(n, 0)]
+
+
+def velo_fov_pack(frames):
+    """The input arguments of mml_velo_fov_select_batch for a list of frames, each an (n_i, k) float32 array with k >= 3 whose
+    columns start x, y, z: (data uint8, byte_offsets int64[n], n_points int32[n], point_step).  All frames must share k."""
+    fs = [_f32(f) for f in frames]
+    fs = [f.reshape(-1, f.shape[-1] if f.ndim > 1 else 3) for f in fs]
+    ks = {f.shape[1] for f in fs}
+    if len(ks) > 1 or (ks and min(ks) < 3):
+        raise ValueError("frames must share one row width of at least 3 floats (x, y, z, ...), not %s" % sorted(ks))
+    k = ks.pop() if ks else 4
+    n_points = np.array([len(f) for f in fs], np.int32)
+    byte_offsets = np.zeros(len(fs), np.int64)
+    if len(fs):
+        byte_offsets[1:] = np.cumsum(n_points[:-1].astype(np.int64)) * 4 * k
+    data = np.ascontiguousarray(np.concatenate(fs + [np.zeros((0, k), np.float32)])).reshape(-1).view(np.uint8)
+    return data, byte_offsets, n_points, 4 * k
+
+
+def velo_fov_select_raw(data, byte_offsets, n_points, point_step, off_x=0, off_y=4, off_z=8, ctx=None):
+    """mml_velo_fov_select_batch on PointCloud2-style payloads: frame i is n_points[i] records of point_step bytes at
+    data[byte_offsets[i]:] with float32 fields at off_x / off_y / off_z.  The sizing call and the filling call.  Returns a dict:
+    xyzt (total, 4) float32 = x, y, z, relTime of the kept points; xyz (total, 3), the velo_xyz of time_offset_search_batch;
+    n_kept int32[n]; offsets int32[n + 1], its velo_offsets; info VELO_FOV_INFO_DTYPE[n].  ctx None: the host routine."""
+    raw = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data).reshape(-1).view(np.uint8)
+    bo = np.ascontiguousarray(byte_offsets, dtype=np.int64)   # (C long: 8 bytes on the LP64 hosts ROCm runs on)
+    npts = np.ascontiguousarray(n_points, dtype=np.int32)
+    if len(bo) != len(npts):
+        raise ValueError("%d byte offsets for %d point counts" % (len(bo), len(npts)))
+    n = len(npts)
+    if n and point_step > 0 and int((bo + npts.astype(np.int64) * point_step).max()) > len(raw) and bo.min() >= 0 and npts.min() >= 0:
+        raise ValueError("a frame ends beyond the %d bytes of data" % len(raw))
+    h = ctx._h if ctx is not None else None
+
+    def call(xyzt, xyz, cap, kept, info):
+        rc = lib().mml_velo_fov_select_batch(h, C.c_int(n), _p(raw) if len(raw) else None, _p(bo), _p(npts), C.c_int(point_step),
+                                             C.c_int(off_x), C.c_int(off_y), C.c_int(off_z), _p(xyzt), _p(xyz), C.c_long(cap), _p(kept),
+                                             _p(info))
+        if ctx is not None:
+            ctx._ck(rc)
+        elif rc != MML_OK:
+            raise MmlError(rc, "mml_velo_fov_select_batch")
+
+    kept = np.zeros(max(n, 1), np.int32)
+    info = np.zeros(max(n, 1), VELO_FOV_INFO_DTYPE)
+    call(None, None, 0, kept, info)
+    total = int(kept[:n].sum())
+    xyzt = np.zeros((max(total, 1), 4), np.float32)
+    xyz = np.zeros((max(total, 1), 3), np.float32)
+    if total:
+        call(xyzt, xyz, total, kept, info)
+    offsets = np.zeros(n + 1, np.int32)
+    offsets[1:] = np.cumsum(kept[:n])
+    return {"xyzt": xyzt[:total], "xyz": xyz[:total], "n_kept": kept[:n], "offsets": offsets, "info": info[:n]}
+
+
+def velo_fov_select(frames, ctx=None):
+    """velo_cloud_handler's FOV selection (unionLidarsAligner.cpp:437-490) for a list of Velodyne frames, each (n_i, k >= 3)
+    float32 rows x, y, z, ...: velo_fov_select_raw on their packed bytes.  ctx None: the host routine (no device needed); a
+    Context: the device kernels, equal to it to the byte."""
+    data, bo, npts, step = velo_fov_pack(frames)
+    return velo_fov_select_raw(data, bo, npts, step, 0, 4, 8, ctx=ctx)
 
 
 def union_plan(S, front, tail, hs, stamps, max_livox_points):
@@ -571,6 +644,10 @@ class Context:
                                                     C.c_int(sliced_points), _p(nn), _p(err), _p(wo), _p(nw), _p(best), _p(lowest)))
         return [{"nn_d2": nn[lo[i]:lo[i + 1]], "window_error": err[wo[i]:wo[i] + nw[i]], "best_window": int(best[i]),
                  "lowest_error": float(lowest[i])} for i in range(n)]
+
+    def velo_fov_select(self, frames):
+        """velo_fov_select(frames, ctx=self): the aligner's FOV selection on the device."""
+        return velo_fov_select(frames, ctx=self)
 
     # ---- the aligner node's frame assembly (unionLidarsAligner.cpp:343-364, :736-868) ----
     def livox_stream(self, capacity):

@@ -116,6 +116,7 @@ void mml_destroy(mml_ctx* ctx) {
     mml_gicp_release(ctx);
     mml_time_offset_release(ctx);
     mml_union_release(ctx);
+    mml_velo_fov_release(ctx);
     ctx->release_memory();
     for (auto& pe : ctx->pending) {
         hipEventDestroy(pe.a);

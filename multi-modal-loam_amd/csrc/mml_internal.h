@@ -73,6 +73,7 @@ struct MmlLioDev;     // lio_init_batch.hip: the block of mml_lio_initialize_bat
 struct MmlGicpDev;    // gicp.hip: the blocks of the GICP alignments (single and batch calls)
 struct MmlTofsDev;    // time_offset.hip: the blocks of the time-offset searches (single and batch calls)
 struct MmlUnionDev;   // livox_stream.hip: the staging blocks of mml_union_assemble
+struct MmlVfovDev;    // velo_fov.hip: the blocks of the Velodyne FOV selection (single and batch calls)
 
 struct mml_ctx {
     mml_config cfg;
@@ -83,6 +84,7 @@ struct mml_ctx {
     MmlGicpDev* gicp = nullptr;
     MmlTofsDev* tofs = nullptr;
     MmlUnionDev* uni = nullptr;
+    MmlVfovDev* vfov = nullptr;
     // frame-parallel window solve (solve.hip): one state machine copy, 4 counters and two record buffers per slot
     void* wstate = nullptr;
     double* wrec = nullptr;
@@ -396,6 +398,7 @@ void mml_lio_init_release(mml_ctx* ctx);
 void mml_gicp_release(mml_ctx* ctx);
 void mml_time_offset_release(mml_ctx* ctx);
 void mml_union_release(mml_ctx* ctx);
+void mml_velo_fov_release(mml_ctx* ctx);
 // mml_union_assemble (livox_stream.hip): the host-only checks, then -- after the entry point's slot checks -- the device part
 int mml_union_check(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int count, const uint64_t* stamps, const float* velo_xyzi,
                     const int* velo_offsets, mml_union_frame* out);

@@ -817,6 +817,89 @@ inline std::vector<TimeOffsetResult> estimate_timeoffset_batch(Context& ctx, con
     return r;
 }
 
+// ---- velo_cloud_handler's FOV selection (unionLidarsAligner.cpp:437-490): velo_fovs_cloud from the PointCloud2 payload -----------
+// data / n_points / point_step / off_*: pointCloudIn->data.data(), width * height, point_step and the offsets of the float32
+// fields x, y, z in pointCloudIn->fields -- no pcl::fromROSMsg loop.  ctx == nullptr runs the same routine on the host.
+// VeloFovCloud is velo_fovs_cloud for one or many frames: xyzi holds the kept points as x, y, z, intensity = relTime (the
+// pcl::PointXYZI fields the reference fills), xyz the same points packed x, y, z, offsets[i] .. offsets[i+1] the rows of frame i
+// (n + 1 entries); info[i] = startOri, endOri, the point that set halfPassed, the count.
+struct VeloFovCloud {
+    std::vector<float> xyzi, xyz;
+    std::vector<int> offsets;
+    std::vector<mml_velo_fov_info> info;
+    size_t size() const { return xyz.size() / 3; }
+};
+struct VeloFrame {  // what the selection needs of a sensor_msgs/PointCloud2: msg.data.data(), msg.width * msg.height
+    const uint8_t* data = nullptr;
+    int n_points = 0;
+};
+inline VeloFovCloud select_velo_fov_batch(Context* ctx, const std::vector<VeloFrame>& frames, int point_step, int off_x, int off_y, int off_z) {
+    VeloFovCloud c;
+    const size_t n = frames.size();
+    c.offsets.assign(n + 1, 0);
+    c.info.resize(n);
+    if (n == 0) return c;
+    mml_ctx* h = ctx ? ctx->get() : nullptr;
+    // the frames lie anywhere in memory: offsets are taken from the lowest address among them
+    const uint8_t* base = nullptr;
+    for (const VeloFrame& f : frames)
+        if (f.n_points > 0 && (!base || f.data < base)) base = f.data;
+    std::vector<long> at(n, 0);
+    std::vector<int> np(n, 0), kept(n, 0);
+    for (size_t i = 0; i < n; ++i) {
+        np[i] = frames[i].n_points;
+        at[i] = frames[i].n_points > 0 ? (long)(frames[i].data - base) : 0;
+    }
+    check(h, mml_velo_fov_select_batch(h, (int)n, base, at.data(), np.data(), point_step, off_x, off_y, off_z, nullptr, nullptr, 0, kept.data(),
+                                       nullptr),
+          "mml_velo_fov_select_batch");
+    for (size_t i = 0; i < n; ++i) c.offsets[i + 1] = c.offsets[i] + kept[i];
+    const long total = c.offsets[n];
+    c.xyzi.resize(4 * (size_t)total + 4);
+    c.xyz.resize(3 * (size_t)total + 3);
+    check(h, mml_velo_fov_select_batch(h, (int)n, base, at.data(), np.data(), point_step, off_x, off_y, off_z, c.xyzi.data(), c.xyz.data(), total,
+                                       kept.data(), c.info.data()),
+          "mml_velo_fov_select_batch");
+    c.xyzi.resize(4 * (size_t)total);
+    c.xyz.resize(3 * (size_t)total);
+    return c;
+}
+inline VeloFovCloud select_velo_fov(Context* ctx, const uint8_t* data, int n_points, int point_step, int off_x, int off_y, int off_z) {
+    return select_velo_fov_batch(ctx, std::vector<VeloFrame>{VeloFrame{data, n_points}}, point_step, off_x, off_y, off_z);
+}
+// estimate_timeoffset_batch on a selection as it stands: cloud i of `velo_fov` against livox[i] -- no repacking of the Velodyne side.
+inline std::vector<TimeOffsetResult> estimate_timeoffset_batch(Context& ctx, const VeloFovCloud& velo_fov, const std::vector<std::vector<float>>& livox,
+                                                               const std::vector<float>& velo_hori_tf, int offset_search_resolution = 30,
+                                                               int offset_search_sliced_points = 12000) {
+    const size_t n = velo_fov.offsets.empty() ? 0 : velo_fov.offsets.size() - 1;
+    if (livox.size() != n || !(velo_hori_tf.empty() || velo_hori_tf.size() == 16 || velo_hori_tf.size() == 16 * n))
+        throw std::runtime_error("estimate_timeoffset_batch: one Livox cloud per Velodyne cloud; 0, 16 or 16 n matrix entries");
+    std::vector<int> lo(n + 1, 0);
+    for (size_t i = 0; i < n; ++i) {
+        if (livox[i].size() % 3) throw std::runtime_error("estimate_timeoffset_batch: clouds are packed x, y, z");
+        lo[i + 1] = lo[i] + (int)(livox[i].size() / 3);
+    }
+    std::vector<float> l(3 * (size_t)lo[n] + 3), tf;
+    for (size_t i = 0; i < n; ++i) std::copy(livox[i].begin(), livox[i].end(), l.begin() + 3 * (size_t)lo[i]);
+    if (velo_hori_tf.size() == 16 && n != 1)
+        for (size_t i = 0; i < n; ++i) tf.insert(tf.end(), velo_hori_tf.begin(), velo_hori_tf.end());
+    else
+        tf = velo_hori_tf;
+    std::vector<int> nwin(n ? n : 1, 0), best(n ? n : 1, -1);
+    std::vector<double> lowest(n ? n : 1, 1000000.0);
+    check(ctx.get(), mml_time_offset_search_batch(ctx.get(), (int)n, velo_fov.xyz.data(), velo_fov.offsets.data(), tf.empty() ? nullptr : tf.data(),
+                                                  l.data(), lo.data(), offset_search_resolution, offset_search_sliced_points, nullptr, nullptr,
+                                                  nullptr, nwin.data(), best.data(), lowest.data()),
+          "mml_time_offset_search_batch");
+    std::vector<TimeOffsetResult> r(n);
+    for (size_t i = 0; i < n; ++i) {
+        r[i].n_windows = nwin[i];
+        r[i].best_window = best[i];
+        r[i].lowest_error = lowest[i];
+    }
+    return r;
+}
+
 // ---- the aligner node's point queue (unionLidarsAligner.cpp: _hori_points_queue / _hori_points_stamp_queue) on the device -------
 // transform_hori_timestamp (:736-763) pushes the queued messages; pub_horipoints_given_stamp (:766-868) cuts one Velodyne frame
 // interval out of the queue and, where the reference publishes a union_cloud (:343-364), fills a scan slot: the Livox points with

@@ -410,3 +410,21 @@ def try_map_initialization_batch(frames_list, samples_list, exTlb=None, ctx=None
                      [fr["bg"] for fr in frames], [fr["ba"] for fr in frames], samples_list[s], ex[s], pre))
     out = M.lio_initialize_batch(segs, ctx)
     return [_apply_map_initialization(M, frames_list[s], samples_list[s], *out[s]) for s in range(n_seg)]
+
+
+def time_offset_from_frames(ctx, velo_frames, livox, tf=None, search_resolution=30, sliced_points=12000):
+    """The aligner's time-offset estimate from raw Velodyne frames: velo_cloud_handler's FOV selection
+    (unionLidarsAligner.cpp:437-490) of every frame in one device call, then estimate_timeoffset's search (:1077-1153) of every
+    selected cloud in one more.  velo_frames: list of (n_i, k >= 3) float32 rows x, y, z, ...; livox: one merged Livox cloud (m, 3)
+    searched by every frame, or one per frame; tf: None, one 4 x 4 matrix or one per frame (_velo_hori_tf_matrix).  The selection's
+    packed x, y, z rows and the running sums of its counts go into the search as they are.  Returns (results, selection): the
+    list of dicts Context.time_offset_search_batch returns and the dict of Context.velo_fov_select."""
+    sel = ctx.velo_fov_select(velo_frames)
+    n = len(sel["n_kept"])
+    vo = sel["offsets"]
+    if isinstance(livox, np.ndarray) or (len(livox) and np.ndim(livox[0]) == 1):
+        livox = [livox] * n
+    if len(livox) != n:
+        raise ValueError("%d Livox clouds for %d Velodyne frames" % (len(livox), n))
+    velo_list = [sel["xyz"][vo[i]:vo[i + 1]] for i in range(n)]     # (views: time_offset_pack concatenates them back in order)
+    return ctx.time_offset_search_batch(velo_list, livox, search_resolution, sliced_points, tfs=tf), sel
