@@ -1913,8 +1913,9 @@ int mml_associate_far_count(mml_ctx* ctx, int* n) {
     if (rc != MML_OK) return rc;
     int h[mml_ctx::MAX_LANES];
     MML_HIP(hipMemcpy(h, ctx->d_misc + 32, sizeof(h), hipMemcpyDeviceToHost));  // (one counter per stream lane: map_assoc.hip hard_count)
+    // (the counters of the lanes the last call did not use still hold an earlier call's counts)
     *n = 0;
-    for (int l = 0; l < mml_ctx::MAX_LANES; ++l) *n += h[l];
+    for (int l = 0; l < ctx->far_lanes; ++l) *n += h[l];
     return MML_OK;
 }
 

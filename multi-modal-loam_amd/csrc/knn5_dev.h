@@ -164,6 +164,68 @@ __device__ __forceinline__ void scan_shell_row(const MmlGrid& g, const KnnQuery&
     }
 }
 
+// Four rows of shell r at once: rows t, t + STRIDE, t + 2 STRIDE, t + 3 STRIDE of the shell's in-grid rectangle
+// (row t is y = ylo + t % wy, z = zlo + t / wy; rows at or beyond nrows do not exist).  scan_shell_row is a dependent chain per
+// row -- extent, two cell_start loads, points -- and a far query's rows are mostly empty, so a lane that walks them one by
+// one waits a full load latency for every "nothing here".  Here the extents of all four rows are worked out first, every
+// cell_start load of the group is issued together (a face row is one span of cells, two loads; any other row is its two end
+// cells, four loads; a piece that does not exist or lies outside `bound` reads cell_start[0] twice and comes out empty), and only
+// the pieces that hold points go on to scan_range: an empty row costs no further memory access.
+// `bound` as in scan_shell_row, finite or not, fixed for the group: it may be stale by the group's own finds, and a looser
+// bound only reads more.  The cells visited are those scan_shell_row visits for the same bound, and the top-5 list is a set
+// ordered by (d2, index) keys, so the order of the visits does not matter.
+template <int STRIDE>
+__device__ __forceinline__ void scan_shell_rows4(const MmlGrid& g, const KnnQuery& q, int r, int ylo, int wy, int zlo, int nrows,
+                                                 int t, Knn5& k, int mytag, float bound) {
+    const int DX = g.dim[0], DY = g.dim[1];
+    const float reach = sqrtf(bound * 1.00001f) * g.inv_cell + 4e-3f;  // cells
+    const float reach2 = reach * reach;
+    const int x0 = q.hx - r, x1 = q.hx + r;
+    unsigned ia[8], ib[8];  // piece v = cells [ia, ib) of cell_start's index space; constant indices only: registers
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int tu = t + u * STRIDE;
+        const int y = ylo + tu % wy, z = zlo + tu / wy;
+        const float gy = y > q.hy ? (float)y - q.fy : (y < q.hy ? q.fy - (float)(y + 1) : 0.f);
+        const float gz = z > q.hz ? (float)z - q.fz : (z < q.hz ? q.fz - (float)(z + 1) : 0.f);
+        const float w2 = reach2 - (gy * gy + gz * gz);
+        const bool in = tu < nrows && !(w2 < 0.f);
+        const float w = sqrtf(fmaxf(w2, 0.f));
+        const int xlo = (int)floorf(fmaxf(q.fx - w, -1.f)), xhi = (int)floorf(fminf(q.fx + w, (float)DX));
+        const bool face = (z == q.hz - r || z == q.hz + r || y == q.hy - r || y == q.hy + r);
+        const int rowbase = DX * (y + DY * z);
+        const int xa = max(max(x0, 0), xlo), xb = min(min(x1, DX - 1), xhi);
+        const bool va = in && (face ? xa <= xb : (x0 >= 0 && x0 < DX && x0 >= xlo));
+        const bool vb = in && !face && x1 >= 0 && x1 < DX && x1 != x0 && x1 <= xhi;
+        ia[2 * u] = va ? (unsigned)(rowbase + (face ? xa : x0)) : 0u;
+        ib[2 * u] = va ? (unsigned)(rowbase + (face ? xb : x0) + 1) : 0u;
+        ia[2 * u + 1] = vb ? (unsigned)(rowbase + x1) : 0u;
+        ib[2 * u + 1] = vb ? (unsigned)(rowbase + x1 + 1) : 0u;
+    }
+    int s[8], e[8];
+#pragma unroll
+    for (int v = 0; v < 8; ++v) {
+        s[v] = g.cell_start[ia[v]];
+        e[v] = g.cell_start[ib[v]];
+    }
+    unsigned todo = 0;
+#pragma unroll
+    for (int v = 0; v < 8; ++v) todo |= (s[v] < e[v] ? 1u : 0u) << v;
+    // every lane takes its own next non-empty piece, so the lanes of a wavefront scan side by side whichever rows theirs are
+#pragma unroll 1
+    while (todo) {
+        const int v = __ffs((int)todo) - 1;
+        todo &= todo - 1;
+        int ss = s[0], ee = e[0];
+#pragma unroll
+        for (int j = 1; j < 8; ++j) {
+            ss = v == j ? s[j] : ss;
+            ee = v == j ? e[j] : ee;
+        }
+        scan_range(g.pts, g.tags, mytag, ss, ee, q.qx, q.qy, q.qz, k);
+    }
+}
+
 // ring 1 rows, nearest first, so that the bound has tightened before the edge and corner rows are reached
 __device__ __constant__ const signed char kRing1Row[9][2] = {{0, 0}, {-1, 0}, {1, 0}, {0, -1}, {0, 1}, {-1, -1}, {1, -1}, {-1, 1}, {1, 1}};
 

@@ -951,22 +951,34 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MML_AW_HARD
         const KnnQuery q = knn_query(g, sx, sy, sz);
         const int rmax = live ? (int)ceilf(sqrtf(P.thres) * g.inv_cell) + 1 : 0;
         bool sdone = !live;
-        if (!sdone && r0 > rmax) {
+        // a query outside the grid: the shells before the grid's near side hold no cell (knn5_search's rnear).  The walk starts at
+        // the first shell that does, unless the shell before it already ends the search.
+        const int rnear = max(max(max(-q.hx, q.hx - (g.dim[0] - 1)), max(-q.hy, q.hy - (g.dim[1] - 1))), max(-q.hz, q.hz - (g.dim[2] - 1)));
+        const int rs = max(r0, rnear);
+        if (!sdone && (r0 > rmax || (rs > r0 && (rs > rmax || knn_done(g, q.inset, rs - 1, start_d5, P.thres))))) {
             sdone = true;
             lanes_merge5<SPAN>(loc, best);
         }
-        for (int r = r0;; ++r) {
+        for (int r = rs;; ++r) {
             if (!sdone && r > rmax) sdone = true;
             if (__all(sdone)) break;
             if (!sdone) {
-                // the rows of the shell that lie inside the grid
-                // (best: merged list of the shells before this one; loc: this lane's own list; lane 0's starting list
-                //  of round 0 holds five real points, so its d[4] bounds the result as well)
+                // the rows of the shell that lie inside the grid, four per lane and turn (scan_shell_rows4)
                 const int ylo = max(q.hy - r, 0), yhi = min(q.hy + r, g.dim[1] - 1), zlo = max(q.hz - r, 0), zhi = min(q.hz + r, g.dim[2] - 1);
                 const int wy = yhi - ylo + 1, wz = zhi - zlo + 1;
                 if (wy > 0 && wz > 0)
-                    for (int t = gl; t < wy * wz; t += SPAN)
-                        scan_shell_row(g, q, r, ylo + (t % wy), zlo + (t / wy), loc, mytag, fminf(fminf(knn_d(best, 4), knn_d(loc, 4)), start_d5));
+                    for (int t = gl; t < wy * wz; t += 4 * SPAN) {
+                        // Bound of the group: any upper bound of the final fifth distance (best: merged list of the shells
+                        // before this one; loc: this lane's own list; lane 0's starting list of round 0 holds five real points),
+                        // and the gate.  P.thres is thres_dist rounded UP to float and a skipped cell holds only points whose
+                        // float d2 is above the bound, so no skipped point has (double)d2 < thres_dist.  A list that passes the
+                        // gate, (double)d5 < thres_dist, has all five members below P.thres: none of them was skipped, and no
+                        // skipped point could have displaced one, so the five ids and d5 are what the unclipped search finds.
+                        // Otherwise the true d5 is >= thres_dist, and so is the clipped list's (it is a subset's fifth, or
+                        // INFINITY): store_none either way.  Only the list of a query that ends without a factor may differ.
+                        const float bound = fminf(fminf(fminf(knn_d(best, 4), knn_d(loc, 4)), start_d5), P.thres);
+                        scan_shell_rows4<SPAN>(g, q, r, ylo, wy, zlo, wy * wz, t, loc, mytag, bound);
+                    }
             }
             lanes_merge5<SPAN>(loc, best);
             if (!sdone && knn_done(g, q.inset, r, knn_d(best, 4), P.thres)) sdone = true;
@@ -1278,6 +1290,8 @@ int mml_launch_associate(mml_ctx* ctx, int first, int count, const double* d_Twl
     P.thres_d = thres_dist;
     // queue storage is sliced by slot index (2 * MF entries per slot), the counter by lane
     P.hard_count = ctx->d_misc + 32 + ctx->cur;
+    // (a top-level call starts on lane 0 -- mml_step's pieces follow in lane order --, so lane 0 opens a new count)
+    ctx->far_lanes = ctx->cur == 0 ? 1 : std::max(ctx->far_lanes, ctx->cur + 1);
     P.hard_list = ctx->hard_list + (size_t)first * ctx->MF * 2;
     P.hard_knn = ctx->hard_knn + (size_t)first * ctx->MF * 2 * 10;
     P.count = count;

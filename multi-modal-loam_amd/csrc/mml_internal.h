@@ -122,6 +122,7 @@ struct mml_ctx {
     std::vector<hipEvent_t> upload_event_pool;
     int n_lanes = 1;
     int cur = 0;
+    int far_lanes = 1;  // lanes whose far-query counters the last top-level association wrote (mml_associate_far_count)
     std::string err;
     MmlFixed fixed;  // owns every buffer below that mml_create allocates (the plain pointers without an owner named beside them)
 
