@@ -110,13 +110,7 @@ void mml_destroy(mml_ctx* ctx) {
         if (ctx->streams[l]) hipStreamSynchronize(ctx->streams[l]);
     if (ctx->copy_stream) hipStreamSynchronize(ctx->copy_stream);
     mml_comm_destroy(ctx);
-    mml_fullwindow_dev_release(ctx);
-    mml_imu_preint_release(ctx);
-    mml_lio_init_release(ctx);
-    mml_gicp_release(ctx);
-    mml_time_offset_release(ctx);
-    mml_union_release(ctx);
-    mml_velo_fov_release(ctx);
+    ctx->side.release();
     ctx->release_memory();
     for (auto& pe : ctx->pending) {
         hipEventDestroy(pe.a);
@@ -2101,6 +2095,14 @@ int mml_sync_all(mml_ctx* ctx) {
     MML_HIP(hipStreamSynchronize(ctx->copy_stream));
     for (auto& u : ctx->uploads) ctx->upload_event_pool.push_back(u.done);
     ctx->uploads.clear();
+    return MML_OK;
+}
+
+int mml_enter_idle(mml_ctx* ctx) {
+    MML_HIP(hipSetDevice(ctx->device));
+    int rc = mml_sync_all(ctx);
+    if (rc != MML_OK) return rc;
+    ctx->cur = 0;
     return MML_OK;
 }
 

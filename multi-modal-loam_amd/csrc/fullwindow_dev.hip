@@ -836,26 +836,16 @@ struct MmlFwDev {  // every buffer holds the largest batch its call has seen; th
     // mml_fullwindow_marginalize_batch
     MmlStaging<FwMargParams> mpar;
     MmlStaging<mml_prior> mout;
+    ~MmlFwDev() {
+        par.release();
+        state.release();
+        out.release();
+        alive.release();
+        rec0.release();
+        mpar.release();
+        mout.release();
+    }
 };
-
-static MmlFwDev* fw_dev(mml_ctx* ctx) {
-    if (!ctx->fwdev) ctx->fwdev = new MmlFwDev();
-    return ctx->fwdev;
-}
-
-void mml_fullwindow_dev_release(mml_ctx* ctx) {
-    MmlFwDev* d = ctx->fwdev;
-    if (!d) return;
-    d->par.release();
-    d->state.release();
-    d->out.release();
-    d->alive.release();
-    d->rec0.release();
-    d->mpar.release();
-    d->mout.release();
-    delete d;
-    ctx->fwdev = nullptr;
-}
 
 // n windows, window w in x + x_stride w; everything is checked before anything is enqueued
 static int fw_solve_batch(mml_ctx* ctx, const char* who, int n, mml_fullwindow* const* fws, const int* first_slot,
@@ -884,7 +874,7 @@ static int fw_solve_batch(mml_ctx* ctx, const char* who, int n, mml_fullwindow* 
             if (seen[i].first == seen[i - 1].first) return refuse(MML_ERR_INVALID, seen[i].second, "the same handle appears twice in the batch");
     }
     MML_HIP(hipSetDevice(ctx->device));
-    MmlFwDev* d = fw_dev(ctx);
+    MmlFwDev* d = mml_side<MmlFwDev>(ctx, MML_SIDE_FULLWINDOW);
     if (d->par.reserve(ctx, n) || d->state.reserve(ctx, n) || d->out.reserve(ctx, n) || d->alive.reserve(ctx, FW_MAX_ROUNDS) ||
         d->rec0.reserve(ctx, 32 * (size_t)n))
         return MML_ERR_HIP;
@@ -1031,7 +1021,7 @@ extern "C" int mml_fullwindow_marginalize_batch(mml_ctx* ctx, int n, mml_fullwin
         if (!fw->U_ok[1]) return refuse(MML_ERR_STATE, w, "pre-integration covariance is not positive definite");
     }
     MML_HIP(hipSetDevice(ctx->device));
-    MmlFwDev* d = fw_dev(ctx);
+    MmlFwDev* d = mml_side<MmlFwDev>(ctx, MML_SIDE_FULLWINDOW);
     if (d->mpar.reserve(ctx, n) || d->mout.reserve(ctx, n)) return MML_ERR_HIP;
     for (int w = 0; w < n; ++w) {  // only what the kernel reads is written (has_prior gates the prior)
         const mml_fullwindow* fw = fws[w];

@@ -791,41 +791,31 @@ __global__ void k_gicp_apply(float4* ln_pts, int first, int NT, int NV, const in
     pts[i] = p;
 }
 
-size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 // io block (device + pinned twin) of a call of n problems: what crosses the bus.  `pts`: the packed clouds of mml_gicp_align*,
 // which come from the host (the refresh gathers its clouds on the device, into the big block)
-struct IoLayout {
-    size_t tab, st, cnt, mat, napp, fi, cb, fl, pts, bytes;
-    IoLayout(size_t n, size_t n_pts) {
-        size_t o = 0;
-        const auto take = [&](size_t b) {
-            const size_t at = o;
-            o += align16(b);
-            return at;
-        };
-        tab = take(sizeof(GicpProb) * n);
-        st = take(sizeof(GicpState) * n);
-        cnt = take(sizeof(int) * 2 * n);
-        mat = take(sizeof(float) * 16 * n);
-        napp = take(sizeof(int) * n);
-        fi = take(sizeof(int) * 8 * n);
-        cb = take(sizeof(int) * 2 * n);
-        fl = take(sizeof(int) * 2 * n);
-        pts = take(sizeof(float4) * n_pts);
-        bytes = o;
-    }
+struct GicpIo {
+    MmlCarve<16> c;
+    MmlField<GicpProb> tab;
+    MmlField<GicpState> st;
+    MmlField<int> cnt;
+    MmlField<float> mat;
+    MmlField<int> napp, fi, cb, fl;
+    MmlField<float4> pts;
+    size_t bytes;
+    GicpIo(size_t n, size_t n_pts)
+        : tab(c.take<GicpProb>(n)), st(c.take<GicpState>(n)), cnt(c.take<int>(2 * n)), mat(c.take<float>(16 * n)), napp(c.take<int>(n)),
+          fi(c.take<int>(8 * n)), cb(c.take<int>(2 * n)), fl(c.take<int>(2 * n)), pts(c.take<float4>(n_pts)), bytes(c.bytes()) {}
 };
 // big block (device only): 72 bytes of covariance per point, 72 + 4 bytes per source point, and the refresh's 16 bytes per point
-struct BigLayout {
-    size_t pts, cov, maha, corr, bytes;
-    BigLayout(size_t n_pts, size_t n_srcs, bool with_pts) {
-        pts = 0;
-        cov = with_pts ? align16(sizeof(float4) * n_pts) : 0;
-        maha = cov + align16(sizeof(double) * 9 * n_pts);
-        corr = maha + align16(sizeof(double) * 9 * n_srcs);
-        bytes = corr + align16(sizeof(int) * n_srcs);
-    }
+struct GicpBig {
+    MmlCarve<16> c;
+    MmlField<float4> pts;
+    MmlField<double> cov, maha;
+    MmlField<int> corr;
+    size_t bytes;
+    GicpBig(size_t n_pts, size_t n_srcs, bool with_pts)
+        : pts(c.take<float4>(with_pts ? n_pts : 0)), cov(c.take<double>(9 * n_pts)), maha(c.take<double>(9 * n_srcs)), corr(c.take<int>(n_srcs)),
+          bytes(c.bytes()) {}
 };
 
 }  // namespace
@@ -835,23 +825,13 @@ struct BigLayout {
 struct MmlGicpDev {
     MmlStaging<char> io;
     MmlStaging<char, false> big;
+    ~MmlGicpDev() {
+        io.release();
+        big.release();
+    }
 };
 
-void mml_gicp_release(mml_ctx* ctx) {
-    MmlGicpDev* d = ctx->gicp;
-    if (!d) return;
-    d->io.release();
-    d->big.release();
-    delete d;
-    ctx->gicp = nullptr;
-}
-
 namespace {
-
-MmlGicpDev* gicp_dev(mml_ctx* ctx) {
-    if (!ctx->gicp) ctx->gicp = new MmlGicpDev();
-    return ctx->gicp;
-}
 
 // Lays problem `P` of ns source and nt target points out behind the n_pts points and n_srcs source points already placed.
 // PCL: "number of points smaller than k_correspondences_" -> no alignment: such a problem gets no room and n_src = n_tgt = 0.
@@ -902,14 +882,6 @@ void gicp_result(const GicpProb& P, const GicpState& h, float* T, int* converged
     }
 }
 
-int gicp_enter(mml_ctx* ctx) {
-    MML_HIP(hipSetDevice(ctx->device));
-    int rc = mml_sync_all(ctx);
-    if (rc != MML_OK) return rc;
-    ctx->cur = 0;
-    return MML_OK;
-}
-
 // The n alignments of mml_gicp_align_batch; mml_gicp_align is its n = 1 case.  `who`: the entry point the caller used, which
 // is the name a refusal carries.
 int gicp_align_n(mml_ctx* ctx, const char* who, int n, const float* src_xyz, const int* src_offsets, const float* tgt_xyz,
@@ -922,7 +894,7 @@ int gicp_align_n(mml_ctx* ctx, const char* who, int n, const float* src_xyz, con
             return mml_refuse(ctx, MML_ERR_INVALID, "%s: problem %d: its clouds end before their start (offsets must not decrease)", who, i);
     if ((src_offsets[n] > src_offsets[0] && !src_xyz) || (tgt_offsets[n] > tgt_offsets[0] && !tgt_xyz))
         return mml_refuse(ctx, MML_ERR_INVALID, "%s: a null cloud", who);
-    int rc = gicp_enter(ctx);
+    int rc = mml_enter_idle(ctx);
     if (rc != MML_OK) return rc;
     std::vector<GicpProb> tab((size_t)n);
     size_t n_pts = 0, n_srcs = 0;
@@ -933,16 +905,16 @@ int gicp_align_n(mml_ctx* ctx, const char* who, int n, const float* src_xyz, con
         max_tgt = tab[i].n_tgt > max_tgt ? tab[i].n_tgt : max_tgt;
     }
     if (n_pts > 0x7fffffffull) return mml_refuse(ctx, MML_ERR_CAPACITY, "%s: %zu points in one call", who, n_pts);
-    const IoLayout io((size_t)n, n_pts);
-    const BigLayout big(n_pts, n_srcs, false);
-    MmlGicpDev* d = gicp_dev(ctx);
+    const GicpIo io((size_t)n, n_pts);
+    const GicpBig big(n_pts, n_srcs, false);
+    MmlGicpDev* d = mml_side<MmlGicpDev>(ctx, MML_SIDE_GICP);
     if (n_pts > 0 && (d->io.reserve(ctx, io.bytes) || d->big.reserve(ctx, big.bytes))) return MML_ERR_HIP;
     GicpState* h_st = nullptr;
     if (n_pts > 0) {
         hipStream_t s = MML_STREAM(ctx);
         char *h = d->io.h, *g = d->io.d;
-        memcpy(h + io.tab, tab.data(), sizeof(GicpProb) * (size_t)n);
-        float4* hp = reinterpret_cast<float4*>(h + io.pts);
+        memcpy(io.tab.in(h), tab.data(), io.tab.bytes());
+        float4* hp = io.pts.in(h);
         for (int i = 0; i < n; ++i) {
             const GicpProb& P = tab[i];
             const float* a = src_xyz + 3 * (size_t)src_offsets[i];
@@ -950,12 +922,11 @@ int gicp_align_n(mml_ctx* ctx, const char* who, int n, const float* src_xyz, con
             for (int k = 0; k < P.n_src; ++k) hp[P.src + k] = make_float4(a[3 * k], a[3 * k + 1], a[3 * k + 2], 0.f);
             for (int k = 0; k < P.n_tgt; ++k) hp[P.tgt + k] = make_float4(b[3 * k], b[3 * k + 1], b[3 * k + 2], 0.f);
         }
-        MML_HIP(hipMemcpyAsync(g + io.tab, h + io.tab, sizeof(GicpProb) * (size_t)n, hipMemcpyHostToDevice, s));
-        MML_HIP(hipMemcpyAsync(g + io.pts, h + io.pts, sizeof(float4) * n_pts, hipMemcpyHostToDevice, s));
-        h_st = reinterpret_cast<GicpState*>(h + io.st);
-        rc = gicp_core(ctx, n, max_src, max_tgt, reinterpret_cast<const GicpProb*>(g + io.tab), reinterpret_cast<const float4*>(g + io.pts),
-                       reinterpret_cast<double*>(d->big.d + big.cov), reinterpret_cast<double*>(d->big.d + big.maha),
-                       reinterpret_cast<int*>(d->big.d + big.corr), reinterpret_cast<GicpState*>(g + io.st), h_st);
+        MML_HIP(hipMemcpyAsync(io.tab.in(g), io.tab.in(h), io.tab.bytes(), hipMemcpyHostToDevice, s));
+        MML_HIP(hipMemcpyAsync(io.pts.in(g), io.pts.in(h), io.pts.bytes(), hipMemcpyHostToDevice, s));
+        h_st = io.st.in(h);
+        rc = gicp_core(ctx, n, max_src, max_tgt, io.tab.in(g), io.pts.in(g), big.cov.in(d->big.d), big.maha.in(d->big.d), big.corr.in(d->big.d),
+                       io.st.in(g), h_st);
         if (rc != MML_OK) return rc;
     }
     const GicpState none = {};
@@ -992,7 +963,7 @@ int gicp_refresh_n(mml_ctx* ctx, const char* who, int first_slot, int count, flo
     if (count > ctx->B - first_slot)
         return mml_refuse(ctx, MML_ERR_INVALID, "%s: slot %d is outside the context's 0 .. %d", who, ctx->B, ctx->B - 1);
     if (!extrinsics) return mml_refuse(ctx, MML_ERR_INVALID, "%s: a null argument", who);
-    int rc = gicp_enter(ctx);
+    int rc = mml_enter_idle(ctx);
     if (rc != MML_OK) return rc;
     // (the gather and the apply below read and rewrite ln_pts / ln_label.  A partly undistorted slot carries the "undistorted" flag
     //  and is refused further down; it is settled all the same, so that no path into those kernels depends on that refusal)
@@ -1000,15 +971,15 @@ int gicp_refresh_n(mml_ctx* ctx, const char* who, int first_slot, int count, flo
     if (rc != MML_OK) return rc;
     hipStream_t s = MML_STREAM(ctx);
     const size_t n = (size_t)count, f = (size_t)first_slot;
-    const IoLayout io(n, 0);
-    MmlGicpDev* d = gicp_dev(ctx);
+    const GicpIo io(n, 0);
+    MmlGicpDev* d = mml_side<MmlGicpDev>(ctx, MML_SIDE_GICP);
     if (d->io.reserve(ctx, io.bytes)) return MML_ERR_HIP;
     char *h = d->io.h, *g = d->io.d;
     // counters, valid points per sensor region of the slots' storage, the slots' state flags
-    const int *fi = reinterpret_cast<const int*>(h + io.fi), *cb = reinterpret_cast<const int*>(h + io.cb), *fl = reinterpret_cast<const int*>(h + io.fl);
-    MML_HIP(hipMemcpyAsync(h + io.fi, ctx->fu_info + 8 * f, sizeof(int) * 8 * n, hipMemcpyDeviceToHost, s));
-    MML_HIP(hipMemcpyAsync(h + io.cb, ctx->cb_n + 2 * f, sizeof(int) * 2 * n, hipMemcpyDeviceToHost, s));
-    MML_HIP(hipMemcpyAsync(h + io.fl, ctx->slot_flags + 2 * f, sizeof(int) * 2 * n, hipMemcpyDeviceToHost, s));
+    const int *fi = io.fi.in(h), *cb = io.cb.in(h), *fl = io.fl.in(h);
+    MML_HIP(hipMemcpyAsync(io.fi.in(h), ctx->fu_info + 8 * f, io.fi.bytes(), hipMemcpyDeviceToHost, s));
+    MML_HIP(hipMemcpyAsync(io.cb.in(h), ctx->cb_n + 2 * f, io.cb.bytes(), hipMemcpyDeviceToHost, s));
+    MML_HIP(hipMemcpyAsync(io.fl.in(h), ctx->slot_flags + 2 * f, io.fl.bytes(), hipMemcpyDeviceToHost, s));
     MML_HIP(hipStreamSynchronize(s));
     for (int i = 0; i < count; ++i) {
         // the refresh belongs to the feature node: it aligns the surf clouds of the EXTRACTED scan (raw coordinates, raw order)
@@ -1042,11 +1013,11 @@ int gicp_refresh_n(mml_ctx* ctx, const char* who, int first_slot, int count, flo
             if (rc != MML_OK) return rc;
         }
         hipLaunchKernelGGL(k_gicp_gather_raw, dim3(2, count), dim3(64), 0, s, A, (const GicpProb*)nullptr, (float4*)nullptr,
-                           reinterpret_cast<int*>(g + io.cnt));
+                           io.cnt.in(g));
         MML_HIP(hipGetLastError());
-        MML_HIP(hipMemcpyAsync(h + io.cnt, g + io.cnt, sizeof(int) * 2 * n, hipMemcpyDeviceToHost, s));
+        MML_HIP(hipMemcpyAsync(io.cnt.in(h), io.cnt.in(g), io.cnt.bytes(), hipMemcpyDeviceToHost, s));
         MML_HIP(hipStreamSynchronize(s));
-        const int* cnt = reinterpret_cast<const int*>(h + io.cnt);
+        const int* cnt = io.cnt.in(h);
         int max_src = 0, max_tgt = 0;
         for (int i = 0; i < count; ++i) {  // source: Livox surf, target: Velodyne surf (:307)
             place_problem(tab[i], cnt[2 * i + 1], cnt[2 * i], n_pts, n_srcs);
@@ -1055,17 +1026,16 @@ int gicp_refresh_n(mml_ctx* ctx, const char* who, int first_slot, int count, flo
         }
         if (n_pts > 0x7fffffffull) return mml_refuse(ctx, MML_ERR_CAPACITY, "%s: %zu surf points in one call", who, n_pts);
         if (n_pts > 0) {
-            const BigLayout big(n_pts, n_srcs, true);
+            const GicpBig big(n_pts, n_srcs, true);
             if (d->big.reserve(ctx, big.bytes)) return MML_ERR_HIP;  // (no slot has been touched yet)
-            memcpy(h + io.tab, tab.data(), sizeof(GicpProb) * n);
-            MML_HIP(hipMemcpyAsync(g + io.tab, h + io.tab, sizeof(GicpProb) * n, hipMemcpyHostToDevice, s));
-            const GicpProb* d_tab = reinterpret_cast<const GicpProb*>(g + io.tab);
-            float4* pts = reinterpret_cast<float4*>(d->big.d + big.pts);
+            memcpy(io.tab.in(h), tab.data(), io.tab.bytes());
+            MML_HIP(hipMemcpyAsync(io.tab.in(g), io.tab.in(h), io.tab.bytes(), hipMemcpyHostToDevice, s));
+            const GicpProb* d_tab = io.tab.in(g);
+            float4* pts = big.pts.in(d->big.d);
             hipLaunchKernelGGL(k_gicp_gather_raw, dim3(2, count), dim3(64), 0, s, A, d_tab, pts, (int*)nullptr);
-            GicpState* hs = reinterpret_cast<GicpState*>(h + io.st);
-            rc = gicp_core(ctx, count, max_src, max_tgt, d_tab, pts, reinterpret_cast<double*>(d->big.d + big.cov),
-                           reinterpret_cast<double*>(d->big.d + big.maha), reinterpret_cast<int*>(d->big.d + big.corr),
-                           reinterpret_cast<GicpState*>(g + io.st), hs);
+            GicpState* hs = io.st.in(h);
+            rc = gicp_core(ctx, count, max_src, max_tgt, d_tab, pts, big.cov.in(d->big.d), big.maha.in(d->big.d), big.corr.in(d->big.d), io.st.in(g),
+                           hs);
             if (rc != MML_OK) return rc;
             h_st = hs;
         }
@@ -1073,8 +1043,8 @@ int gicp_refresh_n(mml_ctx* ctx, const char* who, int first_slot, int count, flo
     // extri_mtx through the frames: a frame that converged replaces it, every other frame keeps what the frame before it left
     // (chained), or its own row (not chained)
     const GicpState none = {};
-    float* h_mat = reinterpret_cast<float*>(h + io.mat);
-    int* h_napp = reinterpret_cast<int*>(h + io.napp);
+    float* h_mat = io.mat.in(h);
+    int* h_napp = io.napp.in(h);
     int max_app = 0;
     for (int i = 0; i < count; ++i) {
         float* row = extrinsics + 16 * (size_t)i;
@@ -1088,9 +1058,10 @@ int gicp_refresh_n(mml_ctx* ctx, const char* who, int first_slot, int count, flo
         max_app = h_napp[i] > max_app ? h_napp[i] : max_app;
     }
     if (max_app > 0) {
-        MML_HIP(hipMemcpyAsync(g + io.mat, h + io.mat, io.fi - io.mat, hipMemcpyHostToDevice, s));  // matrices | point counts
+        // matrices | point counts: one copy, up to the field behind them
+        MML_HIP(hipMemcpyAsync(io.mat.in(g), io.mat.in(h), io.fi.off - io.mat.off, hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_gicp_apply, dim3((max_app + 255) / 256, count), dim3(256), 0, s, ctx->ln_pts, first_slot, ctx->NT, ctx->NV,
-                           reinterpret_cast<const int*>(g + io.napp), reinterpret_cast<const float*>(g + io.mat));
+                           io.napp.in(g), io.mat.in(g));
         MML_HIP(hipGetLastError());
         MML_HIP(hipStreamSynchronize(s));
     }

@@ -3,7 +3,7 @@
 // runs k_imu_preintegrate, one workgroup of one wavefront per interval -- Jacobian, covariance and the per-sample blocks stay
 // in LDS for the whole chain over the samples (13.0 KB, so twelve intervals are resident on a CU) and are written once at the
 // end.  One upload (offsets | biases | samples from one pinned block), one launch, one read-back; the input block and the
-// output array are MmlStaging pairs (mml_mem.h), refusals go through mml_refuse.
+// output array are MmlStaging pairs, the block laid out by MmlCarve (mml_mem.h), refusals go through mml_refuse.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -27,16 +27,11 @@ __global__ __launch_bounds__(64) void k_imu_preintegrate(const double* samples, 
 struct MmlPreintDev {  // each sized for the largest call seen
     MmlStaging<char> in;  // offsets | biases | samples, in bytes
     MmlStaging<mml_imu_preint> out;
+    ~MmlPreintDev() {
+        in.release();
+        out.release();
+    }
 };
-
-void mml_imu_preint_release(mml_ctx* ctx) {
-    MmlPreintDev* d = ctx->preint;
-    if (!d) return;
-    d->in.release();
-    d->out.release();
-    delete d;
-    ctx->preint = nullptr;
-}
 
 extern "C" int mml_imu_preintegrate_batch(mml_ctx* ctx, int n, const double* samples, const int* offsets, const double* bg,
                                           const double* ba, mml_imu_preint* out) {
@@ -55,23 +50,22 @@ extern "C" int mml_imu_preintegrate_batch(mml_ctx* ctx, int n, const double* sam
     }
     MML_HIP(hipSetDevice(ctx->device));
     const size_t total = (size_t)offsets[n];
-    const size_t off_bytes = (sizeof(int) * ((size_t)n + 1) + 7) & ~(size_t)7, bias_bytes = sizeof(double) * 6 * (size_t)n;
-    const size_t in_bytes = off_bytes + bias_bytes + sizeof(double) * 7 * total;
-    if (!ctx->preint) ctx->preint = new MmlPreintDev();
-    MmlPreintDev* d = ctx->preint;
-    if (d->in.reserve(ctx, in_bytes) || d->out.reserve(ctx, n)) return MML_ERR_HIP;
-    memcpy(d->in.h, offsets, sizeof(int) * ((size_t)n + 1));
-    double* h_bias = reinterpret_cast<double*>(d->in.h + off_bytes);
+    MmlCarve<8> c;
+    const auto off = c.take<int>((size_t)n + 1);
+    const auto bias = c.take<double>(6 * (size_t)n), smp = c.take<double>(7 * total);
+    MmlPreintDev* d = mml_side<MmlPreintDev>(ctx, MML_SIDE_PREINT);
+    if (d->in.reserve(ctx, c.bytes()) || d->out.reserve(ctx, n)) return MML_ERR_HIP;
+    memcpy(off.in(d->in.h), offsets, off.bytes());
+    double* h_bias = bias.in(d->in.h);
     for (int i = 0; i < n; ++i) {
         memcpy(h_bias + 6 * (size_t)i, bg + 3 * (size_t)i, sizeof(double) * 3);
         memcpy(h_bias + 6 * (size_t)i + 3, ba + 3 * (size_t)i, sizeof(double) * 3);
     }
-    if (total) memcpy(d->in.h + off_bytes + bias_bytes, samples, sizeof(double) * 7 * total);
+    if (total) memcpy(smp.in(d->in.h), samples, smp.bytes());
     hipStream_t s = MML_STREAM(ctx);
     MmlStageScope t(ctx, "imu_preintegrate");
-    MML_HIP(hipMemcpyAsync(d->in.d, d->in.h, in_bytes, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_imu_preintegrate, dim3(n), dim3(64), 0, s, reinterpret_cast<const double*>(d->in.d + off_bytes + bias_bytes),
-                       reinterpret_cast<const int*>(d->in.d), reinterpret_cast<const double*>(d->in.d + off_bytes), d->out.d);
+    MML_HIP(hipMemcpyAsync(d->in.d, d->in.h, c.bytes(), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_imu_preintegrate, dim3(n), dim3(64), 0, s, smp.in(d->in.d), off.in(d->in.d), bias.in(d->in.d), d->out.d);
     MML_HIP(hipGetLastError());
     MML_HIP(hipMemcpyAsync(d->out.h, d->out.d, sizeof(mml_imu_preint) * n, hipMemcpyDeviceToHost, s));
     MML_HIP(hipStreamSynchronize(s));

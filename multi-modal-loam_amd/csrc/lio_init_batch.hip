@@ -8,7 +8,7 @@
 //   k_lio_preint      again over the marked frames, reading the new biases from the state the kernel before it wrote
 // -- between ONE upload (offsets | times | extrinsics | samples | marks | state, and the given pre-integrations, from one pinned
 // block) and ONE read-back (state | results | pre-integrations).  The host applies a segment's bytes unless its status is 3.
-// The block is an MmlStaging pair (mml_mem.h), refusals go through mml_refuse.
+// The block is an MmlStaging pair laid out by MmlCarve (mml_mem.h), refusals go through mml_refuse.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -43,21 +43,12 @@ __global__ __launch_bounds__(64) void k_lio_initialize(const int* frame_offsets,
     MARG_FOR(i, n) go[f0 + i] = (status == 0 && i >= 1) ? 1 : 0;
 }
 
-size_t align8(size_t b) { return (b + 7) & ~(size_t)7; }
-
 }  // namespace
 
 struct MmlLioDev {
     MmlStaging<char> blk;  // sized for the largest call seen
+    ~MmlLioDev() { blk.release(); }
 };
-
-void mml_lio_init_release(mml_ctx* ctx) {
-    MmlLioDev* d = ctx->lio;
-    if (!d) return;
-    d->blk.release();
-    delete d;
-    ctx->lio = nullptr;
-}
 
 extern "C" int mml_lio_initialize_batch(mml_ctx* ctx, int n_seg, const int* frame_offsets, const double* t, double* P, double* Q, double* V,
                                         double* bg, double* ba, const double* samples, const int* sample_offsets, const double* exTlb,
@@ -120,72 +111,64 @@ extern "C" int mml_lio_initialize_batch(mml_ctx* ctx, int n_seg, const int* fram
     MML_HIP(hipSetDevice(ctx->device));
     // the block: [frame_offsets | sample_offsets | t | exTlb | samples | go] in only, [P | Q | V | bg | ba] both ways,
     // [out | pre] out (pre also in when pre_in is given)
-    size_t o = 0;
-    const auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += align8(bytes);
-        return at;
-    };
-    const size_t o_fo = take(sizeof(int) * ((size_t)n_seg + 1)), o_so = take(sizeof(int) * ((size_t)F + 1)), o_t = take(sizeof(double) * F),
-                 o_ex = take(sizeof(double) * 16 * n_seg), o_smp = take(sizeof(double) * 7 * total), o_go = take(sizeof(int) * F),
-                 o_P = take(sizeof(double) * 3 * F), o_Q = take(sizeof(double) * 4 * F), o_V = take(sizeof(double) * 3 * F),
-                 o_bg = take(sizeof(double) * 3 * F), o_ba = take(sizeof(double) * 3 * F), o_out = take(sizeof(mml_lio_init_result) * n_seg),
-                 o_pre = take(sizeof(mml_imu_preint) * F), bytes = o;
-    if (!ctx->lio) ctx->lio = new MmlLioDev();
-    MmlLioDev* d = ctx->lio;
+    const size_t nf = (size_t)F, ns = (size_t)n_seg;
+    MmlCarve<8> c;
+    const auto fo = c.take<int>(ns + 1), so = c.take<int>(nf + 1);
+    const auto tt = c.take<double>(nf), ex = c.take<double>(16 * ns), smp = c.take<double>(7 * total);
+    const auto go = c.take<int>(nf);
+    const auto fP = c.take<double>(3 * nf), fQ = c.take<double>(4 * nf), fV = c.take<double>(3 * nf), fbg = c.take<double>(3 * nf),
+               fba = c.take<double>(3 * nf);
+    const auto res = c.take<mml_lio_init_result>(ns);
+    const auto pre = c.take<mml_imu_preint>(nf);
+    const size_t bytes = c.bytes();
+    MmlLioDev* d = mml_side<MmlLioDev>(ctx, MML_SIDE_LIO);
     if (d->blk.reserve(ctx, bytes)) return MML_ERR_HIP;
     char* h = d->blk.h;
     char* g = d->blk.d;
-    memcpy(h + o_fo, frame_offsets, sizeof(int) * ((size_t)n_seg + 1));
-    memcpy(h + o_so, sample_offsets, sizeof(int) * ((size_t)F + 1));
-    memcpy(h + o_t, t, sizeof(double) * F);
-    memcpy(h + o_ex, exTlb, sizeof(double) * 16 * n_seg);
-    memcpy(h + o_smp, samples, sizeof(double) * 7 * total);
-    int* h_go = reinterpret_cast<int*>(h + o_go);
+    memcpy(fo.in(h), frame_offsets, fo.bytes());
+    memcpy(so.in(h), sample_offsets, so.bytes());
+    memcpy(tt.in(h), t, tt.bytes());
+    memcpy(ex.in(h), exTlb, ex.bytes());
+    memcpy(smp.in(h), samples, smp.bytes());
+    int* h_go = go.in(h);
     for (int f = 0; f < F; ++f) h_go[f] = 1;
     for (int s = 0; s < n_seg; ++s) h_go[frame_offsets[s]] = 0;
-    memcpy(h + o_P, P, sizeof(double) * 3 * F);
-    memcpy(h + o_Q, Q, sizeof(double) * 4 * F);
-    memcpy(h + o_V, V, sizeof(double) * 3 * F);
-    memcpy(h + o_bg, bg, sizeof(double) * 3 * F);
-    memcpy(h + o_ba, ba, sizeof(double) * 3 * F);
-    size_t up = o_out;
+    memcpy(fP.in(h), P, fP.bytes());
+    memcpy(fQ.in(h), Q, fQ.bytes());
+    memcpy(fV.in(h), V, fV.bytes());
+    memcpy(fbg.in(h), bg, fbg.bytes());
+    memcpy(fba.in(h), ba, fba.bytes());
+    size_t up = res.off;  // everything in front of the results ...
     if (pre_in) {
-        memset(h + o_out, 0, o_pre - o_out);
-        memcpy(h + o_pre, pre_in, sizeof(mml_imu_preint) * F);
-        up = bytes;
+        memset(h + res.off, 0, pre.off - res.off);
+        memcpy(pre.in(h), pre_in, pre.bytes());
+        up = bytes;  // ... or the whole block
     }
     hipStream_t st = MML_STREAM(ctx);
     MmlStageScope scope(ctx, "lio_initialize");
-    const int* g_so = reinterpret_cast<const int*>(g + o_so);
-    const double* g_smp = reinterpret_cast<const double*>(g + o_smp);
-    double *g_bg = reinterpret_cast<double*>(g + o_bg), *g_ba = reinterpret_cast<double*>(g + o_ba);
-    int* g_go = reinterpret_cast<int*>(g + o_go);
-    mml_imu_preint* g_pre = reinterpret_cast<mml_imu_preint*>(g + o_pre);
     MML_HIP(hipMemcpyAsync(g, h, up, hipMemcpyHostToDevice, st));
     if (!pre_in) {
-        hipLaunchKernelGGL(k_lio_preint, dim3(F), dim3(64), 0, st, g_smp, g_so, g_bg, g_ba, g_go, g_pre);
+        hipLaunchKernelGGL(k_lio_preint, dim3(F), dim3(64), 0, st, smp.in(g), so.in(g), fbg.in(g), fba.in(g), go.in(g), pre.in(g));
         MML_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_lio_initialize, dim3(n_seg), dim3(64), 0, st, reinterpret_cast<const int*>(g + o_fo), reinterpret_cast<const double*>(g + o_t),
-                       reinterpret_cast<double*>(g + o_P), reinterpret_cast<double*>(g + o_Q), reinterpret_cast<double*>(g + o_V), g_bg, g_ba, g_smp, g_so,
-                       reinterpret_cast<const double*>(g + o_ex), g_pre, g_go, reinterpret_cast<mml_lio_init_result*>(g + o_out));
+    hipLaunchKernelGGL(k_lio_initialize, dim3(n_seg), dim3(64), 0, st, fo.in(g), tt.in(g), fP.in(g), fQ.in(g), fV.in(g), fbg.in(g), fba.in(g),
+                       smp.in(g), so.in(g), ex.in(g), pre.in(g), go.in(g), res.in(g));
     MML_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_lio_preint, dim3(F), dim3(64), 0, st, g_smp, g_so, g_bg, g_ba, g_go, g_pre);
+    hipLaunchKernelGGL(k_lio_preint, dim3(F), dim3(64), 0, st, smp.in(g), so.in(g), fbg.in(g), fba.in(g), go.in(g), pre.in(g));
     MML_HIP(hipGetLastError());
-    MML_HIP(hipMemcpyAsync(h + o_P, g + o_P, bytes - o_P, hipMemcpyDeviceToHost, st));
+    MML_HIP(hipMemcpyAsync(h + fP.off, g + fP.off, bytes - fP.off, hipMemcpyDeviceToHost, st));  // state | results | pre-integrations
     MML_HIP(hipStreamSynchronize(st));
-    const mml_lio_init_result* h_out = reinterpret_cast<const mml_lio_init_result*>(h + o_out);
-    const mml_imu_preint* h_pre = reinterpret_cast<const mml_imu_preint*>(h + o_pre);
+    const mml_lio_init_result* h_out = res.in(h);
+    const mml_imu_preint* h_pre = pre.in(h);
     for (int s = 0; s < n_seg; ++s) {
         memcpy(out + s, h_out + s, sizeof(mml_lio_init_result));  // (bytes: the padding too)
         if (h_out[s].status == 3) continue;
         const size_t f0 = (size_t)frame_offsets[s], n = (size_t)frame_offsets[s + 1] - f0;
-        memcpy(P + 3 * f0, h + o_P + sizeof(double) * 3 * f0, sizeof(double) * 3 * n);
-        memcpy(Q + 4 * f0, h + o_Q + sizeof(double) * 4 * f0, sizeof(double) * 4 * n);
-        memcpy(V + 3 * f0, h + o_V + sizeof(double) * 3 * f0, sizeof(double) * 3 * n);
-        memcpy(bg + 3 * f0, h + o_bg + sizeof(double) * 3 * f0, sizeof(double) * 3 * n);
-        memcpy(ba + 3 * f0, h + o_ba + sizeof(double) * 3 * f0, sizeof(double) * 3 * n);
+        memcpy(P + 3 * f0, fP.in(h) + 3 * f0, sizeof(double) * 3 * n);
+        memcpy(Q + 4 * f0, fQ.in(h) + 4 * f0, sizeof(double) * 4 * n);
+        memcpy(V + 3 * f0, fV.in(h) + 3 * f0, sizeof(double) * 3 * n);
+        memcpy(bg + 3 * f0, fbg.in(h) + 3 * f0, sizeof(double) * 3 * n);
+        memcpy(ba + 3 * f0, fba.in(h) + 3 * f0, sizeof(double) * 3 * n);
         if (pre_out) memcpy(pre_out + f0 + 1, h_pre + f0 + 1, sizeof(mml_imu_preint) * (n - 1));
     }
     return MML_OK;

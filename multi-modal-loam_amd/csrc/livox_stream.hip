@@ -29,17 +29,12 @@ struct mml_livox_stream {
 // the call drains the stream before it returns, so reserve() never replaces a buffer in use.
 struct MmlUnionDev {
     MmlStaging<char> io;
-    MmlStaging<char, false> velo;
+    MmlStaging<float4, false> velo;
+    ~MmlUnionDev() {
+        io.release();
+        velo.release();
+    }
 };
-
-void mml_union_release(mml_ctx* ctx) {
-    MmlUnionDev* d = ctx->uni;
-    if (!d) return;
-    d->io.release();
-    d->velo.release();
-    delete d;
-    ctx->uni = nullptr;
-}
 
 namespace {
 
@@ -179,21 +174,19 @@ __global__ __launch_bounds__(256) void k_union_gather(const mml_union_frame* __r
     }
 }
 
-size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
-
-// io block: what goes down in one copy (stamps, offsets, tf), then what comes back in one copy (the rows and the verdict)
+// io block: what goes down in one copy (stamps, offsets, tf), then what comes back in one copy (the rows with the verdict
+// directly behind them: 32-byte rows, so it is 8-byte aligned)
 struct UnionIo {
-    size_t stamps, voff, tf, down_bytes, rows, verdict, up_bytes, bytes;
-    explicit UnionIo(size_t count) {
-        stamps = 0;
-        voff = stamps + align256(sizeof(uint64_t) * (count + 1));
-        tf = voff + align256(sizeof(int) * (count + 1));
-        down_bytes = tf + align256(sizeof(float) * 16);
-        rows = down_bytes;
-        verdict = rows + sizeof(mml_union_frame) * count;  // (32-byte rows: 8-byte aligned)
-        up_bytes = verdict + sizeof(unsigned long long) - rows;
-        bytes = align256(verdict + sizeof(unsigned long long));
-    }
+    MmlCarve<256> c;
+    MmlField<uint64_t> stamps;
+    MmlField<int> voff;
+    MmlField<float> tf;
+    MmlField<mml_union_frame> rows;
+    MmlField<unsigned long long> verdict;
+    size_t down_bytes, up_bytes, bytes;
+    explicit UnionIo(size_t count)
+        : stamps(c.take<uint64_t>(count + 1)), voff(c.take<int>(count + 1)), tf(c.take<float>(16)), rows(c.take<mml_union_frame>(count)),
+          verdict(c.pack<unsigned long long>(1)), down_bytes(rows.off), up_bytes(verdict.end() - rows.off), bytes(c.bytes()) {}
 };
 
 // Room for n more points: when the current array's end would be passed, the live part moves to the front of the other array.
@@ -283,22 +276,21 @@ int mml_union_run(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int count, 
     int max_nv = 0;
     for (int i = 0; i < count; ++i) max_nv = vo[i + 1] - vo[i] > max_nv ? vo[i + 1] - vo[i] : max_nv;
     const UnionIo io((size_t)count);
-    if (!ctx->uni) ctx->uni = new MmlUnionDev();
-    MmlUnionDev* u = ctx->uni;
-    if (u->io.reserve(ctx, io.bytes) || u->velo.reserve(ctx, sizeof(float4) * (nv ? nv : 1))) {
+    MmlUnionDev* u = mml_side<MmlUnionDev>(ctx, MML_SIDE_UNION);
+    if (u->io.reserve(ctx, io.bytes) || u->velo.reserve(ctx, nv ? nv : 1)) {
         ctx->err = "mml_union_assemble: the staging block could not be grown: " + ctx->err;
         return MML_ERR_HIP;
     }
     hipStream_t st = MML_STREAM(ctx);
     char *h = u->io.h, *g = u->io.d;
-    memcpy(h + io.stamps, stamps, sizeof(uint64_t) * ((size_t)count + 1));
-    memcpy(h + io.voff, vo, sizeof(int) * ((size_t)count + 1));
-    if (tf) memcpy(h + io.tf, tf, sizeof(float) * 16);
-    const uint64_t* d_stamps = reinterpret_cast<const uint64_t*>(g + io.stamps);
-    const int* d_voff = reinterpret_cast<const int*>(g + io.voff);
-    const float* d_tf = tf ? reinterpret_cast<const float*>(g + io.tf) : nullptr;
-    mml_union_frame* d_rows = reinterpret_cast<mml_union_frame*>(g + io.rows);
-    unsigned long long* d_verdict = reinterpret_cast<unsigned long long*>(g + io.verdict);
+    memcpy(io.stamps.in(h), stamps, io.stamps.bytes());
+    memcpy(io.voff.in(h), vo, io.voff.bytes());
+    if (tf) memcpy(io.tf.in(h), tf, io.tf.bytes());
+    const uint64_t* d_stamps = io.stamps.in(g);
+    const int* d_voff = io.voff.in(g);
+    const float* d_tf = tf ? io.tf.in(g) : nullptr;
+    mml_union_frame* d_rows = io.rows.in(g);
+    unsigned long long* d_verdict = io.verdict.in(g);
     // a frame holds at most max_livox_points points, and no more than the queue does
     const long live = s->tail - s->front;
     const long most = live < (long)ctx->cfg.max_livox_points ? live : (long)ctx->cfg.max_livox_points;
@@ -316,18 +308,18 @@ int mml_union_run(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int count, 
     {   // the call's ONE host synchronisation: the rows and the verdict in one copy
         MmlStageScope t(ctx, "union_gather");
         hipLaunchKernelGGL(k_union_gather, dim3((unsigned)(gl + gv), (unsigned)count), dim3(256), 0, st, d_rows, d_verdict, s->rec[s->cur],
-                           s->stamp[s->cur], s->base, s->hs, d_stamps, reinterpret_cast<const float4*>(u->velo.d), d_voff, d_tf, first_slot, gl,
+                           s->stamp[s->cur], s->base, s->hs, d_stamps, u->velo.d, d_voff, d_tf, first_slot, gl,
                            ctx->velo_in, ctx->NV, reinterpret_cast<uint32_t*>(ctx->livox_in), ctx->NL);
         MML_HIP(hipGetLastError());
-        MML_HIP(hipMemcpyAsync(h + io.rows, g + io.rows, io.up_bytes, hipMemcpyDeviceToHost, st));
+        MML_HIP(hipMemcpyAsync(io.rows.in(h), d_rows, io.up_bytes, hipMemcpyDeviceToHost, st));
     }
     MML_HIP(hipStreamSynchronize(st));
     unsigned long long bad = 0;
-    memcpy(&bad, h + io.verdict, sizeof(bad));
+    memcpy(&bad, io.verdict.in(h), sizeof(bad));
     if (bad)
         return mml_refuse(ctx, MML_ERR_STATE, "mml_union_assemble: the stream holds %llu points older than the point before them; nothing was written",
                           bad);
-    memcpy(out, h + io.rows, sizeof(mml_union_frame) * (size_t)count);
+    memcpy(out, io.rows.in(h), io.rows.bytes());
     s->front = out[count - 1].front_after;
     for (int i = 0; i < count; ++i) {
         ctx->h_n_in[2 * (first_slot + i)] = vo[i + 1] - vo[i];

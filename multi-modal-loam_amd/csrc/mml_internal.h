@@ -67,24 +67,23 @@ struct MmlStageTimer {
 };
 
 struct MmlComm;   // comm.hip: RCCL communicator + window-solve buffers
-struct MmlFwDev;  // fullwindow_dev.hip: parameter / scratch buffers of the device-resident full-window solve
-struct MmlPreintDev;  // imu_preint.hip: buffers of mml_imu_preintegrate_batch
-struct MmlLioDev;     // lio_init_batch.hip: the block of mml_lio_initialize_batch
-struct MmlGicpDev;    // gicp.hip: the blocks of the GICP alignments (single and batch calls)
-struct MmlTofsDev;    // time_offset.hip: the blocks of the time-offset searches (single and batch calls)
-struct MmlUnionDev;   // livox_stream.hip: the staging blocks of mml_union_assemble
-struct MmlVfovDev;    // velo_fov.hip: the blocks of the Velodyne FOV selection (single and batch calls)
+// the side calls' scratch structs, each defined in its own file and kept in mml_ctx::side (mml_side below); mml_destroy releases
+// them in this order
+enum MmlSideId {
+    MML_SIDE_FULLWINDOW,   // fullwindow_dev.hip MmlFwDev: parameter / scratch buffers of the device-resident full-window solve
+    MML_SIDE_PREINT,       // imu_preint.hip MmlPreintDev: buffers of mml_imu_preintegrate_batch
+    MML_SIDE_LIO,          // lio_init_batch.hip MmlLioDev: the block of mml_lio_initialize_batch
+    MML_SIDE_GICP,         // gicp.hip MmlGicpDev: the blocks of the GICP alignments (single and batch calls)
+    MML_SIDE_TIME_OFFSET,  // time_offset.hip MmlTofsDev: the blocks of the time-offset searches (single and batch calls)
+    MML_SIDE_UNION,        // livox_stream.hip MmlUnionDev: the staging blocks of mml_union_assemble
+    MML_SIDE_VELO_FOV,     // velo_fov.hip MmlVfovDev: the blocks of the Velodyne FOV selection (single and batch calls)
+    MML_SIDE_COUNT
+};
 
 struct mml_ctx {
     mml_config cfg;
     MmlComm* comm = nullptr;
-    MmlFwDev* fwdev = nullptr;
-    MmlPreintDev* preint = nullptr;
-    MmlLioDev* lio = nullptr;
-    MmlGicpDev* gicp = nullptr;
-    MmlTofsDev* tofs = nullptr;
-    MmlUnionDev* uni = nullptr;
-    MmlVfovDev* vfov = nullptr;
+    MmlSides<MML_SIDE_COUNT> side;
     // frame-parallel window solve (solve.hip): one state machine copy, 4 counters and two record buffers per slot
     void* wstate = nullptr;
     double* wrec = nullptr;
@@ -322,6 +321,14 @@ __host__ __device__ inline bool mml_voxel_grid_overflows(const float* mn, const 
 }
 #define MML_STREAM(ctx) ((ctx)->streams[(ctx)->cur])
 int mml_sync_all(mml_ctx* ctx);
+// For a call that reads no slot and wants an idle device: selects the context's device, ends everything the context has in
+// flight -- every lane of a pipelined mml_step and the upload stream -- and makes lane 0 the current one.  capi.hip.
+int mml_enter_idle(mml_ctx* ctx);
+// the scratch struct D of side call `id`, created on first use
+template <class D>
+D* mml_side(mml_ctx* ctx, MmlSideId id) {
+    return ctx->side.get<D>(id);
+}
 double* mml_stage_alloc(mml_ctx* ctx, size_t doubles);  // pinned staging ring (capi.hip): small read-backs land here
 int mml_uploads_wait(mml_ctx* ctx, int first, int count);
 
@@ -393,13 +400,6 @@ int mml_launch_solve(mml_ctx* ctx, int first, int count, int window, const doubl
                      bool want_trace, const double* d_x_in = nullptr, double* d_result = nullptr);
 int mml_window_solve_continue(mml_ctx* ctx, int first, int count, int window, const double* d_Tbl, mml_solve_opts opts);
 int mml_feature_init(mml_ctx* ctx);
-void mml_fullwindow_dev_release(mml_ctx* ctx);
-void mml_imu_preint_release(mml_ctx* ctx);
-void mml_lio_init_release(mml_ctx* ctx);
-void mml_gicp_release(mml_ctx* ctx);
-void mml_time_offset_release(mml_ctx* ctx);
-void mml_union_release(mml_ctx* ctx);
-void mml_velo_fov_release(mml_ctx* ctx);
 // mml_union_assemble (livox_stream.hip): the host-only checks, then -- after the entry point's slot checks -- the device part
 int mml_union_check(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int count, const uint64_t* stamps, const float* velo_xyzi,
                     const int* velo_offsets, mml_union_frame* out);

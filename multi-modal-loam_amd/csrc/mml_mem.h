@@ -1,6 +1,8 @@
 // mml_mem.h -- the one place of libmmloam_hip.so that allocates and frees device and pinned memory.  Four owners, one per
 // lifetime: MmlFixed (allocated by a create call, freed by its destroy), MmlStaging (grow-only), MmlGroup (several buffers that
-// exist together or not at all) and MmlTemp (one call).  Host code only: a program without kernels can include it.
+// exist together or not at all) and MmlTemp (one call).  Beside them the two things every batched side call builds on them:
+// MmlCarve, which lays typed arrays out in one block and is the only code that casts block memory, and MmlSides, which holds the
+// side calls' scratch structs for the context and deletes them in one loop.  Host code only: a program without kernels can include it.
 // `Ctx` in the calls below is whatever carries the error text in a std::string `err` (mml_ctx in the library).
 #ifndef MML_MEM_H
 #define MML_MEM_H
@@ -124,6 +126,61 @@ struct MmlTemp {
         const hipError_t e = hipMalloc(reinterpret_cast<void**>(&d), sizeof(T) * n);
         if (e != hipSuccess) d = nullptr;
         return e;
+    }
+};
+
+// One block carved into typed arrays.  A field knows where it lies and how many elements it has, so that an array's type and
+// count are written once: in(base) is the array inside the pinned twin or the device block alike, bytes() its size for a copy.
+template <class T>
+struct MmlField {
+    size_t off = 0, n = 0;  // bytes from the block's start | elements
+    size_t bytes() const { return sizeof(T) * n; }
+    size_t end() const { return off + bytes(); }
+    T* in(void* base) const { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
+};
+// The cursor that hands the fields out, front to back.  take() starts a field on the next multiple of Align (a power of two),
+// pack() directly behind the field before it; a field of no elements takes no room.  bytes(): the block, a multiple of Align.
+template <size_t Align>
+struct MmlCarve {
+    size_t last = 0;  // end of the last field
+    static size_t up(size_t b) { return (b + (Align - 1)) & ~(Align - 1); }
+    template <class T>
+    MmlField<T> take(size_t n) {
+        const MmlField<T> f{up(last), n};
+        last = f.end();
+        return f;
+    }
+    template <class T>
+    MmlField<T> pack(size_t n) {
+        const MmlField<T> f{last, n};
+        last = f.end();
+        return f;
+    }
+    size_t bytes() const { return up(last); }
+};
+
+// The scratch structs of the side calls (the batched calls beside the scan pipeline), one slot per call family.  get<D>(i)
+// creates slot i's struct on first use; release() deletes them all, and a struct's destructor releases its own buffers.
+template <int N>
+struct MmlSides {
+    struct Slot {
+        void* p = nullptr;
+        void (*drop)(void*) = nullptr;
+    } slot[N];
+    template <class D>
+    static void drop_as(void* p) {
+        delete static_cast<D*>(p);
+    }
+    template <class D>
+    D* get(int i) {
+        if (!slot[i].p) slot[i] = Slot{new D(), &drop_as<D>};
+        return static_cast<D*>(slot[i].p);
+    }
+    void release() {
+        for (Slot& s : slot) {
+            if (s.p) s.drop(s.p);
+            s = Slot{};
+        }
     }
 };
 

@@ -325,50 +325,34 @@ void tofs_choose_grid(const float* box, int m, MmlGrid& g) {
     g.ncell = (int)total;
 }
 
-size_t align256(size_t b) { return (b + 255) & ~size_t(255); }
-
 // io block (device + pinned twin): what crosses the bus in small pieces, and the window errors
-struct IoLayout {
-    size_t tab, tf, box, woff, best, err, bytes;
-    IoLayout(size_t n, size_t n_win) {
-        size_t o = 0;
-        const auto take = [&](size_t b) {
-            const size_t at = o;
-            o += align256(b);
-            return at;
-        };
-        tab = take(sizeof(TofsProb) * n);
-        tf = take(sizeof(float) * 16 * n);
-        box = take(sizeof(float) * 6 * n);
-        woff = take(sizeof(long long) * (n + 1));
-        best = take(sizeof(TofsBest) * n);
-        err = take(sizeof(double) * n_win);
-        bytes = o;
-    }
+struct TofsIo {
+    MmlCarve<256> c;
+    MmlField<TofsProb> tab;
+    MmlField<float> tf, box;
+    MmlField<long long> woff;
+    MmlField<TofsBest> best;
+    MmlField<double> err;
+    size_t bytes;
+    TofsIo(size_t n, size_t n_win)
+        : tab(c.take<TofsProb>(n)), tf(c.take<float>(16 * n)), box(c.take<float>(6 * n)), woff(c.take<long long>(n + 1)), best(c.take<TofsBest>(n)),
+          err(c.take<double>(n_win)), bytes(c.bytes()) {}
 };
 // big block (device only): 100 bytes per Velodyne point (cells included), 16 per Livox point, the sort's scratch
-struct BigLayout {
-    size_t vxyz, v4, pts, keys, keys2, vals, vals2, lxyz, nn, cells, sort, bytes;
-    BigLayout(size_t nv, size_t nl, size_t n_cells, size_t sort_bytes) {
-        size_t o = 0;
-        const auto take = [&](size_t b) {
-            const size_t at = o;
-            o += align256(b);
-            return at;
-        };
-        vxyz = take(sizeof(float) * 3 * nv);
-        v4 = take(sizeof(float4) * nv);
-        pts = take(sizeof(float4) * nv);
-        keys = take(sizeof(unsigned long long) * nv);
-        keys2 = take(sizeof(unsigned long long) * nv);
-        vals = take(sizeof(unsigned) * nv);
-        vals2 = take(sizeof(unsigned) * nv);
-        lxyz = take(sizeof(float) * 3 * nl);
-        nn = take(sizeof(float) * nl);
-        cells = take(sizeof(int) * n_cells);
-        sort = take(sort_bytes);
-        bytes = o;
-    }
+struct TofsBig {
+    MmlCarve<256> c;
+    MmlField<float> vxyz;
+    MmlField<float4> v4, pts;
+    MmlField<unsigned long long> keys, keys2;
+    MmlField<unsigned> vals, vals2;
+    MmlField<float> lxyz, nn;
+    MmlField<int> cells;
+    MmlField<char> sort;
+    size_t bytes;
+    TofsBig(size_t nv, size_t nl, size_t n_cells, size_t sort_bytes)
+        : vxyz(c.take<float>(3 * nv)), v4(c.take<float4>(nv)), pts(c.take<float4>(nv)), keys(c.take<unsigned long long>(nv)),
+          keys2(c.take<unsigned long long>(nv)), vals(c.take<unsigned>(nv)), vals2(c.take<unsigned>(nv)), lxyz(c.take<float>(3 * nl)),
+          nn(c.take<float>(nl)), cells(c.take<int>(n_cells)), sort(c.take<char>(sort_bytes)), bytes(c.bytes()) {}
 };
 
 int bits_for(long long values) {  // bits that hold 0 .. values - 1
@@ -384,16 +368,11 @@ int bits_for(long long values) {  // bits that hold 0 .. values - 1
 struct MmlTofsDev {
     MmlStaging<char> io;
     MmlStaging<char, false> big;
+    ~MmlTofsDev() {
+        io.release();
+        big.release();
+    }
 };
-
-void mml_time_offset_release(mml_ctx* ctx) {
-    MmlTofsDev* d = ctx->tofs;
-    if (!d) return;
-    d->io.release();
-    d->big.release();
-    delete d;
-    ctx->tofs = nullptr;
-}
 
 namespace {
 
@@ -430,10 +409,8 @@ int tofs_run(mml_ctx* ctx, const char* who, int n, const float* velo_xyz, const 
 
     // Everything the context has in flight ends here -- every lane of a pipelined mml_step and the upload stream --, so a search that
     // follows a multi-lane step starts on an idle device; it reads no slot anyway: all it touches is the caller's arrays and its own block.
-    MML_HIP(hipSetDevice(ctx->device));
-    int rc = mml_sync_all(ctx);
+    int rc = mml_enter_idle(ctx);
     if (rc != MML_OK) return rc;
-    ctx->cur = 0;
 
     size_t n_win = 0, n_cells = 0;
     int max_v = 0, max_l = 0;
@@ -450,28 +427,25 @@ int tofs_run(mml_ctx* ctx, const char* who, int n, const float* velo_xyz, const 
         size_t sort_bytes = 0;
         MML_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (unsigned*)nullptr,
                                           (unsigned*)nullptr, nv, 0, 64, MML_STREAM(ctx)));
-        const IoLayout io((size_t)n, n_win);
-        const BigLayout big(nv, nl, n_cells, sort_bytes);
-        if (!ctx->tofs) ctx->tofs = new MmlTofsDev();
-        MmlTofsDev* d = ctx->tofs;
+        const TofsIo io((size_t)n, n_win);
+        const TofsBig big(nv, nl, n_cells, sort_bytes);
+        MmlTofsDev* d = mml_side<MmlTofsDev>(ctx, MML_SIDE_TIME_OFFSET);
         if (d->io.reserve(ctx, io.bytes) || d->big.reserve(ctx, big.bytes)) {
             ctx->err = std::string(who) + ": the scratch block could not be grown: " + ctx->err;
             return MML_ERR_HIP;
         }
         hipStream_t s = MML_STREAM(ctx);
         char *h = d->io.h, *g = d->io.d, *b = d->big.d;
-        TofsProb* h_tab = reinterpret_cast<TofsProb*>(h + io.tab);
-        float* h_box = reinterpret_cast<float*>(h + io.box);
-        long long* h_woff = reinterpret_cast<long long*>(h + io.woff);
-        const TofsProb* d_tab = reinterpret_cast<const TofsProb*>(g + io.tab);
-        const float* d_tf = tf ? reinterpret_cast<const float*>(g + io.tf) : nullptr;
-        float4* d_v4 = reinterpret_cast<float4*>(b + big.v4);
-        float4* d_pts = reinterpret_cast<float4*>(b + big.pts);
-        unsigned long long *d_keys = reinterpret_cast<unsigned long long*>(b + big.keys), *d_keys2 = reinterpret_cast<unsigned long long*>(b + big.keys2);
-        unsigned *d_vals = reinterpret_cast<unsigned*>(b + big.vals), *d_vals2 = reinterpret_cast<unsigned*>(b + big.vals2);
-        float* d_lxyz = reinterpret_cast<float*>(b + big.lxyz);
-        float* d_nn = reinterpret_cast<float*>(b + big.nn);
-        double* d_err = reinterpret_cast<double*>(g + io.err);
+        TofsProb* h_tab = io.tab.in(h);
+        float* h_box = io.box.in(h);
+        long long* h_woff = io.woff.in(h);
+        const TofsProb* d_tab = io.tab.in(g);
+        const float* d_tf = tf ? io.tf.in(g) : nullptr;
+        float4 *d_v4 = big.v4.in(b), *d_pts = big.pts.in(b);
+        unsigned long long *d_keys = big.keys.in(b), *d_keys2 = big.keys2.in(b);
+        unsigned *d_vals = big.vals.in(b), *d_vals2 = big.vals2.in(b);
+        float *d_lxyz = big.lxyz.in(b), *d_nn = big.nn.in(b);
+        double* d_err = io.err.in(g);
         h_woff[0] = 0;
         for (int i = 0; i < n; ++i) {
             TofsProb& P = h_tab[i];
@@ -491,17 +465,17 @@ int tofs_run(mml_ctx* ctx, const char* who, int n, const float* velo_xyz, const 
         const unsigned by = (unsigned)n, bx_v = (unsigned)((max_v + 255) / 256);
         {   // host synchronisation 1 of 2: the boxes of all problems in one copy
             MmlStageScope t(ctx, "tofs_box");
-            MML_HIP(hipMemcpyAsync(g + io.tab, h + io.tab, sizeof(TofsProb) * (size_t)n, hipMemcpyHostToDevice, s));
-            MML_HIP(hipMemcpyAsync(g + io.box, h + io.box, sizeof(float) * 6 * (size_t)n, hipMemcpyHostToDevice, s));
-            MML_HIP(hipMemcpyAsync(g + io.woff, h + io.woff, sizeof(long long) * ((size_t)n + 1), hipMemcpyHostToDevice, s));
-            if (tf) MML_HIP(hipMemcpyAsync(g + io.tf, tf, sizeof(float) * 16 * (size_t)n, hipMemcpyHostToDevice, s));
-            MML_HIP(hipMemcpyAsync(b + big.vxyz, velo_xyz + 3 * (size_t)vo[0], sizeof(float) * 3 * nv, hipMemcpyHostToDevice, s));
-            MML_HIP(hipMemcpyAsync(d_lxyz, livox_xyz + 3 * (size_t)lo[0], sizeof(float) * 3 * nl, hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(k_tofs_tf, dim3(bx_v, by), dim3(256), 0, s, d_tab, reinterpret_cast<const float*>(b + big.vxyz), d_tf, d_v4);
+            MML_HIP(hipMemcpyAsync(io.tab.in(g), h_tab, io.tab.bytes(), hipMemcpyHostToDevice, s));
+            MML_HIP(hipMemcpyAsync(io.box.in(g), h_box, io.box.bytes(), hipMemcpyHostToDevice, s));
+            MML_HIP(hipMemcpyAsync(io.woff.in(g), h_woff, io.woff.bytes(), hipMemcpyHostToDevice, s));
+            if (tf) MML_HIP(hipMemcpyAsync(io.tf.in(g), tf, io.tf.bytes(), hipMemcpyHostToDevice, s));
+            MML_HIP(hipMemcpyAsync(big.vxyz.in(b), velo_xyz + 3 * (size_t)vo[0], big.vxyz.bytes(), hipMemcpyHostToDevice, s));
+            MML_HIP(hipMemcpyAsync(d_lxyz, livox_xyz + 3 * (size_t)lo[0], big.lxyz.bytes(), hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(k_tofs_tf, dim3(bx_v, by), dim3(256), 0, s, d_tab, big.vxyz.in(b), d_tf, d_v4);
             hipLaunchKernelGGL(k_tofs_box, dim3(bx_v < (unsigned)TOFS_BOX_BLOCKS ? bx_v : (unsigned)TOFS_BOX_BLOCKS, by), dim3(256), 0, s, d_tab, d_v4,
-                               reinterpret_cast<float*>(g + io.box));
+                               io.box.in(g));
             MML_HIP(hipGetLastError());
-            MML_HIP(hipMemcpyAsync(h + io.box, g + io.box, sizeof(float) * 6 * (size_t)n, hipMemcpyDeviceToHost, s));
+            MML_HIP(hipMemcpyAsync(h_box, io.box.in(g), io.box.bytes(), hipMemcpyDeviceToHost, s));
             MML_HIP(hipStreamSynchronize(s));
         }
         // every problem's cell and dims in one pass; its cell_start array follows the previous problem's in the pool
@@ -513,37 +487,37 @@ int tofs_run(mml_ctx* ctx, const char* who, int n, const float* velo_xyz, const 
             tofs_choose_grid(h_box + 6 * i, P.n_velo, P.g);
             P.g.m = P.n_velo;
             P.g.pts = d_pts + P.v_base;
-            P.g.cell_start = reinterpret_cast<int*>(b + big.cells) + cell_at;
+            P.g.cell_start = big.cells.in(b) + cell_at;
             cell_at += (size_t)P.g.ncell + 1;
             max_cells = P.g.ncell > max_cells ? P.g.ncell : max_cells;
         }
         {   // host synchronisation 2 of 2: the results
             MmlStageScope t(ctx, "tofs_search");
-            MML_HIP(hipMemcpyAsync(g + io.tab, h + io.tab, sizeof(TofsProb) * (size_t)n, hipMemcpyHostToDevice, s));
+            MML_HIP(hipMemcpyAsync(io.tab.in(g), h_tab, io.tab.bytes(), hipMemcpyHostToDevice, s));
             hipLaunchKernelGGL(k_tofs_keys, dim3(bx_v, by), dim3(256), 0, s, d_tab, d_v4, d_keys, d_vals);
             // ONE stable sort over all Velodyne points; with one problem the high word is zero and the cell bits are enough
             const int end_bit = n == 1 ? bits_for(max_cells) : 32 + bits_for(n);
             size_t need = 0;
             MML_HIP(rocprim::radix_sort_pairs(nullptr, need, d_keys, d_keys2, d_vals, d_vals2, nv, 0, end_bit, s));
             if (need > sort_bytes) return mml_refuse(ctx, MML_ERR_HIP, "%s: the sort asks for %zu bytes of scratch, %zu were reserved", who, need, sort_bytes);
-            MML_HIP(rocprim::radix_sort_pairs(b + big.sort, need, d_keys, d_keys2, d_vals, d_vals2, nv, 0, end_bit, s));
+            MML_HIP(rocprim::radix_sort_pairs(big.sort.in(b), need, d_keys, d_keys2, d_vals, d_vals2, nv, 0, end_bit, s));
             hipLaunchKernelGGL(k_tofs_gather, dim3(bx_v, by), dim3(256), 0, s, d_tab, d_v4, d_vals2, d_pts);
             hipLaunchKernelGGL(k_tofs_cell_start, dim3((unsigned)((max_cells + 1 + 255) / 256), by), dim3(256), 0, s, d_tab, d_keys2);
             hipLaunchKernelGGL(k_tofs_nn1, dim3((unsigned)((max_l + 255) / 256), by), dim3(256), 0, s, d_tab, d_lxyz, d_nn);
             if (n_win > 0) {
                 hipLaunchKernelGGL(k_tofs_window_err, dim3((unsigned)((n_win + 63) / 64)), dim3(64), 0, s, d_tab, n,
-                                   reinterpret_cast<const long long*>(g + io.woff), d_lxyz, d_nn, res, sliced, d_err);
-                hipLaunchKernelGGL(k_tofs_best, dim3(by), dim3(256), 0, s, d_tab, d_err, reinterpret_cast<TofsBest*>(g + io.best));
-                MML_HIP(hipMemcpyAsync(h + io.best, g + io.best, sizeof(TofsBest) * (size_t)n, hipMemcpyDeviceToHost, s));
-                if (window_error) MML_HIP(hipMemcpyAsync(h + io.err, g + io.err, sizeof(double) * n_win, hipMemcpyDeviceToHost, s));
+                                   io.woff.in(g), d_lxyz, d_nn, res, sliced, d_err);
+                hipLaunchKernelGGL(k_tofs_best, dim3(by), dim3(256), 0, s, d_tab, d_err, io.best.in(g));
+                MML_HIP(hipMemcpyAsync(io.best.in(h), io.best.in(g), io.best.bytes(), hipMemcpyDeviceToHost, s));
+                if (window_error) MML_HIP(hipMemcpyAsync(io.err.in(h), d_err, io.err.bytes(), hipMemcpyDeviceToHost, s));
             }
             MML_HIP(hipGetLastError());
             if (nn_d2) MML_HIP(hipMemcpyAsync(nn_d2 + lo[0], d_nn, sizeof(float) * nl, hipMemcpyDeviceToHost, s));
             MML_HIP(hipStreamSynchronize(s));
         }
         if (n_win > 0) {
-            memcpy(best.data(), h + io.best, sizeof(TofsBest) * (size_t)n);
-            h_err = reinterpret_cast<const double*>(h + io.err);
+            memcpy(best.data(), io.best.in(h), io.best.bytes());
+            h_err = io.err.in(h);
         }
     }
     long long e_base = 0;

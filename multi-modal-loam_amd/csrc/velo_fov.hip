@@ -197,27 +197,20 @@ __global__ __launch_bounds__(256) void k_vfov_pack(const VfovFrame* __restrict__
     }
 }
 
-size_t vfov_align(size_t b) { return (b + 255) & ~size_t(255); }
-
 }  // namespace
 
 // Grow-only scratch of the selection, owned by the context.  The entry point drains the stream before it returns, so reserve()
 // never replaces a buffer in use.
 struct MmlVfovDev {
     MmlStaging<char> io;          // frame table | info rows
-    MmlStaging<char> in;          // the frames' records, each frame 16-byte aligned
+    MmlStaging<uint8_t> in;       // the frames' records, each frame 16-byte aligned
     MmlStaging<char, false> big;  // azimuths | rows in place | packed x,y,z,relTime | packed x,y,z
+    ~MmlVfovDev() {
+        io.release();
+        in.release();
+        big.release();
+    }
 };
-
-void mml_velo_fov_release(mml_ctx* ctx) {
-    MmlVfovDev* d = ctx->vfov;
-    if (!d) return;
-    d->io.release();
-    d->in.release();
-    d->big.release();
-    delete d;
-    ctx->vfov = nullptr;
-}
 
 namespace {
 
@@ -269,48 +262,46 @@ int vfov_run(mml_ctx* ctx, const char* who, int n, const uint8_t* data, const lo
 
     // ---- device ----
     MML_HIP(hipSetDevice(ctx->device));
-    const size_t tab_bytes = vfov_align(sizeof(VfovFrame) * (size_t)n), info_bytes = vfov_align(sizeof(mml_velo_fov_info) * (size_t)n);
-    size_t in_bytes = 0;
-    int max_n = 0;
-    for (int i = 0; i < n; ++i) {
-        in_bytes += ((size_t)n_points[i] * (size_t)step + 15) & ~size_t(15);
-        max_n = n_points[i] > max_n ? n_points[i] : max_n;
-    }
-    const size_t rows_in = (size_t)total_in;
-    const size_t o_azi = 0, o_rows = o_azi + vfov_align(sizeof(float) * rows_in), o_xyzt = o_rows + vfov_align(sizeof(float4) * rows_in),
-                 o_xyz = o_xyzt + vfov_align(sizeof(float4) * rows_in), big_bytes = o_xyz + vfov_align(sizeof(float) * 3 * rows_in);
-    if (!ctx->vfov) ctx->vfov = new MmlVfovDev();
-    MmlVfovDev* d = ctx->vfov;
-    if (d->io.reserve(ctx, tab_bytes + info_bytes) || d->in.reserve(ctx, in_bytes ? in_bytes : 16) || d->big.reserve(ctx, big_bytes ? big_bytes : 256)) {
+    MmlCarve<256> io;
+    const auto tab = io.take<VfovFrame>((size_t)n);
+    const auto inf = io.take<mml_velo_fov_info>((size_t)n);
+    MmlCarve<16> in;  // the frames' records, one field per frame: here for the block's size, below again for the offsets
+    for (int i = 0; i < n; ++i) in.take<uint8_t>((size_t)n_points[i] * (size_t)step);
+    const size_t in_bytes = in.bytes(), rows_in = (size_t)total_in;
+    MmlCarve<256> big;
+    const auto azi = big.take<float>(rows_in);
+    const auto rows = big.take<float4>(rows_in), packed4 = big.take<float4>(rows_in);
+    const auto packed3 = big.take<float>(3 * rows_in);
+    MmlVfovDev* d = mml_side<MmlVfovDev>(ctx, MML_SIDE_VELO_FOV);
+    if (d->io.reserve(ctx, io.bytes()) || d->in.reserve(ctx, in_bytes ? in_bytes : 16) || d->big.reserve(ctx, big.bytes() ? big.bytes() : 256)) {
         ctx->err = std::string(who) + ": the scratch block could not be grown: " + ctx->err;
         return MML_ERR_HIP;
     }
-    VfovFrame* h_tab = reinterpret_cast<VfovFrame*>(d->io.h);
-    const mml_velo_fov_info* h_info = reinterpret_cast<const mml_velo_fov_info*>(d->io.h + tab_bytes);
-    const VfovFrame* d_tab = reinterpret_cast<const VfovFrame*>(d->io.d);
-    mml_velo_fov_info* d_info = reinterpret_cast<mml_velo_fov_info*>(d->io.d + tab_bytes);
+    VfovFrame* h_tab = tab.in(d->io.h);
+    const mml_velo_fov_info* h_info = inf.in(d->io.h);
+    const VfovFrame* d_tab = tab.in(d->io.d);
+    mml_velo_fov_info* d_info = inf.in(d->io.d);
     {
-        size_t at = 0;
+        MmlCarve<16> at;
         long long row = 0;
         for (int i = 0; i < n; ++i) {
-            const size_t b = (size_t)n_points[i] * (size_t)step;
-            if (b) memcpy(d->in.h + at, data + byte_offsets[i], b);
-            h_tab[i] = VfovFrame{(long long)at, row, 0, n_points[i], 0};
-            at += (b + 15) & ~size_t(15);
+            const auto rec = at.take<uint8_t>((size_t)n_points[i] * (size_t)step);
+            if (rec.n) memcpy(rec.in(d->in.h), data + byte_offsets[i], rec.bytes());
+            h_tab[i] = VfovFrame{(long long)rec.off, row, 0, n_points[i], 0};
             row += n_points[i];
         }
     }
     const VfovLayout L{step, ox, oy, oz, (step & 3) == 0 ? 1 : 0};
     hipStream_t s = MML_STREAM(ctx);
-    float4* d_rows = reinterpret_cast<float4*>(d->big.d + o_rows);
+    float4* d_rows = rows.in(d->big.d);
     {   // host synchronisation 1 of 2: counts and info
         MmlStageScope t(ctx, "velo_fov");
-        MML_HIP(hipMemcpyAsync(d->io.d, d->io.h, sizeof(VfovFrame) * (size_t)n, hipMemcpyHostToDevice, s));
+        MML_HIP(hipMemcpyAsync(tab.in(d->io.d), h_tab, tab.bytes(), hipMemcpyHostToDevice, s));
         if (in_bytes) MML_HIP(hipMemcpyAsync(d->in.d, d->in.h, in_bytes, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_vfov_select, dim3(1, (unsigned)n), dim3(VFOV_BLOCK), 0, s, d_tab, reinterpret_cast<const uint8_t*>(d->in.d), L,
-                           reinterpret_cast<float*>(d->big.d + o_azi), d_rows, d_info);
+        hipLaunchKernelGGL(k_vfov_select, dim3(1, (unsigned)n), dim3(VFOV_BLOCK), 0, s, d_tab, d->in.d, L, azi.in(d->big.d), d_rows,
+                           d_info);
         MML_HIP(hipGetLastError());
-        MML_HIP(hipMemcpyAsync(d->io.h + tab_bytes, d_info, sizeof(mml_velo_fov_info) * (size_t)n, hipMemcpyDeviceToHost, s));
+        MML_HIP(hipMemcpyAsync(inf.in(d->io.h), d_info, inf.bytes(), hipMemcpyDeviceToHost, s));
         MML_HIP(hipStreamSynchronize(s));
     }
     long long total = 0;
@@ -324,10 +315,10 @@ int vfov_run(mml_ctx* ctx, const char* who, int n, const uint8_t* data, const lo
         return mml_refuse(ctx, MML_ERR_CAPACITY, "%s: %lld rows are kept, capacity_rows is %ld", who, total, capacity_rows);
     if (want_rows && total > 0) {  // host synchronisation 2 of 2: the rows
         MmlStageScope t(ctx, "velo_fov");
-        float4* d_xyzt = xyzt ? reinterpret_cast<float4*>(d->big.d + o_xyzt) : nullptr;
-        float* d_xyz = xyz ? reinterpret_cast<float*>(d->big.d + o_xyz) : nullptr;
+        float4* d_xyzt = xyzt ? packed4.in(d->big.d) : nullptr;
+        float* d_xyz = xyz ? packed3.in(d->big.d) : nullptr;
         const unsigned bx = (unsigned)((max_kept + 255) / 256);
-        MML_HIP(hipMemcpyAsync(d->io.d, d->io.h, sizeof(VfovFrame) * (size_t)n, hipMemcpyHostToDevice, s));
+        MML_HIP(hipMemcpyAsync(tab.in(d->io.d), h_tab, tab.bytes(), hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(k_vfov_pack, dim3(bx < (unsigned)VFOV_PACK_BLOCKS ? bx : (unsigned)VFOV_PACK_BLOCKS, (unsigned)n), dim3(256), 0, s, d_tab,
                            d_info, d_rows, d_xyzt, d_xyz);
         MML_HIP(hipGetLastError());

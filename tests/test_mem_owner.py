@@ -1,7 +1,8 @@
 """csrc/mml_mem.h, the owner of the library's device and pinned memory, on its failure paths: a stand-alone host program
 (tests/cpp/mem_owner_replay.cpp) built with AddressSanitizer and UndefinedBehaviorSanitizer.  Without a device every allocation
 fails and leaves its pointer null, which is what the program needs; where a device is visible the test skips, so that no device is
-ever opened under a sanitizer."""
+ever opened under a sanitizer.  The same program checks the header's two device-free helpers: the block layouts of MmlCarve and
+the side calls' registry MmlSides (created once, empty after a failed reserve, released any number of times, nothing leaked)."""
 import os
 import shutil
 import subprocess
