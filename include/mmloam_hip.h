@@ -665,7 +665,7 @@ typedef struct {
 } mml_imu_preint;
 /* IMUIntegrator::PreIntegration (IMUIntegrator.cpp:108-166).  samples: n x 7 doubles = angular_velocity xyz,
  * linear_acceleration xyz as in the message (multiplied by gnorm = 9.805 inside, :119-121), dt to the previous
- * sample (:122). */
+ * sample (:122).  Sample values are not checked; with a non-finite sample the output is unspecified. */
 int mml_imu_preintegrate(const double* samples, int n, const double* bg, const double* ba, mml_imu_preint* out);
 /* Cost_NavState_PRV_Bias (ceresfunc.h:321-393) with sqrt_information = LLT(covariance^-1).matrixL()^T
  * (Estimator.cpp:1240-1242).  pr*: [P(3), rotation vector(3)], vb*: [V(3), bg(3), ba(3)].  residual: 15;

@@ -1,6 +1,6 @@
 // fullwindow_internal.h -- the full-window solver handle shared by window_imu.hip (host trust-region loop, IMU factor,
 // marginalization) and fullwindow_dev.hip (the same loop resident on the device); its prior is the ABI's mml_prior plus
-// a flag.  The dense helpers of window_imu.hip that lio_init.hip (the LIO initialisation) reuses.
+// a flag.  It declares no functions: the dense helpers the host files share (Cholesky, sqrt information) are imu_math.h's.
 #pragma once
 #include <vector>
 
@@ -32,13 +32,3 @@ struct mml_fullwindow {
     int reuse = 0, num_invalid = 0, iter = 0, successful = 0, termination = 0, started = 0, done = 0;
     double initial_cost = 0;
 };
-
-// sqrt information of one pre-integration (15 x 15 upper, row-major): LLT(covariance^-1).matrixL().transpose()
-// (Estimator.cpp:1240-1242); false when the covariance is not positive definite.  window_imu.hip.
-bool mml_imu_sqrt_info(const mml_imu_preint* pre, double* U);
-// The same for the leading n x n block (1 <= n <= 15) of a covariance with row stride ld (U: n x n upper, row-major):
-// the 9 x 9 LLT(cov.block<9,9>(0,0).inverse()).matrixL().transpose() of the initialisation (unionPoseEstimation.cpp:558-561).
-bool mml_sqrt_info_block(const double* cov, int ld, int n, double* U);
-// window_imu.hip's in-place Cholesky A = L L^T (lower, row-major n x n; false when not positive definite) and its solve.
-bool mml_cholesky(double* A, int n);
-void mml_chol_solve(const double* L, int n, double* b);

@@ -4,6 +4,10 @@
 //   * Cost_NavState_PRV_Bias residual and analytic Jacobian before the sqrt information (ceresfunc.h:321-393)
 //   * the sqrt-information products of that factor, element by element (imu_whiten)
 //   * MarginalizationFactor::Evaluate residual (ceresfunc.h:262-301)
+// and for the IMU / LIO-initialisation family around them (imu_preint.h, lio_init_core.h, lio_init.hip):
+//   * mml_sin / mml_cos / mml_atan, and trig_sin / trig_cos: the compile-time choice between them and libm
+//   * the sequential dense Cholesky, its solve and the sqrt information of a covariance block -- the ONE definition behind
+//     every host caller and the device's one-thread use
 #pragma once
 #include <math.h>
 
@@ -93,6 +97,23 @@ MML_HD double mml_cos(double x) {
         case 2: return -mml_kcos(y);
         default: return mml_ksin(y);
     }
+}
+// The compile-time choice between the two: kLibm = true is libm's sin / cos, which only the single host calls take
+// (mml_imu_preintegrate's right Jacobian, the quaternion step of mml_lio_initialize's gravity solve -- their results were
+// pinned with libm); false is the pair above, which everything that also runs on the device takes.
+template <bool kLibm>
+MML_HD double trig_sin(double x) {
+    if constexpr (kLibm)
+        return sin(x);
+    else
+        return mml_sin(x);
+}
+template <bool kLibm>
+MML_HD double trig_cos(double x) {
+    if constexpr (kLibm)
+        return cos(x);
+    else
+        return mml_cos(x);
 }
 MML_HD double mml_atan(double xin) {
     const double aT0 = 3.33333333333329318027e-01, aT1 = -1.99999999998764832476e-01, aT2 = 1.42857142725034663711e-01,
@@ -261,6 +282,58 @@ MML_HD M3 get_block(const double* M, int ld, int r0, int c0) {
     for (int r = 0; r < 3; ++r)
         for (int c = 0; c < 3; ++c) B.a[3 * r + c] = M[(r0 + r) * ld + c0 + c];
     return B;
+}
+
+// ---- the sequential dense Cholesky ---------------------------------------------------------------------------------
+// in-place Cholesky A = L L^T (lower, row-major n x n); false when not positive definite
+MML_HD bool cholesky(double* A, int n) {
+    for (int j = 0; j < n; ++j) {
+        double d = A[j * n + j];
+        for (int k = 0; k < j; ++k) d -= A[j * n + k] * A[j * n + k];
+        if (!(d > 0.0) || !isfinite(d)) return false;
+        d = sqrt(d);
+        A[j * n + j] = d;
+        for (int i = j + 1; i < n; ++i) {
+            double s = A[i * n + j];
+            for (int k = 0; k < j; ++k) s -= A[i * n + k] * A[j * n + k];
+            A[i * n + j] = s / d;
+        }
+    }
+    return true;
+}
+MML_HD void chol_solve(const double* L, int n, double* b) {
+    for (int i = 0; i < n; ++i) {
+        double s = b[i];
+        for (int k = 0; k < i; ++k) s -= L[i * n + k] * b[k];
+        b[i] = s / L[i * n + i];
+    }
+    for (int i = n - 1; i >= 0; --i) {
+        double s = b[i];
+        for (int k = i + 1; k < n; ++k) s -= L[k * n + i] * b[k];
+        b[i] = s / L[i * n + i];
+    }
+}
+// sqrt information of the leading n x n block of a covariance stored with row stride ld:
+// LLT(block^-1).matrixL().transpose(), n x n upper, row-major; false when the block is not positive definite.
+// ws: sqrt_info_ws(n) doubles of work space (L | inverse | a unit vector)
+constexpr int sqrt_info_ws(int n) { return 2 * n * n + n; }
+MML_HD bool sqrt_info_block(const double* cov, int ld, int n, double* U, double* ws) {
+    double *L = ws, *inv = ws + n * n, *e = ws + 2 * n * n;
+    for (int r = 0; r < n; ++r)
+        for (int c = 0; c < n; ++c) L[r * n + c] = cov[r * ld + c];
+    if (!cholesky(L, n)) return false;
+    for (int c = 0; c < n; ++c) {
+        for (int r = 0; r < n; ++r) e[r] = 0.0;
+        e[c] = 1.0;
+        chol_solve(L, n, e);
+        for (int r = 0; r < n; ++r) inv[r * n + c] = e[r];
+    }
+    for (int r = 0; r < n; ++r)
+        for (int c = r + 1; c < n; ++c) inv[r * n + c] = inv[c * n + r] = 0.5 * (inv[r * n + c] + inv[c * n + r]);
+    if (!cholesky(inv, n)) return false;
+    for (int r = 0; r < n; ++r)
+        for (int c = 0; c < n; ++c) U[r * n + c] = (c >= r) ? inv[c * n + r] : 0.0;  // U = L^T
+    return true;
 }
 
 // residual (15) and Jacobian (15 x 30, columns [PR_i 6 | VBias_i 9 | PR_j 6 | VBias_j 9]) BEFORE the sqrt information

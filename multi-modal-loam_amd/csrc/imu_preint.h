@@ -1,12 +1,17 @@
-// imu_preint.h -- the pre-integration of one IMU interval (IMUIntegrator::PreIntegration, IMUIntegrator.cpp:108-166), written
-// once for the host loop of mml_imu_preintegrate_batch and for the device (k_imu_preintegrate, imu_preint.hip): n samples and
-// the linearisation biases in, one mml_imu_preint out.  It is the arithmetic of mml_imu_preintegrate (window_imu.hip) with
-//   * mml_cos / mml_sin (imu_math.h) in the right Jacobian, where that function calls libm -- the one place where a host build
-//     and a device build could part;
-//   * the block structure of A and B used: A is the identity plus seven 3 x 3 blocks, B five blocks, and a dot product adds the
-//     terms of the entries that are not structurally zero, ascending k, to an accumulator that starts at +0.0.  The dense loop
-//     adds +-0.0 for every other k, which never changes such an accumulator (it cannot hold -0.0), so wherever no sin / cos of
-//     the step angle is taken the result has the bytes of mml_imu_preintegrate's (finite samples; 0 * inf is the exception).
+// imu_preint.h -- the pre-integration of one IMU interval (IMUIntegrator::PreIntegration, IMUIntegrator.cpp:108-166): n samples
+// and the linearisation biases in, one mml_imu_preint out.  The ONE text of it: mml_imu_preintegrate (window_imu.hip), the host
+// loops of mml_imu_preintegrate_batch and mml_lio_initialize_batch, and the device (k_imu_preintegrate, imu_preint.hip;
+// k_lio_preint, lio_init_batch.hip) all run imu_preint_interval.  Its template argument chooses the right Jacobian's sin / cos
+// (trig_sin / trig_cos, imu_math.h) -- the one place where a host build and a device build could part:
+//   * kLibm = true, libm: mml_imu_preintegrate alone, whose results were pinned with it;
+//   * kLibm = false, mml_sin / mml_cos: every batch caller, host and device.
+// The right Jacobian feeds only the Jacobian and covariance chains, so the two forms give the same dp, dv, dq, dtime, bg, ba
+// always, and the same bytes throughout wherever no step rotates by more than 1e-5 rad.
+// A and B are used by their block structure: A is the identity plus seven 3 x 3 blocks, B five blocks, and a dot product adds
+// the terms of the entries that are not structurally zero, ascending k, to an accumulator that starts at +0.0.  A dense
+// 15 x 15 loop would add +-0.0 for every other k, which never changes such an accumulator (it cannot hold -0.0), so for finite
+// samples the result has the bytes of the dense products (0 * inf is the exception: with a non-finite sample the output is
+// unspecified).
 // The host build runs every loop from 0 to its end on one thread.  The device build is called by ONE wavefront with the work
 // space in LDS, the way marg_dense.h is (its macros): what depends on one sample only -- exp(gyr dt), the right Jacobian, the
 // bias-corrected acceleration -- is computed for a chunk of samples at a time, a sample per lane (MARG_FOR); the chain over the
@@ -38,6 +43,7 @@ struct PreintWork {
 static_assert(PREINT_CHUNK * 7 <= 225, "a chunk of raw samples is staged in PreintWork::T");
 
 // what one sample contributes on its own (:119-135): m = gyro xyz, accel xyz (message units), dt
+template <bool kLibm>
 MARG_HD void preint_sample_terms(const double* m, const double* bg, const double* ba, double* rec) {
     const double gyr[3] = {m[0] - bg[0], m[1] - bg[1], m[2] - bg[2]};
     const double dt = m[6];
@@ -48,7 +54,7 @@ MARG_HD void preint_sample_terms(const double* m, const double* bg, const double
     if (nrm > 0.00001) {  // :129-135
         const double k[3] = {gdt[0] / nrm, gdt[1] / nrm, gdt[2] / nrm};
         const M3 K = hat(k);
-        Jr = m3_add(m3_add(m3_identity(), m3_scale(K, -(1 - mml_cos(nrm)) / nrm)), m3_scale(m3_mul(K, K), 1 - mml_sin(nrm) / nrm));
+        Jr = m3_add(m3_add(m3_identity(), m3_scale(K, -(1 - trig_cos<kLibm>(nrm)) / nrm)), m3_scale(m3_mul(K, K), 1 - trig_sin<kLibm>(nrm) / nrm));
     }
     for (int i = 0; i < 9; ++i) {
         rec[i] = dRt.a[i];
@@ -111,6 +117,7 @@ MARG_HD double preint_BnB(const PreintWork& w, const double* rec, double dt, dou
 }
 
 // samples: n x 7 (n >= 0); bg, ba: 3 each.  n = 0 gives Reset() (:49-58).
+template <bool kLibm>
 MARG_HD void imu_preint_interval(const double* samples, int n, const double* bg_, const double* ba_, mml_imu_preint* out, PreintWork& w) {
     const double bg[3] = {bg_[0], bg_[1], bg_[2]}, ba[3] = {ba_[0], ba_[1], ba_[2]};
     double dq[4] = {0.0, 0.0, 0.0, 1.0}, dp[3] = {0.0, 0.0, 0.0}, dv[3] = {0.0, 0.0, 0.0}, dtime = 0.0;
@@ -124,7 +131,7 @@ MARG_HD void imu_preint_interval(const double* samples, int n, const double* bg_
         const int cnt = n - s0 < PREINT_CHUNK ? n - s0 : PREINT_CHUNK;
         MARG_FOR(e, 7 * cnt) w.T[e] = samples[7 * (size_t)s0 + e];
         MARG_SYNC();
-        MARG_FOR(i, cnt) preint_sample_terms(w.T + 7 * i, bg, ba, w.rec[i]);
+        MARG_FOR(i, cnt) preint_sample_terms<kLibm>(w.T + 7 * i, bg, ba, w.rec[i]);
         MARG_SYNC();
         for (int i = 0; i < cnt; ++i) {
             const double* rec = w.rec[i];

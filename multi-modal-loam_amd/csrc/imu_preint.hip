@@ -19,7 +19,7 @@ __global__ __launch_bounds__(64) void k_imu_preintegrate(const double* samples, 
     __shared__ PreintWork s_work;
     const size_t i = blockIdx.x;
     const int s0 = offsets[i], cnt = offsets[i + 1] - s0;
-    imu_preint_interval(samples + 7 * (size_t)s0, cnt, bias + 6 * i, bias + 6 * i + 3, out + i, s_work);
+    imu_preint_interval<false>(samples + 7 * (size_t)s0, cnt, bias + 6 * i, bias + 6 * i + 3, out + i, s_work);
 }
 
 }  // namespace
@@ -45,7 +45,7 @@ extern "C" int mml_imu_preintegrate_batch(mml_ctx* ctx, int n, const double* sam
     if (!ctx) {  // the host build of the routine
         PreintWork work;
         for (int i = 0; i < n; ++i)
-            imu_preint_interval(samples + 7 * (size_t)offsets[i], offsets[i + 1] - offsets[i], bg + 3 * (size_t)i, ba + 3 * (size_t)i, out + i, work);
+            imu_preint_interval<false>(samples + 7 * (size_t)offsets[i], offsets[i + 1] - offsets[i], bg + 3 * (size_t)i, ba + 3 * (size_t)i, out + i, work);
         return MML_OK;
     }
     MML_HIP(hipSetDevice(ctx->device));

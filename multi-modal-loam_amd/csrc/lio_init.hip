@@ -2,8 +2,16 @@
 // 4 and 9 + 3 n unknowns, solved once per session (retried every third scan until they succeed); the 15 W dogleg of
 // window_imu.hip already showed that ONE serial dense solve of this size gains nothing on one wavefront.  Many of them at
 // once are another matter: mml_lio_initialize_batch (lio_init_batch.hip, the routine in lio_init_core.h) runs a segment per
-// wavefront for a replay of many segments; this file stays the single call.  Compiled into
-// the same library so that it sits behind the same C-ABI and shares imu_math.h / window_imu.hip's dense helpers.
+// wavefront for a replay of many segments; this file stays the single call.  Compiled into the same library so that it sits
+// behind the same C-ABI.  What it owns is lm_solve and steps 1-7 of mml_lio_initialize; the cost functions (Cost_Initial_G,
+// Cost_Initialization_IMU, the quaternion Plus and its Jacobian), the Ceres constants and kLioGnorm are lio_init_core.h's, the
+// Cholesky and the sqrt information imu_math.h's, the pre-integration imu_preint.h's (through mml_imu_preintegrate) -- one text
+// each for this call and the batch.  The only difference left in that shared text is libm's sin / cos here (lio_quat_plus<true>,
+// imu_preint_interval<true>) against mml_sin / mml_cos there.
+// lm_solve and lio_lm_solve (and the two texts of steps 1-7 around them) stay two routines ON PURPOSE: this call takes any
+// n >= 2 and sizes its vectors by n (the reference's WINDOWSIZE is a run-time value, above 8 before the list is trimmed), the
+// core keeps its whole state in a fixed LDS struct for at most MML_LIO_BATCH_MAX_FRAMES frames.  One routine for both would need
+// pointer views, which cost the device its LDS addressing, or a bound on n here, which changes behaviour.
 //   * IMUIntegrator::GyroIntegration        mm-loam/src/lio/IMUIntegrator.cpp:90-106      -> mml_imu_gyro_integrate
 //   * IMUIntegrator::GetAverageAcc          IMUIntegrator.cpp:168-181                     -> (inside mml_lio_initialize)
 //   * Cost_Initialization_IMU               mm-loam/include/utils/ceresfunc.h:654-741     -> mml_imu_init_factor
@@ -20,40 +28,10 @@
 
 #include <vector>
 
-#include "fullwindow_internal.h"
 #include "imu_math.h"
+#include "lio_init_core.h"
 
 namespace {
-
-constexpr double kGnorm = 9.805;  // IMUIntegrator.h:84, Cost_Initial_G / Cost_Initialization_IMU's G_I (0, 0, -9.805)
-
-// Ceres 2.1.0 defaults (solver.h): max_num_iterations 50, function / gradient / parameter tolerance 1e-6 / 1e-10 / 1e-8,
-// min_relative_decrease 1e-3, initial / max trust region radius 1e4 / 1e16, min radius 1e-32, LM diagonal clamp
-// [1e-6, 1e32], 5 consecutive invalid steps end the solve (trust_region_minimizer.cc HandleInvalidStep).
-constexpr int kMaxIter = 50;
-constexpr double kFuncTol = 1e-6, kGradTol = 1e-10, kParamTol = 1e-8, kMinRelDecrease = 1e-3;
-constexpr double kRadius0 = 1e4, kMaxRadius = 1e16, kMinRadius = 1e-32, kMinDiag = 1e-6, kMaxDiag = 1e32;
-
-// QuaternionParameterization (local_parameterization.cc), x = (w, x, y, z):
-// Plus: [cos|d|, sin|d| / |d| d] (x) x (QuaternionProduct, rotation.h); |d| = 0 leaves x as it is
-void quat_plus(const double* x, const double* d, double* o) {
-    const double nd = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-    if (!(nd > 0.0)) {
-        for (int i = 0; i < 4; ++i) o[i] = x[i];
-        return;
-    }
-    const double s = sin(nd) / nd;
-    const double z[4] = {cos(nd), s * d[0], s * d[1], s * d[2]};
-    o[0] = z[0] * x[0] - z[1] * x[1] - z[2] * x[2] - z[3] * x[3];
-    o[1] = z[0] * x[1] + z[1] * x[0] + z[2] * x[3] - z[3] * x[2];
-    o[2] = z[0] * x[2] - z[1] * x[3] + z[2] * x[0] + z[3] * x[1];
-    o[3] = z[0] * x[3] + z[1] * x[2] - z[2] * x[1] + z[3] * x[0];
-}
-// ComputeJacobian: d Plus(x, d) / d d at d = 0 (4 x 3, row-major)
-void quat_plus_jacobian(const double* x, double* P) {
-    const double J[12] = {-x[1], -x[2], -x[3], x[0], x[3], -x[2], -x[3], x[0], x[1], x[2], -x[1], x[0]};
-    memcpy(P, J, sizeof(J));
-}
 
 // Ceres 2.1.0 TrustRegionMinimizer with the LevenbergMarquardtStrategy on a dense problem of m residuals over one
 // parameter vector of na ambient / nl tangent coordinates (quat: the QuaternionParameterization, else Euclidean).
@@ -66,7 +44,7 @@ mml_solve_summary lm_solve(Eval eval, bool quat, int na, int nl, int m, double* 
         A((size_t)nl * nl), step(nl), delta(nl), mr(m);
     auto plus = [&](const double* xa, const double* d, double* o) {
         if (quat)
-            quat_plus(xa, d, o);
+            lio_quat_plus<true>(xa, d, o);  // libm: this call's results were pinned with it
         else
             for (int i = 0; i < na; ++i) o[i] = xa[i] + d[i];
     };
@@ -82,7 +60,7 @@ mml_solve_summary lm_solve(Eval eval, bool quat, int na, int nl, int m, double* 
         eval(x, r.data(), Ja.data());
         if (quat) {
             double Pj[12];
-            quat_plus_jacobian(x, Pj);
+            lio_quat_plus_jacobian(x, Pj);
             for (int i = 0; i < m; ++i)
                 for (int c = 0; c < nl; ++c) {
                     double a = 0;
@@ -112,17 +90,17 @@ mml_solve_summary lm_solve(Eval eval, bool quat, int na, int nl, int m, double* 
         for (int i = 0; i < m; ++i) a += J[(size_t)i * nl + c] * J[(size_t)i * nl + c];
         scale[c] = 1.0 / (1.0 + sqrt(a));
     }
-    double radius = kRadius0, decrease = 2.0;
+    double radius = kLioRadius0, decrease = 2.0;
     bool reuse = false;
     int invalid = 0;
     for (;;) {
         // FinalizeIterationAndCheckIfMinimizerCanContinue: iterations, gradient, minimum radius, in this order
-        if (s.iterations >= kMaxIter) break;
-        if (gmax <= kGradTol) {
+        if (s.iterations >= kLioMaxIter) break;
+        if (gmax <= kLioGradTol) {
             s.termination = 1;
             break;
         }
-        if (radius < kMinRadius) break;
+        if (radius < kLioMinRadius) break;
         s.iterations++;
         // LevenbergMarquardtStrategy::ComputeStep on the scaled Jacobian Js = J diag(scale):
         // (Js^T Js + diag / radius) y = Js^T r, step = -y; the diagonal (clamped squared column norms) is kept while
@@ -134,7 +112,7 @@ mml_solve_summary lm_solve(Eval eval, bool quat, int na, int nl, int m, double* 
                     const double v = J[(size_t)i * nl + c] * scale[c];
                     a += v * v;
                 }
-                diag[c] = fmin(fmax(a, kMinDiag), kMaxDiag);
+                diag[c] = fmin(fmax(a, kLioMinDiag), kLioMaxDiag);
             }
         for (int a = 0; a < nl; ++a) {
             for (int b = 0; b < nl; ++b) {
@@ -146,9 +124,9 @@ mml_solve_summary lm_solve(Eval eval, bool quat, int na, int nl, int m, double* 
             step[a] = g[a] * scale[a];
         }
         reuse = true;
-        bool valid = mml_cholesky(A.data(), nl);
+        bool valid = cholesky(A.data(), nl);
         if (valid) {
-            mml_chol_solve(A.data(), nl, step.data());
+            chol_solve(A.data(), nl, step.data());
             for (int c = 0; c < nl; ++c) {
                 step[c] = -step[c];
                 if (!isfinite(step[c])) valid = false;
@@ -186,21 +164,21 @@ mml_solve_summary lm_solve(Eval eval, bool quat, int na, int nl, int m, double* 
             xn += x[i] * x[i];
             sn += (x[i] - xc[i]) * (x[i] - xc[i]);
         }
-        if (sqrt(sn) <= kParamTol * (sqrt(xn) + kParamTol)) {
+        if (sqrt(sn) <= kLioParamTol * (sqrt(xn) + kLioParamTol)) {
             s.termination = 2;
             break;
         }
-        if (fabs(cost - cand) <= kFuncTol * cost) {  // FunctionToleranceReached
+        if (fabs(cost - cand) <= kLioFuncTol * cost) {  // FunctionToleranceReached
             s.termination = 3;
             break;
         }
         const double rho = (cost - cand) / model_change;
-        if (rho > kMinRelDecrease) {  // HandleSuccessfulStep + LevenbergMarquardtStrategy::StepAccepted
+        if (rho > kLioMinRelDecrease) {  // HandleSuccessfulStep + LevenbergMarquardtStrategy::StepAccepted
             for (int i = 0; i < na; ++i) x[i] = xc[i];
             cost = evaluate();
             s.successful++;
             const double t = 2.0 * rho - 1.0;
-            radius = fmin(kMaxRadius, radius / fmax(1.0 / 3.0, 1.0 - t * t * t));
+            radius = fmin(kLioMaxRadius, radius / fmax(1.0 / 3.0, 1.0 - t * t * t));
             decrease = 2.0;
             reuse = false;
         } else {  // StepRejected
@@ -210,80 +188,6 @@ mml_solve_summary lm_solve(Eval eval, bool quat, int na, int nl, int m, double* 
     }
     s.final_cost = cost;
     return s;
-}
-
-// Eigen's q * v (_transformVector) for q = (w, x, y, z), not normalised: v + w uv + u x uv with uv = 2 u x v
-void quat_rotate_wxyz(const double* q, const double* v, double* o) {
-    const double u[3] = {q[1], q[2], q[3]};
-    double uv[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
-    for (int k = 0; k < 3; ++k) uv[k] += uv[k];
-    const double c[3] = {u[1] * uv[2] - u[2] * uv[1], u[2] * uv[0] - u[0] * uv[2], u[0] * uv[1] - u[1] * uv[0]};
-    for (int k = 0; k < 3; ++k) o[k] = v[k] + q[0] * uv[k] + c[k];
-}
-
-// Cost_Initial_G (ceresfunc.h:626-652): q_wg * (0, 0, -9.805) - acc, and its ambient Jacobian (3 x 4, columns w x y z):
-// d/dw = uv, d/du = -w [v]x 2 - [uv]x - [u]x [v]x 2 for the formula above
-void cost_initial_g(const double* q, const double* acc, double* r, double* J) {
-    const double v[3] = {0.0, 0.0, -kGnorm};
-    quat_rotate_wxyz(q, v, r);
-    for (int k = 0; k < 3; ++k) r[k] -= acc[k];
-    if (!J) return;
-    const double u[3] = {q[1], q[2], q[3]};
-    double uv[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
-    for (int k = 0; k < 3; ++k) uv[k] += uv[k];
-    const M3 Vx = hat(v), UVx = hat(uv), Ux = hat(u);
-    const M3 D = m3_add(m3_add(m3_scale(Vx, -2.0 * q[0]), m3_scale(UVx, -1.0)), m3_scale(m3_mul(Ux, Vx), -2.0));
-    for (int i = 0; i < 3; ++i) {
-        J[i * 4] = uv[i];
-        for (int c = 0; c < 3; ++c) J[i * 4 + 1 + c] = D.a[3 * i + c];
-    }
-}
-
-// Cost_Initialization_IMU (ceresfunc.h:654-741) before the sqrt information: residual (9) and, when J != NULL, the
-// Jacobian (9 x 15, columns [rwg | vi | vj | ba | bg])
-void init_imu_raw(const mml_imu_preint* pre, const double* ri, const double* rj, const double* dp, const double* rwg,
-                  const double* vi, const double* vj, const double* ba, const double* bg, double* r, double* J) {
-    const double G_I[3] = {0.0, 0.0, -kGnorm};
-    const double dt = pre->dtime, dt2 = dt * dt;
-    const double dbg[3] = {bg[0] - pre->bg[0], bg[1] - pre->bg[1], bg[2] - pre->bg[2]};
-    const double dba[3] = {ba[0] - pre->ba[0], ba[1] - pre->ba[1], ba[2] - pre->ba[2]};
-    const M3 Ri = so3_exp(ri), Rj = so3_exp(rj), Rwg = so3_exp(rwg), RiT = m3_t(Ri);
-    const double* PJ = pre->jacobian;
-    const M3 Jpbg = get_block(PJ, 15, 0, 9), Jpba = get_block(PJ, 15, 0, 12), Jrbg = get_block(PJ, 15, 3, 9),
-             Jvbg = get_block(PJ, 15, 6, 9), Jvba = get_block(PJ, 15, 6, 12);
-    double gw[3], a[3], b[3], Ra[3], Rb[3], t1[3], t2[3];
-    m3_vec(Rwg, G_I, gw);
-    for (int k = 0; k < 3; ++k) {
-        a[k] = dp[k] - vi[k] * dt - gw[k] * dt2 * 0.5;
-        b[k] = vj[k] - vi[k] - gw[k] * dt;
-    }
-    m3_vec(RiT, a, Ra);
-    m3_vec(RiT, b, Rb);
-    m3_vec(Jpbg, dbg, t1);
-    m3_vec(Jpba, dba, t2);
-    for (int k = 0; k < 3; ++k) r[k] = Ra[k] - (pre->dp[k] + t1[k] + t2[k]);
-    double jd[3];
-    m3_vec(Jrbg, dbg, jd);
-    const M3 C = m3_mul(quat_to_m3(pre->dq), so3_exp(jd));
-    const M3 E = m3_mul(m3_t(C), m3_mul(RiT, Rj));
-    so3_log(E, r + 3);
-    m3_vec(Jvbg, dbg, t1);
-    m3_vec(Jvba, dba, t2);
-    for (int k = 0; k < 3; ++k) r[6 + k] = Rb[k] - (pre->dv[k] + t1[k] + t2[k]);
-    if (!J) return;
-    for (int i = 0; i < 9 * 15; ++i) J[i] = 0.0;
-    // d(Rwg G_I) / d rwg = -Rwg [G_I]x Jr(rwg)
-    const M3 dG = m3_mul(RiT, m3_mul(Rwg, m3_mul(hat(G_I), so3_Jr(rwg))));
-    set_block(J, 15, 0, 0, dG, 0.5 * dt2);
-    set_block(J, 15, 0, 3, RiT, -dt);
-    set_block(J, 15, 0, 9, Jpba, -1.0);
-    set_block(J, 15, 0, 12, Jpbg, -1.0);
-    set_block(J, 15, 3, 12, m3_mul(so3_Jr_inv(r + 3), m3_mul(m3_t(E), m3_mul(so3_Jr(jd), Jrbg))), -1.0);
-    set_block(J, 15, 6, 0, dG, dt);
-    set_block(J, 15, 6, 3, RiT, -1.0);
-    set_block(J, 15, 6, 6, RiT);
-    set_block(J, 15, 6, 9, Jvba, -1.0);
-    set_block(J, 15, 6, 12, Jvbg, -1.0);
 }
 
 void apply_upper(const double* U, int n, int cols, const double* in, double* out) {  // out = U in (U: n x n upper)
@@ -323,10 +227,10 @@ int mml_imu_init_factor(const mml_imu_preint* pre, const double* ri, const doubl
                         const double* vi, const double* vj, const double* ba, const double* bg, double* residual,
                         double* jacobian) {
     if (!pre || !ri || !rj || !dp || !rwg || !vi || !vj || !ba || !bg || !residual) return MML_ERR_INVALID;
-    double U[81];
-    if (!mml_sqrt_info_block(pre->covariance, 15, 9, U)) return MML_ERR_STATE;
+    double U[81], ws[sqrt_info_ws(9)];
+    if (!sqrt_info_block(pre->covariance, 15, 9, U, ws)) return MML_ERR_STATE;
     double r[9], J[9 * 15];
-    init_imu_raw(pre, ri, rj, dp, rwg, vi, vj, ba, bg, r, jacobian ? J : nullptr);
+    lio_init_imu_raw(pre, ri, rj, dp, rwg, vi, vj, ba, bg, r, jacobian ? J : nullptr);
     apply_upper(U, 9, 1, r, residual);  // eResiduals.applyOnTheLeft(sqrt_information)
     if (jacobian) apply_upper(U, 9, 15, J, jacobian);
     return MML_OK;
@@ -355,26 +259,27 @@ int mml_lio_initialize(int n, const double* t, double* P, double* Q, double* V, 
         }
     }
     std::vector<double> U((size_t)81 * n);
+    double ws[sqrt_info_ws(9)];
     for (int i = 1; i < n; ++i)
-        if (!mml_sqrt_info_block(pre[i].covariance, 15, 9, &U[81 * (size_t)i])) return MML_ERR_STATE;
+        if (!sqrt_info_block(pre[i].covariance, 15, 9, &U[81 * (size_t)i], ws)) return MML_ERR_STATE;
 
     // 1. average_acc = -GetAverageAcc() of the first frame (the first 31 messages), rescaled to 9.805 (:428-432)
     double acc[3] = {0, 0, 0};
     int cnt = 0;
     for (int s = offsets[0]; s < offsets[1]; ++s) {
         const double* m = samples + 7 * (size_t)s;
-        for (int k = 0; k < 3; ++k) acc[k] += m[3 + k] * kGnorm;
+        for (int k = 0; k < 3; ++k) acc[k] += m[3 + k] * kLioGnorm;
         cnt++;
         if (cnt > 30) break;
     }
     for (int k = 0; k < 3; ++k) acc[k] = -(acc[k] / cnt);
     const double an = sqrt(acc[0] * acc[0] + acc[1] * acc[1] + acc[2] * acc[2]);
-    for (int k = 0; k < 3; ++k) out->average_acc[k] = acc[k] * kGnorm / an;
+    for (int k = 0; k < 3; ++k) out->average_acc[k] = acc[k] * kLioGnorm / an;
 
     // 2. the gravity direction: Cost_Initial_G on para_quat = (1, 0, 0, 0), QuaternionParameterization (:436-455)
     double quat[4] = {1.0, 0.0, 0.0, 0.0};
     const double* avg = out->average_acc;
-    out->gravity_solve = lm_solve([&](const double* q, double* r, double* J) { cost_initial_g(q, avg, r, J); }, true, 4, 3, 3, quat);
+    out->gravity_solve = lm_solve([&](const double* q, double* r, double* J) { lio_cost_initial_g(q, avg, r, J); }, true, 4, 3, 3, quat);
     const double qwg[4] = {quat[1], quat[2], quat[3], quat[0]};  // (x, y, z, w)
     for (int k = 0; k < 4; ++k) out->q_wg[k] = qwg[k];
 
@@ -422,7 +327,7 @@ int mml_lio_initialize(int n, const double* t, double* P, double* Q, double* V, 
             const int row = 9 + 3 * n + 9 * (i - 1);
             double dp[3], rr[9], Jr[9 * 15], Jw[9 * 15];
             for (int k = 0; k < 3; ++k) dp[k] = pb[3 * i + k] - pb[3 * (i - 1) + k];
-            init_imu_raw(&pre[i], &rb[3 * (i - 1)], &rb[3 * i], dp, z, z + 9 + 3 * (i - 1), z + 9 + 3 * i, z + 3, z + 6, rr,
+            lio_init_imu_raw(&pre[i], &rb[3 * (i - 1)], &rb[3 * i], dp, z, z + 9 + 3 * (i - 1), z + 9 + 3 * i, z + 3, z + 6, rr,
                          J ? Jr : nullptr);
             apply_upper(&U[81 * (size_t)i], 9, 1, rr, r + row);
             if (!J) continue;
@@ -436,7 +341,7 @@ int mml_lio_initialize(int n, const double* t, double* P, double* Q, double* V, 
     out->joint_solve = lm_solve(joint, false, nx, nx, m, x.data());
 
     // 5. GravityVector = exp(r_wg) (0, 0, -9.805) (:578-579)
-    const double G_I[3] = {0.0, 0.0, -kGnorm};
+    const double G_I[3] = {0.0, 0.0, -kLioGnorm};
     for (int k = 0; k < 3; ++k) out->r_wg[k] = x[k];
     m3_vec(so3_exp(x.data()), G_I, out->gravity);
     for (int k = 0; k < 3; ++k) {

@@ -28,7 +28,7 @@ __global__ __launch_bounds__(64) void k_lio_preint(const double* samples, const 
     const size_t f = blockIdx.x;
     if (!go[f]) return;
     const int s0 = sample_offsets[f], cnt = sample_offsets[f + 1] - s0;
-    imu_preint_interval(samples + 7 * (size_t)s0, cnt, bg + 3 * (f - 1), ba + 3 * (f - 1), pre + f, s_work);
+    imu_preint_interval<false>(samples + 7 * (size_t)s0, cnt, bg + 3 * (f - 1), ba + 3 * (f - 1), pre + f, s_work);
 }
 
 __global__ __launch_bounds__(64) void k_lio_initialize(const int* frame_offsets, const double* t, double* P, double* Q, double* V, double* bg,
@@ -87,7 +87,7 @@ extern "C" int mml_lio_initialize_batch(mml_ctx* ctx, int n_seg, const int* fram
                 if (pre_in)
                     pre[i] = pre_in[f];
                 else
-                    imu_preint_interval(samples + 7 * (size_t)sample_offsets[f], sample_offsets[f + 1] - sample_offsets[f], bg + 3 * (size_t)(f - 1),
+                    imu_preint_interval<false>(samples + 7 * (size_t)sample_offsets[f], sample_offsets[f + 1] - sample_offsets[f], bg + 3 * (size_t)(f - 1),
                                         ba + 3 * (size_t)(f - 1), &pre[i], *pw);
             }
             const int status = lio_init_segment(n, t + f0, P + 3 * (size_t)f0, Q + 4 * (size_t)f0, V + 3 * (size_t)f0, bg + 3 * (size_t)f0,
@@ -97,7 +97,7 @@ extern "C" int mml_lio_initialize_batch(mml_ctx* ctx, int n_seg, const int* fram
             if (status == 0)  // frame i pre-integrated again from frame i - 1 with that frame's new biases (:602-609)
                 for (int i = 1; i < n; ++i) {
                     const int f = f0 + i;
-                    imu_preint_interval(samples + 7 * (size_t)sample_offsets[f], sample_offsets[f + 1] - sample_offsets[f], bg + 3 * (size_t)(f - 1),
+                    imu_preint_interval<false>(samples + 7 * (size_t)sample_offsets[f], sample_offsets[f + 1] - sample_offsets[f], bg + 3 * (size_t)(f - 1),
                                         ba + 3 * (size_t)(f - 1), &pre[i], *pw);
                 }
             if (pre_out)

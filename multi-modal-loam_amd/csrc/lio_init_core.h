@@ -1,11 +1,14 @@
 // lio_init_core.h -- the LIO initialisation of one segment (TryMAPInitialization, unionPoseEstimation.cpp:425-625), written once
-// for the host loop of mml_lio_initialize_batch and for the device (k_lio_initialize, lio_init_batch.hip).  It is the arithmetic
-// of mml_lio_initialize (lio_init.hip: lm_solve's trust region, Cost_Initial_G, Cost_Initialization_Prior_R / _bv / _IMU, the
-// 9 x 9 sqrt-information blocks, the checks and state writes of its steps 1-7) and departs from it in two places, the two
-// where that function reaches libm:
-//   * quat_plus takes mml_sin / mml_cos (imu_math.h);
-//   * the pre-integrations are not made here at all: the caller hands them in, made by imu_preint_interval (imu_preint.h), and
-//     redoes them with the new biases when the segment comes back with status 0.
+// for the host loop of mml_lio_initialize_batch and for the device (k_lio_initialize, lio_init_batch.hip): lio_lm_solve, the
+// joint problem's evaluation and lio_init_segment, steps 1-7 of mml_lio_initialize (lio_init.hip) for at most LIO_MAX_FRAMES
+// frames with the whole state in one fixed struct.  It also OWNS what that single call shares with it and includes this header
+// for: the cost functions (lio_quat_plus, lio_quat_plus_jacobian, lio_quat_rotate_wxyz, lio_cost_initial_g, lio_init_imu_raw),
+// the Ceres constants and kLioGnorm.  The Cholesky and the 9 x 9 sqrt-information blocks are imu_math.h's, for both.
+// lio_init.hip keeps its own lm_solve and steps 1-7 (any n, vectors sized by n); its header says why.  The routine here departs
+// from that call's arithmetic in two places, the two where it reaches libm:
+//   * lio_quat_plus takes mml_sin / mml_cos (its template argument; imu_math.h);
+//   * the pre-integrations are not made here at all: the caller hands them in, made by imu_preint_interval<false> (imu_preint.h),
+//     and redoes them with the new biases when the segment comes back with status 0.
 // The host build runs every loop from 0 to its end on one thread.  The device build is called by ONE wavefront with the whole
 // solve state (LioWork: the dense Jacobian, the normal matrix, lm_solve's vectors, the factors' blocks) in LDS, through the lane
 // macros of marg_dense.h: MARG_FOR spreads independent elements over the lanes, MARG_LANE gives a sequential piece to one lane,
@@ -27,11 +30,14 @@ namespace {
 constexpr int LIO_MAX_FRAMES = 8;                                 // MML_LIO_BATCH_MAX_FRAMES
 constexpr int LIO_NX = 9 + 3 * LIO_MAX_FRAMES;                    // 33 unknowns: r_wg | b_a | b_g | v_0 .. v_7
 constexpr int LIO_M = LIO_NX + 9 * (LIO_MAX_FRAMES - 1);          // 96 residuals
-constexpr int LIO_SQI = 192;                                      // doubles of work space per sqrt-information block (L | inv | e)
+constexpr int LIO_SQI = 192;                                      // doubles of work space per sqrt-information block
+static_assert(sqrt_info_ws(9) <= LIO_SQI, "imu_math.h's sqrt_info_block on a 9 x 9 block");
 static_assert((LIO_MAX_FRAMES - 1) * LIO_SQI <= LIO_M * LIO_NX, "the sqrt-information work space lies in LioWork::J");
 
-constexpr double kLioGnorm = 9.805;  // IMUIntegrator.h:84
-// Ceres 2.1.0 defaults, as lio_init.hip lists them
+constexpr double kLioGnorm = 9.805;  // IMUIntegrator.h:84, Cost_Initial_G / Cost_Initialization_IMU's G_I (0, 0, -9.805)
+// Ceres 2.1.0 defaults (solver.h): max_num_iterations 50, function / gradient / parameter tolerance 1e-6 / 1e-10 / 1e-8,
+// min_relative_decrease 1e-3, initial / max trust region radius 1e4 / 1e16, min radius 1e-32, LM diagonal clamp
+// [1e-6, 1e32], 5 consecutive invalid steps end the solve (trust_region_minimizer.cc HandleInvalidStep).
 constexpr int kLioMaxIter = 50;
 constexpr double kLioFuncTol = 1e-6, kLioGradTol = 1e-10, kLioParamTol = 1e-8, kLioMinRelDecrease = 1e-3;
 constexpr double kLioRadius0 = 1e4, kLioMaxRadius = 1e16, kLioMinRadius = 1e-32, kLioMinDiag = 1e-6, kLioMaxDiag = 1e32;
@@ -55,56 +61,7 @@ struct LioProblem {  // what the two evaluations read besides LioWork
     const mml_imu_preint* pre;  // n entries, entry 0 unused
 };
 
-// ---- window_imu.hip's cholesky / chol_solve / sqrt_info_block for one thread, the same operations in the same order ---------
-MML_HD bool lio_cholesky_seq(double* A, int n) {
-    for (int j = 0; j < n; ++j) {
-        double d = A[j * n + j];
-        for (int k = 0; k < j; ++k) d -= A[j * n + k] * A[j * n + k];
-        if (!(d > 0.0) || !isfinite(d)) return false;
-        d = sqrt(d);
-        A[j * n + j] = d;
-        for (int i = j + 1; i < n; ++i) {
-            double s = A[i * n + j];
-            for (int k = 0; k < j; ++k) s -= A[i * n + k] * A[j * n + k];
-            A[i * n + j] = s / d;
-        }
-    }
-    return true;
-}
-MML_HD void lio_chol_solve_seq(const double* L, int n, double* b) {
-    for (int i = 0; i < n; ++i) {
-        double s = b[i];
-        for (int k = 0; k < i; ++k) s -= L[i * n + k] * b[k];
-        b[i] = s / L[i * n + i];
-    }
-    for (int i = n - 1; i >= 0; --i) {
-        double s = b[i];
-        for (int k = i + 1; k < n; ++k) s -= L[k * n + i] * b[k];
-        b[i] = s / L[i * n + i];
-    }
-}
-// LLT(cov.block<9,9>(0,0).inverse()).matrixL().transpose() of a 15 x 15 covariance; ws: LIO_SQI doubles
-MML_HD bool lio_sqrt_info9(const double* cov, double* U, double* ws) {
-    const int n = 9;
-    double *L = ws, *inv = ws + 81, *e = ws + 162;
-    for (int r = 0; r < n; ++r)
-        for (int c = 0; c < n; ++c) L[r * n + c] = cov[r * 15 + c];
-    if (!lio_cholesky_seq(L, n)) return false;
-    for (int c = 0; c < n; ++c) {
-        for (int r = 0; r < n; ++r) e[r] = 0.0;
-        e[c] = 1.0;
-        lio_chol_solve_seq(L, n, e);
-        for (int r = 0; r < n; ++r) inv[r * n + c] = e[r];
-    }
-    for (int r = 0; r < n; ++r)
-        for (int c = r + 1; c < n; ++c) inv[r * n + c] = inv[c * n + r] = 0.5 * (inv[r * n + c] + inv[c * n + r]);
-    if (!lio_cholesky_seq(inv, n)) return false;
-    for (int r = 0; r < n; ++r)
-        for (int c = 0; c < n; ++c) U[r * n + c] = (c >= r) ? inv[c * n + r] : 0.0;
-    return true;
-}
-
-// ---- the same Cholesky and substitution for the wavefront --------------------------------------------------------------------
+// ---- imu_math.h's cholesky and chol_solve for the wavefront ------------------------------------------------------------------
 // Column j: every lane takes the pivot's sum itself (the decision is uniform), the rows below are independent.  Only the lower
 // triangle is read, as in the host form.
 MARG_HD bool lio_cholesky_wave(double* A, int n) {
@@ -148,15 +105,17 @@ MARG_HD void lio_chol_solve_wave(const double* L, int n, double* b) {
 }
 
 // ---- the two cost functions ------------------------------------------------------------------------------------------------
-// QuaternionParameterization::Plus, x = (w, x, y, z): [cos|d|, sin|d| / |d| d] (x) x; |d| = 0 leaves x as it is
+// QuaternionParameterization::Plus, x = (w, x, y, z): [cos|d|, sin|d| / |d| d] (x) x; |d| = 0 leaves x as it is.  kLibm (imu_math.h's
+// trig_sin / trig_cos): true in mml_lio_initialize's lm_solve alone, false in lio_lm_solve
+template <bool kLibm>
 MML_HD void lio_quat_plus(const double* x, const double* d, double* o) {
     const double nd = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
     if (!(nd > 0.0)) {
         for (int i = 0; i < 4; ++i) o[i] = x[i];
         return;
     }
-    const double s = mml_sin(nd) / nd;
-    const double z[4] = {mml_cos(nd), s * d[0], s * d[1], s * d[2]};
+    const double s = trig_sin<kLibm>(nd) / nd;
+    const double z[4] = {trig_cos<kLibm>(nd), s * d[0], s * d[1], s * d[2]};
     o[0] = z[0] * x[0] - z[1] * x[1] - z[2] * x[2] - z[3] * x[3];
     o[1] = z[0] * x[1] + z[1] * x[0] + z[2] * x[3] - z[3] * x[2];
     o[2] = z[0] * x[2] - z[1] * x[3] + z[2] * x[0] + z[3] * x[1];
@@ -338,7 +297,7 @@ MML_HD double lio_evaluate(const LioProblem& p, int na, int nl, int m, LioWork& 
     if (p.quat) {
         const double mg[3] = {-w.g[0], -w.g[1], -w.g[2]};
         double xp[4];
-        lio_quat_plus(w.x, mg, xp);
+        lio_quat_plus<false>(w.x, mg, xp);
         for (int i = 0; i < 4; ++i) gmax = fmax(gmax, fabs(w.x[i] - xp[i]));
     } else {
         for (int i = 0; i < na; ++i) {
@@ -438,7 +397,7 @@ MML_HD void lio_lm_solve(const LioProblem& p, int na, int nl, int m, LioWork& w,
         if (p.quat) {
             const double delta[3] = {w.step[0] * w.scale[0], w.step[1] * w.scale[1], w.step[2] * w.scale[2]};
             double xn[4];
-            lio_quat_plus(w.x, delta, xn);
+            lio_quat_plus<false>(w.x, delta, xn);
             MARG_LANE(0) {
                 for (int i = 0; i < 4; ++i) w.xc[i] = xn[i];
             }
@@ -502,7 +461,7 @@ MML_HD int lio_init_segment(int n, const double* t, double* P, double* Q, double
         memset(out, 0, sizeof(*out));
         out->fail_frame = -1;
     }
-    MARG_FOR(f, n - 1) w.ok[f] = lio_sqrt_info9(pre[f + 1].covariance, w.U + 81 * f, w.J + LIO_SQI * f) ? 1 : 0;
+    MARG_FOR(f, n - 1) w.ok[f] = sqrt_info_block(pre[f + 1].covariance, 15, 9, w.U + 81 * f, w.J + LIO_SQI * f) ? 1 : 0;
     MARG_SYNC();
     for (int f = 0; f + 1 < n; ++f)
         if (!w.ok[f]) {

@@ -2,8 +2,10 @@
 // 15 parameters each: O(W) tiny dense work next to the per-frame lidar normal equations that come from the device),
 // compiled into the same library so that it sits behind the same C-ABI; the same trust-region loop resident on the
 // device is fullwindow_dev.hip, the shared arithmetic imu_math.h (IMU residual and Jacobian, the sqrt-information
-// products imu_whiten, the prior residual) and lidar_eval.h's Hget for a record's upper triangle.
+// products imu_whiten, the prior residual, the sequential Cholesky and sqrt_info_block) and lidar_eval.h's Hget for a
+// record's upper triangle.  This file owns the trust-region loop, the factor's entry points and chol_solve_rcp.
 //   * IMUIntegrator::PreIntegration            mm-loam/src/lio/IMUIntegrator.cpp:108-166  -> mml_imu_preintegrate
+//     (the argument checks here; the arithmetic is imu_preint.h's imu_preint_interval, the batch calls' routine)
 //   * Cost_NavState_PRV_Bias (15 residuals)    mm-loam/include/utils/ceresfunc.h:321-393   -> mml_imu_factor
 //     Jacobians: the reference lets Ceres autodiff the functor; here they are analytic (checked against central
 //     differences of the residual in tests/test_imu.py)
@@ -20,40 +22,13 @@
 
 #include "fullwindow_internal.h"
 #include "imu_math.h"
+#include "imu_preint.h"
 #include "lidar_eval.h"
 #include "marg_dense.h"
 
 namespace {
 
-// in-place Cholesky A = L L^T (lower, row-major n x n); false when not positive definite
-bool cholesky(double* A, int n) {
-    for (int j = 0; j < n; ++j) {
-        double d = A[j * n + j];
-        for (int k = 0; k < j; ++k) d -= A[j * n + k] * A[j * n + k];
-        if (!(d > 0.0) || !isfinite(d)) return false;
-        d = sqrt(d);
-        A[j * n + j] = d;
-        for (int i = j + 1; i < n; ++i) {
-            double s = A[i * n + j];
-            for (int k = 0; k < j; ++k) s -= A[i * n + k] * A[j * n + k];
-            A[i * n + j] = s / d;
-        }
-    }
-    return true;
-}
-void chol_solve(const double* L, int n, double* b) {
-    for (int i = 0; i < n; ++i) {
-        double s = b[i];
-        for (int k = 0; k < i; ++k) s -= L[i * n + k] * b[k];
-        b[i] = s / L[i * n + i];
-    }
-    for (int i = n - 1; i >= 0; --i) {
-        double s = b[i];
-        for (int k = i + 1; k < n; ++k) s -= L[k * n + i] * b[k];
-        b[i] = s / L[i * n + i];
-    }
-}
-// The same with the reciprocals of the diagonal taken once and multiplied in: the form the device-resident solver
+// imu_math.h's chol_solve with the reciprocals of the diagonal taken once and multiplied in: the form the device-resident solver
 // (fullwindow_dev.hip) uses, where a division would sit on the dependency chain of every substitution step.  The terms of a
 // row are subtracted in the order a column-by-column (right-looking) substitution meets them -- ascending k forwards,
 // DESCENDING k backwards, "the columns become known from the last one down" -- which is the device's order: the two
@@ -72,125 +47,22 @@ void chol_solve_rcp(const double* L, int n, double* b) {
         b[i] = s * rd[i];
     }
 }
-constexpr double kGnorm = 9.805;                                        // IMUIntegrator.h:84
-constexpr double kAccN = 0.08, kGyrN = 0.004, kAccW = 2.0e-4, kGyrW = 2.0e-5;  // IMUIntegrator.h:79-82
-
-// sqrt information of the leading n x n block (n <= 15) of a covariance stored with row stride ld:
-// LLT(block^-1).matrixL().transpose(), n x n upper, row-major
-bool sqrt_info_block(const double* cov, int ld, int n, double* U) {
-    double L[225];
-    for (int r = 0; r < n; ++r)
-        for (int c = 0; c < n; ++c) L[r * n + c] = cov[r * ld + c];
-    if (!cholesky(L, n)) return false;
-    double inv[225];
-    for (int c = 0; c < n; ++c) {
-        double e[15] = {0};
-        e[c] = 1.0;
-        chol_solve(L, n, e);
-        for (int r = 0; r < n; ++r) inv[r * n + c] = e[r];
-    }
-    for (int r = 0; r < n; ++r)
-        for (int c = r + 1; c < n; ++c) inv[r * n + c] = inv[c * n + r] = 0.5 * (inv[r * n + c] + inv[c * n + r]);
-    if (!cholesky(inv, n)) return false;
-    for (int r = 0; r < n; ++r)
-        for (int c = 0; c < n; ++c) U[r * n + c] = (c >= r) ? inv[c * n + r] : 0.0;  // U = L^T
-    return true;
-}
-
 // sqrt information of one pre-integration: LLT(covariance^-1).matrixL().transpose() (Estimator.cpp:1240-1242)
-bool imu_sqrt_info(const mml_imu_preint* pre, double* U /*15x15 upper*/) { return sqrt_info_block(pre->covariance, 15, 15, U); }
+bool imu_sqrt_info(const mml_imu_preint* pre, double* U /*15x15 upper*/) {
+    double ws[sqrt_info_ws(15)];
+    return sqrt_info_block(pre->covariance, 15, 15, U, ws);
+}
 
 }  // namespace
 
-bool mml_imu_sqrt_info(const mml_imu_preint* pre, double* U) { return imu_sqrt_info(pre, U); }
-bool mml_sqrt_info_block(const double* cov, int ld, int n, double* U) { return n >= 1 && n <= 15 && sqrt_info_block(cov, ld, n, U); }
-bool mml_cholesky(double* A, int n) { return cholesky(A, n); }
-void mml_chol_solve(const double* L, int n, double* b) { chol_solve(L, n, b); }
-
 extern "C" {
 
+// imu_preint.h's routine with libm in the right Jacobian.  Sample values are not checked; with a non-finite sample the output is
+// unspecified.
 int mml_imu_preintegrate(const double* samples, int n, const double* bg, const double* ba, mml_imu_preint* out) {
     if (!out || n < 0 || (n > 0 && !samples) || !bg || !ba) return MML_ERR_INVALID;
-    // Reset() (:49-58)
-    memset(out, 0, sizeof(*out));
-    out->dq[3] = 1.0;
-    for (int i = 0; i < 15; ++i) out->jacobian[i * 15 + i] = 1.0;
-    for (int k = 0; k < 3; ++k) {
-        out->bg[k] = bg[k];
-        out->ba[k] = ba[k];
-    }
-    double noise[12] = {kGyrN * kGyrN, kGyrN* kGyrN, kGyrN* kGyrN, kAccN* kAccN, kAccN* kAccN, kAccN* kAccN,
-                        kGyrW* kGyrW, kGyrW* kGyrW, kGyrW* kGyrW, kAccW* kAccW, kAccW* kAccW, kAccW* kAccW};  // :33-37 (diagonal)
-    std::vector<double> A(225), B(15 * 12), T(225), T2(225);
-    for (int s = 0; s < n; ++s) {
-        const double* m = samples + 7 * s;
-        double gyr[3] = {m[0] - bg[0], m[1] - bg[1], m[2] - bg[2]};
-        double acc[3] = {m[3] * kGnorm - ba[0], m[4] * kGnorm - ba[1], m[5] * kGnorm - ba[2]};
-        const double dt = m[6], dt2 = dt * dt;
-        double gdt[3] = {gyr[0] * dt, gyr[1] * dt, gyr[2] * dt};
-        const M3 dR = so3_exp(gdt);
-        M3 Jr = m3_identity();
-        const double nrm = sqrt((gdt[0] * gdt[0] + gdt[1] * gdt[1]) + gdt[2] * gdt[2]);
-        if (nrm > 0.00001) {  // :129-135
-            double k[3] = {gdt[0] / nrm, gdt[1] / nrm, gdt[2] / nrm};
-            const M3 K = hat(k);
-            Jr = m3_add(m3_add(m3_identity(), m3_scale(K, -(1 - cos(nrm)) / nrm)), m3_scale(m3_mul(K, K), 1 - sin(nrm) / nrm));
-        }
-        const M3 Rq = quat_to_m3(out->dq);
-        const M3 RqA = m3_mul(Rq, hat(acc));
-        for (int i = 0; i < 225; ++i) A[i] = 0;
-        for (int i = 0; i < 15; ++i) A[i * 15 + i] = 1.0;
-        set_block(A.data(), 15, 0, 3, RqA, -0.5 * dt2);
-        set_block(A.data(), 15, 0, 6, m3_identity(), dt);
-        set_block(A.data(), 15, 0, 12, Rq, -0.5 * dt2);
-        set_block(A.data(), 15, 3, 3, m3_t(dR));
-        set_block(A.data(), 15, 3, 9, Jr, -dt);
-        set_block(A.data(), 15, 6, 3, RqA, -dt);
-        set_block(A.data(), 15, 6, 12, Rq, -dt);
-        for (int i = 0; i < 15 * 12; ++i) B[i] = 0;
-        set_block(B.data(), 12, 0, 3, Rq, 0.5 * dt2);
-        set_block(B.data(), 12, 3, 0, Jr, dt);
-        set_block(B.data(), 12, 6, 3, Rq, dt);
-        set_block(B.data(), 12, 9, 6, m3_identity(), dt);
-        set_block(B.data(), 12, 12, 9, m3_identity(), dt);
-        // jacobian = A * jacobian
-        for (int r = 0; r < 15; ++r)
-            for (int c = 0; c < 15; ++c) {
-                double acc_ = 0;
-                for (int k = 0; k < 15; ++k) acc_ += A[r * 15 + k] * out->jacobian[k * 15 + c];
-                T[r * 15 + c] = acc_;
-            }
-        memcpy(out->jacobian, T.data(), sizeof(double) * 225);
-        // covariance = A * covariance * A^T + B * noise * B^T
-        for (int r = 0; r < 15; ++r)
-            for (int c = 0; c < 15; ++c) {
-                double acc_ = 0;
-                for (int k = 0; k < 15; ++k) acc_ += A[r * 15 + k] * out->covariance[k * 15 + c];
-                T[r * 15 + c] = acc_;
-            }
-        for (int r = 0; r < 15; ++r)
-            for (int c = 0; c < 15; ++c) {
-                double acc_ = 0;
-                for (int k = 0; k < 15; ++k) acc_ += T[r * 15 + k] * A[c * 15 + k];
-                double bn = 0;
-                for (int k = 0; k < 12; ++k) bn += B[r * 12 + k] * noise[k] * B[c * 12 + k];
-                T2[r * 15 + c] = acc_ + bn;
-            }
-        memcpy(out->covariance, T2.data(), sizeof(double) * 225);
-        // dp += dv*dt + 0.5*dq*acc*dt2 ; dv += dq*acc*dt   (:159-160)
-        double Ra[3];
-        m3_vec(Rq, acc, Ra);
-        for (int k = 0; k < 3; ++k) out->dp[k] += out->dv[k] * dt + 0.5 * Ra[k] * dt2;
-        for (int k = 0; k < 3; ++k) out->dv[k] += Ra[k] * dt;
-        // dq = normalized(Quaterniond(dq.matrix() * dR)), w >= 0  (:161-165)
-        double q[4];
-        m3_to_quat(m3_mul(Rq, dR), q);
-        if (q[3] < 0)
-            for (int k = 0; k < 4; ++k) q[k] = -q[k];
-        const double nq = sqrt((q[0] * q[0] + q[1] * q[1]) + (q[2] * q[2] + q[3] * q[3]));
-        for (int k = 0; k < 4; ++k) out->dq[k] = q[k] / nq;
-        out->dtime += dt;
-    }
+    PreintWork work;
+    imu_preint_interval<true>(samples, n, bg, ba, out, work);
     return MML_OK;
 }
 

@@ -1,6 +1,6 @@
 """mml_imu_preintegrate_batch with a NULL context -- the host build of csrc/imu_preint.h, the routine the device runs -- against
-mml_imu_preintegrate (bytes wherever no sin / cos of a step angle is taken, the tolerances of tests/test_imu.py elsewhere) and
-against oracle/imu_oracle.py::preintegrate; the argument checks; odometry.preintegrate_windows; the adapter's
+mml_imu_preintegrate (bytes wherever no sin / cos of a step angle is taken; elsewhere the bytes of dp, dv, dq, dtime, bg, ba and
+the tolerances of tests/test_imu.py on the rest) and against oracle/imu_oracle.py::preintegrate; the argument checks; odometry.preintegrate_windows; the adapter's
 PreIntegrationBatch.  The input builders are shared with tests/test_gpu_imu_preint_batch.py."""
 import ctypes as C
 import importlib
@@ -128,6 +128,25 @@ def test_bytes_of_the_single_call_where_no_sin_or_cos_is_taken(M):
     assert np.array_equal(np.array(pre.jacobian).reshape(15, 15), np.eye(15)) and not np.any(np.array(pre.covariance))
     assert list(pre.dq) == [0, 0, 0, 1] and pre.dtime == 0 and not np.any(list(pre.dp) + list(pre.dv))
     assert np.array_equal(np.array(pre.bg), BG) and np.array_equal(np.array(pre.ba), BA)
+
+
+def test_state_bytes_of_the_single_call_where_sin_and_cos_are_taken(M, synth):
+    """Every step rotates by more than the gate, so the single call takes libm's sin / cos and the batch call mml_sin / mml_cos
+    -- in the right Jacobian only, which feeds the Jacobian and covariance chains and nothing else: dp, dv, dq, dtime, bg, ba
+    (the struct up to `jacobian`) have the single call's bytes.  The two calls run one routine (csrc/imu_preint.h) that differs
+    in that choice alone; a choice wired to any other sin / cos (so3_exp's) would show here."""
+    state = M.ImuPreint.jacobian.offset
+    assert state == 17 * 8 and M.ImuPreint.covariance.offset == state + 225 * 8
+    cases = tolerance_cases(synth)
+    smp, bgs, bas = mixed_batch(synth)
+    cases += [("mixed %d" % i, s, bgs[i], bas[i]) for i, s in enumerate(smp) if i in (0, 2, 3, 6, 8)]
+    assert len(cases) == 9
+    for name, s, bg, ba in cases:
+        gdt = (s[:, :3] - bg) * s[:, 6:7]
+        nrm = np.sqrt((gdt[:, 0] * gdt[:, 0] + gdt[:, 1] * gdt[:, 1]) + gdt[:, 2] * gdt[:, 2])
+        assert len(s) and np.all(nrm > GATE), name
+        (pre,) = M.imu_preintegrate_batch([s], bg, ba)
+        assert bytes(pre)[:state] == bytes(M.imu_preintegrate(s, bg, ba))[:state], name
 
 
 def test_against_the_oracle_and_the_single_call(M, synth):
