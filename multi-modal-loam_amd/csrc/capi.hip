@@ -10,13 +10,13 @@
 
 #include <algorithm>
 
+#include "imu_math.h"
 #include "mml_internal.h"
 
 int mml_launch_detect_line(mml_ctx* ctx, int n, uint16_t* d_final);
 
 namespace {
 
-constexpr int kPackMaxSlots = 16;  // calls of up to this many slots move their parameter blocks / results in one copy each way
 // pinned staging ring for small host<->device parameter blocks
 constexpr size_t kStageDoubles = 1u << 22;  // 32 MiB: a 1024-scan step stages ~45 k doubles; a wrap synchronises the device
 
@@ -244,7 +244,7 @@ int mml_create(const mml_config* cfg, int device, mml_ctx** out) {
     ALLOC(ctx->map_vals, MM);
     ALLOC(ctx->map_vals2, MM);
     ALLOC(ctx->d_x, B * 6);
-    ALLOC(ctx->d_pose_in, B * 64);
+    ALLOC(ctx->d_pose_in, B * kPoseSlotDoubles);
     ALLOC(ctx->d_result, B * MML_SOLVE_RESULT);
     ALLOC(ctx->d_summ, B * 8);
     ALLOC(ctx->d_trace, B * 6 * 64);
@@ -847,7 +847,7 @@ int mml_cloud_download_registered_batch(mml_ctx* ctx, int first_slot, int count,
         h_off[i] = run;
         run += h_info[8 * i];
     }
-    double* d_par = ctx->d_pose_in + 64 * (size_t)first_slot;
+    double* d_par = ctx->d_pose_in + kPoseSlotDoubles * (size_t)first_slot;
     MML_HIP(hipMemcpyAsync(d_par, h_par, sizeof(double) * 17 * (size_t)count, hipMemcpyHostToDevice, MML_STREAM(ctx)));
     const SlotArrays A = slot_arrays(ctx, first_slot);
     hipLaunchKernelGGL(k_encode_registered, dim3((ctx->NT + 255) / 256, count), dim3(256), 0, MML_STREAM(ctx), A, d_par, count,
@@ -1022,25 +1022,19 @@ int mml_detect_line(mml_ctx* ctx, const float* pts, int n, int* sharp, int* n_sh
     return MML_OK;
 }
 
-// the sweep motions of `count` slots into the call's slice of d_pose_in, then the whole cloud (the entry point) or the listed points
-// (mml_step) undistorted with them
-static int undistort_enqueue(mml_ctx* ctx, int first_slot, int count, const double* dR, const double* dt, bool listed_only) {
-    double* st = stage_alloc(ctx, 12 * (size_t)count);
-    for (int i = 0; i < count; ++i) {
-        memcpy(st + 12 * i, dR + 9 * i, sizeof(double) * 9);
-        memcpy(st + 12 * i + 9, dt + 3 * i, sizeof(double) * 3);
-    }
-    double* d_par = ctx->d_pose_in + 64 * (size_t)first_slot;  // 64 doubles per slot: [0, 12*count) of this call's slice
-    MML_HIP(hipMemcpyAsync(d_par, st, sizeof(double) * 12 * count, hipMemcpyHostToDevice, MML_STREAM(ctx)));
-    return listed_only ? mml_launch_undistort_listed(ctx, first_slot, count, d_par) : mml_launch_undistort(ctx, first_slot, count, d_par);
-}
-
 int mml_undistort(mml_ctx* ctx, int first_slot, int count, const double* dR, const double* dt) {
     CHECK_SLOTS(first_slot, count);
     MML_REQUIRE(dR && dt, MML_ERR_INVALID, "null dR/dt");
     int rc = mml_cloud_settle(ctx, first_slot, count);  // (a second undistortion starts from a complete first one)
     if (rc != MML_OK) return rc;
-    return undistort_enqueue(ctx, first_slot, count, dR, dt, false);
+    double* st = stage_alloc(ctx, 12 * (size_t)count);  // the sweep motions, at the start of the slots' range of d_pose_in
+    for (int i = 0; i < count; ++i) {
+        memcpy(st + 12 * i, dR + 9 * i, sizeof(double) * 9);
+        memcpy(st + 12 * i + 9, dt + 3 * i, sizeof(double) * 3);
+    }
+    double* d_par = ctx->d_pose_in + kPoseSlotDoubles * (size_t)first_slot;
+    MML_HIP(hipMemcpyAsync(d_par, st, sizeof(double) * 12 * count, hipMemcpyHostToDevice, MML_STREAM(ctx)));
+    return mml_launch_undistort(ctx, first_slot, count, d_par);
 }
 
 int mml_downsample(mml_ctx* ctx, int first_slot, int count) {
@@ -1242,19 +1236,15 @@ static void finish_stats(const double* s, mml_assoc_stats* o) {
     o->is_degenerate = o->min_singular < 3.0 ? 1 : 0;  // Estimator.cpp:772-775
 }
 
-static int associate_enqueue(mml_ctx* ctx, int first_slot, int count, const double* T_wl, double thres_dist, bool with_stats) {
+int mml_associate(mml_ctx* ctx, int first_slot, int count, const double* T_wl, double thres_dist,
+                  mml_assoc_stats* stats) {
     CHECK_SLOTS(first_slot, count);
     MML_REQUIRE(T_wl != nullptr, MML_ERR_INVALID, "null T_wl");
     MML_REQUIRE(ctx->have_map[0] && ctx->have_map[1], MML_ERR_STATE, "mml_associate before both maps were set");
-    double* d_T = ctx->d_pose_in + 64 * (size_t)first_slot;
+    double* d_T = ctx->d_pose_in + kPoseSlotDoubles * (size_t)first_slot;
     int rc = upload_doubles(ctx, d_T, T_wl, 16 * (size_t)count);
     if (rc != MML_OK) return rc;
-    return mml_launch_associate(ctx, first_slot, count, d_T, thres_dist, with_stats);
-}
-
-int mml_associate(mml_ctx* ctx, int first_slot, int count, const double* T_wl, double thres_dist,
-                  mml_assoc_stats* stats) {
-    int rc = associate_enqueue(ctx, first_slot, count, T_wl, thres_dist, true);
+    rc = mml_launch_associate(ctx, first_slot, count, d_T, thres_dist, true);
     if (rc != MML_OK) return rc;
     if (stats) {
         double* h = stage_alloc(ctx, 16 * (size_t)count);  // pinned
@@ -1361,7 +1351,7 @@ int mml_linearize_record(mml_ctx* ctx, int slot, const double* x, const double* 
     double h[22];
     memcpy(h, x, sizeof(double) * 6);
     memcpy(h + 6, T_bl, sizeof(double) * 16);
-    double* d_par = ctx->d_pose_in + 64 * (size_t)slot;
+    double* d_par = ctx->d_pose_in + kPoseSlotDoubles * (size_t)slot;
     int rc = upload_doubles(ctx, d_par, h, 22);
     if (rc != MML_OK) return rc;
     return mml_launch_linearize(ctx, slot, d_par, d_par + 6, plan_weight_tan, huber_delta, d_record);
@@ -1375,7 +1365,7 @@ int mml_linearize_window(mml_ctx* ctx, int first_slot, int frames, int x_stride,
     for (int f = 0; f < frames; ++f) memcpy(h + 6 * f, x + (size_t)x_stride * f, sizeof(double) * 6);
     memcpy(h + 6 * frames, T_bl, sizeof(double) * 16);
     // 64 doubles of parameter space per slot: poses of the window, then T_bl, in the first slot's block
-    double* d_par = ctx->d_pose_in + 64 * (size_t)first_slot;
+    double* d_par = ctx->d_pose_in + kPoseSlotDoubles * (size_t)first_slot;
     int rc = upload_doubles(ctx, d_par, h, 6 * (size_t)frames + 16);
     if (rc != MML_OK) return rc;
     double* d_rec = ctx->d_rec + 32 * (size_t)first_slot;
@@ -1408,24 +1398,18 @@ int mml_linearize(mml_ctx* ctx, int slot, const double* x, const double* T_bl, d
     return MML_OK;
 }
 
-// enqueue only: upload x and T_bl for slots [first, first+count), launch the solver on the current lane
-static int solve_enqueue(mml_ctx* ctx, int first_slot, int count, int window, const double* T_bl,
-                         const mml_solve_opts* opts, const double* x, bool want_trace) {
-    int rc = upload_doubles(ctx, ctx->d_x + 6 * (size_t)first_slot, x, 6 * (size_t)count);
-    if (rc != MML_OK) return rc;
-    double* d_Tbl = ctx->d_pose_in + 64 * (size_t)(first_slot + count) - 16;  // tail of this call's slice
-    rc = upload_doubles(ctx, d_Tbl, T_bl, 16);
-    if (rc != MML_OK) return rc;
-    return mml_launch_solve(ctx, first_slot, count, window, d_Tbl, *opts, want_trace);
-}
-
 int mml_solve(mml_ctx* ctx, int first_slot, int count, int window, const double* T_bl, const mml_solve_opts* opts,
               double* x, mml_solve_summary* summaries, double* trace) {
     CHECK_SLOTS(first_slot, count);
     MML_REQUIRE(T_bl && opts && x, MML_ERR_INVALID, "null argument");
     MML_REQUIRE(opts->max_num_iterations >= 0 && opts->max_num_iterations <= 64, MML_ERR_INVALID,
                 "max_num_iterations must be in [0, 64]");
-    int rc = solve_enqueue(ctx, first_slot, count, window, T_bl, opts, x, trace != nullptr);
+    int rc = upload_doubles(ctx, ctx->d_x + 6 * (size_t)first_slot, x, 6 * (size_t)count);
+    if (rc != MML_OK) return rc;
+    double* d_Tbl = ctx->d_pose_in + kPoseSlotDoubles * (size_t)(first_slot + count) - 16;  // tail of this call's range
+    rc = upload_doubles(ctx, d_Tbl, T_bl, 16);
+    if (rc != MML_OK) return rc;
+    rc = mml_launch_solve(ctx, first_slot, count, window, d_Tbl, *opts, trace != nullptr);
     if (rc != MML_OK) return rc;
     const int nprob = count / window;
     double* hx = stage_alloc(ctx, 6 * (size_t)count + 8 * (size_t)nprob);  // pinned read-back area: poses, then summaries
@@ -1441,7 +1425,6 @@ int mml_solve(mml_ctx* ctx, int first_slot, int count, int window, const double*
         bool open = false;
         for (int p = 0; p < nprob; ++p) open = open || hs[8 * p + 5] != 0.0;
         if (open) {
-            const double* d_Tbl = ctx->d_pose_in + 64 * (size_t)(first_slot + count) - 16;
             rc = mml_window_solve_continue(ctx, first_slot, count, window, d_Tbl, *opts);
             if (rc != MML_OK) return rc;
             MML_HIP(hipMemcpyAsync(hx, ctx->d_x + 6 * (size_t)first_slot, sizeof(double) * 6 * count, hipMemcpyDeviceToHost, MML_STREAM(ctx)));
@@ -1462,6 +1445,7 @@ int mml_solve(mml_ctx* ctx, int first_slot, int count, int window, const double*
 }
 
 // ---- small host-side SO(3) helpers for the orchestration entry points (outside the kernels) ----------------
+// (not imu_math.h's so3_exp_q / so3_log: these call libm where those call mml_sin / mml_cos / mml_atan, and pinned results depend on it)
 static void so3_exp_h(const double* phi, double* q) {  // sophus/so3.hpp:585-622
     double th2 = (phi[0] * phi[0] + phi[1] * phi[1]) + phi[2] * phi[2];
     double imag, real;
@@ -1497,15 +1481,6 @@ static void so3_log_h(const double* qin, double* phi) {  // sophus/so3.hpp:247-2
     phi[1] = f * q[1];
     phi[2] = f * q[2];
 }
-static void quat_to_R_h(const double* q, double* R) {
-    const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
-    const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
-    const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
-    const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
-    R[0] = 1 - (tyy + tzz); R[1] = txy - twz;       R[2] = txz + twy;
-    R[3] = txy + twz;       R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy;       R[7] = tyz + twx;       R[8] = 1 - (txx + tyy);
-}
 // T_bl = inverse(exTlb) (Estimator.cpp:157-159 / :1155-1156)
 static void invert_extrinsic(const double* exTlb, double* T_bl) {
     for (int r = 0; r < 3; ++r)
@@ -1517,8 +1492,8 @@ static void invert_extrinsic(const double* exTlb, double* T_bl) {
 }
 // transformTobeMapped = [Q * exRbl, Q * exPbl + P] (Estimator.cpp:1268-1270) from x = [t, phi]
 static void pose_to_Twl(const double* q, const double* P, const double* T_bl, double* T) {
-    double R[9];
-    quat_to_R_h(q, R);
+    const M3 Rq = quat_to_m3(q);
+    const double* R = Rq.a;
     for (int r = 0; r < 3; ++r) {
         for (int c = 0; c < 3; ++c)
             T[4 * r + c] = (R[3 * r] * T_bl[c] + R[3 * r + 1] * T_bl[4 + c]) + R[3 * r + 2] * T_bl[8 + c];
@@ -1526,6 +1501,84 @@ static void pose_to_Twl(const double* q, const double* P, const double* T_bl, do
     }
     T[12] = T[13] = T[14] = 0;
     T[15] = 1;
+}
+
+// ---- the pose calls (mml_step, mml_estimate): one parameter block down, one read-back up --------------------
+// Fills the pinned twin of `dev` (returned in *host) and sends it down in ONE copy on the current lane.  dR / dt null: a call
+// without sweep motions, the copy starts behind their field.  Q null: the association poses come from x, else from Q as it is.
+static int pose_upload(mml_ctx* ctx, const PoseBlock& dev, const double* dR, const double* dt, const double* x, const double* Q,
+                       const double* T_bl, PoseBlock* host) {
+    const PoseBlock h = dev.at(stage_alloc(ctx, dev.size()));
+    for (size_t i = 0; i < (size_t)dev.count; ++i) {
+        if (dR) {
+            memcpy(h.und() + PoseBlock::kUnd * i, dR + 9 * i, sizeof(double) * 9);
+            memcpy(h.und() + PoseBlock::kUnd * i + 9, dt + 3 * i, sizeof(double) * 3);
+        }
+        double q[4];
+        if (!Q) so3_exp_h(x + 6 * i + 3, q);
+        pose_to_Twl(Q ? Q + 4 * i : q, x + 6 * i, T_bl, h.T_wl() + PoseBlock::kTwl * i);
+    }
+    memcpy(h.x(), x, sizeof(double) * PoseBlock::kX * dev.count);
+    memcpy(h.T_bl(), T_bl, sizeof(double) * PoseBlock::kTbl);
+    const size_t from = dR ? dev.o_und() : dev.o_Twl();
+    MML_HIP(hipMemcpyAsync(dev.base + from, h.base + from, sizeof(double) * (dev.size() - from), hipMemcpyHostToDevice, MML_STREAM(ctx)));
+    *host = h;
+    return MML_OK;
+}
+
+// The pinned read-back area of a call of `count` slots from `first`, MML_SOLVE_RESULT doubles per slot.  packed: k_solve's result
+// records.  Else: the poses from d_x (6 per slot) | the two ft_n rows (ints) | with `stats` the association statistics (16 per slot).
+struct PoseBack {
+    bool packed, stats;
+    int first, count;
+    double* h;
+    int* ftn() const { return reinterpret_cast<int*>(h + 6 * (size_t)count); }
+    double* stat() const { return h + 7 * (size_t)count; }
+};
+static_assert(6 + 1 + 16 <= MML_SOLVE_RESULT, "the unpacked read-back fits the area of the records");
+
+// the solve of one block on the current lane and its part of the read-back behind it
+static int pose_solve_enqueue(mml_ctx* ctx, const PoseBlock& dev, const PoseBlock& host, const mml_solve_opts& so, const PoseBack& back) {
+    const int f = dev.first;
+    const size_t c = (size_t)dev.count, off = (size_t)(f - back.first);
+    if (back.packed) {
+        double* d_res = ctx->d_result + MML_SOLVE_RESULT * (size_t)f;
+        int rc = mml_launch_solve(ctx, f, dev.count, 1, dev.T_bl(), so, false, dev.x(), d_res);
+        if (rc != MML_OK) return rc;
+        MML_HIP(hipMemcpyAsync(back.h + MML_SOLVE_RESULT * off, d_res, sizeof(double) * MML_SOLVE_RESULT * c, hipMemcpyDeviceToHost, MML_STREAM(ctx)));
+        return MML_OK;
+    }
+    // (without result records k_solve starts from d_x and leaves the poses there)
+    MML_HIP(hipMemcpyAsync(ctx->d_x + 6 * (size_t)f, host.x(), sizeof(double) * 6 * c, hipMemcpyHostToDevice, MML_STREAM(ctx)));
+    int rc = mml_launch_solve(ctx, f, dev.count, 1, dev.T_bl(), so, false);
+    if (rc != MML_OK) return rc;
+    MML_HIP(hipMemcpyAsync(back.h + 6 * off, ctx->d_x + 6 * (size_t)f, sizeof(double) * 6 * c, hipMemcpyDeviceToHost, MML_STREAM(ctx)));
+    for (int kind = 0; kind < 2; ++kind)
+        MML_HIP(hipMemcpyAsync(back.ftn() + (size_t)kind * back.count + off, ctx->ft_n + (size_t)kind * ctx->B + f, sizeof(int) * c,
+                               hipMemcpyDeviceToHost, MML_STREAM(ctx)));
+    if (back.stats)
+        MML_HIP(hipMemcpyAsync(back.stat() + 16 * off, ctx->assoc_stats + 16 * (size_t)f, sizeof(double) * 16 * c, hipMemcpyDeviceToHost,
+                               MML_STREAM(ctx)));
+    return MML_OK;
+}
+
+// after the synchronisation: the poses (6 per slot), the stack sizes (ftn[kind * count + i]; a negative one is the down-sampler's
+// overflow mark) and, for a read-back with statistics, those
+static void pose_back_finish(const PoseBack& b, double* x, int* ftn, mml_assoc_stats* st) {
+    const size_t n = (size_t)b.count;
+    if (!b.packed) {
+        memcpy(x, b.h, sizeof(double) * 6 * n);
+        memcpy(ftn, b.ftn(), sizeof(int) * 2 * n);
+    }
+    for (size_t i = 0; i < n; ++i) {
+        const double* r = b.h + MML_SOLVE_RESULT * i;  // the record: pose (6), the two stack sizes, association statistics (16)
+        if (b.packed) {
+            memcpy(x + 6 * i, r, sizeof(double) * 6);
+            ftn[i] = (int)r[6];
+            ftn[n + i] = (int)r[7];
+        }
+        if (st) finish_stats(b.packed ? r + 8 : b.stat() + 16 * i, &st[i]);
+    }
 }
 
 int mml_estimate(mml_ctx* ctx, int first_slot, int count, const double* exTlb, double* P, double* Q, int max_outer,
@@ -1536,10 +1589,11 @@ int mml_estimate(mml_ctx* ctx, int first_slot, int count, const double* exTlb, d
     double T_bl[16];
     invert_extrinsic(exTlb, T_bl);
     std::vector<int> done(count, 0), outer(count, 0), degen(count, 0);
-    std::vector<double> x(6 * (size_t)count), Twl(16 * (size_t)count);
+    std::vector<double> x(6 * (size_t)count), xs(6 * (size_t)count);
     std::vector<mml_assoc_stats> st(count);
-    std::vector<int> last_fn(2 * (size_t)count, 0);  // the slots' stack sizes as the last result records reported them
-    bool have_fn = false;
+    std::vector<int> fn(2 * (size_t)count, 0);  // the slots' stack sizes as the last read-back reported them
+    const bool packed = mml_pose_packed(count, ctx->cus);
+    const PoseBlock dev = PoseBlock::of(ctx->d_pose_in, first_slot, count);
     double thres = 25.0;  // Estimator.cpp:1207
     mml_solve_opts so;
     so.max_num_iterations = inner_iters;
@@ -1556,53 +1610,20 @@ int mml_estimate(mml_ctx* ctx, int first_slot, int count, const double* exTlb, d
             x[6 * i] = P[3 * i];
             x[6 * i + 1] = P[3 * i + 1];
             x[6 * i + 2] = P[3 * i + 2];
-            pose_to_Twl(Q + 4 * i, P + 3 * i, T_bl, &Twl[16 * i]);
         }
         // association and solve are enqueued back to back and read back together: one host synchronisation per outer
         // iteration (the statistics of the association only feed the degeneracy flag, nothing the solve waits for)
-        std::vector<double> xs = x;
-        int rc;
-        if (count <= kPackMaxSlots) {
-            // (the live path: one copy down -- T_wl | x | T_bl --, one record per slot up -- pose, stack sizes, statistics; see mml_step)
-            const size_t c = (size_t)count, n = 22 * c + 16;
-            double* hp = stage_alloc(ctx, n);
-            double* dp = ctx->d_pose_in + 64 * (size_t)first_slot;
-            memcpy(hp, Twl.data(), sizeof(double) * 16 * c);
-            memcpy(hp + 16 * c, x.data(), sizeof(double) * 6 * c);
-            memcpy(hp + 22 * c, T_bl, sizeof(double) * 16);
-            MML_HIP(hipMemcpyAsync(dp, hp, sizeof(double) * n, hipMemcpyHostToDevice, MML_STREAM(ctx)));
-            rc = mml_launch_associate(ctx, first_slot, count, dp, thres, true);
-            if (rc != MML_OK) return rc;
-            thres = (it == 0) ? 10.0 : 1.0;  // :1377-1381
-            double* d_res = ctx->d_result + MML_SOLVE_RESULT * (size_t)first_slot;
-            rc = mml_launch_solve(ctx, first_slot, count, 1, dp + 22 * c, so, false, dp + 16 * c, d_res);
-            if (rc != MML_OK) return rc;
-            double* h_res = stage_alloc(ctx, MML_SOLVE_RESULT * c);
-            MML_HIP(hipMemcpyAsync(h_res, d_res, sizeof(double) * MML_SOLVE_RESULT * c, hipMemcpyDeviceToHost, MML_STREAM(ctx)));
-            MML_HIP(hipStreamSynchronize(MML_STREAM(ctx)));
-            for (int i = 0; i < count; ++i) {
-                const double* r = h_res + MML_SOLVE_RESULT * (size_t)i;
-                finish_stats(r + 8, &st[i]);
-                memcpy(&xs[6 * (size_t)i], r, sizeof(double) * 6);
-                last_fn[2 * i] = (int)r[6];
-                last_fn[2 * i + 1] = (int)r[7];
-            }
-            have_fn = true;
-        } else {
-        rc = mml_associate(ctx, first_slot, count, Twl.data(), thres, nullptr);
+        PoseBlock host;
+        int rc = pose_upload(ctx, dev, nullptr, nullptr, x.data(), Q, T_bl, &host);
+        if (rc != MML_OK) return rc;
+        rc = mml_launch_associate(ctx, first_slot, count, dev.T_wl(), thres, true);
         if (rc != MML_OK) return rc;
         thres = (it == 0) ? 10.0 : 1.0;  // :1377-1381
-        rc = solve_enqueue(ctx, first_slot, count, 1, T_bl, &so, xs.data(), false);
+        const PoseBack back{packed, true, first_slot, count, stage_alloc(ctx, MML_SOLVE_RESULT * (size_t)count)};
+        rc = pose_solve_enqueue(ctx, dev, host, so, back);
         if (rc != MML_OK) return rc;
-        double* h_back = stage_alloc(ctx, 22 * (size_t)count);  // pinned: stats (16 per slot), then poses (6 per slot)
-        MML_HIP(hipMemcpyAsync(h_back, ctx->assoc_stats + 16 * (size_t)first_slot, sizeof(double) * 16 * count, hipMemcpyDeviceToHost,
-                               MML_STREAM(ctx)));
-        MML_HIP(hipMemcpyAsync(h_back + 16 * (size_t)count, ctx->d_x + 6 * (size_t)first_slot, sizeof(double) * 6 * count,
-                               hipMemcpyDeviceToHost, MML_STREAM(ctx)));
         MML_HIP(hipStreamSynchronize(MML_STREAM(ctx)));
-        for (int i = 0; i < count; ++i) finish_stats(h_back + 16 * (size_t)i, &st[i]);
-        memcpy(xs.data(), h_back + 16 * (size_t)count, sizeof(double) * 6 * count);
-        }
+        pose_back_finish(back, xs.data(), fn.data(), st.data());
         for (int i = 0; i < count; ++i) {
             if (done[i]) continue;
             if (st[i].is_degenerate) degen[i] = 1;
@@ -1624,23 +1645,13 @@ int mml_estimate(mml_ctx* ctx, int first_slot, int count, const double* exTlb, d
             if ((deltaR < 0.05 && deltaT < 0.05) || (it + 1) == max_outer) done[i] = 1;  // :1448
         }
     }
-    if (info && have_fn) {
+    if (info)
         for (int i = 0; i < count; ++i) {
             info[i].outer_iterations = outer[i];
             info[i].is_degenerate = degen[i];
-            info[i].n_corner_feat = last_fn[2 * i];
-            info[i].n_surf_feat = last_fn[2 * i + 1];
+            info[i].n_corner_feat = fn[i];
+            info[i].n_surf_feat = fn[count + i];
         }
-    } else if (info) {
-        std::vector<int> fn(2 * (size_t)ctx->B);
-        MML_HIP(hipMemcpy(fn.data(), ctx->ft_n, sizeof(int) * fn.size(), hipMemcpyDeviceToHost));
-        for (int i = 0; i < count; ++i) {
-            info[i].outer_iterations = outer[i];
-            info[i].is_degenerate = degen[i];
-            info[i].n_corner_feat = fn[first_slot + i];
-            info[i].n_surf_feat = fn[ctx->B + first_slot + i];
-        }
-    }
     return MML_OK;
 }
 
@@ -1664,43 +1675,32 @@ int mml_step(mml_ctx* ctx, int first_slot, int count, const double* dR, const do
     // schedule -- pieces of 512 .. 2048 scans, stream 0 extracting piece i + 1 while other streams run the back end of piece
     // i, 2 .. 5 streams, three stage-to-stream maps: 306 k .. 330 k scans/s against 355 k for two lanes (HISTORY.md).
     const int lanes = count >= 64 ? ctx->n_lanes : 1;
-    const int n_pieces = lanes;
-    const int chunk = (count + n_pieces - 1) / n_pieces;
-    std::vector<double> Twl(16 * (size_t)chunk);
+    const int chunk = (count + lanes - 1) / lanes;
+    // Every piece has its own parameter block (pose_upload) and its part of the call's read-back.  A handful of slots (the live
+    // path, `packed`) is one piece, and there every small transfer is a launch of its own in the dependency chain (a blit kernel
+    // of ~4 us plus the gap in front of it): the block is the only copy down and k_solve's result records are the only copy up.
+    const bool packed = mml_pose_packed(count, ctx->cus);
+    const PoseBlock call = PoseBlock::of(ctx->d_pose_in, first_slot, count);
+    struct Piece {
+        PoseBlock dev, host;
+    } pieces[mml_ctx::MAX_LANES];
+    int n_pieces = 0;
+    size_t need = (7 + MML_SOLVE_RESULT) * (size_t)count + 16 + 1024;  // h_x, the read-back; (the ring hands out multiples of 8)
+    for (; n_pieces < lanes; ++n_pieces) {
+        pieces[n_pieces].dev = call.piece(n_pieces, chunk);
+        if (pieces[n_pieces].dev.count <= 0) break;
+        need += pieces[n_pieces].dev.size() + 8;
+    }
     // (the staging ring: a wrap in the middle of the call would drain the streams; wrap now if this call does not fit)
-    {
-        const size_t need = (7 + 16 + 12 + 6 + 8) * (size_t)count + 64 * (size_t)n_pieces + 1024;
-        if (ctx->stage_cursor + need > ctx->h_stage_doubles && need <= ctx->h_stage_doubles) {
-            int rw = mml_sync_all(ctx);
-            if (rw != MML_OK) return rw;
-            ctx->stage_cursor = 0;
-        }
+    if (ctx->stage_cursor + need > ctx->h_stage_doubles && need <= ctx->h_stage_doubles) {
+        int rw = mml_sync_all(ctx);
+        if (rw != MML_OK) return rw;
+        ctx->stage_cursor = 0;
     }
-    double* h_x = stage_alloc(ctx, 7 * (size_t)count + 1);  // pinned read-back area: poses, then the two stack-size arrays
+    double* h_x = stage_alloc(ctx, 7 * (size_t)count + 1);  // poses, then the two stack-size arrays: what the read-back yields
     int* h_ftn = reinterpret_cast<int*>(h_x + 6 * (size_t)count);
+    const PoseBack back{packed, false, first_slot, count, stage_alloc(ctx, MML_SOLVE_RESULT * (size_t)count)};
     int rc = MML_OK;
-    // A handful of slots (the live path): every small transfer is a launch of its own in the dependency chain (a blit kernel of
-    // ~4 us plus the gap in front of it), and a one-scan step made eight of them.  All parameter blocks of the call -- sweep
-    // motions, association poses, start poses, T_bl -- go down in ONE copy into the call's slice of d_pose_in, and everything read
-    // back afterwards (poses, stack sizes) comes up in ONE record per slot that k_solve leaves (MML_SOLVE_RESULT doubles).
-    const bool packed = count <= kPackMaxSlots;
-    double *dp = nullptr, *h_res = nullptr;
-    if (packed) {
-        const size_t c = (size_t)count, n = 34 * c + 16;  // und [0, 12c) | T_wl [12c, 28c) | x [28c, 34c) | T_bl [34c, 34c + 16)
-        double* hp = stage_alloc(ctx, n);
-        dp = ctx->d_pose_in + 64 * (size_t)first_slot;
-        for (size_t i = 0; i < c; ++i) {
-            memcpy(hp + 12 * i, dR + 9 * i, sizeof(double) * 9);
-            memcpy(hp + 12 * i + 9, dt + 3 * i, sizeof(double) * 3);
-            double q[4];
-            so3_exp_h(x_inout + 6 * i + 3, q);
-            pose_to_Twl(q, x_inout + 6 * i, T_bl, hp + 12 * c + 16 * i);
-        }
-        memcpy(hp + 28 * c, x_inout, sizeof(double) * 6 * c);
-        memcpy(hp + 34 * c, T_bl, sizeof(double) * 16);
-        if (hipMemcpyAsync(dp, hp, sizeof(double) * n, hipMemcpyHostToDevice, MML_STREAM(ctx)) != hipSuccess) return MML_ERR_HIP;
-        h_res = stage_alloc(ctx, MML_SOLVE_RESULT * c);
-    }
     // Entry points outside mml_step enqueue on stream 0 (mml_scan_upload's copies, a staged mml_extract ...): the other streams
     // start behind whatever stream 0 holds at this point.  (Found by running 80 slots on the default two lanes straight
     // after their uploads: the last slot's copy was still in flight when lane 1 began to bucket it.)
@@ -1709,82 +1709,34 @@ int mml_step(mml_ctx* ctx, int first_slot, int count, const double* dR, const do
         for (int l = 1; l < mml_ctx::MAX_LANES; ++l)
             if (hipStreamWaitEvent(ctx->streams[l], ctx->lane_mark[0], 0) != hipSuccess) return MML_ERR_HIP;
     }
-    auto piece_span = [&](int p, int& f, int& c) {
-        f = first_slot + p * chunk;
-        c = std::min(chunk, first_slot + count - f);
-        return c > 0;
-    };
-    auto run_stage = [&](int stage, int f, int c) -> int {
-        const int off = f - first_slot;
+    auto run_stage = [&](int stage, Piece& p) -> int {
+        const int f = p.dev.first, c = p.dev.count;
+        const size_t off = (size_t)(f - first_slot);
         switch (stage) {
             case 0: return mml_launch_extract(ctx, f, c, false);
-            case 1:  // (the points the down-sampler reads; the rest of the cloud when somebody asks for it: mml_cloud_settle)
-                if (packed) return ctx->lazy_undistort ? mml_launch_undistort_listed(ctx, f, c, dp) : mml_launch_undistort(ctx, f, c, dp);
-                return undistort_enqueue(ctx, f, c, dR + 9 * (size_t)off, dt + 3 * (size_t)off, ctx->lazy_undistort);
-            case 2: return mml_launch_downsample(ctx, f, c);
-            case 3:
-                if (packed) return mml_launch_associate(ctx, f, c, dp + 12 * (size_t)count, thres_dist, false);
-                for (int i = 0; i < c; ++i) {
-                    double q[4];
-                    so3_exp_h(x_inout + 6 * (size_t)(off + i) + 3, q);
-                    pose_to_Twl(q, x_inout + 6 * (size_t)(off + i), T_bl, &Twl[16 * (size_t)i]);
-                }
-                return associate_enqueue(ctx, f, c, Twl.data(), thres_dist, false);  // (nobody reads the statistics of a step)
-            default: {
-                if (packed) {
-                    int r = mml_launch_solve(ctx, f, c, 1, dp + 34 * (size_t)count, so, false, dp + 28 * (size_t)count,
-                                             ctx->d_result + MML_SOLVE_RESULT * (size_t)f);
-                    if (r != MML_OK) return r;
-                    if (hipMemcpyAsync(h_res, ctx->d_result + MML_SOLVE_RESULT * (size_t)f, sizeof(double) * MML_SOLVE_RESULT * c,
-                                       hipMemcpyDeviceToHost, MML_STREAM(ctx)) != hipSuccess)
-                        return MML_ERR_HIP;
-                    return MML_OK;
-                }
-                int r = solve_enqueue(ctx, f, c, 1, T_bl, &so, x_inout + 6 * (size_t)off, false);
+            case 1: {  // (the points the down-sampler reads; the rest of the cloud when somebody asks for it: mml_cloud_settle)
+                int r = pose_upload(ctx, p.dev, dR + 9 * off, dt + 3 * off, x_inout + 6 * off, nullptr, T_bl, &p.host);
                 if (r != MML_OK) return r;
-                hipError_t e = hipMemcpyAsync(h_x + 6 * (size_t)off, ctx->d_x + 6 * (size_t)f, sizeof(double) * 6 * c, hipMemcpyDeviceToHost,
-                                              MML_STREAM(ctx));
-                if (e != hipSuccess) {
-                    ctx->err = std::string("mml_step read-back: ") + hipGetErrorString(e);
-                    return MML_ERR_HIP;
-                }
-                return MML_OK;
+                return ctx->lazy_undistort ? mml_launch_undistort_listed(ctx, f, c, p.dev.und()) : mml_launch_undistort(ctx, f, c, p.dev.und());
             }
+            case 2: return mml_launch_downsample(ctx, f, c);
+            case 3: return mml_launch_associate(ctx, f, c, p.dev.T_wl(), thres_dist, false);  // (nobody reads the statistics of a step)
+            default: return pose_solve_enqueue(ctx, p.dev, p.host, so, back);
         }
     };
-    {
-        // The stages are enqueued stage by stage across the lanes (each lane's stream keeps its own order): every lane has
-        // its first kernels in its queue within a few tens of microseconds, instead of lane 3 waiting for the host to finish
-        // enqueueing the whole chains of lanes 0..2.
-        for (int stage = 0; stage < 5 && rc == MML_OK; ++stage) {
-            for (int l = 0; l < n_pieces && rc == MML_OK; ++l) {
-                int f, c;
-                if (!piece_span(l, f, c)) break;
-                ctx->cur = l;
-                rc = run_stage(stage, f, c);
-            }
+    // The stages are enqueued stage by stage across the lanes (each lane's stream keeps its own order): every lane has its first
+    // kernels in its queue within a few tens of microseconds, instead of lane 3 waiting for the host to finish enqueueing the whole
+    // chains of lanes 0..2.
+    for (int stage = 0; stage < 5 && rc == MML_OK; ++stage)
+        for (int l = 0; l < n_pieces && rc == MML_OK; ++l) {
+            ctx->cur = l;
+            rc = run_stage(stage, pieces[l]);
         }
-    }
-    // the per-slot stack sizes ride back with the poses: a negative count is the down-sampler's overflow mark
-    if (rc == MML_OK) {
-        ctx->cur = 0;
-        for (int l = 1; l < mml_ctx::MAX_LANES && rc == MML_OK; ++l)
-            if (hipStreamSynchronize(ctx->streams[l]) != hipSuccess) rc = MML_ERR_HIP;
-        for (int kind = 0; kind < 2 && rc == MML_OK && !packed; ++kind)
-            if (hipMemcpyAsync(h_ftn + (size_t)kind * count, ctx->ft_n + kind * ctx->B + first_slot, sizeof(int) * count,
-                               hipMemcpyDeviceToHost, MML_STREAM(ctx)) != hipSuccess)
-                rc = MML_ERR_HIP;
-    }
     ctx->cur = 0;
     int rs = mml_sync_all(ctx);
     if (rc != MML_OK) return rc;
     if (rs != MML_OK) return rs;
-    if (packed)  // the result records: pose (6), the two stack sizes, (association statistics: nobody reads them here)
-        for (int i = 0; i < count; ++i) {
-            memcpy(h_x + 6 * (size_t)i, h_res + MML_SOLVE_RESULT * (size_t)i, sizeof(double) * 6);
-            h_ftn[i] = (int)h_res[MML_SOLVE_RESULT * (size_t)i + 6];
-            h_ftn[count + i] = (int)h_res[MML_SOLVE_RESULT * (size_t)i + 7];
-        }
+    pose_back_finish(back, h_x, h_ftn, nullptr);
     // A negative stack size is the down-sampler's overflow mark.  Slots whose labelled cloud is merely too dense for the
     // LDS sort are redone through the global-sort filter and re-registered one by one (rare: > 8192 corner- or
     // surf-labelled points in one scan); a slot that exceeds max_features stays failed.  Either way every other slot of

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "mml_mem.h"
+#include "pose_block.h"
 #include "mmloam_hip.h"
 
 #define MML_WAVE 64
@@ -271,7 +272,7 @@ struct mml_ctx {
 
     // solver state
     double* d_x = nullptr;        // B * 6
-    double* d_pose_in = nullptr;  // B * 32 generic double params (T_wl, dR/dt ...)
+    double* d_pose_in = nullptr;  // B * kPoseSlotDoubles: the calls' parameter blocks, a call owning its slots' range (pose calls: PoseBlock)
     double* d_result = nullptr;      // B * MML_SOLVE_RESULT: k_solve's result records (pose, stack sizes, association statistics) for small calls
     double* d_summ = nullptr;     // B * 8
     double* d_trace = nullptr;    // B * 6 * MAX_ITERS
@@ -396,6 +397,7 @@ int mml_launch_knn5(mml_ctx* ctx, int kind, const float* d_q, int nq, float max_
 int mml_launch_associate(mml_ctx* ctx, int first, int count, const double* d_Twl, double thres_dist, bool with_stats = true);
 int mml_ensure_assoc_stats(mml_ctx* ctx, int first, int count);
 #define MML_SOLVE_RESULT 24  // doubles per problem of k_solve's result record: x (6), stack sizes (2), association statistics (16)
+// d_x_in / d_result (a PoseBlock's start poses, the result records): packed pose calls only, mml_pose_packed(count, ctx->cus)
 int mml_launch_solve(mml_ctx* ctx, int first, int count, int window, const double* d_Tbl, mml_solve_opts opts,
                      bool want_trace, const double* d_x_in = nullptr, double* d_result = nullptr);
 int mml_window_solve_continue(mml_ctx* ctx, int first, int count, int window, const double* d_Tbl, mml_solve_opts opts);

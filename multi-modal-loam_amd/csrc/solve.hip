@@ -1670,7 +1670,7 @@ int mml_launch_solve(mml_ctx* ctx, int first, int count, int window, const doubl
     MML_REQUIRE((!d_x_in && !d_result) || window == 1, MML_ERR_INVALID, "packed start poses / result records: one-frame problems only");
     MmlStageScope t(ctx, "solve");
     const bool small = count / window <= ctx->cus;  // at most one problem per CU
-    MML_REQUIRE((!d_x_in && !d_result) || small, MML_ERR_INVALID, "packed start poses / result records: small launches only");
+    MML_REQUIRE((!d_x_in && !d_result) || mml_pose_packed(count, ctx->cus), MML_ERR_INVALID, "packed start poses / result records: packed pose calls only");
     // one-frame problems with one-row plane factors (the live path): the 512-thread form (ctx->solve_wide false, $MML_SOLVE_WIDE=0:
     // k_solve<true>, the same values bit for bit)
     if (small && ctx->solve_wide && window == 1 && opts.plan_weight_tan == 0.0)
