@@ -370,6 +370,53 @@ int mml_gicp_align_batch(mml_ctx* ctx, int n, const float* src_xyz, const int* s
                          float* T_inout /* n x 16 */, int* converged /* n */, mml_gicp_info* info /* n, may be NULL */);
 int mml_gicp_refresh_batch(mml_ctx* ctx, int first_slot, int count, float* extrinsics /* count x 16, in/out */, int chain,
                            int apply, int* refreshed /* count, may be NULL */, mml_gicp_info* info /* count, may be NULL */);
+/* mml_gicp_align with the three settings the reference's call sites differ in as arguments.  The entry points above are the
+ * call with {10, 1e-6, 0}, through the same kernels.  The gate is PCL 1.8.1's computeTransformation: a source point enters a
+ * round's correspondence list iff its 1-NN squared distance (the float the search produces) is < the gate squared; a rejected
+ * point contributes no term to the objective or its gradient and does not count in their 1/m, and fewer than 4 kept points end
+ * the alignment unconverged with T_inout untouched, as too few points do.  The (correspondence, BFGS) rounds are enqueued in
+ * chunks of at most ten with one read-back of the state per chunk, until the alignment has converged or failed: host
+ * synchronisations = ceil(outer iterations run / 10), one for max_iterations <= 10.  MML_ERR_INVALID, before any device work,
+ * for NULL opts, max_iterations < 1, a transformation_epsilon that is not finite and positive, a NaN gate. */
+typedef struct {
+    int    max_iterations;               /* setMaximumIterations */
+    double transformation_epsilon;       /* setTransformationEpsilon */
+    double max_correspondence_distance;  /* metres; <= 0: no gate (what mml_gicp_align does) */
+} mml_gicp_opts;
+int mml_gicp_align_opts(mml_ctx* ctx, const float* src_xyz, int n_src, const float* tgt_xyz, int n_tgt, const mml_gicp_opts* opts,
+                        float* T_inout, int* converged, mml_gicp_info* info /* may be NULL */);
+
+/* ---- the aligner node's start-up calibration (unionLidarsAligner.cpp:221-270, lidars_extrinsic_cali.h:493-618) -----------
+ * mml_cloud_crop_voxel: removeFarPointCloud (lidars_extrinsic_cali.h:398-422) + pcl::VoxelGrid<PointXYZI> of a free cloud of
+ * n x (x, y, z, intensity) floats, on the device.  A point is dropped iff (x*x + y*y) + z*z > far_th*far_th in float; order is
+ * kept.  The filter is PCL 1.8.1's applyFilter with the conventions of mml_downsample: inverse leaf in float, floor of the
+ * bounding box, voxel index i + j dx + k dx dy, output ascending by index, a voxel's points summed in input order in float and
+ * divided by their number -- all four fields.  When the box holds more than INT32_MAX voxels (dx dy dz as int64, each
+ * (int64)((max - min) * inverse_leaf) + 1) PCL refuses to filter: the output is then the cropped cloud, in input order, and
+ * *unfiltered = 1.  out_xyzi == NULL: sizing call, *n_out and *unfiltered only.  MML_ERR_CAPACITY, before any record is written,
+ * when capacity < *n_out (which is set); MML_ERR_INVALID for n < 0, a NULL cloud with n > 0, NULL n_out, far_th or leaf that
+ * is not finite and positive.  One host synchronisation: the read-back of count and records in one copy.  The context keeps
+ * grow-only scratch for the largest cloud it has seen (64 bytes per point on the device and the sort's temporary storage, 32
+ * per point pinned), released by mml_destroy; MML_ERR_HIP, before any launch, when it cannot be grown. */
+int mml_cloud_crop_voxel(mml_ctx* ctx, const float* xyzi, int n, float far_th, float leaf, float* out_xyzi, int capacity,
+                         int* n_out, int* unfiltered /* may be NULL */);
+/* calibratePCLICP and its call site: both clouds (source: the integrated Livox cloud _hori_igcloud, intensity = reflectivity;
+ * target: _velo_new_cloud) through mml_cloud_crop_voxel's kernels with (50, 0.05), the filtered clouds staying on the device,
+ * then mml_gicp_align_opts' with {500, 1e-3, 2.0} from the identity guess.  (setRANSACIterations(12) has no effect on PCL
+ * 1.8.1's GICP: nothing is implemented for it.)  hori_tf = getFinalTransformation(); velo_hori_tf is what the caller makes
+ * of it (:251-253): rows 0-2 are R^T and -t, row 3 is hori_tf's row 3 -- NOT the rigid inverse (that would be -R^T t); the
+ * reference's matrix is reproduced as it is.  Both matrices are written only when *converged; fewer than 20 points left in a
+ * cloud, or fewer than 4 correspondences inside the gate, do not converge.  Every result equals the three calls made one after
+ * the other, to the byte.  Host synchronisations: 1 (the two filtered sizes) + ceil(outer iterations run / 10).
+ * MML_ERR_INVALID for a negative count, a NULL cloud with points, NULL hori_tf, velo_hori_tf or converged. */
+typedef struct {
+    int n_hori_in, n_velo_in;              /* points handed in */
+    int n_hori_ds, n_velo_ds;              /* after crop + voxel filter: what the alignment sees */
+    int hori_unfiltered, velo_unfiltered;  /* PCL's overflow refusal hit: the cloud was cropped only */
+    mml_gicp_info gicp;
+} mml_calib_info;
+int mml_aligner_calibrate(mml_ctx* ctx, const float* hori_xyzi, int n_hori, const float* velo_xyzi, int n_velo,
+                          float* hori_tf /* 16 */, float* velo_hori_tf /* 16 */, int* converged, mml_calib_info* info /* may be NULL */);
 
 /* ---- a1..a8: feature extraction -----------------------------------------------------------------
  * feature_extraction::unionCloudHandler minus the PCL GICP refresh (unionFeatureExtract.cpp:266-321):

@@ -144,6 +144,16 @@ class GicpInfo(C.Structure):
                 ("n_source", C.c_int), ("n_target", C.c_int)]
 
 
+class GicpOpts(C.Structure):
+    """mml_gicp_opts: setMaximumIterations, setTransformationEpsilon, setMaxCorrespondenceDistance (<= 0: no gate)."""
+    _fields_ = [("max_iterations", C.c_int), ("transformation_epsilon", C.c_double), ("max_correspondence_distance", C.c_double)]
+
+
+class CalibInfo(C.Structure):
+    _fields_ = [("n_hori_in", C.c_int), ("n_velo_in", C.c_int), ("n_hori_ds", C.c_int), ("n_velo_ds", C.c_int),
+                ("hori_unfiltered", C.c_int), ("velo_unfiltered", C.c_int), ("gicp", GicpInfo)]
+
+
 class Profile(C.Structure):
     _fields_ = [("n_stages", C.c_int), ("name", C.c_char_p * MAX_STAGES), ("total_ms", C.c_double * MAX_STAGES),
                 ("launches", C.c_long * MAX_STAGES)]
@@ -723,6 +733,49 @@ class Context:
         self._ck(lib().mml_gicp_align(self._h, _p(src) if len(src) else None, C.c_int(len(src)), _p(tgt) if len(tgt) else None,
                                       C.c_int(len(tgt)), _p(T), C.byref(conv), C.byref(info)))
         return bool(conv.value), T, info
+
+    def gicp_align_opts(self, src, tgt, max_iterations=10, transformation_epsilon=1e-6, max_correspondence_distance=0.0, T0=None):
+        """mml_gicp_align_opts: gicp_align with PCL's three settings as arguments (the defaults are gicp_align's); returns
+        (converged, T 4x4 float32, GicpInfo)."""
+        src = _f32(src).reshape(-1, 3)
+        tgt = _f32(tgt).reshape(-1, 3)
+        T = np.ascontiguousarray(np.eye(4, dtype=np.float32) if T0 is None else np.asarray(T0, np.float32).reshape(4, 4).copy())
+        opts = GicpOpts(int(max_iterations), float(transformation_epsilon), float(max_correspondence_distance))
+        conv, info = C.c_int(0), GicpInfo()
+        self._ck(lib().mml_gicp_align_opts(self._h, _p(src) if len(src) else None, C.c_int(len(src)), _p(tgt) if len(tgt) else None,
+                                           C.c_int(len(tgt)), C.byref(opts), _p(T), C.byref(conv), C.byref(info)))
+        return bool(conv.value), T, info
+
+    def cloud_crop_voxel(self, xyzi, far_th, leaf, out=None):
+        """mml_cloud_crop_voxel: removeFarPointCloud(far_th) + pcl::VoxelGrid(leaf) of an n x 4 (x, y, z, intensity) cloud on the
+        device; returns (m x 4 float32, unfiltered).  out=None: a sizing call first, then room for exactly the result; else the
+        records go into `out` (k x 4 float32, C order; MmlError MML_ERR_CAPACITY, nothing written, when k is too small)."""
+        xyzi = _f32(xyzi).reshape(-1, 4)
+        f = lib().mml_cloud_crop_voxel
+        n, unf = C.c_int(0), C.c_int(0)
+        a = (self._h, _p(xyzi) if len(xyzi) else None, C.c_int(len(xyzi)), C.c_float(far_th), C.c_float(leaf))
+        if out is None:
+            self._ck(f(*a, None, C.c_int(0), C.byref(n), C.byref(unf)))
+            out = np.zeros((max(n.value, 1), 4), np.float32)
+            cap = n.value
+        else:
+            assert out.dtype == np.float32 and out.flags.c_contiguous and out.ndim == 2 and out.shape[1] == 4
+            cap = len(out)
+        self._ck(f(*a, _p(out), C.c_int(cap), C.byref(n), C.byref(unf)))
+        return out[:n.value], bool(unf.value)
+
+    def aligner_calibrate(self, hori_xyzi, velo_xyzi, hori_tf=None, velo_hori_tf=None):
+        """mml_aligner_calibrate: calibratePCLICP and its call site (unionLidarsAligner.cpp:221-270) on the integrated Livox cloud
+        and the newest Velodyne cloud, both n x 4; returns (converged, hori_tf, velo_hori_tf, CalibInfo).  The two matrices
+        (identity unless given) come back untouched when the alignment does not converge."""
+        h = _f32(hori_xyzi).reshape(-1, 4)
+        v = _f32(velo_xyzi).reshape(-1, 4)
+        mats = [np.ascontiguousarray(np.eye(4, dtype=np.float32) if m is None else np.asarray(m, np.float32).reshape(4, 4).copy())
+                for m in (hori_tf, velo_hori_tf)]
+        conv, info = C.c_int(0), CalibInfo()
+        self._ck(lib().mml_aligner_calibrate(self._h, _p(h) if len(h) else None, C.c_int(len(h)), _p(v) if len(v) else None,
+                                             C.c_int(len(v)), _p(mats[0]), _p(mats[1]), C.byref(conv), C.byref(info)))
+        return bool(conv.value), mats[0], mats[1], info
 
     def gicp_refresh(self, slot, extrinsic, apply=True):
         """unionCloudHandler's extrinsic refresh (:302-318) on a slot extracted without an extrinsic."""

@@ -22,8 +22,16 @@
 //                Every thread runs the (scalar) BFGS / line-search control flow on identical values; an objective
 //                evaluation is a strided pass over the correspondences + a block reduction of 13 doubles, broadcast
 //                back to all threads.  The kernel then forms the new 4 x 4 float transformation, the convergence measure
-//                of the outer loop and the iteration count, so the host enqueues 10 (corr, bfgs) rounds blindly: a
+//                of the outer loop and the iteration count, so the host enqueues up to 10 (corr, bfgs) rounds blindly: a
 //                converged or failed state turns the remaining rounds into no-ops.
+//
+// The three settings the reference's two call sites differ in travel with the call (GicpRun): the feature node's
+// {10 iterations, transformation epsilon 1e-6, no correspondence gate} behind the entry points above, the caller's own behind
+// mml_gicp_align_opts (the aligner's start-up calibration, calibrate.hip, uses {500, 1e-3, 2 m}).  The gate is PCL 1.8.1's
+// computeTransformation: a source point whose 1-NN squared distance is not below the gate squared gets no correspondence
+// (corr = -1); the objective skips it -- no term, and it does not count in the 1/m -- while every other point keeps its place i
+// in the passes.  More than 10 iterations run as chunks of 10 rounds with one read-back of the states per chunk, until every
+// problem has converged or failed: ceil(iterations run / 10) host synchronisations for the alignment, one with the feature node's settings.
 #include <math.h>
 #include <string.h>
 
@@ -36,7 +44,16 @@ namespace {
 constexpr int GK = 20;            // k_correspondences_
 constexpr int TILE = 1024;        // points per LDS tile of the brute-force searches
 constexpr int BF_THREADS = 256;
-constexpr double GICP_EPS = 1e-3, ROT_EPS = 2e-3, TRANS_EPS = 1e-6;
+constexpr double GICP_EPS = 1e-3, ROT_EPS = 2e-3;
+constexpr int ROUNDS_PER_CHUNK = 10;  // (corr, bfgs) rounds enqueued between two read-backs of the states
+
+// the settings of a call, as the kernels take them
+struct GicpRun {
+    int max_it;            // setMaximumIterations
+    double inv_trans_eps;  // 1 / setTransformationEpsilon
+    double gate2;          // setMaxCorrespondenceDistance squared; <= 0: no gate
+};
+constexpr GicpRun FEATURE_NODE_RUN = {10, 1.0 / 1e-6, 0.0};  // icp_ext_matching
 
 struct GicpState {  // device-resident state of the outer loop, one per problem
     float T[16];    // transformation_ (row-major)
@@ -146,7 +163,7 @@ __device__ __forceinline__ void tf_pt(const float* T, float x, float y, float z,
 // grid (blocks of the call's largest source cloud, problems)
 __global__ __launch_bounds__(256) void k_gicp_corr(const GicpProb* __restrict__ tab, const float4* __restrict__ pts_all,
                                                    const double* __restrict__ cov_all, const GicpState* st_all, int* __restrict__ corr_all,
-                                                   double* __restrict__ maha_all) {
+                                                   double* __restrict__ maha_all, double gate2) {
     __shared__ float4 tile[TILE];
     const GicpProb P = tab[blockIdx.y];
     const int ns = P.n_src, nt = P.n_tgt;
@@ -182,6 +199,11 @@ __global__ __launch_bounds__(256) void k_gicp_corr(const GicpProb* __restrict__ 
     }
     if (i >= ns) return;
     const int j = (int)(unsigned)best;
+    // if (nn_dists[0] < dist_threshold) (gicp.hpp computeTransformation): the float the search produced against the double gate
+    if (gate2 > 0.0 && !((double)__uint_as_float((unsigned)(best >> 32)) < gate2)) {
+        corr[i] = -1;
+        return;
+    }
     corr[i] = j;
     double R[9];
 #pragma unroll
@@ -245,9 +267,11 @@ struct EvalCtx {
     const float4* tgt;
     const int* corr;
     const double* maha;
-    int m;
+    int n;            // source points = positions of the strided pass
+    int m;            // correspondences: n without a gate, else the points with corr >= 0
     double* s_terms;  // LDS: 13 rows x EV_ROW terms of the current chunk
     double* s_tot;    // LDS: the 13 totals
+    int* s_keep;      // LDS: EV_CH flags "has a correspondence" of the current chunk; null without a gate
 };
 
 // OptimizationFunctorWithIndices::operator() / fdf: every thread returns the same f and (optionally) gradient.
@@ -256,16 +280,22 @@ struct EvalCtx {
 // that f and the gradient equal the sequential loop's bit for bit -- the line search compares objective values that differ
 // in their last bits near the flat minimum of a cross-sensor alignment, and a strided pass with a tree reduction decides
 // some of those comparisons the other way (round 2: matrices equal to 5e-3 only).
+// With a gate, a point without a correspondence forms no term and the summing lanes step over its place.
 __device__ double gicp_eval(const EvalCtx& E, const double* x, double* g) {
     float T[16];
     apply_state(x, T);
     const int nsum = g ? 13 : 1;
     double run = 0;
-    for (int c0 = 0; c0 < E.m; c0 += EV_CH) {
-        const int cnt = min(EV_CH, E.m - c0);
+    for (int c0 = 0; c0 < E.n; c0 += EV_CH) {
+        const int cnt = min(EV_CH, E.n - c0);
         for (int j = threadIdx.x; j < cnt; j += BF_THREADS) {
             const int i = c0 + j;
-            const float4 ps = E.src[i], pt = E.tgt[E.corr[i]];
+            const int ci = E.corr[i];
+            if (E.s_keep) {
+                E.s_keep[j] = ci >= 0;
+                if (ci < 0) continue;
+            }
+            const float4 ps = E.src[i], pt = E.tgt[ci];
             float pp[3];
             tf_pt(T, ps.x, ps.y, ps.z, pp);
             const double res[3] = {(double)(pp[0] - pt.x), (double)(pp[1] - pt.y), (double)(pp[2] - pt.z)};
@@ -287,7 +317,12 @@ __device__ double gicp_eval(const EvalCtx& E, const double* x, double* g) {
         __syncthreads();
         if ((int)threadIdx.x < nsum) {
             const double* row = E.s_terms + threadIdx.x * EV_ROW;
-            for (int j = 0; j < cnt; ++j) run += row[j];
+            if (E.s_keep) {
+                for (int j = 0; j < cnt; ++j)
+                    if (E.s_keep[j]) run += row[j];
+            } else {
+                for (int j = 0; j < cnt; ++j) run += row[j];
+            }
         }
         __syncthreads();
     }
@@ -609,28 +644,41 @@ __device__ int bfgs_iterate(Bfgs& B, const EvalCtx& E) {
     return 0;
 }
 
-// grid (problems): one workgroup per problem.  s_terms + s_tot are 13 x 513 + 13 doubles = 53,456 bytes of LDS (53,464 as
-// allocated), so a CU's 160 KiB (163,840 bytes) hold THREE such workgroups.  The scalar BFGS state costs 199 VGPRs per lane, which
-// allows two waves per SIMD, and a workgroup puts one wave on each of the four SIMDs: registers, not LDS, bound a CU to TWO
-// workgroups -- 512 problems resident on the 256 CUs at once, the rest queue behind them.
+// grid (problems): one workgroup per problem.  s_terms + s_tot are 13 x 513 + 13 doubles = 53,456 bytes of LDS, the gate's flags
+// 2,052 more: a CU's 160 KiB (163,840 bytes) hold two such workgroups.  The scalar BFGS state costs about 200 VGPRs per lane, which
+// allows two waves per SIMD, and a workgroup puts one wave on each of the four SIMDs: registers bound a CU to TWO workgroups as
+// well -- 512 problems resident on the 256 CUs at once, the rest queue behind them.
 __global__ __launch_bounds__(BF_THREADS) void k_gicp_bfgs(const GicpProb* __restrict__ tab, const float4* pts_all, const int* corr_all,
-                                                         const double* maha_all, GicpState* st_all) {
+                                                         const double* maha_all, GicpState* st_all, GicpRun run) {
     __shared__ double s_terms[13 * EV_ROW];
     __shared__ double s_tot[13];
+    __shared__ int s_keep[EV_CH];
+    __shared__ int s_m;
     const GicpProb P = tab[blockIdx.x];
-    const int m = P.n_src;
-    if (m == 0) return;
+    const int n = P.n_src;
+    if (n == 0) return;
     GicpState* st = st_all + blockIdx.x;
     if (st->converged || st->failed) return;
     const float4* src = pts_all + P.src;
     const float4* tgt = pts_all + P.tgt;
     const int* corr = corr_all + P.moff;
     const double* maha = maha_all + 9 * (size_t)P.moff;
+    const bool gated = run.gate2 > 0.0;  // (workgroup-uniform)
+    int m = n;
+    if (gated) {  // the round's correspondence list: the points k_gicp_corr kept
+        if (threadIdx.x == 0) s_m = 0;
+        __syncthreads();
+        int mine = 0;
+        for (int i = threadIdx.x; i < n; i += BF_THREADS) mine += corr[i] >= 0;
+        if (mine) atomicAdd(&s_m, mine);
+        __syncthreads();
+        m = s_m;
+    }
     if (m < 4) {  // NotEnoughPointsException: the outer loop ends unconverged
         if (threadIdx.x == 0) st->failed = 1;
         return;
     }
-    EvalCtx E{src, tgt, corr, maha, m, s_terms, s_tot};
+    EvalCtx E{src, tgt, corr, maha, n, m, s_terms, s_tot, gated ? s_keep : nullptr};
     float T[16];
 #pragma unroll
     for (int c = 0; c < 16; ++c) T[c] = st->T[c];
@@ -669,7 +717,7 @@ __global__ __launch_bounds__(BF_THREADS) void k_gicp_bfgs(const GicpProb* __rest
     for (int k = 0; k < 4; ++k)
 #pragma unroll
         for (int l = 0; l < 4; ++l) {
-            const double ratio = (k < 3 && l < 3) ? 1.0 / ROT_EPS : 1.0 / TRANS_EPS;
+            const double ratio = (k < 3 && l < 3) ? 1.0 / ROT_EPS : run.inv_trans_eps;
             const double cd = ratio * fabs((double)T[4 * k + l] - (double)Tn[4 * k + l]);
             delta = cd > delta ? cd : delta;
         }
@@ -681,7 +729,7 @@ __global__ __launch_bounds__(BF_THREADS) void k_gicp_bfgs(const GicpProb* __rest
         st->evals += B.evals;
         st->fobj = B.f;
         st->delta = delta;
-        if (st->nr >= 10 || delta < 1) st->converged = 1;
+        if (st->nr >= run.max_it || delta < 1) st->converged = 1;
     }
 }
 
@@ -847,22 +895,30 @@ void place_problem(GicpProb& P, int ns, int nt, size_t& n_pts, size_t& n_srcs) {
     n_srcs += ns;
 }
 
-// The launch sequence of a call: the n alignments of d_tab on the clouds in pts, states read back into h_st (one host
-// synchronisation).  max_src / max_tgt: the largest clouds among the problems that align.
-int gicp_core(mml_ctx* ctx, int n, int max_src, int max_tgt, const GicpProb* d_tab, const float4* pts, double* cov, double* maha, int* corr,
-              GicpState* d_st, GicpState* h_st) {
+// The launch sequence of a call: the n alignments of d_tab on the clouds in pts, states read back into h_st: one host
+// synchronisation per chunk of ROUNDS_PER_CHUNK rounds, so one up to 10 iterations.  max_src / max_tgt: the largest clouds among
+// the problems that align.
+int gicp_core(mml_ctx* ctx, const GicpRun& run, int n, int max_src, int max_tgt, const GicpProb* d_tab, const float4* pts, double* cov,
+              double* maha, int* corr, GicpState* d_st, GicpState* h_st) {
     hipStream_t s = MML_STREAM(ctx);
     MmlStageScope t(ctx, "gicp");
     const int max_c = max_src > max_tgt ? max_src : max_tgt;
     hipLaunchKernelGGL(k_gicp_init, dim3(n), dim3(64), 0, s, d_st);
     hipLaunchKernelGGL(k_gicp_cov, dim3((max_c + 255) / 256, n, 2), dim3(256), 0, s, d_tab, pts, cov);
-    for (int it = 0; it < 10; ++it) {  // setMaximumIterations(10); finished states skip their rounds
-        hipLaunchKernelGGL(k_gicp_corr, dim3((max_src + 255) / 256, n), dim3(256), 0, s, d_tab, pts, cov, d_st, corr, maha);
-        hipLaunchKernelGGL(k_gicp_bfgs, dim3(n), dim3(BF_THREADS), 0, s, d_tab, pts, corr, maha, d_st);
+    for (int done = 0; done < run.max_it;) {  // setMaximumIterations; finished states skip their rounds
+        const int rounds = run.max_it - done < ROUNDS_PER_CHUNK ? run.max_it - done : ROUNDS_PER_CHUNK;
+        for (int it = 0; it < rounds; ++it) {
+            hipLaunchKernelGGL(k_gicp_corr, dim3((max_src + 255) / 256, n), dim3(256), 0, s, d_tab, pts, cov, d_st, corr, maha, run.gate2);
+            hipLaunchKernelGGL(k_gicp_bfgs, dim3(n), dim3(BF_THREADS), 0, s, d_tab, pts, corr, maha, d_st, run);
+        }
+        MML_HIP(hipGetLastError());
+        MML_HIP(hipMemcpyAsync(h_st, d_st, sizeof(GicpState) * (size_t)n, hipMemcpyDeviceToHost, s));
+        MML_HIP(hipStreamSynchronize(s));
+        done += rounds;
+        bool busy = false;  // (the state of a problem that does not align -- n_src = 0 -- is never advanced: nr stays 0)
+        for (int i = 0; i < n && !busy; ++i) busy = !(h_st[i].converged || h_st[i].failed) && h_st[i].nr == done;
+        if (!busy) break;
     }
-    MML_HIP(hipGetLastError());
-    MML_HIP(hipMemcpyAsync(h_st, d_st, sizeof(GicpState) * (size_t)n, hipMemcpyDeviceToHost, s));
-    MML_HIP(hipStreamSynchronize(s));
     return MML_OK;
 }
 
@@ -884,7 +940,7 @@ void gicp_result(const GicpProb& P, const GicpState& h, float* T, int* converged
 
 // The n alignments of mml_gicp_align_batch; mml_gicp_align is its n = 1 case.  `who`: the entry point the caller used, which
 // is the name a refusal carries.
-int gicp_align_n(mml_ctx* ctx, const char* who, int n, const float* src_xyz, const int* src_offsets, const float* tgt_xyz,
+int gicp_align_n(mml_ctx* ctx, const char* who, const GicpRun& run, int n, const float* src_xyz, const int* src_offsets, const float* tgt_xyz,
                  const int* tgt_offsets, float* T_inout, int* converged, mml_gicp_info* info) {
     if (n < 1 || n > MML_GICP_BATCH_MAX) return mml_refuse(ctx, MML_ERR_INVALID, "%s: n = %d is outside 1 .. %d", who, n, MML_GICP_BATCH_MAX);
     if (!(src_offsets && tgt_offsets && T_inout && converged)) return mml_refuse(ctx, MML_ERR_INVALID, "%s: a null argument", who);
@@ -925,8 +981,8 @@ int gicp_align_n(mml_ctx* ctx, const char* who, int n, const float* src_xyz, con
         MML_HIP(hipMemcpyAsync(io.tab.in(g), io.tab.in(h), io.tab.bytes(), hipMemcpyHostToDevice, s));
         MML_HIP(hipMemcpyAsync(io.pts.in(g), io.pts.in(h), io.pts.bytes(), hipMemcpyHostToDevice, s));
         h_st = io.st.in(h);
-        rc = gicp_core(ctx, n, max_src, max_tgt, io.tab.in(g), io.pts.in(g), big.cov.in(d->big.d), big.maha.in(d->big.d), big.corr.in(d->big.d),
-                       io.st.in(g), h_st);
+        rc = gicp_core(ctx, run, n, max_src, max_tgt, io.tab.in(g), io.pts.in(g), big.cov.in(d->big.d), big.maha.in(d->big.d),
+                       big.corr.in(d->big.d), io.st.in(g), h_st);
         if (rc != MML_OK) return rc;
     }
     const GicpState none = {};
@@ -939,7 +995,7 @@ int gicp_align_n(mml_ctx* ctx, const char* who, int n, const float* src_xyz, con
 extern "C" int mml_gicp_align_batch(mml_ctx* ctx, int n, const float* src_xyz, const int* src_offsets, const float* tgt_xyz,
                                     const int* tgt_offsets, float* T_inout, int* converged, mml_gicp_info* info) {
     if (!ctx) return MML_ERR_INVALID;
-    return gicp_align_n(ctx, "mml_gicp_align_batch", n, src_xyz, src_offsets, tgt_xyz, tgt_offsets, T_inout, converged, info);
+    return gicp_align_n(ctx, "mml_gicp_align_batch", FEATURE_NODE_RUN, n, src_xyz, src_offsets, tgt_xyz, tgt_offsets, T_inout, converged, info);
 }
 
 extern "C" int mml_gicp_align(mml_ctx* ctx, const float* src_xyz, int n_src, const float* tgt_xyz, int n_tgt, float* T_inout, int* converged,
@@ -948,7 +1004,69 @@ extern "C" int mml_gicp_align(mml_ctx* ctx, const float* src_xyz, int n_src, con
     MML_REQUIRE(n_src >= 0 && n_tgt >= 0 && (n_src == 0 || src_xyz) && (n_tgt == 0 || tgt_xyz) && T_inout && converged, MML_ERR_INVALID,
                 "bad arguments");
     const int so[2] = {0, n_src}, to[2] = {0, n_tgt};
-    return gicp_align_n(ctx, "mml_gicp_align", 1, src_xyz, so, tgt_xyz, to, T_inout, converged, info);
+    return gicp_align_n(ctx, "mml_gicp_align", FEATURE_NODE_RUN, 1, src_xyz, so, tgt_xyz, to, T_inout, converged, info);
+}
+
+namespace {
+
+// the caller's settings as the kernels take them; a refusal before any device work
+int gicp_run_of(mml_ctx* ctx, const char* who, const mml_gicp_opts* o, GicpRun& run) {
+    if (!o) return mml_refuse(ctx, MML_ERR_INVALID, "%s: null options", who);
+    if (o->max_iterations < 1) return mml_refuse(ctx, MML_ERR_INVALID, "%s: max_iterations = %d is below 1", who, o->max_iterations);
+    if (!(isfinite(o->transformation_epsilon) && o->transformation_epsilon > 0.0))
+        return mml_refuse(ctx, MML_ERR_INVALID, "%s: transformation_epsilon = %g is not a positive finite number", who, o->transformation_epsilon);
+    if (isnan(o->max_correspondence_distance)) return mml_refuse(ctx, MML_ERR_INVALID, "%s: max_correspondence_distance is NaN", who);
+    run.max_it = o->max_iterations;
+    run.inv_trans_eps = 1.0 / o->transformation_epsilon;
+    run.gate2 = o->max_correspondence_distance > 0.0 ? o->max_correspondence_distance * o->max_correspondence_distance : 0.0;
+    return MML_OK;
+}
+
+}  // namespace
+
+extern "C" int mml_gicp_align_opts(mml_ctx* ctx, const float* src_xyz, int n_src, const float* tgt_xyz, int n_tgt, const mml_gicp_opts* opts,
+                                   float* T_inout, int* converged, mml_gicp_info* info) {
+    if (!ctx) return MML_ERR_INVALID;
+    MML_REQUIRE(n_src >= 0 && n_tgt >= 0 && (n_src == 0 || src_xyz) && (n_tgt == 0 || tgt_xyz) && T_inout && converged, MML_ERR_INVALID,
+                "bad arguments");
+    GicpRun run;
+    const int rc = gicp_run_of(ctx, "mml_gicp_align_opts", opts, run);
+    if (rc != MML_OK) return rc;
+    const int so[2] = {0, n_src}, to[2] = {0, n_tgt};
+    return gicp_align_n(ctx, "mml_gicp_align_opts", run, 1, src_xyz, so, tgt_xyz, to, T_inout, converged, info);
+}
+
+// mml_gicp_align_opts on two clouds that are on the device already (calibrate.hip), on an idle context: the clouds are copied
+// device to device into the alignments' own block.  (x, y, z are read; w travels along unused.)
+int mml_gicp_align_device(mml_ctx* ctx, const char* who, const float4* d_src, int n_src, const float4* d_tgt, int n_tgt,
+                          const mml_gicp_opts* opts, float* T_inout, int* converged, mml_gicp_info* info) {
+    GicpRun run;
+    int rc = gicp_run_of(ctx, who, opts, run);
+    if (rc != MML_OK) return rc;
+    GicpProb P;
+    size_t n_pts = 0, n_srcs = 0;
+    place_problem(P, n_src, n_tgt, n_pts, n_srcs);
+    const GicpState none = {};
+    const GicpState* h_st = &none;
+    if (n_pts > 0) {
+        const GicpIo io(1, 0);
+        const GicpBig big(n_pts, n_srcs, true);
+        MmlGicpDev* d = mml_side<MmlGicpDev>(ctx, MML_SIDE_GICP);
+        if (d->io.reserve(ctx, io.bytes) || d->big.reserve(ctx, big.bytes)) return MML_ERR_HIP;
+        hipStream_t s = MML_STREAM(ctx);
+        char *h = d->io.h, *g = d->io.d;
+        memcpy(io.tab.in(h), &P, sizeof(P));
+        float4* pts = big.pts.in(d->big.d);
+        MML_HIP(hipMemcpyAsync(io.tab.in(g), io.tab.in(h), io.tab.bytes(), hipMemcpyHostToDevice, s));
+        MML_HIP(hipMemcpyAsync(pts + P.src, d_src, sizeof(float4) * (size_t)n_src, hipMemcpyDeviceToDevice, s));
+        MML_HIP(hipMemcpyAsync(pts + P.tgt, d_tgt, sizeof(float4) * (size_t)n_tgt, hipMemcpyDeviceToDevice, s));
+        rc = gicp_core(ctx, run, 1, P.n_src, P.n_tgt, io.tab.in(g), pts, big.cov.in(d->big.d), big.maha.in(d->big.d), big.corr.in(d->big.d),
+                       io.st.in(g), io.st.in(h));
+        if (rc != MML_OK) return rc;
+        h_st = io.st.in(h);
+    }
+    gicp_result(P, *h_st, T_inout, converged, info);
+    return MML_OK;
 }
 
 namespace {
@@ -1034,7 +1152,7 @@ int gicp_refresh_n(mml_ctx* ctx, const char* who, int first_slot, int count, flo
             float4* pts = big.pts.in(d->big.d);
             hipLaunchKernelGGL(k_gicp_gather_raw, dim3(2, count), dim3(64), 0, s, A, d_tab, pts, (int*)nullptr);
             GicpState* hs = io.st.in(h);
-            rc = gicp_core(ctx, count, max_src, max_tgt, d_tab, pts, big.cov.in(d->big.d), big.maha.in(d->big.d), big.corr.in(d->big.d), io.st.in(g),
+            rc = gicp_core(ctx, FEATURE_NODE_RUN, count, max_src, max_tgt, d_tab, pts, big.cov.in(d->big.d), big.maha.in(d->big.d), big.corr.in(d->big.d), io.st.in(g),
                            hs);
             if (rc != MML_OK) return rc;
             h_st = hs;

@@ -78,6 +78,7 @@ enum MmlSideId {
     MML_SIDE_TIME_OFFSET,  // time_offset.hip MmlTofsDev: the blocks of the time-offset searches (single and batch calls)
     MML_SIDE_UNION,        // livox_stream.hip MmlUnionDev: the staging blocks of mml_union_assemble
     MML_SIDE_VELO_FOV,     // velo_fov.hip MmlVfovDev: the blocks of the Velodyne FOV selection (single and batch calls)
+    MML_SIDE_CALIB,        // calibrate.hip MmlCalibDev: the blocks of mml_cloud_crop_voxel / mml_aligner_calibrate
     MML_SIDE_COUNT
 };
 
@@ -381,6 +382,9 @@ int mml_launch_downsample(mml_ctx* ctx, int first, int count);
 inline int mml_voxel_cap_corner(const mml_ctx* ctx) { return (ctx->NT > 65536 || MML_VOXEL_LDS_CAP < 2048) ? MML_VOXEL_LDS_CAP : 2048; }
 int mml_build_grid(mml_ctx* ctx, int kind, const float* h_xyz, int m);
 int mml_build_grid_device(mml_ctx* ctx, int kind, int m);
+// gicp.hip: mml_gicp_align_opts on clouds that are on the device already, for a caller that has made the context idle
+int mml_gicp_align_device(mml_ctx* ctx, const char* who, const float4* d_src, int n_src, const float4* d_tgt, int n_tgt,
+                          const mml_gicp_opts* opts, float* T_inout, int* converged, mml_gicp_info* info);
 int mml_downsample_big(mml_ctx* ctx, int first, int count);
 int mml_downsample_redo_overflow(mml_ctx* ctx, int first, int count, std::vector<int>* redone);
 int mml_map_upkeep_increment(mml_ctx* ctx, int slot, const double* T_wl, int* n_out);

@@ -757,6 +757,21 @@ class Estimator {
     bool _fail_detected = false;
 };
 
+// ---- LidarsParamEstimator (unionLidarsAligner.cpp): the start-up calibration of hori_cloud_handler (:221-270) --------------
+// calibratePCLICP (lidars_extrinsic_cali.h:493-618) on the device (mml_aligner_calibrate): source_cloud = _hori_igcloud, target_cloud =
+// _velo_new_cloud, both packed x, y, z, intensity floats.  On convergence tf_matrix (row-major 4 x 4) receives
+// getFinalTransformation() and, when velo_hori_tf is given, that receives _velo_hori_tf_matrix as :251-253 build it ([R^T | -t],
+// not the rigid inverse); otherwise both stay as they were.  Returns hasConverged().  (save_pcd has no counterpart.)
+inline bool calibratePCLICP(Context& ctx, const float* source_cloud, int n_source, const float* target_cloud, int n_target, float* tf_matrix,
+                            float* velo_hori_tf = nullptr, mml_calib_info* info = nullptr) {
+    float unused[16];
+    int converged = 0;
+    check(ctx.get(), mml_aligner_calibrate(ctx.get(), source_cloud, n_source, target_cloud, n_target, tf_matrix,
+                                           velo_hori_tf ? velo_hori_tf : unused, &converged, info),
+          "mml_aligner_calibrate");
+    return converged != 0;
+}
+
 // ---- LidarsParamEstimator (unionLidarsAligner.cpp): the numeric core of estimate_timeoffset (:1077-1153) ----------------
 // velo_fov / livox: packed x, y, z floats (the FOV-cropped Velodyne cloud of :1080 and the merged Livox points of
 // :1053-1068); velo_hori_tf: _velo_hori_tf_matrix, row-major.  Returns the start index of the best window in the merged
