@@ -8,13 +8,13 @@
 //   k_cv_init      the cloud's header: an empty bounding box, zero counts
 //   k_cv_bbox      removeFarPointCloud's test per point ((x*x + y*y) + z*z > far_th*far_th, float, strict), bounding box and number
 //                  of the points that stay (getMinMax3D of the cropped cloud; min / max are order-free)
-//   k_cv_keys      PCL 1.8.1 voxel_grid.hpp applyFilter: inverse leaf in float, floor, min_b offset, index i + j dx + k dx dy.  A
-//                  cropped point gets a key above every index, so that the crop needs no compaction and no count on the host; when
-//                  the box holds more than INT32_MAX voxels PCL hands the cloud back unfiltered: every point is keyed by its own
-//                  place, which is the same thing -- one point per voxel, in input order
-//   rocPRIM        stable radix sort of (key, place) pairs on the key's 33 bits: a voxel's points stay in input order, which is the
+//   k_cv_keys      PCL 1.8.1 voxel_grid.hpp applyFilter's voxel index (MmlVoxGrid, voxel_sort_dev.h).  A cropped point gets a key
+//                  above every index, so that the crop needs no compaction and no count on the host; when the box holds more than
+//                  INT32_MAX voxels PCL hands the cloud back unfiltered: every point is keyed by its own place, which is the same
+//                  thing -- one point per voxel, in input order
+//   mml_sort_pairs stable radix sort of (key, place) pairs on the key's 33 bits: a voxel's points stay in input order, which is the
 //                  order mmlo_voxel_downsample (oracle/estimate.cpp) sums them in
-//   k_cv_heads, rocPRIM exclusive scan, k_cv_centroid
+//   k_run_heads, mml_exclusive_scan, k_cv_centroid
 //                  one lane per voxel: float sums of x, y, z, intensity in that order, divided by the count
 // mml_cloud_crop_voxel reads the header and the records back in one copy (one host synchronisation).  mml_aligner_calibrate runs
 // the chain for both clouds, reads the two headers back (one synchronisation) and hands the filtered clouds, still on the device,
@@ -24,9 +24,8 @@
 #include <math.h>
 #include <string.h>
 
-#include <rocprim/rocprim.hpp>
-
 #include "mml_internal.h"
+#include "voxel_sort_dev.h"
 
 namespace {
 
@@ -40,15 +39,11 @@ struct CvHdr {
 constexpr unsigned long long CV_DROPPED = 1ull << 32;  // key bit of a cropped point: behind every voxel index
 constexpr int CV_KEY_BITS = 33;
 
-__device__ __forceinline__ int cv_key(float v) {
-    const int iv = __float_as_int(v);
-    return iv >= 0 ? iv : (iv ^ 0x7fffffff);
-}
-__device__ __forceinline__ float cv_unkey(int key) { return __int_as_float(key >= 0 ? key : (key ^ 0x7fffffff)); }
 __device__ __forceinline__ bool cv_keep(const float4 p, float far2) { return !((p.x * p.x + p.y * p.y) + p.z * p.z > far2); }
 
 __global__ void k_cv_init(CvHdr* h) {
-    if (threadIdx.x < 6) h->bbox[threadIdx.x] = cv_key(threadIdx.x < 3 ? INFINITY : -INFINITY);
+    const int empty[6] = MML_BBOX_EMPTY;
+    if (threadIdx.x < 6) h->bbox[threadIdx.x] = empty[threadIdx.x];
     if (threadIdx.x == 6) {
         h->n_kept = 0;
         h->n_out = 0;
@@ -57,7 +52,6 @@ __global__ void k_cv_init(CvHdr* h) {
 }
 
 __global__ __launch_bounds__(256) void k_cv_bbox(const float4* __restrict__ in, int n, float far2, CvHdr* h) {
-    __shared__ float s[6][4];
     __shared__ int s_cnt[4];
     float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
     int cnt = 0;
@@ -72,31 +66,9 @@ __global__ __launch_bounds__(256) void k_cv_bbox(const float4* __restrict__ in, 
         mx[1] = fmaxf(mx[1], p.y);
         mx[2] = fmaxf(mx[2], p.z);
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int o = 32; o > 0; o >>= 1) {
-        cnt += __shfl_xor(cnt, o);
-        for (int c = 0; c < 3; ++c) {
-            mn[c] = fminf(mn[c], __shfl_xor(mn[c], o));
-            mx[c] = fmaxf(mx[c], __shfl_xor(mx[c], o));
-        }
-    }
-    if (lane == 0) {
-        for (int c = 0; c < 3; ++c) {
-            s[c][wave] = mn[c];
-            s[3 + c][wave] = mx[c];
-        }
-        s_cnt[wave] = cnt;
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int c = threadIdx.x;
-        float v = s[c][0];
-        for (int w = 1; w < 4; ++w) v = (c < 3) ? fminf(v, s[c][w]) : fmaxf(v, s[c][w]);
-        if (c < 3)
-            atomicMin(&h->bbox[c], cv_key(v));
-        else
-            atomicMax(&h->bbox[c], cv_key(v));
-    }
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = cnt;
+    mml_bbox_block_reduce(mn, mx, h->bbox);  // (its barrier also publishes s_cnt)
     if (threadIdx.x == 6) {
         const int t = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
         if (t) atomicAdd(&h->n_kept, t);
@@ -113,28 +85,11 @@ __global__ __launch_bounds__(256) void k_cv_keys(const float4* __restrict__ in, 
         keys[i] = CV_DROPPED | (unsigned)i;
         return;
     }
-    const float inv = 1.0f / leaf;  // inverse_leaf_size_
-    float bmn[3], bmx[3];
-    int min_b[3], div_b[3];
-    for (int c = 0; c < 3; ++c) {
-        bmn[c] = cv_unkey(h->bbox[c]);
-        bmx[c] = cv_unkey(h->bbox[3 + c]);
-        min_b[c] = static_cast<int>(floor(bmn[c] * inv));
-        const int max_b = static_cast<int>(floor(bmx[c] * inv));
-        div_b[c] = max_b - min_b[c] + 1;
-    }
-    const bool unfiltered = mml_voxel_grid_overflows(bmn, bmx, inv);
-    const int ijk0 = static_cast<int>(floor(p.x * inv) - static_cast<float>(min_b[0]));
-    const int ijk1 = static_cast<int>(floor(p.y * inv) - static_cast<float>(min_b[1]));
-    const int ijk2 = static_cast<int>(floor(p.z * inv) - static_cast<float>(min_b[2]));
-    keys[i] = unfiltered ? (unsigned)i : (unsigned)(ijk0 + ijk1 * div_b[0] + ijk2 * (div_b[0] * div_b[1]));
+    const MmlVoxGrid g = mml_vox_grid_of_keys(h->bbox, leaf);
+    const unsigned idx = g.index(p.x, p.y, p.z);
+    keys[i] = g.overflows ? (unsigned)i : idx;
     // (every kept point computes the same answer; the flag only ever goes from 0 to 1)
-    if (unfiltered) h->unfiltered = 1;
-}
-
-__global__ void k_cv_heads(const unsigned long long* __restrict__ keys, int n, int* __restrict__ flag) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) flag[i] = (keys[i] < CV_DROPPED && (i == 0 || keys[i] != keys[i - 1])) ? 1 : 0;
+    if (g.overflows) h->unfiltered = 1;
 }
 
 // one lane per voxel: the accumulator of pcl::VoxelGrid<PointXYZI> (float sums in input order, then / n), all four fields
@@ -148,19 +103,9 @@ __global__ void k_cv_centroid(const float4* __restrict__ in, const unsigned long
         out[pos[s]] = in[vals[s]];
         return;
     }
-    const unsigned long long vox = keys[s];
-    float sx = 0, sy = 0, sz = 0, si = 0;
-    int e = s;
-    while (e < n && keys[e] == vox) {
-        const float4 p = in[vals[e]];
-        sx += p.x;
-        sy += p.y;
-        sz += p.z;
-        si += p.w;
-        ++e;
-    }
-    const float c = static_cast<float>(e - s);
-    out[pos[s]] = make_float4(sx / c, sy / c, sz / c, si / c);  // (pos[s] < number of heads <= n, the room `out` has)
+    float4 sum;
+    const float c = static_cast<float>(mml_voxel_run_sum(in, keys, vals, s, n, 0, sum));
+    out[pos[s]] = make_float4(sum.x / c, sum.y / c, sum.z / c, sum.w / c);  // (pos[s] < number of heads <= n, the room `out` has)
 }
 
 // block (device + pinned twin): the inputs, the headers, the outputs; a cloud's header and its output are what is read back
@@ -200,20 +145,10 @@ struct MmlCalibDev {
 
 namespace {
 
-// rocPRIM's temporary storage for the sort and the scan of n elements
-int cv_tmp_bytes(mml_ctx* ctx, size_t n, size_t& need) {
-    size_t a = 0, b = 0;
-    MML_HIP(rocprim::radix_sort_pairs(nullptr, a, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (unsigned*)nullptr,
-                                      (unsigned*)nullptr, n, 0, CV_KEY_BITS, MML_STREAM(ctx)));
-    MML_HIP(rocprim::exclusive_scan(nullptr, b, (int*)nullptr, (int*)nullptr, 0, n, rocprim::plus<int>(), MML_STREAM(ctx)));
-    need = a > b ? a : b;
-    return MML_OK;
-}
-
+// (tmp is sized for the sort here, before anything is launched, so that the chain is not held up by an allocation; were the scan
+//  to ask for more, mml_exclusive_scan would drain the stream and grow it)
 int cv_reserve(mml_ctx* ctx, MmlCalibDev* d, const CvIo& io, size_t n_max) {
-    size_t need = 0;
-    const int rc = cv_tmp_bytes(ctx, n_max, need);
-    if (rc != MML_OK) return rc;
+    const size_t need = mml_sort_pairs_bytes<unsigned long long>(n_max, CV_KEY_BITS, MML_STREAM(ctx));
     const CvWork w(n_max);
     if (d->io.reserve(ctx, io.bytes) || d->work.reserve(ctx, w.bytes) || d->tmp.reserve(ctx, need ? need : 1)) return MML_ERR_HIP;
     return MML_OK;
@@ -231,11 +166,12 @@ int cv_launch(mml_ctx* ctx, MmlCalibDev* d, const float4* in, int n, float far_t
     hipLaunchKernelGGL(k_cv_bbox, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, s, in, n, far2, hdr);
     hipLaunchKernelGGL(k_cv_keys, dim3(blocks), dim3(256), 0, s, in, n, far2, leaf, hdr, w.keys.in(g), w.vals.in(g));
     MML_HIP(hipGetLastError());
-    size_t need = d->tmp.cap;
-    MML_HIP(rocprim::radix_sort_pairs(d->tmp.d, need, w.keys.in(g), w.keys2.in(g), w.vals.in(g), w.vals2.in(g), (size_t)n, 0, CV_KEY_BITS, s));
-    hipLaunchKernelGGL(k_cv_heads, dim3(blocks), dim3(256), 0, s, w.keys2.in(g), n, w.flag.in(g));
-    need = d->tmp.cap;
-    MML_HIP(rocprim::exclusive_scan(d->tmp.d, need, w.flag.in(g), w.pos.in(g), 0, (size_t)n, rocprim::plus<int>(), s));
+    int rc = mml_sort_pairs(ctx, d->tmp, w.keys.in(g), w.keys2.in(g), w.vals.in(g), w.vals2.in(g), (size_t)n, CV_KEY_BITS, s);
+    if (rc != MML_OK) return rc;
+    // (a cropped point starts no run)
+    hipLaunchKernelGGL(k_run_heads<unsigned long long>, dim3(blocks), dim3(256), 0, s, w.keys2.in(g), n, 0, CV_DROPPED, w.flag.in(g));
+    rc = mml_exclusive_scan(ctx, d->tmp, w.flag.in(g), w.pos.in(g), (size_t)n, s);
+    if (rc != MML_OK) return rc;
     hipLaunchKernelGGL(k_cv_centroid, dim3(blocks), dim3(256), 0, s, in, w.keys2.in(g), w.vals2.in(g), w.flag.in(g), w.pos.in(g), n, out, hdr);
     MML_HIP(hipGetLastError());
     return MML_OK;

@@ -14,64 +14,14 @@
 
 #include <cstring>
 #include <string.h>
-#include <rocprim/rocprim.hpp>
 
 #include "mml_internal.h"
+#include "voxel_sort_dev.h"
 
 namespace {
 
 // ---------------------------------------------------------------------------------------------------
 // grid build
-__global__ void k_bbox(const float4* pts, int m, float* out /*6: min xyz, max xyz*/) {
-    __shared__ float s[6][4];
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < m; i += gridDim.x * blockDim.x) {
-        float4 p = pts[i];
-        mn[0] = fminf(mn[0], p.x);
-        mn[1] = fminf(mn[1], p.y);
-        mn[2] = fminf(mn[2], p.z);
-        mx[0] = fmaxf(mx[0], p.x);
-        mx[1] = fmaxf(mx[1], p.y);
-        mx[2] = fmaxf(mx[2], p.z);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int c = 0; c < 3; ++c) {
-        for (int o = 32; o > 0; o >>= 1) {
-            mn[c] = fminf(mn[c], __shfl_xor(mn[c], o));
-            mx[c] = fmaxf(mx[c], __shfl_xor(mx[c], o));
-        }
-        if (lane == 0) {
-            s[c][wave] = mn[c];
-            s[3 + c][wave] = mx[c];
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int c = threadIdx.x;
-        float v = s[c][0];
-        for (int w = 1; w < 4; ++w) v = (c < 3) ? fminf(v, s[c][w]) : fmaxf(v, s[c][w]);
-        // float atomics via int reinterpretation (monotone for the sign handled below)
-        if (c < 3) {
-            // atomic min on float
-            int* a = reinterpret_cast<int*>(out + c);
-            int old = *a;
-            while (v < __int_as_float(old)) {
-                int assumed = old;
-                old = atomicCAS(a, assumed, __float_as_int(v));
-                if (old == assumed) break;
-            }
-        } else {
-            int* a = reinterpret_cast<int*>(out + c);
-            int old = *a;
-            while (v > __int_as_float(old)) {
-                int assumed = old;
-                old = atomicCAS(a, assumed, __float_as_int(v));
-                if (old == assumed) break;
-            }
-        }
-    }
-}
-
 struct GridDev {
     float ox, oy, oz, inv_cell, cell;
     int dx, dy, dz, ncell;
@@ -1103,13 +1053,15 @@ static int build_grid_into(mml_ctx* ctx, MmlGrid& g, float4* orig, const float* 
         MML_HIP(hipStreamSynchronize(s));  // tmp goes out of scope
     }
     MmlStageScope t(ctx, "map_build");
-    float init[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
-    float* d_bbox = reinterpret_cast<float*>(ctx->d_misc);
+    const int init[6] = MML_BBOX_EMPTY;
+    int* d_bbox = ctx->d_misc;
     MML_HIP(hipMemcpyAsync(d_bbox, init, sizeof(init), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(k_bbox, dim3(256), dim3(256), 0, s, orig, m, d_bbox);
-    float bbox[6];
-    MML_HIP(hipMemcpyAsync(bbox, d_bbox, sizeof(bbox), hipMemcpyDeviceToHost, s));
+    int bbox_keys[6];
+    MML_HIP(hipMemcpyAsync(bbox_keys, d_bbox, sizeof(bbox_keys), hipMemcpyDeviceToHost, s));
     MML_HIP(hipStreamSynchronize(s));
+    float bbox[6];
+    for (int c = 0; c < 6; ++c) bbox[c] = mml_funkey(bbox_keys[c]);
     const long long max_cells = (long long)4 * ctx->MM + 4096;
     const int blocks = (m + 255) / 256;
     int dim[3];
@@ -1137,13 +1089,8 @@ static int build_grid_into(mml_ctx* ctx, MmlGrid& g, float4* orig, const float* 
         hipLaunchKernelGGL(k_cell_keys, dim3(blocks), dim3(256), 0, s, orig, m, gd, ctx->map_keys, ctx->map_vals);
         int bits = 1;
         while ((1ll << bits) < g.ncell) ++bits;
-        size_t need = 0;
-        MML_HIP(rocprim::radix_sort_pairs(nullptr, need, ctx->map_keys, ctx->map_keys2, ctx->map_vals, ctx->map_vals2,
-                                          (size_t)m, 0, bits, s));
-        const int rt = mml_sort_tmp(ctx, need);
+        const int rt = mml_sort_pairs(ctx, ctx->sort_tmp, ctx->map_keys, ctx->map_keys2, ctx->map_vals, ctx->map_vals2, (size_t)m, bits, s);
         if (rt != MML_OK) return rt;
-        MML_HIP(rocprim::radix_sort_pairs(ctx->sort_tmp.d, need, ctx->map_keys, ctx->map_keys2, ctx->map_vals,
-                                          ctx->map_vals2, (size_t)m, 0, bits, s));
         int* d_occ = ctx->d_misc + 16;
         MML_HIP(hipMemsetAsync(d_occ, 0, sizeof(int), s));
         hipLaunchKernelGGL(k_count_occupied, dim3(blocks), dim3(256), 0, s, ctx->map_keys2, m, d_occ);

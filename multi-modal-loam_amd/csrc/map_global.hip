@@ -19,9 +19,9 @@
 #include <cstring>
 #include <string.h>
 #include <vector>
-#include <rocprim/rocprim.hpp>
 
 #include "mml_internal.h"
+#include "voxel_sort_dev.h"
 
 namespace {
 
@@ -102,12 +102,6 @@ __global__ void k_classify(const uint16_t* stag, int n0, const uint16_t* ptag, i
     sel[u] = filt ? 1 : 0;
 }
 
-__device__ __forceinline__ int fkey(float v) {
-    const int iv = __float_as_int(v);
-    return iv >= 0 ? iv : (iv ^ 0x7fffffff);
-}
-__device__ __forceinline__ float unkey(int key) { return __int_as_float(key >= 0 ? key : (key ^ 0x7fffffff)); }
-
 __global__ void k_scatter(const float4* spts, const uint16_t* stag, int n0, const float4* ppts, const uint16_t* ptag, int np,
                           const int* keep, const int* keep_pos, const int* sel, const int* sel_pos, float4* out_pts,
                           uint16_t* out_tag, float4* sel_pts, uint16_t* sel_tag, int* bbox /* NCUBE x 6 keys */) {
@@ -122,19 +116,20 @@ __global__ void k_scatter(const float4* spts, const uint16_t* stag, int n0, cons
         sel_pts[sel_pos[u]] = p;
         sel_tag[sel_pos[u]] = t;
         int* b = bbox + 6 * (int)t;  // getMinMax3D of the cube's cloud
-        atomicMin(b + 0, fkey(p.x));
-        atomicMin(b + 1, fkey(p.y));
-        atomicMin(b + 2, fkey(p.z));
-        atomicMax(b + 3, fkey(p.x));
-        atomicMax(b + 4, fkey(p.y));
-        atomicMax(b + 5, fkey(p.z));
+        atomicMin(b + 0, mml_fkey(p.x));
+        atomicMin(b + 1, mml_fkey(p.y));
+        atomicMin(b + 2, mml_fkey(p.z));
+        atomicMax(b + 3, mml_fkey(p.x));
+        atomicMax(b + 4, mml_fkey(p.y));
+        atomicMax(b + 5, mml_fkey(p.z));
     }
 }
 
 __global__ void k_init_bbox(int* bbox) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= NCUBE * 6) return;
-    bbox[i] = (i % 6) < 3 ? 0x7f800000 : (int)(0xff800000u ^ 0x7fffffffu);
+    const int empty[6] = MML_BBOX_EMPTY;
+    bbox[i] = empty[i % 6];
 }
 
 // PCL 1.8.1 voxel_grid.hpp applyFilter, per cube: key = cube << 40 | voxel index inside the cube's own grid
@@ -142,27 +137,11 @@ __global__ void k_cube_vox_keys(const float4* pts, const uint16_t* tags, int n, 
                                 unsigned long long* keys, unsigned* vals) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float inv = 1.0f / leaf;
     const int t = tags[i];
-    const int* b = bbox + 6 * t;
-    int min_b[3], div_b[3];
-    for (int c = 0; c < 3; ++c) {
-        min_b[c] = static_cast<int>(floor(unkey(b[c]) * inv));
-        const int max_b = static_cast<int>(floor(unkey(b[3 + c]) * inv));
-        div_b[c] = max_b - min_b[c] + 1;
-    }
+    const MmlVoxGrid g = mml_vox_grid_of_keys(bbox + 6 * t, leaf);  // (no overflow fall-back here: g.overflows is not consulted)
     const float4 p = pts[i];
-    const int ijk0 = static_cast<int>(floor(p.x * inv) - static_cast<float>(min_b[0]));
-    const int ijk1 = static_cast<int>(floor(p.y * inv) - static_cast<float>(min_b[1]));
-    const int ijk2 = static_cast<int>(floor(p.z * inv) - static_cast<float>(min_b[2]));
-    const unsigned idx = (unsigned)(ijk0 + ijk1 * div_b[0] + ijk2 * (div_b[0] * div_b[1]));
-    keys[i] = ((unsigned long long)t << 40) | idx;
+    keys[i] = ((unsigned long long)t << 40) | g.index(p.x, p.y, p.z);
     vals[i] = (unsigned)i;
-}
-
-__global__ void k_heads64(const unsigned long long* keys, int n, int* flag) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) flag[i] = (i == 0 || keys[i] != keys[i - 1]) ? 1 : 0;
 }
 
 __global__ void k_cube_centroid(const float4* pts, const unsigned long long* keys, const unsigned* vals, const int* flag,
@@ -174,17 +153,9 @@ __global__ void k_cube_centroid(const float4* pts, const unsigned long long* key
     const int dst = base + pos[s];
     if (dst >= cap) return;
     const unsigned long long key = keys[s];
-    float sx = 0, sy = 0, sz = 0;
-    int e = s;
-    while (e < n && keys[e] == key) {
-        const float4 p = pts[vals[e]];
-        sx += p.x;
-        sy += p.y;
-        sz += p.z;
-        ++e;
-    }
-    const float c = static_cast<float>(e - s);
-    out_pts[dst] = make_float4(sx / c, sy / c, sz / c, 0.f);
+    float4 sum;
+    const float c = static_cast<float>(mml_voxel_run_sum(pts, keys, vals, s, n, 0, sum));
+    out_pts[dst] = make_float4(sum.x / c, sum.y / c, sum.z / c, 0.f);
     out_tag[dst] = (uint16_t)(key >> 40);
 }
 
@@ -309,12 +280,9 @@ int mml_cube_store_increment(mml_ctx* ctx, const double* T_wl, int* n_out) {
         if (nu) {
             hipLaunchKernelGGL(k_classify, dim3((nu + 255) / 256), dim3(256), 0, s, ctx->gs_tag[kind], n0, ptag, np, cnt, changed,
                                keep, sel);
-            size_t need = 0;
-            MML_HIP(rocprim::exclusive_scan(nullptr, need, keep, keep_pos, 0, (size_t)nu, rocprim::plus<int>(), s));
-            rc = mml_sort_tmp(ctx, need);
+            rc = mml_exclusive_scan(ctx, ctx->sort_tmp, keep, keep_pos, (size_t)nu, s);
+            if (rc == MML_OK) rc = mml_exclusive_scan(ctx, ctx->sort_tmp, sel, sel_pos, (size_t)nu, s);
             if (rc != MML_OK) return rc;
-            MML_HIP(rocprim::exclusive_scan(ctx->sort_tmp.d, need, keep, keep_pos, 0, (size_t)nu, rocprim::plus<int>(), s));
-            MML_HIP(rocprim::exclusive_scan(ctx->sort_tmp.d, need, sel, sel_pos, 0, (size_t)nu, rocprim::plus<int>(), s));
             int last[4];
             MML_HIP(hipMemcpyAsync(&last[0], keep + nu - 1, sizeof(int), hipMemcpyDeviceToHost, s));
             MML_HIP(hipMemcpyAsync(&last[1], keep_pos + nu - 1, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -332,17 +300,12 @@ int mml_cube_store_increment(mml_ctx* ctx, const double* T_wl, int* n_out) {
                 const int blocks = (nsel + 255) / 256;
                 const float leaf = 0.4f;  // MAP_MANAGER's own filters, Map_Manager.cpp:58-60 (corner and surf alike)
                 hipLaunchKernelGGL(k_cube_vox_keys, dim3(blocks), dim3(256), 0, s, sel_pts, sel_tag, nsel, bbox, leaf, keys, vals);
-                need = 0;
-                MML_HIP(rocprim::radix_sort_pairs(nullptr, need, keys, keys2, vals, vals2, (size_t)nsel, 0, 56, s));
-                rc = mml_sort_tmp(ctx, need);
+                rc = mml_sort_pairs(ctx, ctx->sort_tmp, keys, keys2, vals, vals2, (size_t)nsel, 56, s);
                 if (rc != MML_OK) return rc;
-                MML_HIP(rocprim::radix_sort_pairs(ctx->sort_tmp.d, need, keys, keys2, vals, vals2, (size_t)nsel, 0, 56, s));
-                hipLaunchKernelGGL(k_heads64, dim3(blocks), dim3(256), 0, s, keys2, nsel, keep);  // keep / keep_pos are free again
-                need = 0;
-                MML_HIP(rocprim::exclusive_scan(nullptr, need, keep, keep_pos, 0, (size_t)nsel, rocprim::plus<int>(), s));
-                rc = mml_sort_tmp(ctx, need);
+                // keep / keep_pos are free again
+                hipLaunchKernelGGL(k_run_heads<unsigned long long>, dim3(blocks), dim3(256), 0, s, keys2, nsel, 0, ~0ull, keep);
+                rc = mml_exclusive_scan(ctx, ctx->sort_tmp, keep, keep_pos, (size_t)nsel, s);
                 if (rc != MML_OK) return rc;
-                MML_HIP(rocprim::exclusive_scan(ctx->sort_tmp.d, need, keep, keep_pos, 0, (size_t)nsel, rocprim::plus<int>(), s));
                 hipLaunchKernelGGL(k_cube_centroid, dim3(blocks), dim3(256), 0, s, sel_pts, keys2, vals2, keep, keep_pos, nsel, nk,
                                    ctx->MM, ctx->gs_pts2[kind], ctx->gs_tag2[kind], d_heads);
                 MML_HIP(hipMemcpyAsync(&nheads, d_heads, sizeof(int), hipMemcpyDeviceToHost, s));

@@ -16,9 +16,9 @@
 
 #include <cstring>
 #include <string.h>
-#include <rocprim/rocprim.hpp>
 
 #include "mml_internal.h"
+#include "voxel_sort_dev.h"
 
 namespace {
 
@@ -51,71 +51,16 @@ __global__ void k_concat(const float4* ring, int MF, RingOffsets R, float4* cat)
         cat[R.off[s] + i] = ring[(size_t)s * MF + i];
 }
 
-__global__ void k_minmax(const float4* pts, int m, float* out /* 6: min xyz, max xyz */) {
-    __shared__ float s[6][4];
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < m; i += gridDim.x * blockDim.x) {
-        const float4 p = pts[i];
-        mn[0] = fminf(mn[0], p.x);
-        mn[1] = fminf(mn[1], p.y);
-        mn[2] = fminf(mn[2], p.z);
-        mx[0] = fmaxf(mx[0], p.x);
-        mx[1] = fmaxf(mx[1], p.y);
-        mx[2] = fmaxf(mx[2], p.z);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int c = 0; c < 3; ++c) {
-        for (int o = 32; o > 0; o >>= 1) {
-            mn[c] = fminf(mn[c], __shfl_xor(mn[c], o));
-            mx[c] = fmaxf(mx[c], __shfl_xor(mx[c], o));
-        }
-        if (lane == 0) {
-            s[c][wave] = mn[c];
-            s[3 + c][wave] = mx[c];
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int c = threadIdx.x;
-        float v = s[c][0];
-        for (int w = 1; w < 4; ++w) v = (c < 3) ? fminf(v, s[c][w]) : fmaxf(v, s[c][w]);
-        // min / max of floats through their order-preserving integer image
-        int* a = reinterpret_cast<int*>(out + c);
-        const int iv = __float_as_int(v);
-        const int key = iv >= 0 ? iv : (iv ^ 0x7fffffff);
-        if (c < 3)
-            atomicMin(a, key);
-        else
-            atomicMax(a, key);
-    }
-}
-__device__ __forceinline__ float unkey(int key) { return __int_as_float(key >= 0 ? key : (key ^ 0x7fffffff)); }
-
-// PCL 1.8.1 voxel_grid.hpp applyFilter: inverse leaf in float, floor, int, min_b offset (same arithmetic as k_voxel)
+// PCL 1.8.1 voxel_grid.hpp applyFilter (MmlVoxGrid)
 __global__ void k_vox_keys(const float4* pts, int m, const int* bbox_keys, float leaf, unsigned* keys, unsigned* vals) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= m) return;
-    const float inv = 1.0f / leaf;
-    int min_b[3], div_b[3];
-    for (int c = 0; c < 3; ++c) {
-        min_b[c] = static_cast<int>(floor(unkey(bbox_keys[c]) * inv));
-        const int max_b = static_cast<int>(floor(unkey(bbox_keys[3 + c]) * inv));
-        div_b[c] = max_b - min_b[c] + 1;
-    }
+    const MmlVoxGrid g = mml_vox_grid_of_keys(bbox_keys, leaf);
     const float4 p = pts[i];
-    const int ijk0 = static_cast<int>(floor(p.x * inv) - static_cast<float>(min_b[0]));
-    const int ijk1 = static_cast<int>(floor(p.y * inv) - static_cast<float>(min_b[1]));
-    const int ijk2 = static_cast<int>(floor(p.z * inv) - static_cast<float>(min_b[2]));
-    const float bmn[3] = {unkey(bbox_keys[0]), unkey(bbox_keys[1]), unkey(bbox_keys[2])};
-    const float bmx[3] = {unkey(bbox_keys[3]), unkey(bbox_keys[4]), unkey(bbox_keys[5])};
+    const unsigned idx = g.index(p.x, p.y, p.z);
     // (more than INT_MAX voxels in the box: PCL returns the cloud unfiltered = every point its own voxel, in input order)
-    keys[i] = mml_voxel_grid_overflows(bmn, bmx, inv) ? (unsigned)i : (unsigned)(ijk0 + ijk1 * div_b[0] + ijk2 * (div_b[0] * div_b[1]));
+    keys[i] = g.overflows ? (unsigned)i : idx;
     vals[i] = (unsigned)i;
-}
-
-__global__ void k_vox_heads(const unsigned* keys, int m, int* flag) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < m) flag[i] = (i == 0 || keys[i] != keys[i - 1]) ? 1 : 0;
 }
 
 // one lane per voxel: AccumulatorXYZ (float sum in input order, then / n)
@@ -127,18 +72,9 @@ __global__ void k_vox_centroid(const float4* pts, const unsigned* keys, const un
     if (!flag[s]) return;
     const int dst = pos[s];
     if (dst >= cap) return;
-    const unsigned vox = keys[s];
-    float sx = 0, sy = 0, sz = 0;
-    int e = s;
-    while (e < m && keys[e] == vox) {
-        const float4 p = pts[vals[e]];
-        sx += p.x;
-        sy += p.y;
-        sz += p.z;
-        ++e;
-    }
-    const float c = static_cast<float>(e - s);
-    out[dst] = make_float4(sx / c, sy / c, sz / c, 0.f);
+    float4 sum;
+    const float c = static_cast<float>(mml_voxel_run_sum(pts, keys, vals, s, m, 0, sum));
+    out[dst] = make_float4(sum.x / c, sum.y / c, sum.z / c, 0.f);
 }
 
 // pcl::VoxelGrid over `m` device points; the filtered cloud goes to `out` (capacity cap), its size to *h_n
@@ -149,27 +85,18 @@ int voxel_filter_device(mml_ctx* ctx, const float4* pts, int m, float leaf, floa
     MML_REQUIRE(m <= ctx->MM && (size_t)m <= ctx->vox_cap, MML_ERR_CAPACITY, "cloud larger than max_map_points");
     int* d_bbox = ctx->d_misc;
     int* d_n = ctx->d_misc + 8;
-    const int init[6] = {0x7f800000, 0x7f800000, 0x7f800000, (int)0xff800000 ^ 0x7fffffff, (int)0xff800000 ^ 0x7fffffff,
-                         (int)0xff800000 ^ 0x7fffffff};  // +inf x3, key(-inf) x3
+    const int init[6] = MML_BBOX_EMPTY;
     MML_HIP(hipMemcpyAsync(d_bbox, init, sizeof(init), hipMemcpyHostToDevice, s));
     const int blocks = (m + 255) / 256;
-    hipLaunchKernelGGL(k_minmax, dim3(blocks < 256 ? blocks : 256), dim3(256), 0, s, pts, m, reinterpret_cast<float*>(d_bbox));
+    hipLaunchKernelGGL(k_bbox, dim3(blocks < 256 ? blocks : 256), dim3(256), 0, s, pts, m, d_bbox);
     hipLaunchKernelGGL(k_vox_keys, dim3(blocks), dim3(256), 0, s, pts, m, d_bbox, leaf, ctx->map_keys, ctx->map_vals);
-    size_t need = 0;
-    MML_HIP(rocprim::radix_sort_pairs(nullptr, need, ctx->map_keys, ctx->map_keys2, ctx->map_vals, ctx->map_vals2,
-                                      (size_t)m, 0, 32, s));
-    int rc = mml_sort_tmp(ctx, need);
+    int rc = mml_sort_pairs(ctx, ctx->sort_tmp, ctx->map_keys, ctx->map_keys2, ctx->map_vals, ctx->map_vals2, (size_t)m, 32, s);
     if (rc != MML_OK) return rc;
-    MML_HIP(rocprim::radix_sort_pairs(ctx->sort_tmp.d, need, ctx->map_keys, ctx->map_keys2, ctx->map_vals, ctx->map_vals2,
-                                      (size_t)m, 0, 32, s));
     int* flag = ctx->vox_flag;
     int* pos = ctx->vox_flag + ctx->vox_cap + 1;
-    hipLaunchKernelGGL(k_vox_heads, dim3(blocks), dim3(256), 0, s, ctx->map_keys2, m, flag);
-    need = 0;
-    MML_HIP(rocprim::exclusive_scan(nullptr, need, flag, pos, 0, (size_t)m, rocprim::plus<int>(), s));
-    rc = mml_sort_tmp(ctx, need);
+    hipLaunchKernelGGL(k_run_heads<unsigned>, dim3(blocks), dim3(256), 0, s, ctx->map_keys2, m, 0, ~0u, flag);
+    rc = mml_exclusive_scan(ctx, ctx->sort_tmp, flag, pos, (size_t)m, s);
     if (rc != MML_OK) return rc;
-    MML_HIP(rocprim::exclusive_scan(ctx->sort_tmp.d, need, flag, pos, 0, (size_t)m, rocprim::plus<int>(), s));
     hipLaunchKernelGGL(k_vox_centroid, dim3(blocks), dim3(256), 0, s, pts, ctx->map_keys2, ctx->map_vals2, flag, pos, m, cap,
                        out, d_n);
     MML_HIP(hipMemcpyAsync(h_n, d_n, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -220,13 +147,12 @@ __global__ void k_seg_prefix(SegParams P, int* total) {
         P.seg_off[nseg] = run;
         *total = run;
     }
-    for (int i = threadIdx.x; i < 6 * nseg; i += blockDim.x)
-        P.seg_bbox[i] = (i % 6) < 3 ? 0x7f800000 : ((int)0xff800000 ^ 0x7fffffff);  // +inf, key(-inf)
+    const int empty[6] = MML_BBOX_EMPTY;
+    for (int i = threadIdx.x; i < 6 * nseg; i += blockDim.x) P.seg_bbox[i] = empty[i % 6];
 }
 
 // grid (blocks, segment): gather the labelled points and reduce the segment's bounding box
 __global__ void k_seg_gather_bbox(SegParams P) {
-    __shared__ float s[6][4];
     const int g = blockIdx.y, b = P.first + (g >> 1), kind = g & 1;
     const int n = P.fu_info[8 * b + 6 + kind], off = P.seg_off[g];
     const unsigned* list = P.lists + ((size_t)b * 2 + kind) * P.list_stride;
@@ -244,62 +170,24 @@ __global__ void k_seg_gather_bbox(SegParams P) {
         mx[1] = fmaxf(mx[1], p.y);
         mx[2] = fmaxf(mx[2], p.z);
     }
-    if ((int)(blockIdx.x * blockDim.x) >= n) return;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int c = 0; c < 3; ++c) {
-        for (int o = 32; o > 0; o >>= 1) {
-            mn[c] = fminf(mn[c], __shfl_xor(mn[c], o));
-            mx[c] = fmaxf(mx[c], __shfl_xor(mx[c], o));
-        }
-        if (lane == 0) {
-            s[c][wave] = mn[c];
-            s[3 + c][wave] = mx[c];
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int c = threadIdx.x;
-        float v = s[c][0];
-        for (int w = 1; w < 4; ++w) v = (c < 3) ? fminf(v, s[c][w]) : fmaxf(v, s[c][w]);
-        const int iv = __float_as_int(v);
-        const int key = iv >= 0 ? iv : (iv ^ 0x7fffffff);
-        if (c < 3)
-            atomicMin(P.seg_bbox + 6 * g + c, key);
-        else
-            atomicMax(P.seg_bbox + 6 * g + c, key);
-    }
+    if ((int)(blockIdx.x * blockDim.x) >= n) return;  // (the whole workgroup)
+    mml_bbox_block_reduce(mn, mx, P.seg_bbox + 6 * g);
 }
 
 __global__ void k_seg_keys(SegParams P) {
     const int g = blockIdx.y, kind = g & 1;
     const int off = P.seg_off[g], n = P.seg_off[g + 1] - off;
-    const float leaf = kind == 0 ? P.leaf_corner : P.leaf_surf;
-    const float inv = 1.0f / leaf;
-    int min_b[3], div_b[3];
-    for (int c = 0; c < 3; ++c) {
-        min_b[c] = static_cast<int>(floor(unkey(P.seg_bbox[6 * g + c]) * inv));
-        const int max_b = static_cast<int>(floor(unkey(P.seg_bbox[6 * g + 3 + c]) * inv));
-        div_b[c] = max_b - min_b[c] + 1;
-    }
-    const float bmn[3] = {unkey(P.seg_bbox[6 * g]), unkey(P.seg_bbox[6 * g + 1]), unkey(P.seg_bbox[6 * g + 2])};
-    const float bmx[3] = {unkey(P.seg_bbox[6 * g + 3]), unkey(P.seg_bbox[6 * g + 4]), unkey(P.seg_bbox[6 * g + 5])};
-    const bool unfiltered = n > 0 && mml_voxel_grid_overflows(bmn, bmx, inv);  // (PCL returns the cloud as it came)
+    const MmlVoxGrid G = mml_vox_grid_of_keys(P.seg_bbox + 6 * g, kind == 0 ? P.leaf_corner : P.leaf_surf);
+    const bool unfiltered = n > 0 && G.overflows;  // (PCL returns the cloud as it came)
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const float4 p = P.cat[off + i];
-        const int ijk0 = static_cast<int>(floor(p.x * inv) - static_cast<float>(min_b[0]));
-        const int ijk1 = static_cast<int>(floor(p.y * inv) - static_cast<float>(min_b[1]));
-        const int ijk2 = static_cast<int>(floor(p.z * inv) - static_cast<float>(min_b[2]));
+        const unsigned idx = G.index(p.x, p.y, p.z);
         // (unfiltered: every point its own voxel, in the order of the fused cloud -- the gathered list is in storage order)
-        const unsigned vox = unfiltered ? (unsigned)__float_as_int(p.w) : (unsigned)(ijk0 + ijk1 * div_b[0] + ijk2 * (div_b[0] * div_b[1]));
+        const unsigned vox = unfiltered ? (unsigned)__float_as_int(p.w) : idx;
         // (segment 12 bits | voxel 32 bits | fused index 20 bits): one sort gives segment, voxel, reference order
         P.keys[off + i] = ((unsigned long long)g << 52) | ((unsigned long long)vox << 20) | (unsigned)__float_as_int(p.w);
         P.vals[off + i] = (unsigned)(off + i);
     }
-}
-
-__global__ void k_seg_heads(const unsigned long long* keys, int m, int* flag) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < m) flag[i] = (i == 0 || (keys[i] >> 20) != (keys[i - 1] >> 20)) ? 1 : 0;  // new (segment, voxel)
 }
 
 // one lane per voxel; the lane of a segment's first voxel also publishes the segment's voxel count
@@ -315,17 +203,9 @@ __global__ void k_seg_centroid(SegParams P, const unsigned long long* keys, cons
         P.ft_n[kind * P.B + b] = nvox > P.MF ? -1 : nvox;
     }
     if (dst >= P.MF) return;
-    float sx = 0, sy = 0, sz = 0;
-    int e = s;
-    while (e < m && (keys[e] >> 20) == key) {
-        const float4 p = P.cat[vals[e]];
-        sx += p.x;
-        sy += p.y;
-        sz += p.z;
-        ++e;
-    }
-    const float c = static_cast<float>(e - s);
-    (kind == 0 ? P.ft0 : P.ft1)[(size_t)b * P.MF + dst] = make_float4(sx / c, sy / c, sz / c, 0.f);
+    float4 sum;  // (sum.w adds up the fused indices' bit patterns and is not read)
+    const float c = static_cast<float>(mml_voxel_run_sum(P.cat, keys, vals, s, m, 20, sum));
+    (kind == 0 ? P.ft0 : P.ft1)[(size_t)b * P.MF + dst] = make_float4(sum.x / c, sum.y / c, sum.z / c, 0.f);
 }
 
 __global__ void k_seg_empty(SegParams P) {  // segments without labelled points have an empty stack
@@ -391,19 +271,14 @@ int mml_downsample_big(mml_ctx* ctx, int first, int count) {
     if (total == 0) return MML_OK;
     int seg_bits = 1;
     while ((1 << seg_bits) < nseg) ++seg_bits;
-    size_t need = 0;
     MML_REQUIRE(ctx->NT <= (1 << 20) && nseg <= 4096, MML_ERR_CAPACITY, "global-sort down-sampler: scans up to 2^20 points, 2048 slots per call");
-    MML_HIP(rocprim::radix_sort_pairs(nullptr, need, P.keys, keys2, P.vals, vals2, (size_t)total, 0, 52 + seg_bits, s));
-    int rc = ctx->seg_tmp[ctx->cur].reserve(ctx, need, s);
+    int rc = mml_sort_pairs(ctx, ctx->seg_tmp[ctx->cur], P.keys, keys2, P.vals, vals2, (size_t)total, 52 + seg_bits, s);
     if (rc != MML_OK) return rc;
-    MML_HIP(rocprim::radix_sort_pairs(ctx->seg_tmp[ctx->cur].d, need, P.keys, keys2, P.vals, vals2, (size_t)total, 0, 52 + seg_bits, s));
     const int blocks = (total + 255) / 256;
-    hipLaunchKernelGGL(k_seg_heads, dim3(blocks), dim3(256), 0, s, keys2, total, flag);
-    need = 0;
-    MML_HIP(rocprim::exclusive_scan(nullptr, need, flag, pos, 0, (size_t)total, rocprim::plus<int>(), s));
-    rc = ctx->seg_tmp[ctx->cur].reserve(ctx, need, s);
+    // (a head = a new (segment, voxel): the key above the fused index's 20 bits)
+    hipLaunchKernelGGL(k_run_heads<unsigned long long>, dim3(blocks), dim3(256), 0, s, keys2, total, 20, ~0ull, flag);
+    rc = mml_exclusive_scan(ctx, ctx->seg_tmp[ctx->cur], flag, pos, (size_t)total, s);
     if (rc != MML_OK) return rc;
-    MML_HIP(rocprim::exclusive_scan(ctx->seg_tmp[ctx->cur].d, need, flag, pos, 0, (size_t)total, rocprim::plus<int>(), s));
     hipLaunchKernelGGL(k_seg_centroid, dim3(blocks), dim3(256), 0, s, P, keys2, vals2, flag, pos, total);
     MML_HIP(hipGetLastError());
     return MML_OK;

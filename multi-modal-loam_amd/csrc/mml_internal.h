@@ -268,7 +268,7 @@ struct mml_ctx {
     unsigned* map_keys2 = nullptr;
     unsigned* map_vals = nullptr;
     unsigned* map_vals2 = nullptr;
-    MmlStaging<char, false> sort_tmp;  // rocPRIM temporary storage of the map builds and filters (mml_sort_tmp)
+    MmlStaging<char, false> sort_tmp;  // rocPRIM temporary storage of the map builds and filters (voxel_sort_dev.h)
     int MM = 0;
 
     // solver state
@@ -313,14 +313,6 @@ struct mml_ctx {
     }
 };
 
-// pcl::VoxelGrid::applyFilter (PCL 1.8.1 voxel_grid.hpp): a bounding box of more than INT_MAX voxels ("Leaf size is too small for the
-// input dataset. Integer indices would overflow.") returns the cloud UNFILTERED.  The device filters then key every point by its
-// own ordinal, which is the same thing: every voxel holds one point, in input order.
-__host__ __device__ inline bool mml_voxel_grid_overflows(const float* mn, const float* mx, float inv) {
-    const long long dx = static_cast<long long>((mx[0] - mn[0]) * inv) + 1, dy = static_cast<long long>((mx[1] - mn[1]) * inv) + 1,
-                    dz = static_cast<long long>((mx[2] - mn[2]) * inv) + 1;
-    return dx * dy * dz > 2147483647LL;
-}
 #define MML_STREAM(ctx) ((ctx)->streams[(ctx)->cur])
 int mml_sync_all(mml_ctx* ctx);
 // For a call that reads no slot and wants an idle device: selects the context's device, ends everything the context has in
@@ -354,9 +346,6 @@ int mml_uploads_wait(mml_ctx* ctx, int first, int count);
 // A refusal with a formatted message: the text goes to ctx->err when there is a context to carry it (at most 191 characters),
 // `code` comes back.  capi.hip.
 int mml_refuse(mml_ctx* ctx, int code, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
-
-// ctx->sort_tmp with room for `need` bytes; the current stream is drained before a live buffer is replaced
-inline int mml_sort_tmp(mml_ctx* ctx, size_t need) { return ctx->sort_tmp.reserve(ctx, need, MML_STREAM(ctx)); }
 
 // profiling bracket (no-op unless enabled)
 int mml_stage_begin(mml_ctx* ctx, const char* name);

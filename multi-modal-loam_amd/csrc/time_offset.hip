@@ -13,9 +13,8 @@
 #include <math.h>
 #include <string.h>
 
-#include <rocprim/rocprim.hpp>
-
 #include "mml_internal.h"
+#include "voxel_sort_dev.h"
 
 namespace {
 
@@ -55,29 +54,8 @@ __global__ __launch_bounds__(256) void k_tofs_tf(const TofsProb* __restrict__ ta
     out[base + i] = o;
 }
 
-// float minimum / maximum into memory (min and max do not depend on the order of arrival)
-__device__ __forceinline__ void atomic_min_f32(float* addr, float v) {
-    int* a = reinterpret_cast<int*>(addr);
-    int old = *a;
-    while (v < __int_as_float(old)) {
-        const int assumed = old;
-        old = atomicCAS(a, assumed, __float_as_int(v));
-        if (old == assumed) break;
-    }
-}
-__device__ __forceinline__ void atomic_max_f32(float* addr, float v) {
-    int* a = reinterpret_cast<int*>(addr);
-    int old = *a;
-    while (v > __int_as_float(old)) {
-        const int assumed = old;
-        old = atomicCAS(a, assumed, __float_as_int(v));
-        if (old == assumed) break;
-    }
-}
-
-// bounding box of every problem's transformed cloud: box[6 p ..] = min xyz, max xyz (the host uploads +inf / -inf)
-__global__ __launch_bounds__(256) void k_tofs_box(const TofsProb* __restrict__ tab, const float4* __restrict__ pts, float* __restrict__ box) {
-    __shared__ float s[6][4];
+// bounding box of every problem's transformed cloud: box[6 p ..] = min xyz, max xyz as keys (the host uploads MML_BBOX_EMPTY)
+__global__ __launch_bounds__(256) void k_tofs_box(const TofsProb* __restrict__ tab, const float4* __restrict__ pts, int* __restrict__ box) {
     const int base = tab[blockIdx.y].v_base, n = tab[blockIdx.y].n_velo;
     if ((int)blockIdx.x * 256 >= n) return;  // (the whole workgroup)
     float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
@@ -90,27 +68,7 @@ __global__ __launch_bounds__(256) void k_tofs_box(const TofsProb* __restrict__ t
         mx[1] = fmaxf(mx[1], p.y);
         mx[2] = fmaxf(mx[2], p.z);
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int c = 0; c < 3; ++c) {
-        for (int o = 32; o > 0; o >>= 1) {
-            mn[c] = fminf(mn[c], __shfl_xor(mn[c], o));
-            mx[c] = fmaxf(mx[c], __shfl_xor(mx[c], o));
-        }
-        if (lane == 0) {
-            s[c][wave] = mn[c];
-            s[3 + c][wave] = mx[c];
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int c = threadIdx.x;
-        float v = s[c][0];
-        for (int w = 1; w < 4; ++w) v = (c < 3) ? fminf(v, s[c][w]) : fmaxf(v, s[c][w]);
-        if (c < 3)
-            atomic_min_f32(box + 6 * (size_t)blockIdx.y + c, v);
-        else
-            atomic_max_f32(box + 6 * (size_t)blockIdx.y + c, v);
-    }
+    mml_bbox_block_reduce(mn, mx, box + 6 * (size_t)blockIdx.y);
 }
 
 // sort key of every point: problem << 32 | cell (the cell mapping of map_assoc.hip's k_cell_keys), value: its index in the problem
@@ -329,13 +287,14 @@ void tofs_choose_grid(const float* box, int m, MmlGrid& g) {
 struct TofsIo {
     MmlCarve<256> c;
     MmlField<TofsProb> tab;
-    MmlField<float> tf, box;
+    MmlField<float> tf;
+    MmlField<int> box;  // six keys per problem (mml_fkey)
     MmlField<long long> woff;
     MmlField<TofsBest> best;
     MmlField<double> err;
     size_t bytes;
     TofsIo(size_t n, size_t n_win)
-        : tab(c.take<TofsProb>(n)), tf(c.take<float>(16 * n)), box(c.take<float>(6 * n)), woff(c.take<long long>(n + 1)), best(c.take<TofsBest>(n)),
+        : tab(c.take<TofsProb>(n)), tf(c.take<float>(16 * n)), box(c.take<int>(6 * n)), woff(c.take<long long>(n + 1)), best(c.take<TofsBest>(n)),
           err(c.take<double>(n_win)), bytes(c.bytes()) {}
 };
 // big block (device only): 100 bytes per Velodyne point (cells included), 16 per Livox point, the sort's scratch
@@ -424,9 +383,7 @@ int tofs_run(mml_ctx* ctx, const char* who, int n, const float* velo_xyz, const 
     std::vector<TofsBest> best((size_t)n, TofsBest{1000000.0, -1, 0});
     const double* h_err = nullptr;
     if (nl > 0) {  // (no Livox point in the whole call: nothing to search)
-        size_t sort_bytes = 0;
-        MML_HIP(rocprim::radix_sort_pairs(nullptr, sort_bytes, (unsigned long long*)nullptr, (unsigned long long*)nullptr, (unsigned*)nullptr,
-                                          (unsigned*)nullptr, nv, 0, 64, MML_STREAM(ctx)));
+        const size_t sort_bytes = mml_sort_pairs_bytes<unsigned long long>(nv, 64, MML_STREAM(ctx));
         const TofsIo io((size_t)n, n_win);
         const TofsBig big(nv, nl, n_cells, sort_bytes);
         MmlTofsDev* d = mml_side<MmlTofsDev>(ctx, MML_SIDE_TIME_OFFSET);
@@ -437,7 +394,8 @@ int tofs_run(mml_ctx* ctx, const char* who, int n, const float* velo_xyz, const 
         hipStream_t s = MML_STREAM(ctx);
         char *h = d->io.h, *g = d->io.d, *b = d->big.d;
         TofsProb* h_tab = io.tab.in(h);
-        float* h_box = io.box.in(h);
+        int* h_box = io.box.in(h);
+        const int empty_box[6] = MML_BBOX_EMPTY;
         long long* h_woff = io.woff.in(h);
         const TofsProb* d_tab = io.tab.in(g);
         const float* d_tf = tf ? io.tf.in(g) : nullptr;
@@ -457,10 +415,7 @@ int tofs_run(mml_ctx* ctx, const char* who, int n, const float* velo_xyz, const 
             P.e_base = h_woff[i];
             P.n_win = nwin[i];
             h_woff[i + 1] = h_woff[i] + nwin[i];
-            for (int c = 0; c < 3; ++c) {
-                h_box[6 * i + c] = INFINITY;
-                h_box[6 * i + 3 + c] = -INFINITY;
-            }
+            memcpy(h_box + 6 * i, empty_box, sizeof(empty_box));
         }
         const unsigned by = (unsigned)n, bx_v = (unsigned)((max_v + 255) / 256);
         {   // host synchronisation 1 of 2: the boxes of all problems in one copy
@@ -484,7 +439,9 @@ int tofs_run(mml_ctx* ctx, const char* who, int n, const float* velo_xyz, const 
         for (int i = 0; i < n; ++i) {
             TofsProb& P = h_tab[i];
             if (P.n_velo == 0) continue;
-            tofs_choose_grid(h_box + 6 * i, P.n_velo, P.g);
+            float box[6];
+            for (int c = 0; c < 6; ++c) box[c] = mml_funkey(h_box[6 * i + c]);
+            tofs_choose_grid(box, P.n_velo, P.g);
             P.g.m = P.n_velo;
             P.g.pts = d_pts + P.v_base;
             P.g.cell_start = big.cells.in(b) + cell_at;
@@ -497,10 +454,9 @@ int tofs_run(mml_ctx* ctx, const char* who, int n, const float* velo_xyz, const 
             hipLaunchKernelGGL(k_tofs_keys, dim3(bx_v, by), dim3(256), 0, s, d_tab, d_v4, d_keys, d_vals);
             // ONE stable sort over all Velodyne points; with one problem the high word is zero and the cell bits are enough
             const int end_bit = n == 1 ? bits_for(max_cells) : 32 + bits_for(n);
-            size_t need = 0;
-            MML_HIP(rocprim::radix_sort_pairs(nullptr, need, d_keys, d_keys2, d_vals, d_vals2, nv, 0, end_bit, s));
-            if (need > sort_bytes) return mml_refuse(ctx, MML_ERR_HIP, "%s: the sort asks for %zu bytes of scratch, %zu were reserved", who, need, sort_bytes);
-            MML_HIP(rocprim::radix_sort_pairs(big.sort.in(b), need, d_keys, d_keys2, d_vals, d_vals2, nv, 0, end_bit, s));
+            MmlTmpSpan sort_tmp{big.sort.in(b), sort_bytes};  // (carved out of the big block: nothing is allocated between the launches)
+            rc = mml_sort_pairs(ctx, sort_tmp, d_keys, d_keys2, d_vals, d_vals2, nv, end_bit, s);
+            if (rc != MML_OK) return rc;
             hipLaunchKernelGGL(k_tofs_gather, dim3(bx_v, by), dim3(256), 0, s, d_tab, d_v4, d_vals2, d_pts);
             hipLaunchKernelGGL(k_tofs_cell_start, dim3((unsigned)((max_cells + 1 + 255) / 256), by), dim3(256), 0, s, d_tab, d_keys2);
             hipLaunchKernelGGL(k_tofs_nn1, dim3((unsigned)((max_l + 255) / 256), by), dim3(256), 0, s, d_tab, d_lxyz, d_nn);

@@ -9,6 +9,8 @@
 
 #include "mml_internal.h"
 #include "undistort_dev.h"
+#define MML_VOXEL_ARITH_ONLY  // mml_voxel_grid_overflows alone
+#include "voxel_sort_dev.h"
 
 namespace {
 using namespace mml_und;
@@ -387,6 +389,7 @@ __device__ __forceinline__ void voxel_sort(const VoxelArgs& A, VoxelLds<VX_THREA
     }
     VX_MARK(5);
     // 2. voxel index (PCL 1.8.1 voxel_grid.hpp applyFilter): inverse leaf in float, floor, int, min_b offset
+    //    (restates MmlVoxGrid of voxel_sort_dev.h inside this kernel's register budget)
     const float inv = 1.0f / leaf;
     int min_b[3], div_b[3];
     for (int c = 0; c < 3; ++c) {

@@ -10,7 +10,7 @@ PREFIX = [
     ("k_stencil_break", "stencil"), ("k_stencil_redo", "stencil"), ("k_stencil", "stencil"), ("k_queue_prefix", "stencil"),
     ("k_select", "select"), ("k_crop", "crop_compact"), ("k_livox_extrinsic", "livox_extrinsic"),
     ("k_undistort_prep", "undistort"), ("k_undistort", "undistort"),
-    ("k_voxel", "voxel_downsample"), ("k_seg_", "voxel_downsample"),
+    ("k_voxel", "voxel_downsample"), ("k_seg_", "voxel_downsample"), ("k_run_heads", "voxel_downsample"),
     ("k_assoc_prefix", "associate"), ("k_associate_fit_all", "associate_fit"), ("k_associate_fit", "associate_far"),
     ("k_associate_hard", "associate_far"), ("k_associate", "associate"), ("k_assoc_stats", "assoc_stats"),
     ("k_solve", "solve"), ("k_window_round", "solve"), ("k_window_export", "solve"),
