@@ -313,6 +313,45 @@ int mml_union_assemble(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int co
  * front < 0 or tail < front, decreasing stamps; MML_ERR_STATE for a time-order violation in [front, tail). */
 int mml_union_plan(const uint64_t* S, long front, long tail, uint64_t hs, int count, const uint64_t* stamps,
                    int max_livox_points, mml_union_frame* out);
+
+/* The aligner's OTHER live mode: once the time offset is known -- estimated by mml_time_offset_search (:1161) or given
+ * (:178-184) -- velo_cloud_handler (:513-551) calls the one-stamp overload pub_horipoints_given_stamp(start_stamp, msg)
+ * (:872-1009), which cuts a fixed COUNT of points instead of an interval.  This is that overload for `count` Velodyne frames in
+ * one call, on the same stream.  Frame i has the stamp t = starts[i] (absolute ns: the Velodyne header stamp minus the time
+ * offset, formed by the caller in uint64 as :520 does), c = sliced_points (_offset_search_sliced_points) and fills slot
+ * first_slot + i.  With q the front, T the tail and A[k] = hs + S[k]:
+ *   q == T: EMPTY (:874-878), the front stays.
+ *   The walk of :896-918 erases front points while A[front] < t and more than one point is queued.  Let L be the first k in
+ *   [q, T) with A[k] >= t, else T.  L < T: the front becomes L.  L == T: the walk stops with one point left and returns false:
+ *   NOT_REACHED -- and, unlike in mml_union_assemble, the queue HAS changed: front_after = T - 1, begin = end = T - 1,
+ *   n_livox = 0.
+ *   n = min(c, T - L) >= 1 points L .. L + n - 1 go out (:946-980): x, y, z, reflectivity, tag, line unchanged, _pad = 0,
+ *   offset_time = (uint32)(A[k] - t), the truncating assignment of :955/:964.  All of them are erased: OK, begin = L,
+ *   end = front_after = L + n.  There is no keep-100 in this overload.
+ *   Velodyne part: exactly that of mml_union_assemble (tf is _velo_hori_tf_matrix, :528); a frame whose status is not OK still
+ *   gets it, with zero Livox points.
+ * The overload has no undefined read (the front() at :912 and :984 always has an element), so there is no NO_POINTS, and no
+ * OVERFLOW: sliced_points > max_livox_points is refused.  Which Velodyne frame goes with which cut is the caller's business:
+ * rows velo_offsets[i] .. pair with starts[i] (the reference's own handler erases its Velodyne queue twice, :1005 and :543;
+ * see INTEGRATION.md).
+ * Slots afterwards, batch equivalence (count frames in one call equal count calls of one frame to the byte, in slots, rows and
+ * the stream afterwards), the checks before any device work and MML_ERR_STATE are those of mml_union_assemble, with `starts`
+ * (count entries, must not decrease) in the place of `stamps`; in addition MML_ERR_INVALID for sliced_points < 1 and
+ * MML_ERR_CAPACITY for sliced_points > max_livox_points.  The two assemble calls may be mixed on one stream.
+ * ONE host synchronisation and two kernel launches per call whatever count is: the stages "union_offset_plan" (count binary
+ * searches, the recurrence q' = min(max(q, L_i) + c, T) -- T - 1 for NOT_REACHED -- by one lane out of LDS, the rows and the
+ * slots' counts) and "union_gather" (the kernel of mml_union_assemble, unchanged).  The host front advances to the last row's
+ * front_after, which moves for NOT_REACHED too.  Staging is shared with mml_union_assemble. */
+int mml_union_assemble_offset(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int count,
+                              const uint64_t* starts /* count, absolute ns, must not decrease */, int sliced_points,
+                              const float* velo_xyzi, const int* velo_offsets /* count + 1 */,
+                              const float* tf /* 16 or NULL */, mml_union_frame* out /* count */);
+/* Host only, no context: the rows mml_union_assemble_offset returns for the host stamp array S (as mml_union_plan reads it).
+ * MML_ERR_INVALID for count outside 1 .. MML_UNION_BATCH_MAX, a NULL pointer, front < 0 or tail < front, decreasing starts,
+ * sliced_points < 1; MML_ERR_STATE for a time-order violation in [front, tail). */
+int mml_union_plan_offset(const uint64_t* S, long front, long tail, uint64_t hs, int count, const uint64_t* starts,
+                          int sliced_points, mml_union_frame* out);
+
 /* Test hook like mml_libm_f32: a slot's raw input as it stands -- what the upload entry points or mml_union_assemble put
  * there: n_velo rows of x, y, z, intensity and n_livox records.  Either buffer may be NULL with capacity 0 to query the
  * counts; MML_ERR_CAPACITY when a capacity is below its count.  Synchronises. */

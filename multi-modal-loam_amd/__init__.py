@@ -283,6 +283,11 @@ def lib():
             L.mml_union_assemble.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
             L.mml_union_plan.restype = C.c_int
             L.mml_union_plan.argtypes = [C.c_void_p, C.c_long, C.c_long, C.c_uint64, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        if hasattr(L, "mml_union_assemble_offset"):
+            L.mml_union_assemble_offset.restype = C.c_int
+            L.mml_union_assemble_offset.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4
+            L.mml_union_plan_offset.restype = C.c_int
+            L.mml_union_plan_offset.argtypes = [C.c_void_p, C.c_long, C.c_long, C.c_uint64, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
             L.mml_scan_raw_download.restype = C.c_int
             L.mml_scan_raw_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         if hasattr(L, "mml_velo_fov_select_batch"):
@@ -480,6 +485,21 @@ def union_plan(S, front, tail, hs, stamps, max_livox_points):
     return rc, rows[:max(count, 0)]
 
 
+def union_plan_offset(S, front, tail, hs, starts, sliced_points):
+    """mml_union_plan_offset: the frame rows mml_union_assemble_offset returns, on the host alone, for the stamp array S (as
+    union_plan reads it).  starts: one stamp per frame in absolute nanoseconds; each frame takes up to sliced_points points from the
+    first one at or after its stamp.  Returns (code, rows UNION_FRAME_DTYPE[count]); the rows are filled only when code == MML_OK."""
+    Sa = np.ascontiguousarray(S, dtype=np.uint64)
+    st = np.ascontiguousarray(starts, dtype=np.uint64)
+    count = len(st)
+    if tail > len(Sa):
+        raise ValueError("tail = %d lies beyond the %d stamps given" % (tail, len(Sa)))
+    rows = np.zeros(max(count, 1), UNION_FRAME_DTYPE)
+    rc = lib().mml_union_plan_offset(_p(Sa) if len(Sa) else None, C.c_long(front), C.c_long(tail), C.c_uint64(int(hs)), C.c_int(count),
+                                     _p(st) if count else None, C.c_int(sliced_points), _p(rows))
+    return rc, rows[:count]
+
+
 class LivoxStreamState(C.Structure):
     _fields_ = [("start_stamp", C.c_uint64), ("front", C.c_long), ("tail", C.c_long), ("disorder", C.c_long)]
 
@@ -659,7 +679,7 @@ class Context:
         """velo_fov_select(frames, ctx=self): the aligner's FOV selection on the device."""
         return velo_fov_select(frames, ctx=self)
 
-    # ---- the aligner node's frame assembly (unionLidarsAligner.cpp:343-364, :736-868) ----
+    # ---- the aligner node's frame assembly (unionLidarsAligner.cpp:343-364, :736-868; time-offset mode :513-551, :872-1009) ----
     def livox_stream(self, capacity):
         """A LivoxStream of `capacity` points on this context."""
         return LivoxStream(self, capacity)
@@ -680,6 +700,24 @@ class Context:
         rows = np.zeros(max(count, 1), UNION_FRAME_DTYPE)
         self._ck(lib().mml_union_assemble(self._h, stream._h, C.c_int(first_slot), C.c_int(count), _p(st),
                                           _p(velo) if len(velo) else None, _p(vo), _p(t), _p(rows)))
+        return rows[:count]
+
+    def union_assemble_offset(self, stream, first_slot, starts, sliced_points, velo_list, tf=None):
+        """mml_union_assemble_offset, the aligner's time-offset mode (unionLidarsAligner.cpp:513-551, :872-1009): frame i takes up to
+        sliced_points points of `stream` from the first one at or after starts[i] (absolute ns: Velodyne stamp - time offset) into
+        slot first_slot + i, together with velo_list[i] as in union_assemble.  Returns the frames' rows (UNION_FRAME_DTYPE)."""
+        st = np.ascontiguousarray(starts, dtype=np.uint64)
+        count = len(st)
+        if len(velo_list) != count:
+            raise ValueError("%d Velodyne clouds for %d frames" % (len(velo_list), count))
+        vs = [_f32(v).reshape(-1, 4) for v in velo_list]
+        vo = np.zeros(count + 1, np.int32)
+        vo[1:] = np.cumsum([len(v) for v in vs])
+        velo = np.ascontiguousarray(np.concatenate(vs + [np.zeros((0, 4), np.float32)]))
+        t = np.ascontiguousarray(np.asarray(tf, np.float32).reshape(16)) if tf is not None else None
+        rows = np.zeros(max(count, 1), UNION_FRAME_DTYPE)
+        self._ck(lib().mml_union_assemble_offset(self._h, stream._h, C.c_int(first_slot), C.c_int(count), _p(st) if count else None,
+                                                 C.c_int(sliced_points), _p(velo) if len(velo) else None, _p(vo), _p(t), _p(rows)))
         return rows[:count]
 
     def scan_raw_download(self, slot):

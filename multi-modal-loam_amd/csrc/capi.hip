@@ -382,6 +382,15 @@ int mml_union_assemble(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int co
     return mml_union_run(ctx, s, first_slot, count, stamps, velo_xyzi, velo_offsets, tf, out);
 }
 
+int mml_union_assemble_offset(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int count, const uint64_t* starts, int sliced_points,
+                              const float* velo_xyzi, const int* velo_offsets, const float* tf, mml_union_frame* out) {
+    if (!ctx) return MML_ERR_INVALID;
+    const int rc = mml_union_offset_check(ctx, s, first_slot, count, starts, sliced_points, velo_xyzi, velo_offsets, out);
+    if (rc != MML_OK) return rc;
+    CHECK_SLOTS(first_slot, count);
+    return mml_union_offset_run(ctx, s, first_slot, count, starts, sliced_points, velo_xyzi, velo_offsets, tf, out);
+}
+
 int mml_scan_raw_download(mml_ctx* ctx, int slot, float* velo_xyzi, int cap_velo, mml_livox_point* livox, int cap_livox, int* n_velo,
                           int* n_livox) {
     CHECK_SLOTS(slot, 1);

@@ -1,6 +1,7 @@
 // livox_stream.hip -- the aligner node's steady-state work (unionLidarsAligner.cpp) on the device:
 //   :736-763  transform_hori_timestamp      mml_livox_stream_push*: k_stream_stamp / k_stream_decode
 //   :766-868  pub_horipoints_given_stamp    mml_union_assemble: k_union_plan (which points), k_union_gather (the records)
+//   :872-1009 the same, one-stamp overload  mml_union_assemble_offset: k_union_plan_offset, k_union_gather
 //   :350-352  pcl::transformPointCloud      k_union_gather's Velodyne blocks (the expression of k_tofs_tf, time_offset.hip)
 // The stream is a flat array of 20-byte records (5 dwords each) and a flat array of 64-bit stamps; point i (counted over everything
 // ever pushed) sits at element i - base.  The frame recurrence itself is union_plan.h, shared with the host's mml_union_plan.
@@ -126,6 +127,47 @@ __global__ __launch_bounds__(256) void k_union_plan(const uint64_t* __restrict__
     }
 }
 
+// The same for the one-stamp overload (:872-1009, mml_union_assemble_offset): frame i takes up to `sliced` points from the
+// first one at or after starts[i].  The three phases of k_union_plan with one search per frame (a round of c frames needs c, not
+// c + 1: a frame has no end stamp) and mml_union_resolve_offset as the recurrence.  The recurrence is a clamp-add
+// (q' = min(max(q, lb) + sliced, tail)), so a wave scan could replace lane 0's loop; at about 40 cycles per frame that loop is
+// shorter than the Velodyne copy the launch waits behind, and the serial form is the one the host runs too.
+__global__ __launch_bounds__(256) void k_union_plan_offset(const uint64_t* __restrict__ S, long base, long q0, long tail, uint64_t hs, int count,
+                                                           const uint64_t* __restrict__ starts, const int* __restrict__ voff, int first_slot,
+                                                           int sliced, const unsigned long long* __restrict__ disorder,
+                                                           mml_union_frame* __restrict__ rows, unsigned long long* __restrict__ verdict,
+                                                           int* __restrict__ n_in) {
+    __shared__ long s_lb[UNION_CHUNK];
+    __shared__ long s_q[UNION_CHUNK + 1];
+    const unsigned long long bad = *disorder;
+    if (threadIdx.x == 0) *verdict = bad;
+    if (bad) return;  // (the whole workgroup)
+    if (threadIdx.x == 0) s_q[0] = q0;
+    for (int c0 = 0; c0 < count; c0 += UNION_CHUNK) {
+        const int c = count - c0 < UNION_CHUNK ? count - c0 : UNION_CHUNK;
+        for (int t = threadIdx.x; t < c; t += 256) s_lb[t] = mml_union_lower_bound(S, base, q0, tail, hs, starts[c0 + t]);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            long q = s_q[0];
+            mml_union_frame f;
+            for (int t = 0; t < c; ++t) {
+                q = mml_union_resolve_offset(q, tail, s_lb[t], sliced, &f);
+                s_q[t + 1] = q;
+            }
+        }
+        __syncthreads();
+        for (int t = threadIdx.x; t < c; t += 256) {
+            mml_union_frame f;
+            mml_union_resolve_offset(s_q[t], tail, s_lb[t], sliced, &f);
+            rows[c0 + t] = f;
+            n_in[2 * (size_t)(first_slot + c0 + t)] = voff[c0 + t + 1] - voff[c0 + t];
+            n_in[2 * (size_t)(first_slot + c0 + t) + 1] = f.n_livox;  // (0 unless OK)
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) s_q[0] = s_q[c];
+    }
+}
+
 // The records.  Grid (2 * UNION_GATHER_BLOCKS at most, frame): blocks [0, gl) of a frame copy its Livox points, the others
 // transform its Velodyne rows.
 //   Livox: the frame's source [begin, end) is contiguous, so it is copied as a stream of dwords, consecutive lanes on consecutive
@@ -239,26 +281,36 @@ int stream_push(mml_livox_stream* s, const char* who, uint64_t timebase, const v
     return MML_OK;
 }
 
-int plan_args_ok(int count, const uint64_t* stamps) {
-    if (count < 1 || count > MML_UNION_BATCH_MAX || !stamps) return 0;
-    for (int i = 0; i < count; ++i)
-        if (stamps[i + 1] < stamps[i]) return 0;
+// What the two assemble calls differ in.  The interval mode (sliced == 0) cuts frame i at [times[i], times[i + 1]): count + 1
+// times; the offset mode takes up to `sliced` points from times[i]: count times.
+struct UnionMode {
+    const char* who;
+    const uint64_t* times;
+    int sliced;
+    int n_times(int count) const { return sliced ? count : count + 1; }
+};
+
+int plan_args_ok(int count, const uint64_t* times, int n_times) {
+    if (count < 1 || count > MML_UNION_BATCH_MAX || !times) return 0;
+    for (int i = 0; i + 1 < n_times; ++i)
+        if (times[i + 1] < times[i]) return 0;
     return 1;
 }
 
-}  // namespace
-
-// The checks of mml_union_assemble that need no device (capi.hip calls them before it touches the slots).
-int mml_union_check(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int count, const uint64_t* stamps, const float* velo_xyzi,
-                    const int* vo, mml_union_frame* out) {
-    const char* who = "mml_union_assemble";
+// The checks of the assemble calls that need no device.
+int union_check(mml_ctx* ctx, const UnionMode& m, mml_livox_stream* s, int first_slot, int count, const float* velo_xyzi, const int* vo,
+                mml_union_frame* out) {
+    const char* who = m.who;
     if (count < 1 || count > MML_UNION_BATCH_MAX) return mml_refuse(ctx, MML_ERR_INVALID, "%s: count = %d is outside 1 .. %d", who, count, MML_UNION_BATCH_MAX);
     if (first_slot < 0 || first_slot + count > ctx->B) return mml_refuse(ctx, MML_ERR_INVALID, "%s: slot range out of bounds", who);
-    if (!s || !stamps || !vo || !out) return mml_refuse(ctx, MML_ERR_INVALID, "%s: a null argument", who);
+    if (!s || !m.times || !vo || !out) return mml_refuse(ctx, MML_ERR_INVALID, "%s: a null argument", who);
     if (s->ctx != ctx) return mml_refuse(ctx, MML_ERR_INVALID, "%s: the stream belongs to another context", who);
     if (vo[0] < 0) return mml_refuse(ctx, MML_ERR_INVALID, "%s: frame 0: a negative offset", who);
+    const int n_times = m.n_times(count);
     for (int i = 0; i < count; ++i) {
-        if (stamps[i + 1] < stamps[i]) return mml_refuse(ctx, MML_ERR_INVALID, "%s: frame %d ends before it starts (stamps must not decrease)", who, i);
+        if (i + 1 < n_times && m.times[i + 1] < m.times[i])
+            return mml_refuse(ctx, MML_ERR_INVALID, m.sliced ? "%s: frame %d starts after the next one (starts must not decrease)"
+                                                             : "%s: frame %d ends before it starts (stamps must not decrease)", who, i);
         if (vo[i + 1] < vo[i]) return mml_refuse(ctx, MML_ERR_INVALID, "%s: frame %d: velo_offsets must not decrease", who, i);
     }
     for (int i = 0; i < count; ++i)
@@ -269,21 +321,21 @@ int mml_union_check(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int count
     return MML_OK;
 }
 
-// The device part, after the checks above and CHECK_SLOTS.
-int mml_union_run(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int count, const uint64_t* stamps, const float* velo_xyzi, const int* vo,
-                  const float* tf, mml_union_frame* out) {
+// The device part of both assemble calls: one io block down, the mode's plan kernel, the gather, rows and verdict up.
+int union_run(mml_ctx* ctx, const UnionMode& m, mml_livox_stream* s, int first_slot, int count, const float* velo_xyzi, const int* vo,
+              const float* tf, mml_union_frame* out) {
     const size_t nv = (size_t)(vo[count] - vo[0]);
     int max_nv = 0;
     for (int i = 0; i < count; ++i) max_nv = vo[i + 1] - vo[i] > max_nv ? vo[i + 1] - vo[i] : max_nv;
     const UnionIo io((size_t)count);
     MmlUnionDev* u = mml_side<MmlUnionDev>(ctx, MML_SIDE_UNION);
     if (u->io.reserve(ctx, io.bytes) || u->velo.reserve(ctx, nv ? nv : 1)) {
-        ctx->err = "mml_union_assemble: the staging block could not be grown: " + ctx->err;
+        ctx->err = std::string(m.who) + ": the staging block could not be grown: " + ctx->err;
         return MML_ERR_HIP;
     }
     hipStream_t st = MML_STREAM(ctx);
     char *h = u->io.h, *g = u->io.d;
-    memcpy(io.stamps.in(h), stamps, io.stamps.bytes());
+    memcpy(io.stamps.in(h), m.times, sizeof(uint64_t) * (size_t)m.n_times(count));  // (the field has room for count + 1)
     memcpy(io.voff.in(h), vo, io.voff.bytes());
     if (tf) memcpy(io.tf.in(h), tf, io.tf.bytes());
     const uint64_t* d_stamps = io.stamps.in(g);
@@ -291,18 +343,23 @@ int mml_union_run(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int count, 
     const float* d_tf = tf ? io.tf.in(g) : nullptr;
     mml_union_frame* d_rows = io.rows.in(g);
     unsigned long long* d_verdict = io.verdict.in(g);
-    // a frame holds at most max_livox_points points, and no more than the queue does
+    // a frame holds at most max_livox_points points (the offset mode: sliced, which is no more), and no more than the queue does
     const long live = s->tail - s->front;
-    const long most = live < (long)ctx->cfg.max_livox_points ? live : (long)ctx->cfg.max_livox_points;
+    const long room = m.sliced ? (long)m.sliced : (long)ctx->cfg.max_livox_points;
+    const long most = live < room ? live : room;
     int gl = (int)((5 * most + 255) / 256), gv = (max_nv + 255) / 256;
     gl = gl < 1 ? 1 : (gl > UNION_GATHER_BLOCKS ? UNION_GATHER_BLOCKS : gl);
     gv = gv > UNION_GATHER_BLOCKS ? UNION_GATHER_BLOCKS : gv;
     {
-        MmlStageScope t(ctx, "union_plan");
+        MmlStageScope t(ctx, m.sliced ? "union_offset_plan" : "union_plan");
         MML_HIP(hipMemcpyAsync(g, h, io.down_bytes, hipMemcpyHostToDevice, st));
         if (nv) MML_HIP(hipMemcpyAsync(u->velo.d, velo_xyzi + 4 * (size_t)vo[0], sizeof(float4) * nv, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(k_union_plan, dim3(1), dim3(256), 0, st, s->stamp[s->cur], s->base, s->front, s->tail, s->hs, count, d_stamps, d_voff,
-                           first_slot, ctx->cfg.max_livox_points, s->d_disorder, d_rows, d_verdict, ctx->d_n_in);
+        if (m.sliced)
+            hipLaunchKernelGGL(k_union_plan_offset, dim3(1), dim3(256), 0, st, s->stamp[s->cur], s->base, s->front, s->tail, s->hs, count, d_stamps,
+                               d_voff, first_slot, m.sliced, s->d_disorder, d_rows, d_verdict, ctx->d_n_in);
+        else
+            hipLaunchKernelGGL(k_union_plan, dim3(1), dim3(256), 0, st, s->stamp[s->cur], s->base, s->front, s->tail, s->hs, count, d_stamps, d_voff,
+                               first_slot, ctx->cfg.max_livox_points, s->d_disorder, d_rows, d_verdict, ctx->d_n_in);
         MML_HIP(hipGetLastError());
     }
     {   // the call's ONE host synchronisation: the rows and the verdict in one copy
@@ -317,16 +374,43 @@ int mml_union_run(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int count, 
     unsigned long long bad = 0;
     memcpy(&bad, io.verdict.in(h), sizeof(bad));
     if (bad)
-        return mml_refuse(ctx, MML_ERR_STATE, "mml_union_assemble: the stream holds %llu points older than the point before them; nothing was written",
-                          bad);
+        return mml_refuse(ctx, MML_ERR_STATE, "%s: the stream holds %llu points older than the point before them; nothing was written", m.who, bad);
     memcpy(out, io.rows.in(h), io.rows.bytes());
-    s->front = out[count - 1].front_after;
+    s->front = out[count - 1].front_after;  // (the offset mode moves it for NOT_REACHED too)
     for (int i = 0; i < count; ++i) {
         ctx->h_n_in[2 * (first_slot + i)] = vo[i + 1] - vo[i];
         ctx->raw_extracted[first_slot + i] = 0;
         ctx->h_n_in[2 * (first_slot + i) + 1] = out[i].status == MML_UNION_OK ? out[i].n_livox : 0;
     }
     return MML_OK;
+}
+
+}  // namespace
+
+// mml_union_assemble: the checks that need no device (capi.hip calls them before it touches the slots) ...
+int mml_union_check(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int count, const uint64_t* stamps, const float* velo_xyzi,
+                    const int* vo, mml_union_frame* out) {
+    return union_check(ctx, UnionMode{"mml_union_assemble", stamps, 0}, s, first_slot, count, velo_xyzi, vo, out);
+}
+// ... and the device part, after them and CHECK_SLOTS.
+int mml_union_run(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int count, const uint64_t* stamps, const float* velo_xyzi, const int* vo,
+                  const float* tf, mml_union_frame* out) {
+    return union_run(ctx, UnionMode{"mml_union_assemble", stamps, 0}, s, first_slot, count, velo_xyzi, vo, tf, out);
+}
+// The same pair for mml_union_assemble_offset.
+int mml_union_offset_check(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int count, const uint64_t* starts, int sliced_points,
+                           const float* velo_xyzi, const int* vo, mml_union_frame* out) {
+    const char* who = "mml_union_assemble_offset";
+    if (sliced_points < 1) return mml_refuse(ctx, MML_ERR_INVALID, "%s: sliced_points = %d is below 1", who, sliced_points);
+    const int rc = union_check(ctx, UnionMode{who, starts, sliced_points}, s, first_slot, count, velo_xyzi, vo, out);
+    if (rc != MML_OK) return rc;
+    if (sliced_points > ctx->cfg.max_livox_points)
+        return mml_refuse(ctx, MML_ERR_CAPACITY, "%s: sliced_points = %d exceeds max_livox_points = %d", who, sliced_points, ctx->cfg.max_livox_points);
+    return MML_OK;
+}
+int mml_union_offset_run(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int count, const uint64_t* starts, int sliced_points,
+                         const float* velo_xyzi, const int* vo, const float* tf, mml_union_frame* out) {
+    return union_run(ctx, UnionMode{"mml_union_assemble_offset", starts, sliced_points}, s, first_slot, count, velo_xyzi, vo, tf, out);
 }
 
 extern "C" int mml_livox_stream_create(mml_ctx* ctx, long capacity_points, mml_livox_stream** out) {
@@ -397,7 +481,7 @@ extern "C" int mml_livox_stream_state_get(mml_livox_stream* s, mml_livox_stream_
 
 extern "C" int mml_union_plan(const uint64_t* S, long front, long tail, uint64_t hs, int count, const uint64_t* stamps, int max_livox_points,
                               mml_union_frame* out) {
-    if (!out || front < 0 || tail < front || (tail > front && !S) || !plan_args_ok(count, stamps)) return MML_ERR_INVALID;
+    if (!out || front < 0 || tail < front || (tail > front && !S) || !plan_args_ok(count, stamps, count + 1)) return MML_ERR_INVALID;
     for (long i = front + 1; i < tail; ++i)
         if (hs + S[i] < hs + S[i - 1]) return MML_ERR_STATE;
     long q = front;
@@ -407,5 +491,16 @@ extern "C" int mml_union_plan(const uint64_t* S, long front, long tail, uint64_t
         q = mml_union_resolve(q, tail, lbs, lbe, max_livox_points, &out[i]);
         lbs = lbe;
     }
+    return MML_OK;
+}
+
+extern "C" int mml_union_plan_offset(const uint64_t* S, long front, long tail, uint64_t hs, int count, const uint64_t* starts, int sliced_points,
+                                     mml_union_frame* out) {
+    if (!out || front < 0 || tail < front || (tail > front && !S) || sliced_points < 1 || !plan_args_ok(count, starts, count)) return MML_ERR_INVALID;
+    for (long i = front + 1; i < tail; ++i)
+        if (hs + S[i] < hs + S[i - 1]) return MML_ERR_STATE;
+    long q = front;
+    for (int i = 0; i < count; ++i)
+        q = mml_union_resolve_offset(q, tail, mml_union_lower_bound(S, 0, front, tail, hs, starts[i]), sliced_points, &out[i]);
     return MML_OK;
 }

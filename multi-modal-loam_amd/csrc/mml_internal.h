@@ -400,6 +400,11 @@ int mml_union_check(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int count
                     const int* velo_offsets, mml_union_frame* out);
 int mml_union_run(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int count, const uint64_t* stamps, const float* velo_xyzi,
                   const int* velo_offsets, const float* tf, mml_union_frame* out);
+// the same pair for mml_union_assemble_offset
+int mml_union_offset_check(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int count, const uint64_t* starts, int sliced_points,
+                           const float* velo_xyzi, const int* velo_offsets, mml_union_frame* out);
+int mml_union_offset_run(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int count, const uint64_t* starts, int sliced_points,
+                         const float* velo_xyzi, const int* velo_offsets, const float* tf, mml_union_frame* out);
 int mml_launch_detect_line(mml_ctx* ctx, int n, uint16_t* d_final);
 int mml_launch_raw_lines(mml_ctx* ctx, int first, int count);  // raw_line[] of the slots (ring / line id per raw point), for the GICP refresh
 int mml_launch_linearize(mml_ctx* ctx, int slot, const double* d_x, const double* d_Tbl, double w_tan,

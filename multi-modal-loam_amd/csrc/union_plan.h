@@ -1,5 +1,6 @@
 // union_plan.h -- the frame recurrence of the aligner's pub_horipoints_given_stamp (unionLidarsAligner.cpp:766-868), shared by
 // the host (mml_union_plan) and the device (k_union_plan, livox_stream.hip): the pattern of imu_preint.h and marg_dense.h.
+// At the end of the file: the same for the one-stamp overload (:872-1009), mml_union_plan_offset and k_union_plan_offset.
 //
 // The stream is a queue of points with 64-bit stamps S[i] (nanoseconds after hs, the first message's time base), indexed
 // ABSOLUTELY: i counts every point ever pushed, q is the queue's front, tail one past its last point.  The reference compares
@@ -81,6 +82,38 @@ MML_UNION_HD inline long mml_union_resolve(long q, long tail, long lbs, long lbe
     f->n_livox = n > 2147483647L ? 2147483647 : (int)n;
     f->status = n > (long)max_livox_points ? MML_UNION_OVERFLOW : MML_UNION_OK;
     return after;
+}
+
+// The ONE-STAMP overload of pub_horipoints_given_stamp (:872-1009), which the aligner runs once the time offset is known
+// (:513-551): a fixed count of points from the first one at or after t.  With lb the lower bound of t over [q0, tail) for any
+// front q0 at or before q, the first live point at or after t is L = max(q, lb) (the stream is time-ordered), and:
+//   :874-878  q == tail                                   EMPTY, the front stays
+//   :896-918  the walk erases front points while hs + S[front] < t and more than one point is queued: the front becomes L; with
+//             no point at or after t (L == tail) it stops at the last point and returns false: NOT_REACHED, and the queue HAS
+//             changed, front = tail - 1
+//   :946-980  n = min(sliced, tail - L) points go out and all of them are erased: front = L + n (no keep-100 here)
+// Every front() the overload reads (:912, :984) has an element, so nothing needs a definition: there is no NO_POINTS and, as
+// the caller refuses sliced > max_livox_points up front, no OVERFLOW.  Rows that emit nothing: begin = end = front_after.
+MML_UNION_HD inline long mml_union_resolve_offset(long q, long tail, long lb, int sliced, mml_union_frame* f) {
+    f->n_livox = 0;
+    f->begin = f->end = q;
+    f->front_after = q;
+    if (q == tail) {
+        f->status = MML_UNION_EMPTY;
+        return q;
+    }
+    const long L = lb > q ? lb : q;
+    if (L >= tail) {
+        f->status = MML_UNION_NOT_REACHED;
+        f->begin = f->end = f->front_after = tail - 1;
+        return tail - 1;
+    }
+    const long n = tail - L < (long)sliced ? tail - L : (long)sliced;
+    f->status = MML_UNION_OK;
+    f->begin = L;
+    f->end = f->front_after = L + n;
+    f->n_livox = (int)n;
+    return L + n;
 }
 
 #endif

@@ -791,6 +791,14 @@ inline TimeOffsetResult EstimateTimeOffsetCore(Context& ctx, const float* velo_f
           "mml_time_offset_search");
     return r;
 }
+// What the search ends in (:1146, :1161): _time_offset = velo_stamp - (livox_msg.timebase + livox_msg_offset_vec[best_window]), in
+// uint64 nanoseconds as the reference holds it (it wraps when the Livox clock is ahead; :520 subtracts it again in uint64).
+// offset_of_best_window_point: the merged array's entry at TimeOffsetResult::best_window, offset_time + (timebase - livox_timebase)
+// (:1062-1068).  The frames of the time-offset mode then start at velo_stamp - time_offset_ns(...):
+// LivoxPointQueue::pub_horipoints_given_stamp(start_stamp, sliced_points, ...) below.
+inline uint64_t time_offset_ns(uint64_t velo_stamp, uint64_t livox_timebase, uint64_t offset_of_best_window_point) {
+    return velo_stamp - (livox_timebase + offset_of_best_window_point);
+}
 // EstimateTimeOffsetCore for a list of (Velodyne FOV cloud, merged Livox cloud) pairs in one device call
 // (mml_time_offset_search_batch): every queued velo_fov_vec entry against the merged Livox points, or the searches of a bag's
 // fast-rotation events replayed at once.  velo_fov[i] / livox[i]: packed x, y, z floats; velo_hori_tf: 16 floats used for every
@@ -961,6 +969,32 @@ class LivoxPointQueue {
         check(ctx_.get(), mml_union_assemble(ctx_.get(), s_, first_slot, count, stamps.data(), velo_xyzi, velo_offsets.data(), velo_hori_tf,
                                              frames_.data()),
               "mml_union_assemble");
+        std::vector<bool> ok((size_t)count);
+        for (int i = 0; i < count; ++i) ok[(size_t)i] = frames_[(size_t)i].status == 0;
+        return ok;
+    }
+    // :872-1009 with :513-551, the one-stamp overload the aligner runs once the time offset is known: up to sliced_points
+    // (_offset_search_sliced_points) points from the first one at or after start_stamp (= Velodyne stamp - time offset, :520;
+    // time_offset_ns above) into `slot`, with the Velodyne cloud.  A false return may have erased points (NOT_REACHED leaves one).
+    // The overloads are told apart as the reference's are: by the second argument, uint64_t end stamp or int point count.
+    bool pub_horipoints_given_stamp(uint64_t start_stamp, int sliced_points, const float* velo_xyzi, int n_velo, const float* velo_hori_tf,
+                                    int slot) {
+        const int vo[2] = {0, n_velo};
+        frames_.resize(1);
+        check(ctx_.get(), mml_union_assemble_offset(ctx_.get(), s_, slot, 1, &start_stamp, sliced_points, velo_xyzi, vo, velo_hori_tf, frames_.data()),
+              "mml_union_assemble_offset");
+        return frames_[0].status == 0;
+    }
+    // count such frames in one device call: starts[i] with rows velo_offsets[i] .. velo_offsets[i + 1] - 1 into slot first_slot + i.
+    std::vector<bool> pub_horipoints_given_stamp(const std::vector<uint64_t>& starts, int sliced_points, const float* velo_xyzi,
+                                                 const std::vector<int>& velo_offsets, const float* velo_hori_tf, int first_slot) {
+        if (starts.empty() || velo_offsets.size() != starts.size() + 1)
+            throw std::runtime_error("pub_horipoints_given_stamp: count starts and count + 1 offsets");
+        const int count = (int)starts.size();
+        frames_.resize((size_t)count);
+        check(ctx_.get(), mml_union_assemble_offset(ctx_.get(), s_, first_slot, count, starts.data(), sliced_points, velo_xyzi, velo_offsets.data(),
+                                                    velo_hori_tf, frames_.data()),
+              "mml_union_assemble_offset");
         std::vector<bool> ok((size_t)count);
         for (int i = 0; i < count; ++i) ok[(size_t)i] = frames_[(size_t)i].status == 0;
         return ok;
