@@ -3,7 +3,10 @@
 // with their analytic Jacobians and Huber correction, and the 28-value workgroup reduction.
 //   a17/a18 Cost_NavState_IMU_Line / Cost_NavState_IMU_Plan_Vec (mm-loam/include/utils/ceresfunc.h:397-458, 517-570)
 //   a19     analytic Jacobians replacing ceres::AutoDiffCostFunction<...,6> through Sophus::SO3<Jet>::exp
-//           (include/sophus/so3.hpp:585-622): dP/dt = I, dP/dphi = -[R p_b]x J_l(phi)
+//           (include/sophus/so3.hpp:585-622): dP/dt = I, dP/dphi = -[R p_b]x J_l(phi).  Bound: rows, Jacobians, H, g and cost of
+//           every single factor against the exact (80-digit) derivative of the factor's definition, in first-order rounding units
+//           that carry no negative power of |phi| -- tests/test_lidar_eval.py states them, tests/test_gpu_lidar_eval.py applies
+//           them to these kernels (tests/golden/lidar_eval_kat.npz)
 //   a20     J^T J / J^T r with Ceres' Huber correction (corrector.cc: rho'' <= 0 => scale by sqrt(rho'))
 #pragma once
 #include <math.h>
@@ -64,14 +67,16 @@ __device__ void make_pose(const double* x, const double* T_bl, Pose& P) {
     } else {
         double th = sqrt(th2);
         double half = 0.5 * th;
-        // (sincos: one argument reduction per angle instead of two -- every thread of every solver kernel forms the pose once per pass:
-        //  batch solve 0.228 -> 0.220 ms per 1024 problems, B = 1 solve 0.123 -> 0.118 ms; $MML_POSE_SINCOS was the A/B switch)
-        double sh, ch, st, ct;
+        // (sincos for the half angle: one argument reduction for its sine and cosine)
+        double sh, ch;
         sincos(half, &sh, &ch);
-        sincos(th, &st, &ct);
+        const double st = sin(th);
         imag = sh / th;
         real = ch;
-        a = (1.0 - ct) / th2;
+        // J_l = I + a K + b K^2.  a = (1 - cos th) / th^2 is formed as 2 (sin(th/2) / th)^2: 1 - cos th cancels below 1e-4 rad and a K
+        // is first order in th.  b's error eps / th^2 meets |K^2| = th^2.  Both are held to the exact Jacobian, with no power of
+        // 1 / th in the unit, by tests/test_lidar_eval.py (oracle) and tests/test_gpu_lidar_eval.py (device).
+        a = 2.0 * imag * imag;
         b = (th - st) / (th2 * th);
     }
     double Rwb[9];
@@ -96,9 +101,11 @@ __device__ void make_pose(const double* x, const double* T_bl, Pose& P) {
 // every device solver evaluates its factors through this header.
 // x = 0 (a point exactly on its line / plane: ceres::sqrt gives the zero residual there, ceresfunc.h:426-437): the argument of the
 // v_rsq_f64 is clamped at 1e-300, so that root = 0 * 1e150 = 0 and inv_root is a large FINITE number -- every caller multiplies it
-// with a numerator that is exactly zero with x (the cross product, the offset d), and the factor then contributes a zero residual and
-// a zero Jacobian row instead of NaN (the reference's Jet has a NaN derivative at that point; oracle/estimate.cpp takes the same
-// zero-row convention).  One v_max_f64; below 1e-300 the root is only approximate, which no squared length in metres reaches.
+// with a numerator that is exactly zero with x (the cross product, the offset d), so nothing becomes NaN (the reference's Jet has a
+// NaN derivative at that point).  On its line the factor then contributes a zero residual and a zero Jacobian row (ld = |.| has no
+// derivative there: the convention oracle/estimate.cpp shares); on its plane a zero residual and the row it has by the definition,
+// S dP/dx (|d| d is differentiable at 0, weight = 1), so H is not zero while g and cost are -- tests/test_lidar_eval.py.
+// One v_max_f64; below 1e-300 the root is only approximate, which no squared length in metres reaches.
 __device__ __forceinline__ void sqrt_pair(double x, double& root, double& inv_root) {
     const double y = __builtin_amdgcn_rsq(fmax(x, 1e-300));
     double g = x * y, h = 0.5 * y;
@@ -237,7 +244,9 @@ __device__ __forceinline__ void eval_frame(const MmlLineFactor* lf, int nlf, con
         rows[0][1] = ka * w[1];
         rows[0][2] = ka * w[2];
         if (kb != 0.0) {
-            // deterministic tangent basis (any orthonormal completion gives the same H, g, cost)
+            // deterministic tangent basis (any orthonormal completion gives the same H, g, cost for a UNIT omega; omega is a float
+            // vector, unit to 1e-7, so this rule is part of the factor's definition: oracle/estimate.cpp plane_basis, and the
+            // exact references of tests/golden/make_lidar_eval_kat.py)
             double h[3] = {0, 0, 0};
             if (fabs(w[0]) <= fabs(w[1]) && fabs(w[0]) <= fabs(w[2]))
                 h[0] = 1;

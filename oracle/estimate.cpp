@@ -756,7 +756,10 @@ static void left_jacobian(const Vec3& phi, double* J) {
         b = 1.0 / 6.0;
     } else {
         double th = std::sqrt(th2);
-        a = (1.0 - std::cos(th)) / th2;
+        // (1 - cos th) / th^2 as 2 sin^2(th/2) / th^2: 1 - cos th cancels below 1e-4 rad, and a [phi]x is first order in th
+        // (tests/test_lidar_eval.py; b's error eps / th^2 meets |[phi]x^2| = th^2 and needs no such care)
+        double sh = std::sin(0.5 * th);
+        a = 2.0 * sh * sh / th2;
         b = (th - std::sin(th)) / (th2 * th);
     }
     double K[9] = {0, -phi.z, phi.y, phi.z, 0, -phi.x, -phi.y, phi.x, 0};
@@ -831,7 +834,8 @@ static void line_eval(const mmlo_line_factor* f, const PoseEval& pe, double* r, 
     }
 }
 
-// e = weight * (P - proj) and de/dP (3x3); the 3 residual rows are S*e with S^T S = a^2 w w^T + b^2 (I - w w^T)
+// e = weight * (P - proj) and de/dP (3x3); the residual rows are S*e, rows of S: a*w^T and, with plan_weight_tan != 0, b*v2^T, b*v3^T of
+// plane_basis (S^T S = a^2 w w^T + b^2 (I - w w^T) only for a unit omega, which the float omega is not)
 static void plane_core(const mmlo_plane_factor* f, const PoseEval& pe, Vec3* e, double* dedP, Vec3* cp_out, Vec3* P_out) {
     Vec3 cp = mk(f->point_ori[0], f->point_ori[1], f->point_ori[2]);
     Vec3 proj = mk(f->point_proj[0], f->point_proj[1], f->point_proj[2]);
@@ -845,7 +849,8 @@ static void plane_core(const mmlo_plane_factor* f, const PoseEval& pe, Vec3* e, 
     if (dedP) {
         double sm14 = 1.0 / rs;
         double sm54 = sm14 / s;
-        // (nd = 0, a point exactly on its projection: zero rows, as for the line factor)
+        // (nd = 0, a point exactly on its projection: d / |d| has no value, but it is multiplied by |d| -- |d| d is differentiable at 0 --
+        //  so the term is dropped, gw stays finite and de/dP = weight I = I: a zero residual, g and cost, and the row S dP/dx)
         Vec3 gw = (-0.9) * ((nd > 0.0 ? sm14 / nd : 0.0) * d + (nd * (-0.5) * sm54) * P);
         const double dv[3] = {d.x, d.y, d.z};
         const double gv[3] = {gw.x, gw.y, gw.z};
@@ -979,29 +984,36 @@ static void linearize_pe_serial(const mmlo_line_factor* lf, int n_line, const mm
         double dedP[9];
         plane_core(&pf[i], pe, &e, want_jac ? dedP : nullptr, &cp, &P);
         Vec3 w = mk(pf[i].omega[0], pf[i].omega[1], pf[i].omega[2]);
-        // M = S^T S = a^2 w w^T + b^2 (I - w w^T)
-        double we = dot(w, e);
-        Vec3 Me = (ka * ka - kb * kb) * we * w + (kb * kb) * e;
-        double s = dot(e, Me);
+        // the rows of S as mmlo_plane_residual forms them: ka w^T, and with plan_weight_tan != 0 kb v2^T, kb v3^T of plane_basis.
+        // (Not M = S^T S = a^2 w w^T + b^2 (I - w w^T): omega is a float vector, unit to 1e-7 only, and the closed form then
+        //  differs from the rows by 1e-7 kb^2 -- thousands of rounding units of H, tests/test_lidar_eval.py.)
+        Vec3 rows[3] = {ka * w, mk(0, 0, 0), mk(0, 0, 0)};
+        int nrows = 1;
+        if (kb != 0.0) {
+            Vec3 v2, v3;
+            plane_basis(w, &v2, &v3);
+            rows[1] = kb * v2;
+            rows[2] = kb * v3;
+            nrows = 3;
+        }
+        double rr[3], s = 0;
+        for (int q = 0; q < nrows; ++q) {
+            rr[q] = dot(rows[q], e);
+            s += rr[q] * rr[q];
+        }
         double rho0, rho1;
         huber(s, huber_delta, &rho0, &rho1);
         c += 0.5 * rho0;
         if (want_jac) {
             double D[18];
             dP_dx(pe, cp, P, D);
-            double E[18];  // de/dx = dedP * D  (3x6)
-            for (int r = 0; r < 3; ++r)
-                for (int cc = 0; cc < 6; ++cc)
-                    E[6 * r + cc] = dedP[3 * r] * D[cc] + dedP[3 * r + 1] * D[6 + cc] + dedP[3 * r + 2] * D[12 + cc];
-            const double wv[3] = {w.x, w.y, w.z};
-            const double Mev[3] = {Me.x, Me.y, Me.z};
-            double wE[6];
-            for (int cc = 0; cc < 6; ++cc) wE[cc] = wv[0] * E[cc] + wv[1] * E[6 + cc] + wv[2] * E[12 + cc];
-            for (int a = 0; a < 6; ++a) {
-                g[a] += rho1 * (E[a] * Mev[0] + E[6 + a] * Mev[1] + E[12 + a] * Mev[2]);
-                for (int b = 0; b < 6; ++b) {
-                    double ete = E[a] * E[b] + E[6 + a] * E[6 + b] + E[12 + a] * E[12 + b];
-                    H[6 * a + b] += rho1 * ((ka * ka - kb * kb) * wE[a] * wE[b] + (kb * kb) * ete);
+            for (int q = 0; q < nrows; ++q) {
+                double gq[3], J[6];
+                for (int cc = 0; cc < 3; ++cc) gq[cc] = rows[q].x * dedP[cc] + rows[q].y * dedP[3 + cc] + rows[q].z * dedP[6 + cc];
+                for (int cc = 0; cc < 6; ++cc) J[cc] = gq[0] * D[cc] + gq[1] * D[6 + cc] + gq[2] * D[12 + cc];
+                for (int a = 0; a < 6; ++a) {
+                    g[a] += rho1 * J[a] * rr[q];
+                    for (int b = 0; b < 6; ++b) H[6 * a + b] += rho1 * J[a] * J[b];
                 }
             }
         }
