@@ -7,7 +7,8 @@ absent).
   * sqrt_info      LLT(covariance^-1).matrixL().transpose()      mm-loam/src/lio/Estimator.cpp:1240-1242
   * prior_residual MarginalizationFactor::Evaluate               ceresfunc.h:262-301
   * marginalize    MarginalizationInfo::marginalize              ceresfunc.h:149-228
-Jacobians here are central differences of the residuals (the reference uses Ceres autodiff)."""
+Jacobians here are central differences of the residuals (the reference uses Ceres autodiff), and for the IMU factor before its
+square-root information also analytic (imu_jacobian_raw, from the textbook right Jacobian and its inverse)."""
 import numpy as np
 from scipy.spatial.transform import Rotation as Rsc
 
@@ -24,7 +25,16 @@ def exp_so3(w):
 
 
 def log_so3(R):
-    return Rsc.from_matrix(R).as_rotvec()
+    """Sophus::SO3d::log (so3.hpp logAndTheta) of the unit quaternion of R, its decisions included: the series below
+    |imag q| = 1e-10, and pi / |imag q| for |qw| < 1e-10, which drops 2 atan(|qw| / |imag q|) of the angle"""
+    q = Rsc.from_matrix(R).as_quat()
+    n2, qw = float(q[:3] @ q[:3]), float(q[3])
+    if n2 < 1e-20:
+        two_atan = 2.0 / qw - (2.0 / 3.0) * n2 / (qw * qw * qw)
+    else:
+        n = np.sqrt(n2)
+        two_atan = (np.pi if qw > 0 else -np.pi) / n if abs(qw) < 1e-10 else 2.0 * np.arctan(n / qw) / n
+    return two_atan * q[:3]
 
 
 def preintegrate(samples, bg, ba):
@@ -47,7 +57,7 @@ def preintegrate(samples, bg, ba):
         nrm = np.linalg.norm(gdt)
         if nrm > 0.00001:
             K = hat(gdt / nrm)
-            Jr = np.eye(3) - (1 - np.cos(nrm)) / nrm * K + (1 - np.sin(nrm) / nrm) * K @ K
+            Jr = np.eye(3) - 2 * np.sin(0.5 * nrm) ** 2 / nrm * K + (1 - np.sin(nrm) / nrm) * K @ K   # (1 - cos) / nrm, without its cancellation
         A = np.eye(15)
         A[0:3, 3:6] = -0.5 * dq @ hat(acc) * dt2
         A[0:3, 6:9] = np.eye(3) * dt
@@ -90,6 +100,57 @@ def imu_residual_raw(pre, g, pr_i, vb_i, pr_j, vb_j):
     rPhi = log_so3((pre["dR"] @ dR_dbg).T @ Ri.T @ Rj)
     rV = Ri.T @ (Vj - Vi - g * dt) - (pre["dv"] + J[6:9, 9:12] @ dbg + J[6:9, 12:15] @ dba)
     return np.concatenate([rP, rPhi, rV, vb_j[3:9] - vb_i[3:9]])
+
+
+def right_jacobian(w):
+    """Jr(w) = I - a [w]x + b [w]x^2, a = (1 - cos t) / t^2, b = (t - sin t) / t^3 (the textbook form); a is formed as
+    2 (sin(t / 2) / t)^2: 1 - cos t cancels, and just above the series' switch its error reaches 2 eps / t in a [w]x"""
+    w = np.asarray(w, dtype=np.float64)
+    t2 = float(w @ w)
+    K = hat(w)
+    if t2 < 1e-8:
+        a, b = 0.5 - t2 / 24.0, 1.0 / 6.0 - t2 / 120.0
+    else:
+        t = np.sqrt(t2)
+        a, b = 2.0 * (np.sin(0.5 * t) / t) ** 2, (t - np.sin(t)) / (t2 * t)
+    return np.eye(3) - a * K + b * K @ K
+
+
+def right_jacobian_inv(w):
+    """Jr(w)^-1 = I + [w]x / 2 + c [w]x^2, c = 1 / t^2 - (1 + cos t) / (2 t sin t)"""
+    w = np.asarray(w, dtype=np.float64)
+    t2 = float(w @ w)
+    K = hat(w)
+    if t2 < 1e-8:
+        c = 1.0 / 12.0 + t2 / 720.0
+    else:
+        t = np.sqrt(t2)
+        c = 1.0 / t2 - (1.0 + np.cos(t)) / (2.0 * t * np.sin(t))
+    return np.eye(3) + 0.5 * K + c * K @ K
+
+
+def imu_jacobian_raw(pre, g, pr_i, vb_i, pr_j, vb_j):
+    """the derivative of imu_residual_raw in [pr_i | vb_i | pr_j | vb_j] (15 x 30), rotation vectors included, from the textbook
+    right Jacobian and its inverse: d exp(w) = exp(w) [Jr(w) dw]x, d log(E exp(e)) = Jr^-1(log E) e"""
+    Ri, Rj = exp_so3(pr_i[3:]), exp_so3(pr_j[3:])
+    dt = pre["dtime"]
+    Jp = pre["jacobian"]
+    dbg = vb_i[3:6] - pre["bg"]
+    r = imu_residual_raw(pre, g, pr_i, vb_i, pr_j, vb_j)
+    Ra = Ri.T @ (pr_j[:3] - pr_i[:3] - vb_i[:3] * dt - 0.5 * g * dt * dt)
+    Rb = Ri.T @ (vb_j[:3] - vb_i[:3] - g * dt)
+    jd = Jp[3:6, 9:12] @ dbg
+    E = (pre["dR"] @ exp_so3(jd)).T @ Ri.T @ Rj
+    Jri, Jrj, Jinv = right_jacobian(pr_i[3:]), right_jacobian(pr_j[3:]), right_jacobian_inv(r[3:6])
+    J = np.zeros((15, 30))
+    J[0:3, 0:3], J[0:3, 3:6], J[0:3, 6:9] = -Ri.T, hat(Ra) @ Jri, -dt * Ri.T
+    J[0:3, 9:12], J[0:3, 12:15], J[0:3, 15:18] = -Jp[0:3, 9:12], -Jp[0:3, 12:15], Ri.T
+    J[3:6, 3:6] = -Jinv @ Rj.T @ Ri @ Jri
+    J[3:6, 9:12] = -Jinv @ E.T @ right_jacobian(jd) @ Jp[3:6, 9:12]
+    J[3:6, 18:21] = Jinv @ Jrj
+    J[6:9, 3:6], J[6:9, 6:9], J[6:9, 9:12], J[6:9, 12:15], J[6:9, 21:24] = hat(Rb) @ Jri, -Ri.T, -Jp[6:9, 9:12], -Jp[6:9, 12:15], Ri.T
+    J[9:15, 9:15], J[9:15, 24:30] = -np.eye(6), np.eye(6)
+    return J
 
 
 def imu_residual(pre, g, pr_i, vb_i, pr_j, vb_j):
