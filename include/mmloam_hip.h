@@ -945,6 +945,31 @@ int mml_model_fit5(mml_ctx* ctx, int op, const void* in, long n, void* out);
  * mml_fullwindow_marginalize runs (no device needed); otherwise the device build, one workgroup of one wavefront per item.
  * The two are bit-identical. */
 int mml_marginalize_dense(mml_ctx* ctx, long n, const double* A, const double* b, double* J, double* r0);
+/* Test hook: the trust-region state machine of the lidar solves (csrc/solve.hip) replayed on n scripts of records given in
+ * advance (open loop: the records are no function of the candidate).  Per script hdr holds W (1..8), fixed, max_iters, R
+ * (1..rounds_max); x0: n x 48; records: n x rounds_max x 8 x 28 (per frame the 21 upper entries of H, g, cost).  Round 0
+ * initialises from the records at x0, round r >= 1 accepts or rejects on the records of the r-th candidate; every round then
+ * proposes until a candidate needs evaluating or the machine stops (rounds after that change nothing).
+ * variant 0: host tr_propose / tr_decide, what mml_window_solver_step runs (ctx may be NULL);  1: the same two on one device lane;
+ * 2: tr_propose_w1_wave / tr_decide_wave (k_solve, W = 1);  3: tr_propose_w1_regs / tr_decide_w1_regs (k_solve_wide);
+ * 4: tr_propose_wave / tr_decide_wave (the frame-parallel window solve).  2 and 3 refuse W != 1.  One workgroup per script.
+ * Per round: xc (n x rounds_max x 48: the candidate, or x once stopped), digest (MML_TR_DIGEST_DOUBLES: cost, radius, mu, alpha,
+ * dogleg_norm, model_change, step_norm, x_norm, x[48]) and digest_i (MML_TR_DIGEST_INTS: iter, successful, num_invalid, reuse,
+ * termination, go, evaluate, the MML_TR_D_* code of the decision (0: none), the number of proposals of the round, the branch
+ * codes of the first five, 2 spare).  A branch code is one of the MML_TR_* values below + 16 x (the number of times the solve
+ * raised mu inside the call) + MML_TR_FAILED if the call was the fifth invalid step in a row. */
+enum {
+    MML_TR_GAUSS_NEWTON = 1, MML_TR_CAUCHY = 2, MML_TR_INTERP_NEG = 3 /* c <= 0 */, MML_TR_INTERP_POS = 4 /* c > 0 */,
+    MML_TR_SOLVE_FAILED = 5, MML_TR_MODEL_INVALID = 6, MML_TR_STOP_ITER = 8, MML_TR_STOP_RADIUS = 9, MML_TR_FAILED = 256
+};
+enum {
+    MML_TR_D_PARAMETER_TOL = 1, MML_TR_D_FUNCTION_TOL = 2, MML_TR_D_GRADIENT_TOL = 3, MML_TR_D_REJECTED = 4,
+    MML_TR_D_ACCEPT_SHRINK = 5 /* rel < 0.25 */, MML_TR_D_ACCEPT_KEEP = 6, MML_TR_D_ACCEPT_GROW = 7 /* rel > 0.75 */
+};
+#define MML_TR_DIGEST_DOUBLES 56
+#define MML_TR_DIGEST_INTS 16
+int mml_debug_tr_replay(mml_ctx* ctx, int variant, int n, int rounds_max, const int* hdr, const double* x0, const double* records,
+                        double* xc, double* digest, int* digest_i);
 /* How many 5-NN queries of the context's last association call (mml_associate / mml_step's association on the lane that ran
  * last) went beyond rings 0-1 of the grid into the far-query kernels (k_associate_hard): the share to watch when the map's density
  * and the configured cell edge do not fit each other. */

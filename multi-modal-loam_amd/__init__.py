@@ -247,6 +247,9 @@ def lib():
             L.mml_fullwindow_marginalize_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
             L.mml_marginalize_dense.restype = C.c_int
             L.mml_marginalize_dense.argtypes = [C.c_void_p, C.c_long] + [C.c_void_p] * 4
+        if hasattr(L, "mml_debug_tr_replay"):
+            L.mml_debug_tr_replay.restype = C.c_int
+            L.mml_debug_tr_replay.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6
         if hasattr(L, "mml_imu_preintegrate_batch"):
             L.mml_imu_preintegrate_batch.restype = C.c_int
             L.mml_imu_preintegrate_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
@@ -1450,6 +1453,40 @@ def marginalize_dense(ctx, A, b):
     elif rc != MML_OK:
         raise MmlError(rc, "mml_marginalize_dense")
     return (J[0], r0[0]) if single else (J, r0)
+
+
+TR_DIGEST_DOUBLES, TR_DIGEST_INTS = 56, 16
+TR_DIGEST_FIELDS = ("cost", "radius", "mu", "alpha", "dogleg_norm", "model_change", "step_norm", "x_norm")
+TR_DIGEST_INT_FIELDS = ("iter", "successful", "num_invalid", "reuse", "termination", "go", "evaluate", "decide", "nprop")
+
+
+def tr_replay(ctx, variant, scripts):
+    """The trust-region state machine replayed on records given in advance (mml_debug_tr_replay, a test hook).  scripts: a list of
+    dicts with W, fixed, max_iters, x0 (6 W) and records (R, W, 28); variant 0 is the host's tr_propose / tr_decide (ctx may be
+    None), 1..4 the device copies (include/mmloam_hip.h).  Returns (xc (N, Rmax, 48), digest (N, Rmax, 56), digest_i (N, Rmax, 16));
+    the rounds of a script beyond its own R stay zero."""
+    n = len(scripts)
+    rmax = max([np.asarray(s["records"]).shape[0] for s in scripts] + [1])
+    hdr = np.zeros((n, 4), np.int32)
+    x0 = np.zeros((n, 48))
+    rec = np.zeros((n, rmax, 8, 28))
+    for k, s in enumerate(scripts):
+        r = np.asarray(s["records"], dtype=np.float64)
+        W = int(s["W"])
+        if r.ndim != 3 or r.shape[1:] != (W, 28):
+            raise ValueError("script %d: records must be (R, %d, 28), not %s" % (k, W, r.shape))
+        hdr[k] = (W, int(s["fixed"]), int(s["max_iters"]), r.shape[0])
+        x0[k, :6 * W] = np.asarray(s["x0"], dtype=np.float64).reshape(6 * W)
+        rec[k, :r.shape[0], :W] = r
+    xc, dig = np.zeros((n, rmax, 48)), np.zeros((n, rmax, TR_DIGEST_DOUBLES))
+    digi = np.zeros((n, rmax, TR_DIGEST_INTS), np.int32)
+    rc = lib().mml_debug_tr_replay(ctx._h if ctx is not None else None, C.c_int(variant), C.c_int(n), C.c_int(rmax), _p(hdr), _p(x0),
+                                   _p(rec), _p(xc), _p(dig), _p(digi))
+    if ctx is not None:
+        ctx._ck(rc)
+    elif rc != MML_OK:
+        raise MmlError(rc, "mml_debug_tr_replay")
+    return xc, dig, digi
 
 
 class WindowSolver:

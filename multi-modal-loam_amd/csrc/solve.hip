@@ -1459,7 +1459,304 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_window_round(WindowRoundParam
 }
 static_assert(sizeof(TRState) % sizeof(double) == 0, "TRState is copied as doubles");
 
+// ---- record-driven replay of the trust-region state machine (mml_debug_tr_replay, a test hook) -----------------------------------
+// The state machine only consumes records, so a script of records given in advance drives every branch of every copy of it:
+// round 0 initialises from the records at x0, round r >= 1 decides on the records of the r-th candidate, and every round then
+// proposes until a candidate needs evaluating or the machine stops.  What a call did is derived here, from the state before and
+// after it -- the tr_* functions carry no extra stores.
+
+// the state after the records at x0 arrived (S.x, S.x_init, S.rec filled): what k_solve, k_solve_wide and k_window_round's round 1
+// do on lane 0, and mml_window_solver_step's phase 0, which calls this
+__host__ __device__ inline void tr_init(TRState& S, int W, int fixed) {
+    double xn = 0;
+    S.cost = 0;
+    for (int f = 0; f < W; ++f) {
+        S.cost += S.rec[28 * f + 27];
+        for (int i = 0; i < 6; ++i) {
+            S.scale[6 * f + i] = 1.0 / (1.0 + sqrt(Hget(S.rec + 28 * f, i, i)));
+            xn += S.x[6 * f + i] * S.x[6 * f + i];
+        }
+    }
+    S.x_norm = sqrt(xn);
+    S.radius = 1e4;
+    S.mu = 1e-8;
+    S.reuse = 0;
+    S.num_invalid = 0;
+    S.iter = 0;
+    S.successful = 0;
+    S.termination = 0;
+    S.go = 1;
+    S.alpha = 0;
+    S.dogleg_norm = 0;
+    if (!fixed) {
+        double gm = 0;
+        for (int f = 0; f < W; ++f)
+            for (int i = 0; i < 6; ++i) gm = fmax(gm, fabs(S.rec[28 * f + 21 + i]));
+        if (gm <= 1e-10) {
+            S.termination = 1;
+            S.go = 0;
+        }
+    }
+}
+
+struct TRSnap {  // what the classification needs of the state before a call
+    double mu, cost;
+    int iter, reuse, termination, successful;
+};
+__host__ __device__ inline TRSnap tr_snap(const TRState& S) { return TRSnap{S.mu, S.cost, S.iter, S.reuse, S.termination, S.successful}; }
+
+// branch code of one tr_propose call (include/mmloam_hip.h, MML_TR_*)
+__host__ __device__ inline int tr_propose_code(const TRSnap& b, const TRState& S, int W, int max_iters) {
+    if (S.iter == b.iter) return b.iter >= max_iters ? MML_TR_STOP_ITER : MML_TR_STOP_RADIUS;
+    const bool failed = S.termination == 4 && b.termination != 4, invalid = !S.evaluate;
+    // the mu ladder multiplies by 10 and nothing else, so counting the same multiplications finds how often it did
+    int k = 0;
+    double m = b.mu;
+    while (m < S.mu && k < 64) {
+        m *= 10.0;
+        ++k;
+    }
+    const int retries = k - ((invalid && !failed) ? 1 : 0);
+    int code;
+    if (invalid) {
+        double end = b.mu;  // mu when the ladder ended: a solve that failed left it at 1 or above
+        for (int i = 0; i < retries; ++i) end *= 10.0;
+        code = (!b.reuse && !(end < 1.0)) ? MML_TR_SOLVE_FAILED : MML_TR_MODEL_INVALID;
+    } else {
+        const int n = 6 * W;
+        double gradient_norm = 0, gn_norm = 0;
+        for (int i = 0; i < n; ++i) {
+            gradient_norm += S.grad[i] * S.grad[i];
+            gn_norm += S.gn[i] * S.gn[i];
+        }
+        gradient_norm = sqrt(gradient_norm);
+        gn_norm = sqrt(gn_norm);
+        if (gn_norm <= S.radius) {
+            code = MML_TR_GAUSS_NEWTON;
+        } else if (gradient_norm * S.alpha >= S.radius) {
+            code = MML_TR_CAUCHY;
+        } else {
+            double gdot = 0;
+            for (int i = 0; i < n; ++i) gdot += S.grad[i] * S.gn[i];
+            const double b_dot_a = -S.alpha * gdot;
+            const double a_sq = (S.alpha * gradient_norm) * (S.alpha * gradient_norm);
+            code = (b_dot_a - a_sq <= 0) ? MML_TR_INTERP_NEG : MML_TR_INTERP_POS;
+        }
+    }
+    return code + 16 * retries + (failed ? MML_TR_FAILED : 0);
+}
+
+// code of one tr_decide call (MML_TR_D_*)
+__host__ __device__ inline int tr_decide_code(const TRSnap& b, const TRState& S) {
+    if (S.termination != b.termination) return S.termination == 2 ? MML_TR_D_PARAMETER_TOL : S.termination == 3 ? MML_TR_D_FUNCTION_TOL : MML_TR_D_GRADIENT_TOL;
+    if (S.successful == b.successful) return MML_TR_D_REJECTED;
+    const double rel = (b.cost - S.cost) / S.model_change;  // (the accepted candidate's cost is the state's now)
+    return rel < 0.25 ? MML_TR_D_ACCEPT_SHRINK : rel > 0.75 ? MML_TR_D_ACCEPT_GROW : MML_TR_D_ACCEPT_KEEP;
+}
+
+struct TRReplayParams {
+    int Rmax;
+    const int* hdr;     // per script: W, fixed, max_iters, R
+    const double* x0;   // per script 6 MAXW
+    const double* rec;  // per script Rmax x MAXW x 28
+    double* xc;         // per script Rmax x 6 MAXW
+    double* dig;        // per script Rmax x MML_TR_DIGEST_DOUBLES
+    int* digi;          // per script Rmax x MML_TR_DIGEST_INTS
+};
+
+__host__ __device__ inline void tr_digest(const TRState& S, int decide, int nprop, const int* codes, double* xc, double* dig, int* digi) {
+    for (int i = 0; i < 6 * MAXW; ++i) xc[i] = (S.go && S.evaluate) ? S.xc[i] : S.x[i];  // (what mml_window_solver_step hands back)
+    dig[0] = S.cost;
+    dig[1] = S.radius;
+    dig[2] = S.mu;
+    dig[3] = S.alpha;
+    dig[4] = S.dogleg_norm;
+    dig[5] = S.model_change;
+    dig[6] = S.step_norm;
+    dig[7] = S.x_norm;
+    for (int i = 0; i < 6 * MAXW; ++i) dig[8 + i] = S.x[i];
+    digi[0] = S.iter;
+    digi[1] = S.successful;
+    digi[2] = S.num_invalid;
+    digi[3] = S.reuse;
+    digi[4] = S.termination;
+    digi[5] = S.go;
+    digi[6] = S.evaluate;
+    digi[7] = decide;
+    digi[8] = nprop;
+    for (int i = 0; i < 5; ++i) digi[9 + i] = i < nprop ? codes[i] : 0;
+    digi[14] = digi[15] = 0;
+}
+
+// V 1: tr_propose / tr_decide on lane 0 (k_solve, W > 1, whose accept step is tr_decide_wave: the scalar tr_decide runs on the host);
+// 2: tr_propose_w1_wave / tr_decide_wave (k_solve, W = 1);  3: tr_propose_w1_regs / tr_decide_w1_regs (k_solve_wide);
+// 4: tr_propose_wave / tr_decide_wave (k_window_round).  Workgroup size, work areas and the barriers around the calls are the owner's.
+template <int V>
+__global__ __launch_bounds__(V == 3 ? WIDE_THREADS : SOLVE_THREADS) void k_tr_replay(TRReplayParams P) {
+    __shared__ TRState S;
+    __shared__ double s_work[92];
+    __shared__ double s_wd[TRW_DOUBLES];
+    __shared__ TRSnap s_snap;
+    __shared__ int s_codes[8];  // [0..4] proposals of the round, [5] their count, [6] the decision
+    const int tid = threadIdx.x;
+    const size_t s = blockIdx.x;
+    const int W = P.hdr[4 * s], fixed = P.hdr[4 * s + 1], max_iters = P.hdr[4 * s + 2], R = P.hdr[4 * s + 3];
+    {
+        double* dst = reinterpret_cast<double*>(&S);
+        for (int i = tid; i < (int)(sizeof(TRState) / sizeof(double)); i += blockDim.x) dst[i] = 0.0;
+    }
+    __syncthreads();
+    for (int r = 0; r < R; ++r) {
+        const double* rec = P.rec + (s * P.Rmax + r) * 28 * MAXW;
+        if (tid < 8) s_codes[tid] = 0;
+        const int was_go = S.go;
+        __syncthreads();
+        if (r == 0) {
+            if (tid < 6 * W) S.x[tid] = S.x_init[tid] = P.x0[s * 6 * MAXW + tid];
+            for (int i = tid; i < 28 * W; i += blockDim.x) S.rec[i] = rec[i];
+            __syncthreads();
+            if (tid == 0) tr_init(S, W, fixed);
+        } else if (was_go) {
+            for (int i = tid; i < 28 * W; i += blockDim.x) S.recc[i] = rec[i];
+            if (tid == 0) s_snap = tr_snap(S);
+            __syncthreads();
+            if (V == 1) {
+                if (tid == 0) tr_decide(S, W, fixed);
+            } else if (V == 3) {
+                int lane_op = tid;
+                asm volatile("" : "+v"(lane_op));
+                if (tid < 64) tr_decide_w1_regs(S, fixed, lane_op);
+            } else {
+                if (tid < 64) tr_decide_wave(S, s_wd, W, fixed);
+            }
+            __syncthreads();
+            if (tid == 0) s_codes[6] = tr_decide_code(s_snap, S);
+        }
+        __syncthreads();
+        for (;;) {
+            if (!S.go) break;  // (uniform: nobody writes the state between the barriers around this read)
+            if (tid == 0) s_snap = tr_snap(S);
+            __syncthreads();
+            if (V == 1) {
+                if (tid == 0) tr_propose(S, W, max_iters);
+            } else if (V == 2) {
+                if (tid < 64) tr_propose_w1_wave(S, s_work, max_iters);
+            } else if (V == 3) {
+                int lane_op = tid;
+                asm volatile("" : "+v"(lane_op));
+                if (tid < 64) tr_propose_w1_regs(S, s_work, max_iters, lane_op);
+            } else {
+                if (tid < 64) tr_propose_wave(S, s_wd, W, max_iters);
+            }
+            __syncthreads();
+            if (tid == 0) {
+                if (s_codes[5] < 5) s_codes[s_codes[5]] = tr_propose_code(s_snap, S, W, max_iters);
+                s_codes[5]++;
+            }
+            const bool stop = !S.go || S.evaluate;
+            __syncthreads();
+            if (stop) break;
+        }
+        const size_t o = s * P.Rmax + r;
+        if (tid == 0) tr_digest(S, s_codes[6], s_codes[5], s_codes, P.xc + o * 6 * MAXW, P.dig + o * MML_TR_DIGEST_DOUBLES, P.digi + o * MML_TR_DIGEST_INTS);
+        __syncthreads();
+    }
+}
+
+// the same rounds on the host: tr_propose / tr_decide as mml_window_solver_step drives them
+void tr_replay_host(const TRReplayParams& P, size_t s) {
+    TRState* Sp = new TRState();
+    TRState& S = *Sp;
+    const int W = P.hdr[4 * s], fixed = P.hdr[4 * s + 1], max_iters = P.hdr[4 * s + 2], R = P.hdr[4 * s + 3];
+    for (int r = 0; r < R; ++r) {
+        const double* rec = P.rec + (s * P.Rmax + r) * 28 * MAXW;
+        int codes[5] = {0, 0, 0, 0, 0}, nprop = 0, decide = 0;
+        if (r == 0) {
+            for (int i = 0; i < 6 * W; ++i) S.x[i] = S.x_init[i] = P.x0[s * 6 * MAXW + i];
+            for (int i = 0; i < 28 * W; ++i) S.rec[i] = rec[i];
+            tr_init(S, W, fixed);
+        } else if (S.go) {
+            for (int i = 0; i < 28 * W; ++i) S.recc[i] = rec[i];
+            const TRSnap b = tr_snap(S);
+            tr_decide(S, W, fixed);
+            decide = tr_decide_code(b, S);
+        }
+        while (S.go) {
+            const TRSnap b = tr_snap(S);
+            tr_propose(S, W, max_iters);
+            if (nprop < 5) codes[nprop] = tr_propose_code(b, S, W, max_iters);
+            ++nprop;
+            if (!S.go || S.evaluate) break;
+        }
+        const size_t o = s * P.Rmax + r;
+        tr_digest(S, decide, nprop, codes, P.xc + o * 6 * MAXW, P.dig + o * MML_TR_DIGEST_DOUBLES, P.digi + o * MML_TR_DIGEST_INTS);
+    }
+    delete Sp;
+}
+
 }  // namespace
+
+extern "C" int mml_debug_tr_replay(mml_ctx* ctx, int variant, int n, int rounds_max, const int* hdr, const double* x0, const double* records,
+                                   double* xc, double* digest, int* digest_i) {
+    if (variant < 0 || variant > 4 || n < 0 || n > 1 << 16 || rounds_max < 1 || rounds_max > 256 || !hdr || !x0 || !records || !xc || !digest ||
+        !digest_i || (variant != 0 && !ctx))
+        return MML_ERR_INVALID;
+    for (int s = 0; s < n; ++s) {
+        const int W = hdr[4 * s], fixed = hdr[4 * s + 1], max_iters = hdr[4 * s + 2], R = hdr[4 * s + 3];
+        if (W < 1 || W > MAXW || (fixed != 0 && fixed != 1) || max_iters < 0 || max_iters > 1000 || R < 1 || R > rounds_max) return MML_ERR_INVALID;
+        if ((variant == 2 || variant == 3) && W != 1) return MML_ERR_INVALID;
+    }
+    if (n == 0) return MML_OK;
+    const size_t nx = (size_t)n * 6 * MAXW, nr = (size_t)n * rounds_max * 28 * MAXW, no = (size_t)n * rounds_max;
+    for (size_t i = 0; i < no * 6 * MAXW; ++i) xc[i] = 0.0;
+    for (size_t i = 0; i < no * MML_TR_DIGEST_DOUBLES; ++i) digest[i] = 0.0;
+    for (size_t i = 0; i < no * MML_TR_DIGEST_INTS; ++i) digest_i[i] = 0;
+    TRReplayParams P;
+    P.Rmax = rounds_max;
+    if (variant == 0) {
+        P.hdr = hdr;
+        P.x0 = x0;
+        P.rec = records;
+        P.xc = xc;
+        P.dig = digest;
+        P.digi = digest_i;
+        for (int s = 0; s < n; ++s) tr_replay_host(P, (size_t)s);
+        return MML_OK;
+    }
+    int rc = mml_sync_all(ctx);
+    if (rc != MML_OK) return rc;
+    MmlTemp<double> dbuf;  // x0 | records | xc | digest
+    MmlTemp<int> ibuf;     // hdr | digest_i
+    const size_t nxc = no * 6 * MAXW, nd = no * MML_TR_DIGEST_DOUBLES, ni = no * MML_TR_DIGEST_INTS;
+    bool ok = dbuf.alloc(nx + nr + nxc + nd) == hipSuccess && ibuf.alloc(4 * (size_t)n + ni) == hipSuccess;
+    ok = ok && hipMemcpy(dbuf.d, x0, sizeof(double) * nx, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMemcpy(dbuf.d + nx, records, sizeof(double) * nr, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMemset(dbuf.d + nx + nr, 0, sizeof(double) * (nxc + nd)) == hipSuccess;
+    ok = ok && hipMemcpy(ibuf.d, hdr, sizeof(int) * 4 * (size_t)n, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMemset(ibuf.d + 4 * (size_t)n, 0, sizeof(int) * ni) == hipSuccess;
+    if (ok) {
+        P.hdr = ibuf.d;
+        P.x0 = dbuf.d;
+        P.rec = dbuf.d + nx;
+        P.xc = dbuf.d + nx + nr;
+        P.dig = dbuf.d + nx + nr + nxc;
+        P.digi = ibuf.d + 4 * (size_t)n;
+        hipStream_t st = MML_STREAM(ctx);
+        if (variant == 1)
+            hipLaunchKernelGGL(k_tr_replay<1>, dim3((unsigned)n), dim3(SOLVE_THREADS), 0, st, P);
+        else if (variant == 2)
+            hipLaunchKernelGGL(k_tr_replay<2>, dim3((unsigned)n), dim3(SOLVE_THREADS), 0, st, P);
+        else if (variant == 3)
+            hipLaunchKernelGGL(k_tr_replay<3>, dim3((unsigned)n), dim3(WIDE_THREADS), 0, st, P);
+        else
+            hipLaunchKernelGGL(k_tr_replay<4>, dim3((unsigned)n), dim3(SOLVE_THREADS), 0, st, P);
+        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+    }
+    ok = ok && hipMemcpy(xc, P.xc, sizeof(double) * nxc, hipMemcpyDeviceToHost) == hipSuccess;
+    ok = ok && hipMemcpy(digest, P.dig, sizeof(double) * nd, hipMemcpyDeviceToHost) == hipSuccess;
+    ok = ok && hipMemcpy(digest_i, P.digi, sizeof(int) * ni, hipMemcpyDeviceToHost) == hipSuccess;
+    return ok ? MML_OK : MML_ERR_HIP;
+}
 
 size_t mml_window_state_bytes() { return sizeof(TRState); }
 
@@ -1725,38 +2022,12 @@ extern "C" int mml_window_solver_step(mml_window_solver* s, const double* record
         return 1;
     }
     if (s->phase == 0) {
-        double xn = 0;
-        S.cost = 0;
         for (int f = 0; f < W; ++f) {
             for (int k = 0; k < 28; ++k) S.rec[28 * f + k] = records[MML_NEQ_RECORD_DOUBLES * f + k];
-            S.cost += S.rec[28 * f + 27];
-            for (int i = 0; i < 6; ++i) {
-                S.x[6 * f + i] = S.x_init[6 * f + i] = x_eval[6 * f + i];
-                S.scale[6 * f + i] = 1.0 / (1.0 + sqrt(Hget(S.rec + 28 * f, i, i)));
-                xn += S.x[6 * f + i] * S.x[6 * f + i];
-            }
+            for (int i = 0; i < 6; ++i) S.x[6 * f + i] = S.x_init[6 * f + i] = x_eval[6 * f + i];
         }
-        S.x_norm = sqrt(xn);
-        S.radius = 1e4;
-        S.mu = 1e-8;
-        S.reuse = 0;
-        S.num_invalid = 0;
-        S.iter = 0;
-        S.successful = 0;
-        S.termination = 0;
-        S.go = 1;
-        S.alpha = 0;
-        S.dogleg_norm = 0;
+        tr_init(S, W, s->opts.fixed_iterations);
         s->initial_cost = S.cost;
-        if (!s->opts.fixed_iterations) {
-            double gm = 0;
-            for (int f = 0; f < W; ++f)
-                for (int i = 0; i < 6; ++i) gm = fmax(gm, fabs(S.rec[28 * f + 21 + i]));
-            if (gm <= 1e-10) {
-                S.termination = 1;
-                S.go = 0;
-            }
-        }
         s->phase = 1;
     } else {
         for (int f = 0; f < W; ++f)
