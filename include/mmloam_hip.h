@@ -970,6 +970,45 @@ enum {
 #define MML_TR_DIGEST_INTS 16
 int mml_debug_tr_replay(mml_ctx* ctx, int variant, int n, int rounds_max, const int* hdr, const double* x0, const double* records,
                         double* xc, double* digest, int* digest_i);
+/* Test hook: the pieces of the device's GICP (csrc/gicp.hip) on caller-supplied inputs -- the kernels and __device__ functions the
+ * alignments run, not copies.  Clouds are n x 3 floats, covariances and Mahalanobis matrices n x 9 doubles (row-major 3 x 3),
+ * a state is x = (t, roll, pitch, yaw) in 6 doubles, T is a row-major 4 x 4 float matrix.  By operation code:
+ *   MML_GICP_DBG_COV    in  tgt (n_tgt >= 20 points: the cloud)
+ *                       out out_d n x 9: the covariances;  out_i n x 20: every point's neighbour ids in the order of k_gicp_cov's list
+ *   MML_GICP_DBG_CORR   in  src, tgt, cov_src, cov_tgt, T, gate2 (<= 0: no gate)
+ *                       out out_i n_src: corr (-1: gated out);  out_d n_src x 9: maha (zeros where corr = -1)       [k_gicp_corr]
+ *   MML_GICP_DBG_EVAL   in  src, tgt, corr, maha, x (k states), grad (0 / 1), gate2 (> 0: corr may hold -1, as after a gated k_gicp_corr)
+ *                       out out_d k x 2 x 7: f and g[6] (zeros without grad) as lane 0 holds them, then as the workgroup's last lane does
+ *                       [one workgroup as k_gicp_bfgs's calling gicp_eval]
+ *   MML_GICP_DBG_INTERP in  x: k x 8 doubles (a, fa, fpa, b, fb, fpb, xmin, xmax; fpb NaN: the quadratic);  out out_d k: interpolate
+ *   MML_GICP_DBG_QUAD   in  x: k x 3 doubles (a, b, c);  out out_d k x 3: the root count and the two roots (0 where there is none) of solve_quadratic
+ *   MML_GICP_DBG_STATE  in  x: k states;  out out_f k x 16: apply_state;  out_d k x 6: the state k_gicp_bfgs's opening recovers from that matrix
+ *   MML_GICP_DBG_ROUND  in  src, tgt, corr, maha, T, gate2, max_iterations, transformation_epsilon
+ *                       out the state after ONE launch of k_gicp_bfgs from {T, nr = 0}: out_f 16: T;  out_i 4: converged, failed, nr, evals;
+ *                       out_d 2: fobj, delta.  converged = (nr >= max_iterations || delta < 1), delta = the largest |T_in - T_out| entry
+ *                       over 2e-3 (rotation block) or transformation_epsilon (elsewhere); fewer than 4 kept correspondences: failed = 1,
+ *                       T as it came in.
+ * Refused with MML_ERR_INVALID before anything is allocated or launched: an unknown op, a null array the op reads or writes, COV
+ * with fewer than 20 points, any other cloud of fewer than 1 point, more than MML_GICP_DBG_MAX_POINTS points in a cloud, k outside
+ * 1 .. MML_GICP_DBG_MAX_ITEMS, a corr entry outside -1 .. n_tgt - 1 (or -1 without a gate), EVAL with no correspondence, ROUND with
+ * max_iterations < 1 or a transformation_epsilon that is not positive and finite.  Fields an op does not name are ignored. */
+enum {
+    MML_GICP_DBG_COV = 0, MML_GICP_DBG_CORR = 1, MML_GICP_DBG_EVAL = 2, MML_GICP_DBG_INTERP = 3, MML_GICP_DBG_QUAD = 4,
+    MML_GICP_DBG_STATE = 5, MML_GICP_DBG_ROUND = 6
+};
+#define MML_GICP_DBG_MAX_POINTS (1 << 20)
+#define MML_GICP_DBG_MAX_ITEMS  (1 << 20)
+typedef struct mml_gicp_debug {
+    const float* src;  const float* tgt;
+    const double* cov_src;  const double* cov_tgt;
+    const float* T;
+    const int* corr;  const double* maha;
+    const double* x;
+    double* out_d;  int* out_i;  float* out_f;
+    double gate2, transformation_epsilon;
+    int n_src, n_tgt, k, grad, max_iterations, _pad;
+} mml_gicp_debug;
+int mml_debug_gicp(mml_ctx* ctx, int op, const mml_gicp_debug* io);
 /* How many 5-NN queries of the context's last association call (mml_associate / mml_step's association on the lane that ran
  * last) went beyond rings 0-1 of the grid into the far-query kernels (k_associate_hard): the share to watch when the map's density
  * and the configured cell edge do not fit each other. */

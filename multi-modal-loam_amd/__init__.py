@@ -149,6 +149,16 @@ class GicpOpts(C.Structure):
     _fields_ = [("max_iterations", C.c_int), ("transformation_epsilon", C.c_double), ("max_correspondence_distance", C.c_double)]
 
 
+GICP_DBG_COV, GICP_DBG_CORR, GICP_DBG_EVAL, GICP_DBG_INTERP, GICP_DBG_QUAD, GICP_DBG_STATE, GICP_DBG_ROUND = range(7)
+
+
+class GicpDebug(C.Structure):
+    """mml_gicp_debug: the inputs and outputs of mml_debug_gicp."""
+    _fields_ = [(n, C.c_void_p) for n in ("src", "tgt", "cov_src", "cov_tgt", "T", "corr", "maha", "x", "out_d", "out_i", "out_f")] + [
+        ("gate2", C.c_double), ("transformation_epsilon", C.c_double), ("n_src", C.c_int), ("n_tgt", C.c_int), ("k", C.c_int),
+        ("grad", C.c_int), ("max_iterations", C.c_int), ("_pad", C.c_int)]
+
+
 class CalibInfo(C.Structure):
     _fields_ = [("n_hori_in", C.c_int), ("n_velo_in", C.c_int), ("n_hori_ds", C.c_int), ("n_velo_ds", C.c_int),
                 ("hori_unfiltered", C.c_int), ("velo_unfiltered", C.c_int), ("gicp", GicpInfo)]
@@ -786,6 +796,52 @@ class Context:
         self._ck(lib().mml_gicp_align_opts(self._h, _p(src) if len(src) else None, C.c_int(len(src)), _p(tgt) if len(tgt) else None,
                                            C.c_int(len(tgt)), C.byref(opts), _p(T), C.byref(conv), C.byref(info)))
         return bool(conv.value), T, info
+
+    def debug_gicp(self, op, src=None, tgt=None, cov_src=None, cov_tgt=None, T=None, corr=None, maha=None, x=None, gate2=0.0, grad=True,
+                   max_iterations=10, transformation_epsilon=1e-6):
+        """mml_debug_gicp (a test hook): one piece of the device's GICP on the caller's inputs; include/mmloam_hip.h lists the
+        operations.  Returns, by op: COV (cov n x 3 x 3, ids n x 20); CORR (corr n, maha n x 3 x 3); EVAL (f K x 2, g K x 2 x 6: lane 0's
+        copy and the last lane's); INTERP alpha[n]; QUAD (count n, roots n x 2); STATE (T n x 4 x 4 float32, x n x 6);
+        ROUND a dict of T, converged, failed, nr, evals, fobj, delta."""
+        io = GicpDebug()
+        keep = []
+
+        def arr(a, dt, width):
+            if a is None:
+                return None, 0
+            a = np.ascontiguousarray(a, dtype=dt).reshape(-1, width)
+            keep.append(a)
+            return _p(a) if a.size else None, len(a)
+        io.src, io.n_src = arr(src, np.float32, 3)
+        io.tgt, io.n_tgt = arr(tgt, np.float32, 3)
+        io.cov_src, io.cov_tgt = arr(cov_src, np.float64, 9)[0], arr(cov_tgt, np.float64, 9)[0]
+        io.T = arr(T, np.float32, 16)[0]
+        io.corr, io.maha = arr(corr, np.int32, 1)[0], arr(maha, np.float64, 9)[0]
+        io.x, io.k = arr(x, np.float64, {GICP_DBG_INTERP: 8, GICP_DBG_QUAD: 3}.get(op, 6))
+        io.gate2, io.grad = float(gate2), int(bool(grad))
+        io.max_iterations, io.transformation_epsilon = int(max_iterations), float(transformation_epsilon)
+        ns, nt, k = max(io.n_src, 1), max(io.n_tgt, 1), max(io.k, 1)
+        nd = {GICP_DBG_COV: 9 * nt, GICP_DBG_CORR: 9 * ns, GICP_DBG_EVAL: 14 * k, GICP_DBG_INTERP: k, GICP_DBG_QUAD: 3 * k,
+              GICP_DBG_STATE: 6 * k, GICP_DBG_ROUND: 2}.get(op, 1)
+        ni = {GICP_DBG_COV: 20 * nt, GICP_DBG_CORR: ns, GICP_DBG_ROUND: 4}.get(op, 1)
+        od, oi, of = np.zeros(nd), np.zeros(ni, np.int32), np.zeros(16 * k, np.float32)
+        io.out_d, io.out_i, io.out_f = _p(od), _p(oi), _p(of)
+        self._ck(lib().mml_debug_gicp(self._h, C.c_int(op), C.byref(io)))
+        if op == GICP_DBG_COV:
+            return od.reshape(-1, 3, 3), oi.reshape(-1, 20)
+        if op == GICP_DBG_CORR:
+            return oi, od.reshape(-1, 3, 3)
+        if op == GICP_DBG_EVAL:
+            o = od.reshape(-1, 2, 7)
+            return o[:, :, 0], o[:, :, 1:]
+        if op == GICP_DBG_INTERP:
+            return od
+        if op == GICP_DBG_QUAD:
+            o = od.reshape(-1, 3)
+            return o[:, 0].astype(int), o[:, 1:]
+        if op == GICP_DBG_STATE:
+            return of.reshape(-1, 4, 4), od.reshape(-1, 6)
+        return dict(T=of[:16].reshape(4, 4), converged=int(oi[0]), failed=int(oi[1]), nr=int(oi[2]), evals=int(oi[3]), fobj=od[0], delta=od[1])
 
     def cloud_crop_voxel(self, xyzi, far_th, leaf, out=None):
         """mml_cloud_crop_voxel: removeFarPointCloud(far_th) + pcl::VoxelGrid(leaf) of an n x 4 (x, y, z, intensity) cloud on the

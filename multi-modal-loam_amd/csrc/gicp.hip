@@ -77,9 +77,11 @@ __device__ __forceinline__ unsigned long long dkey(float d, int id) {
 }
 
 // grid (blocks of the call's largest cloud, problems, 2): z = 0 the target clouds, 1 the source clouds.  A block wholly past its
-// cloud's size leaves before the first barrier.
+// cloud's size leaves before the first barrier.  IDS (the test hook mml_debug_gicp only): the neighbour list of every point goes to
+// nn_ids, GK ids per point in the list's order; the product's instantiation <false> never reads the pointer.
+template <bool IDS>
 __global__ __launch_bounds__(256) void k_gicp_cov(const GicpProb* __restrict__ tab, const float4* __restrict__ pts_all,
-                                                  double* __restrict__ cov_all) {
+                                                  double* __restrict__ cov_all, int* __restrict__ nn_ids) {
     __shared__ float4 tile[TILE];
     const GicpProb P = tab[blockIdx.y];
     const int n = blockIdx.z ? P.n_src : P.n_tgt, first = blockIdx.z ? P.src : P.tgt;
@@ -113,6 +115,10 @@ __global__ __launch_bounds__(256) void k_gicp_cov(const GicpProb* __restrict__ t
         }
     }
     if (i >= n) return;
+    if (IDS) {
+#pragma unroll
+        for (int j = 0; j < GK; ++j) nn_ids[GK * (size_t)(first + i) + j] = (int)(unsigned)k[j];
+    }
     // computeCovariances: sums in neighbour order, float products accumulated in double
     double mean[3] = {0, 0, 0}, c00 = 0, c10 = 0, c11 = 0, c20 = 0, c21 = 0, c22 = 0;
 #pragma unroll
@@ -258,6 +264,16 @@ __device__ void apply_state(const double* x, float* T) {  // GeneralizedIterativ
     }
     T[12] = T[13] = T[14] = 0.f;
     T[15] = 1.f;
+}
+
+// the state x = (t, roll, pitch, yaw) a 4 x 4 float transformation stands for (gicp.hpp computeTransformation's opening)
+__device__ __forceinline__ void state_of(const float* T, double* x) {
+    x[0] = (double)T[3];
+    x[1] = (double)T[7];
+    x[2] = (double)T[11];
+    x[3] = atan2((double)T[9], (double)T[10]);
+    x[4] = asin(-(double)T[8]);
+    x[5] = atan2((double)T[4], (double)T[0]);
 }
 
 constexpr int EV_CH = 512;            // correspondences per LDS chunk of an objective evaluation
@@ -683,8 +699,8 @@ __global__ __launch_bounds__(BF_THREADS) void k_gicp_bfgs(const GicpProb* __rest
 #pragma unroll
     for (int c = 0; c < 16; ++c) T[c] = st->T[c];
     Bfgs B;
-    double xin[6] = {(double)T[3], (double)T[7], (double)T[11], atan2((double)T[9], (double)T[10]), asin(-(double)T[8]),
-                     atan2((double)T[4], (double)T[0])};
+    double xin[6];
+    state_of(T, xin);
     B.step = 1.0;
     B.delta_f = 0;
     B.evals = 0;
@@ -904,7 +920,7 @@ int gicp_core(mml_ctx* ctx, const GicpRun& run, int n, int max_src, int max_tgt,
     MmlStageScope t(ctx, "gicp");
     const int max_c = max_src > max_tgt ? max_src : max_tgt;
     hipLaunchKernelGGL(k_gicp_init, dim3(n), dim3(64), 0, s, d_st);
-    hipLaunchKernelGGL(k_gicp_cov, dim3((max_c + 255) / 256, n, 2), dim3(256), 0, s, d_tab, pts, cov);
+    hipLaunchKernelGGL(k_gicp_cov<false>, dim3((max_c + 255) / 256, n, 2), dim3(256), 0, s, d_tab, pts, cov, (int*)nullptr);
     for (int done = 0; done < run.max_it;) {  // setMaximumIterations; finished states skip their rounds
         const int rounds = run.max_it - done < ROUNDS_PER_CHUNK ? run.max_it - done : ROUNDS_PER_CHUNK;
         for (int it = 0; it < rounds; ++it) {
@@ -1200,4 +1216,214 @@ extern "C" int mml_gicp_refresh(mml_ctx* ctx, int slot, float* extrinsic_inout, 
     if (refreshed) *refreshed = 0;
     if (info) memset(info, 0, sizeof(*info));
     return gicp_refresh_n(ctx, "mml_gicp_refresh", slot, 1, extrinsic_inout, 0, apply, refreshed, info);
+}
+
+// ---- test hook: the kernels and __device__ functions above on caller-supplied inputs (mml_debug_gicp) ---------------------------
+namespace {
+
+// MML_GICP_DBG_EVAL: one workgroup as k_gicp_bfgs forms it, gicp_eval at K states one after the other; every lane holds the same f
+// and g, lane 0 and lane BF_THREADS - 1 each write their own copy (out: K x 2 x 7)
+__global__ __launch_bounds__(BF_THREADS) void k_gicp_dbg_eval(const float4* src, const float4* tgt, const int* corr, const double* maha, int n,
+                                                             int m, int gated, const double* xs, int K, int grad, double* out) {
+    __shared__ double s_terms[13 * EV_ROW];
+    __shared__ double s_tot[13];
+    __shared__ int s_keep[EV_CH];
+    EvalCtx E{src, tgt, corr, maha, n, m, s_terms, s_tot, gated ? s_keep : nullptr};
+    for (int k = 0; k < K; ++k) {
+        double x[6], g[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int i = 0; i < 6; ++i) x[i] = xs[6 * k + i];
+        const double f = gicp_eval(E, x, grad ? g : nullptr);
+        if (threadIdx.x == 0 || threadIdx.x == BF_THREADS - 1) {
+            double* o = out + 7 * (size_t)(2 * k + (threadIdx.x != 0));
+            o[0] = f;
+#pragma unroll
+            for (int i = 0; i < 6; ++i) o[1 + i] = g[i];
+        }
+    }
+}
+
+// MML_GICP_DBG_INTERP / _QUAD / _STATE: one lane per item
+__global__ void k_gicp_dbg_scalar(int op, const double* in, int n, double* out_d, float* out_f) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (op == MML_GICP_DBG_INTERP) {
+        const double* a = in + 8 * (size_t)i;
+        out_d[i] = interpolate(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7]);
+    } else if (op == MML_GICP_DBG_QUAD) {
+        const double* a = in + 3 * (size_t)i;
+        double x0 = 0, x1 = 0;
+        const int cnt = solve_quadratic(a[0], a[1], a[2], x0, x1);
+        out_d[3 * (size_t)i] = (double)cnt;
+        out_d[3 * (size_t)i + 1] = x0;
+        out_d[3 * (size_t)i + 2] = x1;
+    } else {
+        float T[16];
+        double x[6];
+        apply_state(in + 6 * (size_t)i, T);
+        state_of(T, x);
+#pragma unroll
+        for (int c = 0; c < 16; ++c) out_f[16 * (size_t)i + c] = T[c];
+#pragma unroll
+        for (int c = 0; c < 6; ++c) out_d[6 * (size_t)i + c] = x[c];
+    }
+}
+
+template <class T>
+bool dbg_up(MmlTemp<T>& b, const void* h, size_t n) {
+    return b.alloc(n ? n : 1) == hipSuccess && (n == 0 || hipMemcpy(b.d, h, sizeof(T) * n, hipMemcpyHostToDevice) == hipSuccess);
+}
+template <class T>
+bool dbg_zero(MmlTemp<T>& b, size_t n) {
+    return b.alloc(n ? n : 1) == hipSuccess && hipMemset(b.d, 0, sizeof(T) * (n ? n : 1)) == hipSuccess;
+}
+template <class T>
+bool dbg_down(void* h, const MmlTemp<T>& b, size_t n) {
+    return hipMemcpy(h, b.d, sizeof(T) * n, hipMemcpyDeviceToHost) == hipSuccess;
+}
+// source | target as the kernels' packed float4 array
+std::vector<float4> dbg_pack(const float* src, int ns, const float* tgt, int nt) {
+    std::vector<float4> p((size_t)ns + nt);
+    for (int k = 0; k < ns; ++k) p[k] = make_float4(src[3 * k], src[3 * k + 1], src[3 * k + 2], 0.f);
+    for (int k = 0; k < nt; ++k) p[(size_t)ns + k] = make_float4(tgt[3 * k], tgt[3 * k + 1], tgt[3 * k + 2], 0.f);
+    return p;
+}
+
+}  // namespace
+
+extern "C" int mml_debug_gicp(mml_ctx* ctx, int op, const mml_gicp_debug* io) {
+    if (!ctx) return MML_ERR_INVALID;
+    const char* who = "mml_debug_gicp";
+    if (!io) return mml_refuse(ctx, MML_ERR_INVALID, "%s: a null argument", who);
+    if (op < MML_GICP_DBG_COV || op > MML_GICP_DBG_ROUND) return mml_refuse(ctx, MML_ERR_INVALID, "%s: op = %d is outside 0 .. 6", who, op);
+    const int ns = io->n_src, nt = io->n_tgt, K = io->k;
+    const bool gated = io->gate2 > 0.0;
+    // ---- every refusal, before anything is allocated or launched ----
+    if (op == MML_GICP_DBG_COV) {
+        if (nt < GK || nt > MML_GICP_DBG_MAX_POINTS)
+            return mml_refuse(ctx, MML_ERR_INVALID, "%s: COV: n = %d is outside %d .. %d", who, nt, GK, MML_GICP_DBG_MAX_POINTS);
+        if (!(io->tgt && io->out_d && io->out_i)) return mml_refuse(ctx, MML_ERR_INVALID, "%s: COV: a null argument", who);
+    } else if (op == MML_GICP_DBG_CORR || op == MML_GICP_DBG_EVAL || op == MML_GICP_DBG_ROUND) {
+        if (ns < 1 || nt < 1 || ns > MML_GICP_DBG_MAX_POINTS || nt > MML_GICP_DBG_MAX_POINTS)
+            return mml_refuse(ctx, MML_ERR_INVALID, "%s: clouds of %d and %d points (1 .. %d each)", who, ns, nt, MML_GICP_DBG_MAX_POINTS);
+        if (!(io->src && io->tgt)) return mml_refuse(ctx, MML_ERR_INVALID, "%s: a null cloud", who);
+        if (isnan(io->gate2)) return mml_refuse(ctx, MML_ERR_INVALID, "%s: gate2 is NaN", who);
+        if (op == MML_GICP_DBG_CORR) {
+            if (!(io->cov_src && io->cov_tgt && io->T && io->out_i && io->out_d)) return mml_refuse(ctx, MML_ERR_INVALID, "%s: CORR: a null argument", who);
+        } else {
+            if (!(io->corr && io->maha)) return mml_refuse(ctx, MML_ERR_INVALID, "%s: a null correspondence list", who);
+            // a hole (corr = -1) only with a gate, as k_gicp_corr leaves them; every other entry inside the target
+            for (int i = 0; i < ns; ++i)
+                if (io->corr[i] >= nt || io->corr[i] < (gated ? -1 : 0))
+                    return mml_refuse(ctx, MML_ERR_INVALID, "%s: corr[%d] = %d is outside the target of %d points%s", who, i, io->corr[i], nt,
+                                      gated ? "" : " (holes need gate2 > 0)");
+            if (op == MML_GICP_DBG_EVAL) {
+                int kept = 0;
+                for (int i = 0; i < ns; ++i) kept += io->corr[i] >= 0;
+                if (kept < 1) return mml_refuse(ctx, MML_ERR_INVALID, "%s: EVAL: no correspondence", who);
+                if (K < 1 || K > MML_GICP_DBG_MAX_ITEMS) return mml_refuse(ctx, MML_ERR_INVALID, "%s: EVAL: K = %d is outside 1 .. %d", who, K, MML_GICP_DBG_MAX_ITEMS);
+                if (!(io->x && io->out_d)) return mml_refuse(ctx, MML_ERR_INVALID, "%s: EVAL: a null argument", who);
+            } else {
+                if (!(io->T && io->out_f && io->out_i && io->out_d)) return mml_refuse(ctx, MML_ERR_INVALID, "%s: ROUND: a null argument", who);
+                if (io->max_iterations < 1 || !(isfinite(io->transformation_epsilon) && io->transformation_epsilon > 0.0))
+                    return mml_refuse(ctx, MML_ERR_INVALID, "%s: ROUND: bad settings", who);
+            }
+        }
+    } else {
+        if (K < 1 || K > MML_GICP_DBG_MAX_ITEMS) return mml_refuse(ctx, MML_ERR_INVALID, "%s: n = %d items is outside 1 .. %d", who, K, MML_GICP_DBG_MAX_ITEMS);
+        if (!(io->x && io->out_d) || (op == MML_GICP_DBG_STATE && !io->out_f)) return mml_refuse(ctx, MML_ERR_INVALID, "%s: a null argument", who);
+    }
+    int rc = mml_enter_idle(ctx);
+    if (rc != MML_OK) return rc;
+    hipStream_t s = MML_STREAM(ctx);
+    bool ok = true;
+    if (op == MML_GICP_DBG_INTERP || op == MML_GICP_DBG_QUAD || op == MML_GICP_DBG_STATE) {
+        const size_t wi = op == MML_GICP_DBG_INTERP ? 8 : op == MML_GICP_DBG_QUAD ? 3 : 6, wo = op == MML_GICP_DBG_INTERP ? 1 : op == MML_GICP_DBG_QUAD ? 3 : 6;
+        MmlTemp<double> in, od;
+        MmlTemp<float> of;
+        ok = dbg_up(in, io->x, wi * K) && dbg_zero(od, wo * K) && dbg_zero(of, 16 * (size_t)K);
+        if (ok) {
+            hipLaunchKernelGGL(k_gicp_dbg_scalar, dim3((K + 255) / 256), dim3(256), 0, s, op, in.d, K, od.d, of.d);
+            ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+        }
+        ok = ok && dbg_down(io->out_d, od, wo * K) && (op != MML_GICP_DBG_STATE || dbg_down(io->out_f, of, 16 * (size_t)K));
+        return ok ? MML_OK : MML_ERR_HIP;
+    }
+    if (op == MML_GICP_DBG_COV) {  // a one-problem table: the cloud as the target (blockIdx.z = 0), no source
+        GicpProb P;
+        memset(&P, 0, sizeof(P));
+        P.n_tgt = nt;
+        const std::vector<float4> hp = dbg_pack(nullptr, 0, io->tgt, nt);
+        MmlTemp<GicpProb> tab;
+        MmlTemp<float4> pts;
+        MmlTemp<double> cov;
+        MmlTemp<int> ids;
+        ok = dbg_up(tab, &P, 1) && dbg_up(pts, hp.data(), hp.size()) && dbg_zero(cov, 9 * (size_t)nt) && dbg_zero(ids, GK * (size_t)nt);
+        if (ok) {
+            hipLaunchKernelGGL(k_gicp_cov<true>, dim3((nt + 255) / 256, 1, 1), dim3(256), 0, s, tab.d, pts.d, cov.d, ids.d);
+            ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+        }
+        ok = ok && dbg_down(io->out_d, cov, 9 * (size_t)nt) && dbg_down(io->out_i, ids, GK * (size_t)nt);
+        return ok ? MML_OK : MML_ERR_HIP;
+    }
+    // CORR / EVAL / ROUND: source then target, as place_problem lays a problem out
+    GicpProb P;
+    memset(&P, 0, sizeof(P));
+    P.src = 0;
+    P.tgt = ns;
+    P.n_src = ns;
+    P.n_tgt = nt;
+    const std::vector<float4> hp = dbg_pack(io->src, ns, io->tgt, nt);
+    MmlTemp<GicpProb> tab;
+    MmlTemp<float4> pts;
+    MmlTemp<double> maha;
+    MmlTemp<int> corr;
+    MmlTemp<GicpState> st;
+    ok = dbg_up(tab, &P, 1) && dbg_up(pts, hp.data(), hp.size());
+    GicpState h_st;
+    memset(&h_st, 0, sizeof(h_st));
+    if (io->T) memcpy(h_st.T, io->T, sizeof(float) * 16);
+    ok = ok && dbg_up(st, &h_st, 1);
+    if (op == MML_GICP_DBG_CORR) {
+        std::vector<double> hc(9 * ((size_t)ns + nt));
+        memcpy(hc.data(), io->cov_src, sizeof(double) * 9 * (size_t)ns);
+        memcpy(hc.data() + 9 * (size_t)ns, io->cov_tgt, sizeof(double) * 9 * (size_t)nt);
+        MmlTemp<double> cov;
+        ok = ok && dbg_up(cov, hc.data(), hc.size()) && dbg_zero(maha, 9 * (size_t)ns) && dbg_zero(corr, (size_t)ns);
+        if (ok) {
+            hipLaunchKernelGGL(k_gicp_corr, dim3((ns + 255) / 256, 1), dim3(256), 0, s, tab.d, pts.d, cov.d, st.d, corr.d, maha.d, gated ? io->gate2 : 0.0);
+            ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+        }
+        ok = ok && dbg_down(io->out_i, corr, (size_t)ns) && dbg_down(io->out_d, maha, 9 * (size_t)ns);
+        return ok ? MML_OK : MML_ERR_HIP;
+    }
+    ok = ok && dbg_up(corr, io->corr, (size_t)ns) && dbg_up(maha, io->maha, 9 * (size_t)ns);
+    if (op == MML_GICP_DBG_EVAL) {
+        int m = 0;  // as k_gicp_bfgs counts it: every point without a gate, the kept ones with
+        for (int i = 0; i < ns; ++i) m += io->corr[i] >= 0;
+        MmlTemp<double> xs, out;
+        ok = ok && dbg_up(xs, io->x, 6 * (size_t)K) && dbg_zero(out, 14 * (size_t)K);
+        if (ok) {
+            hipLaunchKernelGGL(k_gicp_dbg_eval, dim3(1), dim3(BF_THREADS), 0, s, pts.d, pts.d + ns, corr.d, maha.d, ns, m, gated ? 1 : 0, xs.d, K,
+                               io->grad ? 1 : 0, out.d);
+            ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+        }
+        ok = ok && dbg_down(io->out_d, out, 14 * (size_t)K);
+        return ok ? MML_OK : MML_ERR_HIP;
+    }
+    const GicpRun run = {io->max_iterations, 1.0 / io->transformation_epsilon, gated ? io->gate2 : 0.0};
+    if (ok) {
+        hipLaunchKernelGGL(k_gicp_bfgs, dim3(1), dim3(BF_THREADS), 0, s, tab.d, pts.d, corr.d, maha.d, st.d, run);
+        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+    }
+    ok = ok && dbg_down(&h_st, st, 1);
+    if (!ok) return MML_ERR_HIP;
+    memcpy(io->out_f, h_st.T, sizeof(float) * 16);
+    io->out_i[0] = h_st.converged;
+    io->out_i[1] = h_st.failed;
+    io->out_i[2] = h_st.nr;
+    io->out_i[3] = h_st.evals;
+    io->out_d[0] = h_st.fobj;
+    io->out_d[1] = h_st.delta;
+    return MML_OK;
 }

@@ -495,6 +495,47 @@ struct Bfgs {
     }
 };
 
+// the state x = (t, roll, pitch, yaw) a transformation stands for (gicp.hpp computeTransformation's opening)
+void state_of(const float* T, double* x) {
+    x[0] = T[3];
+    x[1] = T[7];
+    x[2] = T[11];
+    x[3] = std::atan2((double)T[9], (double)T[10]);
+    x[4] = std::asin(-(double)T[8]);
+    x[5] = std::atan2((double)T[4], (double)T[0]);
+}
+
+// One round of the outer loop after its correspondence step: up to 20 BFGS iterations from the state of T, T replaced by the
+// result's float transformation.  Returns the objective there; *evals grows by the evaluations, *delta is the convergence
+// measure (the largest change of a matrix entry, rotation entries / 2e-3, all others / trans_eps).
+double bfgs_round(const Problem& P, float* T, double trans_eps, int* evals, double* delta_out) {
+    float prev[16];
+    memcpy(prev, T, sizeof(prev));
+    double x[6];
+    state_of(T, x);
+    Bfgs b;
+    b.P = &P;
+    b.init(x);
+    int inner = 0, result = 0;
+    do {
+        ++inner;
+        result = b.iterate();
+        if (result) break;                             // NoProgress
+        result = b.nrm(b.g) < 1e-2 ? 2 : 0;            // testGradient(gradient_tol): Success / Running
+    } while (result == 0 && inner < 20);
+    *evals += b.evals;
+    apply_state(b.x, T);
+    double delta = 0;
+    for (int k = 0; k < 4; ++k)
+        for (int l = 0; l < 4; ++l) {
+            const double ratio = (k < 3 && l < 3) ? 1.0 / ROT_EPS : 1.0 / trans_eps;
+            const double c_delta = ratio * std::fabs((double)prev[4 * k + l] - (double)T[4 * k + l]);
+            if (c_delta > delta) delta = c_delta;
+        }
+    *delta_out = delta;
+    return b.f;
+}
+
 }  // namespace
 
 // icp_ext_matching (unionFeatureExtract.cpp:74-123) on plain buffers.  T_inout: row-major 4 x 4 float, written only on
@@ -535,30 +576,9 @@ extern "C" int mmlo_gicp_align(const float* src, int n_src, const float* tgt, in
             it.push_back(j);
         }
         if (is.size() < 4) break;  // NotEnoughPointsException: the loop ends unconverged
-        float prev[16];
-        memcpy(prev, T, sizeof(T));
-        double x[6] = {T[3], T[7], T[11], std::atan2((double)T[9], (double)T[10]), std::asin(-(double)T[8]), std::atan2((double)T[4], (double)T[0])};
         Problem P{src, tgt, &is, &it, &maha};
-        Bfgs b;
-        b.P = &P;
-        b.init(x);
-        int inner = 0, result = 0;
-        do {
-            ++inner;
-            result = b.iterate();
-            if (result) break;                             // NoProgress
-            result = b.nrm(b.g) < 1e-2 ? 2 : 0;            // testGradient(gradient_tol): Success / Running
-        } while (result == 0 && inner < 20);
-        evals += b.evals;
-        fobj = b.f;
-        apply_state(b.x, T);
-        double delta = 0;
-        for (int k = 0; k < 4; ++k)
-            for (int l = 0; l < 4; ++l) {
-                const double ratio = (k < 3 && l < 3) ? 1.0 / ROT_EPS : 1.0 / 1e-6;
-                const double c_delta = ratio * std::fabs((double)prev[4 * k + l] - (double)T[4 * k + l]);
-                if (c_delta > delta) delta = c_delta;
-            }
+        double delta;
+        fobj = bfgs_round(P, T, 1e-6, &evals, &delta);
         ++nr;
         if (nr >= 10 || delta < 1) converged = true;
     }
@@ -583,4 +603,92 @@ extern "C" void mmlo_gicp_covariances(const float* pts, int n, double* out9) {
     std::vector<M3> c;
     covariances(pts, n, c);
     for (int i = 0; i < n; ++i) memcpy(out9 + 9 * (size_t)i, c[i].m, sizeof(double) * 9);
+}
+
+// ---- the pieces one by one, for tests/test_gicp_kat.py (layouts as mml_debug_gicp's, include/mmloam_hip.h) ----------------------
+// the 20 neighbours of every point in the order covariances() sums them
+extern "C" void mmlo_gicp_neighbours(const float* pts, int n, int* ids20) {
+    for (int i = 0; i < n; ++i) knn_brute(pts, n, pts + 3 * i, K_CORR, ids20 + K_CORR * (size_t)i);
+}
+// one round's correspondence step.  gate2 <= 0: no gate; otherwise the float distance of the search against the double gate
+// (gicp.hpp computeTransformation: if (nn_dists[0] < dist_threshold)), corr = -1 and a zero matrix for a point that fails it
+extern "C" void mmlo_gicp_correspond(const float* src, int n_src, const float* tgt, int n_tgt, const double* cov_src9, const double* cov_tgt9,
+                                     const float* T, double gate2, int* corr, double* maha9) {
+    double R[9];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) R[3 * r + c] = (double)T[4 * r + c];
+    for (int i = 0; i < n_src; ++i) {
+        float q[3];
+        tf_point(T, src + 3 * i, q);
+        int j;
+        knn_brute(tgt, n_tgt, q, 1, &j);
+        double* M = maha9 + 9 * (size_t)i;
+        for (int k = 0; k < 9; ++k) M[k] = 0.0;
+        const float dx = tgt[3 * j] - q[0], dy = tgt[3 * j + 1] - q[1], dz = tgt[3 * j + 2] - q[2];
+        const float d = (dx * dx + dy * dy) + dz * dz;
+        if (gate2 > 0.0 && !((double)d < gate2)) {
+            corr[i] = -1;
+            continue;
+        }
+        corr[i] = j;
+        const double* C1 = cov_src9 + 9 * (size_t)i;
+        const double* C2 = cov_tgt9 + 9 * (size_t)j;
+        double RC[9], tmp[9];
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) RC[3 * r + c] = (R[3 * r] * C1[c] + R[3 * r + 1] * C1[3 + c]) + R[3 * r + 2] * C1[6 + c];
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c)
+                tmp[3 * r + c] = ((RC[3 * r] * R[3 * c] + RC[3 * r + 1] * R[3 * c + 1]) + RC[3 * r + 2] * R[3 * c + 2]) + C2[3 * r + c];
+        inv3(tmp, M);
+    }
+}
+extern "C" void mmlo_gicp_interpolate(const double* items8, int n, double* out) {
+    for (int i = 0; i < n; ++i) {
+        const double* a = items8 + 8 * (size_t)i;
+        out[i] = interpolate(a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7]);
+    }
+}
+extern "C" void mmlo_gicp_solve_quadratic(const double* abc, int n, double* out3) {
+    for (int i = 0; i < n; ++i) {
+        double x0 = 0, x1 = 0;
+        out3[3 * (size_t)i] = (double)solve_quadratic(abc[3 * (size_t)i], abc[3 * (size_t)i + 1], abc[3 * (size_t)i + 2], &x0, &x1);
+        out3[3 * (size_t)i + 1] = x0;
+        out3[3 * (size_t)i + 2] = x1;
+    }
+}
+extern "C" void mmlo_gicp_state(const double* x6, int n, float* T16, double* back6) {
+    for (int i = 0; i < n; ++i) {
+        float* T = T16 + 16 * (size_t)i;
+        apply_state(x6 + 6 * (size_t)i, T);
+        state_of(T, back6 + 6 * (size_t)i);
+    }
+}
+// one inner BFGS round on a given correspondence list (corr[i] = -1: point i has none), from T; the outer loop's bookkeeping as
+// mmlo_gicp_align does it.  out_i: converged, failed, nr, evals; out_d: fobj, delta.  Fewer than 4 correspondences: failed, T kept.
+extern "C" void mmlo_gicp_round(const float* src, int n_src, const float* tgt, const int* corr, const double* maha9, const float* T_in,
+                                int max_iterations, double transformation_epsilon, float* T_out, int* out_i, double* out_d) {
+    std::vector<int> is, it;
+    std::vector<M3> maha(n_src);
+    for (int i = 0; i < n_src; ++i) {
+        memcpy(maha[i].m, maha9 + 9 * (size_t)i, sizeof(double) * 9);
+        if (corr[i] >= 0) {
+            is.push_back(i);
+            it.push_back(corr[i]);
+        }
+    }
+    memcpy(T_out, T_in, sizeof(float) * 16);
+    out_i[0] = out_i[1] = out_i[2] = out_i[3] = 0;
+    out_d[0] = out_d[1] = 0.0;
+    if (is.size() < 4) {
+        out_i[1] = 1;
+        return;
+    }
+    Problem P{src, tgt, &is, &it, &maha};
+    double delta;
+    int evals = 0;
+    out_d[0] = bfgs_round(P, T_out, transformation_epsilon, &evals, &delta);
+    out_d[1] = delta;
+    out_i[2] = 1;
+    out_i[3] = evals;
+    out_i[0] = (1 >= max_iterations || delta < 1) ? 1 : 0;
 }

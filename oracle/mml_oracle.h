@@ -193,6 +193,19 @@ int mmlo_gicp_align(const float* src, int n_src, const float* tgt, int n_tgt, fl
 double mmlo_gicp_objective(const float* src, const float* tgt, const int* idx_src, const int* idx_tgt, int m, const double* maha9,
                            int n_src, const double* x, double* grad);
 void mmlo_gicp_covariances(const float* pts, int n, double* out9);
+/* the remaining pieces, one by one (tests/test_gicp_kat.py; layouts as mml_debug_gicp's in include/mmloam_hip.h): the 20
+ * neighbours of every point in summing order; one round's correspondences and Mahalanobis matrices under T and a squared gate
+ * (<= 0: none; corr = -1 and a zero matrix where the gate rejects); the line search's interpolate (n x 8 items) and
+ * solve_quadratic (n x 3 -> count, root, root); applyState and the state recovered from its matrix; one inner BFGS round on a
+ * given correspondence list (out_i: converged, failed, nr, evals; out_d: fobj, delta) */
+void mmlo_gicp_neighbours(const float* pts, int n, int* ids20);
+void mmlo_gicp_correspond(const float* src, int n_src, const float* tgt, int n_tgt, const double* cov_src9, const double* cov_tgt9,
+                          const float* T, double gate2, int* corr, double* maha9);
+void mmlo_gicp_interpolate(const double* items8, int n, double* out);
+void mmlo_gicp_solve_quadratic(const double* abc, int n, double* out3);
+void mmlo_gicp_state(const double* x6, int n, float* T16, double* back6);
+void mmlo_gicp_round(const float* src, int n_src, const float* tgt, const int* corr, const double* maha9, const float* T_in,
+                     int max_iterations, double transformation_epsilon, float* T_out, int* out_i, double* out_d);
 
 /* Threading of the calling host thread (defaults 1, 1 = the bit-reference configuration of every parity test):
  * livox_line_threads: detectFeaturePoints of the Livox lines in parallel (unionFeatureExtract.cpp:1008-1015, 6 there);

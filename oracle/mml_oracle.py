@@ -442,3 +442,51 @@ def gicp_covariances(pts):
     out = np.zeros((len(pts), 9))
     lib().mmlo_gicp_covariances(_p(pts), C.c_int(len(pts)), _p(out))
     return out.reshape(-1, 3, 3)
+
+
+def gicp_neighbours(pts):
+    pts = _f32(pts).reshape(-1, 3)
+    ids = np.zeros((len(pts), 20), np.int32)
+    lib().mmlo_gicp_neighbours(_p(pts), C.c_int(len(pts)), _p(ids))
+    return ids
+
+
+def gicp_correspond(src, tgt, cov_src, cov_tgt, T, gate2=0.0):
+    """-> (corr n, maha n x 3 x 3)"""
+    src, tgt = _f32(src).reshape(-1, 3), _f32(tgt).reshape(-1, 3)
+    c1, c2, T = _f64(cov_src).reshape(len(src), 9), _f64(cov_tgt).reshape(len(tgt), 9), _f32(T).reshape(16)
+    corr, maha = np.zeros(len(src), np.int32), np.zeros((len(src), 9))
+    lib().mmlo_gicp_correspond(_p(src), C.c_int(len(src)), _p(tgt), C.c_int(len(tgt)), _p(c1), _p(c2), _p(T), C.c_double(gate2), _p(corr), _p(maha))
+    return corr, maha.reshape(-1, 3, 3)
+
+
+def gicp_interpolate(items):
+    a = _f64(items).reshape(-1, 8)
+    out = np.zeros(len(a))
+    lib().mmlo_gicp_interpolate(_p(a), C.c_int(len(a)), _p(out))
+    return out
+
+
+def gicp_solve_quadratic(abc):
+    """-> (count n, roots n x 2)"""
+    a = _f64(abc).reshape(-1, 3)
+    out = np.zeros((len(a), 3))
+    lib().mmlo_gicp_solve_quadratic(_p(a), C.c_int(len(a)), _p(out))
+    return out[:, 0].astype(int), out[:, 1:]
+
+
+def gicp_state(x):
+    """-> (T n x 4 x 4 float32, the state recovered from it n x 6)"""
+    x = _f64(x).reshape(-1, 6)
+    T, back = np.zeros((len(x), 16), np.float32), np.zeros((len(x), 6))
+    lib().mmlo_gicp_state(_p(x), C.c_int(len(x)), _p(T), _p(back))
+    return T.reshape(-1, 4, 4), back
+
+
+def gicp_round(src, tgt, corr, maha, T, max_iterations=10, transformation_epsilon=1e-6):
+    src, tgt = _f32(src).reshape(-1, 3), _f32(tgt).reshape(-1, 3)
+    corr, maha, T = np.ascontiguousarray(corr, dtype=np.int32), _f64(maha).reshape(len(src), 9), _f32(T).reshape(16)
+    To, oi, od = np.zeros(16, np.float32), np.zeros(4, np.int32), np.zeros(2)
+    lib().mmlo_gicp_round(_p(src), C.c_int(len(src)), _p(tgt), _p(corr), _p(maha), _p(T), C.c_int(max_iterations),
+                          C.c_double(transformation_epsilon), _p(To), _p(oi), _p(od))
+    return dict(T=To.reshape(4, 4), converged=int(oi[0]), failed=int(oi[1]), nr=int(oi[2]), evals=int(oi[3]), fobj=od[0], delta=od[1])
