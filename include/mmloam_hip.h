@@ -152,6 +152,30 @@ int mml_cloud_download_registered_batch(mml_ctx* ctx, int first_slot, int count,
 int mml_cloud_download_registered(mml_ctx* ctx, int slot, const double* T_wl /* 16 */, uint8_t* out, int capacity_points,
                                   int* n_points);
 
+/* The feature node's own output: the six PointXYZINormal clouds of one union_cloud message (union-cloud/msg/union_cloud.msg:4-9)
+ * for `count` extracted slots.  Cloud index k, in the message's order: 0 velo_corner, 1 velo_surface, 2 velo_combine,
+ * 3 livox_corner, 4 livox_surface, 5 livox_combine.  Records are the 48-byte records of mml_scan_download_pointxyzinormal
+ * (same fields, same padding); `out` is slot-major, then k, contiguous: cloud (i, k) holds n_points[6 i + k] records and starts
+ * at the sum of all earlier entries of n_points.  out == NULL: only n_points (count x 6) is filled -- the sizing call.
+ *   k = 2, 5: byte for byte the records mml_scan_download_pointxyzinormal returns for the slot, split at the Velodyne count;
+ *       the Livox part as it stands (under the extrinsic when mml_extract was given one or a refresh applied one,
+ *       unionFeatureExtract.cpp:312-318).
+ *   k = 0, 1: the Velodyne points labelled 1 / 2, in the order of the sensor's RAW cloud (:1244-1252), cropped near and far
+ *       (:1287-1295), with the sensor's intensity (velo_combine carries 0, :1254-1256); normal_x = in-sweep time, normal_y = ring,
+ *       normal_z = label.  n_points = velo_corner_num, velo_surf_num of mml_scan_info_get.
+ *   k = 3, 4: the Livox points labelled 1 / 2 in raw order -- of the cloud left by the `line > 5` / `x < 0.01` drops, :985-998 --,
+ *       cropped near ONLY (:925, :933): they include the labelled points beyond far_th, which are in no other output; never
+ *       under the extrinsic (the reference transforms livox_combine alone).  n_points = livox_corner_num, livox_surf_num.
+ * Belongs between mml_extract and mml_undistort, like mml_gicp_refresh: MML_ERR_STATE for a slot that holds an uploaded
+ * (mml_cloud_upload) or an undistorted cloud, or whose raw scan was uploaded again since its extraction (the raw order is read
+ * from the raw records).  MML_ERR_CAPACITY, before any record is written, when capacity_points is below the total;
+ * MML_ERR_INVALID for a slot range outside the context, count < 1 (or above 65535) or NULL n_points.  Nothing in the slots is
+ * modified.  TWO host synchronisations whatever `count` is (counters and flags; records), one for the sizing call. */
+int mml_feature_clouds_download_batch(mml_ctx* ctx, int first_slot, int count, uint8_t* out, long capacity_points,
+                                      int* n_points /* count x 6 */);
+/* One slot: the count = 1 case of the batch call (the same code path). */
+int mml_feature_clouds_download(mml_ctx* ctx, int slot, uint8_t* out, int capacity_points, int* n_points /* 6 */);
+
 /* ---- the aligner's time-offset search ---------------------------
  * The numeric core of LidarsParamEstimator::estimate_timeoffset (unionLidarsAligner.cpp:1077-1153): the Velodyne
  * cloud (n_velo x 3 floats) goes through pcl::transformPointCloud with tf (row-major 4x4 floats, NULL = identity;

@@ -43,6 +43,14 @@ LIVOX_DTYPE = np.dtype([("offset_time", "<u4"), ("x", "<f4"), ("y", "<f4"), ("z"
 
 # mml_union_frame (C long: 8 bytes on the LP64 hosts ROCm runs on)
 UNION_FRAME_DTYPE = np.dtype([("status", "<i4"), ("n_livox", "<i4"), ("begin", "<i8"), ("end", "<i8"), ("front_after", "<i8")])
+# pcl::PointXYZINormal, 48 bytes: the record of mml_scan_download_pointxyzinormal / mml_feature_clouds_download_batch
+POINTXYZINORMAL_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("data_pad", "<f4"), ("normal_x", "<f4"), ("normal_y", "<f4"),
+                                  ("normal_z", "<f4"), ("normal_pad", "<f4"), ("intensity", "<f4"), ("curvature", "<f4"), ("pad0", "<f4"),
+                                  ("pad1", "<f4")])
+# raw points per block of the one-pass bucketing (MML_OP_BLK, csrc/mml_internal.h): a slot's storage is line-bucketed per block
+ASSIGN_BLOCK_POINTS = 4096
+# the clouds of union_cloud.msg:4-9, in the message's order: the cloud index of mml_feature_clouds_download_batch
+FEATURE_CLOUD_NAMES = ("velo_corner", "velo_surface", "velo_combine", "livox_corner", "livox_surface", "livox_combine")
 # mml_velo_fov_info
 VELO_FOV_INFO_DTYPE = np.dtype([("start_ori", "<f4"), ("end_ori", "<f4"), ("half_index", "<i4"), ("n_kept", "<i4")])
 
@@ -281,6 +289,11 @@ def lib():
             L.mml_cloud_download_registered_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]
             L.mml_cloud_download_registered.restype = C.c_int
             L.mml_cloud_download_registered.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        if hasattr(L, "mml_feature_clouds_download_batch"):
+            L.mml_feature_clouds_download_batch.restype = C.c_int
+            L.mml_feature_clouds_download_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_void_p]
+            L.mml_feature_clouds_download.restype = C.c_int
+            L.mml_feature_clouds_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         if hasattr(L, "mml_union_assemble"):
             L.mml_livox_stream_create.restype = C.c_int
             L.mml_livox_stream_create.argtypes = [C.c_void_p, C.c_long, C.c_void_p]
@@ -767,6 +780,24 @@ class Context:
             self._ck(f(self._h, first_slot, count, _p(T), _p(out), total, _p(n)))
         ends = np.cumsum(n)
         return [out[e - k:e] for e, k in zip(ends, n)]
+
+    def feature_clouds(self, first_slot, count):
+        """The feature node's message for `count` extracted slots (union_cloud.msg:4-9): per slot a tuple of six
+        POINTXYZINORMAL_DTYPE arrays in the order of FEATURE_CLOUD_NAMES -- velo_corner, velo_surface, velo_combine, livox_corner,
+        livox_surface, livox_combine.  The sizing call, then ONE data call for all slots (mml_feature_clouds_download_batch)."""
+        count = int(count)
+        if count < 1:
+            raise ValueError("count must be at least 1, not %d" % count)
+        n = np.zeros(6 * count, np.int32)
+        f = lib().mml_feature_clouds_download_batch
+        self._ck(f(self._h, first_slot, count, None, 0, _p(n)))
+        total = int(n.sum())
+        out = np.zeros(max(total, 1), POINTXYZINORMAL_DTYPE)
+        if total:
+            self._ck(f(self._h, first_slot, count, _p(out), total, _p(n)))
+        ends = np.cumsum(n)
+        clouds = [out[e - k:e] for e, k in zip(ends, n)]
+        return [tuple(clouds[6 * i:6 * i + 6]) for i in range(count)]
 
     def cloud_upload(self, slot, records, n_velo=None):
         """A labelled fused cloud (n x 12 float32 = 48-byte PointXYZINormal records, velo_combine then livox_combine)

@@ -12,6 +12,7 @@
 
 #include "imu_math.h"
 #include "mml_internal.h"
+#include "raw_gather_dev.h"
 
 int mml_launch_detect_line(mml_ctx* ctx, int n, uint16_t* d_final);
 
@@ -505,6 +506,12 @@ __global__ void k_encode_xyzinormal(FusedView V, float* out) {
     o[10] = 0.f;
     o[11] = 0.f;
 }
+// the same record as three 16-byte stores (the batched feature-cloud download)
+__device__ __forceinline__ void put_xyzinormal(float4* o, float x, float y, float z, float rel, float line, float label, float intensity) {
+    o[0] = make_float4(x, y, z, 1.0f);
+    o[1] = make_float4(rel, line, label, 0.f);
+    o[2] = make_float4(intensity, 0.f, 0.f, 0.f);
+}
 // the same cloud as four arrays (mml_scan_download): xyzi | reltime | line | label, back to back in one staging buffer
 __global__ void k_fused_arrays(FusedView V, int n, float4* xyzi, float* rel, uint8_t* line, uint8_t* label) {
     const int pos = blockIdx.x * blockDim.x + threadIdx.x;
@@ -588,6 +595,75 @@ __global__ void __launch_bounds__(256) k_encode_registered(SlotArrays A, const d
     o[0] = a;
     o[1] = b;
     o[2] = c;
+}
+// ---- mml_feature_clouds_download_batch: the six clouds of union_cloud.msg:4-9 per slot ------------------------------------------
+// off: where cloud (i, k) starts in `out`, in records -- 6 entries per slot of the call in message order (k: 0 velo_corner,
+// 1 velo_surface, 2 velo_combine, 3 livox_corner, 4 livox_surface, 5 livox_combine) and the call's total behind them, so cloud
+// (i, k) has room for off[6 i + k + 1] - off[6 i + k] records.
+//
+// k = 2, 5: the records of k_encode_xyzinormal, the fused index split at the Velodyne count.  grid (blocks of NT, slots)
+__global__ void __launch_bounds__(256) k_encode_combine(SlotArrays A, const long long* off, float4* out) {
+    const int i = blockIdx.y, slot = A.first + i;
+    const FusedView V = slot_view(A, slot);
+    const int b0 = blockIdx.x * blockDim.x, cv = V.cb_n[0], cl = V.cb_n[1];
+    if (b0 >= V.NV + cl || (b0 >= cv && b0 + (int)blockDim.x <= V.NV)) return;  // (as k_encode_registered)
+    int g, line;
+    float4 p;
+    float rel;
+    if (!fused_at(V, b0 + threadIdx.x, g, p, rel, line)) return;
+    const int n = A.fu_info[8 * (size_t)slot], nv = A.fu_info[8 * (size_t)slot + 1];
+    if (g >= n) return;  // (the records of the slot end at its count, whatever the index array holds)
+    const long long at = g < nv ? off[6 * (size_t)i + 2] + g : off[6 * (size_t)i + 5] + (g - nv);
+    put_xyzinormal(out + 3 * (size_t)at, p.x, p.y, p.z, rel, (float)line, (float)V.label[b0 + threadIdx.x], p.w);
+}
+// k = 0, 1, 3, 4: the labelled points of a sensor in the order of its RAW cloud, as getVeloFeature copies them out before it
+// zeroes the intensity (unionFeatureExtract.cpp:1244-1252; cropped near + far, :1287-1295) and getHoriFeatureExtract before
+// anything is transformed (:1025-1032; cropped near only, :925 / :933 -- the label bytes 0x81 / 0x82 are its points beyond far_th).
+// Coordinates and intensity are the raw record's: ln_pts holds the Livox part under the extrinsic once one was applied, and the
+// reference transforms livox_combine alone (:312).  In-sweep time and label come from the point's bucketed position
+// (raw_gather_dev.h).  grid (2 sensors, slots); a record goes out only where the table has room for it, and got[6 i + k] is
+// what the walk found, which the host holds against the counters the table was laid out from.
+struct FeatCloudArgs {
+    const uint8_t* raw_line;
+    const int *n_in, *seg_flat, *seg_flat_n;
+    const uint8_t* label;
+    const int* rel;
+    const float4* velo_in;
+    const mml_livox_point* livox_in;
+    int first, NT, NV, NL, blk_points;
+};
+__global__ __launch_bounds__(RG_THREADS) void k_feature_gather(FeatCloudArgs A, const long long* off, float4* out, int* got) {
+    const int sensor = blockIdx.x, i = blockIdx.y, slot = A.first + i;
+    const size_t o = (size_t)slot * A.NT;
+    const uint8_t* label = A.label + o;
+    const int* rel = A.rel + o;
+    const float4* velo = A.velo_in + (size_t)slot * A.NV;
+    const mml_livox_point* livox = A.livox_in + (size_t)slot * A.NL;
+    const long long* my_off = off + 6 * (size_t)i + 3 * sensor;
+    const long long at0 = my_off[0], at1 = my_off[1], end1 = my_off[2];
+    const RawGatherSrc S{A.raw_line + o + (sensor == 0 ? 0 : A.NV), A.seg_flat + ((size_t)slot * 2 + sensor) * MML_SEG_FLAT,
+                         A.n_in[2 * (size_t)slot + sensor], A.seg_flat_n[(size_t)slot * 4 + 2 * sensor + 1], A.blk_points, MML_SEG_FLAT, A.NT};
+    const unsigned lim = sensor == 0 ? 0x80u : 0x100u;
+    int n_out[2];
+    raw_gather_walk(
+        S,
+        [&](int p) {
+            const unsigned l = label[p];
+            return ((l & 3u) == 1u || (l & 3u) == 2u) && l < lim ? (int)(l & 3u) - 1 : -1;
+        },
+        [&](int c, int at, int r, int p, int key) {
+            if (at >= (int)(c ? end1 - at1 : at1 - at0)) return;
+            float4 q;
+            if (sensor == 0) {
+                q = velo[r];
+            } else {
+                const mml_livox_point v = livox[r];
+                q = make_float4(v.x, v.y, v.z, (float)v.reflectivity);
+            }
+            put_xyzinormal(out + 3 * (size_t)((c ? at1 : at0) + at), q.x, q.y, q.z, __int_as_float(rel[p]), (float)key, (float)(c + 1), q.w);
+        },
+        n_out);
+    if (threadIdx.x < 2) got[6 * (size_t)i + 3 * sensor + threadIdx.x] = threadIdx.x ? n_out[1] : n_out[0];
 }
 // ---- mml_slot_digest: order-independent 64-bit digests of what the download entry points would hand out -----------------------
 __host__ __device__ __forceinline__ unsigned long long dg_mix(unsigned long long z) {  // splitmix64 finaliser
@@ -870,6 +946,94 @@ int mml_cloud_download_registered_batch(mml_ctx* ctx, int first_slot, int count,
 
 int mml_cloud_download_registered(mml_ctx* ctx, int slot, const double* T_wl, uint8_t* out, int capacity_points, int* n_points) {
     return mml_cloud_download_registered_batch(ctx, slot, 1, T_wl, out, capacity_points, n_points);
+}
+
+// Table block of mml_feature_clouds_download_batch (device + pinned twin), grow-only, owned by the context: the call drains the
+// stream before it returns, so reserve() never replaces a buffer in use.
+struct MmlFeatCloudsDev {
+    MmlStaging<char> io;
+    ~MmlFeatCloudsDev() { io.release(); }
+};
+namespace {
+struct FeatCloudsIo {
+    MmlCarve<16> c;
+    MmlField<int> fi, fl;      // up: the slots' counters and state flags
+    MmlField<long long> off;   // down: where every cloud starts, and the total
+    MmlField<int> got;         // up: what the raw-order walk found
+    size_t bytes;
+    explicit FeatCloudsIo(size_t n) : fi(c.take<int>(8 * n)), fl(c.take<int>(2 * n)), off(c.take<long long>(6 * n + 1)), got(c.take<int>(6 * n)), bytes(c.bytes()) {}
+};
+}  // namespace
+
+int mml_feature_clouds_download_batch(mml_ctx* ctx, int first_slot, int count, uint8_t* out, long capacity_points, int* n_points) {
+    CHECK_SLOTS(first_slot, count);
+    MML_REQUIRE(n_points != nullptr, MML_ERR_INVALID, "null n_points");
+    MML_REQUIRE(count <= 65535, MML_ERR_INVALID, "at most 65535 slots per call (the grid's second dimension)");
+    const char* who = "mml_feature_clouds_download_batch";
+    // the raw-order clouds are those of the EXTRACTED scan: raw_line is re-derived from the raw records (mml_gicp_refresh's rule)
+    for (int i = 0; i < count; ++i)
+        if (!ctx->raw_extracted[first_slot + i])
+            return mml_refuse(ctx, MML_ERR_STATE, "%s: slot %d's raw scan was re-uploaded after mml_extract (or never extracted)", who, first_slot + i);
+    hipStream_t s = MML_STREAM(ctx);
+    const size_t n = (size_t)count, f = (size_t)first_slot;
+    const FeatCloudsIo io(n);
+    MmlFeatCloudsDev* d = mml_side<MmlFeatCloudsDev>(ctx, MML_SIDE_FEATURE_CLOUDS);
+    if (d->io.reserve(ctx, io.bytes, s)) return MML_ERR_HIP;
+    char *h = d->io.h, *g = d->io.d;
+    // synchronisation 1 of 2: counters and state flags of all slots
+    const int *fi = io.fi.in(h), *fl = io.fl.in(h);
+    MML_HIP(hipMemcpyAsync(io.fi.in(h), ctx->fu_info + 8 * f, io.fi.bytes(), hipMemcpyDeviceToHost, s));
+    MML_HIP(hipMemcpyAsync(io.fl.in(h), ctx->slot_flags + 2 * f, io.fl.bytes(), hipMemcpyDeviceToHost, s));
+    MML_HIP(hipStreamSynchronize(s));
+    for (int i = 0; i < count; ++i)
+        if ((fl[2 * i] & 3) != 0)
+            return mml_refuse(ctx, MML_ERR_STATE, "%s: slot %d holds an uploaded or undistorted cloud (call it after mml_extract, before mml_undistort)",
+                              who, first_slot + i);
+    long long* off = io.off.in(h);
+    long long total = 0;
+    for (int i = 0; i < count; ++i) {
+        const int* c = fi + 8 * i;  // n_points, n_velo, velo_corner_num, velo_surf_num, livox_corner_num, livox_surf_num
+        const int np[6] = {c[2], c[3], c[1], c[4], c[5], c[0] - c[1]};
+        for (int k = 0; k < 6; ++k) {
+            off[6 * i + k] = total;
+            total += (n_points[6 * i + k] = np[k]);
+        }
+    }
+    off[6 * n] = total;
+    if (!out) return MML_OK;
+    MML_REQUIRE(capacity_points >= total, MML_ERR_CAPACITY, "download capacity too small");
+    if (total == 0) return MML_OK;
+    const size_t bytes = (size_t)total * 48;
+    int rc = ensure_wire_stage(ctx, bytes);
+    if (rc != MML_OK) return rc;
+    float4* rec = reinterpret_cast<float4*>(ctx->wire_stage.d);
+    MML_HIP(hipMemcpyAsync(io.off.in(g), off, io.off.bytes(), hipMemcpyHostToDevice, s));
+    // (the one-pass bucketing keeps no per-point line ids: recomputed from the raw buffers, which raw_extracted pins -- raw_line,
+    //  raw_ori and blk_cnt are rewritten with the values they already hold)
+    if (ctx->onepass) {
+        rc = mml_launch_raw_lines(ctx, first_slot, count);
+        if (rc != MML_OK) return rc;
+    }
+    const FeatCloudArgs A{ctx->raw_line, ctx->d_n_in, ctx->seg_flat, ctx->seg_flat_n, ctx->ln_label, ctx->ln_rel, ctx->velo_in, ctx->livox_in,
+                          first_slot,    ctx->NT,     ctx->NV,       ctx->NL,         ctx->onepass ? MML_OP_BLK : (1 << 30)};
+    hipLaunchKernelGGL(k_feature_gather, dim3(2, count), dim3(RG_THREADS), 0, s, A, io.off.in(g), rec, io.got.in(g));
+    hipLaunchKernelGGL(k_encode_combine, dim3((ctx->NT + 255) / 256, count), dim3(256), 0, s, slot_arrays(ctx, first_slot), io.off.in(g), rec);
+    MML_HIP(hipGetLastError());
+    // synchronisation 2 of 2: the records, and the walk's own counts
+    MML_HIP(hipMemcpyAsync(io.got.in(h), io.got.in(g), io.got.bytes(), hipMemcpyDeviceToHost, s));
+    MML_HIP(hipMemcpyAsync(out, ctx->wire_stage.d, bytes, hipMemcpyDeviceToHost, s));
+    MML_HIP(hipStreamSynchronize(s));
+    const int* got = io.got.in(h);
+    for (int i = 0; i < count; ++i)
+        for (int k = 0; k < 6; ++k)
+            if (k % 3 != 2 && got[6 * i + k] != n_points[6 * i + k])
+                return mml_refuse(ctx, MML_ERR_STATE, "%s: slot %d, cloud %d: %d labelled points in raw order against a counter of %d", who, first_slot + i, k,
+                                  got[6 * i + k], n_points[6 * i + k]);
+    return MML_OK;
+}
+
+int mml_feature_clouds_download(mml_ctx* ctx, int slot, uint8_t* out, int capacity_points, int* n_points) {
+    return mml_feature_clouds_download_batch(ctx, slot, 1, out, capacity_points, n_points);
 }
 
 int mml_cloud_upload(mml_ctx* ctx, int slot, const uint8_t* pointxyzinormal, int n_points, int n_velo) {

@@ -36,6 +36,7 @@
 #include <string.h>
 
 #include "mml_internal.h"
+#include "raw_gather_dev.h"
 
 namespace {
 
@@ -764,11 +765,11 @@ __global__ void k_gicp_init(GicpState* st_all) {  // grid (problems)
 
 // The slots' surf clouds as the feature node builds them (unionFeatureExtract.cpp:1024-1031, :1242-1252): the points labelled 2 in
 // the order of the sensor's RAW cloud, the Velodyne one cropped near + far (:1287-1293), the Livox one near only (:925) --
-// its labelled points beyond far_th carry bit 7 in their label byte.  One wavefront per (sensor, slot) walks the raw line ids in
-// order and rebuilds every point's bucketed position (line start + rank among the earlier points of its line), which is
-// where its label and its coordinates live.  grid (2, slots), run twice: the count pass (tab == nullptr) leaves counts[2 i + sensor]
-// for the host to lay the call's clouds out -- 0, 0 for a slot the refresh skips (livox_corner_num <= 100) --, the write pass puts
-// the clouds of the problems that align at their offsets in pts.
+// its labelled points beyond far_th carry bit 7 in their label byte.  One workgroup per (sensor, slot) walks the raw line ids in
+// order and rebuilds every point's bucketed position, which is where its label and its coordinates live (raw_gather_dev.h).
+// grid (2, slots), run twice: the count pass (tab == nullptr) leaves counts[2 i + sensor] for the host to lay the call's clouds
+// out -- 0, 0 for a slot the refresh skips (livox_corner_num <= 100) --, the write pass puts the clouds of the problems that align
+// at their offsets in pts.
 struct GatherArgs {
     const uint8_t* raw_line;
     const int *n_in, *seg_flat, *seg_flat_n, *fu_info;
@@ -776,66 +777,35 @@ struct GatherArgs {
     const float4* ln_pts;
     int first, NT, NV, blk_points;
 };
-__global__ __launch_bounds__(64) void k_gicp_gather_raw(GatherArgs A, const GicpProb* tab, float4* pts, int* counts) {
-    __shared__ int s_run[256];
-    const int sensor = blockIdx.x, lane = threadIdx.x, slot = A.first + blockIdx.y;
+__global__ __launch_bounds__(RG_THREADS) void k_gicp_gather_raw(GatherArgs A, const GicpProb* tab, float4* pts, int* counts) {
+    const int sensor = blockIdx.x, slot = A.first + blockIdx.y;
     float4* out = nullptr;
     if (tab) {
         const GicpProb P = tab[blockIdx.y];
         if (P.n_src == 0) return;
         out = pts + (sensor == 0 ? P.tgt : P.src);
     } else if (!(A.fu_info[8 * (size_t)slot + 4] > 100)) {  // union_msg.livox_corner_num > 100 (unionFeatureExtract.cpp:302)
-        if (lane == 0) counts[2 * blockIdx.y + sensor] = 0;
+        if (threadIdx.x == 0) counts[2 * blockIdx.y + sensor] = 0;
         return;
     }
     const size_t o = (size_t)slot * A.NT;
-    const uint8_t* raw_line = A.raw_line + o;
     const uint8_t* label = A.label + o;
     const float4* ln_pts = A.ln_pts + o;
-    const int n = A.n_in[2 * (size_t)slot + sensor], region = sensor == 0 ? 0 : A.NV;
-    const int blk_points = A.blk_points;
-    for (int k = lane; k < 256; k += 64) s_run[k] = 0;
-    __syncthreads();
-    const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    int n_out = 0;
-    // storage: block-major (blocks of blk_points raw points; one block = the whole scan after the three-pass bucketing), line-bucketed
-    // inside a block, raw order inside a (block, line) segment -- segment (blk, key) starts at flat[blk * nkeys + key]
-    const int* flat = A.seg_flat + ((size_t)slot * 2 + sensor) * MML_SEG_FLAT;
-    const int nkeys = A.seg_flat_n[(size_t)slot * 4 + 2 * sensor + 1];
-    for (int i0 = 0; i0 < n; i0 += 64) {
-        if (i0 % blk_points == 0 && i0 > 0) {  // (blk_points is a multiple of 64: a wavefront round never straddles blocks)
-            __syncthreads();
-            for (int k = lane; k < 256; k += 64) s_run[k] = 0;
-            __syncthreads();
-        }
-        const int blk = i0 / blk_points;
-        const int i = i0 + lane;
-        const int key = i < n ? (int)raw_line[region + i] : 255;
-        const bool valid = key < 254;
-        unsigned long long eq = __ballot(valid);  // lanes holding the same line id as mine
-#pragma unroll
-        for (int bit = 0; bit < 8; ++bit) {
-            const bool set = (key >> bit) & 1;
-            const unsigned long long bm = __ballot(valid && set);
-            eq &= set ? bm : ~bm;
-        }
-        int pos = 0;
-        if (valid) pos = s_run[key] + __popcll(eq & lt);
-        __builtin_amdgcn_wave_barrier();
-        if (valid && (eq & lt) == 0) s_run[key] += __popcll(eq);
-        __builtin_amdgcn_wave_barrier();
-        bool take = false;
-        int p = 0;
-        if (valid) {
-            p = flat[blk * nkeys + key] + pos;
+    const RawGatherSrc S{A.raw_line + o + (sensor == 0 ? 0 : A.NV), A.seg_flat + ((size_t)slot * 2 + sensor) * MML_SEG_FLAT,
+                         A.n_in[2 * (size_t)slot + sensor], A.seg_flat_n[(size_t)slot * 4 + 2 * sensor + 1], A.blk_points, MML_SEG_FLAT, A.NT};
+    const unsigned lim = sensor == 0 ? 0x80u : 0x100u;
+    int n_out[2];
+    raw_gather_walk(
+        S,
+        [&](int p) {
             const unsigned l = label[p];
-            take = (l & 3u) == 2u && l < (sensor == 0 ? 0x80u : 0x100u);
-        }
-        const unsigned long long wm = __ballot(take);
-        if (take && out) out[n_out + __popcll(wm & lt)] = ln_pts[p];
-        n_out += __popcll(wm);
-    }
-    if (!tab && lane == 0) counts[2 * blockIdx.y + sensor] = n_out;
+            return ((l & 3u) == 2u && l < lim) ? 0 : -1;
+        },
+        [&](int, int at, int, int p, int) {
+            if (out) out[at] = ln_pts[p];
+        },
+        n_out);
+    if (!tab && threadIdx.x == 0) counts[2 * blockIdx.y + sensor] = n_out[0];
 }
 
 // pcl::transformPointCloud, float (PCL 1.8.1), on the Livox regions of the slots first .. : grid (blocks of the largest region,
@@ -1146,7 +1116,7 @@ int gicp_refresh_n(mml_ctx* ctx, const char* who, int first_slot, int count, flo
             rc = mml_launch_raw_lines(ctx, first_slot + go_lo, go_hi - go_lo + 1);
             if (rc != MML_OK) return rc;
         }
-        hipLaunchKernelGGL(k_gicp_gather_raw, dim3(2, count), dim3(64), 0, s, A, (const GicpProb*)nullptr, (float4*)nullptr,
+        hipLaunchKernelGGL(k_gicp_gather_raw, dim3(2, count), dim3(RG_THREADS), 0, s, A, (const GicpProb*)nullptr, (float4*)nullptr,
                            io.cnt.in(g));
         MML_HIP(hipGetLastError());
         MML_HIP(hipMemcpyAsync(io.cnt.in(h), io.cnt.in(g), io.cnt.bytes(), hipMemcpyDeviceToHost, s));
@@ -1166,7 +1136,7 @@ int gicp_refresh_n(mml_ctx* ctx, const char* who, int first_slot, int count, flo
             MML_HIP(hipMemcpyAsync(io.tab.in(g), io.tab.in(h), io.tab.bytes(), hipMemcpyHostToDevice, s));
             const GicpProb* d_tab = io.tab.in(g);
             float4* pts = big.pts.in(d->big.d);
-            hipLaunchKernelGGL(k_gicp_gather_raw, dim3(2, count), dim3(64), 0, s, A, d_tab, pts, (int*)nullptr);
+            hipLaunchKernelGGL(k_gicp_gather_raw, dim3(2, count), dim3(RG_THREADS), 0, s, A, d_tab, pts, (int*)nullptr);
             GicpState* hs = io.st.in(h);
             rc = gicp_core(ctx, FEATURE_NODE_RUN, count, max_src, max_tgt, d_tab, pts, big.cov.in(d->big.d), big.maha.in(d->big.d), big.corr.in(d->big.d), io.st.in(g),
                            hs);

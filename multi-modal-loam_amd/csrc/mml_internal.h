@@ -79,6 +79,7 @@ enum MmlSideId {
     MML_SIDE_UNION,        // livox_stream.hip MmlUnionDev: the staging blocks of mml_union_assemble
     MML_SIDE_VELO_FOV,     // velo_fov.hip MmlVfovDev: the blocks of the Velodyne FOV selection (single and batch calls)
     MML_SIDE_CALIB,        // calibrate.hip MmlCalibDev: the blocks of mml_cloud_crop_voxel / mml_aligner_calibrate
+    MML_SIDE_FEATURE_CLOUDS,  // capi.hip MmlFeatCloudsDev: the table block of mml_feature_clouds_download_batch
     MML_SIDE_COUNT
 };
 

@@ -41,6 +41,13 @@ struct alignas(16) PointXYZINormal {
 static_assert(sizeof(PointXYZINormal) == 48, "must match pcl::PointXYZINormal");
 using PointCloud = std::vector<PointXYZINormal>;
 
+// union-cloud/msg/union_cloud.msg:4-19 without its header: the six clouds and the four counters of the feature node's message
+struct UnionFeatureClouds {
+    PointCloud velo_corner, velo_surface, velo_combine;
+    PointCloud livox_corner, livox_surface, livox_combine;
+    int velo_corner_num = 0, velo_surf_num = 0, livox_corner_num = 0, livox_surf_num = 0;
+};
+
 struct Matrix3d {  // row-major
     double m[9];
 };
@@ -166,6 +173,65 @@ class feature_extraction {
     }
     void getHoriFeatureExtract(const mml_livox_point* pts, int n, PointCloud& laserCloud, mml_scan_info& info, int slot = 0) {
         unionCloud(nullptr, 0, pts, n, nullptr, laserCloud, info, slot);
+    }
+
+    // The reference's own signatures: getVeloFeature(msg, normal, corner, surf) (:1113-1117) and getHoriFeatureExtract(msg,
+    // cloud, corner, surf) (:952-956).  corner / surf are the sensor's labelled points in RAW order -- the Velodyne ones with the
+    // sensor's intensity, cropped near + far (:1244-1252, :1287-1295), the Livox ones cropped near only (:925, :933) --, normal /
+    // cloud the combine cloud; all three from one mml_feature_clouds_download.
+    void getVeloFeature(const float* velo_xyzi, int n, PointCloud& points_normal, PointCloud& points_corner, PointCloud& points_surf,
+                        mml_scan_info& info, int slot = 0) {
+        extractOnly(velo_xyzi, n, nullptr, 0, info, slot);
+        std::vector<UnionFeatureClouds> m;
+        unionCloudMessage(slot, 1, m);
+        points_normal.swap(m[0].velo_combine);
+        points_corner.swap(m[0].velo_corner);
+        points_surf.swap(m[0].velo_surface);
+    }
+    void getHoriFeatureExtract(const mml_livox_point* pts, int n, PointCloud& laserCloud, PointCloud& laserConerCloud,
+                               PointCloud& laserSurfCloud, mml_scan_info& info, int slot = 0) {
+        extractOnly(nullptr, 0, pts, n, info, slot);
+        std::vector<UnionFeatureClouds> m;
+        unionCloudMessage(slot, 1, m);
+        laserCloud.swap(m[0].livox_combine);
+        laserConerCloud.swap(m[0].livox_corner);
+        laserSurfCloud.swap(m[0].livox_surface);
+    }
+
+    // The union_cloud messages of `count` extracted slots (what unionCloudHandler fills at :287-293 and publishes at :942-947,
+    // :1302-1306), from ONE mml_feature_clouds_download_batch behind its sizing call.  Stamps and frame ids are the caller's.
+    void unionCloudMessage(int first_slot, int count, std::vector<UnionFeatureClouds>& out) {
+        mml_ctx* c = ctx_.get();
+        std::vector<int> n(6 * (size_t)(count > 0 ? count : 1), 0);
+        check(c, mml_feature_clouds_download_batch(c, first_slot, count, nullptr, 0, n.data()), "mml_feature_clouds_download_batch");
+        long total = 0;
+        for (int i = 0; i < 6 * count; ++i) total += n[i];
+        PointCloud data((size_t)total);
+        if (total > 0)
+            check(c, mml_feature_clouds_download_batch(c, first_slot, count, reinterpret_cast<uint8_t*>(data.data()), total, n.data()),
+                  "mml_feature_clouds_download_batch");
+        out.assign(count, UnionFeatureClouds{});
+        const PointXYZINormal* p = data.data();
+        for (int i = 0; i < count; ++i) {
+            UnionFeatureClouds& m = out[i];
+            PointCloud* clouds[6] = {&m.velo_corner, &m.velo_surface, &m.velo_combine, &m.livox_corner, &m.livox_surface, &m.livox_combine};
+            for (int k = 0; k < 6; ++k) {
+                clouds[k]->assign(p, p + n[6 * i + k]);
+                p += n[6 * i + k];
+            }
+            m.velo_corner_num = n[6 * i];
+            m.velo_surf_num = n[6 * i + 1];
+            m.livox_corner_num = n[6 * i + 3];
+            m.livox_surf_num = n[6 * i + 4];
+        }
+    }
+
+    // upload + extract without an extrinsic + counters: the slot is left for the download the caller chooses
+    void extractOnly(const float* velo_xyzi, int n_velo, const mml_livox_point* livox, int n_livox, mml_scan_info& info, int slot) {
+        mml_ctx* c = ctx_.get();
+        check(c, mml_scan_upload(c, slot, velo_xyzi, n_velo, livox, n_livox), "scan_upload");
+        check(c, mml_extract(c, slot, 1, nullptr), "extract");
+        check(c, mml_scan_info_get(c, slot, &info), "scan_info");
     }
 
     void download(int slot, int n, PointCloud& out) {
