@@ -935,6 +935,89 @@ int mml_lio_initialize_batch(mml_ctx* ctx, int n_seg, const int* frame_offsets /
         const double* exTlb /* n_seg x 16 */, const mml_imu_preint* pre_in /* F or NULL */,
         mml_imu_preint* pre_out /* F or NULL */, mml_lio_init_result* out /* n_seg */);
 
+/* ---- the pose node's IMU queue: a device-resident message store cut and pre-integrated per frame interval -------------------
+ * What produces the samples / offsets arrays the batch calls above start from.  A mml_imu_stream is _imuMsgVector
+ * (unionPoseEstimation.cpp:296) in device memory: rows of 7 doubles = header.stamp.toSec(), angular_velocity xyz,
+ * linear_acceleration xyz as in the message (not yet * gnorm).  Messages are counted absolutely over everything ever pushed:
+ * `front` is the first live one, `tail` one past the last.  Housekeeping as for mml_livox_stream: the stream belongs to its
+ * context and is destroyed before it; push is one host-to-device copy and one kernel, asynchronous on the context's stream (the
+ * host buffer must stay valid until the next synchronising call); MML_ERR_CAPACITY, changing nothing, when the live messages plus
+ * n exceed capacity_msgs (1 .. 2^24); when the array's end is reached the live part moves to the front of a second array (one
+ * device-to-device copy on the stream), so a stream holds 112 bytes per message of capacity.
+ * The host keeps a mirror of the stamps (8 bytes per message, written at push), so mml_imu_stream_drop_before -- the trim of
+ * :383-390: while live > keep_min and stamp[front] < t: ++front; the reference has keep_min = 200 and
+ * t = min(_time_last_hori, _time_last_velo) -- and the stamps of mml_imu_stream_state_get need no device work and no
+ * synchronisation; state_get synchronises once, for `disorder`.
+ * TIME ORDER.  The cut needs stamps that do not decrease, across pushes too; equal stamps are allowed.  The push kernel counts
+ * the violations (`disorder`, each message compared with the one before it in the queue); mml_imu_fetch_batch refuses a stream
+ * that has any.  What the reference does with unordered stamps depends on the order of its walk and is not reproduced.
+ * mml_imu_stream_reset empties the stream and forgets the violations. */
+typedef struct mml_imu_stream mml_imu_stream;
+int  mml_imu_stream_create(mml_ctx* ctx, long capacity_msgs, mml_imu_stream** out);
+void mml_imu_stream_destroy(mml_imu_stream* s);
+int  mml_imu_stream_reset(mml_imu_stream* s);
+int  mml_imu_stream_push(mml_imu_stream* s, const double* msgs /* n x 7 */, int n);
+int  mml_imu_stream_drop_before(mml_imu_stream* s, double t, long keep_min);
+typedef struct { long front, tail; long disorder; double first_stamp, last_stamp; /* of the live messages; 0 when none */ } mml_imu_stream_state;
+int  mml_imu_stream_state_get(mml_imu_stream* s, mml_imu_stream_state* out);
+
+/* fetchImuMsgs (unionPoseEstimation.cpp:307-395, called at :719 for every scan) for n intervals (t_start[i], t_end[i]] in one
+ * call, with what process() does to the result at :741-828: the cut, the message synthesised at t_end, the dt column,
+ * PreIntegration with the interval's biases and GyroIntegration from the identity.  The rules, with the reference's lines, are
+ * in csrc/imu_fetch.h; in short, with T the live stamps:
+ *   status 1 EMPTY no live message | 4 REVERSED t_end < t_start | 2 NOT_REACHED T[tail-1] < t_end | 3 TOO_OLD T[front] >= t_end
+ *   (checked in that order) | 0 OK | 5 NO_SAMPLE: the interpolation branch is reached with no message inside, where the
+ *   reference reads back() of an empty vector -- defined here, n = 0; t_end == t_start always lands here.
+ *   OK: the messages with t_start < T <= t_end up to the first one at t_end exactly; when none is at t_end, one more row
+ *   interpolated linearly between the last message inside and the first one past the end (interpolated = 1).  A message at
+ *   exactly t_start is out.  The synthesised message's stamp is t_end itself: the reference rounds it to whole nanoseconds
+ *   (ros::Time::fromSec), the identity for stamps of ROS headers at epoch scale and the one deliberate difference otherwise.
+ * samples: the rows of all intervals packed in order, interval i at rows offsets[i] .. offsets[i+1]-1, in the shape
+ * mml_imu_preintegrate takes (gyro xyz, accel xyz, dt; row 0's dt counts from t_start).  pre[i] has the bytes of
+ * mml_imu_preintegrate_batch on those rows with bg + 3 i, ba + 3 i (the same kernel, launched on the packed rows); dq[i]
+ * (x, y, z, w) is GyroIntegration from the identity (the chain of mml_imu_gyro_integrate).  An interval whose status is not 0
+ * has n = 0, the reset state in pre and dq = (0, 0, 0, 1).  The stream is only read: intervals may overlap or repeat.
+ * sample_capacity bounds the total row count whether samples is NULL (the rows stay on the device, for pre / dq) or not.  When the
+ * total exceeds it the call returns MML_ERR_CAPACITY with rows and offsets written (offsets[n] is the size needed, saturating
+ * at INT_MAX) and samples, pre and dq NOT written.  With samples, pre and dq all NULL it is ignored: a sizing call.
+ * Work per call, whatever n is: one upload, a plan kernel (a lane per interval: two binary searches, status, count), an
+ * exclusive scan of the counts in one workgroup, a write kernel (a wavefront per interval), k_imu_preintegrate, a gyro kernel
+ * (a lane per interval), one read-back -- it moves sample_capacity rows at most, so size it tightly -- and ONE host
+ * synchronisation.  The device runs the host's operations in the host's order: every output byte equals mml_imu_fetch_host's.
+ * Everything is checked before anything is enqueued and the message names the interval: MML_ERR_INVALID for n outside
+ * 1 .. MML_IMU_FETCH_BATCH_MAX, a NULL stream, t_start, t_end, rows or offsets, a stream of another context, exactly one of bg /
+ * ba NULL, pre without biases, a negative sample_capacity, a non-finite time.  MML_ERR_STATE, from the call's one read-back and
+ * with nothing written, for a stream with time-order violations.  The context keeps one device and one pinned block for the
+ * largest call it has seen (3.9 KB per interval and 56 bytes per row of sample_capacity), released by mml_destroy. */
+typedef struct {
+    int status, n;            /* rows emitted, the synthesised one included */
+    long first;               /* absolute index of row 0's message; front when n == 0 */
+    int interpolated, _pad;
+    double front_gyro_z, back_gyro_z;   /* vimuMsg.front() / back()->angular_velocity.z, the operands of :747, :771; 0 when n == 0 */
+} mml_imu_interval;
+#define MML_IMU_FETCH_BATCH_MAX 8192    /* = MML_PREINT_BATCH_MAX */
+int mml_imu_fetch_batch(mml_ctx* ctx, mml_imu_stream* s, int n, const double* t_start, const double* t_end,
+        const double* bg, const double* ba /* n x 3 each, or both NULL: no pre-integration */,
+        mml_imu_interval* rows /* n */, int* offsets /* n + 1 */, double* samples /* sample_capacity x 7 or NULL */,
+        long sample_capacity, mml_imu_preint* pre /* n or NULL */, double* dq /* n x 4 or NULL */);
+/* The same on a host array of messages (n_msgs x 7 as pushed, all of them live, first = 0-based row), no context, no device.
+ * MML_ERR_STATE for decreasing stamps; MML_ERR_INVALID also for n_msgs outside 0 .. 2^24, NULL msgs with n_msgs > 0 or a stamp
+ * that is not finite (which mml_imu_stream_push refuses too). */
+int mml_imu_fetch_host(const double* msgs, long n_msgs, int n, const double* t_start, const double* t_end,
+        const double* bg, const double* ba, mml_imu_interval* rows, int* offsets, double* samples, long sample_capacity,
+        mml_imu_preint* pre, double* dq);
+/* The frame prediction of process() for n intervals, from the results above.  exTlb: one 4 x 4, row-major (exRbl / exPbl are its
+ * inverse's rotation and translation).  With prev (n x 10: the previous frame's body state P(3), Q(4, x y z w), V(3)) and pre
+ * (n), :805-828: state (n x 10) = P + Q * dp, Q * dq, V + Q * dv; delta_Rl (n x 9, row-major) = Qwlpre^* Qwl and delta_tl (n x 3)
+ * = Qwlpre^* (Pwl - Pwlpre), laid out as mml_step / mml_undistort take dR and dt.  With dq (n x 4), the bring-up branch :779-780:
+ * gyro_Rb (n x 9) = dq.toRotationMatrix(), gyro_Rl (n x 9) = R_lb gyro_Rb R_lb^T.  Either group may be left out (all its
+ * pointers NULL).  ctx NULL: the host build of csrc/imu_fetch.h; otherwise one upload, one kernel (a lane per interval), one
+ * read-back, bit-identical to it.  Against the reference the quaternion products are held to rounding, not to bytes (Eigen's
+ * operation order is not restated).  MML_ERR_INVALID for n outside 1 .. MML_IMU_FETCH_BATCH_MAX, NULL exTlb, a group given in part,
+ * or neither group. */
+int mml_imu_predict_batch(mml_ctx* ctx, int n, const double* exTlb, const double* prev, const mml_imu_preint* pre,
+        double* state, double* delta_Rl, double* delta_tl, const double* dq, double* gyro_Rb, double* gyro_Rl);
+
 /* Number of HIP streams mml_step pipelines its sub-batches over (1..8, default 2 or $MML_LANES).  With 1 every
  * kernel covers the whole batch and runs alone on the device, which is what per-kernel timing wants. */
 int mml_set_lanes(mml_ctx* ctx, int lanes);

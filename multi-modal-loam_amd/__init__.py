@@ -35,6 +35,9 @@ UNION_BATCH_MAX = 65535   # MML_UNION_BATCH_MAX: frames per call of mml_union_as
 FOV_BATCH_MAX = 65535     # MML_FOV_BATCH_MAX: frames per call of mml_velo_fov_select_batch
 FOV_TILE_POINTS = 256     # VFOV_BLOCK (csrc/velo_fov.hip): points one workgroup pass of the selection kernel takes
 FOV_REG_POINTS = 4096     # VFOV_REG_POINTS: frames above this park their azimuths in scratch between the phases
+IMU_FETCH_BATCH_MAX = 8192  # MML_IMU_FETCH_BATCH_MAX: intervals per call of mml_imu_fetch_batch / mml_imu_predict_batch
+# mml_imu_interval.status (csrc/imu_fetch.h)
+IMU_FETCH_OK, IMU_FETCH_EMPTY, IMU_FETCH_NOT_REACHED, IMU_FETCH_TOO_OLD, IMU_FETCH_REVERSED, IMU_FETCH_NO_SAMPLE = 0, 1, 2, 3, 4, 5
 UNION_OK, UNION_EMPTY, UNION_NOT_REACHED, UNION_NO_POINTS, UNION_OVERFLOW = 0, 1, 2, 3, 4   # mml_union_frame.status
 
 LIVOX_DTYPE = np.dtype([("offset_time", "<u4"), ("x", "<f4"), ("y", "<f4"), ("z", "<f4"),
@@ -43,6 +46,9 @@ LIVOX_DTYPE = np.dtype([("offset_time", "<u4"), ("x", "<f4"), ("y", "<f4"), ("z"
 
 # mml_union_frame (C long: 8 bytes on the LP64 hosts ROCm runs on)
 UNION_FRAME_DTYPE = np.dtype([("status", "<i4"), ("n_livox", "<i4"), ("begin", "<i8"), ("end", "<i8"), ("front_after", "<i8")])
+# mml_imu_interval
+IMU_INTERVAL_DTYPE = np.dtype([("status", "<i4"), ("n", "<i4"), ("first", "<i8"), ("interpolated", "<i4"), ("_pad", "<i4"),
+                               ("front_gyro_z", "<f8"), ("back_gyro_z", "<f8")])
 # pcl::PointXYZINormal, 48 bytes: the record of mml_scan_download_pointxyzinormal / mml_feature_clouds_download_batch
 POINTXYZINORMAL_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("data_pad", "<f4"), ("normal_x", "<f4"), ("normal_y", "<f4"),
                                   ("normal_z", "<f4"), ("normal_pad", "<f4"), ("intensity", "<f4"), ("curvature", "<f4"), ("pad0", "<f4"),
@@ -322,6 +328,23 @@ def lib():
                                                     + [C.c_void_p] * 2)
             L.mml_velo_fov_select.restype = C.c_int
             L.mml_velo_fov_select.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 2
+        if hasattr(L, "mml_imu_fetch_batch"):
+            L.mml_imu_stream_create.restype = C.c_int
+            L.mml_imu_stream_create.argtypes = [C.c_void_p, C.c_long, C.c_void_p]
+            L.mml_imu_stream_destroy.restype = None
+            L.mml_imu_stream_destroy.argtypes = [C.c_void_p]
+            L.mml_imu_stream_reset.argtypes = [C.c_void_p]
+            L.mml_imu_stream_push.restype = C.c_int
+            L.mml_imu_stream_push.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+            L.mml_imu_stream_drop_before.restype = C.c_int
+            L.mml_imu_stream_drop_before.argtypes = [C.c_void_p, C.c_double, C.c_long]
+            L.mml_imu_stream_state_get.argtypes = [C.c_void_p, C.c_void_p]
+            L.mml_imu_fetch_batch.restype = C.c_int
+            L.mml_imu_fetch_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_long] + [C.c_void_p] * 2
+            L.mml_imu_fetch_host.restype = C.c_int
+            L.mml_imu_fetch_host.argtypes = [C.c_void_p, C.c_long, C.c_int] + [C.c_void_p] * 7 + [C.c_long] + [C.c_void_p] * 2
+            L.mml_imu_predict_batch.restype = C.c_int
+            L.mml_imu_predict_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 9
         _lib = L
     return _lib
 
@@ -581,6 +604,54 @@ class LivoxStream:
         self._ctx._ck(lib().mml_livox_stream_reset(self._h))
 
 
+class ImuStreamState(C.Structure):
+    _fields_ = [("front", C.c_long), ("tail", C.c_long), ("disorder", C.c_long), ("first_stamp", C.c_double), ("last_stamp", C.c_double)]
+
+
+class ImuStream:
+    """One mml_imu_stream: the pose node's IMU message queue in device memory (Context.imu_stream).  Close it before its context."""
+
+    def __init__(self, ctx, capacity):
+        self._ctx = ctx
+        self._h = C.c_void_p()
+        self._keep = []
+        ctx._ck(lib().mml_imu_stream_create(ctx._h, C.c_long(capacity), C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self._ctx, "_h", None):
+            lib().mml_imu_stream_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def push(self, msgs):
+        """Messages as rows of 7 doubles: header stamp (s), angular_velocity xyz, linear_acceleration xyz (message units)."""
+        m = _f64(msgs).reshape(-1, 7)
+        self._keep.append(m)   # host buffers must outlive the asynchronous copy
+        if len(self._keep) > 64:
+            self._ctx.synchronize()
+            self._keep = self._keep[-1:]
+        self._ctx._ck(lib().mml_imu_stream_push(self._h, _p(m) if len(m) else None, C.c_int(len(m))))
+
+    def drop_before(self, t, keep_min=200):
+        """fetchImuMsgs' trim: while more than keep_min messages are live and the front one is older than t, drop it."""
+        self._ctx._ck(lib().mml_imu_stream_drop_before(self._h, C.c_double(t), C.c_long(keep_min)))
+
+    def state(self):
+        """dict(front, tail, disorder, first_stamp, last_stamp); synchronises."""
+        st = ImuStreamState()
+        self._ctx._ck(lib().mml_imu_stream_state_get(self._h, C.byref(st)))
+        return {"front": int(st.front), "tail": int(st.tail), "disorder": int(st.disorder), "first_stamp": float(st.first_stamp),
+                "last_stamp": float(st.last_stamp)}
+
+    def reset(self):
+        self._ctx._ck(lib().mml_imu_stream_reset(self._h))
+
+
 class Context:
     """One mml_ctx: owns device buffers, maps and a HIP stream for `cfg.max_scans` scan slots."""
 
@@ -706,6 +777,10 @@ class Context:
         return velo_fov_select(frames, ctx=self)
 
     # ---- the aligner node's frame assembly (unionLidarsAligner.cpp:343-364, :736-868; time-offset mode :513-551, :872-1009) ----
+    def imu_stream(self, capacity):
+        """An ImuStream of `capacity` messages on this context."""
+        return ImuStream(self, capacity)
+
     def livox_stream(self, capacity):
         """A LivoxStream of `capacity` points on this context."""
         return LivoxStream(self, capacity)
@@ -1275,6 +1350,104 @@ def imu_preintegrate_batch(samples_list, bg, ba, ctx=None):
     elif rc != MML_OK:
         raise MmlError(rc, "mml_imu_preintegrate_batch")
     return [ImuPreint.from_buffer_copy(out[i]) for i in range(n)]
+
+
+def imu_fetch_raw(stream_or_msgs, t_start, t_end, bg=None, ba=None, ctx=None, want=("samples", "pre", "dq"), sample_capacity=None):
+    """mml_imu_fetch_batch (an ImuStream) / mml_imu_fetch_host (an (m, 7) array of messages) without the error check: returns
+    (rc, out) with out = dict(rows (IMU_INTERVAL_DTYPE), offsets (n + 1), and -- as far as `want` names them -- samples
+    (offsets[n], 7), pre (a ctypes array of n ImuPreint), dq (n, 4)).  sample_capacity None: the rows are counted by a sizing
+    call first (one more synchronisation on a stream); give a bound to save it.  After MML_ERR_CAPACITY rows and offsets are
+    valid and the rest is not; after any other refusal nothing is.  Without biases `pre` is left out."""
+    ts, te = _f64(t_start).reshape(-1), _f64(t_end).reshape(-1)
+    n = len(ts)
+    if len(te) != n:
+        raise ValueError("t_start and t_end differ in length (%d, %d)" % (n, len(te)))
+    unknown = set(want) - {"samples", "pre", "dq"}
+    if unknown:
+        raise ValueError("want names %s" % sorted(unknown))
+    if bg is None and ba is None:
+        want = tuple(w for w in want if w != "pre")     # (no biases: no pre-integration)
+    bias = [None, None]
+    if bg is not None or ba is not None:
+        for k, (name, b) in enumerate((("bg", bg), ("ba", ba))):
+            if b is None:
+                continue
+            b = np.asarray(b, dtype=np.float64)
+            if b.shape not in ((3,), (n, 3)):
+                raise ValueError("%s must be one vector or one per interval (%d, 3), not %s" % (name, n, b.shape))
+            bias[k] = np.ascontiguousarray(np.broadcast_to(b, (n, 3)))
+    rows = np.zeros(max(n, 1), IMU_INTERVAL_DTYPE)
+    offsets = np.zeros(n + 1, np.int32)
+    if isinstance(stream_or_msgs, ImuStream):
+        ctx = stream_or_msgs._ctx if ctx is None else ctx
+
+        def call(smp, cap, pre, dq):
+            return lib().mml_imu_fetch_batch(ctx._h, stream_or_msgs._h, C.c_int(n), _p(ts), _p(te), _p(bias[0]), _p(bias[1]), _p(rows),
+                                             _p(offsets), _p(smp), C.c_long(cap), pre, _p(dq))
+    else:
+        msgs = _f64(stream_or_msgs).reshape(-1, 7)
+
+        def call(smp, cap, pre, dq):
+            return lib().mml_imu_fetch_host(_p(msgs) if len(msgs) else None, C.c_long(len(msgs)), C.c_int(n), _p(ts), _p(te), _p(bias[0]),
+                                            _p(bias[1]), _p(rows), _p(offsets), _p(smp), C.c_long(cap), pre, _p(dq))
+    out = dict(rows=rows[:n], offsets=offsets)
+    if not want:
+        return call(None, 0, None, None), out
+    if sample_capacity is None:
+        rc = call(None, 0, None, None)
+        if rc != MML_OK:
+            return rc, out
+        sample_capacity = int(offsets[n])
+    smp = np.zeros((max(int(sample_capacity), 1), 7)) if "samples" in want else None
+    pre = (ImuPreint * max(n, 1))() if "pre" in want else None
+    dq = np.zeros((max(n, 1), 4)) if "dq" in want else None
+    rc = call(smp, int(sample_capacity), pre, dq)
+    if rc == MML_OK:
+        if smp is not None:
+            out["samples"] = smp[:int(offsets[n])]
+        if pre is not None:
+            out["pre"] = pre
+        if dq is not None:
+            out["dq"] = dq[:n]
+    return rc, out
+
+
+def imu_fetch_batch(stream_or_msgs, t_start, t_end, bg=None, ba=None, ctx=None, want=("samples", "pre", "dq"), sample_capacity=None):
+    """fetchImuMsgs for n intervals (t_start[i], t_end[i]] in one call, with the pre-integration (bg, ba: one vector or one per
+    interval) and the gyro integration of what it cuts: imu_fetch_raw with the error check.  An ImuStream: the device call;
+    an (m, 7) array of messages: the host routine, bit-identical to it."""
+    rc, out = imu_fetch_raw(stream_or_msgs, t_start, t_end, bg, ba, ctx, want, sample_capacity)
+    if rc != MML_OK:
+        if isinstance(stream_or_msgs, ImuStream):
+            stream_or_msgs._ctx._ck(rc)
+        raise MmlError(rc, "mml_imu_fetch_host")
+    return out
+
+
+def imu_predict_batch(exTlb, prev=None, pre=None, dq=None, ctx=None):
+    """mml_imu_predict_batch: the frame prediction of the pose node for n intervals.  prev (n, 10: P, Q x y z w, V of the
+    previous frame) with pre (n ImuPreint, list or ctypes array): state (n, 10), delta_Rl (n, 3, 3), delta_tl (n, 3) -- the dR /
+    dt of Context.step / undistort; dq (n, 4): gyro_Rb, gyro_Rl (n, 3, 3), the bring-up branch.  ctx None: the host routine."""
+    ex = _f64(exTlb).reshape(4, 4)
+    out = {}
+    n = len(prev) if prev is not None else len(dq)
+    args = [None] * 5
+    if prev is not None:
+        pv = _f64(prev).reshape(n, 10)
+        arr = pre if isinstance(pre, C.Array) else (ImuPreint * n)(*pre)
+        out.update(state=np.zeros((n, 10)), delta_Rl=np.zeros((n, 3, 3)), delta_tl=np.zeros((n, 3)))
+        args = [_p(pv), arr, _p(out["state"]), _p(out["delta_Rl"]), _p(out["delta_tl"])]
+    gargs = [None] * 3
+    if dq is not None:
+        q = _f64(dq).reshape(n, 4)
+        out.update(gyro_Rb=np.zeros((n, 3, 3)), gyro_Rl=np.zeros((n, 3, 3)))
+        gargs = [_p(q), _p(out["gyro_Rb"]), _p(out["gyro_Rl"])]
+    rc = lib().mml_imu_predict_batch(ctx._h if ctx is not None else None, C.c_int(n), _p(ex), *(args + gargs))
+    if ctx is not None:
+        ctx._ck(rc)
+    elif rc != MML_OK:
+        raise MmlError(rc, "mml_imu_predict_batch")
+    return out
 
 
 def imu_factor(pre, gravity, pr_i, vb_i, pr_j, vb_j, jac=True):

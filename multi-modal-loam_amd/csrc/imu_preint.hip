@@ -24,6 +24,14 @@ __global__ __launch_bounds__(64) void k_imu_preintegrate(const double* samples, 
 
 }  // namespace
 
+// k_imu_preintegrate on arrays that are on the device already (mml_imu_fetch_batch's packed rows), asynchronous on the
+// context's stream; bias: n x (bg | ba).
+int mml_launch_imu_preintegrate(mml_ctx* ctx, int n, const double* d_samples, const int* d_offsets, const double* d_bias, mml_imu_preint* d_out) {
+    hipLaunchKernelGGL(k_imu_preintegrate, dim3(n), dim3(64), 0, MML_STREAM(ctx), d_samples, d_offsets, d_bias, d_out);
+    MML_HIP(hipGetLastError());
+    return MML_OK;
+}
+
 struct MmlPreintDev {  // each sized for the largest call seen
     MmlStaging<char> in;  // offsets | biases | samples, in bytes
     MmlStaging<mml_imu_preint> out;

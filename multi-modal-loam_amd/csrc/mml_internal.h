@@ -80,6 +80,7 @@ enum MmlSideId {
     MML_SIDE_VELO_FOV,     // velo_fov.hip MmlVfovDev: the blocks of the Velodyne FOV selection (single and batch calls)
     MML_SIDE_CALIB,        // calibrate.hip MmlCalibDev: the blocks of mml_cloud_crop_voxel / mml_aligner_calibrate
     MML_SIDE_FEATURE_CLOUDS,  // capi.hip MmlFeatCloudsDev: the table block of mml_feature_clouds_download_batch
+    MML_SIDE_IMU_FETCH,    // imu_stream.hip MmlImuFetchDev: the block of mml_imu_fetch_batch / mml_imu_predict_batch
     MML_SIDE_COUNT
 };
 
@@ -406,6 +407,8 @@ int mml_union_offset_check(mml_ctx* ctx, mml_livox_stream* s, int first_slot, in
                            const float* velo_xyzi, const int* velo_offsets, mml_union_frame* out);
 int mml_union_offset_run(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int count, const uint64_t* starts, int sliced_points,
                          const float* velo_xyzi, const int* velo_offsets, const float* tf, mml_union_frame* out);
+// imu_preint.hip: k_imu_preintegrate on device arrays (bias: n x (bg | ba)), asynchronous on the current stream
+int mml_launch_imu_preintegrate(mml_ctx* ctx, int n, const double* d_samples, const int* d_offsets, const double* d_bias, mml_imu_preint* d_out);
 int mml_launch_detect_line(mml_ctx* ctx, int n, uint16_t* d_final);
 int mml_launch_raw_lines(mml_ctx* ctx, int first, int count);  // raw_line[] of the slots (ring / line id per raw point), for the GICP refresh
 int mml_launch_linearize(mml_ctx* ctx, int slot, const double* d_x, const double* d_Tbl, double w_tan,

@@ -1080,6 +1080,90 @@ class LivoxPointQueue {
     std::vector<mml_union_frame> frames_;
 };
 
+// ---- the pose node's IMU queue (unionPoseEstimation.cpp: _imuMsgVector) --------------------------------------------------------
+// push is imuHandler's push_back (:296); fetchImuMsgs (:307-395) cuts (startTime, endTime] out of the queue, the message
+// synthesised at endTime included, and returns the reference's bool (true iff the status is 0, as :394).  A message is 7
+// doubles: header.stamp.toSec(), angular_velocity xyz, linear_acceleration xyz; vimuMsg comes back as rows of 7 doubles in the
+// shape IMUIntegrator below takes (gyro xyz, accel xyz, dt with lastTime = startTime).  last_interval() tells why a call came
+// back false (mml_imu_interval.status; NO_SAMPLE, which the reference leaves undefined, is defined in include/mmloam_hip.h).
+// With a Context the queue is a mml_imu_stream in device memory and the batch form is ONE mml_imu_fetch_batch call; without one
+// it is a host vector and the calls run mml_imu_fetch_host, bit-identical to it.  Unlike the reference's, fetchImuMsgs does
+// not trim the queue: drop_before is :383-390 (t = min(_time_last_hori, _time_last_velo), keep_min = 200).
+class ImuQueue {
+   public:
+    ImuQueue() = default;
+    ImuQueue(Context& ctx, long capacity_msgs) : ctx_(&ctx) {
+        check(ctx.get(), mml_imu_stream_create(ctx.get(), capacity_msgs, &s_), "mml_imu_stream_create");
+    }
+    ~ImuQueue() { mml_imu_stream_destroy(s_); }
+    ImuQueue(const ImuQueue&) = delete;
+    ImuQueue& operator=(const ImuQueue&) = delete;
+    mml_imu_stream* get() const { return s_; }
+
+    // one message (7 doubles) or n of them.  On a device queue the buffer must stay valid until the next synchronising call.
+    void push(const double* msg, int n = 1) {
+        if (s_)
+            check(ctx_->get(), mml_imu_stream_push(s_, msg, n), "mml_imu_stream_push");
+        else
+            host_.insert(host_.end(), msg, msg + 7 * (size_t)n);
+    }
+    bool fetchImuMsgs(double startTime, double endTime, std::vector<double>& vimuMsg) {
+        const std::vector<bool> ok = fetchImuMsgs(std::vector<double>{startTime}, std::vector<double>{endTime});
+        vimuMsg = samples_;
+        return ok[0];
+    }
+    // n intervals in one call: interval i's rows are last_samples() rows last_offsets()[i] .. last_offsets()[i + 1] - 1.
+    std::vector<bool> fetchImuMsgs(const std::vector<double>& startTimes, const std::vector<double>& endTimes) {
+        if (startTimes.empty() || startTimes.size() != endTimes.size()) throw std::runtime_error("fetchImuMsgs: one start and one end per interval");
+        const int n = (int)startTimes.size();
+        rows_.resize((size_t)n);
+        offsets_.assign((size_t)n + 1, 0);
+        samples_.clear();
+        call(n, startTimes.data(), endTimes.data(), nullptr, 0);   // the sizing call
+        samples_.resize(7 * (size_t)offsets_[(size_t)n]);
+        if (!samples_.empty()) call(n, startTimes.data(), endTimes.data(), samples_.data(), offsets_[(size_t)n]);
+        std::vector<bool> ok((size_t)n);
+        for (int i = 0; i < n; ++i) ok[(size_t)i] = rows_[(size_t)i].status == 0;
+        return ok;
+    }
+    void drop_before(double t, long keep_min = 200) {
+        if (s_) {
+            check(ctx_->get(), mml_imu_stream_drop_before(s_, t, keep_min), "mml_imu_stream_drop_before");
+            return;
+        }
+        size_t front = 0;
+        while ((long)(host_.size() / 7 - front) > keep_min && host_[7 * front] < t) ++front;
+        host_.erase(host_.begin(), host_.begin() + (std::ptrdiff_t)(7 * front));
+    }
+    long size() {
+        if (!s_) return (long)(host_.size() / 7);
+        mml_imu_stream_state st;
+        check(ctx_->get(), mml_imu_stream_state_get(s_, &st), "mml_imu_stream_state_get");
+        return st.tail - st.front;
+    }
+    const std::vector<mml_imu_interval>& last_intervals() const { return rows_; }
+    const mml_imu_interval& last_interval() const { return rows_.back(); }
+    const std::vector<double>& last_samples() const { return samples_; }
+    const std::vector<int>& last_offsets() const { return offsets_; }
+
+   private:
+    void call(int n, const double* ts, const double* te, double* samples, long cap) {
+        if (s_)
+            check(ctx_->get(), mml_imu_fetch_batch(ctx_->get(), s_, n, ts, te, nullptr, nullptr, rows_.data(), offsets_.data(), samples, cap, nullptr, nullptr),
+                  "mml_imu_fetch_batch");
+        else
+            check(nullptr, mml_imu_fetch_host(host_.data(), (long)(host_.size() / 7), n, ts, te, nullptr, nullptr, rows_.data(), offsets_.data(), samples,
+                                              cap, nullptr, nullptr),
+                  "mml_imu_fetch_host");
+    }
+    Context* ctx_ = nullptr;
+    mml_imu_stream* s_ = nullptr;
+    std::vector<double> host_;
+    std::vector<mml_imu_interval> rows_;
+    std::vector<double> samples_;
+    std::vector<int> offsets_;
+};
+
 // ---- IMUIntegrator (IMUIntegrator.h / IMUIntegrator.cpp) over the caller's messages ----------------------------------------
 // A message is 7 doubles: angular_velocity xyz, linear_acceleration xyz (units of g, as the Livox IMU reports them), dt to the
 // previous message (the stamp difference the reference forms from lastTime, :95-97, :122).  Reset() keeps the messages, as

@@ -345,6 +345,45 @@ def preintegrate_windows(samples, frames, ctx=None):
     return [[None] + [next(pres) for _ in range(1, len(fw))] for fw in frames]
 
 
+def fetch_imu_windows(stream_or_msgs, stamps_per_window, frames, ctx=None):
+    """preintegrate_windows from raw IMU messages: fetchImuMsgs and the pre-integration of every frame interval of n windows in
+    ONE imu_fetch_batch call.  stream_or_msgs: an ImuStream (the device call) or an (m, 7) array of messages (the host routine,
+    bit-identical to it); stamps_per_window[w]: the stamps of window w's frames, optionally with one more in front (the stamp
+    before frame 0, which then gets its messages too; otherwise samples[w][0] is empty).  Frame f's interval is
+    (stamp[f-1], stamp[f]], linearised at frames[w][f-1]["bg"] / ["ba"] (frame 0: its own).  Returns (samples, preints):
+    samples[w][f] a (k, 7) array, preints[w][0] None and preints[w][f] an ImuPreint -- the shapes preintegrate_windows,
+    BatchWindowEstimator.estimate and try_map_initialization_batch take.  An interval that is not cut (any status but 0) raises
+    ValueError naming the window, the frame and the status."""
+    import importlib
+    M = importlib.import_module(__package__)
+    if len(stamps_per_window) != len(frames):
+        raise ValueError("stamps_per_window and frames must have one entry per window (%d, %d)" % (len(stamps_per_window), len(frames)))
+    ts, te, bg, ba, where = [], [], [], [], []
+    for w, (sw, fw) in enumerate(zip(stamps_per_window, frames)):
+        lead = len(sw) - len(fw)
+        if lead not in (0, 1):
+            raise ValueError("window %d: %d stamps for %d frames" % (w, len(sw), len(fw)))
+        for f in range(1 - lead, len(fw)):
+            ts.append(sw[f + lead - 1])
+            te.append(sw[f + lead])
+            bg.append(fw[max(f - 1, 0)]["bg"])
+            ba.append(fw[max(f - 1, 0)]["ba"])
+            where.append((w, f))
+    samples = [[np.zeros((0, 7)) for _ in fw] for fw in frames]
+    preints = [[None] * len(fw) for fw in frames]
+    if not where:
+        return samples, preints
+    out = M.imu_fetch_batch(stream_or_msgs, ts, te, np.stack(bg), np.stack(ba), ctx, want=("samples", "pre"))
+    o = out["offsets"]
+    for i, (w, f) in enumerate(where):
+        if out["rows"]["status"][i] != M.IMU_FETCH_OK:
+            raise ValueError("window %d, frame %d: the interval (%r, %r] is not cut: status %d" % (w, f, ts[i], te[i], out["rows"]["status"][i]))
+        samples[w][f] = out["samples"][o[i]:o[i + 1]].copy()
+        if f >= 1:
+            preints[w][f] = M.ImuPreint.from_buffer_copy(out["pre"][i])
+    return samples, preints
+
+
 def try_map_initialization(frames, samples, exTlb=None):
     """TryMAPInitialization (unionPoseEstimation.cpp:425-625) through mml_lio_initialize.  frames: the reference's frame
     list, front first, as dicts in the shape WindowEstimator.estimate uses (P, Q as x y z w = the lidar pose, V, bg, ba)
