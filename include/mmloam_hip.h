@@ -124,7 +124,8 @@ int mml_scan_download_pointxyzinormal(mml_ctx* ctx, int slot, uint8_t* out, int 
  * by livox_combine; the first n_velo are the Velodyne part), decoded on the device: normal_x -> in-sweep time,
  * normal_y -> ring / line, normal_z -> label by abs(normal_z - k) < 1e-5 (Estimator.cpp:995-1003; anything else 0),
  * intensity kept.  Afterwards the slot is in the state mml_extract leaves (mml_scan_info_get, mml_undistort,
- * mml_downsample, mml_estimate work on it); livox_*_num count the kept points only.  Synchronous. */
+ * mml_downsample, mml_estimate work on it); livox_*_num count the kept points only.  Synchronous.
+ * (`count` whole union_cloud messages in one call, the merge decision of :741-773 included: mml_pose_ingest_batch below.) */
 int mml_cloud_upload(mml_ctx* ctx, int slot, const uint8_t* pointxyzinormal, int n_points, int n_velo);
 
 /* The registered cloud: the fused cloud of `count` slots moved into the world frame, the payload of /velo_full_cloud_mapped
@@ -1017,6 +1018,64 @@ int mml_imu_fetch_host(const double* msgs, long n_msgs, int n, const double* t_s
  * or neither group. */
 int mml_imu_predict_batch(mml_ctx* ctx, int n, const double* exTlb, const double* prev, const mml_imu_preint* pre,
         double* state, double* delta_Rl, double* delta_tl, const double* dq, double* gyro_Rb, double* gyro_Rl);
+
+/* ---- the pose node's way in: `count` union_cloud messages into scan slots in one call --------------------------------------
+ * mml_cloud_upload for `count` messages at once, with the decision the pose node takes per message
+ * (unionPoseEstimation.cpp:719-773) taken by the library: the mirror image of mml_feature_clouds_download_batch.  `clouds` /
+ * `n_points` (count x 6) are exactly what that call returns -- slot-major, six clouds per frame in union_cloud.msg order, 48-byte
+ * records, contiguous; only clouds 2 (velo_combine) and 5 (livox_combine) are read as points, and n_points[6 i + 3] is the
+ * frame's livox_corner_num.  `rows` are the rows mml_imu_fetch_batch writes for the frames' intervals (n, front_gyro_z and
+ * back_gyro_z are read), or NULL for IMU_Mode == 0, where vimuMsg stays empty.  Frame i goes to slot first_slot + i.
+ * THE RULES (csrc/pose_ingest.h, one routine; the device call's decisions are computed on the host by the very routine behind
+ * mml_pose_ingest_plan -- the device only decodes).  For frame i, in this order:
+ *   DROPPED    rows given and rows[i].n == 0: fetchImuMsgs returns !vimuMsg.empty(), the reference retries, pops the message and
+ *              continues (:719-730).  The slot is not touched at all; n_points = n_velo = 0; reason = MML_INGEST_WHY_FETCH + the
+ *              row's fetch status.  (A dropped frame does not pass `first_frame` on: the caller names the first frame.)
+ *   VELO_ONLY  without the gate: rows == NULL (reason NO_IMU), or i == opts->first_frame (first_velo_frame, :741, :838-839;
+ *              reason FIRST_FRAME).  fast_rotation = 0.
+ *   otherwise (:746-773), abs being std::abs(double) -- the reference's unqualified call, DESIGN.md section 2 convention 14:
+ *     MERGED iff !velo_only_mode && (abs(front_gyro_z) < hori_rotate_th || abs(back_gyro_z) < hori_rotate_th) &&
+ *     livox_corner_num > 100; else VELO_ONLY with the first failing test of that order as the reason (VELO_ONLY_MODE,
+ *     FAST_ROTATION, FEW_CORNERS).  fast_rotation = abs(front) > velo_rotate_th || abs(back) > velo_rotate_th (:771), whatever
+ *     the decision.  A NaN gyro value fails every comparison, as in the reference.
+ * A MERGED slot holds velo_combine followed by livox_combine (:756); a VELO_ONLY slot velo_combine alone (n_velo == n_points).
+ * The row's n_points / n_velo are what went into the slot.  Afterwards a slot is in the state mml_cloud_upload leaves, byte for
+ * byte, and a dropped frame's slot -- its host-side state too -- is as it was.
+ * Work per call, whatever `count` is: one host-to-device copy of the block, one table upload (32 bytes per frame), one launch of
+ * the decode kernel over all frames (records loaded as whole 16-byte words, turned into points through LDS), one launch of the
+ * label-list kernel over the run of slots -- one per run of adjacent slots when dropped frames split it -- and ONE host
+ * synchronisation.  Synchronous like mml_cloud_upload.
+ * Everything is checked before anything is enqueued, the message names the frame, and a refusal writes nothing, on the host or on
+ * the device: MML_ERR_INVALID for a slot range outside the context, count < 1 or above 65535, NULL n_points / opts / out, NULL
+ * clouds with a non-zero total, a negative count (in n_points or rows[i].n), first_frame outside -1 .. count-1;
+ * MML_ERR_CAPACITY for a frame whose Velodyne part exceeds max_velo_points or whose MERGED Livox part exceeds max_livox_points (a
+ * Livox cloud that is not taken is not measured).  The context keeps a device and a pinned table block for the largest call it
+ * has seen, released by mml_destroy. */
+typedef struct {
+    double hori_rotate_th, velo_rotate_th;  /* 0.3, 1.5: unionPoseEstimation.cpp:146-147 (main() falls back to 0.5 for the
+                                               first when ~hori_rotate_threshold is not set, :1405-1406) */
+    int velo_only_mode;                     /* 0 (:85) */
+    int first_frame;                        /* index of the frame that meets first_velo_frame == true, -1: none */
+} mml_pose_ingest_opts;
+void mml_pose_ingest_opts_default(mml_pose_ingest_opts* opts);
+enum { MML_INGEST_VELO_ONLY = 0, MML_INGEST_MERGED = 1, MML_INGEST_DROPPED = 2 };   /* mml_pose_ingest_row.decision */
+enum {                                                                              /* mml_pose_ingest_row.reason */
+    MML_INGEST_WHY_MERGED = 0,          /* every test of :746-748 passed */
+    MML_INGEST_WHY_NO_IMU = 1,          /* rows == NULL: vimuMsg.empty() at :741 */
+    MML_INGEST_WHY_FIRST_FRAME = 2,     /* first_velo_frame at :741 */
+    MML_INGEST_WHY_VELO_ONLY_MODE = 3,  /* :746, :767 */
+    MML_INGEST_WHY_FAST_ROTATION = 4,   /* :747, :763-765 */
+    MML_INGEST_WHY_FEW_CORNERS = 5,     /* :748, :760-761 */
+    MML_INGEST_WHY_FETCH = 16           /* DROPPED: + rows[i].status, the fetch status 0 .. 5 of mml_imu_fetch_batch */
+};
+typedef struct { int decision, reason, fast_rotation, n_points, n_velo, _pad; } mml_pose_ingest_row;
+/* Host only, no context: the decisions alone (and the counts they imply).  The argument checks of the device call that need no
+ * context; no capacity is checked. */
+int mml_pose_ingest_plan(int count, const int* n_points /* count x 6 */, const mml_imu_interval* rows /* count or NULL */,
+                         const mml_pose_ingest_opts* opts, mml_pose_ingest_row* out /* count */);
+int mml_pose_ingest_batch(mml_ctx* ctx, int first_slot, int count, const uint8_t* clouds, const int* n_points /* count x 6 */,
+                          const mml_imu_interval* rows /* count or NULL */, const mml_pose_ingest_opts* opts,
+                          mml_pose_ingest_row* out /* count */);
 
 /* Number of HIP streams mml_step pipelines its sub-batches over (1..8, default 2 or $MML_LANES).  With 1 every
  * kernel covers the whole batch and runs alone on the device, which is what per-kernel timing wants. */

@@ -36,6 +36,7 @@ FOV_BATCH_MAX = 65535     # MML_FOV_BATCH_MAX: frames per call of mml_velo_fov_s
 FOV_TILE_POINTS = 256     # VFOV_BLOCK (csrc/velo_fov.hip): points one workgroup pass of the selection kernel takes
 FOV_REG_POINTS = 4096     # VFOV_REG_POINTS: frames above this park their azimuths in scratch between the phases
 IMU_FETCH_BATCH_MAX = 8192  # MML_IMU_FETCH_BATCH_MAX: intervals per call of mml_imu_fetch_batch / mml_imu_predict_batch
+POSE_INGEST_MAX = 65535     # frames per call of mml_pose_ingest_batch / mml_pose_ingest_plan
 # mml_imu_interval.status (csrc/imu_fetch.h)
 IMU_FETCH_OK, IMU_FETCH_EMPTY, IMU_FETCH_NOT_REACHED, IMU_FETCH_TOO_OLD, IMU_FETCH_REVERSED, IMU_FETCH_NO_SAMPLE = 0, 1, 2, 3, 4, 5
 UNION_OK, UNION_EMPTY, UNION_NOT_REACHED, UNION_NO_POINTS, UNION_OVERFLOW = 0, 1, 2, 3, 4   # mml_union_frame.status
@@ -57,6 +58,13 @@ POINTXYZINORMAL_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("da
 ASSIGN_BLOCK_POINTS = 4096
 # the clouds of union_cloud.msg:4-9, in the message's order: the cloud index of mml_feature_clouds_download_batch
 FEATURE_CLOUD_NAMES = ("velo_corner", "velo_surface", "velo_combine", "livox_corner", "livox_surface", "livox_combine")
+# mml_pose_ingest_row, and the values of its decision / reason fields (include/mmloam_hip.h)
+POSE_INGEST_ROW_DTYPE = np.dtype([("decision", "<i4"), ("reason", "<i4"), ("fast_rotation", "<i4"), ("n_points", "<i4"), ("n_velo", "<i4"),
+                                  ("_pad", "<i4")])
+INGEST_VELO_ONLY, INGEST_MERGED, INGEST_DROPPED = 0, 1, 2
+(INGEST_WHY_MERGED, INGEST_WHY_NO_IMU, INGEST_WHY_FIRST_FRAME, INGEST_WHY_VELO_ONLY_MODE, INGEST_WHY_FAST_ROTATION,
+ INGEST_WHY_FEW_CORNERS) = range(6)
+INGEST_WHY_FETCH = 16   # DROPPED: + the row's fetch status
 # mml_velo_fov_info
 VELO_FOV_INFO_DTYPE = np.dtype([("start_ori", "<f4"), ("end_ori", "<f4"), ("half_index", "<i4"), ("n_kept", "<i4")])
 
@@ -176,6 +184,10 @@ class GicpDebug(C.Structure):
 class CalibInfo(C.Structure):
     _fields_ = [("n_hori_in", C.c_int), ("n_velo_in", C.c_int), ("n_hori_ds", C.c_int), ("n_velo_ds", C.c_int),
                 ("hori_unfiltered", C.c_int), ("velo_unfiltered", C.c_int), ("gicp", GicpInfo)]
+
+
+class PoseIngestOpts(C.Structure):
+    _fields_ = [("hori_rotate_th", C.c_double), ("velo_rotate_th", C.c_double), ("velo_only_mode", C.c_int), ("first_frame", C.c_int)]
 
 
 class Profile(C.Structure):
@@ -345,6 +357,13 @@ def lib():
             L.mml_imu_fetch_host.argtypes = [C.c_void_p, C.c_long, C.c_int] + [C.c_void_p] * 7 + [C.c_long] + [C.c_void_p] * 2
             L.mml_imu_predict_batch.restype = C.c_int
             L.mml_imu_predict_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 9
+        if hasattr(L, "mml_pose_ingest_batch"):
+            L.mml_pose_ingest_opts_default.restype = None
+            L.mml_pose_ingest_opts_default.argtypes = [C.c_void_p]
+            L.mml_pose_ingest_plan.restype = C.c_int
+            L.mml_pose_ingest_plan.argtypes = [C.c_int] + [C.c_void_p] * 4
+            L.mml_pose_ingest_batch.restype = C.c_int
+            L.mml_pose_ingest_batch.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
         _lib = L
     return _lib
 
@@ -881,6 +900,18 @@ class Context:
         nv = len(rec) if n_velo is None else int(n_velo)
         self._ck(lib().mml_cloud_upload(self._h, C.c_int(slot), _p(rec) if len(rec) else None, C.c_int(len(rec)), C.c_int(nv)))
 
+    def pose_ingest(self, first_slot, clouds, n_points=None, rows=None, **opts):
+        """mml_pose_ingest_batch: n union_cloud messages into slots first_slot .. in ONE call, with the pose node's decision per
+        message (merge the Livox cloud or not, fast rotation, the frame dropped for want of IMU messages).  `clouds`: the list of
+        six-array tuples Context.feature_clouds returns, or the raw block (records as POINTXYZINORMAL_DTYPE, (n, 12) float32 or
+        bytes) with n_points (n, 6).  rows: the IMU_INTERVAL_DTYPE rows of imu_fetch_batch, or None (IMU_Mode 0).  opts:
+        hori_rotate_th, velo_rotate_th, velo_only_mode, first_frame.  Returns the rows (POSE_INGEST_ROW_DTYPE)."""
+        block, n, r, o = pose_ingest_pack(clouds, n_points, rows, opts)
+        out = np.zeros(max(len(n), 1), POSE_INGEST_ROW_DTYPE)
+        self._ck(lib().mml_pose_ingest_batch(self._h, C.c_int(first_slot), C.c_int(len(n)), _p(block) if block.size else None, _p(n), _p(r),
+                                             C.byref(o), _p(out)))
+        return out[:len(n)]
+
     def gicp_align(self, src, tgt, T0=None):
         """icp_ext_matching on plain clouds: returns (converged, T 4x4 float32, GicpInfo)."""
         src = _f32(src).reshape(-1, 3)
@@ -1306,6 +1337,50 @@ class Context:
         g = C.c_double(0)
         self._ck(lib().mml_copy_bandwidth(self._h, C.c_size_t(nbytes), C.c_int(reps), C.byref(g)))
         return g.value
+
+
+def pose_ingest_opts(**over):
+    """mml_pose_ingest_opts with the reference's defaults (0.3, 1.5, velo_only_mode 0, first_frame -1), then `over`."""
+    o = PoseIngestOpts()
+    lib().mml_pose_ingest_opts_default(C.byref(o))
+    for k, v in over.items():
+        if k not in ("hori_rotate_th", "velo_rotate_th", "velo_only_mode", "first_frame"):
+            raise TypeError("unknown ingest option %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+def pose_ingest_pack(clouds, n_points=None, rows=None, opts=None):
+    """The arguments of mml_pose_ingest_batch from what the wrappers hand out: (block uint8, n_points (n, 6) int32, rows or
+    None, PoseIngestOpts).  A list of six-array tuples is concatenated into the block; a block is taken as it is."""
+    if n_points is None:
+        msgs = [tuple(np.ascontiguousarray(c).view(np.uint8).reshape(-1, 48) for c in six) for six in clouds]
+        if any(len(six) != 6 for six in msgs):
+            raise ValueError("a message is six clouds (FEATURE_CLOUD_NAMES)")
+        n = np.array([[len(c) for c in six] for six in msgs], np.int32).reshape(-1, 6)
+        parts = [c for six in msgs for c in six if len(c)]
+        block = np.concatenate(parts) if parts else np.zeros((0, 48), np.uint8)
+    else:
+        n = np.ascontiguousarray(n_points, dtype=np.int32).reshape(-1, 6)
+        block = np.ascontiguousarray(clouds).view(np.uint8).reshape(-1) if clouds is not None else np.zeros(0, np.uint8)
+        if clouds is not None and (n >= 0).all() and block.size != 48 * int(n.sum()):
+            raise ValueError("the block holds %d bytes, n_points announces %d records" % (block.size, int(n.sum())))
+    r = None
+    if rows is not None:
+        r = np.ascontiguousarray(rows, dtype=IMU_INTERVAL_DTYPE).reshape(-1)
+        if len(r) != len(n):
+            raise ValueError("%d fetch rows for %d messages" % (len(r), len(n)))
+    return np.ascontiguousarray(block), n, r, pose_ingest_opts(**(opts or {}))
+
+
+def pose_ingest_plan(n_points, rows=None, **opts):
+    """mml_pose_ingest_plan: the decisions of Context.pose_ingest alone, on the host (the same routine).  n_points (n, 6)."""
+    _, n, r, o = pose_ingest_pack(None, n_points, rows, opts)
+    out = np.zeros(max(len(n), 1), POSE_INGEST_ROW_DTYPE)
+    rc = lib().mml_pose_ingest_plan(C.c_int(len(n)), _p(n), _p(r), C.byref(o), _p(out))
+    if rc != MML_OK:
+        raise MmlError(rc, "mml_pose_ingest_plan")
+    return out[:len(n)]
 
 
 class ImuPreint(C.Structure):

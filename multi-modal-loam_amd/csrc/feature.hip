@@ -215,6 +215,9 @@ struct AssignAux {  // per slot, written by passes A / B
     float startOri, endOri;
     int kept_livox, pad;
 };
+static_assert(sizeof(AssignAux) == sizeof(int) * MML_AUX_INTS && offsetof(AssignAux, kept_velo) == sizeof(int) * MML_AUX_KEPT_VELO &&
+                  offsetof(AssignAux, kept_livox) == sizeof(int) * MML_AUX_KEPT_LIVOX,
+              "mml_internal.h names the two counts for pose_ingest.hip");
 // lidars_extrinsic_cali.h:424-477: removeNearFarPoints keeps near <= |p|^2 <= far, removeNearPointCloud only tests near
 __device__ __forceinline__ void crop_test(const FeatParams& P, float x, float y, float z, bool& keep, bool& near_ok) {
     const float near2 = P.near_th * P.near_th, far2 = P.far_th * P.far_th;
@@ -4190,6 +4193,15 @@ int mml_launch_cloud_decode(mml_ctx* ctx, int slot, const float* d_raw, int n, i
     const int lab_words = (ctx->NT + 3) / 4;
     const int lds_words = lab_words <= MML_CROP_WORDS ? lab_words : MML_CROP_WORDS;
     hipLaunchKernelGGL(k_crop, dim3(1), dim3(CROP_THREADS), sizeof(uint32_t) * (size_t)lds_words, s, P, ctx->VX_CAP, lds_words);
+    MML_HIP(hipGetLastError());
+    return MML_OK;
+}
+
+int mml_launch_cloud_lists(mml_ctx* ctx, int first, int count) {
+    FeatParams P = make_params(ctx, first);
+    const int lab_words = (ctx->NT + 3) / 4;
+    const int lds_words = lab_words <= MML_CROP_WORDS ? lab_words : MML_CROP_WORDS;
+    hipLaunchKernelGGL(k_crop, dim3(count), dim3(CROP_THREADS), sizeof(uint32_t) * (size_t)lds_words, MML_STREAM(ctx), P, ctx->VX_CAP, lds_words);
     MML_HIP(hipGetLastError());
     return MML_OK;
 }

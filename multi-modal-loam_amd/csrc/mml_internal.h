@@ -81,6 +81,7 @@ enum MmlSideId {
     MML_SIDE_CALIB,        // calibrate.hip MmlCalibDev: the blocks of mml_cloud_crop_voxel / mml_aligner_calibrate
     MML_SIDE_FEATURE_CLOUDS,  // capi.hip MmlFeatCloudsDev: the table block of mml_feature_clouds_download_batch
     MML_SIDE_IMU_FETCH,    // imu_stream.hip MmlImuFetchDev: the block of mml_imu_fetch_batch / mml_imu_predict_batch
+    MML_SIDE_POSE_INGEST,  // pose_ingest.hip MmlPoseIngestDev: the table block of mml_pose_ingest_batch
     MML_SIDE_COUNT
 };
 
@@ -362,6 +363,12 @@ struct MmlStageScope {
 // launchers implemented in the .hip files (all asynchronous on ctx->stream)
 int mml_launch_extract(mml_ctx* ctx, int first, int count, bool have_extrinsic);
 int mml_launch_cloud_decode(mml_ctx* ctx, int slot, const float* d_raw, int n, int n_velo);
+// the second half of mml_launch_cloud_decode for `count` slots that a decode kernel has filled: ONE k_crop launch, a workgroup per slot
+int mml_launch_cloud_lists(mml_ctx* ctx, int first, int count);
+// where the two point counts k_crop reads sit in a slot's 8 ints of assign_aux (feature.hip AssignAux, asserted there)
+#define MML_AUX_INTS 8
+#define MML_AUX_KEPT_VELO 3
+#define MML_AUX_KEPT_LIVOX 6
 int mml_launch_undistort(mml_ctx* ctx, int first, int count, const double* d_params);
 // mml_step's form: the points on the slots' label lists only; the slots become partly undistorted (mml_ctx::und_pending)
 int mml_launch_undistort_listed(mml_ctx* ctx, int first, int count, const double* d_params);

@@ -731,6 +731,36 @@ class Estimator {
         return total;
     }
 
+    // The pose node's way in for a replay (unionPoseEstimation.cpp:679-688, :719-773): the messages of `msgs.size()` frames
+    // into slots first_slot ..., packed into one block and handed over in ONE mml_pose_ingest_batch call, which also takes
+    // the node's decision per message -- merge livox_combine or not, detected_fast_rotation, the frame dropped because
+    // fetchImuMsgs returned nothing.  rows: what ImuQueue's fetch wrote for the frames' intervals, or nullptr (IMU_Mode 0).
+    // A frame's livox_corner_num is the size of its livox_corner cloud, as in the feature node's message.  Returns one row per
+    // frame; the slots of the frames that were not dropped are ready for RemoveLidarDistortion / EstimateLidarPose.
+    std::vector<mml_pose_ingest_row> IngestUnionClouds(int first_slot, const std::vector<UnionFeatureClouds>& msgs, const mml_imu_interval* rows,
+                                                       const mml_pose_ingest_opts& opts) {
+        const size_t n = msgs.size();
+        std::vector<int> np(6 * (n ? n : 1), 0);
+        size_t total = 0;
+        for (size_t i = 0; i < n; ++i) {
+            const PointCloud* c[6] = {&msgs[i].velo_corner,  &msgs[i].velo_surface,  &msgs[i].velo_combine,
+                                      &msgs[i].livox_corner, &msgs[i].livox_surface, &msgs[i].livox_combine};
+            for (int k = 0; k < 6; ++k) total += (size_t)(np[6 * i + k] = (int)c[k]->size());
+        }
+        PointCloud block;
+        block.reserve(total);
+        for (const UnionFeatureClouds& m : msgs)
+            for (const PointCloud* c : {&m.velo_corner, &m.velo_surface, &m.velo_combine, &m.livox_corner, &m.livox_surface, &m.livox_combine})
+                block.insert(block.end(), c->begin(), c->end());
+        std::vector<mml_pose_ingest_row> out(n ? n : 1);
+        check(ctx_.get(),
+              mml_pose_ingest_batch(ctx_.get(), first_slot, (int)n, total ? reinterpret_cast<const uint8_t*>(block.data()) : nullptr, np.data(), rows,
+                                    &opts, out.data()),
+              "mml_pose_ingest_batch");
+        out.resize(n);
+        return out;
+    }
+
    private:
     mml_assoc_stats associate(int slot, const Matrix4d& m4d) {
         mml_assoc_stats st;

@@ -384,6 +384,21 @@ def fetch_imu_windows(stream_or_msgs, stamps_per_window, frames, ctx=None):
     return samples, preints
 
 
+def ingest_union_clouds(ctx, first_slot, messages, imu_rows=None, n_points=None, **opts):
+    """The pose node's way in for a replay: the union_cloud messages of n frames (`messages`: what Context.feature_clouds
+    returns, or the raw block with n_points (n, 6)) into slots first_slot .. first_slot + n - 1 with ONE Context.pose_ingest
+    call, which also takes the node's decision per message (unionPoseEstimation.cpp:719-773).  imu_rows: out["rows"] of
+    imu_fetch_batch for the frames' intervals, or None without an IMU.  opts: hori_rotate_th, velo_rotate_th, velo_only_mode,
+    first_frame.  Returns (rows, slots): the POSE_INGEST_ROW_DTYPE rows and the slots that hold a frame (the dropped ones left
+    out) -- what imu_predict_batch's dR / dt and then Context.undistort / step are to be called for; consecutive slots make one
+    call."""
+    import importlib
+    M = importlib.import_module(__package__)
+    rows = ctx.pose_ingest(first_slot, messages, n_points, imu_rows, **opts)
+    slots = [first_slot + i for i in range(len(rows)) if rows["decision"][i] != M.INGEST_DROPPED]
+    return rows, slots
+
+
 def try_map_initialization(frames, samples, exTlb=None):
     """TryMAPInitialization (unionPoseEstimation.cpp:425-625) through mml_lio_initialize.  frames: the reference's frame
     list, front first, as dicts in the shape WindowEstimator.estimate uses (P, Q as x y z w = the lidar pose, V, bg, ba)
