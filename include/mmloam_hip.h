@@ -1136,6 +1136,25 @@ enum {
 #define MML_TR_DIGEST_INTS 16
 int mml_debug_tr_replay(mml_ctx* ctx, int variant, int n, int rounds_max, const int* hdr, const double* x0, const double* records,
                         double* xc, double* digest, int* digest_i);
+/* Test hook: the trust-region state machine of the full-window (IMU_Mode 2) solve replayed on n scripts of normal equations
+ * given in advance (open loop), the full-window analogue of mml_debug_tr_replay with its round semantics and its codes.
+ * hdr: n x 4 (W 1..8, fixed 0/1, max_iters 0..1000, R 1..MML_FW_REPLAY_ROUNDS_MAX); x0: n x 120 (the first 15 W used).  Rounds are
+ * packed raggedly: round r of script s starts at rounds[offsets[s] + r (46 m + 1)], m = 15 W, and holds the band of H as k_fw_step
+ * keeps it (m x 45: row a, band column c stands for column 15 (a / 15 - 1) + c; band columns outside 0 .. m - 1 are ignored),
+ * g (m) and the cost.  rounds_len: the doubles in rounds.  Refused with MML_ERR_INVALID before anything is allocated or launched:
+ * n outside 0..MML_FW_REPLAY_SCRIPTS_MAX, a header value out of range, a null array, a script that does not lie inside rounds,
+ * more than 64 MB of rounds, variant 1 without a context.
+ * variant 0: the host's propose / decide and the initialisation of mml_fullwindow_step (csrc/window_imu.hip; ctx may be NULL), the
+ * dense H being the band with exact zeros outside it;  1: the device's fw_round -- what k_fw_step runs once the equations are
+ * assembled: initialisation, fw_decide, fw_propose with fw_factor_solve -- one workgroup per script.
+ * Outputs are per round, the rounds of script s at rows sum(R of the scripts before s) + r: xc (rows x 120: the candidate, or x
+ * once stopped), digest (rows x MML_FW_DIGEST_DOUBLES: cost, radius, mu, alpha, dogleg_norm, model_change, step_norm, x_norm,
+ * x[120]) and digest_i (rows x MML_TR_DIGEST_INTS, the layout and the codes of mml_debug_tr_replay). */
+#define MML_FW_DIGEST_DOUBLES 128
+#define MML_FW_REPLAY_ROUNDS_MAX 256
+#define MML_FW_REPLAY_SCRIPTS_MAX 1024
+int mml_debug_fw_replay(mml_ctx* ctx, int variant, int n, const int* hdr, const double* x0, const long long* offsets,
+                        const double* rounds, long long rounds_len, double* xc, double* digest, int* digest_i);
 /* Test hook: the pieces of the device's GICP (csrc/gicp.hip) on caller-supplied inputs -- the kernels and __device__ functions the
  * alignments run, not copies.  Clouds are n x 3 floats, covariances and Mahalanobis matrices n x 9 doubles (row-major 3 x 3),
  * a state is x = (t, roll, pitch, yaw) in 6 doubles, T is a row-major 4 x 4 float matrix.  By operation code:

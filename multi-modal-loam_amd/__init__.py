@@ -286,6 +286,9 @@ def lib():
         if hasattr(L, "mml_debug_tr_replay"):
             L.mml_debug_tr_replay.restype = C.c_int
             L.mml_debug_tr_replay.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6
+        if hasattr(L, "mml_debug_fw_replay"):
+            L.mml_debug_fw_replay.restype = C.c_int
+            L.mml_debug_fw_replay.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_longlong] + [C.c_void_p] * 3
         if hasattr(L, "mml_imu_preintegrate_batch"):
             L.mml_imu_preintegrate_batch.restype = C.c_int
             L.mml_imu_preintegrate_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
@@ -1822,6 +1825,51 @@ def tr_replay(ctx, variant, scripts):
     elif rc != MML_OK:
         raise MmlError(rc, "mml_debug_tr_replay")
     return xc, dig, digi
+
+
+FW_DIGEST_DOUBLES = 128
+
+
+def fw_replay(ctx, variant, scripts):
+    """The full-window trust-region state machine replayed on normal equations given in advance (mml_debug_fw_replay, a test hook).
+    scripts: a list of dicts with W, fixed, max_iters, x0 (15 W) and records, a list of R rounds (band (15 W, 45), g (15 W), cost);
+    variant 0 is the host's propose / decide (ctx may be None), 1 the device's fw_round.  The rounds go over packed raggedly.
+    Returns (xc (N, Rmax, 120), digest (N, Rmax, 128), digest_i (N, Rmax, 16)); the rounds of a script beyond its own R stay zero."""
+    n = len(scripts)
+    hdr = np.zeros((n, 4), np.int32)
+    x0 = np.zeros((max(n, 1), 120))
+    off = np.zeros(max(n, 1), np.int64)
+    parts, pos = [], 0
+    for k, s in enumerate(scripts):
+        W = int(s["W"])
+        m = 15 * W
+        hdr[k] = (W, int(s["fixed"]), int(s["max_iters"]), len(s["records"]))
+        x0[k, :m] = np.asarray(s["x0"], dtype=np.float64).reshape(m)
+        off[k] = pos
+        for r, (band, g, cost) in enumerate(s["records"]):
+            band, g = np.asarray(band, dtype=np.float64), np.asarray(g, dtype=np.float64)
+            if band.shape != (m, 45) or g.shape != (m,):
+                raise ValueError("script %d round %d: band must be (%d, 45) and g (%d,), not %s and %s" % (k, r, m, m, band.shape, g.shape))
+            parts += [band.reshape(-1), g, np.array([cost], dtype=np.float64)]
+            pos += 46 * m + 1
+    rounds = np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros(1)
+    rows = int(hdr[:, 3].sum())
+    xc, dig = np.zeros((max(rows, 1), 120)), np.zeros((max(rows, 1), FW_DIGEST_DOUBLES))
+    digi = np.zeros((max(rows, 1), TR_DIGEST_INTS), np.int32)
+    rc = lib().mml_debug_fw_replay(ctx._h if ctx is not None else None, C.c_int(variant), C.c_int(n), _p(hdr), _p(x0), _p(off),
+                                   _p(rounds), C.c_longlong(pos), _p(xc), _p(dig), _p(digi))
+    if ctx is not None:
+        ctx._ck(rc)
+    elif rc != MML_OK:
+        raise MmlError(rc, "mml_debug_fw_replay")
+    rmax = int(hdr[:, 3].max()) if n else 1
+    XC, DG, DI = np.zeros((n, rmax, 120)), np.zeros((n, rmax, FW_DIGEST_DOUBLES)), np.zeros((n, rmax, TR_DIGEST_INTS), np.int32)
+    row = 0
+    for k in range(n):
+        R = int(hdr[k, 3])
+        XC[k, :R], DG[k, :R], DI[k, :R] = xc[row:row + R], dig[row:row + R], digi[row:row + R]
+        row += R
+    return XC, DG, DI
 
 
 class WindowSolver:

@@ -20,8 +20,10 @@
 //               substitutions with the right-hand side in registers (one lane per row, the pivot handed over by a
 //               lane read), dogleg interpolation, the next candidate.  Element-wise work runs on all lanes; sums that
 //               Ceres takes sequentially are taken sequentially by one lane each, on different wavefronts at once.
-// Differences to the host loop are limited to libm vs device sin / cos / atan / sqrt and the summation order of the
-// back substitution.
+// The trust-region step itself -- everything after the normal equations are assembled, fw_round below -- is bit-identical to
+// the host loop's (window_imu.hip: chol_solve_rcp subtracts in the device's order): mml_debug_fw_replay runs both on the same
+// scripted equations and tests/test_gpu_fw_tr_kat.py compares every candidate and every state value for equality, over every
+// branch and over the sizes at which the band code changes behaviour (n = 15, 30, 45, 75, 120).
 // Every kernel carries a window dimension (blockIdx.y = w; parameter block, state machine and output record live in
 // arrays of n): mml_fullwindow_solve_batch advances n independent windows with the same launches, mml_fullwindow_solve
 // is its n = 1 case.  A window's workgroups touch that window's records only, so its arithmetic does not depend on
@@ -381,12 +383,12 @@ __device__ int fw_factor_solve(FwShared& sh, int n) {
 
 // One proposal (mml_fullwindow_step's propose): 1 = sh.v.xc holds a candidate, 0 = invalid step (propose again),
 // -1 = the minimiser has stopped.  The return value is the same in every thread.
-__device__ int fw_propose(const FwDevParams* P, FwShared& sh, int n) {
+__device__ int fw_propose(int max_iters, FwShared& sh, int n) {
     const int tid = threadIdx.x;
     FwScalars& S = sh.s;
     FwVectors& V = sh.v;
     __syncthreads();
-    if (S.iter >= P->max_iters || S.radius < 1e-32) return -1;
+    if (S.iter >= max_iters || S.radius < 1e-32) return -1;
     const int reuse = S.reuse;
     const double* g = V.g[S.cur];
     __syncthreads();
@@ -519,12 +521,12 @@ __device__ int fw_propose(const FwDevParams* P, FwShared& sh, int n) {
 }
 
 // accept / reject after the candidate was evaluated into slot 1 - cur; true when the minimiser stops.  On acceptance
-// sh.H (holding the candidate's band) becomes the current band; on rejection the current band is read back.
-__device__ bool fw_decide(const FwDevParams* P, const FwGlobal* G, FwShared& sh, int n) {
+// sh.H (holding the candidate's band) becomes the current band; on rejection the current band is read back from Hb (the two
+// slots of FwGlobal::Hb).
+__device__ bool fw_decide(bool fixed, const double (*Hb)[FW_N * FW_BW], FwShared& sh, int n) {
     FwScalars& S = sh.s;
     FwVectors& V = sh.v;
     const int tid = threadIdx.x;
-    const bool fixed = P->fixed != 0;
     __syncthreads();
     const double cur = S.cost[S.cur], cand = S.cost[1 - S.cur];
     if (!fixed) {
@@ -570,7 +572,7 @@ __device__ bool fw_decide(const FwDevParams* P, const FwGlobal* G, FwShared& sh,
             S.flag = stop;
         }
     } else {
-        for (int o = tid; o < n * FW_BW; o += FW_THREADS) sh.H[o] = G->Hb[cur_slot][o];
+        for (int o = tid; o < n * FW_BW; o += FW_THREADS) sh.H[o] = Hb[cur_slot][o];
         if (tid == 0) {
             S.radius *= 0.5;
             S.reuse = 1;
@@ -579,6 +581,71 @@ __device__ bool fw_decide(const FwDevParams* P, const FwGlobal* G, FwShared& sh,
     }
     __syncthreads();
     return S.flag != 0;
+}
+
+struct FwTrace {  // what a round did, for mml_debug_fw_replay (in LDS; the solve passes none)
+    int decide, nprop, codes[5], evaluate;
+};
+
+// One round of the state machine once the normal equations have been assembled into sh.H / Hb[e] / V.g[e] / S.cost[e]: round 0
+// initialises (Jacobi scaling, the gradient tolerance), a later round accepts or rejects the candidate; then proposals until a
+// candidate needs evaluating or the minimiser stops.  Returns true when it has stopped (the same value in every thread).
+// TRACE: the replay's build, which classifies every call into tr; the solve's build carries none of it.
+template <bool TRACE>
+__device__ __forceinline__ bool fw_round(bool first, int max_iters, bool fixed, const double (*Hb)[FW_N * FW_BW], FwShared& sh, int n, FwTrace* tr) {
+    FwScalars& S = sh.s;
+    FwVectors& V = sh.v;
+    const int tid = threadIdx.x;
+    bool done;
+    MmlFwSnap snap;  // (thread 0's, when there is a trace)
+    if (first) {
+        if (tid < n) V.scale[tid] = 1.0 / (1.0 + sqrt(sh.H[tid * FW_BW + (tid - band0(tid))]));  // Jacobi scaling
+        if (tid == 0) {
+            S.initial_cost = S.cost[0];
+            S.x_norm = sqrt(ordered_dot(V.x, V.x, n));
+            S.flag = 0;
+            if (!fixed) {
+                double gm = 0;
+                for (int i = 0; i < n; ++i) gm = fmax(gm, fabs(V.g[0][i]));
+                if (gm <= 1e-10) {
+                    S.termination = 1;
+                    S.flag = 1;
+                }
+            }
+        }
+        __syncthreads();
+        done = S.flag != 0;
+    } else {
+        if (TRACE && tid == 0) snap = MmlFwSnap{S.mu, S.cost[S.cur], S.iter, S.reuse, S.termination, S.successful};
+        done = fw_decide(fixed, Hb, sh, n);
+        if (TRACE) {
+            __syncthreads();
+            if (tid == 0) tr->decide = mml_fw_decide_code(snap, S.termination, S.successful, S.cost[S.cur], S.model_change);
+        }
+    }
+    FW_T(1);
+    if (!done) {
+        int p;
+        do {
+            if (TRACE) {
+                __syncthreads();
+                if (tid == 0) snap = MmlFwSnap{S.mu, S.cost[S.cur], S.iter, S.reuse, S.termination, S.successful};
+            }
+            p = fw_propose(max_iters, sh, n);
+            if (TRACE) {
+                __syncthreads();
+                if (tid == 0) {
+                    if (tr->nprop < 5)
+                        tr->codes[tr->nprop] = mml_fw_propose_code(snap, p, S.iter, S.termination, S.mu, max_iters, n, V.grad, V.gn, S.alpha, S.radius);
+                    tr->nprop++;
+                    tr->evaluate = p == 1;
+                }
+            }
+        } while (p == 0);
+        if (p < 0) done = true;
+    }
+    __syncthreads();
+    return done;
 }
 
 __global__ __launch_bounds__(FW_THREADS) void k_fw_step(FwKernelArgs A) {
@@ -654,35 +721,7 @@ __global__ __launch_bounds__(FW_THREADS) void k_fw_step(FwKernelArgs A) {
     }
     __syncthreads();
     FW_T(0);
-    bool done;
-    if (A.round == 0) {
-        if (tid < n) V.scale[tid] = 1.0 / (1.0 + sqrt(sh.H[tid * FW_BW + (tid - band0(tid))]));  // Jacobi scaling
-        if (tid == 0) {
-            S.initial_cost = S.cost[0];
-            S.x_norm = sqrt(ordered_dot(V.x, V.x, n));
-            S.flag = 0;
-            if (!P->fixed) {
-                double gm = 0;
-                for (int i = 0; i < n; ++i) gm = fmax(gm, fabs(V.g[0][i]));
-                if (gm <= 1e-10) {
-                    S.termination = 1;
-                    S.flag = 1;
-                }
-            }
-        }
-        __syncthreads();
-        done = S.flag != 0;
-    } else {
-        done = fw_decide(P, G, sh, n);
-    }
-    FW_T(1);
-    if (!done) {
-        int p;
-        do p = fw_propose(P, sh, n);
-        while (p == 0);
-        if (p < 0) done = true;
-    }
-    __syncthreads();
+    const bool done = fw_round<false>(A.round == 0, P->max_iters, P->fixed != 0, G->Hb, sh, n, nullptr);
     if (tid == 0) {
         if (done) S.go = 0;
         G->s = S;
@@ -821,6 +860,87 @@ __global__ __launch_bounds__(64) void k_marg_dense(const double* A, const double
     if (threadIdx.x < 30) s_b[threadIdx.x] = b[30 * w + threadIdx.x];
     __syncthreads();
     marg_dense(s_A, s_b, J + 225 * w, r0 + 15 * w, s_work);
+}
+
+// test hook (mml_debug_fw_replay, variant 1): workgroup s runs fw_round on the rounds of script s, the normal equations taken from
+// the script where k_fw_step assembles them.  The state stays in LDS over the rounds (k_fw_step carries it through FwGlobal, a
+// copy); Hb: the script's two band slots, 2 x FW_N x FW_BW doubles.
+__global__ __launch_bounds__(FW_THREADS) void k_fw_replay(MmlFwReplay P, double* Hb_all) {
+    __shared__ FwShared sh;
+    __shared__ FwTrace tr;
+    const int tid = threadIdx.x, sc = blockIdx.x;
+    const int W = P.hdr[4 * sc], fixed = P.hdr[4 * sc + 1], max_iters = P.hdr[4 * sc + 2], R = P.hdr[4 * sc + 3], n = 15 * W;
+    double (*Hb)[FW_N * FW_BW] = reinterpret_cast<double (*)[FW_N * FW_BW]>(Hb_all + (size_t)sc * 2 * FW_N * FW_BW);
+    FwScalars& S = sh.s;
+    FwVectors& V = sh.v;
+    {  // k_fw_init
+        double* dst = reinterpret_cast<double*>(&V);
+        for (int i = tid; i < (int)(sizeof(FwVectors) / sizeof(double)); i += FW_THREADS) dst[i] = 0.0;
+        __syncthreads();
+        if (tid < n) V.x[tid] = V.xc[tid] = V.x_init[tid] = P.x0[(size_t)sc * FW_N + tid];
+        if (tid == 0) {
+            FwScalars s;
+            memset(&s, 0, sizeof(s));
+            s.radius = 1e4;
+            s.mu = 1e-8;
+            s.go = 1;
+            S = s;
+            tr.evaluate = 0;
+        }
+    }
+    __syncthreads();
+    for (int r = 0; r < R; ++r) {
+        const double* rnd = P.rounds + P.off[sc] + (size_t)r * (46 * (size_t)n + 1);
+        if (tid == 0) {
+            tr.decide = tr.nprop = 0;
+            for (int i = 0; i < 5; ++i) tr.codes[i] = 0;
+        }
+        __syncthreads();
+        if (S.go) {  // (uniform: nobody writes the state between the barriers around this read)
+            const int e = r == 0 ? 0 : 1 - S.cur;
+            for (int o = tid; o < n * FW_BW; o += FW_THREADS) {
+                const int a = o / FW_BW, b = band0(a) + (o - FW_BW * a);
+                const double h = (b >= 0 && b < n) ? rnd[o] : 0.0;
+                sh.H[o] = h;
+                Hb[e][o] = h;
+            }
+            if (tid < n) V.g[e][tid] = rnd[(size_t)FW_BW * n + tid];
+            if (tid == FW_THREADS - 1) S.cost[e] = rnd[(size_t)(FW_BW + 1) * n];
+            __syncthreads();
+            const bool done = fw_round<true>(r == 0, max_iters, fixed != 0, Hb, sh, n, &tr);
+            if (done && tid == 0) S.go = 0;
+            __syncthreads();
+        }
+        const size_t o = (size_t)P.row[sc] + r;
+        const bool cand = S.go && tr.evaluate;
+        if (tid < n) {
+            P.xc[o * FW_N + tid] = cand ? V.xc[tid] : V.x[tid];
+            P.dig[o * MML_FW_DIGEST_DOUBLES + 8 + tid] = V.x[tid];
+        }
+        if (tid == 0) {
+            double* dig = P.dig + o * MML_FW_DIGEST_DOUBLES;
+            int* digi = P.digi + o * MML_TR_DIGEST_INTS;
+            dig[0] = S.cost[S.cur];
+            dig[1] = S.radius;
+            dig[2] = S.mu;
+            dig[3] = S.alpha;
+            dig[4] = S.dogleg_norm;
+            dig[5] = S.model_change;
+            dig[6] = S.step_norm;
+            dig[7] = S.x_norm;
+            digi[0] = S.iter;
+            digi[1] = S.successful;
+            digi[2] = S.num_invalid;
+            digi[3] = S.reuse;
+            digi[4] = S.termination;
+            digi[5] = S.go;
+            digi[6] = tr.evaluate;
+            digi[7] = tr.decide;
+            digi[8] = tr.nprop;
+            for (int i = 0; i < 5; ++i) digi[9 + i] = i < tr.nprop ? tr.codes[i] : 0;
+        }
+        __syncthreads();
+    }
 }
 
 constexpr int FW_MAX_ROUNDS = 1001;  // max_num_iterations <= 1000
@@ -1072,5 +1192,73 @@ extern "C" int mml_marginalize_dense(mml_ctx* ctx, long n, const double* A, cons
     }
     ok = ok && hipMemcpy(J, d_buf + nA + nb, sizeof(double) * nJ, hipMemcpyDeviceToHost) == hipSuccess;
     ok = ok && hipMemcpy(r0, d_buf + nA + nb + nJ, sizeof(double) * nr, hipMemcpyDeviceToHost) == hipSuccess;
+    return ok ? MML_OK : MML_ERR_HIP;
+}
+
+extern "C" int mml_debug_fw_replay(mml_ctx* ctx, int variant, int n, const int* hdr, const double* x0, const long long* offsets,
+                                   const double* rounds, long long rounds_len, double* xc, double* digest, int* digest_i) {
+    if (variant < 0 || variant > 1 || n < 0 || n > MML_FW_REPLAY_SCRIPTS_MAX || !hdr || !x0 || !offsets || !rounds || !xc || !digest ||
+        !digest_i || rounds_len < 0 || rounds_len > (64ll << 20) / (long long)sizeof(double) || (variant != 0 && !ctx))
+        return MML_ERR_INVALID;
+    std::vector<long long> row((size_t)n + 1, 0);
+    for (int s = 0; s < n; ++s) {
+        const int W = hdr[4 * s], fixed = hdr[4 * s + 1], max_iters = hdr[4 * s + 2], R = hdr[4 * s + 3];
+        if (W < 1 || W > MAXW || (fixed != 0 && fixed != 1) || max_iters < 0 || max_iters > FW_MAX_ROUNDS - 1 || R < 1 ||
+            R > MML_FW_REPLAY_ROUNDS_MAX)
+            return MML_ERR_INVALID;
+        const long long len = (long long)R * (46ll * 15 * W + 1);
+        if (offsets[s] < 0 || offsets[s] > rounds_len - len) return MML_ERR_INVALID;
+        row[s + 1] = row[s] + R;
+    }
+    if (n == 0) return MML_OK;
+    const size_t no = (size_t)row[n], nxc = no * FW_N, nd = no * MML_FW_DIGEST_DOUBLES, ni = no * MML_TR_DIGEST_INTS;
+    for (size_t i = 0; i < nxc; ++i) xc[i] = 0.0;
+    for (size_t i = 0; i < nd; ++i) digest[i] = 0.0;
+    for (size_t i = 0; i < ni; ++i) digest_i[i] = 0;
+    MmlFwReplay P;
+    P.n = n;
+    if (variant == 0) {
+        P.hdr = hdr;
+        P.x0 = x0;
+        P.off = offsets;
+        P.row = row.data();
+        P.rounds = rounds;
+        P.xc = xc;
+        P.dig = digest;
+        P.digi = digest_i;
+        for (int s = 0; s < n; ++s) mml_fw_replay_host(P, s);
+        return MML_OK;
+    }
+    int rc = mml_sync_all(ctx);
+    if (rc != MML_OK) return rc;
+    MmlTemp<double> dbuf;     // x0 | rounds | xc | digest | the band slots
+    MmlTemp<int> ibuf;        // hdr | digest_i
+    MmlTemp<long long> lbuf;  // offsets | rows
+    const size_t nx = (size_t)n * FW_N, nr = (size_t)rounds_len, nh = (size_t)n * 2 * FW_N * FW_BW;
+    bool ok = dbuf.alloc(nx + nr + nxc + nd + nh) == hipSuccess && ibuf.alloc(4 * (size_t)n + ni) == hipSuccess &&
+              lbuf.alloc(2 * (size_t)n) == hipSuccess;
+    ok = ok && hipMemcpy(dbuf.d, x0, sizeof(double) * nx, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && (nr == 0 || hipMemcpy(dbuf.d + nx, rounds, sizeof(double) * nr, hipMemcpyHostToDevice) == hipSuccess);
+    ok = ok && hipMemset(dbuf.d + nx + nr, 0, sizeof(double) * (nxc + nd + nh)) == hipSuccess;
+    ok = ok && hipMemcpy(ibuf.d, hdr, sizeof(int) * 4 * (size_t)n, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMemset(ibuf.d + 4 * (size_t)n, 0, sizeof(int) * ni) == hipSuccess;
+    ok = ok && hipMemcpy(lbuf.d, offsets, sizeof(long long) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess;
+    ok = ok && hipMemcpy(lbuf.d + n, row.data(), sizeof(long long) * (size_t)n, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        P.hdr = ibuf.d;
+        P.x0 = dbuf.d;
+        P.off = lbuf.d;
+        P.row = lbuf.d + n;
+        P.rounds = dbuf.d + nx;
+        P.xc = dbuf.d + nx + nr;
+        P.dig = dbuf.d + nx + nr + nxc;
+        P.digi = ibuf.d + 4 * (size_t)n;
+        hipStream_t st = MML_STREAM(ctx);
+        hipLaunchKernelGGL(k_fw_replay, dim3((unsigned)n), dim3(FW_THREADS), 0, st, P, dbuf.d + nx + nr + nxc + nd);
+        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+    }
+    ok = ok && hipMemcpy(xc, P.xc, sizeof(double) * nxc, hipMemcpyDeviceToHost) == hipSuccess;
+    ok = ok && hipMemcpy(digest, P.dig, sizeof(double) * nd, hipMemcpyDeviceToHost) == hipSuccess;
+    ok = ok && hipMemcpy(digest_i, P.digi, sizeof(int) * ni, hipMemcpyDeviceToHost) == hipSuccess;
     return ok ? MML_OK : MML_ERR_HIP;
 }

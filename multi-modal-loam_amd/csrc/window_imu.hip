@@ -307,7 +307,105 @@ bool decide(mml_fullwindow* s) {
     return false;
 }
 
+// after the normal equations at x0 have arrived in s->cur: the scaling and the first test; returns true when the minimiser stops
+bool begin(mml_fullwindow* s) {
+    const int n = s->n;
+    s->initial_cost = s->cur.cost;
+    double xn = 0;
+    for (int i = 0; i < n; ++i) xn += s->x[i] * s->x[i];
+    s->x_norm = sqrt(xn);
+    for (int i = 0; i < n; ++i) s->scale[i] = 1.0 / (1.0 + sqrt(s->cur.H[(size_t)i * n + i]));  // Jacobi scaling
+    if (!s->opts.fixed_iterations) {
+        double gm = 0;
+        for (int i = 0; i < n; ++i) gm = fmax(gm, fabs(s->cur.g[i]));
+        if (gm <= 1e-10) {
+            s->termination = 1;
+            return true;
+        }
+    }
+    return false;
+}
+
+// a round of a replay script (m x 45 band, g, cost) as the dense equations assemble would have left: exact zeros outside the band
+void expand_round(const double* rnd, int n, MmlFwEval& e) {
+    e.H.assign((size_t)n * n, 0.0);
+    for (int a = 0; a < n; ++a)
+        for (int c = 0; c < 45; ++c) {
+            const int b = 15 * (a / 15 - 1) + c;
+            if (b >= 0 && b < n) e.H[(size_t)a * n + b] = rnd[(size_t)a * 45 + c];
+        }
+    e.g.assign(rnd + (size_t)45 * n, rnd + (size_t)46 * n);
+    e.cost = rnd[(size_t)46 * n];
+}
+
 }  // namespace
+
+// mml_debug_fw_replay, variant 0: begin / decide / propose in the order mml_fullwindow_step calls them, s->cur / s->cand from the
+// script instead of from assemble
+void mml_fw_replay_host(const MmlFwReplay& P, int sc) {
+    const int W = P.hdr[4 * sc], R = P.hdr[4 * sc + 3], n = 15 * W;
+    mml_solve_opts opts;
+    memset(&opts, 0, sizeof(opts));
+    opts.fixed_iterations = P.hdr[4 * sc + 1];
+    opts.max_num_iterations = P.hdr[4 * sc + 2];
+    mml_fullwindow* s = mml_fullwindow_create(W, &opts);
+    if (!s) return;
+    int evaluate = 0;
+    for (int r = 0; r < R; ++r) {
+        const double* rnd = P.rounds + P.off[sc] + (size_t)r * (46 * (size_t)n + 1);
+        int codes[5] = {0, 0, 0, 0, 0}, nprop = 0, decision = 0;
+        const bool was_going = !s->done;
+        if (r == 0) {
+            s->started = 1;
+            s->x.assign(P.x0 + 120 * (size_t)sc, P.x0 + 120 * (size_t)sc + n);
+            s->x_init = s->x;
+            expand_round(rnd, n, s->cur);
+            if (begin(s)) s->done = 1;
+        } else if (was_going) {
+            expand_round(rnd, n, s->cand);
+            const MmlFwSnap b{s->mu, s->cur.cost, s->iter, s->reuse, s->termination, s->successful};
+            if (decide(s)) s->done = 1;
+            decision = mml_fw_decide_code(b, s->termination, s->successful, s->cur.cost, s->model_change);
+        }
+        while (!s->done) {
+            const MmlFwSnap b{s->mu, s->cur.cost, s->iter, s->reuse, s->termination, s->successful};
+            const int p = propose(s);
+            if (nprop < 5)
+                codes[nprop] = mml_fw_propose_code(b, p, s->iter, s->termination, s->mu, opts.max_num_iterations, n, s->grad.data(),
+                                                   s->gn.data(), s->alpha, s->radius);
+            ++nprop;
+            evaluate = p == 1;
+            if (p < 0) s->done = 1;
+            if (p != 0) break;
+        }
+        const size_t o = (size_t)P.row[sc] + r;
+        double* xc = P.xc + o * 120;
+        double* dig = P.dig + o * MML_FW_DIGEST_DOUBLES;
+        int* digi = P.digi + o * MML_TR_DIGEST_INTS;
+        const int go = s->done ? 0 : 1;
+        for (int i = 0; i < n; ++i) xc[i] = (go && evaluate) ? s->xc[i] : s->x[i];  // (what mml_fullwindow_step hands back)
+        dig[0] = s->cur.cost;
+        dig[1] = s->radius;
+        dig[2] = s->mu;
+        dig[3] = s->alpha;
+        dig[4] = s->dogleg_norm;
+        dig[5] = s->model_change;
+        dig[6] = s->step_norm;
+        dig[7] = s->x_norm;
+        for (int i = 0; i < n; ++i) dig[8 + i] = s->x[i];
+        digi[0] = s->iter;
+        digi[1] = s->successful;
+        digi[2] = s->num_invalid;
+        digi[3] = s->reuse;
+        digi[4] = s->termination;
+        digi[5] = go;
+        digi[6] = evaluate;
+        digi[7] = decision;
+        digi[8] = nprop;
+        for (int i = 0; i < 5; ++i) digi[9 + i] = i < nprop ? codes[i] : 0;
+    }
+    mml_fullwindow_destroy(s);
+}
 
 extern "C" {
 
@@ -370,19 +468,9 @@ int mml_fullwindow_step(mml_fullwindow* s, const double* records, double* x_eval
         s->x_init = s->x;
         int rc = assemble(s, records, s->x.data(), s->cur);
         if (rc != MML_OK) return rc;
-        s->initial_cost = s->cur.cost;
-        double xn = 0;
-        for (int i = 0; i < n; ++i) xn += s->x[i] * s->x[i];
-        s->x_norm = sqrt(xn);
-        for (int i = 0; i < n; ++i) s->scale[i] = 1.0 / (1.0 + sqrt(s->cur.H[(size_t)i * n + i]));  // Jacobi scaling
-        if (!s->opts.fixed_iterations) {
-            double gm = 0;
-            for (int i = 0; i < n; ++i) gm = fmax(gm, fabs(s->cur.g[i]));
-            if (gm <= 1e-10) {
-                s->termination = 1;
-                s->done = 1;
-                return 1;
-            }
+        if (begin(s)) {
+            s->done = 1;
+            return 1;
         }
     } else {
         int rc = assemble(s, records, s->xc.data(), s->cand);

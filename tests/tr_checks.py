@@ -129,8 +129,12 @@ class Machine:
     """Ceres' trust-region loop around a proposal function, round by round as the replay hook runs it.  Values are whatever the
     proposal returns (floats, or mpmath numbers in make_tr_kat.py); feed() returns the round's log."""
 
-    def __init__(self, W, fixed, max_iters, x0, propose, scale_of, sqrt=np.sqrt, num=float):
+    def __init__(self, W, fixed, max_iters, x0, propose, scale_of, sqrt=np.sqrt, num=float, cost_terms=None, gradient_max=None):
         self.W, self.fixed, self.max_iters, self.propose, self.scale_of, self.sqrt, self.num = W, fixed, max_iters, propose, scale_of, sqrt, num
+        # how the cost's terms and the largest gradient entry are read out of a round's record (the default: W 28-double records;
+        # fw_tr_checks.py passes its own for the full-window rounds)
+        self.cost_terms = cost_terms if cost_terms is not None else (lambda rec: np.asarray(rec, float)[:, 27])
+        self.gradient_max = gradient_max if gradient_max is not None else (lambda rec: np.max(np.abs(np.asarray(rec, float)[:, 21:27])))
         self.x = [num(v) for v in np.asarray(x0, float).reshape(-1)]
         self.x_init = list(self.x)
         self.round = -1
@@ -139,12 +143,11 @@ class Machine:
         return self.sqrt(sum((t * t for t in v), self.num(0)))
 
     def feed(self, rec):
-        rec = np.asarray(rec, float)
         self.round += 1
         log = dict(decide=0, codes=[], rel=None, margins=[])
         if self.round == 0:
             self.rec, self.scale = rec, self.scale_of(rec)
-            self.cost = sum((self.num(c) for c in rec[:, 27]), self.num(0))
+            self.cost = sum((self.num(c) for c in self.cost_terms(rec)), self.num(0))
             self.x_norm = self._norm(self.x)
             self.radius, self.mu = 1e4, 1e-8
             self.num_invalid = self.iter = self.successful = self.termination = 0
@@ -152,7 +155,7 @@ class Machine:
             self.dogleg_norm = self.model_change = self.step_norm = self.num(0)
             self.xc = list(self.x)
             if not self.fixed:
-                gm = np.max(np.abs(rec[:, 21:27]))
+                gm = self.gradient_max(rec)
                 log["margins"].append(("gradient_tol", gm, 1e-10, 1.0))
                 if gm <= 1e-10:
                     self.termination, self.go = 1, 0
@@ -170,7 +173,7 @@ class Machine:
         return log
 
     def _decide(self, rec, log):
-        cand = sum((self.num(c) for c in rec[:, 27]), self.num(0))
+        cand = sum((self.num(c) for c in self.cost_terms(rec)), self.num(0))
         cond = self.cond
         if not self.fixed:
             thr = 1e-8 * (self.x_norm + 1e-8)
@@ -196,7 +199,7 @@ class Machine:
             self.rec, self.cost = rec, cand
             self.successful += 1
             if not self.fixed:
-                gm = np.max(np.abs(rec[:, 21:27]))
+                gm = self.gradient_max(rec)
                 log["margins"].append(("gradient_tol", gm, 1e-10, 1.0))
                 if gm <= 1e-10:
                     self.termination, self.go, log["decide"] = 1, 0, D_GRAD
