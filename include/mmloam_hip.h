@@ -377,6 +377,78 @@ int mml_union_assemble_offset(mml_ctx* ctx, mml_livox_stream* s, int first_slot,
 int mml_union_plan_offset(const uint64_t* S, long front, long tail, uint64_t hs, int count, const uint64_t* starts,
                           int sliced_points, mml_union_frame* out);
 
+/* ---- the aligner's time-offset estimation on the resident stream -------------------------------------------------------
+ * LidarsParamEstimator::estimate_timeoffset (unionLidarsAligner.cpp:1021-1166) for n queued Velodyne frames against one range of
+ * a mml_livox_stream, in one call and without a hand-over through host memory: frame i (a PointCloud2-style payload, the
+ * arguments of mml_velo_fov_select_batch) goes through the FOV selection of :437-490; its kept points, transformed by tf (ONE
+ * row-major 4 x 4 matrix for all frames, _velo_hori_tf_matrix; NULL: not transformed), are searched from the stream's points
+ * [livox_begin, livox_end) -- absolute point indices with front <= livox_begin <= livox_end <= tail, the merged last eight
+ * messages of :1049-1074, whose boundaries the caller knows from its pushes.  All frames share that one Livox block.
+ * Every numeric output of row i -- n_kept, n_windows, best_window, lowest_error, row i of nn_d2 (livox_end - livox_begin floats
+ * per frame; optional) and the window errors at window_error + window_offsets[i], at most window_offsets[i+1] -
+ * window_offsets[i] of them (optional; the batch call's capacity rule) -- equals, to the byte, mml_velo_fov_select_batch of the
+ * frame followed by mml_time_offset_search of its xyz rows against the x, y, z of the same records.
+ * optim_start = hs + S[livox_begin + best_window * search_resolution], the stream's own stamp of the best window's first point,
+ * which is livox_msg.timebase + livox_msg_offset_vec[cnt * search_res] of :1146 (hs + S[k] = the time base of k's message + its
+ * offset_time).  time_offset = velo_stamps[i] - optim_start in uint64 (:1161; it wraps when the Livox clock is ahead).  accepted =
+ * best_window >= 0 && lowest_error < error_th (:1159).  Without a best window the three are 0.
+ * The stream is only read: front, tail, disorder and every record stay, so mml_union_assemble_offset can follow on it.  A stream
+ * with time-order violations is not refused: the search does not depend on the order.
+ * Checks, all before anything is enqueued, and a refusal writes nothing: MML_ERR_INVALID for the argument rules of
+ * mml_velo_fov_select_batch, n outside 1 .. min(MML_FOV_BATCH_MAX, MML_TOFS_BATCH_MAX), a range outside [front, tail] or
+ * reversed, a stream of another context, search_resolution or sliced_points below 1, a NULL stream / velo_stamps / out (or
+ * window_offsets with window_error), negative or decreasing window_offsets; MML_ERR_CAPACITY for a frame above max_velo_points,
+ * for a frame above max_map_points -- deliberately conservative: the frame's POINTS are counted, not the ones it will keep, which
+ * only the device knows -- and for n x (livox_end - livox_begin) or the frames' points together above INT_MAX.  mml_last_error
+ * names the entry point and, where there is one, the frame.
+ * The one condition known only on the device: a frame that keeps nothing while the range holds points.  The hand-composed path
+ * refuses such a problem up front (mml_time_offset_search: "nearest-neighbour search in an empty cloud"); here it is that row's
+ * status NO_VELO_IN_FOV with 0 windows, -1 and 1e6, its nn_d2 row and window errors are left unwritten, and the other frames
+ * are unaffected.
+ * On the device: one upload of the payload; the FOV kernel's rows are packed straight into the search's Velodyne input (no row
+ * crosses the bus, the counts do); k_tofs_livox_xyz forms the packed x, y, z of the range from the stream's records; the
+ * kernels of mml_time_offset_search_batch do the rest, and k_tofs_rows reads S for the best windows and writes the rows.
+ * Host synchronisations: the call first waits for everything the context has in flight, then synchronises exactly THREE times
+ * whatever n is -- the FOV counts, the bounding boxes, the results -- (ONE, the counts, for an empty range or when no frame keeps a
+ * point).  With profiling on they show as one launch each of the stages "velo_fov", "tofs_box" and "tofs_search" per call.
+ * Scratch: the grow-only blocks of mml_velo_fov_select_batch and mml_time_offset_search_batch (4 n (livox_end - livox_begin)
+ * bytes of distances among them). */
+typedef struct {
+    int status;            /* 0 OK, 1 NO_VELO_IN_FOV (the frame kept nothing while the range holds points) */
+    int n_kept;            /* velo_fovs_cloud size of the frame */
+    int n_windows, best_window;      /* as mml_time_offset_search */
+    double lowest_error;
+    uint64_t optim_start;  /* hs + S[livox_begin + best_window * search_resolution]; 0 when best_window < 0 */
+    uint64_t time_offset;  /* velo_stamps[i] - optim_start in uint64 (:1161); 0 when best_window < 0 */
+    int accepted;          /* best_window >= 0 && lowest_error < error_th (:1159) */
+    int _pad;
+} mml_time_offset_estimate_row;
+#define MML_TOFS_ROW_OK 0
+#define MML_TOFS_ROW_NO_VELO_IN_FOV 1
+int mml_time_offset_estimate_stream(mml_ctx* ctx, mml_livox_stream* s, long livox_begin, long livox_end,
+        int n, const uint8_t* data, const long* byte_offsets /* n */, const int* n_points /* n */,
+        int point_step, int off_x, int off_y, int off_z,
+        const uint64_t* velo_stamps /* n, header stamps in ns */, const float* tf /* 16 or NULL */,
+        int search_resolution, int sliced_points, double error_th,
+        float* nn_d2 /* n x (livox_end - livox_begin), may be NULL */,
+        double* window_error /* may be NULL */, const long* window_offsets /* n + 1, required iff window_error */,
+        mml_time_offset_estimate_row* out /* n */);
+/* Host only, no context: which queued Velodyne frame estimate_timeoffset runs on -- the loop of :1026-1043.  velo_stamps: the
+ * header stamps (ns) of the n_velo queued frames, oldest first (velo_vec); hori_stamp: the header stamp of the newest Livox
+ * message (hori_vec.back(), :1027); n_hori_msgs: hori_vec.size().  From the newest frame backwards a frame is popped while it
+ * is newer than hori_stamp or within 0.2 s of it, stamps compared as ros::Time::toSec() forms them ((double)sec + 1e-9 *
+ * (double)nsec from ns / 1000000000 and ns % 1000000000) and `abs` being std::abs(double) (convention 15).
+ * *selected = the index of the frame :1044 ends on, *status = MML_TOFS_GATE_OK.  Where the reference is undefined this library
+ * refuses and selects nothing (*selected = -1): MML_TOFS_GATE_EMPTY when every frame is popped (the reference pops its last
+ * frame and reads back() of an empty vector, :1037-1039; n_velo == 0 likewise), MML_TOFS_GATE_TOO_FEW_MESSAGES when a frame is
+ * left but n_hori_msgs < 8 (:1051 indexes before the vector's start).  Returns MML_OK, or MML_ERR_INVALID for a negative count
+ * or a NULL pointer. */
+#define MML_TOFS_GATE_OK 0
+#define MML_TOFS_GATE_EMPTY 1
+#define MML_TOFS_GATE_TOO_FEW_MESSAGES 2
+int mml_time_offset_gate(int n_velo, const uint64_t* velo_stamps, uint64_t hori_stamp, int n_hori_msgs,
+                         int* selected /* index of the frame :1044 ends on, or -1 */, int* status);
+
 /* Test hook like mml_libm_f32: a slot's raw input as it stands -- what the upload entry points or mml_union_assemble put
  * there: n_velo rows of x, y, z, intensity and n_livox records.  Either buffer may be NULL with capacity 0 to query the
  * counts; MML_ERR_CAPACITY when a capacity is below its count.  Synchronises. */

@@ -65,6 +65,11 @@ INGEST_VELO_ONLY, INGEST_MERGED, INGEST_DROPPED = 0, 1, 2
 (INGEST_WHY_MERGED, INGEST_WHY_NO_IMU, INGEST_WHY_FIRST_FRAME, INGEST_WHY_VELO_ONLY_MODE, INGEST_WHY_FAST_ROTATION,
  INGEST_WHY_FEW_CORNERS) = range(6)
 INGEST_WHY_FETCH = 16   # DROPPED: + the row's fetch status
+# mml_time_offset_estimate_row, its status values, and the statuses of mml_time_offset_gate
+TOFS_ROW_DTYPE = np.dtype([("status", "<i4"), ("n_kept", "<i4"), ("n_windows", "<i4"), ("best_window", "<i4"), ("lowest_error", "<f8"),
+                           ("optim_start", "<u8"), ("time_offset", "<u8"), ("accepted", "<i4"), ("_pad", "<i4")])
+TOFS_ROW_OK, TOFS_ROW_NO_VELO_IN_FOV = 0, 1
+TOFS_GATE_OK, TOFS_GATE_EMPTY, TOFS_GATE_TOO_FEW_MESSAGES = 0, 1, 2
 # mml_velo_fov_info
 VELO_FOV_INFO_DTYPE = np.dtype([("start_ori", "<f4"), ("end_ori", "<f4"), ("half_index", "<i4"), ("n_kept", "<i4")])
 
@@ -343,6 +348,12 @@ def lib():
                                                     + [C.c_void_p] * 2)
             L.mml_velo_fov_select.restype = C.c_int
             L.mml_velo_fov_select.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 2
+        if hasattr(L, "mml_time_offset_estimate_stream"):
+            L.mml_time_offset_estimate_stream.restype = C.c_int
+            L.mml_time_offset_estimate_stream.argtypes = ([C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 4
+                                                          + [C.c_void_p] * 2 + [C.c_int, C.c_int, C.c_double] + [C.c_void_p] * 4)
+            L.mml_time_offset_gate.restype = C.c_int
+            L.mml_time_offset_gate.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
         if hasattr(L, "mml_imu_fetch_batch"):
             L.mml_imu_stream_create.restype = C.c_int
             L.mml_imu_stream_create.argtypes = [C.c_void_p, C.c_long, C.c_void_p]
@@ -477,6 +488,20 @@ def time_offset_plan(velo_offsets, livox_offsets, search_resolution=30, sliced_p
     rc = lib().mml_time_offset_plan(C.c_int(n), _p(vo), _p(lo), C.c_int(search_resolution), C.c_int(sliced_points),
                                     C.c_int(max_map_points), _p(nwin), C.byref(bad))
     return rc, bad.value, nwin[:max(n, 0)]
+
+
+def time_offset_gate(velo_stamps, hori_stamp, n_hori_msgs):
+    """mml_time_offset_gate (host only): which queued Velodyne frame estimate_timeoffset runs on, the loop of
+    unionLidarsAligner.cpp:1026-1043.  velo_stamps: the queued frames' header stamps in ns, oldest first; hori_stamp: the newest
+    Livox message's header stamp; n_hori_msgs: queued Livox messages.  Returns (selected, status): the frame's index and
+    TOFS_GATE_OK, or -1 and TOFS_GATE_EMPTY (every frame popped) / TOFS_GATE_TOO_FEW_MESSAGES (fewer than 8 messages)."""
+    vs = np.ascontiguousarray(velo_stamps, dtype=np.uint64)
+    sel, st = C.c_int(-7), C.c_int(-7)
+    rc = lib().mml_time_offset_gate(C.c_int(len(vs)), _p(vs) if len(vs) else None, C.c_uint64(int(hori_stamp)), C.c_int(n_hori_msgs),
+                                    C.byref(sel), C.byref(st))
+    if rc != MML_OK:
+        raise MmlError(rc, "mml_time_offset_gate")
+    return sel.value, st.value
 
 
 def velo_fov_pack(frames):
@@ -793,6 +818,38 @@ class Context:
                                                     C.c_int(sliced_points), _p(nn), _p(err), _p(wo), _p(nw), _p(best), _p(lowest)))
         return [{"nn_d2": nn[lo[i]:lo[i + 1]], "window_error": err[wo[i]:wo[i] + nw[i]], "best_window": int(best[i]),
                  "lowest_error": float(lowest[i])} for i in range(n)]
+
+    def time_offset_estimate_stream(self, stream, livox_begin, livox_end, frames, velo_stamps, tf=None, search_resolution=30,
+                                    sliced_points=12000, error_th=1e6):
+        """mml_time_offset_estimate_stream: estimate_timeoffset (unionLidarsAligner.cpp:1021-1166) for the Velodyne frames
+        `frames` ((n_i, k >= 3) float32 rows x, y, z, ...) against the points [livox_begin, livox_end) of `stream`, FOV selection,
+        search and stamps in one call on the resident stream.  velo_stamps: the frames' header stamps (ns); tf: one 4 x 4 matrix or
+        None.  Returns a list of dicts: the fields of the frame's TOFS_ROW_DTYPE row (status, n_kept, n_windows, best_window,
+        lowest_error, optim_start, time_offset, accepted) plus nn_d2 and window_error (empty for a NO_VELO_IN_FOV row)."""
+        data, bo, npts, step = velo_fov_pack(frames)
+        n = len(npts)
+        vs = np.ascontiguousarray(velo_stamps, dtype=np.uint64)
+        if len(vs) != n:
+            raise ValueError("%d stamps for %d frames" % (len(vs), n))
+        t = np.ascontiguousarray(np.asarray(tf, np.float32).reshape(16)) if tf is not None else None
+        L = max(int(livox_end) - int(livox_begin), 0)
+        each = (L - sliced_points - 1) // search_resolution + 1 if search_resolution >= 1 and sliced_points >= 1 and L > sliced_points else 0
+        wo = (np.arange(n + 1, dtype=np.int64) * each)
+        nn = np.zeros(max(n * L, 1), np.float32)
+        err = np.zeros(max(int(wo[-1]), 1), np.float64)
+        rows = np.zeros(max(n, 1), TOFS_ROW_DTYPE)
+        self._ck(lib().mml_time_offset_estimate_stream(self._h, stream._h, C.c_long(int(livox_begin)), C.c_long(int(livox_end)), C.c_int(n),
+                                                       _p(data) if len(data) else None, _p(bo), _p(npts), C.c_int(step), C.c_int(0), C.c_int(4),
+                                                       C.c_int(8), _p(vs), _p(t), C.c_int(search_resolution), C.c_int(sliced_points),
+                                                       C.c_double(error_th), _p(nn), _p(err), _p(wo), _p(rows)))
+        out = []
+        for i in range(n):
+            r = {k: rows[k][i].item() for k in TOFS_ROW_DTYPE.names if k != "_pad"}
+            ok = r["status"] == TOFS_ROW_OK
+            r["nn_d2"] = nn[i * L:(i + 1) * L] if ok else nn[:0]
+            r["window_error"] = err[wo[i]:wo[i] + r["n_windows"]]
+            out.append(r)
+        return out
 
     def velo_fov_select(self, frames):
         """velo_fov_select(frames, ctx=self): the aligner's FOV selection on the device."""

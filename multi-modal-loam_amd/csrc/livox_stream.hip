@@ -387,6 +387,10 @@ int union_run(mml_ctx* ctx, const UnionMode& m, mml_livox_stream* s, int first_s
 
 }  // namespace
 
+MmlLivoxView mml_livox_stream_view(const mml_livox_stream* s) {
+    return MmlLivoxView{s->ctx, s->rec[s->cur], s->stamp[s->cur], s->base, s->front, s->tail, s->hs};
+}
+
 // mml_union_assemble: the checks that need no device (capi.hip calls them before it touches the slots) ...
 int mml_union_check(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int count, const uint64_t* stamps, const float* velo_xyzi,
                     const int* vo, mml_union_frame* out) {

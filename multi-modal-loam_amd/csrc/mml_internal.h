@@ -414,6 +414,25 @@ int mml_union_offset_check(mml_ctx* ctx, mml_livox_stream* s, int first_slot, in
                            const float* velo_xyzi, const int* velo_offsets, mml_union_frame* out);
 int mml_union_offset_run(mml_ctx* ctx, mml_livox_stream* s, int first_slot, int count, const uint64_t* starts, int sliced_points,
                          const float* velo_xyzi, const int* velo_offsets, const float* tf, mml_union_frame* out);
+// What mml_time_offset_estimate_stream (time_offset.hip) reads of a stream: the live part's arrays (point i sits at element
+// i - base of rec, 5 dwords each, and of stamp) and the host's counters.  livox_stream.hip; nothing is enqueued or changed.
+struct MmlLivoxView {
+    mml_ctx* ctx;
+    const uint32_t* rec;
+    const uint64_t* stamp;
+    long base, front, tail;
+    uint64_t hs;
+};
+MmlLivoxView mml_livox_stream_view(const mml_livox_stream* s);
+// velo_fov.hip, for the same caller, which keeps the selection on the device: the argument rules of the FOV calls (n_max: the
+// caller's bound on n); the selection itself -- records down, k_vfov_select, counts and info back in ONE host synchronisation, *info
+// being n rows of pinned memory that stay valid until the context's next selection --; and the packing pass of that selection,
+// enqueued on the current stream: frame i's kept rows as packed x, y, z from row dst[i] of the device array d_xyz.
+int mml_vfov_check(mml_ctx* ctx, const char* who, int n, int n_max, const uint8_t* data, const long* byte_offsets, const int* n_points, int step,
+                   int ox, int oy, int oz);
+int mml_vfov_select_device(mml_ctx* ctx, const char* who, int n, const uint8_t* data, const long* byte_offsets, const int* n_points, int step,
+                           int ox, int oy, int oz, const mml_velo_fov_info** info);
+int mml_vfov_pack_device(mml_ctx* ctx, int n, const long long* dst, int max_kept, float* d_xyz);
 // imu_preint.hip: k_imu_preintegrate on device arrays (bias: n x (bg | ba)), asynchronous on the current stream
 int mml_launch_imu_preintegrate(mml_ctx* ctx, int n, const double* d_samples, const int* d_offsets, const double* d_bias, mml_imu_preint* d_out);
 int mml_launch_detect_line(mml_ctx* ctx, int n, uint16_t* d_final);

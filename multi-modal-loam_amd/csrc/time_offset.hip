@@ -9,11 +9,16 @@
 // table (TofsProb) with the problem index in blockIdx.y, and the single call is the n = 1 case.  A problem's arithmetic does
 // not depend on the problems next to it: its distances come from an EXACT search (knn5_dev.h), which returns the same float
 // whatever grid it walks, and its window sums are formed by one lane each in index order.
+// mml_time_offset_estimate_stream is the whole of estimate_timeoffset (:1021-1166) on a resident mml_livox_stream: the FOV
+// selection's stage (velo_fov.hip) feeds the same kernels on the device, k_tofs_livox_xyz forms the Livox side from the stream's
+// records (one block shared by all frames: TofsProb::q_base) and k_tofs_rows turns the best windows into stamps (:1146, :1159-1161).
+// The gate of :1026-1043 is host code: time_offset_gate.h.
 // Compiled with -ffp-contract=off.
 #include <math.h>
 #include <string.h>
 
 #include "mml_internal.h"
+#include "time_offset_gate.h"
 #include "voxel_sort_dev.h"
 
 namespace {
@@ -25,9 +30,10 @@ namespace {
 struct TofsProb {
     MmlGrid g;
     int v_base, n_velo;
-    int l_base, n_livox;
-    long long e_base;  // first window of the problem in the error array
-    int n_win, _pad;
+    int l_base, n_livox;  // its rows of the distance array
+    long long e_base;     // first window of the problem in the error array
+    int n_win;
+    int q_base;  // its first Livox point in the query array: l_base, or 0 where all problems share one Livox block (the stream call)
 };
 struct TofsBest {
     double lowest;
@@ -137,7 +143,7 @@ __global__ __launch_bounds__(256) void k_tofs_nn1(const TofsProb* __restrict__ t
     g.dim[1] = P.g.dim[1];
     g.dim[2] = P.g.dim[2];
     g.ncell = P.g.ncell;
-    const float* q = q_all + 3 * (size_t)P.l_base;
+    const float* q = q_all + 3 * (size_t)P.q_base;
     const int i = blockIdx.x * 256 + threadIdx.x;
     const bool valid = i < nq;
     Knn5 k;
@@ -162,7 +168,7 @@ __global__ __launch_bounds__(64) void k_tofs_window_err(const TofsProb* __restri
     }
     const TofsProb& P = tab[lo];
     const int cnt = (int)(w - woff[lo]);
-    const float* q = q_all + 3 * (size_t)P.l_base;
+    const float* q = q_all + 3 * (size_t)P.q_base;
     const float* d2 = d2_all + P.l_base;
     double sum_error = 0;
     for (int i = cnt * res; i < cnt * res + sliced; ++i) {
@@ -204,6 +210,50 @@ __global__ __launch_bounds__(256) void k_tofs_best(const TofsProb* __restrict__ 
         out[blockIdx.x].lowest = lo;
         out[blockIdx.x].best = best;
     }
+}
+
+// ---- mml_time_offset_estimate_stream: the Livox side and the stamps come from a resident mml_livox_stream ---------------------
+
+constexpr int TOFS_XYZ_BLOCKS = 1024;  // workgroups of k_tofs_livox_xyz at most (each strides over the output)
+
+// The packed x, y, z of the stream records [rec, rec + 5 n): dwords 1 .. 3 of every 5-dword record (mml_livox_point).  Source and
+// destination are walked as dword streams: consecutive lanes write consecutive dwords of `out` and read dwords that lie at most two
+// apart, so a wave's 64 loads fall into the 107 consecutive dwords the 64 stores need -- every fetched line is used, and the 8 of
+// 20 bytes per record that are not coordinates are the only excess.  Bit copies: no float operation touches a coordinate.
+__global__ __launch_bounds__(256) void k_tofs_livox_xyz(const uint32_t* __restrict__ rec, long long n, uint32_t* __restrict__ out) {
+    const long long nd = 3 * n;
+    for (long long o = (long long)blockIdx.x * 256 + threadIdx.x; o < nd; o += (long long)gridDim.x * 256) {
+        const long long k = o / 3;
+        out[o] = rec[5 * k + 1 + (o - 3 * k)];
+    }
+}
+
+// The rows of the stream call, one lane per frame: what the search found, the stamp of the best window's first point read from the
+// stream's stamp array (S points at the range's first point; :1146), the offset (:1161) and the threshold (:1159).  A frame that
+// kept nothing while the range holds points (range_points > 0) is NO_VELO_IN_FOV; its problem has no window, so best stays -1.
+__global__ __launch_bounds__(64) void k_tofs_rows(const TofsProb* __restrict__ tab, const TofsBest* __restrict__ best, int n,
+                                                  const uint64_t* __restrict__ S, uint64_t hs, int res, long long range_points,
+                                                  const uint64_t* __restrict__ velo_stamps, double error_th,
+                                                  mml_time_offset_estimate_row* __restrict__ out) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const TofsProb& P = tab[i];
+    mml_time_offset_estimate_row r;
+    r.status = (P.n_velo == 0 && range_points > 0) ? MML_TOFS_ROW_NO_VELO_IN_FOV : MML_TOFS_ROW_OK;
+    r.n_kept = P.n_velo;
+    r.n_windows = P.n_win;
+    r.best_window = P.n_win > 0 ? best[i].best : -1;
+    r.lowest_error = P.n_win > 0 ? best[i].lowest : 1000000.0;
+    r.optim_start = 0;
+    r.time_offset = 0;
+    r.accepted = 0;
+    r._pad = 0;
+    if (r.best_window >= 0) {  // (best_window * res + sliced < range_points: the index lies inside the range)
+        r.optim_start = hs + S[(long long)r.best_window * res];
+        r.time_offset = velo_stamps[i] - r.optim_start;
+        r.accepted = r.lowest_error < error_th ? 1 : 0;
+    }
+    out[i] = r;
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
@@ -292,10 +342,12 @@ struct TofsIo {
     MmlField<long long> woff;
     MmlField<TofsBest> best;
     MmlField<double> err;
+    MmlField<uint64_t> vstamps;                 // the stream call only (n_rows = n, else 0): the frames' header stamps ...
+    MmlField<mml_time_offset_estimate_row> rows;  // ... and its result rows
     size_t bytes;
-    TofsIo(size_t n, size_t n_win)
+    TofsIo(size_t n, size_t n_win, size_t n_rows = 0)
         : tab(c.take<TofsProb>(n)), tf(c.take<float>(16 * n)), box(c.take<int>(6 * n)), woff(c.take<long long>(n + 1)), best(c.take<TofsBest>(n)),
-          err(c.take<double>(n_win)), bytes(c.bytes()) {}
+          err(c.take<double>(n_win)), vstamps(c.take<uint64_t>(n_rows)), rows(c.take<mml_time_offset_estimate_row>(n_rows)), bytes(c.bytes()) {}
 };
 // big block (device only): 100 bytes per Velodyne point (cells included), 16 per Livox point, the sort's scratch
 struct TofsBig {
@@ -308,16 +360,87 @@ struct TofsBig {
     MmlField<int> cells;
     MmlField<char> sort;
     size_t bytes;
-    TofsBig(size_t nv, size_t nl, size_t n_cells, size_t sort_bytes)
+    // nq: Livox points in the query array, nd: distances (= nq unless the problems share one Livox block)
+    TofsBig(size_t nv, size_t nq, size_t nd, size_t n_cells, size_t sort_bytes)
         : vxyz(c.take<float>(3 * nv)), v4(c.take<float4>(nv)), pts(c.take<float4>(nv)), keys(c.take<unsigned long long>(nv)),
-          keys2(c.take<unsigned long long>(nv)), vals(c.take<unsigned>(nv)), vals2(c.take<unsigned>(nv)), lxyz(c.take<float>(3 * nl)),
-          nn(c.take<float>(nl)), cells(c.take<int>(n_cells)), sort(c.take<char>(sort_bytes)), bytes(c.bytes()) {}
+          keys2(c.take<unsigned long long>(nv)), vals(c.take<unsigned>(nv)), vals2(c.take<unsigned>(nv)), lxyz(c.take<float>(3 * nq)),
+          nn(c.take<float>(nd)), cells(c.take<int>(n_cells)), sort(c.take<char>(sort_bytes)), bytes(c.bytes()) {}
 };
 
 int bits_for(long long values) {  // bits that hold 0 .. values - 1
     int bits = 1;
     while ((1ll << bits) < values) ++bits;
     return bits;
+}
+
+// Every problem's cell and dims from the boxes that were read back, in one pass; its cell_start array follows the previous
+// problem's in the pool.  Returns the largest cell count.
+int tofs_lay_out_grids(int n, TofsProb* h_tab, const int* h_box, float4* d_pts, int* d_cells) {
+    size_t cell_at = 0;
+    int max_cells = 0;
+    for (int i = 0; i < n; ++i) {
+        TofsProb& P = h_tab[i];
+        if (P.n_velo == 0) continue;
+        float box[6];
+        for (int c = 0; c < 6; ++c) box[c] = mml_funkey(h_box[6 * i + c]);
+        tofs_choose_grid(box, P.n_velo, P.g);
+        P.g.m = P.n_velo;
+        P.g.pts = d_pts + P.v_base;
+        P.g.cell_start = d_cells + cell_at;
+        cell_at += (size_t)P.g.ncell + 1;
+        max_cells = P.g.ncell > max_cells ? P.g.ncell : max_cells;
+    }
+    return max_cells;
+}
+
+// The box stage behind the uploads of the clouds (and of the matrices, with_tf): table, empty boxes and window offsets go down out
+// of the pinned block h, the transform and the box pass run, the boxes come back -- and the stage's host synchronisation.
+int tofs_finish_box(mml_ctx* ctx, int n, const TofsIo& io, const TofsBig& big, char* h, char* g, char* b, int max_v, bool with_tf) {
+    hipStream_t s = MML_STREAM(ctx);
+    const TofsProb* d_tab = io.tab.in(g);
+    float4* d_v4 = big.v4.in(b);
+    const unsigned by = (unsigned)n, bx_v = (unsigned)((max_v + 255) / 256);
+    MML_HIP(hipMemcpyAsync(io.tab.in(g), io.tab.in(h), io.tab.bytes(), hipMemcpyHostToDevice, s));
+    MML_HIP(hipMemcpyAsync(io.box.in(g), io.box.in(h), io.box.bytes(), hipMemcpyHostToDevice, s));
+    MML_HIP(hipMemcpyAsync(io.woff.in(g), io.woff.in(h), io.woff.bytes(), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_tofs_tf, dim3(bx_v, by), dim3(256), 0, s, d_tab, big.vxyz.in(b), with_tf ? io.tf.in(g) : nullptr, d_v4);
+    hipLaunchKernelGGL(k_tofs_box, dim3(bx_v < (unsigned)TOFS_BOX_BLOCKS ? bx_v : (unsigned)TOFS_BOX_BLOCKS, by), dim3(256), 0, s, d_tab, d_v4,
+                       io.box.in(g));
+    MML_HIP(hipGetLastError());
+    MML_HIP(hipMemcpyAsync(io.box.in(h), io.box.in(g), io.box.bytes(), hipMemcpyDeviceToHost, s));
+    MML_HIP(hipStreamSynchronize(s));
+    return MML_OK;
+}
+
+// The launches of the search stage: the finished table (pinned block h) goes down again, then keys, the sort, the gather, the
+// cell starts, the distances and -- with a window in the call -- the window errors and every problem's best one.
+int tofs_enqueue_search(mml_ctx* ctx, int n, const TofsIo& io, const TofsBig& big, char* h, char* g, char* b, size_t nv, size_t sort_bytes,
+                        int max_v, int max_l, int max_cells, size_t n_win, int res, int sliced) {
+    hipStream_t s = MML_STREAM(ctx);
+    const TofsProb* d_tab = io.tab.in(g);
+    float4 *d_v4 = big.v4.in(b), *d_pts = big.pts.in(b);
+    unsigned long long *d_keys = big.keys.in(b), *d_keys2 = big.keys2.in(b);
+    unsigned *d_vals = big.vals.in(b), *d_vals2 = big.vals2.in(b);
+    const float* d_lxyz = big.lxyz.in(b);
+    float* d_nn = big.nn.in(b);
+    const unsigned by = (unsigned)n, bx_v = (unsigned)((max_v + 255) / 256);
+    MML_HIP(hipMemcpyAsync(io.tab.in(g), io.tab.in(h), io.tab.bytes(), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_tofs_keys, dim3(bx_v, by), dim3(256), 0, s, d_tab, d_v4, d_keys, d_vals);
+    // ONE stable sort over all Velodyne points; with one problem the high word is zero and the cell bits are enough
+    const int end_bit = n == 1 ? bits_for(max_cells) : 32 + bits_for(n);
+    MmlTmpSpan sort_tmp{big.sort.in(b), sort_bytes};  // (carved out of the big block: nothing is allocated between the launches)
+    const int rc = mml_sort_pairs(ctx, sort_tmp, d_keys, d_keys2, d_vals, d_vals2, nv, end_bit, s);
+    if (rc != MML_OK) return rc;
+    hipLaunchKernelGGL(k_tofs_gather, dim3(bx_v, by), dim3(256), 0, s, d_tab, d_v4, d_vals2, d_pts);
+    hipLaunchKernelGGL(k_tofs_cell_start, dim3((unsigned)((max_cells + 1 + 255) / 256), by), dim3(256), 0, s, d_tab, d_keys2);
+    hipLaunchKernelGGL(k_tofs_nn1, dim3((unsigned)((max_l + 255) / 256), by), dim3(256), 0, s, d_tab, d_lxyz, d_nn);
+    if (n_win > 0) {
+        hipLaunchKernelGGL(k_tofs_window_err, dim3((unsigned)((n_win + 63) / 64)), dim3(64), 0, s, d_tab, n, io.woff.in(g), d_lxyz, d_nn, res,
+                           sliced, io.err.in(g));
+        hipLaunchKernelGGL(k_tofs_best, dim3(by), dim3(256), 0, s, d_tab, io.err.in(g), io.best.in(g));
+    }
+    MML_HIP(hipGetLastError());
+    return MML_OK;
 }
 
 }  // namespace
@@ -385,7 +508,7 @@ int tofs_run(mml_ctx* ctx, const char* who, int n, const float* velo_xyz, const 
     if (nl > 0) {  // (no Livox point in the whole call: nothing to search)
         const size_t sort_bytes = mml_sort_pairs_bytes<unsigned long long>(nv, 64, MML_STREAM(ctx));
         const TofsIo io((size_t)n, n_win);
-        const TofsBig big(nv, nl, n_cells, sort_bytes);
+        const TofsBig big(nv, nl, nl, n_cells, sort_bytes);
         MmlTofsDev* d = mml_side<MmlTofsDev>(ctx, MML_SIDE_TIME_OFFSET);
         if (d->io.reserve(ctx, io.bytes) || d->big.reserve(ctx, big.bytes)) {
             ctx->err = std::string(who) + ": the scratch block could not be grown: " + ctx->err;
@@ -397,78 +520,37 @@ int tofs_run(mml_ctx* ctx, const char* who, int n, const float* velo_xyz, const 
         int* h_box = io.box.in(h);
         const int empty_box[6] = MML_BBOX_EMPTY;
         long long* h_woff = io.woff.in(h);
-        const TofsProb* d_tab = io.tab.in(g);
-        const float* d_tf = tf ? io.tf.in(g) : nullptr;
-        float4 *d_v4 = big.v4.in(b), *d_pts = big.pts.in(b);
-        unsigned long long *d_keys = big.keys.in(b), *d_keys2 = big.keys2.in(b);
-        unsigned *d_vals = big.vals.in(b), *d_vals2 = big.vals2.in(b);
-        float *d_lxyz = big.lxyz.in(b), *d_nn = big.nn.in(b);
-        double* d_err = io.err.in(g);
         h_woff[0] = 0;
         for (int i = 0; i < n; ++i) {
             TofsProb& P = h_tab[i];
             P = TofsProb{};
             P.v_base = vo[i] - vo[0];
             P.n_velo = vo[i + 1] - vo[i];
-            P.l_base = lo[i] - lo[0];
+            P.l_base = P.q_base = lo[i] - lo[0];
             P.n_livox = lo[i + 1] - lo[i];
             P.e_base = h_woff[i];
             P.n_win = nwin[i];
             h_woff[i + 1] = h_woff[i] + nwin[i];
             memcpy(h_box + 6 * i, empty_box, sizeof(empty_box));
         }
-        const unsigned by = (unsigned)n, bx_v = (unsigned)((max_v + 255) / 256);
         {   // host synchronisation 1 of 2: the boxes of all problems in one copy
             MmlStageScope t(ctx, "tofs_box");
-            MML_HIP(hipMemcpyAsync(io.tab.in(g), h_tab, io.tab.bytes(), hipMemcpyHostToDevice, s));
-            MML_HIP(hipMemcpyAsync(io.box.in(g), h_box, io.box.bytes(), hipMemcpyHostToDevice, s));
-            MML_HIP(hipMemcpyAsync(io.woff.in(g), h_woff, io.woff.bytes(), hipMemcpyHostToDevice, s));
             if (tf) MML_HIP(hipMemcpyAsync(io.tf.in(g), tf, io.tf.bytes(), hipMemcpyHostToDevice, s));
             MML_HIP(hipMemcpyAsync(big.vxyz.in(b), velo_xyz + 3 * (size_t)vo[0], big.vxyz.bytes(), hipMemcpyHostToDevice, s));
-            MML_HIP(hipMemcpyAsync(d_lxyz, livox_xyz + 3 * (size_t)lo[0], big.lxyz.bytes(), hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(k_tofs_tf, dim3(bx_v, by), dim3(256), 0, s, d_tab, big.vxyz.in(b), d_tf, d_v4);
-            hipLaunchKernelGGL(k_tofs_box, dim3(bx_v < (unsigned)TOFS_BOX_BLOCKS ? bx_v : (unsigned)TOFS_BOX_BLOCKS, by), dim3(256), 0, s, d_tab, d_v4,
-                               io.box.in(g));
-            MML_HIP(hipGetLastError());
-            MML_HIP(hipMemcpyAsync(h_box, io.box.in(g), io.box.bytes(), hipMemcpyDeviceToHost, s));
-            MML_HIP(hipStreamSynchronize(s));
+            MML_HIP(hipMemcpyAsync(big.lxyz.in(b), livox_xyz + 3 * (size_t)lo[0], big.lxyz.bytes(), hipMemcpyHostToDevice, s));
+            rc = tofs_finish_box(ctx, n, io, big, h, g, b, max_v, tf != nullptr);
+            if (rc != MML_OK) return rc;
         }
-        // every problem's cell and dims in one pass; its cell_start array follows the previous problem's in the pool
-        size_t cell_at = 0;
-        int max_cells = 0;
-        for (int i = 0; i < n; ++i) {
-            TofsProb& P = h_tab[i];
-            if (P.n_velo == 0) continue;
-            float box[6];
-            for (int c = 0; c < 6; ++c) box[c] = mml_funkey(h_box[6 * i + c]);
-            tofs_choose_grid(box, P.n_velo, P.g);
-            P.g.m = P.n_velo;
-            P.g.pts = d_pts + P.v_base;
-            P.g.cell_start = big.cells.in(b) + cell_at;
-            cell_at += (size_t)P.g.ncell + 1;
-            max_cells = P.g.ncell > max_cells ? P.g.ncell : max_cells;
-        }
+        const int max_cells = tofs_lay_out_grids(n, h_tab, h_box, big.pts.in(b), big.cells.in(b));
         {   // host synchronisation 2 of 2: the results
             MmlStageScope t(ctx, "tofs_search");
-            MML_HIP(hipMemcpyAsync(io.tab.in(g), h_tab, io.tab.bytes(), hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(k_tofs_keys, dim3(bx_v, by), dim3(256), 0, s, d_tab, d_v4, d_keys, d_vals);
-            // ONE stable sort over all Velodyne points; with one problem the high word is zero and the cell bits are enough
-            const int end_bit = n == 1 ? bits_for(max_cells) : 32 + bits_for(n);
-            MmlTmpSpan sort_tmp{big.sort.in(b), sort_bytes};  // (carved out of the big block: nothing is allocated between the launches)
-            rc = mml_sort_pairs(ctx, sort_tmp, d_keys, d_keys2, d_vals, d_vals2, nv, end_bit, s);
+            rc = tofs_enqueue_search(ctx, n, io, big, h, g, b, nv, sort_bytes, max_v, max_l, max_cells, n_win, res, sliced);
             if (rc != MML_OK) return rc;
-            hipLaunchKernelGGL(k_tofs_gather, dim3(bx_v, by), dim3(256), 0, s, d_tab, d_v4, d_vals2, d_pts);
-            hipLaunchKernelGGL(k_tofs_cell_start, dim3((unsigned)((max_cells + 1 + 255) / 256), by), dim3(256), 0, s, d_tab, d_keys2);
-            hipLaunchKernelGGL(k_tofs_nn1, dim3((unsigned)((max_l + 255) / 256), by), dim3(256), 0, s, d_tab, d_lxyz, d_nn);
             if (n_win > 0) {
-                hipLaunchKernelGGL(k_tofs_window_err, dim3((unsigned)((n_win + 63) / 64)), dim3(64), 0, s, d_tab, n,
-                                   io.woff.in(g), d_lxyz, d_nn, res, sliced, d_err);
-                hipLaunchKernelGGL(k_tofs_best, dim3(by), dim3(256), 0, s, d_tab, d_err, io.best.in(g));
                 MML_HIP(hipMemcpyAsync(io.best.in(h), io.best.in(g), io.best.bytes(), hipMemcpyDeviceToHost, s));
-                if (window_error) MML_HIP(hipMemcpyAsync(io.err.in(h), d_err, io.err.bytes(), hipMemcpyDeviceToHost, s));
+                if (window_error) MML_HIP(hipMemcpyAsync(io.err.in(h), io.err.in(g), io.err.bytes(), hipMemcpyDeviceToHost, s));
             }
-            MML_HIP(hipGetLastError());
-            if (nn_d2) MML_HIP(hipMemcpyAsync(nn_d2 + lo[0], d_nn, sizeof(float) * nl, hipMemcpyDeviceToHost, s));
+            if (nn_d2) MML_HIP(hipMemcpyAsync(nn_d2 + lo[0], big.nn.in(b), sizeof(float) * nl, hipMemcpyDeviceToHost, s));
             MML_HIP(hipStreamSynchronize(s));
         }
         if (n_win > 0) {
@@ -491,7 +573,158 @@ int tofs_run(mml_ctx* ctx, const char* who, int n, const float* velo_xyz, const 
     return MML_OK;
 }
 
+// mml_time_offset_estimate_stream.  Every check that needs no device result comes before anything is enqueued and before any
+// output is written; the one condition only the device knows -- a frame that keeps nothing -- becomes that row's status.
+int tofs_stream_run(mml_ctx* ctx, mml_livox_stream* stream, long begin, long end, int n, const uint8_t* data, const long* byte_offsets,
+                    const int* n_points, int step, int ox, int oy, int oz, const uint64_t* velo_stamps, const float* tf, int res, int sliced,
+                    double error_th, float* nn_d2, double* window_error, const long* wo, mml_time_offset_estimate_row* out) {
+    const char* who = "mml_time_offset_estimate_stream";
+    const int n_max = MML_FOV_BATCH_MAX < MML_TOFS_BATCH_MAX ? MML_FOV_BATCH_MAX : MML_TOFS_BATCH_MAX;
+    int rc = mml_vfov_check(ctx, who, n, n_max, data, byte_offsets, n_points, step, ox, oy, oz);
+    if (rc != MML_OK) return rc;
+    if (!stream || !velo_stamps || !out || (window_error && !wo)) return mml_refuse(ctx, MML_ERR_INVALID, "%s: a null argument", who);
+    const MmlLivoxView view = mml_livox_stream_view(stream);
+    if (view.ctx != ctx) return mml_refuse(ctx, MML_ERR_INVALID, "%s: the stream belongs to another context", who);
+    if (res < 1 || sliced < 1) return mml_refuse(ctx, MML_ERR_INVALID, "%s: search_resolution / sliced_points must be >= 1", who);
+    if (!(view.front <= begin && begin <= end && end <= view.tail))
+        return mml_refuse(ctx, MML_ERR_INVALID, "%s: the range [%ld, %ld) is not inside the stream's live points [%ld, %ld)", who, begin, end,
+                          view.front, view.tail);
+    if (window_error) {
+        if (wo[0] < 0) return mml_refuse(ctx, MML_ERR_INVALID, "%s: frame 0: a negative window offset", who);
+        for (int i = 0; i < n; ++i)
+            if (wo[i + 1] < wo[i]) return mml_refuse(ctx, MML_ERR_INVALID, "%s: frame %d: window offsets must not decrease", who, i);
+    }
+    const long long L = end - begin;
+    long long total_in = 0;
+    for (int i = 0; i < n; ++i) {  // (points, not kept points: what a frame keeps is known on the device only)
+        if (n_points[i] > ctx->MM)
+            return mml_refuse(ctx, MML_ERR_CAPACITY, "%s: frame %d: its %d points exceed max_map_points = %d", who, i, n_points[i], ctx->MM);
+        total_in += n_points[i];
+    }
+    if (total_in > 0x7fffffffll || (long long)n * L > 0x7fffffffll)
+        return mml_refuse(ctx, MML_ERR_CAPACITY, "%s: %lld Velodyne points or %d x %lld distances exceed INT_MAX", who, total_in, n, L);
+
+    rc = mml_enter_idle(ctx);  // (the pushes still in flight on the stream end here too)
+    if (rc != MML_OK) return rc;
+    const mml_velo_fov_info* info = nullptr;  // host synchronisation 1 of 3: the FOV counts
+    rc = mml_vfov_select_device(ctx, who, n, data, byte_offsets, n_points, step, ox, oy, oz, &info);
+    if (rc != MML_OK) return rc;
+    std::vector<long long> dst((size_t)n);
+    std::vector<int> kept((size_t)n);
+    size_t nv = 0, n_win = 0, n_cells = 0;
+    int max_v = 0;
+    const int nwin_each = L > sliced ? (int)((L - sliced - 1) / res) + 1 : 0;  // windows: cnt = 0, 1, ... while cnt * res + sliced < L
+    for (int i = 0; i < n; ++i) {
+        const int m = info[i].n_kept;
+        kept[(size_t)i] = m;
+        dst[(size_t)i] = (long long)nv;
+        nv += (size_t)m;
+        if (m > 0) {
+            n_win += (size_t)nwin_each;
+            n_cells += (size_t)tofs_cell_budget(m) + 1;
+        }
+        max_v = m > max_v ? m : max_v;
+    }
+    if (L == 0 || nv == 0) {  // nothing to search: an empty range, or no frame kept a point
+        for (int i = 0; i < n; ++i)
+            out[i] = mml_time_offset_estimate_row{L > 0 ? MML_TOFS_ROW_NO_VELO_IN_FOV : MML_TOFS_ROW_OK, kept[(size_t)i], 0, -1, 1000000.0, 0, 0, 0, 0};
+        return MML_OK;
+    }
+
+    const size_t sort_bytes = mml_sort_pairs_bytes<unsigned long long>(nv, 64, MML_STREAM(ctx));
+    const TofsIo io((size_t)n, n_win, (size_t)n);
+    const TofsBig big(nv, (size_t)L, (size_t)n * (size_t)L, n_cells, sort_bytes);
+    MmlTofsDev* d = mml_side<MmlTofsDev>(ctx, MML_SIDE_TIME_OFFSET);
+    if (d->io.reserve(ctx, io.bytes) || d->big.reserve(ctx, big.bytes)) {
+        ctx->err = std::string(who) + ": the scratch block could not be grown: " + ctx->err;
+        return MML_ERR_HIP;
+    }
+    hipStream_t s = MML_STREAM(ctx);
+    char *h = d->io.h, *g = d->io.d, *b = d->big.d;
+    TofsProb* h_tab = io.tab.in(h);
+    int* h_box = io.box.in(h);
+    const int empty_box[6] = MML_BBOX_EMPTY;
+    long long* h_woff = io.woff.in(h);
+    h_woff[0] = 0;
+    for (int i = 0; i < n; ++i) {
+        const int m = kept[(size_t)i];
+        TofsProb& P = h_tab[i];
+        P = TofsProb{};
+        P.v_base = (int)dst[(size_t)i];
+        P.n_velo = m;
+        P.l_base = (int)(i * L);  // (row i of the distances; all frames read the one Livox block at q_base = 0)
+        P.n_livox = m > 0 ? (int)L : 0;
+        P.e_base = h_woff[i];
+        P.n_win = m > 0 ? nwin_each : 0;
+        h_woff[i + 1] = h_woff[i] + P.n_win;
+        memcpy(h_box + 6 * i, empty_box, sizeof(empty_box));
+        if (tf) memcpy(io.tf.in(h) + 16 * (size_t)i, tf, sizeof(float) * 16);
+    }
+    memcpy(io.vstamps.in(h), velo_stamps, io.vstamps.bytes());
+    const long at = begin - view.base;  // the range's first point in the live arrays
+    {   // host synchronisation 2 of 3: the boxes
+        MmlStageScope t(ctx, "tofs_box");
+        if (tf) MML_HIP(hipMemcpyAsync(io.tf.in(g), io.tf.in(h), io.tf.bytes(), hipMemcpyHostToDevice, s));
+        MML_HIP(hipMemcpyAsync(io.vstamps.in(g), io.vstamps.in(h), io.vstamps.bytes(), hipMemcpyHostToDevice, s));
+        rc = mml_vfov_pack_device(ctx, n, dst.data(), max_v, big.vxyz.in(b));  // the FOV rows, device to device
+        if (rc != MML_OK) return rc;
+        const long long blocks = (3 * L + 255) / 256;
+        hipLaunchKernelGGL(k_tofs_livox_xyz, dim3((unsigned)(blocks < TOFS_XYZ_BLOCKS ? blocks : TOFS_XYZ_BLOCKS)), dim3(256), 0, s,
+                           view.rec + 5 * (size_t)at, L, reinterpret_cast<uint32_t*>(big.lxyz.in(b)));
+        rc = tofs_finish_box(ctx, n, io, big, h, g, b, max_v, tf != nullptr);
+        if (rc != MML_OK) return rc;
+    }
+    const int max_cells = tofs_lay_out_grids(n, h_tab, h_box, big.pts.in(b), big.cells.in(b));
+    {   // host synchronisation 3 of 3: the rows
+        MmlStageScope t(ctx, "tofs_search");
+        rc = tofs_enqueue_search(ctx, n, io, big, h, g, b, nv, sort_bytes, max_v, (int)L, max_cells, n_win, res, sliced);
+        if (rc != MML_OK) return rc;
+        hipLaunchKernelGGL(k_tofs_rows, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, io.tab.in(g), io.best.in(g), n, view.stamp + at, view.hs, res,
+                           L, io.vstamps.in(g), error_th, io.rows.in(g));
+        MML_HIP(hipGetLastError());
+        MML_HIP(hipMemcpyAsync(io.rows.in(h), io.rows.in(g), io.rows.bytes(), hipMemcpyDeviceToHost, s));
+        if (window_error && n_win > 0) MML_HIP(hipMemcpyAsync(io.err.in(h), io.err.in(g), io.err.bytes(), hipMemcpyDeviceToHost, s));
+        if (nn_d2)  // the rows of the frames that searched, runs of neighbours in one copy; a NO_VELO_IN_FOV row stays unwritten
+            for (int i = 0; i < n;) {
+                if (kept[(size_t)i] == 0) {
+                    ++i;
+                    continue;
+                }
+                int j = i;
+                while (j < n && kept[(size_t)j] > 0) ++j;
+                MML_HIP(hipMemcpyAsync(nn_d2 + (size_t)i * (size_t)L, big.nn.in(b) + (size_t)i * (size_t)L, sizeof(float) * (size_t)(j - i) * (size_t)L,
+                                       hipMemcpyDeviceToHost, s));
+                i = j;
+            }
+        MML_HIP(hipStreamSynchronize(s));
+    }
+    memcpy(out, io.rows.in(h), io.rows.bytes());
+    if (window_error && n_win > 0) {
+        const double* h_err = io.err.in(h);
+        for (int i = 0; i < n; ++i) {  // at most the room the caller gave this frame
+            const long room = wo[i + 1] - wo[i], have = h_tab[i].n_win;
+            const long k = room < have ? room : have;
+            if (k > 0) memcpy(window_error + wo[i], h_err + h_tab[i].e_base, sizeof(double) * (size_t)k);
+        }
+    }
+    return MML_OK;
+}
+
 }  // namespace
+
+extern "C" int mml_time_offset_estimate_stream(mml_ctx* ctx, mml_livox_stream* s, long livox_begin, long livox_end, int n, const uint8_t* data,
+                                               const long* byte_offsets, const int* n_points, int point_step, int off_x, int off_y, int off_z,
+                                               const uint64_t* velo_stamps, const float* tf, int search_resolution, int sliced_points,
+                                               double error_th, float* nn_d2, double* window_error, const long* window_offsets,
+                                               mml_time_offset_estimate_row* out) {
+    if (!ctx) return MML_ERR_INVALID;
+    return tofs_stream_run(ctx, s, livox_begin, livox_end, n, data, byte_offsets, n_points, point_step, off_x, off_y, off_z, velo_stamps, tf,
+                           search_resolution, sliced_points, error_th, nn_d2, window_error, window_offsets, out);
+}
+
+extern "C" int mml_time_offset_gate(int n_velo, const uint64_t* velo_stamps, uint64_t hori_stamp, int n_hori_msgs, int* selected, int* status) {
+    return time_offset_gate(n_velo, velo_stamps, hori_stamp, n_hori_msgs, selected, status);
+}
 
 extern "C" int mml_time_offset_plan(int n, const int* velo_offsets, const int* livox_offsets, int search_resolution, int sliced_points,
                                     int max_map_points, int* n_windows, int* bad_problem) {

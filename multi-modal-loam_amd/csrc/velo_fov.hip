@@ -21,6 +21,8 @@
 // Scratch (one grow-only set owned by the context, mml_mem.h, released by mml_destroy), per input point of the largest call:
 // point_step bytes of records (device + pinned), 4 (azimuth), 16 (rows in place), 16 + 12 (the two packed outputs);
 // per frame 48 bytes (device + pinned).  Two launches and at most two host synchronisations per call whatever n is.
+//   The two halves are stages of their own (vfov_select_stage, vfov_pack_stage): mml_time_offset_estimate_stream (time_offset.hip)
+// runs the first and lets the second pack the rows straight into its search's input on the device.
 // Compiled with -ffp-contract=off.
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -205,6 +207,14 @@ struct MmlVfovDev {
     MmlStaging<char> io;          // frame table | info rows
     MmlStaging<uint8_t> in;       // the frames' records, each frame 16-byte aligned
     MmlStaging<char, false> big;  // azimuths | rows in place | packed x,y,z,relTime | packed x,y,z
+    // the selection these blocks hold (vfov_select_stage), for the packing pass that follows it
+    VfovFrame* h_tab = nullptr;
+    VfovFrame* d_tab = nullptr;
+    size_t tab_bytes = 0;
+    mml_velo_fov_info* d_info = nullptr;
+    float4* d_rows = nullptr;
+    float4* d_packed4 = nullptr;
+    float* d_packed3 = nullptr;
     ~MmlVfovDev() {
         io.release();
         in.release();
@@ -214,18 +224,19 @@ struct MmlVfovDev {
 
 namespace {
 
-int vfov_run(mml_ctx* ctx, const char* who, int n, const uint8_t* data, const long* byte_offsets, const int* n_points, int step, int ox, int oy,
-             int oz, float* xyzt, float* xyz, long capacity_rows, int* n_kept, mml_velo_fov_info* info) {
-    // ---- checks: all before any work, a refusal writes nothing ----
-    if (n < 1 || n > MML_FOV_BATCH_MAX) return mml_refuse(ctx, MML_ERR_INVALID, "%s: n = %d is outside 1 .. %d", who, n, MML_FOV_BATCH_MAX);
-    if (!(byte_offsets && n_points && n_kept)) return mml_refuse(ctx, MML_ERR_INVALID, "%s: a null argument", who);
+// The argument rules of the FOV calls, in the order the calls state them; `outputs_ok` / `capacity_rows` are the caller's own
+// (required output pointers present; < 0: refused where the caller wants rows).  A refusal writes nothing.
+int vfov_check(mml_ctx* ctx, const char* who, int n, int n_max, bool outputs_ok, bool want_rows, long capacity_rows, const uint8_t* data,
+               const long* byte_offsets, const int* n_points, int step, int ox, int oy, int oz) {
+    if (n < 1 || n > n_max) return mml_refuse(ctx, MML_ERR_INVALID, "%s: n = %d is outside 1 .. %d", who, n, n_max);
+    if (!(byte_offsets && n_points && outputs_ok)) return mml_refuse(ctx, MML_ERR_INVALID, "%s: a null argument", who);
     if (step < 12) return mml_refuse(ctx, MML_ERR_INVALID, "%s: point_step = %d is below 12", who, step);
     const int offs[3] = {ox, oy, oz};
     for (int c = 0; c < 3; ++c)
         if (offs[c] < 0 || offs[c] > step - 4 || (offs[c] & 3))
             return mml_refuse(ctx, MML_ERR_INVALID, "%s: the offset %d of field %c is outside [0, point_step - 4] or not 4-byte aligned", who, offs[c],
                               "xyz"[c]);
-    if ((xyzt || xyz) && capacity_rows < 0) return mml_refuse(ctx, MML_ERR_INVALID, "%s: capacity_rows = %ld is negative", who, capacity_rows);
+    if (want_rows && capacity_rows < 0) return mml_refuse(ctx, MML_ERR_INVALID, "%s: capacity_rows = %ld is negative", who, capacity_rows);
     long long total_in = 0;
     for (int i = 0; i < n; ++i) {
         if (n_points[i] < 0 || byte_offsets[i] < 0)
@@ -239,7 +250,86 @@ int vfov_run(mml_ctx* ctx, const char* who, int n, const uint8_t* data, const lo
             if (n_points[i] > ctx->cfg.max_velo_points)
                 return mml_refuse(ctx, MML_ERR_CAPACITY, "%s: frame %d: %d points exceed max_velo_points = %d", who, i, n_points[i],
                                   ctx->cfg.max_velo_points);
+    return MML_OK;
+}
+
+// The selection of n checked frames on the device: the records go down, k_vfov_select runs, counts and info come back -- ONE host
+// synchronisation.  *info: the n rows in the pinned block, valid until the context's next selection.  with_packed: room for the
+// two packed outputs of vfov_run behind the rows.
+int vfov_select_stage(mml_ctx* ctx, const char* who, int n, const uint8_t* data, const long* byte_offsets, const int* n_points, int step, int ox,
+                      int oy, int oz, bool with_packed, const mml_velo_fov_info** info) {
+    MML_HIP(hipSetDevice(ctx->device));
+    long long total_in = 0;
+    for (int i = 0; i < n; ++i) total_in += n_points[i];
+    MmlCarve<256> io;
+    const auto tab = io.take<VfovFrame>((size_t)n);
+    const auto inf = io.take<mml_velo_fov_info>((size_t)n);
+    MmlCarve<16> in;  // the frames' records, one field per frame: here for the block's size, below again for the offsets
+    for (int i = 0; i < n; ++i) in.take<uint8_t>((size_t)n_points[i] * (size_t)step);
+    const size_t in_bytes = in.bytes(), rows_in = (size_t)total_in;
+    MmlCarve<256> big;
+    const auto azi = big.take<float>(rows_in);
+    const auto rows = big.take<float4>(rows_in), packed4 = big.take<float4>(with_packed ? rows_in : 0);
+    const auto packed3 = big.take<float>(with_packed ? 3 * rows_in : 0);
+    MmlVfovDev* d = mml_side<MmlVfovDev>(ctx, MML_SIDE_VELO_FOV);
+    if (d->io.reserve(ctx, io.bytes()) || d->in.reserve(ctx, in_bytes ? in_bytes : 16) || d->big.reserve(ctx, big.bytes() ? big.bytes() : 256)) {
+        ctx->err = std::string(who) + ": the scratch block could not be grown: " + ctx->err;
+        return MML_ERR_HIP;
+    }
+    VfovFrame* h_tab = tab.in(d->io.h);
+    d->h_tab = h_tab;
+    d->d_tab = tab.in(d->io.d);
+    d->tab_bytes = tab.bytes();
+    d->d_info = inf.in(d->io.d);
+    d->d_rows = rows.in(d->big.d);
+    d->d_packed4 = with_packed ? packed4.in(d->big.d) : nullptr;
+    d->d_packed3 = with_packed ? packed3.in(d->big.d) : nullptr;
+    {
+        MmlCarve<16> at;
+        long long row = 0;
+        for (int i = 0; i < n; ++i) {
+            const auto rec = at.take<uint8_t>((size_t)n_points[i] * (size_t)step);
+            if (rec.n) memcpy(rec.in(d->in.h), data + byte_offsets[i], rec.bytes());
+            h_tab[i] = VfovFrame{(long long)rec.off, row, 0, n_points[i], 0};
+            row += n_points[i];
+        }
+    }
+    const VfovLayout L{step, ox, oy, oz, (step & 3) == 0 ? 1 : 0};
+    hipStream_t s = MML_STREAM(ctx);
+    {   // the selection's host synchronisation: counts and info
+        MmlStageScope t(ctx, "velo_fov");
+        MML_HIP(hipMemcpyAsync(d->d_tab, h_tab, tab.bytes(), hipMemcpyHostToDevice, s));
+        if (in_bytes) MML_HIP(hipMemcpyAsync(d->in.d, d->in.h, in_bytes, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_vfov_select, dim3(1, (unsigned)n), dim3(VFOV_BLOCK), 0, s, d->d_tab, d->in.d, L, azi.in(d->big.d), d->d_rows,
+                           d->d_info);
+        MML_HIP(hipGetLastError());
+        MML_HIP(hipMemcpyAsync(inf.in(d->io.h), d->d_info, inf.bytes(), hipMemcpyDeviceToHost, s));
+        MML_HIP(hipStreamSynchronize(s));
+    }
+    *info = inf.in(d->io.h);
+    return MML_OK;
+}
+
+// The packing pass of the selection the blocks hold, enqueued on the stream: frame i's kept rows go to row dst[i] of d_xyzt
+// (x, y, z, relTime) and / or d_xyz (x, y, z), device arrays of the caller's.
+int vfov_pack_stage(mml_ctx* ctx, int n, const long long* dst, int max_kept, float4* d_xyzt, float* d_xyz) {
+    MmlVfovDev* d = mml_side<MmlVfovDev>(ctx, MML_SIDE_VELO_FOV);
+    hipStream_t s = MML_STREAM(ctx);
+    for (int i = 0; i < n; ++i) d->h_tab[i].dst = dst[i];
+    const unsigned bx = (unsigned)((max_kept + 255) / 256);
+    MML_HIP(hipMemcpyAsync(d->d_tab, d->h_tab, d->tab_bytes, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_vfov_pack, dim3(bx < (unsigned)VFOV_PACK_BLOCKS ? bx : (unsigned)VFOV_PACK_BLOCKS, (unsigned)n), dim3(256), 0, s, d->d_tab,
+                       d->d_info, d->d_rows, d_xyzt, d_xyz);
+    MML_HIP(hipGetLastError());
+    return MML_OK;
+}
+
+int vfov_run(mml_ctx* ctx, const char* who, int n, const uint8_t* data, const long* byte_offsets, const int* n_points, int step, int ox, int oy,
+             int oz, float* xyzt, float* xyz, long capacity_rows, int* n_kept, mml_velo_fov_info* info) {
+    // ---- checks: all before any work, a refusal writes nothing ----
     const bool want_rows = xyzt || xyz;
+    int rc = vfov_check(ctx, who, n, MML_FOV_BATCH_MAX, n_kept != nullptr, want_rows, capacity_rows, data, byte_offsets, n_points, step, ox, oy, oz);
+    if (rc != MML_OK) return rc;
 
     if (!ctx) {  // the host build of the routine
         std::vector<mml_velo_fov_info> inf((size_t)n);
@@ -261,53 +351,16 @@ int vfov_run(mml_ctx* ctx, const char* who, int n, const uint8_t* data, const lo
     }
 
     // ---- device ----
-    MML_HIP(hipSetDevice(ctx->device));
-    MmlCarve<256> io;
-    const auto tab = io.take<VfovFrame>((size_t)n);
-    const auto inf = io.take<mml_velo_fov_info>((size_t)n);
-    MmlCarve<16> in;  // the frames' records, one field per frame: here for the block's size, below again for the offsets
-    for (int i = 0; i < n; ++i) in.take<uint8_t>((size_t)n_points[i] * (size_t)step);
-    const size_t in_bytes = in.bytes(), rows_in = (size_t)total_in;
-    MmlCarve<256> big;
-    const auto azi = big.take<float>(rows_in);
-    const auto rows = big.take<float4>(rows_in), packed4 = big.take<float4>(rows_in);
-    const auto packed3 = big.take<float>(3 * rows_in);
+    const mml_velo_fov_info* h_info = nullptr;  // host synchronisation 1 of 2: counts and info
+    rc = vfov_select_stage(ctx, who, n, data, byte_offsets, n_points, step, ox, oy, oz, true, &h_info);
+    if (rc != MML_OK) return rc;
     MmlVfovDev* d = mml_side<MmlVfovDev>(ctx, MML_SIDE_VELO_FOV);
-    if (d->io.reserve(ctx, io.bytes()) || d->in.reserve(ctx, in_bytes ? in_bytes : 16) || d->big.reserve(ctx, big.bytes() ? big.bytes() : 256)) {
-        ctx->err = std::string(who) + ": the scratch block could not be grown: " + ctx->err;
-        return MML_ERR_HIP;
-    }
-    VfovFrame* h_tab = tab.in(d->io.h);
-    const mml_velo_fov_info* h_info = inf.in(d->io.h);
-    const VfovFrame* d_tab = tab.in(d->io.d);
-    mml_velo_fov_info* d_info = inf.in(d->io.d);
-    {
-        MmlCarve<16> at;
-        long long row = 0;
-        for (int i = 0; i < n; ++i) {
-            const auto rec = at.take<uint8_t>((size_t)n_points[i] * (size_t)step);
-            if (rec.n) memcpy(rec.in(d->in.h), data + byte_offsets[i], rec.bytes());
-            h_tab[i] = VfovFrame{(long long)rec.off, row, 0, n_points[i], 0};
-            row += n_points[i];
-        }
-    }
-    const VfovLayout L{step, ox, oy, oz, (step & 3) == 0 ? 1 : 0};
     hipStream_t s = MML_STREAM(ctx);
-    float4* d_rows = rows.in(d->big.d);
-    {   // host synchronisation 1 of 2: counts and info
-        MmlStageScope t(ctx, "velo_fov");
-        MML_HIP(hipMemcpyAsync(tab.in(d->io.d), h_tab, tab.bytes(), hipMemcpyHostToDevice, s));
-        if (in_bytes) MML_HIP(hipMemcpyAsync(d->in.d, d->in.h, in_bytes, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_vfov_select, dim3(1, (unsigned)n), dim3(VFOV_BLOCK), 0, s, d_tab, d->in.d, L, azi.in(d->big.d), d_rows,
-                           d_info);
-        MML_HIP(hipGetLastError());
-        MML_HIP(hipMemcpyAsync(inf.in(d->io.h), d_info, inf.bytes(), hipMemcpyDeviceToHost, s));
-        MML_HIP(hipStreamSynchronize(s));
-    }
+    std::vector<long long> dst((size_t)n);
     long long total = 0;
     int max_kept = 0;
     for (int i = 0; i < n; ++i) {
-        h_tab[i].dst = total;
+        dst[(size_t)i] = total;
         total += h_info[i].n_kept;
         max_kept = h_info[i].n_kept > max_kept ? h_info[i].n_kept : max_kept;
     }
@@ -315,13 +368,10 @@ int vfov_run(mml_ctx* ctx, const char* who, int n, const uint8_t* data, const lo
         return mml_refuse(ctx, MML_ERR_CAPACITY, "%s: %lld rows are kept, capacity_rows is %ld", who, total, capacity_rows);
     if (want_rows && total > 0) {  // host synchronisation 2 of 2: the rows
         MmlStageScope t(ctx, "velo_fov");
-        float4* d_xyzt = xyzt ? packed4.in(d->big.d) : nullptr;
-        float* d_xyz = xyz ? packed3.in(d->big.d) : nullptr;
-        const unsigned bx = (unsigned)((max_kept + 255) / 256);
-        MML_HIP(hipMemcpyAsync(tab.in(d->io.d), h_tab, tab.bytes(), hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_vfov_pack, dim3(bx < (unsigned)VFOV_PACK_BLOCKS ? bx : (unsigned)VFOV_PACK_BLOCKS, (unsigned)n), dim3(256), 0, s, d_tab,
-                           d_info, d_rows, d_xyzt, d_xyz);
-        MML_HIP(hipGetLastError());
+        float4* d_xyzt = xyzt ? d->d_packed4 : nullptr;
+        float* d_xyz = xyz ? d->d_packed3 : nullptr;
+        rc = vfov_pack_stage(ctx, n, dst.data(), max_kept, d_xyzt, d_xyz);
+        if (rc != MML_OK) return rc;
         if (xyzt) MML_HIP(hipMemcpyAsync(xyzt, d_xyzt, sizeof(float4) * (size_t)total, hipMemcpyDeviceToHost, s));
         if (xyz) MML_HIP(hipMemcpyAsync(xyz, d_xyz, sizeof(float) * 3 * (size_t)total, hipMemcpyDeviceToHost, s));
         MML_HIP(hipStreamSynchronize(s));
@@ -332,6 +382,19 @@ int vfov_run(mml_ctx* ctx, const char* who, int n, const uint8_t* data, const lo
 }
 
 }  // namespace
+
+// for mml_time_offset_estimate_stream (time_offset.hip), which keeps the selection on the device: mml_internal.h
+int mml_vfov_check(mml_ctx* ctx, const char* who, int n, int n_max, const uint8_t* data, const long* byte_offsets, const int* n_points, int step,
+                   int ox, int oy, int oz) {
+    return vfov_check(ctx, who, n, n_max, true, false, 0, data, byte_offsets, n_points, step, ox, oy, oz);
+}
+int mml_vfov_select_device(mml_ctx* ctx, const char* who, int n, const uint8_t* data, const long* byte_offsets, const int* n_points, int step,
+                           int ox, int oy, int oz, const mml_velo_fov_info** info) {
+    return vfov_select_stage(ctx, who, n, data, byte_offsets, n_points, step, ox, oy, oz, false, info);
+}
+int mml_vfov_pack_device(mml_ctx* ctx, int n, const long long* dst, int max_kept, float* d_xyz) {
+    return vfov_pack_stage(ctx, n, dst, max_kept, nullptr, d_xyz);
+}
 
 extern "C" int mml_velo_fov_select_batch(mml_ctx* ctx, int n, const uint8_t* data, const long* byte_offsets, const int* n_points, int point_step,
                                          int off_x, int off_y, int off_z, float* xyzt, float* xyz, long capacity_rows, int* n_kept,

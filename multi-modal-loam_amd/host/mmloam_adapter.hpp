@@ -1042,8 +1042,25 @@ class LivoxPointQueue {
 
     // :736-763.  The points must stay valid until the next synchronising call (pub_horipoints_given_stamp is one).
     void transform_hori_timestamp(const std::vector<LivoxMsg>& hori_msg_vec) {
-        for (const LivoxMsg& m : hori_msg_vec)
+        for (const LivoxMsg& m : hori_msg_vec) {
             check(ctx_.get(), mml_livox_stream_push(s_, m.timebase, m.points, m.point_num), "mml_livox_stream_push");
+            marks_.push_back(Mark{m.timebase, pushed_, m.point_num});
+            pushed_ += m.point_num;
+        }
+    }
+    // What the queue knows from its pushes: per message its time base, its first point's absolute index and its point count
+    // (hori_vec's boundaries for estimate_timeoffset below, :1049-1074).  drop_marks_before forgets the messages that end at or
+    // before `front` (what the assemble calls have erased).
+    struct Mark {
+        uint64_t timebase;
+        long first;
+        int count;
+    };
+    const std::vector<Mark>& marks() const { return marks_; }
+    void drop_marks_before(long front) {
+        size_t k = 0;
+        while (k < marks_.size() && marks_[k].first + marks_[k].count <= front) ++k;
+        marks_.erase(marks_.begin(), marks_.begin() + (long)k);
     }
     // :766-868 with :350-352: one frame into `slot`.  velo_xyzi: n_velo x (x, y, z, intensity); velo_hori_tf: 16 floats or nullptr.
     bool pub_horipoints_given_stamp(uint64_t velo_start_stamp, uint64_t velo_end_stamp, const float* velo_xyzi, int n_velo,
@@ -1102,13 +1119,51 @@ class LivoxPointQueue {
         check(ctx_.get(), mml_livox_stream_state_get(s_, &st), "mml_livox_stream_state_get");
         return st;
     }
-    void reset() { check(ctx_.get(), mml_livox_stream_reset(s_), "mml_livox_stream_reset"); }
+    void reset() {
+        check(ctx_.get(), mml_livox_stream_reset(s_), "mml_livox_stream_reset");
+        marks_.clear();
+        pushed_ = 0;
+    }
 
    private:
     Context& ctx_;
     mml_livox_stream* s_ = nullptr;
     std::vector<mml_union_frame> frames_;
+    std::vector<Mark> marks_;
+    long pushed_ = 0;
 };
+
+// LidarsParamEstimator::estimate_timeoffset (:1021-1166) on the queue: the gate of :1026-1043 (mml_time_offset_gate) over the queued
+// Velodyne frames, then ONE mml_time_offset_estimate_stream call for the frame it selects against the queue's last eight messages
+// -- FOV selection, search and stamps on the device, nothing handed over through host memory.  velo_msgs / velo_stamps: velo_vec,
+// oldest first, as payloads (point_step / off_*: the PointCloud2 layout) and header stamps in ns; hori_stamp: hori_vec.back()'s
+// header stamp.  The result is the selected frame's row, `accepted` being _time_offset_initd and `time_offset` _time_offset;
+// `selected` is the frame's index, -1 with gate_status EMPTY / TOO_FEW_MESSAGES (defined refusals, include/mmloam_hip.h), in which
+// case no device call is made.
+struct TimeOffsetEstimate {
+    int gate_status = MML_TOFS_GATE_EMPTY, selected = -1;
+    mml_time_offset_estimate_row row = {0, 0, 0, -1, 1000000.0, 0, 0, 0, 0};
+};
+inline TimeOffsetEstimate estimate_timeoffset(Context& ctx, LivoxPointQueue& queue, const std::vector<VeloFrame>& velo_msgs,
+                                              const std::vector<uint64_t>& velo_stamps, uint64_t hori_stamp, const float* velo_hori_tf,
+                                              int offset_search_resolution, int offset_search_sliced_points, double time_esti_error_th,
+                                              int point_step = 16, int off_x = 0, int off_y = 4, int off_z = 8) {
+    if (velo_msgs.size() != velo_stamps.size()) throw std::runtime_error("estimate_timeoffset: one stamp per Velodyne frame");
+    TimeOffsetEstimate r;
+    const std::vector<LivoxPointQueue::Mark>& marks = queue.marks();
+    check(ctx.get(), mml_time_offset_gate((int)velo_stamps.size(), velo_stamps.data(), hori_stamp, (int)marks.size(), &r.selected, &r.gate_status),
+          "mml_time_offset_gate");
+    if (r.selected < 0) return r;
+    const LivoxPointQueue::Mark &first = marks[marks.size() - 8], &last = marks.back();
+    const VeloFrame& f = velo_msgs[(size_t)r.selected];
+    const long at = 0;
+    check(ctx.get(), mml_time_offset_estimate_stream(ctx.get(), queue.get(), first.first, last.first + last.count, 1, f.data, &at, &f.n_points,
+                                                     point_step, off_x, off_y, off_z, &velo_stamps[(size_t)r.selected], velo_hori_tf,
+                                                     offset_search_resolution, offset_search_sliced_points, time_esti_error_th, nullptr, nullptr,
+                                                     nullptr, &r.row),
+          "mml_time_offset_estimate_stream");
+    return r;
+}
 
 // ---- the pose node's IMU queue (unionPoseEstimation.cpp: _imuMsgVector) --------------------------------------------------------
 // push is imuHandler's push_back (:296); fetchImuMsgs (:307-395) cuts (startTime, endTime] out of the queue, the message

@@ -482,3 +482,27 @@ def time_offset_from_frames(ctx, velo_frames, livox, tf=None, search_resolution=
         raise ValueError("%d Livox clouds for %d Velodyne frames" % (len(livox), n))
     velo_list = [sel["xyz"][vo[i]:vo[i + 1]] for i in range(n)]     # (views: time_offset_pack concatenates them back in order)
     return ctx.time_offset_search_batch(velo_list, livox, search_resolution, sliced_points, tfs=tf), sel
+
+
+def time_offset_from_stream(ctx, stream, message_marks, velo_frames, velo_stamps, hori_stamp, tf=None, search_resolution=30,
+                            sliced_points=12000, error_th=1e6, all_frames=False):
+    """LidarsParamEstimator::estimate_timeoffset (unionLidarsAligner.cpp:1021-1166) on a resident Livox stream: the gate of
+    :1026-1043 (time_offset_gate), then ONE Context.time_offset_estimate_stream call for the frame it selects against the merged
+    last eight messages (:1049-1074).  message_marks: per pushed message its first point's absolute index, in push order, with the
+    stream's tail as one more entry (len = messages + 1) -- what the caller knows from its pushes; velo_frames / velo_stamps: the
+    queued Velodyne frames, oldest first, and their header stamps (ns); hori_stamp: the newest Livox message's header stamp.
+    Returns (row, selected, status): the selected frame's dict (None when the gate refuses: TOFS_GATE_EMPTY,
+    TOFS_GATE_TOO_FEW_MESSAGES), its index and the gate's status.  all_frames=True runs every queued frame in the one call and
+    returns the list of their dicts in the place of row (the gate's answer still comes with it; None only for too few messages)."""
+    import importlib
+    M = importlib.import_module(__package__)
+    marks = [int(m) for m in message_marks]
+    n_msgs = len(marks) - 1
+    selected, status = M.time_offset_gate(velo_stamps, hori_stamp, n_msgs)
+    if n_msgs < 8 or (selected < 0 and not all_frames):
+        return None, selected, status
+    begin, end = marks[n_msgs - 8], marks[n_msgs]
+    which = list(range(len(velo_frames))) if all_frames else [selected]
+    rows = ctx.time_offset_estimate_stream(stream, begin, end, [velo_frames[i] for i in which], [int(velo_stamps[i]) for i in which], tf,
+                                           search_resolution, sliced_points, error_th)
+    return (rows if all_frames else rows[0]), selected, status
