@@ -294,6 +294,9 @@ def lib():
         if hasattr(L, "mml_debug_fw_replay"):
             L.mml_debug_fw_replay.restype = C.c_int
             L.mml_debug_fw_replay.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_longlong] + [C.c_void_p] * 3
+        if hasattr(L, "mml_debug_phase_clocks"):
+            L.mml_debug_phase_clocks.restype = C.c_int
+            L.mml_debug_phase_clocks.argtypes = [C.c_char_p, C.POINTER(C.c_ulonglong), C.c_int, C.c_int]
         if hasattr(L, "mml_imu_preintegrate_batch"):
             L.mml_imu_preintegrate_batch.restype = C.c_int
             L.mml_imu_preintegrate_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
@@ -1882,6 +1885,15 @@ def tr_replay(ctx, variant, scripts):
     elif rc != MML_OK:
         raise MmlError(rc, "mml_debug_tr_replay")
     return xc, dig, digi
+
+
+PHASE_CLOCKS_UNKNOWN, PHASE_CLOCKS_NOT_BUILT = -1, -2
+
+
+def phase_clocks(family, out, reset=False):
+    """mml_debug_phase_clocks (a test hook; csrc/phase_clock.h, tools/phases.py): the slots of a timing build's phase clocks into the
+    ctypes c_ulonglong array out, or all of them zeroed.  Returns the slot count or a negative code (the two above; -3 out too small; -4 HIP)."""
+    return lib().mml_debug_phase_clocks(family.encode(), out, len(out), int(reset))
 
 
 FW_DIGEST_DOUBLES = 128

@@ -12,6 +12,7 @@
 
 #include "imu_math.h"
 #include "mml_internal.h"
+#include "phase_clock.h"
 #include "raw_gather_dev.h"
 
 int mml_launch_detect_line(mml_ctx* ctx, int n, uint16_t* d_final);
@@ -2178,6 +2179,39 @@ extern "C" int mml_issue_rate(mml_ctx* ctx, int kind, int reps, double* wave_ins
     }
     *wave_instr_per_s = best;
     return MML_OK;
+}
+
+// ---- the phase clocks' reader (phase_clock.h; a test hook, not in the public header) ----
+namespace {
+constexpr const char* kPhaseFamilies[] = {"op", "st", "sel", "sp", "vx", "sv", "svw"};
+struct PhaseFamily {
+    const char* name;
+    const void* symbol;
+    int slots;
+} g_phase_built[sizeof(kPhaseFamilies) / sizeof(kPhaseFamilies[0])];  // the families this library was built with
+int g_phase_nbuilt = 0;
+}  // namespace
+int phase_clock_register(const char* family, const void* symbol, int slots) {
+    g_phase_built[g_phase_nbuilt++] = {family, symbol, slots};
+    return 0;
+}
+// reset != 0: zeroes the family's slots; else copies them to out[capacity].  Returns the slot count, -1 for a name that is no family,
+// -2 for a family this library was not built with (both before any HIP call), -3 for an out that is missing or too small, -4 HIP error
+extern "C" int mml_debug_phase_clocks(const char* family, unsigned long long* out, int capacity, int reset) {
+    bool known = false;
+    for (const char* name : kPhaseFamilies) known = known || (family && !strcmp(family, name));
+    if (!known) return -1;
+    const PhaseFamily* f = nullptr;
+    for (int i = 0; i < g_phase_nbuilt; ++i)
+        if (!strcmp(family, g_phase_built[i].name)) f = &g_phase_built[i];
+    if (!f) return -2;
+    const size_t bytes = sizeof(unsigned long long) * f->slots;
+    if (reset) {
+        const unsigned long long zeros[PHASE_CLOCK_MAX_SLOTS] = {};
+        return hipMemcpyToSymbol(f->symbol, zeros, bytes) == hipSuccess ? f->slots : -4;
+    }
+    if (!out || capacity < f->slots) return -3;
+    return hipMemcpyFromSymbol(out, f->symbol, bytes) == hipSuccess ? f->slots : -4;
 }
 
 int mml_stage_begin(mml_ctx* ctx, const char* name) {

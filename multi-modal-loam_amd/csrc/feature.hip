@@ -25,6 +25,7 @@
 
 #include "libm_f32.h"
 #include "mml_internal.h"
+#include "phase_clock.h"
 
 namespace {
 
@@ -950,30 +951,14 @@ __device__ __forceinline__ int wave_incl_scan(int v) {
     return v;
 }
 
-#ifdef MML_OP_TIMING
-// phase clocks of one bucketing block (the Velodyne block MML_OP_TIMING of the 518th slot of the launch; tools/assign_phases.py):
+// phase clocks of one bucketing block (the Velodyne block MML_OP_TIMING of the 518th slot of the launch; tools/phases.py op):
 // [0..9] its second wavefront, [10..12] the look-back section of the first one
-__device__ unsigned long long g_op_dbg[16];
-#define OP_MARK_(flag, prev, id)                       \
-    do {                                               \
-        if (flag) {                                    \
-            const unsigned long long now_ = clock64(); \
-            g_op_dbg[id] += now_ - prev;               \
-            prev = now_;                               \
-        }                                              \
-    } while (0)
-#define OP_MARK(id) OP_MARK_(op_dbg, op_prev, id)
-#define OP_MARK0(id) OP_MARK_(op_dbg0, op_prev0, id)
-extern "C" int mml_debug_op_timing(unsigned long long* out, int reset) {
-    if (reset) {
-        unsigned long long z[16] = {};
-        return hipMemcpyToSymbol(HIP_SYMBOL(g_op_dbg), z, sizeof(z)) == hipSuccess ? 0 : -1;
-    }
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_op_dbg), sizeof(unsigned long long) * 16) == hipSuccess ? 0 : -1;
-}
+#ifdef MML_OP_TIMING
+PHASE_CLOCK_FAMILY(op, 16);
+#define OP_WATCH(cond) (cond)
 #else
-#define OP_MARK(id)
-#define OP_MARK0(id)
+PHASE_CLOCK_FAMILY_OFF(op);
+#define OP_WATCH(cond) false
 #endif
 struct OnepassLds {
     int cnt[OP_GROUPS][OP_CSTRIDE];  // points per (group, line); after the scan: points of the line in the groups before
@@ -997,11 +982,8 @@ __device__ __forceinline__ void assign_onepass_body(const FeatParams& P, Onepass
     const int b = blockIdx.y + P.first, blk = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int i0 = blk * MML_OP_BLK;
-#ifdef MML_OP_TIMING
-    const bool op_dbg = SENSOR == 0 && tid == 64 && blk == MML_OP_TIMING && b == P.first + 517;
-    const bool op_dbg0 = SENSOR == 0 && tid == 0 && blk == MML_OP_TIMING && b == P.first + 517;
-    unsigned long long op_prev = clock64(), op_prev0 = op_prev;
-#endif
+    PhaseClock_op clk(OP_WATCH(SENSOR == 0 && tid == 64 && blk == MML_OP_TIMING && b == P.first + 517));
+    PhaseClock_op clk0(OP_WATCH(SENSOR == 0 && tid == 0 && blk == MML_OP_TIMING && b == P.first + 517));
     // ---- 1. the block's records, all loads in flight together ----
     // (requested before the slot's point count is known -- the index clamped to the slot's buffer, the count decides later which
     //  lanes hold a point: the block's first memory round trip is the records themselves, not the count in front of them)
@@ -1061,9 +1043,9 @@ __device__ __forceinline__ void assign_onepass_body(const FeatParams& P, Onepass
     struct {
         float startOri, endOri;
     } aux;
-    OP_MARK(0);
+    clk.mark(0);
     __syncthreads();  // (the counters are zero, the sweep's ends are known)
-    OP_MARK(1);
+    clk.mark(1);
     aux.startOri = S.ori[0];
     aux.endOri = S.ori[1];
     const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
@@ -1119,10 +1101,10 @@ __device__ __forceinline__ void assign_onepass_body(const FeatParams& P, Onepass
         //  wavefronts per SIMD)
         __builtin_amdgcn_sched_barrier(0);
     }
-    OP_MARK(2);
+    clk.mark(2);
     if (lane == 0) s_cond[wave] = cond_min;
     __syncthreads();
-    OP_MARK(3);
+    clk.mark(3);
     // ---- 2. per line: exclusive scan over the 64 groups (lane = group) ----
     const bool gl = lane < OP_GROUPS;
     for (int k = wave; k < nkeys; k += OP_WAVES) {
@@ -1140,12 +1122,12 @@ __device__ __forceinline__ void assign_onepass_body(const FeatParams& P, Onepass
         if (gl) s_gk[lane] = x - v;
         if (lane == 63) s_hist[nkeys + 1] = x;
     }
-    OP_MARK(4);
+    clk.mark(4);
     __syncthreads();
-    OP_MARK(5);
+    clk.mark(5);
     // ---- 3. offsets of the lines inside the block; publish; look back ----
     if (wave == 0) {
-        OP_MARK0(10);
+        clk0.mark(10);
         const int h = lane < nkeys ? s_hist[lane] : 0;
         const int koff = wave_incl_scan(h) - h;
         if (lane < nkeys) s_koff[lane] = koff;
@@ -1180,7 +1162,7 @@ __device__ __forceinline__ void assign_onepass_body(const FeatParams& P, Onepass
                 __builtin_amdgcn_s_sleep(1);
             }
         }
-        OP_MARK0(11);
+        clk0.mark(11);
         int pv = lane < blk ? (int)(w & 0x1fffu) : 0;
         int pk = lane < blk ? (int)((w >> 13) & 0x1fffu) : 0;
         int pc = 0x7fffffff;
@@ -1225,9 +1207,9 @@ __device__ __forceinline__ void assign_onepass_body(const FeatParams& P, Onepass
             rec[MAX_LINES + 1] = tk;
         }
     }
-    OP_MARK0(12);
+    clk0.mark(12);
     __syncthreads();
-    OP_MARK(6);
+    clk.mark(6);
     // ---- 4. the points leave ----
     const int base_valid = region + s_base[0], base_keep = s_base[1], trig = s_base[2];
     double timeSpan = 1.0;
@@ -1271,9 +1253,9 @@ __device__ __forceinline__ void assign_onepass_body(const FeatParams& P, Onepass
         s_out[1][q] = __float_as_int(rel);
         __builtin_amdgcn_sched_barrier(0);
     }
-    OP_MARK(7);
+    clk.mark(7);
     __syncthreads();
-    OP_MARK(8);
+    clk.mark(8);
     {
         const int tv = s_hist[nkeys];
         int* og = P.ln_gidx + (size_t)b * P.NT + base_valid;
@@ -1283,10 +1265,10 @@ __device__ __forceinline__ void assign_onepass_body(const FeatParams& P, Onepass
             orl[k] = s_out[1][k];
         }
     }
-#ifdef MML_OP_TIMING
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the stores have left the wavefront)
-    OP_MARK(9);
-#endif
+    if constexpr (clk.on) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the stores have left the wavefront)
+        clk.mark(9);
+    }
 }
 
 // one launch for both sensors (a handful of scans: one launch less in the chain): z = 0 the Velodyne blocks, z = 1 the Livox blocks,
@@ -1842,27 +1824,14 @@ constexpr WalkTab make_walk_tab() {
 }
 __device__ const WalkTab g_walk_tab = make_walk_tab();
 
-#ifdef MML_ST_TIMING
-// phase clocks of one k_stencil workgroup (line MML_ST_TIMING of the 8th slot of the launch): cycles spent up to each mark, summed
+// phase clocks of one k_stencil wavefront (line MML_ST_TIMING of the 518th slot of the launch): cycles spent up to each mark, summed
 // over the tiles of the line
-__device__ unsigned long long g_st_dbg[16];
-#define ST_MARK(id)                                                       \
-    do {                                                                  \
-        if (st_dbg) {                                                     \
-            const unsigned long long now_ = clock64();                    \
-            g_st_dbg[id] += now_ - st_prev;                               \
-            st_prev = now_;                                               \
-        }                                                                 \
-    } while (0)
-extern "C" int mml_debug_st_timing(unsigned long long* out, int reset) {
-    if (reset) {
-        unsigned long long z[16] = {};
-        return hipMemcpyToSymbol(HIP_SYMBOL(g_st_dbg), z, sizeof(z)) == hipSuccess ? 0 : -1;
-    }
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_st_dbg), sizeof(unsigned long long) * 16) == hipSuccess ? 0 : -1;
-}
+#ifdef MML_ST_TIMING
+PHASE_CLOCK_FAMILY(st, 16);
+#define ST_WATCH(cond) (cond)
 #else
-#define ST_MARK(id)
+PHASE_CLOCK_FAMILY_OFF(st);
+#define ST_WATCH(cond) false
 #endif
 
 // One WAVEFRONT per scan line (four lines per workgroup, nothing shared between them: no workgroup barrier anywhere), the line
@@ -1927,10 +1896,7 @@ __global__ __launch_bounds__(64 * ST_LINES) void k_stencil(FeatParams P) {
     float* s_sq = s_sq_all[wave_id];
     unsigned short* s_attr = s_attr_all[wave_id];
     unsigned short* s_list = reinterpret_cast<unsigned short*>(s_sq);  // (the segment lengths are dead once the rounds are done)
-#ifdef MML_ST_TIMING
-    const bool st_dbg = (threadIdx.x & 63) == 0 && line == MML_ST_TIMING && b == P.first + 517;
-    unsigned long long st_prev = clock64();
-#endif
+    PhaseClock_st clk(ST_WATCH((threadIdx.x & 63) == 0 && line == MML_ST_TIMING && b == P.first + 517));
     // Every phase of the tile loop derives its lane number and addresses from its own opaque copy of the thread index: the
     // compiler otherwise keeps the loop-invariant values of ALL phases in registers across the whole loop
 #define PHASE_IDS()                               \
@@ -1946,7 +1912,7 @@ __global__ __launch_bounds__(64 * ST_LINES) void k_stencil(FeatParams P) {
     const int t_first = MODE == 0 ? 0 : (int)blockIdx.x * ST_TILE, t_step = MODE == 0 ? ST_TILE : (int)gridDim.x * ST_TILE;
     for (int t0 = t_first; t0 < n; t0 += t_step) {
         WAVE_SYNC();  // the previous tile has been consumed
-        ST_MARK(0);
+        clk.mark(0);
         if constexpr (MODE == 2) {  // entry offset = the exits of the tiles before this one, composed
             unsigned c = 0;
             for (int u = 0; u < t0 / ST_TILE; ++u) c = 8u * ((tile_exit[u] >> (c >> 2)) & 3u);
@@ -2015,7 +1981,7 @@ __global__ __launch_bounds__(64 * ST_LINES) void k_stencil(FeatParams P) {
             }
         }
         WAVE_SYNC();
-        ST_MARK(1);
+        clk.mark(1);
         unsigned redo_bits = 0;
         unsigned long long rmask[4] = {0ull, 0ull, 0ull, 0ull};
         if constexpr (MODE != 2) {
@@ -2078,7 +2044,7 @@ __global__ __launch_bounds__(64 * ST_LINES) void k_stencil(FeatParams P) {
                 rmask[rep] = __ballot(attr & A_RFLAT);
             }
         }
-        ST_MARK(2);
+        clk.mark(2);
         // ---- the walk over this tile: lane (w, e), w < 4, = window w entered at offset e ----
         unsigned long long vmask[4] = {0ull, 0ull, 0ull, 0ull};
         {
@@ -2140,7 +2106,7 @@ __global__ __launch_bounds__(64 * ST_LINES) void k_stencil(FeatParams P) {
                 carry = e;
             }
         }
-        ST_MARK(3);
+        clk.mark(3);
         if constexpr (MODE == 1) {  // the attribute words as the rounds left them (launch 2 reads the flatness bits back)
             PHASE_IDS();
 #pragma unroll
@@ -2177,14 +2143,14 @@ __global__ __launch_bounds__(64 * ST_LINES) void k_stencil(FeatParams P) {
                     s_attr[tp] = (unsigned short)(s_attr[tp] | A_C150);
             }
             WAVE_SYNC();
-            ST_MARK(4);
+            clk.mark(4);
 #pragma unroll
             for (int rep = 0; rep < 4; ++rep) {
                 const int tp = rep * 64 + lane, i = t0 + tp;
                 if (i < n) P.ln_attr[base + i] = ((redo_bits >> rep) & 1u) ? (unsigned short)(s_attr[tp] & A_VIS) : s_attr[tp];
             }
         }
-        ST_MARK(5);
+        clk.mark(5);
     }
 #undef PHASE_IDS
 #undef WAVE_SYNC
@@ -2478,16 +2444,11 @@ __device__ __forceinline__ void load_nb_info(WP W, int i, unsigned (&o)[6]) {
 }
 
 #ifdef MML_SEL_TIMING
-__device__ unsigned long long g_sel_dbg[64];
-#define SEL_MARK(id)                                                                  \
-    do {                                                                              \
-        if (threadIdx.x == 0 && blockIdx.x == MML_SEL_TIMING && blockIdx.y == 517) g_sel_dbg[id] = clock64(); \
-    } while (0)
-extern "C" int mml_debug_sel_timing(unsigned long long* out) {
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sel_dbg), sizeof(unsigned long long) * 64) == hipSuccess ? 0 : -1;
-}
+PHASE_CLOCK_FAMILY(sel, 64);
+#define SEL_WATCH(cond) (cond)
 #else
-#define SEL_MARK(id)
+PHASE_CLOCK_FAMILY_OFF(sel);
+#define SEL_WATCH(cond) false
 #endif
 
 // phase 1: can neighbour slot Q suppress me?   phase 2: does picked neighbour Q mark me (before my visit / from a
@@ -2627,7 +2588,10 @@ __device__ __forceinline__ void select_body(const FeatParams& P, int b, int line
 #define ATTR(i, k) (CACHED ? r_attr[k] : (unsigned)attr[i])
 #define RKEY(i) (CACHED ? (unsigned)R[i] : refl_key(refl[i]))
 
-    SEL_MARK(0);
+    // (workgroup (MML_SEL_TIMING, 517) of the grid; stamps: its last pass through each mark, [20] its dependency rounds.  No launch
+    //  has such a workgroup any more -- list launches are one-dimensional, per-slot launches at most 16 slots tall: the slots read 0)
+    PhaseClock_sel clk(SEL_WATCH(threadIdx.x == 0 && blockIdx.x == MML_SEL_TIMING && blockIdx.y == 517));
+    clk.stamp(0);
     int T = 2;  // thNumCurvSize as the last stencil iteration (i = n-6) left it (:492,505)
     unsigned at_last = 0;
     if (n >= 11) at_last = attr[n - 6];
@@ -2660,7 +2624,7 @@ __device__ __forceinline__ void select_body(const FeatParams& P, int b, int line
     if (tid < 3) s_flag[tid] = 0;
     __syncthreads();
 
-    SEL_MARK(1);
+    clk.stamp(1);
     // ---- phase 0: per-point record --------------------------------------------------------------------------
     const float inv_r = range >= 1 ? 1.0f / (float)range : 0.f;
     FOR_POINTS(
@@ -2694,7 +2658,7 @@ __device__ __forceinline__ void select_body(const FeatParams& P, int b, int line
     }
     __syncthreads();
 
-    SEL_MARK(2);
+    clk.stamp(2);
     constexpr bool MASKED = CACHED && KK <= 8;  // (the two mask tables of the masked form fit the 2 KB of s_walk)
     if constexpr (MASKED) {
         // The dependency rounds on bit masks.  A wavefront owns, for each k, the 64 consecutive points i = tid + 512 k: one
@@ -2750,7 +2714,7 @@ __device__ __forceinline__ void select_body(const FeatParams& P, int b, int line
             }
         }
         __syncthreads();
-        SEL_MARK(3);
+        clk.stamp(3);
         int rnd = 0;
         // the 7-bit field [i - 3, i + 3] of a window mask M extended by the adjacent windows' edge bits
         auto field = [&](unsigned long long M, unsigned long long Ml, unsigned long long Mr) -> unsigned {
@@ -2794,9 +2758,7 @@ __device__ __forceinline__ void select_body(const FeatParams& P, int b, int line
                 }
                 pending |= U != 0;
             }
-#ifdef MML_SEL_TIMING
-            if (threadIdx.x == 0 && blockIdx.x == MML_SEL_TIMING && blockIdx.y == 517) g_sel_dbg[20] += 1;
-#endif
+            clk.count(20);
             // No workgroup barrier between passes: a wavefront with undecided windows only waits for edge bits of its
             // neighbours, which they publish as soon as they have them (LDS is coherent across the workgroup and the
             // dependencies form a DAG, so some window can always advance); it simply looks again.
@@ -2805,7 +2767,7 @@ __device__ __forceinline__ void select_body(const FeatParams& P, int b, int line
         }
         (void)rnd;
         __syncthreads();
-        SEL_MARK(4);
+        clk.stamp(4);
         // ---- phase 2: value held when :521-539 runs (f3a) + "a later partition marks me", from the final masks ---------
         // (a picked neighbour whose range covers me marks me 1 at its own, later visit -- it cannot have come first, or I
         //  would not be picked -- unless it sits in a later partition, whose marks land after :521-539 has read me)
@@ -2845,7 +2807,7 @@ __device__ __forceinline__ void select_body(const FeatParams& P, int b, int line
         W[2 * i + 1] = m ? (me | (m << I_MASK_SHIFT)) : ((me & ~I_ST_MASK) | (ST_S << I_ST_SHIFT));
     )
     __syncthreads();
-    SEL_MARK(3);
+    clk.stamp(3);
     unsigned pend = 0;  // cached form: which of my points are still undecided (skips the LDS read of the others)
     if constexpr (CACHED) {
 #pragma unroll
@@ -2908,9 +2870,7 @@ __device__ __forceinline__ void select_body(const FeatParams& P, int b, int line
             for (int i = tid; i < n; i += SELP_THREADS)
                 if (!decide(i)) undecided = 1;
         }
-#ifdef MML_SEL_TIMING
-        if (threadIdx.x == 0 && blockIdx.x == MML_SEL_TIMING && blockIdx.y == 517) g_sel_dbg[20] += 1;
-#endif
+        clk.count(20);
         // one barrier per round: any wavefront with an undecided point raises the round's flag (three slots, the one
         // two rounds ahead is cleared after the barrier, when nobody reads or writes it)
         if (__any(undecided) && lane == 0) s_flag[rnd % 3] = 1;
@@ -2921,7 +2881,7 @@ __device__ __forceinline__ void select_body(const FeatParams& P, int b, int line
         if (!again) break;
     }
 
-    SEL_MARK(4);
+    clk.stamp(4);
     // ---- phase 2: value held when :521-539 runs (f3a) + "a later partition marks me" ------------------------------
     FOR_POINTS(
         const uint2 rec = make_uint2(W[2 * i], W[2 * i + 1]);
@@ -2949,7 +2909,7 @@ __device__ __forceinline__ void select_body(const FeatParams& P, int b, int line
     __syncthreads();
     }
 
-    SEL_MARK(5);
+    clk.stamp(5);
     // ---- phase 3: :521-539 in closed form ---------------------------------------------------------------------------
     // (a) the three first reflect candidates in reflect order, per partition (rounds 2 and 3)
     for (int round = 1; round < 3; ++round) {
@@ -2963,7 +2923,7 @@ __device__ __forceinline__ void select_body(const FeatParams& P, int b, int line
         )
         __syncthreads();
     }
-    SEL_MARK(6);
+    clk.stamp(6);
     // (a2) + (b).  (a2): for each of the <= 3 reflect picks of a partition, does its reflect visit (B_k, k = reflect rank)
     //      come before its own curvature visit (A_k)?  Only read for a pick that holds flag 3 or is a grazing point.
     //      (b): eff3 / G bits, first point of each class in curvature order per partition.
@@ -3051,7 +3011,7 @@ __device__ __forceinline__ void select_body(const FeatParams& P, int b, int line
             if (lane == 0) s_bfirst[t] = (unsigned char)(rr < rc);
         }
         __syncthreads();
-        SEL_MARK(7);
+        clk.stamp(7);
         // (b) eff3 / G bits, first point of each class in curvature order per partition
         FOR_POINTS(
             const unsigned me = W[2 * i + 1];
@@ -3079,9 +3039,9 @@ __device__ __forceinline__ void select_body(const FeatParams& P, int b, int line
     }
     __syncthreads();  // R is dead from here on: the window tables of the cached form live in its storage
 
-    SEL_MARK(8);
+    clk.stamp(8);
     // (phase 4, the stride walk of :543-650, is resolved by k_stencil: attribute bit A_VIS)
-    SEL_MARK(10);
+    clk.stamp(10);
     // ---- phase 5: final value of the serial part (:521-539 (c)), overrides (150, 100/101), emit, label scatter ---------
     uint8_t* lnlab = P.ln_label + (size_t)b * P.NT;
     // (the labels this thread decides, 4 bits each, and where they went: appended to the slot's lists below -- label_append)
@@ -3149,7 +3109,7 @@ __device__ __forceinline__ void select_body(const FeatParams& P, int b, int line
             label_append<8>(P, b, line < P.n_rings, labs_arr[c], pp);
         }
     }
-    SEL_MARK(11);
+    clk.stamp(11);
 #undef FOR_POINTS
 #undef ATTR
 #undef RKEY
@@ -3234,24 +3194,11 @@ __global__ void k_select_list(FeatParams P, int count) {
 // into flags / labels with one point per lane.  Lines outside 161 <= n <= 3211 (a partition of fewer than 3 or more than 64
 // points) are left to k_select (per-line flag sel_done).
 #ifdef MML_SP_TIMING
-__device__ unsigned long long g_sp_dbg[16];
-#define SP_MARK(id)                                                       \
-    do {                                                                  \
-        if (sp_dbg) {                                                     \
-            const unsigned long long now_ = clock64();                    \
-            g_sp_dbg[id] += now_ - sp_prev;                               \
-            sp_prev = now_;                                               \
-        }                                                                 \
-    } while (0)
-extern "C" int mml_debug_sp_timing(unsigned long long* out, int reset) {
-    if (reset) {
-        unsigned long long z[16] = {};
-        return hipMemcpyToSymbol(HIP_SYMBOL(g_sp_dbg), z, sizeof(z)) == hipSuccess ? 0 : -1;
-    }
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sp_dbg), sizeof(unsigned long long) * 16) == hipSuccess ? 0 : -1;
-}
+PHASE_CLOCK_FAMILY(sp, 16);
+#define SP_WATCH(cond) (cond)
 #else
-#define SP_MARK(id)
+PHASE_CLOCK_FAMILY_OFF(sp);
+#define SP_WATCH(cond) false
 #endif
 typedef unsigned long long u64m;
 typedef unsigned __int128 u128m;
@@ -3298,10 +3245,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(size
     const float* refl = P.ln_refl + base;
     u64m(*pl)[MAXWIN] = s_plane_all[wave_id];
     const int nwin = (n + 63) >> 6;
-#ifdef MML_SP_TIMING
-    const bool sp_dbg = lane == 0 && line == MML_SP_TIMING && blockIdx.y == 517;
-    unsigned long long sp_prev = clock64();
-#endif
+    PhaseClock_sp clk(SP_WATCH(lane == 0 && line == MML_SP_TIMING && blockIdx.y == 517));
 #define SP_SYNC()                                          \
     do {                                                   \
         __builtin_amdgcn_wave_barrier();                   \
@@ -3364,7 +3308,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(size
         }
     }
     SP_SYNC();
-    SP_MARK(0);
+    clk.mark(0);
     // ---- phase B: one partition per lane ------------------------------------------------------------------------------------
     {
         const bool act = lane < 50;
@@ -3408,7 +3352,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(size
         const M Pp1 = Cw1 & ~(G1 >> 1) & C, Pp2 = Cw2 & ~(G2 >> 2) & C, Pp3 = Cw3 & ~(G3 >> 3) & C;
         const M has_pred = Pm1 | Pm2 | Pm3 | Pp1 | Pp2 | Pp3;
         M S = C & ~has_pred, U = C & has_pred;
-        SP_MARK(1);
+        clk.mark(1);
         // dependency steps: a partition's first three points wait for the last three of the partition before
         for (int guard = 0; guard < 4096; ++guard) {
             const unsigned e = (unsigned)((S >> (L - 3)) & (M)7) | ((unsigned)((U >> (L - 3)) & (M)7) << 3);
@@ -3424,7 +3368,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(size
             U &= ~(toN | toS);
             if (!__any((toN | toS) != (M)0)) break;
         }
-        SP_MARK(2);
+        clk.mark(2);
         // value held when :521-539 runs: 1 when a pick of the same or an earlier partition marks me (it cannot have come before
         // my own pick, or I would not be picked), else 3 for a pick; marks from the partition behind land after :521-539
         const unsigned e2 = (unsigned)((S >> (L - 3)) & (M)7) | ((unsigned)(S & (M)7) << 3);
@@ -3468,7 +3412,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(size
 #pragma unroll
             for (int r = 0; r < 3; ++r)
                 if (best[r] != ~0ull) inBm |= (M)1 << ((int)(unsigned)best[r] - sp);
-            SP_MARK(3);
+            clk.mark(3);
             // does a pick's reflect visit come before its own curvature visit?  (only read for a pick that holds 3 or is a
             // grazing point): ranks in both orders over the whole partition.  Counted with one POINT per lane: the picks of all
             // partitions are taken four at a time -- the owning lanes broadcast partition and pick, the lanes fetch that
@@ -3523,7 +3467,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(size
                 }
             }
         }
-        SP_MARK(4);
+        clk.mark(4);
         const M eff3 = is3 & ~(inBm & bfirst);
         const M Gm = AN | (eff3 & FR);
         M first = (M)0;
@@ -3550,7 +3494,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(size
             const u64m minE = min_key(eff3), minG = min_key(Gm);
             if (minE != ~0ull && !(minG < minE)) first = (M)1 << ((int)(unsigned)minE - sp);
         }
-        SP_MARK(5);
+        clk.mark(5);
         const M picked = Gm | first;
         const M two_after_300 = inBm & picked & AN & bfirst;
         const M F2 = ((picked & ~inBm) | two_after_300) & ~covLater;
@@ -3604,7 +3548,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(size
         }
     }
     SP_SYNC();
-    SP_MARK(6);
+    clk.mark(6);
     // ---- phase C: flags and labels, one point per lane -----------------------------------------------------------------
     // (labels and fused indices live at the points' STORAGE positions: translated through the line's segment table)
     uint8_t* lnlab = P.ln_label + (size_t)b * P.NT;
@@ -3672,7 +3616,7 @@ __global__ __launch_bounds__(64 * WAVES) __attribute__((amdgpu_waves_per_eu(size
         }
         label_append<8>(P, b, line < P.n_rings, labs, ps4, gi4);
     }
-    SP_MARK(7);
+    clk.mark(7);
 #undef SP_SYNC
 }
 // the two forms: partitions of up to 64 points (rings), up to 128 (Livox lines)

@@ -636,23 +636,11 @@ __device__ __forceinline__ void wide_sums(const double* s_rows, int vt, int ns, 
     }
 }
 
-#ifdef MML_SV_TIMING
-// phase clocks of eval_frame_wide, thread 0 of problem MML_SV_TIMING: rows, wait at the barrier, sums, tree; [4] passes
-__device__ unsigned long long g_svw_dbg[8];
-#define SVW_MARK(id)                                   \
-    do {                                               \
-        if (svw_dbg) {                                 \
-            const unsigned long long now_ = clock64(); \
-            g_svw_dbg[id] += now_ - svw_prev;          \
-            svw_prev = now_;                           \
-        }                                              \
-    } while (0)
-#else
-#define SVW_MARK(id)
-#endif
 // workgroup of WIDE_THREADS; s_rows: WIDE_ROW_LDS doubles, s_vsave: WIDE_SAVE_LDS, s_part: SOLVE_WAVES * 28; out[28] is valid for the FIRST WAVEFRONT on return
+// clk: the caller's phase clock (phase_clock.h; started at the call), slots rows, wait at the barrier, sums, tree; [4] passes
+template <class Clock>
 __device__ __forceinline__ void eval_frame_wide(const MmlLineFactor* lf, int nlf, const MmlPlaneFactor* pf, int npf, const Pose& P,
-                                                double huber_delta, double* s_rows, double* s_vsave, double* s_part, double* out) {
+                                                double huber_delta, double* s_rows, double* s_vsave, double* s_part, double* out, Clock clk) {
     // (the thread number is made opaque to the compiler at every call: as a known function of threadIdx.x every address below is formed
     //  once in front of the solve's loop and held across the trust-region code and the rows phase -- the registers for that are not
     //  there, and a spilled address is a memory round trip when it is needed; see k_solve_wide)
@@ -663,11 +651,7 @@ __device__ __forceinline__ void eval_frame_wide(const MmlLineFactor* lf, int nlf
     const int lane = tx & 63, wv = vt >> 6;
     const int SL = (nlf + SOLVE_THREADS - 1) / SOLVE_THREADS, SP = (npf + SOLVE_THREADS - 1) / SOLVE_THREADS, NS = SL + SP;
     const double ka = 1.0 / kLidarM;
-#ifdef MML_SV_TIMING
-    const bool svw_dbg = threadIdx.x == 0 && blockIdx.x == MML_SV_TIMING;
-    unsigned long long svw_prev = clock64();
-    if (svw_dbg) g_svw_dbg[4] += 1;
-#endif
+    clk.count(4);
     for (int s0 = 0; s0 < NS; s0 += WIDE_ROUND) {
         // ---- rows: slots s0 + sub, + 4, + 8 of this round ----
         const int sA = s0 + sub, sB = sA + WIDE_SUBS, sC = sB + WIDE_SUBS;
@@ -722,9 +706,9 @@ __device__ __forceinline__ void eval_frame_wide(const MmlLineFactor* lf, int nlf
                 }
             }
         }
-        SVW_MARK(0);
+        clk.mark(0);
         __syncthreads();
-        SVW_MARK(1);
+        clk.mark(1);
         // ---- sums: the summing sub-threads' chains over the round's rows, in slot order; behind the last round the tree ----
         // (the sums live in registers only from here to the end of the round: a scan with more than WIDE_ROUND slots per thread parks
         //  them in LDS between its rounds -- held across the rows phase they cost it the registers it needs)
@@ -747,7 +731,7 @@ __device__ __forceinline__ void eval_frame_wide(const MmlLineFactor* lf, int nlf
                 wide_sums<2>(s_rows, vt, ns, v);
             else
                 wide_sums<3>(s_rows, vt, ns, v);
-            SVW_MARK(2);
+            clk.mark(2);
             if (!last) {
 #pragma unroll
                 for (int k = 0; k < 8; ++k) sv[(size_t)k * WIDE_THREADS] = v[k];
@@ -791,7 +775,7 @@ __device__ __forceinline__ void eval_frame_wide(const MmlLineFactor* lf, int nlf
     }
     // (no barrier behind this: out[] is read by the first wavefront, which has just written it -- k_solve_wide's trust-region code --
     //  and everybody else meets that wavefront at the caller's next barrier before s_rows / s_part are written again)
-    SVW_MARK(3);
+    clk.mark(3);
 }
 
 __host__ __device__ __forceinline__ int tri(int a, int b) {  // index into 21-entry upper triangle, a <= b

@@ -10,6 +10,7 @@
 
 #include "lidar_eval.h"
 #include "mml_internal.h"
+#include "phase_clock.h"
 
 namespace {
 
@@ -209,46 +210,17 @@ __host__ __device__ inline __attribute__((always_inline)) void tr_propose(TRStat
         __builtin_amdgcn_wave_barrier(); \
         asm volatile("" ::: "memory");   \
     } while (0)
+// phase clocks of the solve, problem MML_SV_TIMING of every launch, summed over the iterations and launches (tools/phases.py sv, svw):
+// sv [0..4] the phases of one k_solve / k_solve_wide workgroup (thread 0), [7] launches of k_solve, [8..12] inside tr_propose_w1_wave;
+// svw [0..3] eval_frame_wide's rows, wait at the barrier, sums, tree, [4] its passes, [5] k_solve_wide's cycles, [6] its launches
 #ifdef MML_SV_TIMING
-// phase clocks of one k_solve workgroup (problem MML_SV_TIMING of every launch): cycles per phase, summed over the iterations and
-// launches; [7] counts the launches
-__device__ unsigned long long g_sv_dbg[16];
-#define SV_MARK(id)                                    \
-    do {                                               \
-        if (sv_dbg) {                                  \
-            const unsigned long long now_ = clock64(); \
-            g_sv_dbg[id] += now_ - sv_prev;            \
-            sv_prev = now_;                            \
-        }                                              \
-    } while (0)
-extern "C" int mml_debug_sv_timing(unsigned long long* out, int reset) {
-    if (reset) {
-        unsigned long long z[16] = {};
-        return hipMemcpyToSymbol(HIP_SYMBOL(g_sv_dbg), z, sizeof(z)) == hipSuccess ? 0 : -1;
-    }
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sv_dbg), sizeof(unsigned long long) * 16) == hipSuccess ? 0 : -1;
-}
-extern "C" int mml_debug_svw_timing(unsigned long long* out, int reset) {
-    if (reset) {
-        unsigned long long z[8] = {};
-        return hipMemcpyToSymbol(HIP_SYMBOL(g_svw_dbg), z, sizeof(z)) == hipSuccess ? 0 : -1;
-    }
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_svw_dbg), sizeof(unsigned long long) * 8) == hipSuccess ? 0 : -1;
-}
+PHASE_CLOCK_FAMILY(sv, 16);
+PHASE_CLOCK_FAMILY(svw, 8);
+#define SV_WATCH(cond) (cond)
 #else
-#define SV_MARK(id)
-#endif
-#ifdef MML_SV_TIMING
-#define PV_MARK(id)                                                         \
-    do {                                                                    \
-        if (threadIdx.x == 0 && blockIdx.x == MML_SV_TIMING) {              \
-            const unsigned long long now_ = clock64();                      \
-            g_sv_dbg[id] += now_ - pv_prev;                                 \
-            pv_prev = now_;                                                 \
-        }                                                                   \
-    } while (0)
-#else
-#define PV_MARK(id)
+PHASE_CLOCK_FAMILY_OFF(sv);
+PHASE_CLOCK_FAMILY_OFF(svw);
+#define SV_WATCH(cond) false
 #endif
 // (forced inline, as tr_propose and tr_decide_wave: with two instantiations of k_solve calling them the compiler made them real
 //  functions -- a call inside the iteration loop of a kernel with 256 live registers: the batch solve 0.251 -> 0.28 ms per 1024 problems)
@@ -262,9 +234,7 @@ __device__ __forceinline__ void tr_propose_w1_wave(TRState& S, double* w, int ma
     double* fl = w + 90;   // 2 flags
     const int iter = S.iter, num_invalid = S.num_invalid, reuse = S.reuse;
     const double radius = S.radius;
-#ifdef MML_SV_TIMING
-    unsigned long long pv_prev = clock64();
-#endif
+    PhaseClock_sv clk(SV_WATCH(threadIdx.x == 0 && blockIdx.x == MML_SV_TIMING));
     WSYNC();
     if (lane == 0) S.evaluate = 0;
     if (iter >= max_iters || radius < 1e-32) {
@@ -297,7 +267,7 @@ __device__ __forceinline__ void tr_propose_w1_wave(TRState& S, double* w, int ma
             for (int k = 0; k < 36; ++k) q += T[k];
             S.alpha = gg / q;
         }
-        PV_MARK(8);  // diag / gradient / alpha
+        clk.mark(8);  // diag / gradient / alpha
         double mu = S.mu;
         solve_ok = false;
         while (mu < 1.0) {
@@ -325,7 +295,7 @@ __device__ __forceinline__ void tr_propose_w1_wave(TRState& S, double* w, int ma
                 }
                 WSYNC();
             }
-            PV_MARK(9);  // Cholesky
+            clk.mark(9);  // Cholesky
             if (ok) {
                 if (lane == 0) {
                     for (int i = 0; i < 6; ++i) {
@@ -356,7 +326,7 @@ __device__ __forceinline__ void tr_propose_w1_wave(TRState& S, double* w, int ma
         if (lane == 0) S.mu = mu;
         if (solve_ok && in6) S.gn[lane] = bv[lane] * -S.diag[lane];
         WSYNC();
-        PV_MARK(10);  // substitutions
+        clk.mark(10);  // substitutions
     }
     bool step_valid = solve_ok;
     if (solve_ok) {
@@ -397,7 +367,7 @@ __device__ __forceinline__ void tr_propose_w1_wave(TRState& S, double* w, int ma
             }
         }
         WSYNC();
-        PV_MARK(11);  // dogleg
+        clk.mark(11);  // dogleg
         if (in36) T[lane] = st[a] * mab * st[b];
         WSYNC();
         if (lane == 0) {
@@ -410,7 +380,7 @@ __device__ __forceinline__ void tr_propose_w1_wave(TRState& S, double* w, int ma
         }
         WSYNC();
         step_valid = fl[0] != 0.0;
-        PV_MARK(12);  // model change
+        clk.mark(12);  // model change
     }
     if (!step_valid) {
         if (lane == 0) {
@@ -1063,11 +1033,8 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(SolveParams P) {
     const int W = P.window;
     const int b0 = P.first + prob * W;
     const int tid = threadIdx.x;
-#ifdef MML_SV_TIMING
-    const bool sv_dbg = tid == 0 && prob == MML_SV_TIMING;
-    unsigned long long sv_prev = clock64();
-    if (sv_dbg) g_sv_dbg[7] += 1;
-#endif
+    PhaseClock_sv clk(SV_WATCH(tid == 0 && prob == MML_SV_TIMING));
+    clk.count(7);
     if constexpr (SMALL) {
         if (tid < 6 * W) S.x[tid] = S.x_init[tid] = P.x_in ? P.x_in[(size_t)prob * 6 * W + tid] : P.x[(size_t)b0 * 6 + tid];
     } else {
@@ -1124,7 +1091,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(SolveParams P) {
 
     int go = S.go;
     __syncthreads();
-    SV_MARK(0);  // set-up + initial evaluation
+    clk.mark(0);  // set-up + initial evaluation
     while (go) {
         // lane 0 owns the trust-region state between the barriers; every other lane only reads it after one
         // lane 0 (first wavefront for W = 1) owns the trust-region state between the barriers
@@ -1134,7 +1101,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(SolveParams P) {
             tr_propose(S, W, P.max_iters);
         }
         __syncthreads();
-        SV_MARK(1);  // trust-region proposal (first wavefront) + barrier
+        clk.mark(1);  // trust-region proposal (first wavefront) + barrier
         go = S.go;
         const int ev = S.evaluate;
         if (!go) break;
@@ -1147,14 +1114,14 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(SolveParams P) {
                     eval_frame_pairs(P.lf + (size_t)b * P.MF, P.ft_n[b], P.pf + (size_t)b * P.MF, P.ft_n[P.B + b], pose, P.huber, acc);
                 else
                     eval_frame(P.lf + (size_t)b * P.MF, P.ft_n[b], P.pf + (size_t)b * P.MF, P.ft_n[P.B + b], pose, P.w_tan, P.huber, acc);
-                SV_MARK(2);  // factor pass of this thread
+                clk.mark(2);  // factor pass of this thread
                 block_reduce28(acc, s_part, S.recc + 28 * f);
-                SV_MARK(3);  // block reduction (waits for the slowest wavefront's factor pass)
+                clk.mark(3);  // block reduction (waits for the slowest wavefront's factor pass)
             }
             if (tid < 64) tr_decide_wave(S, s_wd, W, P.fixed);
         }
         __syncthreads();
-        SV_MARK(4);  // accept / reject (first wavefront) + barrier
+        clk.mark(4);  // accept / reject (first wavefront) + barrier
         go = S.go;
         if (P.trace && tid < 6 * W) P.trace[((size_t)prob * P.max_iters + (S.iter - 1)) * 6 * W + tid] = S.x[tid];
         __syncthreads();
@@ -1196,11 +1163,8 @@ __global__ __launch_bounds__(WIDE_THREADS) void k_solve_wide(SolveParams P) {
     const int prob = blockIdx.x;
     const int b0 = P.first + prob;
     const int tid = threadIdx.x;
-#ifdef MML_SV_TIMING
-    const unsigned long long svk_t0 = clock64();
-    const bool sv_dbg = tid == 0 && prob == MML_SV_TIMING;
-    unsigned long long sv_prev = svk_t0;
-#endif
+    PhaseClock_svw whole(SV_WATCH(tid == 0 && prob == MML_SV_TIMING));  // (the kernel from end to end)
+    PhaseClock_sv clk(SV_WATCH(tid == 0 && prob == MML_SV_TIMING));
     if (tid < 6) S.x[tid] = S.x_init[tid] = P.x_in ? P.x_in[(size_t)prob * 6 + tid] : P.x[(size_t)b0 * 6 + tid];
     __syncthreads();
     const MmlLineFactor* lf = P.lf + (size_t)b0 * P.MF;
@@ -1209,7 +1173,8 @@ __global__ __launch_bounds__(WIDE_THREADS) void k_solve_wide(SolveParams P) {
     {
         Pose pose;
         make_pose(S.x, P.Tbl, pose);
-        eval_frame_wide(lf, nlf, pf, npf, pose, P.huber, s_rows, s_vsave, s_part, S.rec);
+        eval_frame_wide(lf, nlf, pf, npf, pose, P.huber, s_rows, s_vsave, s_part, S.rec,
+                        PhaseClock_svw(SV_WATCH(tid == 0 && prob == MML_SV_TIMING)));
     }
     if (tid == 0) {
         S.cost = 0;
@@ -1250,23 +1215,24 @@ __global__ __launch_bounds__(WIDE_THREADS) void k_solve_wide(SolveParams P) {
         //  wavefront everybody waits for: +35 k cycles per solve)
         int lane_op = tid;
         asm volatile("" : "+v"(lane_op));
-        SV_MARK(0);  // (everything outside the two trust-region phases: set-up, factor passes, the loop's barriers)
+        clk.mark(0);  // (everything outside the two trust-region phases: set-up, factor passes, the loop's barriers)
         if (tid < 64) tr_propose_w1_regs(S, s_work, P.max_iters, lane_op);
         __syncthreads();
-        SV_MARK(1);  // trust-region proposal (first wavefront) + barrier
+        clk.mark(1);  // trust-region proposal (first wavefront) + barrier
         go = S.go;
         const int ev = S.evaluate;
         if (!go) break;
         if (ev) {
             Pose pose;
             make_pose(S.xc, P.Tbl, pose);
-            eval_frame_wide(lf, nlf, pf, npf, pose, P.huber, s_rows, s_vsave, s_part, S.recc);
+            eval_frame_wide(lf, nlf, pf, npf, pose, P.huber, s_rows, s_vsave, s_part, S.recc,
+                            PhaseClock_svw(SV_WATCH(tid == 0 && prob == MML_SV_TIMING)));
             asm volatile("" : "+v"(lane_op));
-            SV_MARK(0);
+            clk.mark(0);
             if (tid < 64) tr_decide_w1_regs(S, P.fixed, lane_op);
         }
         __syncthreads();
-        SV_MARK(4);  // accept / reject (first wavefront) + barrier
+        clk.mark(4);  // accept / reject (first wavefront) + barrier
         go = S.go;
         if (P.trace && tid < 6) P.trace[((size_t)prob * P.max_iters + (S.iter - 1)) * 6 + tid] = S.x[tid];
         __syncthreads();
@@ -1288,12 +1254,8 @@ __global__ __launch_bounds__(WIDE_THREADS) void k_solve_wide(SolveParams P) {
         o[3] = S.cost;
         o[4] = S.termination;
         o[5] = 0;  // (finished: see k_window_export)
-#ifdef MML_SV_TIMING
-        if (prob == MML_SV_TIMING) {
-            g_svw_dbg[5] += clock64() - svk_t0;
-            g_svw_dbg[6] += 1;
-        }
-#endif
+        whole.mark(5);
+        whole.count(6);
     }
 }
 

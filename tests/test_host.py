@@ -59,6 +59,22 @@ def test_no_device_is_a_loud_error(M, has_gpu):
     assert e.value.code == M.MML_ERR_NO_DEVICE
 
 
+def test_phase_clock_reader_of_a_default_build(M):
+    # The shipped library carries no phase clocks (csrc/phase_clock.h): the reader knows the seven families by name, says of each that
+    # it was not built in, and says so -- as for a name that is no family -- before any HIP call and without touching out.
+    families = ["op", "st", "sel", "sp", "vx", "sv", "svw"]
+    assert M.PHASE_CLOCKS_UNKNOWN < 0 and M.PHASE_CLOCKS_NOT_BUILT < 0 and M.PHASE_CLOCKS_UNKNOWN != M.PHASE_CLOCKS_NOT_BUILT
+    out = (C.c_ulonglong * 64)(*range(1000, 1064))
+    for fam in families:
+        for reset in (False, True):
+            assert M.phase_clocks(fam, out, reset) == M.PHASE_CLOCKS_NOT_BUILT, fam
+    for name in ("", "fw", "OP", "svww", "o"):
+        for reset in (False, True):
+            assert M.phase_clocks(name, out, reset) == M.PHASE_CLOCKS_UNKNOWN, name
+    assert M.lib().mml_debug_phase_clocks(None, out, 64, 0) == M.PHASE_CLOCKS_UNKNOWN
+    assert list(out) == list(range(1000, 1064))
+
+
 def test_cpp_adapter_compiles_links_and_runs_host_side(M, tmp_path):
     """multi-modal-loam_amd/host/mmloam_adapter.hpp (the reference-language mirror of feature_extraction / Estimator)
     builds against include/mmloam_hip.h and the shared library; the IMU pre-integration it forwards to needs no
