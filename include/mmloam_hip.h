@@ -1149,6 +1149,48 @@ int mml_pose_ingest_batch(mml_ctx* ctx, int first_slot, int count, const uint8_t
                           const mml_imu_interval* rows /* count or NULL */, const mml_pose_ingest_opts* opts,
                           mml_pose_ingest_row* out /* count */);
 
+/* ---- the feature node's way in: `count` union_cloud messages in wire form into scan slots in one call ------------------------
+ * mml_scan_upload_wire for `count` messages at once (a feature node in a process of its own, a bag reader that replays recorded
+ * aligner output).  Frame i goes to slot first_slot + i.
+ *   Velodyne part  frame i is n_velo[i] records of point_step bytes from byte velo_at[i] of velo_data; point_step and the field
+ *                  offsets are shared by the call and mean what they mean for mml_scan_upload_pointcloud2, with its limits
+ *                  (12 <= point_step <= 256, every field inside the record, off_intensity < 0: intensity 0).
+ *   Livox part     frame i is n_livox[i] records of livox_record_bytes from byte livox_at[i] of livox_data: 19 = the wire form of
+ *                  mml_scan_upload_wire (_pad is written as 0), 20 = mml_livox_point as it stands, pad byte included, as
+ *                  mml_scan_upload copies it.
+ * A sensor's offsets never decrease and its payloads never overlap: frame i starts at or behind the last byte of frame i - 1 (an
+ * empty frame's offset counts).  GAPS ARE ALLOWED, so the offsets can point into one mapped bag chunk with the message headers
+ * between the payloads.  Per sensor the call copies ONE span, from the first payload's first byte to the last payload's last
+ * byte: the gaps travel too, and a caller whose payloads are far apart pays for the bytes between them.  Either part of any
+ * frame may be empty; a sensor without any point may pass NULL for its data pointer (and for its offsets).
+ * Afterwards every slot is exactly what mml_scan_upload_wire (19) / mml_scan_upload_pointcloud2 (20) leaves on that frame alone:
+ * the rows of the raw buffers, the counts on the device and on the host, and the slot counts as not extracted.
+ * Asynchronous on the context's stream like the single calls, and the host buffers must stay valid until the next synchronising
+ * call.  Work per call, whatever `count` is: at most two payload copies, one table copy (32 bytes per frame), ONE launch of the
+ * decode kernel over (sensor, frame, tile of 256 points), one copy of the counts.  No host synchronisation (the staging buffer grows to the
+ * largest call, and a growth waits for the stream, as for the single calls).
+ * Everything is checked before anything is enqueued; a refusal names the frame in mml_last_error and changes nothing, on the host
+ * or on the device: MML_ERR_INVALID for a slot range outside the context, count < 1 or above 65535, NULL count arrays, a bad
+ * point_step / field offset / livox_record_bytes, a negative count or offset, an offset before the end of the frame before it,
+ * NULL data or offsets with points announced; MML_ERR_CAPACITY for a frame above max_velo_points / max_livox_points. */
+int mml_scan_upload_wire_batch(mml_ctx* ctx, int first_slot, int count, const uint8_t* velo_data, const int64_t* velo_at,
+                               const int* n_velo, int point_step, int off_x, int off_y, int off_z, int off_intensity,
+                               const uint8_t* livox_data, const int64_t* livox_at, const int* n_livox, int livox_record_bytes);
+/* Host only, no context: the argument rules of the call above (csrc/wire_decode.h, the routine the device call runs), with the
+ * capacities given by the caller (negative: not checked).  MML_OK: span = the bytes the call would copy, as half-open ranges --
+ * span[0] the Velodyne span's first byte, span[1] one past its last byte, span[2] / span[3] the same for the Livox span; 0, 0 for
+ * a sensor without points.  Otherwise span is untouched.  *bad_frame (may be NULL): the frame a refusal is about, -1 when it is
+ * about the call as a whole or there is none. */
+int mml_scan_upload_wire_plan(int count, const int64_t* velo_at, const int* n_velo, int point_step, int off_x, int off_y, int off_z,
+                              int off_intensity, const int64_t* livox_at, const int* n_livox, int livox_record_bytes,
+                              int max_velo_points, int max_livox_points, int64_t span[4], int* bad_frame);
+/* The decode itself on the host, for callers without a device: the same arguments and rules (no capacity), frame i's Velodyne
+ * points as x, y, z, intensity from row sum(n_velo[0 .. i)) of velo_xyzi, its Livox points from row sum(n_livox[0 .. i)) of
+ * livox.  Bit patterns are moved, never computed with. */
+int mml_wire_decode_host(int count, const uint8_t* velo_data, const int64_t* velo_at, const int* n_velo, int point_step, int off_x,
+                         int off_y, int off_z, int off_intensity, const uint8_t* livox_data, const int64_t* livox_at,
+                         const int* n_livox, int livox_record_bytes, float* velo_xyzi, mml_livox_point* livox);
+
 /* Number of HIP streams mml_step pipelines its sub-batches over (1..8, default 2 or $MML_LANES).  With 1 every
  * kernel covers the whole batch and runs alone on the device, which is what per-kernel timing wants. */
 int mml_set_lanes(mml_ctx* ctx, int lanes);

@@ -381,6 +381,14 @@ def lib():
             L.mml_pose_ingest_plan.argtypes = [C.c_int] + [C.c_void_p] * 4
             L.mml_pose_ingest_batch.restype = C.c_int
             L.mml_pose_ingest_batch.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
+        if hasattr(L, "mml_scan_upload_wire_batch"):
+            wire = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_int]   # offsets, counts, layout; twice
+            L.mml_scan_upload_wire_plan.restype = C.c_int
+            L.mml_scan_upload_wire_plan.argtypes = [C.c_int] + wire + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+            L.mml_wire_decode_host.restype = C.c_int
+            L.mml_wire_decode_host.argtypes = [C.c_int, C.c_void_p] + wire[:7] + [C.c_void_p] + wire[7:] + [C.c_void_p, C.c_void_p]
+            L.mml_scan_upload_wire_batch.restype = C.c_int
+            L.mml_scan_upload_wire_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p] + wire[:7] + [C.c_void_p] + wire[7:]
         _lib = L
     return _lib
 
@@ -785,6 +793,23 @@ class Context:
                                             C.c_int(off_x), C.c_int(off_y), C.c_int(off_z), C.c_int(off_intensity),
                                             _p(lw) if n_livox else None, C.c_int(n_livox)))
         self.synchronize()
+
+    def scan_upload_wire_batch(self, first_slot, velo_data, velo_at, n_velo, point_step, offs, livox_data, livox_at, n_livox,
+                               livox_record_bytes=19):
+        """mml_scan_upload_wire_batch: len(n_velo) union_cloud messages in wire form into slots first_slot .. in ONE call.  Frame i
+        is n_velo[i] records of point_step bytes from byte velo_at[i] of velo_data (offs = the byte offsets of x, y, z, intensity,
+        the last negative for none) and n_livox[i] records of livox_record_bytes (19: wire form, 20: LIVOX_DTYPE) from byte
+        livox_at[i] of livox_data; gaps between the payloads are allowed and travel with them.  A sensor without points may be
+        None.  Asynchronous: nothing is synchronised here, the buffers are kept alive by the context."""
+        a = wire_batch_pack(velo_data, velo_at, n_velo, point_step, offs, livox_data, livox_at, n_livox, livox_record_bytes)
+        self._keep = getattr(self, "_keep", [])
+        self._keep.append(a)
+        if len(self._keep) > 4 * self.cfg.max_scans + 8:
+            self.synchronize()  # the copies are asynchronous: nothing may be released while one is still in flight
+            self._keep = self._keep[-8:]
+        vd, va, nv, ld, la, nl, lay = a
+        self._ck(lib().mml_scan_upload_wire_batch(self._h, C.c_int(first_slot), C.c_int(len(nv)), _p(vd), _p(va), _p(nv), *lay[:5], _p(ld), _p(la),
+                                                  _p(nl), lay[5]))
 
     def time_offset_search(self, velo_xyz, livox_xyz, search_resolution=30, sliced_points=12000, tf=None):
         """estimate_timeoffset's numeric core (unionLidarsAligner.cpp:1077-1153): per-point 1-NN squared distances and
@@ -1400,6 +1425,61 @@ class Context:
         g = C.c_double(0)
         self._ck(lib().mml_copy_bandwidth(self._h, C.c_size_t(nbytes), C.c_int(reps), C.byref(g)))
         return g.value
+
+
+WIRE_BATCH_MAX = 65535      # MML_WIRE_BATCH_MAX (csrc/wire_decode.h): frames per call of mml_scan_upload_wire_batch
+
+
+WIRE_TILE_POINTS = 256      # records one workgroup of k_wire_decode_batch takes (csrc/wire_ingest.hip WB_THREADS)
+
+
+def wire_batch_pack(velo_data, velo_at, n_velo, point_step, offs, livox_data, livox_at, n_livox, livox_record_bytes=19):
+    """The arguments of the wire-batch calls as contiguous arrays: (velo bytes or None, velo_at int64 or None, n_velo int32, livox
+    bytes or None, livox_at or None, n_livox, (point_step, off_x, off_y, off_z, off_intensity, livox_record_bytes)).  A buffer is
+    only checked to reach the last byte its frames announce; every other rule is the library's."""
+    def part(data, at, n, rec, m):
+        n = np.zeros(m, np.int32) if n is None else np.ascontiguousarray(n, dtype=np.int32).reshape(-1)
+        at = None if at is None else np.ascontiguousarray(at, dtype=np.int64).reshape(-1)
+        if at is not None and len(at) != len(n):
+            raise ValueError("%d offsets for %d counts" % (len(at), len(n)))
+        if data is not None:
+            data = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+            if at is not None and len(n) and (n >= 0).all() and (at >= 0).all() and int((at + n.astype(np.int64) * rec)[n > 0].max(initial=0)) > len(data):
+                raise ValueError("a payload ends behind the %d bytes of its buffer" % len(data))
+            if not len(data):
+                data = None
+        return data, at, n
+    m = len(n_velo) if n_velo is not None else len(n_livox)
+    vd, va, nv = part(velo_data, velo_at, n_velo, int(point_step), m)
+    ld, la, nl = part(livox_data, livox_at, n_livox, int(livox_record_bytes), m)
+    if len(nv) != len(nl):
+        raise ValueError("%d Velodyne counts for %d Livox counts" % (len(nv), len(nl)))
+    ox, oy, oz, oi = (int(o) for o in offs)
+    return vd, va, nv, ld, la, nl, (int(point_step), ox, oy, oz, oi, int(livox_record_bytes))
+
+
+def scan_upload_wire_plan(velo_at, n_velo, point_step, offs, livox_at, n_livox, livox_record_bytes=19, max_velo_points=-1,
+                          max_livox_points=-1):
+    """mml_scan_upload_wire_plan: the argument rules of Context.scan_upload_wire_batch alone, on the host.  Returns (rc, span,
+    bad_frame): span = [velo first byte, one past velo last byte, livox first, one past livox last] (int64; zeros on a refusal),
+    bad_frame = the frame a refusal is about or -1.  A negative capacity is not checked."""
+    _, va, nv, _, la, nl, lay = wire_batch_pack(None, velo_at, n_velo, point_step, offs, None, livox_at, n_livox, livox_record_bytes)
+    span, bad = np.zeros(4, np.int64), C.c_int(-1)
+    rc = lib().mml_scan_upload_wire_plan(C.c_int(len(nv)), _p(va), _p(nv), *lay[:5], _p(la), _p(nl), lay[5], C.c_int(max_velo_points),
+                                         C.c_int(max_livox_points), _p(span), C.byref(bad))
+    return rc, span, bad.value
+
+
+def wire_decode_host(velo_data, velo_at, n_velo, point_step, offs, livox_data, livox_at, n_livox, livox_record_bytes=19):
+    """mml_wire_decode_host: the decode of Context.scan_upload_wire_batch on the host.  Returns (velo (sum n_velo, 4) float32, livox
+    (sum n_livox,) LIVOX_DTYPE), frame after frame."""
+    vd, va, nv, ld, la, nl, lay = wire_batch_pack(velo_data, velo_at, n_velo, point_step, offs, livox_data, livox_at, n_livox, livox_record_bytes)
+    tv, tl = int(np.maximum(nv, 0).sum()), int(np.maximum(nl, 0).sum())
+    v, l = np.zeros((max(tv, 1), 4), np.float32), np.zeros(max(tl, 1), LIVOX_DTYPE)
+    rc = lib().mml_wire_decode_host(C.c_int(len(nv)), _p(vd), _p(va), _p(nv), *lay[:5], _p(ld), _p(la), _p(nl), lay[5], _p(v), _p(l))
+    if rc != MML_OK:
+        raise MmlError(rc, "mml_wire_decode_host")
+    return v[:tv], l[:tl]
 
 
 def pose_ingest_opts(**over):

@@ -226,6 +226,25 @@ class feature_extraction {
         }
     }
 
+    // The way in of unionCloudHandler (:266-293) for `count` union_cloud messages held as raw bytes (a bag reader, a feature node
+    // in a process of its own): pcl::fromROSMsg (:1119-1121) and the CustomPoint field reads (:985-997) for all of them in ONE
+    // mml_scan_upload_wire_batch, then one mml_extract over the slots.  Frame i's velo_time_aligned payload is n_velo[i] records
+    // of point_step bytes at velo_data + velo_at[i] (field offsets as in msg.fields), its livox_time_aligned.points n_livox[i]
+    // serialised records of livox_record_bytes (19, or 20 for in-memory structs) at livox_data + livox_at[i]; the offsets may
+    // point into one mapped chunk with the message headers between the payloads.  infos (may be null): the frames' counters.
+    void unionCloudWire(int first_slot, int count, const uint8_t* velo_data, const int64_t* velo_at, const int* n_velo, int point_step,
+                        int off_x, int off_y, int off_z, int off_intensity, const uint8_t* livox_data, const int64_t* livox_at,
+                        const int* n_livox, int livox_record_bytes = 19, const float* livox_extrinsic = nullptr,
+                        std::vector<mml_scan_info>* infos = nullptr) {
+        mml_ctx* c = ctx_.get();
+        check(c, mml_scan_upload_wire_batch(c, first_slot, count, velo_data, velo_at, n_velo, point_step, off_x, off_y, off_z, off_intensity,
+                                            livox_data, livox_at, n_livox, livox_record_bytes), "mml_scan_upload_wire_batch");
+        check(c, mml_extract(c, first_slot, count, livox_extrinsic), "extract");
+        if (!infos) return;
+        infos->resize(count);
+        for (int i = 0; i < count; ++i) check(c, mml_scan_info_get(c, first_slot + i, &(*infos)[i]), "scan_info");
+    }
+
     // upload + extract without an extrinsic + counters: the slot is left for the download the caller chooses
     void extractOnly(const float* velo_xyzi, int n_velo, const mml_livox_point* livox, int n_livox, mml_scan_info& info, int slot) {
         mml_ctx* c = ctx_.get();
