@@ -351,6 +351,158 @@ __device__ __forceinline__ void eval_frame_pairs(const MmlLineFactor* lf, int nl
     }
 }
 
+// ---- the same evaluation for the batch launches of one-frame problems with one-row plane factors (k_solve_batch1) ----------------
+// eval_frame compiled for the general problem keeps its kernel at 256 registers, two wavefronts per SIMD: four problems per CU.  This
+// form is held to 168 registers -- three wavefronts, six problems per CU (what that buys, measured: solve.hip k_solve_batch1) -- by
+// taking out of the vector registers what does not belong there:
+//   pose:   the 24 doubles of a Pose are the same in every lane.  R and t arrive here as UNIFORM values (pose_uniform: read from LDS,
+//           where one wavefront left them, and passed through v_readfirstlane), live in scalar registers and enter every FMA as its
+//           one scalar operand; t_wb and J_l are read from the LDS copy where row_jacobian uses them (pose_at_use) -- 48 vector
+//           registers less across the factor loops;
+//   rows:   a plane factor is one residual row (plan_weight_tan = 0, W = 1): plane_row's straight-line code, no tangent basis;
+//   lines:  what a pass does not change about a thread's first line factor -- the record, 1 / |p1 - p2| and the validity test -- is
+//           formed once per solve (line_fixed) and kept across the passes;
+//   cost:   a pass whose H and g nobody reads (cost_only: the last one of a fixed-iteration solve) forms residual, Huber and cost only.
+// Every value that is formed comes from eval_frame's expression for it, every sum takes its terms in eval_frame's order: the 28 sums are
+// bit-identical (cost_only: the 28th), which tests/test_gpu_solve_batch_form.py holds against the other forms.
+__device__ __forceinline__ double uniform_f64(double v) {
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+// s: a Pose in LDS, written before the last barrier
+__device__ __forceinline__ void pose_uniform(const Pose& s, Pose& P) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        P.R[k] = uniform_f64(s.R[k]);
+        P.Jl[k] = 0.0;  // (pose_at_use)
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        P.t[k] = uniform_f64(s.t[k]);
+        P.tb[k] = 0.0;
+    }
+}
+
+// the pose row_jacobian reads: R and t of P (scalar registers) with tb and Jl read from the LDS copy HERE, behind a compiler barrier
+// that keeps the twelve loads inside the factor's body
+__device__ __forceinline__ Pose pose_at_use(const Pose& P, const Pose* sp) {
+    Pose Q;
+    asm volatile("" ::: "memory");
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Q.Jl[k] = sp->Jl[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) Q.tb[k] = sp->tb[k];
+    return Q;
+}
+
+struct LineFixed {
+    float c[3], a[3], b[3];  // ori, p1, p2
+    double il12;             // 1 / |p1 - p2|
+    bool valid;              // false: the factor is skipped (no record, or |error| <= 1e-5)
+};
+__device__ __forceinline__ void line_fixed(const MmlLineFactor& f, LineFixed& o) {
+    o.valid = !(f.src < 0 || !(fabs(f.error) > 1e-5));  // Estimator.cpp:1385
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        o.c[k] = f.ori[k];
+        o.a[k] = f.p1[k];
+        o.b[k] = f.p2[k];
+    }
+    const double ax = f.p1[0], ay = f.p1[1], az = f.p1[2], bx = f.p2[0], by = f.p2[1], bz = f.p2[2];
+    double l12;
+    const double dx = ax - bx, dy = ay - by, dz = az - bz;
+    sqrt_pair(__builtin_fma(dz, dz, __builtin_fma(dy, dy, dx * dx)), l12, o.il12);
+}
+// eval_frame's line-factor body behind its validity test
+__device__ __forceinline__ void line_accum(const LineFixed& L, const Pose& P, const Pose* sp, double ka, double huber_delta, bool cost_only, double* acc) {
+    const double cx = L.c[0], cy = L.c[1], cz = L.c[2];
+    const double ax = L.a[0], ay = L.a[1], az = L.a[2], bx = L.b[0], by = L.b[1], bz = L.b[2];
+    double Pw[3];
+    Pw[0] = __builtin_fma(P.R[2], cz, __builtin_fma(P.R[1], cy, __builtin_fma(P.R[0], cx, P.t[0])));
+    Pw[1] = __builtin_fma(P.R[5], cz, __builtin_fma(P.R[4], cy, __builtin_fma(P.R[3], cx, P.t[1])));
+    Pw[2] = __builtin_fma(P.R[8], cz, __builtin_fma(P.R[7], cy, __builtin_fma(P.R[6], cx, P.t[2])));
+    double a012, ia012, s12, is12, rs, sm14;
+    const double dx = ax - bx, dy = ay - by, dz = az - bz, il12 = L.il12;  // (three subtractions: cheaper than six registers)
+    const double pax = Pw[0] - ax, pay = Pw[1] - ay, paz = Pw[2] - az, pbx = Pw[0] - bx, pby = Pw[1] - by, pbz = Pw[2] - bz;
+    const double c0 = __builtin_fma(pax, pby, -(pbx * pay));
+    const double c1 = __builtin_fma(pax, pbz, -(pbx * paz));
+    const double c2 = __builtin_fma(pay, pbz, -(pby * paz));
+    sqrt_pair(__builtin_fma(c2, c2, __builtin_fma(c1, c1, c0 * c0)), a012, ia012);
+    const double ld2 = a012 * il12;
+    const double s = __builtin_fma(Pw[2], Pw[2], __builtin_fma(Pw[1], Pw[1], Pw[0] * Pw[0]));
+    sqrt_pair(s, s12, is12);
+    sqrt_pair(s12, rs, sm14);
+    const double weight = 1.0 - 0.9 * fabs(ld2) * sm14;
+    const double r = ka * weight * ld2;
+    double rho0, rho1;
+    huber(r * r, huber_delta, rho0, rho1);
+    acc[27] += 0.5 * rho0;
+    if (cost_only) return;
+    const double ux = c2 * ia012, uy = -c1 * ia012, uz = c0 * ia012;
+    double gl[3] = {__builtin_fma(dy, uz, -(dz * uy)) * il12, __builtin_fma(dz, ux, -(dx * uz)) * il12, __builtin_fma(dx, uy, -(dy * ux)) * il12};
+    const double sm54 = sm14 * (is12 * is12);
+    double gr[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        double gw = (-0.9) * __builtin_fma(fabs(ld2) * (-0.5) * sm54, Pw[c], sm14 * gl[c]);
+        gr[c] = ka * __builtin_fma(ld2, gw, weight * gl[c]);
+    }
+    double J[6];
+    row_jacobian(pose_at_use(P, sp), Pw, gr, J);
+    accum(acc, J, r, rho1);
+}
+// plane_row and the sums eval_frame takes from it, behind the validity test
+__device__ __forceinline__ void plane_accum(const MmlPlaneFactor& f, const Pose& P, const Pose* sp, double ka, double huber_delta, bool cost_only, double* acc) {
+    const double cx = f.ori[0], cy = f.ori[1], cz = f.ori[2];
+    double Pw[3];
+    Pw[0] = __builtin_fma(P.R[2], cz, __builtin_fma(P.R[1], cy, __builtin_fma(P.R[0], cx, P.t[0])));
+    Pw[1] = __builtin_fma(P.R[5], cz, __builtin_fma(P.R[4], cy, __builtin_fma(P.R[3], cx, P.t[1])));
+    Pw[2] = __builtin_fma(P.R[8], cz, __builtin_fma(P.R[7], cy, __builtin_fma(P.R[6], cx, P.t[2])));
+    const double d[3] = {Pw[0] - f.proj[0], Pw[1] - f.proj[1], Pw[2] - f.proj[2]};
+    double nd, ind, s12, is12, rs, sm14;
+    sqrt_pair(__builtin_fma(d[2], d[2], __builtin_fma(d[1], d[1], d[0] * d[0])), nd, ind);
+    const double s = __builtin_fma(Pw[2], Pw[2], __builtin_fma(Pw[1], Pw[1], Pw[0] * Pw[0]));
+    sqrt_pair(s, s12, is12);
+    sqrt_pair(s12, rs, sm14);
+    const double weight = 1.0 - 0.9 * nd * sm14;
+    const double row[3] = {ka * (double)f.omega[0], ka * (double)f.omega[1], ka * (double)f.omega[2]};
+    const double rr = weight * __builtin_fma(row[2], d[2], __builtin_fma(row[1], d[1], row[0] * d[0]));
+    double sq = 0;
+    sq = __builtin_fma(rr, rr, sq);
+    double rho0, rho1;
+    huber(sq, huber_delta, rho0, rho1);
+    acc[27] += 0.5 * rho0;
+    if (cost_only) return;
+    const double sm54 = sm14 * (is12 * is12);
+    double gw[3];
+    const double gwa = sm14 * ind, gwb = nd * (-0.5) * sm54;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) gw[c] = (-0.9) * __builtin_fma(gwb, Pw[c], gwa * d[c]);
+    const double rd = __builtin_fma(row[2], d[2], __builtin_fma(row[1], d[1], row[0] * d[0]));
+    double gr[3] = {__builtin_fma(rd, gw[0], weight * row[0]), __builtin_fma(rd, gw[1], weight * row[1]), __builtin_fma(rd, gw[2], weight * row[2])};
+    double J[6];
+    row_jacobian(pose_at_use(P, sp), Pw, gr, J);
+    accum(acc, J, rr, rho1);
+}
+// P: uniform (pose_uniform); L0: line_fixed of factor threadIdx.x (valid = false where there is none); nlf, npf >= 0
+__device__ __forceinline__ void eval_frame_w1(const MmlLineFactor* lf, int nlf, const MmlPlaneFactor* pf, int npf, const Pose& P,
+                                              const Pose* sp, const LineFixed& L0, double huber_delta, bool cost_only, double* acc) {
+#pragma unroll
+    for (int k = 0; k < 28; ++k) acc[k] = 0;
+    const double ka = 1.0 / kLidarM;
+    if (L0.valid) line_accum(L0, P, sp, ka, huber_delta, cost_only, acc);
+    // (a thread's second and later line factors -- more than SOLVE_THREADS of them in a scan -- as eval_frame takes them)
+    for (int i = threadIdx.x + SOLVE_THREADS; i < nlf; i += SOLVE_THREADS) {
+        LineFixed L;
+        line_fixed(lf[i], L);
+        if (L.valid) line_accum(L, P, sp, ka, huber_delta, cost_only, acc);
+    }
+    for (int i = threadIdx.x; i < npf; i += SOLVE_THREADS) {
+        const MmlPlaneFactor f = pf[i];
+        if (f.src < 0 || !(fabs(f.error) > 1e-5)) continue;  // Estimator.cpp:1396
+        plane_accum(f, P, sp, ka, huber_delta, cost_only, acc);
+    }
+}
+
 // block reduction of acc[28] into out[28] (LDS or global); result valid for thread 0 after the trailing barrier.
 // Inside a wavefront the 28 sums are reduced as a butterfly that halves the number of values a lane carries at every
 // step (at offset o the lanes with bit o set keep the upper half of their values and hand over the lower half): 16 + 8 +

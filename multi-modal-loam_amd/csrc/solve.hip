@@ -1147,6 +1147,144 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_solve(SolveParams P) {
     }
 }
 
+// k_solve<false> for one-frame problems with one-row plane factors and no trace (mml_step's batch launches: window = 1,
+// plan_weight_tan = 0), compiled for THREE wavefronts per SIMD.  The general form carries the frame loops, the tangent rows and a Pose
+// per lane through its factor pass and sits at 256 registers: four problems per CU.  Here (lidar_eval.h eval_frame_w1)
+//   - W and w_tan are compile-time; s_wd stays at TRW_DOUBLES because tr_decide_wave addresses it at 36 MAXW whatever W is;
+//   - the pose is formed ONCE per pass, by the first wavefront behind its proposal (make_pose: the same expressions), and left in LDS;
+//     after the barrier R and t go into SCALAR registers (v_readfirstlane; one scalar operand per FMA), t_wb and J_l are read from LDS
+//     where row_jacobian uses them (all 24 doubles in scalar registers: 65 spilled to v_readlane, stage 0.231 -> 0.234 ms; this: 21);
+//   - a thread's first line factor and what a pass does not change about it are loaded once per solve;
+//   - the pass behind the last proposal of a fixed-iteration solve forms the cost only: tr_decide_wave reads H and g of the candidate
+//     record only to copy them into S.rec, which nothing reads once the iteration count is reached (and, not fixed, for the gradient
+//     test -- there every pass is a full one).
+// Budget: <= 168 vector registers (512 per SIMD lane / 3 at the granule of 8), no scratch, and 6 workgroups' LDS per CU (6 x ~12 KB of
+// 160 KB); amdgpu_waves_per_eu holds the compiler to it, tools/kernel_regs.sh solve.hip k_solve shows what it made: 163 registers, no
+// scratch, 12 368 B.  eval_frame's one-record-ahead prefetch of the plane records (16 registers) does not fit and is left out.
+// Measured (profiles/solve_batch_form_ab.txt): a problem's own factor pass is 3.6 % of its life (phase clocks), so the third wavefront
+// does not make a problem faster, and 1024 problems on one stream -- four per CU, resident at once either way -- take what they took
+// (0.232 -> 0.231 ms).  What it buys is residency: six problems per CU instead of four in the 4096-problem launches of a step,
+// 1.39 -> 1.12 ms per launch there, the step +0.4 ... +2 %.
+// Same summation orders, same trust-region code: a slot solved here equals the slot solved by any other form bit for bit.
+__global__ __launch_bounds__(SOLVE_THREADS) __attribute__((amdgpu_waves_per_eu(3))) void k_solve_batch1(SolveParams P) {
+    __shared__ TRState S;
+    __shared__ double s_part[SOLVE_WAVES * 28];
+    __shared__ double s_work[92];
+    __shared__ double s_wd[TRW_DOUBLES];
+    __shared__ Pose s_pose;
+    static_assert(3 * 2 * (sizeof(TRState) + sizeof(s_part) + sizeof(s_work) + sizeof(s_wd) + sizeof(Pose)) <= 160 * 1024,
+                  "k_solve_batch1: three wavefronts per SIMD are six workgroups per CU");
+    const int prob = blockIdx.x;
+    const int b0 = P.first + prob;
+    const int tid = threadIdx.x;
+    PhaseClock_sv clk(SV_WATCH(tid == 0 && prob == MML_SV_TIMING));
+    clk.count(7);
+    const MmlLineFactor* lf = P.lf + (size_t)b0 * P.MF;
+    const MmlPlaneFactor* pf = P.pf + (size_t)b0 * P.MF;
+    const int nlf = max(P.ft_n[b0], 0), npf = max(P.ft_n[P.B + b0], 0);  // (-1: the overflow mark of a stack)
+    if (tid < 6) S.x[tid] = S.x_init[tid] = P.x[(size_t)b0 * 6 + tid];
+    if (tid < 64) {
+        __builtin_amdgcn_wave_barrier();
+        asm volatile("" ::: "memory");
+        Pose pose;
+        make_pose(S.x, P.Tbl, pose);
+        if (tid == 0) s_pose = pose;
+    }
+    LineFixed L0;
+    L0.valid = false;
+    if (tid < nlf) line_fixed(lf[tid], L0);
+    __syncthreads();
+
+    double acc[28];
+    {
+        Pose pose;
+        pose_uniform(s_pose, pose);
+        eval_frame_w1(lf, nlf, pf, npf, pose, &s_pose, L0, P.huber, false, acc);
+        block_reduce28(acc, s_part, S.rec);
+    }
+    if (tid == 0) {  // (tr_init's statements, as in k_solve and k_solve_wide: calling it from here changes how the compiler inlines it into them)
+        S.cost = 0;
+        double xn = 0;
+        S.cost += S.rec[27];
+        for (int i = 0; i < 6; ++i) {
+            S.scale[i] = 1.0 / (1.0 + sqrt(Hget(S.rec, i, i)));
+            xn += S.x[i] * S.x[i];
+        }
+        S.x_norm = sqrt(xn);
+        S.radius = 1e4;
+        S.mu = 1e-8;
+        S.reuse = 0;
+        S.num_invalid = 0;
+        S.iter = 0;
+        S.successful = 0;
+        S.termination = 0;
+        S.go = 1;
+        S.alpha = 0;
+        S.dogleg_norm = 0;
+        P.summ[8 * prob + 2] = S.cost;  // initial cost
+        if (!P.fixed) {
+            double gm = 0;
+            for (int i = 0; i < 6; ++i) gm = fmax(gm, fabs(S.rec[21 + i]));
+            if (gm <= 1e-10) {
+                S.termination = 1;
+                S.go = 0;
+            }
+        }
+    }
+    __syncthreads();
+
+    int go = S.go;
+    __syncthreads();
+    clk.mark(0);  // set-up + initial evaluation
+    while (go) {
+        // the first wavefront owns the trust-region state between the barriers; every other lane only reads it after one
+        // (the lane number is opaque to the compiler in every iteration, as in k_solve_wide: as a known function of threadIdx.x the LDS
+        //  addresses of the trust-region code are formed in front of the loop and held across the factor pass -- beyond 168 registers)
+        int lane_op = tid;
+        asm volatile("" : "+v"(lane_op));
+        if (tid < 64) {
+            tr_propose_w1_wave(S, s_work, P.max_iters, lane_op);
+            __builtin_amdgcn_wave_barrier();
+            asm volatile("" ::: "memory");
+            if (S.go && S.evaluate) {  // the candidate's pose, for everybody
+                Pose pose;
+                make_pose(S.xc, P.Tbl, pose);
+                if (tid == 0) s_pose = pose;
+            }
+        }
+        __syncthreads();
+        clk.mark(1);  // trust-region proposal + pose (first wavefront) + barrier
+        go = S.go;
+        const int ev = S.evaluate;
+        if (!go) break;
+        if (ev) {
+            // the evaluation behind the last proposal there will be: its H and g are never read (see above)
+            const bool cost_only = P.fixed && S.iter >= P.max_iters;
+            Pose pose;
+            pose_uniform(s_pose, pose);
+            eval_frame_w1(lf, nlf, pf, npf, pose, &s_pose, L0, P.huber, cost_only, acc);
+            clk.mark(2);  // factor pass of this thread
+            block_reduce28(acc, s_part, S.recc);
+            clk.mark(3);  // block reduction (waits for the slowest wavefront's factor pass)
+            asm volatile("" : "+v"(lane_op));
+            if (tid < 64) tr_decide_wave(S, s_wd, 1, P.fixed, lane_op);
+        }
+        __syncthreads();
+        clk.mark(4);  // accept / reject (first wavefront) + barrier
+        go = S.go;
+        __syncthreads();
+    }
+    if (tid < 6) P.x[(size_t)b0 * 6 + tid] = S.x[tid];
+    if (tid == 0) {
+        double* o = P.summ + 8 * prob;
+        o[0] = S.iter;
+        o[1] = S.successful;
+        o[3] = S.cost;
+        o[4] = S.termination;
+        o[5] = 0;  // (finished: see k_window_export)
+    }
+}
+
 // k_solve<true> for one-frame problems with one-row plane factors (the live path's only setting), on all four SIMDs of the problem's
 // CU: 4 x 128 threads, the factor passes through eval_frame_wide (lidar_eval.h: rows formed by 512 threads, sums and reduction tree of
 // the 128-thread pass -- bit-identical), the trust-region code between the passes on the first wavefront as in k_solve.  About 148 KiB
@@ -1936,6 +2074,8 @@ int mml_launch_solve(mml_ctx* ctx, int first, int count, int window, const doubl
         hipLaunchKernelGGL(k_solve_wide, dim3(count), dim3(WIDE_THREADS), 0, MML_STREAM(ctx), P);
     else if (small)
         hipLaunchKernelGGL(k_solve<true>, dim3(count / window), dim3(SOLVE_THREADS), 0, MML_STREAM(ctx), P);
+    else if (window == 1 && opts.plan_weight_tan == 0.0 && !want_trace)  // the batch launches of mml_step: the three-wavefront form
+        hipLaunchKernelGGL(k_solve_batch1, dim3(count), dim3(SOLVE_THREADS), 0, MML_STREAM(ctx), P);
     else
         hipLaunchKernelGGL(k_solve<false>, dim3(count / window), dim3(SOLVE_THREADS), 0, MML_STREAM(ctx), P);
     MML_HIP(hipGetLastError());
