@@ -641,6 +641,41 @@ int mml_map_global_reset(mml_ctx* ctx);
  * that kd-tree tie order is preserved).  cen: laserCloudCen{Width,Height,Depth}_last (3 ints, NULL keeps
  * the current value, default 10, 5, 10).  m = 0 removes the global map (local-only association). */
 int mml_map_set_global(mml_ctx* ctx, int kind, const float* xyz, const int* cube, int m, const int* cen);
+
+/* ---- map banks: N further local maps per context, every scan slot matched against its own ----------------------
+ * For several sequences in one context (a fleet's bags, or one bag cut into segments, replayed offline).  A bank is one
+ * more local map with the state of the context's own: the 50-entry key-scan ring of corner and surf features with its
+ * counts, localMapID, the two kNN grids with their unsorted clouds, the two map sizes.  The context's own map stays as it
+ * is; it is what an unbound slot is matched against.  A bank that was never set is an empty map (no feature gets a
+ * factor).  Memory per bank: 96 bytes per point of max_map_points, plus 2 x 50 x max_features x 16 bytes from its first
+ * increment on.
+ * mml_map_banks_create: n_banks in [1, MML_MAP_BANKS_MAX]; a context has one set of banks (MML_ERR_STATE when it has
+ * one already).  mml_map_banks_destroy releases them and unbinds every slot; mml_destroy does the same.
+ * mml_map_bank_set_local / _reset / _download: mml_map_set_local / mml_map_local_reset / mml_map_local_download on
+ * bank `bank`.
+ * mml_slot_bind_bank: banks[i] is the bank of slot first_slot + i, -1 the context's own map.  A binding stays until it is
+ * changed.  Every call that associates honours it without a further argument: mml_associate, mml_estimate, mml_step (and
+ * so the factors mml_fullwindow_solve, mml_fullwindow_solve_batch and mml_fullwindow_marginalize_batch read, which are
+ * the ones mml_associate left).  The result of a slot is bit-identical to that of the same call on a context whose own
+ * map holds the bank's cloud.  With every slot of a call bound, the context's own map need not be set.
+ * NO CUBE STAGE: banked slots are matched against their bank alone.  Binding a slot to a bank while a global cube map is
+ * set (mml_map_set_global, mml_map_global_increment) returns MML_ERR_STATE, and so does a call that associates a bound
+ * slot after one was set; nothing is changed in either case.
+ * mml_slot_bank_get reads the bindings back (all -1 on a context without banks).
+ * mml_map_bank_increment: mml_map_increment_local for n DISTINCT banks (a bank named twice is MML_ERR_INVALID, checked
+ * with every other argument before anything changes): bank banks[i] takes the stacks of slot slots[i] at T_wl + 16 i.
+ * Every bank ends bit-identical to the own map of a context with the same history of increments.  n_corner / n_surf: n
+ * new map sizes each, or NULL. */
+#define MML_MAP_BANKS_MAX 1024
+int mml_map_banks_create(mml_ctx* ctx, int n_banks);
+int mml_map_banks_destroy(mml_ctx* ctx);
+int mml_map_bank_set_local(mml_ctx* ctx, int bank, int kind, const float* xyz, int m);
+int mml_map_bank_reset(mml_ctx* ctx, int bank);
+int mml_map_bank_download(mml_ctx* ctx, int bank, int kind, float* xyz, int capacity, int* n);
+int mml_slot_bind_bank(mml_ctx* ctx, int first_slot, int count, const int* banks);
+int mml_slot_bank_get(mml_ctx* ctx, int first_slot, int count, int* banks);
+int mml_map_bank_increment(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl, int* n_corner, int* n_surf);
+
 /* Exact 5-NN against a local map (twin of kdtree->nearestKSearch(p, 5, idx, d2), Estimator.cpp:284,704):
  * q: nq x 3 host floats (already in the map frame); idx: nq x 5 (indices into the uploaded cloud,
  * ascending d2, ties by lower index), d2: nq x 5 (float, ((dx*dx+dy*dy)+dz*dz)). max_d2: search bound

@@ -1208,6 +1208,50 @@ class Context:
         self._ck(lib().mml_map_local_download(self._h, C.c_int(kind), _p(out), C.c_int(n.value), C.byref(n)))
         return out[:n.value].copy()
 
+    # ---- map banks: further local maps, every slot matched against its own (include/mmloam_hip.h, "map banks") ----
+    def map_banks(self, n):
+        """Creates n banks (n = 0: releases them and unbinds every slot)."""
+        if n == 0:
+            self._ck(lib().mml_map_banks_destroy(self._h))
+        else:
+            self._ck(lib().mml_map_banks_create(self._h, C.c_int(n)))
+
+    def bind_banks(self, first, banks):
+        """banks[i]: the bank of slot first + i, -1 the context's own map; stays until it is changed."""
+        b = np.ascontiguousarray(banks, dtype=np.int32).reshape(-1)
+        self._ck(lib().mml_slot_bind_bank(self._h, C.c_int(first), C.c_int(len(b)), _p(b)))
+
+    def slot_banks(self, first, count):
+        b = np.zeros(count, np.int32)
+        self._ck(lib().mml_slot_bank_get(self._h, C.c_int(first), C.c_int(count), _p(b)))
+        return b
+
+    def bank_set_local(self, bank, kind, xyz):
+        xyz = _f32(xyz).reshape(-1, 3)
+        self._ck(lib().mml_map_bank_set_local(self._h, C.c_int(bank), C.c_int(kind), _p(xyz), C.c_int(len(xyz))))
+
+    def bank_reset(self, bank):
+        self._ck(lib().mml_map_bank_reset(self._h, C.c_int(bank)))
+
+    def bank_download(self, bank, kind):
+        n = C.c_int(0)
+        self._ck(lib().mml_map_bank_download(self._h, C.c_int(bank), C.c_int(kind), None, C.c_int(0), C.byref(n)))
+        out = np.zeros((max(n.value, 1), 3), np.float32)
+        self._ck(lib().mml_map_bank_download(self._h, C.c_int(bank), C.c_int(kind), _p(out), C.c_int(n.value), C.byref(n)))
+        return out[:n.value].copy()
+
+    def bank_increment(self, banks, slots, T_wl):
+        """Estimator::MapIncrementLocal for len(banks) distinct banks in one call: bank banks[i] grows by the stacks of slot
+        slots[i] at T_wl[i] (4 x 4).  Returns the new (corner, surf) map sizes, one pair of arrays entry per bank."""
+        b = np.ascontiguousarray(banks, dtype=np.int32).reshape(-1)
+        s = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        T = _f64(T_wl).reshape(-1, 16)
+        if not (len(b) == len(s) == len(T)):
+            raise ValueError("one slot and one pose per bank")
+        nc, ns = np.zeros(max(len(b), 1), np.int32), np.zeros(max(len(b), 1), np.int32)
+        self._ck(lib().mml_map_bank_increment(self._h, C.c_int(len(b)), _p(b), _p(s), _p(T), _p(nc), _p(ns)))
+        return nc[:len(b)], ns[:len(b)]
+
     def map_global_append(self, slot, T_wl):
         self._ck(lib().mml_map_global_append(self._h, C.c_int(slot), _p(_f64(T_wl).reshape(16))))
 

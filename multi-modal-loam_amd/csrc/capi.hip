@@ -1270,7 +1270,7 @@ int mml_map_increment_local(mml_ctx* ctx, int slot, const double* T_wl, int* n_c
     int rc = mml_sync_all(ctx);
     if (rc != MML_OK) return rc;
     int n[2] = {0, 0};
-    rc = mml_map_upkeep_increment(ctx, slot, T_wl, n);
+    rc = mml_map_upkeep_increment(ctx, mml_map_own(ctx), slot, T_wl, n);
     if (n_corner_map) *n_corner_map = n[0];
     if (n_surf_map) *n_surf_map = n[1];
     return rc;
@@ -1414,7 +1414,10 @@ int mml_associate(mml_ctx* ctx, int first_slot, int count, const double* T_wl, d
                   mml_assoc_stats* stats) {
     CHECK_SLOTS(first_slot, count);
     MML_REQUIRE(T_wl != nullptr, MML_ERR_INVALID, "null T_wl");
-    MML_REQUIRE(ctx->have_map[0] && ctx->have_map[1], MML_ERR_STATE, "mml_associate before both maps were set");
+    {
+        const int ready = mml_assoc_ready(ctx, first_slot, count, "mml_associate");
+        if (ready != MML_OK) return ready;
+    }
     double* d_T = ctx->d_pose_in + kPoseSlotDoubles * (size_t)first_slot;
     int rc = upload_doubles(ctx, d_T, T_wl, 16 * (size_t)count);
     if (rc != MML_OK) return rc;
@@ -1759,7 +1762,10 @@ int mml_estimate(mml_ctx* ctx, int first_slot, int count, const double* exTlb, d
                  int inner_iters, mml_estimate_info* info) {
     CHECK_SLOTS(first_slot, count);
     MML_REQUIRE(exTlb && P && Q && max_outer >= 1 && inner_iters >= 0, MML_ERR_INVALID, "bad arguments");
-    MML_REQUIRE(ctx->have_map[0] && ctx->have_map[1], MML_ERR_STATE, "mml_estimate before both maps were set");
+    {
+        const int ready = mml_assoc_ready(ctx, first_slot, count, "mml_estimate");
+        if (ready != MML_OK) return ready;
+    }
     double T_bl[16];
     invert_extrinsic(exTlb, T_bl);
     std::vector<int> done(count, 0), outer(count, 0), degen(count, 0);
@@ -1834,7 +1840,10 @@ int mml_step(mml_ctx* ctx, int first_slot, int count, const double* dR, const do
     CHECK_SLOTS(first_slot, count);
     MML_REQUIRE(dR && dt && exTlb && x_inout, MML_ERR_INVALID, "null argument");
     MML_REQUIRE(gn_iters >= 0 && gn_iters <= 64, MML_ERR_INVALID, "gn_iters must be in [0, 64]");
-    MML_REQUIRE(ctx->have_map[0] && ctx->have_map[1], MML_ERR_STATE, "mml_step before both maps were set");
+    {
+        const int ready = mml_assoc_ready(ctx, first_slot, count, "mml_step");
+        if (ready != MML_OK) return ready;
+    }
     double T_bl[16];
     invert_extrinsic(exTlb, T_bl);
     mml_solve_opts so;

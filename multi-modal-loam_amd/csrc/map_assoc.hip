@@ -327,6 +327,60 @@ struct AssocParams {
     float* hard_knn;   // 10 floats per queued feature: the top-5 (d2, index) found in rings 0-1
 };
 
+// The kernels' argument.  A launch without a bound slot takes AssocParams as it is: every slot is matched against P.g / P.map_orig /
+// P.map_m, which live in the kernel arguments.  A launch with a bound slot (BANKED, map banks) carries the device-resident
+// descriptor table -- row 2 * e + kind, e = 0 the context's own map, e = 1 + bank -- and the bank of every slot of the context;
+// there P.g / P.map_orig / P.map_m are not read, and no cube stage exists (P.have_g is 0: mml_assoc_ready refuses the launch
+// otherwise).
+template <bool BANKED>
+struct AssocArgs;
+template <>
+struct AssocArgs<false> : AssocParams {};
+template <>
+struct AssocArgs<true> : AssocParams {
+    const MmlMapDesc* table;
+    const int* slot_bank;  // B, indexed by the slot itself
+};
+static_assert(sizeof(AssocArgs<false>) == sizeof(AssocParams), "the unbanked kernels' argument block is AssocParams");
+
+// The local map of kind `kind` that slot b is matched against.  Unbanked: the kernel arguments.  Banked: the slot's row of the
+// table; UNIFORM (b and kind are the same in every lane: one block of k_associate / k_associate_fit_all works on one slot and
+// kind) brings the row into scalar registers, as the kernel arguments are -- the search re-reads a descriptor that sits in vector
+// registers or memory in front of every row --; otherwise (a far-query group) every lane loads the row of its own entry.
+template <bool BANKED, bool UNIFORM>
+struct SlotMap;
+template <bool UNIFORM>
+struct SlotMap<false, UNIFORM> {
+    const AssocParams& P;
+    int kind;
+    __device__ __forceinline__ SlotMap(const AssocArgs<false>& P_, int, int kind_) : P(P_), kind(kind_) {}
+    __device__ __forceinline__ const MmlGrid& grid(int ukind) const { return P.g[ukind]; }  // (ukind: the kind as a scalar)
+    __device__ __forceinline__ int m() const { return P.map_m[kind]; }
+    __device__ __forceinline__ const float4* orig() const { return P.map_orig[kind]; }
+};
+template <bool UNIFORM>
+struct SlotMap<true, UNIFORM> {
+    MmlMapDesc d;
+    __device__ __forceinline__ SlotMap(const AssocArgs<true>& P, int b, int kind) {
+        constexpr int N = sizeof(MmlMapDesc) / 4;
+        int w[N];
+        if (UNIFORM) {
+            const int e = __builtin_amdgcn_readfirstlane(P.slot_bank[b]) + 1;
+            const int* src = reinterpret_cast<const int*>(P.table + (2 * e + __builtin_amdgcn_readfirstlane(kind)));
+#pragma unroll
+            for (int j = 0; j < N; ++j) w[j] = __builtin_amdgcn_readfirstlane(src[j]);
+        } else {
+            const int* src = reinterpret_cast<const int*>(P.table + (2 * (P.slot_bank[b] + 1) + kind));
+#pragma unroll
+            for (int j = 0; j < N; ++j) w[j] = src[j];
+        }
+        __builtin_memcpy(&d, w, sizeof(d));
+    }
+    __device__ __forceinline__ const MmlGrid& grid(int) const { return d.g; }
+    __device__ __forceinline__ int m() const { return d.g.m; }
+    __device__ __forceinline__ const float4* orig() const { return d.orig; }
+};
+
 __device__ __forceinline__ void tf_point(const double* T, double x, double y, double z, double& ox, double& oy,
                                          double& oz) {
     ox = ((T[0] * x + T[1] * y) + T[2] * z) + T[3];
@@ -707,7 +761,8 @@ constexpr int HARD_FRESH = 1 << 29;  // queue entry: nothing searched yet, start
 #define MML_AW_FIT 4
 #define MML_AW_HARD 1
 #endif
-__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MML_AW_SEARCH))) void k_associate(AssocParams P) {
+template <bool BANKED>
+__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MML_AW_SEARCH))) void k_associate(AssocArgs<BANKED> P) {
     const int nitems = 2 * P.count;
     const int total = P.work_off[nitems];
     for (int w = blockIdx.x; w < total; w += gridDim.x) {
@@ -716,6 +771,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MML_AW_SEAR
         const int b = slot + P.first;
         const int i = (w - P.work_off[item]) * 128 + threadIdx.x;
         const int nf = P.ft_n[kind * P.B + b];
+        const SlotMap<BANKED, true> map(P, b, kind);  // (in front of the first divergent branch: every lane takes part)
         if (i >= nf) continue;
         int4* rec = assoc_rec(P, kind, b, i);
         const double* T = P.Twl + 16 * slot;
@@ -728,7 +784,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MML_AW_SEAR
         const int cube = find_used_map(sx, sy, sz, P.cen);
         // stage 0: the cube's own cloud when it holds > 100 corner / > 50 surf points (:198, :627); stage 1: local map
         const int stage = (cube != 5000 && P.have_g[kind] && P.cube_cnt[kind][cube] > (kind == 0 ? 100 : 50)) ? 0 : 1;
-        if (cube == 5000 || isnan(sx) || isnan(sy) || isnan(sz) || (stage == 1 && !(P.map_m[kind] > 20))) {  // (:283 / :702)
+        if (cube == 5000 || isnan(sx) || isnan(sy) || isnan(sz) || (stage == 1 && !(map.m() > 20))) {  // (:283 / :702)
             rec[1] = make_int4(0, 0, REC_NONE, 0);
             continue;
         }
@@ -753,7 +809,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MML_AW_SEAR
             rmax = (int)ceilf(sqrtf(P.thres) * g.inv_cell) + 1;
             done = scan_rings01(g, q, rmax, P.thres, k, cube);
         } else {
-            const MmlGrid& g = P.g[ukind];
+            const MmlGrid& g = map.grid(ukind);
             const KnnQuery q = knn_query(g, sx, sy, sz);
             rmax = (int)ceilf(sqrtf(P.thres) * g.inv_cell) + 1;
             done = scan_rings01(g, q, rmax, P.thres, k, -1);
@@ -777,7 +833,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MML_AW_SEAR
 
 // Model fit of every feature pass 1 finished itself, one lane each.  A feature whose cube neighbourhood (stage 0) yields
 // no model is appended to the far-query list with the "search again in the local map" mark (:283 / :702).
-__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MML_AW_FIT))) void k_associate_fit_all(AssocParams P) {
+template <bool BANKED>
+__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MML_AW_FIT))) void k_associate_fit_all(AssocArgs<BANKED> P) {
     const int nitems = 2 * P.count;
     const int total = P.work_off[nitems];
     for (int w = blockIdx.x; w < total; w += gridDim.x) {
@@ -786,6 +843,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MML_AW_FIT)
         const int b = slot + P.first;
         const int i = (w - P.work_off[item]) * 128 + threadIdx.x;
         const int nf = P.ft_n[kind * P.B + b];
+        const SlotMap<BANKED, true> map(P, b, kind);
         if (i >= nf) continue;
         const int4* rec = assoc_rec(P, kind, b, i);
         const int4 r0 = rec[0], r1 = rec[1];
@@ -809,9 +867,9 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MML_AW_FIT)
         k.key[3] = knn_key(d5, r0.w);
         k.key[4] = knn_key(d5, r1.x);
         const bool ok = (double)d5 < P.thres_d;  // :201,285 / :631,705
-        const bool stored = fit_and_store(P, kind, b, i, f, T, sx, sy, sz, ok, k, stage == 0 ? P.gmap_orig[kind] : P.map_orig[kind]);
+        const bool stored = fit_and_store(P, kind, b, i, f, T, sx, sy, sz, ok, k, stage == 0 ? P.gmap_orig[kind] : map.orig());
         if (!stored) {
-            if (stage == 0 && P.map_m[kind] > 20) {
+            if (stage == 0 && map.m() > 20) {
                 const int hw = atomicAdd(P.hard_count, 1);
                 P.hard_list[hw] = make_int4(slot, kind, i, (cube << 1) | HARD_REDO);
             } else {
@@ -834,8 +892,8 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MML_AW_FIT)
 // round 1: the features whose cube-stage fit failed (HARD_REDO), local map from ring 0 (:283 / :702).
 // SPAN = lanes that share one query (they split the rows of every shell): 4 for batches -- many queries, throughput --, 64 / 32 for
 // the live path's handful of scans, where the kernel lasts as long as its slowest query and a far query walks up to 169 rows a shell.
-template <int SPAN>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MML_AW_HARD))) void k_associate_hard(AssocParams P, int round) {
+template <int SPAN, bool BANKED>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MML_AW_HARD))) void k_associate_hard(AssocArgs<BANKED> P, int round) {
     const int gl = threadIdx.x & (SPAN - 1);
     const int group = (blockIdx.x * 256 + threadIdx.x) / SPAN;
     const int ngroups = (gridDim.x * 256) / SPAN;
@@ -880,7 +938,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MML_AW_HARD
         // the entry's grid descriptor, selected field by field into registers once (a reference to one of four kernel
         // argument structs picked per lane is re-read from memory at every use)
         MmlGrid g = P.g[0];
-        {
+        if constexpr (BANKED) {
+            g = SlotMap<true, false>(P, b, kind).d.g;  // the entry's slot names the map (a lane without an entry: that of P.first)
+        } else {
             const bool k1 = kind == 1, s0 = stage == 0;
             const MmlGrid &a = P.g[1], &c = P.gg[0], &d = P.gg[1];
 #define MML_PICK(field) g.field = s0 ? (k1 ? d.field : c.field) : (k1 ? a.field : g.field)
@@ -945,7 +1005,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MML_AW_HARD
 }
 
 // model fit of the far queries, one lane per queued feature (see k_associate_hard)
-__global__ __launch_bounds__(128) void k_associate_fit(AssocParams P, int round) {
+template <bool BANKED>
+__global__ __launch_bounds__(128) void k_associate_fit(AssocArgs<BANKED> P, int round) {
     const int total = *P.hard_count;
     for (int w = blockIdx.x * 128 + threadIdx.x; w < total; w += gridDim.x * 128) {
         const int4 e = P.hard_list[w];
@@ -962,11 +1023,12 @@ __global__ __launch_bounds__(128) void k_associate_fit(AssocParams P, int round)
         for (int j = 0; j < 5; ++j) {
             best.key[j] = knn_key(hd[j], __float_as_int(hd[5 + j]));
         }
+        const SlotMap<BANKED, false> map(P, b, kind);
         const bool ok = (double)knn_d(best, 4) < P.thres_d;
         const bool stored = fit_and_store(P, kind, b, i, f, P.Twl + 16 * slot, sx, sy, sz, ok, best,
-                                          stage == 0 ? P.gmap_orig[kind] : P.map_orig[kind]);
+                                          stage == 0 ? P.gmap_orig[kind] : map.orig());
         if (!stored) {
-            if (stage == 0 && P.map_m[kind] > 20)
+            if (stage == 0 && map.m() > 20)
                 P.hard_list[w].w = e.w | HARD_REDO;  // fall back to the local map (:283 / :702)
             else
                 store_none(P, kind, b, i);
@@ -1110,27 +1172,21 @@ static int build_grid_into(mml_ctx* ctx, MmlGrid& g, float4* orig, const float* 
     return MML_OK;
 }
 
-int mml_build_grid(mml_ctx* ctx, int kind, const float* h_xyz, int m) {
+int mml_build_grid(mml_ctx* ctx, const MmlMapRef& map, int kind, const float* h_xyz, int m) {
     MML_REQUIRE(kind == 0 || kind == 1, MML_ERR_INVALID, "map kind must be 0 (corner) or 1 (surf)");
     MML_REQUIRE(m >= 0 && m <= ctx->MM, MML_ERR_CAPACITY, "map larger than max_map_points");
-    ctx->have_map[kind] = false;
-    ctx->grid[kind].tags = nullptr;
-    int rc = build_grid_into(ctx, ctx->grid[kind], ctx->map_tmp + (size_t)kind * ctx->MM, h_xyz, m,
+    map.have_map[kind] = false;
+    map.grid[kind].tags = nullptr;
+    ctx->banks.dirty = true;  // (the descriptor table of a context with banks holds a copy of this grid)
+    int rc = build_grid_into(ctx, map.grid[kind], map.map_tmp + (size_t)kind * ctx->MM, h_xyz, m,
                              kind == 0 ? ctx->cfg.cell_corner : ctx->cfg.cell_surf, nullptr);
-    if (rc == MML_OK) ctx->have_map[kind] = true;
+    if (rc == MML_OK) map.have_map[kind] = true;
     return rc;
 }
 
-// Same, for a cloud that is already on the device in map_tmp + kind * MM (device-side map upkeep).
-int mml_build_grid_device(mml_ctx* ctx, int kind, int m) {
-    MML_REQUIRE(kind == 0 || kind == 1, MML_ERR_INVALID, "map kind must be 0 (corner) or 1 (surf)");
-    MML_REQUIRE(m >= 0 && m <= ctx->MM, MML_ERR_CAPACITY, "map larger than max_map_points");
-    ctx->have_map[kind] = false;
-    ctx->grid[kind].tags = nullptr;
-    int rc = build_grid_into(ctx, ctx->grid[kind], ctx->map_tmp + (size_t)kind * ctx->MM, nullptr, m,
-                             kind == 0 ? ctx->cfg.cell_corner : ctx->cfg.cell_surf, nullptr);
-    if (rc == MML_OK) ctx->have_map[kind] = true;
-    return rc;
+// Same, for a cloud that is already on the device in the map's map_tmp + kind * MM (device-side map upkeep).
+int mml_build_grid_device(mml_ctx* ctx, const MmlMapRef& map, int kind, int m) {
+    return mml_build_grid(ctx, map, kind, nullptr, m);
 }
 
 // a12: the global map handed to Estimate() (Estimator.cpp:1170-1184) as one concatenated cloud with the cube index
@@ -1208,8 +1264,9 @@ int mml_launch_knn5(mml_ctx* ctx, int kind, const float* d_q, int nq, float max_
     return MML_OK;
 }
 
-int mml_launch_associate(mml_ctx* ctx, int first, int count, const double* d_Twl, double thres_dist, bool with_stats) {
-    AssocParams P;
+// the association chain of one launch form: BANKED when a slot of the launch is bound to a map bank
+template <bool BANKED>
+static int launch_associate(mml_ctx* ctx, AssocArgs<BANKED>& P, int first, int count, const double* d_Twl, double thres_dist) {
     P.first = first;
     P.B = ctx->B;
     P.MF = ctx->MF;
@@ -1248,12 +1305,12 @@ int mml_launch_associate(mml_ctx* ctx, int first, int count, const double* d_Twl
     {
         MmlStageScope t(ctx, "associate");
         hipLaunchKernelGGL(k_assoc_prefix, dim3(1), dim3(AP_THREADS), 0, MML_STREAM(ctx), first, count, ctx->B, ctx->ft_n, work_off, P.hard_count);
-        hipLaunchKernelGGL(k_associate, dim3(4096), dim3(128), 0, MML_STREAM(ctx), P);
+        hipLaunchKernelGGL(k_associate<BANKED>, dim3(4096), dim3(128), 0, MML_STREAM(ctx), P);
     }
     {
         // (before the far-query fit: that one overwrites the parked records of its features with their factors)
         MmlStageScope t(ctx, "associate_fit");
-        hipLaunchKernelGGL(k_associate_fit_all, dim3(4096), dim3(128), 0, MML_STREAM(ctx), P);
+        hipLaunchKernelGGL(k_associate_fit_all<BANKED>, dim3(4096), dim3(128), 0, MML_STREAM(ctx), P);
     }
     {
         MmlStageScope t(ctx, "associate_far");
@@ -1265,21 +1322,39 @@ int mml_launch_associate(mml_ctx* ctx, int first, int count, const double* d_Twl
         // 8: 0.153, 4: 0.147 / 0.113, 2: 0.142 / 0.153, 1: 0.185 ms.
         auto launch_hard = [&](int round) {
             if (!P.fresh_all)
-                hipLaunchKernelGGL(k_associate_hard<4>, dim3(1024), dim3(256), 0, MML_STREAM(ctx), P, round);
+                hipLaunchKernelGGL((k_associate_hard<4, BANKED>), dim3(1024), dim3(256), 0, MML_STREAM(ctx), P, round);
             else if (count <= 4)
-                hipLaunchKernelGGL(k_associate_hard<64>, dim3(2048), dim3(256), 0, MML_STREAM(ctx), P, round);
+                hipLaunchKernelGGL((k_associate_hard<64, BANKED>), dim3(2048), dim3(256), 0, MML_STREAM(ctx), P, round);
             else
-                hipLaunchKernelGGL(k_associate_hard<32>, dim3(2048), dim3(256), 0, MML_STREAM(ctx), P, round);
+                hipLaunchKernelGGL((k_associate_hard<32, BANKED>), dim3(2048), dim3(256), 0, MML_STREAM(ctx), P, round);
         };
         launch_hard(0);
-        hipLaunchKernelGGL(k_associate_fit, dim3(512), dim3(128), 0, MML_STREAM(ctx), P, 0);
+        hipLaunchKernelGGL(k_associate_fit<BANKED>, dim3(512), dim3(128), 0, MML_STREAM(ctx), P, 0);
         if (ctx->have_gmap[0] || ctx->have_gmap[1]) {  // features whose cube neighbourhood did not yield a model
             launch_hard(1);
-            hipLaunchKernelGGL(k_associate_fit, dim3(512), dim3(128), 0, MML_STREAM(ctx), P, 1);
+            hipLaunchKernelGGL(k_associate_fit<BANKED>, dim3(512), dim3(128), 0, MML_STREAM(ctx), P, 1);
         }
     }
     for (int i = 0; i < count; ++i) ctx->stats_stale[first + i] = 1;
     MML_HIP(hipGetLastError());
+    return MML_OK;
+}
+
+int mml_launch_associate(mml_ctx* ctx, int first, int count, const double* d_Twl, double thres_dist, bool with_stats) {
+    int rc;
+    if (mml_any_bound(ctx, first, count)) {
+        // (the entry points bring the device copies up to date before they enqueue anything: mml_assoc_ready)
+        MML_REQUIRE(!ctx->banks.dirty && !ctx->have_gmap[0] && !ctx->have_gmap[1], MML_ERR_STATE,
+                    "association of a bound slot without mml_assoc_ready");
+        AssocArgs<true> P;
+        P.table = ctx->banks.d_table;
+        P.slot_bank = ctx->banks.d_slot_bank;
+        rc = launch_associate<true>(ctx, P, first, count, d_Twl, thres_dist);
+    } else {
+        AssocArgs<false> P;
+        rc = launch_associate<false>(ctx, P, first, count, d_Twl, thres_dist);
+    }
+    if (rc != MML_OK) return rc;
     if (with_stats) return mml_ensure_assoc_stats(ctx, first, count);
     return MML_OK;
 }

@@ -309,11 +309,11 @@ int mml_downsample_redo_overflow(mml_ctx* ctx, int first, int count, std::vector
     return MML_OK;
 }
 
-int mml_map_upkeep_increment(mml_ctx* ctx, int slot, const double* T_wl, int* n_out) {
+int mml_map_upkeep_increment(mml_ctx* ctx, const MmlMapRef& map, int slot, const double* T_wl, int* n_out) {
     hipStream_t s = MML_STREAM(ctx);
     constexpr int W = mml_ctx::LOCAL_WINDOW;
     const size_t ring_pts = (size_t)W * ctx->MF;
-    if (!ctx->ring_mem.present()) {
+    if (!ctx->ring_mem.present()) {  // (the context's ring comes with the scratch every map's upkeep uses)
         MML_HIP(hipStreamSynchronize(s));
         ctx->vox_cap = 0;
         const int rc0 = ctx->ring_mem.reserve(ctx, {mml_part(ctx->ring[0], ring_pts), mml_part(ctx->ring[1], ring_pts), mml_part(ctx->ring_cat, ring_pts),
@@ -321,36 +321,40 @@ int mml_map_upkeep_increment(mml_ctx* ctx, int slot, const double* T_wl, int* n_
         if (rc0 != MML_OK) return rc0;
         ctx->vox_cap = ring_pts;
     }
+    if (!map.ring_mem->present()) {  // a bank's ring
+        const int rc0 = map.ring_mem->reserve(ctx, {mml_part(map.ring[0], ring_pts), mml_part(map.ring[1], ring_pts)});
+        if (rc0 != MML_OK) return rc0;
+    }
     int* n_feat = reinterpret_cast<int*>(mml_stage_alloc(ctx, 1));  // pinned
     MML_HIP(hipMemcpyAsync(&n_feat[0], ctx->ft_n + 0 * ctx->B + slot, sizeof(int), hipMemcpyDeviceToHost, s));
     MML_HIP(hipMemcpyAsync(&n_feat[1], ctx->ft_n + 1 * ctx->B + slot, sizeof(int), hipMemcpyDeviceToHost, s));
     MML_HIP(hipStreamSynchronize(s));
     Tf12 T;
     memcpy(T.m, T_wl, sizeof(double) * 12);
-    const int Id = (int)(ctx->local_map_id % W);  // :1597
+    const int Id = (int)(*map.local_map_id % W);  // :1597
     for (int kind = 0; kind < 2; ++kind)  // both stacks are checked before any ring state changes
         MML_REQUIRE(n_feat[kind] >= 0 && n_feat[kind] <= ctx->MF, MML_ERR_STATE, "slot holds no down-sampled feature stack");
     for (int kind = 0; kind < 2; ++kind) {
         const int n = n_feat[kind];
         if (n)
             hipLaunchKernelGGL(k_to_world, dim3((n + 255) / 256), dim3(256), 0, s, ctx->ft_xyz[kind] + (size_t)slot * ctx->MF,
-                               n, T, ctx->ring[kind] + (size_t)Id * ctx->MF);
-        ctx->ring_n[kind][Id] = n;
+                               n, T, map.ring[kind] + (size_t)Id * ctx->MF);
+        map.ring_n[kind][Id] = n;
         RingOffsets R;
         R.off[0] = 0;
-        for (int i = 0; i < W; ++i) R.off[i + 1] = R.off[i] + ctx->ring_n[kind][i];
+        for (int i = 0; i < W; ++i) R.off[i + 1] = R.off[i] + map.ring_n[kind][i];
         const int total = R.off[W];
-        if (total) hipLaunchKernelGGL(k_concat, dim3(8, W), dim3(256), 0, s, ctx->ring[kind], ctx->MF, R, ctx->ring_cat);
+        if (total) hipLaunchKernelGGL(k_concat, dim3(8, W), dim3(256), 0, s, map.ring[kind], ctx->MF, R, ctx->ring_cat);
         int m = 0;
         int rc = voxel_filter_device(ctx, ctx->ring_cat, total, kind == 0 ? ctx->cfg.leaf_corner : ctx->cfg.leaf_surf,
-                                     ctx->map_tmp + (size_t)kind * ctx->MM, ctx->MM, &m);
+                                     map.map_tmp + (size_t)kind * ctx->MM, ctx->MM, &m);
         if (rc != MML_OK) return rc;
-        rc = mml_build_grid_device(ctx, kind, m);
+        rc = mml_build_grid_device(ctx, map, kind, m);
         if (rc != MML_OK) return rc;
-        ctx->local_map_n[kind] = m;
+        map.local_map_n[kind] = m;
         if (n_out) n_out[kind] = m;
     }
-    ctx->local_map_id++;  // :1642
+    ++*map.local_map_id;  // :1642
     MML_HIP(hipGetLastError());
     return MML_OK;
 }

@@ -61,6 +61,49 @@ struct MmlGrid {         // radix-sorted uniform grid over one map cloud (replac
     int ncell = 1;
 };
 
+// One more local map beside the context's own (mml_map_banks_create): the same state -- the two grids with their unsorted clouds,
+// the key-scan ring with its counts, localMapID, the two map sizes.  A bank that was never set is an empty map.
+#define MML_LOCAL_WINDOW 50  // localMapWindowSize, Estimator.h:326
+struct MmlMapBank {
+    MmlGrid grid[2];
+    bool have_map[2] = {true, true};
+    float4* map_tmp = nullptr;               // 2 x MM: the unsorted clouds
+    MmlGroup grid_mem;                       // owns grid[k].pts / cell_start and map_tmp
+    float4* ring[2] = {nullptr, nullptr};    // MML_LOCAL_WINDOW x MF each
+    MmlGroup ring_mem;                       // owns ring[2]; allocated by the bank's first increment
+    int ring_n[2][MML_LOCAL_WINDOW] = {};
+    long local_map_id = 0;
+    int local_map_n[2] = {0, 0};
+};
+// What the association kernels read of one local map of one kind: a row of the device-resident table of a context with banks.
+struct alignas(16) MmlMapDesc {
+    MmlGrid g;
+    const float4* orig;  // the unsorted cloud (index = original index)
+};
+static_assert(sizeof(MmlMapDesc) % 16 == 0 && sizeof(MmlMapDesc) / 4 <= 32, "a descriptor is read as dwords, at most 32");
+struct MmlBanks {
+    std::vector<MmlMapBank> bank;
+    std::vector<int> slot_bank;       // B: bank of every slot, -1 = the context's own map
+    int n_bound = 0;                  // slots with a bank
+    MmlMapDesc* d_table = nullptr;    // (banks + 1) x 2 kinds; row 0: the context's own map
+    int* d_slot_bank = nullptr;       // B
+    MmlGroup tab_mem;                 // owns the two
+    bool dirty = true;                // a grid or a binding changed since the device copies were written (mml_banks_refresh)
+    void release() {
+        for (MmlMapBank& b : bank) {
+            b.grid_mem.release();
+            b.ring_mem.release();
+        }
+        bank.clear();
+        slot_bank.clear();
+        tab_mem.release();
+        d_table = nullptr;
+        d_slot_bank = nullptr;
+        n_bound = 0;
+        dirty = true;
+    }
+};
+
 struct MmlStageTimer {
     std::string name;
     double total_ms = 0;
@@ -243,7 +286,7 @@ struct mml_ctx {
     int gmap_cap[2] = {0, 0};               // points the group of a kind is sized for
     int cen[3] = {10, 5, 10};  // laserCloudCen{Width,Height,Depth}_last (Map_Manager.h:113-115)
     // device-side local map upkeep (Estimator::MapIncrementLocal): ring of key scans' features in the world frame
-    static constexpr int LOCAL_WINDOW = 50;  // localMapWindowSize, Estimator.h:326
+    static constexpr int LOCAL_WINDOW = MML_LOCAL_WINDOW;
     float4* ring[2] = {nullptr, nullptr};    // LOCAL_WINDOW x MF each
     float4* ring_cat = nullptr;              // concatenation scratch, LOCAL_WINDOW x MF
     int* vox_flag = nullptr;                 // head flags / positions, 2 x (vox_cap + 1)
@@ -266,6 +309,7 @@ struct mml_ctx {
     MmlGroup cube_store;                       // owns gs_pts .. gs_keys, allocated by the first append / increment
     MmlStaging<char, false> wire_stage;      // raw message bytes on their way in / out (one call at a time; grows to the largest)
     int local_map_n[2] = {0, 0};
+    MmlBanks banks;                    // map banks (map_banks.hip): further local maps, and which slot is matched against which
     float4* map_tmp = nullptr;
     unsigned* map_keys = nullptr;
     unsigned* map_keys2 = nullptr;
@@ -309,6 +353,7 @@ struct mml_ctx {
         for (auto& t : seg_tmp) t.release();
         for (auto& g : ggrid_mem) g.release();
         ring_mem.release();
+        banks.release();
         cube_store.release();
         wire_stage.release();
         sort_tmp.release();
@@ -378,14 +423,46 @@ int mml_cloud_settle(mml_ctx* ctx, int first, int count);
 int mml_launch_downsample(mml_ctx* ctx, int first, int count);
 // labelled corner points per (slot, kind) that the LDS sort of k_voxel takes (surf: MML_VOXEL_LDS_CAP)
 inline int mml_voxel_cap_corner(const mml_ctx* ctx) { return (ctx->NT > 65536 || MML_VOXEL_LDS_CAP < 2048) ? MML_VOXEL_LDS_CAP : 2048; }
-int mml_build_grid(mml_ctx* ctx, int kind, const float* h_xyz, int m);
-int mml_build_grid_device(mml_ctx* ctx, int kind, int m);
+// The state of one local map, by reference: the context's own fields (mml_map_own) or a bank's (mml_map_bank).  Map upkeep and
+// the grid build take the map they work on as this parameter; the scratch they use (ring_cat, vox_flag, the sort buffers) is the
+// context's either way.
+struct MmlMapRef {
+    MmlGrid* grid;      // [2]
+    bool* have_map;     // [2]
+    float4* map_tmp;    // 2 x MM
+    float4** ring;      // [2]
+    MmlGroup* ring_mem;
+    int (*ring_n)[MML_LOCAL_WINDOW];  // [2]
+    long* local_map_id;
+    int* local_map_n;   // [2]
+};
+inline MmlMapRef mml_map_own(mml_ctx* c) {
+    return MmlMapRef{c->grid, c->have_map, c->map_tmp, c->ring, &c->ring_mem, c->ring_n, &c->local_map_id, c->local_map_n};
+}
+inline MmlMapRef mml_map_bank(mml_ctx* c, int bank) {
+    MmlMapBank& b = c->banks.bank[(size_t)bank];
+    return MmlMapRef{b.grid, b.have_map, b.map_tmp, b.ring, &b.ring_mem, b.ring_n, &b.local_map_id, b.local_map_n};
+}
+int mml_build_grid(mml_ctx* ctx, const MmlMapRef& map, int kind, const float* h_xyz, int m);
+int mml_build_grid_device(mml_ctx* ctx, const MmlMapRef& map, int kind, int m);
+inline int mml_build_grid(mml_ctx* ctx, int kind, const float* h_xyz, int m) { return mml_build_grid(ctx, mml_map_own(ctx), kind, h_xyz, m); }
+inline int mml_build_grid_device(mml_ctx* ctx, int kind, int m) { return mml_build_grid_device(ctx, mml_map_own(ctx), kind, m); }
+// map_banks.hip.  mml_assoc_ready: the state checks of a call that associates slots [first, first + count) -- an unbound slot needs
+// the context's two maps (`who` before both maps were set), a bound one no global map -- and the device copies of the descriptor
+// table and the bindings brought up to date (a drained context and one small copy, only after a change).
+int mml_assoc_ready(mml_ctx* ctx, int first, int count, const char* who);
+inline bool mml_any_bound(const mml_ctx* ctx, int first, int count) {
+    if (!ctx->banks.n_bound) return false;
+    for (int i = 0; i < count; ++i)
+        if (ctx->banks.slot_bank[(size_t)first + i] >= 0) return true;
+    return false;
+}
 // gicp.hip: mml_gicp_align_opts on clouds that are on the device already, for a caller that has made the context idle
 int mml_gicp_align_device(mml_ctx* ctx, const char* who, const float4* d_src, int n_src, const float4* d_tgt, int n_tgt,
                           const mml_gicp_opts* opts, float* T_inout, int* converged, mml_gicp_info* info);
 int mml_downsample_big(mml_ctx* ctx, int first, int count);
 int mml_downsample_redo_overflow(mml_ctx* ctx, int first, int count, std::vector<int>* redone);
-int mml_map_upkeep_increment(mml_ctx* ctx, int slot, const double* T_wl, int* n_out);
+int mml_map_upkeep_increment(mml_ctx* ctx, const MmlMapRef& map, int slot, const double* T_wl, int* n_out);
 int mml_build_global_grid(mml_ctx* ctx, int kind, const float* h_xyz, const int* h_cube, int m, const int* cen);
 int mml_build_global_grid_device(mml_ctx* ctx, int kind, const float4* d_pts, const uint16_t* d_tags, const int* d_cnt, int m,
                                  const int* cen);

@@ -84,6 +84,15 @@ class Context {
     mml_ctx* get() const { return ctx_; }
     const mml_config& config() const { return cfg_; }
 
+    // Map banks (include/mmloam_hip.h, "map banks"), for a host that replays several sequences in this context: n further local
+    // maps, the bank of every slot (-1: the context's own map, the one the Estimator below uses), and MapIncrementLocal for n
+    // distinct banks in one call (T_wl: n x 16, row-major; the sizes may be null).  Banked slots have no cube stage.
+    void map_banks(int n) { check(ctx_, mml_map_banks_create(ctx_, n), "map_banks"); }
+    void bind_banks(int first_slot, int count, const int* banks) { check(ctx_, mml_slot_bind_bank(ctx_, first_slot, count, banks), "bind_banks"); }
+    void bank_increment(int n, const int* banks, const int* slots, const double* T_wl, int* n_corner = nullptr, int* n_surf = nullptr) {
+        check(ctx_, mml_map_bank_increment(ctx_, n, banks, slots, T_wl, n_corner, n_surf), "bank_increment");
+    }
+
    private:
     mml_ctx* ctx_ = nullptr;
     mml_config cfg_;

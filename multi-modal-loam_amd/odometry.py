@@ -1,6 +1,7 @@
 """Host-side mirror of Estimator::EstimateLidarPose (Estimator.cpp:967-1140) for the live 1-frame mode: down-sample,
 Estimate against the local map, hand the pose back, apply the key-scan rule and grow the local map.  Every stage
-that touches points runs on the device through the C-ABI (mml_downsample, mml_estimate, mml_map_increment_local);
+that touches points runs on the device through the C-ABI (mml_downsample, mml_estimate, mml_map_increment_local;
+for n sequences in one context: the same with map banks, mml_slot_bind_bank and mml_map_bank_increment);
 this file only carries the control flow and the 4x4 / quaternion bookkeeping the reference does in Eigen.
 """
 import numpy as np
@@ -11,6 +12,74 @@ def _quat_to_matrix(q):
     return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
                      [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
                      [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+# ---- the per-sequence host steps of EstimateLidarPose, shared by LidarOdometry and BatchLidarOdometry.  `st` is whatever carries
+# one Estimator's bookkeeping as attributes (_sequence_init): the LidarOdometry itself, or one sequence of the batch class.
+def _sequence_init(st):
+    st.last_velo_update_pose = np.array([-1.0, -1.0, -1.0])       # Estimator.h:339-340
+    st.last_hori_update_pose = np.array([-1.0, -1.0, -1.0])
+    st.n_corner_local = 0
+    st.n_surf_local = 0
+    st.fail_detected = False
+    st.key_scans = 0
+    st.last_T = None                                              # transformTobeMapped the last estimate_lidar_pose ended with
+
+
+def _transform_to_be_mapped(exRbl, exPbl, P, Q):
+    T = np.eye(4)
+    R = _quat_to_matrix(Q)
+    T[:3, :3] = R @ exRbl
+    T[:3, 3] = R @ exPbl + P
+    return T
+
+
+def _local_map_gate(st):
+    """:1032-1035 (local-map half of the gate): Estimate runs only against a local map that holds something."""
+    return st.n_corner_local > 0 and st.n_surf_local > 100
+
+
+def _hand_back(st, lidar_mode, exRbl, exPbl, T, P, Q, is_degenerate, corner_cnt):
+    """The pose hand-back (:1041-1066) and the key-scan rule (:1070-1136) up to the map increment.  T: transformTobeMapped of
+    the prediction; P, Q: what Estimate returned (the prediction when it did not run).  Returns (T, grow)."""
+    if (lidar_mode == 1 and not is_degenerate and corner_cnt > 100) or (lidar_mode == 2 and corner_cnt > 50):
+        T = _transform_to_be_mapped(exRbl, exPbl, P, Q)           # :1041-1049
+    else:                                                         # :1050-1066: keep the predicted x / y, old z
+        T[:3, 3] = [P[0], P[1], T[2, 3]]
+    grow = False
+    if not is_degenerate:                                         # :1070-1136
+        # both modes compare with last_velo_update_pose (:1082, :1119); mode 1 writes last_hori_update_pose (:1115), which
+        # nothing reads -- the reference's bookkeeping as it is
+        d = st.last_velo_update_pose - T[:3, 3]
+        dis = float(np.float32(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])) if lidar_mode == 2 else float(d @ d)
+        grow = dis >= 0.5 and lidar_mode in (1, 2)
+    return T, grow
+
+
+def _grown(st, lidar_mode, T, sizes):
+    """After MapIncrementLocal at T (:1112, :1125-1130): the new map sizes and the key-scan pose."""
+    st.n_corner_local, st.n_surf_local = int(sizes[0]), int(sizes[1])
+    if lidar_mode == 2:
+        st.last_velo_update_pose = T[:3, 3].copy()
+    else:
+        st.last_hori_update_pose = T[:3, 3].copy()
+    st.key_scans += 1
+
+
+def _finish(st, T, is_degenerate):
+    st.fail_detected = is_degenerate                              # :1139
+    st.last_T = T
+
+
+def _adjacent_runs(items, slot_of):
+    """items sorted by slot and cut wherever the next slot is not the one after: one device call per run."""
+    runs = []
+    for it in sorted(items, key=slot_of):
+        if runs and slot_of(it) == slot_of(runs[-1][-1]) + 1:
+            runs[-1].append(it)
+        else:
+            runs.append([it])
+    return runs
 
 
 class LidarOdometry:
@@ -24,21 +93,11 @@ class LidarOdometry:
         self.exPbl = -1.0 * self.exRbl @ self.exTlb[:3, 3]            # :974
         self.lidar_mode = lidar_mode
         self.max_outer, self.inner_iters = max_outer, inner_iters
-        self.last_velo_update_pose = np.array([-1.0, -1.0, -1.0])     # Estimator.h:339-340
-        self.last_hori_update_pose = np.array([-1.0, -1.0, -1.0])
-        self.n_corner_local = 0
-        self.n_surf_local = 0
-        self.fail_detected = False
-        self.key_scans = 0
-        self.last_T = None                                            # transformTobeMapped the last estimate_lidar_pose ended with
+        _sequence_init(self)
         ctx.map_local_reset()
 
     def transform_to_be_mapped(self, P, Q):
-        T = np.eye(4)
-        R = _quat_to_matrix(Q)
-        T[:3, :3] = R @ self.exRbl
-        T[:3, 3] = R @ self.exPbl + P
-        return T
+        return _transform_to_be_mapped(self.exRbl, self.exPbl, P, Q)
 
     def estimate_lidar_pose(self, slot, P, Q):
         """P (3), Q (x, y, z, w): predicted body pose of the scan in `slot` (already extracted and undistorted).
@@ -50,31 +109,14 @@ class LidarOdometry:
         corner_cnt = ctx.scan_info(slot).fused_corner_num              # :990-996
         ctx.downsample(slot, 1)                                        # :1013-1024
         is_degenerate = False
-        if self.n_corner_local > 0 and self.n_surf_local > 100:        # :1032-1035 (local-map half of the gate)
+        if _local_map_gate(self):
             Pn, Qn, info = ctx.estimate(slot, 1, self.exTlb, P[None], Q[None], self.max_outer, self.inner_iters)
             P, Q = Pn[0], Qn[0]
             is_degenerate = bool(info[0].is_degenerate)
-        if (self.lidar_mode == 1 and not is_degenerate and corner_cnt > 100) or (self.lidar_mode == 2 and corner_cnt > 50):
-            T = self.transform_to_be_mapped(P, Q)                      # :1041-1049
-        else:                                                          # :1050-1066: keep the predicted x / y, old z
-            T[:3, 3] = [P[0], P[1], T[2, 3]]
-        grew = False
-        if not is_degenerate:                                          # :1070-1136
-            cur = T[:3, 3].copy()
-            # both modes compare with last_velo_update_pose (:1082, :1119); mode 1 writes last_hori_update_pose (:1115), which
-            # nothing reads -- the reference's bookkeeping as it is
-            d = self.last_velo_update_pose - cur
-            dis = float(np.float32(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])) if self.lidar_mode == 2 else float(d @ d)
-            if dis >= 0.5 and self.lidar_mode in (1, 2):
-                self.n_corner_local, self.n_surf_local = ctx.map_increment_local(slot, T)   # :1112, :1125-1130
-                if self.lidar_mode == 2:
-                    self.last_velo_update_pose = cur
-                else:
-                    self.last_hori_update_pose = cur
-                self.key_scans += 1
-                grew = True
-        self.fail_detected = is_degenerate                              # :1139
-        self.last_T = T
+        T, grew = _hand_back(self, self.lidar_mode, self.exRbl, self.exPbl, T, P, Q, is_degenerate, corner_cnt)
+        if grew:
+            _grown(self, self.lidar_mode, T, ctx.map_increment_local(slot, T))
+        _finish(self, T, is_degenerate)
         return P, Q, grew
 
     def registered_cloud(self, slot):
@@ -84,6 +126,81 @@ class LidarOdometry:
         if self.last_T is None:
             raise ValueError("registered_cloud needs an estimate_lidar_pose first")
         return self.ctx.cloud_download_registered(slot, 1, self.last_T)[0]
+
+
+class _Sequence:
+    """The bookkeeping of one sequence of a BatchLidarOdometry (the attributes _sequence_init sets)."""
+
+    def __init__(self):
+        _sequence_init(self)
+
+
+class BatchLidarOdometry:
+    """n LidarOdometry loops in lockstep in ONE context -- a fleet's bags, or one bag cut into segments, replayed offline.
+    Sequence w owns map bank w (Context.map_banks(n), created here; the context's own map is not used), so every sequence is
+    matched against and grows its own local map.  Per round of scans: one bind_banks and one downsample call per run of
+    adjacent slots, one estimate call per run of adjacent slots among the sequences whose bank passes the local-map gate, the
+    pose hand-back and the key-scan rule per sequence on the host (the functions LidarOdometry calls), and ONE bank_increment
+    call for the sequences that grew.  Every sequence reproduces what a LidarOdometry of its own on a fresh context produces.
+    The per-sequence state is in self.seq[w] (n_corner_local, n_surf_local, key_scans, fail_detected, last_T, ...).
+    Banked slots have no cube stage: the context must not hold a global cube map."""
+
+    def __init__(self, ctx, n, exTlb=None, lidar_mode=2, max_outer=5, inner_iters=10):
+        if n < 1:
+            raise ValueError("n must be at least 1")
+        self.ctx, self.n = ctx, n
+        self.exTlb = np.eye(4) if exTlb is None else np.asarray(exTlb, dtype=np.float64)
+        self.exRbl = self.exTlb[:3, :3].T.copy()
+        self.exPbl = -1.0 * self.exRbl @ self.exTlb[:3, 3]
+        self.lidar_mode = lidar_mode
+        self.max_outer, self.inner_iters = max_outer, inner_iters
+        self.seq = [_Sequence() for _ in range(n)]
+        self._bound = {}                                               # slot -> bank, as this object last bound it
+        ctx.map_banks(n)
+
+    @property
+    def key_scans(self):
+        return [st.key_scans for st in self.seq]
+
+    def estimate_lidar_pose(self, slots, P, Q):
+        """slots[w]: the slot that holds sequence w's scan (already extracted and undistorted), or None when the sequence has
+        no scan this round; P (n, 3), Q (n, 4; x, y, z, w): the predicted body poses.  No two sequences may share a slot.
+        Returns (P, Q, grew): the estimated poses (a sequence without a scan keeps its row) and one bool per sequence."""
+        ctx, n = self.ctx, self.n
+        if len(slots) != n:
+            raise ValueError("one slot (or None) per sequence (%d)" % n)
+        P = np.array(P, dtype=np.float64).reshape(n, 3)
+        Q = np.array(Q, dtype=np.float64).reshape(n, 4)
+        live = [w for w in range(n) if slots[w] is not None]
+        if len(set(slots[w] for w in live)) != len(live):
+            raise ValueError("two sequences share a slot")
+        slot_of = lambda w: slots[w]
+        runs = _adjacent_runs(live, slot_of)
+        for run in runs:                                               # the slots' banks, where they are not bound already
+            if any(self._bound.get(slots[w]) != w for w in run):
+                ctx.bind_banks(slots[run[0]], run)
+                self._bound.update((slots[w], w) for w in run)
+        T = {w: _transform_to_be_mapped(self.exRbl, self.exPbl, P[w], Q[w]) for w in live}       # :975-977
+        corner_cnt = {w: ctx.scan_info(slots[w]).fused_corner_num for w in live}                 # :990-996
+        for run in runs:
+            ctx.downsample(slots[run[0]], len(run))                                              # :1013-1024
+        degenerate = {w: False for w in live}
+        for run in _adjacent_runs([w for w in live if _local_map_gate(self.seq[w])], slot_of):
+            Pn, Qn, info = ctx.estimate(slots[run[0]], len(run), self.exTlb, P[run], Q[run], self.max_outer, self.inner_iters)
+            for i, w in enumerate(run):
+                P[w], Q[w] = Pn[i], Qn[i]
+                degenerate[w] = bool(info[i].is_degenerate)
+        grew = [False] * n
+        for w in live:
+            T[w], grew[w] = _hand_back(self.seq[w], self.lidar_mode, self.exRbl, self.exPbl, T[w], P[w], Q[w], degenerate[w], corner_cnt[w])
+        growing = [w for w in live if grew[w]]
+        if growing:
+            nc, ns = ctx.bank_increment(growing, [slots[w] for w in growing], np.stack([T[w] for w in growing]))
+            for i, w in enumerate(growing):
+                _grown(self.seq[w], self.lidar_mode, T[w], (nc[i], ns[i]))
+        for w in live:
+            _finish(self.seq[w], T[w], degenerate[w])
+        return P, Q, grew
 
 
 def _rotvec_from_quat(q):
