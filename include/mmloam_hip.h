@@ -658,9 +658,29 @@ int mml_map_set_global(mml_ctx* ctx, int kind, const float* xyz, const int* cube
  * so the factors mml_fullwindow_solve, mml_fullwindow_solve_batch and mml_fullwindow_marginalize_batch read, which are
  * the ones mml_associate left).  The result of a slot is bit-identical to that of the same call on a context whose own
  * map holds the bank's cloud.  With every slot of a call bound, the context's own map need not be set.
- * NO CUBE STAGE: banked slots are matched against their bank alone.  Binding a slot to a bank while a global cube map is
- * set (mml_map_set_global, mml_map_global_increment) returns MML_ERR_STATE, and so does a call that associates a bound
- * slot after one was set; nothing is changed in either case.
+ * CUBE STAGE: a bank has a global cube map of its own -- the MAP_MANAGER store and the copy Estimate() matches against, as
+ * the context has them (mml_map_set_global, mml_map_global_*).  A bound slot is matched against its bank's cube first
+ * (> 100 corner / > 50 surf points in the feature's cube) and falls back to the bank's local map, exactly as an unbound slot
+ * is against the context's own pair; a bank without a cube map is matched against its local map alone.  The context's OWN
+ * cube map and bound slots exclude each other: binding a slot to a bank while it is set (mml_map_set_global,
+ * mml_map_global_increment) returns MML_ERR_STATE, and so does a call that associates a bound slot after it was set; nothing
+ * is changed in either case.
+ * mml_map_bank_set_global: mml_map_set_global on bank `bank` (m = 0 removes that bank's cube map).
+ * mml_map_bank_global_append: mml_map_global_append for n DISTINCT banks, slot slots[i] at T_wl + 16 i into bank banks[i].
+ * mml_map_bank_global_increment: mml_map_global_increment for n DISTINCT banks, bank banks[i] at T_wl + 16 i; n_corner /
+ * n_surf: n live store sizes each, or NULL.  The banks are worked through one after the other (two to three host
+ * synchronisations per kind and bank); every bank ends bit-identical, the order inside every cube included, to the own
+ * cube store of a context with the same history.
+ * mml_map_bank_global_download / _reset: mml_map_global_download / _reset on bank `bank` (mml_map_bank_reset keeps its
+ * meaning: the local ring only).
+ * All five check every argument before the device is touched or anything changes: a NULL context and a bank out of range
+ * are MML_ERR_INVALID, a context without banks MML_ERR_STATE, a bank named twice in one append / increment
+ * MML_ERR_INVALID; an append of a slot without a down-sampled stack is MML_ERR_STATE for the whole call.
+ * Memory per bank for its cube map, from its first append / increment on: 72 bytes per point of max_map_points (the live
+ * store and its compaction twin) plus 2 x 16 x max_features x 16 bytes of pending clouds -- 37 748 736 + 4 194 304 bytes at
+ * max_map_points = 1 << 19 and max_features = 8192; the match copy is sized by need, 36 bytes per point it holds (at least
+ * 1024) plus 16 bytes per point of max_map_points for its cell table, per kind, from the first set_global / increment on.
+ * The upkeep's scratch is the context's and is shared by all banks.  mml_map_banks_create allocates none of it.
  * mml_slot_bank_get reads the bindings back (all -1 on a context without banks).
  * mml_map_bank_increment: mml_map_increment_local for n DISTINCT banks (a bank named twice is MML_ERR_INVALID, checked
  * with every other argument before anything changes): bank banks[i] takes the stacks of slot slots[i] at T_wl + 16 i.
@@ -675,6 +695,11 @@ int mml_map_bank_download(mml_ctx* ctx, int bank, int kind, float* xyz, int capa
 int mml_slot_bind_bank(mml_ctx* ctx, int first_slot, int count, const int* banks);
 int mml_slot_bank_get(mml_ctx* ctx, int first_slot, int count, int* banks);
 int mml_map_bank_increment(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl, int* n_corner, int* n_surf);
+int mml_map_bank_set_global(mml_ctx* ctx, int bank, int kind, const float* xyz, const int* cube, int m, const int* cen);
+int mml_map_bank_global_append(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl);
+int mml_map_bank_global_increment(mml_ctx* ctx, int n, const int* banks, const double* T_wl, int* n_corner, int* n_surf);
+int mml_map_bank_global_download(mml_ctx* ctx, int bank, int kind, float* xyz, int* cube, int capacity, int* n, int* cen);
+int mml_map_bank_global_reset(mml_ctx* ctx, int bank);
 
 /* Exact 5-NN against a local map (twin of kdtree->nearestKSearch(p, 5, idx, d2), Estimator.cpp:284,704):
  * q: nq x 3 host floats (already in the map frame); idx: nq x 5 (indices into the uploaded cloud,

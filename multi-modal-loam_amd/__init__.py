@@ -1183,6 +1183,12 @@ class Context:
                                              C.byref(n)))
         return out[:n.value]
 
+    def features_count(self, slot, kind):
+        """Points in the slot's down-sampled stack of `kind`, without the copy."""
+        n = C.c_int(0)
+        self._ck(lib().mml_features_download(self._h, C.c_int(slot), C.c_int(kind), None, C.c_int(0), C.byref(n)))
+        return n.value
+
     def features_upload(self, slot, kind, xyz):
         xyz = _f32(xyz).reshape(-1, 3)
         self._ck(lib().mml_features_upload(self._h, C.c_int(slot), C.c_int(kind), _p(xyz), C.c_int(len(xyz))))
@@ -1251,6 +1257,50 @@ class Context:
         nc, ns = np.zeros(max(len(b), 1), np.int32), np.zeros(max(len(b), 1), np.int32)
         self._ck(lib().mml_map_bank_increment(self._h, C.c_int(len(b)), _p(b), _p(s), _p(T), _p(nc), _p(ns)))
         return nc[:len(b)], ns[:len(b)]
+
+    # ---- a bank's global cube map: its own MAP_MANAGER store and match copy (include/mmloam_hip.h, "map banks") ----
+    def bank_set_global(self, bank, kind, xyz, cube, cen=None):
+        """map_set_global on bank `bank`; an empty cloud removes that bank's cube map."""
+        xyz = _f32(xyz).reshape(-1, 3)
+        cube = np.ascontiguousarray(cube, dtype=np.int32).reshape(-1)
+        if len(cube) != len(xyz):
+            raise ValueError("one cube index per point")
+        cen_p = None if cen is None else _p(np.ascontiguousarray(cen, dtype=np.int32))
+        self._ck(lib().mml_map_bank_set_global(self._h, C.c_int(bank), C.c_int(kind), _p(xyz), _p(cube), C.c_int(len(xyz)), cen_p))
+
+    def bank_global_append(self, banks, slots, T_wl):
+        """map_global_append for len(banks) distinct banks in one call: the stacks of slot slots[i] at T_wl[i] (4 x 4) go to
+        the pending clouds of bank banks[i]."""
+        b = np.ascontiguousarray(banks, dtype=np.int32).reshape(-1)
+        s = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        T = _f64(T_wl).reshape(-1, 16)
+        if not (len(b) == len(s) == len(T)):
+            raise ValueError("one slot and one pose per bank")
+        self._ck(lib().mml_map_bank_global_append(self._h, C.c_int(len(b)), _p(b), _p(s), _p(T)))
+
+    def bank_global_increment(self, banks, T_wl):
+        """map_global_increment for len(banks) distinct banks in one call, bank banks[i] at T_wl[i].  Returns the live (corner,
+        surf) store sizes, one pair of arrays entry per bank."""
+        b = np.ascontiguousarray(banks, dtype=np.int32).reshape(-1)
+        T = _f64(T_wl).reshape(-1, 16)
+        if len(b) != len(T):
+            raise ValueError("one pose per bank")
+        nc, ns = np.zeros(max(len(b), 1), np.int32), np.zeros(max(len(b), 1), np.int32)
+        self._ck(lib().mml_map_bank_global_increment(self._h, C.c_int(len(b)), _p(b), _p(T), _p(nc), _p(ns)))
+        return nc[:len(b)], ns[:len(b)]
+
+    def bank_global_download(self, bank, kind):
+        n = C.c_int(0)
+        cen = np.zeros(3, np.int32)
+        self._ck(lib().mml_map_bank_global_download(self._h, C.c_int(bank), C.c_int(kind), None, None, C.c_int(0), C.byref(n), _p(cen)))
+        xyz = np.zeros((max(n.value, 1), 3), np.float32)
+        cube = np.zeros(max(n.value, 1), np.int32)
+        self._ck(lib().mml_map_bank_global_download(self._h, C.c_int(bank), C.c_int(kind), _p(xyz), _p(cube), C.c_int(n.value), C.byref(n),
+                                                    _p(cen)))
+        return xyz[:n.value].copy(), cube[:n.value].copy(), cen
+
+    def bank_global_reset(self, bank):
+        self._ck(lib().mml_map_bank_global_reset(self._h, C.c_int(bank)))
 
     def map_global_append(self, slot, T_wl):
         self._ck(lib().mml_map_global_append(self._h, C.c_int(slot), _p(_f64(T_wl).reshape(16))))

@@ -1312,7 +1312,7 @@ int mml_map_global_append(mml_ctx* ctx, int slot, const double* T_wl) {
     MML_REQUIRE(T_wl, MML_ERR_INVALID, "null transform");
     int rc = mml_sync_all(ctx);
     if (rc != MML_OK) return rc;
-    return mml_cube_store_append(ctx, slot, T_wl);
+    return mml_cube_store_append(ctx, mml_cube_own(ctx), slot, T_wl);
 }
 
 int mml_map_global_increment(mml_ctx* ctx, const double* T_wl, int* n_corner, int* n_surf) {
@@ -1322,7 +1322,7 @@ int mml_map_global_increment(mml_ctx* ctx, const double* T_wl, int* n_corner, in
     int rc = mml_sync_all(ctx);
     if (rc != MML_OK) return rc;
     int n[2] = {0, 0};
-    rc = mml_cube_store_increment(ctx, T_wl, n);
+    rc = mml_cube_store_increment(ctx, mml_cube_own(ctx), T_wl, n);
     if (n_corner) *n_corner = n[0];
     if (n_surf) *n_surf = n[1];
     return rc;
@@ -1332,7 +1332,7 @@ int mml_map_global_download(mml_ctx* ctx, int kind, float* xyz, int* cube, int c
     if (!ctx) return MML_ERR_INVALID;
     MML_REQUIRE((kind == 0 || kind == 1) && n, MML_ERR_INVALID, "bad arguments");
     MML_HIP(hipSetDevice(ctx->device));
-    return mml_cube_store_download(ctx, kind, xyz, cube, capacity, n, cen);
+    return mml_cube_store_download(ctx, mml_cube_own(ctx), kind, xyz, cube, capacity, n, cen);
 }
 
 int mml_map_global_reset(mml_ctx* ctx) {
@@ -1340,7 +1340,7 @@ int mml_map_global_reset(mml_ctx* ctx) {
     MML_HIP(hipSetDevice(ctx->device));
     int rc = mml_sync_all(ctx);
     if (rc != MML_OK) return rc;
-    return mml_cube_store_reset(ctx);
+    return mml_cube_store_reset(ctx, mml_cube_own(ctx));
 }
 
 int mml_map_set_global(mml_ctx* ctx, int kind, const float* xyz, const int* cube, int m, const int* cen) {
@@ -1348,7 +1348,7 @@ int mml_map_set_global(mml_ctx* ctx, int kind, const float* xyz, const int* cube
     MML_REQUIRE(m >= 0 && (m == 0 || (xyz && cube)), MML_ERR_INVALID, "bad global map arguments");
     MML_HIP(hipSetDevice(ctx->device));
     mml_sync_all(ctx);
-    return mml_build_global_grid(ctx, kind, xyz, cube, m, cen);
+    return mml_build_global_grid(ctx, mml_cube_own(ctx), kind, xyz, cube, m, cen);
 }
 
 int mml_knn5(mml_ctx* ctx, int kind, const float* q, int nq, float max_d2, int* idx, float* d2) {

@@ -329,9 +329,10 @@ struct AssocParams {
 
 // The kernels' argument.  A launch without a bound slot takes AssocParams as it is: every slot is matched against P.g / P.map_orig /
 // P.map_m, which live in the kernel arguments.  A launch with a bound slot (BANKED, map banks) carries the device-resident
-// descriptor table -- row 2 * e + kind, e = 0 the context's own map, e = 1 + bank -- and the bank of every slot of the context;
-// there P.g / P.map_orig / P.map_m are not read, and no cube stage exists (P.have_g is 0: mml_assoc_ready refuses the launch
-// otherwise).
+// descriptor tables -- row 2 * e + kind, e = 0 the context's own map, e = 1 + bank: `table` the local maps, `cube_table` the
+// global cube maps -- and the bank of every slot of the context; there P.g / P.map_orig / P.map_m and P.gg / P.gmap_orig /
+// P.cube_cnt / P.have_g / P.cen are not read.  Entry 0 of cube_table has have_g = 0 (mml_assoc_ready refuses a launch with a bound
+// slot while the context's own cube map is set).
 template <bool BANKED>
 struct AssocArgs;
 template <>
@@ -339,6 +340,7 @@ struct AssocArgs<false> : AssocParams {};
 template <>
 struct AssocArgs<true> : AssocParams {
     const MmlMapDesc* table;
+    const MmlCubeDesc* cube_table;
     const int* slot_bank;  // B, indexed by the slot itself
 };
 static_assert(sizeof(AssocArgs<false>) == sizeof(AssocParams), "the unbanked kernels' argument block is AssocParams");
@@ -380,6 +382,57 @@ struct SlotMap<true, UNIFORM> {
     __device__ __forceinline__ int m() const { return d.g.m; }
     __device__ __forceinline__ const float4* orig() const { return d.orig; }
 };
+
+// The global cube map of kind `kind` that slot b is matched against first: the cube stage's twin of SlotMap<BANKED, true>, for the
+// block-uniform kernels.  Unbanked: the kernel arguments.  Banked: the slot's row of cube_table in scalar registers.
+template <bool BANKED>
+struct SlotCube;
+template <>
+struct SlotCube<false> {
+    const AssocParams& P;
+    int kind;
+    __device__ __forceinline__ SlotCube(const AssocArgs<false>& P_, int, int kind_) : P(P_), kind(kind_) {}
+    __device__ __forceinline__ const MmlGrid& grid(int ukind) const { return P.gg[ukind]; }
+    __device__ __forceinline__ const int* cen() const { return P.cen; }
+    __device__ __forceinline__ int have_g() const { return P.have_g[kind]; }
+    __device__ __forceinline__ const int* cube_cnt() const { return P.cube_cnt[kind]; }
+    __device__ __forceinline__ const float4* orig() const { return P.gmap_orig[kind]; }
+};
+template <>
+struct SlotCube<true> {
+    MmlCubeDesc d;
+    __device__ __forceinline__ SlotCube(const AssocArgs<true>& P, int b, int kind) {
+        constexpr int N = sizeof(MmlCubeDesc) / 4;
+        int w[N];
+        const int e = __builtin_amdgcn_readfirstlane(P.slot_bank[b]) + 1;
+        const int* src = reinterpret_cast<const int*>(P.cube_table + (2 * e + __builtin_amdgcn_readfirstlane(kind)));
+#pragma unroll
+        for (int j = 0; j < N; ++j) w[j] = __builtin_amdgcn_readfirstlane(src[j]);
+        __builtin_memcpy(&d, w, sizeof(d));
+    }
+    __device__ __forceinline__ const MmlGrid& grid(int) const { return d.g; }
+    __device__ __forceinline__ const int* cen() const { return d.cen; }
+    __device__ __forceinline__ int have_g() const { return d.have_g; }
+    __device__ __forceinline__ const int* cube_cnt() const { return d.cube_cnt; }
+    __device__ __forceinline__ const float4* orig() const { return d.orig; }
+};
+// The far-query kernels' reads, one entry per lane.  The grid a far query searches: the row of its stage (the grid leads both
+// row types); the unsorted cloud of its entry's cube map.
+__device__ __forceinline__ MmlGrid far_grid(const AssocArgs<true>& P, int b, int kind, int stage) {
+    constexpr int N = sizeof(MmlGrid) / 4;
+    const int r = 2 * (P.slot_bank[b] + 1) + kind;
+    const int* src = stage == 0 ? reinterpret_cast<const int*>(P.cube_table + r) : reinterpret_cast<const int*>(P.table + r);
+    int w[N];
+#pragma unroll
+    for (int j = 0; j < N; ++j) w[j] = src[j];
+    MmlGrid g;
+    __builtin_memcpy(&g, w, sizeof(g));
+    return g;
+}
+__device__ __forceinline__ const float4* far_cube_orig(const AssocArgs<false>& P, int, int kind) { return P.gmap_orig[kind]; }
+__device__ __forceinline__ const float4* far_cube_orig(const AssocArgs<true>& P, int b, int kind) {
+    return P.cube_table[2 * (P.slot_bank[b] + 1) + kind].orig;
+}
 
 __device__ __forceinline__ void tf_point(const double* T, double x, double y, double z, double& ox, double& oy,
                                          double& oz) {
@@ -772,6 +825,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MML_AW_SEAR
         const int i = (w - P.work_off[item]) * 128 + threadIdx.x;
         const int nf = P.ft_n[kind * P.B + b];
         const SlotMap<BANKED, true> map(P, b, kind);  // (in front of the first divergent branch: every lane takes part)
+        const SlotCube<BANKED> cmap(P, b, kind);
         if (i >= nf) continue;
         int4* rec = assoc_rec(P, kind, b, i);
         const double* T = P.Twl + 16 * slot;
@@ -781,9 +835,9 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MML_AW_SEAR
         tf_point(T, f.x, f.y, f.z, wx, wy, wz);
         const float sx = wx, sy = wy, sz = wz;
         // :192-196 / :621-625: features outside the 21 x 11 x 21 cube grid, or NaN after the transform, get no factor
-        const int cube = find_used_map(sx, sy, sz, P.cen);
+        const int cube = find_used_map(sx, sy, sz, cmap.cen());
         // stage 0: the cube's own cloud when it holds > 100 corner / > 50 surf points (:198, :627); stage 1: local map
-        const int stage = (cube != 5000 && P.have_g[kind] && P.cube_cnt[kind][cube] > (kind == 0 ? 100 : 50)) ? 0 : 1;
+        const int stage = (cube != 5000 && cmap.have_g() && cmap.cube_cnt()[cube] > (kind == 0 ? 100 : 50)) ? 0 : 1;
         if (cube == 5000 || isnan(sx) || isnan(sy) || isnan(sz) || (stage == 1 && !(map.m() > 20))) {  // (:283 / :702)
             rec[1] = make_int4(0, 0, REC_NONE, 0);
             continue;
@@ -804,7 +858,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MML_AW_SEAR
         bool done = false;
         int rmax = 0;
         if (stage == 0) {
-            const MmlGrid& g = P.gg[ukind];
+            const MmlGrid& g = cmap.grid(ukind);
             const KnnQuery q = knn_query(g, sx, sy, sz);
             rmax = (int)ceilf(sqrtf(P.thres) * g.inv_cell) + 1;
             done = scan_rings01(g, q, rmax, P.thres, k, cube);
@@ -844,6 +898,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MML_AW_FIT)
         const int i = (w - P.work_off[item]) * 128 + threadIdx.x;
         const int nf = P.ft_n[kind * P.B + b];
         const SlotMap<BANKED, true> map(P, b, kind);
+        const SlotCube<BANKED> cmap(P, b, kind);
         if (i >= nf) continue;
         const int4* rec = assoc_rec(P, kind, b, i);
         const int4 r0 = rec[0], r1 = rec[1];
@@ -867,7 +922,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(MML_AW_FIT)
         k.key[3] = knn_key(d5, r0.w);
         k.key[4] = knn_key(d5, r1.x);
         const bool ok = (double)d5 < P.thres_d;  // :201,285 / :631,705
-        const bool stored = fit_and_store(P, kind, b, i, f, T, sx, sy, sz, ok, k, stage == 0 ? P.gmap_orig[kind] : map.orig());
+        const bool stored = fit_and_store(P, kind, b, i, f, T, sx, sy, sz, ok, k, stage == 0 ? cmap.orig() : map.orig());
         if (!stored) {
             if (stage == 0 && map.m() > 20) {
                 const int hw = atomicAdd(P.hard_count, 1);
@@ -939,7 +994,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MML_AW_HARD
         // argument structs picked per lane is re-read from memory at every use)
         MmlGrid g = P.g[0];
         if constexpr (BANKED) {
-            g = SlotMap<true, false>(P, b, kind).d.g;  // the entry's slot names the map (a lane without an entry: that of P.first)
+            g = far_grid(P, b, kind, stage);  // the entry's slot and stage name the row (a lane without an entry: the local map of P.first)
         } else {
             const bool k1 = kind == 1, s0 = stage == 0;
             const MmlGrid &a = P.g[1], &c = P.gg[0], &d = P.gg[1];
@@ -1026,7 +1081,7 @@ __global__ __launch_bounds__(128) void k_associate_fit(AssocArgs<BANKED> P, int 
         const SlotMap<BANKED, false> map(P, b, kind);
         const bool ok = (double)knn_d(best, 4) < P.thres_d;
         const bool stored = fit_and_store(P, kind, b, i, f, P.Twl + 16 * slot, sx, sy, sz, ok, best,
-                                          stage == 0 ? P.gmap_orig[kind] : map.orig());
+                                          stage == 0 ? far_cube_orig(P, b, kind) : map.orig());
         if (!stored) {
             if (stage == 0 && map.m() > 20)
                 P.hard_list[w].w = e.w | HARD_REDO;  // fall back to the local map (:283 / :702)
@@ -1191,31 +1246,33 @@ int mml_build_grid_device(mml_ctx* ctx, const MmlMapRef& map, int kind, int m) {
 
 // a12: the global map handed to Estimate() (Estimator.cpp:1170-1184) as one concatenated cloud with the cube index
 // (ToIndex) of every point.  The per-cube kd-trees become one grid whose points carry their cube as a tag.
-static int ensure_global_capacity(mml_ctx* ctx, int kind, int m) {
-    MmlGrid& g = ctx->ggrid[kind];
-    if (m <= ctx->gmap_cap[kind] && ctx->ggrid_mem[kind].present()) return MML_OK;
+static int ensure_global_capacity(mml_ctx* ctx, MmlCubeMatch& G, int kind, int m) {
+    MmlGrid& g = G.ggrid[kind];
+    if (m <= G.gmap_cap[kind] && G.ggrid_mem[kind].present()) return MML_OK;
     MML_HIP(hipStreamSynchronize(MML_STREAM(ctx)));
     const size_t cap = (size_t)(m > 1024 ? m : 1024);
-    ctx->gmap_cap[kind] = 0;
+    G.gmap_cap[kind] = 0;
     // (the cube counts are rewritten by both callers, so they may move with the rest)
-    const int rc = ctx->ggrid_mem[kind].reserve(
+    const int rc = G.ggrid_mem[kind].reserve(
         ctx, {mml_part(g.pts, cap), mml_part(g.cell_start, 4 * (size_t)ctx->MM + 4096 + 2), mml_part(g.tags, cap),
-              mml_part(ctx->gmap_orig[kind], cap), mml_part(ctx->gtag_orig[kind], cap), mml_part(ctx->cube_cnt[kind], 4851)});
-    if (rc == MML_OK) ctx->gmap_cap[kind] = (int)cap;
+              mml_part(G.gmap_orig[kind], cap), mml_part(G.gtag_orig[kind], cap), mml_part(G.cube_cnt[kind], 4851)});
+    if (rc == MML_OK) G.gmap_cap[kind] = (int)cap;
     return rc;
 }
 
-int mml_build_global_grid(mml_ctx* ctx, int kind, const float* h_xyz, const int* h_cube, int m, const int* cen) {
+int mml_build_global_grid(mml_ctx* ctx, const MmlCubeRef& cube, int kind, const float* h_xyz, const int* h_cube, int m, const int* cen) {
+    MmlCubeMatch& G = *cube.match;
     MML_REQUIRE(kind == 0 || kind == 1, MML_ERR_INVALID, "map kind must be 0 (corner) or 1 (surf)");
     MML_REQUIRE(m >= 0 && m <= ctx->MM, MML_ERR_CAPACITY, "global map larger than max_map_points");
     hipStream_t s = MML_STREAM(ctx);
-    ctx->have_gmap[kind] = false;
+    G.have_gmap[kind] = false;
+    ctx->banks.dirty = true;  // (the cube table of a context with banks holds a copy of this map's row)
     if (cen) {
-        ctx->cen[0] = cen[0];
-        ctx->cen[1] = cen[1];
-        ctx->cen[2] = cen[2];
+        G.cen[0] = cen[0];
+        G.cen[1] = cen[1];
+        G.cen[2] = cen[2];
     }
-    int rc = ensure_global_capacity(ctx, kind, m);
+    int rc = ensure_global_capacity(ctx, G, kind, m);
     if (rc != MML_OK) return rc;
     std::vector<uint16_t> tags((size_t)(m ? m : 1));
     std::vector<int> cnt(4851, 0);
@@ -1224,35 +1281,37 @@ int mml_build_global_grid(mml_ctx* ctx, int kind, const float* h_xyz, const int*
         tags[i] = (uint16_t)h_cube[i];
         cnt[h_cube[i]]++;
     }
-    MML_HIP(hipMemcpyAsync(ctx->cube_cnt[kind], cnt.data(), sizeof(int) * 4851, hipMemcpyHostToDevice, s));
-    if (m) MML_HIP(hipMemcpyAsync(ctx->gtag_orig[kind], tags.data(), sizeof(uint16_t) * (size_t)m, hipMemcpyHostToDevice, s));
+    MML_HIP(hipMemcpyAsync(G.cube_cnt[kind], cnt.data(), sizeof(int) * 4851, hipMemcpyHostToDevice, s));
+    if (m) MML_HIP(hipMemcpyAsync(G.gtag_orig[kind], tags.data(), sizeof(uint16_t) * (size_t)m, hipMemcpyHostToDevice, s));
     MML_HIP(hipStreamSynchronize(s));
-    rc = build_grid_into(ctx, ctx->ggrid[kind], ctx->gmap_orig[kind], h_xyz, m,
-                         kind == 0 ? ctx->cfg.cell_corner : ctx->cfg.cell_surf, ctx->gtag_orig[kind]);
-    if (rc == MML_OK) ctx->have_gmap[kind] = m > 0;
+    rc = build_grid_into(ctx, G.ggrid[kind], G.gmap_orig[kind], h_xyz, m,
+                         kind == 0 ? ctx->cfg.cell_corner : ctx->cfg.cell_surf, G.gtag_orig[kind]);
+    if (rc == MML_OK) G.have_gmap[kind] = m > 0;
     return rc;
 }
 
 // Same from device arrays (device-side cube store, map_global.hip): points, their cube tags and the 4851 cube counts.
-int mml_build_global_grid_device(mml_ctx* ctx, int kind, const float4* d_pts, const uint16_t* d_tags, const int* d_cnt, int m,
-                                 const int* cen) {
+int mml_build_global_grid_device(mml_ctx* ctx, const MmlCubeRef& cube, int kind, const float4* d_pts, const uint16_t* d_tags, const int* d_cnt,
+                                 int m, const int* cen) {
+    MmlCubeMatch& G = *cube.match;
     MML_REQUIRE(kind == 0 || kind == 1, MML_ERR_INVALID, "map kind must be 0 (corner) or 1 (surf)");
     MML_REQUIRE(m >= 0 && m <= ctx->MM, MML_ERR_CAPACITY, "global map larger than max_map_points");
     hipStream_t s = MML_STREAM(ctx);
-    ctx->have_gmap[kind] = false;
-    ctx->cen[0] = cen[0];
-    ctx->cen[1] = cen[1];
-    ctx->cen[2] = cen[2];
-    int rc = ensure_global_capacity(ctx, kind, m);
+    G.have_gmap[kind] = false;
+    ctx->banks.dirty = true;  // (the cube table of a context with banks holds a copy of this map's row)
+    G.cen[0] = cen[0];
+    G.cen[1] = cen[1];
+    G.cen[2] = cen[2];
+    int rc = ensure_global_capacity(ctx, G, kind, m);
     if (rc != MML_OK) return rc;
-    MML_HIP(hipMemcpyAsync(ctx->cube_cnt[kind], d_cnt, sizeof(int) * 4851, hipMemcpyDeviceToDevice, s));
+    MML_HIP(hipMemcpyAsync(G.cube_cnt[kind], d_cnt, sizeof(int) * 4851, hipMemcpyDeviceToDevice, s));
     if (m) {
-        MML_HIP(hipMemcpyAsync(ctx->gmap_orig[kind], d_pts, sizeof(float4) * (size_t)m, hipMemcpyDeviceToDevice, s));
-        MML_HIP(hipMemcpyAsync(ctx->gtag_orig[kind], d_tags, sizeof(uint16_t) * (size_t)m, hipMemcpyDeviceToDevice, s));
+        MML_HIP(hipMemcpyAsync(G.gmap_orig[kind], d_pts, sizeof(float4) * (size_t)m, hipMemcpyDeviceToDevice, s));
+        MML_HIP(hipMemcpyAsync(G.gtag_orig[kind], d_tags, sizeof(uint16_t) * (size_t)m, hipMemcpyDeviceToDevice, s));
     }
-    rc = build_grid_into(ctx, ctx->ggrid[kind], ctx->gmap_orig[kind], nullptr, m,
-                         kind == 0 ? ctx->cfg.cell_corner : ctx->cfg.cell_surf, ctx->gtag_orig[kind]);
-    if (rc == MML_OK) ctx->have_gmap[kind] = m > 0;
+    rc = build_grid_into(ctx, G.ggrid[kind], G.gmap_orig[kind], nullptr, m,
+                         kind == 0 ? ctx->cfg.cell_corner : ctx->cfg.cell_surf, G.gtag_orig[kind]);
+    if (rc == MML_OK) G.have_gmap[kind] = m > 0;
     return rc;
 }
 
@@ -1265,8 +1324,9 @@ int mml_launch_knn5(mml_ctx* ctx, int kind, const float* d_q, int nq, float max_
 }
 
 // the association chain of one launch form: BANKED when a slot of the launch is bound to a map bank
+// second_round: some slot of the launch has a cube map to fall back from (the context's own; banked: that of a bound bank)
 template <bool BANKED>
-static int launch_associate(mml_ctx* ctx, AssocArgs<BANKED>& P, int first, int count, const double* d_Twl, double thres_dist) {
+static int launch_associate(mml_ctx* ctx, AssocArgs<BANKED>& P, int first, int count, const double* d_Twl, double thres_dist, bool second_round) {
     P.first = first;
     P.B = ctx->B;
     P.MF = ctx->MF;
@@ -1277,14 +1337,14 @@ static int launch_associate(mml_ctx* ctx, AssocArgs<BANKED>& P, int first, int c
         P.map_m[k] = ctx->grid[k].m;
     }
     for (int k = 0; k < 2; ++k) {
-        P.gg[k] = ctx->ggrid[k];
-        P.gmap_orig[k] = ctx->gmap_orig[k];
-        P.cube_cnt[k] = ctx->cube_cnt[k];
-        P.have_g[k] = ctx->have_gmap[k] ? 1 : 0;
+        P.gg[k] = ctx->cmatch.ggrid[k];
+        P.gmap_orig[k] = ctx->cmatch.gmap_orig[k];
+        P.cube_cnt[k] = ctx->cmatch.cube_cnt[k];
+        P.have_g[k] = ctx->cmatch.have_gmap[k] ? 1 : 0;
     }
-    P.cen[0] = ctx->cen[0];
-    P.cen[1] = ctx->cen[1];
-    P.cen[2] = ctx->cen[2];
+    P.cen[0] = ctx->cmatch.cen[0];
+    P.cen[1] = ctx->cmatch.cen[1];
+    P.cen[2] = ctx->cmatch.cen[2];
     P.ft_n = ctx->ft_n;
     P.lf = ctx->lf;
     P.pf = ctx->pf;
@@ -1330,7 +1390,7 @@ static int launch_associate(mml_ctx* ctx, AssocArgs<BANKED>& P, int first, int c
         };
         launch_hard(0);
         hipLaunchKernelGGL(k_associate_fit<BANKED>, dim3(512), dim3(128), 0, MML_STREAM(ctx), P, 0);
-        if (ctx->have_gmap[0] || ctx->have_gmap[1]) {  // features whose cube neighbourhood did not yield a model
+        if (second_round) {  // features whose cube neighbourhood did not yield a model
             launch_hard(1);
             hipLaunchKernelGGL(k_associate_fit<BANKED>, dim3(512), dim3(128), 0, MML_STREAM(ctx), P, 1);
         }
@@ -1344,15 +1404,21 @@ int mml_launch_associate(mml_ctx* ctx, int first, int count, const double* d_Twl
     int rc;
     if (mml_any_bound(ctx, first, count)) {
         // (the entry points bring the device copies up to date before they enqueue anything: mml_assoc_ready)
-        MML_REQUIRE(!ctx->banks.dirty && !ctx->have_gmap[0] && !ctx->have_gmap[1], MML_ERR_STATE,
+        MML_REQUIRE(!ctx->banks.dirty && !ctx->cmatch.have_gmap[0] && !ctx->cmatch.have_gmap[1], MML_ERR_STATE,
                     "association of a bound slot without mml_assoc_ready");
+        bool cube = false;
+        for (int i = 0; i < count; ++i) {
+            const int bank = ctx->banks.slot_bank[(size_t)first + i];
+            if (bank >= 0) cube = cube || ctx->banks.bank[(size_t)bank].cmatch.have_gmap[0] || ctx->banks.bank[(size_t)bank].cmatch.have_gmap[1];
+        }
         AssocArgs<true> P;
         P.table = ctx->banks.d_table;
+        P.cube_table = ctx->banks.d_cube_table;
         P.slot_bank = ctx->banks.d_slot_bank;
-        rc = launch_associate<true>(ctx, P, first, count, d_Twl, thres_dist);
+        rc = launch_associate<true>(ctx, P, first, count, d_Twl, thres_dist, cube);
     } else {
         AssocArgs<false> P;
-        rc = launch_associate<false>(ctx, P, first, count, d_Twl, thres_dist);
+        rc = launch_associate<false>(ctx, P, first, count, d_Twl, thres_dist, ctx->cmatch.have_gmap[0] || ctx->cmatch.have_gmap[1]);
     }
     if (rc != MML_OK) return rc;
     if (with_stats) return mml_ensure_assoc_stats(ctx, first, count);

@@ -1,9 +1,11 @@
 // map_banks.hip -- map banks: N further local maps per context, and which scan slot is matched against which.
 //   A bank holds what the context's own local map holds (MmlMapBank, mml_internal.h); set, increment, reset and download run
 //   the code of the single-map calls on the bank's state (MmlMapRef).  The association kernels of a launch with a bound slot read
-//   the maps' grid descriptors from a device-resident table, (banks + 1) rows x 2 kinds, through the per-slot bank array
-//   (map_assoc.hip, the BANKED forms); this file keeps the two device arrays equal to the host's state.
-//   Banked slots have no cube stage: binding and a global cube map exclude each other.
+//   the maps' grid descriptors from two device-resident tables, (banks + 1) rows x 2 kinds each -- the local maps and the global
+//   cube maps --, through the per-slot bank array (map_assoc.hip, the BANKED forms); this file keeps the three device arrays
+//   equal to the host's state.
+//   A bank has its own global cube map (MmlCubeMatch / MmlCubeLive, mml_internal.h): the mml_map_bank_global_* calls run the code
+//   of the own-map calls on it (MmlCubeRef), n banks in a loop.  The context's OWN cube map and a bound slot exclude each other.
 #include <string.h>
 
 #include <algorithm>
@@ -30,6 +32,20 @@ int check_slot_range(mml_ctx* ctx, int first, int count) {
     return MML_OK;
 }
 
+// n banks (and, where given, n slots) in range, no bank twice: the argument checks of the calls that work n banks through
+int check_distinct_banks(mml_ctx* ctx, int n, const int* banks, const int* slots, const char* who) {
+    for (int i = 0; i < n; ++i) {
+        int rc = check_bank(ctx, banks[i]);
+        if (rc == MML_OK && slots) rc = check_slot_range(ctx, slots[i], 1);
+        if (rc != MML_OK) return rc;
+    }
+    std::vector<int> seen(banks, banks + n);
+    std::sort(seen.begin(), seen.end());
+    const auto dup = std::adjacent_find(seen.begin(), seen.end());
+    if (dup != seen.end()) return mml_refuse(ctx, MML_ERR_INVALID, "map bank %d appears twice in one %s", *dup, who);
+    return MML_OK;
+}
+
 }  // namespace
 
 int mml_assoc_ready(mml_ctx* ctx, int first, int count, const char* who) {
@@ -41,8 +57,8 @@ int mml_assoc_ready(mml_ctx* ctx, int first, int count, const char* who) {
             if (!(ctx->have_map[0] && ctx->have_map[1])) return mml_refuse(ctx, MML_ERR_STATE, "%s before both maps were set", who);
             continue;
         }
-        if (ctx->have_gmap[0] || ctx->have_gmap[1])
-            return mml_refuse(ctx, MML_ERR_STATE, "%s: slot %d is bound to map bank %d and a global cube map is set (banked slots have no cube stage)",
+        if (ctx->cmatch.have_gmap[0] || ctx->cmatch.have_gmap[1])
+            return mml_refuse(ctx, MML_ERR_STATE, "%s: slot %d is bound to map bank %d and the context's own global cube map is set (a bank has its own)",
                               who, first + i, bank);
         bound = true;
     }
@@ -52,8 +68,17 @@ int mml_assoc_ready(mml_ctx* ctx, int first, int count, const char* who) {
     if (rc != MML_OK) return rc;
     const size_t rows = 2 * (K.bank.size() + 1);
     std::vector<MmlMapDesc> t(rows);
+    std::vector<MmlCubeDesc> tc(rows);
     for (size_t e = 0; e <= K.bank.size(); ++e)
         for (int k = 0; k < 2; ++k) {
+            const MmlCubeMatch& G = e == 0 ? ctx->cmatch : K.bank[e - 1].cmatch;
+            MmlCubeDesc& c = tc[2 * e + k];
+            memset(static_cast<void*>(&c), 0, sizeof(c));
+            c.g = G.ggrid[k];
+            c.orig = G.gmap_orig[k];
+            c.cube_cnt = G.cube_cnt[k];
+            c.have_g = (e > 0 && G.have_gmap[k]) ? 1 : 0;  // (entry 0: never, the exclusion rule above)
+            for (int a = 0; a < 3; ++a) c.cen[a] = G.cen[a];
             MmlMapDesc& d = t[2 * e + k];
             memset(static_cast<void*>(&d), 0, sizeof(d));  // (the padding too: the rows are compared and copied as bytes)
             d.g = e == 0 ? ctx->grid[k] : K.bank[e - 1].grid[k];
@@ -62,8 +87,9 @@ int mml_assoc_ready(mml_ctx* ctx, int first, int count, const char* who) {
         }
     hipStream_t s = ctx->streams[0];
     MML_HIP(hipMemcpyAsync(K.d_table, t.data(), sizeof(MmlMapDesc) * rows, hipMemcpyHostToDevice, s));
+    MML_HIP(hipMemcpyAsync(K.d_cube_table, tc.data(), sizeof(MmlCubeDesc) * rows, hipMemcpyHostToDevice, s));
     MML_HIP(hipMemcpyAsync(K.d_slot_bank, K.slot_bank.data(), sizeof(int) * (size_t)ctx->B, hipMemcpyHostToDevice, s));
-    MML_HIP(hipStreamSynchronize(s));  // (`t` goes out of scope)
+    MML_HIP(hipStreamSynchronize(s));  // (`t` and `tc` go out of scope)
     K.dirty = false;
     return MML_OK;
 }
@@ -83,7 +109,8 @@ int mml_map_banks_create(mml_ctx* ctx, int n_banks) {
     K.n_bound = 0;
     K.dirty = true;
     const size_t MM = (size_t)ctx->MM;
-    rc = K.tab_mem.reserve(ctx, {mml_part(K.d_table, 2 * ((size_t)n_banks + 1)), mml_part(K.d_slot_bank, (size_t)ctx->B)});
+    rc = K.tab_mem.reserve(ctx, {mml_part(K.d_table, 2 * ((size_t)n_banks + 1)), mml_part(K.d_cube_table, 2 * ((size_t)n_banks + 1)),
+                                 mml_part(K.d_slot_bank, (size_t)ctx->B)});
     for (int b = 0; b < n_banks && rc == MML_OK; ++b) {
         MmlMapBank& m = K.bank[(size_t)b];
         rc = m.grid_mem.reserve(ctx, {mml_part(m.grid[0].pts, MM), mml_part(m.grid[0].cell_start, 4 * MM + 4096 + 2), mml_part(m.grid[1].pts, MM),
@@ -158,8 +185,8 @@ int mml_slot_bind_bank(mml_ctx* ctx, int first_slot, int count, const int* banks
             return mml_refuse(ctx, MML_ERR_INVALID, "slot %d: map bank %d outside [-1, %d)", first_slot + i, banks[i], n);
         any = any || banks[i] >= 0;
     }
-    if (any && (ctx->have_gmap[0] || ctx->have_gmap[1]))
-        return mml_refuse(ctx, MML_ERR_STATE, "a global cube map is set: banked slots have no cube stage");
+    if (any && (ctx->cmatch.have_gmap[0] || ctx->cmatch.have_gmap[1]))
+        return mml_refuse(ctx, MML_ERR_STATE, "the context's own global cube map is set: a bound slot is matched against its bank's");
     if (n == 0) return MML_OK;  // (all -1 on a context without banks: nothing to record)
     for (int i = 0; i < count; ++i) {
         int& cur = K.slot_bank[(size_t)first_slot + i];
@@ -184,18 +211,9 @@ int mml_map_bank_increment(mml_ctx* ctx, int n, const int* banks, const int* slo
     if (!ctx) return MML_ERR_INVALID;
     MML_REQUIRE(n >= 1 && banks && slots && T_wl, MML_ERR_INVALID, "bad arguments");
     // all arguments are checked before the device is touched or a bank changes
-    for (int i = 0; i < n; ++i) {
-        int rc = check_bank(ctx, banks[i]);
-        if (rc == MML_OK) rc = check_slot_range(ctx, slots[i], 1);
-        if (rc != MML_OK) return rc;
-    }
-    {
-        std::vector<int> seen(banks, banks + n);
-        std::sort(seen.begin(), seen.end());
-        const auto dup = std::adjacent_find(seen.begin(), seen.end());
-        if (dup != seen.end()) return mml_refuse(ctx, MML_ERR_INVALID, "map bank %d appears twice in one mml_map_bank_increment", *dup);
-    }
-    int rc = enter(ctx);
+    int rc = check_distinct_banks(ctx, n, banks, slots, "mml_map_bank_increment");
+    if (rc != MML_OK) return rc;
+    rc = enter(ctx);
     if (rc != MML_OK) return rc;
     if (!ctx->uploads.empty()) return mml_refuse(ctx, MML_ERR_STATE, "uploads in flight after a drained context");
     for (int i = 0; i < n; ++i) {
@@ -206,6 +224,85 @@ int mml_map_bank_increment(mml_ctx* ctx, int n, const int* banks, const int* slo
         if (rc != MML_OK) return rc;
     }
     return MML_OK;
+}
+
+// ---- a bank's global cube map: the own-map calls of capi.hip on mml_cube_bank(ctx, bank) ----
+
+int mml_map_bank_set_global(mml_ctx* ctx, int bank, int kind, const float* xyz, const int* cube, int m, const int* cen) {
+    if (!ctx) return MML_ERR_INVALID;
+    int rc = check_bank(ctx, bank);
+    if (rc != MML_OK) return rc;
+    MML_REQUIRE(kind == 0 || kind == 1, MML_ERR_INVALID, "map kind must be 0 (corner) or 1 (surf)");
+    MML_REQUIRE(m >= 0 && (m == 0 || (xyz && cube)), MML_ERR_INVALID, "bad global map arguments");
+    MML_REQUIRE(m <= ctx->MM, MML_ERR_CAPACITY, "global map larger than max_map_points");
+    for (int i = 0; i < m; ++i) MML_REQUIRE(cube[i] >= 0 && cube[i] < 4851, MML_ERR_INVALID, "cube index outside [0, 4851)");
+    rc = enter(ctx);
+    if (rc != MML_OK) return rc;
+    return mml_build_global_grid(ctx, mml_cube_bank(ctx, bank), kind, xyz, cube, m, cen);
+}
+
+int mml_map_bank_global_append(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl) {
+    if (!ctx) return MML_ERR_INVALID;
+    MML_REQUIRE(n >= 1 && banks && slots && T_wl, MML_ERR_INVALID, "bad arguments");
+    int rc = check_distinct_banks(ctx, n, banks, slots, "mml_map_bank_global_append");
+    if (rc != MML_OK) return rc;
+    rc = enter(ctx);
+    if (rc != MML_OK) return rc;
+    if (!ctx->uploads.empty()) return mml_refuse(ctx, MML_ERR_STATE, "uploads in flight after a drained context");
+    // the stacks' sizes, checked for every slot before a bank's pending clouds change
+    std::vector<int> nf(2 * (size_t)n);
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < 2; ++k)
+            MML_HIP(hipMemcpyAsync(&nf[2 * (size_t)i + k], ctx->ft_n + k * ctx->B + slots[i], sizeof(int), hipMemcpyDeviceToHost, MML_STREAM(ctx)));
+    MML_HIP(hipStreamSynchronize(MML_STREAM(ctx)));
+    for (int i = 0; i < n; ++i)
+        for (int k = 0; k < 2; ++k) {
+            const int f = nf[2 * (size_t)i + k];
+            const MmlCubeLive& L = ctx->banks.bank[(size_t)banks[i]].clive;
+            if (f < 0 || f > ctx->MF) return mml_refuse(ctx, MML_ERR_STATE, "slot %d holds no down-sampled feature stack", slots[i]);
+            if (L.gp_n[k] + f > 16 * ctx->MF)
+                return mml_refuse(ctx, MML_ERR_CAPACITY, "map bank %d: too many pending map points (16 x max_features)", banks[i]);
+        }
+    for (int i = 0; i < n; ++i) {
+        rc = mml_cube_store_append(ctx, mml_cube_bank(ctx, banks[i]), slots[i], T_wl + 16 * (size_t)i);
+        if (rc != MML_OK) return rc;
+    }
+    return MML_OK;
+}
+
+int mml_map_bank_global_increment(mml_ctx* ctx, int n, const int* banks, const double* T_wl, int* n_corner, int* n_surf) {
+    if (!ctx) return MML_ERR_INVALID;
+    MML_REQUIRE(n >= 1 && banks && T_wl, MML_ERR_INVALID, "bad arguments");
+    int rc = check_distinct_banks(ctx, n, banks, nullptr, "mml_map_bank_global_increment");
+    if (rc != MML_OK) return rc;
+    rc = enter(ctx);
+    if (rc != MML_OK) return rc;
+    for (int i = 0; i < n; ++i) {
+        int m[2] = {0, 0};
+        rc = mml_cube_store_increment(ctx, mml_cube_bank(ctx, banks[i]), T_wl + 16 * (size_t)i, m);
+        if (n_corner) n_corner[i] = m[0];
+        if (n_surf) n_surf[i] = m[1];
+        if (rc != MML_OK) return rc;
+    }
+    return MML_OK;
+}
+
+int mml_map_bank_global_download(mml_ctx* ctx, int bank, int kind, float* xyz, int* cube, int capacity, int* n, int* cen) {
+    if (!ctx) return MML_ERR_INVALID;
+    int rc = check_bank(ctx, bank);
+    if (rc != MML_OK) return rc;
+    MML_REQUIRE((kind == 0 || kind == 1) && n, MML_ERR_INVALID, "bad arguments");
+    MML_HIP(hipSetDevice(ctx->device));
+    return mml_cube_store_download(ctx, mml_cube_bank(ctx, bank), kind, xyz, cube, capacity, n, cen);
+}
+
+int mml_map_bank_global_reset(mml_ctx* ctx, int bank) {
+    if (!ctx) return MML_ERR_INVALID;
+    int rc = check_bank(ctx, bank);
+    if (rc != MML_OK) return rc;
+    rc = enter(ctx);
+    if (rc != MML_OK) return rc;
+    return mml_cube_store_reset(ctx, mml_cube_bank(ctx, bank));
 }
 
 }  // extern "C"

@@ -159,36 +159,45 @@ __global__ void k_cube_centroid(const float4* pts, const unsigned long long* key
     out_tag[dst] = (uint16_t)(key >> 40);
 }
 
-int ensure_store(mml_ctx* ctx) {
-    if (ctx->cube_store.present()) return MML_OK;
+// The store's own memory (per store: 72 bytes x max_map_points + 2 x 16 x max_features x 16 bytes) and the scratch every store of
+// the context works in; each allocated by the first call that needs it.
+int ensure_store(mml_ctx* ctx, const MmlCubeRef& cube) {
+    MmlCubeLive& L = *cube.live;
     const size_t MM = (size_t)ctx->MM;
-    ctx->gp_cap = 16 * ctx->MF;
-    const size_t gp = (size_t)ctx->gp_cap;
+    const size_t gp = 16 * (size_t)ctx->MF;
     const size_t U = (MM + gp + 3) & ~size_t(3);  // keeps the carved-out float4 array 16-byte aligned
-    return ctx->cube_store.reserve(
-        ctx, {mml_part(ctx->gs_pts[0], MM), mml_part(ctx->gs_tag[0], MM), mml_part(ctx->gs_pts2[0], MM), mml_part(ctx->gs_tag2[0], MM), mml_part(ctx->gp_pts[0], gp),
-              mml_part(ctx->gs_pts[1], MM), mml_part(ctx->gs_tag[1], MM), mml_part(ctx->gs_pts2[1], MM), mml_part(ctx->gs_tag2[1], MM), mml_part(ctx->gp_pts[1], gp),
-              // cnt | changed | bbox (6 per cube) | keep | keep_pos | sel | sel_pos | n_heads
-              mml_part(ctx->gs_work, 8 * (size_t)NCUBE + 4 * (U + 1) + 8),
-              // 64-bit keys (in / out), sort values (in / out), selected points + tags + pending tags
-              MmlPart{reinterpret_cast<void**>(&ctx->gs_keys),
-                      sizeof(unsigned long long) * 2 * U + sizeof(unsigned) * 2 * U + sizeof(float4) * U + sizeof(uint16_t) * 2 * U}});
+    if (!ctx->cube_scratch.present()) {
+        const int rc = ctx->cube_scratch.reserve(
+            ctx, {// cnt | changed | bbox (6 per cube) | keep | keep_pos | sel | sel_pos | n_heads
+                  mml_part(ctx->gs_work, 8 * (size_t)NCUBE + 4 * (U + 1) + 8),
+                  // 64-bit keys (in / out), sort values (in / out), selected points + tags + pending tags
+                  MmlPart{reinterpret_cast<void**>(&ctx->gs_keys),
+                          sizeof(unsigned long long) * 2 * U + sizeof(unsigned) * 2 * U + sizeof(float4) * U + sizeof(uint16_t) * 2 * U}});
+        if (rc != MML_OK) return rc;
+    }
+    if (L.mem.present()) return MML_OK;
+    L.gp_cap = (int)gp;
+    return L.mem.reserve(
+        ctx, {mml_part(L.gs_pts[0], MM), mml_part(L.gs_tag[0], MM), mml_part(L.gs_pts2[0], MM), mml_part(L.gs_tag2[0], MM), mml_part(L.gp_pts[0], gp),
+              mml_part(L.gs_pts[1], MM), mml_part(L.gs_tag[1], MM), mml_part(L.gs_pts2[1], MM), mml_part(L.gs_tag2[1], MM), mml_part(L.gp_pts[1], gp)});
 }
 
 }  // namespace
 
-int mml_cube_store_reset(mml_ctx* ctx) {
-    ctx->gs_n[0] = ctx->gs_n[1] = 0;
-    ctx->gp_n[0] = ctx->gp_n[1] = 0;
-    ctx->gs_cen[0] = 10;
-    ctx->gs_cen[1] = 5;
-    ctx->gs_cen[2] = 10;
+int mml_cube_store_reset(mml_ctx* ctx, const MmlCubeRef& cube) {
+    MmlCubeLive& L = *cube.live;
+    L.gs_n[0] = L.gs_n[1] = 0;
+    L.gp_n[0] = L.gp_n[1] = 0;
+    L.gs_cen[0] = 10;
+    L.gs_cen[1] = 5;
+    L.gs_cen[2] = 10;
     return MML_OK;
 }
 
-int mml_cube_store_append(mml_ctx* ctx, int slot, const double* T_wl) {
+int mml_cube_store_append(mml_ctx* ctx, const MmlCubeRef& cube, int slot, const double* T_wl) {
+    MmlCubeLive& L = *cube.live;
     hipStream_t s = MML_STREAM(ctx);
-    int rc = ensure_store(ctx);
+    int rc = ensure_store(ctx, cube);
     if (rc != MML_OK) return rc;
     int n_feat[2];
     MML_HIP(hipMemcpyAsync(&n_feat[0], ctx->ft_n + 0 * ctx->B + slot, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -199,21 +208,22 @@ int mml_cube_store_append(mml_ctx* ctx, int slot, const double* T_wl) {
     for (int kind = 0; kind < 2; ++kind) {
         const int n = n_feat[kind];
         MML_REQUIRE(n >= 0 && n <= ctx->MF, MML_ERR_STATE, "slot holds no down-sampled feature stack");
-        MML_REQUIRE(ctx->gp_n[kind] + n <= ctx->gp_cap, MML_ERR_CAPACITY, "too many pending map points (16 x max_features)");
+        MML_REQUIRE(L.gp_n[kind] + n <= L.gp_cap, MML_ERR_CAPACITY, "too many pending map points (16 x max_features)");
         if (n)
             hipLaunchKernelGGL(k_to_world, dim3((n + 255) / 256), dim3(256), 0, s, ctx->ft_xyz[kind] + (size_t)slot * ctx->MF, n, T,
-                               ctx->gp_pts[kind] + ctx->gp_n[kind]);
-        ctx->gp_n[kind] += n;
+                               L.gp_pts[kind] + L.gp_n[kind]);
+        L.gp_n[kind] += n;
     }
     MML_HIP(hipGetLastError());
     return MML_OK;
 }
 
-int mml_cube_store_increment(mml_ctx* ctx, const double* T_wl, int* n_out) {
+int mml_cube_store_increment(mml_ctx* ctx, const MmlCubeRef& cube, const double* T_wl, int* n_out) {
+    MmlCubeLive& L = *cube.live;
     hipStream_t s = MML_STREAM(ctx);
-    int rc = ensure_store(ctx);
+    int rc = ensure_store(ctx, cube);
     if (rc != MML_OK) return rc;
-    const size_t U = ((size_t)ctx->MM + (size_t)ctx->gp_cap + 3) & ~size_t(3);
+    const size_t U = ((size_t)ctx->MM + (size_t)L.gp_cap + 3) & ~size_t(3);
     int* cnt = ctx->gs_work;
     int* changed = cnt + NCUBE;
     int* bbox = changed + NCUBE;
@@ -232,17 +242,17 @@ int mml_cube_store_increment(mml_ctx* ctx, const double* T_wl, int* n_out) {
 
     // (1) what Estimate() matches against from now on: the store as it is, with its current centre (:136-149)
     for (int kind = 0; kind < 2; ++kind) {
-        const int n0 = ctx->gs_n[kind];
+        const int n0 = L.gs_n[kind];
         MML_HIP(hipMemsetAsync(cnt, 0, sizeof(int) * NCUBE, s));
-        if (n0) hipLaunchKernelGGL(k_hist, dim3((n0 + 255) / 256), dim3(256), 0, s, ctx->gs_tag[kind], n0, cnt, (int*)nullptr);
-        rc = mml_build_global_grid_device(ctx, kind, ctx->gs_pts[kind], ctx->gs_tag[kind], cnt, n0, ctx->gs_cen);
+        if (n0) hipLaunchKernelGGL(k_hist, dim3((n0 + 255) / 256), dim3(256), 0, s, L.gs_tag[kind], n0, cnt, (int*)nullptr);
+        rc = mml_build_global_grid_device(ctx, cube, kind, L.gs_pts[kind], L.gs_tag[kind], cnt, n0, L.gs_cen);
         if (rc != MML_OK) return rc;
     }
     // (2) MapMove (:288-581): the layer shifts that keep the sensor's cube 8 cubes away from every face
     Shifts S;
     S.n = 0;
     {
-        int* cen = ctx->gs_cen;
+        int* cen = L.gs_cen;
         const double t[3] = {T_wl[3], T_wl[7], T_wl[11]};
         int c[3] = {int((t[0] + 25.0) / 50.0) + cen[2], int((t[1] + 25.0) / 50.0) + cen[0], int((t[2] + 25.0) / 50.0) + cen[1]};
         for (int a = 0; a < 3; ++a)
@@ -268,17 +278,17 @@ int mml_cube_store_increment(mml_ctx* ctx, const double* T_wl, int* n_out) {
     }
     // (3) distribute, filter the cubes that grew beyond 300 points, compact
     for (int kind = 0; kind < 2; ++kind) {
-        const int n0 = ctx->gs_n[kind], np = ctx->gp_n[kind], nu = n0 + np;
-        if (n0 && S.n) hipLaunchKernelGGL(k_apply_shifts, dim3((n0 + 255) / 256), dim3(256), 0, s, ctx->gs_tag[kind], n0, S);
+        const int n0 = L.gs_n[kind], np = L.gp_n[kind], nu = n0 + np;
+        if (n0 && S.n) hipLaunchKernelGGL(k_apply_shifts, dim3((n0 + 255) / 256), dim3(256), 0, s, L.gs_tag[kind], n0, S);
         if (np)
-            hipLaunchKernelGGL(k_tag_points, dim3((np + 255) / 256), dim3(256), 0, s, ctx->gp_pts[kind], np, ctx->gs_cen[0],
-                               ctx->gs_cen[1], ctx->gs_cen[2], ptag);
+            hipLaunchKernelGGL(k_tag_points, dim3((np + 255) / 256), dim3(256), 0, s, L.gp_pts[kind], np, L.gs_cen[0],
+                               L.gs_cen[1], L.gs_cen[2], ptag);
         MML_HIP(hipMemsetAsync(cnt, 0, sizeof(int) * 2 * NCUBE, s));  // cnt + changed
-        if (n0) hipLaunchKernelGGL(k_hist, dim3((n0 + 255) / 256), dim3(256), 0, s, ctx->gs_tag[kind], n0, cnt, (int*)nullptr);
+        if (n0) hipLaunchKernelGGL(k_hist, dim3((n0 + 255) / 256), dim3(256), 0, s, L.gs_tag[kind], n0, cnt, (int*)nullptr);
         if (np) hipLaunchKernelGGL(k_hist, dim3((np + 255) / 256), dim3(256), 0, s, ptag, np, cnt, changed);
         int nk = 0, nsel = 0, nheads = 0;
         if (nu) {
-            hipLaunchKernelGGL(k_classify, dim3((nu + 255) / 256), dim3(256), 0, s, ctx->gs_tag[kind], n0, ptag, np, cnt, changed,
+            hipLaunchKernelGGL(k_classify, dim3((nu + 255) / 256), dim3(256), 0, s, L.gs_tag[kind], n0, ptag, np, cnt, changed,
                                keep, sel);
             rc = mml_exclusive_scan(ctx, ctx->sort_tmp, keep, keep_pos, (size_t)nu, s);
             if (rc == MML_OK) rc = mml_exclusive_scan(ctx, ctx->sort_tmp, sel, sel_pos, (size_t)nu, s);
@@ -293,8 +303,8 @@ int mml_cube_store_increment(mml_ctx* ctx, const double* T_wl, int* n_out) {
             nsel = last[2] + last[3];
             MML_REQUIRE(nk + nsel <= ctx->MM, MML_ERR_CAPACITY, "cube store larger than max_map_points");
             hipLaunchKernelGGL(k_init_bbox, dim3((NCUBE * 6 + 255) / 256), dim3(256), 0, s, bbox);
-            hipLaunchKernelGGL(k_scatter, dim3((nu + 255) / 256), dim3(256), 0, s, ctx->gs_pts[kind], ctx->gs_tag[kind], n0,
-                               ctx->gp_pts[kind], ptag, np, keep, keep_pos, sel, sel_pos, ctx->gs_pts2[kind], ctx->gs_tag2[kind],
+            hipLaunchKernelGGL(k_scatter, dim3((nu + 255) / 256), dim3(256), 0, s, L.gs_pts[kind], L.gs_tag[kind], n0,
+                               L.gp_pts[kind], ptag, np, keep, keep_pos, sel, sel_pos, L.gs_pts2[kind], L.gs_tag2[kind],
                                sel_pts, sel_tag, bbox);
             if (nsel) {
                 const int blocks = (nsel + 255) / 256;
@@ -307,34 +317,35 @@ int mml_cube_store_increment(mml_ctx* ctx, const double* T_wl, int* n_out) {
                 rc = mml_exclusive_scan(ctx, ctx->sort_tmp, keep, keep_pos, (size_t)nsel, s);
                 if (rc != MML_OK) return rc;
                 hipLaunchKernelGGL(k_cube_centroid, dim3(blocks), dim3(256), 0, s, sel_pts, keys2, vals2, keep, keep_pos, nsel, nk,
-                                   ctx->MM, ctx->gs_pts2[kind], ctx->gs_tag2[kind], d_heads);
+                                   ctx->MM, L.gs_pts2[kind], L.gs_tag2[kind], d_heads);
                 MML_HIP(hipMemcpyAsync(&nheads, d_heads, sizeof(int), hipMemcpyDeviceToHost, s));
                 MML_HIP(hipStreamSynchronize(s));
             }
         }
         MML_HIP(hipGetLastError());
-        std::swap(ctx->gs_pts[kind], ctx->gs_pts2[kind]);
-        std::swap(ctx->gs_tag[kind], ctx->gs_tag2[kind]);
-        ctx->gs_n[kind] = nk + nheads;
-        ctx->gp_n[kind] = 0;
-        if (n_out) n_out[kind] = ctx->gs_n[kind];
+        std::swap(L.gs_pts[kind], L.gs_pts2[kind]);
+        std::swap(L.gs_tag[kind], L.gs_tag2[kind]);
+        L.gs_n[kind] = nk + nheads;
+        L.gp_n[kind] = 0;
+        if (n_out) n_out[kind] = L.gs_n[kind];
     }
     return MML_OK;
 }
 
 // the LIVE store (tests / visualisation): points, cube index of every point, centre
-int mml_cube_store_download(mml_ctx* ctx, int kind, float* xyz, int* cube, int capacity, int* n, int* cen) {
+int mml_cube_store_download(mml_ctx* ctx, const MmlCubeRef& ref, int kind, float* xyz, int* cube, int capacity, int* n, int* cen) {
+    const MmlCubeLive& L = *ref.live;
     hipStream_t s = MML_STREAM(ctx);
-    const int m = ctx->gs_pts[kind] ? ctx->gs_n[kind] : 0;
+    const int m = L.gs_pts[kind] ? L.gs_n[kind] : 0;
     *n = m;
     if (cen)
-        for (int k = 0; k < 3; ++k) cen[k] = ctx->gs_cen[k];
+        for (int k = 0; k < 3; ++k) cen[k] = L.gs_cen[k];
     if (m == 0 || (!xyz && !cube)) return MML_OK;
     MML_REQUIRE(capacity >= m, MML_ERR_CAPACITY, "capacity below the store size");
     std::vector<float4> p((size_t)m);
     std::vector<uint16_t> t((size_t)m);
-    MML_HIP(hipMemcpyAsync(p.data(), ctx->gs_pts[kind], sizeof(float4) * (size_t)m, hipMemcpyDeviceToHost, s));
-    MML_HIP(hipMemcpyAsync(t.data(), ctx->gs_tag[kind], sizeof(uint16_t) * (size_t)m, hipMemcpyDeviceToHost, s));
+    MML_HIP(hipMemcpyAsync(p.data(), L.gs_pts[kind], sizeof(float4) * (size_t)m, hipMemcpyDeviceToHost, s));
+    MML_HIP(hipMemcpyAsync(t.data(), L.gs_tag[kind], sizeof(uint16_t) * (size_t)m, hipMemcpyDeviceToHost, s));
     MML_HIP(hipStreamSynchronize(s));
     for (int i = 0; i < m; ++i) {
         if (xyz) {

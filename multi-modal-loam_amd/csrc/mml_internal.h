@@ -5,6 +5,7 @@
 #define MML_INTERNAL_H
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include <string>
@@ -61,10 +62,54 @@ struct MmlGrid {         // radix-sorted uniform grid over one map cloud (replac
     int ncell = 1;
 };
 
+// The global cube map of one Estimator (a12 + map_global.hip), in two parts.  The context has one pair of its own and every map
+// bank one more (MmlCubeRef below); the scratch the upkeep works in (gs_work, gs_keys, the sort buffers) is the context's.
+// The MATCH COPY: what Estimate() matches against -- tagged grids over the concatenated cube clouds, the unsorted clouds with
+// their tags, the 4851 cube counts, laserCloudCen*_last.  Sized by need (ensure_global_capacity).
+struct MmlCubeMatch {
+    MmlGrid ggrid[2];
+    bool have_gmap[2] = {false, false};
+    float4* gmap_orig[2] = {nullptr, nullptr};
+    uint16_t* gtag_orig[2] = {nullptr, nullptr};
+    int* cube_cnt[2] = {nullptr, nullptr};  // 4851 ints each
+    MmlGroup ggrid_mem[2];                  // owns ggrid[k].pts / cell_start / tags, gmap_orig[k], gtag_orig[k], cube_cnt[k]
+    int gmap_cap[2] = {0, 0};               // points the group of a kind is sized for
+    int cen[3] = {10, 5, 10};               // laserCloudCen{Width,Height,Depth}_last (Map_Manager.h:113-115)
+    void release() {
+        for (auto& g : ggrid_mem) g.release();
+        for (int k = 0; k < 2; ++k) {
+            ggrid[k] = MmlGrid();
+            have_gmap[k] = false;
+            gmap_orig[k] = nullptr;
+            gtag_orig[k] = nullptr;
+            cube_cnt[k] = nullptr;
+            gmap_cap[k] = 0;
+        }
+    }
+};
+// The LIVE STORE (MAP_MANAGER's cubes): points + cube tags, the ping-pong pair of the compaction, the pending world-frame
+// features (laserCloud{Corner,Surf}_to_map), the live centre.  72 bytes per point of max_map_points plus 2 x 16 x max_features x
+// 16 bytes of pending clouds, allocated by the first append / increment.
+struct MmlCubeLive {
+    float4* gs_pts[2] = {nullptr, nullptr};
+    uint16_t* gs_tag[2] = {nullptr, nullptr};
+    float4* gs_pts2[2] = {nullptr, nullptr};   // ping-pong for compaction
+    uint16_t* gs_tag2[2] = {nullptr, nullptr};
+    int gs_n[2] = {0, 0};
+    float4* gp_pts[2] = {nullptr, nullptr};    // laserCloud{Corner,Surf}_to_map
+    int gp_n[2] = {0, 0};
+    int gp_cap = 0;
+    int gs_cen[3] = {10, 5, 10};               // laserCloudCen{Width,Height,Depth} of the live store
+    MmlGroup mem;                              // owns gs_pts .. gp_pts
+};
+
 // One more local map beside the context's own (mml_map_banks_create): the same state -- the two grids with their unsorted clouds,
-// the key-scan ring with its counts, localMapID, the two map sizes.  A bank that was never set is an empty map.
+// the key-scan ring with its counts, localMapID, the two map sizes -- and one more global cube map (cmatch / clive; no memory
+// before the bank's first set_global / append / increment).  A bank that was never set is an empty map.
 #define MML_LOCAL_WINDOW 50  // localMapWindowSize, Estimator.h:326
 struct MmlMapBank {
+    MmlCubeMatch cmatch;
+    MmlCubeLive clive;
     MmlGrid grid[2];
     bool have_map[2] = {true, true};
     float4* map_tmp = nullptr;               // 2 x MM: the unsorted clouds
@@ -81,23 +126,39 @@ struct alignas(16) MmlMapDesc {
     const float4* orig;  // the unsorted cloud (index = original index)
 };
 static_assert(sizeof(MmlMapDesc) % 16 == 0 && sizeof(MmlMapDesc) / 4 <= 32, "a descriptor is read as dwords, at most 32");
+// What they read of one global cube map of one kind: a row of the second table, beside the first.  The grid comes first, as in
+// MmlMapDesc: a far query picks the row of its stage and reads the grid from either.  Entry 0 (the context's own map) always has
+// have_g = 0: a bound slot and the context's own cube map exclude each other, so a banked launch never reads it.
+struct alignas(16) MmlCubeDesc {
+    MmlGrid g;            // the tagged grid
+    const float4* orig;   // the unsorted cloud
+    const int* cube_cnt;  // 4851 counts
+    int have_g;
+    int cen[3];           // the ENTRY's centre (the same in both rows of an entry)
+};
+static_assert(sizeof(MmlCubeDesc) % 16 == 0 && sizeof(MmlCubeDesc) / 4 <= 32, "a descriptor is read as dwords, at most 32");
+static_assert(offsetof(MmlCubeDesc, g) == 0 && offsetof(MmlMapDesc, g) == 0, "the grid leads both rows");
 struct MmlBanks {
     std::vector<MmlMapBank> bank;
     std::vector<int> slot_bank;       // B: bank of every slot, -1 = the context's own map
     int n_bound = 0;                  // slots with a bank
     MmlMapDesc* d_table = nullptr;    // (banks + 1) x 2 kinds; row 0: the context's own map
+    MmlCubeDesc* d_cube_table = nullptr;  // the same rows for the cube maps
     int* d_slot_bank = nullptr;       // B
-    MmlGroup tab_mem;                 // owns the two
-    bool dirty = true;                // a grid or a binding changed since the device copies were written (mml_banks_refresh)
+    MmlGroup tab_mem;                 // owns the three
+    bool dirty = true;                // a grid, a match copy or a binding changed since the device copies were written (mml_assoc_ready)
     void release() {
         for (MmlMapBank& b : bank) {
             b.grid_mem.release();
             b.ring_mem.release();
+            b.cmatch.release();
+            b.clive.mem.release();
         }
         bank.clear();
         slot_bank.clear();
         tab_mem.release();
         d_table = nullptr;
+        d_cube_table = nullptr;
         d_slot_bank = nullptr;
         n_bound = 0;
         dirty = true;
@@ -276,15 +337,9 @@ struct mml_ctx {
     // maps
     MmlGrid grid[2];
     bool have_map[2] = {false, false};
-    // global cube map (a12): tagged grids over the concatenated cube clouds
-    MmlGrid ggrid[2];
-    bool have_gmap[2] = {false, false};
-    float4* gmap_orig[2] = {nullptr, nullptr};
-    uint16_t* gtag_orig[2] = {nullptr, nullptr};
-    int* cube_cnt[2] = {nullptr, nullptr};  // 4851 ints each
-    MmlGroup ggrid_mem[2];                  // owns ggrid[k].pts / cell_start / tags, gmap_orig[k], gtag_orig[k], cube_cnt[k]
-    int gmap_cap[2] = {0, 0};               // points the group of a kind is sized for
-    int cen[3] = {10, 5, 10};  // laserCloudCen{Width,Height,Depth}_last (Map_Manager.h:113-115)
+    // global cube map (a12) and the device-side MAP_MANAGER cube stores (map_global.hip): the context's own pair
+    MmlCubeMatch cmatch;
+    MmlCubeLive clive;
     // device-side local map upkeep (Estimator::MapIncrementLocal): ring of key scans' features in the world frame
     static constexpr int LOCAL_WINDOW = MML_LOCAL_WINDOW;
     float4* ring[2] = {nullptr, nullptr};    // LOCAL_WINDOW x MF each
@@ -294,19 +349,10 @@ struct mml_ctx {
     MmlGroup ring_mem;                       // owns ring[2], ring_cat, vox_flag; allocated by the first increment
     int ring_n[2][LOCAL_WINDOW] = {};
     long local_map_id = 0;                   // localMapID
-    // device-side MAP_MANAGER cube stores (map_global.hip): live points + cube tags, pending world-frame features
-    float4* gs_pts[2] = {nullptr, nullptr};
-    uint16_t* gs_tag[2] = {nullptr, nullptr};
-    float4* gs_pts2[2] = {nullptr, nullptr};   // ping-pong for compaction
-    uint16_t* gs_tag2[2] = {nullptr, nullptr};
-    int gs_n[2] = {0, 0};
-    float4* gp_pts[2] = {nullptr, nullptr};    // laserCloud{Corner,Surf}_to_map
-    int gp_n[2] = {0, 0};
-    int gp_cap = 0;
-    int gs_cen[3] = {10, 5, 10};               // laserCloudCen{Width,Height,Depth} of the live store
+    // scratch of the cube stores' upkeep, shared by the own store and every bank's (one increment runs at a time)
     int* gs_work = nullptr;                    // histograms / flags / bbox keys / scan scratch
     unsigned long long* gs_keys = nullptr;     // 64-bit sort keys, 2 x MM
-    MmlGroup cube_store;                       // owns gs_pts .. gs_keys, allocated by the first append / increment
+    MmlGroup cube_scratch;                     // owns the two, allocated by the first append / increment of any store
     MmlStaging<char, false> wire_stage;      // raw message bytes on their way in / out (one call at a time; grows to the largest)
     int local_map_n[2] = {0, 0};
     MmlBanks banks;                    // map banks (map_banks.hip): further local maps, and which slot is matched against which
@@ -351,10 +397,11 @@ struct mml_ctx {
         win_state.release();
         seg_scratch.release();
         for (auto& t : seg_tmp) t.release();
-        for (auto& g : ggrid_mem) g.release();
+        cmatch.release();
         ring_mem.release();
         banks.release();
-        cube_store.release();
+        clive.mem.release();
+        cube_scratch.release();
         wire_stage.release();
         sort_tmp.release();
         fixed.release();
@@ -448,8 +495,9 @@ int mml_build_grid_device(mml_ctx* ctx, const MmlMapRef& map, int kind, int m);
 inline int mml_build_grid(mml_ctx* ctx, int kind, const float* h_xyz, int m) { return mml_build_grid(ctx, mml_map_own(ctx), kind, h_xyz, m); }
 inline int mml_build_grid_device(mml_ctx* ctx, int kind, int m) { return mml_build_grid_device(ctx, mml_map_own(ctx), kind, m); }
 // map_banks.hip.  mml_assoc_ready: the state checks of a call that associates slots [first, first + count) -- an unbound slot needs
-// the context's two maps (`who` before both maps were set), a bound one no global map -- and the device copies of the descriptor
-// table and the bindings brought up to date (a drained context and one small copy, only after a change).
+// the context's two maps (`who` before both maps were set), a bound one that the context's OWN global cube map is unset -- and the
+// device copies of the two descriptor tables and the bindings brought up to date (a drained context and small copies, only after
+// a change).
 int mml_assoc_ready(mml_ctx* ctx, int first, int count, const char* who);
 inline bool mml_any_bound(const mml_ctx* ctx, int first, int count) {
     if (!ctx->banks.n_bound) return false;
@@ -463,13 +511,24 @@ int mml_gicp_align_device(mml_ctx* ctx, const char* who, const float4* d_src, in
 int mml_downsample_big(mml_ctx* ctx, int first, int count);
 int mml_downsample_redo_overflow(mml_ctx* ctx, int first, int count, std::vector<int>* redone);
 int mml_map_upkeep_increment(mml_ctx* ctx, const MmlMapRef& map, int slot, const double* T_wl, int* n_out);
-int mml_build_global_grid(mml_ctx* ctx, int kind, const float* h_xyz, const int* h_cube, int m, const int* cen);
-int mml_build_global_grid_device(mml_ctx* ctx, int kind, const float4* d_pts, const uint16_t* d_tags, const int* d_cnt, int m,
-                                 const int* cen);
-int mml_cube_store_append(mml_ctx* ctx, int slot, const double* T_wl);
-int mml_cube_store_increment(mml_ctx* ctx, const double* T_wl, int* n_out);
-int mml_cube_store_download(mml_ctx* ctx, int kind, float* xyz, int* cube, int capacity, int* n, int* cen);
-int mml_cube_store_reset(mml_ctx* ctx);
+// The state of one global cube map, by reference: the context's own (mml_cube_own) or a bank's (mml_cube_bank).  The grid builds
+// and the store's upkeep take the map they work on as this parameter, as the local map's take MmlMapRef.
+struct MmlCubeRef {
+    MmlCubeMatch* match;
+    MmlCubeLive* live;
+};
+inline MmlCubeRef mml_cube_own(mml_ctx* c) { return MmlCubeRef{&c->cmatch, &c->clive}; }
+inline MmlCubeRef mml_cube_bank(mml_ctx* c, int bank) {
+    MmlMapBank& b = c->banks.bank[(size_t)bank];
+    return MmlCubeRef{&b.cmatch, &b.clive};
+}
+int mml_build_global_grid(mml_ctx* ctx, const MmlCubeRef& cube, int kind, const float* h_xyz, const int* h_cube, int m, const int* cen);
+int mml_build_global_grid_device(mml_ctx* ctx, const MmlCubeRef& cube, int kind, const float4* d_pts, const uint16_t* d_tags, const int* d_cnt,
+                                 int m, const int* cen);
+int mml_cube_store_append(mml_ctx* ctx, const MmlCubeRef& cube, int slot, const double* T_wl);
+int mml_cube_store_increment(mml_ctx* ctx, const MmlCubeRef& cube, const double* T_wl, int* n_out);
+int mml_cube_store_download(mml_ctx* ctx, const MmlCubeRef& cube, int kind, float* xyz, int* cube_idx, int capacity, int* n, int* cen);
+int mml_cube_store_reset(mml_ctx* ctx, const MmlCubeRef& cube);
 int mml_launch_knn5(mml_ctx* ctx, int kind, const float* d_q, int nq, float max_d2, int* d_idx, float* d_d2);
 // with_stats = false (mml_step, which reads none of them): the per-slot statistics (counts, normal Gram matrix) are left stale and
 // computed by mml_ensure_assoc_stats when a consumer asks (mml_linearize*, the next mml_associate with statistics)

@@ -86,11 +86,22 @@ class Context {
 
     // Map banks (include/mmloam_hip.h, "map banks"), for a host that replays several sequences in this context: n further local
     // maps, the bank of every slot (-1: the context's own map, the one the Estimator below uses), and MapIncrementLocal for n
-    // distinct banks in one call (T_wl: n x 16, row-major; the sizes may be null).  Banked slots have no cube stage.
+    // distinct banks in one call (T_wl: n x 16, row-major; the sizes may be null).  A bank has its own global cube map, which a
+    // bound slot is matched against first: set it, or feed its MAP_MANAGER store (featureAssociateToMap / MapIncrement) for n
+    // distinct banks in one call each.
     void map_banks(int n) { check(ctx_, mml_map_banks_create(ctx_, n), "map_banks"); }
     void bind_banks(int first_slot, int count, const int* banks) { check(ctx_, mml_slot_bind_bank(ctx_, first_slot, count, banks), "bind_banks"); }
     void bank_increment(int n, const int* banks, const int* slots, const double* T_wl, int* n_corner = nullptr, int* n_surf = nullptr) {
         check(ctx_, mml_map_bank_increment(ctx_, n, banks, slots, T_wl, n_corner, n_surf), "bank_increment");
+    }
+    void bank_set_global(int bank, int kind, const float* xyz, const int* cube, int m, const int* cen = nullptr) {
+        check(ctx_, mml_map_bank_set_global(ctx_, bank, kind, xyz, cube, m, cen), "bank_set_global");
+    }
+    void bank_global_append(int n, const int* banks, const int* slots, const double* T_wl) {
+        check(ctx_, mml_map_bank_global_append(ctx_, n, banks, slots, T_wl), "bank_global_append");
+    }
+    void bank_global_increment(int n, const int* banks, const double* T_wl, int* n_corner = nullptr, int* n_surf = nullptr) {
+        check(ctx_, mml_map_bank_global_increment(ctx_, n, banks, T_wl, n_corner, n_surf), "bank_global_increment");
     }
 
    private:

@@ -3,6 +3,14 @@ Estimate against the local map, hand the pose back, apply the key-scan rule and 
 that touches points runs on the device through the C-ABI (mml_downsample, mml_estimate, mml_map_increment_local;
 for n sequences in one context: the same with map banks, mml_slot_bind_bank and mml_map_bank_increment);
 this file only carries the control flow and the 4x4 / quaternion bookkeeping the reference does in Eigen.
+
+global_map=True adds the second map of an Estimator, the MAP_MANAGER cube store that Estimator::threadMapIncrement
+(Estimator.cpp:92-145) feeds (mml_map_global_append / _increment, per bank mml_map_bank_global_append / _increment).  The
+reference runs that thread asynchronously at 10 Hz; the schedule here is the deterministic one the thread follows when it keeps
+up with the scans: every hand-off (:1070-1077) is taken before the next scan arrives.  After the pose hand-back, when the scan is
+not degenerate and its down-sampled corner stack is not empty (:103): append(slot, T), map_update_ID += 1, and MapIncrement at T
+when map_update_ID % map_skip_frame == 0.  Estimate then matches a feature against its cube first (the copy taken at the start of
+the last MapIncrement) and falls back to the local map, and the gate in front of Estimate is the whole of :1032-1035.
 """
 import numpy as np
 
@@ -23,6 +31,9 @@ def _sequence_init(st):
     st.n_surf_local = 0
     st.fail_detected = False
     st.key_scans = 0
+    st.n_corner_global = 0                                        # laserCloud{Corner,Surf}FromMapNum: the last MapIncrement's sizes
+    st.n_surf_global = 0
+    st.map_update_id = 0                                          # map_update_ID, Estimator.h:332
     st.last_T = None                                              # transformTobeMapped the last estimate_lidar_pose ended with
 
 
@@ -37,6 +48,27 @@ def _transform_to_be_mapped(exRbl, exPbl, P, Q):
 def _local_map_gate(st):
     """:1032-1035 (local-map half of the gate): Estimate runs only against a local map that holds something."""
     return st.n_corner_local > 0 and st.n_surf_local > 100
+
+
+def _map_gate(st):
+    """:1032-1035, the whole gate: the cube store's sizes as the last MapIncrement returned them (0 without global_map), or the
+    local map's."""
+    return (st.n_corner_global > 0 and st.n_surf_global > 100) or _local_map_gate(st)
+
+
+def _map_thread_takes(is_degenerate, n_corner_stack):
+    """Whether threadMapIncrement gets this scan: handed off at all (:1070) and a corner stack that is not empty (:103)."""
+    return (not is_degenerate) and n_corner_stack > 0
+
+
+def _map_thread_appended(st, map_skip_frame):
+    """After featureAssociateToMap of a scan (:105-122): counts it; True when MapIncrement is due (:129)."""
+    st.map_update_id += 1
+    return st.map_update_id % map_skip_frame == 0
+
+
+def _map_thread_incremented(st, sizes):
+    st.n_corner_global, st.n_surf_global = int(sizes[0]), int(sizes[1])
 
 
 def _hand_back(st, lidar_mode, exRbl, exPbl, T, P, Q, is_degenerate, corner_cnt):
@@ -84,17 +116,24 @@ def _adjacent_runs(items, slot_of):
 
 class LidarOdometry:
     """One Estimator instance: `ctx` owns the scan slots and the maps.  lidar_mode 1 = Horizon, 2 = Velodyne
-    (the fused cloud is processed as mode 2, unionPoseEstimation.cpp:872)."""
+    (the fused cloud is processed as mode 2, unionPoseEstimation.cpp:872).  global_map=True: the context's cube store follows
+    the map thread's schedule (the module docstring: the one the reference's asynchronous thread follows when it keeps up) and
+    Estimate matches against it first; the default drives the local map alone, call for call as before."""
 
-    def __init__(self, ctx, exTlb=None, lidar_mode=2, max_outer=5, inner_iters=10):
+    def __init__(self, ctx, exTlb=None, lidar_mode=2, max_outer=5, inner_iters=10, global_map=False, map_skip_frame=2):
+        if map_skip_frame < 1:
+            raise ValueError("map_skip_frame must be at least 1")
         self.ctx = ctx
         self.exTlb = np.eye(4) if exTlb is None else np.asarray(exTlb, dtype=np.float64)
         self.exRbl = self.exTlb[:3, :3].T.copy()                      # :973
         self.exPbl = -1.0 * self.exRbl @ self.exTlb[:3, 3]            # :974
         self.lidar_mode = lidar_mode
         self.max_outer, self.inner_iters = max_outer, inner_iters
+        self.global_map, self.map_skip_frame = global_map, map_skip_frame
         _sequence_init(self)
         ctx.map_local_reset()
+        if global_map:
+            ctx.map_global_reset()
 
     def transform_to_be_mapped(self, P, Q):
         return _transform_to_be_mapped(self.exRbl, self.exPbl, P, Q)
@@ -109,11 +148,15 @@ class LidarOdometry:
         corner_cnt = ctx.scan_info(slot).fused_corner_num              # :990-996
         ctx.downsample(slot, 1)                                        # :1013-1024
         is_degenerate = False
-        if _local_map_gate(self):
+        if _map_gate(self):
             Pn, Qn, info = ctx.estimate(slot, 1, self.exTlb, P[None], Q[None], self.max_outer, self.inner_iters)
             P, Q = Pn[0], Qn[0]
             is_degenerate = bool(info[0].is_degenerate)
         T, grew = _hand_back(self, self.lidar_mode, self.exRbl, self.exPbl, T, P, Q, is_degenerate, corner_cnt)
+        if self.global_map and _map_thread_takes(is_degenerate, ctx.features_count(slot, 0)):
+            ctx.map_global_append(slot, T)
+            if _map_thread_appended(self, self.map_skip_frame):
+                _map_thread_incremented(self, ctx.map_global_increment(T))
         if grew:
             _grown(self, self.lidar_mode, T, ctx.map_increment_local(slot, T))
         _finish(self, T, is_degenerate)
@@ -143,11 +186,17 @@ class BatchLidarOdometry:
     pose hand-back and the key-scan rule per sequence on the host (the functions LidarOdometry calls), and ONE bank_increment
     call for the sequences that grew.  Every sequence reproduces what a LidarOdometry of its own on a fresh context produces.
     The per-sequence state is in self.seq[w] (n_corner_local, n_surf_local, key_scans, fail_detected, last_T, ...).
-    Banked slots have no cube stage: the context must not hold a global cube map."""
+    global_map=True: bank w also keeps sequence w's cube store and match copy, on the map thread's schedule of the module
+    docstring (the one the reference's asynchronous thread follows when it keeps up): per round ONE bank_global_append call for
+    the sequences whose scan the thread takes and ONE bank_global_increment call for those whose MapIncrement is due.  The
+    context's OWN global cube map must stay unset either way: a bound slot and it exclude each other."""
 
-    def __init__(self, ctx, n, exTlb=None, lidar_mode=2, max_outer=5, inner_iters=10):
+    def __init__(self, ctx, n, exTlb=None, lidar_mode=2, max_outer=5, inner_iters=10, global_map=False, map_skip_frame=2):
         if n < 1:
             raise ValueError("n must be at least 1")
+        if map_skip_frame < 1:
+            raise ValueError("map_skip_frame must be at least 1")
+        self.global_map, self.map_skip_frame = global_map, map_skip_frame
         self.ctx, self.n = ctx, n
         self.exTlb = np.eye(4) if exTlb is None else np.asarray(exTlb, dtype=np.float64)
         self.exRbl = self.exTlb[:3, :3].T.copy()
@@ -185,7 +234,7 @@ class BatchLidarOdometry:
         for run in runs:
             ctx.downsample(slots[run[0]], len(run))                                              # :1013-1024
         degenerate = {w: False for w in live}
-        for run in _adjacent_runs([w for w in live if _local_map_gate(self.seq[w])], slot_of):
+        for run in _adjacent_runs([w for w in live if _map_gate(self.seq[w])], slot_of):
             Pn, Qn, info = ctx.estimate(slots[run[0]], len(run), self.exTlb, P[run], Q[run], self.max_outer, self.inner_iters)
             for i, w in enumerate(run):
                 P[w], Q[w] = Pn[i], Qn[i]
@@ -193,6 +242,15 @@ class BatchLidarOdometry:
         grew = [False] * n
         for w in live:
             T[w], grew[w] = _hand_back(self.seq[w], self.lidar_mode, self.exRbl, self.exPbl, T[w], P[w], Q[w], degenerate[w], corner_cnt[w])
+        if self.global_map:
+            taken = [w for w in live if _map_thread_takes(degenerate[w], ctx.features_count(slots[w], 0))]
+            if taken:
+                ctx.bank_global_append(taken, [slots[w] for w in taken], np.stack([T[w] for w in taken]))
+            due = [w for w in taken if _map_thread_appended(self.seq[w], self.map_skip_frame)]
+            if due:
+                nc, ns = ctx.bank_global_increment(due, np.stack([T[w] for w in due]))
+                for i, w in enumerate(due):
+                    _map_thread_incremented(self.seq[w], (nc[i], ns[i]))
         growing = [w for w in live if grew[w]]
         if growing:
             nc, ns = ctx.bank_increment(growing, [slots[w] for w in growing], np.stack([T[w] for w in growing]))

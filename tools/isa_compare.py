@@ -4,8 +4,9 @@
     hipcc <the Makefile's FLAGS> -save-temps -c map_assoc.hip      (once in each tree)
     python tools/isa_compare.py OLD/map_assoc-hip-amdgcn-amd-amdhsa-gfx950.s NEW/map_assoc-hip-amdgcn-amd-amdhsa-gfx950.s
 
-Kernels are matched by their demangled base name and, for templates, the arguments the old build knows (the new build's
-unbanked instantiations carry one more template argument, `false`).  Compared per kernel: the instruction text between the
+Kernels are matched by their demangled base name and, for templates, their arguments without the trailing `false` of the
+unbanked instantiations (a build from before the banked forms has no such argument; the `true` ones are listed, not compared).
+Compared per kernel: the instruction text between the
 kernel's label and its s_endpgm with symbol names removed, and the register / scratch / LDS figures of its .amdhsa block.
 Prints one line per kernel and exits 1 when a pair differs."""
 import re
@@ -43,7 +44,7 @@ def key(dem, new):
     if not m or not m.group(1).startswith(("k_associate", "k_assoc_prefix", "k_knn5")):
         return None
     args = [a.strip() for a in (m.group(2) or "").split(",") if a.strip()]
-    if new and args and args[-1] in ("false", "true"):
+    if args and args[-1] in ("false", "true"):           # (an old build from before the banked forms has no such argument)
         if args[-1] == "true":
             return None
         args = args[:-1]
