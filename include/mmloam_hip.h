@@ -685,8 +685,24 @@ int mml_map_set_global(mml_ctx* ctx, int kind, const float* xyz, const int* cube
  * mml_map_bank_increment: mml_map_increment_local for n DISTINCT banks (a bank named twice is MML_ERR_INVALID, checked
  * with every other argument before anything changes): bank banks[i] takes the stacks of slot slots[i] at T_wl + 16 i.
  * Every bank ends bit-identical to the own map of a context with the same history of increments.  n_corner / n_surf: n
- * new map sizes each, or NULL. */
+ * new map sizes each, or NULL.  The banks are worked through one after the other: at least 7 host synchronisations per bank.
+ * mml_map_bank_increment_segmented: the same call -- arguments, argument checks, drained context -- with the n banks' work in
+ * ONE chain of launches: one launch writes all 2 n stacks into their rings, one concatenates all rings, one stable 64-bit
+ * sort keyed (bank of the call, kind) << 32 | voxel filters all of them, and the 2 n kNN grids are built by one sort per
+ * cell-refinement round.  Every bank ends bit-identical to what mml_map_bank_increment leaves on the same history: ring,
+ * counts, localMapID, the filtered clouds with their order, both grids, the sizes returned.  ONE DIFFERENCE: the stack sizes
+ * of all n slots are read in one copy and checked before any bank changes -- a slot without a down-sampled stack is
+ * MML_ERR_STATE, the message names the slot, and ALL n banks are exactly as before the call (mml_map_bank_increment leaves
+ * banks 0 .. i-1 incremented); a bank whose ring would exceed max_map_points is MML_ERR_CAPACITY in the same way.
+ * Host synchronisations after the entry drain: 2 + R whatever n is (the stack sizes; the filtered sizes and boxes; one per
+ * cell-refinement round, R = the rounds of the slowest (bank, kind), 1 to 5).  Scratch: 48 bytes per ring point the call
+ * works on at a time (both kinds of its banks' rings, the new stacks included) plus the sort's temporary storage, grown on
+ * demand and kept until mml_destroy.  A call whose banks hold more than MML_BANK_INCREMENT_BUDGET ring points works them in
+ * chunks -- greedy, in call order, a bank over the budget a chunk of its own -- and makes one synchronisation for the stack
+ * sizes and 1 + R for every chunk; the default budget keeps every position in an int and the scratch at 192 MiB.
+ * mml_debug_bank_increment_budget (a test hook): sets that budget, in points, for the context's later calls. */
 #define MML_MAP_BANKS_MAX 1024
+#define MML_BANK_INCREMENT_BUDGET (1 << 22)
 int mml_map_banks_create(mml_ctx* ctx, int n_banks);
 int mml_map_banks_destroy(mml_ctx* ctx);
 int mml_map_bank_set_local(mml_ctx* ctx, int bank, int kind, const float* xyz, int m);
@@ -695,6 +711,8 @@ int mml_map_bank_download(mml_ctx* ctx, int bank, int kind, float* xyz, int capa
 int mml_slot_bind_bank(mml_ctx* ctx, int first_slot, int count, const int* banks);
 int mml_slot_bank_get(mml_ctx* ctx, int first_slot, int count, int* banks);
 int mml_map_bank_increment(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl, int* n_corner, int* n_surf);
+int mml_map_bank_increment_segmented(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl, int* n_corner, int* n_surf);
+int mml_debug_bank_increment_budget(mml_ctx* ctx, long points);
 int mml_map_bank_set_global(mml_ctx* ctx, int bank, int kind, const float* xyz, const int* cube, int m, const int* cen);
 int mml_map_bank_global_append(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl);
 int mml_map_bank_global_increment(mml_ctx* ctx, int n, const int* banks, const double* T_wl, int* n_corner, int* n_surf);

@@ -1246,17 +1246,24 @@ class Context:
         self._ck(lib().mml_map_bank_download(self._h, C.c_int(bank), C.c_int(kind), _p(out), C.c_int(n.value), C.byref(n)))
         return out[:n.value].copy()
 
-    def bank_increment(self, banks, slots, T_wl):
+    def bank_increment(self, banks, slots, T_wl, segmented=False):
         """Estimator::MapIncrementLocal for len(banks) distinct banks in one call: bank banks[i] grows by the stacks of slot
-        slots[i] at T_wl[i] (4 x 4).  Returns the new (corner, surf) map sizes, one pair of arrays entry per bank."""
+        slots[i] at T_wl[i] (4 x 4).  Returns the new (corner, surf) map sizes, one pair of arrays entry per bank.
+        segmented=True: mml_map_bank_increment_segmented -- the same banks, bit for bit, from one chain of launches with 2 + R
+        host synchronisations whatever len(banks) is; a slot without a stack is refused before any bank changes."""
         b = np.ascontiguousarray(banks, dtype=np.int32).reshape(-1)
         s = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
         T = _f64(T_wl).reshape(-1, 16)
         if not (len(b) == len(s) == len(T)):
             raise ValueError("one slot and one pose per bank")
         nc, ns = np.zeros(max(len(b), 1), np.int32), np.zeros(max(len(b), 1), np.int32)
-        self._ck(lib().mml_map_bank_increment(self._h, C.c_int(len(b)), _p(b), _p(s), _p(T), _p(nc), _p(ns)))
+        call = lib().mml_map_bank_increment_segmented if segmented else lib().mml_map_bank_increment
+        self._ck(call(self._h, C.c_int(len(b)), _p(b), _p(s), _p(T), _p(nc), _p(ns)))
         return nc[:len(b)], ns[:len(b)]
+
+    def debug_bank_increment_budget(self, points):
+        """mml_debug_bank_increment_budget (a test hook): the ring points a segmented bank_increment works on at a time."""
+        self._ck(lib().mml_debug_bank_increment_budget(self._h, C.c_long(int(points))))
 
     # ---- a bank's global cube map: its own MAP_MANAGER store and match copy (include/mmloam_hip.h, "map banks") ----
     def bank_set_global(self, bank, kind, xyz, cube, cen=None):

@@ -15,6 +15,7 @@
 #include <cstring>
 #include <string.h>
 
+#include "grid_cell_rule.h"
 #include "mml_internal.h"
 #include "voxel_sort_dev.h"
 
@@ -1179,22 +1180,13 @@ static int build_grid_into(mml_ctx* ctx, MmlGrid& g, float4* orig, const float* 
     MML_HIP(hipStreamSynchronize(s));
     float bbox[6];
     for (int c = 0; c < 6; ++c) bbox[c] = mml_funkey(bbox_keys[c]);
-    const long long max_cells = (long long)4 * ctx->MM + 4096;
+    const long long max_cells = mml_grid_max_cells(ctx->MM);
     const int blocks = (m + 255) / 256;
     int dim[3];
     // The configured cell edge suits a voxel-filtered map (<= 1 point per leaf).  If the cloud is denser than
-    // that, shrink the cell until an occupied cell holds <= 12 points on average (bounded by the cell budget).
+    // that, shrink the cell until an occupied cell holds <= 12 points on average (bounded by the cell budget): grid_cell_rule.h.
     for (int round = 0;; ++round) {
-        for (;;) {
-            long long total = 1;
-            for (int c = 0; c < 3; ++c) {
-                dim[c] = (int)floorf((bbox[3 + c] - bbox[c]) / cell) + 1;
-                if (dim[c] < 1) dim[c] = 1;
-                total *= dim[c];
-            }
-            if (total <= max_cells) break;
-            cell *= 1.26f;
-        }
+        mml_grid_fit_cell(bbox, max_cells, cell, dim);
         g.cell = cell;
         g.inv_cell = 1.0f / cell;
         for (int c = 0; c < 3; ++c) {
@@ -1214,9 +1206,7 @@ static int build_grid_into(mml_ctx* ctx, MmlGrid& g, float4* orig, const float* 
         int occ = 1;
         MML_HIP(hipMemcpyAsync(&occ, d_occ, sizeof(int), hipMemcpyDeviceToHost, s));
         MML_HIP(hipStreamSynchronize(s));
-        const double per_cell = (double)m / (occ > 0 ? occ : 1);
-        const long long next_total = (long long)g.ncell * 8;
-        if (per_cell <= 12.0 || round >= 4 || next_total > max_cells) break;
+        if (!mml_grid_refine(m, occ, round, g.ncell, max_cells)) break;
         cell *= 0.5f;
     }
     hipLaunchKernelGGL(k_gather_sorted, dim3(blocks), dim3(256), 0, s, orig, ctx->map_vals2, m, g.pts);
@@ -1242,6 +1232,177 @@ int mml_build_grid(mml_ctx* ctx, const MmlMapRef& map, int kind, const float* h_
 // Same, for a cloud that is already on the device in the map's map_tmp + kind * MM (device-side map upkeep).
 int mml_build_grid_device(mml_ctx* ctx, const MmlMapRef& map, int kind, int m) {
     return mml_build_grid(ctx, map, kind, nullptr, m);
+}
+
+// ---- build_grid_into for many clouds at once (the segmented map-bank increment, map_upkeep.hip) --------------------------------
+// A segment is one cloud with its own grid.  The segments' points lie behind one offset table; a round keys every point by
+// (segment << 32 | cell in the segment's own grid) and ONE stable radix sort orders all of them: the segment is the key's high word
+// and the rows were in segment order, so a segment's points stay in its own rows [off, off + m), in the order k_cell_keys and the
+// 32-bit sort of build_grid_into give them.  A workgroup serves one segment (blockIdx.y), so its table row is wave-uniform and is
+// read through scalar loads.
+namespace {
+struct GridSegDev {
+    const float4* orig;  // the unsorted cloud
+    float4* pts;         // the grid's sorted points
+    int* cell_start;
+    GridDev g;
+    int off, m;  // the segment's rows in the key / value arrays
+};
+
+__global__ __launch_bounds__(256) void k_bseg_cell_keys(const GridSegDev* __restrict__ tab, unsigned long long* __restrict__ keys,
+                                                        unsigned* __restrict__ vals) {
+    const GridSegDev& S = tab[blockIdx.y];
+    const GridDev g = S.g;
+    const int m = S.m, off = S.off;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < m; i += gridDim.x * 256) {
+        const float4 p = S.orig[i];
+        const int cx = cell_coord(p.x, g.ox, g.inv_cell, g.dx);
+        const int cy = cell_coord(p.y, g.oy, g.inv_cell, g.dy);
+        const int cz = cell_coord(p.z, g.oz, g.inv_cell, g.dz);
+        keys[off + i] = ((unsigned long long)blockIdx.y << 32) | (unsigned)(cx + g.dx * (cy + g.dy * cz));
+        vals[off + i] = (unsigned)i;
+    }
+}
+
+// occupied cells of every segment = key changes inside its rows
+__global__ __launch_bounds__(256) void k_bseg_count_occupied(const GridSegDev* __restrict__ tab, const unsigned long long* __restrict__ keys,
+                                                             int* __restrict__ occ) {
+    const int m = tab[blockIdx.y].m;
+    const unsigned long long* k = keys + tab[blockIdx.y].off;
+    for (int base = blockIdx.x * 256; base < m; base += gridDim.x * 256) {  // (whole wavefronts: the ballot)
+        const int i = base + threadIdx.x;
+        const bool head = i < m && (i == 0 || k[i] != k[i - 1]);
+        const unsigned long long b = __ballot(head);
+        if ((threadIdx.x & 63) == 0 && b) atomicAdd(occ + blockIdx.y, __popcll(b));
+    }
+}
+
+__global__ __launch_bounds__(256) void k_bseg_gather_sorted(const GridSegDev* __restrict__ tab, const unsigned* __restrict__ vals) {
+    const GridSegDev& S = tab[blockIdx.y];
+    const int m = S.m;
+    const unsigned* v = vals + S.off;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < m; i += gridDim.x * 256) {
+        const unsigned src = v[i];
+        float4 p = S.orig[src];
+        p.w = __uint_as_float(src);
+        S.pts[i] = p;
+    }
+}
+
+// cell_start[c] = first sorted point of the segment whose cell >= c (lower bound); cell_start[ncell] = m.  m = 0: two zero ints.
+__global__ __launch_bounds__(256) void k_bseg_cell_start(const GridSegDev* __restrict__ tab, const unsigned long long* __restrict__ keys) {
+    const GridSegDev& S = tab[blockIdx.y];
+    const int m = S.m, ncell = S.g.ncell;
+    const unsigned long long* k = keys + S.off;
+    for (int c = blockIdx.x * 256 + threadIdx.x; c <= ncell; c += gridDim.x * 256) {
+        int lo = 0, hi = m;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if ((unsigned)k[mid] < (unsigned)c)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        S.cell_start[c] = lo;
+    }
+}
+}  // namespace
+
+size_t mml_grid_seg_table_bytes(int nseg) { return sizeof(GridSegDev) * (size_t)nseg; }
+
+// The grids of nseg clouds that are on the device (jobs[g].orig, jobs[g].m points, bounding box jobs[g].bbox_keys), each what
+// build_grid_into makes of that cloud: the host takes every segment through the rounds of grid_cell_rule.h, one sort, one count and
+// ONE read-back of the nseg counts per round for all of them.  A segment that has finished keeps its cell edge and is keyed again in
+// the later rounds of the others: the same keys through the same stable sort are the same order, and no second set of buffers has
+// to hold a finished segment's rows.  *rounds: the rounds run = the host synchronisations made.
+int mml_build_grids_segmented(mml_ctx* ctx, int nseg, const MmlGridJob* jobs, const MmlGridSegScratch& W, int* rounds) {
+    hipStream_t s = MML_STREAM(ctx);
+    MmlStageScope t(ctx, "map_build");
+    GridSegDev* h_tab = static_cast<GridSegDev*>(W.tab_h);
+    const GridSegDev* d_tab = static_cast<const GridSegDev*>(W.tab_d);
+    const long long max_cells = mml_grid_max_cells(ctx->MM);
+    std::vector<float> cell((size_t)nseg);
+    std::vector<char> live((size_t)nseg);
+    std::vector<float> bbox(6 * (size_t)nseg);
+    long long total = 0;
+    int max_m = 0;
+    for (int g = 0; g < nseg; ++g) {
+        const MmlGridJob& J = jobs[g];
+        MmlGrid& G = *J.g;
+        G.m = J.m;
+        cell[g] = J.cell;
+        live[g] = J.m > 0;
+        for (int c = 0; c < 6; ++c) bbox[6 * (size_t)g + c] = mml_funkey(J.bbox_keys[c]);
+        if (J.m == 0) {  // (build_grid_into's empty grid; k_bseg_cell_start writes its two zero ints)
+            G.dim[0] = G.dim[1] = G.dim[2] = 1;
+            G.ncell = 1;
+            G.cell = 1.f;
+            G.inv_cell = 1.f;
+            G.origin[0] = G.origin[1] = G.origin[2] = 0.f;
+        }
+        memset(static_cast<void*>(&h_tab[g]), 0, sizeof(GridSegDev));
+        h_tab[g].orig = J.orig;
+        h_tab[g].pts = G.pts;
+        h_tab[g].cell_start = G.cell_start;
+        h_tab[g].off = (int)total;
+        h_tab[g].m = J.m;
+        total += J.m;
+        if (J.m > max_m) max_m = J.m;
+    }
+    MML_REQUIRE(total <= (long long)W.cap, MML_ERR_CAPACITY, "segmented grid build: more points than the scratch holds");
+    int seg_bits = 1;
+    while ((1 << seg_bits) < nseg) ++seg_bits;
+    const int blocks = max_m ? ((max_m + 255) / 256 < 256 ? (max_m + 255) / 256 : 256) : 1;
+    *rounds = 0;
+    int max_ncell = 1;
+    for (int round = 0; total > 0; ++round) {
+        for (int g = 0; g < nseg; ++g) {
+            MmlGrid& G = *jobs[g].g;
+            if (live[g]) {
+                int dim[3];
+                mml_grid_fit_cell(&bbox[6 * (size_t)g], max_cells, cell[g], dim);
+                G.cell = cell[g];
+                G.inv_cell = 1.0f / cell[g];
+                for (int c = 0; c < 3; ++c) {
+                    G.origin[c] = bbox[6 * (size_t)g + c];
+                    G.dim[c] = dim[c];
+                }
+                G.ncell = dim[0] * dim[1] * dim[2];
+            }
+            h_tab[g].g = GridDev{G.origin[0], G.origin[1], G.origin[2], G.inv_cell, G.cell, G.dim[0], G.dim[1], G.dim[2], G.ncell};
+        }
+        MML_HIP(hipMemcpyAsync(W.tab_d, W.tab_h, sizeof(GridSegDev) * (size_t)nseg, hipMemcpyHostToDevice, s));
+        MML_HIP(hipMemsetAsync(W.occ_d, 0, sizeof(int) * (size_t)nseg, s));
+        hipLaunchKernelGGL(k_bseg_cell_keys, dim3(blocks, nseg), dim3(256), 0, s, d_tab, W.keys, W.vals);
+        const int rt = mml_sort_pairs(ctx, ctx->sort_tmp, W.keys, W.keys2, W.vals, W.vals2, (size_t)total, 32 + seg_bits, s);
+        if (rt != MML_OK) return rt;
+        hipLaunchKernelGGL(k_bseg_count_occupied, dim3(blocks, nseg), dim3(256), 0, s, d_tab, W.keys2, W.occ_d);
+        MML_HIP(hipMemcpyAsync(W.occ_h, W.occ_d, sizeof(int) * (size_t)nseg, hipMemcpyDeviceToHost, s));
+        MML_HIP(hipStreamSynchronize(s));
+        ++*rounds;
+        bool again = false;
+        for (int g = 0; g < nseg; ++g) {
+            if (!live[g]) continue;
+            if (mml_grid_refine(jobs[g].m, W.occ_h[g], round, jobs[g].g->ncell, max_cells)) {
+                cell[g] *= 0.5f;
+                again = true;
+            } else {
+                live[g] = 0;
+            }
+        }
+        if (!again) break;
+    }
+    if (total == 0) {  // (every cloud is empty: the table of the empty grids)
+        for (int g = 0; g < nseg; ++g) h_tab[g].g = GridDev{0.f, 0.f, 0.f, 1.f, 1.f, 1, 1, 1, 1};
+        MML_HIP(hipMemcpyAsync(W.tab_d, W.tab_h, sizeof(GridSegDev) * (size_t)nseg, hipMemcpyHostToDevice, s));
+    }
+    for (int g = 0; g < nseg; ++g)
+        if (jobs[g].g->ncell > max_ncell) max_ncell = jobs[g].g->ncell;
+    if (total > 0) hipLaunchKernelGGL(k_bseg_gather_sorted, dim3(blocks, nseg), dim3(256), 0, s, d_tab, W.vals2);
+    const int cblocks = (max_ncell + 1 + 255) / 256 < 1024 ? (max_ncell + 1 + 255) / 256 : 1024;
+    hipLaunchKernelGGL(k_bseg_cell_start, dim3(cblocks, nseg), dim3(256), 0, s, d_tab, W.keys2);
+    MML_HIP(hipGetLastError());
+    return MML_OK;
 }
 
 // a12: the global map handed to Estimate() (Estimator.cpp:1170-1184) as one concatenated cloud with the cube index

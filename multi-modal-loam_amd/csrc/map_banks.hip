@@ -226,6 +226,25 @@ int mml_map_bank_increment(mml_ctx* ctx, int n, const int* banks, const int* slo
     return MML_OK;
 }
 
+int mml_map_bank_increment_segmented(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl, int* n_corner, int* n_surf) {
+    if (!ctx) return MML_ERR_INVALID;
+    MML_REQUIRE(n >= 1 && banks && slots && T_wl, MML_ERR_INVALID, "bad arguments");
+    // all arguments are checked before the device is touched or a bank changes
+    int rc = check_distinct_banks(ctx, n, banks, slots, "mml_map_bank_increment_segmented");
+    if (rc != MML_OK) return rc;
+    rc = enter(ctx);
+    if (rc != MML_OK) return rc;
+    if (!ctx->uploads.empty()) return mml_refuse(ctx, MML_ERR_STATE, "uploads in flight after a drained context");
+    return mml_map_upkeep_increment_segmented(ctx, n, banks, slots, T_wl, n_corner, n_surf);
+}
+
+int mml_debug_bank_increment_budget(mml_ctx* ctx, long points) {
+    if (!ctx) return MML_ERR_INVALID;
+    if (points < 1 || points >= (1l << 31)) return mml_refuse(ctx, MML_ERR_INVALID, "the chunk budget must be in [1, 2^31) points");
+    ctx->bank_inc.budget = points;
+    return MML_OK;
+}
+
 // ---- a bank's global cube map: the own-map calls of capi.hip on mml_cube_bank(ctx, bank) ----
 
 int mml_map_bank_set_global(mml_ctx* ctx, int bank, int kind, const float* xyz, const int* cube, int m, const int* cen) {

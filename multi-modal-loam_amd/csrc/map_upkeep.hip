@@ -358,3 +358,311 @@ int mml_map_upkeep_increment(mml_ctx* ctx, const MmlMapRef& map, int slot, const
     MML_HIP(hipGetLastError());
     return MML_OK;
 }
+
+// ---- mml_map_upkeep_increment for n banks in one chain of launches (mml_map_bank_increment_segmented) --------------------------
+// Segment g = 2 i + kind: bank i of the chunk, kind.  The chunk's rings are concatenated behind one offset table, the voxel filter
+// is mml_downsample_big's pattern (one stable 64-bit radix sort keyed segment << 32 | voxel, one lane per voxel), the grids are
+// mml_build_grids_segmented's.  A workgroup serves one segment (blockIdx.y): its table row is wave-uniform and comes through scalar
+// loads; the sort keeps a segment's points in its own rows [cat_off, cat_off + total), so the kernels behind it index rows the
+// same way.
+namespace {
+struct BankSegDev {
+    double T[12];            // T_wl of the bank's slot (k_to_world's Tf12)
+    const float4* feat;      // the slot's down-sampled stack of this kind
+    float4* ring;            // the bank's ring of this kind, LOCAL_WINDOW x MF
+    float4* map_out;         // the bank's map_tmp + kind * MM
+    int n_feat, ring_slot;   // the stack's size, localMapID % 50
+    int cat_off, total;      // the segment's rows in the concatenation
+    float leaf;
+    int ring_off[mml_ctx::LOCAL_WINDOW + 1];  // k_concat's RingOffsets, relative to cat_off
+};
+
+// k_to_world for every segment: the slot's stack into ring slot ring_slot
+__global__ __launch_bounds__(256) void k_bseg_to_world(const BankSegDev* __restrict__ tab, int MF) {
+    const BankSegDev& S = tab[blockIdx.y];
+    const int n = S.n_feat;
+    float4* out = S.ring + (size_t)S.ring_slot * MF;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
+        const float4 f = S.feat[i];
+        const double x = f.x, y = f.y, z = f.z;
+        float4 o;
+        o.x = (float)(((S.T[0] * x + S.T[1] * y) + S.T[2] * z) + S.T[3]);
+        o.y = (float)(((S.T[4] * x + S.T[5] * y) + S.T[6] * z) + S.T[7]);
+        o.z = (float)(((S.T[8] * x + S.T[9] * y) + S.T[10] * z) + S.T[11]);
+        o.w = 0.f;
+        out[i] = o;
+    }
+}
+
+// k_concat for every segment, one lane per point of the concatenation (the ring slot of a row: upper bound in the segment's 51
+// offsets, held in LDS), and the bounding box of what it copies (getMinMax3D of the cloud the filter sees)
+__global__ __launch_bounds__(256) void k_bseg_concat_bbox(const BankSegDev* __restrict__ tab, int MF, float4* __restrict__ cat,
+                                                          int* __restrict__ bbox) {
+    constexpr int W = mml_ctx::LOCAL_WINDOW;
+    __shared__ int s_off[W + 1];
+    const BankSegDev& S = tab[blockIdx.y];
+    const int total = S.total;
+    if ((int)blockIdx.x * 256 >= total) return;  // (the whole workgroup)
+    if (threadIdx.x <= W) s_off[threadIdx.x] = S.ring_off[threadIdx.x];
+    __syncthreads();
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+        int lo = 0, hi = W;  // the last slot whose offset is <= i (empty slots share an offset: the last of them is the one with points)
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (s_off[mid] <= i)
+                lo = mid;
+            else
+                hi = mid;
+        }
+        const float4 p = S.ring[(size_t)lo * MF + (i - s_off[lo])];
+        cat[S.cat_off + i] = p;
+        mn[0] = fminf(mn[0], p.x);
+        mn[1] = fminf(mn[1], p.y);
+        mn[2] = fminf(mn[2], p.z);
+        mx[0] = fmaxf(mx[0], p.x);
+        mx[1] = fmaxf(mx[1], p.y);
+        mx[2] = fmaxf(mx[2], p.z);
+    }
+    mml_bbox_block_reduce(mn, mx, bbox + 6 * (size_t)blockIdx.y);
+}
+
+// k_vox_keys for every segment: segment << 32 | PCL voxel index in the segment's own box and leaf
+__global__ __launch_bounds__(256) void k_bseg_vox_keys(const BankSegDev* __restrict__ tab, const float4* __restrict__ cat,
+                                                       const int* __restrict__ bbox, unsigned long long* __restrict__ keys,
+                                                       unsigned* __restrict__ vals) {
+    const BankSegDev& S = tab[blockIdx.y];
+    const int total = S.total, off = S.cat_off;
+    if ((int)blockIdx.x * 256 >= total) return;
+    const MmlVoxGrid G = mml_vox_grid_of_keys(bbox + 6 * (size_t)blockIdx.y, S.leaf);
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+        const float4 p = cat[off + i];
+        const unsigned idx = G.index(p.x, p.y, p.z);
+        // (more than INT_MAX voxels in the box: PCL returns the cloud unfiltered = every point its own voxel, in input order)
+        keys[off + i] = ((unsigned long long)blockIdx.y << 32) | (G.overflows ? (unsigned)i : idx);
+        vals[off + i] = (unsigned)(off + i);
+    }
+}
+
+// k_vox_centroid for every segment: one lane per voxel writes the centroid into the bank's map_tmp; the lane of the segment's
+// first row publishes the segment's voxel count (seg_m was zeroed: a segment without points keeps 0)
+__global__ __launch_bounds__(256) void k_bseg_centroid(const BankSegDev* __restrict__ tab, const float4* __restrict__ cat,
+                                                       const unsigned long long* __restrict__ keys, const unsigned* __restrict__ vals,
+                                                       const int* __restrict__ flag, const int* __restrict__ pos, int cap,
+                                                       int* __restrict__ seg_m) {
+    const BankSegDev& S = tab[blockIdx.y];
+    const int off = S.cat_off, end = S.cat_off + S.total;
+    for (int s = off + blockIdx.x * 256 + threadIdx.x; s < end; s += gridDim.x * 256) {
+        if (s == off) seg_m[blockIdx.y] = pos[end - 1] + flag[end - 1] - pos[off];
+        if (!flag[s]) continue;
+        const int dst = pos[s] - pos[off];
+        if (dst >= cap) continue;
+        float4 sum;
+        const float c = static_cast<float>(mml_voxel_run_sum(cat, keys, vals, s, end, 0, sum));
+        S.map_out[dst] = make_float4(sum.x / c, sum.y / c, sum.z / c, 0.f);
+    }
+}
+
+// k_bbox of every segment's filtered cloud (its size is on the device)
+__global__ __launch_bounds__(256) void k_bseg_bbox_out(const BankSegDev* __restrict__ tab, const int* __restrict__ seg_m, int cap,
+                                                       int* __restrict__ bbox) {
+    const float4* pts = tab[blockIdx.y].map_out;
+    int m = seg_m[blockIdx.y];
+    m = m < cap ? m : cap;
+    if ((int)blockIdx.x * 256 >= m) return;  // (the whole workgroup)
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < m; i += gridDim.x * 256) {
+        const float4 p = pts[i];
+        mn[0] = fminf(mn[0], p.x);
+        mn[1] = fminf(mn[1], p.y);
+        mn[2] = fminf(mn[2], p.z);
+        mx[0] = fmaxf(mx[0], p.x);
+        mx[1] = fmaxf(mx[1], p.y);
+        mx[2] = fmaxf(mx[2], p.z);
+    }
+    mml_bbox_block_reduce(mn, mx, bbox + 6 * (size_t)blockIdx.y);
+}
+
+// one chunk of banks [i0, i1) of the call: steps 2-4.  nf: the call's 2 n stack sizes.
+int bank_increment_chunk(mml_ctx* ctx, int i0, int i1, const int* banks, const int* slots, const double* T_wl, const int* nf,
+                         int* n_corner, int* n_surf) {
+    constexpr int W = mml_ctx::LOCAL_WINDOW;
+    hipStream_t s = MML_STREAM(ctx);
+    mml_ctx::BankInc& K = ctx->bank_inc;
+    const int nb = i1 - i0, nseg = 2 * nb;
+    // the chunk's block, the same layout on the device and in the pinned twin
+    MmlCarve<16> carve;
+    const MmlField<BankSegDev> f_seg = carve.take<BankSegDev>((size_t)nseg);
+    const MmlField<int> f_bbox_in = carve.take<int>(6 * (size_t)nseg);
+    const MmlField<int> f_back = carve.take<int>(7 * (size_t)nseg);  // read back in one copy: nseg sizes, nseg filtered boxes
+    const size_t up_bytes = carve.bytes();
+    const MmlField<char> f_grid = carve.take<char>(mml_grid_seg_table_bytes(nseg));
+    const MmlField<int> f_occ = carve.take<int>((size_t)nseg);
+    BankSegDev* h_seg = f_seg.in(K.tab.h);
+    int* h_back = f_back.in(K.tab.h);
+    const int empty[6] = MML_BBOX_EMPTY;
+    long long total = 0;
+    int max_feat = 0, max_total = 0;
+    for (int i = i0; i < i1; ++i) {
+        const MmlMapRef map = mml_map_bank(ctx, banks[i]);
+        const int Id = (int)(*map.local_map_id % W);  // :1597
+        for (int kind = 0; kind < 2; ++kind) {
+            const int g = 2 * (i - i0) + kind, n = nf[2 * (size_t)i + kind];
+            map.ring_n[kind][Id] = n;
+            BankSegDev& S = h_seg[g];
+            memset(static_cast<void*>(&S), 0, sizeof(S));
+            memcpy(S.T, T_wl + 16 * (size_t)i, sizeof(double) * 12);
+            S.feat = ctx->ft_xyz[kind] + (size_t)slots[i] * ctx->MF;
+            S.ring = map.ring[kind];
+            S.map_out = map.map_tmp + (size_t)kind * ctx->MM;
+            S.n_feat = n;
+            S.ring_slot = Id;
+            S.leaf = kind == 0 ? ctx->cfg.leaf_corner : ctx->cfg.leaf_surf;
+            for (int r = 0; r < W; ++r) S.ring_off[r + 1] = S.ring_off[r] + map.ring_n[kind][r];
+            S.cat_off = (int)total;
+            S.total = S.ring_off[W];
+            total += S.total;
+            if (n > max_feat) max_feat = n;
+            if (S.total > max_total) max_total = S.total;
+            for (int c = 0; c < 6; ++c) f_bbox_in.in(K.tab.h)[6 * (size_t)g + c] = h_back[nseg + 6 * (size_t)g + c] = empty[c];
+            h_back[g] = 0;
+        }
+    }
+    MML_REQUIRE(total <= (long long)K.cap, MML_ERR_CAPACITY, "segmented bank increment: more ring points than the scratch holds");
+    MML_HIP(hipMemcpyAsync(K.tab.d, K.tab.h, up_bytes, hipMemcpyHostToDevice, s));
+    const BankSegDev* d_seg = f_seg.in(K.tab.d);
+    int* d_bbox_in = f_bbox_in.in(K.tab.d);
+    int* d_seg_m = f_back.in(K.tab.d);
+    int* d_bbox_out = d_seg_m + nseg;
+    unsigned long long* keys2 = K.keys + K.cap;
+    unsigned* vals2 = K.vals + K.cap;
+    int* flag = K.flag;
+    int* pos = K.flag + K.cap + 1;
+    auto blocks_for = [](int n) { return n > 0 ? ((n + 255) / 256 < 256 ? (n + 255) / 256 : 256) : 1; };
+    if (max_feat) hipLaunchKernelGGL(k_bseg_to_world, dim3(blocks_for(max_feat), nseg), dim3(256), 0, s, d_seg, ctx->MF);
+    if (total) {
+        const int blocks = blocks_for(max_total);
+        hipLaunchKernelGGL(k_bseg_concat_bbox, dim3(blocks, nseg), dim3(256), 0, s, d_seg, ctx->MF, K.cat, d_bbox_in);
+        hipLaunchKernelGGL(k_bseg_vox_keys, dim3(blocks, nseg), dim3(256), 0, s, d_seg, K.cat, d_bbox_in, K.keys, K.vals);
+        int seg_bits = 1;
+        while ((1 << seg_bits) < nseg) ++seg_bits;
+        int rc = mml_sort_pairs(ctx, ctx->sort_tmp, K.keys, keys2, K.vals, vals2, (size_t)total, 32 + seg_bits, s);
+        if (rc != MML_OK) return rc;
+        hipLaunchKernelGGL(k_run_heads<unsigned long long>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, keys2, (int)total, 0,
+                           ~0ull, flag);
+        rc = mml_exclusive_scan(ctx, ctx->sort_tmp, flag, pos, (size_t)total, s);
+        if (rc != MML_OK) return rc;
+        hipLaunchKernelGGL(k_bseg_centroid, dim3(blocks, nseg), dim3(256), 0, s, d_seg, K.cat, keys2, vals2, flag, pos, ctx->MM, d_seg_m);
+        hipLaunchKernelGGL(k_bseg_bbox_out, dim3(blocks, nseg), dim3(256), 0, s, d_seg, d_seg_m, ctx->MM, d_bbox_out);
+    }
+    MML_HIP(hipMemcpyAsync(h_back, d_seg_m, f_back.bytes(), hipMemcpyDeviceToHost, s));
+    MML_HIP(hipStreamSynchronize(s));  // the chunk's second synchronisation of 2 + R (the first read the stack sizes)
+    for (int g = 0; g < nseg; ++g)
+        if (h_back[g] > ctx->MM) return mml_refuse(ctx, MML_ERR_CAPACITY, "map bank %d: filtered local map larger than max_map_points", banks[i0 + g / 2]);
+    std::vector<MmlGridJob> jobs((size_t)nseg);
+    for (int g = 0; g < nseg; ++g) {
+        const MmlMapRef map = mml_map_bank(ctx, banks[i0 + g / 2]);
+        const int kind = g & 1;
+        map.have_map[kind] = false;  // (mml_build_grid)
+        map.grid[kind].tags = nullptr;
+        jobs[g] = MmlGridJob{&map.grid[kind], map.map_tmp + (size_t)kind * ctx->MM, kind == 0 ? ctx->cfg.cell_corner : ctx->cfg.cell_surf,
+                             h_back[g], h_back + nseg + 6 * (size_t)g};
+    }
+    ctx->banks.dirty = true;  // (the descriptor table of a context with banks holds a copy of these grids)
+    MmlGridSegScratch G{K.keys, keys2, K.vals, vals2, K.cap, f_grid.in(K.tab.d), f_grid.in(K.tab.h), f_occ.in(K.tab.d), f_occ.in(K.tab.h)};
+    int rounds = 0;
+    const int rc = mml_build_grids_segmented(ctx, nseg, jobs.data(), G, &rounds);
+    if (rc != MML_OK) return rc;
+    for (int i = i0; i < i1; ++i) {
+        const MmlMapRef map = mml_map_bank(ctx, banks[i]);
+        for (int kind = 0; kind < 2; ++kind) {
+            map.have_map[kind] = true;
+            map.local_map_n[kind] = h_back[2 * (i - i0) + kind];
+        }
+        if (n_corner) n_corner[i] = map.local_map_n[0];
+        if (n_surf) n_surf[i] = map.local_map_n[1];
+        ++*map.local_map_id;  // :1642
+    }
+    return MML_OK;
+}
+}  // namespace
+
+int mml_map_upkeep_increment_segmented(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl, int* n_corner, int* n_surf) {
+    constexpr int W = mml_ctx::LOCAL_WINDOW;
+    hipStream_t s = MML_STREAM(ctx);
+    mml_ctx::BankInc& K = ctx->bank_inc;
+    // step 1: the stack sizes in one copy (the context's 2 B ints), those of the n slots checked before a bank changes
+    std::vector<int> nf(2 * (size_t)n);
+    {
+        int* h = reinterpret_cast<int*>(mml_stage_alloc(ctx, (size_t)ctx->B + 1));  // pinned
+        MML_HIP(hipMemcpyAsync(h, ctx->ft_n, sizeof(int) * 2 * (size_t)ctx->B, hipMemcpyDeviceToHost, s));
+        MML_HIP(hipStreamSynchronize(s));
+        for (int i = 0; i < n; ++i)
+            for (int kind = 0; kind < 2; ++kind) nf[2 * (size_t)i + kind] = h[(size_t)kind * ctx->B + slots[i]];
+    }
+    for (int i = 0; i < n; ++i)
+        for (int kind = 0; kind < 2; ++kind) {
+            const int f = nf[2 * (size_t)i + kind];
+            if (f < 0 || f > ctx->MF) return mml_refuse(ctx, MML_ERR_STATE, "slot %d holds no down-sampled feature stack", slots[i]);
+        }
+    // every segment's ring total after the write, the filter's own limit (voxel_filter_device) and the chunks: greedy, in call order
+    std::vector<long long> pts((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        const MmlMapRef map = mml_map_bank(ctx, banks[i]);
+        const int Id = (int)(*map.local_map_id % W);
+        pts[i] = 0;
+        for (int kind = 0; kind < 2; ++kind) {
+            long long t = nf[2 * (size_t)i + kind];
+            for (int r = 0; r < W; ++r)
+                if (r != Id) t += map.ring_n[kind][r];
+            if (t > ctx->MM) return mml_refuse(ctx, MML_ERR_CAPACITY, "map bank %d: cloud larger than max_map_points", banks[i]);
+            pts[i] += t;
+        }
+    }
+    std::vector<int> cut(1, 0);  // chunk c = banks [cut[c], cut[c + 1]) of the call
+    long long run = 0, max_pts = 1;
+    int max_banks = 1;
+    for (int i = 0; i < n; ++i) {
+        if (i > cut.back() && run + pts[i] > K.budget) {
+            cut.push_back(i);
+            run = 0;
+        }
+        run += pts[i];
+        if (run > max_pts) max_pts = run;
+        if (i + 1 - cut.back() > max_banks) max_banks = i + 1 - cut.back();
+    }
+    cut.push_back(n);
+    MML_REQUIRE(max_pts < (1ll << 31), MML_ERR_CAPACITY, "segmented bank increment: a bank's rings exceed 2^31 points");
+    // memory: the banks' rings (a first increment), the scratch for the largest chunk, its tables, the sort's temporary storage --
+    // all before the first launch, so that nothing is replaced while a chunk's kernels run
+    const size_t ring_pts = (size_t)W * ctx->MF;
+    for (int i = 0; i < n; ++i) {
+        const MmlMapRef map = mml_map_bank(ctx, banks[i]);
+        if (map.ring_mem->present()) continue;
+        const int rc = map.ring_mem->reserve(ctx, {mml_part(map.ring[0], ring_pts), mml_part(map.ring[1], ring_pts)});
+        if (rc != MML_OK) return rc;
+    }
+    if ((size_t)max_pts > K.cap || !K.mem.present()) {
+        const size_t cap = (size_t)max_pts;
+        K.cap = 0;
+        const int rc = K.mem.reserve(ctx, {mml_part(K.cat, cap), mml_part(K.keys, 2 * cap), mml_part(K.vals, 2 * cap), mml_part(K.flag, 2 * (cap + 1))});
+        if (rc != MML_OK) return rc;
+        K.cap = cap;
+    }
+    {
+        const size_t nseg = 2 * (size_t)max_banks;
+        const size_t bytes = sizeof(BankSegDev) * nseg + sizeof(int) * 14 * nseg + mml_grid_seg_table_bytes((int)nseg) + 16 * 8;
+        int rc = K.tab.reserve(ctx, bytes);
+        if (rc != MML_OK) return rc;
+        int seg_bits = 1;
+        while ((1u << seg_bits) < nseg) ++seg_bits;
+        rc = ctx->sort_tmp.reserve(ctx, mml_sort_pairs_bytes<unsigned long long>((size_t)max_pts, 32 + seg_bits, s));
+        if (rc != MML_OK) return rc;
+    }
+    for (size_t c = 0; c + 1 < cut.size(); ++c) {
+        const int rc = bank_increment_chunk(ctx, cut[c], cut[c + 1], banks, slots, T_wl, nf.data(), n_corner, n_surf);
+        if (rc != MML_OK) return rc;
+    }
+    MML_HIP(hipGetLastError());
+    return MML_OK;
+}

@@ -356,6 +356,18 @@ struct mml_ctx {
     MmlStaging<char, false> wire_stage;      // raw message bytes on their way in / out (one call at a time; grows to the largest)
     int local_map_n[2] = {0, 0};
     MmlBanks banks;                    // map banks (map_banks.hip): further local maps, and which slot is matched against which
+    // scratch of the segmented bank increment (map_upkeep.hip mml_map_upkeep_increment_segmented), sized by the ring points of
+    // the largest chunk of banks a call has worked on: 48 bytes per point
+    struct BankInc {
+        float4* cat = nullptr;               // the chunk's rings, concatenated
+        unsigned long long* keys = nullptr;  // 2 x cap: sort keys in / out
+        unsigned* vals = nullptr;            // 2 x cap
+        int* flag = nullptr;                 // 2 x (cap + 1): run heads, positions
+        size_t cap = 0;                      // points
+        MmlGroup mem;                        // owns the four
+        MmlStaging<char> tab;                // a chunk's tables and read-backs: device block and pinned twin
+        long budget = MML_BANK_INCREMENT_BUDGET;  // ring points per chunk (mml_debug_bank_increment_budget)
+    } bank_inc;
     float4* map_tmp = nullptr;
     unsigned* map_keys = nullptr;
     unsigned* map_keys2 = nullptr;
@@ -400,6 +412,8 @@ struct mml_ctx {
         cmatch.release();
         ring_mem.release();
         banks.release();
+        bank_inc.mem.release();
+        bank_inc.tab.release();
         clive.mem.release();
         cube_scratch.release();
         wire_stage.release();
@@ -511,6 +525,28 @@ int mml_gicp_align_device(mml_ctx* ctx, const char* who, const float4* d_src, in
 int mml_downsample_big(mml_ctx* ctx, int first, int count);
 int mml_downsample_redo_overflow(mml_ctx* ctx, int first, int count, std::vector<int>* redone);
 int mml_map_upkeep_increment(mml_ctx* ctx, const MmlMapRef& map, int slot, const double* T_wl, int* n_out);
+// The same for n distinct banks in one chain of launches (map_upkeep.hip); the caller has checked the arguments and drained the
+// context.  Checks every slot's stack before a bank changes.
+int mml_map_upkeep_increment_segmented(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl, int* n_corner, int* n_surf);
+// map_assoc.hip: build_grid_into for nseg clouds that are on the device, one sort and one read-back per refinement round for all
+// of them.  A job: the grid to fill (its pts / cell_start are the destination), the unsorted cloud, the configured cell edge, the
+// cloud's size and its bounding box as six keys (MML_BBOX_EMPTY where m = 0).
+struct MmlGridJob {
+    MmlGrid* g;
+    const float4* orig;
+    float cell;
+    int m;
+    const int* bbox_keys;
+};
+struct MmlGridSegScratch {
+    unsigned long long *keys, *keys2;  // cap each
+    unsigned *vals, *vals2;
+    size_t cap;                        // points
+    void *tab_d, *tab_h;               // mml_grid_seg_table_bytes(nseg) on the device and pinned
+    int *occ_d, *occ_h;                // nseg ints each, occ_h pinned
+};
+size_t mml_grid_seg_table_bytes(int nseg);
+int mml_build_grids_segmented(mml_ctx* ctx, int nseg, const MmlGridJob* jobs, const MmlGridSegScratch& W, int* rounds);
 // The state of one global cube map, by reference: the context's own (mml_cube_own) or a bank's (mml_cube_bank).  The grid builds
 // and the store's upkeep take the map they work on as this parameter, as the local map's take MmlMapRef.
 struct MmlCubeRef {

@@ -88,11 +88,15 @@ class Context {
     // maps, the bank of every slot (-1: the context's own map, the one the Estimator below uses), and MapIncrementLocal for n
     // distinct banks in one call (T_wl: n x 16, row-major; the sizes may be null).  A bank has its own global cube map, which a
     // bound slot is matched against first: set it, or feed its MAP_MANAGER store (featureAssociateToMap / MapIncrement) for n
-    // distinct banks in one call each.
+    // distinct banks in one call each.  bank_increment, segmented = true: mml_map_bank_increment_segmented -- the same banks bit
+    // for bit from one chain of launches (2 + R host synchronisations whatever n is); a slot without a stack is refused before
+    // any bank changes.
     void map_banks(int n) { check(ctx_, mml_map_banks_create(ctx_, n), "map_banks"); }
     void bind_banks(int first_slot, int count, const int* banks) { check(ctx_, mml_slot_bind_bank(ctx_, first_slot, count, banks), "bind_banks"); }
-    void bank_increment(int n, const int* banks, const int* slots, const double* T_wl, int* n_corner = nullptr, int* n_surf = nullptr) {
-        check(ctx_, mml_map_bank_increment(ctx_, n, banks, slots, T_wl, n_corner, n_surf), "bank_increment");
+    void bank_increment(int n, const int* banks, const int* slots, const double* T_wl, int* n_corner = nullptr, int* n_surf = nullptr,
+                        bool segmented = false) {
+        check(ctx_, (segmented ? mml_map_bank_increment_segmented : mml_map_bank_increment)(ctx_, n, banks, slots, T_wl, n_corner, n_surf),
+              "bank_increment");
     }
     void bank_set_global(int bank, int kind, const float* xyz, const int* cube, int m, const int* cen = nullptr) {
         check(ctx_, mml_map_bank_set_global(ctx_, bank, kind, xyz, cube, m, cen), "bank_set_global");

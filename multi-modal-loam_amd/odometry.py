@@ -189,13 +189,20 @@ class BatchLidarOdometry:
     global_map=True: bank w also keeps sequence w's cube store and match copy, on the map thread's schedule of the module
     docstring (the one the reference's asynchronous thread follows when it keeps up): per round ONE bank_global_append call for
     the sequences whose scan the thread takes and ONE bank_global_increment call for those whose MapIncrement is due.  The
-    context's OWN global cube map must stay unset either way: a bound slot and it exclude each other."""
+    context's OWN global cube map must stay unset either way: a bound slot and it exclude each other.
+    increment: "loop" (the default) -- bank_increment works the growing banks through one after the other; "segmented" -- it
+    works them in one chain of launches (Context.bank_increment(..., segmented=True)): the same maps bit for bit, 2 + R host
+    synchronisations per round whatever n is."""
 
-    def __init__(self, ctx, n, exTlb=None, lidar_mode=2, max_outer=5, inner_iters=10, global_map=False, map_skip_frame=2):
+    def __init__(self, ctx, n, exTlb=None, lidar_mode=2, max_outer=5, inner_iters=10, global_map=False, map_skip_frame=2,
+                 increment="loop"):
         if n < 1:
             raise ValueError("n must be at least 1")
         if map_skip_frame < 1:
             raise ValueError("map_skip_frame must be at least 1")
+        if increment not in ("loop", "segmented"):
+            raise ValueError('increment must be "loop" or "segmented"')
+        self.increment = increment
         self.global_map, self.map_skip_frame = global_map, map_skip_frame
         self.ctx, self.n = ctx, n
         self.exTlb = np.eye(4) if exTlb is None else np.asarray(exTlb, dtype=np.float64)
@@ -253,7 +260,8 @@ class BatchLidarOdometry:
                     _map_thread_incremented(self.seq[w], (nc[i], ns[i]))
         growing = [w for w in live if grew[w]]
         if growing:
-            nc, ns = ctx.bank_increment(growing, [slots[w] for w in growing], np.stack([T[w] for w in growing]))
+            how = {"segmented": True} if self.increment == "segmented" else {}    # ("loop": call for call as before)
+            nc, ns = ctx.bank_increment(growing, [slots[w] for w in growing], np.stack([T[w] for w in growing]), **how)
             for i, w in enumerate(growing):
                 _grown(self.seq[w], self.lidar_mode, T[w], (nc[i], ns[i]))
         for w in live:
