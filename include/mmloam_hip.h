@@ -608,7 +608,13 @@ int mml_map_set_local(mml_ctx* ctx, int kind, const float* xyz, int m);
  * T_wl = transformTobeMapped (row-major 4x4; pointAssociateToMap, Map_Manager.cpp:75-89), stores them in ring slot
  * localMapID % 50, rebuilds both local maps as pcl::VoxelGrid(concatenation of the ring) -- the clear() of
  * :1083-1085 / :1125-1127 included -- and rebuilds the kNN grids, all in HBM.  The caller keeps the key-scan rule
- * (pose moved by >= sqrt(0.5) m, :1082,1124).  n_*_map (optional) receive the new map sizes. */
+ * (pose moved by >= sqrt(0.5) m, :1082,1124).  n_*_map (optional) receive the new map sizes.
+ * This is the n = 1 case of the chain mml_map_bank_increment_segmented runs for n banks (below), the two kinds its two
+ * segments: both stacks are checked before any ring state changes (MML_ERR_STATE), and the call makes 2 + R host
+ * synchronisations after its entry drain (the stack sizes; the filtered sizes and boxes; one per cell-refinement round, R =
+ * the rounds of the slower kind, 1 to 5).  Memory, from the first increment on: the ring, 2 x 50 x max_features x 16
+ * bytes, and the chain's scratch, which is shared with the banks and sized by need -- 48 bytes per ring point actually
+ * held (both kinds, the new stacks included) plus the sort's temporary storage, grown on demand and kept until mml_destroy. */
 int mml_map_increment_local(mml_ctx* ctx, int slot, const double* T_wl, int* n_corner_map, int* n_surf_map);
 /* Empties the ring (localMapID = 0); the current local maps stay until the next set / increment. */
 int mml_map_local_reset(mml_ctx* ctx);
@@ -685,7 +691,8 @@ int mml_map_set_global(mml_ctx* ctx, int kind, const float* xyz, const int* cube
  * mml_map_bank_increment: mml_map_increment_local for n DISTINCT banks (a bank named twice is MML_ERR_INVALID, checked
  * with every other argument before anything changes): bank banks[i] takes the stacks of slot slots[i] at T_wl + 16 i.
  * Every bank ends bit-identical to the own map of a context with the same history of increments.  n_corner / n_surf: n
- * new map sizes each, or NULL.  The banks are worked through one after the other: at least 7 host synchronisations per bank.
+ * new map sizes each, or NULL.  The banks are worked through one after the other, each as mml_map_increment_local works
+ * the own map: 2 + R host synchronisations per bank, R the cell-refinement rounds of that bank's slower kind (1 to 5).
  * mml_map_bank_increment_segmented: the same call -- arguments, argument checks, drained context -- with the n banks' work in
  * ONE chain of launches: one launch writes all 2 n stacks into their rings, one concatenates all rings, one stable 64-bit
  * sort keyed (bank of the call, kind) << 32 | voxel filters all of them, and the 2 n kNN grids are built by one sort per

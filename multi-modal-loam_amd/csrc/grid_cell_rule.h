@@ -1,5 +1,5 @@
-// grid_cell_rule.h -- the host's cell-size decisions of a kNN grid build, the one definition behind build_grid_into and the
-// segmented build of the map banks (map_assoc.hip).  Plain C++ without HIP: a host program can include this file alone and check
+// grid_cell_rule.h -- the host's cell-size decisions of a kNN grid build, the one definition behind the one grid builder
+// (map_assoc.hip mml_build_grids: a set map's one cloud, an increment's 2 n).  Plain C++ without HIP: a host program can include this file alone and check
 // the rule on its own (tests/test_bank_increment_segmented_host.py).
 //   The configured cell edge suits a voxel-filtered map (<= 1 point per leaf).  A round of a build fits the cell to the cloud's
 //   bounding box and the cell budget (mml_grid_fit_cell), sorts the points by cell and counts the occupied cells; if the cloud is

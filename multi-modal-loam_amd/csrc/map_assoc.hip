@@ -31,52 +31,82 @@ struct GridDev {
 // cell_coord and the exact 5-NN ring search (Knn5, knn5_search, scan_rings01, ...), shared with time_offset.hip
 #include "knn5_dev.h"
 
-__global__ void k_cell_keys(const float4* pts, int m, GridDev g, unsigned* keys, unsigned* vals) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
-    float4 p = pts[i];
-    int cx = cell_coord(p.x, g.ox, g.inv_cell, g.dx);
-    int cy = cell_coord(p.y, g.oy, g.inv_cell, g.dy);
-    int cz = cell_coord(p.z, g.oz, g.inv_cell, g.dz);
-    keys[i] = (unsigned)(cx + g.dx * (cy + g.dy * cz));
-    vals[i] = (unsigned)i;
-}
+// A segment of the grid build is one cloud with its own grid.  The segments' points lie behind one offset table; a workgroup serves
+// one segment (blockIdx.y), so its table row is wave-uniform and is read through scalar loads.
+struct GridSegDev {
+    const float4* orig;        // the unsorted cloud
+    float4* pts;               // the grid's sorted points
+    int* cell_start;
+    const uint16_t* tag_orig;  // the points' tags in the order of `orig`; null: the cloud has none
+    uint16_t* tags;            // the grid's tags, in the order of `pts`
+    GridDev g;
+    int off, m;  // the segment's rows in the key / value arrays
+};
 
-__global__ void k_gather_sorted(const float4* pts, const unsigned* vals, int m, float4* out) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
-    unsigned src = vals[i];
-    float4 p = pts[src];
-    p.w = __uint_as_float(src);
-    out[i] = p;
-}
-
-__global__ void k_gather_tags(const uint16_t* tag_orig, const unsigned* vals, int m, uint16_t* out) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < m) out[i] = tag_orig[vals[i]];
-}
-
-// number of occupied cells = number of key changes in the sorted key array
-__global__ void k_count_occupied(const unsigned* keys, int m, int* out) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    bool head = i < m && (i == 0 || keys[i] != keys[i - 1]);
-    unsigned long long b = __ballot(head);
-    if ((threadIdx.x & 63) == 0 && b) atomicAdd(out, __popcll(b));
-}
-
-// cell_start[c] = first sorted position whose key >= c (lower bound); cell_start[ncell] = m
-__global__ void k_cell_start(const unsigned* keys, int m, int ncell, int* cell_start) {
-    int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c > ncell) return;
-    int lo = 0, hi = m;
-    while (lo < hi) {
-        int mid = (lo + hi) >> 1;
-        if (keys[mid] < (unsigned)c)
-            lo = mid + 1;
+// Key: unsigned = the cell (one segment), unsigned long long = segment << 32 | cell
+template <class Key>
+__global__ __launch_bounds__(256) void k_grid_keys(const GridSegDev* __restrict__ tab, Key* __restrict__ keys, unsigned* __restrict__ vals) {
+    const GridSegDev& S = tab[blockIdx.y];
+    const GridDev g = S.g;
+    const int m = S.m, off = S.off;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < m; i += gridDim.x * 256) {
+        const float4 p = S.orig[i];
+        const int cx = cell_coord(p.x, g.ox, g.inv_cell, g.dx);
+        const int cy = cell_coord(p.y, g.oy, g.inv_cell, g.dy);
+        const int cz = cell_coord(p.z, g.oz, g.inv_cell, g.dz);
+        const unsigned cell = (unsigned)(cx + g.dx * (cy + g.dy * cz));
+        if (sizeof(Key) == 8)
+            keys[off + i] = (Key)(((unsigned long long)blockIdx.y << 32) | cell);
         else
-            hi = mid;
+            keys[off + i] = (Key)cell;
+        vals[off + i] = (unsigned)i;
     }
-    cell_start[c] = lo;
+}
+
+// occupied cells of every segment = key changes inside its rows
+template <class Key>
+__global__ __launch_bounds__(256) void k_grid_occupied(const GridSegDev* __restrict__ tab, const Key* __restrict__ keys, int* __restrict__ occ) {
+    const int m = tab[blockIdx.y].m;
+    const Key* k = keys + tab[blockIdx.y].off;
+    for (int base = blockIdx.x * 256; base < m; base += gridDim.x * 256) {  // (whole wavefronts: the ballot)
+        const int i = base + threadIdx.x;
+        const bool head = i < m && (i == 0 || k[i] != k[i - 1]);
+        const unsigned long long b = __ballot(head);
+        if ((threadIdx.x & 63) == 0 && b) atomicAdd(occ + blockIdx.y, __popcll(b));
+    }
+}
+
+// the sorted points with their source index in w, and their tags where the cloud has them
+__global__ __launch_bounds__(256) void k_grid_gather(const GridSegDev* __restrict__ tab, const unsigned* __restrict__ vals) {
+    const GridSegDev& S = tab[blockIdx.y];
+    const int m = S.m;
+    const unsigned* v = vals + S.off;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < m; i += gridDim.x * 256) {
+        const unsigned src = v[i];
+        float4 p = S.orig[src];
+        p.w = __uint_as_float(src);
+        S.pts[i] = p;
+        if (S.tag_orig) S.tags[i] = S.tag_orig[src];
+    }
+}
+
+// cell_start[c] = first sorted point of the segment whose cell >= c (lower bound); cell_start[ncell] = m.  m = 0: two zero ints.
+template <class Key>
+__global__ __launch_bounds__(256) void k_grid_cell_start(const GridSegDev* __restrict__ tab, const Key* __restrict__ keys) {
+    const GridSegDev& S = tab[blockIdx.y];
+    const int m = S.m, ncell = S.g.ncell;
+    const Key* k = keys + S.off;
+    for (int c = blockIdx.x * 256 + threadIdx.x; c <= ncell; c += gridDim.x * 256) {
+        int lo = 0, hi = m;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if ((unsigned)k[mid] < (unsigned)c)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        S.cell_start[c] = lo;
+    }
 }
 
 __global__ __launch_bounds__(256) void k_knn5(MmlGrid g, const float* q, int nq, float max_d2, int* idx, float* d2) {
@@ -1150,176 +1180,29 @@ extern "C" int mml_model_fit5(mml_ctx* ctx, int op, const void* in, long n, void
     return ok ? MML_OK : MML_ERR_HIP;
 }
 
-// Builds the radix-sorted grid `g` over m points (host xyz), keeping the unsorted cloud in `orig`.
-static int build_grid_into(mml_ctx* ctx, MmlGrid& g, float4* orig, const float* h_xyz, int m, float cell,
-                           const uint16_t* d_tag_orig) {
-    hipStream_t s = MML_STREAM(ctx);
-    g.m = m;
-    if (m == 0) {
-        g.dim[0] = g.dim[1] = g.dim[2] = 1;
-        g.ncell = 1;
-        g.cell = 1.f;
-        g.inv_cell = 1.f;
-        g.origin[0] = g.origin[1] = g.origin[2] = 0.f;
-        MML_HIP(hipMemsetAsync(g.cell_start, 0, 2 * sizeof(int), s));
-        return MML_OK;
-    }
-    if (h_xyz) {  // host xyz (3 floats) -> device float4 (original order, w unused); null: `orig` is already filled
-        std::vector<float4> tmp((size_t)m);
-        for (int i = 0; i < m; ++i) tmp[i] = make_float4(h_xyz[3 * i], h_xyz[3 * i + 1], h_xyz[3 * i + 2], 0.f);
-        MML_HIP(hipMemcpyAsync(orig, tmp.data(), sizeof(float4) * (size_t)m, hipMemcpyHostToDevice, s));
-        MML_HIP(hipStreamSynchronize(s));  // tmp goes out of scope
-    }
-    MmlStageScope t(ctx, "map_build");
-    const int init[6] = MML_BBOX_EMPTY;
-    int* d_bbox = ctx->d_misc;
-    MML_HIP(hipMemcpyAsync(d_bbox, init, sizeof(init), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_bbox, dim3(256), dim3(256), 0, s, orig, m, d_bbox);
-    int bbox_keys[6];
-    MML_HIP(hipMemcpyAsync(bbox_keys, d_bbox, sizeof(bbox_keys), hipMemcpyDeviceToHost, s));
-    MML_HIP(hipStreamSynchronize(s));
-    float bbox[6];
-    for (int c = 0; c < 6; ++c) bbox[c] = mml_funkey(bbox_keys[c]);
-    const long long max_cells = mml_grid_max_cells(ctx->MM);
-    const int blocks = (m + 255) / 256;
-    int dim[3];
-    // The configured cell edge suits a voxel-filtered map (<= 1 point per leaf).  If the cloud is denser than
-    // that, shrink the cell until an occupied cell holds <= 12 points on average (bounded by the cell budget): grid_cell_rule.h.
-    for (int round = 0;; ++round) {
-        mml_grid_fit_cell(bbox, max_cells, cell, dim);
-        g.cell = cell;
-        g.inv_cell = 1.0f / cell;
-        for (int c = 0; c < 3; ++c) {
-            g.origin[c] = bbox[c];
-            g.dim[c] = dim[c];
-        }
-        g.ncell = dim[0] * dim[1] * dim[2];
-        GridDev gd{g.origin[0], g.origin[1], g.origin[2], g.inv_cell, g.cell, dim[0], dim[1], dim[2], g.ncell};
-        hipLaunchKernelGGL(k_cell_keys, dim3(blocks), dim3(256), 0, s, orig, m, gd, ctx->map_keys, ctx->map_vals);
-        int bits = 1;
-        while ((1ll << bits) < g.ncell) ++bits;
-        const int rt = mml_sort_pairs(ctx, ctx->sort_tmp, ctx->map_keys, ctx->map_keys2, ctx->map_vals, ctx->map_vals2, (size_t)m, bits, s);
-        if (rt != MML_OK) return rt;
-        int* d_occ = ctx->d_misc + 16;
-        MML_HIP(hipMemsetAsync(d_occ, 0, sizeof(int), s));
-        hipLaunchKernelGGL(k_count_occupied, dim3(blocks), dim3(256), 0, s, ctx->map_keys2, m, d_occ);
-        int occ = 1;
-        MML_HIP(hipMemcpyAsync(&occ, d_occ, sizeof(int), hipMemcpyDeviceToHost, s));
-        MML_HIP(hipStreamSynchronize(s));
-        if (!mml_grid_refine(m, occ, round, g.ncell, max_cells)) break;
-        cell *= 0.5f;
-    }
-    hipLaunchKernelGGL(k_gather_sorted, dim3(blocks), dim3(256), 0, s, orig, ctx->map_vals2, m, g.pts);
-    if (d_tag_orig) hipLaunchKernelGGL(k_gather_tags, dim3(blocks), dim3(256), 0, s, d_tag_orig, ctx->map_vals2, m, g.tags);
-    hipLaunchKernelGGL(k_cell_start, dim3((g.ncell + 1 + 255) / 256), dim3(256), 0, s, ctx->map_keys2, m, g.ncell,
-                       g.cell_start);
-    MML_HIP(hipGetLastError());
-    return MML_OK;
-}
+// ---- the grid build: nseg clouds at once ------------------------------------------------------------------------------------------
+// A round keys every point by its cell in its segment's own grid and ONE stable radix sort orders all of them.  With several
+// segments the key is segment << 32 | cell: the segment is the high word and the rows were in segment order, so a segment's points
+// stay in its own rows [off, off + m).  A single cloud (Key = unsigned) is keyed by the cell alone and sorted over exactly the
+// bits its cell count needs.
+size_t mml_grid_table_bytes(int nseg) { return (sizeof(GridSegDev) + sizeof(int)) * (size_t)nseg; }
 
-int mml_build_grid(mml_ctx* ctx, const MmlMapRef& map, int kind, const float* h_xyz, int m) {
-    MML_REQUIRE(kind == 0 || kind == 1, MML_ERR_INVALID, "map kind must be 0 (corner) or 1 (surf)");
-    MML_REQUIRE(m >= 0 && m <= ctx->MM, MML_ERR_CAPACITY, "map larger than max_map_points");
-    map.have_map[kind] = false;
-    map.grid[kind].tags = nullptr;
-    ctx->banks.dirty = true;  // (the descriptor table of a context with banks holds a copy of this grid)
-    int rc = build_grid_into(ctx, map.grid[kind], map.map_tmp + (size_t)kind * ctx->MM, h_xyz, m,
-                             kind == 0 ? ctx->cfg.cell_corner : ctx->cfg.cell_surf, nullptr);
-    if (rc == MML_OK) map.have_map[kind] = true;
-    return rc;
-}
-
-// Same, for a cloud that is already on the device in the map's map_tmp + kind * MM (device-side map upkeep).
-int mml_build_grid_device(mml_ctx* ctx, const MmlMapRef& map, int kind, int m) {
-    return mml_build_grid(ctx, map, kind, nullptr, m);
-}
-
-// ---- build_grid_into for many clouds at once (the segmented map-bank increment, map_upkeep.hip) --------------------------------
-// A segment is one cloud with its own grid.  The segments' points lie behind one offset table; a round keys every point by
-// (segment << 32 | cell in the segment's own grid) and ONE stable radix sort orders all of them: the segment is the key's high word
-// and the rows were in segment order, so a segment's points stay in its own rows [off, off + m), in the order k_cell_keys and the
-// 32-bit sort of build_grid_into give them.  A workgroup serves one segment (blockIdx.y), so its table row is wave-uniform and is
-// read through scalar loads.
-namespace {
-struct GridSegDev {
-    const float4* orig;  // the unsorted cloud
-    float4* pts;         // the grid's sorted points
-    int* cell_start;
-    GridDev g;
-    int off, m;  // the segment's rows in the key / value arrays
-};
-
-__global__ __launch_bounds__(256) void k_bseg_cell_keys(const GridSegDev* __restrict__ tab, unsigned long long* __restrict__ keys,
-                                                        unsigned* __restrict__ vals) {
-    const GridSegDev& S = tab[blockIdx.y];
-    const GridDev g = S.g;
-    const int m = S.m, off = S.off;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < m; i += gridDim.x * 256) {
-        const float4 p = S.orig[i];
-        const int cx = cell_coord(p.x, g.ox, g.inv_cell, g.dx);
-        const int cy = cell_coord(p.y, g.oy, g.inv_cell, g.dy);
-        const int cz = cell_coord(p.z, g.oz, g.inv_cell, g.dz);
-        keys[off + i] = ((unsigned long long)blockIdx.y << 32) | (unsigned)(cx + g.dx * (cy + g.dy * cz));
-        vals[off + i] = (unsigned)i;
-    }
-}
-
-// occupied cells of every segment = key changes inside its rows
-__global__ __launch_bounds__(256) void k_bseg_count_occupied(const GridSegDev* __restrict__ tab, const unsigned long long* __restrict__ keys,
-                                                             int* __restrict__ occ) {
-    const int m = tab[blockIdx.y].m;
-    const unsigned long long* k = keys + tab[blockIdx.y].off;
-    for (int base = blockIdx.x * 256; base < m; base += gridDim.x * 256) {  // (whole wavefronts: the ballot)
-        const int i = base + threadIdx.x;
-        const bool head = i < m && (i == 0 || k[i] != k[i - 1]);
-        const unsigned long long b = __ballot(head);
-        if ((threadIdx.x & 63) == 0 && b) atomicAdd(occ + blockIdx.y, __popcll(b));
-    }
-}
-
-__global__ __launch_bounds__(256) void k_bseg_gather_sorted(const GridSegDev* __restrict__ tab, const unsigned* __restrict__ vals) {
-    const GridSegDev& S = tab[blockIdx.y];
-    const int m = S.m;
-    const unsigned* v = vals + S.off;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < m; i += gridDim.x * 256) {
-        const unsigned src = v[i];
-        float4 p = S.orig[src];
-        p.w = __uint_as_float(src);
-        S.pts[i] = p;
-    }
-}
-
-// cell_start[c] = first sorted point of the segment whose cell >= c (lower bound); cell_start[ncell] = m.  m = 0: two zero ints.
-__global__ __launch_bounds__(256) void k_bseg_cell_start(const GridSegDev* __restrict__ tab, const unsigned long long* __restrict__ keys) {
-    const GridSegDev& S = tab[blockIdx.y];
-    const int m = S.m, ncell = S.g.ncell;
-    const unsigned long long* k = keys + S.off;
-    for (int c = blockIdx.x * 256 + threadIdx.x; c <= ncell; c += gridDim.x * 256) {
-        int lo = 0, hi = m;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if ((unsigned)k[mid] < (unsigned)c)
-                lo = mid + 1;
-            else
-                hi = mid;
-        }
-        S.cell_start[c] = lo;
-    }
-}
-}  // namespace
-
-size_t mml_grid_seg_table_bytes(int nseg) { return sizeof(GridSegDev) * (size_t)nseg; }
-
-// The grids of nseg clouds that are on the device (jobs[g].orig, jobs[g].m points, bounding box jobs[g].bbox_keys), each what
-// build_grid_into makes of that cloud: the host takes every segment through the rounds of grid_cell_rule.h, one sort, one count and
-// ONE read-back of the nseg counts per round for all of them.  A segment that has finished keeps its cell edge and is keyed again in
-// the later rounds of the others: the same keys through the same stable sort are the same order, and no second set of buffers has
-// to hold a finished segment's rows.  *rounds: the rounds run = the host synchronisations made.
-int mml_build_grids_segmented(mml_ctx* ctx, int nseg, const MmlGridJob* jobs, const MmlGridSegScratch& W, int* rounds) {
+// The grids of nseg clouds that are on the device (jobs[g].orig, jobs[g].m points, bounding box jobs[g].bbox_keys): the host takes
+// every segment through the rounds of grid_cell_rule.h, one sort, one count and ONE read-back of the nseg counts per round for all
+// of them.  A segment that has finished keeps its cell edge and is keyed again in the later rounds of the others: the same keys
+// through the same stable sort are the same order, and no second set of buffers has to hold a finished segment's rows.  An empty
+// cloud's grid: dim 1 x 1 x 1, cell 1, two zero ints in cell_start.  *rounds: the rounds run = the host synchronisations made.
+template <class Key>
+int mml_build_grids(mml_ctx* ctx, int nseg, const MmlGridJob* jobs, const MmlGridScratch<Key>& W, int* rounds) {
+    static_assert(sizeof(Key) == 4 || sizeof(Key) == 8, "the cell alone, or segment << 32 | cell");
     hipStream_t s = MML_STREAM(ctx);
     MmlStageScope t(ctx, "map_build");
+    MML_REQUIRE(sizeof(Key) == 8 || nseg == 1, MML_ERR_INVALID, "grid build: 32-bit keys hold one cloud");
+    const size_t tab_bytes = sizeof(GridSegDev) * (size_t)nseg;
     GridSegDev* h_tab = static_cast<GridSegDev*>(W.tab_h);
     const GridSegDev* d_tab = static_cast<const GridSegDev*>(W.tab_d);
+    int* occ_h = reinterpret_cast<int*>(static_cast<char*>(W.tab_h) + tab_bytes);
+    int* occ_d = reinterpret_cast<int*>(static_cast<char*>(W.tab_d) + tab_bytes);
     const long long max_cells = mml_grid_max_cells(ctx->MM);
     std::vector<float> cell((size_t)nseg);
     std::vector<char> live((size_t)nseg);
@@ -1333,7 +1216,7 @@ int mml_build_grids_segmented(mml_ctx* ctx, int nseg, const MmlGridJob* jobs, co
         cell[g] = J.cell;
         live[g] = J.m > 0;
         for (int c = 0; c < 6; ++c) bbox[6 * (size_t)g + c] = mml_funkey(J.bbox_keys[c]);
-        if (J.m == 0) {  // (build_grid_into's empty grid; k_bseg_cell_start writes its two zero ints)
+        if (J.m == 0) {  // (the empty grid; k_grid_cell_start writes its two zero ints)
             G.dim[0] = G.dim[1] = G.dim[2] = 1;
             G.ncell = 1;
             G.cell = 1.f;
@@ -1344,12 +1227,14 @@ int mml_build_grids_segmented(mml_ctx* ctx, int nseg, const MmlGridJob* jobs, co
         h_tab[g].orig = J.orig;
         h_tab[g].pts = G.pts;
         h_tab[g].cell_start = G.cell_start;
+        h_tab[g].tag_orig = J.tag_orig;
+        h_tab[g].tags = G.tags;
         h_tab[g].off = (int)total;
         h_tab[g].m = J.m;
         total += J.m;
         if (J.m > max_m) max_m = J.m;
     }
-    MML_REQUIRE(total <= (long long)W.cap, MML_ERR_CAPACITY, "segmented grid build: more points than the scratch holds");
+    MML_REQUIRE(total <= (long long)W.cap, MML_ERR_CAPACITY, "grid build: more points than the scratch holds");
     int seg_bits = 1;
     while ((1 << seg_bits) < nseg) ++seg_bits;
     const int blocks = max_m ? ((max_m + 255) / 256 < 256 ? (max_m + 255) / 256 : 256) : 1;
@@ -1370,20 +1255,23 @@ int mml_build_grids_segmented(mml_ctx* ctx, int nseg, const MmlGridJob* jobs, co
                 G.ncell = dim[0] * dim[1] * dim[2];
             }
             h_tab[g].g = GridDev{G.origin[0], G.origin[1], G.origin[2], G.inv_cell, G.cell, G.dim[0], G.dim[1], G.dim[2], G.ncell};
+            occ_h[g] = 0;
         }
-        MML_HIP(hipMemcpyAsync(W.tab_d, W.tab_h, sizeof(GridSegDev) * (size_t)nseg, hipMemcpyHostToDevice, s));
-        MML_HIP(hipMemsetAsync(W.occ_d, 0, sizeof(int) * (size_t)nseg, s));
-        hipLaunchKernelGGL(k_bseg_cell_keys, dim3(blocks, nseg), dim3(256), 0, s, d_tab, W.keys, W.vals);
-        const int rt = mml_sort_pairs(ctx, ctx->sort_tmp, W.keys, W.keys2, W.vals, W.vals2, (size_t)total, 32 + seg_bits, s);
+        MML_HIP(hipMemcpyAsync(W.tab_d, W.tab_h, mml_grid_table_bytes(nseg), hipMemcpyHostToDevice, s));  // (the rows and the zeroed counts)
+        hipLaunchKernelGGL(k_grid_keys<Key>, dim3(blocks, nseg), dim3(256), 0, s, d_tab, W.keys, W.vals);
+        int end_bit = 32 + seg_bits;
+        if (sizeof(Key) == 4)  // (one cloud: the bits of its cell count)
+            for (end_bit = 1; (1ll << end_bit) < jobs[0].g->ncell;) ++end_bit;
+        const int rt = mml_sort_pairs(ctx, ctx->sort_tmp, W.keys, W.keys2, W.vals, W.vals2, (size_t)total, end_bit, s);
         if (rt != MML_OK) return rt;
-        hipLaunchKernelGGL(k_bseg_count_occupied, dim3(blocks, nseg), dim3(256), 0, s, d_tab, W.keys2, W.occ_d);
-        MML_HIP(hipMemcpyAsync(W.occ_h, W.occ_d, sizeof(int) * (size_t)nseg, hipMemcpyDeviceToHost, s));
+        hipLaunchKernelGGL(k_grid_occupied<Key>, dim3(blocks, nseg), dim3(256), 0, s, d_tab, W.keys2, occ_d);
+        MML_HIP(hipMemcpyAsync(occ_h, occ_d, sizeof(int) * (size_t)nseg, hipMemcpyDeviceToHost, s));
         MML_HIP(hipStreamSynchronize(s));
         ++*rounds;
         bool again = false;
         for (int g = 0; g < nseg; ++g) {
             if (!live[g]) continue;
-            if (mml_grid_refine(jobs[g].m, W.occ_h[g], round, jobs[g].g->ncell, max_cells)) {
+            if (mml_grid_refine(jobs[g].m, occ_h[g], round, jobs[g].g->ncell, max_cells)) {
                 cell[g] *= 0.5f;
                 again = true;
             } else {
@@ -1394,15 +1282,64 @@ int mml_build_grids_segmented(mml_ctx* ctx, int nseg, const MmlGridJob* jobs, co
     }
     if (total == 0) {  // (every cloud is empty: the table of the empty grids)
         for (int g = 0; g < nseg; ++g) h_tab[g].g = GridDev{0.f, 0.f, 0.f, 1.f, 1.f, 1, 1, 1, 1};
-        MML_HIP(hipMemcpyAsync(W.tab_d, W.tab_h, sizeof(GridSegDev) * (size_t)nseg, hipMemcpyHostToDevice, s));
+        MML_HIP(hipMemcpyAsync(W.tab_d, W.tab_h, tab_bytes, hipMemcpyHostToDevice, s));
     }
     for (int g = 0; g < nseg; ++g)
         if (jobs[g].g->ncell > max_ncell) max_ncell = jobs[g].g->ncell;
-    if (total > 0) hipLaunchKernelGGL(k_bseg_gather_sorted, dim3(blocks, nseg), dim3(256), 0, s, d_tab, W.vals2);
+    if (total > 0) hipLaunchKernelGGL(k_grid_gather, dim3(blocks, nseg), dim3(256), 0, s, d_tab, W.vals2);
     const int cblocks = (max_ncell + 1 + 255) / 256 < 1024 ? (max_ncell + 1 + 255) / 256 : 1024;
-    hipLaunchKernelGGL(k_bseg_cell_start, dim3(cblocks, nseg), dim3(256), 0, s, d_tab, W.keys2);
+    hipLaunchKernelGGL(k_grid_cell_start<Key>, dim3(cblocks, nseg), dim3(256), 0, s, d_tab, W.keys2);
     MML_HIP(hipGetLastError());
+    if (total == 0) MML_HIP(hipStreamSynchronize(s));  // (no round has waited for the copy out of the pinned table, which the next build rewrites)
     return MML_OK;
+}
+template int mml_build_grids<unsigned>(mml_ctx*, int, const MmlGridJob*, const MmlGridScratch<unsigned>&, int*);
+template int mml_build_grids<unsigned long long>(mml_ctx*, int, const MmlGridJob*, const MmlGridScratch<unsigned long long>&, int*);
+
+// One cloud of m points into the grid `g`, the unsorted cloud kept in `orig` (filled from h_xyz; null: it is there already): the
+// bounding box with its one read-back, then the build with the cell as the whole key, in the context's map_keys / map_vals.
+static int build_grid_into(mml_ctx* ctx, MmlGrid& g, float4* orig, const float* h_xyz, int m, float cell,
+                           const uint16_t* d_tag_orig) {
+    hipStream_t s = MML_STREAM(ctx);
+    const int init[6] = MML_BBOX_EMPTY;
+    int bbox_keys[6] = MML_BBOX_EMPTY;
+    if (m && h_xyz) {  // host xyz (3 floats) -> device float4 (original order, w unused)
+        std::vector<float4> tmp((size_t)m);
+        for (int i = 0; i < m; ++i) tmp[i] = make_float4(h_xyz[3 * i], h_xyz[3 * i + 1], h_xyz[3 * i + 2], 0.f);
+        MML_HIP(hipMemcpyAsync(orig, tmp.data(), sizeof(float4) * (size_t)m, hipMemcpyHostToDevice, s));
+        MML_HIP(hipStreamSynchronize(s));  // tmp goes out of scope
+    }
+    if (m) {
+        MmlStageScope t(ctx, "map_build");
+        int* d_bbox = ctx->d_misc;
+        MML_HIP(hipMemcpyAsync(d_bbox, init, sizeof(init), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_bbox, dim3(256), dim3(256), 0, s, orig, m, d_bbox);
+        MML_HIP(hipMemcpyAsync(bbox_keys, d_bbox, sizeof(bbox_keys), hipMemcpyDeviceToHost, s));
+        MML_HIP(hipStreamSynchronize(s));
+    }
+    const int rc = ctx->grid_tab.reserve(ctx, mml_grid_table_bytes(1));
+    if (rc != MML_OK) return rc;
+    const MmlGridJob job{&g, orig, cell, m, bbox_keys, d_tag_orig};
+    const MmlGridScratch<unsigned> W{ctx->map_keys, ctx->map_keys2, ctx->map_vals, ctx->map_vals2, (size_t)ctx->MM, ctx->grid_tab.d, ctx->grid_tab.h};
+    int rounds = 0;
+    return mml_build_grids(ctx, 1, &job, W, &rounds);
+}
+
+int mml_build_grid(mml_ctx* ctx, const MmlMapRef& map, int kind, const float* h_xyz, int m) {
+    MML_REQUIRE(kind == 0 || kind == 1, MML_ERR_INVALID, "map kind must be 0 (corner) or 1 (surf)");
+    MML_REQUIRE(m >= 0 && m <= ctx->MM, MML_ERR_CAPACITY, "map larger than max_map_points");
+    map.have_map[kind] = false;
+    map.grid[kind].tags = nullptr;
+    ctx->banks.dirty = true;  // (the descriptor table of a context with banks holds a copy of this grid)
+    int rc = build_grid_into(ctx, map.grid[kind], map.map_tmp + (size_t)kind * ctx->MM, h_xyz, m,
+                             kind == 0 ? ctx->cfg.cell_corner : ctx->cfg.cell_surf, nullptr);
+    if (rc == MML_OK) map.have_map[kind] = true;
+    return rc;
+}
+
+// Same, for a cloud that is already on the device in the map's map_tmp + kind * MM (the map broadcast of comm.hip).
+int mml_build_grid_device(mml_ctx* ctx, const MmlMapRef& map, int kind, int m) {
+    return mml_build_grid(ctx, map, kind, nullptr, m);
 }
 
 // a12: the global map handed to Estimate() (Estimator.cpp:1170-1184) as one concatenated cloud with the cube index

@@ -235,7 +235,9 @@ int mml_map_bank_increment_segmented(mml_ctx* ctx, int n, const int* banks, cons
     rc = enter(ctx);
     if (rc != MML_OK) return rc;
     if (!ctx->uploads.empty()) return mml_refuse(ctx, MML_ERR_STATE, "uploads in flight after a drained context");
-    return mml_map_upkeep_increment_segmented(ctx, n, banks, slots, T_wl, n_corner, n_surf);
+    std::vector<MmlMapIncrement> inc;
+    for (int i = 0; i < n; ++i) inc.push_back(MmlMapIncrement{mml_map_bank(ctx, banks[i]), slots[i], T_wl + 16 * (size_t)i});
+    return mml_map_upkeep_increment_segmented(ctx, n, inc.data(), n_corner, n_surf);
 }
 
 int mml_debug_bank_increment_budget(mml_ctx* ctx, long points) {

@@ -36,7 +36,7 @@ struct Shifts {
     signed char axis[64], dir[64];
 };
 
-__global__ void k_to_world(const float4* feat, int n, Tf12 T, float4* out) {
+__global__ void k_store_to_world(const float4* feat, int n, Tf12 T, float4* out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float4 f = feat[i];
@@ -210,7 +210,7 @@ int mml_cube_store_append(mml_ctx* ctx, const MmlCubeRef& cube, int slot, const 
         MML_REQUIRE(n >= 0 && n <= ctx->MF, MML_ERR_STATE, "slot holds no down-sampled feature stack");
         MML_REQUIRE(L.gp_n[kind] + n <= L.gp_cap, MML_ERR_CAPACITY, "too many pending map points (16 x max_features)");
         if (n)
-            hipLaunchKernelGGL(k_to_world, dim3((n + 255) / 256), dim3(256), 0, s, ctx->ft_xyz[kind] + (size_t)slot * ctx->MF, n, T,
+            hipLaunchKernelGGL(k_store_to_world, dim3((n + 255) / 256), dim3(256), 0, s, ctx->ft_xyz[kind] + (size_t)slot * ctx->MF, n, T,
                                L.gp_pts[kind] + L.gp_n[kind]);
         L.gp_n[kind] += n;
     }

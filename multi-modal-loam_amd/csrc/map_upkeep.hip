@@ -3,15 +3,16 @@
 //
 // The reference keeps the last localMapWindowSize = 50 key scans' features as 50 PCL clouds in the world frame,
 // concatenates them and runs pcl::VoxelGrid over the concatenation; kdtree->setInputCloud then rebuilds both trees on
-// the next Estimate() (:1159-1167).  Here the ring lives in HBM next to the scan slots it is fed from:
-//   k_to_world    : pointAssociateToMap (Map_Manager.cpp:75-89) of one slot's down-sampled stack into ring slot
-//                   localMapID % 50
-//   k_concat      : the ring in slot order = the cloud the filter sees
-//   voxel filter  : bounding box -> PCL voxel index -> rocPRIM radix sort of (index, position) pairs (stable, so
-//                   the points of a voxel stay in input order = the order the oracle sums them in) -> head flags ->
-//                   exclusive scan -> one lane per voxel sums its run and writes the centroid
-//   grid build    : the filtered cloud is already where mml_build_grid_device expects it
-// Nothing but the two cloud sizes crosses PCIe.  Compiled with -ffp-contract=off.
+// the next Estimate() (:1159-1167).  Here the ring lives in HBM next to the scan slots it is fed from, and there is ONE chain,
+// written for n maps at once (the end of this file); a single map -- the context's own or one bank of a loop -- is its n = 1 case.
+// A segment is (map, kind):
+//   k_inc_to_world    : pointAssociateToMap (Map_Manager.cpp:75-89) of a slot's down-sampled stack into ring slot localMapID % 50
+//   k_inc_concat_bbox : the ring in slot order = the cloud the filter sees, and its bounding box
+//   voxel filter      : PCL voxel index -> ONE stable rocPRIM radix sort of (segment << 32 | index, position) pairs (the points of
+//                       a voxel stay in input order = the order the oracle sums them in) -> head flags -> exclusive scan -> one
+//                       lane per voxel sums its run and writes the centroid
+//   grid build        : the filtered clouds are where mml_build_grids expects them
+// Nothing but the cloud sizes and their bounding boxes crosses PCIe.  Compiled with -ffp-contract=off.
 #include <math.h>
 
 #include <cstring>
@@ -19,93 +20,6 @@
 
 #include "mml_internal.h"
 #include "voxel_sort_dev.h"
-
-namespace {
-
-struct Tf12 {
-    double m[12];
-};
-
-__global__ void k_to_world(const float4* feat, int n, Tf12 T, float4* out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float4 f = feat[i];
-    const double x = f.x, y = f.y, z = f.z;
-    float4 o;
-    o.x = (float)(((T.m[0] * x + T.m[1] * y) + T.m[2] * z) + T.m[3]);
-    o.y = (float)(((T.m[4] * x + T.m[5] * y) + T.m[6] * z) + T.m[7]);
-    o.z = (float)(((T.m[8] * x + T.m[9] * y) + T.m[10] * z) + T.m[11]);
-    o.w = 0.f;
-    out[i] = o;
-}
-
-struct RingOffsets {
-    int off[mml_ctx::LOCAL_WINDOW + 1];
-};
-
-// grid.y = ring slot
-__global__ void k_concat(const float4* ring, int MF, RingOffsets R, float4* cat) {
-    const int s = blockIdx.y;
-    const int n = R.off[s + 1] - R.off[s];
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-        cat[R.off[s] + i] = ring[(size_t)s * MF + i];
-}
-
-// PCL 1.8.1 voxel_grid.hpp applyFilter (MmlVoxGrid)
-__global__ void k_vox_keys(const float4* pts, int m, const int* bbox_keys, float leaf, unsigned* keys, unsigned* vals) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
-    const MmlVoxGrid g = mml_vox_grid_of_keys(bbox_keys, leaf);
-    const float4 p = pts[i];
-    const unsigned idx = g.index(p.x, p.y, p.z);
-    // (more than INT_MAX voxels in the box: PCL returns the cloud unfiltered = every point its own voxel, in input order)
-    keys[i] = g.overflows ? (unsigned)i : idx;
-    vals[i] = (unsigned)i;
-}
-
-// one lane per voxel: AccumulatorXYZ (float sum in input order, then / n)
-__global__ void k_vox_centroid(const float4* pts, const unsigned* keys, const unsigned* vals, const int* flag,
-                               const int* pos, int m, int cap, float4* out, int* n_out) {
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= m) return;
-    if (s == m - 1) *n_out = pos[s] + flag[s];
-    if (!flag[s]) return;
-    const int dst = pos[s];
-    if (dst >= cap) return;
-    float4 sum;
-    const float c = static_cast<float>(mml_voxel_run_sum(pts, keys, vals, s, m, 0, sum));
-    out[dst] = make_float4(sum.x / c, sum.y / c, sum.z / c, 0.f);
-}
-
-// pcl::VoxelGrid over `m` device points; the filtered cloud goes to `out` (capacity cap), its size to *h_n
-int voxel_filter_device(mml_ctx* ctx, const float4* pts, int m, float leaf, float4* out, int cap, int* h_n) {
-    hipStream_t s = MML_STREAM(ctx);
-    *h_n = 0;
-    if (m == 0) return MML_OK;
-    MML_REQUIRE(m <= ctx->MM && (size_t)m <= ctx->vox_cap, MML_ERR_CAPACITY, "cloud larger than max_map_points");
-    int* d_bbox = ctx->d_misc;
-    int* d_n = ctx->d_misc + 8;
-    const int init[6] = MML_BBOX_EMPTY;
-    MML_HIP(hipMemcpyAsync(d_bbox, init, sizeof(init), hipMemcpyHostToDevice, s));
-    const int blocks = (m + 255) / 256;
-    hipLaunchKernelGGL(k_bbox, dim3(blocks < 256 ? blocks : 256), dim3(256), 0, s, pts, m, d_bbox);
-    hipLaunchKernelGGL(k_vox_keys, dim3(blocks), dim3(256), 0, s, pts, m, d_bbox, leaf, ctx->map_keys, ctx->map_vals);
-    int rc = mml_sort_pairs(ctx, ctx->sort_tmp, ctx->map_keys, ctx->map_keys2, ctx->map_vals, ctx->map_vals2, (size_t)m, 32, s);
-    if (rc != MML_OK) return rc;
-    int* flag = ctx->vox_flag;
-    int* pos = ctx->vox_flag + ctx->vox_cap + 1;
-    hipLaunchKernelGGL(k_run_heads<unsigned>, dim3(blocks), dim3(256), 0, s, ctx->map_keys2, m, 0, ~0u, flag);
-    rc = mml_exclusive_scan(ctx, ctx->sort_tmp, flag, pos, (size_t)m, s);
-    if (rc != MML_OK) return rc;
-    hipLaunchKernelGGL(k_vox_centroid, dim3(blocks), dim3(256), 0, s, pts, ctx->map_keys2, ctx->map_vals2, flag, pos, m, cap,
-                       out, d_n);
-    MML_HIP(hipMemcpyAsync(h_n, d_n, sizeof(int), hipMemcpyDeviceToHost, s));
-    MML_HIP(hipStreamSynchronize(s));
-    MML_REQUIRE(*h_n <= cap, MML_ERR_CAPACITY, "filtered local map larger than max_map_points");
-    return MML_OK;
-}
-
-}  // namespace
 
 // ---- a10 for labelled clouds beyond the LDS sort of k_voxel: the whole batch through ONE global sort --------------------
 // Segment = (slot, kind).  The labelled points of every segment are gathered into one array, keyed by
@@ -309,77 +223,26 @@ int mml_downsample_redo_overflow(mml_ctx* ctx, int first, int count, std::vector
     return MML_OK;
 }
 
-int mml_map_upkeep_increment(mml_ctx* ctx, const MmlMapRef& map, int slot, const double* T_wl, int* n_out) {
-    hipStream_t s = MML_STREAM(ctx);
-    constexpr int W = mml_ctx::LOCAL_WINDOW;
-    const size_t ring_pts = (size_t)W * ctx->MF;
-    if (!ctx->ring_mem.present()) {  // (the context's ring comes with the scratch every map's upkeep uses)
-        MML_HIP(hipStreamSynchronize(s));
-        ctx->vox_cap = 0;
-        const int rc0 = ctx->ring_mem.reserve(ctx, {mml_part(ctx->ring[0], ring_pts), mml_part(ctx->ring[1], ring_pts), mml_part(ctx->ring_cat, ring_pts),
-                                                    mml_part(ctx->vox_flag, 2 * (ring_pts + 1))});
-        if (rc0 != MML_OK) return rc0;
-        ctx->vox_cap = ring_pts;
-    }
-    if (!map.ring_mem->present()) {  // a bank's ring
-        const int rc0 = map.ring_mem->reserve(ctx, {mml_part(map.ring[0], ring_pts), mml_part(map.ring[1], ring_pts)});
-        if (rc0 != MML_OK) return rc0;
-    }
-    int* n_feat = reinterpret_cast<int*>(mml_stage_alloc(ctx, 1));  // pinned
-    MML_HIP(hipMemcpyAsync(&n_feat[0], ctx->ft_n + 0 * ctx->B + slot, sizeof(int), hipMemcpyDeviceToHost, s));
-    MML_HIP(hipMemcpyAsync(&n_feat[1], ctx->ft_n + 1 * ctx->B + slot, sizeof(int), hipMemcpyDeviceToHost, s));
-    MML_HIP(hipStreamSynchronize(s));
-    Tf12 T;
-    memcpy(T.m, T_wl, sizeof(double) * 12);
-    const int Id = (int)(*map.local_map_id % W);  // :1597
-    for (int kind = 0; kind < 2; ++kind)  // both stacks are checked before any ring state changes
-        MML_REQUIRE(n_feat[kind] >= 0 && n_feat[kind] <= ctx->MF, MML_ERR_STATE, "slot holds no down-sampled feature stack");
-    for (int kind = 0; kind < 2; ++kind) {
-        const int n = n_feat[kind];
-        if (n)
-            hipLaunchKernelGGL(k_to_world, dim3((n + 255) / 256), dim3(256), 0, s, ctx->ft_xyz[kind] + (size_t)slot * ctx->MF,
-                               n, T, map.ring[kind] + (size_t)Id * ctx->MF);
-        map.ring_n[kind][Id] = n;
-        RingOffsets R;
-        R.off[0] = 0;
-        for (int i = 0; i < W; ++i) R.off[i + 1] = R.off[i] + map.ring_n[kind][i];
-        const int total = R.off[W];
-        if (total) hipLaunchKernelGGL(k_concat, dim3(8, W), dim3(256), 0, s, map.ring[kind], ctx->MF, R, ctx->ring_cat);
-        int m = 0;
-        int rc = voxel_filter_device(ctx, ctx->ring_cat, total, kind == 0 ? ctx->cfg.leaf_corner : ctx->cfg.leaf_surf,
-                                     map.map_tmp + (size_t)kind * ctx->MM, ctx->MM, &m);
-        if (rc != MML_OK) return rc;
-        rc = mml_build_grid_device(ctx, map, kind, m);
-        if (rc != MML_OK) return rc;
-        map.local_map_n[kind] = m;
-        if (n_out) n_out[kind] = m;
-    }
-    ++*map.local_map_id;  // :1642
-    MML_HIP(hipGetLastError());
-    return MML_OK;
-}
-
-// ---- mml_map_upkeep_increment for n banks in one chain of launches (mml_map_bank_increment_segmented) --------------------------
-// Segment g = 2 i + kind: bank i of the chunk, kind.  The chunk's rings are concatenated behind one offset table, the voxel filter
+// ---- Estimator::MapIncrementLocal for n maps in one chain of launches ------------------------------------------------------------
+// Segment g = 2 i + kind: map i of the chunk, kind.  The chunk's rings are concatenated behind one offset table, the voxel filter
 // is mml_downsample_big's pattern (one stable 64-bit radix sort keyed segment << 32 | voxel, one lane per voxel), the grids are
-// mml_build_grids_segmented's.  A workgroup serves one segment (blockIdx.y): its table row is wave-uniform and comes through scalar
-// loads; the sort keeps a segment's points in its own rows [cat_off, cat_off + total), so the kernels behind it index rows the
-// same way.
+// mml_build_grids'.  A workgroup serves one segment (blockIdx.y): its table row is wave-uniform and comes through scalar loads;
+// the sort keeps a segment's points in its own rows [cat_off, cat_off + total), so the kernels behind it index rows the same way.
 namespace {
-struct BankSegDev {
-    double T[12];            // T_wl of the bank's slot (k_to_world's Tf12)
+struct IncSegDev {
+    double T[12];            // T_wl of the map's slot
     const float4* feat;      // the slot's down-sampled stack of this kind
-    float4* ring;            // the bank's ring of this kind, LOCAL_WINDOW x MF
-    float4* map_out;         // the bank's map_tmp + kind * MM
+    float4* ring;            // the map's ring of this kind, LOCAL_WINDOW x MF
+    float4* map_out;         // the map's map_tmp + kind * MM
     int n_feat, ring_slot;   // the stack's size, localMapID % 50
     int cat_off, total;      // the segment's rows in the concatenation
     float leaf;
-    int ring_off[mml_ctx::LOCAL_WINDOW + 1];  // k_concat's RingOffsets, relative to cat_off
+    int ring_off[mml_ctx::LOCAL_WINDOW + 1];  // the ring slots' first rows, relative to cat_off
 };
 
-// k_to_world for every segment: the slot's stack into ring slot ring_slot
-__global__ __launch_bounds__(256) void k_bseg_to_world(const BankSegDev* __restrict__ tab, int MF) {
-    const BankSegDev& S = tab[blockIdx.y];
+// the slot's stack into ring slot ring_slot, in the world frame
+__global__ __launch_bounds__(256) void k_inc_to_world(const IncSegDev* __restrict__ tab, int MF) {
+    const IncSegDev& S = tab[blockIdx.y];
     const int n = S.n_feat;
     float4* out = S.ring + (size_t)S.ring_slot * MF;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
@@ -394,13 +257,13 @@ __global__ __launch_bounds__(256) void k_bseg_to_world(const BankSegDev* __restr
     }
 }
 
-// k_concat for every segment, one lane per point of the concatenation (the ring slot of a row: upper bound in the segment's 51
+// the ring in slot order, one lane per point of the concatenation (the ring slot of a row: upper bound in the segment's 51
 // offsets, held in LDS), and the bounding box of what it copies (getMinMax3D of the cloud the filter sees)
-__global__ __launch_bounds__(256) void k_bseg_concat_bbox(const BankSegDev* __restrict__ tab, int MF, float4* __restrict__ cat,
-                                                          int* __restrict__ bbox) {
+__global__ __launch_bounds__(256) void k_inc_concat_bbox(const IncSegDev* __restrict__ tab, int MF, float4* __restrict__ cat,
+                                                         int* __restrict__ bbox) {
     constexpr int W = mml_ctx::LOCAL_WINDOW;
     __shared__ int s_off[W + 1];
-    const BankSegDev& S = tab[blockIdx.y];
+    const IncSegDev& S = tab[blockIdx.y];
     const int total = S.total;
     if ((int)blockIdx.x * 256 >= total) return;  // (the whole workgroup)
     if (threadIdx.x <= W) s_off[threadIdx.x] = S.ring_off[threadIdx.x];
@@ -427,11 +290,11 @@ __global__ __launch_bounds__(256) void k_bseg_concat_bbox(const BankSegDev* __re
     mml_bbox_block_reduce(mn, mx, bbox + 6 * (size_t)blockIdx.y);
 }
 
-// k_vox_keys for every segment: segment << 32 | PCL voxel index in the segment's own box and leaf
-__global__ __launch_bounds__(256) void k_bseg_vox_keys(const BankSegDev* __restrict__ tab, const float4* __restrict__ cat,
-                                                       const int* __restrict__ bbox, unsigned long long* __restrict__ keys,
-                                                       unsigned* __restrict__ vals) {
-    const BankSegDev& S = tab[blockIdx.y];
+// PCL 1.8.1 voxel_grid.hpp applyFilter (MmlVoxGrid): segment << 32 | voxel index in the segment's own box and leaf
+__global__ __launch_bounds__(256) void k_inc_voxel_keys(const IncSegDev* __restrict__ tab, const float4* __restrict__ cat,
+                                                        const int* __restrict__ bbox, unsigned long long* __restrict__ keys,
+                                                        unsigned* __restrict__ vals) {
+    const IncSegDev& S = tab[blockIdx.y];
     const int total = S.total, off = S.cat_off;
     if ((int)blockIdx.x * 256 >= total) return;
     const MmlVoxGrid G = mml_vox_grid_of_keys(bbox + 6 * (size_t)blockIdx.y, S.leaf);
@@ -444,13 +307,13 @@ __global__ __launch_bounds__(256) void k_bseg_vox_keys(const BankSegDev* __restr
     }
 }
 
-// k_vox_centroid for every segment: one lane per voxel writes the centroid into the bank's map_tmp; the lane of the segment's
-// first row publishes the segment's voxel count (seg_m was zeroed: a segment without points keeps 0)
-__global__ __launch_bounds__(256) void k_bseg_centroid(const BankSegDev* __restrict__ tab, const float4* __restrict__ cat,
-                                                       const unsigned long long* __restrict__ keys, const unsigned* __restrict__ vals,
-                                                       const int* __restrict__ flag, const int* __restrict__ pos, int cap,
-                                                       int* __restrict__ seg_m) {
-    const BankSegDev& S = tab[blockIdx.y];
+// one lane per voxel: AccumulatorXYZ (float sum in input order, then / n) into the map's map_tmp; the lane of the segment's first
+// row publishes the segment's voxel count (seg_m was zeroed: a segment without points keeps 0)
+__global__ __launch_bounds__(256) void k_inc_centroid(const IncSegDev* __restrict__ tab, const float4* __restrict__ cat,
+                                                      const unsigned long long* __restrict__ keys, const unsigned* __restrict__ vals,
+                                                      const int* __restrict__ flag, const int* __restrict__ pos, int cap,
+                                                      int* __restrict__ seg_m) {
+    const IncSegDev& S = tab[blockIdx.y];
     const int off = S.cat_off, end = S.cat_off + S.total;
     for (int s = off + blockIdx.x * 256 + threadIdx.x; s < end; s += gridDim.x * 256) {
         if (s == off) seg_m[blockIdx.y] = pos[end - 1] + flag[end - 1] - pos[off];
@@ -463,9 +326,9 @@ __global__ __launch_bounds__(256) void k_bseg_centroid(const BankSegDev* __restr
     }
 }
 
-// k_bbox of every segment's filtered cloud (its size is on the device)
-__global__ __launch_bounds__(256) void k_bseg_bbox_out(const BankSegDev* __restrict__ tab, const int* __restrict__ seg_m, int cap,
-                                                       int* __restrict__ bbox) {
+// the bounding box of every segment's filtered cloud (its size is on the device)
+__global__ __launch_bounds__(256) void k_inc_bbox_out(const IncSegDev* __restrict__ tab, const int* __restrict__ seg_m, int cap,
+                                                      int* __restrict__ bbox) {
     const float4* pts = tab[blockIdx.y].map_out;
     int m = seg_m[blockIdx.y];
     m = m < cap ? m : cap;
@@ -483,36 +346,37 @@ __global__ __launch_bounds__(256) void k_bseg_bbox_out(const BankSegDev* __restr
     mml_bbox_block_reduce(mn, mx, bbox + 6 * (size_t)blockIdx.y);
 }
 
-// one chunk of banks [i0, i1) of the call: steps 2-4.  nf: the call's 2 n stack sizes.
-int bank_increment_chunk(mml_ctx* ctx, int i0, int i1, const int* banks, const int* slots, const double* T_wl, const int* nf,
-                         int* n_corner, int* n_surf) {
+// what a message calls a map
+std::string map_name(const MmlMapRef& map) { return map.bank < 0 ? std::string("the context's own local map") : "map bank " + std::to_string(map.bank); }
+
+// one chunk of maps [i0, i1) of the call: steps 2-4.  nf: the call's 2 n stack sizes.
+int increment_chunk(mml_ctx* ctx, int i0, int i1, const MmlMapIncrement* inc, const int* nf, int* n_corner, int* n_surf) {
     constexpr int W = mml_ctx::LOCAL_WINDOW;
     hipStream_t s = MML_STREAM(ctx);
     mml_ctx::BankInc& K = ctx->bank_inc;
     const int nb = i1 - i0, nseg = 2 * nb;
     // the chunk's block, the same layout on the device and in the pinned twin
     MmlCarve<16> carve;
-    const MmlField<BankSegDev> f_seg = carve.take<BankSegDev>((size_t)nseg);
+    const MmlField<IncSegDev> f_seg = carve.take<IncSegDev>((size_t)nseg);
     const MmlField<int> f_bbox_in = carve.take<int>(6 * (size_t)nseg);
     const MmlField<int> f_back = carve.take<int>(7 * (size_t)nseg);  // read back in one copy: nseg sizes, nseg filtered boxes
     const size_t up_bytes = carve.bytes();
-    const MmlField<char> f_grid = carve.take<char>(mml_grid_seg_table_bytes(nseg));
-    const MmlField<int> f_occ = carve.take<int>((size_t)nseg);
-    BankSegDev* h_seg = f_seg.in(K.tab.h);
+    const MmlField<char> f_grid = carve.take<char>(mml_grid_table_bytes(nseg));
+    IncSegDev* h_seg = f_seg.in(K.tab.h);
     int* h_back = f_back.in(K.tab.h);
     const int empty[6] = MML_BBOX_EMPTY;
     long long total = 0;
     int max_feat = 0, max_total = 0;
     for (int i = i0; i < i1; ++i) {
-        const MmlMapRef map = mml_map_bank(ctx, banks[i]);
+        const MmlMapRef& map = inc[i].map;
         const int Id = (int)(*map.local_map_id % W);  // :1597
         for (int kind = 0; kind < 2; ++kind) {
             const int g = 2 * (i - i0) + kind, n = nf[2 * (size_t)i + kind];
             map.ring_n[kind][Id] = n;
-            BankSegDev& S = h_seg[g];
+            IncSegDev& S = h_seg[g];
             memset(static_cast<void*>(&S), 0, sizeof(S));
-            memcpy(S.T, T_wl + 16 * (size_t)i, sizeof(double) * 12);
-            S.feat = ctx->ft_xyz[kind] + (size_t)slots[i] * ctx->MF;
+            memcpy(S.T, inc[i].T_wl, sizeof(double) * 12);
+            S.feat = ctx->ft_xyz[kind] + (size_t)inc[i].slot * ctx->MF;
             S.ring = map.ring[kind];
             S.map_out = map.map_tmp + (size_t)kind * ctx->MM;
             S.n_feat = n;
@@ -528,9 +392,9 @@ int bank_increment_chunk(mml_ctx* ctx, int i0, int i1, const int* banks, const i
             h_back[g] = 0;
         }
     }
-    MML_REQUIRE(total <= (long long)K.cap, MML_ERR_CAPACITY, "segmented bank increment: more ring points than the scratch holds");
+    MML_REQUIRE(total <= (long long)K.cap, MML_ERR_CAPACITY, "local-map increment: more ring points than the scratch holds");
     MML_HIP(hipMemcpyAsync(K.tab.d, K.tab.h, up_bytes, hipMemcpyHostToDevice, s));
-    const BankSegDev* d_seg = f_seg.in(K.tab.d);
+    const IncSegDev* d_seg = f_seg.in(K.tab.d);
     int* d_bbox_in = f_bbox_in.in(K.tab.d);
     int* d_seg_m = f_back.in(K.tab.d);
     int* d_bbox_out = d_seg_m + nseg;
@@ -539,11 +403,11 @@ int bank_increment_chunk(mml_ctx* ctx, int i0, int i1, const int* banks, const i
     int* flag = K.flag;
     int* pos = K.flag + K.cap + 1;
     auto blocks_for = [](int n) { return n > 0 ? ((n + 255) / 256 < 256 ? (n + 255) / 256 : 256) : 1; };
-    if (max_feat) hipLaunchKernelGGL(k_bseg_to_world, dim3(blocks_for(max_feat), nseg), dim3(256), 0, s, d_seg, ctx->MF);
+    if (max_feat) hipLaunchKernelGGL(k_inc_to_world, dim3(blocks_for(max_feat), nseg), dim3(256), 0, s, d_seg, ctx->MF);
     if (total) {
         const int blocks = blocks_for(max_total);
-        hipLaunchKernelGGL(k_bseg_concat_bbox, dim3(blocks, nseg), dim3(256), 0, s, d_seg, ctx->MF, K.cat, d_bbox_in);
-        hipLaunchKernelGGL(k_bseg_vox_keys, dim3(blocks, nseg), dim3(256), 0, s, d_seg, K.cat, d_bbox_in, K.keys, K.vals);
+        hipLaunchKernelGGL(k_inc_concat_bbox, dim3(blocks, nseg), dim3(256), 0, s, d_seg, ctx->MF, K.cat, d_bbox_in);
+        hipLaunchKernelGGL(k_inc_voxel_keys, dim3(blocks, nseg), dim3(256), 0, s, d_seg, K.cat, d_bbox_in, K.keys, K.vals);
         int seg_bits = 1;
         while ((1 << seg_bits) < nseg) ++seg_bits;
         int rc = mml_sort_pairs(ctx, ctx->sort_tmp, K.keys, keys2, K.vals, vals2, (size_t)total, 32 + seg_bits, s);
@@ -552,29 +416,30 @@ int bank_increment_chunk(mml_ctx* ctx, int i0, int i1, const int* banks, const i
                            ~0ull, flag);
         rc = mml_exclusive_scan(ctx, ctx->sort_tmp, flag, pos, (size_t)total, s);
         if (rc != MML_OK) return rc;
-        hipLaunchKernelGGL(k_bseg_centroid, dim3(blocks, nseg), dim3(256), 0, s, d_seg, K.cat, keys2, vals2, flag, pos, ctx->MM, d_seg_m);
-        hipLaunchKernelGGL(k_bseg_bbox_out, dim3(blocks, nseg), dim3(256), 0, s, d_seg, d_seg_m, ctx->MM, d_bbox_out);
+        hipLaunchKernelGGL(k_inc_centroid, dim3(blocks, nseg), dim3(256), 0, s, d_seg, K.cat, keys2, vals2, flag, pos, ctx->MM, d_seg_m);
+        hipLaunchKernelGGL(k_inc_bbox_out, dim3(blocks, nseg), dim3(256), 0, s, d_seg, d_seg_m, ctx->MM, d_bbox_out);
     }
     MML_HIP(hipMemcpyAsync(h_back, d_seg_m, f_back.bytes(), hipMemcpyDeviceToHost, s));
     MML_HIP(hipStreamSynchronize(s));  // the chunk's second synchronisation of 2 + R (the first read the stack sizes)
     for (int g = 0; g < nseg; ++g)
-        if (h_back[g] > ctx->MM) return mml_refuse(ctx, MML_ERR_CAPACITY, "map bank %d: filtered local map larger than max_map_points", banks[i0 + g / 2]);
+        if (h_back[g] > ctx->MM)
+            return mml_refuse(ctx, MML_ERR_CAPACITY, "%s: filtered local map larger than max_map_points", map_name(inc[i0 + g / 2].map).c_str());
     std::vector<MmlGridJob> jobs((size_t)nseg);
     for (int g = 0; g < nseg; ++g) {
-        const MmlMapRef map = mml_map_bank(ctx, banks[i0 + g / 2]);
+        const MmlMapRef& map = inc[i0 + g / 2].map;
         const int kind = g & 1;
         map.have_map[kind] = false;  // (mml_build_grid)
         map.grid[kind].tags = nullptr;
         jobs[g] = MmlGridJob{&map.grid[kind], map.map_tmp + (size_t)kind * ctx->MM, kind == 0 ? ctx->cfg.cell_corner : ctx->cfg.cell_surf,
-                             h_back[g], h_back + nseg + 6 * (size_t)g};
+                             h_back[g], h_back + nseg + 6 * (size_t)g, nullptr};
     }
     ctx->banks.dirty = true;  // (the descriptor table of a context with banks holds a copy of these grids)
-    MmlGridSegScratch G{K.keys, keys2, K.vals, vals2, K.cap, f_grid.in(K.tab.d), f_grid.in(K.tab.h), f_occ.in(K.tab.d), f_occ.in(K.tab.h)};
+    const MmlGridScratch<unsigned long long> G{K.keys, keys2, K.vals, vals2, K.cap, f_grid.in(K.tab.d), f_grid.in(K.tab.h)};
     int rounds = 0;
-    const int rc = mml_build_grids_segmented(ctx, nseg, jobs.data(), G, &rounds);
+    const int rc = mml_build_grids(ctx, nseg, jobs.data(), G, &rounds);
     if (rc != MML_OK) return rc;
     for (int i = i0; i < i1; ++i) {
-        const MmlMapRef map = mml_map_bank(ctx, banks[i]);
+        const MmlMapRef& map = inc[i].map;
         for (int kind = 0; kind < 2; ++kind) {
             map.have_map[kind] = true;
             map.local_map_n[kind] = h_back[2 * (i - i0) + kind];
@@ -587,41 +452,41 @@ int bank_increment_chunk(mml_ctx* ctx, int i0, int i1, const int* banks, const i
 }
 }  // namespace
 
-int mml_map_upkeep_increment_segmented(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl, int* n_corner, int* n_surf) {
+int mml_map_upkeep_increment_segmented(mml_ctx* ctx, int n, const MmlMapIncrement* inc, int* n_corner, int* n_surf) {
     constexpr int W = mml_ctx::LOCAL_WINDOW;
     hipStream_t s = MML_STREAM(ctx);
     mml_ctx::BankInc& K = ctx->bank_inc;
-    // step 1: the stack sizes in one copy (the context's 2 B ints), those of the n slots checked before a bank changes
+    // step 1: the stack sizes in one copy (the context's 2 B ints), those of the n slots checked before a map changes
     std::vector<int> nf(2 * (size_t)n);
     {
         int* h = reinterpret_cast<int*>(mml_stage_alloc(ctx, (size_t)ctx->B + 1));  // pinned
         MML_HIP(hipMemcpyAsync(h, ctx->ft_n, sizeof(int) * 2 * (size_t)ctx->B, hipMemcpyDeviceToHost, s));
         MML_HIP(hipStreamSynchronize(s));
         for (int i = 0; i < n; ++i)
-            for (int kind = 0; kind < 2; ++kind) nf[2 * (size_t)i + kind] = h[(size_t)kind * ctx->B + slots[i]];
+            for (int kind = 0; kind < 2; ++kind) nf[2 * (size_t)i + kind] = h[(size_t)kind * ctx->B + inc[i].slot];
     }
     for (int i = 0; i < n; ++i)
         for (int kind = 0; kind < 2; ++kind) {
             const int f = nf[2 * (size_t)i + kind];
-            if (f < 0 || f > ctx->MF) return mml_refuse(ctx, MML_ERR_STATE, "slot %d holds no down-sampled feature stack", slots[i]);
+            if (f < 0 || f > ctx->MF) return mml_refuse(ctx, MML_ERR_STATE, "slot %d holds no down-sampled feature stack", inc[i].slot);
         }
-    // every segment's ring total after the write, the filter's own limit (voxel_filter_device) and the chunks: greedy, in call order
+    // every segment's ring total after the write, the filter's own limit and the chunks: greedy, in call order
     std::vector<long long> pts((size_t)n);
     for (int i = 0; i < n; ++i) {
-        const MmlMapRef map = mml_map_bank(ctx, banks[i]);
+        const MmlMapRef& map = inc[i].map;
         const int Id = (int)(*map.local_map_id % W);
         pts[i] = 0;
         for (int kind = 0; kind < 2; ++kind) {
             long long t = nf[2 * (size_t)i + kind];
             for (int r = 0; r < W; ++r)
                 if (r != Id) t += map.ring_n[kind][r];
-            if (t > ctx->MM) return mml_refuse(ctx, MML_ERR_CAPACITY, "map bank %d: cloud larger than max_map_points", banks[i]);
+            if (t > ctx->MM) return mml_refuse(ctx, MML_ERR_CAPACITY, "%s: cloud larger than max_map_points", map_name(map).c_str());
             pts[i] += t;
         }
     }
-    std::vector<int> cut(1, 0);  // chunk c = banks [cut[c], cut[c + 1]) of the call
+    std::vector<int> cut(1, 0);  // chunk c = maps [cut[c], cut[c + 1]) of the call
     long long run = 0, max_pts = 1;
-    int max_banks = 1;
+    int max_maps = 1;
     for (int i = 0; i < n; ++i) {
         if (i > cut.back() && run + pts[i] > K.budget) {
             cut.push_back(i);
@@ -629,15 +494,15 @@ int mml_map_upkeep_increment_segmented(mml_ctx* ctx, int n, const int* banks, co
         }
         run += pts[i];
         if (run > max_pts) max_pts = run;
-        if (i + 1 - cut.back() > max_banks) max_banks = i + 1 - cut.back();
+        if (i + 1 - cut.back() > max_maps) max_maps = i + 1 - cut.back();
     }
     cut.push_back(n);
-    MML_REQUIRE(max_pts < (1ll << 31), MML_ERR_CAPACITY, "segmented bank increment: a bank's rings exceed 2^31 points");
-    // memory: the banks' rings (a first increment), the scratch for the largest chunk, its tables, the sort's temporary storage --
+    MML_REQUIRE(max_pts < (1ll << 31), MML_ERR_CAPACITY, "local-map increment: a chunk's rings exceed 2^31 points");
+    // memory: the maps' rings (a first increment), the scratch for the largest chunk, its tables, the sort's temporary storage --
     // all before the first launch, so that nothing is replaced while a chunk's kernels run
     const size_t ring_pts = (size_t)W * ctx->MF;
     for (int i = 0; i < n; ++i) {
-        const MmlMapRef map = mml_map_bank(ctx, banks[i]);
+        const MmlMapRef& map = inc[i].map;
         if (map.ring_mem->present()) continue;
         const int rc = map.ring_mem->reserve(ctx, {mml_part(map.ring[0], ring_pts), mml_part(map.ring[1], ring_pts)});
         if (rc != MML_OK) return rc;
@@ -650,8 +515,8 @@ int mml_map_upkeep_increment_segmented(mml_ctx* ctx, int n, const int* banks, co
         K.cap = cap;
     }
     {
-        const size_t nseg = 2 * (size_t)max_banks;
-        const size_t bytes = sizeof(BankSegDev) * nseg + sizeof(int) * 14 * nseg + mml_grid_seg_table_bytes((int)nseg) + 16 * 8;
+        const size_t nseg = 2 * (size_t)max_maps;
+        const size_t bytes = sizeof(IncSegDev) * nseg + sizeof(int) * 13 * nseg + mml_grid_table_bytes((int)nseg) + 16 * 8;
         int rc = K.tab.reserve(ctx, bytes);
         if (rc != MML_OK) return rc;
         int seg_bits = 1;
@@ -660,9 +525,18 @@ int mml_map_upkeep_increment_segmented(mml_ctx* ctx, int n, const int* banks, co
         if (rc != MML_OK) return rc;
     }
     for (size_t c = 0; c + 1 < cut.size(); ++c) {
-        const int rc = bank_increment_chunk(ctx, cut[c], cut[c + 1], banks, slots, T_wl, nf.data(), n_corner, n_surf);
+        const int rc = increment_chunk(ctx, cut[c], cut[c + 1], inc, nf.data(), n_corner, n_surf);
         if (rc != MML_OK) return rc;
     }
     MML_HIP(hipGetLastError());
     return MML_OK;
+}
+
+// one map: the chain with n = 1, its two kinds two segments
+int mml_map_upkeep_increment(mml_ctx* ctx, const MmlMapRef& map, int slot, const double* T_wl, int* n_out) {
+    const MmlMapIncrement inc{map, slot, T_wl};
+    int n[2] = {0, 0};
+    const int rc = mml_map_upkeep_increment_segmented(ctx, 1, &inc, &n[0], &n[1]);
+    if (rc == MML_OK && n_out) n_out[0] = n[0], n_out[1] = n[1];
+    return rc;
 }

@@ -343,10 +343,7 @@ struct mml_ctx {
     // device-side local map upkeep (Estimator::MapIncrementLocal): ring of key scans' features in the world frame
     static constexpr int LOCAL_WINDOW = MML_LOCAL_WINDOW;
     float4* ring[2] = {nullptr, nullptr};    // LOCAL_WINDOW x MF each
-    float4* ring_cat = nullptr;              // concatenation scratch, LOCAL_WINDOW x MF
-    int* vox_flag = nullptr;                 // head flags / positions, 2 x (vox_cap + 1)
-    size_t vox_cap = 0;                      // points ring_cat / vox_flag are sized for
-    MmlGroup ring_mem;                       // owns ring[2], ring_cat, vox_flag; allocated by the first increment
+    MmlGroup ring_mem;                       // owns ring[2]; allocated by the first increment, like a bank's
     int ring_n[2][LOCAL_WINDOW] = {};
     long local_map_id = 0;                   // localMapID
     // scratch of the cube stores' upkeep, shared by the own store and every bank's (one increment runs at a time)
@@ -356,8 +353,8 @@ struct mml_ctx {
     MmlStaging<char, false> wire_stage;      // raw message bytes on their way in / out (one call at a time; grows to the largest)
     int local_map_n[2] = {0, 0};
     MmlBanks banks;                    // map banks (map_banks.hip): further local maps, and which slot is matched against which
-    // scratch of the segmented bank increment (map_upkeep.hip mml_map_upkeep_increment_segmented), sized by the ring points of
-    // the largest chunk of banks a call has worked on: 48 bytes per point
+    // scratch of the local-map increment (map_upkeep.hip mml_map_upkeep_increment_segmented), of the own map's as of the banks':
+    // sized by the ring points of the largest chunk of maps a call has worked on, 48 bytes per point
     struct BankInc {
         float4* cat = nullptr;               // the chunk's rings, concatenated
         unsigned long long* keys = nullptr;  // 2 x cap: sort keys in / out
@@ -373,6 +370,7 @@ struct mml_ctx {
     unsigned* map_keys2 = nullptr;
     unsigned* map_vals = nullptr;
     unsigned* map_vals2 = nullptr;
+    MmlStaging<char> grid_tab;         // the one-cloud grid build's table (mml_grid_table_bytes(1)): device block and pinned twin
     MmlStaging<char, false> sort_tmp;  // rocPRIM temporary storage of the map builds and filters (voxel_sort_dev.h)
     int MM = 0;
 
@@ -417,6 +415,7 @@ struct mml_ctx {
         clive.mem.release();
         cube_scratch.release();
         wire_stage.release();
+        grid_tab.release();
         sort_tmp.release();
         fixed.release();
     }
@@ -485,24 +484,25 @@ int mml_launch_downsample(mml_ctx* ctx, int first, int count);
 // labelled corner points per (slot, kind) that the LDS sort of k_voxel takes (surf: MML_VOXEL_LDS_CAP)
 inline int mml_voxel_cap_corner(const mml_ctx* ctx) { return (ctx->NT > 65536 || MML_VOXEL_LDS_CAP < 2048) ? MML_VOXEL_LDS_CAP : 2048; }
 // The state of one local map, by reference: the context's own fields (mml_map_own) or a bank's (mml_map_bank).  Map upkeep and
-// the grid build take the map they work on as this parameter; the scratch they use (ring_cat, vox_flag, the sort buffers) is the
-// context's either way.
+// the grid build take the maps they work on as this parameter -- there is one increment chain and one grid builder, each written
+// for n maps, and the own map is simply one more; the scratch they use (bank_inc, the sort buffers) is the context's either way.
 struct MmlMapRef {
     MmlGrid* grid;      // [2]
     bool* have_map;     // [2]
     float4* map_tmp;    // 2 x MM
     float4** ring;      // [2]
-    MmlGroup* ring_mem;
+    MmlGroup* ring_mem; // owns ring[2]
     int (*ring_n)[MML_LOCAL_WINDOW];  // [2]
     long* local_map_id;
     int* local_map_n;   // [2]
+    int bank;           // what a message calls the map: the bank, -1 the context's own
 };
 inline MmlMapRef mml_map_own(mml_ctx* c) {
-    return MmlMapRef{c->grid, c->have_map, c->map_tmp, c->ring, &c->ring_mem, c->ring_n, &c->local_map_id, c->local_map_n};
+    return MmlMapRef{c->grid, c->have_map, c->map_tmp, c->ring, &c->ring_mem, c->ring_n, &c->local_map_id, c->local_map_n, -1};
 }
 inline MmlMapRef mml_map_bank(mml_ctx* c, int bank) {
     MmlMapBank& b = c->banks.bank[(size_t)bank];
-    return MmlMapRef{b.grid, b.have_map, b.map_tmp, b.ring, &b.ring_mem, b.ring_n, &b.local_map_id, b.local_map_n};
+    return MmlMapRef{b.grid, b.have_map, b.map_tmp, b.ring, &b.ring_mem, b.ring_n, &b.local_map_id, b.local_map_n, bank};
 }
 int mml_build_grid(mml_ctx* ctx, const MmlMapRef& map, int kind, const float* h_xyz, int m);
 int mml_build_grid_device(mml_ctx* ctx, const MmlMapRef& map, int kind, int m);
@@ -524,29 +524,39 @@ int mml_gicp_align_device(mml_ctx* ctx, const char* who, const float4* d_src, in
                           const mml_gicp_opts* opts, float* T_inout, int* converged, mml_gicp_info* info);
 int mml_downsample_big(mml_ctx* ctx, int first, int count);
 int mml_downsample_redo_overflow(mml_ctx* ctx, int first, int count, std::vector<int>* redone);
+// Estimator::MapIncrementLocal (map_upkeep.hip): map `map` grows by the two stacks of `slot` at T_wl (16 doubles, row-major).
+struct MmlMapIncrement {
+    MmlMapRef map;
+    int slot;
+    const double* T_wl;
+};
+// n distinct maps in one chain of launches; the caller has checked the arguments and drained the context.  Checks every slot's
+// stack before a map changes: all or nothing.
+int mml_map_upkeep_increment_segmented(mml_ctx* ctx, int n, const MmlMapIncrement* inc, int* n_corner, int* n_surf);
+// one map: the chain with n = 1
 int mml_map_upkeep_increment(mml_ctx* ctx, const MmlMapRef& map, int slot, const double* T_wl, int* n_out);
-// The same for n distinct banks in one chain of launches (map_upkeep.hip); the caller has checked the arguments and drained the
-// context.  Checks every slot's stack before a bank changes.
-int mml_map_upkeep_increment_segmented(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl, int* n_corner, int* n_surf);
-// map_assoc.hip: build_grid_into for nseg clouds that are on the device, one sort and one read-back per refinement round for all
-// of them.  A job: the grid to fill (its pts / cell_start are the destination), the unsorted cloud, the configured cell edge, the
-// cloud's size and its bounding box as six keys (MML_BBOX_EMPTY where m = 0).
+// map_assoc.hip, the grid build: nseg clouds that are on the device, one sort and one read-back per refinement round for all of
+// them.  A job: the grid to fill (its pts / cell_start / tags are the destination), the unsorted cloud, the configured cell edge,
+// the cloud's size, its bounding box as six keys (MML_BBOX_EMPTY where m = 0), and the points' tags in the cloud's order (null: the
+// cloud has none).  Key: unsigned long long (segment << 32 | cell) for any nseg, unsigned (the cell alone) for nseg = 1.
 struct MmlGridJob {
     MmlGrid* g;
     const float4* orig;
     float cell;
     int m;
     const int* bbox_keys;
+    const uint16_t* tag_orig;
 };
-struct MmlGridSegScratch {
-    unsigned long long *keys, *keys2;  // cap each
+template <class Key>
+struct MmlGridScratch {
+    Key *keys, *keys2;    // cap each
     unsigned *vals, *vals2;
-    size_t cap;                        // points
-    void *tab_d, *tab_h;               // mml_grid_seg_table_bytes(nseg) on the device and pinned
-    int *occ_d, *occ_h;                // nseg ints each, occ_h pinned
+    size_t cap;           // points
+    void *tab_d, *tab_h;  // mml_grid_table_bytes(nseg) on the device and pinned
 };
-size_t mml_grid_seg_table_bytes(int nseg);
-int mml_build_grids_segmented(mml_ctx* ctx, int nseg, const MmlGridJob* jobs, const MmlGridSegScratch& W, int* rounds);
+size_t mml_grid_table_bytes(int nseg);
+template <class Key>
+int mml_build_grids(mml_ctx* ctx, int nseg, const MmlGridJob* jobs, const MmlGridScratch<Key>& W, int* rounds);
 // The state of one global cube map, by reference: the context's own (mml_cube_own) or a bank's (mml_cube_bank).  The grid builds
 // and the store's upkeep take the map they work on as this parameter, as the local map's take MmlMapRef.
 struct MmlCubeRef {

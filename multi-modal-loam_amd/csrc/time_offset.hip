@@ -77,7 +77,7 @@ __global__ __launch_bounds__(256) void k_tofs_box(const TofsProb* __restrict__ t
     mml_bbox_block_reduce(mn, mx, box + 6 * (size_t)blockIdx.y);
 }
 
-// sort key of every point: problem << 32 | cell (the cell mapping of map_assoc.hip's k_cell_keys), value: its index in the problem
+// sort key of every point: problem << 32 | cell (the cell mapping of map_assoc.hip's k_grid_keys), value: its index in the problem
 __global__ __launch_bounds__(256) void k_tofs_keys(const TofsProb* __restrict__ tab, const float4* __restrict__ pts,
                                                    unsigned long long* __restrict__ keys, unsigned* __restrict__ vals) {
     const TofsProb& P = tab[blockIdx.y];

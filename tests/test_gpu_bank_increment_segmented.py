@@ -1,16 +1,25 @@
-"""mml_map_bank_increment_segmented (include/mmloam_hip.h, "map banks"): the n banks of a call in one chain of launches.
+"""mml_map_bank_increment and mml_map_bank_increment_segmented (include/mmloam_hip.h, "map banks"): the loop over the banks of a call
+and the n banks of a call in one chain of launches.
 
-Everything here is bit-equality between two contexts with the same feature stacks: A grows its banks with bank_increment (the loop),
-B with bank_increment(..., segmented=True).  The segmented kernels restate the loop's arithmetic expression for expression and both
-paths sort stably, so no tolerance is needed and none is used.  What is compared: the sizes returned, the filtered clouds with their
-order (bank_download), and -- through associate on bound slots -- the grids (grid.pts with its source indices, cell_start, the
-descriptors): factor records, src arrays and the far-query count."""
+Both call forms run the one increment chain of map_upkeep.hip, so comparing one with the other alone would prove nothing.  They are
+anchored twice.  tests/golden/bank_increment_parent.npz (make_bank_increment_parent.py) holds what the loop of the commit before the
+chains were merged -- a separate implementation -- returned on a MI355X for the inputs of tests 1-4 and 6: sizes, poses and SHA-256
+digests of every downloaded byte string.  Both forms must reproduce it exactly.  test_oracle_history holds both forms to the CPU
+oracle's LocalMap, and says which map is wrong should the fixture ever disagree.  Loop against segmented in the same run stays as a
+second assertion.  What is compared: the sizes returned, the filtered clouds with their order (bank_download), and -- through
+associate on bound slots -- the grids (grid.pts with its source indices, cell_start, the descriptors): factor records, src arrays
+and the far-query count.  No tolerance is needed anywhere but in the oracle's factor records, and none is used.
+
+A run_* function below is one test's computation for one call form; it returns a flat dict name -> bytes / array / int.  The fixture
+is digest() of the loop form's dict (names starting with "_" are for the test's own use and are left out)."""
+import hashlib
 import importlib
+import os
 
 import numpy as np
 import pytest
 
-from conftest import perturbed
+from conftest import GOLDEN, perturbed
 
 pytestmark = pytest.mark.gpu
 
@@ -20,6 +29,37 @@ EMPTY = np.zeros((0, 3), np.float32)
 # finds the corner stack of bank 1's slot empty
 HISTORY = [[0, 1, 2], [2], [1, 0], [0, 1, 2], [2, 0], [0, 1, 2]]
 EMPTY_CORNER = (2, 1)   # (round, bank)
+FORMS = (False, True)   # segmented=
+
+
+def digest(run):
+    """The fixture form of a run: byte strings as their SHA-256 (32 uint8), arrays and ints as they are."""
+    out = {}
+    for name, v in run.items():
+        if name.startswith("_"):
+            continue
+        out[name] = np.frombuffer(hashlib.sha256(v).digest(), np.uint8) if isinstance(v, bytes) else np.asarray(v)
+    return out
+
+
+def _raw(run):
+    return {k: (v if isinstance(v, bytes) else (np.asarray(v).dtype.str, np.asarray(v).shape, np.asarray(v).tobytes()))
+            for k, v in run.items() if not k.startswith("_")}
+
+
+@pytest.fixture(scope="module")
+def parent():
+    with np.load(os.path.join(GOLDEN, "bank_increment_parent.npz")) as z:
+        return {k: z[k] for k in z.files}
+
+
+def assert_parent(parent, run, prefix, what):
+    """Every entry of the run equals the fixture's, and the fixture has no entry under `prefix` that the run lacks."""
+    got = digest(run)
+    assert sorted(got) == sorted(k for k in parent if k.startswith(prefix)), what
+    for k, v in got.items():
+        w = parent[k]
+        assert v.dtype == w.dtype and v.shape == w.shape and v.tobytes() == w.tobytes(), "%s: %s differs from the parent commit's loop" % (what, k)
 
 
 def _pair(M, **cfg):
@@ -47,134 +87,166 @@ def _records(c, s):
     return gl.tobytes(), glsrc.tobytes(), gp.tobytes(), gpsrc.tobytes()
 
 
-def _run_history(c, scene, synth, segmented, after_round=None):
-    """HISTORY on context c (slot b feeds bank b); returns the sizes and the four banks' clouds after every round."""
+def _history_round(c, scene, synth, rnd, how):
+    """Round rnd of HISTORY on context c (slot b feeds bank b): the sizes returned."""
+    banks = HISTORY[rnd]
+    if rnd == EMPTY_CORNER[0]:
+        c.features_upload(EMPTY_CORNER[1], 0, EMPTY)
+    nc, ns = c.bank_increment(banks, banks, np.stack([_pose(synth, scene, rnd, b) for b in banks]), **how)
+    if rnd == EMPTY_CORNER[0]:
+        c.features_upload(EMPTY_CORNER[1], 0, scene["frames"][EMPTY_CORNER[1]]["corner"])
+    return nc, ns
+
+
+def _associate_poses(synth, scene):
+    return np.stack([perturbed(_pose(synth, scene, len(HISTORY) - 1, b), dt=(0.02, 0.01, -0.01)) for b in range(4)])
+
+
+def run_histories(M, scene, synth, segmented, budget=None):
+    """Tests 1 and 4: HISTORY on a fresh context, the sizes and the four banks' clouds after every round, then slots 0-3 bound to
+    banks 0-3 and associated at perturbed poses: the far count and the four slots' records."""
     how = dict(segmented=True) if segmented else {}
-    out = []
-    for rnd, banks in enumerate(HISTORY):
-        if rnd == EMPTY_CORNER[0]:
-            c.features_upload(EMPTY_CORNER[1], 0, EMPTY)
-        nc, ns = c.bank_increment(banks, banks, np.stack([_pose(synth, scene, rnd, b) for b in banks]), **how)
-        if rnd == EMPTY_CORNER[0]:
-            c.features_upload(EMPTY_CORNER[1], 0, scene["frames"][EMPTY_CORNER[1]]["corner"])
-        out.append((nc.tobytes(), ns.tobytes(), _maps(c, range(4))))
-        if after_round:
-            after_round(rnd, out[-1])
+    out = {}
+    c = M.Context(max_scans=4, max_map_points=MM)
+    try:
+        c.map_banks(4)
+        if budget is not None:
+            c.debug_bank_increment_budget(budget)
+        _load(c, scene)
+        for rnd in range(len(HISTORY)):
+            nc, ns = _history_round(c, scene, synth, rnd, how)
+            out["hist.r%d.nc" % rnd], out["hist.r%d.ns" % rnd] = np.asarray(nc, np.int32), np.asarray(ns, np.int32)
+            for j, m in enumerate(_maps(c, range(4))):
+                out["hist.r%d.bank%d.kind%d" % (rnd, j // 2, j % 2)] = m
+        out["_n_bank1_corner"], out["_n_bank3_surf"] = len(c.bank_download(1, 0)), len(c.bank_download(3, 1))
+        c.bind_banks(0, [0, 1, 2, 3])
+        c.associate(0, 4, _associate_poses(synth, scene), 25.0)
+        out["hist.far"] = np.int64(c.associate_far_count())
+        for s in range(4):
+            rec = _records(c, s)
+            out["_n_rec%d" % s] = (len(rec[1]), len(rec[3]))
+            for j, r in enumerate(rec):
+                out["hist.rec.slot%d.%d" % (s, j)] = r
+    finally:
+        c.close()
     return out
 
 
-def _associate_all(c, scene, synth):
-    """Slots 0-3 bound to banks 0-3, associated at perturbed poses: (far count, the four slots' records)."""
-    c.bind_banks(0, [0, 1, 2, 3])
-    T = np.stack([perturbed(_pose(synth, scene, len(HISTORY) - 1, b), dt=(0.02, 0.01, -0.01)) for b in range(4)])
-    c.associate(0, 4, T, 25.0)
-    return c.associate_far_count(), [_records(c, s) for s in range(4)]
-
-
 @pytest.fixture(scope="module")
-def loop_history(M, scene, synth):
-    """Context A's results on HISTORY, computed once and read by tests 1 and 4: per round the sizes and clouds, then the association."""
-    a = M.Context(max_scans=4, max_map_points=MM)
-    try:
-        a.map_banks(4)
-        _load(a, scene)
-        rounds = _run_history(a, scene, synth, False)
-        far, rec = _associate_all(a, scene, synth)
-    finally:
-        a.close()
-    assert all(len(r[1]) > 0 for r in rec[:3]) and len(rec[3][1]) == 0 and len(rec[3][3]) == 0   # banks 0-2 give factors, bank 3 none
-    return dict(rounds=rounds, far=far, rec=rec)
+def histories(M, scene, synth):
+    """Both call forms' results on HISTORY, computed once and read by tests 1 and 4."""
+    return {seg: run_histories(M, scene, synth, seg) for seg in FORMS}
 
 
-def test_histories(M, scene, synth, loop_history):
+def test_histories(parent, histories):
     """Test 1: 4 banks over 6 rounds with different subsets per round."""
-    b = M.Context(max_scans=4, max_map_points=MM)
-    try:
-        b.map_banks(4)
-        _load(b, scene)
-
-        def check(rnd, got):
-            want = loop_history["rounds"][rnd]
-            assert got[0] == want[0] and got[1] == want[1], "sizes after round %d" % rnd
-            assert got[2] == want[2], "clouds after round %d" % rnd
-        _run_history(b, scene, synth, True, check)
-        assert len(b.bank_download(1, 0)) > 0 and len(b.bank_download(3, 1)) == 0
-        far, rec = _associate_all(b, scene, synth)
-        assert far == loop_history["far"]
-        for s in range(4):
-            assert rec[s] == loop_history["rec"][s], "slot %d" % s
-        assert len(rec[3][1]) == 0 and len(rec[3][3]) == 0            # bank 3 never grew: its slot gets no factor
-    finally:
-        b.close()
+    for seg in FORMS:
+        run = histories[seg]
+        assert_parent(parent, run, "hist.", "segmented=%s" % seg)
+        assert run["_n_bank1_corner"] > 0 and run["_n_bank3_surf"] == 0
+        assert all(min(run["_n_rec%d" % s]) > 0 for s in range(3))   # banks 0-2 give factors
+        assert run["_n_rec3"] == (0, 0)                               # bank 3 never grew: its slot gets no factor
+    assert _raw(histories[False]) == _raw(histories[True])
 
 
-def test_ring_wrap(M, scene, synth):
+def run_ring_wrap(M, scene, synth, segmented):
     """Test 2: 52 increments of bank 0 (the ring wraps at 50) next to bank 1 on every third round: localMapID % 50 differs."""
-    a, b = _pair(M)
+    how = dict(segmented=True) if segmented else {}
+    out = {}
+    sizes = np.full((52, 2, 2), -1, np.int32)   # [increment, corner / surf, bank of the call]
+    c = M.Context(max_scans=4, max_map_points=MM)
     try:
-        for c in (a, b):
-            c.map_banks(2)
-            c.features_upload(0, 0, scene["frames"][0]["corner"][:200])
-            c.features_upload(0, 1, scene["frames"][0]["surf"][:400])
-            c.features_upload(1, 0, scene["frames"][1]["corner"][:150])
-            c.features_upload(1, 1, scene["frames"][1]["surf"][:300])
+        c.map_banks(2)
+        c.features_upload(0, 0, scene["frames"][0]["corner"][:200])
+        c.features_upload(0, 1, scene["frames"][0]["surf"][:400])
+        c.features_upload(1, 0, scene["frames"][1]["corner"][:150])
+        c.features_upload(1, 1, scene["frames"][1]["surf"][:300])
         for i in range(1, 53):
             banks = [0, 1] if i % 3 == 0 else [0]
             T = np.stack([synth.pose_matrix(3 * i + k) for k in banks])
-            sa = a.bank_increment(banks, banks, T)
-            sb = b.bank_increment(banks, banks, T, segmented=True)
-            assert sa[0].tobytes() == sb[0].tobytes() and sa[1].tobytes() == sb[1].tobytes(), "sizes, increment %d" % i
+            nc, ns = c.bank_increment(banks, banks, T, **how)
+            sizes[i - 1, 0, :len(banks)], sizes[i - 1, 1, :len(banks)] = nc, ns
             if i in (1, 50, 51, 52):
-                assert _maps(a, (0, 1)) == _maps(b, (0, 1)), "increment %d" % i
-                assert len(b.bank_download(0, 1)) > 0
+                for j, m in enumerate(_maps(c, (0, 1))):
+                    out["wrap.i%d.bank%d.kind%d" % (i, j // 2, j % 2)] = m
+                assert len(c.bank_download(0, 1)) > 0
     finally:
-        a.close()
-        b.close()
+        c.close()
+    out["wrap.sizes"] = sizes
+    return out
+
+
+def test_ring_wrap(M, scene, synth, parent):
+    runs = {seg: run_ring_wrap(M, scene, synth, seg) for seg in FORMS}
+    for seg in FORMS:
+        assert_parent(parent, runs[seg], "wrap.", "segmented=%s" % seg)
+    assert _raw(runs[False]) == _raw(runs[True])
 
 
 def _per_cell(cloud, cell):
-    """Points per occupied cell of build_grid_into's first round: origin = the cloud's minimum, floor((p - o) * (1 / cell))."""
+    """Points per occupied cell of the grid build's first round: origin = the cloud's minimum, floor((p - o) * (1 / cell))."""
     inv = np.float32(1.0) / np.float32(cell)
     ijk = np.floor((cloud - cloud.min(axis=0)) * inv).astype(np.int64)
     return len(cloud) / len(np.unique(ijk, axis=0))
 
 
-def test_refinement(M):
-    """Test 3: cell = 8 x leaf.  Bank 0's surf map is a plane sampled just above the leaf: ~58 points per cell, two more rounds; bank 1's
-    maps finish in round 0 -- in the same call."""
-    leaf_c, leaf_s = 0.4, 0.2
-    a, b = _pair(M, leaf_corner=leaf_c, leaf_surf=leaf_s, cell_corner=8 * leaf_c, cell_surf=8 * leaf_s)
+REFINE_LEAF = (0.4, 0.2)
+
+
+def refinement_clouds():
+    """(line, dense, sparse): the dense plane is sampled just above the surf leaf, ~58 points per cell at cell = 8 x leaf."""
+    g = np.arange(60, dtype=np.float32)
+    xx, yy = np.meshgrid(g * np.float32(0.21), g * np.float32(0.21))
+    dense = np.stack([xx.ravel(), yy.ravel(), np.float32(0.05) * np.sin(xx.ravel())], axis=1).astype(np.float32)
+    sx, sy = np.meshgrid(g[:30] * np.float32(0.7), g[:30] * np.float32(0.7))
+    sparse = np.stack([sx.ravel(), sy.ravel(), np.float32(0.1) * np.cos(sy.ravel())], axis=1).astype(np.float32)
+    line = np.stack([g * np.float32(0.45), np.float32(0.3) * g, np.zeros(60, np.float32)], axis=1).astype(np.float32)
+    return line, dense, sparse
+
+
+def run_refinement(M, segmented):
+    """Test 3: cell = 8 x leaf.  Bank 0's surf map takes two more rounds; bank 1's maps finish in round 0 -- in the same call."""
+    how = dict(segmented=True) if segmented else {}
+    leaf_c, leaf_s = REFINE_LEAF
+    line, dense, sparse = refinement_clouds()
+    T = np.stack([perturbed(np.eye(4)), perturbed(np.eye(4), dt=(1.0, -2.0, 0.5))])
+    out = {}
+    c = M.Context(max_scans=4, max_map_points=MM, leaf_corner=leaf_c, leaf_surf=leaf_s, cell_corner=8 * leaf_c, cell_surf=8 * leaf_s)
     try:
-        g = np.arange(60, dtype=np.float32)
-        xx, yy = np.meshgrid(g * np.float32(0.21), g * np.float32(0.21))
-        dense = np.stack([xx.ravel(), yy.ravel(), np.float32(0.05) * np.sin(xx.ravel())], axis=1).astype(np.float32)
-        sx, sy = np.meshgrid(g[:30] * np.float32(0.7), g[:30] * np.float32(0.7))
-        sparse = np.stack([sx.ravel(), sy.ravel(), np.float32(0.1) * np.cos(sy.ravel())], axis=1).astype(np.float32)
-        line = np.stack([g * np.float32(0.45), np.float32(0.3) * g, np.zeros(60, np.float32)], axis=1).astype(np.float32)
-        T = np.stack([perturbed(np.eye(4)), perturbed(np.eye(4), dt=(1.0, -2.0, 0.5))])
-        for c, how in ((a, {}), (b, dict(segmented=True))):
-            c.map_banks(2)
-            c.features_upload(0, 0, line)
-            c.features_upload(0, 1, dense)
-            c.features_upload(1, 0, line[::2])
-            c.features_upload(1, 1, sparse)
-            c.bank_increment([0, 1], [0, 1], T, **how)
-        surf0, surf1 = b.bank_download(0, 1), b.bank_download(1, 1)
-        d0, d1 = _per_cell(surf0, 8 * leaf_s), _per_cell(surf1, 8 * leaf_s)
+        c.map_banks(2)
+        c.features_upload(0, 0, line)
+        c.features_upload(0, 1, dense)
+        c.features_upload(1, 0, line[::2])
+        c.features_upload(1, 1, sparse)
+        c.bank_increment([0, 1], [0, 1], T, **how)
+        out["_surf0"], out["_surf1"], out["_corner1"] = c.bank_download(0, 1), c.bank_download(1, 1), c.bank_download(1, 0)
+        for j, m in enumerate(_maps(c, (0, 1))):
+            out["refine.bank%d.kind%d" % (j // 2, j % 2)] = m
+        c.bind_banks(0, [0, 1])
+        c.associate(0, 2, np.stack([perturbed(t, dt=(0.01, 0.02, -0.01)) for t in T]), 25.0)
+        out["refine.far"] = np.int64(c.associate_far_count())
+        for s in range(2):
+            rec = _records(c, s)
+            out["_n_plane%d" % s] = len(rec[3])
+            for j, r in enumerate(rec):
+                out["refine.rec.slot%d.%d" % (s, j)] = r
+    finally:
+        c.close()
+    return out
+
+
+def test_refinement(M, parent):
+    leaf_c, leaf_s = REFINE_LEAF
+    runs = {seg: run_refinement(M, seg) for seg in FORMS}
+    for seg in FORMS:
+        run = runs[seg]
+        d0, d1 = _per_cell(run["_surf0"], 8 * leaf_s), _per_cell(run["_surf1"], 8 * leaf_s)
         print("points per occupied cell at 8 x leaf: bank 0 %.2f, bank 1 %.2f" % (d0, d1))
         assert d0 > 12.0, "bank 0's surf map no longer reaches the refinement rounds"
-        assert d1 <= 12.0 and _per_cell(b.bank_download(1, 0), 8 * leaf_c) <= 12.0
-        assert _maps(a, (0, 1)) == _maps(b, (0, 1))
-        rec = []
-        for c in (a, b):
-            c.bind_banks(0, [0, 1])
-            c.associate(0, 2, np.stack([perturbed(t, dt=(0.01, 0.02, -0.01)) for t in T]), 25.0)
-            rec.append((c.associate_far_count(), _records(c, 0), _records(c, 1)))
-        assert rec[0] == rec[1]
-        assert len(rec[1][1][3]) > 0 and len(rec[1][2][3]) > 0       # plane factors against both banks
-    finally:
-        a.close()
-        b.close()
+        assert d1 <= 12.0 and _per_cell(run["_corner1"], 8 * leaf_c) <= 12.0
+        assert_parent(parent, run, "refine.", "segmented=%s" % seg)
+        assert run["_n_plane0"] > 0 and run["_n_plane1"] > 0          # plane factors against both banks
+    assert _raw(runs[False]) == _raw(runs[True])
 
 
 def _chunks(scene, budget):
@@ -194,7 +266,7 @@ def _chunks(scene, budget):
 
 
 @pytest.mark.parametrize("tight", [True, False])
-def test_chunks(M, scene, synth, loop_history, tight):
+def test_chunks(M, scene, synth, parent, histories, tight):
     """Test 4: test 1's history with the budget below the ring points of any two banks (every bank a chunk of its own), and with one
     that the first round's banks share and the later rounds' do not."""
     n = [len(scene["frames"][s]["corner"]) + len(scene["frames"][s]["surf"]) for s in range(4)]
@@ -205,22 +277,60 @@ def test_chunks(M, scene, synth, loop_history, tight):
         assert all(c == 3 for c in full), chunks
     else:
         assert full[0] == 2 and full[-1] == 3, chunks               # a chunk of two banks, later every bank its own
-    b = M.Context(max_scans=4, max_map_points=MM)
-    try:
-        b.map_banks(4)
-        b.debug_bank_increment_budget(budget)
-        _load(b, scene)
-        got = _run_history(b, scene, synth, True)
-        assert got == loop_history["rounds"]                        # = the loop's, and (test 1) the unchunked segmented run's
-        far, rec = _associate_all(b, scene, synth)
-        assert far == loop_history["far"] and rec == loop_history["rec"]
-    finally:
-        b.close()
+    run = run_histories(M, scene, synth, True, budget=budget)
+    assert_parent(parent, run, "hist.", "budget %d" % budget)
+    assert _raw(run) == _raw(histories[False])                      # = the loop's, and (test 1) the unchunked segmented run's
+
+
+def test_oracle_history(M, O, scene, synth):
+    """HISTORY through O.LocalMap, one per bank: every bank's two clouds byte-equal to the oracle's after every round, for both call
+    forms; then the association of slot b against bank b: source indices equal O.associate_lines / O.associate_planes on the
+    oracle's maps, records within the 1e-9 that test_gpu_parity.py uses for them."""
+    from test_gpu_parity import _factor_arrays
+    lms, want = [O.LocalMap(window=50, leaf_corner=0.4, leaf_surf=0.2) for _ in range(4)], []
+    for rnd, banks in enumerate(HISTORY):
+        for b in banks:
+            fr = scene["frames"][b]
+            lms[b].increment(EMPTY if (rnd, b) == EMPTY_CORNER else fr["corner"], fr["surf"], _pose(synth, scene, rnd, b))
+        want.append([lms[b].get(k) for b in range(4) for k in (0, 1)])
+    T = _associate_poses(synth, scene)
+    facts = []
+    for b in range(3):
+        fr = scene["frames"][b]
+        lf, lsrc = O.associate_lines(fr["corner"], O.KdTree(lms[b].get(0)), T[b], 25.0)
+        pf, psrc = O.associate_planes(fr["surf"], O.KdTree(lms[b].get(1)), T[b], 25.0)
+        facts.append(_factor_arrays(lf, pf) + (lsrc, psrc))
+        assert len(lsrc) > 0 and len(psrc) > 100
+    for seg in FORMS:
+        how = dict(segmented=True) if seg else {}
+        c = M.Context(max_scans=4, max_map_points=MM)
+        try:
+            assert (c.cfg.leaf_corner, c.cfg.leaf_surf) == (np.float32(0.4), np.float32(0.2))
+            c.map_banks(4)
+            _load(c, scene)
+            for rnd in range(len(HISTORY)):
+                nc, ns = _history_round(c, scene, synth, rnd, how)
+                for i, b in enumerate(HISTORY[rnd]):
+                    assert (nc[i], ns[i]) == (len(want[rnd][2 * b]), len(want[rnd][2 * b + 1])), (seg, rnd, b)
+                for j, m in enumerate(_maps(c, range(4))):
+                    assert m == want[rnd][j].tobytes(), "segmented=%s round %d bank %d kind %d differs from the oracle" % (seg, rnd, j // 2, j % 2)
+            c.bind_banks(0, [0, 1, 2, 3])
+            c.associate(0, 4, T, 25.0)
+            for b in range(3):
+                gl, glsrc = c.factors_download(b, 0)
+                gp, gpsrc = c.factors_download(b, 1)
+                ol, op, lsrc, psrc = facts[b]
+                assert np.array_equal(glsrc, lsrc) and np.array_equal(gpsrc, psrc), (seg, b)
+                assert np.allclose(gl, ol, rtol=0, atol=1e-9) and np.allclose(gp, op, rtol=0, atol=1e-9), (seg, b)
+            assert len(c.factors_download(3, 0)[1]) == 0 and len(c.factors_download(3, 1)[1]) == 0
+        finally:
+            c.close()
 
 
 def test_refusals(M, scene, synth):
     """Test 5: a bank twice, a bank out of range, no banks, a slot without a stack in the middle of the list: the code, a message that
-    names the offender, every bank as it was; the next valid call equals the loop's."""
+    names the offender, every bank as it was; the next valid call equals the loop's.  The loop refuses the same slot at its place
+    in the list and leaves the banks before it incremented."""
     a, b = _pair(M, max_features=64)
     try:
         for c in (a, b):
@@ -258,33 +368,49 @@ def test_refusals(M, scene, synth):
             sb = b.bank_increment([2, 0, 1], [0, 3, 2], T, segmented=True)
             assert sa[0].tobytes() == sb[0].tobytes() and sa[1].tobytes() == sb[1].tobytes()
             assert _maps(a, range(3)) == _maps(b, range(3))
+        # the loop: bank 2 (before the bad slot) is incremented, banks 0 and 1 are as they were
+        held = _maps(a, range(3))
+        with pytest.raises(M.MmlError) as e:
+            a.bank_increment([2, 0, 1], [0, 1, 2], T3)
+        assert e.value.code == M.MML_ERR_STATE
+        b.bank_increment([2], [0], T3[:1], segmented=True)
+        after = _maps(a, range(3))
+        assert after[:4] == held[:4] and after[4:] != held[4:] and after == _maps(b, range(3))
     finally:
         a.close()
         b.close()
 
 
-def test_batch_lidar_odometry(M, synth):
-    """Test 6: 3 sequences x 8 scans through BatchLidarOdometry, increment="segmented" against increment="loop"."""
+def run_batch_odometry(M, synth, how):
+    """Test 6: 3 sequences x 8 scans through BatchLidarOdometry with increment=how: poses, key scans, final state."""
     from test_gpu_map_banks import _sequence_inputs
     odometry = importlib.import_module("multi-modal-loam_amd.odometry")
     W, rounds = 3, 8
     inputs = [_sequence_inputs(synth, w, rounds) for w in range(W)]
-    runs = []
-    for how in ("loop", "segmented"):
-        c = M.Context(max_scans=W, max_map_points=MM)
-        try:
-            bat = odometry.BatchLidarOdometry(c, W, lidar_mode=2, increment=how)
-            poses = []
-            for i in range(rounds):
-                for w in range(W):
-                    c.scan_upload(w, inputs[w][i][0], inputs[w][i][1])
-                c.extract(0, W)
-                c.undistort(0, W, np.stack([inputs[w][i][2].reshape(9) for w in range(W)]), np.stack([inputs[w][i][3] for w in range(W)]))
-                P, Q, grew = bat.estimate_lidar_pose(list(range(W)), np.stack([inputs[w][i][4] for w in range(W)]),
-                                                     np.stack([inputs[w][i][5] for w in range(W)]))
-                poses.append((P.tobytes(), Q.tobytes(), tuple(grew)))
-            runs.append((poses, bat.key_scans, [st.last_T.tobytes() for st in bat.seq], [(st.n_corner_local, st.n_surf_local) for st in bat.seq]))
-        finally:
-            c.close()
-    assert runs[0] == runs[1]
-    assert all(k >= 2 for k in runs[1][1])
+    P_all, Q_all, grew_all = [], [], []
+    c = M.Context(max_scans=W, max_map_points=MM)
+    try:
+        bat = odometry.BatchLidarOdometry(c, W, lidar_mode=2, increment=how)
+        for i in range(rounds):
+            for w in range(W):
+                c.scan_upload(w, inputs[w][i][0], inputs[w][i][1])
+            c.extract(0, W)
+            c.undistort(0, W, np.stack([inputs[w][i][2].reshape(9) for w in range(W)]), np.stack([inputs[w][i][3] for w in range(W)]))
+            P, Q, grew = bat.estimate_lidar_pose(list(range(W)), np.stack([inputs[w][i][4] for w in range(W)]),
+                                                 np.stack([inputs[w][i][5] for w in range(W)]))
+            P_all.append(np.asarray(P, np.float64))
+            Q_all.append(np.asarray(Q, np.float64))
+            grew_all.append(np.asarray(grew, np.int32))
+        return {"odo.P": np.stack(P_all), "odo.Q": np.stack(Q_all), "odo.grew": np.stack(grew_all),   # grew: the key scans, per round
+                "odo.key_scans": np.asarray(bat.key_scans, np.int32), "odo.last_T": np.stack([np.asarray(st.last_T, np.float64) for st in bat.seq]),
+                "odo.local_n": np.asarray([(st.n_corner_local, st.n_surf_local) for st in bat.seq], np.int32)}
+    finally:
+        c.close()
+
+
+def test_batch_lidar_odometry(M, synth, parent):
+    runs = {how: run_batch_odometry(M, synth, how) for how in ("loop", "segmented")}
+    for how in runs:
+        assert_parent(parent, runs[how], "odo.", "increment=%s" % how)
+    assert _raw(runs["loop"]) == _raw(runs["segmented"])
+    assert all(k >= 2 for k in runs["segmented"]["odo.key_scans"])

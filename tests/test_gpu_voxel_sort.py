@@ -2,9 +2,10 @@
 through the public calls that reach them, at the smallest shapes at which a 256-thread kernel can go wrong, bit for bit against the
 oracle's filter / search:
   mml_cloud_crop_voxel                 k_cv_bbox, 64-bit keys, limit CV_DROPPED, the four-field run sum, a side call's own scratch
-  features_upload + map_increment_local  k_bbox, 32-bit keys, the three-field run sum, the context's sort_tmp; the rebuilt grid (map_assoc.hip's
-                                         k_bbox and sort) is then read through knn5
-  map_set_local + knn5                  map_assoc.hip's grid build alone
+  features_upload + map_increment_local  the increment chain with one map (k_inc_concat_bbox, kind << 32 | voxel keys, the three-field run
+                                         sum, the context's sort_tmp); the rebuilt grids (map_assoc.hip's mml_build_grids, two segments) are
+                                         then read through knn5
+  map_set_local + knn5                  map_assoc.hip's grid build alone (k_bbox, one cloud, 32-bit keys)
   mml_time_offset_search                k_tofs_box, the box decoded on the host, the sort scratch carved out of the call's block
 The clouds come from calibrate_checks' generators.  Every case takes well under a second."""
 import numpy as np

@@ -28,23 +28,57 @@ from map_banks_probe import REPS, ROUNDS, TRAJ, make_inputs  # noqa: E402
 
 SYNCS = [
     "host synchronisations of the increment per round, from the code (after the entry drain; g = the banks that grow this round):",
-    "  loop       per bank: 1 (the two stack sizes) + per kind with points: 1 (the filter's output size) + 1 (the filtered cloud's box)",
-    "             + 1 per cell-refinement round (1 to 5)  =  at least 7 g   (csrc/map_upkeep.hip mml_map_upkeep_increment,",
-    "             csrc/map_assoc.hip build_grid_into)",
+    "  loop       per bank, the chain below with that one bank: 1 (the two stack sizes) + 1 (the two filtered sizes and boxes) + 1 per",
+    "             cell-refinement round of the bank's slower kind (1 to 5)  =  (2 + R) g.  (On a build from before the chains were merged:",
+    "             a chain of its own, per kind a size, a box and the rounds, at least 7 g.)",
     "  segmented  1 (all stack sizes) + per chunk of banks: 1 (all filtered sizes and boxes) + 1 per cell-refinement round of the",
     "             chunk's slowest (bank, kind)  =  2 + R whatever g is, while the banks' rings fit one chunk (2^22 points)",
-    "             (csrc/map_upkeep.hip mml_map_upkeep_increment_segmented, csrc/map_assoc.hip mml_build_grids_segmented)",
+    "             (csrc/map_upkeep.hip mml_map_upkeep_increment_segmented, csrc/map_assoc.hip mml_build_grids)",
 ]
 
 
-def worker(ns, mode, dump):
+def grid_times(M, synth, sizes, reps=5):
+    """Host clock, ending in a synchronise, of map_set_local(1, cloud) at each size and of one map_global_increment: every repetition's
+    milliseconds.  The clouds: uniform points in a 40 x 40 x 6 m box (seeded); the increment: one 4 000 + 8 000 point key scan appended."""
+    rng = np.random.default_rng(11)
+    out = {}
+    ctx = M.Context(max_scans=1, max_map_points=max(1 << 19, max(sizes)))
+    for m in sizes:
+        cloud = (rng.random((m, 3)) * np.array([40.0, 40.0, 6.0])).astype(np.float32)
+        t = []
+        for rep in range(1 + reps):
+            ctx.synchronize()
+            t0 = time.perf_counter()
+            ctx.map_set_local(1, cloud)
+            ctx.synchronize()
+            if rep:
+                t.append(1e3 * (time.perf_counter() - t0))
+        out["map_set_local_%d_ms" % m] = t
+    t = []
+    for rep in range(1 + reps):
+        ctx.map_global_reset()
+        for kind, m in ((0, 4000), (1, 8000)):
+            ctx.features_upload(0, kind, (rng.random((m, 3)) * np.array([40.0, 40.0, 6.0])).astype(np.float32))
+        ctx.map_global_append(0, np.eye(4))
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        ctx.map_global_increment(np.eye(4))
+        ctx.synchronize()
+        if rep:
+            t.append(1e3 * (time.perf_counter() - t0))
+    out["map_global_increment_ms"] = t
+    ctx.close()
+    return out
+
+
+def worker(ns, mode, dump, how=None, grid_sizes=()):
     M = importlib.import_module("multi-modal-loam_amd")
     synth = importlib.import_module("multi-modal-loam_amd.synth")
     odometry = importlib.import_module("multi-modal-loam_amd.odometry")
     nmax = max(ns)
     scans, pred = make_inputs(synth, nmax)
     ctx = M.Context(max_scans=nmax, max_map_points=1 << 19)
-    how = "loop" if mode == "prev" else "segmented"
+    how = how or ("loop" if mode == "prev" else "segmented")
 
     def replay(n):
         poses = np.zeros((n, ROUNDS, 7))
@@ -71,9 +105,11 @@ def worker(ns, mode, dump):
             if rep:
                 t.append(time.perf_counter() - t0)
         t = sorted(t)
-        out[str(n)] = dict(s=t[len(t) // 2], lo=t[0], hi=t[-1], scans=n * ROUNDS, keys=[int(k) for k in res[1]])
+        out[str(n)] = dict(s=t[len(t) // 2], lo=t[0], hi=t[-1], t=t, scans=n * ROUNDS, keys=[int(k) for k in res[1]])
         arrays["poses_%d" % n] = res[0]
     ctx.close()
+    if grid_sizes:  # (--grid: the one-map grid build and the cube store's increment, for an A/B of two builds)
+        out["grid"] = grid_times(M, synth, grid_sizes)
     np.savez(dump, **arrays)
     print("RESULT " + json.dumps(out), flush=True)
 
@@ -96,11 +132,13 @@ def main():
     ap.add_argument("--worker", default=None)
     ap.add_argument("--dump", default=None)
     ap.add_argument("--limit", type=int, default=300)
+    ap.add_argument("--how", default=None, choices=["loop", "segmented"], help="--worker: the increment to run whatever the mode")
+    ap.add_argument("--grid", default="", help="--worker: also time map_set_local at these sizes (comma-separated) and one map_global_increment")
     ap.add_argument("ns", nargs="*", type=int)
     a = ap.parse_args()
     ns = a.ns or [1, 8, 64]
     if a.worker:
-        return worker(ns, a.worker, a.dump)
+        return worker(ns, a.worker, a.dump, a.how, [int(m) for m in a.grid.split(",") if m])
     if not os.path.exists(a.prev):
         raise SystemExit("no parent build at %s (see the docstring)" % a.prev)
     tmp = os.path.dirname(os.path.abspath(a.out))
