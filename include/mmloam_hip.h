@@ -707,9 +707,41 @@ int mml_map_set_global(mml_ctx* ctx, int kind, const float* xyz, const int* cube
  * demand and kept until mml_destroy.  A call whose banks hold more than MML_BANK_INCREMENT_BUDGET ring points works them in
  * chunks -- greedy, in call order, a bank over the budget a chunk of its own -- and makes one synchronisation for the stack
  * sizes and 1 + R for every chunk; the default budget keeps every position in an int and the scratch at 192 MiB.
- * mml_debug_bank_increment_budget (a test hook): sets that budget, in points, for the context's later calls. */
+ * mml_debug_bank_increment_budget (a test hook): sets that budget, in points, for the context's later calls.
+ * mml_map_bank_global_increment_segmented / mml_map_bank_global_append_segmented: mml_map_bank_global_increment / _append --
+ * arguments, argument checks, drained context -- with the n banks' work in ONE chain of launches.  A segment is (bank of the
+ * call, kind), 2 n of them behind one device-resident table: one launch tags all rows (a stored point's cube with the MapMove
+ * shifts applied as it is read, a pending point's from the moved centre) and fills the per-segment cube histograms, one
+ * classifies, ONE scan per flag array runs over all segments, one launch scatters, ONE stable 64-bit sort keyed
+ * segment << 53 | cube << 40 | voxel index (over 53 + the bits of the segment count) filters every cube that grew beyond 300
+ * points, and the 2 n match copies are built by one sort per cell-refinement round.  Every bank ends bit-identical to what
+ * the loop call leaves on the same history -- live store with its tags and the order inside every cube, centre, emptied
+ * pending clouds, the match copy (the store at the START of the increment with the centre before MapMove) with its grid and
+ * cube counts, the sizes returned.  TWO DIFFERENCES:
+ * (1) ALL OR NOTHING.  Every refusal leaves EVERY bank of the call exactly as it was -- live store, tags, centre, pending
+ * clouds, match copy -- and n_corner / n_surf unwritten: a bank twice or out of range, n < 1, a context without banks, an
+ * append of a slot without a stack (MML_ERR_STATE) or beyond 16 x max_features pending points (MML_ERR_CAPACITY), a store
+ * that would exceed max_map_points (MML_ERR_CAPACITY; the message names the bank), a pose that needs more layer shifts than
+ * the 64 the one-store call lists (MML_ERR_INVALID).  (The loop leaves banks 0 .. i-1 incremented, and a capacity refusal
+ * leaves bank i with its tags shifted and its centre moved.)  The refusals are decided in this order: arguments; poses, on a
+ * host copy of every centre; then the one read-back of every segment's kept / selected totals, before which only scratch is
+ * written.  The live arrays are read-only until every chunk (below) has passed; the match copies are built after that from
+ * the untouched arrays, then the buffer pairs are swapped and the host state is written.
+ * (2) Host synchronisations after the entry drain, whatever n is: 1 for the kept / selected totals of all segments (the
+ * capacity decision), 1 for the filtered sizes (none when no cube is filtered), at most 1 when a match copy has to grow, 1
+ * for the bounding boxes of all match copies, R for the cell-refinement rounds of the slowest match copy: 3 + R, 4 + R on
+ * growth.  The append reads all stack sizes in ONE copy and transforms all 2 n stacks in ONE launch.
+ * Scratch: an allocation group of its own, grown on demand and kept until mml_destroy -- 60 bytes per point (store + pending,
+ * both kinds) the call works on at a time plus 155 232 bytes (8 x 4851 ints) per segment, and the sorts' temporary storage.
+ * A call whose banks hold more than MML_BANK_GLOBAL_INCREMENT_BUDGET points, or more than MML_BANK_GLOBAL_CHUNK_BANKS banks,
+ * works them in chunks -- greedy, in call order, a bank over the budget a chunk of its own -- with the synchronisations above
+ * per chunk; the store chains of ALL chunks run, and pass their capacity decisions, before the first match copy is built.
+ * The defaults bound the scratch by 240 MiB + 38 MiB and keep every position in an int.
+ * mml_debug_bank_global_increment_budget (a test hook): sets that budget, in points, for the context's later calls. */
 #define MML_MAP_BANKS_MAX 1024
 #define MML_BANK_INCREMENT_BUDGET (1 << 22)
+#define MML_BANK_GLOBAL_INCREMENT_BUDGET (1 << 22)
+#define MML_BANK_GLOBAL_CHUNK_BANKS 128
 int mml_map_banks_create(mml_ctx* ctx, int n_banks);
 int mml_map_banks_destroy(mml_ctx* ctx);
 int mml_map_bank_set_local(mml_ctx* ctx, int bank, int kind, const float* xyz, int m);
@@ -723,6 +755,9 @@ int mml_debug_bank_increment_budget(mml_ctx* ctx, long points);
 int mml_map_bank_set_global(mml_ctx* ctx, int bank, int kind, const float* xyz, const int* cube, int m, const int* cen);
 int mml_map_bank_global_append(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl);
 int mml_map_bank_global_increment(mml_ctx* ctx, int n, const int* banks, const double* T_wl, int* n_corner, int* n_surf);
+int mml_map_bank_global_increment_segmented(mml_ctx* ctx, int n, const int* banks, const double* T_wl, int* n_corner, int* n_surf);
+int mml_map_bank_global_append_segmented(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl);
+int mml_debug_bank_global_increment_budget(mml_ctx* ctx, long points);
 int mml_map_bank_global_download(mml_ctx* ctx, int bank, int kind, float* xyz, int* cube, int capacity, int* n, int* cen);
 int mml_map_bank_global_reset(mml_ctx* ctx, int bank);
 

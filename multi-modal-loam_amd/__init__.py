@@ -1275,26 +1275,35 @@ class Context:
         cen_p = None if cen is None else _p(np.ascontiguousarray(cen, dtype=np.int32))
         self._ck(lib().mml_map_bank_set_global(self._h, C.c_int(bank), C.c_int(kind), _p(xyz), _p(cube), C.c_int(len(xyz)), cen_p))
 
-    def bank_global_append(self, banks, slots, T_wl):
+    def bank_global_append(self, banks, slots, T_wl, segmented=False):
         """map_global_append for len(banks) distinct banks in one call: the stacks of slot slots[i] at T_wl[i] (4 x 4) go to
-        the pending clouds of bank banks[i]."""
+        the pending clouds of bank banks[i].  segmented=True: mml_map_bank_global_append_segmented -- one read-back of all
+        stack sizes, one launch for all banks."""
         b = np.ascontiguousarray(banks, dtype=np.int32).reshape(-1)
         s = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
         T = _f64(T_wl).reshape(-1, 16)
         if not (len(b) == len(s) == len(T)):
             raise ValueError("one slot and one pose per bank")
-        self._ck(lib().mml_map_bank_global_append(self._h, C.c_int(len(b)), _p(b), _p(s), _p(T)))
+        call = lib().mml_map_bank_global_append_segmented if segmented else lib().mml_map_bank_global_append
+        self._ck(call(self._h, C.c_int(len(b)), _p(b), _p(s), _p(T)))
 
-    def bank_global_increment(self, banks, T_wl):
+    def bank_global_increment(self, banks, T_wl, segmented=False):
         """map_global_increment for len(banks) distinct banks in one call, bank banks[i] at T_wl[i].  Returns the live (corner,
-        surf) store sizes, one pair of arrays entry per bank."""
+        surf) store sizes, one pair of arrays entry per bank.  segmented=True: mml_map_bank_global_increment_segmented -- the
+        same banks, bit for bit, from one chain of launches with 3 + R host synchronisations whatever len(banks) is; every
+        refusal leaves every bank of the call as it was."""
         b = np.ascontiguousarray(banks, dtype=np.int32).reshape(-1)
         T = _f64(T_wl).reshape(-1, 16)
         if len(b) != len(T):
             raise ValueError("one pose per bank")
         nc, ns = np.zeros(max(len(b), 1), np.int32), np.zeros(max(len(b), 1), np.int32)
-        self._ck(lib().mml_map_bank_global_increment(self._h, C.c_int(len(b)), _p(b), _p(T), _p(nc), _p(ns)))
+        call = lib().mml_map_bank_global_increment_segmented if segmented else lib().mml_map_bank_global_increment
+        self._ck(call(self._h, C.c_int(len(b)), _p(b), _p(T), _p(nc), _p(ns)))
         return nc[:len(b)], ns[:len(b)]
+
+    def bank_global_increment_budget(self, points):
+        """mml_debug_bank_global_increment_budget (a test hook): the points a segmented bank_global_increment works on at a time."""
+        self._ck(lib().mml_debug_bank_global_increment_budget(self._h, C.c_long(int(points))))
 
     def bank_global_download(self, bank, kind):
         n = C.c_int(0)

@@ -5,7 +5,8 @@
 //   cube maps --, through the per-slot bank array (map_assoc.hip, the BANKED forms); this file keeps the three device arrays
 //   equal to the host's state.
 //   A bank has its own global cube map (MmlCubeMatch / MmlCubeLive, mml_internal.h): the mml_map_bank_global_* calls run the code
-//   of the own-map calls on it (MmlCubeRef), n banks in a loop.  The context's OWN cube map and a bound slot exclude each other.
+//   of the own-map calls on it (MmlCubeRef), n banks in a loop; the *_segmented forms work the n banks in one chain of launches
+//   (map_global_seg.hip).  The context's OWN cube map and a bound slot exclude each other.
 #include <string.h>
 
 #include <algorithm>
@@ -305,6 +306,39 @@ int mml_map_bank_global_increment(mml_ctx* ctx, int n, const int* banks, const d
         if (n_surf) n_surf[i] = m[1];
         if (rc != MML_OK) return rc;
     }
+    return MML_OK;
+}
+
+// the segmented forms (map_global_seg.hip): the same argument checks and drain, then ONE chain for all n banks
+int mml_map_bank_global_append_segmented(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl) {
+    if (!ctx) return MML_ERR_INVALID;
+    MML_REQUIRE(n >= 1 && banks && slots && T_wl, MML_ERR_INVALID, "bad arguments");
+    int rc = check_distinct_banks(ctx, n, banks, slots, "mml_map_bank_global_append_segmented");
+    if (rc != MML_OK) return rc;
+    rc = enter(ctx);
+    if (rc != MML_OK) return rc;
+    if (!ctx->uploads.empty()) return mml_refuse(ctx, MML_ERR_STATE, "uploads in flight after a drained context");
+    std::vector<MmlCubeRef> cubes;
+    for (int i = 0; i < n; ++i) cubes.push_back(mml_cube_bank(ctx, banks[i]));
+    return mml_cube_store_append_segmented(ctx, n, cubes.data(), banks, slots, T_wl);
+}
+
+int mml_map_bank_global_increment_segmented(mml_ctx* ctx, int n, const int* banks, const double* T_wl, int* n_corner, int* n_surf) {
+    if (!ctx) return MML_ERR_INVALID;
+    MML_REQUIRE(n >= 1 && banks && T_wl, MML_ERR_INVALID, "bad arguments");
+    int rc = check_distinct_banks(ctx, n, banks, nullptr, "mml_map_bank_global_increment_segmented");
+    if (rc != MML_OK) return rc;
+    rc = enter(ctx);
+    if (rc != MML_OK) return rc;
+    std::vector<MmlCubeRef> cubes;
+    for (int i = 0; i < n; ++i) cubes.push_back(mml_cube_bank(ctx, banks[i]));
+    return mml_cube_store_increment_segmented(ctx, n, cubes.data(), banks, T_wl, n_corner, n_surf);
+}
+
+int mml_debug_bank_global_increment_budget(mml_ctx* ctx, long points) {
+    if (!ctx) return MML_ERR_INVALID;
+    if (points < 1 || points >= (1l << 31)) return mml_refuse(ctx, MML_ERR_INVALID, "the chunk budget must be in [1, 2^31) points");
+    ctx->bank_cube.budget = points;
     return MML_OK;
 }
 

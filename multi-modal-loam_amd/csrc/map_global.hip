@@ -159,9 +159,11 @@ __global__ void k_cube_centroid(const float4* pts, const unsigned long long* key
     out_tag[dst] = (uint16_t)(key >> 40);
 }
 
+}  // namespace
+
 // The store's own memory (per store: 72 bytes x max_map_points + 2 x 16 x max_features x 16 bytes) and the scratch every store of
 // the context works in; each allocated by the first call that needs it.
-int ensure_store(mml_ctx* ctx, const MmlCubeRef& cube) {
+int mml_cube_store_ensure(mml_ctx* ctx, const MmlCubeRef& cube) {
     MmlCubeLive& L = *cube.live;
     const size_t MM = (size_t)ctx->MM;
     const size_t gp = 16 * (size_t)ctx->MF;
@@ -182,8 +184,6 @@ int ensure_store(mml_ctx* ctx, const MmlCubeRef& cube) {
               mml_part(L.gs_pts[1], MM), mml_part(L.gs_tag[1], MM), mml_part(L.gs_pts2[1], MM), mml_part(L.gs_tag2[1], MM), mml_part(L.gp_pts[1], gp)});
 }
 
-}  // namespace
-
 int mml_cube_store_reset(mml_ctx* ctx, const MmlCubeRef& cube) {
     MmlCubeLive& L = *cube.live;
     L.gs_n[0] = L.gs_n[1] = 0;
@@ -197,7 +197,7 @@ int mml_cube_store_reset(mml_ctx* ctx, const MmlCubeRef& cube) {
 int mml_cube_store_append(mml_ctx* ctx, const MmlCubeRef& cube, int slot, const double* T_wl) {
     MmlCubeLive& L = *cube.live;
     hipStream_t s = MML_STREAM(ctx);
-    int rc = ensure_store(ctx, cube);
+    int rc = mml_cube_store_ensure(ctx, cube);
     if (rc != MML_OK) return rc;
     int n_feat[2];
     MML_HIP(hipMemcpyAsync(&n_feat[0], ctx->ft_n + 0 * ctx->B + slot, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -221,7 +221,7 @@ int mml_cube_store_append(mml_ctx* ctx, const MmlCubeRef& cube, int slot, const 
 int mml_cube_store_increment(mml_ctx* ctx, const MmlCubeRef& cube, const double* T_wl, int* n_out) {
     MmlCubeLive& L = *cube.live;
     hipStream_t s = MML_STREAM(ctx);
-    int rc = ensure_store(ctx, cube);
+    int rc = mml_cube_store_ensure(ctx, cube);
     if (rc != MML_OK) return rc;
     const size_t U = ((size_t)ctx->MM + (size_t)L.gp_cap + 3) & ~size_t(3);
     int* cnt = ctx->gs_work;

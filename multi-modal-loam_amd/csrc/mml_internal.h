@@ -365,6 +365,21 @@ struct mml_ctx {
         MmlStaging<char> tab;                // a chunk's tables and read-backs: device block and pinned twin
         long budget = MML_BANK_INCREMENT_BUDGET;  // ring points per chunk (mml_debug_bank_increment_budget)
     } bank_inc;
+    // scratch of the segmented cube-store increment (map_global_seg.hip), a group of its own: sized by the points (store + pending,
+    // both kinds) and the segments of the largest chunk of stores a call has worked on -- 60 bytes per point, 8 x 4851 ints per segment
+    struct BankCube {
+        int* work = nullptr;                 // seg_cap x (cnt | changed | six box keys per cube)
+        int* flags = nullptr;                // 4 x (cap + 1): keep, keep_pos, sel, sel_pos (run heads and positions after the scatter)
+        unsigned long long* keys = nullptr;  // 2 x cap: sort keys in / out
+        unsigned* vals = nullptr;            // 2 x cap
+        float4* sel_pts = nullptr;           // cap: the selected rows
+        uint16_t* tags = nullptr;            // 2 x cap: every row's cube | the selected rows' cubes
+        size_t cap = 0;                      // points
+        int seg_cap = 0;                     // segments
+        MmlGroup mem;                        // owns the six
+        MmlStaging<char> tab;                // a chunk's tables and read-backs: device block and pinned twin
+        long budget = MML_BANK_GLOBAL_INCREMENT_BUDGET;  // points per chunk (mml_debug_bank_global_increment_budget)
+    } bank_cube;
     float4* map_tmp = nullptr;
     unsigned* map_keys = nullptr;
     unsigned* map_keys2 = nullptr;
@@ -412,6 +427,8 @@ struct mml_ctx {
         banks.release();
         bank_inc.mem.release();
         bank_inc.tab.release();
+        bank_cube.mem.release();
+        bank_cube.tab.release();
         clive.mem.release();
         cube_scratch.release();
         wire_stage.release();
@@ -575,6 +592,27 @@ int mml_cube_store_append(mml_ctx* ctx, const MmlCubeRef& cube, int slot, const 
 int mml_cube_store_increment(mml_ctx* ctx, const MmlCubeRef& cube, const double* T_wl, int* n_out);
 int mml_cube_store_download(mml_ctx* ctx, const MmlCubeRef& cube, int kind, float* xyz, int* cube_idx, int capacity, int* n, int* cen);
 int mml_cube_store_reset(mml_ctx* ctx, const MmlCubeRef& cube);
+int mml_cube_store_ensure(mml_ctx* ctx, const MmlCubeRef& cube);  // the store's memory and the one-store scratch, on first use
+// map_global_seg.hip: n DISTINCT stores in one chain of launches; the caller has checked the arguments and drained the context.
+// names[i]: what a message calls store i (its bank).  Bit-identical to n calls of the one-store forms above; every refusal leaves
+// all n stores -- live arrays, tags, centres, pending clouds, match copies -- as they were.
+int mml_cube_store_increment_segmented(mml_ctx* ctx, int n, const MmlCubeRef* cubes, const int* names, const double* T_wl, int* n_corner,
+                                       int* n_surf);
+int mml_cube_store_append_segmented(mml_ctx* ctx, int n, const MmlCubeRef* cubes, const int* names, const int* slots, const double* T_wl);
+// The chunks of such a call: chunk c = stores [cut[c], cut[c + 1]) -- greedy, in call order, at most `budget` points (pts[i]: store +
+// pending, both kinds) and at most max_stores stores per chunk, a store over the budget a chunk of its own.
+std::vector<int> mml_cube_chunks(int n, const long long* pts, long long budget, int max_stores);
+// The sort key of the segmented filter: segment << 53 | cube << 40 | PCL voxel index.  4851 cubes take 13 bits, the index 40
+// (the one-store chain keys cube << 40 | index): up to 2048 segments in 64 bits.
+__host__ __device__ inline unsigned long long mml_cube_key(unsigned seg, unsigned cube, unsigned long long vox) {
+    return ((unsigned long long)seg << 53) | ((unsigned long long)cube << 40) | vox;
+}
+__host__ __device__ inline unsigned mml_cube_key_cube(unsigned long long key) { return (unsigned)(key >> 40) & 0x1fffu; }
+inline int mml_cube_key_bits(int nseg) {  // the sort's end_bit
+    int b = 1;
+    while ((1 << b) < nseg) ++b;
+    return 53 + b;
+}
 int mml_launch_knn5(mml_ctx* ctx, int kind, const float* d_q, int nq, float max_d2, int* d_idx, float* d_d2);
 // with_stats = false (mml_step, which reads none of them): the per-slot statistics (counts, normal Gram matrix) are left stale and
 // computed by mml_ensure_assoc_stats when a consumer asks (mml_linearize*, the next mml_associate with statistics)

@@ -101,11 +101,16 @@ class Context {
     void bank_set_global(int bank, int kind, const float* xyz, const int* cube, int m, const int* cen = nullptr) {
         check(ctx_, mml_map_bank_set_global(ctx_, bank, kind, xyz, cube, m, cen), "bank_set_global");
     }
-    void bank_global_append(int n, const int* banks, const int* slots, const double* T_wl) {
-        check(ctx_, mml_map_bank_global_append(ctx_, n, banks, slots, T_wl), "bank_global_append");
+    // segmented = true: mml_map_bank_global_append_segmented / _increment_segmented -- the same stores and match copies bit for
+    // bit from one chain of launches (3 + R host synchronisations whatever n is); every refusal leaves every bank as it was.
+    void bank_global_append(int n, const int* banks, const int* slots, const double* T_wl, bool segmented = false) {
+        check(ctx_, (segmented ? mml_map_bank_global_append_segmented : mml_map_bank_global_append)(ctx_, n, banks, slots, T_wl),
+              "bank_global_append");
     }
-    void bank_global_increment(int n, const int* banks, const double* T_wl, int* n_corner = nullptr, int* n_surf = nullptr) {
-        check(ctx_, mml_map_bank_global_increment(ctx_, n, banks, T_wl, n_corner, n_surf), "bank_global_increment");
+    void bank_global_increment(int n, const int* banks, const double* T_wl, int* n_corner = nullptr, int* n_surf = nullptr,
+                               bool segmented = false) {
+        check(ctx_, (segmented ? mml_map_bank_global_increment_segmented : mml_map_bank_global_increment)(ctx_, n, banks, T_wl, n_corner, n_surf),
+              "bank_global_increment");
     }
 
    private:

@@ -192,17 +192,23 @@ class BatchLidarOdometry:
     context's OWN global cube map must stay unset either way: a bound slot and it exclude each other.
     increment: "loop" (the default) -- bank_increment works the growing banks through one after the other; "segmented" -- it
     works them in one chain of launches (Context.bank_increment(..., segmented=True)): the same maps bit for bit, 2 + R host
-    synchronisations per round whatever n is."""
+    synchronisations per round whatever n is.
+    global_increment: the same choice for the two cube calls of a round (global_map=True): "loop" (the default) or "segmented"
+    (Context.bank_global_append / bank_global_increment with segmented=True): the same stores and match copies bit for bit,
+    3 + R host synchronisations per round whatever n is."""
 
     def __init__(self, ctx, n, exTlb=None, lidar_mode=2, max_outer=5, inner_iters=10, global_map=False, map_skip_frame=2,
-                 increment="loop"):
+                 increment="loop", global_increment="loop"):
         if n < 1:
             raise ValueError("n must be at least 1")
         if map_skip_frame < 1:
             raise ValueError("map_skip_frame must be at least 1")
         if increment not in ("loop", "segmented"):
             raise ValueError('increment must be "loop" or "segmented"')
+        if global_increment not in ("loop", "segmented"):
+            raise ValueError('global_increment must be "loop" or "segmented"')
         self.increment = increment
+        self.global_increment = global_increment
         self.global_map, self.map_skip_frame = global_map, map_skip_frame
         self.ctx, self.n = ctx, n
         self.exTlb = np.eye(4) if exTlb is None else np.asarray(exTlb, dtype=np.float64)
@@ -250,12 +256,13 @@ class BatchLidarOdometry:
         for w in live:
             T[w], grew[w] = _hand_back(self.seq[w], self.lidar_mode, self.exRbl, self.exPbl, T[w], P[w], Q[w], degenerate[w], corner_cnt[w])
         if self.global_map:
+            ghow = {"segmented": True} if self.global_increment == "segmented" else {}     # ("loop": call for call as before)
             taken = [w for w in live if _map_thread_takes(degenerate[w], ctx.features_count(slots[w], 0))]
             if taken:
-                ctx.bank_global_append(taken, [slots[w] for w in taken], np.stack([T[w] for w in taken]))
+                ctx.bank_global_append(taken, [slots[w] for w in taken], np.stack([T[w] for w in taken]), **ghow)
             due = [w for w in taken if _map_thread_appended(self.seq[w], self.map_skip_frame)]
             if due:
-                nc, ns = ctx.bank_global_increment(due, np.stack([T[w] for w in due]))
+                nc, ns = ctx.bank_global_increment(due, np.stack([T[w] for w in due]), **ghow)
                 for i, w in enumerate(due):
                     _map_thread_incremented(self.seq[w], (nc[i], ns[i]))
         growing = [w for w in live if grew[w]]
