@@ -153,6 +153,49 @@ int mml_cloud_download_registered_batch(mml_ctx* ctx, int first_slot, int count,
 int mml_cloud_download_registered(mml_ctx* ctx, int slot, const double* T_wl /* 16 */, uint8_t* out, int capacity_points,
                                   int* n_points);
 
+/* The world map: the registered clouds above voxel-merged ON the device, one map per sequence, n_maps (1 .. 1024 =
+ * MML_MAP_BANKS_MAX) maps per context numbered like the banks -- what a replay keeps of /velo_full_cloud_mapped where the
+ * reference leaves the accumulation to a recorder.  One hash table of voxels holds all maps; the work of an add does not depend
+ * on how much the maps hold.  The arithmetic is defined once, in csrc/world_map_key.h (host and device):
+ *   world point   the slot's fused point through the function mml_cloud_download_registered_batch uses (double, Eigen's order,
+ *                 no fused multiply-add, rounded once to float); intensity carried over;
+ *   voxel index   per axis i = (int)floor((double)(x * inv)), inv = 1.0f / leaf and the product in float.  A point is SKIPPED
+ *                 and counted when its label is not in label_mask (n_masked), else when a coordinate or the intensity is not
+ *                 finite (n_nonfinite), else when an index is outside [-2^17, 2^17) (n_out_of_range; the one voxel
+ *                 (2^17-1, 2^17-1, 2^17-1) of map 1023, whose key would be the table's empty marker, counts as outside too);
+ *   voxel         float sums of x, y, z, intensity and a count.  A voxel's points are added one after the other in float,
+ *                 starting from the stored sum, in call order, then slot order inside the call, then fused point order inside
+ *                 the slot; the centroid is sum / (float)count per field.
+ * mml_world_map_create: once per context (MML_ERR_STATE if present); capacity_voxels (1 .. 2^29) is the total over all maps,
+ * 28 bytes per table position at 2 .. 4 positions per voxel.  _destroy frees it (mml_destroy does too); _reset empties one map
+ * (the others keep every bit of theirs) or, map = -1, all.  _size: the voxels of one map, or of all (map = -1).
+ * mml_world_map_add: slot first_slot + i into map map_of_slot[i] (-1: the slot is skipped) at pose i of T_wl (row-major 4x4,
+ * the upper three rows applied as given).  label_mask bit l: the points labelled l take part (0 none, 1 corner, 2 surf; 7 = all).
+ * The slots are read as they stand and never modified; slots filled by mml_extract and by mml_cloud_upload both work.  `info`
+ * (may be NULL) receives the call's counts: n_points = n_kept + n_nonfinite + n_out_of_range + n_masked over the slots that
+ * take part, the voxels the call created and the total of all maps after it.  One chain of launches and ONE host synchronisation
+ * whatever `count` is.  BATCHING GUARANTEE: one call over `count` slots leaves exactly the bytes that `count` calls of one slot
+ * each, in slot order, leave -- every map's download and the sums of the info counts.  Refused before anything is written to
+ * the table: MML_ERR_STATE without a map; MML_ERR_INVALID for a slot range outside the context, count outside 1 .. 65535, a map
+ * number outside [-1, n_maps), NULL map_of_slot / T_wl, label_mask & 7 == 0; MML_ERR_HIP when the scratch (52 bytes per point
+ * of count x the context's points per slot, grow-only) cannot grow; MML_ERR_CAPACITY, naming the figures, when the voxels held
+ * plus the call's new ones exceed capacity_voxels -- the table is then bit for bit what it was and a smaller call still works.
+ * mml_world_map_download: the voxels of one map in ascending key order (z index, then y, then x) as centroids x, y, z,
+ * intensity (4 floats each) and, out_count != NULL, their point counts.  out_xyzi == NULL: only *n_voxels (the sizing call);
+ * MML_ERR_CAPACITY when `capacity` (voxels) is below it.  Which table position a voxel occupies may differ from run to run;
+ * nothing a call returns depends on it. */
+typedef struct {
+    long n_points, n_kept, n_nonfinite, n_out_of_range, n_masked, n_new_voxels, n_voxels_total;
+} mml_world_map_info;
+int mml_world_map_create(mml_ctx* ctx, int n_maps /* 1..1024 */, float leaf, long capacity_voxels);
+int mml_world_map_destroy(mml_ctx* ctx);
+int mml_world_map_reset(mml_ctx* ctx, int map /* -1: all */);
+int mml_world_map_add(mml_ctx* ctx, int first_slot, int count, const int* map_of_slot /* count; -1 skips the slot */,
+                      const double* T_wl /* count x 16 */, unsigned label_mask /* bit l: label l takes part; 7 = all */,
+                      mml_world_map_info* info /* may be NULL */);
+int mml_world_map_size(mml_ctx* ctx, int map /* -1: all */, long* n_voxels);
+int mml_world_map_download(mml_ctx* ctx, int map, float* out_xyzi, int* out_count /* may be NULL */, long capacity, long* n_voxels);
+
 /* The feature node's own output: the six PointXYZINormal clouds of one union_cloud message (union-cloud/msg/union_cloud.msg:4-9)
  * for `count` extracted slots.  Cloud index k, in the message's order: 0 velo_corner, 1 velo_surface, 2 velo_combine,
  * 3 livox_corner, 4 livox_surface, 5 livox_combine.  Records are the 48-byte records of mml_scan_download_pointxyzinormal

@@ -200,6 +200,23 @@ class Profile(C.Structure):
                 ("launches", C.c_long * MAX_STAGES)]
 
 
+class WorldMapInfo(C.Structure):
+    """mml_world_map_info: what one mml_world_map_add call did."""
+    _fields_ = [(k, C.c_long) for k in ("n_points", "n_kept", "n_nonfinite", "n_out_of_range", "n_masked", "n_new_voxels",
+                                        "n_voxels_total")]
+
+
+# the world map's seven entry points as include/mmloam_hip.h declares them, argument for argument
+WORLD_MAP_ARGTYPES = {
+    "mml_world_map_create": [C.c_void_p, C.c_int, C.c_float, C.c_long],
+    "mml_world_map_destroy": [C.c_void_p],
+    "mml_world_map_reset": [C.c_void_p, C.c_int],
+    "mml_world_map_add": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p],
+    "mml_world_map_size": [C.c_void_p, C.c_int, C.c_void_p],
+    "mml_world_map_download": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p],
+}
+
+
 def build(force=False):
     """Compile csrc/*.hip for gfx950 into libmmloam_hip.so (hipcc cross-compiles without a GPU)."""
     csrc = os.path.join(_HERE, "csrc")
@@ -389,6 +406,10 @@ def lib():
             L.mml_wire_decode_host.argtypes = [C.c_int, C.c_void_p] + wire[:7] + [C.c_void_p] + wire[7:] + [C.c_void_p, C.c_void_p]
             L.mml_scan_upload_wire_batch.restype = C.c_int
             L.mml_scan_upload_wire_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p] + wire[:7] + [C.c_void_p] + wire[7:]
+        if hasattr(L, "mml_world_map_create"):
+            for name, args in WORLD_MAP_ARGTYPES.items():
+                getattr(L, name).restype = C.c_int
+                getattr(L, name).argtypes = args
         _lib = L
     return _lib
 
@@ -1213,6 +1234,44 @@ class Context:
         out = np.zeros((max(n.value, 1), 3), np.float32)
         self._ck(lib().mml_map_local_download(self._h, C.c_int(kind), _p(out), C.c_int(n.value), C.byref(n)))
         return out[:n.value].copy()
+
+    # ---- the world map: the registered clouds voxel-merged on the device, n maps (include/mmloam_hip.h, "The world map") ----
+    def world_map_create(self, n_maps, leaf, capacity_voxels):
+        """n_maps (1 .. 1024) voxel maps of leaf size `leaf` in one table of capacity_voxels voxels; once per context."""
+        self._ck(lib().mml_world_map_create(self._h, int(n_maps), float(leaf), int(capacity_voxels)))
+
+    def world_map_destroy(self):
+        self._ck(lib().mml_world_map_destroy(self._h))
+
+    def world_map_reset(self, map=-1):
+        """Empties one map, or all (-1)."""
+        self._ck(lib().mml_world_map_reset(self._h, int(map)))
+
+    def world_map_add(self, first_slot, maps, T_wl, label_mask=7):
+        """Slot first_slot + i into map maps[i] (-1: skipped) at T_wl[i] (4 x 4), the points whose label's bit is set in
+        label_mask: ONE mml_world_map_add call.  Returns its WorldMapInfo."""
+        m = np.ascontiguousarray(maps, dtype=np.int32).reshape(-1)
+        T = registered_poses(len(m), T_wl)
+        info = WorldMapInfo()
+        self._ck(lib().mml_world_map_add(self._h, int(first_slot), len(m), _p(m), _p(T), int(label_mask), C.byref(info)))
+        return info
+
+    def world_map_size(self, map=-1):
+        """The voxels of one map, or of all (-1)."""
+        n = C.c_long(0)
+        self._ck(lib().mml_world_map_size(self._h, int(map), C.byref(n)))
+        return n.value
+
+    def world_map_download(self, map, counts=False):
+        """The voxels of one map in ascending key order: (n, 4) float32 centroids x, y, z, intensity; counts=True: and the
+        (n,) int32 point counts.  The sizing call, then one data call."""
+        n = C.c_long(0)
+        f = lib().mml_world_map_download
+        self._ck(f(self._h, int(map), None, None, 0, C.byref(n)))
+        out, cnt = np.zeros((max(n.value, 1), 4), np.float32), np.zeros(max(n.value, 1), np.int32)
+        if n.value:
+            self._ck(f(self._h, int(map), _p(out), _p(cnt), n.value, C.byref(n)))
+        return (out[:n.value], cnt[:n.value]) if counts else out[:n.value]
 
     # ---- map banks: further local maps, every slot matched against its own (include/mmloam_hip.h, "map banks") ----
     def map_banks(self, n):

@@ -12,8 +12,10 @@
 
 #include "imu_math.h"
 #include "mml_internal.h"
+#include "fused_view_dev.h"
 #include "phase_clock.h"
 #include "raw_gather_dev.h"
+#include "world_map_key.h"
 
 int mml_launch_detect_line(mml_ctx* ctx, int n, uint16_t* d_final);
 
@@ -445,47 +447,7 @@ __global__ void k_decode_custompoints(const uint8_t* raw, int n, mml_livox_point
     q._pad = 0;
     out[i] = q;
 }
-// The fused cloud [velo_combine ; livox_combine] in its own order, gathered from the line-bucketed storage: position pos
-// (Velodyne region [0, cv), Livox region [NV, NV + cl)) holds fused point ln_gidx[pos] when that is >= 0.  The Velodyne
-// part of an extracted cloud carries intensity 0 (unionFeatureExtract.cpp:1254-1256); an uploaded cloud keeps its own.
-struct FusedView {
-    const float4* pts;
-    const int* gidx;
-    const int* rel;
-    const uint8_t* line;      // uploaded clouds
-    const uint8_t* label;
-    const int* cb_n;          // this slot's two valid counts
-    const int* seg_flat;      // extracted clouds: per sensor the starts of the storage segments in storage order (block-major,
-    const int* seg_flat_n;    //   line inside a block) -- 2 x MML_SEG_FLAT ints -- and (entries, lines per block) per sensor
-    int NV, NT, L, n_rings, flags;
-};
-__device__ __forceinline__ bool fused_at(const FusedView& V, int pos, int& g, float4& p, float& rel, int& line) {
-    if (pos >= V.NT) return false;
-    if (pos < V.NV ? pos >= V.cb_n[0] : pos - V.NV >= V.cb_n[1]) return false;
-    g = V.gidx[pos];
-    if (g < 0) return false;
-    p = V.pts[pos];
-    rel = (V.flags & 2) ? 1.0f : __int_as_float(V.rel[pos]);  // RemoveLidarDistortion leaves normal_x = 1 (unionPoseEstimation.cpp:419)
-    if (V.flags & 1) {
-        line = V.line[pos];
-    } else {
-        if (pos < V.NV) p.w = 0.f;  // intensity of the Velodyne part is zeroed (unionFeatureExtract.cpp:1254-1256)
-        // last storage segment of the region whose start is <= pos (starts are non-decreasing; an empty segment shares its start
-        // with the next one); segment f belongs to line f mod (lines per block)
-        const int sensor = pos < V.NV ? 0 : 1;
-        const int* flat = V.seg_flat + sensor * MML_SEG_FLAT;
-        int lo = 0, hi = V.seg_flat_n[2 * sensor] - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (flat[mid] <= pos)
-                lo = mid;
-            else
-                hi = mid - 1;
-        }
-        line = lo % V.seg_flat_n[2 * sensor + 1];
-    }
-    return true;
-}
+// (FusedView / fused_at, the fused cloud [velo_combine ; livox_combine] in its own order: fused_view_dev.h)
 // pcl::toROSMsg<PointXYZINormal> payload: 48-byte records, x y z 1 | normal_x normal_y normal_z 0 | intensity curvature 0 0
 __global__ void k_encode_xyzinormal(FusedView V, float* out) {
     const int pos = blockIdx.x * blockDim.x + threadIdx.x;
@@ -525,40 +487,7 @@ __global__ void k_fused_arrays(FusedView V, int n, float4* xyzi, float* rel, uin
     line[g] = (uint8_t)ln;
     label[g] = V.label[pos];
 }
-// the per-point and per-slot arrays of a context that a kernel over the slots [first, ...) indexes by slot
-struct SlotArrays {
-    const float4* pts;
-    const int* gidx;
-    const int* rel;
-    const uint8_t* line;
-    const uint8_t* label;
-    const int* cb_n;
-    const int* seg_flat;
-    const int* seg_flat_n;
-    const int* slot_flags;
-    const int* fu_info;
-    int NV, NT, L, n_rings, first;
-};
-// The FusedView of one slot, derived on the device from the context-wide arrays; the flag word is read here, where fused_view
-// spends a synchronising read-back per slot.
-__device__ __forceinline__ FusedView slot_view(const SlotArrays& A, int slot) {
-    FusedView V;
-    const size_t off = (size_t)slot * A.NT;
-    V.pts = A.pts + off;
-    V.gidx = A.gidx + off;
-    V.rel = A.rel + off;
-    V.line = A.line + off;
-    V.label = A.label + off;
-    V.cb_n = A.cb_n + 2 * (size_t)slot;
-    V.seg_flat = A.seg_flat + (size_t)slot * 2 * MML_SEG_FLAT;
-    V.seg_flat_n = A.seg_flat_n + (size_t)slot * 4;
-    V.NV = A.NV;
-    V.NT = A.NT;
-    V.L = A.L;
-    V.n_rings = A.n_rings;
-    V.flags = A.slot_flags[2 * (size_t)slot];
-    return V;
-}
+// (SlotArrays / slot_view, the view of one slot derived on the device from the context-wide arrays: fused_view_dev.h)
 // The registered cloud (unionPoseEstimation.cpp:896-903): every fused point of slot A.first + blockIdx.y through
 // pointAssociateToMap (:199-213) with that slot's pose, as the PointXYZINormal the loop pushes back -- a default-constructed
 // point (x y z 1 | 0 0 0 0 | 0 0 0 0) that receives x y z, intensity and normal_z only.  pout = R * pin + t in double, in Eigen's
@@ -580,9 +509,7 @@ __global__ void __launch_bounds__(256) k_encode_registered(SlotArrays A, const d
     const long long rec_off = reinterpret_cast<const long long*>(par + 16 * (size_t)count)[i];
     const double x = p.x, y = p.y, z = p.z;
     float4 a, b, c;
-    a.x = (float)(((T[0] * x + T[1] * y) + T[2] * z) + T[3]);
-    a.y = (float)(((T[4] * x + T[5] * y) + T[6] * z) + T[7]);
-    a.z = (float)(((T[8] * x + T[9] * y) + T[10] * z) + T[11]);
+    mml_world_point(T, x, y, z, a.x, a.y, a.z);  // (world_map_key.h: the one definition, shared with the world map)
     a.w = 1.0f;
     b.x = 0.f;
     b.y = 0.f;
@@ -837,25 +764,6 @@ int upload_wire_impl(mml_ctx* ctx, int slot, const uint8_t* data, int n_points, 
 }  // namespace
 
 namespace {
-SlotArrays slot_arrays(const mml_ctx* ctx, int first) {
-    SlotArrays A;
-    A.pts = ctx->ln_pts;
-    A.gidx = ctx->ln_gidx;
-    A.rel = ctx->ln_rel;
-    A.line = ctx->ln_line;
-    A.label = ctx->ln_label;
-    A.cb_n = ctx->cb_n;
-    A.seg_flat = ctx->seg_flat;
-    A.seg_flat_n = ctx->seg_flat_n;
-    A.slot_flags = ctx->slot_flags;
-    A.fu_info = ctx->fu_info;
-    A.NV = ctx->NV;
-    A.NT = ctx->NT;
-    A.L = ctx->L;
-    A.n_rings = ctx->cfg.n_rings;
-    A.first = first;
-    return A;
-}
 int fused_view(mml_ctx* ctx, int slot, FusedView& V) {
     int fl = 0;
     MML_HIP(hipMemcpyAsync(&fl, ctx->slot_flags + 2 * (size_t)slot, sizeof(int), hipMemcpyDeviceToHost, MML_STREAM(ctx)));

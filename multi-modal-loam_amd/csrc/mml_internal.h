@@ -380,6 +380,34 @@ struct mml_ctx {
         MmlStaging<char> tab;                // a chunk's tables and read-backs: device block and pinned twin
         long budget = MML_BANK_GLOBAL_INCREMENT_BUDGET;  // points per chunk (mml_debug_bank_global_increment_budget)
     } bank_cube;
+    // the world map (world_map.hip, mml_world_map_*): one open-addressing table of voxels for n maps, a group of its own.
+    // 28 bytes per table position (key, float4 sum, count), 2 .. 4 positions per voxel of capacity; the add chain's scratch is 52
+    // bytes per point of the call's bound (count x NT), grow-only, beside rocPRIM's temporary storage and the call's table block
+    struct WorldMap {
+        int n_maps = 0;                      // 0: no world map
+        float leaf = 0.f;
+        long capacity = 0;                   // voxels, all maps together
+        unsigned long long slots = 0;        // table positions: the next power of two >= 2 x capacity
+        unsigned long long* keys = nullptr;  // slots: world_map_key.h keys, MML_WM_EMPTY where free
+        float4* sum = nullptr;               // slots: x, y, z, intensity
+        int* count = nullptr;                // slots
+        int* map_n = nullptr;                // n_maps + 1: voxels per map, then the total
+        MmlGroup mem;                        // owns the four
+        MmlStaging<char, false> scratch;     // the calls' scratch (one call at a time)
+        MmlStaging<char, false> tmp;         // rocPRIM temporary storage
+        MmlStaging<char> tab;                // a call's slot rows and counters: device block and pinned twin
+        void release() {
+            mem.release();
+            scratch.release();
+            tmp.release();
+            tab.release();
+            keys = nullptr;
+            sum = nullptr;
+            count = nullptr;
+            map_n = nullptr;
+            n_maps = 0;
+        }
+    } world;
     float4* map_tmp = nullptr;
     unsigned* map_keys = nullptr;
     unsigned* map_keys2 = nullptr;
@@ -429,6 +457,7 @@ struct mml_ctx {
         bank_inc.tab.release();
         bank_cube.mem.release();
         bank_cube.tab.release();
+        world.release();
         clive.mem.release();
         cube_scratch.release();
         wire_stage.release();

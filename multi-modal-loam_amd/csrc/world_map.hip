@@ -1,0 +1,441 @@
+// world_map.hip -- the world map: the registered clouds of n sequences voxel-merged on the device (mml_world_map_*).
+// One open-addressing hash table per context (mml_ctx::world): key (world_map_key.h: map << 54 | three 18-bit voxel indices),
+// float4 sum (x, y, z, intensity) and count per position, linear probing, MML_WM_EMPTY where free; n maps share the table, the
+// map number is part of the key.  A voxel is never moved or removed by an add, so the work of a call does not depend on the size
+// of the map.  The arithmetic -- world point, voxel index, key, hash, accumulator -- is world_map_key.h's and nowhere else.
+//
+// mml_world_map_add, one chain for the `count` slots of the call (B = the call's bound: NT points for every slot that takes part):
+//   k_wm_keys      grid (NT / 256, count): the slot's row (pose, map, offset) is wave-uniform; every fused point of the slot through
+//                  mml_world_point and mml_wm_classify, label_mask applied, the skipped points counted; kept point g of slot i
+//                  writes its world point, key and ordinal at index off_i + g (the keys were preset to MML_WM_EMPTY, so every
+//                  other index sorts behind the kept points)
+//   sort           one stable mml_sort_pairs<unsigned long long> over the B pairs: equal keys stay in ordinal order = slot order,
+//                  then fused point order; k_run_heads (the empty marker starts no run) and one exclusive scan
+//   k_wm_lookup    one lane per distinct voxel of the call: probes the table read-only, records the position or a miss; the launch
+//                  counts the distinct voxels and the misses
+//   read-back      the call's ONLY host synchronisation: the seven counters and the table's total.  total + misses > capacity:
+//                  MML_ERR_CAPACITY -- only scratch has been written up to here
+//   k_wm_insert    one lane per distinct voxel: a miss claims a position with a 64-bit atomicCAS on the key array; then the run of
+//                  the voxel's points is added in order to the stored accumulator (zero for a new voxel) and stored with plain
+//                  stores -- keys inside a call are distinct, one lane owns a voxel; the per-map counts and the total follow
+// Scratch per point of B: 16 (world point) + 2 x 8 (keys in / out) + 2 x 4 (ordinals in / out) + 3 x 4 (run head, scan, hit) = 52
+// bytes, grow-only, and rocPRIM's temporary storage beside it.
+#include <limits.h>
+#include <math.h>
+#include <string.h>
+
+#include "mml_internal.h"
+#include "fused_view_dev.h"
+#include "voxel_sort_dev.h"
+#include "world_map_key.h"
+
+namespace {
+// one slot of the call, read through scalar loads (blockIdx.y)
+struct WmRow {
+    double T[16];  // T_wl, row-major
+    int map;       // -1: the slot is skipped
+    int off;       // the slot's first index in the call's arrays
+    int pad[2];
+};
+enum { WM_POINTS, WM_KEPT, WM_NONFINITE, WM_RANGE, WM_MASKED, WM_DISTINCT, WM_MISSES, WM_COUNTERS };
+
+// one add per wave of the lanes for which `pred` holds
+__device__ __forceinline__ void wm_count(int* counter, bool pred) {
+    const unsigned long long b = __ballot(pred);
+    if (b && (threadIdx.x & 63) == 0) atomicAdd(counter, __popcll(b));
+}
+
+__global__ __launch_bounds__(256) void k_wm_keys(SlotArrays A, const WmRow* __restrict__ rows, float inv, unsigned label_mask,
+                                                 float4* __restrict__ pts, unsigned long long* __restrict__ keys,
+                                                 unsigned* __restrict__ vals, int* __restrict__ counters) {
+    const WmRow& R = rows[blockIdx.y];
+    if (R.map < 0) return;  // (the whole workgroup)
+    const int slot = A.first + blockIdx.y;
+    const FusedView V = slot_view(A, slot);
+    const int b0 = blockIdx.x * blockDim.x, cv = V.cb_n[0], cl = V.cb_n[1];
+    if (b0 >= V.NV + cl || (b0 >= cv && b0 + (int)blockDim.x <= V.NV)) return;  // (as k_encode_registered: no valid position here)
+    int g = 0, line;
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
+    float rel;
+    bool valid = fused_at(V, b0 + threadIdx.x, g, p, rel, line);
+    valid = valid && g < A.fu_info[8 * (size_t)slot] && g < A.NT;  // (the slot's points end at its count; an index stays inside the slot's NT)
+    int what = -1;  // -1: masked (or no point)
+    unsigned long long key = MML_WM_EMPTY;
+    float wx = 0.f, wy = 0.f, wz = 0.f;
+    if (valid) {
+        const unsigned label = V.label[b0 + threadIdx.x];
+        if (label < 3 && ((label_mask >> label) & 1u)) {
+            mml_world_point(R.T, p.x, p.y, p.z, wx, wy, wz);
+            what = mml_wm_classify(R.map, wx, wy, wz, p.w, inv, key);
+        }
+    }
+    wm_count(counters + WM_POINTS, valid);
+    wm_count(counters + WM_MASKED, valid && what < 0);
+    wm_count(counters + WM_NONFINITE, what == MML_WM_NONFINITE);
+    wm_count(counters + WM_RANGE, what == MML_WM_OUT_OF_RANGE);
+    wm_count(counters + WM_KEPT, what == MML_WM_KEPT);
+    if (what == MML_WM_KEPT) {
+        const size_t at = (size_t)R.off + g;
+        pts[at] = make_float4(wx, wy, wz, p.w);
+        keys[at] = key;
+        vals[at] = (unsigned)at;
+    }
+}
+
+// where `key` sits in the table, or -1: the probe ends at the key or at the first free position (there always is one: the table
+// holds at most half as many voxels as it has positions)
+__device__ __forceinline__ long long wm_find(const unsigned long long* __restrict__ tab, unsigned long long slots, unsigned long long key) {
+    unsigned long long h = mml_wm_hash(key, slots);
+    for (unsigned long long step = 0; step < slots; ++step) {
+        const unsigned long long k = tab[h];
+        if (k == key) return (long long)h;
+        if (k == MML_WM_EMPTY) return -1;
+        h = (h + 1) & (slots - 1);
+    }
+    return -1;
+}
+// claims a free position for `key` (which is not in the table, and which no other lane inserts); -1 only from a full table
+__device__ __forceinline__ long long wm_claim(unsigned long long* __restrict__ tab, unsigned long long slots, unsigned long long key) {
+    unsigned long long h = mml_wm_hash(key, slots);
+    for (unsigned long long step = 0; step < slots; ++step) {
+        if (atomicCAS(tab + h, MML_WM_EMPTY, key) == MML_WM_EMPTY) return (long long)h;
+        h = (h + 1) & (slots - 1);
+    }
+    return -1;
+}
+
+__global__ __launch_bounds__(256) void k_wm_lookup(const unsigned long long* __restrict__ keys, const int* __restrict__ flag, int n,
+                                                   const unsigned long long* __restrict__ tab, unsigned long long slots,
+                                                   int* __restrict__ hit, int* __restrict__ counters) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool head = s < n && flag[s];
+    long long at = 0;
+    if (head) {
+        at = wm_find(tab, slots, keys[s]);
+        hit[s] = (int)at;
+    }
+    wm_count(counters + WM_DISTINCT, head);
+    wm_count(counters + WM_MISSES, head && at < 0);
+}
+
+__global__ __launch_bounds__(256) void k_wm_insert(const unsigned long long* __restrict__ keys, const unsigned* __restrict__ vals,
+                                                   const int* __restrict__ flag, const int* __restrict__ hit, int n,
+                                                   const float4* __restrict__ pts, unsigned long long* __restrict__ tab,
+                                                   unsigned long long slots, float4* __restrict__ sum, int* __restrict__ count,
+                                                   int* __restrict__ map_n, int n_maps) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool head = s < n && flag[s];
+    bool fresh = false;
+    if (head) {
+        const unsigned long long key = keys[s];
+        long long at = hit[s];
+        MmlWmAcc a = {0.f, 0.f, 0.f, 0.f, 0};
+        if (at < 0) {
+            fresh = true;
+            at = wm_claim(tab, slots, key);
+            atomicAdd(map_n + (int)(key >> MML_WM_MAP_SHIFT), 1);
+        } else {
+            const float4 v = sum[at];
+            a.x = v.x;
+            a.y = v.y;
+            a.z = v.z;
+            a.w = v.w;
+            a.n = count[at];
+        }
+        if (at >= 0) {  // (always: the host refused the call that would have filled the table)
+            for (int e = s; e < n && keys[e] == key; ++e) {
+                const float4 p = pts[vals[e]];
+                mml_wm_add(a, p.x, p.y, p.z, p.w);
+            }
+            sum[at] = make_float4(a.x, a.y, a.z, a.w);
+            count[at] = a.n;
+        }
+    }
+    wm_count(map_n + n_maps, fresh);
+}
+
+// download / reset: the occupied positions of one map (or of every map but one) appended to a list in any order
+template <bool Others>
+__global__ __launch_bounds__(256) void k_wm_collect(const unsigned long long* __restrict__ tab, unsigned long long slots, int map, int cap,
+                                                    int* __restrict__ cursor, unsigned long long* __restrict__ keys, unsigned* __restrict__ vals) {
+    for (unsigned long long h = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; h < slots; h += (unsigned long long)gridDim.x * blockDim.x) {
+        const unsigned long long k = tab[h];
+        if (k == MML_WM_EMPTY || ((int)(k >> MML_WM_MAP_SHIFT) == map) == Others) continue;
+        const int at = atomicAdd(cursor, 1);
+        if (at < cap) {
+            keys[at] = k;
+            vals[at] = (unsigned)h;
+        }
+    }
+}
+// download: the centroids of the sorted positions
+__global__ __launch_bounds__(256) void k_wm_centroids(const unsigned* __restrict__ vals, int n, const float4* __restrict__ sum,
+                                                      const int* __restrict__ count, float4* __restrict__ out, int* __restrict__ out_n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const unsigned at = vals[i];
+    const float4 v = sum[at];
+    const MmlWmAcc a = {v.x, v.y, v.z, v.w, count[at]};
+    float c[4];
+    mml_wm_centroid(a, c);
+    out[i] = make_float4(c[0], c[1], c[2], c[3]);
+    out_n[i] = a.n;
+}
+// reset of one map: the survivors' accumulators beside their keys, before the table is cleared ...
+__global__ __launch_bounds__(256) void k_wm_take(const unsigned* __restrict__ vals, int n, const float4* __restrict__ sum,
+                                                 const int* __restrict__ count, float4* __restrict__ s_sum, int* __restrict__ s_n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    s_sum[i] = sum[vals[i]];
+    s_n[i] = count[vals[i]];
+}
+// ... and back into the cleared table; lane 0 writes the counts of the map that went and the new total
+__global__ __launch_bounds__(256) void k_wm_reinsert(const unsigned long long* __restrict__ keys, int n, const float4* __restrict__ s_sum,
+                                                     const int* __restrict__ s_n, unsigned long long* __restrict__ tab,
+                                                     unsigned long long slots, float4* __restrict__ sum, int* __restrict__ count,
+                                                     int* __restrict__ map_n, int n_maps, int map) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0) {
+        map_n[map] = 0;
+        map_n[n_maps] = n;
+    }
+    if (i >= n) return;
+    const long long at = wm_claim(tab, slots, keys[i]);
+    if (at < 0) return;
+    sum[at] = s_sum[i];
+    count[at] = s_n[i];
+}
+
+int wm_enter(mml_ctx* ctx, const char* who) {
+    if (!ctx) return MML_ERR_INVALID;
+    if (ctx->world.n_maps == 0) return mml_refuse(ctx, MML_ERR_STATE, "%s: the context has no world map (mml_world_map_create)", who);
+    MML_HIP(hipSetDevice(ctx->device));
+    return MML_OK;
+}
+int wm_clear(mml_ctx* ctx, hipStream_t s) {
+    mml_ctx::WorldMap& W = ctx->world;
+    MML_HIP(hipMemsetAsync(W.keys, 0xff, sizeof(unsigned long long) * W.slots, s));
+    MML_HIP(hipMemsetAsync(W.map_n, 0, sizeof(int) * ((size_t)W.n_maps + 1), s));
+    return MML_OK;
+}
+unsigned wm_blocks(size_t n) { return (unsigned)((n + 255) / 256); }
+}  // namespace
+
+int mml_world_map_create(mml_ctx* ctx, int n_maps, float leaf, long capacity_voxels) {
+    if (!ctx) return MML_ERR_INVALID;
+    MML_REQUIRE(n_maps >= 1 && n_maps <= MML_WM_MAPS_MAX, MML_ERR_INVALID, "mml_world_map_create: n_maps outside 1..1024");
+    MML_REQUIRE(isfinite(leaf) && leaf > 0.f, MML_ERR_INVALID, "mml_world_map_create: leaf must be finite and positive");
+    MML_REQUIRE(capacity_voxels >= 1 && capacity_voxels <= (1L << 29), MML_ERR_INVALID, "mml_world_map_create: capacity_voxels outside 1..2^29");
+    mml_ctx::WorldMap& W = ctx->world;
+    if (W.n_maps) return mml_refuse(ctx, MML_ERR_STATE, "mml_world_map_create: the context has a world map of %d maps already", W.n_maps);
+    MML_HIP(hipSetDevice(ctx->device));
+    const unsigned long long slots = mml_wm_table_slots(capacity_voxels);
+    int rc = W.mem.reserve(ctx, {mml_part(W.keys, (size_t)slots), mml_part(W.sum, (size_t)slots), mml_part(W.count, (size_t)slots),
+                                 mml_part(W.map_n, (size_t)n_maps + 1)});
+    if (rc != MML_OK) return rc;
+    W.n_maps = n_maps;
+    W.leaf = leaf;
+    W.capacity = capacity_voxels;
+    W.slots = slots;
+    hipStream_t s = MML_STREAM(ctx);
+    rc = wm_clear(ctx, s);
+    if (rc == MML_OK && hipStreamSynchronize(s) != hipSuccess) rc = mml_refuse(ctx, MML_ERR_HIP, "mml_world_map_create: hipStreamSynchronize failed");
+    if (rc != MML_OK) W.release();
+    return rc;
+}
+
+int mml_world_map_destroy(mml_ctx* ctx) {
+    int rc = wm_enter(ctx, "mml_world_map_destroy");
+    if (rc != MML_OK) return rc;
+    MML_HIP(hipStreamSynchronize(MML_STREAM(ctx)));
+    ctx->world.release();
+    return MML_OK;
+}
+
+int mml_world_map_size(mml_ctx* ctx, int map, long* n_voxels) {
+    int rc = wm_enter(ctx, "mml_world_map_size");
+    if (rc != MML_OK) return rc;
+    mml_ctx::WorldMap& W = ctx->world;
+    MML_REQUIRE(n_voxels != nullptr, MML_ERR_INVALID, "mml_world_map_size: null n_voxels");
+    if (map < -1 || map >= W.n_maps) return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_size: map %d outside [-1, %d)", map, W.n_maps);
+    int* h = reinterpret_cast<int*>(mml_stage_alloc(ctx, 1));
+    MML_HIP(hipMemcpyAsync(h, W.map_n + (map < 0 ? W.n_maps : map), sizeof(int), hipMemcpyDeviceToHost, MML_STREAM(ctx)));
+    MML_HIP(hipStreamSynchronize(MML_STREAM(ctx)));
+    *n_voxels = h[0];
+    return MML_OK;
+}
+
+int mml_world_map_reset(mml_ctx* ctx, int map) {
+    int rc = wm_enter(ctx, "mml_world_map_reset");
+    if (rc != MML_OK) return rc;
+    mml_ctx::WorldMap& W = ctx->world;
+    if (map < -1 || map >= W.n_maps) return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_reset: map %d outside [-1, %d)", map, W.n_maps);
+    hipStream_t s = MML_STREAM(ctx);
+    if (map < 0) return wm_clear(ctx, s);
+    // One map of several: an open-addressing table has no way to free a position inside a probe chain (every key value is in use,
+    // there is no tombstone), so the other maps' voxels are taken out, the table is cleared and they are put back.
+    int* h = reinterpret_cast<int*>(mml_stage_alloc(ctx, 1));
+    MML_HIP(hipMemcpyAsync(h, W.map_n + map, sizeof(int), hipMemcpyDeviceToHost, s));
+    MML_HIP(hipMemcpyAsync(h + 1, W.map_n + W.n_maps, sizeof(int), hipMemcpyDeviceToHost, s));
+    MML_HIP(hipStreamSynchronize(s));
+    if (h[0] == 0) return MML_OK;
+    const size_t m = (size_t)(h[1] - h[0]);
+    MmlCarve<16> c;
+    const MmlField<unsigned long long> f_keys = c.take<unsigned long long>(m);
+    const MmlField<unsigned> f_vals = c.take<unsigned>(m);
+    const MmlField<float4> f_sum = c.take<float4>(m);
+    const MmlField<int> f_n = c.take<int>(m);
+    const MmlField<int> f_cur = c.take<int>(1);
+    rc = W.scratch.reserve(ctx, c.bytes(), s);
+    if (rc != MML_OK) return rc;
+    char* d = W.scratch.d;
+    MML_HIP(hipMemsetAsync(f_cur.in(d), 0, sizeof(int), s));
+    if (m) {
+        MML_HIP(hipMemsetAsync(f_vals.in(d), 0, f_vals.bytes(), s));  // (every entry a table position, whatever the walk finds)
+        hipLaunchKernelGGL(k_wm_collect<true>, dim3(wm_blocks((size_t)W.slots) < 1024 ? wm_blocks((size_t)W.slots) : 1024), dim3(256), 0, s, W.keys,
+                           W.slots, map, (int)m, f_cur.in(d), f_keys.in(d), f_vals.in(d));
+        hipLaunchKernelGGL(k_wm_take, dim3(wm_blocks(m)), dim3(256), 0, s, f_vals.in(d), (int)m, W.sum, W.count, f_sum.in(d), f_n.in(d));
+    }
+    MML_HIP(hipMemsetAsync(W.keys, 0xff, sizeof(unsigned long long) * W.slots, s));
+    hipLaunchKernelGGL(k_wm_reinsert, dim3(m ? wm_blocks(m) : 1), dim3(256), 0, s, f_keys.in(d), (int)m, f_sum.in(d), f_n.in(d), W.keys, W.slots,
+                       W.sum, W.count, W.map_n, W.n_maps, map);
+    MML_HIP(hipGetLastError());
+    return MML_OK;
+}
+
+int mml_world_map_add(mml_ctx* ctx, int first_slot, int count, const int* map_of_slot, const double* T_wl, unsigned label_mask,
+                      mml_world_map_info* info) {
+    int rc = wm_enter(ctx, "mml_world_map_add");
+    if (rc != MML_OK) return rc;
+    mml_ctx::WorldMap& W = ctx->world;
+    MML_REQUIRE(count >= 1 && count <= 65535, MML_ERR_INVALID, "mml_world_map_add: count outside 1..65535 (the grid's second dimension)");
+    MML_REQUIRE(first_slot >= 0 && first_slot + count <= ctx->B, MML_ERR_INVALID, "mml_world_map_add: slot range out of bounds");
+    MML_REQUIRE(map_of_slot != nullptr && T_wl != nullptr, MML_ERR_INVALID, "mml_world_map_add: null map_of_slot / T_wl");
+    MML_REQUIRE((label_mask & 7u) != 0, MML_ERR_INVALID, "mml_world_map_add: label_mask selects no label");
+    int live = 0;
+    for (int i = 0; i < count; ++i) {
+        if (map_of_slot[i] < -1 || map_of_slot[i] >= W.n_maps)
+            return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_add: map %d of slot %d outside [-1, %d)", map_of_slot[i], first_slot + i, W.n_maps);
+        live += map_of_slot[i] >= 0;
+    }
+    if (!ctx->uploads.empty() && (rc = mml_uploads_wait(ctx, first_slot, count)) != MML_OK) return rc;
+    if (info) memset(info, 0, sizeof(*info));
+    hipStream_t s = MML_STREAM(ctx);
+    if (live == 0) {
+        if (info) return mml_world_map_size(ctx, -1, &info->n_voxels_total);
+        return MML_OK;
+    }
+    rc = mml_cloud_settle(ctx, first_slot, count);  // (as every reader of the cloud outside the step: mml_internal.h, und_pending)
+    if (rc != MML_OK) return rc;
+    const long long bound = (long long)live * ctx->NT;
+    if (bound > INT_MAX) return mml_refuse(ctx, MML_ERR_CAPACITY, "mml_world_map_add: %d slots of %d points exceed 2^31 - 1 points per call", live, ctx->NT);
+    const size_t n = (size_t)bound;
+    // scratch and tables, all before the first launch
+    MmlCarve<16> c;
+    const MmlField<float4> f_pts = c.take<float4>(n);
+    const MmlField<unsigned long long> f_keys = c.take<unsigned long long>(2 * n);
+    const MmlField<unsigned> f_vals = c.take<unsigned>(2 * n);
+    const MmlField<int> f_flag = c.take<int>(n), f_pos = c.take<int>(n), f_hit = c.take<int>(n);
+    rc = W.scratch.reserve(ctx, c.bytes(), s);
+    if (rc != MML_OK) return rc;
+    int map_bits = 1;
+    while ((1 << map_bits) < W.n_maps) ++map_bits;
+    // one bit above the map numbers in use, so that the empty marker sorts behind every key (with more than 512 maps all 64 bits
+    // are compared, and no kept key equals the marker)
+    const int end_bit = MML_WM_MAP_SHIFT + map_bits + 1 < 64 ? MML_WM_MAP_SHIFT + map_bits + 1 : 64;
+    rc = W.tmp.reserve(ctx, mml_sort_pairs_bytes<unsigned long long>(n, end_bit, s), s);
+    if (rc != MML_OK) return rc;
+    MmlCarve<16> t;
+    const MmlField<WmRow> f_rows = t.take<WmRow>((size_t)count);
+    const MmlField<int> f_cnt = t.take<int>(WM_COUNTERS + 1);  // the counters, and behind them (read-back only) the table's total
+    rc = W.tab.reserve(ctx, t.bytes(), s);
+    if (rc != MML_OK) return rc;
+    // (the pinned twin is free: the last call that used it waited for its read-back, which ran behind its copy down)
+    WmRow* h_rows = f_rows.in(W.tab.h);
+    int off = 0;
+    for (int i = 0; i < count; ++i) {
+        memset(static_cast<void*>(&h_rows[i]), 0, sizeof(WmRow));
+        memcpy(h_rows[i].T, T_wl + 16 * (size_t)i, sizeof(double) * 16);
+        h_rows[i].map = map_of_slot[i];
+        h_rows[i].off = off;
+        if (map_of_slot[i] >= 0) off += ctx->NT;
+    }
+    int* h_cnt = f_cnt.in(W.tab.h);
+    memset(h_cnt, 0, f_cnt.bytes());
+    MML_HIP(hipMemcpyAsync(W.tab.d, W.tab.h, t.bytes(), hipMemcpyHostToDevice, s));
+    char* d = W.scratch.d;
+    unsigned long long *keys = f_keys.in(d), *keys2 = keys + n;
+    unsigned *vals = f_vals.in(d), *vals2 = vals + n;
+    int* d_cnt = f_cnt.in(W.tab.d);
+    MML_HIP(hipMemsetAsync(keys, 0xff, sizeof(unsigned long long) * n, s));
+    MML_HIP(hipMemsetAsync(vals, 0, sizeof(unsigned) * n, s));
+    hipLaunchKernelGGL(k_wm_keys, dim3(wm_blocks((size_t)ctx->NT), count), dim3(256), 0, s, slot_arrays(ctx, first_slot), f_rows.in(W.tab.d),
+                       mml_wm_inv_leaf(W.leaf), label_mask & 7u, f_pts.in(d), keys, vals, d_cnt);
+    rc = mml_sort_pairs(ctx, W.tmp, keys, keys2, vals, vals2, n, end_bit, s);
+    if (rc != MML_OK) return rc;
+    hipLaunchKernelGGL(k_run_heads<unsigned long long>, dim3(wm_blocks(n)), dim3(256), 0, s, keys2, (int)n, 0, MML_WM_EMPTY, f_flag.in(d));
+    rc = mml_exclusive_scan(ctx, W.tmp, f_flag.in(d), f_pos.in(d), n, s);
+    if (rc != MML_OK) return rc;
+    hipLaunchKernelGGL(k_wm_lookup, dim3(wm_blocks(n)), dim3(256), 0, s, keys2, f_flag.in(d), (int)n, W.keys, W.slots, f_hit.in(d), d_cnt);
+    MML_HIP(hipGetLastError());
+    // the call's one read-back
+    MML_HIP(hipMemcpyAsync(h_cnt, d_cnt, sizeof(int) * WM_COUNTERS, hipMemcpyDeviceToHost, s));
+    MML_HIP(hipMemcpyAsync(h_cnt + WM_COUNTERS, W.map_n + W.n_maps, sizeof(int), hipMemcpyDeviceToHost, s));
+    MML_HIP(hipStreamSynchronize(s));
+    const long total = h_cnt[WM_COUNTERS], misses = h_cnt[WM_MISSES];
+    if (total + misses > W.capacity)
+        return mml_refuse(ctx, MML_ERR_CAPACITY, "mml_world_map_add: %ld voxels held + %ld new ones exceed capacity_voxels %ld; nothing was added", total,
+                          misses, W.capacity);
+    if (h_cnt[WM_DISTINCT])
+        hipLaunchKernelGGL(k_wm_insert, dim3(wm_blocks(n)), dim3(256), 0, s, keys2, vals2, f_flag.in(d), f_hit.in(d), (int)n, f_pts.in(d), W.keys,
+                           W.slots, W.sum, W.count, W.map_n, W.n_maps);
+    MML_HIP(hipGetLastError());
+    if (info) {
+        info->n_points = h_cnt[WM_POINTS];
+        info->n_kept = h_cnt[WM_KEPT];
+        info->n_nonfinite = h_cnt[WM_NONFINITE];
+        info->n_out_of_range = h_cnt[WM_RANGE];
+        info->n_masked = h_cnt[WM_MASKED];
+        info->n_new_voxels = misses;
+        info->n_voxels_total = total + misses;
+    }
+    return MML_OK;
+}
+
+int mml_world_map_download(mml_ctx* ctx, int map, float* out_xyzi, int* out_count, long capacity, long* n_voxels) {
+    int rc = wm_enter(ctx, "mml_world_map_download");
+    if (rc != MML_OK) return rc;
+    mml_ctx::WorldMap& W = ctx->world;
+    MML_REQUIRE(n_voxels != nullptr, MML_ERR_INVALID, "mml_world_map_download: null n_voxels");
+    if (map < 0 || map >= W.n_maps) return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_download: map %d outside [0, %d)", map, W.n_maps);
+    rc = mml_world_map_size(ctx, map, n_voxels);
+    if (rc != MML_OK || !out_xyzi || *n_voxels == 0) return rc;
+    if (capacity < *n_voxels) return mml_refuse(ctx, MML_ERR_CAPACITY, "mml_world_map_download: map %d holds %ld voxels, capacity is %ld", map, *n_voxels, capacity);
+    hipStream_t s = MML_STREAM(ctx);
+    const size_t n = (size_t)*n_voxels;
+    MmlCarve<16> c;
+    const MmlField<unsigned long long> f_keys = c.take<unsigned long long>(2 * n);
+    const MmlField<unsigned> f_vals = c.take<unsigned>(2 * n);
+    const MmlField<float4> f_out = c.take<float4>(n);
+    const MmlField<int> f_n = c.take<int>(n);
+    const MmlField<int> f_cur = c.take<int>(1);
+    rc = W.scratch.reserve(ctx, c.bytes(), s);
+    if (rc != MML_OK) return rc;
+    rc = W.tmp.reserve(ctx, mml_sort_pairs_bytes<unsigned long long>(n, MML_WM_MAP_SHIFT, s), s);
+    if (rc != MML_OK) return rc;
+    char* d = W.scratch.d;
+    unsigned long long* keys = f_keys.in(d);
+    unsigned* vals = f_vals.in(d);
+    MML_HIP(hipMemsetAsync(f_cur.in(d), 0, sizeof(int), s));
+    MML_HIP(hipMemsetAsync(vals, 0, sizeof(unsigned) * n, s));  // (every entry a table position, whatever the walk finds)
+    hipLaunchKernelGGL(k_wm_collect<false>, dim3(wm_blocks((size_t)W.slots) < 1024 ? wm_blocks((size_t)W.slots) : 1024), dim3(256), 0, s, W.keys, W.slots,
+                       map, (int)n, f_cur.in(d), keys, vals);
+    rc = mml_sort_pairs(ctx, W.tmp, keys, keys + n, vals, vals + n, n, MML_WM_MAP_SHIFT, s);  // (the map number is the same in all)
+    if (rc != MML_OK) return rc;
+    hipLaunchKernelGGL(k_wm_centroids, dim3(wm_blocks(n)), dim3(256), 0, s, vals + n, (int)n, W.sum, W.count, f_out.in(d), f_n.in(d));
+    MML_HIP(hipGetLastError());
+    MML_HIP(hipMemcpyAsync(out_xyzi, f_out.in(d), sizeof(float4) * n, hipMemcpyDeviceToHost, s));
+    if (out_count) MML_HIP(hipMemcpyAsync(out_count, f_n.in(d), sizeof(int) * n, hipMemcpyDeviceToHost, s));
+    MML_HIP(hipStreamSynchronize(s));
+    return MML_OK;
+}

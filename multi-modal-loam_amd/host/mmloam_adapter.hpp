@@ -118,6 +118,51 @@ class Context {
     mml_config cfg_;
 };
 
+// The world map of a context (include/mmloam_hip.h, "The world map"): what a replay keeps of /velo_full_cloud_mapped, the
+// registered clouds of n sequences voxel-merged on the device.  Created with the object and destroyed with it; the context must
+// outlive it.  add: slot first_slot + i into map map_of_slot[i] (-1: skipped) at T_wl[16 i ...] (transformTobeMapped, row-major),
+// one device call and one host synchronisation for all slots.  download: the voxels of one map in ascending key order as points
+// x, y, z, intensity = the centroid, curvature = the voxel's point count, everything else as in a default-constructed point.
+class WorldMap {
+   public:
+    WorldMap(Context& ctx, int n_maps, float leaf, long capacity_voxels) : ctx_(ctx) {
+        check(ctx_.get(), mml_world_map_create(ctx_.get(), n_maps, leaf, capacity_voxels), "mml_world_map_create");
+    }
+    ~WorldMap() { mml_world_map_destroy(ctx_.get()); }
+    WorldMap(const WorldMap&) = delete;
+    WorldMap& operator=(const WorldMap&) = delete;
+    mml_world_map_info add(int first_slot, int count, const int* map_of_slot, const double* T_wl, unsigned label_mask = 7) {
+        mml_world_map_info info;
+        check(ctx_.get(), mml_world_map_add(ctx_.get(), first_slot, count, map_of_slot, T_wl, label_mask, &info), "mml_world_map_add");
+        return info;
+    }
+    void reset(int map = -1) { check(ctx_.get(), mml_world_map_reset(ctx_.get(), map), "mml_world_map_reset"); }
+    long size(int map = -1) {
+        long n = 0;
+        check(ctx_.get(), mml_world_map_size(ctx_.get(), map, &n), "mml_world_map_size");
+        return n;
+    }
+    long download(int map, PointCloud& cloud) {
+        long n = 0;
+        check(ctx_.get(), mml_world_map_download(ctx_.get(), map, nullptr, nullptr, 0, &n), "mml_world_map_download");
+        std::vector<float> xyzi(4 * (size_t)(n ? n : 1));
+        std::vector<int> cnt((size_t)(n ? n : 1));
+        if (n) check(ctx_.get(), mml_world_map_download(ctx_.get(), map, xyzi.data(), cnt.data(), n, &n), "mml_world_map_download");
+        cloud.assign((size_t)n, PointXYZINormal{0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f});
+        for (long i = 0; i < n; ++i) {
+            cloud[i].x = xyzi[4 * i];
+            cloud[i].y = xyzi[4 * i + 1];
+            cloud[i].z = xyzi[4 * i + 2];
+            cloud[i].intensity = xyzi[4 * i + 3];
+            cloud[i].curvature = (float)cnt[i];
+        }
+        return n;
+    }
+
+   private:
+    Context& ctx_;
+};
+
 // ---- feature_extraction (unionFeatureExtract.cpp:143-1320), hot-path members only -----------------------------------
 class feature_extraction {
    public:

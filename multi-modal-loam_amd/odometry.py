@@ -103,6 +103,29 @@ def _finish(st, T, is_degenerate):
     st.last_T = T
 
 
+def _published(st, fast_rotation):
+    """Whether the pose node publishes the scan's registered cloud (unionPoseEstimation.cpp:906): no failure detected by the
+    estimate that just ended, and no fast rotation seen by the caller."""
+    return not st.fail_detected and not fast_rotation
+
+
+def _world_map_create(ctx, n, world_map):
+    """world_map: None, or (leaf, capacity_voxels) -- n device-resident voxel maps of the registered clouds, one per sequence."""
+    if world_map is None:
+        return None
+    leaf, capacity = world_map
+    ctx.world_map_create(n, leaf, capacity)
+    return float(leaf), int(capacity)
+
+
+def _world_map_download(od, n, seq):
+    if not od._world_map:
+        raise ValueError("no world map: pass world_map=(leaf, capacity_voxels)")
+    if not 0 <= seq < n:
+        raise ValueError("sequence %d outside [0, %d)" % (seq, n))
+    return od.ctx.world_map_download(seq)
+
+
 def _adjacent_runs(items, slot_of):
     """items sorted by slot and cut wherever the next slot is not the one after: one device call per run."""
     runs = []
@@ -120,9 +143,11 @@ class LidarOdometry:
     the map thread's schedule (the module docstring: the one the reference's asynchronous thread follows when it keeps up) and
     Estimate matches against it first; the default drives the local map alone, call for call as before."""
 
-    def __init__(self, ctx, exTlb=None, lidar_mode=2, max_outer=5, inner_iters=10, global_map=False, map_skip_frame=2):
+    def __init__(self, ctx, exTlb=None, lidar_mode=2, max_outer=5, inner_iters=10, global_map=False, map_skip_frame=2,
+                 world_map=None):
         if map_skip_frame < 1:
             raise ValueError("map_skip_frame must be at least 1")
+        self._world_map = _world_map_create(ctx, 1, world_map)
         self.ctx = ctx
         self.exTlb = np.eye(4) if exTlb is None else np.asarray(exTlb, dtype=np.float64)
         self.exRbl = self.exTlb[:3, :3].T.copy()                      # :973
@@ -138,9 +163,10 @@ class LidarOdometry:
     def transform_to_be_mapped(self, P, Q):
         return _transform_to_be_mapped(self.exRbl, self.exPbl, P, Q)
 
-    def estimate_lidar_pose(self, slot, P, Q):
+    def estimate_lidar_pose(self, slot, P, Q, fast_rotation=False):
         """P (3), Q (x, y, z, w): predicted body pose of the scan in `slot` (already extracted and undistorted).
-        Returns the estimated (P, Q) and whether the local map grew."""
+        Returns the estimated (P, Q) and whether the local map grew.  With world_map=(leaf, capacity_voxels) the scan goes into
+        the world map when the pose node would publish it (_published; fast_rotation: the node's detected_fast_rotation)."""
         ctx = self.ctx
         P = np.asarray(P, dtype=np.float64).copy()
         Q = np.asarray(Q, dtype=np.float64).copy()
@@ -160,7 +186,13 @@ class LidarOdometry:
         if grew:
             _grown(self, self.lidar_mode, T, ctx.map_increment_local(slot, T))
         _finish(self, T, is_degenerate)
+        if self._world_map and _published(self, fast_rotation):
+            ctx.world_map_add(slot, [0], T)
         return P, Q, grew
+
+    def world_map(self, seq=0):
+        """The world map of the sequence: (n, 4) float32 voxel centroids x, y, z, intensity in ascending key order."""
+        return _world_map_download(self, 1, seq)
 
     def registered_cloud(self, slot):
         """The scan of `slot` in the world frame at the pose the last estimate_lidar_pose ended with -- the cloud the pose node
@@ -198,9 +230,10 @@ class BatchLidarOdometry:
     3 + R host synchronisations per round whatever n is."""
 
     def __init__(self, ctx, n, exTlb=None, lidar_mode=2, max_outer=5, inner_iters=10, global_map=False, map_skip_frame=2,
-                 increment="loop", global_increment="loop"):
+                 increment="loop", global_increment="loop", world_map=None):
         if n < 1:
             raise ValueError("n must be at least 1")
+        self._world_map = _world_map_create(ctx, n, world_map)
         if map_skip_frame < 1:
             raise ValueError("map_skip_frame must be at least 1")
         if increment not in ("loop", "segmented"):
@@ -224,10 +257,12 @@ class BatchLidarOdometry:
     def key_scans(self):
         return [st.key_scans for st in self.seq]
 
-    def estimate_lidar_pose(self, slots, P, Q):
+    def estimate_lidar_pose(self, slots, P, Q, fast_rotation=None):
         """slots[w]: the slot that holds sequence w's scan (already extracted and undistorted), or None when the sequence has
         no scan this round; P (n, 3), Q (n, 4; x, y, z, w): the predicted body poses.  No two sequences may share a slot.
-        Returns (P, Q, grew): the estimated poses (a sequence without a scan keeps its row) and one bool per sequence."""
+        Returns (P, Q, grew): the estimated poses (a sequence without a scan keeps its row) and one bool per sequence.
+        With world_map=(leaf, capacity_voxels), sequence w's scan goes into world map w at its transformTobeMapped when the pose
+        node would publish it (_published; fast_rotation: one detected_fast_rotation flag per sequence, None = none)."""
         ctx, n = self.ctx, self.n
         if len(slots) != n:
             raise ValueError("one slot (or None) per sequence (%d)" % n)
@@ -273,7 +308,15 @@ class BatchLidarOdometry:
                 _grown(self.seq[w], self.lidar_mode, T[w], (nc[i], ns[i]))
         for w in live:
             _finish(self.seq[w], T[w], degenerate[w])
+        if self._world_map:                                            # one add per run of adjacent slots among the published scans
+            fast = [False] * n if fast_rotation is None else list(fast_rotation)
+            for run in _adjacent_runs([w for w in live if _published(self.seq[w], fast[w])], slot_of):
+                ctx.world_map_add(slots[run[0]], run, np.stack([T[w] for w in run]))
         return P, Q, grew
+
+    def world_map(self, seq):
+        """The world map of sequence `seq`: (n, 4) float32 voxel centroids x, y, z, intensity in ascending key order."""
+        return _world_map_download(self, self.n, seq)
 
 
 def _rotvec_from_quat(q):

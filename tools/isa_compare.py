@@ -3,6 +3,8 @@
 
     hipcc <the Makefile's FLAGS> -save-temps -c map_assoc.hip      (once in each tree)
     python tools/isa_compare.py OLD/map_assoc-hip-amdgcn-amd-amdhsa-gfx950.s NEW/map_assoc-hip-amdgcn-amd-amdhsa-gfx950.s
+    python tools/isa_compare.py OLD/capi-hip-amdgcn-amd-amdhsa-gfx950.s NEW/capi-hip-amdgcn-amd-amdhsa-gfx950.s k_encode,k_fused
+        (a third argument: the name prefixes of the kernels to compare, for another translation unit)
 
 Kernels are matched by their demangled base name and, for templates, their arguments without the trailing `false` of the
 unbanked instantiations (a build from before the banked forms has no such argument; the `true` ones are listed, not compared).
@@ -17,7 +19,7 @@ import sys
 def kernels(path):
     text = open(path).read()
     out = {}
-    for m in re.finditer(r"^(_Z\w+):[^\n]*\n(.*?)^\s*s_endpgm", text, re.S | re.M):
+    for m in re.finditer(r"^(_Z\w+|k_\w+):[^\n]*\n(.*?)^\s*s_endpgm", text, re.S | re.M):   # (k_...: an extern "C" kernel)
         name, body = m.group(1), m.group(2)
         meta = re.search(r"\.amdhsa_kernel %s\n(.*?)\.end_amdhsa_kernel" % re.escape(name), text, re.S)
         if not meta:
@@ -40,8 +42,8 @@ def demangle(names):
 
 def key(dem, new):
     """k_associate_hard<4>(AssocParams, int) and k_associate_hard<4, false>(AssocArgs<false>, int) -> ('k_associate_hard', '4')"""
-    m = re.search(r"(k_\w+)(?:<([^>]*)>)?\(", dem)
-    if not m or not m.group(1).startswith(("k_associate", "k_assoc_prefix", "k_knn5")):
+    m = re.search(r"(k_\w+)(?:<([^>]*)>)?(?:\(|$)", dem)
+    if not m or not m.group(1).startswith(PREFIXES):
         return None
     args = [a.strip() for a in (m.group(2) or "").split(",") if a.strip()]
     if args and args[-1] in ("false", "true"):           # (an old build from before the banked forms has no such argument)
@@ -51,7 +53,13 @@ def key(dem, new):
     return (m.group(1), ",".join(args))
 
 
+PREFIXES = ("k_associate", "k_assoc_prefix", "k_knn5")
+
+
 def main():
+    global PREFIXES
+    if len(sys.argv) > 3:   # another translation unit's kernels: a comma-separated list of name prefixes, e.g. k_encode
+        PREFIXES = tuple(sys.argv[3].split(","))
     old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
     dold, dnew = demangle(list(old)), demangle(list(new))
     kold = {key(dold[n], False): n for n in old if key(dold[n], False)}
