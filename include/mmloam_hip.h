@@ -196,6 +196,38 @@ int mml_world_map_add(mml_ctx* ctx, int first_slot, int count, const int* map_of
 int mml_world_map_size(mml_ctx* ctx, int map /* -1: all */, long* n_voxels);
 int mml_world_map_download(mml_ctx* ctx, int map, float* out_xyzi, int* out_count /* may be NULL */, long capacity, long* n_voxels);
 
+/* Surfel maps: per-voxel scatter, normals and planarity on the device, opt-in per context.  mml_world_map_create_opts with
+ * flags = MML_WM_SURFELS creates a world map whose table holds 12 floats of moments per position beside the sum and the count,
+ * 76 bytes per position instead of 28; flags = 0 IS mml_world_map_create (the same code path, the same 28 bytes, every download
+ * byte-identical); unknown flag bits: MML_ERR_INVALID.  Every other call works on both kinds; an add into a surfel map keeps the
+ * refusal point, the single host synchronisation and the batching guarantee of mml_world_map_add, now over the moment bytes too,
+ * and needs no scratch beyond the 52 bytes per point (0 new bytes per point; one float4 origin per slot in the call's table
+ * block).  _reset of one map carries the other maps' moments over.  The arithmetic, csrc/world_map_key.h (host and device):
+ *   voxel centre  per axis c = ((float)i + 0.5f) * leaf in float, i the voxel index; offset d = w - c in float, w the world point;
+ *   view vector   v = o - w per axis in float, o = ((float)T[3], (float)T[7], (float)T[11]) the sensor origin of the point's slot;
+ *   moments       12 floats, three float4: (sdx, sdy, sdz, vx) (sxx, sxy, sxz, vy) (syy, syz, szz, vz).  One point: sd += d per
+ *                 axis; the six products dx*dx, dx*dy, dx*dz, dy*dy, dy*dz, dz*dz, each rounded to float and then added; v +=
+ *                 v_point per axis.  The points of a voxel in the order of the sums (call, slot, fused point order), each add
+ *                 starting from the stored value;
+ *   covariance    of a voxel of n >= 3 points, in double: nd = (double)n, m_a = (double)sd_a / nd, C_ab = (double)s_ab / nd -
+ *                 m_a * m_b; Eigen's 3x3 self-adjoint solver as restated in csrc/eig3_dev.h (what mml_model_fit5's MML_FIT_EIG3
+ *                 runs) on m00 = Cxx, m10 = Cxy, m11 = Cyy, m20 = Cxz, m21 = Cyz, m22 = Czz;
+ *   surfel        8 floats: nx ny nz = (float) of the eigenvector of ev[0] as the solver returns it, all three components negated
+ *                 when (n.x*V.x + n.y*V.y) + n.z*V.z < 0 -- the dot product in double of the solver's vector and the stored view
+ *                 sum V; a dot of exactly 0 leaves the vector as it is --; l0 l1 l2 = (float)ev[0..2], ascending, as computed
+ *                 (values slightly below 0 from rounding are reported, not clamped); planarity = (float)((ev1 - ev0) / ev2) and
+ *                 linearity = (float)((ev2 - ev1) / ev2), in double, both 0 when ev2 <= 0.  A voxel of n < 3 points: eight zeros.
+ * mml_world_map_download_moments: the raw accumulators, 12 floats per voxel in the order above -- what an NDT or GICP user
+ * builds a covariance from.  mml_world_map_download_surfels: the 8-float records, one lane per voxel.  Both return the voxels in
+ * the ascending key order of mml_world_map_download (row i of all three is the same voxel) through the same collect, sort and
+ * gather chain; out == NULL is the sizing call; MML_ERR_CAPACITY when `capacity` (voxels) is below the count; MML_ERR_STATE,
+ * naming the flag, on a map created without MML_WM_SURFELS; MML_ERR_INVALID for a NULL context, a NULL n_voxels or a map outside
+ * [0, n_maps). */
+#define MML_WM_SURFELS 1u
+int mml_world_map_create_opts(mml_ctx* ctx, int n_maps /* 1..1024 */, float leaf, long capacity_voxels, unsigned flags);
+int mml_world_map_download_moments(mml_ctx* ctx, int map, float* out /* n x 12 */, long capacity, long* n_voxels);
+int mml_world_map_download_surfels(mml_ctx* ctx, int map, float* out /* n x 8 */, long capacity, long* n_voxels);
+
 /* The feature node's own output: the six PointXYZINormal clouds of one union_cloud message (union-cloud/msg/union_cloud.msg:4-9)
  * for `count` extracted slots.  Cloud index k, in the message's order: 0 velo_corner, 1 velo_surface, 2 velo_combine,
  * 3 livox_corner, 4 livox_surface, 5 livox_combine.  Records are the 48-byte records of mml_scan_download_pointxyzinormal

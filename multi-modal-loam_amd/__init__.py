@@ -215,6 +215,13 @@ WORLD_MAP_ARGTYPES = {
     "mml_world_map_size": [C.c_void_p, C.c_int, C.c_void_p],
     "mml_world_map_download": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p],
 }
+# ... and the three of a surfel map (include/mmloam_hip.h, "Surfel maps")
+MML_WM_SURFELS = 1
+WORLD_MAP_SURFEL_ARGTYPES = {
+    "mml_world_map_create_opts": [C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_uint],
+    "mml_world_map_download_moments": [C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_void_p],
+    "mml_world_map_download_surfels": [C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_void_p],
+}
 
 
 def build(force=False):
@@ -408,6 +415,10 @@ def lib():
             L.mml_scan_upload_wire_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p] + wire[:7] + [C.c_void_p] + wire[7:]
         if hasattr(L, "mml_world_map_create"):
             for name, args in WORLD_MAP_ARGTYPES.items():
+                getattr(L, name).restype = C.c_int
+                getattr(L, name).argtypes = args
+        if hasattr(L, "mml_world_map_create_opts"):
+            for name, args in WORLD_MAP_SURFEL_ARGTYPES.items():
                 getattr(L, name).restype = C.c_int
                 getattr(L, name).argtypes = args
         _lib = L
@@ -1236,9 +1247,32 @@ class Context:
         return out[:n.value].copy()
 
     # ---- the world map: the registered clouds voxel-merged on the device, n maps (include/mmloam_hip.h, "The world map") ----
-    def world_map_create(self, n_maps, leaf, capacity_voxels):
-        """n_maps (1 .. 1024) voxel maps of leaf size `leaf` in one table of capacity_voxels voxels; once per context."""
-        self._ck(lib().mml_world_map_create(self._h, int(n_maps), float(leaf), int(capacity_voxels)))
+    def world_map_create(self, n_maps, leaf, capacity_voxels, surfels=False):
+        """n_maps (1 .. 1024) voxel maps of leaf size `leaf` in one table of capacity_voxels voxels; once per context.
+        surfels=True: a surfel map (MML_WM_SURFELS), 76 bytes per table position instead of 28; world_map_moments and
+        world_map_surfels read it."""
+        if surfels:
+            self._ck(lib().mml_world_map_create_opts(self._h, int(n_maps), float(leaf), int(capacity_voxels), MML_WM_SURFELS))
+        else:
+            self._ck(lib().mml_world_map_create(self._h, int(n_maps), float(leaf), int(capacity_voxels)))
+
+    def _world_map_rows(self, f, map, width):
+        n = C.c_long(0)
+        self._ck(f(self._h, int(map), None, 0, C.byref(n)))
+        out = np.zeros((max(n.value, 1), width), np.float32)
+        if n.value:
+            self._ck(f(self._h, int(map), _p(out), n.value, C.byref(n)))
+        return out[:n.value]
+
+    def world_map_moments(self, map):
+        """The raw accumulators of a surfel map's voxels in the order of world_map_download: (n, 12) float32
+        sdx sdy sdz vx | sxx sxy sxz vy | syy syz szz vz (offsets from the voxel's centre, their products, the view sum)."""
+        return self._world_map_rows(lib().mml_world_map_download_moments, map, 12)
+
+    def world_map_surfels(self, map):
+        """The surfels of a surfel map's voxels in the order of world_map_download: (n, 8) float32 nx ny nz | l0 l1 l2 |
+        planarity linearity; eight zeros for a voxel of fewer than 3 points."""
+        return self._world_map_rows(lib().mml_world_map_download_surfels, map, 8)
 
     def world_map_destroy(self):
         self._ck(lib().mml_world_map_destroy(self._h))

@@ -381,10 +381,14 @@ struct mml_ctx {
         long budget = MML_BANK_GLOBAL_INCREMENT_BUDGET;  // points per chunk (mml_debug_bank_global_increment_budget)
     } bank_cube;
     // the world map (world_map.hip, mml_world_map_*): one open-addressing table of voxels for n maps, a group of its own.
-    // 28 bytes per table position (key, float4 sum, count), 2 .. 4 positions per voxel of capacity; the add chain's scratch is 52
-    // bytes per point of the call's bound (count x NT), grow-only, beside rocPRIM's temporary storage and the call's table block
+    // 28 bytes per table position (key, float4 sum, count), 2 .. 4 positions per voxel of capacity; a surfel map (MML_WM_SURFELS)
+    // holds three float4 of moments per position more, 76 bytes.  The add chain's scratch is 52 bytes per point of the call's bound
+    // (count x NT), grow-only, for both kinds, beside rocPRIM's temporary storage and the call's table block (a surfel map: 16
+    // bytes per slot more, the sensor origins)
     struct WorldMap {
         int n_maps = 0;                      // 0: no world map
+        bool surfels = false;                // MML_WM_SURFELS: mom[] allocated
+        float4* mom[3] = {nullptr, nullptr, nullptr};  // slots each: (sdx sdy sdz vx) (sxx sxy sxz vy) (syy syz szz vz), world_map_key.h
         float leaf = 0.f;
         long capacity = 0;                   // voxels, all maps together
         unsigned long long slots = 0;        // table positions: the next power of two >= 2 x capacity
@@ -392,7 +396,7 @@ struct mml_ctx {
         float4* sum = nullptr;               // slots: x, y, z, intensity
         int* count = nullptr;                // slots
         int* map_n = nullptr;                // n_maps + 1: voxels per map, then the total
-        MmlGroup mem;                        // owns the four
+        MmlGroup mem;                        // owns the four, and mom[] of a surfel map
         MmlStaging<char, false> scratch;     // the calls' scratch (one call at a time)
         MmlStaging<char, false> tmp;         // rocPRIM temporary storage
         MmlStaging<char> tab;                // a call's slot rows and counters: device block and pinned twin
@@ -405,6 +409,8 @@ struct mml_ctx {
             sum = nullptr;
             count = nullptr;
             map_n = nullptr;
+            mom[0] = mom[1] = mom[2] = nullptr;
+            surfels = false;
             n_maps = 0;
         }
     } world;

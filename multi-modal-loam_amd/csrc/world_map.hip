@@ -20,6 +20,18 @@
 //                  stores -- keys inside a call are distinct, one lane owns a voxel; the per-map counts and the total follow
 // Scratch per point of B: 16 (world point) + 2 x 8 (keys in / out) + 2 x 4 (ordinals in / out) + 3 x 4 (run head, scan, hit) = 52
 // bytes, grow-only, and rocPRIM's temporary storage beside it.
+//
+// A SURFEL MAP (mml_world_map_create_opts, MML_WM_SURFELS) holds three float4 of moments per position beside the sum and the
+// count (world_map_key.h, MmlWmMoments: the offsets from the voxel's centre, their six products, the view vectors), 76 bytes per
+// position instead of 28.  Its add runs the same chain with k_wm_insert<true>: the lane carries the moments beside the sums --
+// loaded on a hit, zero on a claim, plain stores at the end -- with the voxel's centre from the key it holds and the point's
+// sensor origin from the call's origin table: a point's ordinal is off_i + g and every slot that takes part owns NT ordinals, so
+// ordinal / NT is the slot's place among them.  NEW SCRATCH PER POINT: 0 bytes (52 as for a plain map); the call's table block
+// grows by one float4 origin per slot, written by the host from the pose (mml_wm_origin).  The moments of a position are read
+// only after its key is claimed and its accumulators are stored, so neither reset(-1) nor create clears them.
+// mml_world_map_download, _download_moments and _download_surfels share one collect, sort and gather chain (wm_download); the
+// surfel gather is one lane per voxel: the covariance in double (mml_wm_covariance), eig3_sym register-only, the normal turned
+// towards the view sum.
 #include <limits.h>
 #include <math.h>
 #include <string.h>
@@ -30,6 +42,8 @@
 #include "world_map_key.h"
 
 namespace {
+#include "eig3_dev.h"
+
 // one slot of the call, read through scalar loads (blockIdx.y)
 struct WmRow {
     double T[16];  // T_wl, row-major
@@ -118,11 +132,26 @@ __global__ __launch_bounds__(256) void k_wm_lookup(const unsigned long long* __r
     wm_count(counters + WM_MISSES, head && at < 0);
 }
 
+// what k_wm_insert<true> takes beside the arguments of a plain map's insert; <false> takes nothing
+template <bool Surfels>
+struct WmMomentArgs {};
+template <>
+struct WmMomentArgs<true> {
+    float4 *m0, *m1, *m2;   // the table's three moment arrays
+    const float4* origin;   // the sensor origin of the call's i-th slot that takes part
+    float leaf;
+    int nt;                 // ordinals per slot that takes part (the context's NT)
+};
+__device__ __forceinline__ MmlWmMoments wm_moments(const float4& a, const float4& b, const float4& c) {
+    return MmlWmMoments{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w};
+}
+
+template <bool Surfels>
 __global__ __launch_bounds__(256) void k_wm_insert(const unsigned long long* __restrict__ keys, const unsigned* __restrict__ vals,
                                                    const int* __restrict__ flag, const int* __restrict__ hit, int n,
                                                    const float4* __restrict__ pts, unsigned long long* __restrict__ tab,
                                                    unsigned long long slots, float4* __restrict__ sum, int* __restrict__ count,
-                                                   int* __restrict__ map_n, int n_maps) {
+                                                   int* __restrict__ map_n, int n_maps, WmMomentArgs<Surfels> S) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     const bool head = s < n && flag[s];
     bool fresh = false;
@@ -130,6 +159,7 @@ __global__ __launch_bounds__(256) void k_wm_insert(const unsigned long long* __r
         const unsigned long long key = keys[s];
         long long at = hit[s];
         MmlWmAcc a = {0.f, 0.f, 0.f, 0.f, 0};
+        MmlWmMoments m = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (at < 0) {
             fresh = true;
             at = wm_claim(tab, slots, key);
@@ -141,11 +171,28 @@ __global__ __launch_bounds__(256) void k_wm_insert(const unsigned long long* __r
             a.z = v.z;
             a.w = v.w;
             a.n = count[at];
+            if constexpr (Surfels) m = wm_moments(S.m0[at], S.m1[at], S.m2[at]);
         }
         if (at >= 0) {  // (always: the host refused the call that would have filled the table)
-            for (int e = s; e < n && keys[e] == key; ++e) {
-                const float4 p = pts[vals[e]];
-                mml_wm_add(a, p.x, p.y, p.z, p.w);
+            if constexpr (Surfels) {
+                int map, i, j, k;
+                mml_wm_unkey(key, map, i, j, k);
+                const float cx = mml_wm_centre(i, S.leaf), cy = mml_wm_centre(j, S.leaf), cz = mml_wm_centre(k, S.leaf);
+                for (int e = s; e < n && keys[e] == key; ++e) {
+                    const unsigned v = vals[e];
+                    const float4 p = pts[v];
+                    const float4 o = S.origin[v / (unsigned)S.nt];
+                    mml_wm_add(a, p.x, p.y, p.z, p.w);
+                    mml_wm_add_moments(m, p.x, p.y, p.z, cx, cy, cz, o.x, o.y, o.z);
+                }
+                S.m0[at] = make_float4(m.sdx, m.sdy, m.sdz, m.vx);
+                S.m1[at] = make_float4(m.sxx, m.sxy, m.sxz, m.vy);
+                S.m2[at] = make_float4(m.syy, m.syz, m.szz, m.vz);
+            } else {
+                for (int e = s; e < n && keys[e] == key; ++e) {
+                    const float4 p = pts[vals[e]];
+                    mml_wm_add(a, p.x, p.y, p.z, p.w);
+                }
             }
             sum[at] = make_float4(a.x, a.y, a.z, a.w);
             count[at] = a.n;
@@ -181,19 +228,69 @@ __global__ __launch_bounds__(256) void k_wm_centroids(const unsigned* __restrict
     out[i] = make_float4(c[0], c[1], c[2], c[3]);
     out_n[i] = a.n;
 }
+// the three moment arrays of a surfel map (or of a reset's scratch copy); null in a plain map
+struct WmMom {
+    float4 *m0, *m1, *m2;
+};
+// download_moments: the raw accumulators of the sorted positions, 12 floats each
+__global__ __launch_bounds__(256) void k_wm_moments(const unsigned* __restrict__ vals, int n, WmMom M, float4* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const unsigned at = vals[i];
+    out[3 * (size_t)i] = M.m0[at];
+    out[3 * (size_t)i + 1] = M.m1[at];
+    out[3 * (size_t)i + 2] = M.m2[at];
+}
+// download_surfels: one lane per sorted position.  8 floats: the normal (the eigenvector of the smallest eigenvalue, turned
+// towards the view sum), the eigenvalues ascending, planarity and linearity; eight zeros for a voxel of fewer than 3 points.
+__global__ __launch_bounds__(256) void k_wm_surfels(const unsigned* __restrict__ vals, int n, WmMom M, const int* __restrict__ count,
+                                                    float4* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const unsigned at = vals[i];
+    const int np = count[at];
+    float4 o0 = make_float4(0.f, 0.f, 0.f, 0.f), o1 = o0;
+    if (np >= 3) {
+        const MmlWmMoments m = wm_moments(M.m0[at], M.m1[at], M.m2[at]);
+        double c[6], ev[3], v2[3], v0[3];
+        mml_wm_covariance(m, np, c);
+        eig3_sym(c[0], c[1], c[2], c[3], c[4], c[5], ev, v2, v0);
+        const double dot = (v0[0] * (double)m.vx + v0[1] * (double)m.vy) + v0[2] * (double)m.vz;
+        if (dot < 0.0) {
+            v0[0] = -v0[0];
+            v0[1] = -v0[1];
+            v0[2] = -v0[2];
+        }
+        double planarity = 0.0, linearity = 0.0;
+        if (!(ev[2] <= 0.0)) {
+            planarity = (ev[1] - ev[0]) / ev[2];
+            linearity = (ev[2] - ev[1]) / ev[2];
+        }
+        o0 = make_float4((float)v0[0], (float)v0[1], (float)v0[2], (float)ev[0]);
+        o1 = make_float4((float)ev[1], (float)ev[2], (float)planarity, (float)linearity);
+    }
+    out[2 * (size_t)i] = o0;
+    out[2 * (size_t)i + 1] = o1;
+}
 // reset of one map: the survivors' accumulators beside their keys, before the table is cleared ...
 __global__ __launch_bounds__(256) void k_wm_take(const unsigned* __restrict__ vals, int n, const float4* __restrict__ sum,
-                                                 const int* __restrict__ count, float4* __restrict__ s_sum, int* __restrict__ s_n) {
+                                                 const int* __restrict__ count, float4* __restrict__ s_sum, int* __restrict__ s_n, WmMom M,
+                                                 WmMom S) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     s_sum[i] = sum[vals[i]];
     s_n[i] = count[vals[i]];
+    if (M.m0) {  // (a surfel map: the whole launch)
+        S.m0[i] = M.m0[vals[i]];
+        S.m1[i] = M.m1[vals[i]];
+        S.m2[i] = M.m2[vals[i]];
+    }
 }
 // ... and back into the cleared table; lane 0 writes the counts of the map that went and the new total
 __global__ __launch_bounds__(256) void k_wm_reinsert(const unsigned long long* __restrict__ keys, int n, const float4* __restrict__ s_sum,
                                                      const int* __restrict__ s_n, unsigned long long* __restrict__ tab,
                                                      unsigned long long slots, float4* __restrict__ sum, int* __restrict__ count,
-                                                     int* __restrict__ map_n, int n_maps, int map) {
+                                                     int* __restrict__ map_n, int n_maps, int map, WmMom M, WmMom S) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i == 0) {
         map_n[map] = 0;
@@ -204,6 +301,11 @@ __global__ __launch_bounds__(256) void k_wm_reinsert(const unsigned long long* _
     if (at < 0) return;
     sum[at] = s_sum[i];
     count[at] = s_n[i];
+    if (M.m0) {
+        M.m0[at] = S.m0[i];
+        M.m1[at] = S.m1[i];
+        M.m2[at] = S.m2[i];
+    }
 }
 
 int wm_enter(mml_ctx* ctx, const char* who) {
@@ -219,20 +321,28 @@ int wm_clear(mml_ctx* ctx, hipStream_t s) {
     return MML_OK;
 }
 unsigned wm_blocks(size_t n) { return (unsigned)((n + 255) / 256); }
-}  // namespace
+WmMom wm_mom(const mml_ctx::WorldMap& W) { return WmMom{W.mom[0], W.mom[1], W.mom[2]}; }
 
-int mml_world_map_create(mml_ctx* ctx, int n_maps, float leaf, long capacity_voxels) {
+// mml_world_map_create and _create_opts
+int wm_create(mml_ctx* ctx, int n_maps, float leaf, long capacity_voxels, unsigned flags) {
     if (!ctx) return MML_ERR_INVALID;
     MML_REQUIRE(n_maps >= 1 && n_maps <= MML_WM_MAPS_MAX, MML_ERR_INVALID, "mml_world_map_create: n_maps outside 1..1024");
     MML_REQUIRE(isfinite(leaf) && leaf > 0.f, MML_ERR_INVALID, "mml_world_map_create: leaf must be finite and positive");
     MML_REQUIRE(capacity_voxels >= 1 && capacity_voxels <= (1L << 29), MML_ERR_INVALID, "mml_world_map_create: capacity_voxels outside 1..2^29");
+    if (flags & ~MML_WM_SURFELS) return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_create_opts: unknown flag bits 0x%x (MML_WM_SURFELS is 0x%x)", flags & ~MML_WM_SURFELS, MML_WM_SURFELS);
     mml_ctx::WorldMap& W = ctx->world;
     if (W.n_maps) return mml_refuse(ctx, MML_ERR_STATE, "mml_world_map_create: the context has a world map of %d maps already", W.n_maps);
     MML_HIP(hipSetDevice(ctx->device));
     const unsigned long long slots = mml_wm_table_slots(capacity_voxels);
-    int rc = W.mem.reserve(ctx, {mml_part(W.keys, (size_t)slots), mml_part(W.sum, (size_t)slots), mml_part(W.count, (size_t)slots),
-                                 mml_part(W.map_n, (size_t)n_maps + 1)});
+    const bool surfels = (flags & MML_WM_SURFELS) != 0;
+    // (a plain map allocates what it always did)
+    int rc = surfels ? W.mem.reserve(ctx, {mml_part(W.keys, (size_t)slots), mml_part(W.sum, (size_t)slots), mml_part(W.count, (size_t)slots),
+                                           mml_part(W.map_n, (size_t)n_maps + 1), mml_part(W.mom[0], (size_t)slots),
+                                           mml_part(W.mom[1], (size_t)slots), mml_part(W.mom[2], (size_t)slots)})
+                     : W.mem.reserve(ctx, {mml_part(W.keys, (size_t)slots), mml_part(W.sum, (size_t)slots), mml_part(W.count, (size_t)slots),
+                                           mml_part(W.map_n, (size_t)n_maps + 1)});
     if (rc != MML_OK) return rc;
+    W.surfels = surfels;
     W.n_maps = n_maps;
     W.leaf = leaf;
     W.capacity = capacity_voxels;
@@ -242,6 +352,12 @@ int mml_world_map_create(mml_ctx* ctx, int n_maps, float leaf, long capacity_vox
     if (rc == MML_OK && hipStreamSynchronize(s) != hipSuccess) rc = mml_refuse(ctx, MML_ERR_HIP, "mml_world_map_create: hipStreamSynchronize failed");
     if (rc != MML_OK) W.release();
     return rc;
+}
+}  // namespace
+
+int mml_world_map_create(mml_ctx* ctx, int n_maps, float leaf, long capacity_voxels) { return wm_create(ctx, n_maps, leaf, capacity_voxels, 0u); }
+int mml_world_map_create_opts(mml_ctx* ctx, int n_maps, float leaf, long capacity_voxels, unsigned flags) {
+    return wm_create(ctx, n_maps, leaf, capacity_voxels, flags);
 }
 
 int mml_world_map_destroy(mml_ctx* ctx) {
@@ -286,19 +402,22 @@ int mml_world_map_reset(mml_ctx* ctx, int map) {
     const MmlField<float4> f_sum = c.take<float4>(m);
     const MmlField<int> f_n = c.take<int>(m);
     const MmlField<int> f_cur = c.take<int>(1);
+    const MmlField<float4> f_mom = c.take<float4>(W.surfels ? 3 * m : 0);  // a surfel map: the survivors' moments, three arrays of m
     rc = W.scratch.reserve(ctx, c.bytes(), s);
     if (rc != MML_OK) return rc;
     char* d = W.scratch.d;
+    const WmMom kept = W.surfels ? WmMom{f_mom.in(d), f_mom.in(d) + m, f_mom.in(d) + 2 * m} : WmMom{nullptr, nullptr, nullptr};
     MML_HIP(hipMemsetAsync(f_cur.in(d), 0, sizeof(int), s));
     if (m) {
         MML_HIP(hipMemsetAsync(f_vals.in(d), 0, f_vals.bytes(), s));  // (every entry a table position, whatever the walk finds)
         hipLaunchKernelGGL(k_wm_collect<true>, dim3(wm_blocks((size_t)W.slots) < 1024 ? wm_blocks((size_t)W.slots) : 1024), dim3(256), 0, s, W.keys,
                            W.slots, map, (int)m, f_cur.in(d), f_keys.in(d), f_vals.in(d));
-        hipLaunchKernelGGL(k_wm_take, dim3(wm_blocks(m)), dim3(256), 0, s, f_vals.in(d), (int)m, W.sum, W.count, f_sum.in(d), f_n.in(d));
+        hipLaunchKernelGGL(k_wm_take, dim3(wm_blocks(m)), dim3(256), 0, s, f_vals.in(d), (int)m, W.sum, W.count, f_sum.in(d), f_n.in(d),
+                           wm_mom(W), kept);
     }
     MML_HIP(hipMemsetAsync(W.keys, 0xff, sizeof(unsigned long long) * W.slots, s));
     hipLaunchKernelGGL(k_wm_reinsert, dim3(m ? wm_blocks(m) : 1), dim3(256), 0, s, f_keys.in(d), (int)m, f_sum.in(d), f_n.in(d), W.keys, W.slots,
-                       W.sum, W.count, W.map_n, W.n_maps, map);
+                       W.sum, W.count, W.map_n, W.n_maps, map, wm_mom(W), kept);
     MML_HIP(hipGetLastError());
     return MML_OK;
 }
@@ -348,6 +467,7 @@ int mml_world_map_add(mml_ctx* ctx, int first_slot, int count, const int* map_of
     MmlCarve<16> t;
     const MmlField<WmRow> f_rows = t.take<WmRow>((size_t)count);
     const MmlField<int> f_cnt = t.take<int>(WM_COUNTERS + 1);  // the counters, and behind them (read-back only) the table's total
+    const MmlField<float4> f_org = t.take<float4>(W.surfels ? (size_t)live : 0);  // a surfel map: the origin of every slot that takes part
     rc = W.tab.reserve(ctx, t.bytes(), s);
     if (rc != MML_OK) return rc;
     // (the pinned twin is free: the last call that used it waited for its read-back, which ran behind its copy down)
@@ -358,7 +478,13 @@ int mml_world_map_add(mml_ctx* ctx, int first_slot, int count, const int* map_of
         memcpy(h_rows[i].T, T_wl + 16 * (size_t)i, sizeof(double) * 16);
         h_rows[i].map = map_of_slot[i];
         h_rows[i].off = off;
-        if (map_of_slot[i] >= 0) off += ctx->NT;
+        if (map_of_slot[i] < 0) continue;
+        if (W.surfels) {  // (off = NT x the slot's place among those that take part: k_wm_insert<true> divides an ordinal by NT)
+            float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+            mml_wm_origin(h_rows[i].T, o.x, o.y, o.z);
+            f_org.in(W.tab.h)[off / ctx->NT] = o;
+        }
+        off += ctx->NT;
     }
     int* h_cnt = f_cnt.in(W.tab.h);
     memset(h_cnt, 0, f_cnt.bytes());
@@ -386,9 +512,13 @@ int mml_world_map_add(mml_ctx* ctx, int first_slot, int count, const int* map_of
     if (total + misses > W.capacity)
         return mml_refuse(ctx, MML_ERR_CAPACITY, "mml_world_map_add: %ld voxels held + %ld new ones exceed capacity_voxels %ld; nothing was added", total,
                           misses, W.capacity);
-    if (h_cnt[WM_DISTINCT])
-        hipLaunchKernelGGL(k_wm_insert, dim3(wm_blocks(n)), dim3(256), 0, s, keys2, vals2, f_flag.in(d), f_hit.in(d), (int)n, f_pts.in(d), W.keys,
-                           W.slots, W.sum, W.count, W.map_n, W.n_maps);
+    if (h_cnt[WM_DISTINCT] && W.surfels)
+        hipLaunchKernelGGL(k_wm_insert<true>, dim3(wm_blocks(n)), dim3(256), 0, s, keys2, vals2, f_flag.in(d), f_hit.in(d), (int)n, f_pts.in(d), W.keys,
+                           W.slots, W.sum, W.count, W.map_n, W.n_maps,
+                           WmMomentArgs<true>{W.mom[0], W.mom[1], W.mom[2], f_org.in(W.tab.d), W.leaf, ctx->NT});
+    else if (h_cnt[WM_DISTINCT])
+        hipLaunchKernelGGL(k_wm_insert<false>, dim3(wm_blocks(n)), dim3(256), 0, s, keys2, vals2, f_flag.in(d), f_hit.in(d), (int)n, f_pts.in(d), W.keys,
+                           W.slots, W.sum, W.count, W.map_n, W.n_maps, WmMomentArgs<false>{});
     MML_HIP(hipGetLastError());
     if (info) {
         info->n_points = h_cnt[WM_POINTS];
@@ -402,21 +532,27 @@ int mml_world_map_add(mml_ctx* ctx, int first_slot, int count, const int* map_of
     return MML_OK;
 }
 
-int mml_world_map_download(mml_ctx* ctx, int map, float* out_xyzi, int* out_count, long capacity, long* n_voxels) {
-    int rc = wm_enter(ctx, "mml_world_map_download");
+namespace {
+// The three downloads: the occupied positions of the map collected, sorted by key and gathered -- the chain is this function's
+// and nobody else's; `what` chooses the gather kernel and the floats per voxel.
+enum WmWhat { WM_CENTROIDS = 4, WM_MOMENTS = 12, WM_SURFELS = 8 };  // (the value: floats per voxel)
+int wm_download(mml_ctx* ctx, const char* who, WmWhat what, int map, float* out, int* out_count, long capacity, long* n_voxels) {
+    int rc = wm_enter(ctx, who);
     if (rc != MML_OK) return rc;
     mml_ctx::WorldMap& W = ctx->world;
-    MML_REQUIRE(n_voxels != nullptr, MML_ERR_INVALID, "mml_world_map_download: null n_voxels");
-    if (map < 0 || map >= W.n_maps) return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_download: map %d outside [0, %d)", map, W.n_maps);
+    if (what != WM_CENTROIDS && !W.surfels)
+        return mml_refuse(ctx, MML_ERR_STATE, "%s: the world map was created without MML_WM_SURFELS (mml_world_map_create_opts)", who);
+    if (!n_voxels) return mml_refuse(ctx, MML_ERR_INVALID, "%s: null n_voxels", who);
+    if (map < 0 || map >= W.n_maps) return mml_refuse(ctx, MML_ERR_INVALID, "%s: map %d outside [0, %d)", who, map, W.n_maps);
     rc = mml_world_map_size(ctx, map, n_voxels);
-    if (rc != MML_OK || !out_xyzi || *n_voxels == 0) return rc;
-    if (capacity < *n_voxels) return mml_refuse(ctx, MML_ERR_CAPACITY, "mml_world_map_download: map %d holds %ld voxels, capacity is %ld", map, *n_voxels, capacity);
+    if (rc != MML_OK || !out || *n_voxels == 0) return rc;
+    if (capacity < *n_voxels) return mml_refuse(ctx, MML_ERR_CAPACITY, "%s: map %d holds %ld voxels, capacity is %ld", who, map, *n_voxels, capacity);
     hipStream_t s = MML_STREAM(ctx);
     const size_t n = (size_t)*n_voxels;
     MmlCarve<16> c;
     const MmlField<unsigned long long> f_keys = c.take<unsigned long long>(2 * n);
     const MmlField<unsigned> f_vals = c.take<unsigned>(2 * n);
-    const MmlField<float4> f_out = c.take<float4>(n);
+    const MmlField<float4> f_out = c.take<float4>((size_t)what / 4 * n);
     const MmlField<int> f_n = c.take<int>(n);
     const MmlField<int> f_cur = c.take<int>(1);
     rc = W.scratch.reserve(ctx, c.bytes(), s);
@@ -432,10 +568,26 @@ int mml_world_map_download(mml_ctx* ctx, int map, float* out_xyzi, int* out_coun
                        map, (int)n, f_cur.in(d), keys, vals);
     rc = mml_sort_pairs(ctx, W.tmp, keys, keys + n, vals, vals + n, n, MML_WM_MAP_SHIFT, s);  // (the map number is the same in all)
     if (rc != MML_OK) return rc;
-    hipLaunchKernelGGL(k_wm_centroids, dim3(wm_blocks(n)), dim3(256), 0, s, vals + n, (int)n, W.sum, W.count, f_out.in(d), f_n.in(d));
+    if (what == WM_CENTROIDS)
+        hipLaunchKernelGGL(k_wm_centroids, dim3(wm_blocks(n)), dim3(256), 0, s, vals + n, (int)n, W.sum, W.count, f_out.in(d), f_n.in(d));
+    else if (what == WM_MOMENTS)
+        hipLaunchKernelGGL(k_wm_moments, dim3(wm_blocks(n)), dim3(256), 0, s, vals + n, (int)n, wm_mom(W), f_out.in(d));
+    else
+        hipLaunchKernelGGL(k_wm_surfels, dim3(wm_blocks(n)), dim3(256), 0, s, vals + n, (int)n, wm_mom(W), W.count, f_out.in(d));
     MML_HIP(hipGetLastError());
-    MML_HIP(hipMemcpyAsync(out_xyzi, f_out.in(d), sizeof(float4) * n, hipMemcpyDeviceToHost, s));
+    MML_HIP(hipMemcpyAsync(out, f_out.in(d), f_out.bytes(), hipMemcpyDeviceToHost, s));
     if (out_count) MML_HIP(hipMemcpyAsync(out_count, f_n.in(d), sizeof(int) * n, hipMemcpyDeviceToHost, s));
     MML_HIP(hipStreamSynchronize(s));
     return MML_OK;
+}
+}  // namespace
+
+int mml_world_map_download(mml_ctx* ctx, int map, float* out_xyzi, int* out_count, long capacity, long* n_voxels) {
+    return wm_download(ctx, "mml_world_map_download", WM_CENTROIDS, map, out_xyzi, out_count, capacity, n_voxels);
+}
+int mml_world_map_download_moments(mml_ctx* ctx, int map, float* out, long capacity, long* n_voxels) {
+    return wm_download(ctx, "mml_world_map_download_moments", WM_MOMENTS, map, out, nullptr, capacity, n_voxels);
+}
+int mml_world_map_download_surfels(mml_ctx* ctx, int map, float* out, long capacity, long* n_voxels) {
+    return wm_download(ctx, "mml_world_map_download_surfels", WM_SURFELS, map, out, nullptr, capacity, n_voxels);
 }

@@ -1,8 +1,9 @@
 // world_map_key.h -- the one definition of the world map's arithmetic (world_map.hip, mml_world_map_*): the world point, the voxel
-// index, the 64-bit key, the hash of a key to a table position and the per-voxel accumulator.  Host and device, no other header
+// index, the 64-bit key, the hash of a key to a table position, the per-voxel accumulator and, for a surfel map, the per-voxel
+// moments and the covariance they give (the eigen-decomposition of it is eig3_dev.h's, device only).  Host and device, no other header
 // of the project needed: a host program can include this file and check the arithmetic on its own
 // (tests/cpp/world_map_key_check.cpp), or compute which keys collide in a table of a given size.
-// Adds, multiplies and one divide only, none of them contracted: every translation unit that includes this file is built with
+// Adds, multiplies and divides only, none of them contracted: every translation unit that includes this file is built with
 // -ffp-contract=off (the Makefile's FLAGS; the host check passes it too).
 #ifndef MML_WORLD_MAP_KEY_H
 #define MML_WORLD_MAP_KEY_H
@@ -111,6 +112,55 @@ MML_WM_HD void mml_wm_centroid(const MmlWmAcc& a, float out[4]) {
     out[1] = a.y / c;
     out[2] = a.z / c;
     out[3] = a.w / c;
+}
+
+// ---- surfel maps (MML_WM_SURFELS): the second moments of a voxel's points about the voxel's centre, and their view sum ----
+// the centre of voxel index i (what mml_wm_axis returned) on one axis: (float)i + 0.5f is exact for |i| <= 2^17, one rounding
+MML_WM_HD float mml_wm_centre(int i, float leaf) { return ((float)i + 0.5f) * leaf; }
+// the sensor origin of a slot: the translation of its row-major pose, each rounded to float
+MML_WM_HD void mml_wm_origin(const double* T, float& ox, float& oy, float& oz) {
+    ox = (float)T[3];
+    oy = (float)T[7];
+    oz = (float)T[11];
+}
+// One voxel, 12 floats as three float4 of the table: the sums of the offsets d = w - centre, of their six products and of the
+// view vectors v = origin - w.
+struct MmlWmMoments {
+    float sdx, sdy, sdz, vx;
+    float sxx, sxy, sxz, vy;
+    float syy, syz, szz, vz;
+};
+// One world point (wx, wy, wz) of the voxel centred at (cx, cy, cz), seen from (ox, oy, oz): every difference and every product
+// is rounded to float on its own and then added, in the order written.
+MML_WM_HD void mml_wm_add_moments(MmlWmMoments& m, float wx, float wy, float wz, float cx, float cy, float cz, float ox, float oy,
+                                  float oz) {
+    const float dx = wx - cx, dy = wy - cy, dz = wz - cz;
+    m.sdx += dx;
+    m.sdy += dy;
+    m.sdz += dz;
+    const float xx = dx * dx, xy = dx * dy, xz = dx * dz, yy = dy * dy, yz = dy * dz, zz = dz * dz;
+    m.sxx += xx;
+    m.sxy += xy;
+    m.sxz += xz;
+    m.syy += yy;
+    m.syz += yz;
+    m.szz += zz;
+    const float px = ox - wx, py = oy - wy, pz = oz - wz;
+    m.vx += px;
+    m.vy += py;
+    m.vz += pz;
+}
+// The covariance of a voxel of n points about its mean, in double, as the lower triangle the eigen-solver takes:
+// c = {Cxx, Cxy, Cyy, Cxz, Cyz, Czz} = m00 m10 m11 m20 m21 m22, C_ab = s_ab / n - m_a m_b with m_a = sd_a / n.
+MML_WM_HD void mml_wm_covariance(const MmlWmMoments& m, int n, double c[6]) {
+    const double nd = (double)n;
+    const double mx = (double)m.sdx / nd, my = (double)m.sdy / nd, mz = (double)m.sdz / nd;
+    c[0] = (double)m.sxx / nd - mx * mx;
+    c[1] = (double)m.sxy / nd - mx * my;
+    c[2] = (double)m.syy / nd - my * my;
+    c[3] = (double)m.sxz / nd - mx * mz;
+    c[4] = (double)m.syz / nd - my * mz;
+    c[5] = (double)m.szz / nd - mz * mz;
 }
 
 #endif

@@ -125,8 +125,10 @@ class Context {
 // x, y, z, intensity = the centroid, curvature = the voxel's point count, everything else as in a default-constructed point.
 class WorldMap {
    public:
-    WorldMap(Context& ctx, int n_maps, float leaf, long capacity_voxels) : ctx_(ctx) {
-        check(ctx_.get(), mml_world_map_create(ctx_.get(), n_maps, leaf, capacity_voxels), "mml_world_map_create");
+    // surfels = true: a surfel map (MML_WM_SURFELS), 76 bytes per table position instead of 28; moments() and surfels() read it
+    WorldMap(Context& ctx, int n_maps, float leaf, long capacity_voxels, bool surfels = false) : ctx_(ctx) {
+        check(ctx_.get(), mml_world_map_create_opts(ctx_.get(), n_maps, leaf, capacity_voxels, surfels ? MML_WM_SURFELS : 0u),
+              "mml_world_map_create_opts");
     }
     ~WorldMap() { mml_world_map_destroy(ctx_.get()); }
     WorldMap(const WorldMap&) = delete;
@@ -158,8 +160,19 @@ class WorldMap {
         }
         return n;
     }
+    // a surfel map's voxels in the order of download(): 12 floats each (sdx sdy sdz vx | sxx sxy sxz vy | syy syz szz vz) ...
+    std::vector<float> moments(int map) { return rows(map, 12, mml_world_map_download_moments, "mml_world_map_download_moments"); }
+    // ... and 8 floats each: nx ny nz | l0 l1 l2 | planarity linearity (eight zeros for a voxel of fewer than 3 points)
+    std::vector<float> surfels(int map) { return rows(map, 8, mml_world_map_download_surfels, "mml_world_map_download_surfels"); }
 
    private:
+    std::vector<float> rows(int map, int width, int (*call)(mml_ctx*, int, float*, long, long*), const char* who) {
+        long n = 0;
+        check(ctx_.get(), call(ctx_.get(), map, nullptr, 0, &n), who);
+        std::vector<float> out((size_t)width * (size_t)n);
+        if (n) check(ctx_.get(), call(ctx_.get(), map, out.data(), n, &n), who);
+        return out;
+    }
     Context& ctx_;
 };
 

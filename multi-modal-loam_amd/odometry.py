@@ -110,20 +110,29 @@ def _published(st, fast_rotation):
 
 
 def _world_map_create(ctx, n, world_map):
-    """world_map: None, or (leaf, capacity_voxels) -- n device-resident voxel maps of the registered clouds, one per sequence."""
+    """world_map: None, or (leaf, capacity_voxels) -- n device-resident voxel maps of the registered clouds, one per sequence --,
+    or (leaf, capacity_voxels, "surfels"): the same maps with per-voxel moments, normals and planarity (a surfel map)."""
     if world_map is None:
         return None
+    if len(world_map) == 3:
+        if world_map[2] != "surfels":
+            raise ValueError('world_map: the third element, if given, is "surfels"')
+        leaf, capacity = world_map[:2]
+        ctx.world_map_create(n, leaf, capacity, surfels=True)
+        return float(leaf), int(capacity), "surfels"
     leaf, capacity = world_map
     ctx.world_map_create(n, leaf, capacity)
     return float(leaf), int(capacity)
 
 
-def _world_map_download(od, n, seq):
+def _world_map_download(od, n, seq, surfels=False):
     if not od._world_map:
         raise ValueError("no world map: pass world_map=(leaf, capacity_voxels)")
+    if surfels and len(od._world_map) != 3:
+        raise ValueError('no surfel map: pass world_map=(leaf, capacity_voxels, "surfels")')
     if not 0 <= seq < n:
         raise ValueError("sequence %d outside [0, %d)" % (seq, n))
-    return od.ctx.world_map_download(seq)
+    return od.ctx.world_map_surfels(seq) if surfels else od.ctx.world_map_download(seq)
 
 
 def _adjacent_runs(items, slot_of):
@@ -193,6 +202,11 @@ class LidarOdometry:
     def world_map(self, seq=0):
         """The world map of the sequence: (n, 4) float32 voxel centroids x, y, z, intensity in ascending key order."""
         return _world_map_download(self, 1, seq)
+
+    def world_map_surfels(self, seq=0):
+        """The surfels of the sequence's world map (world_map=(leaf, capacity_voxels, "surfels")), row for row the voxels of
+        world_map(): (n, 8) float32 nx ny nz | l0 l1 l2 | planarity linearity."""
+        return _world_map_download(self, 1, seq, surfels=True)
 
     def registered_cloud(self, slot):
         """The scan of `slot` in the world frame at the pose the last estimate_lidar_pose ended with -- the cloud the pose node
@@ -317,6 +331,11 @@ class BatchLidarOdometry:
     def world_map(self, seq):
         """The world map of sequence `seq`: (n, 4) float32 voxel centroids x, y, z, intensity in ascending key order."""
         return _world_map_download(self, self.n, seq)
+
+    def world_map_surfels(self, seq):
+        """The surfels of sequence `seq`'s world map (world_map=(leaf, capacity_voxels, "surfels")), row for row the voxels of
+        world_map(seq): (n, 8) float32 nx ny nz | l0 l1 l2 | planarity linearity."""
+        return _world_map_download(self, self.n, seq, surfels=True)
 
 
 def _rotvec_from_quat(q):
