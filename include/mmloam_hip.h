@@ -707,6 +707,14 @@ int mml_map_local_download(mml_ctx* ctx, int kind, float* xyz, int capacity, int
  *                           matches against becomes the store as it was BEFORE this call (cubes, trees and centre):
  *                           the a12 grids and laserCloudCen*_last are rebuilt from it.  n_* (optional): live store
  *                           sizes after the update.
+ * Both are the n-store chain of the map banks (mml_map_bank_global_*_segmented below) with n = 1 on the context's own store:
+ * the same launches, 3 + R host synchronisations per increment, and the same refusals -- an append of a slot without a
+ * down-sampled stack of EITHER kind (MML_ERR_STATE) or beyond 16 x max_features pending points (MML_ERR_CAPACITY), an increment
+ * whose store would exceed max_map_points (MML_ERR_CAPACITY) or whose pose needs more than 64 layer shifts (MML_ERR_INVALID)
+ * -- each of which leaves the store exactly as it was: live arrays, tags, centre, pending clouds, match copy.
+ * Memory: the store's own arrays from the first append / increment on (72 bytes per point of max_map_points plus
+ * 2 x 16 x max_features x 16 bytes of pending clouds); the upkeep's scratch is the chain's, sized by the points actually worked
+ * on (60 bytes per stored + pending point, 155 232 bytes per segment), not by max_map_points.
  * mml_map_global_download: the LIVE store (xyz: 3 floats per point, cube: its index, cen: 3 ints; any may be NULL). */
 int mml_map_global_append(mml_ctx* ctx, int slot, const double* T_wl);
 int mml_map_global_increment(mml_ctx* ctx, const double* T_wl, int* n_corner, int* n_surf);
@@ -749,9 +757,11 @@ int mml_map_set_global(mml_ctx* ctx, int kind, const float* xyz, const int* cube
  * mml_map_bank_set_global: mml_map_set_global on bank `bank` (m = 0 removes that bank's cube map).
  * mml_map_bank_global_append: mml_map_global_append for n DISTINCT banks, slot slots[i] at T_wl + 16 i into bank banks[i].
  * mml_map_bank_global_increment: mml_map_global_increment for n DISTINCT banks, bank banks[i] at T_wl + 16 i; n_corner /
- * n_surf: n live store sizes each, or NULL.  The banks are worked through one after the other (two to three host
- * synchronisations per kind and bank); every bank ends bit-identical, the order inside every cube included, to the own
- * cube store of a context with the same history.
+ * n_surf: n live store sizes each, or NULL.  The banks are worked through one after the other, each by the chain of
+ * mml_map_bank_global_increment_segmented with n = 1 (3 + R host synchronisations per bank, 4 + R when its match copy has
+ * to grow); every bank ends bit-identical, the order inside every cube included, to the own cube store of a context with
+ * the same history.  A refusal at bank i (its store would exceed max_map_points, its pose needs more than 64 layer shifts)
+ * leaves bank i and the banks after it exactly as they were and banks 0 .. i-1 incremented.
  * mml_map_bank_global_download / _reset: mml_map_global_download / _reset on bank `bank` (mml_map_bank_reset keeps its
  * meaning: the local ring only).
  * All five check every argument before the device is touched or anything changes: a NULL context and a bank out of range
@@ -761,7 +771,9 @@ int mml_map_set_global(mml_ctx* ctx, int kind, const float* xyz, const int* cube
  * store and its compaction twin) plus 2 x 16 x max_features x 16 bytes of pending clouds -- 37 748 736 + 4 194 304 bytes at
  * max_map_points = 1 << 19 and max_features = 8192; the match copy is sized by need, 36 bytes per point it holds (at least
  * 1024) plus 16 bytes per point of max_map_points for its cell table, per kind, from the first set_global / increment on.
- * The upkeep's scratch is the context's and is shared by all banks.  mml_map_banks_create allocates none of it.
+ * The upkeep's scratch is the context's and is shared by all banks and the own store: the chain's, 60 bytes per point
+ * worked on at a time plus 155 232 bytes per segment, grown on demand (a context holds no fixed scratch sized by
+ * max_map_points for it).  mml_map_banks_create allocates none of it.
  * mml_slot_bank_get reads the bindings back (all -1 on a context without banks).
  * mml_map_bank_increment: mml_map_increment_local for n DISTINCT banks (a bank named twice is MML_ERR_INVALID, checked
  * with every other argument before anything changes): bank banks[i] takes the stacks of slot slots[i] at T_wl + 16 i.
@@ -789,28 +801,29 @@ int mml_map_set_global(mml_ctx* ctx, int kind, const float* xyz, const int* cube
  * shifts applied as it is read, a pending point's from the moved centre) and fills the per-segment cube histograms, one
  * classifies, ONE scan per flag array runs over all segments, one launch scatters, ONE stable 64-bit sort keyed
  * segment << 53 | cube << 40 | voxel index (over 53 + the bits of the segment count) filters every cube that grew beyond 300
- * points, and the 2 n match copies are built by one sort per cell-refinement round.  Every bank ends bit-identical to what
- * the loop call leaves on the same history -- live store with its tags and the order inside every cube, centre, emptied
- * pending clouds, the match copy (the store at the START of the increment with the centre before MapMove) with its grid and
- * cube counts, the sizes returned.  TWO DIFFERENCES:
- * (1) ALL OR NOTHING.  Every refusal leaves EVERY bank of the call exactly as it was -- live store, tags, centre, pending
+ * points, and the 2 n match copies are built by one sort per cell-refinement round.  This chain is the only implementation:
+ * the loop call runs it once per bank with n = 1, mml_map_global_increment / _append once on the own store, and both append
+ * entry points are the same call.  Every bank ends bit-identical to what the loop call leaves on the same history -- live
+ * store with its tags and the order inside every cube, centre, emptied pending clouds, the match copy (the store at the START
+ * of the increment with the centre before MapMove) with its grid and cube counts, the sizes returned.
+ * ALL OR NOTHING -- the one difference to the loop increment, which differs only in that its banks 0 .. i-1 stay incremented
+ * when bank i is refused.  Every refusal leaves EVERY bank of the call exactly as it was -- live store, tags, centre, pending
  * clouds, match copy -- and n_corner / n_surf unwritten: a bank twice or out of range, n < 1, a context without banks, an
  * append of a slot without a stack (MML_ERR_STATE) or beyond 16 x max_features pending points (MML_ERR_CAPACITY), a store
- * that would exceed max_map_points (MML_ERR_CAPACITY; the message names the bank), a pose that needs more layer shifts than
- * the 64 the one-store call lists (MML_ERR_INVALID).  (The loop leaves banks 0 .. i-1 incremented, and a capacity refusal
- * leaves bank i with its tags shifted and its centre moved.)  The refusals are decided in this order: arguments; poses, on a
- * host copy of every centre; then the one read-back of every segment's kept / selected totals, before which only scratch is
+ * that would exceed max_map_points (MML_ERR_CAPACITY; the message names the bank), a pose that needs more than 64 layer
+ * shifts (MML_ERR_INVALID).  The refusals are decided in this order: arguments; poses, on a host copy of every centre; then
+ * the one read-back of every segment's kept / selected totals, before which only scratch is
  * written.  The live arrays are read-only until every chunk (below) has passed; the match copies are built after that from
  * the untouched arrays, then the buffer pairs are swapped and the host state is written.
- * (2) Host synchronisations after the entry drain, whatever n is: 1 for the kept / selected totals of all segments (the
- * capacity decision), 1 for the filtered sizes (none when no cube is filtered), at most 1 when a match copy has to grow, 1
+ * Host synchronisations after the entry drain, whatever n is (the loop makes them per bank): 1 for the kept / selected totals
+ * of all segments (the capacity decision), 1 for the filtered sizes (none when no cube is filtered), at most 1 when a match copy has to grow, 1
  * for the bounding boxes of all match copies, R for the cell-refinement rounds of the slowest match copy: 3 + R, 4 + R on
  * growth.  The append reads all stack sizes in ONE copy and transforms all 2 n stacks in ONE launch.
  * Scratch: an allocation group of its own, grown on demand and kept until mml_destroy -- 60 bytes per point (store + pending,
  * both kinds) the call works on at a time plus 155 232 bytes (8 x 4851 ints) per segment, and the sorts' temporary storage.
  * A call whose banks hold more than MML_BANK_GLOBAL_INCREMENT_BUDGET points, or more than MML_BANK_GLOBAL_CHUNK_BANKS banks,
- * works them in chunks -- greedy, in call order, a bank over the budget a chunk of its own -- with the synchronisations above
- * per chunk; the store chains of ALL chunks run, and pass their capacity decisions, before the first match copy is built.
+ * works them in chunks -- greedy, in call order, a bank over the budget a chunk of its own (as is the one store of a loop or
+ * own-store call: the budget hook applies to them and changes nothing) -- with the synchronisations above per chunk; the store chains of ALL chunks run, and pass their capacity decisions, before the first match copy is built.
  * The defaults bound the scratch by 240 MiB + 38 MiB and keep every position in an int.
  * mml_debug_bank_global_increment_budget (a test hook): sets that budget, in points, for the context's later calls. */
 #define MML_MAP_BANKS_MAX 1024

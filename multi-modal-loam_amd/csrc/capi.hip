@@ -1220,7 +1220,7 @@ int mml_map_global_append(mml_ctx* ctx, int slot, const double* T_wl) {
     MML_REQUIRE(T_wl, MML_ERR_INVALID, "null transform");
     int rc = mml_sync_all(ctx);
     if (rc != MML_OK) return rc;
-    return mml_cube_store_append(ctx, mml_cube_own(ctx), slot, T_wl);
+    return mml_cube_store_append(ctx, mml_cube_own(ctx), -1, slot, T_wl);
 }
 
 int mml_map_global_increment(mml_ctx* ctx, const double* T_wl, int* n_corner, int* n_surf) {
@@ -1230,7 +1230,7 @@ int mml_map_global_increment(mml_ctx* ctx, const double* T_wl, int* n_corner, in
     int rc = mml_sync_all(ctx);
     if (rc != MML_OK) return rc;
     int n[2] = {0, 0};
-    rc = mml_cube_store_increment(ctx, mml_cube_own(ctx), T_wl, n);
+    rc = mml_cube_store_increment(ctx, mml_cube_own(ctx), -1, T_wl, n);
     if (n_corner) *n_corner = n[0];
     if (n_surf) *n_surf = n[1];
     return rc;

@@ -1344,13 +1344,11 @@ int mml_build_grid_device(mml_ctx* ctx, const MmlMapRef& map, int kind, int m) {
 
 // a12: the global map handed to Estimate() (Estimator.cpp:1170-1184) as one concatenated cloud with the cube index
 // (ToIndex) of every point.  The per-cube kd-trees become one grid whose points carry their cube as a tag.
-static int ensure_global_capacity(mml_ctx* ctx, MmlCubeMatch& G, int kind, int m) {
+int mml_cube_match_ensure(mml_ctx* ctx, MmlCubeMatch& G, int kind, int m) {
     MmlGrid& g = G.ggrid[kind];
-    if (m <= G.gmap_cap[kind] && G.ggrid_mem[kind].present()) return MML_OK;
-    MML_HIP(hipStreamSynchronize(MML_STREAM(ctx)));
+    if (mml_cube_match_fits(G, kind, m)) return MML_OK;
     const size_t cap = (size_t)(m > 1024 ? m : 1024);
     G.gmap_cap[kind] = 0;
-    // (the cube counts are rewritten by both callers, so they may move with the rest)
     const int rc = G.ggrid_mem[kind].reserve(
         ctx, {mml_part(g.pts, cap), mml_part(g.cell_start, 4 * (size_t)ctx->MM + 4096 + 2), mml_part(g.tags, cap),
               mml_part(G.gmap_orig[kind], cap), mml_part(G.gtag_orig[kind], cap), mml_part(G.cube_cnt[kind], 4851)});
@@ -1370,7 +1368,8 @@ int mml_build_global_grid(mml_ctx* ctx, const MmlCubeRef& cube, int kind, const 
         G.cen[1] = cen[1];
         G.cen[2] = cen[2];
     }
-    int rc = ensure_global_capacity(ctx, G, kind, m);
+    if (!mml_cube_match_fits(G, kind, m)) MML_HIP(hipStreamSynchronize(s));  // (a copy that grows is replaced with nothing in flight)
+    int rc = mml_cube_match_ensure(ctx, G, kind, m);
     if (rc != MML_OK) return rc;
     std::vector<uint16_t> tags((size_t)(m ? m : 1));
     std::vector<int> cnt(4851, 0);
@@ -1383,31 +1382,6 @@ int mml_build_global_grid(mml_ctx* ctx, const MmlCubeRef& cube, int kind, const 
     if (m) MML_HIP(hipMemcpyAsync(G.gtag_orig[kind], tags.data(), sizeof(uint16_t) * (size_t)m, hipMemcpyHostToDevice, s));
     MML_HIP(hipStreamSynchronize(s));
     rc = build_grid_into(ctx, G.ggrid[kind], G.gmap_orig[kind], h_xyz, m,
-                         kind == 0 ? ctx->cfg.cell_corner : ctx->cfg.cell_surf, G.gtag_orig[kind]);
-    if (rc == MML_OK) G.have_gmap[kind] = m > 0;
-    return rc;
-}
-
-// Same from device arrays (device-side cube store, map_global.hip): points, their cube tags and the 4851 cube counts.
-int mml_build_global_grid_device(mml_ctx* ctx, const MmlCubeRef& cube, int kind, const float4* d_pts, const uint16_t* d_tags, const int* d_cnt,
-                                 int m, const int* cen) {
-    MmlCubeMatch& G = *cube.match;
-    MML_REQUIRE(kind == 0 || kind == 1, MML_ERR_INVALID, "map kind must be 0 (corner) or 1 (surf)");
-    MML_REQUIRE(m >= 0 && m <= ctx->MM, MML_ERR_CAPACITY, "global map larger than max_map_points");
-    hipStream_t s = MML_STREAM(ctx);
-    G.have_gmap[kind] = false;
-    ctx->banks.dirty = true;  // (the cube table of a context with banks holds a copy of this map's row)
-    G.cen[0] = cen[0];
-    G.cen[1] = cen[1];
-    G.cen[2] = cen[2];
-    int rc = ensure_global_capacity(ctx, G, kind, m);
-    if (rc != MML_OK) return rc;
-    MML_HIP(hipMemcpyAsync(G.cube_cnt[kind], d_cnt, sizeof(int) * 4851, hipMemcpyDeviceToDevice, s));
-    if (m) {
-        MML_HIP(hipMemcpyAsync(G.gmap_orig[kind], d_pts, sizeof(float4) * (size_t)m, hipMemcpyDeviceToDevice, s));
-        MML_HIP(hipMemcpyAsync(G.gtag_orig[kind], d_tags, sizeof(uint16_t) * (size_t)m, hipMemcpyDeviceToDevice, s));
-    }
-    rc = build_grid_into(ctx, G.ggrid[kind], G.gmap_orig[kind], nullptr, m,
                          kind == 0 ? ctx->cfg.cell_corner : ctx->cfg.cell_surf, G.gtag_orig[kind]);
     if (rc == MML_OK) G.have_gmap[kind] = m > 0;
     return rc;

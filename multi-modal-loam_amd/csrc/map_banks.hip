@@ -5,8 +5,9 @@
 //   cube maps --, through the per-slot bank array (map_assoc.hip, the BANKED forms); this file keeps the three device arrays
 //   equal to the host's state.
 //   A bank has its own global cube map (MmlCubeMatch / MmlCubeLive, mml_internal.h): the mml_map_bank_global_* calls run the code
-//   of the own-map calls on it (MmlCubeRef), n banks in a loop; the *_segmented forms work the n banks in one chain of launches
-//   (map_global_seg.hip).  The context's OWN cube map and a bound slot exclude each other.
+//   of the own-map calls on it (MmlCubeRef): one chain of launches for n stores (map_global.hip), which the *_segmented forms
+//   and both appends run once for all n banks and the loop increment once per bank.  The context's OWN cube map and a bound
+//   slot exclude each other.
 #include <string.h>
 
 #include <algorithm>
@@ -263,57 +264,12 @@ int mml_map_bank_set_global(mml_ctx* ctx, int bank, int kind, const float* xyz, 
     return mml_build_global_grid(ctx, mml_cube_bank(ctx, bank), kind, xyz, cube, m, cen);
 }
 
-int mml_map_bank_global_append(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl) {
+// a call's arguments checked and the context drained, then ONE append chain for all n banks (map_global.hip): every slot's stacks
+// are checked before a bank's pending clouds change
+static int global_append(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl, const char* who) {
     if (!ctx) return MML_ERR_INVALID;
     MML_REQUIRE(n >= 1 && banks && slots && T_wl, MML_ERR_INVALID, "bad arguments");
-    int rc = check_distinct_banks(ctx, n, banks, slots, "mml_map_bank_global_append");
-    if (rc != MML_OK) return rc;
-    rc = enter(ctx);
-    if (rc != MML_OK) return rc;
-    if (!ctx->uploads.empty()) return mml_refuse(ctx, MML_ERR_STATE, "uploads in flight after a drained context");
-    // the stacks' sizes, checked for every slot before a bank's pending clouds change
-    std::vector<int> nf(2 * (size_t)n);
-    for (int i = 0; i < n; ++i)
-        for (int k = 0; k < 2; ++k)
-            MML_HIP(hipMemcpyAsync(&nf[2 * (size_t)i + k], ctx->ft_n + k * ctx->B + slots[i], sizeof(int), hipMemcpyDeviceToHost, MML_STREAM(ctx)));
-    MML_HIP(hipStreamSynchronize(MML_STREAM(ctx)));
-    for (int i = 0; i < n; ++i)
-        for (int k = 0; k < 2; ++k) {
-            const int f = nf[2 * (size_t)i + k];
-            const MmlCubeLive& L = ctx->banks.bank[(size_t)banks[i]].clive;
-            if (f < 0 || f > ctx->MF) return mml_refuse(ctx, MML_ERR_STATE, "slot %d holds no down-sampled feature stack", slots[i]);
-            if (L.gp_n[k] + f > 16 * ctx->MF)
-                return mml_refuse(ctx, MML_ERR_CAPACITY, "map bank %d: too many pending map points (16 x max_features)", banks[i]);
-        }
-    for (int i = 0; i < n; ++i) {
-        rc = mml_cube_store_append(ctx, mml_cube_bank(ctx, banks[i]), slots[i], T_wl + 16 * (size_t)i);
-        if (rc != MML_OK) return rc;
-    }
-    return MML_OK;
-}
-
-int mml_map_bank_global_increment(mml_ctx* ctx, int n, const int* banks, const double* T_wl, int* n_corner, int* n_surf) {
-    if (!ctx) return MML_ERR_INVALID;
-    MML_REQUIRE(n >= 1 && banks && T_wl, MML_ERR_INVALID, "bad arguments");
-    int rc = check_distinct_banks(ctx, n, banks, nullptr, "mml_map_bank_global_increment");
-    if (rc != MML_OK) return rc;
-    rc = enter(ctx);
-    if (rc != MML_OK) return rc;
-    for (int i = 0; i < n; ++i) {
-        int m[2] = {0, 0};
-        rc = mml_cube_store_increment(ctx, mml_cube_bank(ctx, banks[i]), T_wl + 16 * (size_t)i, m);
-        if (n_corner) n_corner[i] = m[0];
-        if (n_surf) n_surf[i] = m[1];
-        if (rc != MML_OK) return rc;
-    }
-    return MML_OK;
-}
-
-// the segmented forms (map_global_seg.hip): the same argument checks and drain, then ONE chain for all n banks
-int mml_map_bank_global_append_segmented(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl) {
-    if (!ctx) return MML_ERR_INVALID;
-    MML_REQUIRE(n >= 1 && banks && slots && T_wl, MML_ERR_INVALID, "bad arguments");
-    int rc = check_distinct_banks(ctx, n, banks, slots, "mml_map_bank_global_append_segmented");
+    int rc = check_distinct_banks(ctx, n, banks, slots, who);
     if (rc != MML_OK) return rc;
     rc = enter(ctx);
     if (rc != MML_OK) return rc;
@@ -323,6 +279,33 @@ int mml_map_bank_global_append_segmented(mml_ctx* ctx, int n, const int* banks, 
     return mml_cube_store_append_segmented(ctx, n, cubes.data(), banks, slots, T_wl);
 }
 
+int mml_map_bank_global_append(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl) {
+    return global_append(ctx, n, banks, slots, T_wl, "mml_map_bank_global_append");
+}
+
+int mml_map_bank_global_append_segmented(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl) {
+    return global_append(ctx, n, banks, slots, T_wl, "mml_map_bank_global_append_segmented");
+}
+
+// the loop: one n = 1 chain per bank, in call order; a refusal leaves bank i as it was and banks 0 .. i-1 incremented
+int mml_map_bank_global_increment(mml_ctx* ctx, int n, const int* banks, const double* T_wl, int* n_corner, int* n_surf) {
+    if (!ctx) return MML_ERR_INVALID;
+    MML_REQUIRE(n >= 1 && banks && T_wl, MML_ERR_INVALID, "bad arguments");
+    int rc = check_distinct_banks(ctx, n, banks, nullptr, "mml_map_bank_global_increment");
+    if (rc != MML_OK) return rc;
+    rc = enter(ctx);
+    if (rc != MML_OK) return rc;
+    for (int i = 0; i < n; ++i) {
+        int m[2] = {0, 0};
+        rc = mml_cube_store_increment(ctx, mml_cube_bank(ctx, banks[i]), banks[i], T_wl + 16 * (size_t)i, m);
+        if (n_corner) n_corner[i] = m[0];
+        if (n_surf) n_surf[i] = m[1];
+        if (rc != MML_OK) return rc;
+    }
+    return MML_OK;
+}
+
+// ONE chain for all n banks
 int mml_map_bank_global_increment_segmented(mml_ctx* ctx, int n, const int* banks, const double* T_wl, int* n_corner, int* n_surf) {
     if (!ctx) return MML_ERR_INVALID;
     MML_REQUIRE(n >= 1 && banks && T_wl, MML_ERR_INVALID, "bad arguments");

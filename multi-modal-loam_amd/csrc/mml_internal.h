@@ -63,9 +63,9 @@ struct MmlGrid {         // radix-sorted uniform grid over one map cloud (replac
 };
 
 // The global cube map of one Estimator (a12 + map_global.hip), in two parts.  The context has one pair of its own and every map
-// bank one more (MmlCubeRef below); the scratch the upkeep works in (gs_work, gs_keys, the sort buffers) is the context's.
+// bank one more (MmlCubeRef below); the scratch the upkeep works in (bank_cube, the sort buffers) is the context's.
 // The MATCH COPY: what Estimate() matches against -- tagged grids over the concatenated cube clouds, the unsorted clouds with
-// their tags, the 4851 cube counts, laserCloudCen*_last.  Sized by need (ensure_global_capacity).
+// their tags, the 4851 cube counts, laserCloudCen*_last.  Sized by need (mml_cube_match_ensure).
 struct MmlCubeMatch {
     MmlGrid ggrid[2];
     bool have_gmap[2] = {false, false};
@@ -346,10 +346,6 @@ struct mml_ctx {
     MmlGroup ring_mem;                       // owns ring[2]; allocated by the first increment, like a bank's
     int ring_n[2][LOCAL_WINDOW] = {};
     long local_map_id = 0;                   // localMapID
-    // scratch of the cube stores' upkeep, shared by the own store and every bank's (one increment runs at a time)
-    int* gs_work = nullptr;                    // histograms / flags / bbox keys / scan scratch
-    unsigned long long* gs_keys = nullptr;     // 64-bit sort keys, 2 x MM
-    MmlGroup cube_scratch;                     // owns the two, allocated by the first append / increment of any store
     MmlStaging<char, false> wire_stage;      // raw message bytes on their way in / out (one call at a time; grows to the largest)
     int local_map_n[2] = {0, 0};
     MmlBanks banks;                    // map banks (map_banks.hip): further local maps, and which slot is matched against which
@@ -365,8 +361,9 @@ struct mml_ctx {
         MmlStaging<char> tab;                // a chunk's tables and read-backs: device block and pinned twin
         long budget = MML_BANK_INCREMENT_BUDGET;  // ring points per chunk (mml_debug_bank_increment_budget)
     } bank_inc;
-    // scratch of the segmented cube-store increment (map_global_seg.hip), a group of its own: sized by the points (store + pending,
-    // both kinds) and the segments of the largest chunk of stores a call has worked on -- 60 bytes per point, 8 x 4851 ints per segment
+    // scratch of the cube stores' upkeep (map_global.hip), of the own store's as of the banks' (one increment runs at a time), a group
+    // of its own: sized by the points (store + pending, both kinds) and the segments of the largest chunk of stores a call has
+    // worked on -- 60 bytes per point, 8 x 4851 ints per segment
     struct BankCube {
         int* work = nullptr;                 // seg_cap x (cnt | changed | six box keys per cube)
         int* flags = nullptr;                // 4 x (cap + 1): keep, keep_pos, sel, sel_pos (run heads and positions after the scatter)
@@ -465,7 +462,6 @@ struct mml_ctx {
         bank_cube.tab.release();
         world.release();
         clive.mem.release();
-        cube_scratch.release();
         wire_stage.release();
         grid_tab.release();
         sort_tmp.release();
@@ -621,24 +617,28 @@ inline MmlCubeRef mml_cube_bank(mml_ctx* c, int bank) {
     return MmlCubeRef{&b.cmatch, &b.clive};
 }
 int mml_build_global_grid(mml_ctx* ctx, const MmlCubeRef& cube, int kind, const float* h_xyz, const int* h_cube, int m, const int* cen);
-int mml_build_global_grid_device(mml_ctx* ctx, const MmlCubeRef& cube, int kind, const float4* d_pts, const uint16_t* d_tags, const int* d_cnt,
-                                 int m, const int* cen);
-int mml_cube_store_append(mml_ctx* ctx, const MmlCubeRef& cube, int slot, const double* T_wl);
-int mml_cube_store_increment(mml_ctx* ctx, const MmlCubeRef& cube, const double* T_wl, int* n_out);
+// The one capacity rule of a match copy: room for m points of `kind` (at least 1024; the cube counts move with the rest, every
+// builder rewrites them).  A copy that has to grow is replaced, so the caller waits for work in flight first -- once per call,
+// when mml_cube_match_fits says no.
+inline bool mml_cube_match_fits(const MmlCubeMatch& G, int kind, int m) { return m <= G.gmap_cap[kind] && G.ggrid_mem[kind].present(); }
+int mml_cube_match_ensure(mml_ctx* ctx, MmlCubeMatch& G, int kind, int m);
 int mml_cube_store_download(mml_ctx* ctx, const MmlCubeRef& cube, int kind, float* xyz, int* cube_idx, int capacity, int* n, int* cen);
 int mml_cube_store_reset(mml_ctx* ctx, const MmlCubeRef& cube);
-int mml_cube_store_ensure(mml_ctx* ctx, const MmlCubeRef& cube);  // the store's memory and the one-store scratch, on first use
-// map_global_seg.hip: n DISTINCT stores in one chain of launches; the caller has checked the arguments and drained the context.
-// names[i]: what a message calls store i (its bank).  Bit-identical to n calls of the one-store forms above; every refusal leaves
+int mml_cube_store_ensure(mml_ctx* ctx, const MmlCubeRef& cube);  // the store's own memory, on first use
+// The upkeep (map_global.hip): n DISTINCT stores in one chain of launches; the caller has checked the arguments and drained the
+// context.  names[i]: what a message calls store i -- its bank, or -1 for the context's own store (no prefix).  Every refusal leaves
 // all n stores -- live arrays, tags, centres, pending clouds, match copies -- as they were.
 int mml_cube_store_increment_segmented(mml_ctx* ctx, int n, const MmlCubeRef* cubes, const int* names, const double* T_wl, int* n_corner,
                                        int* n_surf);
 int mml_cube_store_append_segmented(mml_ctx* ctx, int n, const MmlCubeRef* cubes, const int* names, const int* slots, const double* T_wl);
+// one store: the same chain with n = 1.  n_out: the two sizes (corner, surf).
+int mml_cube_store_append(mml_ctx* ctx, const MmlCubeRef& cube, int name, int slot, const double* T_wl);
+int mml_cube_store_increment(mml_ctx* ctx, const MmlCubeRef& cube, int name, const double* T_wl, int* n_out);
 // The chunks of such a call: chunk c = stores [cut[c], cut[c + 1]) -- greedy, in call order, at most `budget` points (pts[i]: store +
 // pending, both kinds) and at most max_stores stores per chunk, a store over the budget a chunk of its own.
 std::vector<int> mml_cube_chunks(int n, const long long* pts, long long budget, int max_stores);
-// The sort key of the segmented filter: segment << 53 | cube << 40 | PCL voxel index.  4851 cubes take 13 bits, the index 40
-// (the one-store chain keys cube << 40 | index): up to 2048 segments in 64 bits.
+// The sort key of the cube filter: segment << 53 | cube << 40 | PCL voxel index.  4851 cubes take 13 bits, the index 40: up to 2048
+// segments in 64 bits.
 __host__ __device__ inline unsigned long long mml_cube_key(unsigned seg, unsigned cube, unsigned long long vox) {
     return ((unsigned long long)seg << 53) | ((unsigned long long)cube << 40) | vox;
 }

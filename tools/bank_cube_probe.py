@@ -183,14 +183,14 @@ def main():
             pa.shape[0] * pa.shape[1], keys, sizes))
     lines += ["", "cube stores that pass the gate at the end (corner > 0 and surf > 100, Estimator.cpp:1032): " +
               ", ".join("n = %s: %d of %d" % (n, sum(1 for c, s in new[str(n)]["sizes"] if c > 0 and s > 100), int(n)) for n in map(str, ns)),
-              "", "host synchronisations of a round of increments in (b).  From the code, per bank and increment: the match copy's grid build",
-              "(map_assoc.hip build_grid_into) 2 + one per cell refinement round per kind with points, one more when its buffers grow;",
-              "the store's update (map_global.hip) 1 per kind with points + 1 per kind with a cube over 300 to filter: 2 to 3 per kind in a",
-              "store that holds points, 4 to 6 (and more with refinement rounds) per bank.  Banks per mml_map_bank_global_increment call:"]
+              "", "host synchronisations of a round of increments in (b).  From the code, per bank and increment (map_global.hip, the n-store",
+              "chain with n = 1): 1 kept / selected totals of both kinds (the capacity decision) + 1 filtered sizes (none when no cube is",
+              "over 300) + at most 1 when the match copy grows + 1 bounding boxes of both kinds + R, the cell-refinement rounds of the slower",
+              "kind (map_assoc.hip mml_build_grids): 3 + R, 4 + R on growth.  Banks per mml_map_bank_global_increment call:"]
     for n in ns:
         inc = new[str(n)]["increments"] or []
         lines.append("  n = %3d: %s banks in the %d calls of a replay -> about %d .. %d synchronisations in the largest round" % (
-            n, inc, len(inc), 4 * max(inc + [0]), 6 * max(inc + [0])))
+            n, inc, len(inc), 4 * max(inc + [0]), 8 * max(inc + [0])))
     lines += ["", "ISA of the association kernels, parent build against this build (tools/isa_compare.py on the -save-temps assembly of",
               "csrc/map_assoc.hip, the Makefile's flags; the unbanked instantiations are what a launch without a bound slot runs):"]
     lines += open(a.isa_report).read().rstrip().splitlines() if a.isa_report else ["(not supplied: --isa-report)"]

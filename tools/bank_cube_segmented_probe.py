@@ -3,7 +3,7 @@ n map banks, the live 1-frame loop with the map thread's cube schedule -- with t
   (a) on a build of the PARENT commit: global_increment="loop", mml_map_bank_global_append / _increment work the banks of a call
       through one after the other;
   (b) on this build: global_increment="segmented", mml_map_bank_global_append_segmented / _increment_segmented work them in one
-      chain of launches (csrc/map_global_seg.hip).
+      chain of launches (csrc/map_global.hip).
     python tools/bank_cube_segmented_probe.py [--prev <parent .so>] [--out <table>] [n ...]
 Defaults: n = 1, 8, 64 sequences of 7 scans (16 rings x 450 azimuths + 6 000 Livox points).  The inputs are those of
 tools/bank_cube_probe.py (make_inputs, imported).
@@ -34,14 +34,15 @@ from bank_cube_probe import ROUNDS, TRAJ, make_inputs  # noqa: E402
 REPS = 3
 SYNCS = [
     "host synchronisations of a round's cube upkeep after each call's entry drain, from the code:",
-    "  (a) loop      append: 1 (all stack sizes) + 1 per bank (mml_cube_store_append reads its slot's two sizes again)",
-    "                increment, per bank: the match copy 2 + one per cell-refinement round per kind with points (+1 when its buffers",
-    "                grow); the store 1 per kind with points + 1 per kind with a cube over 300 points: 4 to 6 and more per bank",
+    "  (a) loop      on a parent from before the chains were merged -- append: 1 (all stack sizes) + 1 per bank; increment, per bank:",
+    "                the match copy 2 + one per cell-refinement round per kind with points (+1 when its buffers grow); the store 1 per",
+    "                kind with points + 1 per kind with a cube over 300 points: 4 to 6 and more per bank.  On this build the loop's",
+    "                append is (b)'s, and its increment is (b)'s chain once per bank: 3 + R per bank, 4 + R on growth",
     "  (b) segmented append: 1 (all stack sizes), one launch for all banks",
     "                increment, whatever n: 1 kept / selected totals of all segments (the capacity decision) + 1 filtered sizes (none",
     "                when no cube is filtered) + at most 1 when a match copy grows + 1 bounding boxes of all match copies + R, the",
     "                cell-refinement rounds of the slowest match copy: 3 + R, 4 + R on growth",
-    "                (csrc/map_global_seg.hip chain_chunk / match_chunk, csrc/map_assoc.hip mml_build_grids); per chunk when the call's",
+    "                (csrc/map_global.hip chain_chunk / match_chunk, csrc/map_assoc.hip mml_build_grids); per chunk when the call's",
     "                banks hold more than MML_BANK_GLOBAL_INCREMENT_BUDGET points or number more than MML_BANK_GLOBAL_CHUNK_BANKS",
 ]
 
