@@ -728,7 +728,9 @@ int mml_map_global_reset(mml_ctx* ctx);
  * neighbourhood fails the fit.  Here the cubes arrive as ONE concatenated cloud: xyz (3 floats per point) and
  * cube[i] = ToIndex(i, j, k) = i + 21 j + 441 k of point i (points of one cube in the cube cloud's order, so
  * that kd-tree tie order is preserved).  cen: laserCloudCen{Width,Height,Depth}_last (3 ints, NULL keeps
- * the current value, default 10, 5, 10).  m = 0 removes the global map (local-only association). */
+ * the current value, default 10, 5, 10).  m = 0 removes the global map (local-only association).  Every argument -- the
+ * kind, m <= max_map_points (MML_ERR_CAPACITY), every cube index in [0, 4851) (MML_ERR_INVALID) -- is checked before anything
+ * changes: a refused call leaves the global map as it was. */
 int mml_map_set_global(mml_ctx* ctx, int kind, const float* xyz, const int* cube, int m, const int* cen);
 
 /* ---- map banks: N further local maps per context, every scan slot matched against its own ----------------------

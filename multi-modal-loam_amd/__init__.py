@@ -1239,12 +1239,19 @@ class Context:
     def map_local_reset(self):
         self._ck(lib().mml_map_local_reset(self._h))
 
+    def _download(self, f, head, shapes, tail=(), count=C.c_int):
+        """The two-call download f(handle, *head, *buffers, capacity, &n, *tail): with null buffers it reports n, then it fills
+        one buffer of n rows per entry of shapes -- (columns, or None for a flat array; dtype).  Returns the buffers, n rows each."""
+        n = count(0)
+        self._ck(f(self._h, *head, *[None] * len(shapes), 0, C.byref(n), *tail))
+        rows = max(n.value, 1)
+        out = [np.zeros(rows if w is None else (rows, w), t) for w, t in shapes]
+        if n.value:
+            self._ck(f(self._h, *head, *[_p(a) for a in out], n.value, C.byref(n), *tail))
+        return [a[:n.value] for a in out]
+
     def map_local_download(self, kind):
-        n = C.c_int(0)
-        self._ck(lib().mml_map_local_download(self._h, C.c_int(kind), None, C.c_int(0), C.byref(n)))
-        out = np.zeros((max(n.value, 1), 3), np.float32)
-        self._ck(lib().mml_map_local_download(self._h, C.c_int(kind), _p(out), C.c_int(n.value), C.byref(n)))
-        return out[:n.value].copy()
+        return self._download(lib().mml_map_local_download, (int(kind),), [(3, np.float32)])[0]
 
     # ---- the world map: the registered clouds voxel-merged on the device, n maps (include/mmloam_hip.h, "The world map") ----
     def world_map_create(self, n_maps, leaf, capacity_voxels, surfels=False):
@@ -1257,12 +1264,7 @@ class Context:
             self._ck(lib().mml_world_map_create(self._h, int(n_maps), float(leaf), int(capacity_voxels)))
 
     def _world_map_rows(self, f, map, width):
-        n = C.c_long(0)
-        self._ck(f(self._h, int(map), None, 0, C.byref(n)))
-        out = np.zeros((max(n.value, 1), width), np.float32)
-        if n.value:
-            self._ck(f(self._h, int(map), _p(out), n.value, C.byref(n)))
-        return out[:n.value]
+        return self._download(f, (int(map),), [(width, np.float32)], count=C.c_long)[0]
 
     def world_map_moments(self, map):
         """The raw accumulators of a surfel map's voxels in the order of world_map_download: (n, 12) float32
@@ -1299,13 +1301,8 @@ class Context:
     def world_map_download(self, map, counts=False):
         """The voxels of one map in ascending key order: (n, 4) float32 centroids x, y, z, intensity; counts=True: and the
         (n,) int32 point counts.  The sizing call, then one data call."""
-        n = C.c_long(0)
-        f = lib().mml_world_map_download
-        self._ck(f(self._h, int(map), None, None, 0, C.byref(n)))
-        out, cnt = np.zeros((max(n.value, 1), 4), np.float32), np.zeros(max(n.value, 1), np.int32)
-        if n.value:
-            self._ck(f(self._h, int(map), _p(out), _p(cnt), n.value, C.byref(n)))
-        return (out[:n.value], cnt[:n.value]) if counts else out[:n.value]
+        out, cnt = self._download(lib().mml_world_map_download, (int(map),), [(4, np.float32), (None, np.int32)], count=C.c_long)
+        return (out, cnt) if counts else out
 
     # ---- map banks: further local maps, every slot matched against its own (include/mmloam_hip.h, "map banks") ----
     def map_banks(self, n):
@@ -1333,11 +1330,7 @@ class Context:
         self._ck(lib().mml_map_bank_reset(self._h, C.c_int(bank)))
 
     def bank_download(self, bank, kind):
-        n = C.c_int(0)
-        self._ck(lib().mml_map_bank_download(self._h, C.c_int(bank), C.c_int(kind), None, C.c_int(0), C.byref(n)))
-        out = np.zeros((max(n.value, 1), 3), np.float32)
-        self._ck(lib().mml_map_bank_download(self._h, C.c_int(bank), C.c_int(kind), _p(out), C.c_int(n.value), C.byref(n)))
-        return out[:n.value].copy()
+        return self._download(lib().mml_map_bank_download, (int(bank), int(kind)), [(3, np.float32)])[0]
 
     def bank_increment(self, banks, slots, T_wl, segmented=False):
         """Estimator::MapIncrementLocal for len(banks) distinct banks in one call: bank banks[i] grows by the stacks of slot
@@ -1399,14 +1392,7 @@ class Context:
         self._ck(lib().mml_debug_bank_global_increment_budget(self._h, C.c_long(int(points))))
 
     def bank_global_download(self, bank, kind):
-        n = C.c_int(0)
-        cen = np.zeros(3, np.int32)
-        self._ck(lib().mml_map_bank_global_download(self._h, C.c_int(bank), C.c_int(kind), None, None, C.c_int(0), C.byref(n), _p(cen)))
-        xyz = np.zeros((max(n.value, 1), 3), np.float32)
-        cube = np.zeros(max(n.value, 1), np.int32)
-        self._ck(lib().mml_map_bank_global_download(self._h, C.c_int(bank), C.c_int(kind), _p(xyz), _p(cube), C.c_int(n.value), C.byref(n),
-                                                    _p(cen)))
-        return xyz[:n.value].copy(), cube[:n.value].copy(), cen
+        return self._cube_download(lib().mml_map_bank_global_download, (int(bank), int(kind)))
 
     def bank_global_reset(self, bank):
         self._ck(lib().mml_map_bank_global_reset(self._h, C.c_int(bank)))
@@ -1420,14 +1406,13 @@ class Context:
         self._ck(lib().mml_map_global_increment(self._h, _p(_f64(T_wl).reshape(16)), C.byref(nc), C.byref(ns)))
         return nc.value, ns.value
 
-    def map_global_download(self, kind):
-        n = C.c_int(0)
+    def _cube_download(self, f, head):
         cen = np.zeros(3, np.int32)
-        self._ck(lib().mml_map_global_download(self._h, C.c_int(kind), None, None, C.c_int(0), C.byref(n), _p(cen)))
-        xyz = np.zeros((max(n.value, 1), 3), np.float32)
-        cube = np.zeros(max(n.value, 1), np.int32)
-        self._ck(lib().mml_map_global_download(self._h, C.c_int(kind), _p(xyz), _p(cube), C.c_int(n.value), C.byref(n), _p(cen)))
-        return xyz[:n.value].copy(), cube[:n.value].copy(), cen
+        xyz, cube = self._download(f, head, [(3, np.float32), (None, np.int32)], tail=(_p(cen),))
+        return xyz, cube, cen
+
+    def map_global_download(self, kind):
+        return self._cube_download(lib().mml_map_global_download, (int(kind),))
 
     def map_global_reset(self):
         self._ck(lib().mml_map_global_reset(self._h))

@@ -237,12 +237,7 @@ int mml_create(const mml_config* cfg, int device, mml_ctx** out) {
     ALLOC(ctx->hard_list, B * MF * 2);
     ALLOC(ctx->hard_knn, B * MF * 2 * 10);
     ALLOC(ctx->work_off, 2 * B + 8);
-    for (int k = 0; k < 2; ++k) {
-        ALLOC(ctx->grid[k].pts, MM);
-        ALLOC(ctx->grid[k].cell_start, 4 * MM + 4096 + 2);
-        ctx->grid[k].m = 0;
-    }
-    ALLOC(ctx->map_tmp, 2 * MM);
+    if (mml_map_local_alloc(ctx, ctx->own) != MML_OK) return fail(hipErrorOutOfMemory, "the own local map");
     ALLOC(ctx->map_keys, MM);
     ALLOC(ctx->map_keys2, MM);
     ALLOC(ctx->map_vals, MM);
@@ -1165,104 +1160,12 @@ int mml_features_upload(mml_ctx* ctx, int slot, int kind, const float* xyz, int 
     return MML_OK;
 }
 
-int mml_map_set_local(mml_ctx* ctx, int kind, const float* xyz, int m) {
-    if (!ctx) return MML_ERR_INVALID;
-    MML_REQUIRE(m >= 0 && (m == 0 || xyz), MML_ERR_INVALID, "bad map arguments");
-    MML_HIP(hipSetDevice(ctx->device));
-    return mml_build_grid(ctx, kind, xyz, m);
-}
-
-int mml_map_increment_local(mml_ctx* ctx, int slot, const double* T_wl, int* n_corner_map, int* n_surf_map) {
-    CHECK_SLOTS(slot, 1);
-    MML_REQUIRE(T_wl, MML_ERR_INVALID, "null transform");
-    int rc = mml_sync_all(ctx);
-    if (rc != MML_OK) return rc;
-    int n[2] = {0, 0};
-    rc = mml_map_upkeep_increment(ctx, mml_map_own(ctx), slot, T_wl, n);
-    if (n_corner_map) *n_corner_map = n[0];
-    if (n_surf_map) *n_surf_map = n[1];
-    return rc;
-}
-
-int mml_map_local_reset(mml_ctx* ctx) {
-    if (!ctx) return MML_ERR_INVALID;
-    MML_HIP(hipSetDevice(ctx->device));
-    int rc = mml_sync_all(ctx);
-    if (rc != MML_OK) return rc;
-    memset(ctx->ring_n, 0, sizeof(ctx->ring_n));
-    ctx->local_map_id = 0;
-    return MML_OK;
-}
-
-int mml_map_local_download(mml_ctx* ctx, int kind, float* xyz, int capacity, int* n) {
-    if (!ctx) return MML_ERR_INVALID;
-    MML_REQUIRE((kind == 0 || kind == 1) && n, MML_ERR_INVALID, "bad arguments");
-    MML_REQUIRE(ctx->have_map[kind], MML_ERR_STATE, "no local map");
-    MML_HIP(hipSetDevice(ctx->device));
-    const int m = ctx->grid[kind].m;
-    *n = m;
-    if (!xyz || m == 0) return MML_OK;
-    MML_REQUIRE(capacity >= m, MML_ERR_CAPACITY, "capacity below the map size");
-    std::vector<float4> tmp((size_t)m);
-    MML_HIP(hipMemcpyAsync(tmp.data(), ctx->map_tmp + (size_t)kind * ctx->MM, sizeof(float4) * (size_t)m, hipMemcpyDeviceToHost,
-                           MML_STREAM(ctx)));
-    MML_HIP(hipStreamSynchronize(MML_STREAM(ctx)));
-    for (int i = 0; i < m; ++i) {
-        xyz[3 * i] = tmp[i].x;
-        xyz[3 * i + 1] = tmp[i].y;
-        xyz[3 * i + 2] = tmp[i].z;
-    }
-    return MML_OK;
-}
-
-int mml_map_global_append(mml_ctx* ctx, int slot, const double* T_wl) {
-    CHECK_SLOTS(slot, 1);
-    MML_REQUIRE(T_wl, MML_ERR_INVALID, "null transform");
-    int rc = mml_sync_all(ctx);
-    if (rc != MML_OK) return rc;
-    return mml_cube_store_append(ctx, mml_cube_own(ctx), -1, slot, T_wl);
-}
-
-int mml_map_global_increment(mml_ctx* ctx, const double* T_wl, int* n_corner, int* n_surf) {
-    if (!ctx) return MML_ERR_INVALID;
-    MML_REQUIRE(T_wl, MML_ERR_INVALID, "null transform");
-    MML_HIP(hipSetDevice(ctx->device));
-    int rc = mml_sync_all(ctx);
-    if (rc != MML_OK) return rc;
-    int n[2] = {0, 0};
-    rc = mml_cube_store_increment(ctx, mml_cube_own(ctx), -1, T_wl, n);
-    if (n_corner) *n_corner = n[0];
-    if (n_surf) *n_surf = n[1];
-    return rc;
-}
-
-int mml_map_global_download(mml_ctx* ctx, int kind, float* xyz, int* cube, int capacity, int* n, int* cen) {
-    if (!ctx) return MML_ERR_INVALID;
-    MML_REQUIRE((kind == 0 || kind == 1) && n, MML_ERR_INVALID, "bad arguments");
-    MML_HIP(hipSetDevice(ctx->device));
-    return mml_cube_store_download(ctx, mml_cube_own(ctx), kind, xyz, cube, capacity, n, cen);
-}
-
-int mml_map_global_reset(mml_ctx* ctx) {
-    if (!ctx) return MML_ERR_INVALID;
-    MML_HIP(hipSetDevice(ctx->device));
-    int rc = mml_sync_all(ctx);
-    if (rc != MML_OK) return rc;
-    return mml_cube_store_reset(ctx, mml_cube_own(ctx));
-}
-
-int mml_map_set_global(mml_ctx* ctx, int kind, const float* xyz, const int* cube, int m, const int* cen) {
-    if (!ctx) return MML_ERR_INVALID;
-    MML_REQUIRE(m >= 0 && (m == 0 || (xyz && cube)), MML_ERR_INVALID, "bad global map arguments");
-    MML_HIP(hipSetDevice(ctx->device));
-    mml_sync_all(ctx);
-    return mml_build_global_grid(ctx, mml_cube_own(ctx), kind, xyz, cube, m, cen);
-}
+// (the map calls -- mml_map_set_local ... mml_map_set_global -- live in map_banks.hip, beside the banks' forms of them)
 
 int mml_knn5(mml_ctx* ctx, int kind, const float* q, int nq, float max_d2, int* idx, float* d2) {
     if (!ctx) return MML_ERR_INVALID;
     MML_REQUIRE((kind == 0 || kind == 1) && nq >= 0 && (nq == 0 || (q && idx && d2)), MML_ERR_INVALID, "bad arguments");
-    MML_REQUIRE(ctx->have_map[kind], MML_ERR_STATE, "mml_knn5 before mml_map_set_local");
+    MML_REQUIRE(ctx->own.have_map[kind], MML_ERR_STATE, "mml_knn5 before mml_map_set_local");
     if (nq == 0) return MML_OK;
     MML_HIP(hipSetDevice(ctx->device));
     MmlTemp<float> d_q, d_d2;

@@ -117,7 +117,7 @@ static int win_end(mml_ctx* ctx, int n_local, int rounds, double* x_local, doubl
 static int local_map_received(mml_ctx* ctx, const int* m, bool is_root) {
     if (!is_root)
         for (int kind = 0; kind < 2; ++kind) {
-            int rc = mml_build_grid_device(ctx, kind, m[kind]);
+            int rc = mml_build_grid(ctx, ctx->own, kind, nullptr, m[kind]);  // (the cloud is in map_tmp already)
             if (rc != MML_OK) return rc;
         }
     return mml_sync_all(ctx);
@@ -338,7 +338,7 @@ int mml_comm_broadcast_local_map(mml_ctx* ctx, int root) {
     MmlComm* c = ctx->comm;
     MML_REQUIRE(!c->loopback, MML_ERR_STATE, "a loopback group is driven through the *_loopback entry points");
     MML_REQUIRE(root >= 0 && root < c->n_ranks, MML_ERR_INVALID, "bad root");
-    MML_REQUIRE(c->rank != root || (ctx->have_map[0] && ctx->have_map[1]), MML_ERR_STATE, "the root rank has no local map to broadcast");
+    MML_REQUIRE(c->rank != root || (ctx->own.have_map[0] && ctx->own.have_map[1]), MML_ERR_STATE, "the root rank has no local map to broadcast");
     MML_HIP(hipSetDevice(ctx->device));
     int rc = mml_sync_all(ctx);
     if (rc != MML_OK) return rc;
@@ -346,14 +346,14 @@ int mml_comm_broadcast_local_map(mml_ctx* ctx, int root) {
     hipStream_t s = MML_STREAM(ctx);
     // sizes through the device (RCCL moves device memory), then the two source clouds, then every replica builds its
     // own grid: the sort is deterministic, so the replicas are bit-identical
-    int m[2] = {ctx->grid[0].m, ctx->grid[1].m};
+    int m[2] = {ctx->own.grid[0].m, ctx->own.grid[1].m};
     MML_HIP(hipMemcpyAsync(ctx->d_misc, m, sizeof(m), hipMemcpyHostToDevice, s));
     MML_NCCL(ncclBroadcast(ctx->d_misc, ctx->d_misc, 2, ncclInt32, root, c->comm, s));
     MML_HIP(hipMemcpyAsync(m, ctx->d_misc, sizeof(m), hipMemcpyDeviceToHost, s));
     MML_HIP(hipStreamSynchronize(s));
     MML_REQUIRE(m[0] >= 0 && m[1] >= 0 && m[0] <= ctx->MM && m[1] <= ctx->MM, MML_ERR_CAPACITY, "broadcast map exceeds max_map_points");
     for (int kind = 0; kind < 2; ++kind) {
-        float4* p = ctx->map_tmp + (size_t)kind * ctx->MM;
+        float4* p = ctx->own.map_tmp + (size_t)kind * ctx->MM;
         if (m[kind] > 0) MML_NCCL(ncclBroadcast(p, p, 4 * (size_t)m[kind], ncclFloat32, root, c->comm, s));
     }
     return local_map_received(ctx, m, c->rank == root);
@@ -393,19 +393,19 @@ int mml_comm_broadcast_local_map_loopback(mml_ctx** ctxs, int n_ranks, int root)
         if (!ctx) return MML_ERR_INVALID;
         MML_REQUIRE(ctx->comm && ctx->comm->loopback && ctx->comm->n_ranks == n_ranks && ctx->comm->rank == r, MML_ERR_STATE,
                     "not the loopback group these contexts were initialised as (mml_comm_init_loopback)");
-        MML_REQUIRE(r != root || (ctx->have_map[0] && ctx->have_map[1]), MML_ERR_STATE, "the root rank has no local map to broadcast");
+        MML_REQUIRE(r != root || (ctx->own.have_map[0] && ctx->own.have_map[1]), MML_ERR_STATE, "the root rank has no local map to broadcast");
         int rc = mml_sync_all(ctx);
         if (rc != MML_OK) return rc;
     }
     mml_ctx* src = ctxs[root];
-    int m[2] = {src->grid[0].m, src->grid[1].m};
+    int m[2] = {src->own.grid[0].m, src->own.grid[1].m};
     for (int r = 0; r < n_ranks; ++r) {
         mml_ctx* ctx = ctxs[r];
         MML_REQUIRE(m[0] >= 0 && m[1] >= 0 && m[0] <= ctx->MM && m[1] <= ctx->MM, MML_ERR_CAPACITY, "broadcast map exceeds max_map_points");
         if (r != root)
             for (int kind = 0; kind < 2; ++kind)
                 if (m[kind] > 0)
-                    MML_HIP(hipMemcpyAsync(ctx->map_tmp + (size_t)kind * ctx->MM, src->map_tmp + (size_t)kind * src->MM,
+                    MML_HIP(hipMemcpyAsync(ctx->own.map_tmp + (size_t)kind * ctx->MM, src->own.map_tmp + (size_t)kind * src->MM,
                                            sizeof(float4) * (size_t)m[kind], hipMemcpyDeviceToDevice, MML_STREAM(ctx)));
         int rc = local_map_received(ctx, m, r == root);
         if (rc != MML_OK) return rc;

@@ -1325,7 +1325,7 @@ static int build_grid_into(mml_ctx* ctx, MmlGrid& g, float4* orig, const float* 
     return mml_build_grids(ctx, 1, &job, W, &rounds);
 }
 
-int mml_build_grid(mml_ctx* ctx, const MmlMapRef& map, int kind, const float* h_xyz, int m) {
+int mml_build_grid(mml_ctx* ctx, MmlMapState& map, int kind, const float* h_xyz, int m) {
     MML_REQUIRE(kind == 0 || kind == 1, MML_ERR_INVALID, "map kind must be 0 (corner) or 1 (surf)");
     MML_REQUIRE(m >= 0 && m <= ctx->MM, MML_ERR_CAPACITY, "map larger than max_map_points");
     map.have_map[kind] = false;
@@ -1335,11 +1335,6 @@ int mml_build_grid(mml_ctx* ctx, const MmlMapRef& map, int kind, const float* h_
                              kind == 0 ? ctx->cfg.cell_corner : ctx->cfg.cell_surf, nullptr);
     if (rc == MML_OK) map.have_map[kind] = true;
     return rc;
-}
-
-// Same, for a cloud that is already on the device in the map's map_tmp + kind * MM (the map broadcast of comm.hip).
-int mml_build_grid_device(mml_ctx* ctx, const MmlMapRef& map, int kind, int m) {
-    return mml_build_grid(ctx, map, kind, nullptr, m);
 }
 
 // a12: the global map handed to Estimate() (Estimator.cpp:1170-1184) as one concatenated cloud with the cube index
@@ -1356,10 +1351,8 @@ int mml_cube_match_ensure(mml_ctx* ctx, MmlCubeMatch& G, int kind, int m) {
     return rc;
 }
 
-int mml_build_global_grid(mml_ctx* ctx, const MmlCubeRef& cube, int kind, const float* h_xyz, const int* h_cube, int m, const int* cen) {
-    MmlCubeMatch& G = *cube.match;
-    MML_REQUIRE(kind == 0 || kind == 1, MML_ERR_INVALID, "map kind must be 0 (corner) or 1 (surf)");
-    MML_REQUIRE(m >= 0 && m <= ctx->MM, MML_ERR_CAPACITY, "global map larger than max_map_points");
+int mml_build_global_grid(mml_ctx* ctx, MmlMapState& map, int kind, const float* h_xyz, const int* h_cube, int m, const int* cen) {
+    MmlCubeMatch& G = map.cmatch;
     hipStream_t s = MML_STREAM(ctx);
     G.have_gmap[kind] = false;
     ctx->banks.dirty = true;  // (the cube table of a context with banks holds a copy of this map's row)
@@ -1374,7 +1367,6 @@ int mml_build_global_grid(mml_ctx* ctx, const MmlCubeRef& cube, int kind, const 
     std::vector<uint16_t> tags((size_t)(m ? m : 1));
     std::vector<int> cnt(4851, 0);
     for (int i = 0; i < m; ++i) {
-        MML_REQUIRE(h_cube[i] >= 0 && h_cube[i] < 4851, MML_ERR_INVALID, "cube index outside [0, 4851)");
         tags[i] = (uint16_t)h_cube[i];
         cnt[h_cube[i]]++;
     }
@@ -1389,7 +1381,7 @@ int mml_build_global_grid(mml_ctx* ctx, const MmlCubeRef& cube, int kind, const 
 
 int mml_launch_knn5(mml_ctx* ctx, int kind, const float* d_q, int nq, float max_d2, int* d_idx, float* d_d2) {
     MmlStageScope t(ctx, "knn5");
-    hipLaunchKernelGGL(k_knn5, dim3((nq + 255) / 256), dim3(256), 0, MML_STREAM(ctx), ctx->grid[kind], d_q, nq, max_d2,
+    hipLaunchKernelGGL(k_knn5, dim3((nq + 255) / 256), dim3(256), 0, MML_STREAM(ctx), ctx->own.grid[kind], d_q, nq, max_d2,
                        d_idx, d_d2);
     MML_HIP(hipGetLastError());
     return MML_OK;
@@ -1402,21 +1394,22 @@ static int launch_associate(mml_ctx* ctx, AssocArgs<BANKED>& P, int first, int c
     P.first = first;
     P.B = ctx->B;
     P.MF = ctx->MF;
+    const MmlMapState& own = ctx->own;
     for (int k = 0; k < 2; ++k) {
-        P.g[k] = ctx->grid[k];
-        P.map_orig[k] = ctx->map_tmp + (size_t)k * ctx->MM;
+        P.g[k] = own.grid[k];
+        P.map_orig[k] = own.map_tmp + (size_t)k * ctx->MM;
         P.ft[k] = ctx->ft_xyz[k];
-        P.map_m[k] = ctx->grid[k].m;
+        P.map_m[k] = own.grid[k].m;
     }
     for (int k = 0; k < 2; ++k) {
-        P.gg[k] = ctx->cmatch.ggrid[k];
-        P.gmap_orig[k] = ctx->cmatch.gmap_orig[k];
-        P.cube_cnt[k] = ctx->cmatch.cube_cnt[k];
-        P.have_g[k] = ctx->cmatch.have_gmap[k] ? 1 : 0;
+        P.gg[k] = own.cmatch.ggrid[k];
+        P.gmap_orig[k] = own.cmatch.gmap_orig[k];
+        P.cube_cnt[k] = own.cmatch.cube_cnt[k];
+        P.have_g[k] = own.cmatch.have_gmap[k] ? 1 : 0;
     }
-    P.cen[0] = ctx->cmatch.cen[0];
-    P.cen[1] = ctx->cmatch.cen[1];
-    P.cen[2] = ctx->cmatch.cen[2];
+    P.cen[0] = own.cmatch.cen[0];
+    P.cen[1] = own.cmatch.cen[1];
+    P.cen[2] = own.cmatch.cen[2];
     P.ft_n = ctx->ft_n;
     P.lf = ctx->lf;
     P.pf = ctx->pf;
@@ -1476,7 +1469,7 @@ int mml_launch_associate(mml_ctx* ctx, int first, int count, const double* d_Twl
     int rc;
     if (mml_any_bound(ctx, first, count)) {
         // (the entry points bring the device copies up to date before they enqueue anything: mml_assoc_ready)
-        MML_REQUIRE(!ctx->banks.dirty && !ctx->cmatch.have_gmap[0] && !ctx->cmatch.have_gmap[1], MML_ERR_STATE,
+        MML_REQUIRE(!ctx->banks.dirty && !ctx->own.cmatch.have_gmap[0] && !ctx->own.cmatch.have_gmap[1], MML_ERR_STATE,
                     "association of a bound slot without mml_assoc_ready");
         bool cube = false;
         for (int i = 0; i < count; ++i) {
@@ -1490,7 +1483,7 @@ int mml_launch_associate(mml_ctx* ctx, int first, int count, const double* d_Twl
         rc = launch_associate<true>(ctx, P, first, count, d_Twl, thres_dist, cube);
     } else {
         AssocArgs<false> P;
-        rc = launch_associate<false>(ctx, P, first, count, d_Twl, thres_dist, ctx->cmatch.have_gmap[0] || ctx->cmatch.have_gmap[1]);
+        rc = launch_associate<false>(ctx, P, first, count, d_Twl, thres_dist, ctx->own.cmatch.have_gmap[0] || ctx->own.cmatch.have_gmap[1]);
     }
     if (rc != MML_OK) return rc;
     if (with_stats) return mml_ensure_assoc_stats(ctx, first, count);

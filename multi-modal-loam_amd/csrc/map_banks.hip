@@ -1,13 +1,13 @@
-// map_banks.hip -- map banks: N further local maps per context, and which scan slot is matched against which.
-//   A bank holds what the context's own local map holds (MmlMapBank, mml_internal.h); set, increment, reset and download run
-//   the code of the single-map calls on the bank's state (MmlMapRef).  The association kernels of a launch with a bound slot read
-//   the maps' grid descriptors from two device-resident tables, (banks + 1) rows x 2 kinds each -- the local maps and the global
-//   cube maps --, through the per-slot bank array (map_assoc.hip, the BANKED forms); this file keeps the three device arrays
-//   equal to the host's state.
-//   A bank has its own global cube map (MmlCubeMatch / MmlCubeLive, mml_internal.h): the mml_map_bank_global_* calls run the code
-//   of the own-map calls on it (MmlCubeRef): one chain of launches for n stores (map_global.hip), which the *_segmented forms
-//   and both appends run once for all n banks and the loop increment once per bank.  The context's OWN cube map and a bound
-//   slot exclude each other.
+// map_banks.hip -- the map entry points, and the map banks: N further Estimators' maps per context, and which scan slot is matched
+//   against which.
+//   The context's own maps and every bank's are one struct (MmlMapState, mml_internal.h; mml_map_at).  Each map call exists twice
+//   in the C API -- mml_map_* for the own maps, mml_map_bank_* for a bank's -- and once here: the public function checks what only
+//   it can check (a slot range; check_bank / check_distinct_banks) and calls the shared body with the state.
+//   The association kernels of a launch with a bound slot read the maps' grid descriptors from two device-resident tables,
+//   (banks + 1) rows x 2 kinds each -- the local maps and the global cube maps --, through the per-slot bank array (map_assoc.hip,
+//   the BANKED forms); mml_assoc_ready keeps the three device arrays equal to the host's state.
+//   The cube stores' upkeep is one chain of launches for n stores (map_global.hip), which the *_segmented forms and the appends run
+//   once for all n banks and the loop increment once per bank.  The context's OWN cube map and a bound slot exclude each other.
 #include <string.h>
 
 #include <algorithm>
@@ -34,6 +34,12 @@ int check_slot_range(mml_ctx* ctx, int first, int count) {
     return MML_OK;
 }
 
+// the slot of an own-map call
+int check_own_slot(mml_ctx* ctx, int slot) {
+    MML_REQUIRE(slot >= 0 && slot < ctx->B, MML_ERR_INVALID, "slot range out of bounds");
+    return MML_OK;
+}
+
 // n banks (and, where given, n slots) in range, no bank twice: the argument checks of the calls that work n banks through
 int check_distinct_banks(mml_ctx* ctx, int n, const int* banks, const int* slots, const char* who) {
     for (int i = 0; i < n; ++i) {
@@ -48,18 +54,136 @@ int check_distinct_banks(mml_ctx* ctx, int n, const int* banks, const int* slots
     return MML_OK;
 }
 
+const int kOwn = -1;  // the own maps in a list of banks
+
+std::vector<MmlMapState*> maps_at(mml_ctx* ctx, int n, const int* banks) {
+    std::vector<MmlMapState*> maps;
+    for (int i = 0; i < n; ++i) maps.push_back(&mml_map_at(ctx, banks[i]));
+    return maps;
+}
+
+// ---- the shared bodies: the caller has checked ctx and whatever names the map ----
+
+int set_local(mml_ctx* ctx, MmlMapState& map, int kind, const float* xyz, int m) {
+    MML_REQUIRE(m >= 0 && (m == 0 || xyz), MML_ERR_INVALID, "bad map arguments");
+    MML_HIP(hipSetDevice(ctx->device));
+    return mml_build_grid(ctx, map, kind, xyz, m);
+}
+
+int local_reset(mml_ctx* ctx, MmlMapState& map) {
+    const int rc = enter(ctx);
+    if (rc != MML_OK) return rc;
+    memset(map.ring_n, 0, sizeof(map.ring_n));
+    map.local_map_id = 0;
+    return MML_OK;
+}
+
+int local_download(mml_ctx* ctx, const MmlMapState& map, int kind, float* xyz, int capacity, int* n) {
+    MML_REQUIRE((kind == 0 || kind == 1) && n, MML_ERR_INVALID, "bad arguments");
+    MML_REQUIRE(map.have_map[kind], MML_ERR_STATE, map.name < 0 ? "no local map" : "the bank's last map build failed");
+    MML_HIP(hipSetDevice(ctx->device));
+    const int m = map.grid[kind].m;
+    *n = m;
+    if (!xyz || m == 0) return MML_OK;
+    MML_REQUIRE(capacity >= m, MML_ERR_CAPACITY, "capacity below the map size");
+    std::vector<float4> tmp((size_t)m);
+    MML_HIP(hipMemcpyAsync(tmp.data(), map.map_tmp + (size_t)kind * ctx->MM, sizeof(float4) * (size_t)m, hipMemcpyDeviceToHost, MML_STREAM(ctx)));
+    MML_HIP(hipStreamSynchronize(MML_STREAM(ctx)));
+    for (int i = 0; i < m; ++i) {
+        xyz[3 * i] = tmp[i].x;
+        xyz[3 * i + 1] = tmp[i].y;
+        xyz[3 * i + 2] = tmp[i].z;
+    }
+    return MML_OK;
+}
+
+// Estimator::MapIncrementLocal for the n maps `banks`: the context drained, then ONE chain for all of them (one_chain: all or
+// nothing) or one n = 1 chain per map in call order (a refusal leaves map i as it was, its two sizes 0, and maps 0 .. i-1 incremented)
+int local_increment(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl, int* n_corner, int* n_surf, bool one_chain) {
+    int rc = enter(ctx);
+    if (rc != MML_OK) return rc;
+    std::vector<MmlMapIncrement> inc;
+    for (int i = 0; i < n; ++i) inc.push_back(MmlMapIncrement{&mml_map_at(ctx, banks[i]), slots[i], T_wl + 16 * (size_t)i});
+    if (one_chain) return mml_map_upkeep_increment_segmented(ctx, n, inc.data(), n_corner, n_surf);
+    for (int i = 0; i < n && rc == MML_OK; ++i) {
+        if (n_corner) n_corner[i] = 0;
+        if (n_surf) n_surf[i] = 0;
+        rc = mml_map_upkeep_increment_segmented(ctx, 1, &inc[(size_t)i], n_corner ? n_corner + i : nullptr, n_surf ? n_surf + i : nullptr);
+    }
+    return rc;
+}
+
+// Validates everything and drains the context before the map changes: a refused call leaves the match copy as it was.
+int set_global(mml_ctx* ctx, MmlMapState& map, int kind, const float* xyz, const int* cube, int m, const int* cen) {
+    MML_REQUIRE(kind == 0 || kind == 1, MML_ERR_INVALID, "map kind must be 0 (corner) or 1 (surf)");
+    MML_REQUIRE(m >= 0 && (m == 0 || (xyz && cube)), MML_ERR_INVALID, "bad global map arguments");
+    MML_REQUIRE(m <= ctx->MM, MML_ERR_CAPACITY, "global map larger than max_map_points");
+    for (int i = 0; i < m; ++i) MML_REQUIRE(cube[i] >= 0 && cube[i] < 4851, MML_ERR_INVALID, "cube index outside [0, 4851)");
+    const int rc = enter(ctx);
+    if (rc != MML_OK) return rc;
+    return mml_build_global_grid(ctx, map, kind, xyz, cube, m, cen);
+}
+
+// the context drained, then ONE append chain for all n stores (map_global.hip): every slot's stacks are checked before a store's
+// pending clouds change
+int global_append(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl) {
+    const int rc = enter(ctx);
+    if (rc != MML_OK) return rc;
+    return mml_cube_store_append_segmented(ctx, n, maps_at(ctx, n, banks).data(), slots, T_wl);
+}
+
+// the context drained, then ONE increment chain for all n stores or one n = 1 chain per store, as local_increment
+int global_increment(mml_ctx* ctx, int n, const int* banks, const double* T_wl, int* n_corner, int* n_surf, bool one_chain) {
+    int rc = enter(ctx);
+    if (rc != MML_OK) return rc;
+    const std::vector<MmlMapState*> maps = maps_at(ctx, n, banks);
+    if (one_chain) return mml_cube_store_increment_segmented(ctx, n, maps.data(), T_wl, n_corner, n_surf);
+    for (int i = 0; i < n && rc == MML_OK; ++i) {
+        if (n_corner) n_corner[i] = 0;
+        if (n_surf) n_surf[i] = 0;
+        rc = mml_cube_store_increment_segmented(ctx, 1, &maps[(size_t)i], T_wl + 16 * (size_t)i, n_corner ? n_corner + i : nullptr,
+                                                n_surf ? n_surf + i : nullptr);
+    }
+    return rc;
+}
+
+int global_download(mml_ctx* ctx, const MmlMapState& map, int kind, float* xyz, int* cube, int capacity, int* n, int* cen) {
+    MML_REQUIRE((kind == 0 || kind == 1) && n, MML_ERR_INVALID, "bad arguments");
+    MML_HIP(hipSetDevice(ctx->device));
+    return mml_cube_store_download(ctx, map, kind, xyz, cube, capacity, n, cen);
+}
+
+int global_reset(mml_ctx* ctx, MmlMapState& map) {
+    const int rc = enter(ctx);
+    if (rc != MML_OK) return rc;
+    return mml_cube_store_reset(ctx, map);
+}
+
+// the checks of the bank calls that work n banks through
+int check_bank_call(mml_ctx* ctx, int n, const int* banks, const int* slots, bool need_slots, const double* T_wl, const char* who) {
+    MML_REQUIRE(n >= 1 && banks && (slots || !need_slots) && T_wl, MML_ERR_INVALID, "bad arguments");
+    return check_distinct_banks(ctx, n, banks, slots, who);
+}
+
 }  // namespace
+
+int mml_map_local_alloc(mml_ctx* ctx, MmlMapState& map) {
+    const size_t MM = (size_t)ctx->MM;
+    return map.grid_mem.reserve(ctx, {mml_part(map.grid[0].pts, MM), mml_part(map.grid[0].cell_start, 4 * MM + 4096 + 2), mml_part(map.grid[1].pts, MM),
+                                      mml_part(map.grid[1].cell_start, 4 * MM + 4096 + 2), mml_part(map.map_tmp, 2 * MM)});
+}
 
 int mml_assoc_ready(mml_ctx* ctx, int first, int count, const char* who) {
     MmlBanks& K = ctx->banks;
+    const MmlMapState& own = ctx->own;
     bool bound = false;
     for (int i = 0; i < count; ++i) {
         const int bank = K.n_bound ? K.slot_bank[(size_t)first + i] : -1;
         if (bank < 0) {
-            if (!(ctx->have_map[0] && ctx->have_map[1])) return mml_refuse(ctx, MML_ERR_STATE, "%s before both maps were set", who);
+            if (!(own.have_map[0] && own.have_map[1])) return mml_refuse(ctx, MML_ERR_STATE, "%s before both maps were set", who);
             continue;
         }
-        if (ctx->cmatch.have_gmap[0] || ctx->cmatch.have_gmap[1])
+        if (own.cmatch.have_gmap[0] || own.cmatch.have_gmap[1])
             return mml_refuse(ctx, MML_ERR_STATE, "%s: slot %d is bound to map bank %d and the context's own global cube map is set (a bank has its own)",
                               who, first + i, bank);
         bound = true;
@@ -71,9 +195,10 @@ int mml_assoc_ready(mml_ctx* ctx, int first, int count, const char* who) {
     const size_t rows = 2 * (K.bank.size() + 1);
     std::vector<MmlMapDesc> t(rows);
     std::vector<MmlCubeDesc> tc(rows);
-    for (size_t e = 0; e <= K.bank.size(); ++e)
+    for (size_t e = 0; e <= K.bank.size(); ++e) {
+        const MmlMapState& M = mml_map_at(ctx, (int)e - 1);
         for (int k = 0; k < 2; ++k) {
-            const MmlCubeMatch& G = e == 0 ? ctx->cmatch : K.bank[e - 1].cmatch;
+            const MmlCubeMatch& G = M.cmatch;
             MmlCubeDesc& c = tc[2 * e + k];
             memset(static_cast<void*>(&c), 0, sizeof(c));
             c.g = G.ggrid[k];
@@ -83,10 +208,11 @@ int mml_assoc_ready(mml_ctx* ctx, int first, int count, const char* who) {
             for (int a = 0; a < 3; ++a) c.cen[a] = G.cen[a];
             MmlMapDesc& d = t[2 * e + k];
             memset(static_cast<void*>(&d), 0, sizeof(d));  // (the padding too: the rows are compared and copied as bytes)
-            d.g = e == 0 ? ctx->grid[k] : K.bank[e - 1].grid[k];
-            d.orig = (e == 0 ? ctx->map_tmp : K.bank[e - 1].map_tmp) + (size_t)k * ctx->MM;
-            if (e == 0 && !ctx->have_map[k]) d.g.m = 0;  // (an unset own map: only bound slots are in the launch)
+            d.g = M.grid[k];
+            d.orig = M.map_tmp + (size_t)k * ctx->MM;
+            if (e == 0 && !M.have_map[k]) d.g.m = 0;  // (an unset own map: only bound slots are in the launch)
         }
+    }
     hipStream_t s = ctx->streams[0];
     MML_HIP(hipMemcpyAsync(K.d_table, t.data(), sizeof(MmlMapDesc) * rows, hipMemcpyHostToDevice, s));
     MML_HIP(hipMemcpyAsync(K.d_cube_table, tc.data(), sizeof(MmlCubeDesc) * rows, hipMemcpyHostToDevice, s));
@@ -110,13 +236,13 @@ int mml_map_banks_create(mml_ctx* ctx, int n_banks) {
     K.slot_bank.assign((size_t)ctx->B, -1);
     K.n_bound = 0;
     K.dirty = true;
-    const size_t MM = (size_t)ctx->MM;
     rc = K.tab_mem.reserve(ctx, {mml_part(K.d_table, 2 * ((size_t)n_banks + 1)), mml_part(K.d_cube_table, 2 * ((size_t)n_banks + 1)),
                                  mml_part(K.d_slot_bank, (size_t)ctx->B)});
     for (int b = 0; b < n_banks && rc == MML_OK; ++b) {
-        MmlMapBank& m = K.bank[(size_t)b];
-        rc = m.grid_mem.reserve(ctx, {mml_part(m.grid[0].pts, MM), mml_part(m.grid[0].cell_start, 4 * MM + 4096 + 2), mml_part(m.grid[1].pts, MM),
-                                      mml_part(m.grid[1].cell_start, 4 * MM + 4096 + 2), mml_part(m.map_tmp, 2 * MM)});
+        MmlMapState& m = K.bank[(size_t)b];
+        m.name = b;
+        m.have_map[0] = m.have_map[1] = true;  // a bank that was never set is an empty map
+        rc = mml_map_local_alloc(ctx, m);
     }
     if (rc != MML_OK) K.release();
     return rc;
@@ -127,50 +253,6 @@ int mml_map_banks_destroy(mml_ctx* ctx) {
     const int rc = enter(ctx);
     if (rc != MML_OK) return rc;
     ctx->banks.release();
-    return MML_OK;
-}
-
-int mml_map_bank_set_local(mml_ctx* ctx, int bank, int kind, const float* xyz, int m) {
-    if (!ctx) return MML_ERR_INVALID;
-    int rc = check_bank(ctx, bank);
-    if (rc != MML_OK) return rc;
-    MML_REQUIRE(m >= 0 && (m == 0 || xyz), MML_ERR_INVALID, "bad map arguments");
-    MML_HIP(hipSetDevice(ctx->device));
-    return mml_build_grid(ctx, mml_map_bank(ctx, bank), kind, xyz, m);
-}
-
-int mml_map_bank_reset(mml_ctx* ctx, int bank) {
-    if (!ctx) return MML_ERR_INVALID;
-    int rc = check_bank(ctx, bank);
-    if (rc != MML_OK) return rc;
-    rc = enter(ctx);
-    if (rc != MML_OK) return rc;
-    MmlMapBank& b = ctx->banks.bank[(size_t)bank];
-    memset(b.ring_n, 0, sizeof(b.ring_n));
-    b.local_map_id = 0;
-    return MML_OK;
-}
-
-int mml_map_bank_download(mml_ctx* ctx, int bank, int kind, float* xyz, int capacity, int* n) {
-    if (!ctx) return MML_ERR_INVALID;
-    int rc = check_bank(ctx, bank);
-    if (rc != MML_OK) return rc;
-    MML_REQUIRE((kind == 0 || kind == 1) && n, MML_ERR_INVALID, "bad arguments");
-    const MmlMapBank& b = ctx->banks.bank[(size_t)bank];
-    MML_REQUIRE(b.have_map[kind], MML_ERR_STATE, "the bank's last map build failed");
-    MML_HIP(hipSetDevice(ctx->device));
-    const int m = b.grid[kind].m;
-    *n = m;
-    if (!xyz || m == 0) return MML_OK;
-    MML_REQUIRE(capacity >= m, MML_ERR_CAPACITY, "capacity below the map size");
-    std::vector<float4> tmp((size_t)m);
-    MML_HIP(hipMemcpyAsync(tmp.data(), b.map_tmp + (size_t)kind * ctx->MM, sizeof(float4) * (size_t)m, hipMemcpyDeviceToHost, MML_STREAM(ctx)));
-    MML_HIP(hipStreamSynchronize(MML_STREAM(ctx)));
-    for (int i = 0; i < m; ++i) {
-        xyz[3 * i] = tmp[i].x;
-        xyz[3 * i + 1] = tmp[i].y;
-        xyz[3 * i + 2] = tmp[i].z;
-    }
     return MML_OK;
 }
 
@@ -187,7 +269,7 @@ int mml_slot_bind_bank(mml_ctx* ctx, int first_slot, int count, const int* banks
             return mml_refuse(ctx, MML_ERR_INVALID, "slot %d: map bank %d outside [-1, %d)", first_slot + i, banks[i], n);
         any = any || banks[i] >= 0;
     }
-    if (any && (ctx->cmatch.have_gmap[0] || ctx->cmatch.have_gmap[1]))
+    if (any && (ctx->own.cmatch.have_gmap[0] || ctx->own.cmatch.have_gmap[1]))
         return mml_refuse(ctx, MML_ERR_STATE, "the context's own global cube map is set: a bound slot is matched against its bank's");
     if (n == 0) return MML_OK;  // (all -1 on a context without banks: nothing to record)
     for (int i = 0; i < count; ++i) {
@@ -209,113 +291,11 @@ int mml_slot_bank_get(mml_ctx* ctx, int first_slot, int count, int* banks) {
     return MML_OK;
 }
 
-int mml_map_bank_increment(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl, int* n_corner, int* n_surf) {
-    if (!ctx) return MML_ERR_INVALID;
-    MML_REQUIRE(n >= 1 && banks && slots && T_wl, MML_ERR_INVALID, "bad arguments");
-    // all arguments are checked before the device is touched or a bank changes
-    int rc = check_distinct_banks(ctx, n, banks, slots, "mml_map_bank_increment");
-    if (rc != MML_OK) return rc;
-    rc = enter(ctx);
-    if (rc != MML_OK) return rc;
-    if (!ctx->uploads.empty()) return mml_refuse(ctx, MML_ERR_STATE, "uploads in flight after a drained context");
-    for (int i = 0; i < n; ++i) {
-        int m[2] = {0, 0};
-        rc = mml_map_upkeep_increment(ctx, mml_map_bank(ctx, banks[i]), slots[i], T_wl + 16 * (size_t)i, m);
-        if (n_corner) n_corner[i] = m[0];
-        if (n_surf) n_surf[i] = m[1];
-        if (rc != MML_OK) return rc;
-    }
-    return MML_OK;
-}
-
-int mml_map_bank_increment_segmented(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl, int* n_corner, int* n_surf) {
-    if (!ctx) return MML_ERR_INVALID;
-    MML_REQUIRE(n >= 1 && banks && slots && T_wl, MML_ERR_INVALID, "bad arguments");
-    // all arguments are checked before the device is touched or a bank changes
-    int rc = check_distinct_banks(ctx, n, banks, slots, "mml_map_bank_increment_segmented");
-    if (rc != MML_OK) return rc;
-    rc = enter(ctx);
-    if (rc != MML_OK) return rc;
-    if (!ctx->uploads.empty()) return mml_refuse(ctx, MML_ERR_STATE, "uploads in flight after a drained context");
-    std::vector<MmlMapIncrement> inc;
-    for (int i = 0; i < n; ++i) inc.push_back(MmlMapIncrement{mml_map_bank(ctx, banks[i]), slots[i], T_wl + 16 * (size_t)i});
-    return mml_map_upkeep_increment_segmented(ctx, n, inc.data(), n_corner, n_surf);
-}
-
 int mml_debug_bank_increment_budget(mml_ctx* ctx, long points) {
     if (!ctx) return MML_ERR_INVALID;
     if (points < 1 || points >= (1l << 31)) return mml_refuse(ctx, MML_ERR_INVALID, "the chunk budget must be in [1, 2^31) points");
     ctx->bank_inc.budget = points;
     return MML_OK;
-}
-
-// ---- a bank's global cube map: the own-map calls of capi.hip on mml_cube_bank(ctx, bank) ----
-
-int mml_map_bank_set_global(mml_ctx* ctx, int bank, int kind, const float* xyz, const int* cube, int m, const int* cen) {
-    if (!ctx) return MML_ERR_INVALID;
-    int rc = check_bank(ctx, bank);
-    if (rc != MML_OK) return rc;
-    MML_REQUIRE(kind == 0 || kind == 1, MML_ERR_INVALID, "map kind must be 0 (corner) or 1 (surf)");
-    MML_REQUIRE(m >= 0 && (m == 0 || (xyz && cube)), MML_ERR_INVALID, "bad global map arguments");
-    MML_REQUIRE(m <= ctx->MM, MML_ERR_CAPACITY, "global map larger than max_map_points");
-    for (int i = 0; i < m; ++i) MML_REQUIRE(cube[i] >= 0 && cube[i] < 4851, MML_ERR_INVALID, "cube index outside [0, 4851)");
-    rc = enter(ctx);
-    if (rc != MML_OK) return rc;
-    return mml_build_global_grid(ctx, mml_cube_bank(ctx, bank), kind, xyz, cube, m, cen);
-}
-
-// a call's arguments checked and the context drained, then ONE append chain for all n banks (map_global.hip): every slot's stacks
-// are checked before a bank's pending clouds change
-static int global_append(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl, const char* who) {
-    if (!ctx) return MML_ERR_INVALID;
-    MML_REQUIRE(n >= 1 && banks && slots && T_wl, MML_ERR_INVALID, "bad arguments");
-    int rc = check_distinct_banks(ctx, n, banks, slots, who);
-    if (rc != MML_OK) return rc;
-    rc = enter(ctx);
-    if (rc != MML_OK) return rc;
-    if (!ctx->uploads.empty()) return mml_refuse(ctx, MML_ERR_STATE, "uploads in flight after a drained context");
-    std::vector<MmlCubeRef> cubes;
-    for (int i = 0; i < n; ++i) cubes.push_back(mml_cube_bank(ctx, banks[i]));
-    return mml_cube_store_append_segmented(ctx, n, cubes.data(), banks, slots, T_wl);
-}
-
-int mml_map_bank_global_append(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl) {
-    return global_append(ctx, n, banks, slots, T_wl, "mml_map_bank_global_append");
-}
-
-int mml_map_bank_global_append_segmented(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl) {
-    return global_append(ctx, n, banks, slots, T_wl, "mml_map_bank_global_append_segmented");
-}
-
-// the loop: one n = 1 chain per bank, in call order; a refusal leaves bank i as it was and banks 0 .. i-1 incremented
-int mml_map_bank_global_increment(mml_ctx* ctx, int n, const int* banks, const double* T_wl, int* n_corner, int* n_surf) {
-    if (!ctx) return MML_ERR_INVALID;
-    MML_REQUIRE(n >= 1 && banks && T_wl, MML_ERR_INVALID, "bad arguments");
-    int rc = check_distinct_banks(ctx, n, banks, nullptr, "mml_map_bank_global_increment");
-    if (rc != MML_OK) return rc;
-    rc = enter(ctx);
-    if (rc != MML_OK) return rc;
-    for (int i = 0; i < n; ++i) {
-        int m[2] = {0, 0};
-        rc = mml_cube_store_increment(ctx, mml_cube_bank(ctx, banks[i]), banks[i], T_wl + 16 * (size_t)i, m);
-        if (n_corner) n_corner[i] = m[0];
-        if (n_surf) n_surf[i] = m[1];
-        if (rc != MML_OK) return rc;
-    }
-    return MML_OK;
-}
-
-// ONE chain for all n banks
-int mml_map_bank_global_increment_segmented(mml_ctx* ctx, int n, const int* banks, const double* T_wl, int* n_corner, int* n_surf) {
-    if (!ctx) return MML_ERR_INVALID;
-    MML_REQUIRE(n >= 1 && banks && T_wl, MML_ERR_INVALID, "bad arguments");
-    int rc = check_distinct_banks(ctx, n, banks, nullptr, "mml_map_bank_global_increment_segmented");
-    if (rc != MML_OK) return rc;
-    rc = enter(ctx);
-    if (rc != MML_OK) return rc;
-    std::vector<MmlCubeRef> cubes;
-    for (int i = 0; i < n; ++i) cubes.push_back(mml_cube_bank(ctx, banks[i]));
-    return mml_cube_store_increment_segmented(ctx, n, cubes.data(), banks, T_wl, n_corner, n_surf);
 }
 
 int mml_debug_bank_global_increment_budget(mml_ctx* ctx, long points) {
@@ -325,22 +305,131 @@ int mml_debug_bank_global_increment_budget(mml_ctx* ctx, long points) {
     return MML_OK;
 }
 
+// ---- the map calls: the own maps', then the banks' ----
+
+int mml_map_set_local(mml_ctx* ctx, int kind, const float* xyz, int m) {
+    if (!ctx) return MML_ERR_INVALID;
+    return set_local(ctx, ctx->own, kind, xyz, m);
+}
+
+int mml_map_local_reset(mml_ctx* ctx) {
+    if (!ctx) return MML_ERR_INVALID;
+    return local_reset(ctx, ctx->own);
+}
+
+int mml_map_local_download(mml_ctx* ctx, int kind, float* xyz, int capacity, int* n) {
+    if (!ctx) return MML_ERR_INVALID;
+    return local_download(ctx, ctx->own, kind, xyz, capacity, n);
+}
+
+int mml_map_increment_local(mml_ctx* ctx, int slot, const double* T_wl, int* n_corner_map, int* n_surf_map) {
+    if (!ctx) return MML_ERR_INVALID;
+    const int rc = check_own_slot(ctx, slot);
+    if (rc != MML_OK) return rc;
+    MML_REQUIRE(T_wl, MML_ERR_INVALID, "null transform");
+    return local_increment(ctx, 1, &kOwn, &slot, T_wl, n_corner_map, n_surf_map, false);
+}
+
+int mml_map_set_global(mml_ctx* ctx, int kind, const float* xyz, const int* cube, int m, const int* cen) {
+    if (!ctx) return MML_ERR_INVALID;
+    return set_global(ctx, ctx->own, kind, xyz, cube, m, cen);
+}
+
+int mml_map_global_append(mml_ctx* ctx, int slot, const double* T_wl) {
+    if (!ctx) return MML_ERR_INVALID;
+    const int rc = check_own_slot(ctx, slot);
+    if (rc != MML_OK) return rc;
+    MML_REQUIRE(T_wl, MML_ERR_INVALID, "null transform");
+    return global_append(ctx, 1, &kOwn, &slot, T_wl);
+}
+
+int mml_map_global_increment(mml_ctx* ctx, const double* T_wl, int* n_corner, int* n_surf) {
+    if (!ctx) return MML_ERR_INVALID;
+    MML_REQUIRE(T_wl, MML_ERR_INVALID, "null transform");
+    return global_increment(ctx, 1, &kOwn, T_wl, n_corner, n_surf, false);
+}
+
+int mml_map_global_download(mml_ctx* ctx, int kind, float* xyz, int* cube, int capacity, int* n, int* cen) {
+    if (!ctx) return MML_ERR_INVALID;
+    return global_download(ctx, ctx->own, kind, xyz, cube, capacity, n, cen);
+}
+
+int mml_map_global_reset(mml_ctx* ctx) {
+    if (!ctx) return MML_ERR_INVALID;
+    return global_reset(ctx, ctx->own);
+}
+
+int mml_map_bank_set_local(mml_ctx* ctx, int bank, int kind, const float* xyz, int m) {
+    if (!ctx) return MML_ERR_INVALID;
+    const int rc = check_bank(ctx, bank);
+    return rc != MML_OK ? rc : set_local(ctx, mml_map_at(ctx, bank), kind, xyz, m);
+}
+
+int mml_map_bank_reset(mml_ctx* ctx, int bank) {
+    if (!ctx) return MML_ERR_INVALID;
+    const int rc = check_bank(ctx, bank);
+    return rc != MML_OK ? rc : local_reset(ctx, mml_map_at(ctx, bank));
+}
+
+int mml_map_bank_download(mml_ctx* ctx, int bank, int kind, float* xyz, int capacity, int* n) {
+    if (!ctx) return MML_ERR_INVALID;
+    const int rc = check_bank(ctx, bank);
+    return rc != MML_OK ? rc : local_download(ctx, mml_map_at(ctx, bank), kind, xyz, capacity, n);
+}
+
+// all arguments are checked before the device is touched or a bank changes
+int mml_map_bank_increment(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl, int* n_corner, int* n_surf) {
+    if (!ctx) return MML_ERR_INVALID;
+    const int rc = check_bank_call(ctx, n, banks, slots, true, T_wl, "mml_map_bank_increment");
+    return rc != MML_OK ? rc : local_increment(ctx, n, banks, slots, T_wl, n_corner, n_surf, false);
+}
+
+int mml_map_bank_increment_segmented(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl, int* n_corner, int* n_surf) {
+    if (!ctx) return MML_ERR_INVALID;
+    const int rc = check_bank_call(ctx, n, banks, slots, true, T_wl, "mml_map_bank_increment_segmented");
+    return rc != MML_OK ? rc : local_increment(ctx, n, banks, slots, T_wl, n_corner, n_surf, true);
+}
+
+int mml_map_bank_set_global(mml_ctx* ctx, int bank, int kind, const float* xyz, const int* cube, int m, const int* cen) {
+    if (!ctx) return MML_ERR_INVALID;
+    const int rc = check_bank(ctx, bank);
+    return rc != MML_OK ? rc : set_global(ctx, mml_map_at(ctx, bank), kind, xyz, cube, m, cen);
+}
+
+int mml_map_bank_global_append(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl) {
+    if (!ctx) return MML_ERR_INVALID;
+    const int rc = check_bank_call(ctx, n, banks, slots, true, T_wl, "mml_map_bank_global_append");
+    return rc != MML_OK ? rc : global_append(ctx, n, banks, slots, T_wl);
+}
+
+int mml_map_bank_global_append_segmented(mml_ctx* ctx, int n, const int* banks, const int* slots, const double* T_wl) {
+    if (!ctx) return MML_ERR_INVALID;
+    const int rc = check_bank_call(ctx, n, banks, slots, true, T_wl, "mml_map_bank_global_append_segmented");
+    return rc != MML_OK ? rc : global_append(ctx, n, banks, slots, T_wl);
+}
+
+int mml_map_bank_global_increment(mml_ctx* ctx, int n, const int* banks, const double* T_wl, int* n_corner, int* n_surf) {
+    if (!ctx) return MML_ERR_INVALID;
+    const int rc = check_bank_call(ctx, n, banks, nullptr, false, T_wl, "mml_map_bank_global_increment");
+    return rc != MML_OK ? rc : global_increment(ctx, n, banks, T_wl, n_corner, n_surf, false);
+}
+
+int mml_map_bank_global_increment_segmented(mml_ctx* ctx, int n, const int* banks, const double* T_wl, int* n_corner, int* n_surf) {
+    if (!ctx) return MML_ERR_INVALID;
+    const int rc = check_bank_call(ctx, n, banks, nullptr, false, T_wl, "mml_map_bank_global_increment_segmented");
+    return rc != MML_OK ? rc : global_increment(ctx, n, banks, T_wl, n_corner, n_surf, true);
+}
+
 int mml_map_bank_global_download(mml_ctx* ctx, int bank, int kind, float* xyz, int* cube, int capacity, int* n, int* cen) {
     if (!ctx) return MML_ERR_INVALID;
-    int rc = check_bank(ctx, bank);
-    if (rc != MML_OK) return rc;
-    MML_REQUIRE((kind == 0 || kind == 1) && n, MML_ERR_INVALID, "bad arguments");
-    MML_HIP(hipSetDevice(ctx->device));
-    return mml_cube_store_download(ctx, mml_cube_bank(ctx, bank), kind, xyz, cube, capacity, n, cen);
+    const int rc = check_bank(ctx, bank);
+    return rc != MML_OK ? rc : global_download(ctx, mml_map_at(ctx, bank), kind, xyz, cube, capacity, n, cen);
 }
 
 int mml_map_bank_global_reset(mml_ctx* ctx, int bank) {
     if (!ctx) return MML_ERR_INVALID;
-    int rc = check_bank(ctx, bank);
-    if (rc != MML_OK) return rc;
-    rc = enter(ctx);
-    if (rc != MML_OK) return rc;
-    return mml_cube_store_reset(ctx, mml_cube_bank(ctx, bank));
+    const int rc = check_bank(ctx, bank);
+    return rc != MML_OK ? rc : global_reset(ctx, mml_map_at(ctx, bank));
 }
 
 }  // extern "C"

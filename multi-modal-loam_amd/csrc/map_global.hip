@@ -2,7 +2,7 @@
 // context's own store and every map bank's (include/mmloam_hip.h) through ONE chain of launches for n stores:
 //   MAP_MANAGER::featureAssociateToMap (Map_Manager.cpp:91-117)  -> mml_cube_store_append_segmented      (features of n slots -> world)
 //   MAP_MANAGER::MapIncrement (:125-281) + MapMove (:288-581)     -> mml_cube_store_increment_segmented
-// mml_cube_store_append / _increment are the chain with n = 1; there is no other implementation.
+// The own-map calls (map_banks.hip) are the chain with n = 1 on mml_ctx::own; there is no other implementation.
 // The reference keeps 4851 PCL clouds per kind and rotates pointers between them; here a store is ONE array of points with a
 // 16-bit cube tag each (the layout k_associate consumes, a12):
 //   * MapMove becomes per-axis counts of layer shifts applied to the tags; a point whose layer leaves the 21 x 21 x 11 grid is
@@ -293,9 +293,9 @@ int plan_move(mml_ctx* ctx, const int* cen_now, const double* T_wl, Move& M) {
     return MML_OK;
 }
 
-// a refusal that names store `name`: a bank, or -1 for the context's own store (the text alone)
-int refuse_store(mml_ctx* ctx, int code, int name, const char* what) {
-    return name < 0 ? mml_refuse(ctx, code, "%s", what) : mml_refuse(ctx, code, "map bank %d: %s", name, what);
+// a refusal that names the map's store: a bank, or the text alone for the context's own
+int refuse_store(mml_ctx* ctx, int code, const MmlMapState& map, const char* what) {
+    return map.name < 0 ? mml_refuse(ctx, code, "%s", what) : mml_refuse(ctx, code, "map bank %d: %s", map.name, what);
 }
 
 // what the chain of one chunk leaves on the host for the commit
@@ -323,14 +323,14 @@ struct Chunk {
         return sizeof(CubeSegDev) * (size_t)nseg + sizeof(int) * 10 * (size_t)nseg + mml_grid_table_bytes(nseg) + 16 * 8;
     }
     // the chunk's rows in the pinned twin (the match phase fills m_pts / m_tag / m_cnt in), the read-backs zeroed / emptied
-    long long fill(const MmlCubeRef* cubes, const Move* mv, bool match) const {
+    long long fill(MmlMapState* const* maps, const Move* mv, bool match) const {
         CubeSegDev* h = f_seg.in(K.tab.h);
         const int empty[6] = MML_BBOX_EMPTY;
         long long total = 0;
         for (int g = 0; g < nseg; ++g) {
             const int i = i0 + g / 2, kind = g & 1;
-            const MmlCubeLive& L = *cubes[i].live;
-            const MmlCubeMatch& G = *cubes[i].match;
+            const MmlCubeLive& L = maps[i]->clive;
+            const MmlCubeMatch& G = maps[i]->cmatch;
             CubeSegDev& S = h[g];
             memset(static_cast<void*>(&S), 0, sizeof(S));
             S.spts = L.gs_pts[kind];
@@ -360,12 +360,12 @@ struct Chunk {
 };
 
 // the store chain of one chunk: writes scratch and the stores' second buffers only.  res: the call's 2 n results.
-int chain_chunk(const Chunk& C, const MmlCubeRef* cubes, const int* names, const Move* mv, SegResult* res) {
+int chain_chunk(const Chunk& C, MmlMapState* const* maps, const Move* mv, SegResult* res) {
     mml_ctx* ctx = C.ctx;
     mml_ctx::BankCube& K = C.K;
     hipStream_t s = MML_STREAM(ctx);
     const int nseg = C.nseg;
-    const long long total = C.fill(cubes, mv, false);
+    const long long total = C.fill(maps, mv, false);
     MML_REQUIRE(total <= (long long)K.cap && nseg <= K.seg_cap, MML_ERR_CAPACITY, "cube increment: more points than the scratch holds");
     if (total == 0) return MML_OK;  // (nothing stored, nothing pending: every size stays 0)
     const int P = (int)total;
@@ -402,7 +402,7 @@ int chain_chunk(const Chunk& C, const MmlCubeRef* cubes, const int* names, const
     for (int g = 0; g < nseg; ++g) {
         const int nk = h_back[g], nsel = h_back[nseg + g];
         if (nk + (long long)nsel > ctx->MM)
-            return refuse_store(ctx, MML_ERR_CAPACITY, names[C.i0 + g / 2], "cube store larger than max_map_points");
+            return refuse_store(ctx, MML_ERR_CAPACITY, *maps[C.i0 + g / 2], "cube store larger than max_map_points");
         res[2 * (size_t)C.i0 + g].nk = nk;
         nsel_total += nsel;
         max_sel = std::max(max_sel, nsel);
@@ -430,7 +430,7 @@ int chain_chunk(const Chunk& C, const MmlCubeRef* cubes, const int* names, const
 }
 
 // the match copies of one chunk, from the live arrays the chain has not touched: every capacity decision of the call has passed
-int match_chunk(const Chunk& C, const MmlCubeRef* cubes, const Move* mv, int* rounds) {
+int match_chunk(const Chunk& C, MmlMapState* const* maps, const Move* mv, int* rounds) {
     mml_ctx* ctx = C.ctx;
     mml_ctx::BankCube& K = C.K;
     hipStream_t s = MML_STREAM(ctx);
@@ -438,13 +438,13 @@ int match_chunk(const Chunk& C, const MmlCubeRef* cubes, const Move* mv, int* ro
     int max_n0 = 0;
     bool grows = false;
     for (int g = 0; g < nseg; ++g) {
-        const MmlCubeMatch& G = *cubes[C.i0 + g / 2].match;
-        grows = grows || !mml_cube_match_fits(G, g & 1, cubes[C.i0 + g / 2].live->gs_n[g & 1]);
+        const MmlMapState& M = *maps[C.i0 + g / 2];
+        grows = grows || !mml_cube_match_fits(M.cmatch, g & 1, M.clive.gs_n[g & 1]);
     }
     if (grows) MML_HIP(hipStreamSynchronize(s));  // (a copy that has to grow is replaced with nothing in flight: at most one more wait)
     for (int g = 0; g < nseg; ++g) {
-        MmlCubeMatch& G = *cubes[C.i0 + g / 2].match;
-        const MmlCubeLive& L = *cubes[C.i0 + g / 2].live;
+        MmlCubeMatch& G = maps[C.i0 + g / 2]->cmatch;
+        const MmlCubeLive& L = maps[C.i0 + g / 2]->clive;
         const int kind = g & 1;
         G.have_gmap[kind] = false;
         for (int a = 0; a < 3; ++a) G.cen[a] = L.gs_cen[a];  // the centre BEFORE MapMove (laserCloudCen*_last)
@@ -453,7 +453,7 @@ int match_chunk(const Chunk& C, const MmlCubeRef* cubes, const Move* mv, int* ro
         max_n0 = std::max(max_n0, L.gs_n[kind]);
     }
     ctx->banks.dirty = true;  // (the cube table of a context with banks holds a copy of these maps' rows)
-    C.fill(cubes, mv, true);
+    C.fill(maps, mv, true);
     MML_HIP(hipMemcpyAsync(K.tab.d, K.tab.h, C.up_bytes, hipMemcpyHostToDevice, s));
     const CubeSegDev* d_seg = C.f_seg.in(K.tab.d);
     int* d_mbox = C.f_mbox.in(K.tab.d);
@@ -464,15 +464,15 @@ int match_chunk(const Chunk& C, const MmlCubeRef* cubes, const Move* mv, int* ro
     MML_HIP(hipStreamSynchronize(s));  // the bounding boxes of all match copies
     std::vector<MmlGridJob> jobs((size_t)nseg);
     for (int g = 0; g < nseg; ++g) {
-        MmlCubeMatch& G = *cubes[C.i0 + g / 2].match;
+        MmlCubeMatch& G = maps[C.i0 + g / 2]->cmatch;
         const int kind = g & 1;
         jobs[g] = MmlGridJob{&G.ggrid[kind], G.gmap_orig[kind], kind == 0 ? ctx->cfg.cell_corner : ctx->cfg.cell_surf,
-                             cubes[C.i0 + g / 2].live->gs_n[kind], h_mbox + 6 * (size_t)g, G.gtag_orig[kind]};
+                             maps[C.i0 + g / 2]->clive.gs_n[kind], h_mbox + 6 * (size_t)g, G.gtag_orig[kind]};
     }
     const MmlGridScratch<unsigned long long> W{K.keys, K.keys + K.cap, K.vals, K.vals + K.cap, K.cap, C.f_grid.in(K.tab.d), C.f_grid.in(K.tab.h)};
     const int rc = mml_build_grids(ctx, nseg, jobs.data(), W, rounds);
     if (rc != MML_OK) return rc;
-    for (int g = 0; g < nseg; ++g) cubes[C.i0 + g / 2].match->have_gmap[g & 1] = jobs[g].m > 0;
+    for (int g = 0; g < nseg; ++g) maps[C.i0 + g / 2]->cmatch.have_gmap[g & 1] = jobs[g].m > 0;
     return MML_OK;
 }
 
@@ -480,8 +480,8 @@ int match_chunk(const Chunk& C, const MmlCubeRef* cubes, const Move* mv, int* ro
 
 // The store's own memory (72 bytes x max_map_points + 2 x 16 x max_features x 16 bytes), allocated by the first call that needs it.
 // The scratch the chain works in is the context's bank_cube, grown by the increment to the points it works on.
-int mml_cube_store_ensure(mml_ctx* ctx, const MmlCubeRef& cube) {
-    MmlCubeLive& L = *cube.live;
+int mml_cube_store_ensure(mml_ctx* ctx, MmlMapState& map) {
+    MmlCubeLive& L = map.clive;
     if (L.mem.present()) return MML_OK;
     const size_t MM = (size_t)ctx->MM;
     const size_t gp = 16 * (size_t)ctx->MF;
@@ -491,8 +491,8 @@ int mml_cube_store_ensure(mml_ctx* ctx, const MmlCubeRef& cube) {
               mml_part(L.gs_pts[1], MM), mml_part(L.gs_tag[1], MM), mml_part(L.gs_pts2[1], MM), mml_part(L.gs_tag2[1], MM), mml_part(L.gp_pts[1], gp)});
 }
 
-int mml_cube_store_reset(mml_ctx* ctx, const MmlCubeRef& cube) {
-    MmlCubeLive& L = *cube.live;
+int mml_cube_store_reset(mml_ctx* ctx, MmlMapState& map) {
+    MmlCubeLive& L = map.clive;
     L.gs_n[0] = L.gs_n[1] = 0;
     L.gp_n[0] = L.gp_n[1] = 0;
     L.gs_cen[0] = 10;
@@ -502,8 +502,8 @@ int mml_cube_store_reset(mml_ctx* ctx, const MmlCubeRef& cube) {
 }
 
 // the LIVE store (tests / visualisation): points, cube index of every point, centre
-int mml_cube_store_download(mml_ctx* ctx, const MmlCubeRef& ref, int kind, float* xyz, int* cube, int capacity, int* n, int* cen) {
-    const MmlCubeLive& L = *ref.live;
+int mml_cube_store_download(mml_ctx* ctx, const MmlMapState& map, int kind, float* xyz, int* cube, int capacity, int* n, int* cen) {
+    const MmlCubeLive& L = map.clive;
     hipStream_t s = MML_STREAM(ctx);
     const int m = L.gs_pts[kind] ? L.gs_n[kind] : 0;
     *n = m;
@@ -541,23 +541,22 @@ std::vector<int> mml_cube_chunks(int n, const long long* pts, long long budget, 
     return cut;
 }
 
-int mml_cube_store_increment_segmented(mml_ctx* ctx, int n, const MmlCubeRef* cubes, const int* names, const double* T_wl, int* n_corner,
-                                       int* n_surf) {
+int mml_cube_store_increment_segmented(mml_ctx* ctx, int n, MmlMapState* const* maps, const double* T_wl, int* n_corner, int* n_surf) {
     hipStream_t s = MML_STREAM(ctx);
     mml_ctx::BankCube& K = ctx->bank_cube;
     // MapMove of every store on a host copy of its centre: a pose outside the grid refuses the call before the device is touched
     std::vector<Move> mv((size_t)n);
     for (int i = 0; i < n; ++i) {
-        const int rc = plan_move(ctx, cubes[i].live->gs_cen, T_wl + 16 * (size_t)i, mv[i]);
-        if (rc != MML_OK) return refuse_store(ctx, rc, names[i], "pose far outside the cube grid");
+        const int rc = plan_move(ctx, maps[i]->clive.gs_cen, T_wl + 16 * (size_t)i, mv[i]);
+        if (rc != MML_OK) return refuse_store(ctx, rc, *maps[i], "pose far outside the cube grid");
     }
     // memory, all of it before the first launch: the stores (a first increment), the scratch of the largest chunk, its tables,
     // the temporary storage of the sorts and scans
     std::vector<long long> pts((size_t)n);
     for (int i = 0; i < n; ++i) {
-        const int rc = mml_cube_store_ensure(ctx, cubes[i]);
+        const int rc = mml_cube_store_ensure(ctx, *maps[i]);
         if (rc != MML_OK) return rc;
-        const MmlCubeLive& L = *cubes[i].live;
+        const MmlCubeLive& L = maps[i]->clive;
         pts[i] = (long long)L.gs_n[0] + L.gp_n[0] + L.gs_n[1] + L.gp_n[1];
     }
     const std::vector<int> cut = mml_cube_chunks(n, pts.data(), K.budget, MML_BANK_GLOBAL_CHUNK_BANKS);
@@ -597,18 +596,18 @@ int mml_cube_store_increment_segmented(mml_ctx* ctx, int n, const MmlCubeRef* cu
     std::vector<Chunk> chunks;
     for (size_t c = 0; c + 1 < cut.size(); ++c) chunks.emplace_back(ctx, cut[c], cut[c + 1]);
     for (const Chunk& C : chunks) {
-        const int rc = chain_chunk(C, cubes, names, mv.data(), res.data());
+        const int rc = chain_chunk(C, maps, mv.data(), res.data());
         if (rc != MML_OK) return rc;
     }
     // the match copies: the stores as they are, with their centres before MapMove (Map_Manager.cpp:136-149)
     for (const Chunk& C : chunks) {
         int rounds = 0;
-        const int rc = match_chunk(C, cubes, mv.data(), &rounds);
+        const int rc = match_chunk(C, maps, mv.data(), &rounds);
         if (rc != MML_OK) return rc;
     }
     // the commit: the buffer pairs swapped, sizes, centres, the pending clouds emptied
     for (int i = 0; i < n; ++i) {
-        MmlCubeLive& L = *cubes[i].live;
+        MmlCubeLive& L = maps[i]->clive;
         for (int kind = 0; kind < 2; ++kind) {
             std::swap(L.gs_pts[kind], L.gs_pts2[kind]);
             std::swap(L.gs_tag[kind], L.gs_tag2[kind]);
@@ -623,7 +622,7 @@ int mml_cube_store_increment_segmented(mml_ctx* ctx, int n, const MmlCubeRef* cu
     return MML_OK;
 }
 
-int mml_cube_store_append_segmented(mml_ctx* ctx, int n, const MmlCubeRef* cubes, const int* names, const int* slots, const double* T_wl) {
+int mml_cube_store_append_segmented(mml_ctx* ctx, int n, MmlMapState* const* maps, const int* slots, const double* T_wl) {
     hipStream_t s = MML_STREAM(ctx);
     mml_ctx::BankCube& K = ctx->bank_cube;
     // the stack sizes in one copy (the context's 2 B ints), those of the n slots checked before a store's pending clouds change
@@ -639,11 +638,11 @@ int mml_cube_store_append_segmented(mml_ctx* ctx, int n, const MmlCubeRef* cubes
         for (int kind = 0; kind < 2; ++kind) {
             const int f = nf[2 * (size_t)i + kind];
             if (f < 0 || f > ctx->MF) return mml_refuse(ctx, MML_ERR_STATE, "slot %d holds no down-sampled feature stack", slots[i]);
-            if (cubes[i].live->gp_n[kind] + (long long)f > 16ll * ctx->MF)
-                return refuse_store(ctx, MML_ERR_CAPACITY, names[i], "too many pending map points (16 x max_features)");
+            if (maps[i]->clive.gp_n[kind] + (long long)f > 16ll * ctx->MF)
+                return refuse_store(ctx, MML_ERR_CAPACITY, *maps[i], "too many pending map points (16 x max_features)");
         }
     for (int i = 0; i < n; ++i) {
-        const int rc = mml_cube_store_ensure(ctx, cubes[i]);
+        const int rc = mml_cube_store_ensure(ctx, *maps[i]);
         if (rc != MML_OK) return rc;
     }
     const size_t nseg = 2 * (size_t)n;
@@ -652,7 +651,7 @@ int mml_cube_store_append_segmented(mml_ctx* ctx, int n, const MmlCubeRef* cubes
     CubeAppDev* h = reinterpret_cast<CubeAppDev*>(K.tab.h);
     int max_n = 0;
     for (int i = 0; i < n; ++i) {
-        MmlCubeLive& L = *cubes[i].live;
+        MmlCubeLive& L = maps[i]->clive;
         for (int kind = 0; kind < 2; ++kind) {
             CubeAppDev& S = h[2 * (size_t)i + kind];
             memset(static_cast<void*>(&S), 0, sizeof(S));
@@ -669,15 +668,6 @@ int mml_cube_store_append_segmented(mml_ctx* ctx, int n, const MmlCubeRef* cubes
         MML_HIP(hipGetLastError());
     }
     for (int i = 0; i < n; ++i)
-        for (int kind = 0; kind < 2; ++kind) cubes[i].live->gp_n[kind] += nf[2 * (size_t)i + kind];
+        for (int kind = 0; kind < 2; ++kind) maps[i]->clive.gp_n[kind] += nf[2 * (size_t)i + kind];
     return MML_OK;
-}
-
-// one store: the chain with n = 1
-int mml_cube_store_append(mml_ctx* ctx, const MmlCubeRef& cube, int name, int slot, const double* T_wl) {
-    return mml_cube_store_append_segmented(ctx, 1, &cube, &name, &slot, T_wl);
-}
-
-int mml_cube_store_increment(mml_ctx* ctx, const MmlCubeRef& cube, int name, const double* T_wl, int* n_out) {
-    return mml_cube_store_increment_segmented(ctx, 1, &cube, &name, T_wl, n_out, n_out ? n_out + 1 : nullptr);
 }

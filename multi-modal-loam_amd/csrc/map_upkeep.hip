@@ -347,7 +347,7 @@ __global__ __launch_bounds__(256) void k_inc_bbox_out(const IncSegDev* __restric
 }
 
 // what a message calls a map
-std::string map_name(const MmlMapRef& map) { return map.bank < 0 ? std::string("the context's own local map") : "map bank " + std::to_string(map.bank); }
+std::string map_name(const MmlMapState& map) { return map.name < 0 ? std::string("the context's own local map") : "map bank " + std::to_string(map.name); }
 
 // one chunk of maps [i0, i1) of the call: steps 2-4.  nf: the call's 2 n stack sizes.
 int increment_chunk(mml_ctx* ctx, int i0, int i1, const MmlMapIncrement* inc, const int* nf, int* n_corner, int* n_surf) {
@@ -368,8 +368,8 @@ int increment_chunk(mml_ctx* ctx, int i0, int i1, const MmlMapIncrement* inc, co
     long long total = 0;
     int max_feat = 0, max_total = 0;
     for (int i = i0; i < i1; ++i) {
-        const MmlMapRef& map = inc[i].map;
-        const int Id = (int)(*map.local_map_id % W);  // :1597
+        MmlMapState& map = *inc[i].map;
+        const int Id = (int)(map.local_map_id % W);  // :1597
         for (int kind = 0; kind < 2; ++kind) {
             const int g = 2 * (i - i0) + kind, n = nf[2 * (size_t)i + kind];
             map.ring_n[kind][Id] = n;
@@ -423,10 +423,10 @@ int increment_chunk(mml_ctx* ctx, int i0, int i1, const MmlMapIncrement* inc, co
     MML_HIP(hipStreamSynchronize(s));  // the chunk's second synchronisation of 2 + R (the first read the stack sizes)
     for (int g = 0; g < nseg; ++g)
         if (h_back[g] > ctx->MM)
-            return mml_refuse(ctx, MML_ERR_CAPACITY, "%s: filtered local map larger than max_map_points", map_name(inc[i0 + g / 2].map).c_str());
+            return mml_refuse(ctx, MML_ERR_CAPACITY, "%s: filtered local map larger than max_map_points", map_name(*inc[i0 + g / 2].map).c_str());
     std::vector<MmlGridJob> jobs((size_t)nseg);
     for (int g = 0; g < nseg; ++g) {
-        const MmlMapRef& map = inc[i0 + g / 2].map;
+        MmlMapState& map = *inc[i0 + g / 2].map;
         const int kind = g & 1;
         map.have_map[kind] = false;  // (mml_build_grid)
         map.grid[kind].tags = nullptr;
@@ -439,14 +439,14 @@ int increment_chunk(mml_ctx* ctx, int i0, int i1, const MmlMapIncrement* inc, co
     const int rc = mml_build_grids(ctx, nseg, jobs.data(), G, &rounds);
     if (rc != MML_OK) return rc;
     for (int i = i0; i < i1; ++i) {
-        const MmlMapRef& map = inc[i].map;
+        MmlMapState& map = *inc[i].map;
         for (int kind = 0; kind < 2; ++kind) {
             map.have_map[kind] = true;
             map.local_map_n[kind] = h_back[2 * (i - i0) + kind];
         }
         if (n_corner) n_corner[i] = map.local_map_n[0];
         if (n_surf) n_surf[i] = map.local_map_n[1];
-        ++*map.local_map_id;  // :1642
+        ++map.local_map_id;  // :1642
     }
     return MML_OK;
 }
@@ -473,8 +473,8 @@ int mml_map_upkeep_increment_segmented(mml_ctx* ctx, int n, const MmlMapIncremen
     // every segment's ring total after the write, the filter's own limit and the chunks: greedy, in call order
     std::vector<long long> pts((size_t)n);
     for (int i = 0; i < n; ++i) {
-        const MmlMapRef& map = inc[i].map;
-        const int Id = (int)(*map.local_map_id % W);
+        MmlMapState& map = *inc[i].map;
+        const int Id = (int)(map.local_map_id % W);
         pts[i] = 0;
         for (int kind = 0; kind < 2; ++kind) {
             long long t = nf[2 * (size_t)i + kind];
@@ -502,9 +502,9 @@ int mml_map_upkeep_increment_segmented(mml_ctx* ctx, int n, const MmlMapIncremen
     // all before the first launch, so that nothing is replaced while a chunk's kernels run
     const size_t ring_pts = (size_t)W * ctx->MF;
     for (int i = 0; i < n; ++i) {
-        const MmlMapRef& map = inc[i].map;
-        if (map.ring_mem->present()) continue;
-        const int rc = map.ring_mem->reserve(ctx, {mml_part(map.ring[0], ring_pts), mml_part(map.ring[1], ring_pts)});
+        MmlMapState& map = *inc[i].map;
+        if (map.ring_mem.present()) continue;
+        const int rc = map.ring_mem.reserve(ctx, {mml_part(map.ring[0], ring_pts), mml_part(map.ring[1], ring_pts)});
         if (rc != MML_OK) return rc;
     }
     if ((size_t)max_pts > K.cap || !K.mem.present()) {
@@ -530,13 +530,4 @@ int mml_map_upkeep_increment_segmented(mml_ctx* ctx, int n, const MmlMapIncremen
     }
     MML_HIP(hipGetLastError());
     return MML_OK;
-}
-
-// one map: the chain with n = 1, its two kinds two segments
-int mml_map_upkeep_increment(mml_ctx* ctx, const MmlMapRef& map, int slot, const double* T_wl, int* n_out) {
-    const MmlMapIncrement inc{map, slot, T_wl};
-    int n[2] = {0, 0};
-    const int rc = mml_map_upkeep_increment_segmented(ctx, 1, &inc, &n[0], &n[1]);
-    if (rc == MML_OK && n_out) n_out[0] = n[0], n_out[1] = n[1];
-    return rc;
 }

@@ -62,8 +62,8 @@ struct MmlGrid {         // radix-sorted uniform grid over one map cloud (replac
     int ncell = 1;
 };
 
-// The global cube map of one Estimator (a12 + map_global.hip), in two parts.  The context has one pair of its own and every map
-// bank one more (MmlCubeRef below); the scratch the upkeep works in (bank_cube, the sort buffers) is the context's.
+// The global cube map of one Estimator (a12 + map_global.hip), in two parts, both held by the Estimator's MmlMapState below; the
+// scratch the upkeep works in (bank_cube, the sort buffers) is the context's.
 // The MATCH COPY: what Estimate() matches against -- tagged grids over the concatenated cube clouds, the unsorted clouds with
 // their tags, the 4851 cube counts, laserCloudCen*_last.  Sized by need (mml_cube_match_ensure).
 struct MmlCubeMatch {
@@ -103,22 +103,32 @@ struct MmlCubeLive {
     MmlGroup mem;                              // owns gs_pts .. gp_pts
 };
 
-// One more local map beside the context's own (mml_map_banks_create): the same state -- the two grids with their unsorted clouds,
-// the key-scan ring with its counts, localMapID, the two map sizes -- and one more global cube map (cmatch / clive; no memory
-// before the bank's first set_global / append / increment).  A bank that was never set is an empty map.
+// The maps of one Estimator: the local map -- the two grids with their unsorted clouds, the key-scan ring with its counts,
+// localMapID, the two map sizes -- and the global cube map (cmatch / clive).  The context holds one of its own (mml_ctx::own) and
+// every map bank one more (mml_map_banks_create); all code that works on "a map" takes this struct (mml_map_at).  Only the grids'
+// arrays exist from the start (mml_map_local_alloc): the ring comes with the first increment, the live store with the first
+// append / increment, the match copy is sized by need.  As defined here a state is the context's own, whose two kinds are unset
+// until mml_map_set_local; a bank is created set and empty.
 #define MML_LOCAL_WINDOW 50  // localMapWindowSize, Estimator.h:326
-struct MmlMapBank {
+struct MmlMapState {
+    int name = -1;                           // what a message calls it: the bank, -1 the context's own
     MmlCubeMatch cmatch;
     MmlCubeLive clive;
     MmlGrid grid[2];
-    bool have_map[2] = {true, true};
+    bool have_map[2] = {false, false};
     float4* map_tmp = nullptr;               // 2 x MM: the unsorted clouds
     MmlGroup grid_mem;                       // owns grid[k].pts / cell_start and map_tmp
     float4* ring[2] = {nullptr, nullptr};    // MML_LOCAL_WINDOW x MF each
-    MmlGroup ring_mem;                       // owns ring[2]; allocated by the bank's first increment
+    MmlGroup ring_mem;                       // owns ring[2]
     int ring_n[2][MML_LOCAL_WINDOW] = {};
-    long local_map_id = 0;
+    long local_map_id = 0;                   // localMapID
     int local_map_n[2] = {0, 0};
+    void release() {
+        grid_mem.release();
+        ring_mem.release();
+        cmatch.release();
+        clive.mem.release();
+    }
 };
 // What the association kernels read of one local map of one kind: a row of the device-resident table of a context with banks.
 struct alignas(16) MmlMapDesc {
@@ -139,7 +149,7 @@ struct alignas(16) MmlCubeDesc {
 static_assert(sizeof(MmlCubeDesc) % 16 == 0 && sizeof(MmlCubeDesc) / 4 <= 32, "a descriptor is read as dwords, at most 32");
 static_assert(offsetof(MmlCubeDesc, g) == 0 && offsetof(MmlMapDesc, g) == 0, "the grid leads both rows");
 struct MmlBanks {
-    std::vector<MmlMapBank> bank;
+    std::vector<MmlMapState> bank;    // sized once by mml_map_banks_create: pointers into it hold until mml_map_banks_destroy
     std::vector<int> slot_bank;       // B: bank of every slot, -1 = the context's own map
     int n_bound = 0;                  // slots with a bank
     MmlMapDesc* d_table = nullptr;    // (banks + 1) x 2 kinds; row 0: the context's own map
@@ -148,12 +158,7 @@ struct MmlBanks {
     MmlGroup tab_mem;                 // owns the three
     bool dirty = true;                // a grid, a match copy or a binding changed since the device copies were written (mml_assoc_ready)
     void release() {
-        for (MmlMapBank& b : bank) {
-            b.grid_mem.release();
-            b.ring_mem.release();
-            b.cmatch.release();
-            b.clive.mem.release();
-        }
+        for (MmlMapState& b : bank) b.release();
         bank.clear();
         slot_bank.clear();
         tab_mem.release();
@@ -334,21 +339,11 @@ struct mml_ctx {
     int4* hard_list = nullptr;     // B * MF * 2 queued (slot, kind, feature) triples
     double* assoc_stats = nullptr; // B * 16: n_line, n_plane, n_line_used, n_plane_used, gram[9], ...
 
-    // maps
-    MmlGrid grid[2];
-    bool have_map[2] = {false, false};
-    // global cube map (a12) and the device-side MAP_MANAGER cube stores (map_global.hip): the context's own pair
-    MmlCubeMatch cmatch;
-    MmlCubeLive clive;
-    // device-side local map upkeep (Estimator::MapIncrementLocal): ring of key scans' features in the world frame
+    // maps: the context's own (what an unbound slot is matched against) and the banks'
+    MmlMapState own;
     static constexpr int LOCAL_WINDOW = MML_LOCAL_WINDOW;
-    float4* ring[2] = {nullptr, nullptr};    // LOCAL_WINDOW x MF each
-    MmlGroup ring_mem;                       // owns ring[2]; allocated by the first increment, like a bank's
-    int ring_n[2][LOCAL_WINDOW] = {};
-    long local_map_id = 0;                   // localMapID
     MmlStaging<char, false> wire_stage;      // raw message bytes on their way in / out (one call at a time; grows to the largest)
-    int local_map_n[2] = {0, 0};
-    MmlBanks banks;                    // map banks (map_banks.hip): further local maps, and which slot is matched against which
+    MmlBanks banks;                    // map banks (map_banks.hip): further maps, and which slot is matched against which
     // scratch of the local-map increment (map_upkeep.hip mml_map_upkeep_increment_segmented), of the own map's as of the banks':
     // sized by the ring points of the largest chunk of maps a call has worked on, 48 bytes per point
     struct BankInc {
@@ -411,7 +406,6 @@ struct mml_ctx {
             n_maps = 0;
         }
     } world;
-    float4* map_tmp = nullptr;
     unsigned* map_keys = nullptr;
     unsigned* map_keys2 = nullptr;
     unsigned* map_vals = nullptr;
@@ -453,15 +447,13 @@ struct mml_ctx {
         win_state.release();
         seg_scratch.release();
         for (auto& t : seg_tmp) t.release();
-        cmatch.release();
-        ring_mem.release();
+        own.release();
         banks.release();
         bank_inc.mem.release();
         bank_inc.tab.release();
         bank_cube.mem.release();
         bank_cube.tab.release();
         world.release();
-        clive.mem.release();
         wire_stage.release();
         grid_tab.release();
         sort_tmp.release();
@@ -531,31 +523,14 @@ int mml_cloud_settle(mml_ctx* ctx, int first, int count);
 int mml_launch_downsample(mml_ctx* ctx, int first, int count);
 // labelled corner points per (slot, kind) that the LDS sort of k_voxel takes (surf: MML_VOXEL_LDS_CAP)
 inline int mml_voxel_cap_corner(const mml_ctx* ctx) { return (ctx->NT > 65536 || MML_VOXEL_LDS_CAP < 2048) ? MML_VOXEL_LDS_CAP : 2048; }
-// The state of one local map, by reference: the context's own fields (mml_map_own) or a bank's (mml_map_bank).  Map upkeep and
-// the grid build take the maps they work on as this parameter -- there is one increment chain and one grid builder, each written
-// for n maps, and the own map is simply one more; the scratch they use (bank_inc, the sort buffers) is the context's either way.
-struct MmlMapRef {
-    MmlGrid* grid;      // [2]
-    bool* have_map;     // [2]
-    float4* map_tmp;    // 2 x MM
-    float4** ring;      // [2]
-    MmlGroup* ring_mem; // owns ring[2]
-    int (*ring_n)[MML_LOCAL_WINDOW];  // [2]
-    long* local_map_id;
-    int* local_map_n;   // [2]
-    int bank;           // what a message calls the map: the bank, -1 the context's own
-};
-inline MmlMapRef mml_map_own(mml_ctx* c) {
-    return MmlMapRef{c->grid, c->have_map, c->map_tmp, c->ring, &c->ring_mem, c->ring_n, &c->local_map_id, c->local_map_n, -1};
-}
-inline MmlMapRef mml_map_bank(mml_ctx* c, int bank) {
-    MmlMapBank& b = c->banks.bank[(size_t)bank];
-    return MmlMapRef{b.grid, b.have_map, b.map_tmp, b.ring, &b.ring_mem, b.ring_n, &b.local_map_id, b.local_map_n, bank};
-}
-int mml_build_grid(mml_ctx* ctx, const MmlMapRef& map, int kind, const float* h_xyz, int m);
-int mml_build_grid_device(mml_ctx* ctx, const MmlMapRef& map, int kind, int m);
-inline int mml_build_grid(mml_ctx* ctx, int kind, const float* h_xyz, int m) { return mml_build_grid(ctx, mml_map_own(ctx), kind, h_xyz, m); }
-inline int mml_build_grid_device(mml_ctx* ctx, int kind, int m) { return mml_build_grid_device(ctx, mml_map_own(ctx), kind, m); }
+// The maps of bank `bank`, -1: the context's own.
+inline MmlMapState& mml_map_at(mml_ctx* ctx, int bank) { return bank < 0 ? ctx->own : ctx->banks.bank[(size_t)bank]; }
+// map_banks.hip: the arrays every local map has from the start -- grid[k].pts, grid[k].cell_start, map_tmp -- for the own map
+// (mml_create) as for a bank
+int mml_map_local_alloc(mml_ctx* ctx, MmlMapState& map);
+// map_assoc.hip, the one-cloud grid build: kind `kind` of the map's local map from m host points (null: the cloud is in the map's
+// map_tmp + kind * MM already, the map broadcast of comm.hip).  The scratch it uses (the sort buffers) is the context's.
+int mml_build_grid(mml_ctx* ctx, MmlMapState& map, int kind, const float* h_xyz, int m);
 // map_banks.hip.  mml_assoc_ready: the state checks of a call that associates slots [first, first + count) -- an unbound slot needs
 // the context's two maps (`who` before both maps were set), a bound one that the context's OWN global cube map is unset -- and the
 // device copies of the two descriptor tables and the bindings brought up to date (a drained context and small copies, only after
@@ -574,15 +549,13 @@ int mml_downsample_big(mml_ctx* ctx, int first, int count);
 int mml_downsample_redo_overflow(mml_ctx* ctx, int first, int count, std::vector<int>* redone);
 // Estimator::MapIncrementLocal (map_upkeep.hip): map `map` grows by the two stacks of `slot` at T_wl (16 doubles, row-major).
 struct MmlMapIncrement {
-    MmlMapRef map;
+    MmlMapState* map;
     int slot;
     const double* T_wl;
 };
-// n distinct maps in one chain of launches; the caller has checked the arguments and drained the context.  Checks every slot's
-// stack before a map changes: all or nothing.
+// n distinct maps in one chain of launches (one map: n = 1, its two kinds two segments); the caller has checked the arguments
+// and drained the context.  Checks every slot's stack before a map changes: all or nothing.
 int mml_map_upkeep_increment_segmented(mml_ctx* ctx, int n, const MmlMapIncrement* inc, int* n_corner, int* n_surf);
-// one map: the chain with n = 1
-int mml_map_upkeep_increment(mml_ctx* ctx, const MmlMapRef& map, int slot, const double* T_wl, int* n_out);
 // map_assoc.hip, the grid build: nseg clouds that are on the device, one sort and one read-back per refinement round for all of
 // them.  A job: the grid to fill (its pts / cell_start / tags are the destination), the unsorted cloud, the configured cell edge,
 // the cloud's size, its bounding box as six keys (MML_BBOX_EMPTY where m = 0), and the points' tags in the cloud's order (null: the
@@ -605,35 +578,22 @@ struct MmlGridScratch {
 size_t mml_grid_table_bytes(int nseg);
 template <class Key>
 int mml_build_grids(mml_ctx* ctx, int nseg, const MmlGridJob* jobs, const MmlGridScratch<Key>& W, int* rounds);
-// The state of one global cube map, by reference: the context's own (mml_cube_own) or a bank's (mml_cube_bank).  The grid builds
-// and the store's upkeep take the map they work on as this parameter, as the local map's take MmlMapRef.
-struct MmlCubeRef {
-    MmlCubeMatch* match;
-    MmlCubeLive* live;
-};
-inline MmlCubeRef mml_cube_own(mml_ctx* c) { return MmlCubeRef{&c->cmatch, &c->clive}; }
-inline MmlCubeRef mml_cube_bank(mml_ctx* c, int bank) {
-    MmlMapBank& b = c->banks.bank[(size_t)bank];
-    return MmlCubeRef{&b.cmatch, &b.clive};
-}
-int mml_build_global_grid(mml_ctx* ctx, const MmlCubeRef& cube, int kind, const float* h_xyz, const int* h_cube, int m, const int* cen);
+// the match copy of the map's cube map set from host points (map_assoc.hip); the caller has checked the arguments -- the cube indices
+// too -- and drained the context
+int mml_build_global_grid(mml_ctx* ctx, MmlMapState& map, int kind, const float* h_xyz, const int* h_cube, int m, const int* cen);
 // The one capacity rule of a match copy: room for m points of `kind` (at least 1024; the cube counts move with the rest, every
 // builder rewrites them).  A copy that has to grow is replaced, so the caller waits for work in flight first -- once per call,
 // when mml_cube_match_fits says no.
 inline bool mml_cube_match_fits(const MmlCubeMatch& G, int kind, int m) { return m <= G.gmap_cap[kind] && G.ggrid_mem[kind].present(); }
 int mml_cube_match_ensure(mml_ctx* ctx, MmlCubeMatch& G, int kind, int m);
-int mml_cube_store_download(mml_ctx* ctx, const MmlCubeRef& cube, int kind, float* xyz, int* cube_idx, int capacity, int* n, int* cen);
-int mml_cube_store_reset(mml_ctx* ctx, const MmlCubeRef& cube);
-int mml_cube_store_ensure(mml_ctx* ctx, const MmlCubeRef& cube);  // the store's own memory, on first use
-// The upkeep (map_global.hip): n DISTINCT stores in one chain of launches; the caller has checked the arguments and drained the
-// context.  names[i]: what a message calls store i -- its bank, or -1 for the context's own store (no prefix).  Every refusal leaves
+int mml_cube_store_download(mml_ctx* ctx, const MmlMapState& map, int kind, float* xyz, int* cube_idx, int capacity, int* n, int* cen);
+int mml_cube_store_reset(mml_ctx* ctx, MmlMapState& map);
+int mml_cube_store_ensure(mml_ctx* ctx, MmlMapState& map);  // the store's own memory, on first use
+// The upkeep (map_global.hip): the stores of n DISTINCT maps in one chain of launches; the caller has checked the arguments and
+// drained the context.  A message names a bank's store by the map's name, the context's own by no prefix.  Every refusal leaves
 // all n stores -- live arrays, tags, centres, pending clouds, match copies -- as they were.
-int mml_cube_store_increment_segmented(mml_ctx* ctx, int n, const MmlCubeRef* cubes, const int* names, const double* T_wl, int* n_corner,
-                                       int* n_surf);
-int mml_cube_store_append_segmented(mml_ctx* ctx, int n, const MmlCubeRef* cubes, const int* names, const int* slots, const double* T_wl);
-// one store: the same chain with n = 1.  n_out: the two sizes (corner, surf).
-int mml_cube_store_append(mml_ctx* ctx, const MmlCubeRef& cube, int name, int slot, const double* T_wl);
-int mml_cube_store_increment(mml_ctx* ctx, const MmlCubeRef& cube, int name, const double* T_wl, int* n_out);
+int mml_cube_store_increment_segmented(mml_ctx* ctx, int n, MmlMapState* const* maps, const double* T_wl, int* n_corner, int* n_surf);
+int mml_cube_store_append_segmented(mml_ctx* ctx, int n, MmlMapState* const* maps, const int* slots, const double* T_wl);
 // The chunks of such a call: chunk c = stores [cut[c], cut[c + 1]) -- greedy, in call order, at most `budget` points (pts[i]: store +
 // pending, both kinds) and at most max_stores stores per chunk, a store over the budget a chunk of its own.
 std::vector<int> mml_cube_chunks(int n, const long long* pts, long long budget, int max_stores);

@@ -3,7 +3,7 @@ and the cube stage of the association for bound slots.
 
 Everything here is bit-equality against a context without banks whose OWN maps hold the same clouds.  The banked kernels run the
 arithmetic of the unbanked ones in the same order (one template, csrc/map_assoc.hip) and the banks' upkeep is the own store's
-code on the bank's state (MmlCubeRef), so no tolerance is needed and none is used.
+code on the bank's state (MmlMapState), so no tolerance is needed and none is used.
 
 Slot counts 6 and 12 lie on either side of `fresh_all = count <= 8` (csrc/map_assoc.hip): both launch forms run."""
 import importlib
@@ -432,5 +432,88 @@ def test_append_without_a_stack_is_refused(M, synth, cube_scene):
         c.bank_global_append([0], [0], T[:1])
         nc, ns = c.bank_global_increment([0], T[:1])
         assert (int(nc[0]), int(ns[0])) == (50, 60)
+    finally:
+        c.close()
+
+
+def _cube_ctx(M, cs, max_map_points, bank):
+    """Two slots, one bank, the cube scene's local map in the own map and in bank 0; slot 0 bound to `bank` (-1: unbound)."""
+    c = M.Context(max_scans=2, max_map_points=max_map_points)
+    c.map_banks(1)
+    for kind, name in ((0, "corner"), (1, "surf")):
+        c.map_set_local(kind, cs[name + "_local"])
+        c.bank_set_local(0, kind, cs[name + "_local"])
+    c.bind_banks(0, [bank])
+    _load_features(c, cs, 1)
+    return c
+
+
+def _set_global(c, bank, kind, xyz, cube, cen=None):
+    if bank < 0:
+        c.map_set_global(kind, xyz, cube, cen)
+    else:
+        c.bank_set_global(bank, kind, xyz, cube, cen)
+
+
+def test_own_cube_map_and_bank_are_the_same_code(M, cube_scene):
+    """The same cube map in the context's own and in bank 0: equal factor records of a slot matched against either; then one
+    append + increment of both stores from the same slot and pose: equal sizes, points, cube indices and centre."""
+    cs = cube_scene
+    T = _poses(cs, 1)
+    c = _cube_ctx(M, cs, MM, -1)
+    try:
+        rec = {}
+        for bank in (-1, 0):
+            for kind, name in ((0, "corner"), (1, "surf")):
+                _set_global(c, bank, kind, cs[name + "_global"], cs[name + "_cube"], [10, 5, 10])
+            c.bind_banks(0, [bank])
+            c.associate(0, 1, T, 1.0)
+            rec[bank] = _records(c, 0)
+            if bank < 0:                                  # the own cube map and a bound slot exclude each other
+                for kind in (0, 1):
+                    c.map_set_global(kind, EMPTY, NOCUBE)
+        assert rec[-1] == rec[0] and len(c.factors_download(0, 1)[1]) > 0
+        c.map_global_append(0, T[0])
+        c.bank_global_append([0], [0], T)
+        n_own = c.map_global_increment(T[0])
+        nb = c.bank_global_increment([0], T)
+        assert n_own == (int(nb[0][0]), int(nb[1][0])) and min(n_own) > 0
+        for kind in (0, 1):
+            own, bnk = c.map_global_download(kind), c.bank_global_download(0, kind)
+            assert len(own[0]) == n_own[kind] and all(a.tobytes() == b.tobytes() for a, b in zip(own, bnk)), kind
+    finally:
+        c.close()
+
+
+@pytest.mark.parametrize("bank", [-1, 0])
+def test_refused_set_global_changes_nothing(M, cube_scene, bank):
+    """A set_global that is refused -- a cube index of 4851, one point more than max_map_points -- leaves the cube map as it was: a
+    slot matched against it gets the factor records it got before.  Cube index 4850 and max_map_points points are accepted."""
+    cs = cube_scene
+    mm = 1 << 15                                          # max_map_points here: the accepted full-size call stays small
+    assert max(len(cs["surf_local"]), len(cs["corner_local"])) <= mm
+    T = _poses(cs, 1)
+    c = _cube_ctx(M, cs, mm, bank)
+    try:
+        for kind, name in ((0, "corner"), (1, "surf")):
+            _set_global(c, bank, kind, cs[name + "_global"], cs[name + "_cube"])
+        c.associate(0, 1, T, 1.0)
+        before = _records(c, 0)
+        bad = cs["surf_cube"].copy()
+        bad[len(bad) // 2] = 4851
+        for kind in (0, 1):
+            with pytest.raises(M.MmlError) as e:
+                _set_global(c, bank, kind, cs["surf_global"], bad, [3, 3, 3])
+            assert e.value.code == M.MML_ERR_INVALID
+            with pytest.raises(M.MmlError) as e:
+                _set_global(c, bank, kind, np.zeros((mm + 1, 3), np.float32), np.zeros(mm + 1, np.int32), [3, 3, 3])
+            assert e.value.code == M.MML_ERR_CAPACITY
+        c.associate(0, 1, T, 1.0)
+        assert _records(c, 0) == before
+        xyz = np.random.default_rng(11).uniform(-20.0, 20.0, (mm, 3)).astype(np.float32)
+        _set_global(c, bank, 1, xyz, np.full(mm, 4850, np.int32))
+        c.associate(0, 1, T, 1.0)
+        assert _records(c, 0) != before                   # the records do depend on the cube map
+        c.synchronize()
     finally:
         c.close()

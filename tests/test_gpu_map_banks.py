@@ -334,3 +334,80 @@ def test_errors_change_nothing(M, scene, cube_scene, maps):
         c.associate(0, n, np.stack(_poses(scene, n)), 25.0)
     finally:
         c.close()
+
+
+WINDOW = 50                  # MML_LOCAL_WINDOW (csrc/mml_internal.h): the ring wraps at the 51st increment
+
+
+def _code(M, call):
+    with pytest.raises(M.MmlError) as e:
+        call()
+    return e.value.code
+
+
+def test_own_map_and_bank_are_the_same_code(M, scene, synth, maps):
+    """The context's own map and bank 0 from the same inputs: equal bytes after set_local, and equal sizes and bytes after every
+    one of WINDOW + 1 increments from the same slot and pose (the ring wraps at the last)."""
+    cm, sm = maps[1][0][:400], maps[1][1][:900]
+    fr = scene["frames"][0]
+    c = M.Context(max_scans=2, max_map_points=MM)
+    try:
+        c.map_banks(1)
+        for kind, xyz in ((0, cm), (1, sm)):
+            c.map_set_local(kind, xyz)
+            c.bank_set_local(0, kind, xyz)
+            own = c.map_local_download(kind)
+            assert len(own) == len(xyz) and own.tobytes() == c.bank_download(0, kind).tobytes()
+        c.features_upload(1, 0, fr["corner"][:300])
+        c.features_upload(1, 1, fr["surf"][:700])
+        for i in range(WINDOW + 1):
+            T = synth.pose_matrix(3 * i + 1)
+            n_own = c.map_increment_local(1, T)
+            nb = c.bank_increment([0], [1], T[None])
+            assert n_own == (int(nb[0][0]), int(nb[1][0])) and min(n_own) > 0, i
+            for kind in (0, 1):
+                own = c.map_local_download(kind)
+                assert len(own) == n_own[kind] and own.tobytes() == c.bank_download(0, kind).tobytes(), (i, kind)
+    finally:
+        c.close()
+
+
+def test_fresh_own_map_is_unset_and_fresh_bank_is_empty(M, scene):
+    """The two defaults: a context's own map refuses until both kinds are set; a bank that was never set is an empty map."""
+    c = M.Context(max_scans=2, max_map_points=MM)
+    try:
+        _load_features(c, scene, 2)
+        T = np.stack(_poses(scene, 2))
+        for own_call in (lambda: c.associate(0, 1, T[:1], 25.0), lambda: c.knn5(0, np.zeros((1, 3))), lambda: c.knn5(1, np.zeros((1, 3))),
+                         lambda: c.map_local_download(0), lambda: c.map_local_download(1)):
+            assert _code(M, own_call) == M.MML_ERR_STATE
+        c.map_banks(1)
+        for kind in (0, 1):
+            assert c.bank_download(0, kind).shape == (0, 3)
+        c.bind_banks(0, [0])
+        c.associate(0, 1, T[:1], 25.0)
+        assert len(c.factors_download(0, 0)[1]) == 0 and len(c.factors_download(0, 1)[1]) == 0
+        assert _code(M, lambda: c.associate(1, 1, T[1:], 25.0)) == M.MML_ERR_STATE      # slot 1 is unbound: the own map is still unset
+        assert _code(M, lambda: c.map_local_download(0)) == M.MML_ERR_STATE
+    finally:
+        c.close()
+
+
+def test_context_with_banks_twice_in_one_process(M, scene, synth):
+    """Create, use and close a context with banks, twice: one increment of the own map and one of bank 0 (the rings' first
+    allocation), a refused call on each, and a clean synchronize."""
+    T = synth.pose_matrix(3)
+    for _ in range(2):
+        c = M.Context(max_scans=2, max_map_points=MM)
+        try:
+            c.map_banks(1)
+            _load_features(c, scene, 2)
+            n_own = c.map_increment_local(0, T)
+            nb = c.bank_increment([0], [0], T[None])
+            assert n_own == (int(nb[0][0]), int(nb[1][0])) and min(n_own) > 0
+            assert _code(M, lambda: c.map_increment_local(2, T)) == M.MML_ERR_INVALID          # slots 0, 1 exist
+            assert _code(M, lambda: c.bank_increment([1], [0], T[None])) == M.MML_ERR_INVALID  # bank 0 exists
+            c.synchronize()
+            assert c.map_local_download(1).tobytes() == c.bank_download(0, 1).tobytes()
+        finally:
+            c.close()
