@@ -928,6 +928,66 @@ typedef struct {
 int mml_estimate(mml_ctx* ctx, int first_slot, int count, const double* exTlb, double* P, double* Q,
                  int max_outer, int inner_iters, mml_estimate_info* info /* count entries or NULL */);
 
+/* ---- localisation in a surfel world map ("The world map", "Surfel maps" above) ----------------------------------------------
+ * mml_world_map_export / _import: a map leaves the device and comes back bit for bit.  Export runs the collect / sort / gather
+ * chain of the downloads with a raw gather: row r is the voxel of row r of the other downloads; ijk = the voxel indices of its
+ * key (i, j, k), sums = the stored float4 (NOT the centroid), counts = the point counts, moments = the stored 12 floats (a surfel
+ * map; must be NULL on a plain one).  ijk, sums and counts all NULL: the sizing call.  MML_ERR_CAPACITY when `capacity` (voxels)
+ * is below the count.  Import inserts n voxels into `map`, one lane per voxel, plain stores; a later mml_world_map_add goes on
+ * from the stored sums.  Checked on the host before any device work, each MML_ERR_INVALID: an index outside [-2^17, 2^17) or the
+ * voxel whose packed key is the free marker (map 1023, all three indices 2^17 - 1), counts[r] < 1, a duplicate row, moments NULL
+ * on a surfel map or non-NULL on a plain one, a NULL array with n > 0, n < 0.  Then, as mml_world_map_add, one lookup launch and
+ * ONE read-back: MML_ERR_STATE if a voxel of the call is present already, MML_ERR_CAPACITY naming the figures if the voxels held
+ * plus n exceed capacity_voxels; either way the table is bit for bit what it was.  The call returns with the rows stored.
+ *
+ * mml_world_map_associate: plane factors for the surf stack (kind 1, as mml_downsample left it) of slot first_slot + i from the
+ * surfels of map map_of_slot[i] (-1: the slot is skipped and left as it is), count slots in ONE launch.  The arithmetic is
+ * csrc/world_map_assoc.h (host and device), per feature f of index s:
+ *   w           the float world point of f at the slot's pose (the function mml_world_map_add uses); f is skipped when a
+ *               coordinate of w is not finite or a voxel index of w leaves [-2^17, 2^17);
+ *   candidates  the voxel (i, j, k) of w (neighbourhood 0) or the 27 voxels (i + di, j + dj, k + dk), di dj dk in {-1, 0, 1},
+ *               that lie in range, each looked up read-only under the slot's map and kept when its count >= min_points; c =
+ *               sum.xyz / (float)count in float; r2 = ((wx-cx)^2 + (wy-cy)^2) + (wz-cz)^2, differences and products in double;
+ *               the smallest r2 wins, ties go to the smaller packed key; no candidate: no factor;
+ *   gates       the winner's surfel record (the function mml_world_map_download_surfels runs) -- planarity < min_planarity: no
+ *               factor, and no second choice; d = (nx*(wx-cx) + ny*(wy-cy)) + nz*(wz-cz) in double; |d| > max_plane_dist: none;
+ *   record      ori = f, omega = (nx, ny, nz) as stored, proj_a = (double)w_a - d * (double)n_a, error = |T f - proj| as
+ *               mml_associate computes a plane factor's, src = s.
+ * The slot is left as mml_associate leaves it: plane records at index s of the slot's list (none: src = -1), NO line factors,
+ * the statistics as mml_associate produces them; mml_linearize*, mml_solve and mml_factors_download work on it unchanged.
+ * Host synchronisations: ONE, the read-back of the slots' stack sizes that the refusal below needs, and one more when stats is
+ * given; with stats NULL the launch itself is only enqueued behind that read-back.  The table is only read.  Refused before anything is written, the message names the slot:
+ * MML_ERR_STATE without a world map, on a plain map, or for a slot that takes part and holds no down-sampled stack;
+ * MML_ERR_INVALID for a slot range outside the context, count outside 1 .. 65535, a map outside [-1, n_maps), min_points < 3,
+ * neighbourhood other than 0 / 1, a non-finite or negative gate, NULL map_of_slot / T_wl / opts.
+ *
+ * mml_world_map_localize: mml_estimate's outer loop and convergence test with mml_world_map_associate in the place of
+ * mml_associate and max_plane_dist_by_outer[min(outer, 2)] in the place of the 25 -> 10 -> 1 schedule (opts->assoc.max_plane_dist
+ * itself is not read); the solve and its options are mml_estimate's.  Every slot of the call must name a map (no -1).  One host
+ * synchronisation per outer iteration, as mml_estimate, and one more at entry (the stack sizes).  The maps are only read. */
+typedef struct {
+    int   neighbourhood;      /* 0: the point's own voxel, 1: the 27 voxels around it (default 1) */
+    int   min_points;         /* a voxel takes part from this count on; >= 3 (default 5) */
+    float min_planarity;      /* gate on the surfel's planarity (default 0.5) */
+    double max_plane_dist;    /* gate on |d|, metres */
+} mml_wm_assoc_opts;
+typedef struct {
+    mml_wm_assoc_opts assoc;
+    double max_plane_dist_by_outer[3];
+    int max_outer, inner_iters;
+} mml_wm_localize_opts;
+void mml_wm_assoc_opts_default(mml_wm_assoc_opts* opts, float leaf);   /* max_plane_dist = leaf */
+void mml_wm_localize_opts_default(mml_wm_localize_opts* opts, float leaf);  /* 2 leaf, leaf, leaf / 2; 5 outer, 10 inner */
+int mml_world_map_export(mml_ctx* ctx, int map, int* ijk /* n x 3 */, float* sums /* n x 4 */, int* counts,
+                         float* moments /* n x 12, NULL on a plain map */, long capacity, long* n_voxels);
+int mml_world_map_import(mml_ctx* ctx, int map, long n, const int* ijk, const float* sums, const int* counts,
+                         const float* moments);
+int mml_world_map_associate(mml_ctx* ctx, int first_slot, int count, const int* map_of_slot /* -1 skips */,
+                            const double* T_wl /* count x 16 */, const mml_wm_assoc_opts* opts,
+                            mml_assoc_stats* stats /* count entries or NULL: nothing is read back behind the launch */);
+int mml_world_map_localize(mml_ctx* ctx, int first_slot, int count, const int* map_of_slot, const double* exTlb,
+                           double* P, double* Q, const mml_wm_localize_opts* opts, mml_estimate_info* info);
+
 /* ---- the benchmarked step ---------------------------------------------------------------------------
  * One pass of the hot path over slots [first, first+count) with inputs already uploaded:
  * extract -> undistort -> downsample -> associate (1 pass, thres_dist) -> `gn_iters` trust-region

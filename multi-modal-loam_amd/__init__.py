@@ -224,6 +224,43 @@ WORLD_MAP_SURFEL_ARGTYPES = {
 }
 
 
+# ... and localisation in a surfel map (include/mmloam_hip.h, "localisation in a surfel world map")
+class WmAssocOpts(C.Structure):
+    """mml_wm_assoc_opts"""
+    _fields_ = [("neighbourhood", C.c_int), ("min_points", C.c_int), ("min_planarity", C.c_float), ("max_plane_dist", C.c_double)]
+
+
+class WmLocalizeOpts(C.Structure):
+    """mml_wm_localize_opts"""
+    _fields_ = [("assoc", WmAssocOpts), ("max_plane_dist_by_outer", C.c_double * 3), ("max_outer", C.c_int), ("inner_iters", C.c_int)]
+
+
+WORLD_MAP_LOCALIZE_ARGTYPES = {
+    "mml_world_map_export": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p],
+    "mml_world_map_import": [C.c_void_p, C.c_int, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mml_world_map_associate": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mml_world_map_localize": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+}
+
+
+def wm_assoc_opts(leaf, **over):
+    """mml_wm_assoc_opts_default(leaf) with fields replaced"""
+    o = WmAssocOpts()
+    lib().mml_wm_assoc_opts_default(C.byref(o), C.c_float(leaf))
+    for k, v in over.items():
+        setattr(o, k, v)
+    return o
+
+
+def wm_localize_opts(leaf, **over):
+    """mml_wm_localize_opts_default(leaf) with fields replaced; max_plane_dist_by_outer: three values; assoc: a WmAssocOpts"""
+    o = WmLocalizeOpts()
+    lib().mml_wm_localize_opts_default(C.byref(o), C.c_float(leaf))
+    for k, v in over.items():
+        setattr(o, k, (C.c_double * 3)(*v) if k == "max_plane_dist_by_outer" else v)
+    return o
+
+
 def build(force=False):
     """Compile csrc/*.hip for gfx950 into libmmloam_hip.so (hipcc cross-compiles without a GPU)."""
     csrc = os.path.join(_HERE, "csrc")
@@ -421,6 +458,13 @@ def lib():
             for name, args in WORLD_MAP_SURFEL_ARGTYPES.items():
                 getattr(L, name).restype = C.c_int
                 getattr(L, name).argtypes = args
+        if hasattr(L, "mml_world_map_localize"):
+            for name, args in WORLD_MAP_LOCALIZE_ARGTYPES.items():
+                getattr(L, name).restype = C.c_int
+                getattr(L, name).argtypes = args
+            for name in ("mml_wm_assoc_opts_default", "mml_wm_localize_opts_default"):
+                getattr(L, name).restype = None
+                getattr(L, name).argtypes = [C.c_void_p, C.c_float]
         _lib = L
     return _lib
 
@@ -1258,6 +1302,7 @@ class Context:
         """n_maps (1 .. 1024) voxel maps of leaf size `leaf` in one table of capacity_voxels voxels; once per context.
         surfels=True: a surfel map (MML_WM_SURFELS), 76 bytes per table position instead of 28; world_map_moments and
         world_map_surfels read it."""
+        self._wm_leaf, self._wm_surfels = float(leaf), bool(surfels)   # (opts=None of world_map_associate / _localize; world_map_export)
         if surfels:
             self._ck(lib().mml_world_map_create_opts(self._h, int(n_maps), float(leaf), int(capacity_voxels), MML_WM_SURFELS))
         else:
@@ -1303,6 +1348,54 @@ class Context:
         (n,) int32 point counts.  The sizing call, then one data call."""
         out, cnt = self._download(lib().mml_world_map_download, (int(map),), [(4, np.float32), (None, np.int32)], count=C.c_long)
         return (out, cnt) if counts else out
+
+    def world_map_export(self, map):
+        """One map as it is stored, in the order of world_map_download: dict(ijk (n, 3) int32 voxel indices, sums (n, 4) float32
+        (the sums, not the centroids), counts (n,) int32, moments (n, 12) float32 or None on a plain map)."""
+        L = lib()
+        n = C.c_long(0)
+        self._ck(L.mml_world_map_export(self._h, int(map), None, None, None, None, 0, C.byref(n)))
+        rows = n.value
+        ijk, sums, counts = np.zeros((rows, 3), np.int32), np.zeros((rows, 4), np.float32), np.zeros(rows, np.int32)
+        mom = np.zeros((rows, 12), np.float32) if getattr(self, "_wm_surfels", False) else None   # (a plain map takes no moments)
+        if rows:
+            self._ck(L.mml_world_map_export(self._h, int(map), _p(ijk), _p(sums), _p(counts), _p(mom), rows, C.byref(n)))
+        return dict(ijk=ijk, sums=sums, counts=counts, moments=mom)
+
+    def world_map_import(self, map, ijk, sums, counts, moments=None):
+        """The inverse of world_map_export (its dict unpacked): n voxels that the map does not hold yet."""
+        ijk = np.ascontiguousarray(ijk, np.int32).reshape(-1, 3)
+        sums = _f32(sums).reshape(-1, 4)
+        counts = np.ascontiguousarray(counts, np.int32).reshape(-1)
+        mom = None if moments is None else _f32(moments).reshape(-1, 12)
+        if len(sums) != len(ijk) or len(counts) != len(ijk) or (mom is not None and len(mom) != len(ijk)):
+            raise ValueError("ijk, sums, counts and moments must have one row per voxel")
+        self._ck(lib().mml_world_map_import(self._h, int(map), len(ijk), _p(ijk), _p(sums), _p(counts), _p(mom)))
+
+    def world_map_associate(self, first, maps, T_wl, opts=None, stats=True):
+        """Plane factors for the surf stacks of slots first + i from the surfels of map maps[i] (-1: skipped): ONE launch.
+        opts: a WmAssocOpts (wm_assoc_opts(leaf, ...); None: the defaults for the map's leaf).  stats=False: no statistics are read
+        back (the poses and map numbers are staged before the call returns)."""
+        m = np.ascontiguousarray(maps, dtype=np.int32).reshape(-1)
+        T = _f64(T_wl).reshape(len(m), 16)
+        st = (AssocStats * len(m))() if stats else None
+        if opts is None:
+            opts = wm_assoc_opts(getattr(self, "_wm_leaf", 1.0))
+        self._ck(lib().mml_world_map_associate(self._h, int(first), len(m), _p(m), _p(T), C.byref(opts), st))
+        return list(st) if stats else None
+
+    def world_map_localize(self, first, maps, exTlb, P, Q, opts=None):
+        """mml_world_map_localize: Context.estimate's loop against the surfel map.  opts: a WmLocalizeOpts
+        (wm_localize_opts(leaf, ...)).  Returns P, Q, [EstimateInfo]."""
+        m = np.ascontiguousarray(maps, dtype=np.int32).reshape(-1)
+        P = _f64(P).reshape(len(m), 3).copy()
+        Q = _f64(Q).reshape(len(m), 4).copy()
+        info = (EstimateInfo * len(m))()
+        if opts is None:
+            opts = wm_localize_opts(getattr(self, "_wm_leaf", 1.0))
+        self._ck(lib().mml_world_map_localize(self._h, int(first), len(m), _p(m), _p(_f64(exTlb).reshape(16)), _p(P), _p(Q),
+                                              C.byref(opts), info))
+        return P, Q, list(info)
 
     # ---- map banks: further local maps, every slot matched against its own (include/mmloam_hip.h, "map banks") ----
     def map_banks(self, n):

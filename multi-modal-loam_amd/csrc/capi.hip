@@ -1569,14 +1569,11 @@ static void pose_back_finish(const PoseBack& b, double* x, int* ftn, mml_assoc_s
     }
 }
 
-int mml_estimate(mml_ctx* ctx, int first_slot, int count, const double* exTlb, double* P, double* Q, int max_outer,
-                 int inner_iters, mml_estimate_info* info) {
-    CHECK_SLOTS(first_slot, count);
-    MML_REQUIRE(exTlb && P && Q && max_outer >= 1 && inner_iters >= 0, MML_ERR_INVALID, "bad arguments");
-    {
-        const int ready = mml_assoc_ready(ctx, first_slot, count, "mml_estimate");
-        if (ready != MML_OK) return ready;
-    }
+// Estimator::Estimate's outer loop and convergence test for `count` slots (mml_estimate, mml_world_map_localize): the start poses
+// down, the association of outer iteration `it` -- against the local maps with the 25 -> 10 -> 1 schedule, or, wm != NULL, against
+// the surfel world map with wm[min(it, 2)] --, the solve behind it, ONE read-back and host synchronisation per outer iteration.
+static int estimate_loop(mml_ctx* ctx, int first_slot, int count, const double* exTlb, double* P, double* Q, int max_outer, int inner_iters,
+                         mml_estimate_info* info, const mml_wm_assoc_opts* wm) {
     double T_bl[16];
     invert_extrinsic(exTlb, T_bl);
     std::vector<int> done(count, 0), outer(count, 0), degen(count, 0);
@@ -1585,7 +1582,6 @@ int mml_estimate(mml_ctx* ctx, int first_slot, int count, const double* exTlb, d
     std::vector<int> fn(2 * (size_t)count, 0);  // the slots' stack sizes as the last read-back reported them
     const bool packed = mml_pose_packed(count, ctx->cus);
     const PoseBlock dev = PoseBlock::of(ctx->d_pose_in, first_slot, count);
-    double thres = 25.0;  // Estimator.cpp:1207
     mml_solve_opts so;
     so.max_num_iterations = inner_iters;
     so.fixed_iterations = 0;
@@ -1607,9 +1603,14 @@ int mml_estimate(mml_ctx* ctx, int first_slot, int count, const double* exTlb, d
         PoseBlock host;
         int rc = pose_upload(ctx, dev, nullptr, nullptr, x.data(), Q, T_bl, &host);
         if (rc != MML_OK) return rc;
-        rc = mml_launch_associate(ctx, first_slot, count, dev.T_wl(), thres, true);
+        if (wm) {
+            rc = mml_launch_wm_associate(ctx, first_slot, count, dev.T_wl(), wm[it < 2 ? it : 2]);
+            if (rc == MML_OK) rc = mml_ensure_assoc_stats(ctx, first_slot, count);
+        } else {
+            const double thres = it == 0 ? 25.0 : (it == 1 ? 10.0 : 1.0);  // Estimator.cpp:1207, :1377-1381
+            rc = mml_launch_associate(ctx, first_slot, count, dev.T_wl(), thres, true);
+        }
         if (rc != MML_OK) return rc;
-        thres = (it == 0) ? 10.0 : 1.0;  // :1377-1381
         const PoseBack back{packed, true, first_slot, count, stage_alloc(ctx, MML_SOLVE_RESULT * (size_t)count)};
         rc = pose_solve_enqueue(ctx, dev, host, so, back);
         if (rc != MML_OK) return rc;
@@ -1644,6 +1645,60 @@ int mml_estimate(mml_ctx* ctx, int first_slot, int count, const double* exTlb, d
             info[i].n_surf_feat = fn[count + i];
         }
     return MML_OK;
+}
+
+int mml_estimate(mml_ctx* ctx, int first_slot, int count, const double* exTlb, double* P, double* Q, int max_outer,
+                 int inner_iters, mml_estimate_info* info) {
+    CHECK_SLOTS(first_slot, count);
+    MML_REQUIRE(exTlb && P && Q && max_outer >= 1 && inner_iters >= 0, MML_ERR_INVALID, "bad arguments");
+    {
+        const int ready = mml_assoc_ready(ctx, first_slot, count, "mml_estimate");
+        if (ready != MML_OK) return ready;
+    }
+    return estimate_loop(ctx, first_slot, count, exTlb, P, Q, max_outer, inner_iters, info, nullptr);
+}
+
+// ---- localisation in a surfel world map (world_map_assoc.hip): the entry points beside the calls they mirror ----
+int mml_world_map_associate(mml_ctx* ctx, int first_slot, int count, const int* map_of_slot, const double* T_wl,
+                            const mml_wm_assoc_opts* opts, mml_assoc_stats* stats) {
+    CHECK_SLOTS(first_slot, count);
+    MML_REQUIRE(T_wl != nullptr, MML_ERR_INVALID, "mml_world_map_associate: null T_wl");
+    int rc = mml_wm_assoc_ready(ctx, "mml_world_map_associate", first_slot, count, map_of_slot, opts, false);
+    if (rc != MML_OK) return rc;
+    double* d_T = ctx->d_pose_in + kPoseSlotDoubles * (size_t)first_slot;
+    rc = upload_doubles(ctx, d_T, T_wl, 16 * (size_t)count);
+    if (rc != MML_OK) return rc;
+    rc = mml_launch_wm_associate(ctx, first_slot, count, d_T, *opts);
+    if (rc != MML_OK || !stats) return rc;
+    rc = mml_ensure_assoc_stats(ctx, first_slot, count);
+    if (rc != MML_OK) return rc;
+    double* h = stage_alloc(ctx, 16 * (size_t)count);  // pinned
+    MML_HIP(hipMemcpyAsync(h, ctx->assoc_stats + 16 * (size_t)first_slot, sizeof(double) * 16 * (size_t)count, hipMemcpyDeviceToHost, MML_STREAM(ctx)));
+    MML_HIP(hipStreamSynchronize(MML_STREAM(ctx)));
+    for (int i = 0; i < count; ++i) {  // (a slot that was skipped: zeros)
+        if (map_of_slot[i] < 0)
+            memset(&stats[i], 0, sizeof(stats[i]));
+        else
+            finish_stats(h + 16 * i, &stats[i]);
+    }
+    return MML_OK;
+}
+
+int mml_world_map_localize(mml_ctx* ctx, int first_slot, int count, const int* map_of_slot, const double* exTlb, double* P, double* Q,
+                           const mml_wm_localize_opts* opts, mml_estimate_info* info) {
+    CHECK_SLOTS(first_slot, count);
+    MML_REQUIRE(exTlb && P && Q && opts, MML_ERR_INVALID, "mml_world_map_localize: null exTlb / P / Q / opts");
+    MML_REQUIRE(opts->max_outer >= 1 && opts->inner_iters >= 0, MML_ERR_INVALID, "mml_world_map_localize: max_outer < 1 or inner_iters < 0");
+    mml_wm_assoc_opts ao[3];
+    for (int k = 0; k < 3; ++k) {
+        ao[k] = opts->assoc;
+        ao[k].max_plane_dist = opts->max_plane_dist_by_outer[k];
+        if (!isfinite(ao[k].max_plane_dist) || ao[k].max_plane_dist < 0.0)
+            return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_localize: max_plane_dist_by_outer[%d] must be finite and >= 0", k);
+    }
+    const int rc = mml_wm_assoc_ready(ctx, "mml_world_map_localize", first_slot, count, map_of_slot, &ao[0], true);
+    if (rc != MML_OK) return rc;
+    return estimate_loop(ctx, first_slot, count, exTlb, P, Q, opts->max_outer, opts->inner_iters, info, ao);
 }
 
 int mml_step(mml_ctx* ctx, int first_slot, int count, const double* dR, const double* dt, const double* exTlb,

@@ -392,11 +392,13 @@ struct mml_ctx {
         MmlStaging<char, false> scratch;     // the calls' scratch (one call at a time)
         MmlStaging<char, false> tmp;         // rocPRIM temporary storage
         MmlStaging<char> tab;                // a call's slot rows and counters: device block and pinned twin
+        MmlStaging<int, false> assoc_maps;   // B: the map of every slot of the last association against the map (world_map_assoc.hip)
         void release() {
             mem.release();
             scratch.release();
             tmp.release();
             tab.release();
+            assoc_maps.release();
             keys = nullptr;
             sum = nullptr;
             count = nullptr;
@@ -613,6 +615,11 @@ int mml_launch_knn5(mml_ctx* ctx, int kind, const float* d_q, int nq, float max_
 // computed by mml_ensure_assoc_stats when a consumer asks (mml_linearize*, the next mml_associate with statistics)
 int mml_launch_associate(mml_ctx* ctx, int first, int count, const double* d_Twl, double thres_dist, bool with_stats = true);
 int mml_ensure_assoc_stats(mml_ctx* ctx, int first, int count);
+// world_map_assoc.hip: association against a surfel world map.  mml_wm_assoc_ready: the refusals of a call over slots
+// [first, first + count) -- before any device work but ONE read-back of the stack sizes -- and the call's map numbers sent down;
+// mml_launch_wm_associate: k_wm_associate for those slots at the poses d_Twl (16 doubles per slot, on the device), enqueue only.
+int mml_wm_assoc_ready(mml_ctx* ctx, const char* who, int first, int count, const int* map_of_slot, const mml_wm_assoc_opts* o, bool need_all);
+int mml_launch_wm_associate(mml_ctx* ctx, int first, int count, const double* d_Twl, const mml_wm_assoc_opts& o);
 #define MML_SOLVE_RESULT 24  // doubles per problem of k_solve's result record: x (6), stack sizes (2), association statistics (16)
 // d_x_in / d_result (a PoseBlock's start poses, the result records): packed pose calls only, mml_pose_packed(count, ctx->cus)
 int mml_launch_solve(mml_ctx* ctx, int first, int count, int window, const double* d_Tbl, mml_solve_opts opts,

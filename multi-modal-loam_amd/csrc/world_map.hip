@@ -31,10 +31,16 @@
 // only after its key is claimed and its accumulators are stored, so neither reset(-1) nor create clears them.
 // mml_world_map_download, _download_moments and _download_surfels share one collect, sort and gather chain (wm_download); the
 // surfel gather is one lane per voxel: the covariance in double (mml_wm_covariance), eig3_sym register-only, the normal turned
-// towards the view sum.
+// towards the view sum (wm_surfel, world_map_dev.h: the association against the map, world_map_assoc.hip, runs it too).
+// mml_world_map_export is a fourth gather of that chain (the stored sums, counts, moments and the sorted keys as voxel indices);
+// mml_world_map_import checks its rows on the host, looks all of them up in one launch (k_wm_import_find), refuses at the add's
+// refusal point -- one read-back, only scratch written -- and then claims and stores them, one lane per voxel (k_wm_import_put).
 #include <limits.h>
 #include <math.h>
 #include <string.h>
+
+#include <algorithm>
+#include <vector>
 
 #include "mml_internal.h"
 #include "fused_view_dev.h"
@@ -43,6 +49,7 @@
 
 namespace {
 #include "eig3_dev.h"
+#include "world_map_dev.h"
 
 // one slot of the call, read through scalar loads (blockIdx.y)
 struct WmRow {
@@ -52,12 +59,6 @@ struct WmRow {
     int pad[2];
 };
 enum { WM_POINTS, WM_KEPT, WM_NONFINITE, WM_RANGE, WM_MASKED, WM_DISTINCT, WM_MISSES, WM_COUNTERS };
-
-// one add per wave of the lanes for which `pred` holds
-__device__ __forceinline__ void wm_count(int* counter, bool pred) {
-    const unsigned long long b = __ballot(pred);
-    if (b && (threadIdx.x & 63) == 0) atomicAdd(counter, __popcll(b));
-}
 
 __global__ __launch_bounds__(256) void k_wm_keys(SlotArrays A, const WmRow* __restrict__ rows, float inv, unsigned label_mask,
                                                  float4* __restrict__ pts, unsigned long long* __restrict__ keys,
@@ -96,18 +97,6 @@ __global__ __launch_bounds__(256) void k_wm_keys(SlotArrays A, const WmRow* __re
     }
 }
 
-// where `key` sits in the table, or -1: the probe ends at the key or at the first free position (there always is one: the table
-// holds at most half as many voxels as it has positions)
-__device__ __forceinline__ long long wm_find(const unsigned long long* __restrict__ tab, unsigned long long slots, unsigned long long key) {
-    unsigned long long h = mml_wm_hash(key, slots);
-    for (unsigned long long step = 0; step < slots; ++step) {
-        const unsigned long long k = tab[h];
-        if (k == key) return (long long)h;
-        if (k == MML_WM_EMPTY) return -1;
-        h = (h + 1) & (slots - 1);
-    }
-    return -1;
-}
 // claims a free position for `key` (which is not in the table, and which no other lane inserts); -1 only from a full table
 __device__ __forceinline__ long long wm_claim(unsigned long long* __restrict__ tab, unsigned long long slots, unsigned long long key) {
     unsigned long long h = mml_wm_hash(key, slots);
@@ -142,9 +131,6 @@ struct WmMomentArgs<true> {
     float leaf;
     int nt;                 // ordinals per slot that takes part (the context's NT)
 };
-__device__ __forceinline__ MmlWmMoments wm_moments(const float4& a, const float4& b, const float4& c) {
-    return MmlWmMoments{a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w};
-}
 
 template <bool Surfels>
 __global__ __launch_bounds__(256) void k_wm_insert(const unsigned long long* __restrict__ keys, const unsigned* __restrict__ vals,
@@ -228,10 +214,6 @@ __global__ __launch_bounds__(256) void k_wm_centroids(const unsigned* __restrict
     out[i] = make_float4(c[0], c[1], c[2], c[3]);
     out_n[i] = a.n;
 }
-// the three moment arrays of a surfel map (or of a reset's scratch copy); null in a plain map
-struct WmMom {
-    float4 *m0, *m1, *m2;
-};
 // download_moments: the raw accumulators of the sorted positions, 12 floats each
 __global__ __launch_bounds__(256) void k_wm_moments(const unsigned* __restrict__ vals, int n, WmMom M, float4* __restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -241,8 +223,7 @@ __global__ __launch_bounds__(256) void k_wm_moments(const unsigned* __restrict__
     out[3 * (size_t)i + 1] = M.m1[at];
     out[3 * (size_t)i + 2] = M.m2[at];
 }
-// download_surfels: one lane per sorted position.  8 floats: the normal (the eigenvector of the smallest eigenvalue, turned
-// towards the view sum), the eigenvalues ascending, planarity and linearity; eight zeros for a voxel of fewer than 3 points.
+// download_surfels: one lane per sorted position, 8 floats (wm_surfel, world_map_dev.h)
 __global__ __launch_bounds__(256) void k_wm_surfels(const unsigned* __restrict__ vals, int n, WmMom M, const int* __restrict__ count,
                                                     float4* __restrict__ out) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -252,22 +233,7 @@ __global__ __launch_bounds__(256) void k_wm_surfels(const unsigned* __restrict__
     float4 o0 = make_float4(0.f, 0.f, 0.f, 0.f), o1 = o0;
     if (np >= 3) {
         const MmlWmMoments m = wm_moments(M.m0[at], M.m1[at], M.m2[at]);
-        double c[6], ev[3], v2[3], v0[3];
-        mml_wm_covariance(m, np, c);
-        eig3_sym(c[0], c[1], c[2], c[3], c[4], c[5], ev, v2, v0);
-        const double dot = (v0[0] * (double)m.vx + v0[1] * (double)m.vy) + v0[2] * (double)m.vz;
-        if (dot < 0.0) {
-            v0[0] = -v0[0];
-            v0[1] = -v0[1];
-            v0[2] = -v0[2];
-        }
-        double planarity = 0.0, linearity = 0.0;
-        if (!(ev[2] <= 0.0)) {
-            planarity = (ev[1] - ev[0]) / ev[2];
-            linearity = (ev[2] - ev[1]) / ev[2];
-        }
-        o0 = make_float4((float)v0[0], (float)v0[1], (float)v0[2], (float)ev[0]);
-        o1 = make_float4((float)ev[1], (float)ev[2], (float)planarity, (float)linearity);
+        wm_surfel(m, np, o0, o1);
     }
     out[2 * (size_t)i] = o0;
     out[2 * (size_t)i + 1] = o1;
@@ -306,6 +272,44 @@ __global__ __launch_bounds__(256) void k_wm_reinsert(const unsigned long long* _
         M.m1[at] = S.m1[i];
         M.m2[at] = S.m2[i];
     }
+}
+
+// export: the stored sums and counts of the sorted positions, as they are (the moments go through k_wm_moments)
+__global__ __launch_bounds__(256) void k_wm_raw(const unsigned* __restrict__ vals, int n, const float4* __restrict__ sum,
+                                                const int* __restrict__ count, float4* __restrict__ out, int* __restrict__ out_n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = sum[vals[i]];
+    out_n[i] = count[vals[i]];
+}
+// import: which of the call's n distinct keys the table holds already -- counted, nothing is written to the table
+__global__ __launch_bounds__(256) void k_wm_import_find(const unsigned long long* __restrict__ keys, int n, const unsigned long long* __restrict__ tab,
+                                                        unsigned long long slots, int* __restrict__ hits) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool held = false;
+    if (i < n) held = wm_find(tab, slots, keys[i]) >= 0;
+    wm_count(hits, held);
+}
+// ... and, none of them held: k_wm_insert's claim path with the accumulators as given -- one lane per voxel, the keys distinct,
+// plain stores behind the claim; the map's count and the total by one add per wave
+__global__ __launch_bounds__(256) void k_wm_import_put(const unsigned long long* __restrict__ keys, int n, const float4* __restrict__ s_sum,
+                                                       const int* __restrict__ s_n, const float4* __restrict__ s_mom, unsigned long long* __restrict__ tab,
+                                                       unsigned long long slots, float4* __restrict__ sum, int* __restrict__ count,
+                                                       int* __restrict__ map_n, int n_maps, int map, WmMom M) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    long long at = -1;
+    if (i < n) at = wm_claim(tab, slots, keys[i]);
+    if (at >= 0) {  // (always for i < n: the host refused the call that would have filled the table)
+        sum[at] = s_sum[i];
+        count[at] = s_n[i];
+        if (M.m0) {  // (a surfel map: the whole launch)
+            M.m0[at] = s_mom[3 * (size_t)i];
+            M.m1[at] = s_mom[3 * (size_t)i + 1];
+            M.m2[at] = s_mom[3 * (size_t)i + 2];
+        }
+    }
+    wm_count(map_n + map, at >= 0);
+    wm_count(map_n + n_maps, at >= 0);
 }
 
 int wm_enter(mml_ctx* ctx, const char* who) {
@@ -533,17 +537,24 @@ int mml_world_map_add(mml_ctx* ctx, int first_slot, int count, const int* map_of
 }
 
 namespace {
-// The three downloads: the occupied positions of the map collected, sorted by key and gathered -- the chain is this function's
-// and nobody else's; `what` chooses the gather kernel and the floats per voxel.
-enum WmWhat { WM_CENTROIDS = 4, WM_MOMENTS = 12, WM_SURFELS = 8 };  // (the value: floats per voxel)
-int wm_download(mml_ctx* ctx, const char* who, WmWhat what, int map, float* out, int* out_count, long capacity, long* n_voxels) {
+// The three downloads and the export: the occupied positions of the map collected, sorted by key and gathered -- the chain is this
+// function's and nobody else's; `what` chooses the gather kernel and the floats per voxel.  The export (WM_RAW) gathers the stored
+// sums into `out`, the counts, the sorted keys as voxel indices into `ijk` and, on a surfel map, the moments into `moments`.
+enum WmWhat { WM_CENTROIDS = 4, WM_MOMENTS = 12, WM_SURFELS = 8, WM_RAW = 16 };  // (the value: floats per voxel; WM_RAW: 4, or 16 with moments)
+int wm_download(mml_ctx* ctx, const char* who, WmWhat what, int map, float* out, int* out_count, long capacity, long* n_voxels,
+                int* ijk = nullptr, float* moments = nullptr) {
     int rc = wm_enter(ctx, who);
     if (rc != MML_OK) return rc;
     mml_ctx::WorldMap& W = ctx->world;
-    if (what != WM_CENTROIDS && !W.surfels)
+    if (what != WM_CENTROIDS && what != WM_RAW && !W.surfels)
         return mml_refuse(ctx, MML_ERR_STATE, "%s: the world map was created without MML_WM_SURFELS (mml_world_map_create_opts)", who);
     if (!n_voxels) return mml_refuse(ctx, MML_ERR_INVALID, "%s: null n_voxels", who);
     if (map < 0 || map >= W.n_maps) return mml_refuse(ctx, MML_ERR_INVALID, "%s: map %d outside [0, %d)", who, map, W.n_maps);
+    if (what == WM_RAW && (out || out_count || ijk || moments)) {  // (all NULL: the sizing call)
+        if (!out || !out_count || !ijk) return mml_refuse(ctx, MML_ERR_INVALID, "%s: ijk, sums and counts are given together or not at all", who);
+        if ((moments != nullptr) != W.surfels)
+            return mml_refuse(ctx, MML_ERR_INVALID, "%s: moments must be %s", who, W.surfels ? "given: the map holds surfels" : "NULL: the map is a plain one");
+    }
     rc = mml_world_map_size(ctx, map, n_voxels);
     if (rc != MML_OK || !out || *n_voxels == 0) return rc;
     if (capacity < *n_voxels) return mml_refuse(ctx, MML_ERR_CAPACITY, "%s: map %d holds %ld voxels, capacity is %ld", who, map, *n_voxels, capacity);
@@ -552,7 +563,7 @@ int wm_download(mml_ctx* ctx, const char* who, WmWhat what, int map, float* out,
     MmlCarve<16> c;
     const MmlField<unsigned long long> f_keys = c.take<unsigned long long>(2 * n);
     const MmlField<unsigned> f_vals = c.take<unsigned>(2 * n);
-    const MmlField<float4> f_out = c.take<float4>((size_t)what / 4 * n);
+    const MmlField<float4> f_out = c.take<float4>((what == WM_RAW ? (W.surfels ? 4 : 1) : (size_t)what / 4) * n);
     const MmlField<int> f_n = c.take<int>(n);
     const MmlField<int> f_cur = c.take<int>(1);
     rc = W.scratch.reserve(ctx, c.bytes(), s);
@@ -572,9 +583,25 @@ int wm_download(mml_ctx* ctx, const char* who, WmWhat what, int map, float* out,
         hipLaunchKernelGGL(k_wm_centroids, dim3(wm_blocks(n)), dim3(256), 0, s, vals + n, (int)n, W.sum, W.count, f_out.in(d), f_n.in(d));
     else if (what == WM_MOMENTS)
         hipLaunchKernelGGL(k_wm_moments, dim3(wm_blocks(n)), dim3(256), 0, s, vals + n, (int)n, wm_mom(W), f_out.in(d));
-    else
+    else if (what == WM_RAW) {
+        hipLaunchKernelGGL(k_wm_raw, dim3(wm_blocks(n)), dim3(256), 0, s, vals + n, (int)n, W.sum, W.count, f_out.in(d), f_n.in(d));
+        if (W.surfels) hipLaunchKernelGGL(k_wm_moments, dim3(wm_blocks(n)), dim3(256), 0, s, vals + n, (int)n, wm_mom(W), f_out.in(d) + n);
+    } else
         hipLaunchKernelGGL(k_wm_surfels, dim3(wm_blocks(n)), dim3(256), 0, s, vals + n, (int)n, wm_mom(W), W.count, f_out.in(d));
     MML_HIP(hipGetLastError());
+    if (what == WM_RAW) {
+        std::vector<unsigned long long> h_keys(n);
+        MML_HIP(hipMemcpyAsync(out, f_out.in(d), sizeof(float4) * n, hipMemcpyDeviceToHost, s));
+        if (W.surfels) MML_HIP(hipMemcpyAsync(moments, f_out.in(d) + n, sizeof(float4) * 3 * n, hipMemcpyDeviceToHost, s));
+        MML_HIP(hipMemcpyAsync(out_count, f_n.in(d), sizeof(int) * n, hipMemcpyDeviceToHost, s));
+        MML_HIP(hipMemcpyAsync(h_keys.data(), keys + n, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, s));
+        MML_HIP(hipStreamSynchronize(s));
+        for (size_t r = 0; r < n; ++r) {
+            int m;
+            mml_wm_unkey(h_keys[r], m, ijk[3 * r], ijk[3 * r + 1], ijk[3 * r + 2]);
+        }
+        return MML_OK;
+    }
     MML_HIP(hipMemcpyAsync(out, f_out.in(d), f_out.bytes(), hipMemcpyDeviceToHost, s));
     if (out_count) MML_HIP(hipMemcpyAsync(out_count, f_n.in(d), sizeof(int) * n, hipMemcpyDeviceToHost, s));
     MML_HIP(hipStreamSynchronize(s));
@@ -590,4 +617,73 @@ int mml_world_map_download_moments(mml_ctx* ctx, int map, float* out, long capac
 }
 int mml_world_map_download_surfels(mml_ctx* ctx, int map, float* out, long capacity, long* n_voxels) {
     return wm_download(ctx, "mml_world_map_download_surfels", WM_SURFELS, map, out, nullptr, capacity, n_voxels);
+}
+int mml_world_map_export(mml_ctx* ctx, int map, int* ijk, float* sums, int* counts, float* moments, long capacity, long* n_voxels) {
+    return wm_download(ctx, "mml_world_map_export", WM_RAW, map, sums, counts, capacity, n_voxels, ijk, moments);
+}
+
+int mml_world_map_import(mml_ctx* ctx, int map, long n, const int* ijk, const float* sums, const int* counts, const float* moments) {
+    int rc = wm_enter(ctx, "mml_world_map_import");
+    if (rc != MML_OK) return rc;
+    mml_ctx::WorldMap& W = ctx->world;
+    // the arguments, on the host, before any device work
+    if (map < 0 || map >= W.n_maps) return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_import: map %d outside [0, %d)", map, W.n_maps);
+    MML_REQUIRE(n >= 0 && n <= (1L << 29), MML_ERR_INVALID, "mml_world_map_import: n outside 0..2^29");
+    MML_REQUIRE(n == 0 || (ijk && sums && counts), MML_ERR_INVALID, "mml_world_map_import: null ijk / sums / counts");
+    if (n > 0 && (moments != nullptr) != W.surfels)
+        return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_import: moments must be %s", W.surfels ? "given: the map holds surfels" : "NULL: the map is a plain one");
+    if (n == 0) return MML_OK;
+    std::vector<unsigned long long> h_keys((size_t)n);
+    for (long r = 0; r < n; ++r) {
+        const int i = ijk[3 * r], j = ijk[3 * r + 1], k = ijk[3 * r + 2];
+        const bool in = i >= -MML_WM_HALF && i < MML_WM_HALF && j >= -MML_WM_HALF && j < MML_WM_HALF && k >= -MML_WM_HALF && k < MML_WM_HALF;
+        if (!in || mml_wm_key(map, i, j, k) == MML_WM_EMPTY)
+            return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_import: row %ld: voxel (%d, %d, %d) %s", r, i, j, k,
+                              in ? "of this map packs to the free marker" : "outside [-2^17, 2^17)");
+        if (counts[r] < 1) return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_import: row %ld: count %d < 1", r, counts[r]);
+        h_keys[(size_t)r] = mml_wm_key(map, i, j, k);
+    }
+    {
+        std::vector<unsigned long long> sorted(h_keys);
+        std::sort(sorted.begin(), sorted.end());
+        const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
+        if (dup != sorted.end()) {
+            int m, i, j, k;
+            mml_wm_unkey(*dup, m, i, j, k);
+            return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_import: voxel (%d, %d, %d) is given twice", i, j, k);
+        }
+    }
+    hipStream_t s = MML_STREAM(ctx);
+    const size_t m = (size_t)n;
+    MmlCarve<16> c;
+    const MmlField<unsigned long long> f_keys = c.take<unsigned long long>(m);
+    const MmlField<float4> f_sum = c.take<float4>(m);
+    const MmlField<int> f_n = c.take<int>(m);
+    const MmlField<float4> f_mom = c.take<float4>(W.surfels ? 3 * m : 0);
+    const MmlField<int> f_cnt = c.take<int>(2);  // the hits, and behind them (read-back only) the table's total
+    rc = W.scratch.reserve(ctx, c.bytes(), s);
+    if (rc != MML_OK) return rc;
+    char* d = W.scratch.d;
+    MML_HIP(hipMemsetAsync(f_cnt.in(d), 0, sizeof(int) * 2, s));
+    MML_HIP(hipMemcpyAsync(f_keys.in(d), h_keys.data(), f_keys.bytes(), hipMemcpyHostToDevice, s));
+    MML_HIP(hipMemcpyAsync(f_sum.in(d), sums, f_sum.bytes(), hipMemcpyHostToDevice, s));
+    MML_HIP(hipMemcpyAsync(f_n.in(d), counts, f_n.bytes(), hipMemcpyHostToDevice, s));
+    if (W.surfels) MML_HIP(hipMemcpyAsync(f_mom.in(d), moments, f_mom.bytes(), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_wm_import_find, dim3(wm_blocks(m)), dim3(256), 0, s, f_keys.in(d), (int)m, W.keys, W.slots, f_cnt.in(d));
+    MML_HIP(hipGetLastError());
+    // the read-back: the refusal point of mml_world_map_add -- only scratch has been written up to here
+    int h_cnt[2] = {0, 0};
+    MML_HIP(hipMemcpyAsync(h_cnt, f_cnt.in(d), sizeof(int), hipMemcpyDeviceToHost, s));
+    MML_HIP(hipMemcpyAsync(h_cnt + 1, W.map_n + W.n_maps, sizeof(int), hipMemcpyDeviceToHost, s));
+    MML_HIP(hipStreamSynchronize(s));
+    if (h_cnt[0] > 0)
+        return mml_refuse(ctx, MML_ERR_STATE, "mml_world_map_import: %d of the %ld voxels are present in map %d already; nothing was imported", h_cnt[0], n, map);
+    if ((long)h_cnt[1] + n > W.capacity)
+        return mml_refuse(ctx, MML_ERR_CAPACITY, "mml_world_map_import: %d voxels held + %ld imported exceed capacity_voxels %ld; nothing was imported",
+                          h_cnt[1], n, W.capacity);
+    hipLaunchKernelGGL(k_wm_import_put, dim3(wm_blocks(m)), dim3(256), 0, s, f_keys.in(d), (int)m, f_sum.in(d), f_n.in(d), f_mom.in(d), W.keys, W.slots, W.sum,
+                       W.count, W.map_n, W.n_maps, map, wm_mom(W));
+    MML_HIP(hipGetLastError());
+    MML_HIP(hipStreamSynchronize(s));  // (the caller's arrays and the key vector were the copies' sources)
+    return MML_OK;
 }

@@ -165,6 +165,44 @@ class WorldMap {
     // ... and 8 floats each: nx ny nz | l0 l1 l2 | planarity linearity (eight zeros for a voxel of fewer than 3 points)
     std::vector<float> surfels(int map) { return rows(map, 8, mml_world_map_download_surfels, "mml_world_map_download_surfels"); }
 
+    // One map as it is stored, in the order of download(): what import_voxels takes back bit for bit (into a map that does not hold
+    // the voxels yet).  moments stays empty on a plain map.
+    struct Voxels {
+        std::vector<int> ijk;        // n x 3 voxel indices
+        std::vector<float> sums;     // n x 4: the sums x, y, z, intensity (not the centroids)
+        std::vector<int> counts;     // n
+        std::vector<float> moments;  // n x 12 on a surfel map
+    };
+    Voxels export_voxels(int map, bool surfels) {
+        long n = 0;
+        check(ctx_.get(), mml_world_map_export(ctx_.get(), map, nullptr, nullptr, nullptr, nullptr, 0, &n), "mml_world_map_export");
+        Voxels v;
+        v.ijk.resize(3 * (size_t)n);
+        v.sums.resize(4 * (size_t)n);
+        v.counts.resize((size_t)n);
+        if (surfels) v.moments.resize(12 * (size_t)n);
+        if (n)
+            check(ctx_.get(), mml_world_map_export(ctx_.get(), map, v.ijk.data(), v.sums.data(), v.counts.data(), surfels ? v.moments.data() : nullptr, n, &n),
+                  "mml_world_map_export");
+        return v;
+    }
+    void import_voxels(int map, const Voxels& v) {
+        check(ctx_.get(), mml_world_map_import(ctx_.get(), map, (long)v.counts.size(), v.ijk.data(), v.sums.data(), v.counts.data(),
+                                               v.moments.empty() ? nullptr : v.moments.data()),
+              "mml_world_map_import");
+    }
+    // Plane factors for the surf stacks of slots first_slot + i from the surfels of map map_of_slot[i] (-1: skipped), one launch;
+    // stats: count entries, or nullptr to enqueue only.  The slots are then ready for mml_solve / mml_linearize.
+    void associate(int first_slot, int count, const int* map_of_slot, const double* T_wl, const mml_wm_assoc_opts& opts,
+                   mml_assoc_stats* stats = nullptr) {
+        check(ctx_.get(), mml_world_map_associate(ctx_.get(), first_slot, count, map_of_slot, T_wl, &opts, stats), "mml_world_map_associate");
+    }
+    // Estimator::Estimate's loop against the map: P (count x 3), Q (count x 4) in and out; the map is only read
+    void localize(int first_slot, int count, const int* map_of_slot, const double* exTlb, double* P, double* Q, const mml_wm_localize_opts& opts,
+                  mml_estimate_info* info = nullptr) {
+        check(ctx_.get(), mml_world_map_localize(ctx_.get(), first_slot, count, map_of_slot, exTlb, P, Q, &opts, info), "mml_world_map_localize");
+    }
+
    private:
     std::vector<float> rows(int map, int width, int (*call)(mml_ctx*, int, float*, long, long*), const char* who) {
         long n = 0;

@@ -395,6 +395,25 @@ def _new_solver(M, W, inner_iters, w_tan, preints, gravity, prior):
     return fw
 
 
+class MapLocalizer:
+    """Scans registered against a finished surfel world map of the context (Context.world_map_create(..., surfels=True), filled
+    by world_map_add or world_map_import): localize(slots, P, Q) runs ONE mml_world_map_localize for a run of consecutive slots
+    whose surf stacks are down-sampled.  maps: the map of every slot of the context, or one map for all.  The maps are only
+    read; a localised scan enters its map when the caller calls ctx.world_map_add."""
+
+    def __init__(self, ctx, maps, exTlb=None, opts=None):
+        self.ctx, self.maps, self.opts = ctx, maps, opts
+        self.exTlb = np.eye(4) if exTlb is None else np.asarray(exTlb, np.float64).reshape(4, 4)
+
+    def localize(self, slots, P, Q):
+        """slots: consecutive slot numbers; P (n, 3), Q (n, 4): the start poses.  Returns P, Q, [EstimateInfo]."""
+        slots = [int(s) for s in slots]
+        if not slots or slots != list(range(slots[0], slots[0] + len(slots))):
+            raise ValueError("localize takes a run of consecutive slots")
+        maps = [self.maps] * len(slots) if np.isscalar(self.maps) else [self.maps[s] for s in slots]
+        return self.ctx.world_map_localize(slots[0], maps, self.exTlb, P, Q, self.opts)
+
+
 class _FullWindowBase:
     """What the two full-window estimators share: the extrinsic, the constants of Estimator::Estimate and the
     marginalization switch."""
