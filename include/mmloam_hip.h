@@ -988,6 +988,83 @@ int mml_world_map_associate(mml_ctx* ctx, int first_slot, int count, const int* 
 int mml_world_map_localize(mml_ctx* ctx, int first_slot, int count, const int* map_of_slot, const double* exTlb,
                            double* P, double* Q, const mml_wm_localize_opts* opts, mml_estimate_info* info);
 
+/* ---- relocalisation in a surfel world map: pose hypotheses scored on the device, a coarse-to-fine search -------------------
+ * mml_world_map_score: how well the surf stack of slot first_slot + i fits map map_of_slot[i] at each of n_hyp pose hypotheses
+ * (T_wl: count x n_hyp x 16, row-major lidar poses as mml_world_map_associate takes them), count x n_hyp results from ONE launch.
+ * The arithmetic is csrc/world_map_score.h (host and device).  Of the stack the call looks at the features 0, stride, 2 stride,
+ * ...; each goes through exactly the steps of mml_world_map_associate above: the world point; skipped when it has no voxel; the
+ * candidates and the choice; the winner's surfel normal and planarity; the two gates.  A feature that mml_world_map_associate
+ * would make a factor of is a match and contributes
+ *     q = (unsigned)((1.0 - fabs(d) / max_plane_dist) * 65536.0)     double arithmetic, truncated: 0 .. 65536
+ * with d the plane distance of the gate (a d that is not a number contributes 0).  Per (slot, hypothesis): n_scored = the features
+ * looked at and not skipped, n_match = the matches, score_q = the sum of q.  All three are integers: a result does not depend on
+ * summation order, launch geometry or batching, and is compared exactly.  A hypothesis with an entry that is not finite is not
+ * refused: its features have no voxel, n_scored = 0.  A slot with map -1 is skipped: its rows are zeros.
+ * Ranking, wherever a best hypothesis is chosen: the larger score_q, then the larger n_match, then the smaller index.
+ * The surfel cache: the first call that scores allocates one float4 (nx, ny, nz, planarity) per table position in the map's
+ * memory, 16 bytes per position more (MML_ERR_HIP before any launch if that fails), filled by one kernel, one lane per position,
+ * with the function mml_world_map_download_surfels runs.  mml_world_map_add (past its refusal point), _import, _reset, _create*
+ * and _destroy mark it stale on the host; the next score call rebuilds it first.  A match then costs one 16-byte load where the
+ * association loads 36 bytes of moments and runs the eigen-solver.  mml_world_map_associate itself does not use the cache.
+ * Host synchronisations: the read-back of the stack sizes at entry (the refusal of a slot without a stack, as in
+ * mml_world_map_associate) and ONE more, the read-back of the results.  The table, the slots, their factors and statistics are
+ * only read.  Refused before anything is written, the message names the offender: everything mml_world_map_associate refuses;
+ * MML_ERR_INVALID for n_hyp outside 1 .. 65536, count * n_hyp above 2^22, stride < 1, max_plane_dist not finite or <= 0 (the
+ * quantisation divides by it), NULL T_wl / out.
+ *
+ * mml_wm_pose_grid (host, no context): the hypotheses of a grid around the pose seed_T16.  Cells per axis: 2 floor(half / step) +
+ * 1 (the quotient is taken with 1e-9 added, so that 0.6 / 0.2 counts three steps); half = 0: one cell, the step is not read.  x
+ * and y share half_xy / step_xy.  Index ((iyaw nz + iz) ny + iy) nx + ix; cell c of an axis is offset (c - floor(half / step))
+ * step.  Hypothesis = Trans(t_seed + (dx, dy, dz)) Rz(yaw) R_seed: a shift along the world axes and a turn about the world z axis
+ * through the lidar's origin.  When the yaw cells cover the whole circle (2 floor(half_yaw / step_yaw) step_yaw = 2 pi to 1e-9)
+ * the last one, which would repeat the first, is dropped.  out NULL: the sizing call, *n_hyp alone.  MML_ERR_INVALID for an
+ * argument that is not finite, a negative half, half_yaw > pi, a step <= 0 on an axis with half > 0, NULL seed / n_hyp, more than
+ * 2^22 cells; MML_ERR_CAPACITY when capacity (hypotheses) is below the count (*n_hyp is set).
+ * mml_wm_body_pose (host): P, Q of the body from a lidar pose T_wl and exTlb -- the inverse of the composition mml_estimate and
+ * mml_world_map_localize apply to P, Q (T_wl = [Q, P] inverse(exTlb)); the conversion mml_world_map_relocalize hands T_start to
+ * its loop with.  mml_wm_lidar_pose (host): that composition itself, T_wl from P, Q and exTlb -- the seed of the level-0 grid and
+ * the pose `final` is scored at.
+ *
+ * mml_world_map_relocalize: a coarse-to-fine search around the seed poses P, Q of `count` slots, ending in
+ * mml_world_map_localize.  Level 0 scores mml_wm_pose_grid around every slot's seed lidar pose in one mml_world_map_score; the
+ * `keep` best hypotheses per slot (all of them when the grid has fewer) are chosen on the host; each further level divides every
+ * step by `refine` and scores, again in one call for all slots, the grids of +-1 previous step around the kept hypotheses in
+ * their order (index = kept rank x cells + cell).  The best hypothesis of the last level is T_start; one
+ * mml_world_map_localize runs over the count slots from mml_wm_body_pose(T_start); one last score call at the result fills
+ * `final`.  info[i]: best = the score of the best level-0 hypothesis; second = that of the best level-0 hypothesis that is not
+ * its neighbour (index distance > 1 on some axis, yaw cyclic when the grid covers the circle; zeros when there is none) -- its
+ * ratio to best is the caller's ambiguity measure, the call applies no threshold; n_hyp_scored = the hypotheses of all levels;
+ * est = mml_world_map_localize's.  All slots share one grid shape.  Host synchronisations: one at entry (the stack sizes), one per
+ * level, mml_world_map_localize's (one at entry and one per outer iteration) and one for `final`.  Refused before anything is
+ * written: what the score and the loop refuse, levels outside 1 .. 3, refine outside 2 .. 4, keep outside 1 .. 16, what
+ * mml_wm_pose_grid refuses, a level of more than 65536 hypotheses per slot or 2^22 per call. */
+typedef struct { unsigned long long score_q; int n_match; int n_scored; } mml_wm_score;
+typedef struct { mml_wm_assoc_opts assoc; int stride; } mml_wm_score_opts;  /* features 0, stride, 2 stride, ...; stride >= 1 */
+void mml_wm_score_opts_default(mml_wm_score_opts* opts, float leaf);         /* assoc defaults, max_plane_dist = leaf, stride 1 */
+int mml_world_map_score(mml_ctx* ctx, int first_slot, int count, const int* map_of_slot /* -1 skips: its results are zeros */,
+                        int n_hyp /* per slot, 1..65536; count * n_hyp <= 2^22 */, const double* T_wl /* count x n_hyp x 16 */,
+                        const mml_wm_score_opts* opts, mml_wm_score* out /* count x n_hyp */);
+typedef struct {
+    double half_xy, step_xy, half_z, step_z;   /* metres, world axes; half 0: one cell on that axis */
+    double half_yaw, step_yaw;                 /* radians about the world z axis through the lidar's origin; half_yaw <= pi */
+    int levels;                                /* 1..3 */
+    int refine;                                /* 2..4: a further level divides every step by this and spans +-1 previous step */
+    int keep;                                  /* 1..16 hypotheses carried from one level to the next */
+    mml_wm_score_opts score;
+    mml_wm_localize_opts localize;
+} mml_wm_reloc_opts;
+typedef struct { mml_wm_score best, second, final; long n_hyp_scored; double T_start[16]; mml_estimate_info est; } mml_wm_reloc_info;
+/* 2 m / 0.5 m in x and y, one z cell, the whole circle in steps of pi / 16; 2 levels, refine 2, keep 4; the score's and the
+ * loop's defaults for the leaf */
+void mml_wm_reloc_opts_default(mml_wm_reloc_opts* opts, float leaf);
+int mml_wm_pose_grid(const double* seed_T16, double half_xy, double step_xy, double half_z, double step_z, double half_yaw,
+                     double step_yaw, double* out /* H x 16 or NULL: sizing */, long capacity, long* n_hyp);
+int mml_wm_body_pose(const double* T_wl, const double* exTlb, double* P /* 3 */, double* Q /* 4: x y z w */);
+int mml_wm_lidar_pose(const double* P, const double* Q, const double* exTlb, double* T_wl /* 16 */);
+int mml_world_map_relocalize(mml_ctx* ctx, int first_slot, int count, const int* map_of_slot, const double* exTlb,
+                             double* P, double* Q /* in: seed body poses; out: result */, const mml_wm_reloc_opts* opts,
+                             mml_wm_reloc_info* info /* count entries or NULL */);
+
 /* ---- the benchmarked step ---------------------------------------------------------------------------
  * One pass of the hot path over slots [first, first+count) with inputs already uploaded:
  * extract -> undistort -> downsample -> associate (1 pass, thres_dist) -> `gn_iters` trust-region

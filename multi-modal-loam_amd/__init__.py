@@ -261,6 +261,93 @@ def wm_localize_opts(leaf, **over):
     return o
 
 
+# ... and relocalisation in it (include/mmloam_hip.h, "relocalisation in a surfel world map")
+class WmScore(C.Structure):
+    """mml_wm_score"""
+    _fields_ = [("score_q", C.c_ulonglong), ("n_match", C.c_int), ("n_scored", C.c_int)]
+
+
+WM_SCORE_DT = np.dtype([("score_q", np.uint64), ("n_match", np.int32), ("n_scored", np.int32)])
+
+
+class WmScoreOpts(C.Structure):
+    """mml_wm_score_opts"""
+    _fields_ = [("assoc", WmAssocOpts), ("stride", C.c_int)]
+
+
+class WmRelocOpts(C.Structure):
+    """mml_wm_reloc_opts"""
+    _fields_ = [("half_xy", C.c_double), ("step_xy", C.c_double), ("half_z", C.c_double), ("step_z", C.c_double), ("half_yaw", C.c_double),
+                ("step_yaw", C.c_double), ("levels", C.c_int), ("refine", C.c_int), ("keep", C.c_int), ("score", WmScoreOpts),
+                ("localize", WmLocalizeOpts)]
+
+
+class WmRelocInfo(C.Structure):
+    """mml_wm_reloc_info"""
+    _fields_ = [("best", WmScore), ("second", WmScore), ("final", WmScore), ("n_hyp_scored", C.c_long), ("T_start", C.c_double * 16),
+                ("est", EstimateInfo)]
+
+
+WORLD_MAP_SCORE_ARGTYPES = {
+    "mml_world_map_score": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "mml_wm_pose_grid": [C.c_void_p] + [C.c_double] * 6 + [C.c_void_p, C.c_long, C.c_void_p],
+    "mml_wm_body_pose": [C.c_void_p] * 4,
+    "mml_wm_lidar_pose": [C.c_void_p] * 4,
+    "mml_world_map_relocalize": [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6,
+}
+
+
+def wm_score_opts(leaf, **over):
+    """mml_wm_score_opts_default(leaf) with fields replaced; the fields of `assoc` may be given directly (max_plane_dist=...)"""
+    o = WmScoreOpts()
+    lib().mml_wm_score_opts_default(C.byref(o), C.c_float(leaf))
+    for k, v in over.items():
+        setattr(o.assoc if k in ("neighbourhood", "min_points", "min_planarity", "max_plane_dist") else o, k, v)
+    return o
+
+
+def wm_reloc_opts(leaf, **over):
+    """mml_wm_reloc_opts_default(leaf) with fields replaced; score: a WmScoreOpts, localize: a WmLocalizeOpts"""
+    o = WmRelocOpts()
+    lib().mml_wm_reloc_opts_default(C.byref(o), C.c_float(leaf))
+    for k, v in over.items():
+        setattr(o, k, v)
+    return o
+
+
+def wm_pose_grid(seed, half_xy, step_xy, half_z=0.0, step_z=1.0, half_yaw=0.0, step_yaw=1.0):
+    """mml_wm_pose_grid: the (H, 4, 4) hypotheses of the grid around the pose `seed`, index ((iyaw nz + iz) ny + iy) nx + ix"""
+    seed = _f64(seed).reshape(16)
+    n = C.c_long(0)
+    a = [C.c_double(float(v)) for v in (half_xy, step_xy, half_z, step_z, half_yaw, step_yaw)]
+    rc = lib().mml_wm_pose_grid(_p(seed), *a, None, 0, C.byref(n))
+    if rc != MML_OK:
+        raise MmlError(rc, "mml_wm_pose_grid: refused (a value not finite, a negative half, half_yaw > pi, a step <= 0, too many cells)")
+    out = np.zeros((n.value, 4, 4))
+    rc = lib().mml_wm_pose_grid(_p(seed), *a, _p(out), n.value, C.byref(n))
+    if rc != MML_OK:
+        raise MmlError(rc, "mml_wm_pose_grid")
+    return out
+
+
+def wm_body_pose(T_wl, exTlb):
+    """mml_wm_body_pose: P (3), Q (4, x y z w) of the body from the lidar pose T_wl and exTlb"""
+    P, Q = np.zeros(3), np.zeros(4)
+    rc = lib().mml_wm_body_pose(_p(_f64(T_wl).reshape(16)), _p(_f64(exTlb).reshape(16)), _p(P), _p(Q))
+    if rc != MML_OK:
+        raise MmlError(rc, "mml_wm_body_pose")
+    return P, Q
+
+
+def wm_lidar_pose(P, Q, exTlb):
+    """mml_wm_lidar_pose: the (4, 4) lidar pose T_wl = [Q, P] inverse(exTlb), as the pose calls compose it"""
+    T = np.zeros((4, 4))
+    rc = lib().mml_wm_lidar_pose(_p(_f64(P).reshape(3)), _p(_f64(Q).reshape(4)), _p(_f64(exTlb).reshape(16)), _p(T))
+    if rc != MML_OK:
+        raise MmlError(rc, "mml_wm_lidar_pose")
+    return T
+
+
 def build(force=False):
     """Compile csrc/*.hip for gfx950 into libmmloam_hip.so (hipcc cross-compiles without a GPU)."""
     csrc = os.path.join(_HERE, "csrc")
@@ -463,6 +550,13 @@ def lib():
                 getattr(L, name).restype = C.c_int
                 getattr(L, name).argtypes = args
             for name in ("mml_wm_assoc_opts_default", "mml_wm_localize_opts_default"):
+                getattr(L, name).restype = None
+                getattr(L, name).argtypes = [C.c_void_p, C.c_float]
+        if hasattr(L, "mml_world_map_score"):
+            for name, args in WORLD_MAP_SCORE_ARGTYPES.items():
+                getattr(L, name).restype = C.c_int
+                getattr(L, name).argtypes = args
+            for name in ("mml_wm_score_opts_default", "mml_wm_reloc_opts_default"):
                 getattr(L, name).restype = None
                 getattr(L, name).argtypes = [C.c_void_p, C.c_float]
         _lib = L
@@ -1395,6 +1489,31 @@ class Context:
             opts = wm_localize_opts(getattr(self, "_wm_leaf", 1.0))
         self._ck(lib().mml_world_map_localize(self._h, int(first), len(m), _p(m), _p(_f64(exTlb).reshape(16)), _p(P), _p(Q),
                                               C.byref(opts), info))
+        return P, Q, list(info)
+
+    def world_map_score(self, first, maps, T_wl, opts=None):
+        """mml_world_map_score: the surf stacks of slots first + i against map maps[i] (-1: zeros) at every hypothesis of T_wl
+        (len(maps), H, 4, 4), ONE launch.  opts: a WmScoreOpts (wm_score_opts(leaf, ...)).  Returns a (len(maps), H) structured
+        array (score_q, n_match, n_scored)."""
+        m = np.ascontiguousarray(maps, dtype=np.int32).reshape(-1)
+        T = _f64(T_wl).reshape(len(m), -1, 16)
+        out = np.zeros((len(m), T.shape[1]), WM_SCORE_DT)
+        if opts is None:
+            opts = wm_score_opts(getattr(self, "_wm_leaf", 1.0))
+        self._ck(lib().mml_world_map_score(self._h, int(first), len(m), _p(m), T.shape[1], _p(T), C.byref(opts), _p(out)))
+        return out
+
+    def world_map_relocalize(self, first, maps, exTlb, P, Q, opts=None):
+        """mml_world_map_relocalize: the coarse-to-fine search around the seed poses P, Q, ending in world_map_localize.  opts: a
+        WmRelocOpts (wm_reloc_opts(leaf, ...)).  Returns P, Q, [WmRelocInfo]."""
+        m = np.ascontiguousarray(maps, dtype=np.int32).reshape(-1)
+        P = _f64(P).reshape(len(m), 3).copy()
+        Q = _f64(Q).reshape(len(m), 4).copy()
+        info = (WmRelocInfo * len(m))()
+        if opts is None:
+            opts = wm_reloc_opts(getattr(self, "_wm_leaf", 1.0))
+        self._ck(lib().mml_world_map_relocalize(self._h, int(first), len(m), _p(m), _p(_f64(exTlb).reshape(16)), _p(P), _p(Q),
+                                                C.byref(opts), info))
         return P, Q, list(info)
 
     # ---- map banks: further local maps, every slot matched against its own (include/mmloam_hip.h, "map banks") ----

@@ -15,7 +15,7 @@
 #include "fused_view_dev.h"
 #include "phase_clock.h"
 #include "raw_gather_dev.h"
-#include "world_map_key.h"
+#include "world_map_score.h"
 
 int mml_launch_detect_line(mml_ctx* ctx, int n, uint16_t* d_final);
 
@@ -1699,6 +1699,240 @@ int mml_world_map_localize(mml_ctx* ctx, int first_slot, int count, const int* m
     const int rc = mml_wm_assoc_ready(ctx, "mml_world_map_localize", first_slot, count, map_of_slot, &ao[0], true);
     if (rc != MML_OK) return rc;
     return estimate_loop(ctx, first_slot, count, exTlb, P, Q, opts->max_outer, opts->inner_iters, info, ao);
+}
+
+// ---- relocalisation in a surfel world map (world_map_score.hip): the score call, the search grid and the search ----
+int mml_world_map_score(mml_ctx* ctx, int first_slot, int count, const int* map_of_slot, int n_hyp, const double* T_wl,
+                        const mml_wm_score_opts* opts, mml_wm_score* out) {
+    CHECK_SLOTS(first_slot, count);
+    return mml_wm_score_run(ctx, "mml_world_map_score", first_slot, count, map_of_slot, n_hyp, T_wl, opts, out, true);
+}
+
+// The shape of mml_wm_pose_grid: k steps on each side of an axis, floor(half / step) with 1e-9 added to the quotient, so that
+// 0.6 / 0.2 counts three; nw: the yaw cells, one fewer than 2 kw + 1 when they cover the circle.  Plain host arithmetic.
+struct WmGridShape {
+    long kx, kz, kw, nx, nz, nw, n;
+    bool cyclic;
+};
+static bool wm_grid_axis(double half, double step, long& k) {
+    k = 0;
+    if (!isfinite(half) || !isfinite(step) || half < 0.0) return false;
+    if (half == 0.0) return true;
+    if (!(step > 0.0)) return false;
+    const double q = floor(half / step + 1e-9);
+    if (!(q <= (double)(1 << 22))) return false;
+    k = (long)q;
+    return true;
+}
+static bool wm_grid_shape(double half_xy, double step_xy, double half_z, double step_z, double half_yaw, double step_yaw, WmGridShape& g) {
+    if (!wm_grid_axis(half_xy, step_xy, g.kx) || !wm_grid_axis(half_z, step_z, g.kz) || !wm_grid_axis(half_yaw, step_yaw, g.kw)) return false;
+    if (half_yaw > M_PI) return false;
+    g.nx = 2 * g.kx + 1;
+    g.nz = 2 * g.kz + 1;
+    g.nw = 2 * g.kw + 1;
+    g.cyclic = g.kw > 0 && fabs(2.0 * (double)g.kw * step_yaw - 2.0 * M_PI) <= 1e-9;
+    if (g.cyclic) g.nw -= 1;  // (the last cell would repeat the first)
+    if (((double)g.nx * (double)g.nx) * ((double)g.nz * (double)g.nw) > (double)(1 << 22)) return false;
+    g.n = g.nx * g.nx * g.nz * g.nw;
+    return true;
+}
+
+int mml_wm_pose_grid(const double* seed, double half_xy, double step_xy, double half_z, double step_z, double half_yaw, double step_yaw,
+                     double* out, long capacity, long* n_hyp) {
+    if (!seed || !n_hyp) return MML_ERR_INVALID;
+    for (int c = 0; c < 12; ++c)
+        if (!isfinite(seed[c])) return MML_ERR_INVALID;
+    WmGridShape g;
+    if (!wm_grid_shape(half_xy, step_xy, half_z, step_z, half_yaw, step_yaw, g)) return MML_ERR_INVALID;
+    *n_hyp = g.n;
+    if (!out) return MML_OK;
+    if (capacity < g.n) return MML_ERR_CAPACITY;
+    for (long iw = 0; iw < g.nw; ++iw) {
+        const double yaw = (double)(iw - g.kw) * step_yaw, cw = cos(yaw), sw = sin(yaw);
+        for (long iz = 0; iz < g.nz; ++iz)
+            for (long iy = 0; iy < g.nx; ++iy)
+                for (long ix = 0; ix < g.nx; ++ix) {
+                    double* T = out + 16 * (((iw * g.nz + iz) * g.nx + iy) * g.nx + ix);
+                    for (int c = 0; c < 3; ++c) {  // Rz(yaw) R_seed
+                        T[c] = cw * seed[c] - sw * seed[4 + c];
+                        T[4 + c] = sw * seed[c] + cw * seed[4 + c];
+                        T[8 + c] = seed[8 + c];
+                    }
+                    T[3] = seed[3] + (double)(ix - g.kx) * step_xy;
+                    T[7] = seed[7] + (double)(iy - g.kx) * step_xy;
+                    T[11] = seed[11] + (double)(iz - g.kz) * step_z;
+                    T[12] = T[13] = T[14] = 0.0;
+                    T[15] = 1.0;
+                }
+    }
+    return MML_OK;
+}
+
+// [Q, P] = T_wl exTlb: the inverse of pose_to_Twl (T_wl = [Q, P] inverse(exTlb))
+int mml_wm_body_pose(const double* T_wl, const double* exTlb, double* P, double* Q) {
+    if (!T_wl || !exTlb || !P || !Q) return MML_ERR_INVALID;
+    M3 R;
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) R.a[3 * r + c] = (T_wl[4 * r] * exTlb[c] + T_wl[4 * r + 1] * exTlb[4 + c]) + T_wl[4 * r + 2] * exTlb[8 + c];
+        P[r] = ((T_wl[4 * r] * exTlb[3] + T_wl[4 * r + 1] * exTlb[7]) + T_wl[4 * r + 2] * exTlb[11]) + T_wl[4 * r + 3];
+    }
+    double q[4];
+    m3_to_quat(R, q);
+    const double n = sqrt((q[0] * q[0] + q[1] * q[1]) + (q[2] * q[2] + q[3] * q[3]));
+    for (int c = 0; c < 4; ++c) Q[c] = q[c] / n;
+    return MML_OK;
+}
+
+// T_wl = [Q, P] inverse(exTlb), as estimate_loop composes it
+int mml_wm_lidar_pose(const double* P, const double* Q, const double* exTlb, double* T_wl) {
+    if (!P || !Q || !exTlb || !T_wl) return MML_ERR_INVALID;
+    double T_bl[16];
+    invert_extrinsic(exTlb, T_bl);
+    pose_to_Twl(Q, P, T_bl, T_wl);
+    return MML_OK;
+}
+
+void mml_wm_reloc_opts_default(mml_wm_reloc_opts* o, float leaf) {
+    if (!o) return;
+    memset(o, 0, sizeof(*o));
+    o->half_xy = 2.0;
+    o->step_xy = 0.5;
+    o->half_z = 0.0;
+    o->step_z = 0.5;
+    o->half_yaw = M_PI;
+    o->step_yaw = M_PI / 16.0;
+    o->levels = 2;
+    o->refine = 2;
+    o->keep = 4;
+    mml_wm_score_opts_default(&o->score, leaf);
+    mml_wm_localize_opts_default(&o->localize, leaf);
+}
+
+int mml_world_map_relocalize(mml_ctx* ctx, int first_slot, int count, const int* map_of_slot, const double* exTlb, double* P, double* Q,
+                             const mml_wm_reloc_opts* o, mml_wm_reloc_info* info) {
+    static const char* who = "mml_world_map_relocalize";
+    CHECK_SLOTS(first_slot, count);
+    MML_REQUIRE(exTlb && P && Q && o, MML_ERR_INVALID, "mml_world_map_relocalize: null exTlb / P / Q / opts");
+    if (o->levels < 1 || o->levels > 3) return mml_refuse(ctx, MML_ERR_INVALID, "%s: levels %d outside 1..3", who, o->levels);
+    if (o->refine < 2 || o->refine > 4) return mml_refuse(ctx, MML_ERR_INVALID, "%s: refine %d outside 2..4", who, o->refine);
+    if (o->keep < 1 || o->keep > 16) return mml_refuse(ctx, MML_ERR_INVALID, "%s: keep %d outside 1..16", who, o->keep);
+    if (o->score.stride < 1) return mml_refuse(ctx, MML_ERR_INVALID, "%s: stride %d < 1", who, o->score.stride);
+    if (!(isfinite(o->score.assoc.max_plane_dist) && o->score.assoc.max_plane_dist > 0.0))
+        return mml_refuse(ctx, MML_ERR_INVALID, "%s: score.assoc.max_plane_dist must be finite and > 0 (the score divides by it)", who);
+    MML_REQUIRE(o->localize.max_outer >= 1 && o->localize.inner_iters >= 0, MML_ERR_INVALID, "mml_world_map_relocalize: localize.max_outer < 1 or inner_iters < 0");
+    for (int k = 0; k < 3; ++k) {
+        mml_wm_assoc_opts a = o->localize.assoc;
+        a.max_plane_dist = o->localize.max_plane_dist_by_outer[k];
+        const int rc = mml_wm_assoc_opts_ok(ctx, who, &a);
+        if (rc != MML_OK) return rc;
+    }
+    for (int i = 0; i < count; ++i)
+        for (int c = 0; c < 7; ++c)
+            if (!isfinite(c < 3 ? P[3 * i + c] : Q[4 * i + c - 3])) return mml_refuse(ctx, MML_ERR_INVALID, "%s: the seed pose of slot %d is not finite", who, first_slot + i);
+    for (int c = 0; c < 12; ++c)
+        if (!isfinite(exTlb[c])) return mml_refuse(ctx, MML_ERR_INVALID, "%s: exTlb is not finite", who);
+    // the shapes of all levels, before anything runs: level l > 0 holds, per kept hypothesis, the grid of +-1 step of level l - 1
+    WmGridShape shape[3];
+    double step[3][3];  // per level: xy, z, yaw
+    long kept[3], n_level[3];
+    for (int l = 0; l < o->levels; ++l) {
+        bool ok;
+        if (l == 0) {
+            step[0][0] = o->step_xy, step[0][1] = o->step_z, step[0][2] = o->step_yaw;
+            ok = wm_grid_shape(o->half_xy, o->step_xy, o->half_z, o->step_z, o->half_yaw, o->step_yaw, shape[0]);
+            kept[0] = 1;
+        } else {
+            for (int a = 0; a < 3; ++a) step[l][a] = step[l - 1][a] / (double)o->refine;
+            const WmGridShape& p = shape[l - 1];  // (an axis of one cell stays one cell)
+            ok = wm_grid_shape(p.kx ? step[l - 1][0] : 0.0, step[l][0], p.kz ? step[l - 1][1] : 0.0, step[l][1], p.kw ? step[l - 1][2] : 0.0, step[l][2], shape[l]);
+            kept[l] = n_level[l - 1] < o->keep ? n_level[l - 1] : o->keep;
+        }
+        if (!ok) return mml_refuse(ctx, MML_ERR_INVALID, "%s: mml_wm_pose_grid refuses the grid of level %d (not finite, half < 0, half_yaw > pi, step <= 0 or above 2^22 cells)", who, l);
+        n_level[l] = kept[l] * shape[l].n;
+        if (n_level[l] > 65536 || (long long)count * n_level[l] > (1LL << 22))
+            return mml_refuse(ctx, MML_ERR_INVALID, "%s: level %d has %ld hypotheses per slot: above 65536, or above 2^22 for the %d slots", who, l, n_level[l], count);
+    }
+    int rc = mml_wm_assoc_ready(ctx, who, first_slot, count, map_of_slot, &o->score.assoc, true);
+    if (rc != MML_OK) return rc;
+    double T_bl[16];
+    invert_extrinsic(exTlb, T_bl);
+    std::vector<double> T, Tprev;
+    std::vector<mml_wm_score> sc;
+    std::vector<mml_wm_reloc_info> inf((size_t)count);
+    memset(static_cast<void*>(inf.data()), 0, sizeof(mml_wm_reloc_info) * (size_t)count);
+    std::vector<long> top((size_t)count * 16, 0);  // per slot: the kept hypotheses of the level, best first
+    for (int l = 0; l < o->levels; ++l) {
+        const size_t H = (size_t)n_level[l];
+        T.assign(16 * H * (size_t)count, 0.0);
+        for (int i = 0; i < count; ++i)
+            for (long k = 0; k < kept[l]; ++k) {
+                double seed[16];
+                if (l == 0)
+                    pose_to_Twl(Q + 4 * i, P + 3 * i, T_bl, seed);
+                else
+                    memcpy(seed, &Tprev[16 * ((size_t)i * (size_t)n_level[l - 1] + (size_t)top[16 * (size_t)i + (size_t)k])], sizeof(seed));
+                const WmGridShape& p = shape[l > 0 ? l - 1 : 0];
+                long n = 0;
+                rc = l == 0 ? mml_wm_pose_grid(seed, o->half_xy, o->step_xy, o->half_z, o->step_z, o->half_yaw, o->step_yaw, &T[16 * H * (size_t)i], (long)H, &n)
+                            : mml_wm_pose_grid(seed, p.kx ? step[l - 1][0] : 0.0, step[l][0], p.kz ? step[l - 1][1] : 0.0, step[l][1],
+                                               p.kw ? step[l - 1][2] : 0.0, step[l][2], &T[16 * (H * (size_t)i + (size_t)(k * shape[l].n))], shape[l].n, &n);
+                if (rc != MML_OK || n != shape[l].n) return mml_refuse(ctx, MML_ERR_INVALID, "%s: the grid of level %d around slot %d could not be made", who, l, first_slot + i);
+            }
+        sc.assign(H * (size_t)count, mml_wm_score{0, 0, 0});
+        rc = mml_wm_score_run(ctx, who, first_slot, count, map_of_slot, (int)H, T.data(), &o->score, sc.data(), false);
+        if (rc != MML_OK) return rc;
+        const long keep_n = (long)H < o->keep ? (long)H : o->keep;
+        for (int i = 0; i < count; ++i) {
+            const mml_wm_score* s = &sc[H * (size_t)i];
+            long* tp = &top[16 * (size_t)i];
+            for (long k = 0; k < keep_n; ++k) {  // selection of the keep_n best, in ranking order
+                long b = -1;
+                for (long h = 0; h < (long)H; ++h) {
+                    bool taken = false;
+                    for (long j = 0; j < k; ++j) taken = taken || tp[j] == h;
+                    if (taken) continue;
+                    if (b < 0 || mml_wms_better(s[h].score_q, s[h].n_match, h, s[b].score_q, s[b].n_match, b)) b = h;
+                }
+                tp[k] = b;
+            }
+            inf[(size_t)i].n_hyp_scored += (long)H;
+            if (l == 0) {
+                const WmGridShape& g = shape[0];
+                inf[(size_t)i].best = s[tp[0]];
+                const long b = tp[0], bx = b % g.nx, by = (b / g.nx) % g.nx, bz = (b / (g.nx * g.nx)) % g.nz, bw = b / (g.nx * g.nx * g.nz);
+                long second = -1;
+                for (long h = 0; h < (long)H; ++h) {
+                    const long hx = h % g.nx, hy = (h / g.nx) % g.nx, hz = (h / (g.nx * g.nx)) % g.nz, hw = h / (g.nx * g.nx * g.nz);
+                    long dw = labs(hw - bw);
+                    if (g.cyclic && g.nw - dw < dw) dw = g.nw - dw;
+                    if (labs(hx - bx) <= 1 && labs(hy - by) <= 1 && labs(hz - bz) <= 1 && dw <= 1) continue;  // a neighbour (or the best itself)
+                    if (second < 0 || mml_wms_better(s[h].score_q, s[h].n_match, h, s[second].score_q, s[second].n_match, second)) second = h;
+                }
+                if (second >= 0) inf[(size_t)i].second = s[second];
+            }
+            if (l == o->levels - 1) memcpy(inf[(size_t)i].T_start, &T[16 * (H * (size_t)i + (size_t)tp[0])], sizeof(double) * 16);
+        }
+        Tprev.swap(T);
+    }
+    std::vector<double> Ps(3 * (size_t)count), Qs(4 * (size_t)count);
+    for (int i = 0; i < count; ++i) mml_wm_body_pose(inf[(size_t)i].T_start, exTlb, &Ps[3 * (size_t)i], &Qs[4 * (size_t)i]);
+    std::vector<mml_estimate_info> est((size_t)count);
+    rc = mml_world_map_localize(ctx, first_slot, count, map_of_slot, exTlb, Ps.data(), Qs.data(), &o->localize, est.data());
+    if (rc != MML_OK) return rc;
+    T.assign(16 * (size_t)count, 0.0);
+    for (int i = 0; i < count; ++i) pose_to_Twl(&Qs[4 * (size_t)i], &Ps[3 * (size_t)i], T_bl, &T[16 * (size_t)i]);
+    sc.assign((size_t)count, mml_wm_score{0, 0, 0});
+    rc = mml_wm_score_run(ctx, who, first_slot, count, map_of_slot, 1, T.data(), &o->score, sc.data(), false);
+    if (rc != MML_OK) return rc;
+    memcpy(P, Ps.data(), sizeof(double) * 3 * (size_t)count);
+    memcpy(Q, Qs.data(), sizeof(double) * 4 * (size_t)count);
+    if (info)
+        for (int i = 0; i < count; ++i) {
+            inf[(size_t)i].final = sc[(size_t)i];
+            inf[(size_t)i].est = est[(size_t)i];
+            info[i] = inf[(size_t)i];
+        }
+    return MML_OK;
 }
 
 int mml_step(mml_ctx* ctx, int first_slot, int count, const double* dR, const double* dt, const double* exTlb,

@@ -191,6 +191,7 @@ enum MmlSideId {
     MML_SIDE_FEATURE_CLOUDS,  // capi.hip MmlFeatCloudsDev: the table block of mml_feature_clouds_download_batch
     MML_SIDE_IMU_FETCH,    // imu_stream.hip MmlImuFetchDev: the block of mml_imu_fetch_batch / mml_imu_predict_batch
     MML_SIDE_POSE_INGEST,  // pose_ingest.hip MmlPoseIngestDev: the table block of mml_pose_ingest_batch
+    MML_SIDE_WM_SCORE,     // world_map_score.hip MmlWmScoreDev: the hypotheses and results of mml_world_map_score
     MML_SIDE_COUNT
 };
 
@@ -388,7 +389,11 @@ struct mml_ctx {
         float4* sum = nullptr;               // slots: x, y, z, intensity
         int* count = nullptr;                // slots
         int* map_n = nullptr;                // n_maps + 1: voxels per map, then the total
-        MmlGroup mem;                        // owns the four, and mom[] of a surfel map
+        MmlGroup mem;                        // owns the four, mom[] of a surfel map and, once a call has scored, the cache
+        float4* cache = nullptr;             // slots: (nx, ny, nz, planarity) of every position's surfel, 16 bytes per position more;
+                                             //        allocated by the first mml_world_map_score (world_map.hip mml_wm_cache_ready)
+        unsigned long long version = 0;      // advanced on the host by every call that writes the table (world_map.hip wm_touch)
+        unsigned long long cache_version = 0;  // the version the cache was filled from; behind `version`: stale
         MmlStaging<char, false> scratch;     // the calls' scratch (one call at a time)
         MmlStaging<char, false> tmp;         // rocPRIM temporary storage
         MmlStaging<char> tab;                // a call's slot rows and counters: device block and pinned twin
@@ -404,6 +409,8 @@ struct mml_ctx {
             count = nullptr;
             map_n = nullptr;
             mom[0] = mom[1] = mom[2] = nullptr;
+            cache = nullptr;
+            ++version;
             surfels = false;
             n_maps = 0;
         }
@@ -619,7 +626,14 @@ int mml_ensure_assoc_stats(mml_ctx* ctx, int first, int count);
 // [first, first + count) -- before any device work but ONE read-back of the stack sizes -- and the call's map numbers sent down;
 // mml_launch_wm_associate: k_wm_associate for those slots at the poses d_Twl (16 doubles per slot, on the device), enqueue only.
 int mml_wm_assoc_ready(mml_ctx* ctx, const char* who, int first, int count, const int* map_of_slot, const mml_wm_assoc_opts* o, bool need_all);
+int mml_wm_assoc_opts_ok(mml_ctx* ctx, const char* who, const mml_wm_assoc_opts* o);  // the option refusals alone, host only
 int mml_launch_wm_associate(mml_ctx* ctx, int first, int count, const double* d_Twl, const mml_wm_assoc_opts& o);
+// world_map.hip: the surfel cache of a surfel map made valid for the table as it is (allocated on first use, rebuilt when stale),
+// enqueue only.  world_map_score.hip: mml_world_map_score behind its argument checks; ready = false: the caller has run
+// mml_wm_assoc_ready for these slots and maps itself (mml_world_map_relocalize, once for all its levels).
+int mml_wm_cache_ready(mml_ctx* ctx);
+int mml_wm_score_run(mml_ctx* ctx, const char* who, int first, int count, const int* map_of_slot, int n_hyp, const double* T_wl,
+                     const mml_wm_score_opts* o, mml_wm_score* out, bool ready);
 #define MML_SOLVE_RESULT 24  // doubles per problem of k_solve's result record: x (6), stack sizes (2), association statistics (16)
 // d_x_in / d_result (a PoseBlock's start poses, the result records): packed pose calls only, mml_pose_packed(count, ctx->cus)
 int mml_launch_solve(mml_ctx* ctx, int first, int count, int window, const double* d_Tbl, mml_solve_opts opts,

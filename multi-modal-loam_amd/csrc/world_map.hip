@@ -35,6 +35,13 @@
 // mml_world_map_export is a fourth gather of that chain (the stored sums, counts, moments and the sorted keys as voxel indices);
 // mml_world_map_import checks its rows on the host, looks all of them up in one launch (k_wm_import_find), refuses at the add's
 // refusal point -- one read-back, only scratch written -- and then claims and stores them, one lane per voxel (k_wm_import_put).
+//
+// THE SURFEL CACHE (mml_wm_cache_ready, for mml_world_map_score): one float4 per table position, (nx, ny, nz, planarity) of the
+// position's surfel, 16 bytes per position more (92 instead of 76), allocated in the map's memory group by the first call that
+// scores and filled by k_wm_surfel_cache, one lane per position, register-only, wm_surfel as everywhere.  It is valid for the
+// table version it was built from: every call that writes the table -- add past its refusal point, import, reset, create, destroy
+// -- advances WorldMap::version on the host (wm_touch; no kernel of theirs knows of the cache), and a score call rebuilds a
+// cache whose version is behind.
 #include <limits.h>
 #include <math.h>
 #include <string.h>
@@ -45,7 +52,7 @@
 #include "mml_internal.h"
 #include "fused_view_dev.h"
 #include "voxel_sort_dev.h"
-#include "world_map_key.h"
+#include "world_map_assoc.h"
 
 namespace {
 #include "eig3_dev.h"
@@ -238,6 +245,15 @@ __global__ __launch_bounds__(256) void k_wm_surfels(const unsigned* __restrict__
     out[2 * (size_t)i] = o0;
     out[2 * (size_t)i + 1] = o1;
 }
+// the surfel cache: every position's entry (wm_cache_entry, world_map_dev.h); a free position holds zeros
+__global__ __launch_bounds__(256) void k_wm_surfel_cache(const unsigned long long* __restrict__ tab, unsigned long long slots, WmMom M,
+                                                         const int* __restrict__ count, float4* __restrict__ cache) {
+    const unsigned long long h = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (h >= slots) return;
+    float4 e = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (tab[h] != MML_WM_EMPTY) e = wm_cache_entry(wm_moments(M.m0[h], M.m1[h], M.m2[h]), count[h]);
+    cache[h] = e;
+}
 // reset of one map: the survivors' accumulators beside their keys, before the table is cleared ...
 __global__ __launch_bounds__(256) void k_wm_take(const unsigned* __restrict__ vals, int n, const float4* __restrict__ sum,
                                                  const int* __restrict__ count, float4* __restrict__ s_sum, int* __restrict__ s_n, WmMom M,
@@ -325,6 +341,8 @@ int wm_clear(mml_ctx* ctx, hipStream_t s) {
     return MML_OK;
 }
 unsigned wm_blocks(size_t n) { return (unsigned)((n + 255) / 256); }
+// the table is about to be written: whatever was derived from it (the surfel cache) is stale from here on
+void wm_touch(mml_ctx::WorldMap& W) { ++W.version; }
 WmMom wm_mom(const mml_ctx::WorldMap& W) { return WmMom{W.mom[0], W.mom[1], W.mom[2]}; }
 
 // mml_world_map_create and _create_opts
@@ -351,6 +369,7 @@ int wm_create(mml_ctx* ctx, int n_maps, float leaf, long capacity_voxels, unsign
     W.leaf = leaf;
     W.capacity = capacity_voxels;
     W.slots = slots;
+    wm_touch(W);
     hipStream_t s = MML_STREAM(ctx);
     rc = wm_clear(ctx, s);
     if (rc == MML_OK && hipStreamSynchronize(s) != hipSuccess) rc = mml_refuse(ctx, MML_ERR_HIP, "mml_world_map_create: hipStreamSynchronize failed");
@@ -391,6 +410,7 @@ int mml_world_map_reset(mml_ctx* ctx, int map) {
     mml_ctx::WorldMap& W = ctx->world;
     if (map < -1 || map >= W.n_maps) return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_reset: map %d outside [-1, %d)", map, W.n_maps);
     hipStream_t s = MML_STREAM(ctx);
+    wm_touch(W);
     if (map < 0) return wm_clear(ctx, s);
     // One map of several: an open-addressing table has no way to free a position inside a probe chain (every key value is in use,
     // there is no tombstone), so the other maps' voxels are taken out, the table is cleared and they are put back.
@@ -516,6 +536,7 @@ int mml_world_map_add(mml_ctx* ctx, int first_slot, int count, const int* map_of
     if (total + misses > W.capacity)
         return mml_refuse(ctx, MML_ERR_CAPACITY, "mml_world_map_add: %ld voxels held + %ld new ones exceed capacity_voxels %ld; nothing was added", total,
                           misses, W.capacity);
+    wm_touch(W);
     if (h_cnt[WM_DISTINCT] && W.surfels)
         hipLaunchKernelGGL(k_wm_insert<true>, dim3(wm_blocks(n)), dim3(256), 0, s, keys2, vals2, f_flag.in(d), f_hit.in(d), (int)n, f_pts.in(d), W.keys,
                            W.slots, W.sum, W.count, W.map_n, W.n_maps,
@@ -681,9 +702,27 @@ int mml_world_map_import(mml_ctx* ctx, int map, long n, const int* ijk, const fl
     if ((long)h_cnt[1] + n > W.capacity)
         return mml_refuse(ctx, MML_ERR_CAPACITY, "mml_world_map_import: %d voxels held + %ld imported exceed capacity_voxels %ld; nothing was imported",
                           h_cnt[1], n, W.capacity);
+    wm_touch(W);
     hipLaunchKernelGGL(k_wm_import_put, dim3(wm_blocks(m)), dim3(256), 0, s, f_keys.in(d), (int)m, f_sum.in(d), f_n.in(d), f_mom.in(d), W.keys, W.slots, W.sum,
                        W.count, W.map_n, W.n_maps, map, wm_mom(W));
     MML_HIP(hipGetLastError());
     MML_HIP(hipStreamSynchronize(s));  // (the caller's arrays and the key vector were the copies' sources)
+    return MML_OK;
+}
+
+// The surfel cache of a surfel map, valid for the table as it is: allocated on first use, rebuilt when a call has written the table
+// since it was filled.  Enqueue only; a failed allocation is reported before any launch.
+int mml_wm_cache_ready(mml_ctx* ctx) {
+    mml_ctx::WorldMap& W = ctx->world;
+    if (!W.cache) {
+        const hipError_t e = W.mem.alloc(&W.cache, (size_t)W.slots);
+        if (e != hipSuccess) return mml_mem_fail(ctx, "mml_world_map_score: the surfel cache (16 bytes per table position), hipMalloc", e);
+        W.cache_version = 0;
+    }
+    if (W.cache_version == W.version) return MML_OK;
+    MmlStageScope t(ctx, "wm_surfel_cache");
+    hipLaunchKernelGGL(k_wm_surfel_cache, dim3(wm_blocks((size_t)W.slots)), dim3(256), 0, MML_STREAM(ctx), W.keys, W.slots, wm_mom(W), W.count, W.cache);
+    MML_HIP(hipGetLastError());
+    W.cache_version = W.version;
     return MML_OK;
 }

@@ -63,11 +63,22 @@ struct MmlWmaFactor {
     double proj[3];
     double error;
 };
+// the signed distance of w to the plane through the centroid c with the normal n: differences and products in double
+MML_WM_HD double mml_wma_plane_dist(float wx, float wy, float wz, float cx, float cy, float cz, float nx, float ny, float nz) {
+    return ((double)nx * ((double)wx - (double)cx) + (double)ny * ((double)wy - (double)cy)) + (double)nz * ((double)wz - (double)cz);
+}
+// The two gates on the winner, and the distance they leave: false when the planarity or |d| rejects it.  mml_wma_factor and the
+// pose score (world_map_score.h) both decide through this function.
+MML_WM_HD bool mml_wma_gates(float wx, float wy, float wz, float cx, float cy, float cz, float nx, float ny, float nz, float planarity,
+                             float min_planarity, double max_plane_dist, double& d) {
+    if (planarity < min_planarity) return false;
+    d = mml_wma_plane_dist(wx, wy, wz, cx, cy, cz, nx, ny, nz);
+    return !(fabs(d) > max_plane_dist);
+}
 MML_WM_HD int mml_wma_factor(const double* T, float fx, float fy, float fz, float wx, float wy, float wz, float cx, float cy, float cz,
                              float nx, float ny, float nz, float planarity, float min_planarity, double max_plane_dist, MmlWmaFactor& out) {
-    if (planarity < min_planarity) return 0;
-    const double d = ((double)nx * ((double)wx - (double)cx) + (double)ny * ((double)wy - (double)cy)) + (double)nz * ((double)wz - (double)cz);
-    if (fabs(d) > max_plane_dist) return 0;
+    double d = 0.0;
+    if (!mml_wma_gates(wx, wy, wz, cx, cy, cz, nx, ny, nz, planarity, min_planarity, max_plane_dist, d)) return 0;
     out.ori[0] = fx;
     out.ori[1] = fy;
     out.ori[2] = fz;

@@ -5,8 +5,8 @@
 //
 // k_wm_associate  grid (max_features / 256, count), one lane per feature.  What is the same for a whole workgroup -- the slot's
 //                 map, pose and the two stack sizes -- is indexed by blockIdx.y alone and comes through scalar loads, before the
-//                 first store.  The up to 27 probes run in three groups of nine (one k layer each): the nine hash positions are
-//                 computed, their first key loads are issued together, and only a probe that met another voxel's key walks on.
+//                 first store.  The up to 27 probes are wm_probe27's (world_map_dev.h, shared with k_wm_score): three groups of nine
+//                 first loads, and only a probe that met another voxel's key walks on.
 //                 The winner's count and moments are loaded once, one eig3_sym per lane.  The table is only read: no atomics, no
 //                 LDS.  A lane below the slot's CORNER count clears the line record of its index (src = -1), so the slot is left
 //                 with plane factors only, as mml_associate leaves a slot whose corner features found no model.
@@ -64,46 +64,7 @@ __global__ __launch_bounds__(256) void k_wm_associate(int first, int B, int MF, 
     const bool ok = mml_wma_voxel(wx, wy, wz, O.inv, vi, vj, vk);
     MmlWmaBest best;
     mml_wma_best_init(best);
-    if (ok) {
-        for (int dk = -1; dk <= 1; ++dk) {
-            if (!O.nb && dk != 0) continue;
-            unsigned long long key[9], k0[9];
-            unsigned h[9];
-            bool use[9];
-#pragma unroll
-            for (int c = 0; c < 9; ++c) {
-                const int di = c % 3 - 1, dj = c / 3 - 1;
-                key[c] = 0;
-                use[c] = (O.nb || (di == 0 && dj == 0)) && mml_wma_candidate(map, vi + di, vj + dj, vk + dk, key[c]);
-                h[c] = use[c] ? (unsigned)mml_wm_hash(key[c], W.slots) : 0u;
-            }
-#pragma unroll
-            for (int c = 0; c < 9; ++c) k0[c] = use[c] ? W.keys[h[c]] : MML_WM_EMPTY;  // the nine first loads, none waits for another
-#pragma unroll
-            for (int c = 0; c < 9; ++c) {
-                if (!use[c]) continue;
-                long long at = -1;
-                unsigned long long k = k0[c], hh = h[c];
-                for (unsigned long long step = 1;; ++step) {  // (wm_find, from its second position on)
-                    if (k == key[c]) {
-                        at = (long long)hh;
-                        break;
-                    }
-                    if (k == MML_WM_EMPTY || step >= W.slots) break;
-                    hh = (hh + 1) & (W.slots - 1);
-                    k = W.keys[hh];
-                }
-                if (at < 0) continue;
-                const int n = W.count[at];
-                if (n < O.min_points) continue;
-                const float4 s = W.sum[at];
-                const MmlWmAcc a = {s.x, s.y, s.z, s.w, n};
-                float cen[4];
-                mml_wm_centroid(a, cen);
-                mml_wma_offer(best, mml_wma_r2(wx, wy, wz, cen[0], cen[1], cen[2]), key[c], at, n, cen[0], cen[1], cen[2]);
-            }
-        }
-    }
+    if (ok) wm_probe27(W.keys, W.slots, W.sum, W.count, map, O.nb, O.min_points, vi, vj, vk, wx, wy, wz, best);
     MmlPlaneFactor out;
     memset(&out, 0, sizeof(out));
     out.src = -1;
@@ -147,6 +108,15 @@ void mml_wm_localize_opts_default(mml_wm_localize_opts* o, float leaf) {
     o->inner_iters = 10;
 }
 
+// the refusals of a set of association options, host only
+int mml_wm_assoc_opts_ok(mml_ctx* ctx, const char* who, const mml_wm_assoc_opts* o) {
+    if (o->neighbourhood != 0 && o->neighbourhood != 1) return mml_refuse(ctx, MML_ERR_INVALID, "%s: neighbourhood %d is neither 0 nor 1", who, o->neighbourhood);
+    if (o->min_points < 3) return mml_refuse(ctx, MML_ERR_INVALID, "%s: min_points %d < 3 (a surfel needs three points)", who, o->min_points);
+    if (!isfinite(o->min_planarity)) return mml_refuse(ctx, MML_ERR_INVALID, "%s: min_planarity is not finite", who);
+    if (!isfinite(o->max_plane_dist) || o->max_plane_dist < 0.0) return mml_refuse(ctx, MML_ERR_INVALID, "%s: max_plane_dist must be finite and >= 0", who);
+    return MML_OK;
+}
+
 // The refusals of a call that associates slots [first, first + count) against the world map, all before any device work but the
 // read-back of the stack sizes, and the call's map numbers sent down (mml_ctx::WorldMap::assoc_maps, one int per slot of the
 // context).  need_all: every slot must name a map (mml_world_map_localize).
@@ -159,10 +129,8 @@ int mml_wm_assoc_ready(mml_ctx* ctx, const char* who, int first, int count, cons
     for (int i = 0; i < count; ++i)
         if (map_of_slot[i] < (need_all ? 0 : -1) || map_of_slot[i] >= W.n_maps)
             return mml_refuse(ctx, MML_ERR_INVALID, "%s: map %d of slot %d outside [%d, %d)", who, map_of_slot[i], first + i, need_all ? 0 : -1, W.n_maps);
-    if (o->neighbourhood != 0 && o->neighbourhood != 1) return mml_refuse(ctx, MML_ERR_INVALID, "%s: neighbourhood %d is neither 0 nor 1", who, o->neighbourhood);
-    if (o->min_points < 3) return mml_refuse(ctx, MML_ERR_INVALID, "%s: min_points %d < 3 (a surfel needs three points)", who, o->min_points);
-    if (!isfinite(o->min_planarity)) return mml_refuse(ctx, MML_ERR_INVALID, "%s: min_planarity is not finite", who);
-    if (!isfinite(o->max_plane_dist) || o->max_plane_dist < 0.0) return mml_refuse(ctx, MML_ERR_INVALID, "%s: max_plane_dist must be finite and >= 0", who);
+    int rc = mml_wm_assoc_opts_ok(ctx, who, o);
+    if (rc != MML_OK) return rc;
     hipStream_t s = MML_STREAM(ctx);
     int* h = reinterpret_cast<int*>(mml_stage_alloc(ctx, (size_t)ctx->B + 1));  // pinned: the context's 2 B stack sizes
     MML_HIP(hipMemcpyAsync(h, ctx->ft_n, sizeof(int) * 2 * (size_t)ctx->B, hipMemcpyDeviceToHost, s));
@@ -174,7 +142,7 @@ int mml_wm_assoc_ready(mml_ctx* ctx, const char* who, int first, int count, cons
             if (f < 0 || f > ctx->MF) return mml_refuse(ctx, MML_ERR_STATE, "%s: slot %d holds no down-sampled feature stack", who, first + i);
         }
     }
-    int rc = W.assoc_maps.reserve(ctx, (size_t)ctx->B, s);
+    rc = W.assoc_maps.reserve(ctx, (size_t)ctx->B, s);
     if (rc != MML_OK) return rc;
     int* hm = reinterpret_cast<int*>(mml_stage_alloc(ctx, ((size_t)count + 1) / 2));
     memcpy(hm, map_of_slot, sizeof(int) * (size_t)count);

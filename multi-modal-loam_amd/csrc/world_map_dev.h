@@ -1,10 +1,11 @@
-// world_map_dev.h -- what the world map's kernels in more than one translation unit share (world_map.hip, world_map_assoc.hip):
-// the per-wave counter add, the read-only probe, the moment arrays and the surfel record of one voxel.  Device only; include
-// inside an anonymous namespace of the translation unit, behind eig3_dev.h.
+// world_map_dev.h -- what the world map's kernels in more than one translation unit share (world_map.hip, world_map_assoc.hip,
+// world_map_score.hip): the per-wave counter add, the read-only probe, the association's candidate walk, the moment arrays, the
+// surfel record of one voxel and the entry of the surfel cache made from it.  Device only; include inside an anonymous namespace
+// of the translation unit, behind eig3_dev.h and world_map_assoc.h.
 #ifndef MML_WORLD_MAP_DEV_H
 #define MML_WORLD_MAP_DEV_H
 
-#include "world_map_key.h"
+#include "world_map_assoc.h"
 
 // one add per wave of the lanes for which `pred` holds
 __device__ __forceinline__ void wm_count(int* counter, bool pred) {
@@ -23,6 +24,52 @@ __device__ __forceinline__ long long wm_find(const unsigned long long* __restric
         h = (h + 1) & (slots - 1);
     }
     return -1;
+}
+
+// The association's walk over the candidates of a world point w in voxel (vi, vj, vk) of map `map` (world_map_assoc.h: which
+// voxels, which of them wins), for k_wm_associate and k_wm_score alike: the up to 27 probes run in three groups of nine (one k
+// layer each) -- the nine hash positions are computed, their first key loads are issued together, and only a probe that met
+// another voxel's key walks on (wm_find, from its second position on).  The table is only read.
+__device__ __forceinline__ void wm_probe27(const unsigned long long* keys, unsigned long long slots, const float4* sum, const int* count, int map,
+                                           int nb, int min_points, int vi, int vj, int vk, float wx, float wy, float wz, MmlWmaBest& best) {
+    for (int dk = -1; dk <= 1; ++dk) {
+        if (!nb && dk != 0) continue;
+        unsigned long long key[9], k0[9];
+        unsigned h[9];
+        bool use[9];
+#pragma unroll
+        for (int c = 0; c < 9; ++c) {
+            const int di = c % 3 - 1, dj = c / 3 - 1;
+            key[c] = 0;
+            use[c] = (nb || (di == 0 && dj == 0)) && mml_wma_candidate(map, vi + di, vj + dj, vk + dk, key[c]);
+            h[c] = use[c] ? (unsigned)mml_wm_hash(key[c], slots) : 0u;
+        }
+#pragma unroll
+        for (int c = 0; c < 9; ++c) k0[c] = use[c] ? keys[h[c]] : MML_WM_EMPTY;  // the nine first loads, none waits for another
+#pragma unroll
+        for (int c = 0; c < 9; ++c) {
+            if (!use[c]) continue;
+            long long at = -1;
+            unsigned long long k = k0[c], hh = h[c];
+            for (unsigned long long step = 1;; ++step) {  // (wm_find, from its second position on)
+                if (k == key[c]) {
+                    at = (long long)hh;
+                    break;
+                }
+                if (k == MML_WM_EMPTY || step >= slots) break;
+                hh = (hh + 1) & (slots - 1);
+                k = keys[hh];
+            }
+            if (at < 0) continue;
+            const int n = count[at];
+            if (n < min_points) continue;
+            const float4 s = sum[at];
+            const MmlWmAcc a = {s.x, s.y, s.z, s.w, n};
+            float cen[4];
+            mml_wm_centroid(a, cen);
+            mml_wma_offer(best, mml_wma_r2(wx, wy, wz, cen[0], cen[1], cen[2]), key[c], at, n, cen[0], cen[1], cen[2]);
+        }
+    }
 }
 
 // the three moment arrays of a surfel map (or of a reset's scratch copy); null in a plain map
@@ -53,6 +100,15 @@ __device__ __forceinline__ void wm_surfel(const MmlWmMoments& m, int np, float4&
     }
     o0 = make_float4((float)v0[0], (float)v0[1], (float)v0[2], (float)ev[0]);
     o1 = make_float4((float)ev[1], (float)ev[2], (float)planarity, (float)linearity);
+}
+
+// The surfel cache (mml_ctx::WorldMap::cache, read by k_wm_score): one float4 per table position, (nx, ny, nz, planarity) =
+// o0.xyz, o1.z of wm_surfel for the position's moments and count; zeros below three points.
+__device__ __forceinline__ float4 wm_cache_entry(const MmlWmMoments& m, int np) {
+    if (np < 3) return make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 o0, o1;
+    wm_surfel(m, np, o0, o1);
+    return make_float4(o0.x, o0.y, o0.z, o1.z);
 }
 
 #endif

@@ -202,6 +202,18 @@ class WorldMap {
                   mml_estimate_info* info = nullptr) {
         check(ctx_.get(), mml_world_map_localize(ctx_.get(), first_slot, count, map_of_slot, exTlb, P, Q, &opts, info), "mml_world_map_localize");
     }
+    // n_hyp pose hypotheses per slot (T_wl: count x n_hyp x 16) scored against the maps in one launch: count x n_hyp results,
+    // integers, zeros for a slot with map -1; the map and the slots are only read
+    std::vector<mml_wm_score> score(int first_slot, int count, const int* map_of_slot, int n_hyp, const double* T_wl, const mml_wm_score_opts& opts) {
+        std::vector<mml_wm_score> out((size_t)(count > 0 ? count : 0) * (size_t)(n_hyp > 0 ? n_hyp : 0));
+        check(ctx_.get(), mml_world_map_score(ctx_.get(), first_slot, count, map_of_slot, n_hyp, T_wl, &opts, out.data()), "mml_world_map_score");
+        return out;
+    }
+    // the coarse-to-fine search around the seed poses P, Q, ending in localize: P, Q in and out
+    void relocalize(int first_slot, int count, const int* map_of_slot, const double* exTlb, double* P, double* Q, const mml_wm_reloc_opts& opts,
+                    mml_wm_reloc_info* info = nullptr) {
+        check(ctx_.get(), mml_world_map_relocalize(ctx_.get(), first_slot, count, map_of_slot, exTlb, P, Q, &opts, info), "mml_world_map_relocalize");
+    }
 
    private:
     std::vector<float> rows(int map, int width, int (*call)(mml_ctx*, int, float*, long, long*), const char* who) {

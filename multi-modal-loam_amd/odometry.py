@@ -413,6 +413,16 @@ class MapLocalizer:
         maps = [self.maps] * len(slots) if np.isscalar(self.maps) else [self.maps[s] for s in slots]
         return self.ctx.world_map_localize(slots[0], maps, self.exTlb, P, Q, self.opts)
 
+    def relocalize(self, slots, P, Q, opts=None):
+        """The same run of slots without a good start pose: P, Q are seeds, the coarse-to-fine search of
+        Context.world_map_relocalize (opts: a WmRelocOpts, None: the defaults for the map's leaf) finds the start and the loop
+        above ends it.  Returns P, Q, [WmRelocInfo]."""
+        slots = [int(s) for s in slots]
+        if not slots or slots != list(range(slots[0], slots[0] + len(slots))):
+            raise ValueError("relocalize takes a run of consecutive slots")
+        maps = [self.maps] * len(slots) if np.isscalar(self.maps) else [self.maps[s] for s in slots]
+        return self.ctx.world_map_relocalize(slots[0], maps, self.exTlb, P, Q, opts)
+
 
 class _FullWindowBase:
     """What the two full-window estimators share: the extrinsic, the constants of Estimator::Estimate and the
