@@ -74,6 +74,148 @@ TOFS_GATE_OK, TOFS_GATE_EMPTY, TOFS_GATE_TOO_FEW_MESSAGES = 0, 1, 2
 VELO_FOV_INFO_DTYPE = np.dtype([("start_ori", "<f4"), ("end_ori", "<f4"), ("half_index", "<i4"), ("n_kept", "<i4")])
 
 
+def _signatures():
+    """SIGNATURES: name -> (restype, [argtypes]) of every entry point, in the order and under the section titles of
+    include/mmloam_hip.h.  One rule: any pointer parameter (handles included) is c_void_p, a scalar is its own ctypes type; a
+    returned int is c_int, void None, const char* c_char_p, any other pointer c_void_p.  tests/test_abi_signatures.py holds the
+    table against the header, declaration for declaration."""
+    P, I, U, L, LL, U64, SZ, F, D, STR = (C.c_void_p, C.c_int, C.c_uint, C.c_long, C.c_longlong, C.c_uint64, C.c_size_t, C.c_float,
+                                          C.c_double, C.c_char_p)
+    return {
+        # ---- (the header's head: configuration, contexts)
+        "mml_config_default": (None, [P, I]), "mml_abi_version": (I, []), "mml_create": (I, [P, I, P]), "mml_destroy": (None, [P]),
+        "mml_last_error": (STR, [P]), "mml_config_get": (I, [P, P]), "mml_synchronize": (I, [P]),
+        # ---- input
+        "mml_scan_upload": (I, [P, I, P, I, P, I]), "mml_scan_upload_batch": (I, [P, I, I, P, P, P, P]),
+        "mml_scan_upload_pointcloud2": (I, [P, I, P, I, I, I, I, I, I, P, I]), "mml_scan_upload_wire": (I, [P, I, P, I, I, I, I, I, I, P, I]),
+        "mml_scan_download_pointxyzinormal": (I, [P, I, P, I, P]), "mml_cloud_upload": (I, [P, I, P, I, I]),
+        "mml_cloud_download_registered_batch": (I, [P, I, I, P, P, L, P]), "mml_cloud_download_registered": (I, [P, I, P, P, I, P]),
+        "mml_world_map_create": (I, [P, I, F, L]), "mml_world_map_destroy": (I, [P]), "mml_world_map_reset": (I, [P, I]),
+        "mml_world_map_add": (I, [P, I, I, P, P, U, P]), "mml_world_map_size": (I, [P, I, P]), "mml_world_map_download": (I, [P, I, P, P, L, P]),
+        "mml_world_map_create_opts": (I, [P, I, F, L, U]), "mml_world_map_download_moments": (I, [P, I, P, L, P]),
+        "mml_world_map_download_surfels": (I, [P, I, P, L, P]), "mml_feature_clouds_download_batch": (I, [P, I, I, P, L, P]),
+        "mml_feature_clouds_download": (I, [P, I, P, I, P]),
+        # ---- SURVEY section 8(f) rank 4 (part): the aligner's time-offset search
+        "mml_time_offset_search": (I, [P, P, I, P, P, I, I, I, P, P, I, P, P, P]),
+        "mml_time_offset_search_batch": (I, [P, I, P, P, P, P, P, I, I, P, P, P, P, P, P]), "mml_time_offset_plan": (I, [I, P, P, I, I, I, P, P]),
+        # ---- the aligner's Velodyne field-of-view selection: the input of the time-offset search
+        "mml_velo_fov_select_batch": (I, [P, I, P, P, P, I, I, I, I, P, P, L, P, P]),
+        "mml_velo_fov_select": (I, [P, P, I, I, I, I, I, P, P, I, P, P]),
+        # ---- the aligner node's frame assembly: a Livox point stream cut into scan slots
+        "mml_livox_stream_create": (I, [P, L, P]), "mml_livox_stream_destroy": (None, [P]), "mml_livox_stream_reset": (I, [P]),
+        "mml_livox_stream_push": (I, [P, U64, P, I]), "mml_livox_stream_push_wire": (I, [P, U64, P, I]), "mml_livox_stream_state_get": (I, [P, P]),
+        "mml_union_assemble": (I, [P, P, I, I, P, P, P, P, P]), "mml_union_plan": (I, [P, L, L, U64, I, P, I, P]),
+        "mml_union_assemble_offset": (I, [P, P, I, I, P, I, P, P, P, P]), "mml_union_plan_offset": (I, [P, L, L, U64, I, P, I, P]),
+        # ---- the aligner's time-offset estimation on the resident stream
+        "mml_time_offset_estimate_stream": (I, [P, P, L, L, I, P, P, P, I, I, I, I, P, P, I, I, D, P, P, P, P]),
+        "mml_time_offset_gate": (I, [I, P, U64, I, P, P]), "mml_scan_raw_download": (I, [P, I, P, I, P, I, P, P]),
+        # ---- SURVEY section 8(f) rank 4 (the other part): the per-frame GICP extrinsic refresh
+        "mml_gicp_align": (I, [P, P, I, P, I, P, P, P]), "mml_gicp_refresh": (I, [P, I, P, I, P, P]),
+        "mml_gicp_align_batch": (I, [P, I, P, P, P, P, P, P, P]), "mml_gicp_refresh_batch": (I, [P, I, I, P, I, I, P, P]),
+        "mml_gicp_align_opts": (I, [P, P, I, P, I, P, P, P, P]),
+        # ---- the aligner node's start-up calibration
+        "mml_cloud_crop_voxel": (I, [P, P, I, F, F, P, I, P, P]), "mml_aligner_calibrate": (I, [P, P, I, P, I, P, P, P, P]),
+        # ---- a1..a8: feature extraction
+        "mml_extract": (I, [P, I, I, P]), "mml_scan_info_get": (I, [P, I, P]), "mml_scan_download": (I, [P, I, P, P, P, P, I]),
+        "mml_detect_line": (I, [P, P, I, P, P, P, P, P]),
+        # ---- a9: RemoveLidarDistortion
+        "mml_undistort": (I, [P, I, I, P, P]),
+        # ---- a10: label split + pcl::VoxelGrid down-sample
+        "mml_downsample": (I, [P, I, I]), "mml_features_download": (I, [P, I, I, P, I, P]), "mml_features_upload": (I, [P, I, I, P, I]),
+        # ---- a13 map side: laserCloud{Corner,Surf}FromLocal
+        "mml_map_set_local": (I, [P, I, P, I]),
+        # ---- SURVEY section 8(f) rank 2: Estimator::MapIncrementLocal, on the device
+        "mml_map_increment_local": (I, [P, I, P, P, P]), "mml_map_local_reset": (I, [P]), "mml_map_local_download": (I, [P, I, P, I, P]),
+        # ---- SURVEY section 8(f) rank 2, global half: the MAP_MANAGER cube stores on the device
+        "mml_map_global_append": (I, [P, I, P]), "mml_map_global_increment": (I, [P, P, P, P]),
+        "mml_map_global_download": (I, [P, I, P, P, I, P, P]), "mml_map_global_reset": (I, [P]),
+        # ---- a12: laserCloud{Corner,Surf}FromMap cube store
+        "mml_map_set_global": (I, [P, I, P, P, I, P]),
+        # ---- map banks: N further local maps per context, every scan slot matched against its own
+        "mml_map_banks_create": (I, [P, I]), "mml_map_banks_destroy": (I, [P]), "mml_map_bank_set_local": (I, [P, I, I, P, I]),
+        "mml_map_bank_reset": (I, [P, I]), "mml_map_bank_download": (I, [P, I, I, P, I, P]), "mml_slot_bind_bank": (I, [P, I, I, P]),
+        "mml_slot_bank_get": (I, [P, I, I, P]), "mml_map_bank_increment": (I, [P, I, P, P, P, P, P]),
+        "mml_map_bank_increment_segmented": (I, [P, I, P, P, P, P, P]), "mml_debug_bank_increment_budget": (I, [P, L]),
+        "mml_map_bank_set_global": (I, [P, I, I, P, P, I, P]), "mml_map_bank_global_append": (I, [P, I, P, P, P]),
+        "mml_map_bank_global_increment": (I, [P, I, P, P, P, P]), "mml_map_bank_global_increment_segmented": (I, [P, I, P, P, P, P]),
+        "mml_map_bank_global_append_segmented": (I, [P, I, P, P, P]), "mml_debug_bank_global_increment_budget": (I, [P, L]),
+        "mml_map_bank_global_download": (I, [P, I, I, P, P, I, P, P]), "mml_map_bank_global_reset": (I, [P, I]),
+        "mml_knn5": (I, [P, I, P, I, F, P, P]),
+        # ---- a11..a16: association + model fit
+        "mml_associate": (I, [P, I, I, P, D, P]), "mml_factors_download": (I, [P, I, I, P, P, I, P]), "mml_factors_upload": (I, [P, I, I, P, I]),
+        # ---- a17..a20: residual + Jacobian + normal equations
+        "mml_linearize": (I, [P, I, P, P, D, D, P, P, P]), "mml_linearize_window": (I, [P, I, I, I, P, P, D, D, P]),
+        "mml_solve": (I, [P, I, I, I, P, P, P, P, P]),
+        # ---- a21: Estimator::Estimate, 1-frame mode
+        "mml_estimate": (I, [P, I, I, P, P, P, I, I, P]),
+        # ---- localisation in a surfel world map
+        "mml_wm_assoc_opts_default": (None, [P, F]), "mml_wm_localize_opts_default": (None, [P, F]),
+        "mml_world_map_export": (I, [P, I, P, P, P, P, L, P]), "mml_world_map_import": (I, [P, I, L, P, P, P, P]),
+        "mml_world_map_associate": (I, [P, I, I, P, P, P, P]), "mml_world_map_localize": (I, [P, I, I, P, P, P, P, P, P]),
+        # ---- relocalisation in a surfel world map: pose hypotheses scored on the device, a coarse-to-fine search
+        "mml_wm_score_opts_default": (None, [P, F]), "mml_world_map_score": (I, [P, I, I, P, I, P, P, P]),
+        "mml_wm_reloc_opts_default": (None, [P, F]), "mml_wm_pose_grid": (I, [P, D, D, D, D, D, D, P, L, P]),
+        "mml_wm_body_pose": (I, [P, P, P, P]), "mml_wm_lidar_pose": (I, [P, P, P, P]), "mml_world_map_relocalize": (I, [P, I, I, P, P, P, P, P, P]),
+        # ---- the benchmarked step
+        "mml_step": (I, [P, I, I, P, P, P, D, I, P]),
+        # ---- multi-GPU window solve (one frame per GPU)
+        "mml_linearize_record": (I, [P, I, P, P, D, D, P]), "mml_window_solver_create": (P, [I, P]), "mml_window_solver_destroy": (None, [P]),
+        "mml_window_solver_step": (I, [P, P, P]), "mml_window_solver_summary": (I, [P, P]),
+        # ---- multi-GPU: RCCL inside the C-ABI
+        "mml_comm_unique_id": (I, [P]), "mml_comm_init": (I, [P, I, I, P]), "mml_comm_destroy": (I, [P]), "mml_comm_info": (I, [P, P, P]),
+        "mml_rccl_version": (I, [P]), "mml_window_solve_allgather": (I, [P, I, I, P, P, P, P, P, P]),
+        "mml_comm_broadcast_features": (I, [P, I, I]), "mml_comm_broadcast_local_map": (I, [P, I]),
+        # ---- loopback group: the N-rank path on ONE device
+        "mml_comm_init_loopback": (I, [P, I]), "mml_window_solve_allgather_loopback": (I, [P, I, P, I, P, P, P, P, P]),
+        "mml_comm_broadcast_features_loopback": (I, [P, I, I, I]), "mml_comm_broadcast_local_map_loopback": (I, [P, I, I]),
+        # ---- verification hook: digests of the per-slot state
+        "mml_slot_digest": (I, [P, I, I, P]),
+        # ---- SURVEY section 8(f) rank 1: IMU factor, marginalization prior, full-window solve (host side)
+        "mml_imu_preintegrate": (I, [P, I, P, P, P]), "mml_imu_factor": (I, [P, P, P, P, P, P, P, P]), "mml_fullwindow_create": (P, [I, P]),
+        "mml_fullwindow_destroy": (None, [P]), "mml_fullwindow_set_imu": (I, [P, I, P, P]), "mml_fullwindow_set_prior": (I, [P, P]),
+        "mml_fullwindow_step": (I, [P, P, P]), "mml_fullwindow_summary": (I, [P, P]),
+        "mml_fullwindow_normal_equations": (I, [P, P, P, P, P, P]), "mml_fullwindow_marginalize": (I, [P, P, P, P]),
+        # ---- the LIO initialisation that opens full-window mode, and the batched calls
+        "mml_imu_gyro_integrate": (I, [P, I, P]), "mml_imu_init_factor": (I, [P, P, P, P, P, P, P, P, P, P, P]),
+        "mml_lio_initialize": (I, [I, P, P, P, P, P, P, P, P, P, P, P, P]), "mml_fullwindow_solve": (I, [P, P, I, P, P, P, P]),
+        "mml_fullwindow_solve_batch": (I, [P, I, P, P, P, P, P, P, P]), "mml_fullwindow_marginalize_batch": (I, [P, I, P, P, P, P, P]),
+        "mml_imu_preintegrate_batch": (I, [P, I, P, P, P, P, P]), "mml_lio_initialize_batch": (I, [P, I, P, P, P, P, P, P, P, P, P, P, P, P, P]),
+        # ---- the pose node's IMU queue: a device-resident message store cut and pre-integrated per frame interval
+        "mml_imu_stream_create": (I, [P, L, P]), "mml_imu_stream_destroy": (None, [P]), "mml_imu_stream_reset": (I, [P]),
+        "mml_imu_stream_push": (I, [P, P, I]), "mml_imu_stream_drop_before": (I, [P, D, L]), "mml_imu_stream_state_get": (I, [P, P]),
+        "mml_imu_fetch_batch": (I, [P, P, I, P, P, P, P, P, P, P, L, P, P]), "mml_imu_fetch_host": (I, [P, L, I, P, P, P, P, P, P, P, L, P, P]),
+        "mml_imu_predict_batch": (I, [P, I, P, P, P, P, P, P, P, P, P]),
+        # ---- the pose node's way in: `count` union_cloud messages into scan slots in one call
+        "mml_pose_ingest_opts_default": (None, [P]), "mml_pose_ingest_plan": (I, [I, P, P, P, P]),
+        "mml_pose_ingest_batch": (I, [P, I, I, P, P, P, P, P]),
+        # ---- the feature node's way in: `count` union_cloud messages in wire form into scan slots in one call
+        "mml_scan_upload_wire_batch": (I, [P, I, I, P, P, P, I, I, I, I, I, P, P, P, I]),
+        "mml_scan_upload_wire_plan": (I, [I, P, P, I, I, I, I, I, P, P, I, I, I, P, P]),
+        "mml_wire_decode_host": (I, [I, P, P, P, I, I, I, I, I, P, P, P, I, P, P]),
+        # ---- (the header's tail: measurement and test hooks)
+        "mml_set_lanes": (I, [P, I]), "mml_profile_enable": (I, [P, I]), "mml_profile_reset": (I, [P]), "mml_profile_get": (I, [P, P]),
+        "mml_extract_queue_counts": (I, [P, I, P, P]), "mml_libm_f32": (I, [P, P, P, L, P, P]), "mml_model_fit5": (I, [P, I, P, L, P]),
+        "mml_marginalize_dense": (I, [P, L, P, P, P, P]), "mml_debug_tr_replay": (I, [P, I, I, I, P, P, P, P, P, P]),
+        "mml_debug_fw_replay": (I, [P, I, I, P, P, P, P, LL, P, P, P]), "mml_debug_gicp": (I, [P, I, P]),
+        "mml_associate_far_count": (I, [P, P]), "mml_device_info": (I, [P, P, I, P, P]), "mml_copy_bandwidth": (I, [P, SZ, I, P]),
+        "mml_issue_rate": (I, [P, I, I, P]),
+        # ---- not in the public header (NOT_IN_HEADER): exported by csrc/capi.hip for tools/phases.py
+        "mml_debug_phase_clocks": (I, [P, P, I, I]),
+    }
+
+
+SIGNATURES = _signatures()
+NOT_IN_HEADER = ("mml_debug_phase_clocks",)
+# the world map's entry points by the change that brought them (tests/test_world_map_*.py): views onto SIGNATURES
+WORLD_MAP_ARGTYPES, WORLD_MAP_SURFEL_ARGTYPES, WORLD_MAP_LOCALIZE_ARGTYPES, WORLD_MAP_SCORE_ARGTYPES = (
+    {n: SIGNATURES[n][1] for n in names} for names in (
+        ("mml_world_map_create", "mml_world_map_destroy", "mml_world_map_reset", "mml_world_map_add", "mml_world_map_size",
+         "mml_world_map_download"),
+        ("mml_world_map_create_opts", "mml_world_map_download_moments", "mml_world_map_download_surfels"),
+        ("mml_world_map_export", "mml_world_map_import", "mml_world_map_associate", "mml_world_map_localize"),
+        ("mml_world_map_score", "mml_wm_pose_grid", "mml_wm_body_pose", "mml_wm_lidar_pose", "mml_world_map_relocalize")))
+
+
 class MmlError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("mmloam_hip error %d: %s" % (code, msg))
@@ -129,7 +271,7 @@ class LoopbackGroup:
         self.ctxs = list(contexts)
         self.n = len(self.ctxs)
         self._arr = (C.c_void_p * self.n)(*[c._h for c in self.ctxs])
-        self._ck(lib().mml_comm_init_loopback(self._arr, C.c_int(self.n)), "mml_comm_init_loopback")
+        self._ck(lib().mml_comm_init_loopback(self._arr, self.n), "mml_comm_init_loopback")
 
     def _ck(self, rc, what):
         if rc != 0:
@@ -144,17 +286,15 @@ class LoopbackGroup:
         fs = np.ascontiguousarray(first_slots, dtype=np.int32)
         opts = SolveOpts(max_iters, 1 if fixed else 0, huber, w_tan)
         summ = (SolveSummary * self.n)()
-        self._ck(lib().mml_window_solve_allgather_loopback(self._arr, C.c_int(self.n), _p(fs), C.c_int(n_local), _p(_f64(T_bl).reshape(16)),
-                                                           C.byref(opts), _p(x), _p(out), summ), "mml_window_solve_allgather_loopback")
+        self._ck(lib().mml_window_solve_allgather_loopback(self._arr, self.n, _p(fs), n_local, _p(_f64(T_bl).reshape(16)), C.byref(opts), _p(x),
+                                                           _p(out), summ), "mml_window_solve_allgather_loopback")
         return out, list(summ)
 
     def broadcast_features(self, slot, root):
-        self._ck(lib().mml_comm_broadcast_features_loopback(self._arr, C.c_int(self.n), C.c_int(slot), C.c_int(root)),
-                 "mml_comm_broadcast_features_loopback")
+        self._ck(lib().mml_comm_broadcast_features_loopback(self._arr, self.n, slot, root), "mml_comm_broadcast_features_loopback")
 
     def broadcast_local_map(self, root):
-        self._ck(lib().mml_comm_broadcast_local_map_loopback(self._arr, C.c_int(self.n), C.c_int(root)),
-                 "mml_comm_broadcast_local_map_loopback")
+        self._ck(lib().mml_comm_broadcast_local_map_loopback(self._arr, self.n, root), "mml_comm_broadcast_local_map_loopback")
 
 
 def comm_unique_id():
@@ -206,25 +346,10 @@ class WorldMapInfo(C.Structure):
                                         "n_voxels_total")]
 
 
-# the world map's seven entry points as include/mmloam_hip.h declares them, argument for argument
-WORLD_MAP_ARGTYPES = {
-    "mml_world_map_create": [C.c_void_p, C.c_int, C.c_float, C.c_long],
-    "mml_world_map_destroy": [C.c_void_p],
-    "mml_world_map_reset": [C.c_void_p, C.c_int],
-    "mml_world_map_add": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p],
-    "mml_world_map_size": [C.c_void_p, C.c_int, C.c_void_p],
-    "mml_world_map_download": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p],
-}
-# ... and the three of a surfel map (include/mmloam_hip.h, "Surfel maps")
-MML_WM_SURFELS = 1
-WORLD_MAP_SURFEL_ARGTYPES = {
-    "mml_world_map_create_opts": [C.c_void_p, C.c_int, C.c_float, C.c_long, C.c_uint],
-    "mml_world_map_download_moments": [C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_void_p],
-    "mml_world_map_download_surfels": [C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_void_p],
-}
+MML_WM_SURFELS = 1   # the flag of mml_world_map_create_opts (include/mmloam_hip.h, "Surfel maps")
 
 
-# ... and localisation in a surfel map (include/mmloam_hip.h, "localisation in a surfel world map")
+# localisation in a surfel map (include/mmloam_hip.h, "localisation in a surfel world map")
 class WmAssocOpts(C.Structure):
     """mml_wm_assoc_opts"""
     _fields_ = [("neighbourhood", C.c_int), ("min_points", C.c_int), ("min_planarity", C.c_float), ("max_plane_dist", C.c_double)]
@@ -235,18 +360,10 @@ class WmLocalizeOpts(C.Structure):
     _fields_ = [("assoc", WmAssocOpts), ("max_plane_dist_by_outer", C.c_double * 3), ("max_outer", C.c_int), ("inner_iters", C.c_int)]
 
 
-WORLD_MAP_LOCALIZE_ARGTYPES = {
-    "mml_world_map_export": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p],
-    "mml_world_map_import": [C.c_void_p, C.c_int, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
-    "mml_world_map_associate": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
-    "mml_world_map_localize": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
-}
-
-
 def wm_assoc_opts(leaf, **over):
     """mml_wm_assoc_opts_default(leaf) with fields replaced"""
     o = WmAssocOpts()
-    lib().mml_wm_assoc_opts_default(C.byref(o), C.c_float(leaf))
+    lib().mml_wm_assoc_opts_default(C.byref(o), leaf)
     for k, v in over.items():
         setattr(o, k, v)
     return o
@@ -255,7 +372,7 @@ def wm_assoc_opts(leaf, **over):
 def wm_localize_opts(leaf, **over):
     """mml_wm_localize_opts_default(leaf) with fields replaced; max_plane_dist_by_outer: three values; assoc: a WmAssocOpts"""
     o = WmLocalizeOpts()
-    lib().mml_wm_localize_opts_default(C.byref(o), C.c_float(leaf))
+    lib().mml_wm_localize_opts_default(C.byref(o), leaf)
     for k, v in over.items():
         setattr(o, k, (C.c_double * 3)(*v) if k == "max_plane_dist_by_outer" else v)
     return o
@@ -288,19 +405,10 @@ class WmRelocInfo(C.Structure):
                 ("est", EstimateInfo)]
 
 
-WORLD_MAP_SCORE_ARGTYPES = {
-    "mml_world_map_score": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
-    "mml_wm_pose_grid": [C.c_void_p] + [C.c_double] * 6 + [C.c_void_p, C.c_long, C.c_void_p],
-    "mml_wm_body_pose": [C.c_void_p] * 4,
-    "mml_wm_lidar_pose": [C.c_void_p] * 4,
-    "mml_world_map_relocalize": [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6,
-}
-
-
 def wm_score_opts(leaf, **over):
     """mml_wm_score_opts_default(leaf) with fields replaced; the fields of `assoc` may be given directly (max_plane_dist=...)"""
     o = WmScoreOpts()
-    lib().mml_wm_score_opts_default(C.byref(o), C.c_float(leaf))
+    lib().mml_wm_score_opts_default(C.byref(o), leaf)
     for k, v in over.items():
         setattr(o.assoc if k in ("neighbourhood", "min_points", "min_planarity", "max_plane_dist") else o, k, v)
     return o
@@ -309,7 +417,7 @@ def wm_score_opts(leaf, **over):
 def wm_reloc_opts(leaf, **over):
     """mml_wm_reloc_opts_default(leaf) with fields replaced; score: a WmScoreOpts, localize: a WmLocalizeOpts"""
     o = WmRelocOpts()
-    lib().mml_wm_reloc_opts_default(C.byref(o), C.c_float(leaf))
+    lib().mml_wm_reloc_opts_default(C.byref(o), leaf)
     for k, v in over.items():
         setattr(o, k, v)
     return o
@@ -319,7 +427,7 @@ def wm_pose_grid(seed, half_xy, step_xy, half_z=0.0, step_z=1.0, half_yaw=0.0, s
     """mml_wm_pose_grid: the (H, 4, 4) hypotheses of the grid around the pose `seed`, index ((iyaw nz + iz) ny + iy) nx + ix"""
     seed = _f64(seed).reshape(16)
     n = C.c_long(0)
-    a = [C.c_double(float(v)) for v in (half_xy, step_xy, half_z, step_z, half_yaw, step_yaw)]
+    a = [float(v) for v in (half_xy, step_xy, half_z, step_z, half_yaw, step_yaw)]
     rc = lib().mml_wm_pose_grid(_p(seed), *a, None, 0, C.byref(n))
     if rc != MML_OK:
         raise MmlError(rc, "mml_wm_pose_grid: refused (a value not finite, a negative half, half_yaw > pi, a step <= 0, too many cells)")
@@ -411,6 +519,15 @@ def _share_torch_runtime():
     return done
 
 
+def _bind(L):
+    """SIGNATURES onto the entry points of the loaded library L.  A name L lacks is skipped: an A/B build of an older commit
+    through $MML_LIB_PATH has not got the newest ones, and still loads."""
+    for name, (restype, argtypes) in SIGNATURES.items():
+        f = getattr(L, name, None)
+        if f is not None:
+            f.restype, f.argtypes = restype, argtypes
+
+
 def lib():
     """Load libmmloam_hip.so; fails loudly when the HIP extension has not been built."""
     global _lib
@@ -420,145 +537,7 @@ def lib():
                                           "(or make -C multi-modal-loam_amd/csrc); there is no CPU fallback")
         _share_torch_runtime()
         L = C.CDLL(LIB_PATH)
-        L.mml_last_error.restype = C.c_char_p
-        L.mml_last_error.argtypes = [C.c_void_p]
-        L.mml_window_solver_create.restype = C.c_void_p
-        L.mml_window_solver_create.argtypes = [C.c_int, C.POINTER(SolveOpts)]
-        L.mml_window_solver_destroy.argtypes = [C.c_void_p]
-        L.mml_window_solver_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.mml_window_solver_summary.argtypes = [C.c_void_p, C.POINTER(SolveSummary)]
-        L.mml_destroy.argtypes = [C.c_void_p]
-        if hasattr(L, "mml_fullwindow_solve_batch"):     # (an A/B build of an older commit through $MML_LIB_PATH has none)
-            L.mml_fullwindow_solve_batch.restype = C.c_int
-            L.mml_fullwindow_solve_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
-        if hasattr(L, "mml_fullwindow_marginalize_batch"):
-            L.mml_fullwindow_marginalize_batch.restype = C.c_int
-            L.mml_fullwindow_marginalize_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
-            L.mml_marginalize_dense.restype = C.c_int
-            L.mml_marginalize_dense.argtypes = [C.c_void_p, C.c_long] + [C.c_void_p] * 4
-        if hasattr(L, "mml_debug_tr_replay"):
-            L.mml_debug_tr_replay.restype = C.c_int
-            L.mml_debug_tr_replay.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6
-        if hasattr(L, "mml_debug_fw_replay"):
-            L.mml_debug_fw_replay.restype = C.c_int
-            L.mml_debug_fw_replay.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_longlong] + [C.c_void_p] * 3
-        if hasattr(L, "mml_debug_phase_clocks"):
-            L.mml_debug_phase_clocks.restype = C.c_int
-            L.mml_debug_phase_clocks.argtypes = [C.c_char_p, C.POINTER(C.c_ulonglong), C.c_int, C.c_int]
-        if hasattr(L, "mml_imu_preintegrate_batch"):
-            L.mml_imu_preintegrate_batch.restype = C.c_int
-            L.mml_imu_preintegrate_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
-        if hasattr(L, "mml_lio_initialize_batch"):
-            L.mml_lio_initialize_batch.restype = C.c_int
-            L.mml_lio_initialize_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 13
-        if hasattr(L, "mml_gicp_align_batch"):
-            L.mml_gicp_align_batch.restype = C.c_int
-            L.mml_gicp_align_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
-            L.mml_gicp_refresh_batch.restype = C.c_int
-            L.mml_gicp_refresh_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        if hasattr(L, "mml_time_offset_search_batch"):
-            L.mml_time_offset_search_batch.restype = C.c_int
-            L.mml_time_offset_search_batch.argtypes = ([C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_int] + [C.c_void_p] * 6)
-            L.mml_time_offset_plan.restype = C.c_int
-            L.mml_time_offset_plan.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        if hasattr(L, "mml_cloud_download_registered_batch"):
-            L.mml_cloud_download_registered_batch.restype = C.c_int
-            L.mml_cloud_download_registered_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]
-            L.mml_cloud_download_registered.restype = C.c_int
-            L.mml_cloud_download_registered.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        if hasattr(L, "mml_feature_clouds_download_batch"):
-            L.mml_feature_clouds_download_batch.restype = C.c_int
-            L.mml_feature_clouds_download_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_void_p]
-            L.mml_feature_clouds_download.restype = C.c_int
-            L.mml_feature_clouds_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-        if hasattr(L, "mml_union_assemble"):
-            L.mml_livox_stream_create.restype = C.c_int
-            L.mml_livox_stream_create.argtypes = [C.c_void_p, C.c_long, C.c_void_p]
-            L.mml_livox_stream_destroy.restype = None
-            L.mml_livox_stream_destroy.argtypes = [C.c_void_p]
-            L.mml_livox_stream_reset.argtypes = [C.c_void_p]
-            L.mml_livox_stream_push.restype = C.c_int
-            L.mml_livox_stream_push.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int]
-            L.mml_livox_stream_push_wire.restype = C.c_int
-            L.mml_livox_stream_push_wire.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int]
-            L.mml_livox_stream_state_get.argtypes = [C.c_void_p, C.c_void_p]
-            L.mml_union_assemble.restype = C.c_int
-            L.mml_union_assemble.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
-            L.mml_union_plan.restype = C.c_int
-            L.mml_union_plan.argtypes = [C.c_void_p, C.c_long, C.c_long, C.c_uint64, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-        if hasattr(L, "mml_union_assemble_offset"):
-            L.mml_union_assemble_offset.restype = C.c_int
-            L.mml_union_assemble_offset.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4
-            L.mml_union_plan_offset.restype = C.c_int
-            L.mml_union_plan_offset.argtypes = [C.c_void_p, C.c_long, C.c_long, C.c_uint64, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-            L.mml_scan_raw_download.restype = C.c_int
-            L.mml_scan_raw_download.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        if hasattr(L, "mml_velo_fov_select_batch"):
-            L.mml_velo_fov_select_batch.restype = C.c_int
-            L.mml_velo_fov_select_batch.argtypes = ([C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p] * 2 + [C.c_long]
-                                                    + [C.c_void_p] * 2)
-            L.mml_velo_fov_select.restype = C.c_int
-            L.mml_velo_fov_select.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 2 + [C.c_int] + [C.c_void_p] * 2
-        if hasattr(L, "mml_time_offset_estimate_stream"):
-            L.mml_time_offset_estimate_stream.restype = C.c_int
-            L.mml_time_offset_estimate_stream.argtypes = ([C.c_void_p, C.c_void_p, C.c_long, C.c_long, C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 4
-                                                          + [C.c_void_p] * 2 + [C.c_int, C.c_int, C.c_double] + [C.c_void_p] * 4)
-            L.mml_time_offset_gate.restype = C.c_int
-            L.mml_time_offset_gate.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
-        if hasattr(L, "mml_imu_fetch_batch"):
-            L.mml_imu_stream_create.restype = C.c_int
-            L.mml_imu_stream_create.argtypes = [C.c_void_p, C.c_long, C.c_void_p]
-            L.mml_imu_stream_destroy.restype = None
-            L.mml_imu_stream_destroy.argtypes = [C.c_void_p]
-            L.mml_imu_stream_reset.argtypes = [C.c_void_p]
-            L.mml_imu_stream_push.restype = C.c_int
-            L.mml_imu_stream_push.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-            L.mml_imu_stream_drop_before.restype = C.c_int
-            L.mml_imu_stream_drop_before.argtypes = [C.c_void_p, C.c_double, C.c_long]
-            L.mml_imu_stream_state_get.argtypes = [C.c_void_p, C.c_void_p]
-            L.mml_imu_fetch_batch.restype = C.c_int
-            L.mml_imu_fetch_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7 + [C.c_long] + [C.c_void_p] * 2
-            L.mml_imu_fetch_host.restype = C.c_int
-            L.mml_imu_fetch_host.argtypes = [C.c_void_p, C.c_long, C.c_int] + [C.c_void_p] * 7 + [C.c_long] + [C.c_void_p] * 2
-            L.mml_imu_predict_batch.restype = C.c_int
-            L.mml_imu_predict_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 9
-        if hasattr(L, "mml_pose_ingest_batch"):
-            L.mml_pose_ingest_opts_default.restype = None
-            L.mml_pose_ingest_opts_default.argtypes = [C.c_void_p]
-            L.mml_pose_ingest_plan.restype = C.c_int
-            L.mml_pose_ingest_plan.argtypes = [C.c_int] + [C.c_void_p] * 4
-            L.mml_pose_ingest_batch.restype = C.c_int
-            L.mml_pose_ingest_batch.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
-        if hasattr(L, "mml_scan_upload_wire_batch"):
-            wire = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_int]   # offsets, counts, layout; twice
-            L.mml_scan_upload_wire_plan.restype = C.c_int
-            L.mml_scan_upload_wire_plan.argtypes = [C.c_int] + wire + [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-            L.mml_wire_decode_host.restype = C.c_int
-            L.mml_wire_decode_host.argtypes = [C.c_int, C.c_void_p] + wire[:7] + [C.c_void_p] + wire[7:] + [C.c_void_p, C.c_void_p]
-            L.mml_scan_upload_wire_batch.restype = C.c_int
-            L.mml_scan_upload_wire_batch.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p] + wire[:7] + [C.c_void_p] + wire[7:]
-        if hasattr(L, "mml_world_map_create"):
-            for name, args in WORLD_MAP_ARGTYPES.items():
-                getattr(L, name).restype = C.c_int
-                getattr(L, name).argtypes = args
-        if hasattr(L, "mml_world_map_create_opts"):
-            for name, args in WORLD_MAP_SURFEL_ARGTYPES.items():
-                getattr(L, name).restype = C.c_int
-                getattr(L, name).argtypes = args
-        if hasattr(L, "mml_world_map_localize"):
-            for name, args in WORLD_MAP_LOCALIZE_ARGTYPES.items():
-                getattr(L, name).restype = C.c_int
-                getattr(L, name).argtypes = args
-            for name in ("mml_wm_assoc_opts_default", "mml_wm_localize_opts_default"):
-                getattr(L, name).restype = None
-                getattr(L, name).argtypes = [C.c_void_p, C.c_float]
-        if hasattr(L, "mml_world_map_score"):
-            for name, args in WORLD_MAP_SCORE_ARGTYPES.items():
-                getattr(L, name).restype = C.c_int
-                getattr(L, name).argtypes = args
-            for name in ("mml_wm_score_opts_default", "mml_wm_reloc_opts_default"):
-                getattr(L, name).restype = None
-                getattr(L, name).argtypes = [C.c_void_p, C.c_float]
+        _bind(L)
         _lib = L
     return _lib
 
@@ -579,7 +558,7 @@ def cube_index(xyz, cen=(10, 5, 10)):
 
 def default_config(max_scans=1, **over):
     cfg = Config()
-    lib().mml_config_default(C.byref(cfg), C.c_int(max_scans))
+    lib().mml_config_default(C.byref(cfg), max_scans)
     for k, v in over.items():
         setattr(cfg, k, v)
     return cfg
@@ -666,8 +645,7 @@ def time_offset_plan(velo_offsets, livox_offsets, search_resolution=30, sliced_p
     n = len(vo) - 1
     nwin = np.zeros(max(n, 1), np.int32)
     bad = C.c_int(-1)
-    rc = lib().mml_time_offset_plan(C.c_int(n), _p(vo), _p(lo), C.c_int(search_resolution), C.c_int(sliced_points),
-                                    C.c_int(max_map_points), _p(nwin), C.byref(bad))
+    rc = lib().mml_time_offset_plan(n, _p(vo), _p(lo), search_resolution, sliced_points, max_map_points, _p(nwin), C.byref(bad))
     return rc, bad.value, nwin[:max(n, 0)]
 
 
@@ -678,8 +656,7 @@ def time_offset_gate(velo_stamps, hori_stamp, n_hori_msgs):
     TOFS_GATE_OK, or -1 and TOFS_GATE_EMPTY (every frame popped) / TOFS_GATE_TOO_FEW_MESSAGES (fewer than 8 messages)."""
     vs = np.ascontiguousarray(velo_stamps, dtype=np.uint64)
     sel, st = C.c_int(-7), C.c_int(-7)
-    rc = lib().mml_time_offset_gate(C.c_int(len(vs)), _p(vs) if len(vs) else None, C.c_uint64(int(hori_stamp)), C.c_int(n_hori_msgs),
-                                    C.byref(sel), C.byref(st))
+    rc = lib().mml_time_offset_gate(len(vs), _p(vs) if len(vs) else None, int(hori_stamp), n_hori_msgs, C.byref(sel), C.byref(st))
     if rc != MML_OK:
         raise MmlError(rc, "mml_time_offset_gate")
     return sel.value, st.value
@@ -718,9 +695,8 @@ def velo_fov_select_raw(data, byte_offsets, n_points, point_step, off_x=0, off_y
     h = ctx._h if ctx is not None else None
 
     def call(xyzt, xyz, cap, kept, info):
-        rc = lib().mml_velo_fov_select_batch(h, C.c_int(n), _p(raw) if len(raw) else None, _p(bo), _p(npts), C.c_int(point_step),
-                                             C.c_int(off_x), C.c_int(off_y), C.c_int(off_z), _p(xyzt), _p(xyz), C.c_long(cap), _p(kept),
-                                             _p(info))
+        rc = lib().mml_velo_fov_select_batch(h, n, _p(raw) if len(raw) else None, _p(bo), _p(npts), point_step, off_x, off_y, off_z, _p(xyzt),
+                                             _p(xyz), cap, _p(kept), _p(info))
         if ctx is not None:
             ctx._ck(rc)
         elif rc != MML_OK:
@@ -757,8 +733,7 @@ def union_plan(S, front, tail, hs, stamps, max_livox_points):
     if tail > len(Sa):
         raise ValueError("tail = %d lies beyond the %d stamps given" % (tail, len(Sa)))
     rows = np.zeros(max(count, 1), UNION_FRAME_DTYPE)
-    rc = lib().mml_union_plan(_p(Sa) if len(Sa) else None, C.c_long(front), C.c_long(tail), C.c_uint64(int(hs)), C.c_int(count), _p(st),
-                              C.c_int(max_livox_points), _p(rows))
+    rc = lib().mml_union_plan(_p(Sa) if len(Sa) else None, front, tail, int(hs), count, _p(st), max_livox_points, _p(rows))
     return rc, rows[:max(count, 0)]
 
 
@@ -772,8 +747,7 @@ def union_plan_offset(S, front, tail, hs, starts, sliced_points):
     if tail > len(Sa):
         raise ValueError("tail = %d lies beyond the %d stamps given" % (tail, len(Sa)))
     rows = np.zeros(max(count, 1), UNION_FRAME_DTYPE)
-    rc = lib().mml_union_plan_offset(_p(Sa) if len(Sa) else None, C.c_long(front), C.c_long(tail), C.c_uint64(int(hs)), C.c_int(count),
-                                     _p(st) if count else None, C.c_int(sliced_points), _p(rows))
+    rc = lib().mml_union_plan_offset(_p(Sa) if len(Sa) else None, front, tail, int(hs), count, _p(st) if count else None, sliced_points, _p(rows))
     return rc, rows[:count]
 
 
@@ -788,7 +762,7 @@ class LivoxStream:
         self._ctx = ctx
         self._h = C.c_void_p()
         self._keep = []
-        ctx._ck(lib().mml_livox_stream_create(ctx._h, C.c_long(capacity), C.byref(self._h)))
+        ctx._ck(lib().mml_livox_stream_create(ctx._h, capacity, C.byref(self._h)))
 
     def close(self):
         if getattr(self, "_h", None) and getattr(self._ctx, "_h", None):
@@ -812,7 +786,7 @@ class LivoxStream:
         l = np.ascontiguousarray(points)
         assert l.dtype.itemsize == 20
         self._held(l)
-        self._ctx._ck(lib().mml_livox_stream_push(self._h, C.c_uint64(int(timebase)), _p(l) if len(l) else None, C.c_int(len(l))))
+        self._ctx._ck(lib().mml_livox_stream_push(self._h, int(timebase), _p(l) if len(l) else None, len(l)))
 
     def push_wire(self, timebase, wire, n):
         """The same message with its points in wire form: the serialised CustomPoint array, 19 bytes per point."""
@@ -820,7 +794,7 @@ class LivoxStream:
         if len(w) < 19 * n:
             raise ValueError("wire shorter than 19 * n bytes")
         self._held(w)
-        self._ctx._ck(lib().mml_livox_stream_push_wire(self._h, C.c_uint64(int(timebase)), _p(w) if n else None, C.c_int(n)))
+        self._ctx._ck(lib().mml_livox_stream_push_wire(self._h, int(timebase), _p(w) if n else None, n))
 
     def state(self):
         """dict(start_stamp, front, tail, disorder); synchronises."""
@@ -843,7 +817,7 @@ class ImuStream:
         self._ctx = ctx
         self._h = C.c_void_p()
         self._keep = []
-        ctx._ck(lib().mml_imu_stream_create(ctx._h, C.c_long(capacity), C.byref(self._h)))
+        ctx._ck(lib().mml_imu_stream_create(ctx._h, capacity, C.byref(self._h)))
 
     def close(self):
         if getattr(self, "_h", None) and getattr(self._ctx, "_h", None):
@@ -863,11 +837,11 @@ class ImuStream:
         if len(self._keep) > 64:
             self._ctx.synchronize()
             self._keep = self._keep[-1:]
-        self._ctx._ck(lib().mml_imu_stream_push(self._h, _p(m) if len(m) else None, C.c_int(len(m))))
+        self._ctx._ck(lib().mml_imu_stream_push(self._h, _p(m) if len(m) else None, len(m)))
 
     def drop_before(self, t, keep_min=200):
         """fetchImuMsgs' trim: while more than keep_min messages are live and the front one is older than t, drop it."""
-        self._ctx._ck(lib().mml_imu_stream_drop_before(self._h, C.c_double(t), C.c_long(keep_min)))
+        self._ctx._ck(lib().mml_imu_stream_drop_before(self._h, t, keep_min))
 
     def state(self):
         """dict(front, tail, disorder, first_stamp, last_stamp); synchronises."""
@@ -886,7 +860,7 @@ class Context:
     def __init__(self, cfg=None, device=0, **over):
         self.cfg = cfg if cfg is not None else default_config(**over)
         self._h = C.c_void_p()
-        rc = lib().mml_create(C.byref(self.cfg), C.c_int(device), C.byref(self._h))
+        rc = lib().mml_create(C.byref(self.cfg), device, C.byref(self._h))
         if rc != MML_OK:
             raise MmlError(rc, "mml_create failed (no HIP device?)" if rc == MML_ERR_NO_DEVICE else "mml_create failed")
         self.device = device
@@ -916,7 +890,7 @@ class Context:
         assert l.dtype.itemsize == 20
         self._keep = getattr(self, "_keep", [])
         self._keep.append((v, l))  # host buffers must outlive the async copy
-        self._ck(lib().mml_scan_upload(self._h, C.c_int(slot), _p(v), C.c_int(len(v)), _p(l), C.c_int(len(l))))
+        self._ck(lib().mml_scan_upload(self._h, slot, _p(v), len(v), _p(l), len(l)))
         if len(self._keep) > 4 * self.cfg.max_scans:
             self.synchronize()
             self._keep = self._keep[-self.cfg.max_scans:]
@@ -937,7 +911,7 @@ class Context:
         if len(self._keep) > 4 * self.cfg.max_scans + 8:
             self.synchronize()  # the copies are asynchronous: nothing may be released while one is still in flight
             self._keep = self._keep[-8:]
-        self._ck(lib().mml_scan_upload_batch(self._h, C.c_int(first), C.c_int(count), _p(v), _p(nv), _p(l), _p(nl)))
+        self._ck(lib().mml_scan_upload_batch(self._h, first, count, _p(v), _p(nv), _p(l), _p(nl)))
 
     def scan_upload_pointcloud2(self, slot, data, n_points, point_step, off_x, off_y, off_z, off_intensity, livox):
         """Velodyne part as a sensor_msgs/PointCloud2 payload (bytes / uint8 array), decoded on the device."""
@@ -946,9 +920,8 @@ class Context:
         nl = 0 if lv is None else len(lv)
         if len(raw) < n_points * point_step:
             raise ValueError("PointCloud2 payload shorter than n_points * point_step bytes")
-        self._ck(lib().mml_scan_upload_pointcloud2(self._h, C.c_int(slot), _p(raw), C.c_int(n_points), C.c_int(point_step),
-                                                   C.c_int(off_x), C.c_int(off_y), C.c_int(off_z), C.c_int(off_intensity),
-                                                   _p(lv) if nl else None, C.c_int(nl)))
+        self._ck(lib().mml_scan_upload_pointcloud2(self._h, slot, _p(raw), n_points, point_step, off_x, off_y, off_z, off_intensity,
+                                                   _p(lv) if nl else None, nl))
         self.synchronize()
 
     def scan_upload_wire(self, slot, data, n_points, point_step, off_x, off_y, off_z, off_intensity, livox_wire, n_livox):
@@ -959,9 +932,8 @@ class Context:
             raise ValueError("livox_wire shorter than 19 * n_livox bytes")
         if len(raw) < n_points * point_step:
             raise ValueError("PointCloud2 payload shorter than n_points * point_step bytes")
-        self._ck(lib().mml_scan_upload_wire(self._h, C.c_int(slot), _p(raw), C.c_int(n_points), C.c_int(point_step),
-                                            C.c_int(off_x), C.c_int(off_y), C.c_int(off_z), C.c_int(off_intensity),
-                                            _p(lw) if n_livox else None, C.c_int(n_livox)))
+        self._ck(lib().mml_scan_upload_wire(self._h, slot, _p(raw), n_points, point_step, off_x, off_y, off_z, off_intensity,
+                                            _p(lw) if n_livox else None, n_livox))
         self.synchronize()
 
     def scan_upload_wire_batch(self, first_slot, velo_data, velo_at, n_velo, point_step, offs, livox_data, livox_at, n_livox,
@@ -978,8 +950,7 @@ class Context:
             self.synchronize()  # the copies are asynchronous: nothing may be released while one is still in flight
             self._keep = self._keep[-8:]
         vd, va, nv, ld, la, nl, lay = a
-        self._ck(lib().mml_scan_upload_wire_batch(self._h, C.c_int(first_slot), C.c_int(len(nv)), _p(vd), _p(va), _p(nv), *lay[:5], _p(ld), _p(la),
-                                                  _p(nl), lay[5]))
+        self._ck(lib().mml_scan_upload_wire_batch(self._h, first_slot, len(nv), _p(vd), _p(va), _p(nv), *lay[:5], _p(ld), _p(la), _p(nl), lay[5]))
 
     def time_offset_search(self, velo_xyz, livox_xyz, search_resolution=30, sliced_points=12000, tf=None):
         """estimate_timeoffset's numeric core (unionLidarsAligner.cpp:1077-1153): per-point 1-NN squared distances and
@@ -991,10 +962,9 @@ class Context:
         cap = max((len(l) - sliced_points) // max(search_resolution, 1) + 2, 1)
         err = np.zeros(cap, np.float64)
         nwin, best, lowest = C.c_int(0), C.c_int(-1), C.c_double(0)
-        self._ck(lib().mml_time_offset_search(self._h, _p(v) if len(v) else None, C.c_int(len(v)), _p(t) if t is not None else None,
-                                              _p(l) if len(l) else None, C.c_int(len(l)), C.c_int(search_resolution),
-                                              C.c_int(sliced_points), _p(nn), _p(err), C.c_int(cap), C.byref(nwin),
-                                              C.byref(best), C.byref(lowest)))
+        self._ck(lib().mml_time_offset_search(self._h, _p(v) if len(v) else None, len(v), _p(t) if t is not None else None, _p(l) if len(l) else None,
+                                              len(l), search_resolution, sliced_points, _p(nn), _p(err), cap, C.byref(nwin), C.byref(best),
+                                              C.byref(lowest)))
         return {"nn_d2": nn[:len(l)], "window_error": err[:nwin.value], "best_window": best.value, "lowest_error": lowest.value}
 
     def time_offset_search_batch(self, velo_list, livox_list, search_resolution=30, sliced_points=12000, tfs=None):
@@ -1011,9 +981,8 @@ class Context:
         nw = np.zeros(max(n, 1), np.int32)
         best = np.zeros(max(n, 1), np.int32)
         lowest = np.zeros(max(n, 1), np.float64)
-        self._ck(lib().mml_time_offset_search_batch(self._h, C.c_int(n), _p(velo) if len(velo) else None, _p(vo),
-                                                    _p(tf), _p(livox) if len(livox) else None, _p(lo), C.c_int(search_resolution),
-                                                    C.c_int(sliced_points), _p(nn), _p(err), _p(wo), _p(nw), _p(best), _p(lowest)))
+        self._ck(lib().mml_time_offset_search_batch(self._h, n, _p(velo) if len(velo) else None, _p(vo), _p(tf), _p(livox) if len(livox) else None,
+                                                    _p(lo), search_resolution, sliced_points, _p(nn), _p(err), _p(wo), _p(nw), _p(best), _p(lowest)))
         return [{"nn_d2": nn[lo[i]:lo[i + 1]], "window_error": err[wo[i]:wo[i] + nw[i]], "best_window": int(best[i]),
                  "lowest_error": float(lowest[i])} for i in range(n)]
 
@@ -1036,10 +1005,9 @@ class Context:
         nn = np.zeros(max(n * L, 1), np.float32)
         err = np.zeros(max(int(wo[-1]), 1), np.float64)
         rows = np.zeros(max(n, 1), TOFS_ROW_DTYPE)
-        self._ck(lib().mml_time_offset_estimate_stream(self._h, stream._h, C.c_long(int(livox_begin)), C.c_long(int(livox_end)), C.c_int(n),
-                                                       _p(data) if len(data) else None, _p(bo), _p(npts), C.c_int(step), C.c_int(0), C.c_int(4),
-                                                       C.c_int(8), _p(vs), _p(t), C.c_int(search_resolution), C.c_int(sliced_points),
-                                                       C.c_double(error_th), _p(nn), _p(err), _p(wo), _p(rows)))
+        self._ck(lib().mml_time_offset_estimate_stream(self._h, stream._h, int(livox_begin), int(livox_end), n, _p(data) if len(data) else None,
+                                                       _p(bo), _p(npts), step, 0, 4, 8, _p(vs), _p(t), search_resolution, sliced_points, error_th,
+                                                       _p(nn), _p(err), _p(wo), _p(rows)))
         out = []
         for i in range(n):
             r = {k: rows[k][i].item() for k in TOFS_ROW_DTYPE.names if k != "_pad"}
@@ -1076,8 +1044,7 @@ class Context:
         velo = np.ascontiguousarray(np.concatenate(vs + [np.zeros((0, 4), np.float32)]))
         t = np.ascontiguousarray(np.asarray(tf, np.float32).reshape(16)) if tf is not None else None
         rows = np.zeros(max(count, 1), UNION_FRAME_DTYPE)
-        self._ck(lib().mml_union_assemble(self._h, stream._h, C.c_int(first_slot), C.c_int(count), _p(st),
-                                          _p(velo) if len(velo) else None, _p(vo), _p(t), _p(rows)))
+        self._ck(lib().mml_union_assemble(self._h, stream._h, first_slot, count, _p(st), _p(velo) if len(velo) else None, _p(vo), _p(t), _p(rows)))
         return rows[:count]
 
     def union_assemble_offset(self, stream, first_slot, starts, sliced_points, velo_list, tf=None):
@@ -1094,26 +1061,25 @@ class Context:
         velo = np.ascontiguousarray(np.concatenate(vs + [np.zeros((0, 4), np.float32)]))
         t = np.ascontiguousarray(np.asarray(tf, np.float32).reshape(16)) if tf is not None else None
         rows = np.zeros(max(count, 1), UNION_FRAME_DTYPE)
-        self._ck(lib().mml_union_assemble_offset(self._h, stream._h, C.c_int(first_slot), C.c_int(count), _p(st) if count else None,
-                                                 C.c_int(sliced_points), _p(velo) if len(velo) else None, _p(vo), _p(t), _p(rows)))
+        self._ck(lib().mml_union_assemble_offset(self._h, stream._h, first_slot, count, _p(st) if count else None, sliced_points,
+                                                 _p(velo) if len(velo) else None, _p(vo), _p(t), _p(rows)))
         return rows[:count]
 
     def scan_raw_download(self, slot):
         """mml_scan_raw_download: the slot's raw input as it stands, (velo n x 4 float32, livox LIVOX_DTYPE)."""
         nv, nl = C.c_int(0), C.c_int(0)
-        self._ck(lib().mml_scan_raw_download(self._h, C.c_int(slot), None, C.c_int(0), None, C.c_int(0), C.byref(nv), C.byref(nl)))
+        self._ck(lib().mml_scan_raw_download(self._h, slot, None, 0, None, 0, C.byref(nv), C.byref(nl)))
         v = np.zeros((max(nv.value, 1), 4), np.float32)
         l = np.zeros(max(nl.value, 1), LIVOX_DTYPE)
-        self._ck(lib().mml_scan_raw_download(self._h, C.c_int(slot), _p(v), C.c_int(nv.value), _p(l), C.c_int(nl.value),
-                                             C.byref(nv), C.byref(nl)))
+        self._ck(lib().mml_scan_raw_download(self._h, slot, _p(v), nv.value, _p(l), nl.value, C.byref(nv), C.byref(nl)))
         return v[:nv.value], l[:nl.value]
 
     def scan_download_pointxyzinormal(self, slot):
         """The fused labelled cloud as 48-byte PointXYZINormal records (the velo_combine / livox_combine payload)."""
         n = C.c_int(0)
-        self._ck(lib().mml_scan_download_pointxyzinormal(self._h, C.c_int(slot), None, C.c_int(0), C.byref(n)))
+        self._ck(lib().mml_scan_download_pointxyzinormal(self._h, slot, None, 0, C.byref(n)))
         out = np.zeros((max(n.value, 1), 12), np.float32)
-        self._ck(lib().mml_scan_download_pointxyzinormal(self._h, C.c_int(slot), _p(out), C.c_int(n.value), C.byref(n)))
+        self._ck(lib().mml_scan_download_pointxyzinormal(self._h, slot, _p(out), n.value, C.byref(n)))
         return out[:n.value]
 
     def cloud_download_registered(self, first_slot, count, T_wl):
@@ -1156,7 +1122,7 @@ class Context:
         into a slot: the PoseEstimation side of /union_feature_cloud."""
         rec = np.ascontiguousarray(records, dtype=np.float32).reshape(-1, 12)
         nv = len(rec) if n_velo is None else int(n_velo)
-        self._ck(lib().mml_cloud_upload(self._h, C.c_int(slot), _p(rec) if len(rec) else None, C.c_int(len(rec)), C.c_int(nv)))
+        self._ck(lib().mml_cloud_upload(self._h, slot, _p(rec) if len(rec) else None, len(rec), nv))
 
     def pose_ingest(self, first_slot, clouds, n_points=None, rows=None, **opts):
         """mml_pose_ingest_batch: n union_cloud messages into slots first_slot .. in ONE call, with the pose node's decision per
@@ -1166,8 +1132,7 @@ class Context:
         hori_rotate_th, velo_rotate_th, velo_only_mode, first_frame.  Returns the rows (POSE_INGEST_ROW_DTYPE)."""
         block, n, r, o = pose_ingest_pack(clouds, n_points, rows, opts)
         out = np.zeros(max(len(n), 1), POSE_INGEST_ROW_DTYPE)
-        self._ck(lib().mml_pose_ingest_batch(self._h, C.c_int(first_slot), C.c_int(len(n)), _p(block) if block.size else None, _p(n), _p(r),
-                                             C.byref(o), _p(out)))
+        self._ck(lib().mml_pose_ingest_batch(self._h, first_slot, len(n), _p(block) if block.size else None, _p(n), _p(r), C.byref(o), _p(out)))
         return out[:len(n)]
 
     def gicp_align(self, src, tgt, T0=None):
@@ -1176,8 +1141,8 @@ class Context:
         tgt = _f32(tgt).reshape(-1, 3)
         T = np.ascontiguousarray(np.eye(4, dtype=np.float32) if T0 is None else np.asarray(T0, np.float32).reshape(4, 4).copy())
         conv, info = C.c_int(0), GicpInfo()
-        self._ck(lib().mml_gicp_align(self._h, _p(src) if len(src) else None, C.c_int(len(src)), _p(tgt) if len(tgt) else None,
-                                      C.c_int(len(tgt)), _p(T), C.byref(conv), C.byref(info)))
+        self._ck(lib().mml_gicp_align(self._h, _p(src) if len(src) else None, len(src), _p(tgt) if len(tgt) else None, len(tgt), _p(T), C.byref(conv),
+                                      C.byref(info)))
         return bool(conv.value), T, info
 
     def gicp_align_opts(self, src, tgt, max_iterations=10, transformation_epsilon=1e-6, max_correspondence_distance=0.0, T0=None):
@@ -1188,8 +1153,8 @@ class Context:
         T = np.ascontiguousarray(np.eye(4, dtype=np.float32) if T0 is None else np.asarray(T0, np.float32).reshape(4, 4).copy())
         opts = GicpOpts(int(max_iterations), float(transformation_epsilon), float(max_correspondence_distance))
         conv, info = C.c_int(0), GicpInfo()
-        self._ck(lib().mml_gicp_align_opts(self._h, _p(src) if len(src) else None, C.c_int(len(src)), _p(tgt) if len(tgt) else None,
-                                           C.c_int(len(tgt)), C.byref(opts), _p(T), C.byref(conv), C.byref(info)))
+        self._ck(lib().mml_gicp_align_opts(self._h, _p(src) if len(src) else None, len(src), _p(tgt) if len(tgt) else None, len(tgt), C.byref(opts),
+                                           _p(T), C.byref(conv), C.byref(info)))
         return bool(conv.value), T, info
 
     def debug_gicp(self, op, src=None, tgt=None, cov_src=None, cov_tgt=None, T=None, corr=None, maha=None, x=None, gate2=0.0, grad=True,
@@ -1221,7 +1186,7 @@ class Context:
         ni = {GICP_DBG_COV: 20 * nt, GICP_DBG_CORR: ns, GICP_DBG_ROUND: 4}.get(op, 1)
         od, oi, of = np.zeros(nd), np.zeros(ni, np.int32), np.zeros(16 * k, np.float32)
         io.out_d, io.out_i, io.out_f = _p(od), _p(oi), _p(of)
-        self._ck(lib().mml_debug_gicp(self._h, C.c_int(op), C.byref(io)))
+        self._ck(lib().mml_debug_gicp(self._h, op, C.byref(io)))
         if op == GICP_DBG_COV:
             return od.reshape(-1, 3, 3), oi.reshape(-1, 20)
         if op == GICP_DBG_CORR:
@@ -1245,15 +1210,15 @@ class Context:
         xyzi = _f32(xyzi).reshape(-1, 4)
         f = lib().mml_cloud_crop_voxel
         n, unf = C.c_int(0), C.c_int(0)
-        a = (self._h, _p(xyzi) if len(xyzi) else None, C.c_int(len(xyzi)), C.c_float(far_th), C.c_float(leaf))
+        a = (self._h, _p(xyzi) if len(xyzi) else None, len(xyzi), far_th, leaf)
         if out is None:
-            self._ck(f(*a, None, C.c_int(0), C.byref(n), C.byref(unf)))
+            self._ck(f(*a, None, 0, C.byref(n), C.byref(unf)))
             out = np.zeros((max(n.value, 1), 4), np.float32)
             cap = n.value
         else:
             assert out.dtype == np.float32 and out.flags.c_contiguous and out.ndim == 2 and out.shape[1] == 4
             cap = len(out)
-        self._ck(f(*a, _p(out), C.c_int(cap), C.byref(n), C.byref(unf)))
+        self._ck(f(*a, _p(out), cap, C.byref(n), C.byref(unf)))
         return out[:n.value], bool(unf.value)
 
     def aligner_calibrate(self, hori_xyzi, velo_xyzi, hori_tf=None, velo_hori_tf=None):
@@ -1265,15 +1230,15 @@ class Context:
         mats = [np.ascontiguousarray(np.eye(4, dtype=np.float32) if m is None else np.asarray(m, np.float32).reshape(4, 4).copy())
                 for m in (hori_tf, velo_hori_tf)]
         conv, info = C.c_int(0), CalibInfo()
-        self._ck(lib().mml_aligner_calibrate(self._h, _p(h) if len(h) else None, C.c_int(len(h)), _p(v) if len(v) else None,
-                                             C.c_int(len(v)), _p(mats[0]), _p(mats[1]), C.byref(conv), C.byref(info)))
+        self._ck(lib().mml_aligner_calibrate(self._h, _p(h) if len(h) else None, len(h), _p(v) if len(v) else None, len(v), _p(mats[0]), _p(mats[1]),
+                                             C.byref(conv), C.byref(info)))
         return bool(conv.value), mats[0], mats[1], info
 
     def gicp_refresh(self, slot, extrinsic, apply=True):
         """unionCloudHandler's extrinsic refresh (:302-318) on a slot extracted without an extrinsic."""
         T = np.ascontiguousarray(np.asarray(extrinsic, np.float32).reshape(4, 4).copy())
         ref, info = C.c_int(0), GicpInfo()
-        self._ck(lib().mml_gicp_refresh(self._h, C.c_int(slot), _p(T), C.c_int(1 if apply else 0), C.byref(ref), C.byref(info)))
+        self._ck(lib().mml_gicp_refresh(self._h, slot, _p(T), 1 if apply else 0, C.byref(ref), C.byref(info)))
         return bool(ref.value), T, info
 
     def gicp_align_batch(self, pairs, T0=None):
@@ -1282,8 +1247,8 @@ class Context:
         n = len(pairs)
         conv = np.zeros(max(n, 1), np.int32)
         info = (GicpInfo * max(n, 1))()
-        self._ck(lib().mml_gicp_align_batch(self._h, C.c_int(n), _p(src) if len(src) else None, _p(so), _p(tgt) if len(tgt) else None,
-                                            _p(to), _p(T), _p(conv), C.cast(info, C.c_void_p)))
+        self._ck(lib().mml_gicp_align_batch(self._h, n, _p(src) if len(src) else None, _p(so), _p(tgt) if len(tgt) else None, _p(to), _p(T), _p(conv),
+                                            C.cast(info, C.c_void_p)))
         return [(bool(conv[i]), T[i], info[i]) for i in range(n)]
 
     def gicp_refresh_batch(self, first_slot, count, extrinsic, chain=True, apply=True):
@@ -1299,17 +1264,17 @@ class Context:
             T[:] = e.reshape(n, 4, 4)
         ref = np.zeros(n, np.int32)
         info = (GicpInfo * n)()
-        self._ck(lib().mml_gicp_refresh_batch(self._h, C.c_int(first_slot), C.c_int(count), _p(T), C.c_int(1 if chain else 0),
-                                              C.c_int(1 if apply else 0), _p(ref), C.cast(info, C.c_void_p)))
+        self._ck(lib().mml_gicp_refresh_batch(self._h, first_slot, count, _p(T), 1 if chain else 0, 1 if apply else 0, _p(ref),
+                                              C.cast(info, C.c_void_p)))
         return ref[:count].astype(bool), T[:count], list(info)[:count]
 
     def extract(self, first=0, count=1, livox_extrinsic=None):
         e = _f32(livox_extrinsic).reshape(16) if livox_extrinsic is not None else None
-        self._ck(lib().mml_extract(self._h, C.c_int(first), C.c_int(count), _p(e)))
+        self._ck(lib().mml_extract(self._h, first, count, _p(e)))
 
     def scan_info(self, slot):
         info = ScanInfo()
-        self._ck(lib().mml_scan_info_get(self._h, C.c_int(slot), C.byref(info)))
+        self._ck(lib().mml_scan_info_get(self._h, slot, C.byref(info)))
         return info
 
     def scan_download(self, slot):
@@ -1319,7 +1284,7 @@ class Context:
         rel = np.zeros(max(n, 1), np.float32)
         line = np.zeros(max(n, 1), np.uint8)
         label = np.zeros(max(n, 1), np.uint8)
-        self._ck(lib().mml_scan_download(self._h, C.c_int(slot), _p(xyzi), _p(rel), _p(line), _p(label), C.c_int(max(n, 1))))
+        self._ck(lib().mml_scan_download(self._h, slot, _p(xyzi), _p(rel), _p(line), _p(label), max(n, 1)))
         return dict(xyzi=xyzi[:n], reltime=rel[:n], ring=line[:n].astype(np.int32), label=label[:n].astype(np.int32),
                     info=info)
 
@@ -1331,47 +1296,45 @@ class Context:
         flat = np.zeros(max(n, 1), np.int32)
         flags = np.zeros(max(n, 1), np.int32)
         ns, nf = C.c_int(0), C.c_int(0)
-        self._ck(lib().mml_detect_line(self._h, _p(pts), C.c_int(n), _p(sharp), C.byref(ns), _p(flat), C.byref(nf),
-                                       _p(flags)))
+        self._ck(lib().mml_detect_line(self._h, _p(pts), n, _p(sharp), C.byref(ns), _p(flat), C.byref(nf), _p(flags)))
         return sharp[:ns.value].copy(), flat[:nf.value].copy(), flags[:n].copy()
 
     # ---- RemoveLidarDistortion ----
     def undistort(self, first, count, dR, dt):
         dR = _f64(dR).reshape(count, 9)
         dt = _f64(dt).reshape(count, 3)
-        self._ck(lib().mml_undistort(self._h, C.c_int(first), C.c_int(count), _p(dR), _p(dt)))
+        self._ck(lib().mml_undistort(self._h, first, count, _p(dR), _p(dt)))
 
     # ---- Estimator::EstimateLidarPose pieces ----
     def downsample(self, first=0, count=1):
-        self._ck(lib().mml_downsample(self._h, C.c_int(first), C.c_int(count)))
+        self._ck(lib().mml_downsample(self._h, first, count))
 
     def features_download(self, slot, kind):
         n = C.c_int(0)
-        self._ck(lib().mml_features_download(self._h, C.c_int(slot), C.c_int(kind), None, C.c_int(0), C.byref(n)))
+        self._ck(lib().mml_features_download(self._h, slot, kind, None, 0, C.byref(n)))
         out = np.zeros((max(n.value, 1), 3), np.float32)
-        self._ck(lib().mml_features_download(self._h, C.c_int(slot), C.c_int(kind), _p(out), C.c_int(max(n.value, 1)),
-                                             C.byref(n)))
+        self._ck(lib().mml_features_download(self._h, slot, kind, _p(out), max(n.value, 1), C.byref(n)))
         return out[:n.value]
 
     def features_count(self, slot, kind):
         """Points in the slot's down-sampled stack of `kind`, without the copy."""
         n = C.c_int(0)
-        self._ck(lib().mml_features_download(self._h, C.c_int(slot), C.c_int(kind), None, C.c_int(0), C.byref(n)))
+        self._ck(lib().mml_features_download(self._h, slot, kind, None, 0, C.byref(n)))
         return n.value
 
     def features_upload(self, slot, kind, xyz):
         xyz = _f32(xyz).reshape(-1, 3)
-        self._ck(lib().mml_features_upload(self._h, C.c_int(slot), C.c_int(kind), _p(xyz), C.c_int(len(xyz))))
+        self._ck(lib().mml_features_upload(self._h, slot, kind, _p(xyz), len(xyz)))
 
     def map_set_local(self, kind, xyz):
         xyz = _f32(xyz).reshape(-1, 3)
-        self._ck(lib().mml_map_set_local(self._h, C.c_int(kind), _p(xyz), C.c_int(len(xyz))))
+        self._ck(lib().mml_map_set_local(self._h, kind, _p(xyz), len(xyz)))
 
     def map_increment_local(self, slot, T_wl):
         """Estimator::MapIncrementLocal on the device; returns the new (corner, surf) local map sizes."""
         nc, ns = C.c_int(0), C.c_int(0)
         T = _f64(T_wl).reshape(16)
-        self._ck(lib().mml_map_increment_local(self._h, C.c_int(slot), _p(T), C.byref(nc), C.byref(ns)))
+        self._ck(lib().mml_map_increment_local(self._h, slot, _p(T), C.byref(nc), C.byref(ns)))
         return nc.value, ns.value
 
     def map_local_reset(self):
@@ -1522,24 +1485,24 @@ class Context:
         if n == 0:
             self._ck(lib().mml_map_banks_destroy(self._h))
         else:
-            self._ck(lib().mml_map_banks_create(self._h, C.c_int(n)))
+            self._ck(lib().mml_map_banks_create(self._h, n))
 
     def bind_banks(self, first, banks):
         """banks[i]: the bank of slot first + i, -1 the context's own map; stays until it is changed."""
         b = np.ascontiguousarray(banks, dtype=np.int32).reshape(-1)
-        self._ck(lib().mml_slot_bind_bank(self._h, C.c_int(first), C.c_int(len(b)), _p(b)))
+        self._ck(lib().mml_slot_bind_bank(self._h, first, len(b), _p(b)))
 
     def slot_banks(self, first, count):
         b = np.zeros(count, np.int32)
-        self._ck(lib().mml_slot_bank_get(self._h, C.c_int(first), C.c_int(count), _p(b)))
+        self._ck(lib().mml_slot_bank_get(self._h, first, count, _p(b)))
         return b
 
     def bank_set_local(self, bank, kind, xyz):
         xyz = _f32(xyz).reshape(-1, 3)
-        self._ck(lib().mml_map_bank_set_local(self._h, C.c_int(bank), C.c_int(kind), _p(xyz), C.c_int(len(xyz))))
+        self._ck(lib().mml_map_bank_set_local(self._h, bank, kind, _p(xyz), len(xyz)))
 
     def bank_reset(self, bank):
-        self._ck(lib().mml_map_bank_reset(self._h, C.c_int(bank)))
+        self._ck(lib().mml_map_bank_reset(self._h, bank))
 
     def bank_download(self, bank, kind):
         return self._download(lib().mml_map_bank_download, (int(bank), int(kind)), [(3, np.float32)])[0]
@@ -1556,12 +1519,12 @@ class Context:
             raise ValueError("one slot and one pose per bank")
         nc, ns = np.zeros(max(len(b), 1), np.int32), np.zeros(max(len(b), 1), np.int32)
         call = lib().mml_map_bank_increment_segmented if segmented else lib().mml_map_bank_increment
-        self._ck(call(self._h, C.c_int(len(b)), _p(b), _p(s), _p(T), _p(nc), _p(ns)))
+        self._ck(call(self._h, len(b), _p(b), _p(s), _p(T), _p(nc), _p(ns)))
         return nc[:len(b)], ns[:len(b)]
 
     def debug_bank_increment_budget(self, points):
         """mml_debug_bank_increment_budget (a test hook): the ring points a segmented bank_increment works on at a time."""
-        self._ck(lib().mml_debug_bank_increment_budget(self._h, C.c_long(int(points))))
+        self._ck(lib().mml_debug_bank_increment_budget(self._h, int(points)))
 
     # ---- a bank's global cube map: its own MAP_MANAGER store and match copy (include/mmloam_hip.h, "map banks") ----
     def bank_set_global(self, bank, kind, xyz, cube, cen=None):
@@ -1571,7 +1534,7 @@ class Context:
         if len(cube) != len(xyz):
             raise ValueError("one cube index per point")
         cen_p = None if cen is None else _p(np.ascontiguousarray(cen, dtype=np.int32))
-        self._ck(lib().mml_map_bank_set_global(self._h, C.c_int(bank), C.c_int(kind), _p(xyz), _p(cube), C.c_int(len(xyz)), cen_p))
+        self._ck(lib().mml_map_bank_set_global(self._h, bank, kind, _p(xyz), _p(cube), len(xyz), cen_p))
 
     def bank_global_append(self, banks, slots, T_wl, segmented=False):
         """map_global_append for len(banks) distinct banks in one call: the stacks of slot slots[i] at T_wl[i] (4 x 4) go to
@@ -1583,7 +1546,7 @@ class Context:
         if not (len(b) == len(s) == len(T)):
             raise ValueError("one slot and one pose per bank")
         call = lib().mml_map_bank_global_append_segmented if segmented else lib().mml_map_bank_global_append
-        self._ck(call(self._h, C.c_int(len(b)), _p(b), _p(s), _p(T)))
+        self._ck(call(self._h, len(b), _p(b), _p(s), _p(T)))
 
     def bank_global_increment(self, banks, T_wl, segmented=False):
         """map_global_increment for len(banks) distinct banks in one call, bank banks[i] at T_wl[i].  Returns the live (corner,
@@ -1596,21 +1559,21 @@ class Context:
             raise ValueError("one pose per bank")
         nc, ns = np.zeros(max(len(b), 1), np.int32), np.zeros(max(len(b), 1), np.int32)
         call = lib().mml_map_bank_global_increment_segmented if segmented else lib().mml_map_bank_global_increment
-        self._ck(call(self._h, C.c_int(len(b)), _p(b), _p(T), _p(nc), _p(ns)))
+        self._ck(call(self._h, len(b), _p(b), _p(T), _p(nc), _p(ns)))
         return nc[:len(b)], ns[:len(b)]
 
     def bank_global_increment_budget(self, points):
         """mml_debug_bank_global_increment_budget (a test hook): the points a segmented bank_global_increment works on at a time."""
-        self._ck(lib().mml_debug_bank_global_increment_budget(self._h, C.c_long(int(points))))
+        self._ck(lib().mml_debug_bank_global_increment_budget(self._h, int(points)))
 
     def bank_global_download(self, bank, kind):
         return self._cube_download(lib().mml_map_bank_global_download, (int(bank), int(kind)))
 
     def bank_global_reset(self, bank):
-        self._ck(lib().mml_map_bank_global_reset(self._h, C.c_int(bank)))
+        self._ck(lib().mml_map_bank_global_reset(self._h, bank))
 
     def map_global_append(self, slot, T_wl):
-        self._ck(lib().mml_map_global_append(self._h, C.c_int(slot), _p(_f64(T_wl).reshape(16))))
+        self._ck(lib().mml_map_global_append(self._h, slot, _p(_f64(T_wl).reshape(16))))
 
     def map_global_increment(self, T_wl):
         """MAP_MANAGER::MapIncrement on the device; returns the live (corner, surf) store sizes."""
@@ -1636,14 +1599,14 @@ class Context:
         if len(cube) != len(xyz):
             raise ValueError("one cube index per point")
         cen_p = None if cen is None else _p(np.ascontiguousarray(cen, dtype=np.int32))
-        self._ck(lib().mml_map_set_global(self._h, C.c_int(kind), _p(xyz), _p(cube), C.c_int(len(xyz)), cen_p))
+        self._ck(lib().mml_map_set_global(self._h, kind, _p(xyz), _p(cube), len(xyz), cen_p))
 
     def knn5(self, kind, q, max_d2=np.inf):
         q = _f32(q).reshape(-1, 3)
         idx = np.zeros((len(q), 5), np.int32)
         d2 = np.zeros((len(q), 5), np.float32)
         md = np.float32(min(max_d2, 3.0e38))
-        self._ck(lib().mml_knn5(self._h, C.c_int(kind), _p(q), C.c_int(len(q)), C.c_float(md), _p(idx), _p(d2)))
+        self._ck(lib().mml_knn5(self._h, kind, _p(q), len(q), md, _p(idx), _p(d2)))
         return idx, d2
 
     def associate(self, first, count, T_wl, thres_dist, stats=True):
@@ -1652,44 +1615,40 @@ class Context:
         T = _f64(T_wl).reshape(count, 16)
         if not stats:
             self._keep_T = T                              # the poses are staged before the call returns; kept anyway
-            self._ck(lib().mml_associate(self._h, C.c_int(first), C.c_int(count), _p(T), C.c_double(thres_dist), None))
+            self._ck(lib().mml_associate(self._h, first, count, _p(T), thres_dist, None))
             return None
         st = (AssocStats * count)()
-        self._ck(lib().mml_associate(self._h, C.c_int(first), C.c_int(count), _p(T), C.c_double(thres_dist), st))
+        self._ck(lib().mml_associate(self._h, first, count, _p(T), thres_dist, st))
         return list(st)
 
     def factors_download(self, slot, kind):
         n = C.c_int(0)
-        self._ck(lib().mml_factors_download(self._h, C.c_int(slot), C.c_int(kind), None, None, C.c_int(0), C.byref(n)))
+        self._ck(lib().mml_factors_download(self._h, slot, kind, None, None, 0, C.byref(n)))
         out = np.zeros((max(n.value, 1), 10))
         src = np.zeros(max(n.value, 1), np.int32)
-        self._ck(lib().mml_factors_download(self._h, C.c_int(slot), C.c_int(kind), _p(out), _p(src),
-                                            C.c_int(max(n.value, 1)), C.byref(n)))
+        self._ck(lib().mml_factors_download(self._h, slot, kind, _p(out), _p(src), max(n.value, 1), C.byref(n)))
         return out[:n.value], src[:n.value]
 
     def factors_upload(self, slot, kind, rec):
         rec = _f64(rec).reshape(-1, 10)
-        self._ck(lib().mml_factors_upload(self._h, C.c_int(slot), C.c_int(kind), _p(rec), C.c_int(len(rec))))
+        self._ck(lib().mml_factors_upload(self._h, slot, kind, _p(rec), len(rec)))
 
     def linearize(self, slot, x, T_bl, w_tan=0.0, huber=0.1 / 1.5e-3):
         H = np.zeros((6, 6))
         g = np.zeros(6)
         c = C.c_double(0)
-        self._ck(lib().mml_linearize(self._h, C.c_int(slot), _p(_f64(x)), _p(_f64(T_bl).reshape(16)), C.c_double(w_tan),
-                                     C.c_double(huber), _p(H), _p(g), C.byref(c)))
+        self._ck(lib().mml_linearize(self._h, slot, _p(_f64(x)), _p(_f64(T_bl).reshape(16)), w_tan, huber, _p(H), _p(g), C.byref(c)))
         return H, g, c.value
 
     def linearize_window(self, first, frames, x, T_bl, w_tan=0.0, huber=0.1 / 1.5e-3):
         """Records (frames, 32) of the consecutive slots first .. first + frames - 1 at x (frames, >= 6): one launch."""
         x = _f64(x).reshape(frames, -1)
         rec = np.zeros((frames, NEQ_RECORD_DOUBLES))
-        self._ck(lib().mml_linearize_window(self._h, C.c_int(first), C.c_int(frames), C.c_int(x.shape[1]), _p(x),
-                                            _p(_f64(T_bl).reshape(16)), C.c_double(w_tan), C.c_double(huber), _p(rec)))
+        self._ck(lib().mml_linearize_window(self._h, first, frames, x.shape[1], _p(x), _p(_f64(T_bl).reshape(16)), w_tan, huber, _p(rec)))
         return rec
 
     def linearize_record(self, slot, x, T_bl, d_record_ptr, w_tan=0.0, huber=0.1 / 1.5e-3):
-        self._ck(lib().mml_linearize_record(self._h, C.c_int(slot), _p(_f64(x)), _p(_f64(T_bl).reshape(16)),
-                                            C.c_double(w_tan), C.c_double(huber), C.c_void_p(d_record_ptr)))
+        self._ck(lib().mml_linearize_record(self._h, slot, _p(_f64(x)), _p(_f64(T_bl).reshape(16)), w_tan, huber, C.c_void_p(d_record_ptr)))
 
     def solve(self, first, count, x, T_bl, window=1, max_iters=10, fixed=False, huber=0.1 / 1.5e-3, w_tan=0.0,
               trace=False):
@@ -1698,23 +1657,20 @@ class Context:
         nprob = count // window
         summ = (SolveSummary * nprob)()
         tr = np.zeros((nprob, max_iters, 6 * window)) if trace else None
-        self._ck(lib().mml_solve(self._h, C.c_int(first), C.c_int(count), C.c_int(window), _p(_f64(T_bl).reshape(16)),
-                                 C.byref(opts), _p(x), summ, _p(tr)))
+        self._ck(lib().mml_solve(self._h, first, count, window, _p(_f64(T_bl).reshape(16)), C.byref(opts), _p(x), summ, _p(tr)))
         return x, list(summ), tr
 
     def estimate(self, first, count, exTlb, P, Q, max_outer=5, inner_iters=10):
         P = _f64(P).reshape(count, 3).copy()
         Q = _f64(Q).reshape(count, 4).copy()
         info = (EstimateInfo * count)()
-        self._ck(lib().mml_estimate(self._h, C.c_int(first), C.c_int(count), _p(_f64(exTlb).reshape(16)), _p(P), _p(Q),
-                                    C.c_int(max_outer), C.c_int(inner_iters), info))
+        self._ck(lib().mml_estimate(self._h, first, count, _p(_f64(exTlb).reshape(16)), _p(P), _p(Q), max_outer, inner_iters, info))
         return P, Q, list(info)
 
     def step(self, first, count, dR, dt, exTlb, thres_dist, gn_iters, x):
         x = _f64(x).reshape(count, 6).copy()
-        self._ck(lib().mml_step(self._h, C.c_int(first), C.c_int(count), _p(_f64(dR).reshape(count, 9)),
-                                _p(_f64(dt).reshape(count, 3)), _p(_f64(exTlb).reshape(16)), C.c_double(thres_dist),
-                                C.c_int(gn_iters), _p(x)))
+        self._ck(lib().mml_step(self._h, first, count, _p(_f64(dR).reshape(count, 9)), _p(_f64(dt).reshape(count, 3)), _p(_f64(exTlb).reshape(16)),
+                                thres_dist, gn_iters, _p(x)))
         return x
 
     # ---- multi-GPU (RCCL inside the C-ABI) ----
@@ -1726,7 +1682,7 @@ class Context:
         if len(comm_id) != COMM_ID_BYTES:
             raise ValueError("the communicator id is %d bytes" % COMM_ID_BYTES)
         buf = (C.c_uint8 * COMM_ID_BYTES).from_buffer_copy(bytes(comm_id))
-        self._ck(lib().mml_comm_init(self._h, C.c_int(n_ranks), C.c_int(rank), buf))
+        self._ck(lib().mml_comm_init(self._h, n_ranks, rank, buf))
 
     def comm_destroy(self):
         self._ck(lib().mml_comm_destroy(self._h))
@@ -1743,22 +1699,22 @@ class Context:
         xw = np.zeros((n_ranks * n_local, 6))
         opts = SolveOpts(max_iters, 1 if fixed else 0, huber, w_tan)
         summ, tim = SolveSummary(), WindowTiming()
-        self._ck(lib().mml_window_solve_allgather(self._h, C.c_int(first), C.c_int(n_local), _p(_f64(T_bl).reshape(16)),
-                                                  C.byref(opts), _p(x), _p(xw), C.byref(summ), C.byref(tim)))
+        self._ck(lib().mml_window_solve_allgather(self._h, first, n_local, _p(_f64(T_bl).reshape(16)), C.byref(opts), _p(x), _p(xw), C.byref(summ),
+                                                  C.byref(tim)))
         return x, xw, summ, tim
 
     def comm_broadcast_features(self, slot, root):
-        self._ck(lib().mml_comm_broadcast_features(self._h, C.c_int(slot), C.c_int(root)))
+        self._ck(lib().mml_comm_broadcast_features(self._h, slot, root))
 
     def comm_broadcast_local_map(self, root):
-        self._ck(lib().mml_comm_broadcast_local_map(self._h, C.c_int(root)))
+        self._ck(lib().mml_comm_broadcast_local_map(self._h, root))
 
     # ---- measurement ----
     def set_lanes(self, lanes):
-        self._ck(lib().mml_set_lanes(self._h, C.c_int(lanes)))
+        self._ck(lib().mml_set_lanes(self._h, lanes))
 
     def profile_enable(self, on=True):
-        self._ck(lib().mml_profile_enable(self._h, C.c_int(1 if on else 0)))
+        self._ck(lib().mml_profile_enable(self._h, 1 if on else 0))
 
     def profile_reset(self):
         self._ck(lib().mml_profile_reset(self._h))
@@ -1772,13 +1728,13 @@ class Context:
         """(redo, brk): points of the slot's last extraction recomputed with the full decision chain / finished as break-point
         candidates."""
         r, b = C.c_int(0), C.c_int(0)
-        self._ck(lib().mml_extract_queue_counts(self._h, C.c_int(slot), C.byref(r), C.byref(b)))
+        self._ck(lib().mml_extract_queue_counts(self._h, slot, C.byref(r), C.byref(b)))
         return r.value, b.value
 
     def issue_rate(self, kind=0, reps=3):
         """wave64 instructions per second of the device on v_fma_f32 (kind 0) / v_add_u32 (kind 1) chains (mml_issue_rate)."""
         r = C.c_double(0)
-        self._ck(lib().mml_issue_rate(self._h, C.c_int(kind), C.c_int(reps), C.byref(r)))
+        self._ck(lib().mml_issue_rate(self._h, kind, reps, C.byref(r)))
         return r.value
 
     def libm_f32(self, y, x):
@@ -1786,7 +1742,7 @@ class Context:
         y, x = np.ascontiguousarray(y, np.float32).ravel(), np.ascontiguousarray(x, np.float32).ravel()
         assert len(x) == len(y)
         o2, o1 = np.empty_like(x), np.empty_like(x)
-        self._ck(lib().mml_libm_f32(self._h, _p(y), _p(x), C.c_long(len(x)), _p(o2), _p(o1)))
+        self._ck(lib().mml_libm_f32(self._h, _p(y), _p(x), len(x), _p(o2), _p(o1)))
         return o2, o1
 
     _FIT_SHAPES = {0: (np.float64, 6, np.float64, 12), 1: (np.float64, 15, np.float64, 4), 2: (np.float32, 15, np.float64, 13),
@@ -1798,7 +1754,7 @@ class Context:
         ti, wi, to, wo = self._FIT_SHAPES[op]
         a = np.ascontiguousarray(items, ti).reshape(-1, wi)
         out = np.empty((len(a), wo), to)
-        self._ck(lib().mml_model_fit5(self._h, C.c_int(op), _p(a), C.c_long(len(a)), _p(out)))
+        self._ck(lib().mml_model_fit5(self._h, op, _p(a), len(a), _p(out)))
         return out
 
     def associate_far_count(self):
@@ -1811,19 +1767,19 @@ class Context:
         name = C.create_string_buffer(256)
         cus = C.c_int(0)
         mem = C.c_size_t(0)
-        self._ck(lib().mml_device_info(self._h, name, C.c_int(256), C.byref(cus), C.byref(mem)))
+        self._ck(lib().mml_device_info(self._h, name, 256, C.byref(cus), C.byref(mem)))
         return name.value.decode(), cus.value, mem.value
 
     def slot_digest(self, first, count):
         """(count, DIGEST_WORDS) uint64: one digest per slot and piece of state (mml_slot_digest; recomputable on the host from
         the download entry points, see `host_digest`)."""
         out = np.zeros((count, DIGEST_WORDS), np.uint64)
-        self._ck(lib().mml_slot_digest(self._h, C.c_int(first), C.c_int(count), _p(out)))
+        self._ck(lib().mml_slot_digest(self._h, first, count, _p(out)))
         return out
 
     def copy_bandwidth(self, nbytes=1 << 30, reps=10):
         g = C.c_double(0)
-        self._ck(lib().mml_copy_bandwidth(self._h, C.c_size_t(nbytes), C.c_int(reps), C.byref(g)))
+        self._ck(lib().mml_copy_bandwidth(self._h, nbytes, reps, C.byref(g)))
         return g.value
 
 
@@ -1865,8 +1821,8 @@ def scan_upload_wire_plan(velo_at, n_velo, point_step, offs, livox_at, n_livox, 
     bad_frame = the frame a refusal is about or -1.  A negative capacity is not checked."""
     _, va, nv, _, la, nl, lay = wire_batch_pack(None, velo_at, n_velo, point_step, offs, None, livox_at, n_livox, livox_record_bytes)
     span, bad = np.zeros(4, np.int64), C.c_int(-1)
-    rc = lib().mml_scan_upload_wire_plan(C.c_int(len(nv)), _p(va), _p(nv), *lay[:5], _p(la), _p(nl), lay[5], C.c_int(max_velo_points),
-                                         C.c_int(max_livox_points), _p(span), C.byref(bad))
+    rc = lib().mml_scan_upload_wire_plan(len(nv), _p(va), _p(nv), *lay[:5], _p(la), _p(nl), lay[5], max_velo_points, max_livox_points, _p(span),
+                                         C.byref(bad))
     return rc, span, bad.value
 
 
@@ -1876,7 +1832,7 @@ def wire_decode_host(velo_data, velo_at, n_velo, point_step, offs, livox_data, l
     vd, va, nv, ld, la, nl, lay = wire_batch_pack(velo_data, velo_at, n_velo, point_step, offs, livox_data, livox_at, n_livox, livox_record_bytes)
     tv, tl = int(np.maximum(nv, 0).sum()), int(np.maximum(nl, 0).sum())
     v, l = np.zeros((max(tv, 1), 4), np.float32), np.zeros(max(tl, 1), LIVOX_DTYPE)
-    rc = lib().mml_wire_decode_host(C.c_int(len(nv)), _p(vd), _p(va), _p(nv), *lay[:5], _p(ld), _p(la), _p(nl), lay[5], _p(v), _p(l))
+    rc = lib().mml_wire_decode_host(len(nv), _p(vd), _p(va), _p(nv), *lay[:5], _p(ld), _p(la), _p(nl), lay[5], _p(v), _p(l))
     if rc != MML_OK:
         raise MmlError(rc, "mml_wire_decode_host")
     return v[:tv], l[:tl]
@@ -1920,7 +1876,7 @@ def pose_ingest_plan(n_points, rows=None, **opts):
     """mml_pose_ingest_plan: the decisions of Context.pose_ingest alone, on the host (the same routine).  n_points (n, 6)."""
     _, n, r, o = pose_ingest_pack(None, n_points, rows, opts)
     out = np.zeros(max(len(n), 1), POSE_INGEST_ROW_DTYPE)
-    rc = lib().mml_pose_ingest_plan(C.c_int(len(n)), _p(n), _p(r), C.byref(o), _p(out))
+    rc = lib().mml_pose_ingest_plan(len(n), _p(n), _p(r), C.byref(o), _p(out))
     if rc != MML_OK:
         raise MmlError(rc, "mml_pose_ingest_plan")
     return out[:len(n)]
@@ -1940,7 +1896,7 @@ def imu_preintegrate(samples, bg, ba):
     """IMUIntegrator::PreIntegration: samples (n, 7) = gyro xyz, accel xyz (message units), dt."""
     smp = _f64(samples).reshape(-1, 7)
     out = ImuPreint()
-    rc = lib().mml_imu_preintegrate(_p(smp), C.c_int(len(smp)), _p(_f64(bg)), _p(_f64(ba)), C.byref(out))
+    rc = lib().mml_imu_preintegrate(_p(smp), len(smp), _p(_f64(bg)), _p(_f64(ba)), C.byref(out))
     if rc != MML_OK:
         raise MmlError(rc, "mml_imu_preintegrate")
     return out
@@ -1961,8 +1917,7 @@ def imu_preintegrate_batch(samples_list, bg, ba, ctx=None):
             raise ValueError("%s must be one vector or one per interval (%d, 3), not %s" % (name, n, b.shape))
         bias.append(np.ascontiguousarray(np.broadcast_to(b, (n, 3))))
     out = (ImuPreint * max(n, 1))()
-    rc = lib().mml_imu_preintegrate_batch(ctx._h if ctx is not None else None, C.c_int(n), _p(flat), _p(offsets), _p(bias[0]),
-                                          _p(bias[1]), out)
+    rc = lib().mml_imu_preintegrate_batch(ctx._h if ctx is not None else None, n, _p(flat), _p(offsets), _p(bias[0]), _p(bias[1]), out)
     if ctx is not None:
         ctx._ck(rc)
     elif rc != MML_OK:
@@ -2000,14 +1955,14 @@ def imu_fetch_raw(stream_or_msgs, t_start, t_end, bg=None, ba=None, ctx=None, wa
         ctx = stream_or_msgs._ctx if ctx is None else ctx
 
         def call(smp, cap, pre, dq):
-            return lib().mml_imu_fetch_batch(ctx._h, stream_or_msgs._h, C.c_int(n), _p(ts), _p(te), _p(bias[0]), _p(bias[1]), _p(rows),
-                                             _p(offsets), _p(smp), C.c_long(cap), pre, _p(dq))
+            return lib().mml_imu_fetch_batch(ctx._h, stream_or_msgs._h, n, _p(ts), _p(te), _p(bias[0]), _p(bias[1]), _p(rows), _p(offsets), _p(smp),
+                                             cap, pre, _p(dq))
     else:
         msgs = _f64(stream_or_msgs).reshape(-1, 7)
 
         def call(smp, cap, pre, dq):
-            return lib().mml_imu_fetch_host(_p(msgs) if len(msgs) else None, C.c_long(len(msgs)), C.c_int(n), _p(ts), _p(te), _p(bias[0]),
-                                            _p(bias[1]), _p(rows), _p(offsets), _p(smp), C.c_long(cap), pre, _p(dq))
+            return lib().mml_imu_fetch_host(_p(msgs) if len(msgs) else None, len(msgs), n, _p(ts), _p(te), _p(bias[0]), _p(bias[1]), _p(rows),
+                                            _p(offsets), _p(smp), cap, pre, _p(dq))
     out = dict(rows=rows[:n], offsets=offsets)
     if not want:
         return call(None, 0, None, None), out
@@ -2060,7 +2015,7 @@ def imu_predict_batch(exTlb, prev=None, pre=None, dq=None, ctx=None):
         q = _f64(dq).reshape(n, 4)
         out.update(gyro_Rb=np.zeros((n, 3, 3)), gyro_Rl=np.zeros((n, 3, 3)))
         gargs = [_p(q), _p(out["gyro_Rb"]), _p(out["gyro_Rl"])]
-    rc = lib().mml_imu_predict_batch(ctx._h if ctx is not None else None, C.c_int(n), _p(ex), *(args + gargs))
+    rc = lib().mml_imu_predict_batch(ctx._h if ctx is not None else None, n, _p(ex), *(args + gargs))
     if ctx is not None:
         ctx._ck(rc)
     elif rc != MML_OK:
@@ -2094,7 +2049,7 @@ def imu_gyro_integrate(samples, dq=(0.0, 0.0, 0.0, 1.0)):
     """IMUIntegrator::GyroIntegration: the gyro samples (n, 7) accumulated onto dq (x, y, z, w).  Returns the new dq."""
     smp = _f64(samples).reshape(-1, 7)
     q = _f64(dq).reshape(4).copy()
-    rc = lib().mml_imu_gyro_integrate(_p(smp), C.c_int(len(smp)), _p(q))
+    rc = lib().mml_imu_gyro_integrate(_p(smp), len(smp), _p(q))
     if rc != MML_OK:
         raise MmlError(rc, "mml_imu_gyro_integrate")
     return q
@@ -2127,8 +2082,8 @@ def lio_initialize(t, P, Q, V, bg, ba, samples, exTlb, pre=None):
             pin[i] = pre[i]
     pout = (ImuPreint * n)()
     res = LioInitResult()
-    rc = lib().mml_lio_initialize(C.c_int(n), _p(_f64(t).reshape(n)), _p(st["P"]), _p(st["Q"]), _p(st["V"]), _p(st["bg"]),
-                                  _p(st["ba"]), _p(flat), _p(offsets), _p(_f64(exTlb).reshape(16)), pin, pout, C.byref(res))
+    rc = lib().mml_lio_initialize(n, _p(_f64(t).reshape(n)), _p(st["P"]), _p(st["Q"]), _p(st["V"]), _p(st["bg"]), _p(st["ba"]), _p(flat), _p(offsets),
+                                  _p(_f64(exTlb).reshape(16)), pin, pout, C.byref(res))
     if rc != MML_OK:
         raise MmlError(rc, "mml_lio_initialize")
     pres = [None] + [ImuPreint.from_buffer_copy(pout[i]) for i in range(1, n)]
@@ -2169,8 +2124,8 @@ def lio_initialize_batch(segments, ctx=None):
                 pin[fo[s] + i] = segs[s][8][i] if segs[s][8] is not None else next(made)
     pout = (ImuPreint * max(F, 1))()
     res = (LioInitResult * max(n_seg, 1))()
-    rc = lib().mml_lio_initialize_batch(ctx._h if ctx is not None else None, C.c_int(n_seg), _p(fo), _p(t), _p(st["P"]), _p(st["Q"]),
-                                        _p(st["V"]), _p(st["bg"]), _p(st["ba"]), _p(flat), _p(so), _p(ex), pin, pout, res)
+    rc = lib().mml_lio_initialize_batch(ctx._h if ctx is not None else None, n_seg, _p(fo), _p(t), _p(st["P"]), _p(st["Q"]), _p(st["V"]),
+                                        _p(st["bg"]), _p(st["ba"]), _p(flat), _p(so), _p(ex), pin, pout, res)
     if ctx is not None:
         ctx._ck(rc)
     elif rc != MML_OK:
@@ -2191,8 +2146,7 @@ class FullWindowSolver:
     def __init__(self, W, max_iters=10, fixed=False, huber=0.0, w_tan=3e-4):
         self.W = W
         self._opts = SolveOpts(max_iters, 1 if fixed else 0, huber, w_tan)
-        lib().mml_fullwindow_create.restype = C.c_void_p
-        self._h = C.c_void_p(lib().mml_fullwindow_create(C.c_int(W), C.byref(self._opts)))
+        self._h = C.c_void_p(lib().mml_fullwindow_create(W, C.byref(self._opts)))
         if not self._h:
             raise MmlError(MML_ERR_INVALID, "mml_fullwindow_create failed")
 
@@ -2202,7 +2156,7 @@ class FullWindowSolver:
         return rc
 
     def set_imu(self, f, pre, gravity):
-        self._ck(lib().mml_fullwindow_set_imu(self._h, C.c_int(f), C.byref(pre), _p(_f64(gravity))), "set_imu")
+        self._ck(lib().mml_fullwindow_set_imu(self._h, f, C.byref(pre), _p(_f64(gravity))), "set_imu")
 
     def set_prior(self, prior):
         self._ck(lib().mml_fullwindow_set_prior(self._h, C.byref(prior) if prior is not None else None), "set_prior")
@@ -2220,7 +2174,7 @@ class FullWindowSolver:
         T = _f64(T_bl).reshape(16)
         s = SolveSummary()
         ev = C.c_int(0)
-        ctx._ck(lib().mml_fullwindow_solve(ctx._h, self._h, C.c_int(first_slot), _p(T), _p(x), C.byref(s), C.byref(ev)))
+        ctx._ck(lib().mml_fullwindow_solve(ctx._h, self._h, first_slot, _p(T), _p(x), C.byref(s), C.byref(ev)))
         return x, s, ev.value
 
     def summary(self):
@@ -2277,8 +2231,7 @@ def fullwindow_solve_batch(ctx, solvers, first_slots, T_bl, xs, records0=False):
     summ = (SolveSummary * max(n, 1))()
     ev = np.zeros(max(n, 1), np.int32)
     rec = np.zeros((max(n, 1), NEQ_RECORD_DOUBLES)) if records0 else None
-    ctx._ck(lib().mml_fullwindow_solve_batch(ctx._h, C.c_int(n), handles, _p(first), _p(_f64(T_bl).reshape(16)), _p(x), summ, _p(ev),
-                                             _p(rec)))
+    ctx._ck(lib().mml_fullwindow_solve_batch(ctx._h, n, handles, _p(first), _p(_f64(T_bl).reshape(16)), _p(x), summ, _p(ev), _p(rec)))
     out = ([x[w, :15 * fw.W].reshape(fw.W, 15).copy() for w, fw in enumerate(solvers)], list(summ)[:n], [int(e) for e in ev[:n]])
     return out + (rec[:n],) if records0 else out
 
@@ -2300,8 +2253,7 @@ def fullwindow_marginalize_batch(ctx, solvers, first_slots, T_bl, xs):
     handles = (C.c_void_p * max(n, 1))(*[fw._h.value if isinstance(fw._h, C.c_void_p) else fw._h for fw in solvers])
     first = np.ascontiguousarray(list(first_slots) + [0] * (n == 0), dtype=np.int32)
     out = (Prior * max(n, 1))()
-    rc = lib().mml_fullwindow_marginalize_batch(ctx._h if ctx is not None else None, C.c_int(n), handles, _p(first),
-                                                _p(_f64(T_bl).reshape(16)), _p(x), out)
+    rc = lib().mml_fullwindow_marginalize_batch(ctx._h if ctx is not None else None, n, handles, _p(first), _p(_f64(T_bl).reshape(16)), _p(x), out)
     if ctx is not None:
         ctx._ck(rc)
     elif rc != MML_OK:
@@ -2325,7 +2277,7 @@ def marginalize_dense(ctx, A, b):
     b = np.ascontiguousarray(b.reshape(-1, 30))
     n = len(A)
     J, r0 = np.zeros((n, 15, 15)), np.zeros((n, 15))
-    rc = lib().mml_marginalize_dense(ctx._h if ctx is not None else None, C.c_long(n), _p(A), _p(b), _p(J), _p(r0))
+    rc = lib().mml_marginalize_dense(ctx._h if ctx is not None else None, n, _p(A), _p(b), _p(J), _p(r0))
     if ctx is not None:
         ctx._ck(rc)
     elif rc != MML_OK:
@@ -2358,8 +2310,7 @@ def tr_replay(ctx, variant, scripts):
         rec[k, :r.shape[0], :W] = r
     xc, dig = np.zeros((n, rmax, 48)), np.zeros((n, rmax, TR_DIGEST_DOUBLES))
     digi = np.zeros((n, rmax, TR_DIGEST_INTS), np.int32)
-    rc = lib().mml_debug_tr_replay(ctx._h if ctx is not None else None, C.c_int(variant), C.c_int(n), C.c_int(rmax), _p(hdr), _p(x0),
-                                   _p(rec), _p(xc), _p(dig), _p(digi))
+    rc = lib().mml_debug_tr_replay(ctx._h if ctx is not None else None, variant, n, rmax, _p(hdr), _p(x0), _p(rec), _p(xc), _p(dig), _p(digi))
     if ctx is not None:
         ctx._ck(rc)
     elif rc != MML_OK:
@@ -2405,8 +2356,8 @@ def fw_replay(ctx, variant, scripts):
     rows = int(hdr[:, 3].sum())
     xc, dig = np.zeros((max(rows, 1), 120)), np.zeros((max(rows, 1), FW_DIGEST_DOUBLES))
     digi = np.zeros((max(rows, 1), TR_DIGEST_INTS), np.int32)
-    rc = lib().mml_debug_fw_replay(ctx._h if ctx is not None else None, C.c_int(variant), C.c_int(n), _p(hdr), _p(x0), _p(off),
-                                   _p(rounds), C.c_longlong(pos), _p(xc), _p(dig), _p(digi))
+    rc = lib().mml_debug_fw_replay(ctx._h if ctx is not None else None, variant, n, _p(hdr), _p(x0), _p(off), _p(rounds), pos, _p(xc), _p(dig),
+                                   _p(digi))
     if ctx is not None:
         ctx._ck(rc)
     elif rc != MML_OK:
@@ -2427,7 +2378,7 @@ class WindowSolver:
     def __init__(self, W, max_iters=10, fixed=False, huber=0.0, w_tan=3e-4):
         self.W = W
         self._opts = SolveOpts(max_iters, 1 if fixed else 0, huber, w_tan)
-        self._h = lib().mml_window_solver_create(C.c_int(W), C.byref(self._opts))
+        self._h = lib().mml_window_solver_create(W, C.byref(self._opts))
         if not self._h:
             raise MmlError(MML_ERR_INVALID, "mml_window_solver_create failed")
 
@@ -2467,3 +2418,18 @@ def pack_record(H, g, cost, n_line_used=0, n_plane_used=0):
     rec[28] = n_line_used
     rec[29] = n_plane_used
     return rec
+
+
+# every struct of include/mmloam_hip.h that the package mirrors -> its ctypes.Structure, its numpy dtype, or both
+# (tests/test_abi_structs.py compiles the header and holds each mirror's size and field offsets against the C compiler's)
+ABI_STRUCTS = {
+    "mml_livox_point": LIVOX_DTYPE, "mml_config": Config, "mml_world_map_info": WorldMapInfo, "mml_velo_fov_info": VELO_FOV_INFO_DTYPE,
+    "mml_livox_stream_state": LivoxStreamState, "mml_union_frame": UNION_FRAME_DTYPE, "mml_time_offset_estimate_row": TOFS_ROW_DTYPE,
+    "mml_gicp_info": GicpInfo, "mml_gicp_opts": GicpOpts, "mml_calib_info": CalibInfo, "mml_scan_info": ScanInfo,
+    "mml_assoc_stats": AssocStats, "mml_solve_opts": SolveOpts, "mml_solve_summary": SolveSummary, "mml_estimate_info": EstimateInfo,
+    "mml_wm_assoc_opts": WmAssocOpts, "mml_wm_localize_opts": WmLocalizeOpts, "mml_wm_score": (WmScore, WM_SCORE_DT),
+    "mml_wm_score_opts": WmScoreOpts, "mml_wm_reloc_opts": WmRelocOpts, "mml_wm_reloc_info": WmRelocInfo,
+    "mml_window_timing": WindowTiming, "mml_profile": Profile, "mml_imu_preint": ImuPreint, "mml_prior": Prior,
+    "mml_lio_init_result": LioInitResult, "mml_imu_stream_state": ImuStreamState, "mml_imu_interval": IMU_INTERVAL_DTYPE,
+    "mml_pose_ingest_opts": PoseIngestOpts, "mml_pose_ingest_row": POSE_INGEST_ROW_DTYPE, "mml_gicp_debug": GicpDebug,
+}
