@@ -11,6 +11,7 @@ origin 0, 21 cells per axis; they lie farther than the gate from every query.  T
 import numpy as np
 import pytest
 
+from assoc_cases import _anchors, _cells, _centre, _dummy, _five
 from conftest import pose_to_x
 
 pytestmark = pytest.mark.gpu
@@ -23,43 +24,6 @@ def ctx(M):
     c = M.Context(max_scans=12)
     yield c
     c.close()
-
-
-def _cells(ctx):
-    """The grid cells of the two kinds as the library derives them: the configured cell, else 5 x leaf in float."""
-    cfg = ctx.cfg
-    f = np.float32
-    return (float(f(cfg.cell_corner) if cfg.cell_corner > 0 else f(5.0) * f(cfg.leaf_corner)),
-            float(f(cfg.cell_surf) if cfg.cell_surf > 0 else f(5.0) * f(cfg.leaf_surf)))
-
-
-def _anchors(c, queries, keep_off, dims=(20, 20, 20)):
-    """Corners and edge midpoints of the box [0, dims * c], without those nearer than keep_off to a query."""
-    g = [np.array([0.0, d / 2.0, float(d)]) * c for d in dims]
-    pts = np.array([[x, y, z] for i, x in enumerate(g[0]) for j, y in enumerate(g[1]) for k, z in enumerate(g[2])
-                    if (i == 1) + (j == 1) + (k == 1) <= 1])
-    q = np.asarray(queries, np.float64).reshape(-1, 3)
-    far = np.all(np.linalg.norm(pts[:, None, :] - q[None], axis=2) > keep_off, axis=1)
-    pts = pts[far]
-    assert np.all(pts.min(0) == 0) and np.all(pts.max(0) == np.array(dims) * c) and len(pts) >= 17
-    return pts
-
-
-def _five(kind, base, step, a, b=None):
-    """Five points at `base` and beyond along unit axis vectors: a line along a (corner kind), a quincunx in the a / b plane
-    (surf kind).  base + multiples of step: the other four are base + step * (...)."""
-    base, a = np.asarray(base, np.float64), np.asarray(a, np.float64)
-    if kind == 0:
-        return np.array([base + j * step * a for j in range(5)])
-    b = np.asarray(b, np.float64)
-    return np.array([base, base + step * (a + b), base + step * (a - b), base + 2 * step * (a + b), base + 2 * step * (a - b)])
-
-
-def _dummy(c):
-    """A map and one feature for the kind a case does not look at."""
-    q = np.array([[10.5 * c, 10.5 * c, 10.5 * c]])
-    faces = np.array([[10, 10, 0], [10, 10, 20], [10, 0, 10], [10, 20, 10], [0, 10, 10], [20, 10, 10]]) * c
-    return np.concatenate([_anchors(c, q, 0.0), faces]), q
 
 
 def _run(ctx, O, maps, feats, thres):
@@ -101,10 +65,6 @@ def _run_kind(ctx, O, kind, cmap, feats, thres):
     maps, fts = [dm, dm], [df, df]
     maps[kind], fts[kind] = cmap, feats
     return _run(ctx, O, maps, fts, thres)[kind]
-
-
-def _centre(c):
-    return np.array([10.5, 10.5, 10.5]) * c
 
 
 @pytest.mark.parametrize("kind", [0, 1])
