@@ -1065,6 +1065,57 @@ int mml_world_map_relocalize(mml_ctx* ctx, int first_slot, int count, const int*
                              double* P, double* Q /* in: seed body poses; out: result */, const mml_wm_reloc_opts* opts,
                              mml_wm_reloc_info* info /* count entries or NULL */);
 
+/* ---- eviction: voxels leave the world map by box and by count, their rows handed back --------------------------------------
+ * mml_world_map_evict: one rule per map named, n_rules maps in ONE device chain; the decision per voxel is
+ * csrc/world_map_evict.h's mml_wme_goes (host and device, integers only): the box test by mode -- OUTSIDE: a voxel goes unless
+ * lo[a] <= index[a] < hi[a] on all three axes, INSIDE: it goes if so, NOBOX: the box is not read -- OR count < min_count.  A box
+ * with lo[a] >= hi[a] on some axis is empty: OUTSIDE then empties the map, INSIDE evicts nothing by the box.
+ *   maps not named     keep every bit of theirs.
+ *   survivors          keep sum, count and moments bit for bit; which table position holds them may change, and nothing a call
+ *                      returns depends on that.  Every survivor is found by every later call (add, import, associate, score); an
+ *                      evicted voxel is not, and an add into its place starts from zero: the table is rebuilt (the survivors of
+ *                      ALL maps taken out, the keys cleared, the survivors put back by claim, as mml_world_map_reset does for one
+ *                      map), no free marker is stored into a probe chain.
+ *   rows               the evicted voxels in ascending packed-key order -- map, then k, j, i --, so one map's rows are one run in
+ *                      the order of mml_world_map_export, beginning at info[r].first_row, in the layout mml_world_map_import
+ *                      takes (ijk, stored sums, counts, the 12 stored moments on a surfel map); out_map[row] = the map.  Evicting a
+ *                      voxel and importing its row leaves every export what it was, bit for bit.  out_map, out_ijk, out_sums,
+ *                      out_counts and out_moments all NULL with capacity 0: the voxels are dropped, nothing is handed back.
+ *   counts, version    mml_world_map_size is right afterwards; the surfel cache is marked stale exactly when the table is
+ *                      written: not by a dry run, not by a call that evicts nothing (the table is untouched), not by a refusal.
+ *   MML_WM_EVICT_DRY   counts only (info, *n_evicted): nothing but scratch is written, out arrays and capacity are not used.
+ * Host synchronisations: ONE, the read-back of the counters behind the marking pass -- the refusal point: MML_ERR_CAPACITY naming
+ * both figures when rows are wanted and capacity < the voxels to evict, info and *n_evicted filled, the table bit for bit what it
+ * was -- and a second one only when rows are handed back (the copies up).  The rebuild costs a pass over the whole table however
+ * few voxels go.  Scratch per voxel of capacity_voxels: 12 bytes for a dry run, 32 (80 on a surfel map) when the rows are dropped,
+ * 44 (92) when they are handed back, grow-only, MML_ERR_HIP before any launch when it cannot grow.
+ * Refused before anything is written, the message names the rule: MML_ERR_STATE without a world map; MML_ERR_INVALID for NULL
+ * rules, n_rules outside 1 .. n_maps, a map outside [0, n_maps), a map named twice, an unknown mode, min_count < 0, unknown flag
+ * bits, capacity < 0, out arrays partly NULL (or a capacity without them), out_moments given on a plain map or missing on a
+ * surfel map when rows are wanted.
+ * mml_wm_index_box (host, no context): the index box of a metric one with mml_world_map_add's arithmetic (inv = 1.0f / leaf, the
+ * product in float, floor): lo = index(lo_xyz), hi = index(hi_xyz) + 1, each clamped to [-2^17, 2^17].  MML_ERR_INVALID for a
+ * coordinate or a leaf that is not finite, a leaf <= 0, a NULL array. */
+#ifndef MML_WM_EVICT_RULE_DEFINED
+#define MML_WM_EVICT_RULE_DEFINED
+#define MML_WM_EVICT_OUTSIDE 0   /* voxels outside the box go */
+#define MML_WM_EVICT_INSIDE  1   /* voxels inside the box go  */
+#define MML_WM_EVICT_NOBOX   2   /* the box is not read; only min_count decides */
+typedef struct {
+    int map;            /* 0 .. n_maps-1; a map may be named by at most one rule of a call */
+    int mode;
+    int lo[3], hi[3];   /* voxel indices i, j, k: inside means lo[a] <= index[a] < hi[a] on all three axes */
+    int min_count;      /* a voxel whose point count is < min_count goes as well; 0 or 1: none does */
+} mml_wm_evict_rule;
+#endif
+typedef struct { long n_before, n_evicted, n_kept, first_row; } mml_wm_evict_info;   /* per rule */
+#define MML_WM_EVICT_DRY 1u      /* count only: nothing is written anywhere on the device but scratch */
+int mml_wm_index_box(float leaf, const float lo_xyz[3], const float hi_xyz[3], int lo[3], int hi[3]);
+int mml_world_map_evict(mml_ctx* ctx, int n_rules, const mml_wm_evict_rule* rules, unsigned flags,
+                        mml_wm_evict_info* info /* n_rules, may be NULL */, long capacity /* rows the out arrays hold */,
+                        int* out_map, int* out_ijk /* n x 3 */, float* out_sums /* n x 4 */, int* out_counts,
+                        float* out_moments /* n x 12; NULL on a plain map */, long* n_evicted /* may be NULL */);
+
 /* ---- the benchmarked step ---------------------------------------------------------------------------
  * One pass of the hot path over slots [first, first+count) with inputs already uploaded:
  * extract -> undistort -> downsample -> associate (1 pass, thres_dist) -> `gn_iters` trust-region

@@ -156,6 +156,8 @@ def _signatures():
         "mml_wm_score_opts_default": (None, [P, F]), "mml_world_map_score": (I, [P, I, I, P, I, P, P, P]),
         "mml_wm_reloc_opts_default": (None, [P, F]), "mml_wm_pose_grid": (I, [P, D, D, D, D, D, D, P, L, P]),
         "mml_wm_body_pose": (I, [P, P, P, P]), "mml_wm_lidar_pose": (I, [P, P, P, P]), "mml_world_map_relocalize": (I, [P, I, I, P, P, P, P, P, P]),
+        # ---- eviction: voxels leave the world map by box and by count, their rows handed back
+        "mml_wm_index_box": (I, [F, P, P, P, P]), "mml_world_map_evict": (I, [P, I, P, U, P, L, P, P, P, P, P, P]),
         # ---- the benchmarked step
         "mml_step": (I, [P, I, I, P, P, P, D, I, P]),
         # ---- multi-GPU window solve (one frame per GPU)
@@ -403,6 +405,35 @@ class WmRelocInfo(C.Structure):
     """mml_wm_reloc_info"""
     _fields_ = [("best", WmScore), ("second", WmScore), ("final", WmScore), ("n_hyp_scored", C.c_long), ("T_start", C.c_double * 16),
                 ("est", EstimateInfo)]
+
+
+# ... and eviction from it (include/mmloam_hip.h, "eviction")
+WM_EVICT_OUTSIDE, WM_EVICT_INSIDE, WM_EVICT_NOBOX = 0, 1, 2   # mml_wm_evict_rule.mode
+MML_WM_EVICT_DRY = 1                                          # the flag of mml_world_map_evict
+
+
+class WmEvictRule(C.Structure):
+    """mml_wm_evict_rule"""
+    _fields_ = [("map", C.c_int), ("mode", C.c_int), ("lo", C.c_int * 3), ("hi", C.c_int * 3), ("min_count", C.c_int)]
+
+
+class WmEvictInfo(C.Structure):
+    """mml_wm_evict_info"""
+    _fields_ = [(k, C.c_long) for k in ("n_before", "n_evicted", "n_kept", "first_row")]
+
+
+def wm_evict_rule(map, mode=WM_EVICT_NOBOX, lo=(0, 0, 0), hi=(0, 0, 0), min_count=0):
+    """One mml_wm_evict_rule: the voxels of `map` outside / inside the index box [lo, hi) go (mode), and those below min_count"""
+    return WmEvictRule(int(map), int(mode), (C.c_int * 3)(*[int(v) for v in lo]), (C.c_int * 3)(*[int(v) for v in hi]), int(min_count))
+
+
+def wm_index_box(leaf, lo_xyz, hi_xyz):
+    """mml_wm_index_box: the index box (lo, hi), two (3,) int32, of the metric box [lo_xyz, hi_xyz] in a map of leaf size `leaf`"""
+    lo, hi = np.zeros(3, np.int32), np.zeros(3, np.int32)
+    rc = lib().mml_wm_index_box(float(leaf), _p(_f32(lo_xyz).reshape(3)), _p(_f32(hi_xyz).reshape(3)), _p(lo), _p(hi))
+    if rc != MML_OK:
+        raise MmlError(rc, "mml_wm_index_box: refused (a coordinate or the leaf not finite, leaf <= 0)")
+    return lo, hi
 
 
 def wm_score_opts(leaf, **over):
@@ -1479,6 +1510,35 @@ class Context:
                                                 C.byref(opts), info))
         return P, Q, list(info)
 
+    def world_map_index_box(self, lo_xyz, hi_xyz):
+        """wm_index_box for this context's world map: the index box (lo, hi) of the metric box [lo_xyz, hi_xyz]."""
+        return wm_index_box(self._wm_leaf, lo_xyz, hi_xyz)
+
+    def world_map_evict(self, rules, rows=True, dry=False):
+        """mml_world_map_evict: rules, a list of WmEvictRule (wm_evict_rule(map, mode, lo, hi, min_count)), at most one per map, in
+        ONE call.  Returns the list of WmEvictInfo, one per rule; with rows=True (and not dry) also {map: dict(ijk, sums, counts,
+        moments)} of the evicted voxels per named map, each as world_map_import takes it (world_map_import(map, **rows[map])); the
+        arrays are sized by a dry run first.  rows=False drops the evicted voxels.  dry=True: counts only, nothing is written."""
+        L = lib()
+        arr = (WmEvictRule * len(rules))(*rules)
+        info = (WmEvictInfo * len(rules))()
+        n = C.c_long(0)
+        if dry or not rows:
+            self._ck(L.mml_world_map_evict(self._h, len(rules), arr, MML_WM_EVICT_DRY if dry else 0, info, 0, None, None, None, None, None,
+                                           C.byref(n)))
+            return list(info)
+        self._ck(L.mml_world_map_evict(self._h, len(rules), arr, MML_WM_EVICT_DRY, info, 0, None, None, None, None, None, C.byref(n)))
+        cap = max(n.value, 1)
+        omap, ijk, sums, counts = np.zeros(cap, np.int32), np.zeros((cap, 3), np.int32), np.zeros((cap, 4), np.float32), np.zeros(cap, np.int32)
+        mom = np.zeros((cap, 12), np.float32) if getattr(self, "_wm_surfels", False) else None
+        self._ck(L.mml_world_map_evict(self._h, len(rules), arr, 0, info, cap, _p(omap), _p(ijk), _p(sums), _p(counts), _p(mom), C.byref(n)))
+        out = {}
+        for r, i in zip(rules, info):
+            a, b = i.first_row, i.first_row + i.n_evicted
+            out[int(r.map)] = dict(ijk=ijk[a:b].copy(), sums=sums[a:b].copy(), counts=counts[a:b].copy(),
+                                   moments=None if mom is None else mom[a:b].copy())
+        return list(info), out
+
     # ---- map banks: further local maps, every slot matched against its own (include/mmloam_hip.h, "map banks") ----
     def map_banks(self, n):
         """Creates n banks (n = 0: releases them and unbinds every slot)."""
@@ -2429,6 +2489,7 @@ ABI_STRUCTS = {
     "mml_assoc_stats": AssocStats, "mml_solve_opts": SolveOpts, "mml_solve_summary": SolveSummary, "mml_estimate_info": EstimateInfo,
     "mml_wm_assoc_opts": WmAssocOpts, "mml_wm_localize_opts": WmLocalizeOpts, "mml_wm_score": (WmScore, WM_SCORE_DT),
     "mml_wm_score_opts": WmScoreOpts, "mml_wm_reloc_opts": WmRelocOpts, "mml_wm_reloc_info": WmRelocInfo,
+    "mml_wm_evict_rule": WmEvictRule, "mml_wm_evict_info": WmEvictInfo,
     "mml_window_timing": WindowTiming, "mml_profile": Profile, "mml_imu_preint": ImuPreint, "mml_prior": Prior,
     "mml_lio_init_result": LioInitResult, "mml_imu_stream_state": ImuStreamState, "mml_imu_interval": IMU_INTERVAL_DTYPE,
     "mml_pose_ingest_opts": PoseIngestOpts, "mml_pose_ingest_row": POSE_INGEST_ROW_DTYPE, "mml_gicp_debug": GicpDebug,

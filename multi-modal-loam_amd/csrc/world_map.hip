@@ -35,6 +35,11 @@
 // mml_world_map_export is a fourth gather of that chain (the stored sums, counts, moments and the sorted keys as voxel indices);
 // mml_world_map_import checks its rows on the host, looks all of them up in one launch (k_wm_import_find), refuses at the add's
 // refusal point -- one read-back, only scratch written -- and then claims and stores them, one lane per voxel (k_wm_import_put).
+// mml_world_map_evict removes voxels by rule (world_map_evict.h: an index box and a minimum count per map named): k_wm_evict_mark
+// walks the table once and splits the occupied positions into an evicted and a survivor list; one read-back of the counters, the
+// refusal point; then the evicted rows are sorted and gathered (k_wm_raw, k_wm_moments), the survivors of every map taken out
+// (k_wm_take), the keys cleared and the survivors put back by claim (k_wm_evict_put) -- reset(map)'s rebuild, since a position
+// inside a probe chain cannot be freed -- and the rows copied up behind a second synchronisation when they are wanted.
 //
 // THE SURFEL CACHE (mml_wm_cache_ready, for mml_world_map_score): one float4 per table position, (nx, ny, nz, planarity) of the
 // position's surfel, 16 bytes per position more (92 instead of 76), allocated in the map's memory group by the first call that
@@ -53,6 +58,7 @@
 #include "fused_view_dev.h"
 #include "voxel_sort_dev.h"
 #include "world_map_assoc.h"
+#include "world_map_evict.h"
 
 namespace {
 #include "eig3_dev.h"
@@ -326,6 +332,93 @@ __global__ __launch_bounds__(256) void k_wm_import_put(const unsigned long long*
     }
     wm_count(map_n + map, at >= 0);
     wm_count(map_n + n_maps, at >= 0);
+}
+
+// evict: every table position once.  An occupied position goes, with its key, to the evicted list (the front of keys / vals, from
+// index 0 up) when its map is named by a rule and mml_wme_goes says so (world_map_evict.h), else to the survivor list (the back of
+// the same arrays, from index cap - 1 down: the two lists together hold at most `cap` = capacity_voxels entries).  One wave takes
+// 64 consecutive positions per pass, 512 contiguous bytes of keys; the count is loaded only under a rule with min_count > 1.  One
+// atomic per wave and list (wm_count's ballot), one per wave and rule met for n_before / n_evicted.  The order inside both lists
+// depends on scheduling.  counters: WME_EVICTED, WME_KEPT, then (n_before, n_evicted) per rule.
+enum { WME_EVICTED, WME_KEPT, WME_RULES };
+__global__ __launch_bounds__(256) void k_wm_evict_mark(const unsigned long long* __restrict__ tab, unsigned long long slots,
+                                                       const int* __restrict__ count, const int* __restrict__ rule_of, int n_maps,
+                                                       const mml_wm_evict_rule* __restrict__ rules, int cap, int* __restrict__ counters,
+                                                       unsigned long long* __restrict__ keys, unsigned* __restrict__ vals) {
+    const unsigned lane = threadIdx.x & 63u;
+    const unsigned long long below = (1ull << lane) - 1;
+    // (the loop is wave-uniform: all 64 lanes stay in it, a lane past the table's end holds the free marker)
+    for (unsigned long long base = (unsigned long long)blockIdx.x * blockDim.x + (threadIdx.x - lane); base < slots;
+         base += (unsigned long long)gridDim.x * blockDim.x) {
+        const unsigned long long h = base + lane;
+        const unsigned long long key = h < slots ? tab[h] : MML_WM_EMPTY;
+        const bool held = key != MML_WM_EMPTY;
+        int rule = -1;
+        bool goes = false;
+        if (held) {
+            int map, i, j, k;
+            mml_wm_unkey(key, map, i, j, k);
+            if (map < n_maps) rule = rule_of[map];
+            if (rule >= 0) {
+                const mml_wm_evict_rule R = rules[rule];
+                goes = mml_wme_goes(R, i, j, k, R.min_count > 1 ? count[h] : 1);
+            }
+        }
+        const unsigned long long ev = __ballot(goes), kp = __ballot(held && !goes);
+        int b_ev = 0, b_kp = 0;
+        if (lane == 0) {
+            if (ev) b_ev = atomicAdd(counters + WME_EVICTED, __popcll(ev));
+            if (kp) b_kp = atomicAdd(counters + WME_KEPT, __popcll(kp));
+        }
+        b_ev = __shfl(b_ev, 0);
+        b_kp = __shfl(b_kp, 0);
+        if (goes) {
+            const int at = b_ev + __popcll(ev & below);
+            if (at < cap) {
+                keys[at] = key;
+                vals[at] = (unsigned)h;
+            }
+        } else if (held) {
+            const int at = b_kp + __popcll(kp & below);
+            if (at < cap) {
+                keys[cap - 1 - at] = key;
+                vals[cap - 1 - at] = (unsigned)h;
+            }
+        }
+        unsigned long long todo = __ballot(rule >= 0);  // the named maps' voxels of this pass, rule by rule
+        while (todo) {
+            const int lead = __ffsll((long long)todo) - 1;
+            const int r = __shfl(rule, lead);
+            const unsigned long long same = __ballot(rule == r), gone = __ballot(rule == r && goes);
+            if ((int)lane == lead) {
+                atomicAdd(counters + WME_RULES + 2 * r, __popcll(same));
+                if (gone) atomicAdd(counters + WME_RULES + 2 * r + 1, __popcll(gone));
+            }
+            todo &= ~same;
+        }
+    }
+}
+// ... and, the evicted rows gathered, the survivors taken (k_wm_take) and the keys cleared: the survivors back by claim, as
+// k_wm_reinsert; the first workgroup writes the named maps' counts (n_before - n_evicted of their rules) and the new total
+__global__ __launch_bounds__(256) void k_wm_evict_put(const unsigned long long* __restrict__ keys, int n, const float4* __restrict__ s_sum,
+                                                      const int* __restrict__ s_n, unsigned long long* __restrict__ tab,
+                                                      unsigned long long slots, float4* __restrict__ sum, int* __restrict__ count,
+                                                      int* __restrict__ map_n, int n_maps, const mml_wm_evict_rule* __restrict__ rules,
+                                                      const int* __restrict__ per_rule, int n_rules, WmMom M, WmMom S) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (blockIdx.x == 0)
+        for (int r = threadIdx.x; r < n_rules; r += blockDim.x) map_n[rules[r].map] = per_rule[2 * r] - per_rule[2 * r + 1];
+    if (i == 0) map_n[n_maps] = n;
+    if (i >= n) return;
+    const long long at = wm_claim(tab, slots, keys[i]);
+    if (at < 0) return;
+    sum[at] = s_sum[i];
+    count[at] = s_n[i];
+    if (M.m0) {
+        M.m0[at] = S.m0[i];
+        M.m1[at] = S.m1[i];
+        M.m2[at] = S.m2[i];
+    }
 }
 
 int wm_enter(mml_ctx* ctx, const char* who) {
@@ -707,6 +800,133 @@ int mml_world_map_import(mml_ctx* ctx, int map, long n, const int* ijk, const fl
                        W.count, W.map_n, W.n_maps, map, wm_mom(W));
     MML_HIP(hipGetLastError());
     MML_HIP(hipStreamSynchronize(s));  // (the caller's arrays and the key vector were the copies' sources)
+    return MML_OK;
+}
+
+int mml_wm_index_box(float leaf, const float* lo_xyz, const float* hi_xyz, int* lo, int* hi) {
+    if (!lo_xyz || !hi_xyz || !lo || !hi) return MML_ERR_INVALID;
+    return mml_wme_index_box(leaf, lo_xyz, hi_xyz, lo, hi) == 0 ? MML_OK : MML_ERR_INVALID;
+}
+
+// Scratch per voxel of capacity_voxels (the lists are sized before the walk has counted): 8 + 4 for the two lists, which share
+// one pair of arrays; past a dry run 16 + 4 for the rows taken out (the evicted ones in front, the survivors behind them) and,
+// on a surfel map, 48 for their moments; 8 + 4 more for the sorted pairs when rows are handed back.
+int mml_world_map_evict(mml_ctx* ctx, int n_rules, const mml_wm_evict_rule* rules, unsigned flags, mml_wm_evict_info* info, long capacity,
+                        int* out_map, int* out_ijk, float* out_sums, int* out_counts, float* out_moments, long* n_evicted) {
+    int rc = wm_enter(ctx, "mml_world_map_evict");
+    if (rc != MML_OK) return rc;
+    mml_ctx::WorldMap& W = ctx->world;
+    MML_REQUIRE(rules != nullptr, MML_ERR_INVALID, "mml_world_map_evict: null rules");
+    if (n_rules < 1 || n_rules > W.n_maps) return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_evict: n_rules %d outside 1..%d (n_maps)", n_rules, W.n_maps);
+    if (flags & ~MML_WM_EVICT_DRY)
+        return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_evict: unknown flag bits 0x%x (MML_WM_EVICT_DRY is 0x%x)", flags & ~MML_WM_EVICT_DRY, MML_WM_EVICT_DRY);
+    if (capacity < 0) return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_evict: capacity %ld < 0", capacity);
+    std::vector<int> rule_of((size_t)W.n_maps, -1);
+    for (int r = 0; r < n_rules; ++r) {
+        const mml_wm_evict_rule& R = rules[r];
+        if (R.map < 0 || R.map >= W.n_maps) return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_evict: rule %d: map %d outside [0, %d)", r, R.map, W.n_maps);
+        if (rule_of[(size_t)R.map] >= 0)
+            return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_evict: rule %d: map %d is named by rule %d already", r, R.map, rule_of[(size_t)R.map]);
+        if (R.mode != MML_WM_EVICT_OUTSIDE && R.mode != MML_WM_EVICT_INSIDE && R.mode != MML_WM_EVICT_NOBOX)
+            return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_evict: rule %d: unknown mode %d", r, R.mode);
+        if (R.min_count < 0) return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_evict: rule %d: min_count %d < 0", r, R.min_count);
+        rule_of[(size_t)R.map] = r;
+    }
+    const bool rows = out_ijk != nullptr, dry = (flags & MML_WM_EVICT_DRY) != 0;
+    if (rows) {
+        if (!out_map || !out_sums || !out_counts)
+            return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_evict: out_map, out_ijk, out_sums and out_counts are given together or not at all");
+        if ((out_moments != nullptr) != W.surfels)
+            return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_evict: out_moments must be %s", W.surfels ? "given: the map holds surfels" : "NULL: the map is a plain one");
+    } else {
+        if (out_map || out_sums || out_counts || out_moments)
+            return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_evict: out_map, out_ijk, out_sums and out_counts are given together or not at all");
+        if (capacity != 0) return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_evict: capacity %ld without out arrays (0 drops the rows)", capacity);
+    }
+    hipStream_t s = MML_STREAM(ctx);
+    // scratch and tables, all before the first launch
+    const size_t cap = (size_t)W.capacity;
+    const bool sorted = rows && !dry;
+    MmlCarve<16> c;
+    const MmlField<unsigned long long> f_keys = c.take<unsigned long long>(cap);
+    const MmlField<unsigned> f_vals = c.take<unsigned>(cap);
+    const MmlField<unsigned long long> f_keys2 = c.take<unsigned long long>(sorted ? cap : 0);
+    const MmlField<unsigned> f_vals2 = c.take<unsigned>(sorted ? cap : 0);
+    const MmlField<float4> f_sum = c.take<float4>(dry ? 0 : cap);
+    const MmlField<int> f_n = c.take<int>(dry ? 0 : cap);
+    const MmlField<float4> f_mom = c.take<float4>(!dry && W.surfels ? 3 * cap : 0);
+    rc = W.scratch.reserve(ctx, c.bytes(), s);
+    if (rc != MML_OK) return rc;
+    int map_bits = 1;
+    while ((1 << map_bits) < W.n_maps) ++map_bits;
+    const int end_bit = MML_WM_MAP_SHIFT + map_bits;  // (<= 64; no entry of the evicted list is the free marker)
+    if (sorted && (rc = W.tmp.reserve(ctx, mml_sort_pairs_bytes<unsigned long long>(cap, end_bit, s), s)) != MML_OK) return rc;
+    MmlCarve<16> t;
+    const MmlField<int> f_of = t.take<int>((size_t)W.n_maps);
+    const MmlField<mml_wm_evict_rule> f_rules = t.take<mml_wm_evict_rule>((size_t)n_rules);
+    const MmlField<int> f_cnt = t.take<int>(WME_RULES + 2 * (size_t)n_rules);
+    rc = W.tab.reserve(ctx, t.bytes(), s);
+    if (rc != MML_OK) return rc;
+    // (the pinned twin is free: the last call that used it waited for its read-back, which ran behind its copy down)
+    memcpy(f_of.in(W.tab.h), rule_of.data(), sizeof(int) * rule_of.size());
+    memcpy(static_cast<void*>(f_rules.in(W.tab.h)), rules, sizeof(mml_wm_evict_rule) * (size_t)n_rules);
+    int* h_cnt = f_cnt.in(W.tab.h);
+    memset(h_cnt, 0, f_cnt.bytes());
+    MML_HIP(hipMemcpyAsync(W.tab.d, W.tab.h, t.bytes(), hipMemcpyHostToDevice, s));
+    char* d = W.scratch.d;
+    int* d_cnt = f_cnt.in(W.tab.d);
+    const mml_wm_evict_rule* d_rules = f_rules.in(W.tab.d);
+    hipLaunchKernelGGL(k_wm_evict_mark, dim3(wm_blocks((size_t)W.slots) < 1024 ? wm_blocks((size_t)W.slots) : 1024), dim3(256), 0, s, W.keys, W.slots,
+                       W.count, f_of.in(W.tab.d), W.n_maps, d_rules, (int)cap, d_cnt, f_keys.in(d), f_vals.in(d));
+    MML_HIP(hipGetLastError());
+    // the call's first read-back and its refusal point: only scratch has been written up to here
+    MML_HIP(hipMemcpyAsync(h_cnt, d_cnt, f_cnt.bytes(), hipMemcpyDeviceToHost, s));
+    MML_HIP(hipStreamSynchronize(s));
+    const size_t n_ev = (size_t)h_cnt[WME_EVICTED], n_sv = (size_t)h_cnt[WME_KEPT];
+    if (n_evicted) *n_evicted = (long)n_ev;
+    if (info)
+        for (int r = 0; r < n_rules; ++r) {
+            info[r].n_before = h_cnt[WME_RULES + 2 * r];
+            info[r].n_evicted = h_cnt[WME_RULES + 2 * r + 1];
+            info[r].n_kept = info[r].n_before - info[r].n_evicted;
+            info[r].first_row = 0;  // the evicted rows of the rules that name a smaller map come first
+            for (int q = 0; q < n_rules; ++q)
+                if (rules[q].map < rules[r].map) info[r].first_row += h_cnt[WME_RULES + 2 * q + 1];
+        }
+    if (n_ev + n_sv > cap)
+        return mml_refuse(ctx, MML_ERR_STATE, "mml_world_map_evict: the table holds %zu voxels, more than capacity_voxels %zu; nothing was evicted", n_ev + n_sv, cap);
+    if (dry) return MML_OK;
+    if (rows && capacity < (long)n_ev)
+        return mml_refuse(ctx, MML_ERR_CAPACITY, "mml_world_map_evict: %zu voxels to evict, capacity is %ld rows; nothing was evicted", n_ev, capacity);
+    if (n_ev == 0) return MML_OK;
+    wm_touch(W);
+    float4* r_sum = f_sum.in(d);
+    int* r_n = f_n.in(d);
+    float4* r_mom = W.surfels ? f_mom.in(d) : nullptr;
+    if (rows) {  // the evicted rows in key order, in front of the survivors' in the same arrays
+        rc = mml_sort_pairs(ctx, W.tmp, f_keys.in(d), f_keys2.in(d), f_vals.in(d), f_vals2.in(d), n_ev, end_bit, s);
+        if (rc != MML_OK) return rc;
+        hipLaunchKernelGGL(k_wm_raw, dim3(wm_blocks(n_ev)), dim3(256), 0, s, f_vals2.in(d), (int)n_ev, W.sum, W.count, r_sum, r_n);
+        if (W.surfels) hipLaunchKernelGGL(k_wm_moments, dim3(wm_blocks(n_ev)), dim3(256), 0, s, f_vals2.in(d), (int)n_ev, wm_mom(W), r_mom);
+    }
+    const unsigned long long* sv_keys = f_keys.in(d) + (cap - n_sv);
+    const unsigned* sv_vals = f_vals.in(d) + (cap - n_sv);
+    const WmMom kept = W.surfels ? WmMom{r_mom + 3 * n_ev, r_mom + 3 * n_ev + n_sv, r_mom + 3 * n_ev + 2 * n_sv} : WmMom{nullptr, nullptr, nullptr};
+    if (n_sv)
+        hipLaunchKernelGGL(k_wm_take, dim3(wm_blocks(n_sv)), dim3(256), 0, s, sv_vals, (int)n_sv, W.sum, W.count, r_sum + n_ev, r_n + n_ev, wm_mom(W), kept);
+    MML_HIP(hipMemsetAsync(W.keys, 0xff, sizeof(unsigned long long) * W.slots, s));
+    hipLaunchKernelGGL(k_wm_evict_put, dim3(n_sv ? wm_blocks(n_sv) : 1), dim3(256), 0, s, sv_keys, (int)n_sv, r_sum + n_ev, r_n + n_ev, W.keys, W.slots, W.sum,
+                       W.count, W.map_n, W.n_maps, d_rules, d_cnt + WME_RULES, n_rules, wm_mom(W), kept);
+    MML_HIP(hipGetLastError());
+    if (!rows) return MML_OK;
+    // the rows up, and the call's second synchronisation
+    std::vector<unsigned long long> h_keys(n_ev);
+    MML_HIP(hipMemcpyAsync(out_sums, r_sum, sizeof(float4) * n_ev, hipMemcpyDeviceToHost, s));
+    MML_HIP(hipMemcpyAsync(out_counts, r_n, sizeof(int) * n_ev, hipMemcpyDeviceToHost, s));
+    if (W.surfels) MML_HIP(hipMemcpyAsync(out_moments, r_mom, sizeof(float4) * 3 * n_ev, hipMemcpyDeviceToHost, s));
+    MML_HIP(hipMemcpyAsync(h_keys.data(), f_keys2.in(d), sizeof(unsigned long long) * n_ev, hipMemcpyDeviceToHost, s));
+    MML_HIP(hipStreamSynchronize(s));
+    for (size_t r = 0; r < n_ev; ++r) mml_wm_unkey(h_keys[r], out_map[r], out_ijk[3 * r], out_ijk[3 * r + 1], out_ijk[3 * r + 2]);
     return MML_OK;
 }
 

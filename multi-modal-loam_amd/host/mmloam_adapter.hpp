@@ -214,6 +214,43 @@ class WorldMap {
                     mml_wm_reloc_info* info = nullptr) {
         check(ctx_.get(), mml_world_map_relocalize(ctx_.get(), first_slot, count, map_of_slot, exTlb, P, Q, &opts, info), "mml_world_map_relocalize");
     }
+    // The index box of a metric one in a map of leaf size `leaf`: lo = index(lo_xyz), hi = index(hi_xyz) + 1 (no context needed)
+    static void index_box(float leaf, const float lo_xyz[3], const float hi_xyz[3], int lo[3], int hi[3]) {
+        if (mml_wm_index_box(leaf, lo_xyz, hi_xyz, lo, hi) != MML_OK) throw std::runtime_error("mml_wm_index_box: leaf or a coordinate not finite");
+    }
+    // What one evict call took out: the rows of all named maps in ascending key order (map, then k, j, i), as import_voxels takes
+    // them map by map -- info[r].first_row is where the rows of rules[r].map begin -- and one info per rule
+    struct Evicted {
+        std::vector<int> map;   // n: the map of every row
+        Voxels rows;
+        std::vector<mml_wm_evict_info> info;
+    };
+    // At most one rule per map, all in one device chain.  rows = false drops the evicted voxels; dry = true only counts (info).
+    Evicted evict(const std::vector<mml_wm_evict_rule>& rules, bool surfels, bool rows = true, bool dry = false) {
+        Evicted e;
+        e.info.resize(rules.size());
+        long n = 0;
+        const bool sized = rows && !dry;   // the arrays are sized by a dry run first
+        check(ctx_.get(), mml_world_map_evict(ctx_.get(), (int)rules.size(), rules.data(), sized || dry ? MML_WM_EVICT_DRY : 0u, e.info.data(), 0, nullptr,
+                                              nullptr, nullptr, nullptr, nullptr, &n),
+              "mml_world_map_evict");
+        if (!sized) return e;
+        const size_t cap = n > 0 ? (size_t)n : 1;
+        e.map.resize(cap);
+        e.rows.ijk.resize(3 * cap);
+        e.rows.sums.resize(4 * cap);
+        e.rows.counts.resize(cap);
+        if (surfels) e.rows.moments.resize(12 * cap);
+        check(ctx_.get(), mml_world_map_evict(ctx_.get(), (int)rules.size(), rules.data(), 0u, e.info.data(), (long)cap, e.map.data(), e.rows.ijk.data(),
+                                              e.rows.sums.data(), e.rows.counts.data(), surfels ? e.rows.moments.data() : nullptr, &n),
+              "mml_world_map_evict");
+        e.map.resize((size_t)n);
+        e.rows.ijk.resize(3 * (size_t)n);
+        e.rows.sums.resize(4 * (size_t)n);
+        e.rows.counts.resize((size_t)n);
+        if (surfels) e.rows.moments.resize(12 * (size_t)n);
+        return e;
+    }
 
    private:
     std::vector<float> rows(int map, int width, int (*call)(mml_ctx*, int, float*, long, long*), const char* who) {

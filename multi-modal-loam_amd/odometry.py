@@ -135,6 +135,49 @@ def _world_map_download(od, n, seq, surfels=False):
     return od.ctx.world_map_surfels(seq) if surfels else od.ctx.world_map_download(seq)
 
 
+def _world_map_roll_init(od, world_map_roll, on_evict):
+    """world_map_roll: None, or (half_extent_xyz_m, every) -- after the world-map add of every `every`-th round ONE
+    Context.world_map_evict for all sequences removes, from each sequence's map, the voxels outside the box of that half extent
+    (one value or three, metres) around the sequence's current position; their rows go to on_evict(seq, rows) when given (rows as
+    Context.world_map_import takes them) and are dropped otherwise."""
+    od._roll = None
+    if world_map_roll is None:
+        if on_evict is not None:
+            raise ValueError("on_evict needs world_map_roll=(half_extent_xyz_m, every)")
+        return
+    if not od._world_map:
+        raise ValueError("world_map_roll needs world_map=(leaf, capacity_voxels)")
+    half, every = world_map_roll
+    half = np.broadcast_to(np.asarray(half, dtype=np.float64), (3,)).copy()
+    if not (np.isfinite(half).all() and (half > 0).all()) or int(every) != every or every < 1:
+        raise ValueError("world_map_roll: a finite positive half extent and every >= 1")
+    od._roll, od._on_evict, od._roll_rounds = (half, int(every)), on_evict, 0
+
+
+def _world_map_rolled(od, last_T):
+    """The end of a round: last_T[w] is sequence w's lidar pose, None while it has none."""
+    if od._roll is None:
+        return
+    od._roll_rounds += 1
+    half, every = od._roll
+    if od._roll_rounds % every:
+        return
+    from . import WM_EVICT_OUTSIDE, wm_evict_rule
+    rules = []
+    for w, T in enumerate(last_T):
+        if T is not None:
+            lo, hi = od.ctx.world_map_index_box(T[:3, 3] - half, T[:3, 3] + half)
+            rules.append(wm_evict_rule(w, WM_EVICT_OUTSIDE, lo, hi))
+    if not rules:
+        return
+    if od._on_evict is None:
+        od.ctx.world_map_evict(rules, rows=False)
+        return
+    _, rows = od.ctx.world_map_evict(rules)
+    for r in rules:
+        od._on_evict(r.map, rows[r.map])
+
+
 def _adjacent_runs(items, slot_of):
     """items sorted by slot and cut wherever the next slot is not the one after: one device call per run."""
     runs = []
@@ -150,14 +193,17 @@ class LidarOdometry:
     """One Estimator instance: `ctx` owns the scan slots and the maps.  lidar_mode 1 = Horizon, 2 = Velodyne
     (the fused cloud is processed as mode 2, unionPoseEstimation.cpp:872).  global_map=True: the context's cube store follows
     the map thread's schedule (the module docstring: the one the reference's asynchronous thread follows when it keeps up) and
-    Estimate matches against it first; the default drives the local map alone, call for call as before."""
+    Estimate matches against it first; the default drives the local map alone, call for call as before.
+    world_map_roll=(half_extent_xyz_m, every), with world_map: the world map follows the sensor (_world_map_roll_init); the
+    default None calls nothing."""
 
     def __init__(self, ctx, exTlb=None, lidar_mode=2, max_outer=5, inner_iters=10, global_map=False, map_skip_frame=2,
-                 world_map=None):
+                 world_map=None, world_map_roll=None, on_evict=None):
         if map_skip_frame < 1:
             raise ValueError("map_skip_frame must be at least 1")
         self._world_map = _world_map_create(ctx, 1, world_map)
         self.ctx = ctx
+        _world_map_roll_init(self, world_map_roll, on_evict)       # (_world_map_roll_init: a rolling world map)
         self.exTlb = np.eye(4) if exTlb is None else np.asarray(exTlb, dtype=np.float64)
         self.exRbl = self.exTlb[:3, :3].T.copy()                      # :973
         self.exPbl = -1.0 * self.exRbl @ self.exTlb[:3, 3]            # :974
@@ -197,6 +243,7 @@ class LidarOdometry:
         _finish(self, T, is_degenerate)
         if self._world_map and _published(self, fast_rotation):
             ctx.world_map_add(slot, [0], T)
+        _world_map_rolled(self, [self.last_T])
         return P, Q, grew
 
     def world_map(self, seq=0):
@@ -241,13 +288,17 @@ class BatchLidarOdometry:
     synchronisations per round whatever n is.
     global_increment: the same choice for the two cube calls of a round (global_map=True): "loop" (the default) or "segmented"
     (Context.bank_global_append / bank_global_increment with segmented=True): the same stores and match copies bit for bit,
-    3 + R host synchronisations per round whatever n is."""
+    3 + R host synchronisations per round whatever n is.
+    world_map_roll=(half_extent_xyz_m, every), with world_map: after the add of every `every`-th round ONE world_map_evict for all
+    sequences keeps each map to a box around its sequence's position (_world_map_roll_init); the default None calls nothing."""
 
     def __init__(self, ctx, n, exTlb=None, lidar_mode=2, max_outer=5, inner_iters=10, global_map=False, map_skip_frame=2,
-                 increment="loop", global_increment="loop", world_map=None):
+                 increment="loop", global_increment="loop", world_map=None, world_map_roll=None, on_evict=None):
         if n < 1:
             raise ValueError("n must be at least 1")
         self._world_map = _world_map_create(ctx, n, world_map)
+        self.ctx = ctx
+        _world_map_roll_init(self, world_map_roll, on_evict)       # (_world_map_roll_init: rolling world maps)
         if map_skip_frame < 1:
             raise ValueError("map_skip_frame must be at least 1")
         if increment not in ("loop", "segmented"):
@@ -326,6 +377,7 @@ class BatchLidarOdometry:
             fast = [False] * n if fast_rotation is None else list(fast_rotation)
             for run in _adjacent_runs([w for w in live if _published(self.seq[w], fast[w])], slot_of):
                 ctx.world_map_add(slots[run[0]], run, np.stack([T[w] for w in run]))
+        _world_map_rolled(self, [st.last_T for st in self.seq])
         return P, Q, grew
 
     def world_map(self, seq):
