@@ -32,14 +32,26 @@
 // mml_world_map_download, _download_moments and _download_surfels share one collect, sort and gather chain (wm_download); the
 // surfel gather is one lane per voxel: the covariance in double (mml_wm_covariance), eig3_sym register-only, the normal turned
 // towards the view sum (wm_surfel, world_map_dev.h: the association against the map, world_map_assoc.hip, runs it too).
-// mml_world_map_export is a fourth gather of that chain (the stored sums, counts, moments and the sorted keys as voxel indices);
-// mml_world_map_import checks its rows on the host, looks all of them up in one launch (k_wm_import_find), refuses at the add's
-// refusal point -- one read-back, only scratch written -- and then claims and stores them, one lane per voxel (k_wm_import_put).
-// mml_world_map_evict removes voxels by rule (world_map_evict.h: an index box and a minimum count per map named): k_wm_evict_mark
-// walks the table once and splits the occupied positions into an evicted and a survivor list; one read-back of the counters, the
-// refusal point; then the evicted rows are sorted and gathered (k_wm_raw, k_wm_moments), the survivors of every map taken out
-// (k_wm_take), the keys cleared and the survivors put back by claim (k_wm_evict_put) -- reset(map)'s rebuild, since a position
-// inside a probe chain cannot be freed -- and the rows copied up behind a second synchronisation when they are wanted.
+//
+// ROWS OUT OF THE TABLE AND BACK.  Outside the table a voxel is a row of a WmRows: its key, its stored sum and count and, on a
+// surfel map, its moments as three float4 per row (the export's layout; there is no other).  Rows leave the table through ONE
+// gather (k_wm_gather: row i is position vals[i], sorted or not) and enter it through ONE put (k_wm_put: claim, then plain
+// stores; a by-value WmCounts says what the launch writes into the per-map counts and the total).  On the host wm_rebuild is
+// "gather these survivors, clear the keys, put them back, write the counts" -- a position inside a probe chain cannot be freed, so
+// whatever removes voxels rebuilds -- and wm_rows_up is "these rows to the caller's arrays, the keys as voxel indices".  Behind them:
+//   mml_world_map_export           a fourth gather of the download chain (k_wm_gather over the sorted positions), then wm_rows_up;
+//                                  mml_world_map_download_moments is the same gather with the moments alone
+//   mml_world_map_import           checks its rows on the host, looks all of them up in one launch (k_wm_import_find), refuses at the
+//                                  add's refusal point -- one read-back, only scratch written -- and then puts them, the map's count
+//                                  and the total growing by one add per wave
+//   mml_world_map_reset(map >= 0)  collects the other maps' positions (k_wm_collect<true>) and rebuilds from them, the map's count
+//                                  zeroed; scratch by the survivors it has counted
+//   mml_world_map_evict            removes voxels by rule (world_map_evict.h: an index box and a minimum count per map named):
+//                                  k_wm_evict_mark walks the table once and splits the occupied positions into an evicted and a
+//                                  survivor list; one read-back of the counters, the refusal point; then the evicted rows are sorted
+//                                  and gathered when they are wanted, the table is rebuilt from the survivors, every ruled map's count
+//                                  set to n_before - n_evicted from the device's counters, and the evicted rows go up behind a second
+//                                  synchronisation (wm_rows_up); scratch by capacity_voxels
 //
 // THE SURFEL CACHE (mml_wm_cache_ready, for mml_world_map_score): one float4 per table position, (nx, ny, nz, planarity) of the
 // position's surfel, 16 bytes per position more (92 instead of 76), allocated in the map's memory group by the first call that
@@ -227,15 +239,6 @@ __global__ __launch_bounds__(256) void k_wm_centroids(const unsigned* __restrict
     out[i] = make_float4(c[0], c[1], c[2], c[3]);
     out_n[i] = a.n;
 }
-// download_moments: the raw accumulators of the sorted positions, 12 floats each
-__global__ __launch_bounds__(256) void k_wm_moments(const unsigned* __restrict__ vals, int n, WmMom M, float4* __restrict__ out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const unsigned at = vals[i];
-    out[3 * (size_t)i] = M.m0[at];
-    out[3 * (size_t)i + 1] = M.m1[at];
-    out[3 * (size_t)i + 2] = M.m2[at];
-}
 // download_surfels: one lane per sorted position, 8 floats (wm_surfel, world_map_dev.h)
 __global__ __launch_bounds__(256) void k_wm_surfels(const unsigned* __restrict__ vals, int n, WmMom M, const int* __restrict__ count,
                                                     float4* __restrict__ out) {
@@ -260,49 +263,32 @@ __global__ __launch_bounds__(256) void k_wm_surfel_cache(const unsigned long lon
     if (tab[h] != MML_WM_EMPTY) e = wm_cache_entry(wm_moments(M.m0[h], M.m1[h], M.m2[h]), count[h]);
     cache[h] = e;
 }
-// reset of one map: the survivors' accumulators beside their keys, before the table is cleared ...
-__global__ __launch_bounds__(256) void k_wm_take(const unsigned* __restrict__ vals, int n, const float4* __restrict__ sum,
-                                                 const int* __restrict__ count, float4* __restrict__ s_sum, int* __restrict__ s_n, WmMom M,
-                                                 WmMom S) {
+// ROWS OUTSIDE THE TABLE, in scratch -- the survivors of a rebuild, the rows of an export, an import or an eviction: row i is the key,
+// the stored float4 sum and the count of one voxel and, on a surfel map, its moments as three float4 at mom[3 i ..] (the layout of
+// mml_world_map_export); mom is null on a plain map.  There is no other layout outside the table.
+struct WmRows {
+    unsigned long long* keys;
+    float4* sum;
+    int* n;
+    float4* mom;
+};
+// rows out of the table: row i is position vals[i] (sorted or not), one lane per row, plain loads and stores; the keys are in R
+// already (the walk that made vals wrote them).  download_moments gathers the moments alone (R.sum null); both branches are
+// launch-uniform
+__global__ __launch_bounds__(256) void k_wm_gather(const unsigned* __restrict__ vals, int n, const float4* __restrict__ sum,
+                                                   const int* __restrict__ count, WmMom M, WmRows R) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    s_sum[i] = sum[vals[i]];
-    s_n[i] = count[vals[i]];
-    if (M.m0) {  // (a surfel map: the whole launch)
-        S.m0[i] = M.m0[vals[i]];
-        S.m1[i] = M.m1[vals[i]];
-        S.m2[i] = M.m2[vals[i]];
+    const unsigned at = vals[i];
+    if (R.sum) {
+        R.sum[i] = sum[at];
+        R.n[i] = count[at];
     }
-}
-// ... and back into the cleared table; lane 0 writes the counts of the map that went and the new total
-__global__ __launch_bounds__(256) void k_wm_reinsert(const unsigned long long* __restrict__ keys, int n, const float4* __restrict__ s_sum,
-                                                     const int* __restrict__ s_n, unsigned long long* __restrict__ tab,
-                                                     unsigned long long slots, float4* __restrict__ sum, int* __restrict__ count,
-                                                     int* __restrict__ map_n, int n_maps, int map, WmMom M, WmMom S) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0) {
-        map_n[map] = 0;
-        map_n[n_maps] = n;
+    if (R.mom) {
+        R.mom[3 * (size_t)i] = M.m0[at];
+        R.mom[3 * (size_t)i + 1] = M.m1[at];
+        R.mom[3 * (size_t)i + 2] = M.m2[at];
     }
-    if (i >= n) return;
-    const long long at = wm_claim(tab, slots, keys[i]);
-    if (at < 0) return;
-    sum[at] = s_sum[i];
-    count[at] = s_n[i];
-    if (M.m0) {
-        M.m0[at] = S.m0[i];
-        M.m1[at] = S.m1[i];
-        M.m2[at] = S.m2[i];
-    }
-}
-
-// export: the stored sums and counts of the sorted positions, as they are (the moments go through k_wm_moments)
-__global__ __launch_bounds__(256) void k_wm_raw(const unsigned* __restrict__ vals, int n, const float4* __restrict__ sum,
-                                                const int* __restrict__ count, float4* __restrict__ out, int* __restrict__ out_n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    out[i] = sum[vals[i]];
-    out_n[i] = count[vals[i]];
 }
 // import: which of the call's n distinct keys the table holds already -- counted, nothing is written to the table
 __global__ __launch_bounds__(256) void k_wm_import_find(const unsigned long long* __restrict__ keys, int n, const unsigned long long* __restrict__ tab,
@@ -312,26 +298,42 @@ __global__ __launch_bounds__(256) void k_wm_import_find(const unsigned long long
     if (i < n) held = wm_find(tab, slots, keys[i]) >= 0;
     wm_count(hits, held);
 }
-// ... and, none of them held: k_wm_insert's claim path with the accumulators as given -- one lane per voxel, the keys distinct,
-// plain stores behind the claim; the map's count and the total by one add per wave
-__global__ __launch_bounds__(256) void k_wm_import_put(const unsigned long long* __restrict__ keys, int n, const float4* __restrict__ s_sum,
-                                                       const int* __restrict__ s_n, const float4* __restrict__ s_mom, unsigned long long* __restrict__ tab,
-                                                       unsigned long long slots, float4* __restrict__ sum, int* __restrict__ count,
-                                                       int* __restrict__ map_n, int n_maps, int map, WmMom M) {
+// What a put writes into map_n beside its rows, by value; every branch on it is launch-uniform.  reset(map): zero_map and total;
+// evict: the rules with their (n_before, n_evicted) counter pairs, and total; import: add_map.
+struct WmCounts {
+    const mml_wm_evict_rule* rules;  // map_n[rules[r].map] = per_rule[2 r] - per_rule[2 r + 1] for r < n_rules
+    const int* per_rule;
+    int n_rules;
+    int zero_map;  // the map whose count becomes 0, or -1
+    int total;     // what the total becomes, or -1
+    int add_map;   // the map whose count, and with it the total, grows by the rows put (one add per wave), or -1
+};
+// rows into the table: k_wm_insert's claim path with the accumulators as given -- one lane per row, the keys distinct and none of
+// them in the table, plain stores behind the claim; the first workgroup writes the counts that are set
+__global__ __launch_bounds__(256) void k_wm_put(WmRows R, int n, unsigned long long* __restrict__ tab, unsigned long long slots,
+                                                float4* __restrict__ sum, int* __restrict__ count, WmMom M, int* __restrict__ map_n, int n_maps,
+                                                WmCounts C) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (blockIdx.x == 0) {
+        for (int r = threadIdx.x; r < C.n_rules; r += blockDim.x) map_n[C.rules[r].map] = C.per_rule[2 * r] - C.per_rule[2 * r + 1];
+        if (threadIdx.x == 0 && C.zero_map >= 0) map_n[C.zero_map] = 0;
+        if (threadIdx.x == 0 && C.total >= 0) map_n[n_maps] = C.total;
+    }
     long long at = -1;
-    if (i < n) at = wm_claim(tab, slots, keys[i]);
-    if (at >= 0) {  // (always for i < n: the host refused the call that would have filled the table)
-        sum[at] = s_sum[i];
-        count[at] = s_n[i];
-        if (M.m0) {  // (a surfel map: the whole launch)
-            M.m0[at] = s_mom[3 * (size_t)i];
-            M.m1[at] = s_mom[3 * (size_t)i + 1];
-            M.m2[at] = s_mom[3 * (size_t)i + 2];
+    if (i < n) at = wm_claim(tab, slots, R.keys[i]);
+    if (at >= 0) {  // (always for i < n: a table that held these rows, or whose host refused the call that would have filled it)
+        sum[at] = R.sum[i];
+        count[at] = R.n[i];
+        if (R.mom) {  // (a surfel map: the whole launch)
+            M.m0[at] = R.mom[3 * (size_t)i];
+            M.m1[at] = R.mom[3 * (size_t)i + 1];
+            M.m2[at] = R.mom[3 * (size_t)i + 2];
         }
     }
-    wm_count(map_n + map, at >= 0);
-    wm_count(map_n + n_maps, at >= 0);
+    if (C.add_map >= 0) {
+        wm_count(map_n + C.add_map, at >= 0);
+        wm_count(map_n + n_maps, at >= 0);
+    }
 }
 
 // evict: every table position once.  An occupied position goes, with its key, to the evicted list (the front of keys / vals, from
@@ -398,29 +400,6 @@ __global__ __launch_bounds__(256) void k_wm_evict_mark(const unsigned long long*
         }
     }
 }
-// ... and, the evicted rows gathered, the survivors taken (k_wm_take) and the keys cleared: the survivors back by claim, as
-// k_wm_reinsert; the first workgroup writes the named maps' counts (n_before - n_evicted of their rules) and the new total
-__global__ __launch_bounds__(256) void k_wm_evict_put(const unsigned long long* __restrict__ keys, int n, const float4* __restrict__ s_sum,
-                                                      const int* __restrict__ s_n, unsigned long long* __restrict__ tab,
-                                                      unsigned long long slots, float4* __restrict__ sum, int* __restrict__ count,
-                                                      int* __restrict__ map_n, int n_maps, const mml_wm_evict_rule* __restrict__ rules,
-                                                      const int* __restrict__ per_rule, int n_rules, WmMom M, WmMom S) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (blockIdx.x == 0)
-        for (int r = threadIdx.x; r < n_rules; r += blockDim.x) map_n[rules[r].map] = per_rule[2 * r] - per_rule[2 * r + 1];
-    if (i == 0) map_n[n_maps] = n;
-    if (i >= n) return;
-    const long long at = wm_claim(tab, slots, keys[i]);
-    if (at < 0) return;
-    sum[at] = s_sum[i];
-    count[at] = s_n[i];
-    if (M.m0) {
-        M.m0[at] = S.m0[i];
-        M.m1[at] = S.m1[i];
-        M.m2[at] = S.m2[i];
-    }
-}
-
 int wm_enter(mml_ctx* ctx, const char* who) {
     if (!ctx) return MML_ERR_INVALID;
     if (ctx->world.n_maps == 0) return mml_refuse(ctx, MML_ERR_STATE, "%s: the context has no world map (mml_world_map_create)", who);
@@ -434,9 +413,55 @@ int wm_clear(mml_ctx* ctx, hipStream_t s) {
     return MML_OK;
 }
 unsigned wm_blocks(size_t n) { return (unsigned)((n + 255) / 256); }
+// the grid of a grid-stride walk over the table's positions: at most 1 024 workgroups
+unsigned wm_walk_blocks(const mml_ctx::WorldMap& W) { return std::min(wm_blocks((size_t)W.slots), 1024u); }
+// where a sort of the table's keys may stop: above the map numbers in use, and `marker_bit` = 1 bit higher where the empty marker
+// is among the keys and has to sort behind every one of them (with more than 512 maps all 64 bits are then compared, and no kept
+// key equals the marker)
+int wm_end_bit(const mml_ctx::WorldMap& W, int marker_bit) {
+    int map_bits = 1;
+    while ((1 << map_bits) < W.n_maps) ++map_bits;
+    return std::min(MML_WM_MAP_SHIFT + map_bits + marker_bit, 64);
+}
 // the table is about to be written: whatever was derived from it (the surfel cache) is stale from here on
 void wm_touch(mml_ctx::WorldMap& W) { ++W.version; }
 WmMom wm_mom(const mml_ctx::WorldMap& W) { return WmMom{W.mom[0], W.mom[1], W.mom[2]}; }
+// a moments array is given on a surfel map and on no other
+int wm_moments_arg(mml_ctx* ctx, const char* who, const char* name, const void* moments) {
+    const bool surfels = ctx->world.surfels;
+    if ((moments != nullptr) == surfels) return MML_OK;
+    return mml_refuse(ctx, MML_ERR_INVALID, "%s: %s must be %s", who, name, surfels ? "given: the map holds surfels" : "NULL: the map is a plain one");
+}
+
+// THE REBUILD.  An open-addressing table has no way to free a position inside a probe chain (every key value is in use, there is
+// no tombstone), so a call that removes voxels takes the `n` survivors out -- the positions vals[0..n), whose keys are in R.keys
+// already, gathered into R --, clears the keys and puts the rows back by claim; the put writes the total and what C says of the
+// maps' counts.  Enqueue only.
+int wm_rebuild(mml_ctx* ctx, const unsigned* vals, WmRows R, size_t n, WmCounts C, hipStream_t s) {
+    mml_ctx::WorldMap& W = ctx->world;
+    if (n) hipLaunchKernelGGL(k_wm_gather, dim3(wm_blocks(n)), dim3(256), 0, s, vals, (int)n, W.sum, W.count, wm_mom(W), R);
+    MML_HIP(hipMemsetAsync(W.keys, 0xff, sizeof(unsigned long long) * W.slots, s));
+    C.total = (int)n;
+    hipLaunchKernelGGL(k_wm_put, dim3(n ? wm_blocks(n) : 1), dim3(256), 0, s, R, (int)n, W.keys, W.slots, W.sum, W.count, wm_mom(W), W.map_n, W.n_maps, C);
+    MML_HIP(hipGetLastError());
+    return MML_OK;
+}
+// the `n` rows R up to the caller's arrays (moments on a surfel map), one synchronisation, the keys unpacked on the host into
+// voxel indices and, where wanted, map numbers
+int wm_rows_up(mml_ctx* ctx, WmRows R, size_t n, int* out_map, int* ijk, float* sums, int* counts, float* moments, hipStream_t s) {
+    std::vector<unsigned long long> h_keys(n);
+    MML_HIP(hipMemcpyAsync(sums, R.sum, sizeof(float4) * n, hipMemcpyDeviceToHost, s));
+    MML_HIP(hipMemcpyAsync(counts, R.n, sizeof(int) * n, hipMemcpyDeviceToHost, s));
+    if (R.mom) MML_HIP(hipMemcpyAsync(moments, R.mom, sizeof(float4) * 3 * n, hipMemcpyDeviceToHost, s));
+    MML_HIP(hipMemcpyAsync(h_keys.data(), R.keys, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, s));
+    MML_HIP(hipStreamSynchronize(s));
+    for (size_t r = 0; r < n; ++r) {
+        int map;
+        mml_wm_unkey(h_keys[r], map, ijk[3 * r], ijk[3 * r + 1], ijk[3 * r + 2]);
+        if (out_map) out_map[r] = map;
+    }
+    return MML_OK;
+}
 
 // mml_world_map_create and _create_opts
 int wm_create(mml_ctx* ctx, int n_maps, float leaf, long capacity_voxels, unsigned flags) {
@@ -505,8 +530,7 @@ int mml_world_map_reset(mml_ctx* ctx, int map) {
     hipStream_t s = MML_STREAM(ctx);
     wm_touch(W);
     if (map < 0) return wm_clear(ctx, s);
-    // One map of several: an open-addressing table has no way to free a position inside a probe chain (every key value is in use,
-    // there is no tombstone), so the other maps' voxels are taken out, the table is cleared and they are put back.
+    // One map of several: the other maps' voxels are the survivors of a rebuild (wm_rebuild), sized by their number.
     int* h = reinterpret_cast<int*>(mml_stage_alloc(ctx, 1));
     MML_HIP(hipMemcpyAsync(h, W.map_n + map, sizeof(int), hipMemcpyDeviceToHost, s));
     MML_HIP(hipMemcpyAsync(h + 1, W.map_n + W.n_maps, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -519,24 +543,18 @@ int mml_world_map_reset(mml_ctx* ctx, int map) {
     const MmlField<float4> f_sum = c.take<float4>(m);
     const MmlField<int> f_n = c.take<int>(m);
     const MmlField<int> f_cur = c.take<int>(1);
-    const MmlField<float4> f_mom = c.take<float4>(W.surfels ? 3 * m : 0);  // a surfel map: the survivors' moments, three arrays of m
+    const MmlField<float4> f_mom = c.take<float4>(W.surfels ? 3 * m : 0);
     rc = W.scratch.reserve(ctx, c.bytes(), s);
     if (rc != MML_OK) return rc;
     char* d = W.scratch.d;
-    const WmMom kept = W.surfels ? WmMom{f_mom.in(d), f_mom.in(d) + m, f_mom.in(d) + 2 * m} : WmMom{nullptr, nullptr, nullptr};
     MML_HIP(hipMemsetAsync(f_cur.in(d), 0, sizeof(int), s));
     if (m) {
         MML_HIP(hipMemsetAsync(f_vals.in(d), 0, f_vals.bytes(), s));  // (every entry a table position, whatever the walk finds)
-        hipLaunchKernelGGL(k_wm_collect<true>, dim3(wm_blocks((size_t)W.slots) < 1024 ? wm_blocks((size_t)W.slots) : 1024), dim3(256), 0, s, W.keys,
-                           W.slots, map, (int)m, f_cur.in(d), f_keys.in(d), f_vals.in(d));
-        hipLaunchKernelGGL(k_wm_take, dim3(wm_blocks(m)), dim3(256), 0, s, f_vals.in(d), (int)m, W.sum, W.count, f_sum.in(d), f_n.in(d),
-                           wm_mom(W), kept);
+        hipLaunchKernelGGL(k_wm_collect<true>, dim3(wm_walk_blocks(W)), dim3(256), 0, s, W.keys, W.slots, map, (int)m, f_cur.in(d), f_keys.in(d),
+                           f_vals.in(d));
     }
-    MML_HIP(hipMemsetAsync(W.keys, 0xff, sizeof(unsigned long long) * W.slots, s));
-    hipLaunchKernelGGL(k_wm_reinsert, dim3(m ? wm_blocks(m) : 1), dim3(256), 0, s, f_keys.in(d), (int)m, f_sum.in(d), f_n.in(d), W.keys, W.slots,
-                       W.sum, W.count, W.map_n, W.n_maps, map, wm_mom(W), kept);
-    MML_HIP(hipGetLastError());
-    return MML_OK;
+    return wm_rebuild(ctx, f_vals.in(d), WmRows{f_keys.in(d), f_sum.in(d), f_n.in(d), W.surfels ? f_mom.in(d) : nullptr}, m,
+                      WmCounts{nullptr, nullptr, 0, map, -1, -1}, s);
 }
 
 int mml_world_map_add(mml_ctx* ctx, int first_slot, int count, const int* map_of_slot, const double* T_wl, unsigned label_mask,
@@ -574,11 +592,7 @@ int mml_world_map_add(mml_ctx* ctx, int first_slot, int count, const int* map_of
     const MmlField<int> f_flag = c.take<int>(n), f_pos = c.take<int>(n), f_hit = c.take<int>(n);
     rc = W.scratch.reserve(ctx, c.bytes(), s);
     if (rc != MML_OK) return rc;
-    int map_bits = 1;
-    while ((1 << map_bits) < W.n_maps) ++map_bits;
-    // one bit above the map numbers in use, so that the empty marker sorts behind every key (with more than 512 maps all 64 bits
-    // are compared, and no kept key equals the marker)
-    const int end_bit = MML_WM_MAP_SHIFT + map_bits + 1 < 64 ? MML_WM_MAP_SHIFT + map_bits + 1 : 64;
+    const int end_bit = wm_end_bit(W, 1);  // (the keys were preset to the empty marker)
     rc = W.tmp.reserve(ctx, mml_sort_pairs_bytes<unsigned long long>(n, end_bit, s), s);
     if (rc != MML_OK) return rc;
     MmlCarve<16> t;
@@ -652,8 +666,9 @@ int mml_world_map_add(mml_ctx* ctx, int first_slot, int count, const int* map_of
 
 namespace {
 // The three downloads and the export: the occupied positions of the map collected, sorted by key and gathered -- the chain is this
-// function's and nobody else's; `what` chooses the gather kernel and the floats per voxel.  The export (WM_RAW) gathers the stored
-// sums into `out`, the counts, the sorted keys as voxel indices into `ijk` and, on a surfel map, the moments into `moments`.
+// function's and nobody else's; `what` chooses the gather kernel and the floats per voxel.  The export (WM_RAW) hands up whole rows
+// (wm_rows_up): the stored sums into `out`, the counts, the sorted keys as voxel indices into `ijk` and, on a surfel map, the
+// moments into `moments`.
 enum WmWhat { WM_CENTROIDS = 4, WM_MOMENTS = 12, WM_SURFELS = 8, WM_RAW = 16 };  // (the value: floats per voxel; WM_RAW: 4, or 16 with moments)
 int wm_download(mml_ctx* ctx, const char* who, WmWhat what, int map, float* out, int* out_count, long capacity, long* n_voxels,
                 int* ijk = nullptr, float* moments = nullptr) {
@@ -666,8 +681,7 @@ int wm_download(mml_ctx* ctx, const char* who, WmWhat what, int map, float* out,
     if (map < 0 || map >= W.n_maps) return mml_refuse(ctx, MML_ERR_INVALID, "%s: map %d outside [0, %d)", who, map, W.n_maps);
     if (what == WM_RAW && (out || out_count || ijk || moments)) {  // (all NULL: the sizing call)
         if (!out || !out_count || !ijk) return mml_refuse(ctx, MML_ERR_INVALID, "%s: ijk, sums and counts are given together or not at all", who);
-        if ((moments != nullptr) != W.surfels)
-            return mml_refuse(ctx, MML_ERR_INVALID, "%s: moments must be %s", who, W.surfels ? "given: the map holds surfels" : "NULL: the map is a plain one");
+        if ((rc = wm_moments_arg(ctx, who, "moments", moments)) != MML_OK) return rc;
     }
     rc = mml_world_map_size(ctx, map, n_voxels);
     if (rc != MML_OK || !out || *n_voxels == 0) return rc;
@@ -677,7 +691,8 @@ int wm_download(mml_ctx* ctx, const char* who, WmWhat what, int map, float* out,
     MmlCarve<16> c;
     const MmlField<unsigned long long> f_keys = c.take<unsigned long long>(2 * n);
     const MmlField<unsigned> f_vals = c.take<unsigned>(2 * n);
-    const MmlField<float4> f_out = c.take<float4>((what == WM_RAW ? (W.surfels ? 4 : 1) : (size_t)what / 4) * n);
+    const MmlField<float4> f_out = c.take<float4>((what == WM_RAW ? 1 : (size_t)what / 4) * n);
+    const MmlField<float4> f_mom = c.take<float4>(what == WM_RAW && W.surfels ? 3 * n : 0);
     const MmlField<int> f_n = c.take<int>(n);
     const MmlField<int> f_cur = c.take<int>(1);
     rc = W.scratch.reserve(ctx, c.bytes(), s);
@@ -689,33 +704,19 @@ int wm_download(mml_ctx* ctx, const char* who, WmWhat what, int map, float* out,
     unsigned* vals = f_vals.in(d);
     MML_HIP(hipMemsetAsync(f_cur.in(d), 0, sizeof(int), s));
     MML_HIP(hipMemsetAsync(vals, 0, sizeof(unsigned) * n, s));  // (every entry a table position, whatever the walk finds)
-    hipLaunchKernelGGL(k_wm_collect<false>, dim3(wm_blocks((size_t)W.slots) < 1024 ? wm_blocks((size_t)W.slots) : 1024), dim3(256), 0, s, W.keys, W.slots,
-                       map, (int)n, f_cur.in(d), keys, vals);
+    hipLaunchKernelGGL(k_wm_collect<false>, dim3(wm_walk_blocks(W)), dim3(256), 0, s, W.keys, W.slots, map, (int)n, f_cur.in(d), keys, vals);
     rc = mml_sort_pairs(ctx, W.tmp, keys, keys + n, vals, vals + n, n, MML_WM_MAP_SHIFT, s);  // (the map number is the same in all)
     if (rc != MML_OK) return rc;
+    const WmRows R = what == WM_RAW ? WmRows{keys + n, f_out.in(d), f_n.in(d), W.surfels ? f_mom.in(d) : nullptr}
+                                    : WmRows{nullptr, nullptr, nullptr, f_out.in(d)};
     if (what == WM_CENTROIDS)
         hipLaunchKernelGGL(k_wm_centroids, dim3(wm_blocks(n)), dim3(256), 0, s, vals + n, (int)n, W.sum, W.count, f_out.in(d), f_n.in(d));
-    else if (what == WM_MOMENTS)
-        hipLaunchKernelGGL(k_wm_moments, dim3(wm_blocks(n)), dim3(256), 0, s, vals + n, (int)n, wm_mom(W), f_out.in(d));
-    else if (what == WM_RAW) {
-        hipLaunchKernelGGL(k_wm_raw, dim3(wm_blocks(n)), dim3(256), 0, s, vals + n, (int)n, W.sum, W.count, f_out.in(d), f_n.in(d));
-        if (W.surfels) hipLaunchKernelGGL(k_wm_moments, dim3(wm_blocks(n)), dim3(256), 0, s, vals + n, (int)n, wm_mom(W), f_out.in(d) + n);
-    } else
+    else if (what == WM_SURFELS)
         hipLaunchKernelGGL(k_wm_surfels, dim3(wm_blocks(n)), dim3(256), 0, s, vals + n, (int)n, wm_mom(W), W.count, f_out.in(d));
+    else  // the stored accumulators as they are: the moments alone, or the export's rows
+        hipLaunchKernelGGL(k_wm_gather, dim3(wm_blocks(n)), dim3(256), 0, s, vals + n, (int)n, W.sum, W.count, wm_mom(W), R);
     MML_HIP(hipGetLastError());
-    if (what == WM_RAW) {
-        std::vector<unsigned long long> h_keys(n);
-        MML_HIP(hipMemcpyAsync(out, f_out.in(d), sizeof(float4) * n, hipMemcpyDeviceToHost, s));
-        if (W.surfels) MML_HIP(hipMemcpyAsync(moments, f_out.in(d) + n, sizeof(float4) * 3 * n, hipMemcpyDeviceToHost, s));
-        MML_HIP(hipMemcpyAsync(out_count, f_n.in(d), sizeof(int) * n, hipMemcpyDeviceToHost, s));
-        MML_HIP(hipMemcpyAsync(h_keys.data(), keys + n, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, s));
-        MML_HIP(hipStreamSynchronize(s));
-        for (size_t r = 0; r < n; ++r) {
-            int m;
-            mml_wm_unkey(h_keys[r], m, ijk[3 * r], ijk[3 * r + 1], ijk[3 * r + 2]);
-        }
-        return MML_OK;
-    }
+    if (what == WM_RAW) return wm_rows_up(ctx, R, n, nullptr, ijk, out, out_count, moments, s);
     MML_HIP(hipMemcpyAsync(out, f_out.in(d), f_out.bytes(), hipMemcpyDeviceToHost, s));
     if (out_count) MML_HIP(hipMemcpyAsync(out_count, f_n.in(d), sizeof(int) * n, hipMemcpyDeviceToHost, s));
     MML_HIP(hipStreamSynchronize(s));
@@ -744,8 +745,7 @@ int mml_world_map_import(mml_ctx* ctx, int map, long n, const int* ijk, const fl
     if (map < 0 || map >= W.n_maps) return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_import: map %d outside [0, %d)", map, W.n_maps);
     MML_REQUIRE(n >= 0 && n <= (1L << 29), MML_ERR_INVALID, "mml_world_map_import: n outside 0..2^29");
     MML_REQUIRE(n == 0 || (ijk && sums && counts), MML_ERR_INVALID, "mml_world_map_import: null ijk / sums / counts");
-    if (n > 0 && (moments != nullptr) != W.surfels)
-        return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_import: moments must be %s", W.surfels ? "given: the map holds surfels" : "NULL: the map is a plain one");
+    if (n > 0 && (rc = wm_moments_arg(ctx, "mml_world_map_import", "moments", moments)) != MML_OK) return rc;
     if (n == 0) return MML_OK;
     std::vector<unsigned long long> h_keys((size_t)n);
     for (long r = 0; r < n; ++r) {
@@ -796,8 +796,8 @@ int mml_world_map_import(mml_ctx* ctx, int map, long n, const int* ijk, const fl
         return mml_refuse(ctx, MML_ERR_CAPACITY, "mml_world_map_import: %d voxels held + %ld imported exceed capacity_voxels %ld; nothing was imported",
                           h_cnt[1], n, W.capacity);
     wm_touch(W);
-    hipLaunchKernelGGL(k_wm_import_put, dim3(wm_blocks(m)), dim3(256), 0, s, f_keys.in(d), (int)m, f_sum.in(d), f_n.in(d), f_mom.in(d), W.keys, W.slots, W.sum,
-                       W.count, W.map_n, W.n_maps, map, wm_mom(W));
+    hipLaunchKernelGGL(k_wm_put, dim3(wm_blocks(m)), dim3(256), 0, s, WmRows{f_keys.in(d), f_sum.in(d), f_n.in(d), W.surfels ? f_mom.in(d) : nullptr}, (int)m,
+                       W.keys, W.slots, W.sum, W.count, wm_mom(W), W.map_n, W.n_maps, WmCounts{nullptr, nullptr, 0, -1, -1, map});
     MML_HIP(hipGetLastError());
     MML_HIP(hipStreamSynchronize(s));  // (the caller's arrays and the key vector were the copies' sources)
     return MML_OK;
@@ -836,8 +836,7 @@ int mml_world_map_evict(mml_ctx* ctx, int n_rules, const mml_wm_evict_rule* rule
     if (rows) {
         if (!out_map || !out_sums || !out_counts)
             return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_evict: out_map, out_ijk, out_sums and out_counts are given together or not at all");
-        if ((out_moments != nullptr) != W.surfels)
-            return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_evict: out_moments must be %s", W.surfels ? "given: the map holds surfels" : "NULL: the map is a plain one");
+        if ((rc = wm_moments_arg(ctx, "mml_world_map_evict", "out_moments", out_moments)) != MML_OK) return rc;
     } else {
         if (out_map || out_sums || out_counts || out_moments)
             return mml_refuse(ctx, MML_ERR_INVALID, "mml_world_map_evict: out_map, out_ijk, out_sums and out_counts are given together or not at all");
@@ -857,9 +856,7 @@ int mml_world_map_evict(mml_ctx* ctx, int n_rules, const mml_wm_evict_rule* rule
     const MmlField<float4> f_mom = c.take<float4>(!dry && W.surfels ? 3 * cap : 0);
     rc = W.scratch.reserve(ctx, c.bytes(), s);
     if (rc != MML_OK) return rc;
-    int map_bits = 1;
-    while ((1 << map_bits) < W.n_maps) ++map_bits;
-    const int end_bit = MML_WM_MAP_SHIFT + map_bits;  // (<= 64; no entry of the evicted list is the free marker)
+    const int end_bit = wm_end_bit(W, 0);  // (no entry of the evicted list is the free marker)
     if (sorted && (rc = W.tmp.reserve(ctx, mml_sort_pairs_bytes<unsigned long long>(cap, end_bit, s), s)) != MML_OK) return rc;
     MmlCarve<16> t;
     const MmlField<int> f_of = t.take<int>((size_t)W.n_maps);
@@ -876,8 +873,8 @@ int mml_world_map_evict(mml_ctx* ctx, int n_rules, const mml_wm_evict_rule* rule
     char* d = W.scratch.d;
     int* d_cnt = f_cnt.in(W.tab.d);
     const mml_wm_evict_rule* d_rules = f_rules.in(W.tab.d);
-    hipLaunchKernelGGL(k_wm_evict_mark, dim3(wm_blocks((size_t)W.slots) < 1024 ? wm_blocks((size_t)W.slots) : 1024), dim3(256), 0, s, W.keys, W.slots,
-                       W.count, f_of.in(W.tab.d), W.n_maps, d_rules, (int)cap, d_cnt, f_keys.in(d), f_vals.in(d));
+    hipLaunchKernelGGL(k_wm_evict_mark, dim3(wm_walk_blocks(W)), dim3(256), 0, s, W.keys, W.slots, W.count, f_of.in(W.tab.d), W.n_maps, d_rules, (int)cap,
+                       d_cnt, f_keys.in(d), f_vals.in(d));
     MML_HIP(hipGetLastError());
     // the call's first read-back and its refusal point: only scratch has been written up to here
     MML_HIP(hipMemcpyAsync(h_cnt, d_cnt, f_cnt.bytes(), hipMemcpyDeviceToHost, s));
@@ -900,34 +897,20 @@ int mml_world_map_evict(mml_ctx* ctx, int n_rules, const mml_wm_evict_rule* rule
         return mml_refuse(ctx, MML_ERR_CAPACITY, "mml_world_map_evict: %zu voxels to evict, capacity is %ld rows; nothing was evicted", n_ev, capacity);
     if (n_ev == 0) return MML_OK;
     wm_touch(W);
-    float4* r_sum = f_sum.in(d);
-    int* r_n = f_n.in(d);
-    float4* r_mom = W.surfels ? f_mom.in(d) : nullptr;
-    if (rows) {  // the evicted rows in key order, in front of the survivors' in the same arrays
+    // the rows taken out, in one set of arrays: the evicted ones in front (in key order, when they are handed back), the survivors
+    // behind them
+    float4* mom = W.surfels ? f_mom.in(d) : nullptr;
+    const WmRows ev = {f_keys2.in(d), f_sum.in(d), f_n.in(d), mom};
+    const WmRows sv = {f_keys.in(d) + (cap - n_sv), ev.sum + n_ev, ev.n + n_ev, mom ? mom + 3 * n_ev : nullptr};
+    if (rows) {
         rc = mml_sort_pairs(ctx, W.tmp, f_keys.in(d), f_keys2.in(d), f_vals.in(d), f_vals2.in(d), n_ev, end_bit, s);
         if (rc != MML_OK) return rc;
-        hipLaunchKernelGGL(k_wm_raw, dim3(wm_blocks(n_ev)), dim3(256), 0, s, f_vals2.in(d), (int)n_ev, W.sum, W.count, r_sum, r_n);
-        if (W.surfels) hipLaunchKernelGGL(k_wm_moments, dim3(wm_blocks(n_ev)), dim3(256), 0, s, f_vals2.in(d), (int)n_ev, wm_mom(W), r_mom);
+        hipLaunchKernelGGL(k_wm_gather, dim3(wm_blocks(n_ev)), dim3(256), 0, s, f_vals2.in(d), (int)n_ev, W.sum, W.count, wm_mom(W), ev);
     }
-    const unsigned long long* sv_keys = f_keys.in(d) + (cap - n_sv);
-    const unsigned* sv_vals = f_vals.in(d) + (cap - n_sv);
-    const WmMom kept = W.surfels ? WmMom{r_mom + 3 * n_ev, r_mom + 3 * n_ev + n_sv, r_mom + 3 * n_ev + 2 * n_sv} : WmMom{nullptr, nullptr, nullptr};
-    if (n_sv)
-        hipLaunchKernelGGL(k_wm_take, dim3(wm_blocks(n_sv)), dim3(256), 0, s, sv_vals, (int)n_sv, W.sum, W.count, r_sum + n_ev, r_n + n_ev, wm_mom(W), kept);
-    MML_HIP(hipMemsetAsync(W.keys, 0xff, sizeof(unsigned long long) * W.slots, s));
-    hipLaunchKernelGGL(k_wm_evict_put, dim3(n_sv ? wm_blocks(n_sv) : 1), dim3(256), 0, s, sv_keys, (int)n_sv, r_sum + n_ev, r_n + n_ev, W.keys, W.slots, W.sum,
-                       W.count, W.map_n, W.n_maps, d_rules, d_cnt + WME_RULES, n_rules, wm_mom(W), kept);
-    MML_HIP(hipGetLastError());
-    if (!rows) return MML_OK;
-    // the rows up, and the call's second synchronisation
-    std::vector<unsigned long long> h_keys(n_ev);
-    MML_HIP(hipMemcpyAsync(out_sums, r_sum, sizeof(float4) * n_ev, hipMemcpyDeviceToHost, s));
-    MML_HIP(hipMemcpyAsync(out_counts, r_n, sizeof(int) * n_ev, hipMemcpyDeviceToHost, s));
-    if (W.surfels) MML_HIP(hipMemcpyAsync(out_moments, r_mom, sizeof(float4) * 3 * n_ev, hipMemcpyDeviceToHost, s));
-    MML_HIP(hipMemcpyAsync(h_keys.data(), f_keys2.in(d), sizeof(unsigned long long) * n_ev, hipMemcpyDeviceToHost, s));
-    MML_HIP(hipStreamSynchronize(s));
-    for (size_t r = 0; r < n_ev; ++r) mml_wm_unkey(h_keys[r], out_map[r], out_ijk[3 * r], out_ijk[3 * r + 1], out_ijk[3 * r + 2]);
-    return MML_OK;
+    // every ruled map's count becomes n_before - n_evicted of its rule, from the device's counters
+    rc = wm_rebuild(ctx, f_vals.in(d) + (cap - n_sv), sv, n_sv, WmCounts{d_rules, d_cnt + WME_RULES, n_rules, -1, -1, -1}, s);
+    if (rc != MML_OK || !rows) return rc;
+    return wm_rows_up(ctx, ev, n_ev, out_map, out_ijk, out_sums, out_counts, out_moments, s);  // the call's second synchronisation
 }
 
 // The surfel cache of a surfel map, valid for the table as it is: allocated on first use, rebuilt when a call has written the table

@@ -72,7 +72,7 @@ __device__ __forceinline__ void wm_probe27(const unsigned long long* keys, unsig
     }
 }
 
-// the three moment arrays of a surfel map (or of a reset's scratch copy); null in a plain map
+// the three moment arrays of a surfel map; null in a plain map
 struct WmMom {
     float4 *m0, *m1, *m2;
 };

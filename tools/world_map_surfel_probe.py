@@ -181,8 +181,8 @@ def main():
             "%.3f" % r["max_angle_deg"] if r.get("same_voxels") else "-"))
     if a.isa and os.path.exists(a.isa):
         lines += ["", "ISA of the world map's kernels (world_map.hip) against the parent commit's, tools/isa_compare.py <old .s> <new .s> k_wm:",
-                  "k_wm_insert in the first column is k_wm_insert<false>, the plain map's insert; k_wm_take and k_wm_reinsert (reset of one map",
-                  "among several) gained the moment arrays as arguments and one uniform branch; \"(banked form)\" is the tool's word for the",
+                  "k_wm_insert in the first column is k_wm_insert<false>, the plain map's insert; k_wm_gather and k_wm_put (the rows of a rebuild,",
+                  "reset of one map among several) carry the moments behind one launch-uniform branch; \"(banked form)\" is the tool's word for the",
                   "<true> instantiations, which it lists and does not compare (k_wm_insert<true> is the surfel map's insert)"] + open(a.isa).read().rstrip().splitlines()
     text = "\n".join(lines)
     print(text)
